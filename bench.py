@@ -13,7 +13,10 @@ HBM, through the C ABI (slfp_conv2d_fwd), with weights prepared once (quantize-o
 Layer geometry and the per-layer Ka/Kw come from the reference's own tables
 (cnns_slfp_quantization_amd/data/layer_specs.json).  Random-init weights, synthetic data.
 
-Prints ONE JSON line on rank 0 (see README/DESIGN.md for the field meanings).
+Prints ONE JSON line on rank 0 (see README/DESIGN.md for the field meanings).  A plain run sets up, warms up, times
+exactly K steps and reports them (`value`, `ms_per_step`); `--full` adds every secondary measurement (per-kernel and
+roofline figures, the single-stream and float32-equivalent timings, the code path, BASELINE configs 3-5, the codec, the
+whole net, the CPU baseline).  `--dump-outputs DIR` writes the layer outputs of the last timed step to DIR/*.npy.
 """
 import argparse
 import ctypes
@@ -35,6 +38,7 @@ from cnns_slfp_quantization_amd import _lib, layer_specs, sharding  # noqa: E402
 HBM_PEAK_GBS = 8000.0       # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 HBM_COPY_GBS = 6290.0       # measured float4-copy ceiling from the same guide
 MFMA_F16_PEAK_TFLOPS = 2500.0  # dense fp16/bf16 MFMA peak (same guide; never the 2:1-sparsity figure)
+DUMP_BUDGET_BYTES = 48 << 20   # --dump-outputs: all layers' outputs (or samples of them) together
 
 
 class Layer:
@@ -375,14 +379,39 @@ def group_stream(dev, g):
     return _GROUP_STREAMS[key]
 
 
+def sample_outputs(layer_ys, seed=0, budget_bytes=DUMP_BUDGET_BYTES):
+    """What a caller of the timed path receives from one step: every layer's float32 output over the whole batch.
+    layer_ys[i] lists layer i's output tensors in batch order (one per image group).  A layer's output is returned whole
+    (NHWC) when it fits its share of `budget_bytes`, else as a fixed sample of its elements: the same flat positions of
+    the whole-batch NHWC tensor on every run, chosen by a generator seeded with (seed, layer index), in ascending order."""
+    cap = max(1, budget_bytes // 4 // len(layer_ys))
+    out = {}
+    for i, ys in enumerate(layer_ys):
+        per = ys[0].numel()
+        n = per * len(ys)
+        if n <= cap:
+            y = torch.cat([t.reshape(-1) for t in ys]).view(len(ys) * ys[0].shape[0], *ys[0].shape[1:])
+        else:
+            idx = torch.from_numpy(np.sort(np.random.default_rng([seed, i]).choice(n, size=cap, replace=False))).to(ys[0].device)
+            y = torch.empty(cap, dtype=ys[0].dtype, device=ys[0].device)
+            for g, t in enumerate(ys):
+                sel = (idx >= g * per) & (idx < (g + 1) * per)
+                y[sel] = t.reshape(-1)[idx[sel] - g * per]
+        out[f"layer{i:02d}_y"] = y.float().cpu().numpy()
+    return out
+
+
 def run_config(L, net, batch, qbits, passes, steps, warmup, dev, rank, world, post=False, per_layer=False, exact_too=False,
-               image_groups=1):
+               image_groups=1, full=True, dump=None):
     """One workload: every Conv2d_Q layer of `net` at `batch` images on this rank.  Returns (result dict, per-rank seconds).
     image_groups = G > 1: the timed steps run the batch as G groups of batch / G images, each group on its own HIP stream
     through all the layers (images are independent units of this path -- SURVEY 8e -- so the groups never synchronise: while
     one group's kernel drains its last workgroups, another group's kernel fills the CUs; the per-launch gap of one stream is
     the other's work).  Same weights (one prepared blob per layer), same images per step; the per-kernel figures of the
-    result are measured on whole-batch launches in a separate single-stream pass, which is also reported."""
+    result are measured on whole-batch launches in a separate single-stream pass, which is also reported.
+    full=False times the headline steps and nothing else: no single-stream timing next to the image groups, no per-kernel
+    pass (no `roofline` / `kernels`; per_layer still runs that pass), no float32-equivalent or north-star-scope timing.
+    dump: a dict that receives sample_outputs() of the timed path right after its timed steps."""
     specs = layer_specs.conv_layers(net)
     gen = torch.Generator(device=dev).manual_seed(1234 + rank)
     layers = [Layer(L, s, batch, dev, passes, gen, qbits, post) for s in specs]
@@ -406,14 +435,19 @@ def run_config(L, net, batch, qbits, passes, steps, warmup, dev, rank, world, po
         for l in layers:
             l.run(L, stream)
 
-    for _ in range(warmup):
-        step()
-    dt_rank = timed_steps(step, steps, world, dev)
-    rank_dts = sharding.rank_times(dt_rank, device=dev)   # every rank's seconds; the job's time is the slowest rank's
-    dt = max(rank_dts)
+    grouped = image_groups > 1 and batch % image_groups == 0
     single = None
-    if image_groups > 1 and batch % image_groups == 0:
-        single = {"value": round(batch * world * steps / dt, 1), "ms_per_step": round(dt / steps * 1e3, 4)}
+    if full or not grouped:
+        for _ in range(warmup):
+            step()
+        dt_rank = timed_steps(step, steps, world, dev)
+        rank_dts = sharding.rank_times(dt_rank, device=dev)   # every rank's seconds; the job's time is the slowest rank's
+        dt = max(rank_dts)
+        if grouped:
+            single = {"value": round(batch * world * steps / dt, 1), "ms_per_step": round(dt / steps * 1e3, 4)}
+        elif dump is not None:
+            dump.update(sample_outputs([[l.y] for l in layers]))
+    if grouped:
         groups = []
         for g in range(image_groups):
             st = group_stream(dev, g)
@@ -454,7 +488,25 @@ def run_config(L, net, batch, qbits, passes, steps, warmup, dev, rank, world, po
         dt_rank = timed_steps(gstep, steps, world, dev)
         rank_dts = sharding.rank_times(dt_rank, device=dev)
         dt = max(rank_dts)
+        if dump is not None:
+            dump.update(sample_outputs([[gl[i].y for _, gl in groups] for i in range(len(specs))]))
         del groups
+
+    imgs = batch * world * steps
+    value = imgs / dt
+    bytes_img = layer_specs.algorithmic_bytes_per_image(net, batch)
+    whole_gbs = bytes_img * value / 1e9 / world  # per GPU
+    res = {"value": round(value, 1), "ms_per_step": round(dt / steps * 1e3, 4),
+           "hbm_roofline_frac_whole_path": round(whole_gbs / HBM_PEAK_GBS, 4),
+           "algorithmic_bytes_per_image": int(bytes_img),
+           "pointwise_mfma": next((l.kernel for l in layers if l.kernel.startswith("pw_")), None),
+           "n_layers": len(layers)}
+    if grouped:
+        res["image_groups"] = image_groups
+    if not (full or per_layer):
+        del layers
+        torch.cuda.empty_cache()
+        return res, rank_dts
 
     # ---- per-kernel timing with HIP events on the launch stream (separate pass, same step order: cold caches)
     ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in layers] for _ in range(steps)]
@@ -477,7 +529,7 @@ def run_config(L, net, batch, qbits, passes, steps, warmup, dev, rank, world, po
     dom_gbs = dom["bytes"] / (dom["ms"] * 1e-3) / 1e9
 
     exact_value = None
-    if exact_too and passes == 0 and qbits == 8:   # the float32-equivalent mode (fp16 hi/lo split, 3 MFMA passes), same buffers
+    if exact_too and full and passes == 0 and qbits == 8:   # the float32-equivalent mode (fp16 hi/lo split, 3 MFMA passes), same buffers
         for l in layers:
             l.set_passes(L, stream, _lib.MFMA_F16X3)
         step()
@@ -489,7 +541,7 @@ def run_config(L, net, batch, qbits, passes, steps, warmup, dev, rank, world, po
     # the north-star scope by itself (BASELINE.json: "3x3 depthwise + 1x1 pointwise"): the same steps WITHOUT the image stem, by
     # the wall clock -- the per-family HIP-event sums above carry ~2 us of event overhead per launch that a step does not have
     scope = None
-    if exact_too and world == 1:
+    if exact_too and full and world == 1:
         sub = [l for l in layers if l.spec.c_in > 4]
         if len(sub) != len(layers) and sub:
             def sub_step():
@@ -504,14 +556,7 @@ def run_config(L, net, batch, qbits, passes, steps, warmup, dev, rank, world, po
                      "hbm_roofline_frac": round(sub_bytes * steps / dts / 1e9 / HBM_PEAK_GBS, 4),
                      "note": "depthwise + pointwise layers only (no stem), wall clock over the same number of steps"}
 
-    imgs = batch * world * steps
-    value = imgs / dt
-    bytes_img = layer_specs.algorithmic_bytes_per_image(net, batch)
-    whole_gbs = bytes_img * value / 1e9 / world  # per GPU
-    res = {
-        "value": round(value, 1), "ms_per_step": round(dt / steps * 1e3, 4),
-        "hbm_roofline_frac_whole_path": round(whole_gbs / HBM_PEAK_GBS, 4),
-        "algorithmic_bytes_per_image": int(bytes_img),
+    res.update({
         "roofline": {"bound": "hbm", "kernel": dominant, "achieved": round(dom_gbs, 1), "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": round(dom_gbs / HBM_PEAK_GBS, 4),
                      "frac_of_measured_copy_ceiling": round(dom_gbs / HBM_COPY_GBS, 4),
@@ -523,9 +568,7 @@ def run_config(L, net, batch, qbits, passes, steps, warmup, dev, rank, world, po
         "kernels": {k: {"ms_per_step": round(v["ms"], 4), "GB/s": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1),
                         "TFLOP/s": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 1), "launches": v["launches"]}
                     for k, v in fam.items()},
-        "pointwise_mfma": next((l.kernel for l in layers if l.kernel.startswith("pw_")), None),
-        "n_layers": len(layers),
-    }
+    })
     if dominant.startswith(("dense_mfma", "stem_mfma_")):
         # compute-bound families (VGG-16 / ResNet-50 3x3, large stems): price against the matrix cores.
         # achieved = algorithmic flops (2 * MACs of the layers) / measured time incl. the fp16 encode pre-pass
@@ -542,7 +585,6 @@ def run_config(L, net, batch, qbits, passes, steps, warmup, dev, rank, world, po
     if single is not None:
         single["hbm_roofline_frac_whole_path"] = round(bytes_img * single["value"] / 1e9 / world / HBM_PEAK_GBS, 4)
         res["single_stream"] = single
-        res["image_groups"] = image_groups
     if per_layer and rank == 0:
         for l, ms in zip(layers, layer_ms):
             sp = l.spec
@@ -730,13 +772,35 @@ OTHER_CONFIGS = (("vgg16_224", 128, 8), ("resnet50_imagenet224", 128, 8), ("sque
                  ("shufflenetv2_224", 256, 7))
 
 
+def _positive(s):
+    v = int(s)
+    if v < 1:
+        raise argparse.ArgumentTypeError("must be at least 1")
+    return v
+
+
+def _non_negative(s):
+    v = int(s)
+    if v < 0:
+        raise argparse.ArgumentTypeError("must be at least 0")
+    return v
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     # 200 timed steps after 100 warm-up steps (0.65 s of GPU time): the step time settles ~1.3 % below what 20 steps after 5 show
     # (clocks and the Infinity Cache reach their steady state) and repeats within +-0.1 % on one box (profiles/ab_env_long.sh)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=100)
+    ap.add_argument("--steps", type=_positive, default=200)
+    ap.add_argument("--warmup", type=_non_negative, default=100)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement: the single-stream timing next to the image groups, the "
+                         "per-kernel pass (roofline, kernels), the float32-equivalent mode, the north-star scope, the code "
+                         "path, BASELINE configs 3-5 and the codec, the whole net and the CPU baseline (the --no-* options "
+                         "leave some out)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write every layer's output of the last timed step (float32; a fixed "
+                         "sample of a large one) to DIR/layer<i>_y.npy")
     ap.add_argument("--net", default="mobilenetv1_imagenet224")
     ap.add_argument("--batch", type=int, default=256, help="images per GPU per step (weak scaling)")
     ap.add_argument("--global-batch", type=int, default=0,
@@ -745,11 +809,12 @@ def main():
     ap.add_argument("--passes", type=int, default=0, choices=[0, 1, 3], help="pointwise MFMA precision (0 = library default)")
     ap.add_argument("--qbits", type=int, default=8, choices=[8, 7], help="8 = SLFP<3,4> (headline), 7 = SFP<3,3> (BASELINE config 5)")
     ap.add_argument("--post", action="store_true", help="run every layer with the fused BN+ReLU epilogue (secondary measurement)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-whole-net", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short runs of BASELINE configs 3-5 and the codec")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-whole-net", action="store_true", help="with --full: skip the whole-net measurements")
+    ap.add_argument("--no-other-configs", action="store_true",
+                    help="with --full: skip the short runs of BASELINE configs 3-5 and the codec")
     ap.add_argument("--cpu-sample-batch", type=int, default=16)
-    ap.add_argument("--per-layer", action="store_true", help="also print a per-layer table to stderr")
+    ap.add_argument("--per-layer", action="store_true", help="also run the per-kernel pass and print a per-layer table to stderr")
     ap.add_argument("--image-groups", type=int, default=2,
                     help="run a step's batch as this many independent image groups on as many HIP streams (1 = one stream)")
     args = ap.parse_args()
@@ -781,8 +846,14 @@ def main():
     if strong and batch * world != args.global_batch:
         raise SystemExit("--global-batch must divide evenly over the ranks (the bench reports one per-rank batch)")
 
+    dump = {} if args.dump_outputs and rank == 0 else None
     res, rank_dts = run_config(L, args.net, batch, args.qbits, args.passes, args.steps, args.warmup, dev, rank, world,
-                               post=args.post, per_layer=args.per_layer, exact_too=True, image_groups=args.image_groups)
+                               post=args.post, per_layer=args.per_layer, exact_too=True, image_groups=args.image_groups,
+                               full=args.full, dump=dump)
+    if dump is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in dump.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
 
     if rank == 0:
         out = {
@@ -801,17 +872,19 @@ def main():
                        "pointwise_mfma": res["pointwise_mfma"]},
             "hbm_roofline_frac_whole_path": res["hbm_roofline_frac_whole_path"],
             "algorithmic_bytes_per_image": res["algorithmic_bytes_per_image"],
-            "roofline": res["roofline"], "kernels": res["kernels"],
             "rank_ms_per_step": [round(d / args.steps * 1e3, 4) for d in rank_dts],
         }
+        if "roofline" in res:   # the per-kernel pass (--full, --per-layer)
+            out["roofline"], out["kernels"] = res["roofline"], res["kernels"]
         if "value_pointwise_f16x3_float32_equivalent" in res:
             out["value_pointwise_f16x3_float32_equivalent"] = res["value_pointwise_f16x3_float32_equivalent"]
         if "dw_pw_scope" in res:
             out["dw_pw_scope"] = res["dw_pw_scope"]
         if "single_stream" in res:
             out["single_stream"] = res["single_stream"]   # the same steps as 27 whole-batch launches on one stream
+        if "image_groups" in res:
             out["image_groups"] = res["image_groups"]
-    if world == 1 and rank == 0:
+    if args.full and world == 1 and rank == 0:
         if not args.no_other_configs:
             # BASELINE configs 3-5 at their named batch sizes: short runs (3 steps), each with its own roofline object
             other = {}

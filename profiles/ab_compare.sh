@@ -19,10 +19,11 @@ case "$1" in
   run)
     shift
     cd _ab_old
+    FULL=$(python bench.py --help | grep -q -- --full && echo --full)   # older bench.py ran everything by default
     for i in 1 2 3; do
       for v in old new; do
         cp cnns_slfp_quantization_amd/libslfp_hip_$v.so cnns_slfp_quantization_amd/libslfp_hip.so
-        python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-whole-net --passes 1 "$@" 2>/dev/null | \
+        python bench.py $FULL --steps 10 --warmup 3 --no-cpu-baseline --no-whole-net --passes 1 "$@" 2>/dev/null | \
           python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$v', d['value'], {k:v['ms_per_step'] for k,v in d['kernels'].items()})"
       done
     done

@@ -6,7 +6,7 @@ VAR="$1"; shift
 for i in 1 2 3; do
   for v in off on; do
     if [ "$v" = on ]; then export "$VAR"=1; else unset "$VAR"; fi
-    python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-whole-net --passes 1 "$@" 2>/dev/null | \
+    python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-whole-net --passes 1 "$@" 2>/dev/null | \
       python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$VAR=$v', d['value'], {k:(v['ms_per_step'], v['GB/s']) for k,v in d['kernels'].items()})"
   done
 done

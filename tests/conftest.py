@@ -8,6 +8,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 GOLDEN = os.path.join(ROOT, "tests", "golden")
+if GOLDEN not in sys.path:
+    sys.path.insert(0, GOLDEN)
+from golden_parts import GoldenParts  # noqa: E402
 
 
 def pytest_configure(config):
@@ -30,12 +33,12 @@ def pytest_sessionstart(session):
 
 @pytest.fixture(scope="session")
 def codec_golden():
-    return np.load(os.path.join(GOLDEN, "codec_golden.npz"))
+    return GoldenParts(os.path.join(GOLDEN, "codec_golden"))
 
 
 @pytest.fixture(scope="session")
 def conv_golden():
-    return np.load(os.path.join(GOLDEN, "conv_golden.npz"))
+    return GoldenParts(os.path.join(GOLDEN, "conv_golden"))
 
 
 def same_bits(a, b):

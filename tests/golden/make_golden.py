@@ -11,8 +11,8 @@ What it does
      oracle/slfp_oracle.c and oracle/torch_port.py bit-for-bit; checks edge cases; checks
      the oracle's conv2d/linear against the reference's Conv2d_Q / Linear_Q modules.
   2. WRITES FIXTURES (inputs + the reference's outputs, data only):
-       codec_golden.npz   known-answer vectors for the three codecs (+ scaled division)
-       conv_golden.npz    per-layer Conv2d_Q / Conv2d_Q(bias) / Linear_Q cases, Qbits 8/7/32
+       codec_golden_part<i>.npz  known-answer vectors for the three codecs (+ scaled division)
+       conv_golden_part<i>.npz   per-layer Conv2d_Q / Conv2d_Q(bias) / Linear_Q cases, Qbits 8/7/32
        sweep_report.json  the sweep verdicts (counts, mismatches = 0)
 The inputs come from this repo's own numpy generator (seeded); only data is stored.
 """
@@ -35,6 +35,8 @@ import torch  # noqa: E402
 
 from oracle import slfp_oracle as so  # noqa: E402
 from oracle import torch_port as tp  # noqa: E402
+sys.path.append(HERE)
+import golden_parts as gp  # noqa: E402
 from utils.conv2d_func import conv2d_Q, conv2d_Q_bias, linear_Q  # noqa: E402  (reference)
 from utils.sfp_quant import quantize_act, quantize_layerout, quantize_weight  # noqa: E402  (reference)
 
@@ -309,10 +311,10 @@ def main():
         report = sweep()
         report["_torch"] = torch.__version__
         json.dump(report, open(rep_path, "w"))
-    np.savez_compressed(os.path.join(HERE, "codec_golden.npz"), **make_codec(report, rng))
-    np.savez_compressed(os.path.join(HERE, "conv_golden.npz"), **make_conv())
+    parts = gp.save_parts(os.path.join(HERE, "codec_golden"), make_codec(report, rng))
+    parts += gp.save_parts(os.path.join(HERE, "conv_golden"), make_conv())
     np.savez_compressed(os.path.join(HERE, "net_golden.npz"), **make_net())
-    for f in ("codec_golden.npz", "conv_golden.npz", "net_golden.npz", "sweep_report.json"):
+    for f in [os.path.basename(p) for p in parts] + ["net_golden.npz", "sweep_report.json"]:
         print(f, os.path.getsize(os.path.join(HERE, f)), "bytes")
 
 
