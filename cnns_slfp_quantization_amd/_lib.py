@@ -14,6 +14,7 @@ OK, ERR_BAD_ARG, ERR_SHAPE, ERR_UNSUPPORTED, ERR_ALIGNMENT, ERR_HIP = 0, -1, -2,
 FMT_ACT8, FMT_W8, FMT_SFP7, FMT_EXT = 0, 1, 2, 4
 LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
 MFMA_DEFAULT, MFMA_F16X1, MFMA_F16X3 = 0, 1, 3
+OPT_SGD, OPT_DSGD, OPT_SSGD = 0, 1, 2
 
 # every symbol include/slfp.h declares (tests check the .so exports exactly these)
 SYMBOLS = (
@@ -25,7 +26,7 @@ SYMBOLS = (
     "slfp_nchw_to_nhwc_f32", "slfp_nhwc_to_nchw_f32", "slfp_debug_div_mismatches",
     "slfp_debug_enc_mismatches", "slfp_enc_table_ok", "slfp_dwpw_supported", "slfp_dwpw_fwd",
     "slfp_conv2d_codes_supported", "slfp_conv2d_fwd_codes", "slfp_conv2d_fwd_codes_ws", "slfp_maxpool2d_codes", "slfp_debug_code_mismatches", "slfp_debug_reload_switches",
-    "slfp_debug_enc_hl_mismatches",
+    "slfp_debug_enc_hl_mismatches", "slfp_sgd_step_f32",
 )
 
 
@@ -45,6 +46,13 @@ class ConvDesc(ctypes.Structure):
 class ConvIo(ctypes.Structure):
     """struct slfp_conv2d_io: float32 or 1-byte codes on either side of a layer (slfp_conv2d_fwd_codes)"""
     _fields_ = [("x_codes", ctypes.c_int32), ("y_codes", ctypes.c_int32), ("y_ka", ctypes.c_float), ("y_qbits", ctypes.c_int32)]
+
+
+class SgdHparams(ctypes.Structure):
+    """struct slfp_sgd_hparams (slfp_sgd_step_f32)"""
+    _fields_ = [("rule", ctypes.c_int32), ("qbits", ctypes.c_int32), ("lr", ctypes.c_float), ("momentum", ctypes.c_float),
+                ("damp_alpha", ctypes.c_float), ("weight_decay", ctypes.c_float), ("nesterov", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
 
 
 class SlfpError(RuntimeError):
@@ -108,6 +116,7 @@ def load():
         "slfp_debug_code_mismatches": (ci, [cf, ci, vp, vp]),
         "slfp_debug_reload_switches": (None, []),
         "slfp_debug_enc_hl_mismatches": (ci, [cf, ci, vp, vp]),
+        "slfp_sgd_step_f32": (ci, [ctypes.POINTER(SgdHparams), sz, vp, vp, vp, vp, vp, vp]),
     }
     assert set(sigs) == set(SYMBOLS)
     for name, (res, args) in sigs.items():

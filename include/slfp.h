@@ -248,6 +248,28 @@ int slfp_debug_enc_hl_mismatches(float scale_div, int fmt, unsigned long long* o
 /* 1 if the threshold table exists for this scale / format (host-only query, no device work). */
 int slfp_enc_table_ok(float scale_div, int fmt);
 
+/* ---- optimizer step: replaces DSGD / SSGD / NormalSGD.step (utils/optimizer.py) ---------------------------------------
+ * For every tensor i (numel[i] float32 elements; param[i], grad[i] and momentum_buf[i] share one dense layout), in place:
+ *     g = g + weight_decay * p                      (weight_decay != 0; grad[i] keeps the result, as p.grad does)
+ *     buf = first_step[i] ? g : (buf * momentum) + damp_alpha * g      (momentum != 0; buf is not read on the first step)
+ *     d = momentum != 0 ? (nesterov ? g + momentum * buf : buf) : g
+ *     t = d * -lr;   wb = Q(p);   p = p + t
+ *     SLFP_OPT_DSGD: s = |wb - Q(p)| < 1e-4f ? 2 : 0;   SLFP_OPT_SSGD: s = |p| + 1;   then p = p + t * s
+ * Q = quantize_weight(qbits) at unit scale (32 = identity).  Every line is its own float32 rounding; `a + alpha * b` is one
+ * fused multiply-add, as ATen's add(alpha=) computes it on gfx950.  lr, momentum, damp_alpha = float32(1 - dampening) (the
+ * subtraction in double) and weight_decay are the float32 values ATen applies.  momentum_buf: NULL iff momentum == 0.  The
+ * host arrays are read during the call only; tensors are grouped into launches of up to 48 (no device allocation, no copy). */
+#define SLFP_OPT_SGD 0  /* NormalSGD */
+#define SLFP_OPT_DSGD 1
+#define SLFP_OPT_SSGD 2
+typedef struct slfp_sgd_hparams {
+    int32_t rule, qbits;                          /* SLFP_OPT_*, 8 / 7 / 32                        */
+    float lr, momentum, damp_alpha, weight_decay; /* the float32 values ATen applies               */
+    int32_t nesterov, reserved;                   /* nesterov: 0 / 1                               */
+} slfp_sgd_hparams;
+int slfp_sgd_step_f32(const slfp_sgd_hparams* h, size_t ntensors, float* const* param, float* const* grad,
+                      float* const* momentum_buf, const int64_t* numel, const uint8_t* first_step, void* stream);
+
 /* ---- layout helpers (the reference is NCHW; the kernels are NHWC) -------------------- */
 int slfp_nchw_to_nhwc_f32(const float* x, float* y, int64_t n, int64_t c, int64_t h, int64_t w, void* stream);
 int slfp_nhwc_to_nchw_f32(const float* x, float* y, int64_t n, int64_t c, int64_t h, int64_t w, void* stream);
