@@ -27,6 +27,7 @@ SYMBOLS = (
     "slfp_debug_enc_mismatches", "slfp_enc_table_ok", "slfp_dwpw_supported", "slfp_dwpw_fwd",
     "slfp_conv2d_codes_supported", "slfp_conv2d_fwd_codes", "slfp_conv2d_fwd_codes_ws", "slfp_maxpool2d_codes", "slfp_debug_code_mismatches", "slfp_debug_reload_switches",
     "slfp_debug_enc_hl_mismatches", "slfp_sgd_step_f32",
+    "slfp_conv2d_bwd_supported", "slfp_conv2d_bwd_kernel_name", "slfp_conv2d_bwd_workspace_bytes", "slfp_conv2d_bwd",
 )
 
 
@@ -117,6 +118,10 @@ def load():
         "slfp_debug_reload_switches": (None, []),
         "slfp_debug_enc_hl_mismatches": (ci, [cf, ci, vp, vp]),
         "slfp_sgd_step_f32": (ci, [ctypes.POINTER(SgdHparams), sz, vp, vp, vp, vp, vp, vp]),
+        "slfp_conv2d_bwd_supported": (ci, [dp]),
+        "slfp_conv2d_bwd_kernel_name": (ctypes.c_char_p, [dp]),
+        "slfp_conv2d_bwd_workspace_bytes": (sz, [dp, ci, ci]),
+        "slfp_conv2d_bwd": (ci, [dp, vp, vp, vp, vp, vp, vp, vp, vp]),
     }
     assert set(sigs) == set(SYMBOLS)
     for name, (res, args) in sigs.items():

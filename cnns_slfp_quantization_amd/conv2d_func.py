@@ -28,8 +28,11 @@ which `.view()`s NCHW strides (nets_cifar/shufflenet_v2.py:41) keeps working.  U
 `model.to(memory_format=torch.channels_last)` + a channels_last input for the fast path.
 
 There is no CPU compute path here (q_bit 8/7 need a ROCm tensor; q_bit 32 is the
-reference's passthrough).  Autograd: forward is always the HIP kernel; backward is the
-reference's STE composite on the GPU (training is outside the accelerated scope).
+reference's passthrough).  Autograd: forward is always the HIP kernel.  Backward follows
+`options.backward`: "composite" (the default) is the reference's STE composite on the GPU
+(torch.nn.grad on the quantized operands); "hip" runs the 3x3 depthwise, stride-1 1x1 and
+Linear_Q layers through one slfp_conv2d_bwd call each (float32 accumulation, deterministic;
+`module._last_bwd_kernel` names what ran) and keeps every other layer on the composite.
 """
 import contextlib
 import ctypes
@@ -58,8 +61,15 @@ class _Options:
     dwpw_all = False                 # True: fusion.DwPwBlock uses the one-kernel form wherever the library supports it,
                                      # not only where it measured faster than two kernels
     dwpw_pairs = {(32, 1)}           # (depthwise channels, stride) pairs that run as one kernel by default
+    backward = "composite"           # "composite": the reference's STE composite; "hip": slfp_conv2d_bwd where it covers the layer
+
+    def __setattr__(self, name, value):
+        if name == "backward" and value not in _BACKWARDS:
+            raise ValueError(f"options.backward must be one of {_BACKWARDS}, got {value!r}")
+        super().__setattr__(name, value)
 
 
+_BACKWARDS = ("composite", "hip")
 options = _Options()
 
 
@@ -313,9 +323,78 @@ def _hip_conv2d_codes(mod, x, weight, bias):
     return y
 
 
+def _aligned(t):
+    """`t` itself if its data is 16-byte aligned (what the C ABI requires), else an aligned copy."""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _hip_backward(mod, x, w, gy, desc, need_gx, need_gw, need_gb):
+    """One slfp_conv2d_bwd call on dense, aligned NCHW / NHWC operands (the layouts `desc` names).  Returns (gx, gw, gb)
+    with None for what was not asked; gx has x's memory format, gw is contiguous like `w`."""
+    L = _lib.load()
+    gx = torch.empty_like(x) if need_gx else None
+    gw = torch.empty(w.shape, dtype=torch.float32, device=x.device) if need_gw else None
+    gb = torch.empty(desc.c_out, dtype=torch.float32, device=x.device) if need_gb else None
+    with _on_device(x.device):
+        nbytes = L.slfp_conv2d_bwd_workspace_bytes(ctypes.byref(desc), int(need_gx), int(need_gw))
+        ws = _workspace(x.device, nbytes) if nbytes else None
+        _lib.check(L.slfp_conv2d_bwd(ctypes.byref(desc), x.data_ptr(), w.data_ptr(), gy.data_ptr(),
+                                     gx.data_ptr() if gx is not None else None, gw.data_ptr() if gw is not None else None,
+                                     gb.data_ptr() if gb is not None else None, ws.data_ptr() if ws is not None else None,
+                                     _stream_handle(x)))
+    return gx, gw, gb
+
+
+def _conv_backward_hip(ctx, gy):
+    """_SlfpConv2dFn.backward on the HIP kernels, or None where slfp_conv2d_bwd does not cover the layer."""
+    mod = ctx.mod
+    x, weight = ctx.saved_tensors
+    squeeze = x.dim() == 3
+    if squeeze:
+        x, gy = x.unsqueeze(0), gy.unsqueeze(0)
+    if x.numel() == 0 or gy.numel() == 0 or not x.is_cuda:
+        return None
+    x = x.detach()
+    nhwc_x = x.is_contiguous(memory_format=torch.channels_last)
+    if not nhwc_x and not x.is_contiguous():
+        x = x.contiguous()
+    if gy.is_contiguous(memory_format=torch.channels_last):
+        nhwc_y = True
+    elif gy.is_contiguous():
+        nhwc_y = False
+    else:   # e.g. the stride-0 gy of out.sum().backward()
+        nhwc_y = nhwc_x
+        gy = gy.contiguous(memory_format=torch.channels_last if nhwc_y else torch.contiguous_format)
+    N, C, H, W = x.shape
+    sh, sw = _pair(mod.stride)
+    ph, pw = _pair(mod.padding) if not isinstance(mod.padding, str) else (-1, -1)
+    dh, dw = _pair(mod.dilation)
+    d = _lib.ConvDesc(n=N, c_in=C, h=H, w=W, c_out=mod.out_channels, kh=weight.shape[2], kw=weight.shape[3],
+                      stride_h=sh, stride_w=sw, pad_h=ph, pad_w=pw, dil_h=dh, dil_w=dw, groups=mod.groups,
+                      x_layout=_lib.LAYOUT_NHWC if nhwc_x else _lib.LAYOUT_NCHW,
+                      y_layout=_lib.LAYOUT_NHWC if nhwc_y else _lib.LAYOUT_NCHW,
+                      qbits=mod.q_bit, ka=_f32(mod.Ka), kw_scale=_f32(mod.Kw), mfma_passes=options.mfma_passes, reserved=0)
+    L = _lib.load()
+    if ph < 0 or not L.slfp_conv2d_bwd_supported(ctypes.byref(d)):
+        return None
+    need_gx, need_gw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    need_gb = ctx.has_bias and ctx.needs_input_grad[2]
+    w = weight.detach()
+    w = _aligned(w if w.is_contiguous() else w.contiguous())   # OIHW
+    # the bias sum comes with the weight gradient's pass (a frozen weight with a trainable bias still runs it)
+    gx, gw, gb = _hip_backward(mod, _aligned(x), w, _aligned(gy), d, need_gx, need_gw or need_gb, need_gb)
+    if not need_gw:
+        gw = None
+    mod._last_bwd_kernel = L.slfp_conv2d_bwd_kernel_name(ctypes.byref(d)).decode()
+    if squeeze and gx is not None:
+        gx = gx.squeeze(0)
+    return gx, gw, gb
+
+
 class _SlfpConv2dFn(torch.autograd.Function):
     """HIP forward; backward = the reference's composite (STE through both quantizers:
-    utils/sfp_quant.py:50-53, :99-102; conv gradients from torch.nn.grad on the GPU)."""
+    utils/sfp_quant.py:50-53, :99-102; conv gradients from torch.nn.grad on the GPU), or the HIP kernels of
+    slfp_conv2d_bwd with options.backward = "hip"."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, mod, scaled_bias):
@@ -328,6 +407,11 @@ class _SlfpConv2dFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         mod = ctx.mod
+        if options.backward == "hip":
+            res = _conv_backward_hip(ctx, gy)
+            if res is not None:
+                return res[0], res[1], res[2], None, None
+        mod._last_bwd_kernel = "composite"
         x, weight = ctx.saved_tensors
         ka, kw = _f32(mod.Ka), _f32(mod.Kw)
         fa = _lib.FMT_ACT8 if mod.q_bit == 8 else _lib.FMT_SFP7
@@ -374,6 +458,7 @@ def _conv_class(q_bit, Kw, Ka, bias_default, scaled_bias):
             self._input_q = None
             self._weight_q32 = None
             self._last_kernel = None
+            self._last_bwd_kernel = None   # what the last backward ran: a slfp_conv2d_bwd kernel name or "composite"
             self._post = None  # (scale, shift, relu): fused eval-BN + ReLU epilogue (fusion.fuse_bn_relu)
             self._code_out = None   # (Ka, q_bit) of the next Conv2d_Q: hand it 1-byte codes (fusion.link_codes)
             self._last_codes = None
@@ -517,6 +602,27 @@ class _SlfpLinearFn(torch.autograd.Function):
     def backward(ctx, gy):
         mod = ctx.mod
         x, weight = ctx.saved_tensors
+        if options.backward == "hip" and x.is_cuda and x.numel() > 0:
+            # the pointwise kernels with rows = the product of the leading dims and H = W = 1
+            I, O = x.shape[-1], weight.shape[0]
+            x2 = _aligned(x.detach().reshape(-1, I).contiguous())
+            gy2 = _aligned(gy.reshape(-1, O).contiguous())
+            d = _lib.ConvDesc(n=x2.shape[0], c_in=I, h=1, w=1, c_out=O, kh=1, kw=1, stride_h=1, stride_w=1, pad_h=0, pad_w=0,
+                              dil_h=1, dil_w=1, groups=1, x_layout=_lib.LAYOUT_NHWC, y_layout=_lib.LAYOUT_NHWC,
+                              qbits=mod.q_bit, ka=_f32(mod.Ka), kw_scale=_f32(mod.Kw), mfma_passes=options.mfma_passes,
+                              reserved=0)
+            L = _lib.load()
+            if L.slfp_conv2d_bwd_supported(ctypes.byref(d)):
+                need_gx, need_gw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+                need_gb = ctx.has_bias and ctx.needs_input_grad[2]
+                w = weight.detach()
+                w = _aligned(w if w.is_contiguous() else w.contiguous())
+                gx, gw, gb = _hip_backward(mod, x2, w, gy2, d, need_gx, need_gw or need_gb, need_gb)
+                if not need_gw:
+                    gw = None
+                mod._last_bwd_kernel = L.slfp_conv2d_bwd_kernel_name(ctypes.byref(d)).decode()
+                return (gx.reshape(x.shape) if gx is not None else None), gw, gb, None
+        mod._last_bwd_kernel = "composite"
         ka, kw = _f32(mod.Ka), _f32(mod.Kw)
         fa = _lib.FMT_ACT8 if mod.q_bit == 8 else _lib.FMT_SFP7
         fw = _lib.FMT_W8 if mod.q_bit == 8 else _lib.FMT_SFP7
@@ -546,6 +652,7 @@ def linear_Q(q_bit, Kw, Ka):
             self._input_q = None
             self._weight_q = None
             self.bias_q = None
+            self._last_bwd_kernel = None
 
         # The reference stores input_q / weight_q / bias_q on every forward (utils/conv2d_func.py:60-64) and its nets
         # read them back afterwards (nets_cifar/mobilenetv1.py:169-170, resnet50.py:353-354, alexnet.py:107-114);

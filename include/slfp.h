@@ -270,6 +270,22 @@ typedef struct slfp_sgd_hparams {
 int slfp_sgd_step_f32(const slfp_sgd_hparams* h, size_t ntensors, float* const* param, float* const* grad,
                       float* const* momentum_buf, const int64_t* numel, const uint8_t* first_step, void* stream);
 
+/* ---- backward of Conv2d_Q / Linear_Q (the reference's STE gradients, utils/conv2d_func.py) ----------------------------
+ *     gx = conv_input(QW(w / Kw), gy) * Kw      gw = conv_weight(QA(x / Ka), gy) * Ka      gb = sum_{n,h,w} gy
+ * accumulated in float32 (VALU FMAs for depthwise, float32 MFMA for pointwise); QA is applied on load, bit-identical to
+ * slfp_quantize_f32.  Deterministic: partial sums go through the workspace and are added in a fixed order, no atomics.
+ * Covered: 3x3 depthwise (groups == C_in == C_out, stride 1 or 2, pad 1, dilation 1) and 1x1 stride-1 pad-0 groups-1 layers
+ * (a Linear_Q is the 1x1 case with n = rows, h = w = 1); everything else returns SLFP_ERR_UNSUPPORTED.
+ * slfp_conv2d_bwd_kernel_name: "dw3x3_bwd", "pw_bwd_mfma_f32" or "composite" (not covered).  mfma_passes is ignored.
+ * x / gx follow d->x_layout, gy follows d->y_layout, w_oihw and gw_oihw are contiguous OIHW.  gx / gw / gb may be NULL (not
+ * needed); gb needs gw.  All tensors 16-byte aligned; workspace: slfp_conv2d_bwd_workspace_bytes(d, gx != NULL, gw != NULL)
+ * bytes, 16-byte aligned (NULL if 0). */
+int slfp_conv2d_bwd_supported(const slfp_conv2d_desc* d);
+const char* slfp_conv2d_bwd_kernel_name(const slfp_conv2d_desc* d);
+size_t slfp_conv2d_bwd_workspace_bytes(const slfp_conv2d_desc* d, int need_gx, int need_gw);
+int slfp_conv2d_bwd(const slfp_conv2d_desc* d, const float* x, const float* w_oihw, const float* gy, float* gx, float* gw_oihw,
+                    float* gb, void* workspace, void* stream);
+
 /* ---- layout helpers (the reference is NCHW; the kernels are NHWC) -------------------- */
 int slfp_nchw_to_nhwc_f32(const float* x, float* y, int64_t n, int64_t c, int64_t h, int64_t w, void* stream);
 int slfp_nhwc_to_nchw_f32(const float* x, float* y, int64_t n, int64_t c, int64_t h, int64_t w, void* stream);

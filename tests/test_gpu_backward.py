@@ -1,0 +1,333 @@
+"""GPU: the HIP backward of Conv2d_Q / Linear_Q (options.backward = "hip", slfp_conv2d_bwd) against a float64 reference
+built from the C oracle's quantized operands, next to the composite's error on the same inputs; module-level behaviour,
+determinism and a short fine-tune of the MobileNetV1-CIFAR stack."""
+import numpy as np
+import pytest
+import torch
+
+from oracle import slfp_oracle
+from cnns_slfp_quantization_amd import layer_specs, optimizer as O
+from cnns_slfp_quantization_amd import conv2d_func as cf
+from cnns_slfp_quantization_amd.conv2d_func import conv2d_Q, conv2d_Q_bias, linear_Q
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+
+
+@pytest.fixture(autouse=True)
+def _composite_default():
+    cf.options.backward = "composite"
+    yield
+    cf.options.backward = "composite"
+
+
+def _covered(s):
+    dw = s.groups == s.c_in == s.c_out and s.k == (3, 3) and s.stride[0] == s.stride[1] and s.stride[0] in (1, 2) and s.pad == (1, 1)
+    pw = s.k == (1, 1) and s.groups == 1 and s.stride == (1, 1) and s.pad == (0, 0)
+    return dw or pw
+
+
+def _geometries():
+    seen, out = set(), []
+    for net in ("mobilenetv1_imagenet224", "mobilenetv1_cifar32", "resnet50_imagenet224", "squeezenet1_0_imagenet224",
+                "shufflenetv2_224"):
+        for s in layer_specs.conv_layers(net):
+            key = (s.c_in, s.c_out, s.k, s.stride, s.groups, s.h, s.w)
+            if _covered(s) and key not in seen:
+                seen.add(key)
+                out.append((net, s))
+    return out
+
+
+GEOMS = _geometries()
+
+
+def _x_values(shape, ka, gen, relu=False):
+    """Every code range: below 0.0625*Ka, the log range, above the clamp, negatives, exact zeros."""
+    mag = torch.exp2(torch.empty(shape).uniform_(-9, 5, generator=gen)) * ka
+    sign = torch.where(torch.rand(shape, generator=gen) < 0.5, -1.0, 1.0) if not relu else 1.0
+    x = mag * sign
+    x[torch.rand(shape, generator=gen) < 0.05] = 0.0
+    return x.float()
+
+
+def _reference(x, w, gy, mod):
+    """(gx, gw, gb) and the same contractions over absolute values, in float64 from the oracle's quantized operands."""
+    q = mod.q_bit
+    ka, kw = cf._f32(mod.Ka), cf._f32(mod.Kw)
+    xq = torch.from_numpy(slfp_oracle.quantize(x.numpy(), ka, 0 if q == 8 else 2)).double()
+    wq = torch.from_numpy(slfp_oracle.quantize(w.numpy(), kw, 1 if q == 8 else 2)).double()
+    g = gy.double()
+    args = (mod.stride, mod.padding, mod.dilation, mod.groups)
+    gx = torch.nn.grad.conv2d_input(x.shape, wq, g, *args) * kw
+    ax = torch.nn.grad.conv2d_input(x.shape, wq.abs(), g.abs(), *args) * kw
+    gw = torch.nn.grad.conv2d_weight(xq, w.shape, g, *args) * ka
+    aw = torch.nn.grad.conv2d_weight(xq.abs(), w.shape, g.abs(), *args) * ka
+    gb = g.sum(dim=(0, 2, 3))
+    ab = g.abs().sum(dim=(0, 2, 3))
+    return (gx, ax), (gw, aw), (gb, ab)
+
+
+def _errors(got, ref):
+    """(max |g - ref| / abs64 elementwise, tensor-relative L2)."""
+    r, a = ref
+    d = (got.double().cpu() - r).abs()
+    elem = torch.where(a > 0, d / a.clamp_min(1e-300), torch.where(d > 0, torch.inf, 0.0)).max().item()
+    l2 = (d.norm() / r.norm().clamp_min(1e-300)).item()
+    return elem, l2
+
+
+def _conv_grads(mod, x, gy, mode, need=(True, True, True)):
+    cf.options.backward = mode
+    xi = x.detach().clone().requires_grad_(need[0])
+    mod.weight.requires_grad_(need[1])
+    if mod.bias is not None:
+        mod.bias.requires_grad_(need[2])
+    mod.zero_grad(set_to_none=True)
+    out = mod(xi)
+    out.backward(gy)
+    gb = mod.bias.grad if mod.bias is not None else None
+    return xi.grad, mod.weight.grad, gb, out
+
+
+def _make(spec, q, scaled, gen, bias=True):
+    cls = conv2d_Q_bias if scaled else conv2d_Q
+    mod = cls(q, spec.Kw, spec.Ka)(spec.c_in, spec.c_out, spec.k, stride=spec.stride, padding=spec.pad,
+                                   groups=spec.groups, bias=bias).to(DEV)
+    with torch.no_grad():
+        fan = spec.c_in // spec.groups * spec.k[0] * spec.k[1]
+        mod.weight.copy_((torch.randn(mod.weight.shape, generator=gen) * (2.0 / fan) ** 0.5).to(DEV))
+        if mod.bias is not None:
+            mod.bias.copy_((torch.randn(spec.c_out, generator=gen) * 0.1).to(DEV))
+    return mod
+
+
+def _check_case(spec, n, q, scaled, gen, channels_last, sparse=False, label=""):
+    mod = _make(spec, q, scaled, gen)
+    x = _x_values((n, spec.c_in, spec.h, spec.w), spec.Ka, gen)
+    gy = torch.randn((n, spec.c_out, spec.h_out, spec.w_out), generator=gen)
+    if sparse:
+        keep = torch.zeros_like(gy, dtype=torch.bool).view(n, spec.c_out, -1)
+        for c in range(spec.c_out):
+            idx = torch.randperm(keep.shape[0] * keep.shape[2], generator=gen)[:2]
+            keep[idx // keep.shape[2], c, idx % keep.shape[2]] = True
+        gy = gy * keep.view_as(gy)
+    fmt = torch.channels_last if channels_last else torch.contiguous_format
+    xd = x.to(DEV).contiguous(memory_format=fmt)
+    gyd = gy.to(DEV).contiguous(memory_format=fmt)
+    refs = _reference(x, mod.weight.detach().cpu(), gy, mod)
+    res = {}
+    for mode in ("hip", "composite"):
+        gx, gw, gb, _ = _conv_grads(mod, xd, gyd, mode)
+        res[mode] = [_errors(gx, refs[0]), _errors(gw, refs[1])]
+        if mod.bias is not None and scaled:
+            res[mode].append(_errors(gb, refs[2]))
+        if mode == "hip":
+            assert mod._last_bwd_kernel in ("dw3x3_bwd", "pw_bwd_mfma_f32"), mod._last_bwd_kernel
+            assert gx.is_contiguous(memory_format=fmt)
+    print(f"{label} {spec.c_in}->{spec.c_out} k{spec.k[0]} s{spec.stride[0]} @{spec.h} n={n} q{q} "
+          f"{'scaled' if scaled else 'raw'} {'nhwc' if channels_last else 'nchw'}: "
+          f"hip {[(f'{e:.2e}', f'{l:.2e}') for e, l in res['hip']]}  composite {[(f'{e:.2e}', f'{l:.2e}') for e, l in res['composite']]}")
+    for e, l in res["hip"]:
+        assert e <= 1e-5 and l <= 1e-6, res["hip"]
+
+
+@pytest.mark.parametrize("i", range(len(GEOMS)), ids=[f"{n}-{s.c_in}x{s.c_out}k{s.k[0]}s{s.stride[0]}@{s.h}" for n, s in GEOMS])
+def test_every_geometry_against_float64(i):
+    net, spec = GEOMS[i]
+    gen = torch.Generator().manual_seed(1000 + i)
+    n = 2 if spec.h >= 56 else 4
+    _check_case(spec, n, 8 if i % 2 == 0 else 7, (i // 2) % 2 == 0, gen, channels_last=i % 3 != 0, label=net)
+
+
+@pytest.mark.parametrize("spec", [
+    layer_specs.ConvSpec(512, 512, (1, 1), (1, 1), (0, 0), 1, False, 14, 14, 14, 14, 0.21, 0.037),
+    layer_specs.ConvSpec(1024, 1024, (1, 1), (1, 1), (0, 0), 1, False, 7, 7, 7, 7, 0.19, 0.031),
+], ids=["pw512@14", "pw1024@7"])
+def test_pointwise_at_size(spec):
+    _check_case(spec, 128, 8, True, torch.Generator().manual_seed(7), channels_last=True, label="at size")
+
+
+@pytest.mark.parametrize("stride", [1, 2])
+def test_depthwise_at_size(stride):
+    ho = 112 // stride
+    spec = layer_specs.ConvSpec(32, 32, (3, 3), (stride, stride), (1, 1), 32, False, 112, 112, ho, ho, 0.17, 0.13)
+    _check_case(spec, 32, 8, True, torch.Generator().manual_seed(8), channels_last=True, label="at size")
+
+
+@pytest.mark.parametrize("spec", [s for _, s in GEOMS if s.h <= 28 and s.c_in <= 256][:8], ids=lambda s: f"{s.c_in}x{s.c_out}k{s.k[0]}s{s.stride[0]}@{s.h}")
+def test_sparse_gy_probe(spec):
+    """gy non-zero at 2 positions per channel: each gw element sums a handful of terms, so one wrong quantization code is
+    a percent-level error, not noise."""
+    _check_case(spec, 2, 8, True, torch.Generator().manual_seed(9), channels_last=True, sparse=True, label="sparse")
+
+
+def test_module_level_kernel_names_layouts_and_needs():
+    gen = torch.Generator().manual_seed(3)
+    dw = _make(layer_specs.ConvSpec(64, 64, (3, 3), (1, 1), (1, 1), 64, False, 14, 14, 14, 14, 0.2, 0.1), 8, False, gen, bias=False)
+    dense = _make(layer_specs.ConvSpec(16, 32, (3, 3), (1, 1), (1, 1), 1, False, 14, 14, 14, 14, 0.2, 0.1), 8, True, gen)
+    x = _x_values((2, 64, 14, 14), 0.2, gen).to(DEV)
+    for fmt in (torch.contiguous_format, torch.channels_last):
+        xi = x.contiguous(memory_format=fmt)
+        gx_h, gw_h, _, out = _conv_grads(dw, xi, torch.ones(1, device=DEV).expand(2, 64, 14, 14), "hip")
+        assert dw._last_bwd_kernel == "dw3x3_bwd"
+        assert gx_h.is_contiguous(memory_format=fmt)
+        # out.sum().backward(): a stride-0 gy
+        cf.options.backward = "hip"
+        xs = xi.detach().clone().requires_grad_(True)
+        dw.zero_grad(set_to_none=True)
+        dw(xs).sum().backward()
+        assert torch.equal(xs.grad, gx_h) and torch.equal(dw.weight.grad, gw_h)
+        gx_c, gw_c, _, _ = _conv_grads(dw, xi, torch.ones(2, 64, 14, 14, device=DEV), "composite")
+        assert dw._last_bwd_kernel == "composite"
+        torch.testing.assert_close(gx_h, gx_c, rtol=1e-5, atol=1e-6)
+        torch.testing.assert_close(gw_h, gw_c, rtol=1e-5, atol=1e-3)
+    xd = _x_values((2, 16, 14, 14), 0.2, gen).to(DEV)
+    _conv_grads(dense, xd, torch.randn(2, 32, 14, 14, generator=gen).to(DEV), "hip")
+    assert dense._last_bwd_kernel == "composite"
+    # needs_input_grad: a first layer's x, a frozen weight, a frozen bias
+    pw = _make(layer_specs.ConvSpec(32, 48, (1, 1), (1, 1), (0, 0), 1, True, 8, 8, 8, 8, 0.2, 0.1), 8, True, gen)
+    xp = _x_values((3, 32, 8, 8), 0.2, gen).to(DEV).contiguous(memory_format=torch.channels_last)
+    gyp = torch.randn(3, 48, 8, 8, generator=gen).to(DEV)
+    full = _conv_grads(pw, xp, gyp, "hip")
+    for need in ((False, True, True), (True, False, True), (True, True, False), (False, False, True), (True, False, False)):
+        got = _conv_grads(pw, xp, gyp, "hip", need)
+        assert pw._last_bwd_kernel == "pw_bwd_mfma_f32"
+        for k in range(3):
+            assert (got[k] is None) == (not need[k]), (need, k)
+            if need[k]:
+                assert torch.equal(got[k], full[k]), (need, k)
+    for m in (dw, pw, dense):
+        m.weight.requires_grad_(True)
+
+
+def test_linear_q_2d_and_3d():
+    gen = torch.Generator().manual_seed(4)
+    for shape in ((32, 1024), (4, 7, 256), (5, 10)):
+        I = shape[-1]
+        lin = linear_Q(8, 0.05, 0.3)(I, 100 if I > 10 else 6).to(DEV)
+        x = _x_values(shape, 0.3, gen).to(DEV)
+        gy = torch.randn(*shape[:-1], lin.out_features, generator=gen).to(DEV)
+        res = {}
+        for mode in ("hip", "composite"):
+            cf.options.backward = mode
+            xi = x.clone().requires_grad_(True)
+            lin.zero_grad(set_to_none=True)
+            lin(xi).backward(gy)
+            res[mode] = (xi.grad, lin.weight.grad, lin.bias.grad)
+            assert lin._last_bwd_kernel == ("pw_bwd_mfma_f32" if mode == "hip" else "composite")
+        xq = torch.from_numpy(slfp_oracle.quantize(x.cpu().numpy(), cf._f32(lin.Ka), 0)).double().reshape(-1, I)
+        wq = torch.from_numpy(slfp_oracle.quantize(lin.weight.detach().cpu().numpy(), cf._f32(lin.Kw), 1)).double()
+        g = gy.cpu().double().reshape(-1, lin.out_features)
+        ref_gx = ((g @ wq) * cf._f32(lin.Kw), (g.abs() @ wq.abs()) * cf._f32(lin.Kw))
+        ref_gw = ((g.t() @ xq) * cf._f32(lin.Ka), (g.abs().t() @ xq.abs()) * cf._f32(lin.Ka))
+        gx, gw, gb = res["hip"]
+        assert gx.shape == x.shape
+        for got, ref in ((gx.reshape(-1, I), ref_gx), (gw, ref_gw), (gb, (g.sum(0), g.abs().sum(0)))):
+            e, l = _errors(got, ref)
+            assert e <= 1e-5 and l <= 1e-6, (shape, e, l)
+
+
+def test_nan_inf_in_x_match_composite():
+    """NaN / inf in x: gw is NaN exactly where the float64 reference is, and the composite is NaN there too.  (MIOpen's
+    depthwise weight gradient adds 0 * NaN terms for the padded output column past the right edge, so the composite has
+    a few NaN taps more than the mathematics; the HIP kernel sums only the real terms.)"""
+    gen = torch.Generator().manual_seed(5)
+    for spec in (layer_specs.ConvSpec(32, 32, (3, 3), (2, 2), (1, 1), 32, False, 15, 15, 8, 8, 0.2, 0.1),
+                 layer_specs.ConvSpec(32, 32, (3, 3), (1, 1), (1, 1), 32, False, 9, 9, 9, 9, 0.2, 0.1),
+                 layer_specs.ConvSpec(32, 64, (1, 1), (1, 1), (0, 0), 1, False, 6, 6, 6, 6, 0.2, 0.1)):
+        mod = _make(spec, 8, True, gen)
+        x = _x_values((2, spec.c_in, spec.h, spec.w), 0.2, gen)
+        x[0, 3, 0, spec.w - 1] = float("nan")
+        x[1, 5, spec.h - 1, 2] = float("inf")
+        x[1, 6, 4, 4] = -float("inf")
+        x[0, 7, spec.h - 1, spec.w - 1] = float("nan")
+        gy = torch.randn(2, spec.c_out, spec.h_out, spec.w_out, generator=gen)
+        ref = _reference(x, mod.weight.detach().cpu(), gy, mod)[1][0]
+        xd = x.to(DEV).contiguous(memory_format=torch.channels_last)
+        gw_h = _conv_grads(mod, xd, gy.to(DEV), "hip")[1].cpu()
+        gw_c = _conv_grads(mod, xd, gy.to(DEV), "composite")[1].cpu()
+        assert torch.equal(torch.isnan(gw_h), torch.isnan(ref))
+        assert torch.equal(torch.isinf(gw_h), torch.isinf(ref))
+        assert torch.isnan(gw_h).any()
+        assert not (torch.isnan(gw_h) & ~torch.isnan(gw_c)).any()
+        assert torch.equal(torch.isinf(gw_h), torch.isinf(gw_c))
+        fin = torch.isfinite(ref)
+        torch.testing.assert_close(gw_h[fin].double(), ref[fin], rtol=1e-5, atol=1e-5 * ref[fin].abs().max().item())
+
+
+def test_deterministic():
+    gen = torch.Generator().manual_seed(6)
+    for spec in (layer_specs.ConvSpec(128, 128, (3, 3), (1, 1), (1, 1), 128, False, 28, 28, 28, 28, 0.2, 0.1),
+                 layer_specs.ConvSpec(256, 256, (1, 1), (1, 1), (0, 0), 1, False, 14, 14, 14, 14, 0.2, 0.1)):
+        mod = _make(spec, 8, True, gen)
+        x = _x_values((32, spec.c_in, spec.h, spec.w), 0.2, gen).to(DEV).contiguous(memory_format=torch.channels_last)
+        gy = torch.randn(32, spec.c_out, spec.h_out, spec.w_out, generator=gen).to(DEV)
+        a = _conv_grads(mod, x, gy, "hip")[:3]
+        b = _conv_grads(mod, x, gy, "hip")[:3]
+        for u, v in zip(a, b):
+            assert torch.equal(u, v)
+
+
+def _finetune_model():
+    layers = []
+    for l in layer_specs.conv_layers("mobilenetv1_cifar32"):
+        Conv = conv2d_Q(8, l.Kw, l.Ka)
+        layers += [Conv(l.c_in, l.c_out, l.k, stride=l.stride, padding=l.pad, groups=l.groups),
+                   torch.nn.BatchNorm2d(l.c_out), torch.nn.ReLU()]
+    fc = [r for r in layer_specs.nets()["mobilenetv1_cifar32"]["layers"] if r["kind"] == "linear"][0]
+    layers += [torch.nn.AdaptiveAvgPool2d(1), torch.nn.Flatten(), linear_Q(8, fc["Kw"], fc["Ka"])(fc["c_in"], fc["c_out"])]
+    return torch.nn.Sequential(*layers)
+
+
+def test_finetune_mobilenetv1_cifar_matches_composite():
+    """Grads of every parameter agree with the composite; after 3 NormalSGD steps the losses agree.  A quantized net is
+    discontinuous in its weights, so two runs whose gradients differ in the last bits drift apart by a few weight codes
+    per step: the bar is 1e-3 relative, or 3x the drift of a control run (the composite with its gradients scaled by
+    1 +- 2^-20, i.e. about the HIP path's summation-order difference) where that is larger."""
+    torch.manual_seed(0)
+    base = _finetune_model()
+    x = torch.randn(32, 3, 32, 32).to(DEV).contiguous(memory_format=torch.channels_last)
+    y = torch.randint(0, 100, (32,)).to(DEV)
+    loss_fn = torch.nn.CrossEntropyLoss()
+    grads, losses, models = {}, {}, {}
+    for mode in ("composite", "hip", "control"):
+        cf.options.backward = "hip" if mode == "hip" else "composite"
+        m = _finetune_model()
+        m.load_state_dict(base.state_dict())
+        m = m.to(DEV).to(memory_format=torch.channels_last)
+        loss_fn(m(x), y).backward()
+        grads[mode] = [p.grad.detach().clone() for p in m.parameters()]
+        kinds = [mod._last_bwd_kernel for mod in m.modules() if hasattr(mod, "_last_bwd_kernel")]
+        if mode == "hip":
+            assert kinds[0] == "composite" and all(k != "composite" for k in kinds[1:]), kinds
+        m.zero_grad(set_to_none=True)
+        opt = O.NormalSGD(m.parameters(), lr=1e-3, momentum=0.9)
+        gen = torch.Generator(device=DEV).manual_seed(1)
+        losses[mode] = []
+        for _ in range(3):
+            opt.zero_grad(set_to_none=True)
+            loss = loss_fn(m(x), y)
+            loss.backward()
+            if mode == "control":
+                for p in m.parameters():
+                    r = torch.rand(p.grad.shape, generator=gen, device=DEV)
+                    p.grad.mul_(torch.where(r < 0.5, 1 - 2.0 ** -20, 1 + 2.0 ** -20))
+            opt.step()
+            losses[mode].append(loss.item())
+        models[mode] = m
+    names = [n for n, _ in base.named_parameters()]
+    for n, a, b in zip(names, grads["hip"], grads["composite"]):
+        atol = (1e-3 if a.dim() == 1 else 1e-5) * b.abs().max().item()   # BN and bias grads compound over the layers
+        torch.testing.assert_close(a, b, rtol=1e-4, atol=atol, msg=lambda s, n=n: f"{n}: {s}")
+    print("losses", losses)
+    for h, c, k in zip(losses["hip"], losses["composite"], losses["control"]):
+        assert abs(h - c) <= max(1e-3 * abs(c), 3 * abs(k - c)), losses
+    # DSGD's fused kernel takes every conv weight gradient the HIP backward produced
+    cf.options.backward = "hip"
+    m = models["hip"]
+    m.zero_grad(set_to_none=True)
+    loss_fn(m(x), y).backward()
+    convs = [mod for mod in m.modules() if isinstance(mod, torch.nn.Conv2d)]
+    assert all(O._fusable(c.weight, c.weight.grad, None) for c in convs)
+    O.DSGD(m.parameters(), 8, lr=0.01, momentum=0.9).step()
