@@ -101,32 +101,63 @@ def _pair(v):
     return (int(v[0]), int(v[1])) if isinstance(v, (tuple, list)) else (int(v), int(v))
 
 
+def _ready_event(stream, cache):
+    """The event that users of a cached blob on other streams wait on: recorded on the preparing stream right after the
+    prepare.  None when the blob is not kept for reuse (cache=False) or was written inside a hipGraph capture (an event
+    recorded there cannot be waited on outside it); a hit from another stream then prepares the blob again."""
+    if not cache or torch.cuda.is_current_stream_capturing():
+        return None
+    ev = torch.cuda.Event()
+    ev.record(stream)
+    return ev
+
+
+def _hit_from_other_stream(blob, ready, synced, stream):
+    """A cache hit on `stream`, which did not prepare `blob`: the stream waits for the prepare, and the blob's memory is
+    tied to it (record_stream), once per stream and blob.  Skipped while capturing: GraphedModule warms the cache up
+    before the capture and torch.cuda.graph synchronises on entry, so the blob is complete by then."""
+    h = stream.cuda_stream
+    if h in synced or torch.cuda.is_current_stream_capturing():
+        return
+    stream.wait_event(ready)
+    blob.record_stream(stream)
+    synced.add(h)
+
+
 class _PreparedWeights:
-    """Per-module cache of the kernel-specific weight blob (and the OIHW weight_q tensor)."""
+    """Per-module cache of the kernel-specific weight blob (and the OIHW weight_q tensor).  The blob is written on the
+    stream that missed the cache; a hit from another stream (streams.forward_image_groups) waits for it there."""
 
     def __init__(self):
-        self.key = None
-        self.blob = None
-        self.weight_q = None
+        self.invalidate()
 
     def invalidate(self):
         self.key = None
         self.blob = None
         self.weight_q = None
+        self.stream = None    # handle of the stream that wrote the blob
+        self.ready = None     # event recorded there after the prepare (_ready_event)
+        self.synced = set()   # handles of the other streams that have waited on `ready`
 
-    def get(self, L, desc, weight, want_weight_q, cache=True, kernel=None):
+    def get(self, L, desc, weight, want_weight_q, cache=True, kernel=None, stream=None):
+        """The prepared blob, usable on `stream` (default: the current stream of the weight's device)."""
+        stream = stream if stream is not None else torch.cuda.current_stream(weight.device)
         key = (weight.device, weight.data_ptr(), weight._version, tuple(weight.shape), desc.qbits,
                desc.kw_scale, kernel if kernel is not None else L.slfp_conv2d_kernel_name(ctypes.byref(desc)))
-        if not cache or key != self.key or self.blob is None or (want_weight_q and self.weight_q is None):
+        h = stream.cuda_stream
+        if (not cache or key != self.key or self.blob is None or (want_weight_q and self.weight_q is None)
+                or (h != self.stream and self.ready is None)):
             nbytes = L.slfp_conv2d_wprep_bytes(ctypes.byref(desc))
             w = weight.detach()
             w = w if w.is_contiguous() else w.contiguous()  # OIHW
             blob = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
             wq = torch.empty_like(w) if want_weight_q else None
             _lib.check(L.slfp_conv2d_prepare_weights(ctypes.byref(desc), w.data_ptr(), blob.data_ptr(),
-                                                     wq.data_ptr() if wq is not None else None,
-                                                     _stream_handle(weight)))
+                                                     wq.data_ptr() if wq is not None else None, h))
             self.key, self.blob, self.weight_q = key, blob, wq
+            self.stream, self.ready, self.synced = h, _ready_event(stream, cache), set()
+        elif h != self.stream:
+            _hit_from_other_stream(self.blob, self.ready, self.synced, stream)
         return self.blob
 
 
@@ -208,8 +239,9 @@ def _hip_conv2d(mod, x, weight, bias, cache_ok=False):
         mod._plans[pkey] = plan
     d = plan.desc
     with _on_device(x.device):
+        stream = torch.cuda.current_stream(x.device)
         # cache the prepared weights only where they cannot change unseen: inference (see the module docstring)
-        blob = mod._prep.get(L, d, weight, want_weight_q=options.eager_stash, cache=cache_ok, kernel=plan.kernel)
+        blob = mod._prep.get(L, d, weight, want_weight_q=options.eager_stash, cache=cache_ok, kernel=plan.kernel, stream=stream)
         y = torch.empty((N, mod.out_channels, plan.ho, plan.wo), dtype=torch.float32, device=x.device,
                         memory_format=torch.channels_last if nhwc_out else torch.contiguous_format)
         ws = _workspace(x.device, plan.ws_bytes) if plan.ws_bytes else None
@@ -231,7 +263,7 @@ def _hip_conv2d(mod, x, weight, bias, cache_ok=False):
                                           ps.data_ptr() if ps is not None else None,
                                           psh.data_ptr() if psh is not None else None, int(relu), y.data_ptr(),
                                           xq.data_ptr() if xq is not None else None,
-                                          ws.data_ptr() if ws is not None else None, _stream_handle(x)))
+                                          ws.data_ptr() if ws is not None else None, stream.cuda_stream))
     mod._last_kernel = plan.kernel
     mod._last_input = x.detach()
     mod._input_q = xq
@@ -294,7 +326,8 @@ def _hip_conv2d_codes(mod, x, weight, bias):
         return hip_encode(y, out[0], _act_fmt(out[1])) if out is not None else y
     d = plan.desc
     with _on_device(x.device):
-        blob = mod._prep.get(L, d, weight, want_weight_q=False, cache=True, kernel=plan.kernel)
+        stream = torch.cuda.current_stream(x.device)
+        blob = mod._prep.get(L, d, weight, want_weight_q=False, cache=True, kernel=plan.kernel, stream=stream)
         y = torch.empty((N, mod.out_channels, plan.ho, plan.wo), dtype=torch.uint8 if out is not None else torch.float32,
                         device=x.device, memory_format=torch.channels_last)
         b = None
@@ -313,7 +346,7 @@ def _hip_conv2d_codes(mod, x, weight, bias):
                                               b.data_ptr() if b is not None else None,
                                               ps.data_ptr() if ps is not None else None,
                                               psh.data_ptr() if psh is not None else None, int(relu), y.data_ptr(),
-                                              ws.data_ptr() if ws is not None else None, _stream_handle(x)))
+                                              ws.data_ptr() if ws is not None else None, stream.cuda_stream))
     mod._last_kernel = plan.kernel + ("+codes_in" if x_codes else "") + ("+codes_out" if out is not None else "")
     if x_codes:
         mod._last_input, mod._last_codes = None, x.detach()
@@ -429,6 +462,21 @@ class _SlfpConv2dFn(torch.autograd.Function):
         return gx, gw, gb, None, None
 
 
+def mark_grouped_stash(model):
+    """Called by streams.forward_image_groups once all groups have run: every module's stash now holds the last group's
+    slice of the batch only, so `input_q` raises until the module's next ordinary forward.  (Reads inside a group's own
+    forward, as the reference's CIFAR nets do, see that group's slice.)"""
+    for m in model.modules():
+        if "_grouped_stash" in m.__dict__:
+            m.__dict__["_grouped_stash"] = True
+
+
+def _check_stash(mod):
+    if mod._grouped_stash:
+        raise RuntimeError(f"{type(mod).__name__}.input_q: the last forward ran as image groups (streams.forward_image_groups), "
+                           "so the stash holds one group's slice of the batch only; run an ordinary forward to read it")
+
+
 def _apply_post_composite(out, post):
     """The fused epilogue written with stock ATen ops (q_bit == 32 passthrough only)."""
     if post is None:
@@ -464,11 +512,13 @@ def _conv_class(q_bit, Kw, Ka, bias_default, scaled_bias):
             self._last_codes = None
             self._scaled_bias = scaled_bias
             self.output = None
+            self._grouped_stash = False   # the stash is one image group's (mark_grouped_stash)
 
         # -- the reference stores these on every forward (utils/conv2d_func.py:21-22);
         #    here they are computed on first access after a forward.
         @property
         def input_q(self):
+            _check_stash(self)
             if self.q_bit == 32:
                 return self._input_q
             if self._input_q is None and self._last_input is not None:
@@ -500,6 +550,8 @@ def _conv_class(q_bit, Kw, Ka, bias_default, scaled_bias):
             return super(Conv2d_Q, self).train(mode)
 
         def forward(self, input, order=None):
+            if self._grouped_stash:
+                self._grouped_stash = False
             if self.q_bit == 32:
                 # identity quantizers (utils/sfp_quant.py:11-12, :60-61): stock ATen, any device
                 self._input_q = input / self.Ka
@@ -577,16 +629,19 @@ def _hip_linear(mod, x, weight, bias, cache_ok=False):
         # utils/conv2d_func.py:62: AlexNet's 9216x4096 / VGG-16's 25088x4096 layers make that the
         # dominant cost of their classifiers)
         key = (w.device, w.data_ptr(), weight._version, tuple(w.shape), mod.q_bit, kw, options.mfma_passes)
-        cache = mod.__dict__.get("_lin_prep")
-        if cache is None or cache[0] != key or not cache_ok:   # see the module docstring
+        stream = torch.cuda.current_stream(x.device)
+        h = stream.cuda_stream
+        cache = mod.__dict__.get("_lin_prep")   # (key, blob, preparing stream, ready event, synced streams): _PreparedWeights
+        if cache is None or cache[0] != key or not cache_ok or (h != cache[2] and cache[3] is None):   # see the module docstring
             blob = torch.empty(max(L.slfp_linear_workspace_bytes(1, I, O), 16), dtype=torch.uint8, device=x.device)
             _lib.check(L.slfp_linear_prepare_weights(w.data_ptr(), blob.data_ptr(), I, O, kw, mod.q_bit,
-                                                     options.mfma_passes, _stream_handle(x)))
-            cache = (key, blob)
+                                                     options.mfma_passes, h))
+            cache = (key, blob, h, _ready_event(stream, cache_ok), set())
             mod.__dict__["_lin_prep"] = cache
+        elif h != cache[2]:
+            _hit_from_other_stream(cache[1], cache[3], cache[4], stream)
         _lib.check(L.slfp_linear_fwd_prepared(x2.data_ptr(), cache[1].data_ptr(), b.data_ptr() if b is not None else None,
-                                              y.data_ptr(), B, I, O, ka, kw, mod.q_bit, options.mfma_passes,
-                                              _stream_handle(x)))
+                                              y.data_ptr(), B, I, O, ka, kw, mod.q_bit, options.mfma_passes, h))
     return y.reshape(*lead, O)
 
 
@@ -653,12 +708,14 @@ def linear_Q(q_bit, Kw, Ka):
             self._weight_q = None
             self.bias_q = None
             self._last_bwd_kernel = None
+            self._grouped_stash = False   # the stash is one image group's (mark_grouped_stash)
 
         # The reference stores input_q / weight_q / bias_q on every forward (utils/conv2d_func.py:60-64) and its nets
         # read them back afterwards (nets_cifar/mobilenetv1.py:169-170, resnet50.py:353-354, alexnet.py:107-114);
         # here the two quantized tensors are computed on first access after a forward.
         @property
         def input_q(self):
+            _check_stash(self)
             if self.q_bit != 32 and self._input_q is None and self._last_input is not None:
                 fmt = _lib.FMT_ACT8 if self.q_bit == 8 else _lib.FMT_SFP7
                 self._input_q = hip_quantize(self._last_input, _f32(self.Ka), fmt)
@@ -679,6 +736,8 @@ def linear_Q(q_bit, Kw, Ka):
             return super(Linear_Q, self).train(mode)
 
         def forward(self, input):
+            if self._grouped_stash:
+                self._grouped_stash = False
             if self.q_bit == 32:
                 self._input_q = input / self.Ka
                 self._weight_q = self.weight / self.Kw

@@ -201,7 +201,6 @@ class DwPwBlock(nn.Module):
     def forward(self, x):
         from . import _lib
         from .conv2d_func import _f32, _scalar_scale, options
-        from .sfp_quant import _stream_handle
         dw, pw = self.dw, self.pw
         ok = (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)
               and not self.training and not torch.is_grad_enabled() and options.mfma_passes in (_lib.MFMA_DEFAULT, _lib.MFMA_F16X1)
@@ -232,8 +231,9 @@ class DwPwBlock(nn.Module):
             if not L.slfp_dwpw_supported(ctypes.byref(d1), ctypes.byref(d2)):
                 self._last_kernel = None
                 return pw(dw(x))
-            b1 = dw._prep.get(L, d1, dw.weight, want_weight_q=False, cache=True)
-            b2 = pw._prep.get(L, d2, pw.weight, want_weight_q=False, cache=True)
+            stream = torch.cuda.current_stream(x.device)
+            b1 = dw._prep.get(L, d1, dw.weight, want_weight_q=False, cache=True, stream=stream)
+            b2 = pw._prep.get(L, d2, pw.weight, want_weight_q=False, cache=True, stream=stream)
             s1, h1, f1 = dw._post
             s2, h2, f2 = pw._post
             if s1.device != x.device:
@@ -250,10 +250,13 @@ class DwPwBlock(nn.Module):
             _lib.check(L.slfp_dwpw_fwd(ctypes.byref(d1), ctypes.byref(d2), x.data_ptr(), b1.data_ptr(), s1.data_ptr(), h1.data_ptr(),
                                        int(f1) & 1, b2.data_ptr(), bias2.data_ptr() if bias2 is not None else None,
                                        s2.data_ptr() if s2 is not None else None, h2.data_ptr() if s2 is not None else None,
-                                       int(f2) & 1, y.data_ptr(), _stream_handle(x)))
+                                       int(f2) & 1, y.data_ptr(), stream.cuda_stream))
         self._last_kernel = "dwpw_fused_f16x1" if dw.q_bit == 8 else "dwpw_fused_f16_exact"
         dw._last_input, dw._input_q = x.detach(), None
         pw._last_input, pw._input_q = None, None   # the pointwise input never exists as a tensor
+        for m in (dw, pw):
+            if m._grouped_stash:
+                m._grouped_stash = False
         return y
 
 

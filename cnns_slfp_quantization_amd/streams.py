@@ -19,6 +19,8 @@ N / G images than at N: logits can differ in the last bits although every Conv2d
 The reference has nothing comparable (one CUDA stream, utils/conv2d_func.py:20-25 is called layer by layer on the whole batch)."""
 import torch
 
+from .conv2d_func import mark_grouped_stash
+
 _side = {}
 
 
@@ -38,19 +40,24 @@ def forward_image_groups(model, x, groups=2, streams=None):
     do -- 107 k instead of 126 k images/s); the first two streams a process creates have always landed on different queues.  `x`: a ROCm ('cuda') tensor with the
     batch in dimension 0; the model must treat images independently (inference: eval-mode BatchNorm).  The caller's current
     stream waits for all groups before the result is returned.  Returns the concatenated outputs (a tensor, or a tuple of
-    tensors if the model returns a tuple)."""
+    tensors if the model returns a tuple).  Afterwards each module's `input_q` raises until its next ordinary forward: the
+    stash would hold the last group's slice of the batch only."""
     if not x.is_cuda:
         raise TypeError("forward_image_groups: expected a ROCm ('cuda') tensor")
     n = x.shape[0]
     groups = max(1, min(int(groups), n))
+    if streams is not None and len(streams) < groups:
+        raise ValueError(f"forward_image_groups: {groups} image groups need {groups} streams, got {len(streams)}")
     if groups == 1:
         return model(x)
+    streams = streams if streams is not None else _streams(x.device, groups)
     cur = torch.cuda.current_stream(x.device)
     ready = torch.cuda.Event()
     ready.record(cur)
     bounds = [(n * g) // groups for g in range(groups + 1)]
     outs, done = [], []
-    for g, st in enumerate(streams if streams is not None else _streams(x.device, groups)):
+    for g in range(groups):
+        st = streams[g]
         st.wait_event(ready)                       # x (and the weights) are complete on the caller's stream
         with torch.cuda.stream(st):
             xg = x[bounds[g]:bounds[g + 1]]
@@ -59,6 +66,7 @@ def forward_image_groups(model, x, groups=2, streams=None):
             ev = torch.cuda.Event()
             ev.record(st)
             done.append(ev)
+    mark_grouped_stash(model)
     for ev in done:
         cur.wait_event(ev)
     for o in outs:

@@ -280,52 +280,46 @@ def _finetune_model():
     return torch.nn.Sequential(*layers)
 
 
-def test_finetune_mobilenetv1_cifar_matches_composite():
-    """Grads of every parameter agree with the composite; after 3 NormalSGD steps the losses agree.  A quantized net is
-    discontinuous in its weights, so two runs whose gradients differ in the last bits drift apart by a few weight codes
-    per step: the bar is 1e-3 relative, or 3x the drift of a control run (the composite with its gradients scaled by
-    1 +- 2^-20, i.e. about the HIP path's summation-order difference) where that is larger."""
+def test_finetune_mobilenetv1_cifar_every_step_matches_composite():
+    """Three NormalSGD steps of a fine-tune on the HIP backward.  At every step the composite runs on the same weights
+    first: the losses are bit-identical (one forward path) and every parameter's gradient agrees with the composite's.
+    The two trajectories are not run apart and compared: the net is discontinuous in its weights, and the composite's own
+    MIOpen gradients change in the last bits from run to run, which moved its third-step loss by up to 1 % between
+    repeats of the same process; that spread is larger than any bar such a comparison could hold the HIP path to."""
     torch.manual_seed(0)
-    base = _finetune_model()
+    m = _finetune_model().to(DEV).to(memory_format=torch.channels_last)
     x = torch.randn(32, 3, 32, 32).to(DEV).contiguous(memory_format=torch.channels_last)
     y = torch.randint(0, 100, (32,)).to(DEV)
     loss_fn = torch.nn.CrossEntropyLoss()
-    grads, losses, models = {}, {}, {}
-    for mode in ("composite", "hip", "control"):
-        cf.options.backward = "hip" if mode == "hip" else "composite"
-        m = _finetune_model()
-        m.load_state_dict(base.state_dict())
-        m = m.to(DEV).to(memory_format=torch.channels_last)
-        loss_fn(m(x), y).backward()
-        grads[mode] = [p.grad.detach().clone() for p in m.parameters()]
-        kinds = [mod._last_bwd_kernel for mod in m.modules() if hasattr(mod, "_last_bwd_kernel")]
-        if mode == "hip":
-            assert kinds[0] == "composite" and all(k != "composite" for k in kinds[1:]), kinds
-        m.zero_grad(set_to_none=True)
-        opt = O.NormalSGD(m.parameters(), lr=1e-3, momentum=0.9)
-        gen = torch.Generator(device=DEV).manual_seed(1)
-        losses[mode] = []
-        for _ in range(3):
+    names = [n for n, _ in m.named_parameters()]
+    opt = O.NormalSGD(m.parameters(), lr=1e-3, momentum=0.9)
+    running = [b.clone() for b in m.buffers()]
+    losses = []
+    for step in range(3):
+        grads, loss = {}, {}
+        for mode in ("composite", "hip"):
+            cf.options.backward = mode
+            for b, r in zip(m.buffers(), running):   # both passes see the same BatchNorm state
+                b.copy_(r)
             opt.zero_grad(set_to_none=True)
-            loss = loss_fn(m(x), y)
-            loss.backward()
-            if mode == "control":
-                for p in m.parameters():
-                    r = torch.rand(p.grad.shape, generator=gen, device=DEV)
-                    p.grad.mul_(torch.where(r < 0.5, 1 - 2.0 ** -20, 1 + 2.0 ** -20))
-            opt.step()
-            losses[mode].append(loss.item())
-        models[mode] = m
-    names = [n for n, _ in base.named_parameters()]
-    for n, a, b in zip(names, grads["hip"], grads["composite"]):
-        atol = (1e-3 if a.dim() == 1 else 1e-5) * b.abs().max().item()   # BN and bias grads compound over the layers
-        torch.testing.assert_close(a, b, rtol=1e-4, atol=atol, msg=lambda s, n=n: f"{n}: {s}")
+            out = loss_fn(m(x), y)
+            out.backward()
+            grads[mode] = [p.grad.detach().clone() for p in m.parameters()]
+            loss[mode] = out.item()
+            kinds = [mod._last_bwd_kernel for mod in m.modules() if hasattr(mod, "_last_bwd_kernel")]
+            if mode == "hip":
+                assert kinds[0] == "composite" and all(k != "composite" for k in kinds[1:]), kinds
+        running = [b.clone() for b in m.buffers()]
+        assert loss["hip"] == loss["composite"], (step, loss)
+        for n, a, b in zip(names, grads["hip"], grads["composite"]):
+            atol = (1e-3 if a.dim() == 1 else 1e-5) * b.abs().max().item()   # BN and bias grads compound over the layers
+            torch.testing.assert_close(a, b, rtol=1e-4, atol=atol, msg=lambda s, n=n, step=step: f"step {step}, {n}: {s}")
+        opt.step()   # with the HIP backward's gradients
+        losses.append(loss["hip"])
     print("losses", losses)
-    for h, c, k in zip(losses["hip"], losses["composite"], losses["control"]):
-        assert abs(h - c) <= max(1e-3 * abs(c), 3 * abs(k - c)), losses
+    assert all(np.isfinite(losses))
     # DSGD's fused kernel takes every conv weight gradient the HIP backward produced
     cf.options.backward = "hip"
-    m = models["hip"]
     m.zero_grad(set_to_none=True)
     loss_fn(m(x), y).backward()
     convs = [mod for mod in m.modules() if isinstance(mod, torch.nn.Conv2d)]
