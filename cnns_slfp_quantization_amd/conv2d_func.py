@@ -101,6 +101,42 @@ def _pair(v):
     return (int(v[0]), int(v[1])) if isinstance(v, (tuple, list)) else (int(v), int(v))
 
 
+def _act_fmt(q_bit):
+    return _lib.FMT_ACT8 if q_bit == 8 else _lib.FMT_SFP7
+
+
+def _w_fmt(q_bit):
+    return _lib.FMT_W8 if q_bit == 8 else _lib.FMT_SFP7
+
+
+def _conv_desc(mod, shape, nhwc_in=True, nhwc_out=True):
+    """The C ABI's descriptor of module `mod` on an input of `shape` (N, C, H, W) in the given layouts: the one place that
+    spells the struct's fields.  A Linear_Q is the pointwise geometry (1x1, stride 1, no padding) with H = W = 1."""
+    n, c, h, w = shape
+    if isinstance(mod, nn.Linear):
+        c_out, kh, kw, groups = mod.out_features, 1, 1, 1
+        sh = sw = dh = dw = 1
+        ph = pw = 0
+    else:
+        if isinstance(mod.padding, str) or mod.padding_mode != "zeros":
+            raise NotImplementedError("Conv2d_Q (HIP): only explicit zero padding is supported")
+        c_out, groups = mod.out_channels, mod.groups
+        (kh, kw), (sh, sw), (ph, pw), (dh, dw) = mod.kernel_size, _pair(mod.stride), _pair(mod.padding), _pair(mod.dilation)
+    return _lib.ConvDesc(n=n, c_in=c, h=h, w=w, c_out=c_out, kh=kh, kw=kw, stride_h=sh, stride_w=sw, pad_h=ph, pad_w=pw,
+                         dil_h=dh, dil_w=dw, groups=groups,
+                         x_layout=_lib.LAYOUT_NHWC if nhwc_in else _lib.LAYOUT_NCHW,
+                         y_layout=_lib.LAYOUT_NHWC if nhwc_out else _lib.LAYOUT_NCHW,
+                         qbits=mod.q_bit, ka=_f32(_scalar_scale(mod.Ka, "Ka")), kw_scale=_f32(_scalar_scale(mod.Kw, "Kw")),
+                         mfma_passes=options.mfma_passes, reserved=0)
+
+
+def _conv_io(x_codes, out):
+    """slfp_conv2d_fwd_codes' io struct: does the layer read 1-byte codes, and `out` = (Ka, q_bit) of the layer it writes
+    codes for (None: float32 out)."""
+    return _lib.ConvIo(x_codes=1 if x_codes else 0, y_codes=1 if out is not None else 0,
+                       y_ka=_f32(out[0]) if out is not None else 1.0, y_qbits=int(out[1]) if out is not None else 8)
+
+
 def _ready_event(stream, cache):
     """The event that users of a cached blob on other streams wait on: recorded on the preparing stream right after the
     prepare.  None when the blob is not kept for reuse (cache=False) or was written inside a hipGraph capture (an event
@@ -125,35 +161,33 @@ def _hit_from_other_stream(blob, ready, synced, stream):
 
 
 class _PreparedWeights:
-    """Per-module cache of the kernel-specific weight blob (and the OIHW weight_q tensor).  The blob is written on the
-    stream that missed the cache; a hit from another stream (streams.forward_image_groups) waits for it there."""
+    """Per-module cache of the kernel-specific weight blob (and, for a conv, the OIHW weight_q tensor).  The blob is
+    written on the stream that missed the cache; a hit from another stream (streams.forward_image_groups) waits for it
+    there.  What fills the blob is the caller's business (_conv_weights, _hip_linear)."""
 
     def __init__(self):
         self.invalidate()
 
     def invalidate(self):
-        self.key = None
+        self.key = None       # (device, data_ptr, weight._version, shape, q_bit, Kw, kernel or precision)
         self.blob = None
         self.weight_q = None
         self.stream = None    # handle of the stream that wrote the blob
         self.ready = None     # event recorded there after the prepare (_ready_event)
         self.synced = set()   # handles of the other streams that have waited on `ready`
 
-    def get(self, L, desc, weight, want_weight_q, cache=True, kernel=None, stream=None):
-        """The prepared blob, usable on `stream` (default: the current stream of the weight's device)."""
-        stream = stream if stream is not None else torch.cuda.current_stream(weight.device)
-        key = (weight.device, weight.data_ptr(), weight._version, tuple(weight.shape), desc.qbits,
-               desc.kw_scale, kernel if kernel is not None else L.slfp_conv2d_kernel_name(ctypes.byref(desc)))
+    @property
+    def weight_version(self):
+        """`weight._version` of the cached blob (None: nothing cached)."""
+        return None if self.key is None else self.key[2]
+
+    def get(self, key, stream, cache, make, want_weight_q=False):
+        """The prepared blob for `key`, usable on `stream`.  On a miss -- and always with cache=False -- make(stream handle)
+        allocates and fills a new one and returns (blob, weight_q or None)."""
         h = stream.cuda_stream
         if (not cache or key != self.key or self.blob is None or (want_weight_q and self.weight_q is None)
                 or (h != self.stream and self.ready is None)):
-            nbytes = L.slfp_conv2d_wprep_bytes(ctypes.byref(desc))
-            w = weight.detach()
-            w = w if w.is_contiguous() else w.contiguous()  # OIHW
-            blob = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
-            wq = torch.empty_like(w) if want_weight_q else None
-            _lib.check(L.slfp_conv2d_prepare_weights(ctypes.byref(desc), w.data_ptr(), blob.data_ptr(),
-                                                     wq.data_ptr() if wq is not None else None, h))
+            blob, wq = make(h)
             self.key, self.blob, self.weight_q = key, blob, wq
             self.stream, self.ready, self.synced = h, _ready_event(stream, cache), set()
         elif h != self.stream:
@@ -161,12 +195,78 @@ class _PreparedWeights:
         return self.blob
 
 
-class _Plan:
-    """What one (module, input shape, layout, scales, precision) combination resolves to in the C ABI."""
-    __slots__ = ("desc", "ho", "wo", "ws_bytes", "kernel", "io", "codes_ok")
+def _conv_weights(mod, desc, weight, stream, cache, kernel=None, want_weight_q=False):
+    """Conv2d_Q's prepared weight blob for `desc` on `stream`, through the module's cache."""
+    def make(h):
+        L = _lib.load()
+        w = weight.detach()
+        w = w if w.is_contiguous() else w.contiguous()  # OIHW
+        blob = torch.empty(L.slfp_conv2d_wprep_bytes(ctypes.byref(desc)), dtype=torch.uint8, device=weight.device)
+        wq = torch.empty_like(w) if want_weight_q else None
+        _lib.check(L.slfp_conv2d_prepare_weights(ctypes.byref(desc), w.data_ptr(), blob.data_ptr(),
+                                                 wq.data_ptr() if wq is not None else None, h))
+        return blob, wq
 
-    def __init__(self, desc, ho, wo, ws_bytes, kernel):
-        self.desc, self.ho, self.wo, self.ws_bytes, self.kernel = desc, ho, wo, ws_bytes, kernel
+    key = (weight.device, weight.data_ptr(), weight._version, weight.shape, desc.qbits, desc.kw_scale,
+           kernel if kernel is not None else _lib.load().slfp_conv2d_kernel_name(ctypes.byref(desc)))
+    return mod._prep.get(key, stream, cache, make, want_weight_q)
+
+
+class _Plan:
+    """What one (module, input shape, layout, scales, precision) combination resolves to in the C ABI; for the code path
+    also its io struct and whether libslfp_hip has a kernel for the combination."""
+    __slots__ = ("desc", "y_shape", "ws_bytes", "kernel", "io", "codes_ok")
+
+    def __init__(self, desc, y_shape, ws_bytes, kernel):
+        self.desc, self.y_shape, self.ws_bytes, self.kernel = desc, y_shape, ws_bytes, kernel
+        self.io, self.codes_ok = None, False
+
+
+def _plan(mod, x, weight, nhwc_in, nhwc_out, codes=None, bias=None):
+    """Everything that depends only on (module geometry, input shape, layouts, scales, precision) is computed once per
+    distinct key and kept on the module: descriptor, output shape, workspace size, kernel name.  codes: None for the
+    float32 interface, ("codes", does x hold codes, mod._code_out) for slfp_conv2d_fwd_codes."""
+    shape = x.shape
+    key = (codes, shape, nhwc_in, nhwc_out, _scale_key(mod.Ka, "Ka"), _scale_key(mod.Kw, "Kw"), options.mfma_passes,
+           mod.stride, mod.padding, mod.dilation, weight.shape)
+    plan = mod._plans.get(key) if options.plan_cache else None
+    if plan is None:
+        L = _lib.load()
+        d = _conv_desc(mod, shape, nhwc_in, nhwc_out)
+        if shape[1] != mod.in_channels:
+            raise RuntimeError(f"Given groups={mod.groups}, weight of size {list(weight.shape)}, expected input"
+                               f"{list(shape)} to have {mod.in_channels} channels, but got {shape[1]} channels instead")
+        ho, wo = ctypes.c_int64(), ctypes.c_int64()
+        _lib.check(L.slfp_conv2d_out_shape(ctypes.byref(d), ctypes.byref(ho), ctypes.byref(wo)))
+        plan = _Plan(d, (d.n, d.c_out, ho.value, wo.value), L.slfp_conv2d_workspace_bytes(ctypes.byref(d)),
+                     L.slfp_conv2d_kernel_name(ctypes.byref(d)).decode())
+        if codes is not None:
+            plan.io = _conv_io(codes[1], codes[2])
+            flags = int(mod._post[2]) if mod._post is not None else 0
+            plan.codes_ok = bool(L.slfp_conv2d_codes_supported(ctypes.byref(d), ctypes.byref(plan.io),
+                                                               1 if bias is not None else 0, flags))
+            if not plan.codes_ok:   # the layer goes through the float32 interface, whose own plan sizes its workspace
+                plan.ws_bytes = 0
+        if len(mod._plans) >= 64:   # a net fed ever-changing shapes: do not grow without bound
+            mod._plans.clear()
+        mod._plans[key] = plan
+    return plan
+
+
+def _epilogue_args(mod, bias, device):
+    """(bias or None, post scale, post shift, flags) as the kernels' epilogue takes them on `device`.  mod._post is the
+    (scale, shift, flags) set by fusion.fuse_bn_relu: eval-BN (+ layerout) + ReLU in the epilogue; its two vectors are
+    moved to the device once."""
+    if bias is not None:
+        bias = bias.detach()
+        bias = bias if bias.is_contiguous() else bias.contiguous()
+    if mod._post is None:
+        return bias, None, None, 0
+    ps, psh, flags = mod._post
+    if ps is not None and ps.device != device:
+        ps, psh = ps.to(device), psh.to(device)
+        mod._post = (ps, psh, flags)
+    return bias, ps, psh, int(flags)
 
 
 _workspaces = {}
@@ -204,74 +304,32 @@ def _hip_conv2d(mod, x, weight, bias, cache_ok=False):
         x = x.unsqueeze(0)
     if x.dim() != 4:
         raise RuntimeError(f"Expected 3D (unbatched) or 4D (batched) input to conv2d, but got input of size: {list(x.shape)}")
-    if isinstance(mod.padding, str) or mod.padding_mode != "zeros":
-        raise NotImplementedError("Conv2d_Q (HIP): only explicit zero padding is supported")
     L = _lib.load()
     nhwc_in = x.is_contiguous(memory_format=torch.channels_last)
     if not nhwc_in and not x.is_contiguous():
         x = x.contiguous()
-    N, C, H, W = x.shape
-    if C != mod.in_channels:
-        raise RuntimeError(f"Given groups={mod.groups}, weight of size {list(weight.shape)}, expected input"
-                           f"{list(x.shape)} to have {mod.in_channels} channels, but got {C} channels instead")
     nhwc_out = nhwc_in or options.output_layout == "nhwc"
-    # Everything that depends only on (module geometry, input shape, layouts, scales, precision) is computed once
-    # per distinct key and kept on the module: descriptor, output shape, workspace size, kernel name.
-    ka, kw_ = _scale_key(mod.Ka, "Ka"), _scale_key(mod.Kw, "Kw")
-    pkey = (N, H, W, nhwc_in, nhwc_out, ka, kw_, options.mfma_passes, mod.stride, mod.padding, mod.dilation, tuple(weight.shape))
-    plan = mod._plans.get(pkey) if options.plan_cache else None
-    if plan is None:
-        sh, sw = _pair(mod.stride)
-        ph, pw = _pair(mod.padding)
-        dh, dw = _pair(mod.dilation)
-        d = _lib.ConvDesc(n=N, c_in=C, h=H, w=W, c_out=mod.out_channels, kh=weight.shape[2], kw=weight.shape[3],
-                          stride_h=sh, stride_w=sw, pad_h=ph, pad_w=pw, dil_h=dh, dil_w=dw, groups=mod.groups,
-                          x_layout=_lib.LAYOUT_NHWC if nhwc_in else _lib.LAYOUT_NCHW,
-                          y_layout=_lib.LAYOUT_NHWC if nhwc_out else _lib.LAYOUT_NCHW,
-                          qbits=mod.q_bit, ka=_f32(_scalar_scale(mod.Ka, "Ka")), kw_scale=_f32(_scalar_scale(mod.Kw, "Kw")),
-                          mfma_passes=options.mfma_passes, reserved=0)
-        ho, wo = ctypes.c_int64(), ctypes.c_int64()
-        _lib.check(L.slfp_conv2d_out_shape(ctypes.byref(d), ctypes.byref(ho), ctypes.byref(wo)))
-        plan = _Plan(d, ho.value, wo.value, L.slfp_conv2d_workspace_bytes(ctypes.byref(d)),
-                     L.slfp_conv2d_kernel_name(ctypes.byref(d)).decode())
-        if len(mod._plans) >= 64:   # a net fed ever-changing shapes: do not grow without bound
-            mod._plans.clear()
-        mod._plans[pkey] = plan
+    plan = _plan(mod, x, weight, nhwc_in, nhwc_out)
     d = plan.desc
     with _on_device(x.device):
         stream = torch.cuda.current_stream(x.device)
         # cache the prepared weights only where they cannot change unseen: inference (see the module docstring)
-        blob = mod._prep.get(L, d, weight, want_weight_q=options.eager_stash, cache=cache_ok, kernel=plan.kernel, stream=stream)
-        y = torch.empty((N, mod.out_channels, plan.ho, plan.wo), dtype=torch.float32, device=x.device,
+        blob = _conv_weights(mod, d, weight, stream, cache_ok, plan.kernel, want_weight_q=options.eager_stash)
+        y = torch.empty(plan.y_shape, dtype=torch.float32, device=x.device,
                         memory_format=torch.channels_last if nhwc_out else torch.contiguous_format)
         ws = _workspace(x.device, plan.ws_bytes) if plan.ws_bytes else None
-        b = None
-        if bias is not None:
-            b = bias.detach()
-            b = b if b.is_contiguous() else b.contiguous()
+        b, ps, psh, flags = _epilogue_args(mod, bias, x.device)
         xq = torch.empty_like(x) if options.eager_stash else None
-        post = getattr(mod, "_post", None)  # (scale, shift, flags) set by fusion.fuse_bn_relu: eval-BN (+ layerout) + ReLU in the epilogue
-        ps = psh = None
-        relu = 0
-        if post is not None:
-            ps, psh, relu = post
-            if ps is not None and ps.device != x.device:
-                ps, psh = ps.to(x.device), psh.to(x.device)
-                mod._post = (ps, psh, relu)
         _lib.check(L.slfp_conv2d_fwd_post(ctypes.byref(d), x.data_ptr(), blob.data_ptr(),
                                           b.data_ptr() if b is not None else None,
                                           ps.data_ptr() if ps is not None else None,
-                                          psh.data_ptr() if psh is not None else None, int(relu), y.data_ptr(),
+                                          psh.data_ptr() if psh is not None else None, flags, y.data_ptr(),
                                           xq.data_ptr() if xq is not None else None,
                                           ws.data_ptr() if ws is not None else None, stream.cuda_stream))
     mod._last_kernel = plan.kernel
     mod._last_input = x.detach()
     mod._input_q = xq
     return y.squeeze(0) if squeeze else y
-
-
-def _act_fmt(q_bit):
-    return _lib.FMT_ACT8 if q_bit == 8 else _lib.FMT_SFP7
 
 
 def _hip_conv2d_codes(mod, x, weight, bias):
@@ -285,67 +343,29 @@ def _hip_conv2d_codes(mod, x, weight, bias):
         _require_gpu_f32(x, "Conv2d_Q")
     elif not x.is_cuda:
         raise RuntimeError("Conv2d_Q: code tensors live on the ROCm device")
+
+    def float32_interface():
+        y = _hip_conv2d(mod, hip_decode(x, _act_fmt(mod.q_bit)) if x_codes else x, weight, bias, cache_ok=True)
+        return hip_encode(y, out[0], _act_fmt(out[1])) if out is not None else y
+
     if x.dim() != 4 or not x.is_contiguous(memory_format=torch.channels_last):
-        # the code path is NHWC only; anything else takes the float32 interface
-        x32 = hip_decode(x, _act_fmt(mod.q_bit)) if x_codes else x
-        y = _hip_conv2d(mod, x32, weight, bias, cache_ok=True)
-        return hip_encode(y, out[0], _act_fmt(out[1])) if out is not None else y
-    L = _lib.load()
-    N, C, H, W = x.shape
-    if C != mod.in_channels:
-        raise RuntimeError(f"Given groups={mod.groups}, weight of size {list(weight.shape)}, expected input"
-                           f"{list(x.shape)} to have {mod.in_channels} channels, but got {C} channels instead")
-    ka, kw_ = _scale_key(mod.Ka, "Ka"), _scale_key(mod.Kw, "Kw")
-    pkey = ("codes", N, H, W, x_codes, out, ka, kw_, options.mfma_passes, mod.stride, mod.padding, mod.dilation, tuple(weight.shape))
-    plan = mod._plans.get(pkey)
-    if plan is None:
-        sh, sw = _pair(mod.stride)
-        ph, pw = _pair(mod.padding)
-        dh, dw = _pair(mod.dilation)
-        d = _lib.ConvDesc(n=N, c_in=C, h=H, w=W, c_out=mod.out_channels, kh=weight.shape[2], kw=weight.shape[3],
-                          stride_h=sh, stride_w=sw, pad_h=ph, pad_w=pw, dil_h=dh, dil_w=dw, groups=mod.groups,
-                          x_layout=_lib.LAYOUT_NHWC, y_layout=_lib.LAYOUT_NHWC, qbits=mod.q_bit,
-                          ka=_f32(_scalar_scale(mod.Ka, "Ka")), kw_scale=_f32(_scalar_scale(mod.Kw, "Kw")),
-                          mfma_passes=options.mfma_passes, reserved=0)
-        ho, wo = ctypes.c_int64(), ctypes.c_int64()
-        _lib.check(L.slfp_conv2d_out_shape(ctypes.byref(d), ctypes.byref(ho), ctypes.byref(wo)))
-        io = _lib.ConvIo(x_codes=1 if x_codes else 0, y_codes=1 if out is not None else 0,
-                         y_ka=_f32(out[0]) if out is not None else 1.0, y_qbits=int(out[1]) if out is not None else 8)
-        post = mod._post
-        flags = int(post[2]) if post is not None else 0
-        ok = bool(L.slfp_conv2d_codes_supported(ctypes.byref(d), ctypes.byref(io), 1 if bias is not None else 0, flags))
-        plan = _Plan(d, ho.value, wo.value, L.slfp_conv2d_workspace_bytes(ctypes.byref(d)) if ok else 0,
-                     L.slfp_conv2d_kernel_name(ctypes.byref(d)).decode())
-        plan.io, plan.codes_ok = io, ok
-        if len(mod._plans) >= 64:
-            mod._plans.clear()
-        mod._plans[pkey] = plan
+        return float32_interface()   # the code path is NHWC only; anything else takes the float32 interface
+    plan = _plan(mod, x, weight, True, True, ("codes", x_codes, out), bias)
     if not plan.codes_ok:
-        x32 = hip_decode(x, _act_fmt(mod.q_bit)) if x_codes else x
-        y = _hip_conv2d(mod, x32, weight, bias, cache_ok=True)
-        return hip_encode(y, out[0], _act_fmt(out[1])) if out is not None else y
+        return float32_interface()
+    L = _lib.load()
     d = plan.desc
     with _on_device(x.device):
         stream = torch.cuda.current_stream(x.device)
-        blob = mod._prep.get(L, d, weight, want_weight_q=False, cache=True, kernel=plan.kernel, stream=stream)
-        y = torch.empty((N, mod.out_channels, plan.ho, plan.wo), dtype=torch.uint8 if out is not None else torch.float32,
-                        device=x.device, memory_format=torch.channels_last)
-        b = None
-        if bias is not None:
-            b = bias.detach()
-            b = b if b.is_contiguous() else b.contiguous()
-        ps = psh = None
-        relu = 0
-        if mod._post is not None:
-            ps, psh, relu = mod._post
-            if ps is not None and ps.device != x.device:
-                ps, psh = ps.to(x.device), psh.to(x.device)
-                mod._post = (ps, psh, relu)
+        blob = _conv_weights(mod, d, weight, stream, True, plan.kernel)
+        y = torch.empty(plan.y_shape, dtype=torch.uint8 if out is not None else torch.float32, device=x.device,
+                        memory_format=torch.channels_last)
+        b, ps, psh, flags = _epilogue_args(mod, bias, x.device)
         ws = _workspace(x.device, plan.ws_bytes) if plan.ws_bytes else None   # dense k x k layers: the fp16 operand copy
         _lib.check(L.slfp_conv2d_fwd_codes_ws(ctypes.byref(d), ctypes.byref(plan.io), x.data_ptr(), blob.data_ptr(),
                                               b.data_ptr() if b is not None else None,
                                               ps.data_ptr() if ps is not None else None,
-                                              psh.data_ptr() if psh is not None else None, int(relu), y.data_ptr(),
+                                              psh.data_ptr() if psh is not None else None, flags, y.data_ptr(),
                                               ws.data_ptr() if ws is not None else None, stream.cuda_stream))
     mod._last_kernel = plan.kernel + ("+codes_in" if x_codes else "") + ("+codes_out" if out is not None else "")
     if x_codes:
@@ -361,21 +381,36 @@ def _aligned(t):
     return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
-def _hip_backward(mod, x, w, gy, desc, need_gx, need_gw, need_gb):
-    """One slfp_conv2d_bwd call on dense, aligned NCHW / NHWC operands (the layouts `desc` names).  Returns (gx, gw, gb)
-    with None for what was not asked; gx has x's memory format, gw is contiguous like `w`."""
+def _hip_backward(mod, desc, x, w, gy, needs):
+    """One slfp_conv2d_bwd call on dense NCHW / NHWC operands (the layouts `desc` names), or None where the library does
+    not cover the layer.  needs = (gx, gw, gb wanted); returns (gx, gw, gb) with None for what was not asked: gx has x's
+    memory format, gw is contiguous like `w`."""
     L = _lib.load()
+    if not L.slfp_conv2d_bwd_supported(ctypes.byref(desc)):
+        return None
+    need_gx, need_gw, need_gb = needs
+    x, gy = _aligned(x), _aligned(gy)
+    w = w.detach()
+    w = _aligned(w if w.is_contiguous() else w.contiguous())   # OIHW
+    # the bias sum comes with the weight gradient's pass (a frozen weight with a trainable bias still runs it)
+    run_gw = need_gw or need_gb
     gx = torch.empty_like(x) if need_gx else None
-    gw = torch.empty(w.shape, dtype=torch.float32, device=x.device) if need_gw else None
+    gw = torch.empty(w.shape, dtype=torch.float32, device=x.device) if run_gw else None
     gb = torch.empty(desc.c_out, dtype=torch.float32, device=x.device) if need_gb else None
     with _on_device(x.device):
-        nbytes = L.slfp_conv2d_bwd_workspace_bytes(ctypes.byref(desc), int(need_gx), int(need_gw))
+        nbytes = L.slfp_conv2d_bwd_workspace_bytes(ctypes.byref(desc), int(need_gx), int(run_gw))
         ws = _workspace(x.device, nbytes) if nbytes else None
         _lib.check(L.slfp_conv2d_bwd(ctypes.byref(desc), x.data_ptr(), w.data_ptr(), gy.data_ptr(),
                                      gx.data_ptr() if gx is not None else None, gw.data_ptr() if gw is not None else None,
                                      gb.data_ptr() if gb is not None else None, ws.data_ptr() if ws is not None else None,
                                      _stream_handle(x)))
-    return gx, gw, gb
+    mod._last_bwd_kernel = L.slfp_conv2d_bwd_kernel_name(ctypes.byref(desc)).decode()
+    return gx, gw if need_gw else None, gb
+
+
+def _needs(ctx):
+    """(gx, gw, gb) wanted by autograd from a Function whose inputs start with (x, weight, bias)."""
+    return ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
 
 
 def _conv_backward_hip(ctx, gy):
@@ -385,7 +420,7 @@ def _conv_backward_hip(ctx, gy):
     squeeze = x.dim() == 3
     if squeeze:
         x, gy = x.unsqueeze(0), gy.unsqueeze(0)
-    if x.numel() == 0 or gy.numel() == 0 or not x.is_cuda:
+    if x.numel() == 0 or gy.numel() == 0 or not x.is_cuda or isinstance(mod.padding, str):
         return None
     x = x.detach()
     nhwc_x = x.is_contiguous(memory_format=torch.channels_last)
@@ -398,30 +433,10 @@ def _conv_backward_hip(ctx, gy):
     else:   # e.g. the stride-0 gy of out.sum().backward()
         nhwc_y = nhwc_x
         gy = gy.contiguous(memory_format=torch.channels_last if nhwc_y else torch.contiguous_format)
-    N, C, H, W = x.shape
-    sh, sw = _pair(mod.stride)
-    ph, pw = _pair(mod.padding) if not isinstance(mod.padding, str) else (-1, -1)
-    dh, dw = _pair(mod.dilation)
-    d = _lib.ConvDesc(n=N, c_in=C, h=H, w=W, c_out=mod.out_channels, kh=weight.shape[2], kw=weight.shape[3],
-                      stride_h=sh, stride_w=sw, pad_h=ph, pad_w=pw, dil_h=dh, dil_w=dw, groups=mod.groups,
-                      x_layout=_lib.LAYOUT_NHWC if nhwc_x else _lib.LAYOUT_NCHW,
-                      y_layout=_lib.LAYOUT_NHWC if nhwc_y else _lib.LAYOUT_NCHW,
-                      qbits=mod.q_bit, ka=_f32(mod.Ka), kw_scale=_f32(mod.Kw), mfma_passes=options.mfma_passes, reserved=0)
-    L = _lib.load()
-    if ph < 0 or not L.slfp_conv2d_bwd_supported(ctypes.byref(d)):
-        return None
-    need_gx, need_gw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-    need_gb = ctx.has_bias and ctx.needs_input_grad[2]
-    w = weight.detach()
-    w = _aligned(w if w.is_contiguous() else w.contiguous())   # OIHW
-    # the bias sum comes with the weight gradient's pass (a frozen weight with a trainable bias still runs it)
-    gx, gw, gb = _hip_backward(mod, _aligned(x), w, _aligned(gy), d, need_gx, need_gw or need_gb, need_gb)
-    if not need_gw:
-        gw = None
-    mod._last_bwd_kernel = L.slfp_conv2d_bwd_kernel_name(ctypes.byref(d)).decode()
-    if squeeze and gx is not None:
-        gx = gx.squeeze(0)
-    return gx, gw, gb
+    res = _hip_backward(mod, _conv_desc(mod, x.shape, nhwc_x, nhwc_y), x, weight, gy, _needs(ctx))
+    if res is not None and squeeze and res[0] is not None:
+        res = (res[0].squeeze(0),) + res[1:]
+    return res
 
 
 class _SlfpConv2dFn(torch.autograd.Function):
@@ -447,15 +462,13 @@ class _SlfpConv2dFn(torch.autograd.Function):
         mod._last_bwd_kernel = "composite"
         x, weight = ctx.saved_tensors
         ka, kw = _f32(mod.Ka), _f32(mod.Kw)
-        fa = _lib.FMT_ACT8 if mod.q_bit == 8 else _lib.FMT_SFP7
-        fw = _lib.FMT_W8 if mod.q_bit == 8 else _lib.FMT_SFP7
         g = (gy * kw * ka).contiguous()
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
-            wq = hip_quantize(weight.detach().contiguous(), kw, fw)
+            wq = hip_quantize(weight.detach().contiguous(), kw, _w_fmt(mod.q_bit))
             gx = torch.nn.grad.conv2d_input(x.shape, wq, g, mod.stride, mod.padding, mod.dilation, mod.groups) / ka
         if ctx.needs_input_grad[1]:
-            xq = hip_quantize(x.detach().contiguous(), ka, fa)
+            xq = hip_quantize(x.detach().contiguous(), ka, _act_fmt(mod.q_bit))
             gw = torch.nn.grad.conv2d_weight(xq, weight.shape, g, mod.stride, mod.padding, mod.dilation, mod.groups) / kw
         if ctx.has_bias and ctx.needs_input_grad[2]:
             gb = gy.sum(dim=(0, 2, 3)) if ctx.scaled_bias else g.sum(dim=(0, 2, 3))
@@ -522,8 +535,7 @@ def _conv_class(q_bit, Kw, Ka, bias_default, scaled_bias):
             if self.q_bit == 32:
                 return self._input_q
             if self._input_q is None and self._last_input is not None:
-                fmt = _lib.FMT_ACT8 if self.q_bit == 8 else _lib.FMT_SFP7
-                self._input_q = hip_quantize(self._last_input, _f32(self.Ka), fmt)
+                self._input_q = hip_quantize(self._last_input, _f32(self.Ka), _act_fmt(self.q_bit))
             elif self._input_q is None and self._last_codes is not None:
                 # inside a code chain the input arrived already quantized: input_q = decode(codes), bit for bit
                 self._input_q = hip_decode(self._last_codes, _act_fmt(self.q_bit))
@@ -535,10 +547,9 @@ def _conv_class(q_bit, Kw, Ka, bias_default, scaled_bias):
                 return self._weight_q32
             if self._last_input is None and self._last_codes is None:
                 return None
-            stale = self._prep.weight_q is None or self._prep.key is None or self._prep.key[2] != self.weight._version
+            stale = self._prep.weight_q is None or self._prep.weight_version != self.weight._version
             if stale or self.training or torch.is_grad_enabled():   # p.data updates are invisible to _version
-                fmt = _lib.FMT_W8 if self.q_bit == 8 else _lib.FMT_SFP7
-                self._prep.weight_q = hip_quantize(self.weight.detach().contiguous(), _f32(self.Kw), fmt)
+                self._prep.weight_q = hip_quantize(self.weight.detach().contiguous(), _f32(self.Kw), _w_fmt(self.q_bit))
             return self._prep.weight_q
 
         def invalidate(self):
@@ -624,24 +635,21 @@ def _hip_linear(mod, x, weight, bias, cache_ok=False):
         b = b if b.is_contiguous() else b.contiguous()
     y = torch.empty((B, O), dtype=torch.float32, device=x.device)
     ka, kw = _f32(_scalar_scale(mod.Ka, "Ka")), _f32(_scalar_scale(mod.Kw, "Kw"))
-    with torch.cuda.device(x.device):
+
+    def make(h):
+        blob = torch.empty(max(L.slfp_linear_workspace_bytes(1, I, O), 16), dtype=torch.uint8, device=x.device)
+        _lib.check(L.slfp_linear_prepare_weights(w.data_ptr(), blob.data_ptr(), I, O, kw, mod.q_bit, options.mfma_passes, h))
+        return blob, None
+
+    with _on_device(x.device):
         # quantize the weights once per weight version (the reference re-quantizes on every forward,
         # utils/conv2d_func.py:62: AlexNet's 9216x4096 / VGG-16's 25088x4096 layers make that the
-        # dominant cost of their classifiers)
+        # dominant cost of their classifiers); cached only where cache_ok, see the module docstring
         key = (w.device, w.data_ptr(), weight._version, tuple(w.shape), mod.q_bit, kw, options.mfma_passes)
         stream = torch.cuda.current_stream(x.device)
-        h = stream.cuda_stream
-        cache = mod.__dict__.get("_lin_prep")   # (key, blob, preparing stream, ready event, synced streams): _PreparedWeights
-        if cache is None or cache[0] != key or not cache_ok or (h != cache[2] and cache[3] is None):   # see the module docstring
-            blob = torch.empty(max(L.slfp_linear_workspace_bytes(1, I, O), 16), dtype=torch.uint8, device=x.device)
-            _lib.check(L.slfp_linear_prepare_weights(w.data_ptr(), blob.data_ptr(), I, O, kw, mod.q_bit,
-                                                     options.mfma_passes, h))
-            cache = (key, blob, h, _ready_event(stream, cache_ok), set())
-            mod.__dict__["_lin_prep"] = cache
-        elif h != cache[2]:
-            _hit_from_other_stream(cache[1], cache[3], cache[4], stream)
-        _lib.check(L.slfp_linear_fwd_prepared(x2.data_ptr(), cache[1].data_ptr(), b.data_ptr() if b is not None else None,
-                                              y.data_ptr(), B, I, O, ka, kw, mod.q_bit, options.mfma_passes, h))
+        blob = mod._prep.get(key, stream, cache_ok, make)
+        _lib.check(L.slfp_linear_fwd_prepared(x2.data_ptr(), blob.data_ptr(), b.data_ptr() if b is not None else None,
+                                              y.data_ptr(), B, I, O, ka, kw, mod.q_bit, options.mfma_passes, stream.cuda_stream))
     return y.reshape(*lead, O)
 
 
@@ -660,33 +668,18 @@ class _SlfpLinearFn(torch.autograd.Function):
         if options.backward == "hip" and x.is_cuda and x.numel() > 0:
             # the pointwise kernels with rows = the product of the leading dims and H = W = 1
             I, O = x.shape[-1], weight.shape[0]
-            x2 = _aligned(x.detach().reshape(-1, I).contiguous())
-            gy2 = _aligned(gy.reshape(-1, O).contiguous())
-            d = _lib.ConvDesc(n=x2.shape[0], c_in=I, h=1, w=1, c_out=O, kh=1, kw=1, stride_h=1, stride_w=1, pad_h=0, pad_w=0,
-                              dil_h=1, dil_w=1, groups=1, x_layout=_lib.LAYOUT_NHWC, y_layout=_lib.LAYOUT_NHWC,
-                              qbits=mod.q_bit, ka=_f32(mod.Ka), kw_scale=_f32(mod.Kw), mfma_passes=options.mfma_passes,
-                              reserved=0)
-            L = _lib.load()
-            if L.slfp_conv2d_bwd_supported(ctypes.byref(d)):
-                need_gx, need_gw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-                need_gb = ctx.has_bias and ctx.needs_input_grad[2]
-                w = weight.detach()
-                w = _aligned(w if w.is_contiguous() else w.contiguous())
-                gx, gw, gb = _hip_backward(mod, x2, w, gy2, d, need_gx, need_gw or need_gb, need_gb)
-                if not need_gw:
-                    gw = None
-                mod._last_bwd_kernel = L.slfp_conv2d_bwd_kernel_name(ctypes.byref(d)).decode()
-                return (gx.reshape(x.shape) if gx is not None else None), gw, gb, None
+            x2, gy2 = x.detach().reshape(-1, I).contiguous(), gy.reshape(-1, O).contiguous()
+            res = _hip_backward(mod, _conv_desc(mod, (x2.shape[0], I, 1, 1)), x2, weight, gy2, _needs(ctx))
+            if res is not None:
+                return (res[0].reshape(x.shape) if res[0] is not None else None), res[1], res[2], None
         mod._last_bwd_kernel = "composite"
         ka, kw = _f32(mod.Ka), _f32(mod.Kw)
-        fa = _lib.FMT_ACT8 if mod.q_bit == 8 else _lib.FMT_SFP7
-        fw = _lib.FMT_W8 if mod.q_bit == 8 else _lib.FMT_SFP7
         g = gy * kw * ka
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
-            gx = (g @ hip_quantize(weight.detach().contiguous(), kw, fw)) / ka
+            gx = (g @ hip_quantize(weight.detach().contiguous(), kw, _w_fmt(mod.q_bit))) / ka
         if ctx.needs_input_grad[1]:
-            xq = hip_quantize(x.detach().contiguous(), ka, fa)
+            xq = hip_quantize(x.detach().contiguous(), ka, _act_fmt(mod.q_bit))
             gw = (g.reshape(-1, g.shape[-1]).t() @ xq.reshape(-1, xq.shape[-1])) / kw
         if ctx.has_bias and ctx.needs_input_grad[2]:
             gb = gy.reshape(-1, gy.shape[-1]).sum(0)
@@ -703,6 +696,7 @@ def linear_Q(q_bit, Kw, Ka):
             self.quantize_act = act_quantize_func(q_bit=q_bit)
             self.Kw = torch.tensor(Kw)
             self.Ka = torch.tensor(Ka)
+            self._prep = _PreparedWeights()
             self._last_input = None
             self._input_q = None
             self._weight_q = None
@@ -717,19 +711,18 @@ def linear_Q(q_bit, Kw, Ka):
         def input_q(self):
             _check_stash(self)
             if self.q_bit != 32 and self._input_q is None and self._last_input is not None:
-                fmt = _lib.FMT_ACT8 if self.q_bit == 8 else _lib.FMT_SFP7
-                self._input_q = hip_quantize(self._last_input, _f32(self.Ka), fmt)
+                self._input_q = hip_quantize(self._last_input, _f32(self.Ka), _act_fmt(self.q_bit))
             return self._input_q
 
         @property
         def weight_q(self):
             if self.q_bit != 32 and self._weight_q is None and self._last_input is not None:
-                fmt = _lib.FMT_W8 if self.q_bit == 8 else _lib.FMT_SFP7
-                self._weight_q = hip_quantize(self.weight.detach().contiguous(), _f32(self.Kw), fmt)
+                self._weight_q = hip_quantize(self.weight.detach().contiguous(), _f32(self.Kw), _w_fmt(self.q_bit))
             return self._weight_q
 
         def invalidate(self):
-            self.__dict__.pop("_lin_prep", None)
+            """Drop the cached quantized weights (call after changing `weight.data` in place during inference)."""
+            self._prep.invalidate()
 
         def train(self, mode=True):
             self.invalidate()

@@ -200,7 +200,7 @@ class DwPwBlock(nn.Module):
 
     def forward(self, x):
         from . import _lib
-        from .conv2d_func import _f32, _scalar_scale, options
+        from .conv2d_func import _conv_desc, _conv_weights, _epilogue_args, options
         dw, pw = self.dw, self.pw
         ok = (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)
               and not self.training and not torch.is_grad_enabled() and options.mfma_passes in (_lib.MFMA_DEFAULT, _lib.MFMA_F16X1)
@@ -214,43 +214,28 @@ class DwPwBlock(nn.Module):
             self._last_kernel = None
             return pw(dw(x))
         L = _lib.load()
-        N, C, H, W = x.shape
-
-        def desc(m, n, c, h, w):
-            return _lib.ConvDesc(n=n, c_in=c, h=h, w=w, c_out=m.out_channels, kh=m.weight.shape[2], kw=m.weight.shape[3],
-                                 stride_h=m.stride[0], stride_w=m.stride[1], pad_h=m.padding[0], pad_w=m.padding[1], dil_h=1, dil_w=1,
-                                 groups=m.groups, x_layout=_lib.LAYOUT_NHWC, y_layout=_lib.LAYOUT_NHWC, qbits=m.q_bit,
-                                 ka=_f32(_scalar_scale(m.Ka, "Ka")), kw_scale=_f32(_scalar_scale(m.Kw, "Kw")),
-                                 mfma_passes=options.mfma_passes, reserved=0)
-
-        d1 = desc(dw, N, C, H, W)
+        N = x.shape[0]
+        d1 = _conv_desc(dw, x.shape)
         ho, wo = ctypes.c_int64(), ctypes.c_int64()
         with torch.cuda.device(x.device):
             _lib.check(L.slfp_conv2d_out_shape(ctypes.byref(d1), ctypes.byref(ho), ctypes.byref(wo)))
-            d2 = desc(pw, N, dw.out_channels, ho.value, wo.value)
+            d2 = _conv_desc(pw, (N, dw.out_channels, ho.value, wo.value))
             if not L.slfp_dwpw_supported(ctypes.byref(d1), ctypes.byref(d2)):
                 self._last_kernel = None
                 return pw(dw(x))
             stream = torch.cuda.current_stream(x.device)
-            b1 = dw._prep.get(L, d1, dw.weight, want_weight_q=False, cache=True, stream=stream)
-            b2 = pw._prep.get(L, d2, pw.weight, want_weight_q=False, cache=True, stream=stream)
-            s1, h1, f1 = dw._post
-            s2, h2, f2 = pw._post
-            if s1.device != x.device:
-                s1, h1 = s1.to(x.device), h1.to(x.device)
-                dw._post = (s1, h1, f1)
-            if s2 is not None and s2.device != x.device:
-                s2, h2 = s2.to(x.device), h2.to(x.device)
-                pw._post = (s2, h2, f2)
-            bias2 = pw.bias.detach().contiguous() if (pw.bias is not None and getattr(pw, "_scaled_bias", False)) else None
+            b1 = _conv_weights(dw, d1, dw.weight, stream, True)
+            b2 = _conv_weights(pw, d2, pw.weight, stream, True)
+            _, s1, h1, f1 = _epilogue_args(dw, None, x.device)
+            bias2, s2, h2, f2 = _epilogue_args(pw, pw.bias if getattr(pw, "_scaled_bias", False) else None, x.device)
             if pw.bias is not None and bias2 is None:
                 return pw(dw(x))   # conv2d_Q's raw bias is added outside the kernels
             y = torch.empty((N, pw.out_channels, ho.value, wo.value), dtype=torch.float32, device=x.device,
                             memory_format=torch.channels_last)
             _lib.check(L.slfp_dwpw_fwd(ctypes.byref(d1), ctypes.byref(d2), x.data_ptr(), b1.data_ptr(), s1.data_ptr(), h1.data_ptr(),
-                                       int(f1) & 1, b2.data_ptr(), bias2.data_ptr() if bias2 is not None else None,
+                                       f1 & 1, b2.data_ptr(), bias2.data_ptr() if bias2 is not None else None,
                                        s2.data_ptr() if s2 is not None else None, h2.data_ptr() if s2 is not None else None,
-                                       int(f2) & 1, y.data_ptr(), stream.cuda_stream))
+                                       f2 & 1, y.data_ptr(), stream.cuda_stream))
         self._last_kernel = "dwpw_fused_f16x1" if dw.q_bit == 8 else "dwpw_fused_f16_exact"
         dw._last_input, dw._input_q = x.detach(), None
         pw._last_input, pw._input_q = None, None   # the pointwise input never exists as a tensor
@@ -336,6 +321,15 @@ def _poolable(m):
             and (m.dilation == 1 or m.dilation == (1, 1)))
 
 
+def _codes_kernel_exists(m, shape, x_codes, out, flags):
+    """Does libslfp_hip run Conv2d_Q `m` on a channels_last input of `shape` with codes in (x_codes) / codes out for the
+    layer `out` = (Ka, q_bit) describes (None: float32 out), with `flags` in its epilogue?"""
+    from . import _lib
+    from .conv2d_func import _conv_desc, _conv_io
+    d, io = _conv_desc(m, shape), _conv_io(x_codes, out)
+    return bool(_lib.load().slfp_conv2d_codes_supported(ctypes.byref(d), ctypes.byref(io), 1 if m.bias is not None else 0, flags))
+
+
 def link_codes(model, example_input=None):
     """After fuse_bn_relu: wherever a Conv2d_Q's (fused BN + ReLU) output feeds the next Conv2d_Q of an nn.Sequential
     directly (only nn.Identity in between -- nets_imgnet/mobilenetv1.py:24-33 after fusion), link the two: the producer's
@@ -345,8 +339,7 @@ def link_codes(model, example_input=None):
     With `example_input` (a channels_last ROCm batch) only links for which both kernels exist are made (one forward
     records the shapes); without it every candidate is linked and combinations without a kernel run through the float32
     interface plus an encode / decode pass (correct, slower).  Inference only.  Returns the number of links."""
-    from . import _lib
-    from .conv2d_func import _f32, _scalar_scale, options
+    from .conv2d_func import _scalar_scale
     shapes = {}
     if example_input is not None:
         hooks = []
@@ -367,17 +360,7 @@ def link_codes(model, example_input=None):
         shp = shapes.get(m)
         if shp is None or len(shp) != 4:
             return False
-        L = _lib.load()
-        n, c, h, w = shp
-        d = _lib.ConvDesc(n=n, c_in=c, h=h, w=w, c_out=m.out_channels, kh=m.weight.shape[2], kw=m.weight.shape[3],
-                          stride_h=m.stride[0], stride_w=m.stride[1], pad_h=m.padding[0], pad_w=m.padding[1], dil_h=m.dilation[0],
-                          dil_w=m.dilation[1], groups=m.groups, x_layout=_lib.LAYOUT_NHWC, y_layout=_lib.LAYOUT_NHWC, qbits=m.q_bit,
-                          ka=_f32(_scalar_scale(m.Ka, "Ka")), kw_scale=_f32(_scalar_scale(m.Kw, "Kw")),
-                          mfma_passes=options.mfma_passes, reserved=0)
-        io = _lib.ConvIo(x_codes=1 if x_codes else 0, y_codes=1 if out is not None else 0,
-                         y_ka=_f32(out[0]) if out is not None else 1.0, y_qbits=int(out[1]) if out is not None else 8)
-        flags = int(m._post[2]) if m._post is not None else 0
-        return bool(L.slfp_conv2d_codes_supported(ctypes.byref(d), ctypes.byref(io), 1 if m.bias is not None else 0, flags))
+        return _codes_kernel_exists(m, shp, x_codes, out, int(m._post[2]) if m._post is not None else 0)
 
     def eligible(m):
         return (_is_conv_q(m) and m.q_bit in (8, 7) and not m.training and isinstance(m.padding, tuple)
@@ -442,9 +425,7 @@ def link_codes_traced(model, example_input):
     two consumers, and the whole set is VERIFIED: the linked model must reproduce the unlinked output bit for bit on
     `example_input`, otherwise (a functional use of the tensor that hooks cannot see, e.g. a torch.cat) everything is rolled
     back and 0 is returned.  Inference only; unlink_codes undoes it.  Returns the number of links."""
-    import ctypes as _ct
-    from . import _lib
-    from .conv2d_func import _f32, _scalar_scale, options
+    from .conv2d_func import _scalar_scale
     conv_io, relu_io, pool_io, order, keep = {}, [], [], [], []
     hooks = []
     for m in model.modules():
@@ -487,15 +468,7 @@ def link_codes_traced(model, example_input):
         xin = conv_io[m][0]
         if xin.dim() != 4:
             return False
-        n, c, h, w = xin.shape
-        d = _lib.ConvDesc(n=n, c_in=c, h=h, w=w, c_out=m.out_channels, kh=m.weight.shape[2], kw=m.weight.shape[3],
-                          stride_h=m.stride[0], stride_w=m.stride[1], pad_h=m.padding[0], pad_w=m.padding[1], dil_h=m.dilation[0],
-                          dil_w=m.dilation[1], groups=m.groups, x_layout=_lib.LAYOUT_NHWC, y_layout=_lib.LAYOUT_NHWC, qbits=m.q_bit,
-                          ka=_f32(_scalar_scale(m.Ka, "Ka")), kw_scale=_f32(_scalar_scale(m.Kw, "Kw")),
-                          mfma_passes=options.mfma_passes, reserved=0)
-        io = _lib.ConvIo(x_codes=1 if x_codes else 0, y_codes=1 if out is not None else 0,
-                         y_ka=_f32(out[0]) if out is not None else 1.0, y_qbits=int(out[1]) if out is not None else 8)
-        return bool(_lib.load().slfp_conv2d_codes_supported(_ct.byref(d), _ct.byref(io), 1 if m.bias is not None else 0, flags))
+        return _codes_kernel_exists(m, xin.shape, x_codes, out, flags)
 
     cand = {}
     for b in order:

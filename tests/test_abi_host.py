@@ -269,6 +269,63 @@ def test_round2_host_logic_on_cpu():
         _scale_key(torch.tensor([0.1, 0.2]), "Ka")
 
 
+def test_conv_desc_is_the_modules_geometry_and_carries_dilation():
+    """conv2d_func._conv_desc, the one descriptor builder of the module layer: every field equals a hand-written struct for
+    int and tuple geometry, grouped and biased convs, both layouts and a Linear_Q, with the scales cast as ATen casts the
+    0-dim float64 tensors; bad scales and string padding raise.  The dilation reaches slfp_dwpw_supported: a dilated
+    depthwise conv in front of a 1x1 conv is not a pair the one-kernel form runs (DwPwBlock once described it to the
+    library as undilated)."""
+    import utils.conv2d_func as cf
+    from cnns_slfp_quantization_amd.conv2d_func import _conv_desc, options
+    Ka, Kw = np.float64(2.64) / 15.5, np.float64(0.86) / 15.5
+    ka, kw = float(np.float32(Ka)), float(np.float32(Kw))
+    C, Cb = cf.conv2d_Q(8, Kw, Ka), cf.conv2d_Q_bias(8, Kw, Ka)
+    NCHW, NHWC = _lib.LAYOUT_NCHW, _lib.LAYOUT_NHWC
+
+    def want(**f):
+        f.update(qbits=8, ka=ka, kw_scale=kw, mfma_passes=options.mfma_passes, reserved=0)
+        return _lib.ConvDesc(**f)
+
+    cases = [
+        (C(16, 24, 3, Kw, Ka, 2, 1), (2, 16, 15, 17), (True, True),            # int stride / padding / dilation
+         want(n=2, c_in=16, h=15, w=17, c_out=24, kh=3, kw=3, stride_h=2, stride_w=2, pad_h=1, pad_w=1, dil_h=1, dil_w=1,
+              groups=1, x_layout=NHWC, y_layout=NHWC)),
+        (C(16, 24, (3, 5), Kw, Ka, (2, 1), (1, 2), (1, 3)), (1, 16, 20, 22), (False, False),   # tuples, NCHW both sides
+         want(n=1, c_in=16, h=20, w=22, c_out=24, kh=3, kw=5, stride_h=2, stride_w=1, pad_h=1, pad_w=2, dil_h=1, dil_w=3,
+              groups=1, x_layout=NCHW, y_layout=NCHW)),
+        (Cb(32, 64, 3, Kw, Ka, 1, 2, 2, groups=4), (3, 32, 9, 9), (False, True),   # grouped, biased, dilated, NCHW in / NHWC out
+         want(n=3, c_in=32, h=9, w=9, c_out=64, kh=3, kw=3, stride_h=1, stride_w=1, pad_h=2, pad_w=2, dil_h=2, dil_w=2,
+              groups=4, x_layout=NCHW, y_layout=NHWC)),
+        (cf.linear_Q(8, Kw, Ka)(64, 10), (37, 64, 1, 1), (True, True),          # a Linear is the pointwise geometry, H = W = 1
+         want(n=37, c_in=64, h=1, w=1, c_out=10, kh=1, kw=1, stride_h=1, stride_w=1, pad_h=0, pad_w=0, dil_h=1, dil_w=1,
+              groups=1, x_layout=NHWC, y_layout=NHWC)),
+    ]
+    for mod, shape, layouts, ref in cases:
+        got = _conv_desc(mod, shape, *layouts)
+        for name, _ in _lib.ConvDesc._fields_:
+            assert getattr(got, name) == getattr(ref, name), (type(mod).__name__, shape, name)
+        assert got.ka == ka and got.kw_scale == kw
+    m = cases[0][0]
+    assert _conv_desc(m, (2, 16, 15, 17)).x_layout == NHWC and _conv_desc(m, (2, 16, 15, 17)).y_layout == NHWC   # the default
+    m.Ka = torch.tensor([0.1, 0.2])
+    with pytest.raises(ValueError):
+        _conv_desc(m, (2, 16, 15, 17))
+    with pytest.raises(NotImplementedError):
+        _conv_desc(C(16, 24, 3, Kw, Ka, 1, "same"), (2, 16, 15, 17))
+    # the dilated pair of the default options.dwpw_pairs case (32 channels, stride 1)
+    L = _lib.load()
+    pw = C(32, 64, 1, Kw, Ka)
+    for pad, dil, one_kernel in ((2, 2, 0), (1, 1, 1)):
+        dw = C(32, 32, 3, Kw, Ka, 1, pad, dil, groups=32)
+        d1 = _conv_desc(dw, (2, 32, 16, 16))
+        assert d1.dil_h == d1.dil_w == dil
+        ho, wo = ctypes.c_int64(), ctypes.c_int64()
+        assert L.slfp_conv2d_out_shape(ctypes.byref(d1), ctypes.byref(ho), ctypes.byref(wo)) == 0
+        assert (ho.value, wo.value) == (16, 16)
+        d2 = _conv_desc(pw, (2, 32, ho.value, wo.value))
+        assert L.slfp_dwpw_supported(ctypes.byref(d1), ctypes.byref(d2)) == one_kernel, (pad, dil)
+
+
 def test_fuse_named_bn_on_hand_wired_blocks():
     """fusion.fuse_named_bn: a torchvision-style residual block (conv1/bn1/relu, conv2/bn2, + identity, relu: the wiring of
     nets_imgnet/resnet50.py:24-100) folds its BatchNorms by name; with an example input it checks the WIRING (bn<k> must be

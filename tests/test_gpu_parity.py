@@ -206,12 +206,12 @@ def test_linear_golden(lib, dev, conv_golden):
             # the quantized weights are cached per weight version: same result on the second call, a new blob
             # after an in-place update, and the one-shot C entry point (prepare + forward) agrees bit for bit
             with torch.no_grad():
-                blob0 = m._lin_prep[1]
+                blob0 = m._prep.blob
                 y2 = m(torch.from_numpy(conv_golden["linear_x"]).to(dev))
-                assert torch.equal(y, y2) and m._lin_prep[1] is blob0
+                assert torch.equal(y, y2) and m._prep.blob is blob0
                 m.weight.mul_(0.5)
                 y3 = m(torch.from_numpy(conv_golden["linear_x"]).to(dev))
-                assert m._lin_prep[1] is not blob0 and not torch.equal(y3, y)
+                assert m._prep.blob is not blob0 and not torch.equal(y3, y)
                 ref3 = tp.linear_q(torch.from_numpy(conv_golden["linear_x"]).to(dev), m.weight, m.bias, Ka, Kw, q)
                 assert rel_errors(y3.cpu().numpy(), ref3.cpu().numpy())[0] <= tol
         # larger, classifier-like shape with an odd batch, through the C ABI both ways
@@ -858,6 +858,32 @@ def test_fused_depthwise_pointwise_block_is_bit_identical(dev):
         q_got = so.quantize(mid_fused.permute(0, 2, 3, 1).contiguous().cpu().numpy(), np.float32(Ka2), so.FMT_ACT8)
         assert np.mean(q_ref.view(np.uint32) != q_got.view(np.uint32)) <= 2e-4   # folded-BN fma vs stock BN: rare one-step flips
     cf.options.dwpw_all = False
+    # a dilated depthwise conv is not a pair the one-kernel form covers (slfp_dwpw_supported): the block is told the true
+    # dilation and runs its two convs, under the default options (32 channels, stride 1 is in options.dwpw_pairs)
+    Ka1, Kw1, Ka2, Kw2 = np.float64(0.21), np.float64(0.11), np.float64(0.33), np.float64(0.07)
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(3202)
+        dw = cf.conv2d_Q(8, Kw1, Ka1)(32, 32, 3, Kw1, Ka1, 1, 2, 2, groups=32, bias=False)
+        pw = cf.conv2d_Q(8, Kw2, Ka2)(32, 64, 1, Kw2, Ka2, 1, 0, bias=False)
+    m = torch.nn.Sequential(dw, torch.nn.BatchNorm2d(32), torch.nn.ReLU(inplace=True), pw, torch.nn.BatchNorm2d(64), torch.nn.ReLU(inplace=True)).to(dev).eval()
+    with torch.no_grad():
+        for bn in (m[1], m[4]):
+            bn.running_mean.normal_(0.0, 0.2, generator=g)
+            bn.running_var.uniform_(0.5, 1.5, generator=g)
+            bn.weight.uniform_(0.8, 1.6, generator=g)
+            bn.bias.normal_(0.1, 0.2, generator=g)
+        dw.weight.mul_(3.0)
+    m = m.to(memory_format=torch.channels_last)
+    x = (torch.randn((2, 32, 16, 16), generator=g, device=dev).abs() * 1.5).contiguous(memory_format=torch.channels_last)
+    with torch.no_grad():
+        assert fusion.fuse_bn_relu(m) == 2
+        y_two = m(x).clone()
+        assert fusion.unfuse(m) == 2
+        assert fusion.fuse_bn_relu(m, dw_pw=True) == 2
+        blk = [mod for mod in m if isinstance(mod, fusion.DwPwBlock)][0]
+        y_blk = m(x)
+    assert blk._last_kernel is None and tuple(y_blk.shape) == (2, 64, 16, 16)
+    assert torch.equal(y_blk, y_two)
 
 
 # ------------------------------------------------------------------ whole net (BASELINE config 1)
