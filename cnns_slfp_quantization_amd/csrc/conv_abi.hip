@@ -267,6 +267,15 @@ const char* slfp_conv2d_kernel_name(const slfp_conv2d_desc* d) {
     return family_name(p, *d);
 }
 
+const char* slfp_debug_dw3x3_variant(const slfp_conv2d_desc* d, int has_post) {
+    ConvPlan p;
+    if (make_plan(d, &p) != SLFP_OK || p.family != kDw3x3) return "none";
+    static const float one = 1.f;   // the predicates only ask whether a scale / shift pair is present
+    const PostOp post = {has_post ? &one : nullptr, has_post ? &one : nullptr, 0, 0};
+    if (dw3x3_rows_applicable(*d, p, nullptr, post)) return "rows";
+    return dw3x3_tile_applicable(*d, p, nullptr, post) ? "tile" : "general";
+}
+
 size_t slfp_conv2d_wprep_bytes(const slfp_conv2d_desc* d) {
     ConvPlan p;
     if (make_plan(d, &p) != SLFP_OK) return 0;

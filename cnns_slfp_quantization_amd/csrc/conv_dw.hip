@@ -228,6 +228,7 @@ __global__ __launch_bounds__(kDwThreads) void k_dw3x3(const float* __restrict__ 
 
 int launch_dw3x3(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x, const float* wq9c,
                  const float* bias, const PostOp& post, float* y, hipStream_t stream) {
+    if (dw3x3_rows_applicable(d, plan, bias, post)) return launch_dw3x3_rows(d, plan, x, wq9c, post, y, stream);
     if (dw3x3_tile_applicable(d, plan, bias, post)) return launch_dw3x3_tile(d, plan, x, wq9c, post, y, stream);
     DwParams p;
     p.post = post;

@@ -22,6 +22,8 @@
 // conv_dw.hip + table 1058 total, this kernel 984 (5.2 TB/s algorithmic), persistent x16 1126.
 // Neighbouring tiles share 2-pixel halos; logical workgroup ids are dealt to XCDs contiguously (xcd_remap) so
 // the re-reads hit the same L2 (HBM reads = algorithmic bytes, profiles/r02c).
+// Round 4: the stride-2 layers take conv_dw3.hip (k_dw3x3_rows, no LDS tile) unless SLFP_DW_ROWS=0; the stride-2 instance here is
+// their reference (tests/test_gpu_dw_rows.py: byte-equal) and the A/B arm.
 #include <cstdlib>
 #include "slfp_device.hpp"
 #include "slfp_enc.hpp"

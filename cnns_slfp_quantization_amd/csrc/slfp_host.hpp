@@ -47,6 +47,8 @@ inline ScaleDiv make_scale_div(float d, int esh = 0) {
 //   SLFP_PW_NOTAB       pointwise kernels on the long-form quantizer
 //   SLFP_PW_STG_MAXKS   stream kernel: staged stores up to this many k-steps (default: 1, 2 and 8)
 //   SLFP_PW_NT_MIN_MB / SLFP_DW_NT_MIN_MB   output size from which staged / depthwise stores carry the nt hint
+//   SLFP_DW_ROWS        0: stride-2 depthwise layers stay on the tile kernel (conv_dw2.hip); unset: the measured rule
+//                       (dw3x3_rows_applicable); any other value: a mask of size classes that take conv_dw3.hip (A/B runs)
 struct Switches {
     bool long_encode, dw_old, pw_nostg, pw_notab;
     int pw_stg_maxks;         // -1: default rule
@@ -60,6 +62,7 @@ struct Switches {
     bool dense_encx;          // SLFP_DENSE_NOENCX unsets it: k_dense3x3_res encodes the float32 halo on load (C_in == 64, C_out <= 64) instead of reading the pre-pass's fp16 copy
     bool dense_res;           // SLFP_DENSE_NORES unsets it: 3x3 stride-1 layers with C_in <= 64 on the persistent weights-resident k_dense3x3_res
     bool stem_im2row;         // SLFP_STEM_IM2ROW: large-kernel stems through the im2row workspace (the round-1 form; A/B of k_stem_rows)
+    int dw_rows;              // SLFP_DW_ROWS: -1 (unset) the measured rule, 0 never, else bit k = size class k (dw_rows_class) on k_dw3x3_rows
     int pw_stream_max_kb;     // SLFP_PW_STREAM_MAX_KB: largest W (KiB, fp16) the float32-interface path gives to the LDS-resident stream kernel (default 30; its capacity is 128)
 };
 const Switches& switches();
@@ -106,6 +109,21 @@ int launch_dw3x3(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, c
 bool dw3x3_tile_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, const float* bias, const PostOp& post);
 int launch_dw3x3_tile(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const float* wq9c,
                       const PostOp& post, float* y, hipStream_t stream);
+// the register-window depthwise kernel (conv_dw3.hip): the tile kernel's preconditions, stride 2, and the SLFP_DW_ROWS rule
+bool dw3x3_rows_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, const float* bias, const PostOp& post);
+int launch_dw3x3_rows(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const float* wq9c,
+                      const PostOp& post, float* y, hipStream_t stream);
+// SLFP_DW_ROWS as the environment gives it (nullptr: unset) -> Switches::dw_rows
+inline int parse_dw_rows(const char* e) {
+    if (!e || !*e) return -1;
+    const long v = strtol(e, nullptr, 0);
+    return v <= 0 ? 0 : (int)(v & 0xF);
+}
+// size class of a depthwise layer: 0 / 1 / 2 / 3 = output images of at least 56 x 56 / 28 x 28 / 14 x 14 / fewer pixels
+inline int dw_rows_class(int64_t h_out, int64_t w_out) {
+    const int64_t px = h_out * w_out;
+    return px >= 56 * 56 ? 0 : (px >= 28 * 28 ? 1 : (px >= 14 * 14 ? 2 : 3));
+}
 int launch_pointwise(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const void* wfrag,
                      const float* bias, const PostOp& post, float* y, hipStream_t stream);
 // ---- 1-byte activation codes between layers (slfp_codes.hpp; slfp_conv2d_fwd_codes) ----

@@ -102,6 +102,11 @@ int slfp_conv2d_out_shape(const slfp_conv2d_desc* d, int64_t* h_out, int64_t* w_
 /* Which kernel family slfp_conv2d_fwd will run for this descriptor (for logs/tests):
  * a static string such as "dw3x3_nhwc", "pw_mfma_f16x3", "dense_mfma_f16x1", "direct_nhwc". */
 const char* slfp_conv2d_kernel_name(const slfp_conv2d_desc* d);
+/* Which depthwise 3x3 kernel slfp_conv2d_fwd (has_post == 0) / slfp_conv2d_fwd_post (has_post != 0; no layer-output
+ * quantizer) will run for this bias-free descriptor under the switches read at load (tests, logs): "rows" (csrc/conv_dw3.hip),
+ * "tile" (csrc/conv_dw2.hip), "general" (csrc/conv_dw.hip), or "none" when the descriptor is not of the dw3x3 family.
+ * Host only: no device is touched. */
+const char* slfp_debug_dw3x3_variant(const slfp_conv2d_desc* d, int has_post);
 
 /* Bytes of the prepared-weight blob for this layer (device memory the caller owns). */
 size_t slfp_conv2d_wprep_bytes(const slfp_conv2d_desc* d);
