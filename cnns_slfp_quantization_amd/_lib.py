@@ -28,6 +28,7 @@ SYMBOLS = (
     "slfp_conv2d_codes_supported", "slfp_conv2d_fwd_codes", "slfp_conv2d_fwd_codes_ws", "slfp_maxpool2d_codes", "slfp_debug_code_mismatches", "slfp_debug_reload_switches",
     "slfp_debug_enc_hl_mismatches", "slfp_sgd_step_f32", "slfp_debug_dw3x3_variant",
     "slfp_conv2d_bwd_supported", "slfp_conv2d_bwd_kernel_name", "slfp_conv2d_bwd_workspace_bytes", "slfp_conv2d_bwd",
+    "slfp_conv2d_res_supported", "slfp_conv2d_fwd_res",
 )
 
 
@@ -123,6 +124,8 @@ def load():
         "slfp_conv2d_bwd_kernel_name": (ctypes.c_char_p, [dp]),
         "slfp_conv2d_bwd_workspace_bytes": (sz, [dp, ci, ci]),
         "slfp_conv2d_bwd": (ci, [dp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "slfp_conv2d_res_supported": (ci, [dp, ctypes.POINTER(ConvIo), ci, ci]),
+        "slfp_conv2d_fwd_res": (ci, [dp, ctypes.POINTER(ConvIo), vp, vp, vp, vp, vp, ci, vp, vp, vp, vp]),
     }
     assert set(sigs) == set(SYMBOLS)
     for name, (res, args) in sigs.items():

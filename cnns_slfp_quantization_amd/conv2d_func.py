@@ -215,17 +215,18 @@ def _conv_weights(mod, desc, weight, stream, cache, kernel=None, want_weight_q=F
 class _Plan:
     """What one (module, input shape, layout, scales, precision) combination resolves to in the C ABI; for the code path
     also its io struct and whether libslfp_hip has a kernel for the combination."""
-    __slots__ = ("desc", "y_shape", "ws_bytes", "kernel", "io", "codes_ok")
+    __slots__ = ("desc", "y_shape", "ws_bytes", "kernel", "io", "codes_ok", "res_ok")
 
     def __init__(self, desc, y_shape, ws_bytes, kernel):
         self.desc, self.y_shape, self.ws_bytes, self.kernel = desc, y_shape, ws_bytes, kernel
-        self.io, self.codes_ok = None, False
+        self.io, self.codes_ok, self.res_ok = None, False, False
 
 
 def _plan(mod, x, weight, nhwc_in, nhwc_out, codes=None, bias=None):
     """Everything that depends only on (module geometry, input shape, layouts, scales, precision) is computed once per
     distinct key and kept on the module: descriptor, output shape, workspace size, kernel name.  codes: None for the
-    float32 interface, ("codes", does x hold codes, mod._code_out) for slfp_conv2d_fwd_codes."""
+    float32 interface, ("codes", does x hold codes, mod._code_out) for slfp_conv2d_fwd_codes, ("res", does x hold codes, ReLU
+    after the add) for slfp_conv2d_fwd_res."""
     shape = x.shape
     key = (codes, shape, nhwc_in, nhwc_out, _scale_key(mod.Ka, "Ka"), _scale_key(mod.Kw, "Kw"), options.mfma_passes,
            mod.stride, mod.padding, mod.dilation, weight.shape)
@@ -240,7 +241,13 @@ def _plan(mod, x, weight, nhwc_in, nhwc_out, codes=None, bias=None):
         _lib.check(L.slfp_conv2d_out_shape(ctypes.byref(d), ctypes.byref(ho), ctypes.byref(wo)))
         plan = _Plan(d, (d.n, d.c_out, ho.value, wo.value), L.slfp_conv2d_workspace_bytes(ctypes.byref(d)),
                      L.slfp_conv2d_kernel_name(ctypes.byref(d)).decode())
-        if codes is not None:
+        if codes is not None and codes[0] == "res":
+            plan.io = _conv_io(codes[1], None)
+            flags = int(mod._post[2]) if mod._post is not None else 0
+            # an epilogue ReLU or layer-output quantizer would sit BEFORE the add: not what the residual kernels compute
+            plan.res_ok = flags == 0 and bool(L.slfp_conv2d_res_supported(ctypes.byref(d), ctypes.byref(plan.io),
+                                                                          1 if bias is not None else 0, 1 if codes[2] else 0))
+        elif codes is not None:
             plan.io = _conv_io(codes[1], codes[2])
             flags = int(mod._post[2]) if mod._post is not None else 0
             plan.codes_ok = bool(L.slfp_conv2d_codes_supported(ctypes.byref(d), ctypes.byref(plan.io),
@@ -368,6 +375,44 @@ def _hip_conv2d_codes(mod, x, weight, bias):
                                               psh.data_ptr() if psh is not None else None, flags, y.data_ptr(),
                                               ws.data_ptr() if ws is not None else None, stream.cuda_stream))
     mod._last_kernel = plan.kernel + ("+codes_in" if x_codes else "") + ("+codes_out" if out is not None else "")
+    if x_codes:
+        mod._last_input, mod._last_codes = None, x.detach()
+    else:
+        mod._last_input, mod._last_codes = x.detach(), None
+    mod._input_q = None
+    return y
+
+
+def _hip_conv2d_res(mod, x, weight, bias, residual, relu):
+    """Conv2d_Q.forward(x, residual=r) as ONE slfp_conv2d_fwd_res call: relu?(epilogue(conv(x)) + r), bit-identical to the
+    module's ordinary forward followed by torch.add and torch.relu.  `x` is float32 or the uint8 codes a linked producer
+    wrote for this module.  Returns None where the library has no residual kernel for the combination (layer geometry,
+    layouts, an epilogue ReLU in front of the add): the caller then computes the same values with ATen."""
+    x_codes = x.dtype == torch.uint8
+    nhwc = torch.channels_last
+    if not (x.is_cuda and x.dim() == 4 and (x_codes or x.dtype == torch.float32) and x.is_contiguous(memory_format=nhwc)
+            and weight.device == x.device):
+        return None
+    plan = _plan(mod, x, weight, True, True, ("res", x_codes, bool(relu)), bias)
+    if not plan.res_ok:
+        return None
+    r = residual
+    if not (torch.is_tensor(r) and r.dtype == torch.float32 and r.device == x.device and tuple(r.shape) == tuple(plan.y_shape)
+            and r.is_contiguous(memory_format=nhwc) and r.data_ptr() % 16 == 0):
+        return None
+    L = _lib.load()
+    d = plan.desc
+    with _on_device(x.device):
+        stream = torch.cuda.current_stream(x.device)
+        blob = _conv_weights(mod, d, weight, stream, True, plan.kernel)   # the same blob (and cache entry) as the other paths
+        y = torch.empty(plan.y_shape, dtype=torch.float32, device=x.device, memory_format=nhwc)
+        b, ps, psh, _ = _epilogue_args(mod, bias, x.device)
+        _lib.check(L.slfp_conv2d_fwd_res(ctypes.byref(d), ctypes.byref(plan.io), x.data_ptr(), blob.data_ptr(),
+                                         b.data_ptr() if b is not None else None,
+                                         ps.data_ptr() if ps is not None else None,
+                                         psh.data_ptr() if psh is not None else None, 1 if relu else 0,
+                                         r.data_ptr(), y.data_ptr(), None, stream.cuda_stream))
+    mod._last_kernel = plan.kernel + ("+codes_in" if x_codes else "") + "+res"
     if x_codes:
         mod._last_input, mod._last_codes = None, x.detach()
     else:
@@ -523,6 +568,7 @@ def _conv_class(q_bit, Kw, Ka, bias_default, scaled_bias):
             self._post = None  # (scale, shift, relu): fused eval-BN + ReLU epilogue (fusion.fuse_bn_relu)
             self._code_out = None   # (Ka, q_bit) of the next Conv2d_Q: hand it 1-byte codes (fusion.link_codes)
             self._last_codes = None
+            self.residual_relu = False   # forward(x, residual=r): a ReLU follows the add (fusion.fuse_residual sets it)
             self._scaled_bias = scaled_bias
             self.output = None
             self._grouped_stash = False   # the stash is one image group's (mark_grouped_stash)
@@ -560,7 +606,29 @@ def _conv_class(q_bit, Kw, Ka, bias_default, scaled_bias):
             self._prep.invalidate()   # weights may have been stepped through `.data` since the last forward
             return super(Conv2d_Q, self).train(mode)
 
-        def forward(self, input, order=None):
+        def _forward_residual(self, input, order, residual):
+            out = None
+            if (self.q_bit in (8, 7) and not self.training and not torch.is_grad_enabled() and self._code_out is None
+                    and (self.bias is None or scaled_bias)):
+                if self._grouped_stash:
+                    self._grouped_stash = False
+                out = _hip_conv2d_res(self, input, self.weight, self.bias, residual, self.residual_relu)
+            if out is None:   # training, NCHW, q_bit 32, a layer without a residual kernel: the same values with ATen
+                out = self.forward(input, order) + residual
+                if self.residual_relu:
+                    out = torch.relu(out)
+            self.output = out
+            return out
+
+        def forward(self, input, order=None, *, residual=None):
+            """Conv2d_Q.forward of the reference (utils/conv2d_func.py:20-25).  `residual` (keyword-only, not part of the
+            reference's surface): returns relu?(forward(input) + residual), the ReLU if `self.residual_relu` -- the tail of a
+            residual block.  In inference on channels_last ROCm tensors, where libslfp_hip has a residual kernel for the
+            layer, that is ONE launch (slfp_conv2d_fwd_res; `_last_kernel` then ends in "+res"); otherwise the add and the
+            ReLU run as ATen ops after the ordinary forward.  Both give the same bits.  With a residual `self.output` is
+            the tensor AFTER the add (and ReLU), not the convolution's own output."""
+            if residual is not None:
+                return self._forward_residual(input, order, residual)
             if self._grouped_stash:
                 self._grouped_stash = False
             if self.q_bit == 32:

@@ -489,6 +489,55 @@ extern "C" int slfp_conv2d_fwd_codes_ws(const slfp_conv2d_desc* d, const slfp_co
     return launch_stem_codes(*d, p, reinterpret_cast<const float*>(x), reinterpret_cast<const float*>(wprep), bias, post, y, cio, st);
 }
 
+// ---- residual operand in the pointwise epilogue (include/slfp.h: slfp_conv2d_fwd_res) ----
+static bool res_route(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, bool has_bias, int relu, ConvPlan* p) {
+    if (!d || !io) return false;
+    if (make_plan(d, p) != SLFP_OK) return false;
+    if (d->x_layout != SLFP_LAYOUT_NHWC || d->y_layout != SLFP_LAYOUT_NHWC) return false;
+    if ((relu & ~SLFP_POST_RELU) != 0 || io->y_codes) return false;   // no layer-output quantizer, float32 out
+    if (long_encode_forced()) return false;
+    if (io->x_codes) {
+        const slfp_conv2d_io cio{1, 0, 1.f, 8};
+        ConvPlan q;
+        return p->family == kPointwise && d->stride_h == 1 && d->stride_w == 1 && codes_route(d, &cio, has_bias, relu, &q) == 2;
+    }
+    return pointwise_res_applicable(*d, *p);
+}
+
+extern "C" int slfp_conv2d_res_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int relu) {
+    ConvPlan p;
+    return res_route(d, io, has_bias != 0, relu, &p) ? 1 : 0;
+}
+
+extern "C" int slfp_conv2d_fwd_res(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
+                                   const float* bias, const float* post_scale, const float* post_shift, int relu,
+                                   const float* res, float* y, void* workspace, void* stream) {
+    (void)workspace;
+    if (!d || !io) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_res: null descriptor");
+    ConvPlan p;
+    int rc = make_plan(d, &p);
+    if (rc != SLFP_OK) return rc;
+    if (!x || !wprep || !y || !res) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_res: null pointer");
+    if ((post_scale == nullptr) != (post_shift == nullptr))
+        return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_res: post_scale and post_shift must be given together");
+    if (!aligned16(x) || !aligned16(y) || !aligned16(res) || !aligned16(wprep) || (bias && !aligned16(bias)) ||
+        (post_scale && (!aligned16(post_scale) || !aligned16(post_shift))))
+        return fail(SLFP_ERR_ALIGNMENT, "slfp_conv2d_fwd_res: pointers must be 16-byte aligned");
+    {   // res is read while y is written, in a different order by different workgroups: the two must not overlap
+        const uintptr_t nbytes = (uintptr_t)d->n * (uintptr_t)d->c_out * (uintptr_t)p.h_out * (uintptr_t)p.w_out * sizeof(float);
+        const uintptr_t a = reinterpret_cast<uintptr_t>(res), b = reinterpret_cast<uintptr_t>(y);
+        if (a < b + nbytes && b < a + nbytes) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_res: res and y overlap");
+    }
+    if (!res_route(d, io, bias != nullptr, relu, &p))
+        return fail(SLFP_ERR_UNSUPPORTED, "slfp_conv2d_fwd_res: this layer / io combination has no residual kernel "
+                                          "(slfp_conv2d_res_supported); use slfp_conv2d_fwd_post and add the residual afterwards");
+    const PostOp post{post_scale, post_shift, (relu & SLFP_POST_RELU) ? 1 : 0, 0};
+    hipStream_t st = as_stream(stream);
+    if (io->x_codes)
+        return launch_pwc(*d, p, reinterpret_cast<const uint8_t*>(x), wprep, bias, post, y, false, 1.f, kFmtAct8, st, res);
+    return launch_pointwise(*d, p, reinterpret_cast<const float*>(x), wprep, bias, post, y, st, res);
+}
+
 extern "C" {
 
 size_t slfp_linear_workspace_bytes(int64_t batch, int64_t in_f, int64_t out_f) {

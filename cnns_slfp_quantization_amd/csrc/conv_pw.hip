@@ -44,6 +44,10 @@
 // is folded into the divisor, x/(Ka/16)) so hi is always a normal fp16 and lo keeps 2^-26
 // relative precision; the 2^-8 is folded into the first epilogue scale (power-of-two
 // scaling commutes with rounding), which keeps the reference's (out * Ka) * Kw roundings.
+// Residual operand (slfp_conv2d_fwd_res; the tail of a ResNet block, out = relu(bn3(conv3(h)) + identity)): a compile-time RES
+// switch on both kernels' store path adds p.res to the finished value -- one float32 add after the affine's fma, the ReLU
+// after it -- with every 16 bytes of the residual loaded in the layout of the store they pair with and requested one tile ahead
+// of the values they are added to.  The instantiations without it are unchanged.
 #include <cstdlib>
 #include "slfp_device.hpp"
 #include "slfp_enc.hpp"
@@ -124,9 +128,12 @@ constexpr int kStreamThreads = 512;
 // STG (with TAB): the outputs of two channel tiles at a time go through a 2 KiB per-wave LDS buffer and leave as 128-byte
 // pieces (8 pixels x 32 channels per store instruction) instead of the accumulator layout's 64-byte pieces (16 pixels x
 // 16 channels): HBM writes of 64-byte pieces run at about half the rate (profiles/micro/bw_patterns.hip).
-template <int FMT, int PASSES, int KS, bool KFULL, bool A8 = false, bool TAB = false, bool STG = false>
+// RES (with TAB): y = relu?(affine(conv) + res) (slfp_conv2d_fwd_res).  Each piece of p.res is loaded with the address pattern
+// of the store it pairs with, one tile (STG: one pair of tiles) ahead of the MFMA sweep that produces the values it is added to.
+template <int FMT, int PASSES, int KS, bool KFULL, bool A8 = false, bool TAB = false, bool STG = false, bool RES = false>
 __global__ __launch_bounds__(kStreamThreads) void k_pw_stream(const PwParams p) {
     static_assert(!STG || (TAB && !A8), "staged stores: table kernels with 16-byte channel alignment");
+    static_assert(!RES || (TAB && !A8), "residual operand: table kernels with 16-byte channel alignment");
     constexpr int TABB = TAB ? kPwTab : 64;
     constexpr int TABL = (TAB && PASSES == 3) ? kPwTab : 16;   // three-pass table kernels: the residual plane's table
     // The quantizer's table is STATIC LDS: its address is a compile-time constant, so a lookup is `ds_read_b64 v, bin`
@@ -268,15 +275,29 @@ __global__ __launch_bounds__(kStreamThreads) void k_pw_stream(const PwParams p) 
             } else {
                 r = epilogue(acc, make_float4(0.f, 0.f, 0.f, 0.f), p.s1x, p.s2);
             }
-            if (p.post.relu) { r.x = fmaxf(r.x, 0.f); r.y = fmaxf(r.y, 0.f); r.z = fmaxf(r.z, 0.f); r.w = fmaxf(r.w, 0.f); }
+            if constexpr (!RES) {   // with a residual the ReLU follows the add (res_add)
+                if (p.post.relu) { r.x = fmaxf(r.x, 0.f); r.y = fmaxf(r.y, 0.f); r.z = fmaxf(r.z, 0.f); r.w = fmaxf(r.w, 0.f); }
+            }
             return r;
         };
         if constexpr (STG) {
             // per-unit descriptor: rows beyond M and channels beyond N get an out-of-range offset (store dropped)
-            const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
-                p.y + (size_t)g * 16 * p.N, 0, (uint32_t)(((uint64_t)(p.M - g * 16) * p.N * 4) > 0xFFFFFFFFull ? 0xFFFFFFFFull : ((uint64_t)(p.M - g * 16) * p.N * 4)), 0x00020000);
+            const uint32_t ybytes = (uint32_t)(((uint64_t)(p.M - g * 16) * p.N * 4) > 0xFFFFFFFFull ? 0xFFFFFFFFull : ((uint64_t)(p.M - g * 16) * p.N * 4));
+            const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(p.y + (size_t)g * 16 * p.N, 0, ybytes, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(RES ? p.res : p.y) + (size_t)g * 16 * p.N, 0, ybytes, 0x00020000);
             const int spx = lane >> 3, sch = lane & 7;
+            // byte offset of piece h of tile pair j0 inside the unit (stores and residual loads alike)
+            auto piece = [&](int j0, int h) {
+                return (j0 * 16 + sch * 4) < p.N ? (uint32_t)((spx + 8 * h) * p.N + j0 * 16 + sch * 4) * 4u : 0xFFFFFFF0u;
+            };
+            u32x4r rq[2];   // RES: the residual pieces of the NEXT pair, in flight under this pair's MFMAs
+            if constexpr (RES) { rq[0] = res_load_stg(rr, piece(0, 0)); rq[1] = res_load_stg(rr, piece(0, 1)); }
             for (int j0 = 0; j0 < p.n_tiles; j0 += 2) {
+                u32x4r rc[2];
+                if constexpr (RES) {
+                    rc[0] = rq[0]; rc[1] = rq[1];
+                    rq[0] = res_load_stg(rr, piece(j0 + 2, 0)); rq[1] = res_load_stg(rr, piece(j0 + 2, 1));   // past the last pair: out of range
+                }
                 const float4 ra = tile_out(j0), rb = tile_out(j0 + 1);
                 *reinterpret_cast<float4*>(stg + col * 128 + kq * 16) = ra;
                 *reinterpret_cast<float4*>(stg + col * 128 + 64 + kq * 16) = rb;
@@ -285,7 +306,8 @@ __global__ __launch_bounds__(kStreamThreads) void k_pw_stream(const PwParams p) 
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-                    const u32x4 v = *reinterpret_cast<const u32x4*>(stg + lane * 16 + h * 1024);
+                    u32x4 v = *reinterpret_cast<const u32x4*>(stg + lane * 16 + h * 1024);
+                    if constexpr (RES) v = res_add_stg(v, rc[h], p.post.relu);
                     uint32_t so = ch_ok ? (uint32_t)((spx + 8 * h) * p.N + j0 * 16 + sch * 4) * 4u : 0xFFFFFFF0u;
                     asm volatile("" : "+v"(so));
                     if (p.nt_out) __builtin_amdgcn_raw_buffer_store_b128(v, ry, so, 0, 2);
@@ -294,8 +316,19 @@ __global__ __launch_bounds__(kStreamThreads) void k_pw_stream(const PwParams p) 
             }
         } else {
             float* yr = p.y + (size_t)m * p.N + kq * 4;
+            // RES: the 16 bytes a store will overwrite, one tile ahead (unconditional: dead rows / channels re-read a live element)
+            const float* rrow = (RES ? p.res : p.y) + (size_t)(live ? m : p.M - 1) * p.N;
+            float4 rn;
+            if constexpr (RES) rn = ld_stream4<SLFP_NT_PW_RES>(rrow + (kq * 4 < p.N ? kq * 4 : 0));
             for (int j = 0; j < p.n_tiles; ++j) {
-                const float4 r = tile_out(j);
+                float4 rc;
+                if constexpr (RES) {
+                    rc = rn;
+                    const int n1 = (j + 1) * 16 + kq * 4;
+                    rn = ld_stream4<SLFP_NT_PW_RES>(rrow + (n1 < p.N ? n1 : 0));
+                }
+                float4 r = tile_out(j);
+                if constexpr (RES) r = res_add(r, rc, p.post.relu);
                 const int n = j * 16 + kq * 4;
                 if constexpr (A8) {
                     if (live && n < p.N) *reinterpret_cast<float2*>(yr + j * 16) = make_float2(r.x, r.y);
@@ -319,9 +352,12 @@ __global__ __launch_bounds__(kStreamThreads) void k_pw_stream(const PwParams p) 
 // in the middle of the MFMA block, draining the HBM loads it has just issued (r01c ISA).
 // STG: the epilogue goes through a per-wave LDS staging area so that every store instruction writes whole 256-byte runs
 // (4 pixel rows x the wave's 64 adjacent channels) instead of 64-byte pieces, with the nt hint (SLFP_NT_PW_STG).
-template <int FMT, int PASSES, int WM, int WN, int MT, int NT, bool KFULL, bool TAB = false, bool STG = false>
+// RES (with STG): y = relu?(affine(conv) + res) (slfp_conv2d_fwd_res).  The residual is loaded in the staged layout (the 16 bytes
+// each staged store writes), one 16-row tile ahead: the first tile row's pieces are requested before the last MFMA sweep.
+template <int FMT, int PASSES, int WM, int WN, int MT, int NT, bool KFULL, bool TAB = false, bool STG = false, bool RES = false>
 __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pw_tiled(const PwParams p) {
     static_assert(!STG || NT == 4, "the staged epilogue stores a wave's 64 channels per row");
+    static_assert(!RES || STG, "residual operand: staged epilogue only");
     constexpr int TABB = TAB ? kPwTab : 64;
     constexpr int TABL = (TAB && PASSES == 3) ? kPwTab : 16;
     constexpr int T = 64 * WM * WN;
@@ -520,11 +556,27 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pw_til
 #endif
     }
     SLFP_STAMP(12);
+    // staged epilogue geometry: piece h of tile row i = 4 pixel rows x the wave's 64 channels, 16 bytes per lane
+    const int srow = lane >> 4, sch = lane & 15;
+    const int n_st = ntile0 * 16 + sch * 4;
+    const uint64_t yleft = (uint64_t)(p.M - m0) * p.N * 4;
+    const uint32_t ybytes = (uint32_t)(yleft > 0xFFFFFFFFull ? 0xFFFFFFFFull : yleft);
+    auto piece = [&](int i, int h) {   // byte offset from row m0 (stores and residual loads alike); out of range: dropped / 0
+        const int row = (wm * MT + i) * 16 + h * 4 + srow;
+        const bool ok = row < p.rb && m0 + row < p.M && n_st < p.N;
+        return ok ? (uint32_t)(row * p.N + n_st) * 4u : 0xFFFFFFF0u;
+    };
+    const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(RES ? p.res : p.y) + (size_t)m0 * p.N, 0, ybytes, 0x00020000);
+    u32x4r rq[4];   // RES: four residual pieces in flight (16 registers): piece h of the tile row that is stored next
     {   // last stage: nothing left to prefetch
         const int t = KT - 1, buf = t & 1;
         load_w(t * 2);
         mfma_step(buf, 0);
         load_w(t * 2 + 1);
+        if constexpr (RES) {   // behind the last W loads (loads retire in order: the W wait must not include these), under the last sweep
+#pragma unroll
+            for (int h = 0; h < 4; ++h) rq[h] = res_load_stg(rr, piece(0, h));
+        }
         mfma_step(buf, 1);
     }
 
@@ -546,11 +598,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pw_til
     SLFP_STAMP(13);
     if constexpr (STG) {
         unsigned char* stg = xs + 2 * (PASSES == 3 ? 2 : 1) * XBYTES + wave * (16 * kStgRow);   // private to this wave
-        const uint64_t left = (uint64_t)(p.M - m0) * p.N * 4;
-        const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(p.y + (size_t)m0 * p.N, 0,
-                                                                             (uint32_t)(left > 0xFFFFFFFFull ? 0xFFFFFFFFull : left), 0x00020000);
-        const int srow = lane >> 4, sch = lane & 15;
-        const int n_st = ntile0 * 16 + sch * 4;
+        const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(p.y + (size_t)m0 * p.N, 0, ybytes, 0x00020000);
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
 #pragma unroll
@@ -565,7 +613,9 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pw_til
                     r.z = __builtin_fmaf(r.z, sc.z, sh.z); r.w = __builtin_fmaf(r.w, sc.w, sh.w);
                     if (p.post.layerout) r = layerout4(r);
                 }
-                if (p.post.relu) { r.x = fmaxf(r.x, 0.f); r.y = fmaxf(r.y, 0.f); r.z = fmaxf(r.z, 0.f); r.w = fmaxf(r.w, 0.f); }
+                if constexpr (!RES) {   // with a residual the ReLU follows the add (res_add_stg)
+                    if (p.post.relu) { r.x = fmaxf(r.x, 0.f); r.y = fmaxf(r.y, 0.f); r.z = fmaxf(r.z, 0.f); r.w = fmaxf(r.w, 0.f); }
+                }
                 *reinterpret_cast<float4*>(stg + col * kStgRow + j * 64 + kq * 16) = r;
             }
             // LDS operations of one wave execute in order: the reads see the writes, the next tile's writes follow the reads
@@ -573,7 +623,11 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pw_til
             for (int h = 0; h < 4; ++h) {
                 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
                 const int row = (wm * MT + i) * 16 + h * 4 + srow;
-                const u32x4 v = *reinterpret_cast<const u32x4*>(stg + (h * 4 + srow) * kStgRow + sch * 16);
+                u32x4 v = *reinterpret_cast<const u32x4*>(stg + (h * 4 + srow) * kStgRow + sch * 16);
+                if constexpr (RES) {
+                    v = res_add_stg(v, rq[h], p.post.relu);
+                    if (i + 1 < MT) rq[h] = res_load_stg(rr, piece(i + 1, h));   // the next tile row's piece takes the register over
+                }
                 const bool ok = row < p.rb && m0 + row < p.M && n_st < p.N;
                 uint32_t so = ok ? (uint32_t)(row * p.N + n_st) * 4u : 0xFFFFFFF0u;
 #ifdef SLFP_ABL_NOST
@@ -632,6 +686,19 @@ static int launch_tiled_k(PwParams& p, hipStream_t stream) {
     const int64_t nblocks = (int64_t)p.m_blocks * p.n_blocks;
     if (nblocks > 0x7FFFFFFF) return fail(SLFP_ERR_UNSUPPORTED, "pointwise: grid too large");
     p.nblocks = (uint32_t)nblocks;
+    if (p.res) {   // residual operand: the table quantizer + staged epilogue form only (pointwise_res_applicable asks for both)
+        if constexpr (NT == 4) {
+            if (p.enc.valid && (PASSES == 1 || p.enc_lo.valid) && !switches().pw_nostg) {
+                const size_t lds = (size_t)2 * (PASSES == 3 ? 2 : 1) * BM * 128 + (size_t)(T / 64) * 16 * kStgRow;
+                auto fn = k_pw_tiled<FMT, PASSES, WM, WN, MT, NT, KFULL, true, true, true>;
+                int rc = set_lds_limit(reinterpret_cast<const void*>(fn), lds);
+                if (rc != SLFP_OK) return rc;
+                hipLaunchKernelGGL(fn, dim3(p.nblocks), dim3(T), lds, stream, p);
+                return check_launch("slfp pointwise (tiled, residual) kernel");
+            }
+        }
+        return fail(SLFP_ERR_UNSUPPORTED, "pointwise: no residual form of this kernel variant");
+    }
     {
         if (p.enc.valid && (PASSES == 1 || p.enc_lo.valid)) {
             if constexpr (NT == 4) {
@@ -675,8 +742,11 @@ static int launch_stream_ks(PwParams& p, hipStream_t stream) {
     // same-box A/B profiles/ab_env_long.sh, 3 rounds: depthwise family 1.035 -> 0.997 ms, pointwise 1.098 -> 1.112, step -1 %):
     // staged everywhere since round 3.  K = 160 / 192 (KS 5..6: no MobileNetV1 layer) keep the direct stores they were measured with
     const int mk = switches().pw_stg_maxks;   // experiment switch (slfp_host.hpp), read once at load
-    const bool stg_ks = mk >= 0 ? KS <= mk : (KS <= 4 || KS == 8);
+    constexpr bool kStgDefault = KS <= 4 || KS == 8;
+    const bool stg_ks = (mk >= 0 && !p.res) ? KS <= mk : kStgDefault;   // the residual forms exist for the default rule only
     const bool stg = tab && stg_ks && !(p.K % 4 || p.N % 4) && !switches().pw_nostg;
+    if (p.res && (!tab || (p.K % 4 || p.N % 4) || stg != kStgDefault))
+        return fail(SLFP_ERR_UNSUPPORTED, "pointwise: no residual form of this kernel variant");
     const size_t lds = (size_t)(PASSES == 3 ? 2 : 1) * p.n_tiles * p.KS * 1024 + (size_t)3 * p.n_tiles * 16 * sizeof(float) +
                        (stg ? (size_t)(kStreamThreads / 64) * 2048 : 0);   // dynamic part; the table (2 KiB / 64 B) is static LDS
     const size_t lds_total = lds + (tab ? kPwTab * (PASSES == 3 ? 2 : 1) : 64);
@@ -686,6 +756,7 @@ static int launch_stream_ks(PwParams& p, hipStream_t stream) {
         if (tab) fn = (p.K % 4 || p.N % 4) ? k_pw_stream<FMT, PASSES, KS, false, true, true>
                       : (p.K % 32 == 0)    ? k_pw_stream<FMT, PASSES, KS, true, false, true> : k_pw_stream<FMT, PASSES, KS, false, false, true>;
         if (stg) fn = (p.K % 32 == 0) ? k_pw_stream<FMT, PASSES, KS, true, false, true, true> : k_pw_stream<FMT, PASSES, KS, false, false, true, true>;
+        if (p.res) fn = (p.K % 32 == 0) ? k_pw_stream<FMT, PASSES, KS, true, false, true, kStgDefault, true> : k_pw_stream<FMT, PASSES, KS, false, false, true, kStgDefault, true>;
     }
     int rc = set_lds_limit(reinterpret_cast<const void*>(fn), lds);
     if (rc != SLFP_OK) return rc;
@@ -745,11 +816,22 @@ static int launch_pw(PwParams& p, const ConvPlan& plan, hipStream_t stream) {
     }
 }
 
+// Does a residual form of the kernel launch_pointwise would pick exist?  Host-only: the planner's answer, the quantizer table
+// of the layer's scale and the two experiment switches that take the table / the staged stores away.
+bool pointwise_res_applicable(const slfp_conv2d_desc& d, const ConvPlan& plan) {
+    if (plan.family != kPointwise || plan.repad || d.stride_h != 1 || d.stride_w != 1) return false;
+    if (d.c_in % 4 || d.c_out % 4) return false;   // the 8-byte (A8) forms have no residual variant
+    if (switches().pw_notab || switches().pw_nostg) return false;
+    if (!act_table(d.ka, plan.fmt_act, kEncF16P)) return false;
+    if (plan.passes == 3 && !act_table(d.ka, plan.fmt_act, kEncF16LO)) return false;
+    return true;
+}
+
 int launch_pointwise(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x, const void* wfrag,
-                     const float* bias, const PostOp& post, float* y, hipStream_t stream) {
+                     const float* bias, const PostOp& post, float* y, hipStream_t stream, const float* res) {
     PwParams p;
     p.post = post;
-    p.x = x; p.bias = bias; p.y = y;
+    p.x = x; p.bias = bias; p.y = y; p.res = res;
     p.K = (int)d.c_in; p.N = (int)d.c_out;
     p.KS = (int)(plan.k_pad / 32);
     p.n_tiles = (int)(plan.n_pad / 16);

@@ -20,6 +20,8 @@
 //     per lane: per pixel the wave writes 64 contiguous bytes.
 // Two kernels, as in conv_pw.hip: k_pwc_stream (W resident in LDS, persistent, a wave's unit = 16 pixels) and
 // k_pwc_tiled (W fragments streamed from L2, X tile decoded once into the swizzled LDS image).
+// The float32-output forms of all three take a residual operand (RES; slfp_conv2d_fwd_res with io->x_codes = 1): conv3 of a
+// ResNet block that reads conv2's codes and adds the float32 trunk, as in conv_pw.hip.
 #include "slfp_device.hpp"
 #include "slfp_enc.hpp"
 #include "slfp_codes.hpp"
@@ -33,6 +35,7 @@ struct PwcParams {
     const _Float16* whi;
     const float* bias;
     void* y;
+    const float* res;     // RES kernels (float32 out): the residual operand, NHWC like y; nullptr otherwise
     int64_t M;            // output pixels
     int K, N, KS, n_tiles;
     int H, W, Ho, Wo, S;
@@ -66,10 +69,12 @@ __device__ __forceinline__ half8 dec_frag(uint32_t ca, uint32_t cb, const unsign
 constexpr int kPwcThreads = 512;
 
 // KS: 32-deep k-steps (K = 32 * KS exactly); XW: K is a multiple of 64 (16-byte code loads + transpose), else two
-// dword loads per k-step; YC: output codes (N a multiple of 16), else float32.
-template <int FMT, int KS, bool XW, bool YC>
+// dword loads per k-step; YC: output codes (N a multiple of 16), else float32.  RES (float32 out): y = relu?(affine(conv) + res),
+// each 16 bytes of p.res loaded with the address of the store they pair with, one channel tile ahead of its MFMA sweep.
+template <int FMT, int KS, bool XW, bool YC, bool RES = false>
 __global__ __launch_bounds__(kPwcThreads) void k_pwc_stream(const PwcParams p) {
     static_assert(!XW || KS % 2 == 0, "16-byte code loads cover two k-steps");
+    static_assert(!RES || !YC, "residual operand: float32 output only");
     __shared__ __attribute__((aligned(16))) uint32_t sdec[256];
     __shared__ __attribute__((aligned(16))) unsigned char senc[YC ? kPwTab : 16];
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -148,7 +153,7 @@ __global__ __launch_bounds__(kPwcThreads) void k_pwc_stream(const PwcParams p) {
             } else {
                 r = epilogue(acc, make_float4(0.f, 0.f, 0.f, 0.f), p.s1x, p.s2);
             }
-            if constexpr (!YC) {   // with code output the ReLU is the quantizer's (enc4_code_relu)
+            if constexpr (!YC && !RES) {   // with code output the ReLU is the quantizer's (enc4_code_relu); with a residual it follows the add
                 if (p.post.relu) { r.x = fmaxf(r.x, 0.f); r.y = fmaxf(r.y, 0.f); r.z = fmaxf(r.z, 0.f); r.w = fmaxf(r.w, 0.f); }
             }
             return r;
@@ -169,8 +174,19 @@ __global__ __launch_bounds__(kPwcThreads) void k_pwc_stream(const PwcParams p) {
             }
         } else {
             float* yr = reinterpret_cast<float*>(p.y) + (size_t)m * p.N + kq * 4;
+            // RES: unconditional loads (dead rows / channels re-read a live element and are dropped)
+            const float* rrow = (RES ? p.res : reinterpret_cast<const float*>(p.y)) + (size_t)(live ? m : p.M - 1) * p.N;
+            float4 rn;
+            if constexpr (RES) rn = ld_stream4<SLFP_NT_PW_RES>(rrow + (kq * 4 < p.N ? kq * 4 : 0));
             for (int j = 0; j < p.n_tiles; ++j) {
-                const float4 r = tile_out(j);
+                float4 rc;
+                if constexpr (RES) {
+                    rc = rn;
+                    const int n1 = (j + 1) * 16 + kq * 4;
+                    rn = ld_stream4<SLFP_NT_PW_RES>(rrow + (n1 < p.N ? n1 : 0));
+                }
+                float4 r = tile_out(j);
+                if constexpr (RES) r = res_add(r, rc, p.post.relu);
                 if (live && j * 16 + kq * 4 < p.N) *reinterpret_cast<float4*>(yr + j * 16) = r;
             }
         }
@@ -192,10 +208,15 @@ __global__ __launch_bounds__(kPwcThreads) void k_pwc_stream(const PwcParams p) {
 // 42 -> 34; but 512->512 @14 54 -> 54-64 and 1024->1024 @7 45 -> 66-76 (512 or 1024 threads): with W in LDS every MFMA needs a
 // 1 KiB fragment read, exactly the LDS rate of a CU, and the decode lookups come on top -- at K >= 512 the register-blocked
 // k_pwc_tiled (4 x 4 tiles per wave, W straight from L2) stays.  Used for K = 256 only (two workgroups per CU).
+// RES (float32 out): y = relu?(affine(conv) + res); the first RP tiles' 16-byte pieces of p.res are requested before the unit's K
+// sweep, RP more right after it (in the registers the decoded X fragments leave), then one per tile stored: the kernel has to
+// stay within 128 VGPRs (two workgroups per CU).
 constexpr int kSliceThreads = 512;
-template <int FMT, int NTS, bool YC>
-__global__ __launch_bounds__(kSliceThreads) void k_pwc_slice(const PwcParams p) {
+template <int FMT, int NTS, bool YC, bool RES = false>
+__global__ __launch_bounds__(kSliceThreads, RES ? 4 : 1) void k_pwc_slice(const PwcParams p) {   // RES: 4 waves per SIMD = the 128 VGPRs of two workgroups per CU
+    static_assert(!RES || !YC, "residual operand: float32 output only");
     constexpr int KC = 8;   // k-steps per chunk = 256 channels = 4 x 16-byte code loads per lane
+    constexpr int RP = 2;   // RES: residual pieces in flight under the K sweep
     static_assert(NTS % 4 == 0, "code output leaves in groups of 4 channel tiles");
     __shared__ __attribute__((aligned(16))) uint32_t sdec[256];
     __shared__ __attribute__((aligned(16))) unsigned char senc[YC ? kPwTab : 16];
@@ -255,6 +276,14 @@ __global__ __launch_bounds__(kSliceThreads) void k_pwc_slice(const PwcParams p) 
         floatx4 acc[NTS];
 #pragma unroll
         for (int j = 0; j < NTS; ++j) acc[j] = floatx4{0.f, 0.f, 0.f, 0.f};
+        // RES: unconditional loads (dead rows / channels re-read a live element and are dropped)
+        const float* rrow = (RES ? p.res : reinterpret_cast<const float*>(p.y)) + (size_t)(live ? m : p.M - 1) * p.N;
+        auto res_at = [&](int j) { const int n = n_lo + j * 16 + kq * 4; return ld_stream4<SLFP_NT_PW_RES>(rrow + (n < p.N ? n : 0)); };
+        float4 rq[NTS];
+        if constexpr (RES) {
+#pragma unroll
+            for (int j = 0; j < RP && j < NTS; ++j) rq[j] = res_at(j);
+        }
         for (int kc = 0; kc < n_chunks; ++kc) {
             half8 xh[KC];
 #pragma unroll
@@ -294,7 +323,7 @@ __global__ __launch_bounds__(kSliceThreads) void k_pwc_slice(const PwcParams p) 
             } else {
                 r = epilogue(acc[j], make_float4(0.f, 0.f, 0.f, 0.f), p.s1x, p.s2);
             }
-            if constexpr (!YC) {
+            if constexpr (!YC && !RES) {   // with a residual the ReLU follows the add
                 if (p.post.relu) { r.x = fmaxf(r.x, 0.f); r.y = fmaxf(r.y, 0.f); r.z = fmaxf(r.z, 0.f); r.w = fmaxf(r.w, 0.f); }
             }
             return r;
@@ -316,9 +345,17 @@ __global__ __launch_bounds__(kSliceThreads) void k_pwc_slice(const PwcParams p) 
             }
         } else {
             float* yr = reinterpret_cast<float*>(p.y) + (size_t)m * p.N + n_lo + kq * 4;
+            if constexpr (RES) {
+#pragma unroll
+                for (int j = RP; j < 2 * RP && j < NTS; ++j) rq[j] = res_at(j);
+            }
 #pragma unroll
             for (int j = 0; j < NTS; ++j) {
-                const float4 r = finish(j);
+                float4 r = finish(j);
+                if constexpr (RES) {
+                    r = res_add(r, rq[j], p.post.relu);
+                    if (j + 2 * RP < NTS) rq[j + 2 * RP] = res_at(j + 2 * RP);   // 2 RP pieces in flight: the consumed one's registers
+                }
                 if (live && n_lo + j * 16 + kq * 4 < p.N) *reinterpret_cast<float4*>(yr + j * 16) = r;
             }
         }
@@ -329,8 +366,11 @@ __global__ __launch_bounds__(kSliceThreads) void k_pwc_slice(const PwcParams p) 
 // k_pwc_tiled: codes -> swizzled fp16 LDS tile (decoded once), W fragments straight from L2.
 // ======================================================================================
 // K a multiple of 64; NT = 4 channel tiles per wave.  STG-style float32 epilogue as in conv_pw.hip's k_pw_tiled.
-template <int FMT, int WM, int WN, int MT, bool YC>
+// RES (float32 out): y = relu?(affine(conv) + res), the residual loaded in the staged layout one 16-row tile ahead, the first
+// tile row's pieces in front of the staging barrier, while the last sweep's MFMAs drain.
+template <int FMT, int WM, int WN, int MT, bool YC, bool RES = false>
 __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_tiled(const PwcParams p) {
+    static_assert(!RES || !YC, "residual operand: float32 output only");
     constexpr int NT = 4;
     constexpr int T = 64 * WM * WN;
     constexpr int BM = WM * MT * 16;
@@ -443,11 +483,29 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_ti
         mfma_step(buf, 1, 1);
         __syncthreads();
     }
+    // staged epilogue geometry (float32 out): piece h of tile row i = 4 pixel rows x the wave's 64 channels, 16 bytes per lane
+    const int srow = lane >> 4, sch = lane & 15;
+    const int n_st = ntile0 * 16 + sch * 4;
+    const uint64_t yleft = (uint64_t)(p.M - m0) * p.N * 4;
+    const uint32_t ybytes = (uint32_t)(yleft > 0xFFFFFFFFull ? 0xFFFFFFFFull : yleft);
+    auto piece = [&](int i, int h) {   // byte offset from row m0 (stores and residual loads alike); out of range: dropped / 0
+        const int row = (wm * MT + i) * 16 + h * 4 + srow;
+        const bool ok = row < p.rb && m0 + row < p.M && n_st < p.N;
+        return ok ? (uint32_t)(row * p.N + n_st) * 4u : 0xFFFFFFF0u;
+    };
+    const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(RES ? p.res : reinterpret_cast<const float*>(p.y)) + (size_t)m0 * p.N, 0, ybytes, 0x00020000);
+    u32x4r rq[4];   // RES: four residual pieces in flight (16 registers): piece h of the tile row that is stored next
     {
         const int t = KT - 1, buf = t & 1;
         load_w(t * 2 + 1, 1);
         mfma_step(buf, 0, 0);
         mfma_step(buf, 1, 1);
+        // RES: requested behind the last sweep's MFMA issue, in the registers of the W buffers it frees (the 8-wave form sits
+        // at its 128-VGPR cap): in flight while the matrix pipeline drains and through the epilogue vectors' barriers below
+        if constexpr (RES) {
+#pragma unroll
+            for (int h = 0; h < 4; ++h) rq[h] = res_load_stg(rr, piece(0, h));
+        }
     }
 
     const int n_lo = (int)nb * BN;
@@ -474,7 +532,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_ti
             r.x = __builtin_fmaf(r.x, sc.x, sh.x); r.y = __builtin_fmaf(r.y, sc.y, sh.y);
             r.z = __builtin_fmaf(r.z, sc.z, sh.z); r.w = __builtin_fmaf(r.w, sc.w, sh.w);
         }
-        if constexpr (!YC) {
+        if constexpr (!YC && !RES) {   // with a residual the ReLU follows the add
             if (p.post.relu) { r.x = fmaxf(r.x, 0.f); r.y = fmaxf(r.y, 0.f); r.z = fmaxf(r.z, 0.f); r.w = fmaxf(r.w, 0.f); }
         }
         return r;
@@ -500,11 +558,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_ti
     } else {
         // float32 out: staged through a per-wave LDS area into 256-byte runs (4 rows x the wave's 64 channels per store)
         unsigned char* stg = xs + 2 * XBYTES + wave * (16 * kStgRow);
-        const uint64_t left = (uint64_t)(p.M - m0) * p.N * 4;
-        const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(p.y) + (size_t)m0 * p.N, 0,
-                                                                             (uint32_t)(left > 0xFFFFFFFFull ? 0xFFFFFFFFull : left), 0x00020000);
-        const int srow = lane >> 4, sch = lane & 15;
-        const int n_st = ntile0 * 16 + sch * 4;
+        const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(p.y) + (size_t)m0 * p.N, 0, ybytes, 0x00020000);
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
 #pragma unroll
@@ -512,7 +566,11 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_ti
 #pragma unroll
             for (int h = 0; h < 4; ++h) {
                 const int row = (wm * MT + i) * 16 + h * 4 + srow;
-                const u32x4c v = *reinterpret_cast<const u32x4c*>(stg + (h * 4 + srow) * kStgRow + sch * 16);
+                u32x4c v = *reinterpret_cast<const u32x4c*>(stg + (h * 4 + srow) * kStgRow + sch * 16);
+                if constexpr (RES) {
+                    v = res_add_stg(v, rq[h], p.post.relu);
+                    if (i + 1 < MT) rq[h] = res_load_stg(rr, piece(i + 1, h));   // the next tile row's piece takes the register over
+                }
                 const bool ok = row < p.rb && m0 + row < p.M && n_st < p.N;
                 uint32_t so = ok ? (uint32_t)(row * p.N + n_st) * 4u : 0xFFFFFFF0u;
                 asm volatile("" : "+v"(so));
@@ -541,7 +599,7 @@ template <int FMT, int KS, bool XW>
 static int launch_pwc_stream(PwcParams& p, bool y_codes, hipStream_t stream) {
     const size_t lds = (size_t)p.n_tiles * p.KS * 1024 + (size_t)3 * p.n_tiles * 16 * sizeof(float);
     const size_t lds_total = lds + 1024 + (y_codes ? kPwTab : 16);
-    auto fn = y_codes ? k_pwc_stream<FMT, KS, XW, true> : k_pwc_stream<FMT, KS, XW, false>;
+    auto fn = y_codes ? k_pwc_stream<FMT, KS, XW, true> : (p.res ? k_pwc_stream<FMT, KS, XW, false, true> : k_pwc_stream<FMT, KS, XW, false>);
     int rc = raise_lds_limit(reinterpret_cast<const void*>(fn), lds);
     if (rc != SLFP_OK) return rc;
     int per_cu = resident_blocks_per_cu(reinterpret_cast<const void*>(fn), kPwcThreads, lds);
@@ -565,7 +623,7 @@ static int launch_pwc_tiled(PwcParams& p, bool y_codes, hipStream_t stream) {
     if (nblocks > 0x7FFFFFFF) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): grid too large");
     p.nblocks = (uint32_t)nblocks;
     const size_t lds = (size_t)2 * BM * 128 + (y_codes ? 0 : (size_t)(T / 64) * 16 * kStgRow);
-    auto fn = y_codes ? k_pwc_tiled<FMT, WM, WN, MT, true> : k_pwc_tiled<FMT, WM, WN, MT, false>;
+    auto fn = y_codes ? k_pwc_tiled<FMT, WM, WN, MT, true> : (p.res ? k_pwc_tiled<FMT, WM, WN, MT, false, true> : k_pwc_tiled<FMT, WM, WN, MT, false>);
     int rc = raise_lds_limit(reinterpret_cast<const void*>(fn), lds);
     if (rc != SLFP_OK) return rc;
     hipLaunchKernelGGL(fn, dim3(p.nblocks), dim3(T), lds, stream, p);
@@ -584,7 +642,7 @@ static int pwc_slice_nts(const PwcParams& p) {
 template <int FMT, int NTS>
 static int launch_pwc_slice(PwcParams& p, bool y_codes, hipStream_t stream) {
     const size_t lds = (size_t)NTS * p.KS * 1024 + (size_t)3 * NTS * 16 * sizeof(float);
-    auto fn = y_codes ? k_pwc_slice<FMT, NTS, true> : k_pwc_slice<FMT, NTS, false>;
+    auto fn = y_codes ? k_pwc_slice<FMT, NTS, true> : (p.res ? k_pwc_slice<FMT, NTS, false, true> : k_pwc_slice<FMT, NTS, false>);
     int rc = raise_lds_limit(reinterpret_cast<const void*>(fn), lds);
     if (rc != SLFP_OK) return rc;
     int per_cu = resident_blocks_per_cu(reinterpret_cast<const void*>(fn), kSliceThreads, lds);
@@ -624,10 +682,11 @@ static int launch_pwc_fmt(PwcParams& p, const ConvPlan& plan, bool y_codes, hipS
 }
 
 int launch_pwc(const slfp_conv2d_desc& d, const ConvPlan& plan, const uint8_t* x, const void* wfrag, const float* bias,
-               const PostOp& post, void* y, bool y_codes, float y_ka, int y_fmt, hipStream_t stream) {
+               const PostOp& post, void* y, bool y_codes, float y_ka, int y_fmt, hipStream_t stream, const float* res) {
+    if (res && y_codes) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): a residual operand needs float32 output");
     PwcParams p;
     p.post = post;
-    p.x = x; p.bias = bias; p.y = y;
+    p.x = x; p.bias = bias; p.y = y; p.res = res;
     p.K = (int)d.c_in; p.N = (int)d.c_out;
     p.KS = (int)(plan.k_pad / 32);
     p.n_tiles = (int)(plan.n_pad / 16);

@@ -28,6 +28,7 @@ struct PwParams {
     uint32_t m_blocks, n_blocks, nblocks;
     int rb;               // k_pw_tiled: pixel rows a workgroup really owns (<= BM; the rest of its tile is padding)
     int nt_out;           // staged (whole-line) stores carry the nt hint: outputs too large for the Infinity Cache
+    const float* res;     // RES kernels: the residual operand, NHWC like y (y = relu?(affine(conv) + res)); nullptr otherwise
     PostOp post;
     EncArgs enc;          // threshold table of fp16(16 * QA(x / Ka)) (TAB kernels; slfp_enc.hpp)
     EncArgsCompact enc_lo;   // three-pass TAB kernels: the residual plane's table (kEncF16LO) of the same scale
@@ -60,6 +61,28 @@ __device__ __forceinline__ float4 bias_q256(const PwParams& p, int n) {
     const float4 bb = *reinterpret_cast<const float4*>(p.bias + n);
     return make_float4(256.f * ((bb.x / p.s1) / p.s2), 256.f * ((bb.y / p.s1) / p.s2),
                        256.f * ((bb.z / p.s1) / p.s2), 256.f * ((bb.w / p.s1) / p.s2));
+}
+
+// The residual epilogue (slfp_conv2d_fwd_res): t = r + q, one float32 add AFTER the affine's rounding (the library is built
+// with -ffp-contract=off, so the add never merges into the fma in front of it), then the ReLU's max: what torch.add and
+// torch.relu compute on the unfused result.
+__device__ __forceinline__ float4 res_add(float4 r, const float4 q, const int relu) {
+    r.x = r.x + q.x; r.y = r.y + q.y; r.z = r.z + q.z; r.w = r.w + q.w;
+    if (relu) { r.x = fmaxf(r.x, 0.f); r.y = fmaxf(r.y, 0.f); r.z = fmaxf(r.z, 0.f); r.w = fmaxf(r.w, 0.f); }
+    return r;
+}
+
+typedef uint32_t u32x4r __attribute__((ext_vector_type(4)));
+// 16 bytes of the residual in the layout of the staged store they pair with: same descriptor bounds, same byte offset (an
+// out-of-range offset -- rows past M, channels past N -- reads nothing and returns 0)
+__device__ __forceinline__ u32x4r res_load_stg(const __amdgpu_buffer_rsrc_t rr, uint32_t so) {
+    asm volatile("" : "+v"(so));
+    return __builtin_amdgcn_raw_buffer_load_b128(rr, so, 0, (SLFP_NT_PW_RES & 1) ? 2 : 0);
+}
+__device__ __forceinline__ u32x4r res_add_stg(const u32x4r v, const u32x4r q, const int relu) {
+    const float4 r = res_add(make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3])),
+                             make_float4(__uint_as_float(q[0]), __uint_as_float(q[1]), __uint_as_float(q[2]), __uint_as_float(q[3])), relu);
+    return u32x4r{__float_as_uint(r.x), __float_as_uint(r.y), __float_as_uint(r.z), __float_as_uint(r.w)};
 }
 
 // 128-byte rows (64 fp16); XOR swizzle so that the 16 rows a fragment read touches hit

@@ -41,6 +41,11 @@ namespace slfp {
 #ifndef SLFP_NT_PW_STG
 #define SLFP_NT_PW_STG 2
 #endif
+// SLFP_NT_PW_RES: the residual operand of the pointwise kernels (slfp_conv2d_fwd_res).  nt loads measured 2 % slower on whole
+// ResNet-50 forwards: the block's first conv has just read the same tensor.
+#ifndef SLFP_NT_PW_RES
+#define SLFP_NT_PW_RES 0
+#endif
 #ifndef SLFP_NT_STEM_MFMA
 #define SLFP_NT_STEM_MFMA 0
 #endif

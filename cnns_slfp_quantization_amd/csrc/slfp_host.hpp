@@ -124,8 +124,10 @@ inline int dw_rows_class(int64_t h_out, int64_t w_out) {
     const int64_t px = h_out * w_out;
     return px >= 56 * 56 ? 0 : (px >= 28 * 28 ? 1 : (px >= 14 * 14 ? 2 : 3));
 }
+// res: the residual operand of slfp_conv2d_fwd_res (float32 NHWC like y; needs pointwise_res_applicable) or nullptr
 int launch_pointwise(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const void* wfrag,
-                     const float* bias, const PostOp& post, float* y, hipStream_t stream);
+                     const float* bias, const PostOp& post, float* y, hipStream_t stream, const float* res = nullptr);
+bool pointwise_res_applicable(const slfp_conv2d_desc& d, const ConvPlan& p);
 // ---- 1-byte activation codes between layers (slfp_codes.hpp; slfp_conv2d_fwd_codes) ----
 // How a layer's input arrives and its output leaves: float32, or the extended codes of QA(. / ka) in format fmt.
 struct CodeIo {
@@ -142,7 +144,7 @@ int device_cu_count();
 // pointwise on codes (conv_pw_codes.hpp): codes in, codes or float32 out; the SAME prepared blob as launch_pointwise
 bool pwc_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, int post_flags, bool y_codes);
 int launch_pwc(const slfp_conv2d_desc& d, const ConvPlan& p, const uint8_t* x, const void* wfrag, const float* bias,
-               const PostOp& post, void* y, bool y_codes, float y_ka, int y_fmt, hipStream_t stream);
+               const PostOp& post, void* y, bool y_codes, float y_ka, int y_fmt, hipStream_t stream, const float* res = nullptr);
 // the MobileNetV1 image stem with code output (conv_direct.hip)
 bool stem_codes_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, int post_flags);
 int launch_stem_codes(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const float* wq_hwio, const float* bias,

@@ -461,6 +461,8 @@ def link_codes_traced(model, example_input):
         pool_uses[mod] = pool_uses.get(mod, 0) + 1
 
     def eligible(m, producer_side=False):
+        if producer_side and getattr(m, "_in_residual", False):
+            return False   # fuse_residual: the module's output is the block's float32 trunk (conv + identity), not a conv output
         return (m.q_bit in (8, 7) and not m.training and isinstance(m.padding, tuple) and (m._code_out is None or not producer_side)
                 and (m.bias is None or getattr(m, "_scaled_bias", False)) and not (m._post is not None and (int(m._post[2]) & 2)))
 
@@ -543,5 +545,117 @@ def unlink_codes(model):
             if hasattr(m, "_pre_link_post"):
                 m._post = m._pre_link_post
                 del m._pre_link_post
+            n += 1
+    return n
+
+
+# ------------------------------------------------------------------ residual add + ReLU in the last 1x1 conv's epilogue
+_BOTTLENECK_CHILDREN = ("conv1", "bn1", "conv2", "bn2", "conv3", "relu")
+
+
+def _bottleneck_forward(self, x):
+    """The dataflow of the torchvision Bottleneck the reference copies (nets_imgnet/resnet50.py:76-100) with the tail
+    relu(bn3(conv3(h)) + identity) handed to conv3 as its residual operand (bn3 is folded already)."""
+    out = self.relu(self.bn1(self.conv1(x)))
+    out = self.relu(self.bn2(self.conv2(out)))
+    identity = x if getattr(self, "downsample", None) is None else self.downsample(x)
+    return self.conv3(out, residual=identity)
+
+
+def _residual_candidate(blk):
+    if isinstance(blk, nn.Sequential) or "forward" in blk.__dict__:
+        return False
+    ch = blk._modules
+    if any(ch.get(k) is None for k in _BOTTLENECK_CHILDREN) or "downsample" not in ch and not hasattr(blk, "downsample"):
+        return False
+    conv3, bn3 = ch["conv3"], ch.get("bn3")
+    if not (_is_pw(conv3) and tuple(_pair2(conv3.padding)) == (0, 0) and conv3._code_out is None and isinstance(ch["relu"], nn.ReLU)):
+        return False
+    if bn3 is not None and not isinstance(bn3, nn.Identity):
+        return False   # fold it first (fuse_named_bn): the add follows the BatchNorm
+    if conv3._post is not None and (int(conv3._post[2]) & 3):
+        return False   # a ReLU / layer-output quantizer in front of the add is another block
+    return all(_is_conv_q(ch[k]) for k in ("conv1", "conv2"))
+
+
+def _pair2(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+def _restore_block(blk):
+    del blk.__dict__["forward"]
+    del blk.__dict__["_residual_fused"]
+    blk.conv3.residual_relu = False
+    del blk.conv3._in_residual
+
+
+def fuse_residual(model, example_input):
+    """After fuse_named_bn: every block that follows the torchvision Bottleneck naming (conv1 / bn1 / conv2 / bn2 / conv3 / bn3 /
+    relu / downsample children of a non-Sequential module; conv3 a 1x1 stride-1 Conv2d_Q whose BatchNorm is folded or absent)
+    gets an instance-level forward with the same dataflow that ends in conv3(h, residual=identity) with the ReLU folded:
+    out = relu(bn3(conv3(h)) + identity) becomes ONE launch (slfp_conv2d_fwd_res) instead of three, 8 B per trunk element
+    through HBM instead of 24.  A name is only a convention, so -- the rule link_codes_traced set -- one traced forward on
+    `example_input` records every candidate's input and output, each rewritten block must reproduce its recorded output
+    bit for bit on its recorded input (otherwise it is restored and not counted), and the rewritten model must reproduce
+    the logits bit for bit (otherwise everything is restored and 0 is returned).  Composes with fuse_named_bn,
+    link_codes_traced / unlink_codes in either order, and graph.GraphedModule.  Inference only (with grad enabled conv3
+    computes the same values with ATen).  Returns the number of blocks rewritten; unfuse_residual undoes it."""
+    import types
+    cands = [m for m in model.modules() if _residual_candidate(m)]
+    if not cands:
+        return 0
+    rec, hooks = {}, []
+    for blk in cands:
+        hooks.append(blk.register_forward_hook(lambda mod, inp, out: rec.__setitem__(mod, rec.get(mod, []) + [(inp, out)])))
+    try:
+        with torch.no_grad():
+            y0 = model(example_input)
+    finally:
+        for h in hooks:
+            h.remove()
+    done = []
+    for blk in cands:
+        calls = rec.get(blk, [])
+        if len(calls) != 1 or len(calls[0][0]) != 1 or not torch.is_tensor(calls[0][0][0]) or not torch.is_tensor(calls[0][1]):
+            continue   # not run, run twice, or not a tensor -> tensor block
+        x, want = calls[0][0][0], calls[0][1]
+        blk.conv3.residual_relu = True
+        blk.conv3._in_residual = True
+        blk.__dict__["_residual_fused"] = True
+        blk.__dict__["forward"] = types.MethodType(_bottleneck_forward, blk)
+        ok = False
+        try:
+            with torch.no_grad():
+                got = blk(x)
+            ok = torch.is_tensor(got) and got.dtype == want.dtype and got.shape == want.shape and torch.equal(got, want)
+        except Exception:
+            ok = False
+        if ok:
+            done.append(blk)
+        else:
+            _restore_block(blk)
+    rec.clear()
+    if not done:
+        return 0
+    ok = False
+    try:
+        with torch.no_grad():
+            y1 = model(example_input)
+        ok = y1.dtype == y0.dtype and torch.equal(y1, y0)
+    except Exception:
+        ok = False
+    if not ok:
+        for blk in done:
+            _restore_block(blk)
+        return 0
+    return len(done)
+
+
+def unfuse_residual(model):
+    """Undo fuse_residual."""
+    n = 0
+    for blk in model.modules():
+        if blk.__dict__.get("_residual_fused"):
+            _restore_block(blk)
             n += 1
     return n

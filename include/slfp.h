@@ -199,6 +199,26 @@ int slfp_conv2d_fwd_codes(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, c
 int slfp_conv2d_fwd_codes_ws(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
                              const float* bias, const float* post_scale, const float* post_shift, int relu, void* y,
                              void* workspace, void* stream);
+/* ---- residual operand: y = relu?(affine(conv(x)) + res) in ONE launch -------------------------------------------------
+ * The tail of every residual block, out = relu(bn3(conv3(h)) + identity) (nets_imgnet/resnet50.py:82-88), for the 1x1
+ * stride-1 layers of the pw_mfma_* family.  Per output element, in this order, every step rounded to float32:
+ *     r = the conv result with the reference's (out * Ka) * Kw roundings, exactly as slfp_conv2d_fwd_post computes it
+ *     t = fma(r, post_scale[c], post_shift[c])      when post_scale / post_shift are given
+ *     t = t + res[i]                                one float32 add; res is indexed like y
+ *     y[i] = (relu & SLFP_POST_RELU) ? max(t, 0) : t
+ * which is what slfp_conv2d_fwd_post(relu = 0) followed by a float32 add and a ReLU pass computes: the result is
+ * bit-identical to that sequence on NaN-free data, with 8 B per output element through HBM instead of 24.
+ * io->x_codes 0 / 1: x is float32, or the uint8 codes slfp_conv2d_fwd_codes takes; io->y_codes must be 0.  res and y: float32
+ * NHWC tensors of the output shape, 16-byte aligned, not overlapping (SLFP_ERR_BAD_ARG otherwise).  Supported: 1x1, stride 1,
+ * groups 1, both layouts NHWC, C_in and C_out multiples of 4, in the F16X1, F16X3 and SFP<3,3> operand modes with float32
+ * input, and wherever slfp_conv2d_codes_supported says yes with code input.  Everything else -- dense, depthwise and stem
+ * layers, strided 1x1, NCHW, SLFP_POST_LAYEROUT, y_codes -- returns SLFP_ERR_UNSUPPORTED.  `workspace` is reserved (no
+ * supported layer needs one; pass NULL).  slfp_conv2d_res_supported answers 1 / 0 without device work. */
+int slfp_conv2d_res_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int relu);
+int slfp_conv2d_fwd_res(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
+                        const float* bias, const float* post_scale, const float* post_shift, int relu,
+                        const float* res, float* y, void* workspace, void* stream);
+
 /* nn.MaxPool2d (floor mode, dilation 1) on a tensor of activation codes (NHWC, C a multiple of 4; 16-byte aligned): the class
  * of a window's largest input is the highest class among its codes in the order of the classes' pre-images (the clamp literal
  * of Qbits 8 ranks above the top regular code, "tiny" above exact zero, signed codes by decreasing magnitude), so

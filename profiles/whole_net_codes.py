@@ -43,5 +43,9 @@ for net in ("vgg16", "resnet50"):
         n_l = fusion.link_codes(m, x) + fusion.link_codes_traced(m, x)
         same = bool(torch.equal(m(x), y_f))
     r_codes = rate(m, x)
-    print(f"{net} batch {batch}: stock modules {r_stock:.0f} images/s; {n_f} conv+bn pairs fused {r_fused:.0f}; + {n_l} code hand-overs {r_codes:.0f} "
-          f"(logits bit-identical: {same})")
+    with torch.no_grad():   # residual add + ReLU in the last 1x1 conv's epilogue (fusion.fuse_residual): blocks with the Bottleneck naming
+        n_r = fusion.fuse_residual(m, x)
+        same = same and bool(torch.equal(m(x), y_f))
+    r_res = rate(m, x) if n_r else r_codes
+    print(f"{net} batch {batch}: stock modules {r_stock:.0f} images/s; {n_f} conv+bn pairs fused {r_fused:.0f}; + {n_l} code hand-overs {r_codes:.0f}; "
+          f"+ {n_r} residual tails fused {r_res:.0f} (logits bit-identical: {same})")
