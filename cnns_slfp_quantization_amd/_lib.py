@@ -29,6 +29,7 @@ SYMBOLS = (
     "slfp_debug_enc_hl_mismatches", "slfp_sgd_step_f32", "slfp_debug_dw3x3_variant",
     "slfp_conv2d_bwd_supported", "slfp_conv2d_bwd_kernel_name", "slfp_conv2d_bwd_workspace_bytes", "slfp_conv2d_bwd",
     "slfp_conv2d_res_supported", "slfp_conv2d_fwd_res",
+    "slfp_conv2d_codes_slice_supported", "slfp_conv2d_fwd_codes_slice", "slfp_maxpool2d_codes_ex", "slfp_maxpool2d_out_shape",
 )
 
 
@@ -126,6 +127,10 @@ def load():
         "slfp_conv2d_bwd": (ci, [dp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "slfp_conv2d_res_supported": (ci, [dp, ctypes.POINTER(ConvIo), ci, ci]),
         "slfp_conv2d_fwd_res": (ci, [dp, ctypes.POINTER(ConvIo), vp, vp, vp, vp, vp, ci, vp, vp, vp, vp]),
+        "slfp_conv2d_codes_slice_supported": (ci, [dp, ctypes.POINTER(ConvIo), ci, ci, i64]),
+        "slfp_conv2d_fwd_codes_slice": (ci, [dp, ctypes.POINTER(ConvIo), vp, vp, vp, vp, vp, ci, vp, i64, vp, vp]),
+        "slfp_maxpool2d_codes_ex": (ci, [vp, vp, i64, i64, i64, i64, ci, ci, ci, ci, ci, ci, ci, ci, vp]),
+        "slfp_maxpool2d_out_shape": (ci, [i64, i64, ci, ci, ci, ci, ci, ci, ci, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
     }
     assert set(sigs) == set(SYMBOLS)
     for name, (res, args) in sigs.items():

@@ -215,18 +215,19 @@ def _conv_weights(mod, desc, weight, stream, cache, kernel=None, want_weight_q=F
 class _Plan:
     """What one (module, input shape, layout, scales, precision) combination resolves to in the C ABI; for the code path
     also its io struct and whether libslfp_hip has a kernel for the combination."""
-    __slots__ = ("desc", "y_shape", "ws_bytes", "kernel", "io", "codes_ok", "res_ok")
+    __slots__ = ("desc", "y_shape", "ws_bytes", "kernel", "io", "codes_ok", "res_ok", "slice_ok")
 
     def __init__(self, desc, y_shape, ws_bytes, kernel):
         self.desc, self.y_shape, self.ws_bytes, self.kernel = desc, y_shape, ws_bytes, kernel
-        self.io, self.codes_ok, self.res_ok = None, False, False
+        self.io, self.codes_ok, self.res_ok, self.slice_ok = None, False, False, False
 
 
 def _plan(mod, x, weight, nhwc_in, nhwc_out, codes=None, bias=None):
     """Everything that depends only on (module geometry, input shape, layouts, scales, precision) is computed once per
     distinct key and kept on the module: descriptor, output shape, workspace size, kernel name.  codes: None for the
     float32 interface, ("codes", does x hold codes, mod._code_out) for slfp_conv2d_fwd_codes, ("res", does x hold codes, ReLU
-    after the add) for slfp_conv2d_fwd_res."""
+    after the add) for slfp_conv2d_fwd_res, ("slice", does x hold codes, mod._code_out, channel count of the wider tensor) for
+    slfp_conv2d_fwd_codes_slice."""
     shape = x.shape
     key = (codes, shape, nhwc_in, nhwc_out, _scale_key(mod.Ka, "Ka"), _scale_key(mod.Kw, "Kw"), options.mfma_passes,
            mod.stride, mod.padding, mod.dilation, weight.shape)
@@ -247,6 +248,11 @@ def _plan(mod, x, weight, nhwc_in, nhwc_out, codes=None, bias=None):
             # an epilogue ReLU or layer-output quantizer would sit BEFORE the add: not what the residual kernels compute
             plan.res_ok = flags == 0 and bool(L.slfp_conv2d_res_supported(ctypes.byref(d), ctypes.byref(plan.io),
                                                                           1 if bias is not None else 0, 1 if codes[2] else 0))
+        elif codes is not None and codes[0] == "slice":
+            plan.io = _conv_io(codes[1], codes[2])
+            flags = int(mod._post[2]) if mod._post is not None else 0
+            plan.slice_ok = bool(L.slfp_conv2d_codes_slice_supported(ctypes.byref(d), ctypes.byref(plan.io),
+                                                                     1 if bias is not None else 0, flags, int(codes[3])))
         elif codes is not None:
             plan.io = _conv_io(codes[1], codes[2])
             flags = int(mod._post[2]) if mod._post is not None else 0
@@ -381,6 +387,54 @@ def _hip_conv2d_codes(mod, x, weight, bias):
         mod._last_input, mod._last_codes = x.detach(), None
     mod._input_q = None
     return y
+
+
+def _hip_conv2d_slice(mod, x, weight, bias, out_slice):
+    """Conv2d_Q.forward_slice(x, (buffer, c_off)) as ONE slfp_conv2d_fwd_codes_slice call: the codes this linked producer
+    (mod._code_out) would return go into buffer[:, c_off:c_off + C_out] of a wider uint8 channels_last tensor instead of one of
+    their own -- the concat of a Fire module without the copy (fusion.fuse_fire).  Same plan cache and weight blob as the other
+    paths.  There is no second way to compute this: a combination without a kernel raises."""
+    try:
+        buf, c_off = out_slice
+        c_off = int(c_off)
+    except (TypeError, ValueError):
+        raise TypeError("Conv2d_Q: out_slice must be (uint8 channels_last buffer, channel offset)") from None
+    x_codes = torch.is_tensor(x) and x.dtype == torch.uint8
+    nhwc = torch.channels_last
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and (x_codes or x.dtype == torch.float32)
+            and x.is_contiguous(memory_format=nhwc) and weight.device == x.device):
+        raise RuntimeError("Conv2d_Q: out_slice needs a 4-d channels_last ROCm input (float32 or uint8 codes) on the weights' device")
+    if not (torch.is_tensor(buf) and buf.dtype == torch.uint8 and buf.dim() == 4 and buf.device == x.device
+            and buf.is_contiguous(memory_format=nhwc)):
+        raise RuntimeError("Conv2d_Q: out_slice's buffer must be a 4-d uint8 channels_last tensor on the input's device")
+    ld = buf.shape[1]
+    plan = _plan(mod, x, weight, True, True, ("slice", x_codes, mod._code_out, ld), bias)
+    n, c_out, ho, wo = plan.y_shape
+    if (buf.shape[0], buf.shape[2], buf.shape[3]) != (n, ho, wo) or c_off < 0 or c_off + c_out > ld:
+        raise RuntimeError(f"Conv2d_Q: out_slice channels [{c_off}, {c_off + c_out}) of a buffer of shape {list(buf.shape)} do not "
+                           f"hold this layer's output {list(plan.y_shape)}")
+    if not plan.slice_ok or c_off % 16 or buf.data_ptr() % 16:
+        raise RuntimeError(f"Conv2d_Q: no kernel writes this layer's codes into channels {c_off}.. of a {ld}-channel tensor "
+                           "(slfp_conv2d_codes_slice_supported; offset and width are multiples of 16)")
+    L = _lib.load()
+    d = plan.desc
+    with _on_device(x.device):
+        stream = torch.cuda.current_stream(x.device)
+        blob = _conv_weights(mod, d, weight, stream, True, plan.kernel)
+        b, ps, psh, flags = _epilogue_args(mod, bias, x.device)
+        ws = _workspace(x.device, plan.ws_bytes) if plan.ws_bytes else None
+        _lib.check(L.slfp_conv2d_fwd_codes_slice(ctypes.byref(d), ctypes.byref(plan.io), x.data_ptr(), blob.data_ptr(),
+                                                 b.data_ptr() if b is not None else None,
+                                                 ps.data_ptr() if ps is not None else None,
+                                                 psh.data_ptr() if psh is not None else None, flags, buf.data_ptr() + c_off, ld,
+                                                 ws.data_ptr() if ws is not None else None, stream.cuda_stream))
+    mod._last_kernel = plan.kernel + ("+codes_in" if x_codes else "") + "+codes_out+slice"
+    if x_codes:
+        mod._last_input, mod._last_codes = None, x.detach()
+    else:
+        mod._last_input, mod._last_codes = x.detach(), None
+    mod._input_q = None
+    return buf
 
 
 def _hip_conv2d_res(mod, x, weight, bias, residual, relu):
@@ -619,6 +673,23 @@ def _conv_class(q_bit, Kw, Ka, bias_default, scaled_bias):
                     out = torch.relu(out)
             self.output = out
             return out
+
+        def forward_slice(self, input, out_slice):
+            """`out_slice=(buffer, c_off)`: a linked code producer writes its codes into buffer[:, c_off:c_off + C_out] (uint8,
+            channels_last, wider than this layer) in ONE launch (slfp_conv2d_fwd_codes_slice; `_last_kernel` ends in "+slice")
+            and returns `buffer`: the concat of a Fire module without the copy (fusion.fuse_fire).  Anything else -- an unlinked
+            module, training, a layer without such a kernel -- raises.  A method of its own, not a keyword of forward(): the
+            reference's forward surface (and the `residual` keyword beside it) stays as it is.  Like forward() called directly
+            it runs no module hooks."""
+            if (self._code_out is None or self.q_bit not in (8, 7) or self.training
+                    or (self.bias is not None and not scaled_bias)):
+                raise RuntimeError("Conv2d_Q: out_slice is for a linked code producer in inference (fusion.link_codes / fuse_fire "
+                                   "set `_code_out`; module.eval(); the scaled-bias class)")
+            if self._grouped_stash:
+                self._grouped_stash = False
+            with torch.no_grad():
+                self.output = _hip_conv2d_slice(self, input, self.weight, self.bias, out_slice)
+            return self.output
 
         def forward(self, input, order=None, *, residual=None):
             """Conv2d_Q.forward of the reference (utils/conv2d_func.py:20-25).  `residual` (keyword-only, not part of the

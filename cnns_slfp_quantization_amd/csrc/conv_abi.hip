@@ -452,9 +452,51 @@ extern "C" int slfp_conv2d_fwd_codes(const slfp_conv2d_desc* d, const slfp_conv2
     return slfp_conv2d_fwd_codes_ws(d, io, x, wprep, bias, post_scale, post_shift, relu, y, nullptr, stream);
 }
 
+// y_ld: 0 = y is a dense tensor (slfp_conv2d_fwd_codes_ws); else the channel count of the wider code tensor y is a slice of
+static int fwd_codes_any(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
+                         const float* bias, const float* post_scale, const float* post_shift, int relu, void* y, int64_t y_ld,
+                         void* workspace, void* stream);
+
 extern "C" int slfp_conv2d_fwd_codes_ws(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
                                         const float* bias, const float* post_scale, const float* post_shift, int relu, void* y,
                                         void* workspace, void* stream) {
+    return fwd_codes_any(d, io, x, wprep, bias, post_scale, post_shift, relu, y, 0, workspace, stream);
+}
+
+// ---- code output into a channel slice of a wider NHWC code tensor (include/slfp.h: slfp_conv2d_fwd_codes_slice) ----
+// The kernels whose code store takes a pixel stride: the pw_mfma_* code kernels (route 2) and the dense k x k code epilogue (route 4).
+static bool slice_route(int route) { return route == 2 || route == 4; }
+
+extern "C" int slfp_conv2d_codes_slice_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int relu,
+                                                 int64_t y_ld) {
+    ConvPlan p;
+    if (!d || !io || !io->y_codes) return 0;
+    if (!slice_route(codes_route(d, io, has_bias != 0, relu, &p))) return 0;
+    return (y_ld >= d->c_out && y_ld % 16 == 0 && y_ld <= 0x7FFFFFFF) ? 1 : 0;
+}
+
+extern "C" int slfp_conv2d_fwd_codes_slice(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
+                                           const float* bias, const float* post_scale, const float* post_shift, int relu, void* y,
+                                           int64_t y_ld, void* workspace, void* stream) {
+    if (!d || !io) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_codes_slice: null descriptor");
+    ConvPlan p;
+    const int rc = make_plan(d, &p);
+    if (rc != SLFP_OK) return rc;
+    if (!x || !wprep || !y) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_codes_slice: null pointer");
+    if (!io->y_codes) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_codes_slice: a channel slice is written as codes (io->y_codes == 1)");
+    if (!aligned16(y)) return fail(SLFP_ERR_ALIGNMENT, "slfp_conv2d_fwd_codes_slice: y (the slice's first channel) must be 16-byte aligned");
+    if (y_ld < d->c_out || y_ld % 16 != 0 || y_ld > 0x7FFFFFFF)
+        return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_codes_slice: y_ld = %lld must be a multiple of 16, >= C_out = %lld", (long long)y_ld,
+                    (long long)d->c_out);
+    if (!slice_route(codes_route(d, io, bias != nullptr, relu, &p)))
+        return fail(SLFP_ERR_UNSUPPORTED, "slfp_conv2d_fwd_codes_slice: this layer / io combination has no code kernel with a channel-slice "
+                                          "store (slfp_conv2d_codes_slice_supported)");
+    return fwd_codes_any(d, io, x, wprep, bias, post_scale, post_shift, relu, y, y_ld, workspace, stream);
+}
+
+static int fwd_codes_any(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
+                         const float* bias, const float* post_scale, const float* post_shift, int relu, void* y, int64_t y_ld,
+                         void* workspace, void* stream) {
     if (!d || !io) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_codes: null descriptor");
     ConvPlan p;
     int rc = make_plan(d, &p);
@@ -472,18 +514,20 @@ extern "C" int slfp_conv2d_fwd_codes_ws(const slfp_conv2d_desc* d, const slfp_co
     const PostOp post{post_scale, post_shift, (relu & SLFP_POST_RELU) ? 1 : 0, 0};
     const int y_fmt = io->y_qbits == 7 ? kFmtSfp7 : kFmtAct8;
     hipStream_t st = as_stream(stream);
+    if (route == 1 && y_ld) return fail(SLFP_ERR_UNSUPPORTED, "slfp_conv2d_fwd_codes_slice: no channel-slice store in this kernel family");
     if (route == 1)
         return launch_dwc(*d, p, reinterpret_cast<const uint8_t*>(x), reinterpret_cast<const float*>(wprep), post, y,
                           io->y_codes != 0, io->y_ka, y_fmt, st);
     if (route == 2)
-        return launch_pwc(*d, p, reinterpret_cast<const uint8_t*>(x), wprep, bias, post, y, io->y_codes != 0, io->y_ka, y_fmt, st);
+        return launch_pwc(*d, p, reinterpret_cast<const uint8_t*>(x), wprep, bias, post, y, io->y_codes != 0, io->y_ka, y_fmt, st, nullptr, y_ld);
     if (route == 4) {
         const size_t ws_need = workspace_bytes_for(d, p);
         if (ws_need && (!workspace || !aligned16(workspace)))
             return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_codes_ws: %zu bytes of 16-byte aligned workspace required (slfp_conv2d_workspace_bytes)", ws_need);
-        const CodeIo cio{io->x_codes != 0, io->y_codes != 0, io->y_ka, y_fmt};
+        const CodeIo cio{io->x_codes != 0, io->y_codes != 0, io->y_ka, y_fmt, y_ld};
         return launch_dense_mfma_io(*d, p, x, wprep, bias, post, y, workspace, cio, st);
     }
+    if (y_ld) return fail(SLFP_ERR_UNSUPPORTED, "slfp_conv2d_fwd_codes_slice: no channel-slice store in this kernel family");
     const CodeIo cio{false, true, io->y_ka, y_fmt};
     if (route == 5) return launch_stem_small_io(*d, p, reinterpret_cast<const float*>(x), wprep, bias, post, y, cio, st);
     return launch_stem_codes(*d, p, reinterpret_cast<const float*>(x), reinterpret_cast<const float*>(wprep), bias, post, y, cio, st);

@@ -65,6 +65,7 @@ struct DenseParams {
     // k_dense3x3_res<ENCX>: the float32 input itself (C_in == 64) is encoded where the halo is staged -- no pre-pass, no fp16 copy
     const float* x32;
     EncArgsCompact enc_in;   // kEncF16P table of (Ka, fmt_act)
+    int y_ld;             // yc: bytes from one pixel's codes to the next (O: a dense tensor; more: a channel slice of a wider one)
 };
 
 __device__ __forceinline__ uint32_t dn_x_off(int row, int chunk16) {
@@ -211,7 +212,7 @@ __device__ __forceinline__ void dense_epilogue_apply(const DenseParams& p, const
             rows_transpose4(c[0], c[1], c[2], c[3]);
             if (goh < p.Ho && gow < p.Wo && chs < p.O) {
                 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-                *reinterpret_cast<u32x4*>(p.yc + (((size_t)n * p.Ho + goh) * p.Wo + gow) * p.O + chs) = u32x4{c[0], c[1], c[2], c[3]};
+                *reinterpret_cast<u32x4*>(p.yc + (((size_t)n * p.Ho + goh) * p.Wo + gow) * p.y_ld + chs) = u32x4{c[0], c[1], c[2], c[3]};
             }
         }
         return;
@@ -1028,6 +1029,9 @@ int launch_dense_mfma_io(const slfp_conv2d_desc& d, const ConvPlan& plan, const 
         p.y_sgn = post.relu ? 0 : 1;
         p.y_fmt = io.y_fmt;
     }
+    if (io.y_ld && (!io.y_codes || io.y_ld < d.c_out || io.y_ld % 16 || io.y_ld > 0x7FFFFFFF))
+        return fail(SLFP_ERR_BAD_ARG, "dense MFMA conv: a channel-slice output needs code output and a pixel stride that is a multiple of 16, >= C_out");
+    p.y_ld = io.y_ld ? (int)io.y_ld : (int)d.c_out;
     p.wlo = p.w + (size_t)d.kh * d.kw * plan.k_pad * plan.n_pad;   // second plane of the blob (float32-equivalent mode)
     p.N = (int)d.n; p.H = (int)d.h; p.W = (int)d.w; p.Cp = cp; p.O = (int)d.c_out;
     p.KH = (int)d.kh; p.KW = (int)d.kw; p.S = d.stride_h; p.ph = d.pad_h; p.pw = d.pad_w;

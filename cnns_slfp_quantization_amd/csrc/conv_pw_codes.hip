@@ -46,6 +46,7 @@ struct PwcParams {
     int fmt_out;          // YC: format of the output codes (kFmtAct8 | kFmtSfp7)
     PostOp post;
     EncArgs enc;          // YC: code table of the consumer's Ka (kEncCode)
+    int y_ld;             // YC: bytes from one pixel's codes to the next (N: a dense tensor; more: a channel slice of a wider one)
 };
 
 typedef uint32_t u32x4c __attribute__((ext_vector_type(4)));
@@ -71,10 +72,15 @@ constexpr int kPwcThreads = 512;
 // KS: 32-deep k-steps (K = 32 * KS exactly); XW: K is a multiple of 64 (16-byte code loads + transpose), else two
 // dword loads per k-step; YC: output codes (N a multiple of 16), else float32.  RES (float32 out): y = relu?(affine(conv) + res),
 // each 16 bytes of p.res loaded with the address of the store they pair with, one channel tile ahead of its MFMA sweep.
-template <int FMT, int KS, bool XW, bool YC, bool RES = false>
+// HALF (K = 32 * KS - 16, SqueezeNet's 16- and 48-channel squeeze outputs): only channels 0..15 of the last
+// k-step exist.  Its second dword -- channels 16..31, which would be the NEXT pixel's codes, or past the tensor for the last
+// pixel -- is not loaded: that half of the fragment is the fp16 zero (the blob holds zero weights there; the float32
+// interface's k_pw_stream feeds the same zeros), so the accumulators are the same bit for bit.
+template <int FMT, int KS, bool XW, bool YC, bool RES = false, bool HALF = false>
 __global__ __launch_bounds__(kPwcThreads) void k_pwc_stream(const PwcParams p) {
     static_assert(!XW || KS % 2 == 0, "16-byte code loads cover two k-steps");
     static_assert(!RES || !YC, "residual operand: float32 output only");
+    static_assert(!HALF || !XW, "a half-live last k-step is loaded dword by dword");
     __shared__ __attribute__((aligned(16))) uint32_t sdec[256];
     __shared__ __attribute__((aligned(16))) unsigned char senc[YC ? kPwTab : 16];
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -124,12 +130,19 @@ __global__ __launch_bounds__(kPwcThreads) void k_pwc_stream(const PwcParams p) {
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
                 cw[ks][0] = *reinterpret_cast<const uint32_t*>(xr + ks * 32 + kq * 4);
-                cw[ks][1] = *reinterpret_cast<const uint32_t*>(xr + ks * 32 + 16 + kq * 4);
+                if (!HALF || ks + 1 < KS) cw[ks][1] = *reinterpret_cast<const uint32_t*>(xr + ks * 32 + 16 + kq * 4);
             }
         }
         half8 xh[KS];
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) xh[ks] = dec_frag(cw[ks][0], cw[ks][1], dtab);
+        for (int ks = 0; ks < KS; ++ks) {
+            if (HALF && ks + 1 == KS) {
+                const uint2 pa = dec4_f16(cw[ks][0], dtab);
+                xh[ks] = __builtin_bit_cast(half8, u32x4c{pa.x, pa.y, 0u, 0u});
+            } else {
+                xh[ks] = dec_frag(cw[ks][0], cw[ks][1], dtab);
+            }
+        }
 
         auto tile_out = [&](int j) {
             floatx4 acc = floatx4{0.f, 0.f, 0.f, 0.f};
@@ -159,7 +172,7 @@ __global__ __launch_bounds__(kPwcThreads) void k_pwc_stream(const PwcParams p) {
             return r;
         };
         if constexpr (YC) {
-            uint8_t* yr = reinterpret_cast<uint8_t*>(p.y) + (size_t)m * p.N;
+            uint8_t* yr = reinterpret_cast<uint8_t*>(p.y) + (size_t)m * p.y_ld;
             for (int j0 = 0; j0 < p.n_tiles; j0 += 4) {   // n_tiles is a multiple of 4 (the blob is padded to 64 channels)
                 uint32_t c[4];
 #pragma unroll
@@ -329,7 +342,7 @@ __global__ __launch_bounds__(kSliceThreads, RES ? 4 : 1) void k_pwc_slice(const 
             return r;
         };
         if constexpr (YC) {
-            uint8_t* yr = reinterpret_cast<uint8_t*>(p.y) + (size_t)m * p.N + n_lo;
+            uint8_t* yr = reinterpret_cast<uint8_t*>(p.y) + (size_t)m * p.y_ld + n_lo;
 #pragma unroll
             for (int j0 = 0; j0 < NTS; j0 += 4) {
                 uint32_t c[4];
@@ -553,7 +566,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_ti
             const int row = (wm * MT + i) * 16 + col;
             const int n = (ntile0 + kq) * 16;
             if (row < p.rb && m0 + row < p.M && n < p.N)
-                *reinterpret_cast<u32x4c*>(yb + (size_t)(m0 + row) * p.N + n) = u32x4c{c[0], c[1], c[2], c[3]};
+                *reinterpret_cast<u32x4c*>(yb + (size_t)(m0 + row) * p.y_ld + n) = u32x4c{c[0], c[1], c[2], c[3]};
         }
     } else {
         // float32 out: staged through a per-wave LDS area into 256-byte runs (4 rows x the wave's 64 channels per store)
@@ -586,20 +599,22 @@ static bool pwc_stream_fits(const ConvPlan& plan) { return pointwise_stream_fits
 bool pwc_applicable(const slfp_conv2d_desc& d, const ConvPlan& plan, int post_flags, bool y_codes) {
     if (plan.family != kPointwise || plan.repad || plan.passes != 1) return false;
     if (post_flags & SLFP_POST_LAYEROUT) return false;
-    if (d.c_in % 32 != 0) return false;
     if (y_codes ? (d.c_out % 16 != 0) : (d.c_out % 4 != 0)) return false;
+    // 16 and 48 channels (a half-live last k-step: k_pwc_stream's HALF form), inside the LDS-resident kernel's range only
+    if (d.c_in == 16 || d.c_in == 48) return pwc_stream_fits(plan);
+    if (d.c_in % 32 != 0) return false;
     if (pwc_stream_fits(plan)) {
         const int ks = (int)(d.c_in / 32);
-        return ks == 1 || ks == 2 || ks == 4 || ks == 8;
+        return ks == 1 || ks == 2 || ks == 3 || ks == 4 || ks == 8;   // 3: the 96 -> 16 squeeze behind SqueezeNet's stem
     }
     return d.c_in % 64 == 0;
 }
 
-template <int FMT, int KS, bool XW>
+template <int FMT, int KS, bool XW, bool HALF = false>
 static int launch_pwc_stream(PwcParams& p, bool y_codes, hipStream_t stream) {
     const size_t lds = (size_t)p.n_tiles * p.KS * 1024 + (size_t)3 * p.n_tiles * 16 * sizeof(float);
     const size_t lds_total = lds + 1024 + (y_codes ? kPwTab : 16);
-    auto fn = y_codes ? k_pwc_stream<FMT, KS, XW, true> : (p.res ? k_pwc_stream<FMT, KS, XW, false, true> : k_pwc_stream<FMT, KS, XW, false>);
+    auto fn = y_codes ? k_pwc_stream<FMT, KS, XW, true, false, HALF> : (p.res ? k_pwc_stream<FMT, KS, XW, false, true, HALF> : k_pwc_stream<FMT, KS, XW, false, false, HALF>);
     int rc = raise_lds_limit(reinterpret_cast<const void*>(fn), lds);
     if (rc != SLFP_OK) return rc;
     int per_cu = resident_blocks_per_cu(reinterpret_cast<const void*>(fn), kPwcThreads, lds);
@@ -667,9 +682,12 @@ static int launch_pwc_fmt(PwcParams& p, const ConvPlan& plan, bool y_codes, hipS
         return launch_pwc_slice<FMT, 4>(p, y_codes, stream);
     }
     if (pwc_stream_fits(plan)) {
+        if (p.K == 16) return launch_pwc_stream<FMT, 1, false, true>(p, y_codes, stream);
+        if (p.K == 48) return launch_pwc_stream<FMT, 2, false, true>(p, y_codes, stream);
         switch (p.K / 32) {
             case 1: return launch_pwc_stream<FMT, 1, false>(p, y_codes, stream);
             case 2: return launch_pwc_stream<FMT, 2, true>(p, y_codes, stream);
+            case 3: return launch_pwc_stream<FMT, 3, false>(p, y_codes, stream);
             case 4: return launch_pwc_stream<FMT, 4, true>(p, y_codes, stream);
             case 8: return launch_pwc_stream<FMT, 8, true>(p, y_codes, stream);
             default: return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): unsupported channel count %d", p.K);
@@ -682,12 +700,15 @@ static int launch_pwc_fmt(PwcParams& p, const ConvPlan& plan, bool y_codes, hipS
 }
 
 int launch_pwc(const slfp_conv2d_desc& d, const ConvPlan& plan, const uint8_t* x, const void* wfrag, const float* bias,
-               const PostOp& post, void* y, bool y_codes, float y_ka, int y_fmt, hipStream_t stream, const float* res) {
+               const PostOp& post, void* y, bool y_codes, float y_ka, int y_fmt, hipStream_t stream, const float* res, int64_t y_ld) {
     if (res && y_codes) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): a residual operand needs float32 output");
+    if (y_ld && (!y_codes || y_ld < d.c_out || y_ld % 16 || y_ld > 0x7FFFFFFF))
+        return fail(SLFP_ERR_BAD_ARG, "pointwise (codes): a channel-slice output needs code output and a pixel stride that is a multiple of 16, >= C_out");
     PwcParams p;
     p.post = post;
     p.x = x; p.bias = bias; p.y = y; p.res = res;
     p.K = (int)d.c_in; p.N = (int)d.c_out;
+    p.y_ld = y_ld ? (int)y_ld : p.N;
     p.KS = (int)(plan.k_pad / 32);
     p.n_tiles = (int)(plan.n_pad / 16);
     p.whi = reinterpret_cast<const _Float16*>(wfrag);

@@ -84,16 +84,48 @@ __global__ __launch_bounds__(256) void k_maxpool_codes(const uint8_t* __restrict
 
 }  // namespace slfp
 
+// nn.MaxPool2d's output size along one axis; 0: bad geometry.  ceil mode rounds the window count up, then drops a last window
+// that would start past the input and its left padding (it would hold padding only) -- ATen's pooling_output_shape.
+static int64_t pool_out_size(int64_t in, int k, int s, int p, int ceil_mode) {
+    if (in <= 0 || k <= 0 || s <= 0 || p < 0 || 2 * p > k) return 0;
+    const int64_t span = in + 2 * (int64_t)p - k;
+    if (!ceil_mode) return span / s + 1;   // slfp_maxpool2d_codes' size, unchanged
+    if (span < 0) return 0;
+    int64_t out = (span + s - 1) / s + 1;
+    if ((out - 1) * s >= in + p) --out;
+    // every window holds at least one input element (the kernel skips out-of-image taps): first -p + k > 0, last start < in
+    if (out <= 0 || (out - 1) * s - p >= in || k - p <= 0) return 0;
+    return out;
+}
+
+extern "C" int slfp_maxpool2d_out_shape(int64_t h, int64_t w, int kh, int kw, int sh, int sw, int ph, int pw, int ceil_mode,
+                                        int64_t* h_out, int64_t* w_out) {
+    using namespace slfp;
+    if (ceil_mode != 0 && ceil_mode != 1) return fail(SLFP_ERR_BAD_ARG, "slfp_maxpool2d_out_shape: ceil_mode must be 0 or 1");
+    const int64_t ho = pool_out_size(h, kh, sh, ph, ceil_mode), wo = pool_out_size(w, kw, sw, pw, ceil_mode);
+    if (ho <= 0 || wo <= 0) return fail(SLFP_ERR_SHAPE, "slfp_maxpool2d_out_shape: bad geometry");
+    if (h_out) *h_out = ho;
+    if (w_out) *w_out = wo;
+    return SLFP_OK;
+}
+
 extern "C" int slfp_maxpool2d_codes(const uint8_t* x, uint8_t* y, int64_t n, int64_t h, int64_t w, int64_t c, int kh, int kw, int sh,
                                     int sw, int ph, int pw, int qbits, void* stream) {
+    return slfp_maxpool2d_codes_ex(x, y, n, h, w, c, kh, kw, sh, sw, ph, pw, qbits, 0, stream);
+}
+
+extern "C" int slfp_maxpool2d_codes_ex(const uint8_t* x, uint8_t* y, int64_t n, int64_t h, int64_t w, int64_t c, int kh, int kw, int sh,
+                                       int sw, int ph, int pw, int qbits, int ceil_mode, void* stream) {
     using namespace slfp;
     if (!x || !y) return fail(SLFP_ERR_BAD_ARG, "slfp_maxpool2d_codes: null pointer");
     if (qbits != 8 && qbits != 7) return fail(SLFP_ERR_BAD_ARG, "slfp_maxpool2d_codes: qbits must be 8 or 7");
+    if (ceil_mode != 0 && ceil_mode != 1) return fail(SLFP_ERR_BAD_ARG, "slfp_maxpool2d_codes: ceil_mode must be 0 or 1");
     if (n < 0 || h <= 0 || w <= 0 || c <= 0 || kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 || ph < 0 || pw < 0 || 2 * ph > kh || 2 * pw > kw)
         return fail(SLFP_ERR_SHAPE, "slfp_maxpool2d_codes: bad geometry");
     if (c % 4) return fail(SLFP_ERR_UNSUPPORTED, "slfp_maxpool2d_codes: channel count must be a multiple of 4");
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) return fail(SLFP_ERR_ALIGNMENT, "slfp_maxpool2d_codes: 16-byte aligned pointers");
-    const int64_t ho = (h + 2 * ph - kh) / sh + 1, wo = (w + 2 * pw - kw) / sw + 1;   // floor mode (ceil_mode = False)
+    // floor mode (ceil_mode = False) or nn.MaxPool2d(ceil_mode=True)'s sizes
+    const int64_t ho = pool_out_size(h, kh, sh, ph, ceil_mode), wo = pool_out_size(w, kw, sw, pw, ceil_mode);
     if (ho <= 0 || wo <= 0) return fail(SLFP_ERR_SHAPE, "slfp_maxpool2d_codes: empty output");
     if (n == 0) return SLFP_OK;
     const int vec = (c % 16 == 0) ? 16 : 4;

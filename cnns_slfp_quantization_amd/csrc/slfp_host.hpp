@@ -135,6 +135,7 @@ struct CodeIo {
     bool y_codes;     // y receives uint8 codes of QA(out / y_ka) in format y_fmt instead of float32
     float y_ka;
     int y_fmt;        // kFmtAct8 | kFmtSfp7
+    int64_t y_ld = 0; // y_codes: channel count of the (wider) NHWC code tensor y is a channel slice of; 0: y is dense (C_out)
 };
 // Workgroups of `fn` (block size, dynamic LDS) that fit one CU at once (hipOccupancyMaxActiveBlocksPerMultiprocessor, cached
 // per device / function / LDS size): how persistent grids are sized.  >= 1.
@@ -144,7 +145,8 @@ int device_cu_count();
 // pointwise on codes (conv_pw_codes.hpp): codes in, codes or float32 out; the SAME prepared blob as launch_pointwise
 bool pwc_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, int post_flags, bool y_codes);
 int launch_pwc(const slfp_conv2d_desc& d, const ConvPlan& p, const uint8_t* x, const void* wfrag, const float* bias,
-               const PostOp& post, void* y, bool y_codes, float y_ka, int y_fmt, hipStream_t stream, const float* res = nullptr);
+               const PostOp& post, void* y, bool y_codes, float y_ka, int y_fmt, hipStream_t stream, const float* res = nullptr,
+               int64_t y_ld = 0);   // y_ld: code output into a channel slice (see CodeIo::y_ld); 0: dense
 // the MobileNetV1 image stem with code output (conv_direct.hip)
 bool stem_codes_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, int post_flags);
 int launch_stem_codes(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const float* wq_hwio, const float* bias,

@@ -299,7 +299,8 @@ def unfuse_dw_pw(model):
 
 # ------------------------------------------------------------------ 1-byte activation codes between layers
 class CodeMaxPool2d(nn.Module):
-    """An nn.MaxPool2d inside a code chain (link_codes): uint8 codes are pooled as codes (slfp_maxpool2d_codes: the class of a
+    """An nn.MaxPool2d inside a code chain (link_codes): uint8 codes are pooled as codes (slfp_maxpool2d_codes, or
+    slfp_maxpool2d_codes_ex where the pool has ceil_mode=True -- fuse_fire wraps such pools: the class of a
     window's largest input -- bit-identical to pooling the float32 tensor and encoding it), anything else goes to the original
     module, which this wrapper keeps (`pool`; it has no parameters, the state dict does not change)."""
 
@@ -312,7 +313,7 @@ class CodeMaxPool2d(nn.Module):
         if x.dtype == torch.uint8:
             from .sfp_quant import hip_maxpool_codes
             p = self.pool
-            return hip_maxpool_codes(x, p.kernel_size, p.stride, p.padding, self.q_bit)
+            return hip_maxpool_codes(x, p.kernel_size, p.stride, p.padding, self.q_bit, ceil_mode=bool(p.ceil_mode))
         return self.pool(x)
 
 
@@ -657,5 +658,227 @@ def unfuse_residual(model):
     for blk in model.modules():
         if blk.__dict__.get("_residual_fused"):
             _restore_block(blk)
+            n += 1
+    return n
+
+
+# ------------------------------------------------------------------ SqueezeNet's Fire module on 1-byte codes, without the concat
+_FIRE_CHILDREN = ("squeeze", "squeeze_activation", "expand1x1", "expand1x1_activation", "expand3x3", "expand3x3_activation")
+
+
+def _fire_forward(self, x):
+    """The dataflow of the Fire module (nets_imgnet/squeezenet1_0.py:41-46) on codes: the three ReLUs sit in the conv epilogues,
+    `squeeze` writes ONE code tensor that both expands read, and the expands write the next layer's codes into the two channel
+    halves of one buffer -- what torch.cat([relu(e1), relu(e3)], 1) followed by the consumer's quantizer would hold."""
+    from .conv2d_func import _f32, _act_fmt
+    from .sfp_quant import hip_encode
+    if self.training:
+        raise RuntimeError("fuse_fire: a rewritten Fire module is inference-only; call fusion.unfuse_fire(model) to train")
+    sq, e1, e3 = self.squeeze, self.expand1x1, self.expand3x3
+    with torch.no_grad():
+        if x.dtype != torch.uint8:   # head of the chain (the pooled float32 stem output): one slfp_encode_f32 pass
+            if not x.is_contiguous(memory_format=torch.channels_last):
+                x = x.contiguous(memory_format=torch.channels_last)
+            x = hip_encode(x, _f32(sq.Ka), _act_fmt(sq.q_bit))
+        h = sq(x)
+        buf = torch.empty((h.shape[0], e1.out_channels + e3.out_channels, h.shape[2], h.shape[3]), dtype=torch.uint8,
+                          device=h.device, memory_format=torch.channels_last)
+        e1.forward_slice(h, (buf, 0))
+        e3.forward_slice(h, (buf, e1.out_channels))
+    return buf
+
+
+def _fire_candidate(blk):
+    if isinstance(blk, nn.Sequential) or "forward" in blk.__dict__ or blk.training:
+        return False
+    ch = blk._modules
+    if any(ch.get(k) is None for k in _FIRE_CHILDREN):
+        return False
+    sq, e1, e3 = ch["squeeze"], ch["expand1x1"], ch["expand3x3"]
+    if not all(_is_conv_q(c) for c in (sq, e1, e3)) or not all(isinstance(ch[k + "_activation"], nn.ReLU) for k in ("squeeze", "expand1x1", "expand3x3")):
+        return False
+    for c in (sq, e1, e3):
+        if (c.q_bit not in (8, 7) or c.training or not isinstance(c.padding, tuple) or c._code_out is not None or c.groups != 1
+                or (c.bias is not None and not getattr(c, "_scaled_bias", False)) or (c._post is not None and int(c._post[2]) != 0)
+                or getattr(c, "_in_residual", False)):
+            return False
+    same_size = all(tuple(c.stride) == (1, 1) and tuple(_pair2(c.dilation)) == (1, 1)
+                    and tuple(k - 1 for k in c.kernel_size) == tuple(2 * p for p in c.padding) for c in (sq, e1, e3))
+    return (same_size and e1.in_channels == e3.in_channels == sq.out_channels and e1.out_channels % 16 == 0
+            and e3.out_channels % 16 == 0 and float(e1.Ka) == float(e3.Ka) and e1.q_bit == e3.q_bit)   # ONE code tensor serves both
+
+
+def _restore_fire(blk):
+    st = blk.__dict__.pop("_fire_fused")
+    del blk.__dict__["forward"]
+    for conv, post in st["posts"]:
+        conv._post, conv._code_out = post, None
+    for parent, name, pool in st["pools"]:
+        if isinstance(parent._modules.get(name), CodeMaxPool2d) and parent._modules[name].pool is pool:
+            parent._modules[name] = pool
+
+
+def fuse_fire(model, example_input):
+    """SqueezeNet's Fire modules (nets_imgnet/squeezenet1_0.py:20-46; any non-Sequential block with the six children squeeze /
+    squeeze_activation / expand1x1 / expand1x1_activation / expand3x3 / expand3x3_activation, Conv2d_Q and nn.ReLU) on 1-byte
+    codes: the block gets an instance-level forward in which the three ReLUs are folded into the conv epilogues, `squeeze` writes
+    ONE code tensor for both expands (they must share Ka and q_bit) and both expands write the NEXT consumer's codes into the two
+    channel halves of one buffer (Conv2d_Q.forward_slice, slfp_conv2d_fwd_codes_slice): no in-place ReLU passes, no
+    torch.cat, 1 B per element where the float32 path moves 24.  The next consumer is found from one traced forward on
+    `example_input`: the single Conv2d_Q that reads the block's output, looking through nn.MaxPool2d (floor or ceil mode; wrapped
+    in CodeMaxPool2d), nn.Dropout in eval mode and nn.Identity.  A block without such a consumer, or with a leg libslfp_hip has
+    no kernel for, is left exactly as it was.  The first block of a chain encodes its float32 input in one pass.  As in
+    link_codes_traced / fuse_residual the rewrite verifies itself: every rewritten block must reproduce, code for code,
+    slfp_encode_f32 of its recorded output on its recorded input, and the model must reproduce its logits bit for bit -- blocks
+    that do not are restored one by one.  An exception while verifying is a refusal too, with a warning that names it -- except an
+    error status from libslfp_hip itself (_lib.SlfpError), which restores the blocks and is re-raised: a kernel that fails where the
+    support queries said yes must not pass as a skipped block.  Inference only; composes with graph.GraphedModule.  Returns the number of blocks
+    rewritten; unfuse_fire undoes it."""
+    import types
+    import warnings
+    from .conv2d_func import _scalar_scale, _conv_desc, _conv_io, _f32, _act_fmt
+    from .sfp_quant import hip_encode
+    from . import _lib
+    cands = [m for m in model.modules() if _fire_candidate(m)]
+    if not cands or model.training:
+        return 0
+    rec, conv_in, thru, keep, hooks = {}, [], [], [], []
+    for m in model.modules():
+        if m in cands:
+            hooks.append(m.register_forward_hook(lambda mod, inp, out: rec.__setitem__(mod, rec.get(mod, []) + [(inp, out)])))
+        elif _is_conv_q(m):
+            def _rec_conv(mod, inp, out):
+                conv_in.append((mod, inp[0]))
+                keep.append(inp[0])
+            hooks.append(m.register_forward_hook(_rec_conv))
+        elif isinstance(m, (nn.MaxPool2d, nn.Dropout, nn.Identity)):
+            def _rec_thru(mod, inp, out):
+                thru.append((mod, inp[0], out))
+                keep.extend((inp[0], out))
+            hooks.append(m.register_forward_hook(_rec_thru))
+    try:
+        with torch.no_grad():
+            y0 = model(example_input)
+    finally:
+        for h in hooks:
+            h.remove()
+
+    def same(a, b):   # every recorded tensor is kept alive, so an address names one tensor
+        return a is b or (torch.is_tensor(a) and torch.is_tensor(b) and a.data_ptr() == b.data_ptr() and a.shape == b.shape
+                          and a.dtype == b.dtype and a.stride() == b.stride())
+
+    def consumer_of(t):
+        """(the single Conv2d_Q that reads `t`, the pools on the way) or None."""
+        found = []
+        for mod, xin in conv_in:
+            cur, pools, ok = xin, [], False
+            for _ in range(6):
+                if same(cur, t):
+                    ok = True
+                    break
+                src = [(m_, i_) for m_, i_, o_ in thru if same(o_, cur)]
+                if len(src) != 1:
+                    break
+                m_, cur = src[0]
+                if isinstance(m_, nn.MaxPool2d):
+                    pools.append(m_)
+            if ok:
+                found.append((mod, pools))
+        # any other module that takes `t` (or a pooled / passed-through copy) without ending in that conv is a second use
+        # (a module that hands its input through -- nn.Dropout in eval mode, nn.Identity -- is not a use of its own)
+        direct = sum(1 for m_, i_, o_ in thru if same(i_, t) and not same(o_, t)) + sum(1 for mod, xin in conv_in if same(xin, t))
+        if len(found) != 1 or direct != 1:
+            return None
+        return found[0]
+
+    L = _lib.load()
+
+    def kernel_exists(m, shape, x_codes, out, flags, y_ld=None):
+        d, io = _conv_desc(m, shape), _conv_io(x_codes, out)
+        hb = 1 if m.bias is not None else 0
+        if y_ld is None:
+            return bool(L.slfp_conv2d_codes_supported(ctypes.byref(d), ctypes.byref(io), hb, flags))
+        return bool(L.slfp_conv2d_codes_slice_supported(ctypes.byref(d), ctypes.byref(io), hb, flags, y_ld))
+
+    done = []
+    for blk in cands:
+        calls = rec.get(blk, [])
+        if len(calls) != 1 or len(calls[0][0]) != 1 or not torch.is_tensor(calls[0][0][0]) or not torch.is_tensor(calls[0][1]):
+            continue   # not run, run twice, or not a tensor -> tensor block
+        x, want = calls[0][0][0], calls[0][1]
+        sq, e1, e3 = blk.squeeze, blk.expand1x1, blk.expand3x3
+        ld = e1.out_channels + e3.out_channels
+        if (x.dim() != 4 or want.dim() != 4 or want.shape[1] != ld or not x.is_cuda
+                or not want.is_contiguous(memory_format=torch.channels_last)):
+            continue
+        cons = consumer_of(want)
+        if cons is None:
+            continue
+        nxt, pools = cons
+        if (nxt.q_bit not in (8, 7) or nxt.training or (nxt.bias is not None and not getattr(nxt, "_scaled_bias", False))
+                or any(p.return_indices or _pair2(p.dilation) != (1, 1) or ld % 4 for p in pools)):
+            continue
+        out_e = (float(_scalar_scale(e1.Ka, "Ka")), int(e1.q_bit))
+        out_n = (float(_scalar_scale(nxt.Ka, "Ka")), int(nxt.q_bit))
+        hshape = (x.shape[0], sq.out_channels, x.shape[2], x.shape[3])
+        nshape = (x.shape[0], nxt.in_channels) + tuple(next(xin for mod, xin in conv_in if mod is nxt).shape[2:])
+        nflags = int(nxt._post[2]) if nxt._post is not None else 0
+        if not (kernel_exists(sq, tuple(x.shape), True, out_e, 1) and kernel_exists(e1, hshape, True, out_n, 1, ld)
+                and kernel_exists(e3, hshape, True, out_n, 1, ld) and kernel_exists(nxt, nshape, True, None, nflags)):
+            continue
+        st = {"posts": [(c, c._post) for c in (sq, e1, e3)], "pools": []}
+        for c in (sq, e1, e3):
+            c._post = ((c._post[0], c._post[1]) if c._post is not None else (None, None)) + (1,)
+        sq._code_out, e1._code_out, e3._code_out = out_e, out_n, out_n
+        blk.__dict__["_fire_fused"] = st
+        blk.__dict__["forward"] = types.MethodType(_fire_forward, blk)
+        ok = False
+        try:
+            with torch.no_grad():
+                got = blk(x)
+                ref = hip_encode(want, _f32(out_n[0]), _act_fmt(out_n[1]))
+            ok = torch.is_tensor(got) and got.dtype == torch.uint8 and got.shape == ref.shape and torch.equal(got, ref)
+        except _lib.SlfpError:
+            _restore_fire(blk)
+            raise   # libslfp_hip refused or failed a call the support queries had granted: a defect, not an ordinary refusal
+        except Exception as e:   # e.g. a block whose own forward() does more than the six children say
+            warnings.warn(f"fuse_fire: {type(blk).__name__} left as it was: its rewritten form raised {type(e).__name__}: {e}")
+            ok = False
+        if not ok:
+            _restore_fire(blk)
+            continue
+        for pm in pools:   # the pools between the block and its consumer now see codes
+            for parent in [m for m in model.modules() if not isinstance(m, CodeMaxPool2d)]:
+                for name, child in list(parent._modules.items()):
+                    if child is pm:
+                        parent._modules[name] = CodeMaxPool2d(pm, nxt.q_bit)
+                        st["pools"].append((parent, name, pm))
+        done.append(blk)
+    rec.clear(); conv_in.clear(); thru.clear(); keep.clear()
+
+    def model_ok():
+        try:
+            with torch.no_grad():
+                y1 = model(example_input)
+            return y1.dtype == y0.dtype and y1.shape == y0.shape and torch.equal(y1, y0)
+        except _lib.SlfpError:
+            while done:
+                _restore_fire(done.pop())
+            raise
+        except Exception as e:   # e.g. a functional op behind a block that cannot take its codes
+            warnings.warn(f"fuse_fire: the rewritten model raised {type(e).__name__}: {e}; restoring the last rewritten block")
+            return False
+
+    while done and not model_ok():   # restored one by one, last block first, until the logits are the recorded ones again
+        _restore_fire(done.pop())
+    return len(done)
+
+
+def unfuse_fire(model):
+    """Undo fuse_fire."""
+    n = 0
+    for blk in list(model.modules()):
+        if "_fire_fused" in blk.__dict__:
+            _restore_fire(blk)
             n += 1
     return n

@@ -82,9 +82,9 @@ def hip_decode(codes, fmt):
     return y
 
 
-def hip_maxpool_codes(codes, kernel_size, stride, padding, q_bit):
-    """nn.MaxPool2d (floor mode, dilation 1) on a channels_last tensor of extended activation codes (slfp_maxpool2d_codes):
-    equal to encoding the pooled float32 tensor, bit for bit."""
+def hip_maxpool_codes(codes, kernel_size, stride, padding, q_bit, ceil_mode=False):
+    """nn.MaxPool2d (floor or ceil mode, dilation 1) on a channels_last tensor of extended activation codes
+    (slfp_maxpool2d_codes / slfp_maxpool2d_codes_ex): equal to encoding the pooled float32 tensor, bit for bit."""
     if not codes.is_cuda or codes.dtype != torch.uint8 or codes.dim() != 4:
         raise TypeError("slfp maxpool: expected a 4-d ROCm ('cuda') uint8 tensor of codes")
     if not codes.is_contiguous(memory_format=torch.channels_last):
@@ -94,11 +94,22 @@ def hip_maxpool_codes(codes, kernel_size, stride, padding, q_bit):
     sh, sw = (stride, stride) if isinstance(stride, int) else stride
     ph, pw = (padding, padding) if isinstance(padding, int) else padding
     n, c, h, w = codes.shape
-    ho, wo = (h + 2 * ph - kh) // sh + 1, (w + 2 * pw - kw) // sw + 1
-    y = torch.empty((n, c, ho, wo), dtype=torch.uint8, device=codes.device, memory_format=torch.channels_last)
     L = _lib.load()
+    if ceil_mode:
+        import ctypes
+        oh, ow = ctypes.c_int64(), ctypes.c_int64()
+        _lib.check(L.slfp_maxpool2d_out_shape(h, w, kh, kw, sh, sw, ph, pw, 1, ctypes.byref(oh), ctypes.byref(ow)))
+        ho, wo = oh.value, ow.value
+    else:
+        ho, wo = (h + 2 * ph - kh) // sh + 1, (w + 2 * pw - kw) // sw + 1
+    y = torch.empty((n, c, ho, wo), dtype=torch.uint8, device=codes.device, memory_format=torch.channels_last)
     with torch.cuda.device(codes.device):
-        _lib.check(L.slfp_maxpool2d_codes(codes.data_ptr(), y.data_ptr(), n, h, w, c, kh, kw, sh, sw, ph, pw, int(q_bit), _stream_handle(codes)))
+        if ceil_mode:
+            _lib.check(L.slfp_maxpool2d_codes_ex(codes.data_ptr(), y.data_ptr(), n, h, w, c, kh, kw, sh, sw, ph, pw, int(q_bit), 1,
+                                                 _stream_handle(codes)))
+        else:
+            _lib.check(L.slfp_maxpool2d_codes(codes.data_ptr(), y.data_ptr(), n, h, w, c, kh, kw, sh, sw, ph, pw, int(q_bit),
+                                              _stream_handle(codes)))
     return y
 
 

@@ -177,7 +177,7 @@ int slfp_dwpw_fwd(const slfp_conv2d_desc* dw, const slfp_conv2d_desc* pw, const 
  * SFP<3,3>), while activations cross HBM as 1 B per element instead of 4.  NaN has no code (it becomes 0x00, as in
  * slfp_encode_f32).  Both tensors are NHWC; x, y and wprep 16-byte aligned; wprep is the blob of
  * slfp_conv2d_prepare_weights for the same descriptor.  Supported: 3x3 depthwise (x_codes), 1x1 (x_codes; C_in a
- * multiple of 32, C_out of 16 with y_codes), and the 3x3 stride-2 RGB stem -> 32 channels (float32 in, y_codes):
+ * multiple of 32, or 16 or 48; C_out a multiple of 16 with y_codes), and the 3x3 stride-2 RGB stem -> 32 channels (float32 in, y_codes):
  * every layer of nets_imgnet/mobilenetv1.py:43-57; the 3x3 RGB stem -> 64 channels of VGG-16 (float32 in, y_codes); dense k x k
  * layers through slfp_conv2d_fwd_codes_ws (below).
  * slfp_conv2d_codes_supported answers 1 / 0 without device work. */
@@ -199,6 +199,21 @@ int slfp_conv2d_fwd_codes(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, c
 int slfp_conv2d_fwd_codes_ws(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
                              const float* bias, const float* post_scale, const float* post_shift, int relu, void* y,
                              void* workspace, void* stream);
+/* ---- code output into a channel slice: a concat without the copy ------------------------------------------------------------
+ * slfp_conv2d_fwd_codes_ws with the code output written into a channel slice of a WIDER NHWC code tensor: y points at the
+ * slice's first channel of pixel 0, y_ld is the wider tensor's channel count = the byte distance between two pixels.  The two
+ * expand layers of a SqueezeNet Fire module (nets_imgnet/squeezenet1_0.py:41-46) write the two halves of the concatenated
+ * tensor this way, so torch.cat never runs.  Requires io->y_codes == 1, y_ld >= c_out, y_ld a multiple of 16 and y 16-byte
+ * aligned (so the channel offset is a multiple of 16).  The bytes written are exactly those slfp_conv2d_fwd_codes_ws writes for
+ * the same arguments, pixel by pixel; nothing outside the slice is touched; y_ld == c_out is slfp_conv2d_fwd_codes_ws.
+ * Supported (slfp_conv2d_codes_slice_supported: 1 / 0, host only): the 1x1 layers on codes of the pw_mfma_* family and the dense
+ * k x k layers (codes or float32 in), wherever slfp_conv2d_codes_supported says yes; depthwise and stem layers return
+ * SLFP_ERR_UNSUPPORTED.  1x1 layers on codes take C_in = 16 and 48 next to the multiples of 32 (Fire 3/4 and 8/9 squeeze to
+ * 16 and 48 channels), and 96 among those (the squeeze behind the stem).  workspace: as slfp_conv2d_fwd_codes_ws. */
+int slfp_conv2d_codes_slice_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int relu, int64_t y_ld);
+int slfp_conv2d_fwd_codes_slice(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
+                                const float* bias, const float* post_scale, const float* post_shift, int relu, void* y,
+                                int64_t y_ld, void* workspace, void* stream);
 /* ---- residual operand: y = relu?(affine(conv(x)) + res) in ONE launch -------------------------------------------------
  * The tail of every residual block, out = relu(bn3(conv3(h)) + identity) (nets_imgnet/resnet50.py:82-88), for the 1x1
  * stride-1 layers of the pw_mfma_* family.  Per output element, in this order, every step rounded to float32:
@@ -226,6 +241,14 @@ int slfp_conv2d_fwd_res(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, con
  * bit -- the pools between VGG-16's stages (nets_cifar/vgg16.py:39,49,63,78,92) can stay inside a code chain. */
 int slfp_maxpool2d_codes(const uint8_t* x, uint8_t* y, int64_t n, int64_t h, int64_t w, int64_t c, int kh, int kw, int sh, int sw,
                          int ph, int pw, int qbits, void* stream);
+/* The same with nn.MaxPool2d's ceil_mode (0 / 1; SqueezeNet's three pools, nets_imgnet/squeezenet1_0.py:60-71): with 1 the
+ * output size per axis is ceil((in + 2 p - k) / s) + 1, minus one if the last window would start past the input and its left
+ * padding -- ATen's rule; windows that hang over the edge take the maximum of the taps inside the image.  ceil_mode == 0 is
+ * slfp_maxpool2d_codes.  slfp_maxpool2d_out_shape answers the size on the host (SLFP_ERR_SHAPE: bad geometry). */
+int slfp_maxpool2d_codes_ex(const uint8_t* x, uint8_t* y, int64_t n, int64_t h, int64_t w, int64_t c, int kh, int kw, int sh, int sw,
+                            int ph, int pw, int qbits, int ceil_mode, void* stream);
+int slfp_maxpool2d_out_shape(int64_t h, int64_t w, int kh, int kw, int sh, int sw, int ph, int pw, int ceil_mode, int64_t* h_out,
+                             int64_t* w_out);
 /* Self-check of the producer side: sweeps ALL 2^32 float32 inputs on the device; out3[0] = inputs whose table-driven code
  * (signed variant) differs from slfp_encode_f32(.., fmt | SLFP_FMT_EXT), out3[1] = the same for the unsigned variant a
  * producer with a ReLU epilogue runs (inputs >= +0 and -0), out3[2] = code bytes whose decode-table entries (float32 and
