@@ -155,6 +155,25 @@ def test_depthwise_at_size(stride):
     _check_case(spec, 32, 8, True, torch.Generator().manual_seed(8), channels_last=True, label="at size")
 
 
+RECT = [   # non-square inputs (every layer of the tables is square): h != w, h_out != w_out
+    layer_specs.ConvSpec(32, 32, (3, 3), (1, 1), (1, 1), 32, False, 9, 20, 9, 20, 0.17, 0.13),
+    layer_specs.ConvSpec(32, 32, (3, 3), (1, 1), (1, 1), 32, False, 20, 9, 20, 9, 0.17, 0.13),
+    layer_specs.ConvSpec(64, 64, (3, 3), (2, 2), (1, 1), 64, False, 21, 10, 11, 5, 0.17, 0.13),
+    layer_specs.ConvSpec(64, 64, (3, 3), (2, 2), (1, 1), 64, False, 10, 21, 5, 11, 0.17, 0.13),
+    layer_specs.ConvSpec(64, 128, (1, 1), (1, 1), (0, 0), 1, False, 5, 23, 5, 23, 0.21, 0.037),
+    layer_specs.ConvSpec(64, 128, (1, 1), (1, 1), (0, 0), 1, False, 23, 5, 23, 5, 0.21, 0.037),
+]
+
+
+@pytest.mark.parametrize("channels_last", [False, True], ids=["nchw", "nhwc"])
+@pytest.mark.parametrize("spec", RECT, ids=lambda s: f"{s.c_in}x{s.c_out}k{s.k[0]}s{s.stride[0]}@{s.h}x{s.w}")
+def test_non_square_inputs_against_float64(spec, channels_last):
+    """dw3x3_bwd (stride 1 and 2) and pw_bwd_mfma_f32 on h != w, both layouts, both formats, the bars of every other case."""
+    for q in (8, 7):
+        gen = torch.Generator().manual_seed(1700 + spec.h * 41 + spec.w + q)
+        _check_case(spec, 3, q, q == 8, gen, channels_last=channels_last, label="non-square")
+
+
 @pytest.mark.parametrize("spec", [s for _, s in GEOMS if s.h <= 28 and s.c_in <= 256][:8], ids=lambda s: f"{s.c_in}x{s.c_out}k{s.k[0]}s{s.stride[0]}@{s.h}")
 def test_sparse_gy_probe(spec):
     """gy non-zero at 2 positions per channel: each gw element sums a handful of terms, so one wrong quantization code is

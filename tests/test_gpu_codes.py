@@ -250,6 +250,63 @@ def test_resident_weight_dense_kernel_writes_the_same_codes_on_long_walks(lib, d
                 del yc
 
 
+def _rect_spec(ci, co, k, st, pd, h, w, groups=1, Ka=0.37, Kw=0.021):
+    """A hand-built layer on an h x w input, h != w: the layer tables hold square layers only."""
+    from cnns_slfp_quantization_amd.layer_specs import ConvSpec
+    ho, wo = (h + 2 * pd[0] - k[0]) // st[0] + 1, (w + 2 * pd[1] - k[1]) // st[1] + 1
+    return ConvSpec(c_in=ci, c_out=co, k=k, stride=st, pad=pd, groups=groups, bias=False, h=h, w=w, h_out=ho, w_out=wo, Ka=Ka, Kw=Kw)
+
+
+# (kind, spec, kernel family): every code kernel on a non-square input.  On square inputs a swapped H / W, H_out / W_out or
+# pad_h / pad_w in a pixel index is invisible.
+def _rect_code_layers():
+    R = _rect_spec
+    return [
+        ("dw", R(32, 32, (3, 3), (1, 1), (1, 1), 9, 20, 32), "dw3x3_nhwc"),
+        ("dw", R(64, 64, (3, 3), (2, 2), (1, 1), 29, 14, 64), "dw3x3_nhwc"),
+        ("dw", R(128, 128, (3, 3), (1, 1), (1, 1), 7, 19, 128), "dw3x3_nhwc"),
+        ("pw", R(64, 128, (1, 1), (1, 1), (0, 0), 5, 23), "pw_mfma"),
+        ("pw", R(64, 128, (1, 1), (2, 2), (0, 0), 23, 5), "pw_mfma"),          # the strided kernel indexes pixels through W
+        ("pw", R(16, 64, (1, 1), (1, 1), (0, 0), 6, 11), "pw_mfma"),
+        ("pw", R(48, 64, (1, 1), (1, 1), (0, 0), 6, 11), "pw_mfma"),
+        ("pw", R(512, 512, (1, 1), (1, 1), (0, 0), 3, 11), "pw_mfma"),
+        ("dense", R(16, 32, (3, 5), (1, 1), (1, 2), 11, 18), "dense_mfma"),
+        ("dense", R(64, 64, (3, 3), (1, 1), (1, 0), 9, 21), "dense_mfma"),     # the resident-weight form
+        ("stem", R(3, 64, (3, 3), (1, 1), (1, 1), 33, 20, Ka=0.17, Kw=0.05), "stem_small_mfma"),
+        ("stem", R(3, 32, (3, 3), (2, 2), (1, 1), 40, 22, Ka=0.17, Kw=0.05), "stem_nhwc"),
+    ]
+
+
+@pytest.mark.parametrize("qbits", [8, 7])
+def test_rectangular_layers_on_codes_are_bit_identical_to_the_float32_interface(lib, dev, qbits):
+    """Depthwise, 1x1 (stride 1 and 2, C_in 16 / 48 / 64 / 512), dense (3x5 with pad (1, 2); the resident-weight 3x3 with pad
+    (1, 0)) and both stems on H != W inputs: the consumer from codes == the consumer from float32 bit for bit, the producer's
+    bytes == slfp_encode_f32(float32 output)."""
+    gen = torch.Generator(device=dev).manual_seed(4242 + qbits)
+    fmt = lib.FMT_ACT8 if qbits == 8 else lib.FMT_SFP7
+    ka_next = 0.2345
+    n = 3
+    for kind, s, family in _rect_code_layers():
+        if family == "stem_nhwc" and qbits != 8:
+            continue   # the specialised stem kernel is SLFP<3,4> only; SFP<3,3> chains start after the stem
+        lay = _Layer(lib, s, n, qbits, dev, gen)
+        assert lay.kernel.startswith(family), (lay.kernel, s)
+        x = _synthetic_input(s, n, dev, gen, signed=(kind == "stem"))
+        y_ref = lay.fwd_f32(lib, x)
+        codes_ref = _encode(lib, y_ref, ka_next, fmt)
+        if kind in ("stem", "dense"):   # float32 in, the consumer's codes out
+            yc = lay.fwd_codes(lib, x, False, ka_next, qbits)
+            assert torch.equal(yc, codes_ref), (kind, s, "producer from float32", int((yc != codes_ref).sum()))
+        if kind == "stem":
+            continue
+        xc = _encode(lib, x, s.Ka, fmt)
+        y = lay.fwd_codes(lib, xc, True)
+        assert torch.equal(y.view(torch.int32), y_ref.view(torch.int32)), (lay.kernel, s, "consumer", float((y - y_ref).abs().max()))
+        yc = lay.fwd_codes(lib, xc, True, ka_next, qbits)
+        bad = int((yc != codes_ref).sum())
+        assert bad == 0, (lay.kernel, s, "producer", bad, yc.numel())
+
+
 @pytest.mark.parametrize("qbits", [8, 7])
 def test_small_k_stem_writes_the_next_layers_codes(lib, dev, qbits):
     """VGG-16's first layer (3x3 s1 3 -> 64 on the one-k-step MFMA stem, nets_cifar/vgg16.py:31): float32 image in, the
@@ -285,7 +342,9 @@ def test_maxpool_on_codes_equals_encoding_the_pooled_tensor(lib, dev, qbits):
     gen = torch.Generator(device=dev).manual_seed(11 + qbits)
     ka = 0.23
     for (n, c, h, w), (k, st, pd), signed in (((3, 64, 30, 30), (2, 2, 0), False), ((2, 12, 17, 19), (2, 2, 0), True),
-                                               ((2, 32, 23, 23), (3, 2, 1), False), ((2, 16, 9, 9), (3, 1, 1), True)):
+                                               ((2, 32, 23, 23), (3, 2, 1), False), ((2, 16, 9, 9), (3, 1, 1), True),
+                                               ((2, 16, 13, 22), ((3, 2), (2, 1), (1, 0)), False),
+                                               ((2, 12, 22, 13), ((2, 3), (1, 2), (0, 1)), True)):
         x = torch.randn((n, c, h, w), generator=gen, device=dev) * (5.0 * ka)
         x = x if signed else torch.relu(x)
         x.view(-1)[::7] = 15.4 * ka            # the top regular class
@@ -382,8 +441,9 @@ def test_codes_vs_oracle_direct(lib, dev):
     kernels): decode with the oracle, convolve in double, compare under the per-family bars of test_gpu_parity.py."""
     specs = _mobilenet_specs()
     gen = torch.Generator(device=dev).manual_seed(5)
-    for i, tol in ((7, 1e-5), (8, 1e-3)):   # dw 128@56 s2 (float32 FMA), pw 128->256@28 (single-pass fp16 MFMA)
-        s = specs[i]
+    # dw 128@56 s2 (float32 FMA), pw 128->256@28 (single-pass fp16 MFMA); the same two families on non-square inputs
+    rect = [(_rect_spec(64, 64, (3, 3), (2, 2), (1, 1), 29, 14, 64), 1e-5), (_rect_spec(64, 128, (1, 1), (2, 2), (0, 0), 23, 5), 1e-3)]
+    for i, (s, tol) in enumerate([(specs[7], 1e-5), (specs[8], 1e-3)] + rect):
         lay = _Layer(lib, s, 2, 8, dev, gen, post=False, relu=False)
         x = _synthetic_input(s, 2, dev, gen)
         xc = _encode(lib, x, s.Ka, lib.FMT_ACT8)

@@ -56,12 +56,13 @@ def _encode(lib, x, ka, qbits):
 
 
 class _Layer:
-    """One Conv2d_Q layer (NHWC tensors, logical sizes n x c_in x h x h) with random weights and bias."""
+    """One Conv2d_Q layer (NHWC tensors, logical sizes n x c_in x h x w; w defaults to h) with random weights and bias."""
 
-    def __init__(self, lib, dev, gen, n, c_in, c_out, h, k, qbits, relu, ka=0.31, kw=0.02, bias=True):
+    def __init__(self, lib, dev, gen, n, c_in, c_out, h, k, qbits, relu, ka=0.31, kw=0.02, bias=True, w=None):
         L = lib.load()
         self.lib, self.n, self.c_in, self.c_out, self.h, self.k, self.qbits, self.relu, self.ka = lib, n, c_in, c_out, h, k, qbits, relu, ka
-        self.d = lib.ConvDesc(n=n, c_in=c_in, h=h, w=h, c_out=c_out, kh=k, kw=k, stride_h=1, stride_w=1, pad_h=k // 2, pad_w=k // 2,
+        self.wd = h if w is None else w   # the input's width (self.w is the weight tensor)
+        self.d = lib.ConvDesc(n=n, c_in=c_in, h=h, w=self.wd, c_out=c_out, kh=k, kw=k, stride_h=1, stride_w=1, pad_h=k // 2, pad_w=k // 2,
                               dil_h=1, dil_w=1, groups=1, x_layout=lib.LAYOUT_NHWC, y_layout=lib.LAYOUT_NHWC, qbits=qbits,
                               ka=float(np.float32(ka)), kw_scale=float(np.float32(kw)), mfma_passes=lib.MFMA_F16X1, reserved=0)
         fan = c_in * k * k
@@ -77,7 +78,7 @@ class _Layer:
         return t.data_ptr() if t is not None else None
 
     def out_shape(self, c=None):
-        return (self.n, self.h, self.h, self.c_out if c is None else c)
+        return (self.n, self.h, self.wd, self.c_out if c is None else c)
 
     def io(self, x_codes, y_ka, y_qbits=None):
         return self.lib.ConvIo(x_codes=1 if x_codes else 0, y_codes=0 if y_ka is None else 1,
@@ -191,19 +192,29 @@ SLICE_GEOMS = [
     ("dense 3x3 (resident weights)", 64, 256, 13, 3, 3),
     ("dense 3x3 (64 -> 64: float32 input encoded in the kernel)", 64, 64, 14, 3, 2),
     ("dense 3x3 (generic tiling)", 128, 128, 13, 3, 2),
+    # h given as (h, w): non-square inputs and their twins (a pixel's slice starts at (row * W + col) * y_ld)
+    ("k_pwc_stream, 12 x 21", 32, 128, (12, 21), 1, 3),
+    ("k_pwc_stream, 21 x 12", 32, 128, (21, 12), 1, 3),
+    ("dense 3x3, 12 x 21", 64, 256, (12, 21), 3, 3),
+    ("dense 3x3, 21 x 12", 64, 256, (21, 12), 3, 3),
 ]
+
+
+def _hw(h):
+    return h if isinstance(h, tuple) else (h, h)
 
 
 @pytest.mark.parametrize("qbits", [7, 8])
 @pytest.mark.parametrize("geom", SLICE_GEOMS, ids=[g[0] for g in SLICE_GEOMS])
 def test_code_output_into_a_channel_slice(lib, dev, qbits, geom):
     what, c_in, c_out, h, k, n = geom
+    h, w = _hw(h)
     gen = torch.Generator(device=dev).manual_seed(7 * qbits + c_in + k)
     y_ka = 0.29
     for relu in (True, False):
-        lay = _Layer(lib, dev, gen, n, c_in, c_out, h, k, qbits, relu)
+        lay = _Layer(lib, dev, gen, n, c_in, c_out, h, k, qbits, relu, w=w)
         assert lay.kernel.startswith("dense_mfma" if k == 3 else "pw_mfma"), lay.kernel
-        x = _synthetic((n, h, h, c_in), lay.ka, dev, gen, signed=not relu)
+        x = _synthetic((n, h, w, c_in), lay.ka, dev, gen, signed=not relu)
         xc = _encode(lib, x, lay.ka, qbits)
         dense = lay.fwd_codes(xc, True, y_ka)
         assert torch.equal(dense, _encode(lib, lay.fwd_f32(x), y_ka, qbits))
@@ -224,15 +235,16 @@ def test_code_output_into_a_channel_slice(lib, dev, qbits, geom):
 
 
 @pytest.mark.parametrize("qbits", [7, 8])
-@pytest.mark.parametrize("geom", [(16, 64, 54), (48, 192, 27), (64, 256, 13)])
+@pytest.mark.parametrize("geom", [(16, 64, 54), (48, 192, 27), (64, 256, 13), (16, 64, (12, 21)), (16, 64, (21, 12))])
 def test_both_halves_of_a_fire_equal_the_encoded_concat(lib, dev, qbits, geom):
     """expand1x1 and expand3x3 write the two halves of ONE buffer: encode(cat(relu(e1), relu(e3))), with no byte left over."""
     c_in, c_out, h = geom
+    h, w = _hw(h)
     gen = torch.Generator(device=dev).manual_seed(31 * qbits + c_in)
     n, y_ka = 3, 0.33
-    e1 = _Layer(lib, dev, gen, n, c_in, c_out, h, 1, qbits, True)
-    e3 = _Layer(lib, dev, gen, n, c_in, c_out, h, 3, qbits, True)
-    x = _synthetic((n, h, h, c_in), e1.ka, dev, gen)
+    e1 = _Layer(lib, dev, gen, n, c_in, c_out, h, 1, qbits, True, w=w)
+    e3 = _Layer(lib, dev, gen, n, c_in, c_out, h, 3, qbits, True, w=w)
+    x = _synthetic((n, h, w, c_in), e1.ka, dev, gen)
     xc = _encode(lib, x, e1.ka, qbits)
     buf = torch.full(e1.out_shape(2 * c_out), 0xA5, dtype=torch.uint8, device=dev)
     e1.fwd_slice(xc, True, y_ka, buf, 0)
@@ -252,7 +264,9 @@ def test_ceil_mode_maxpool_on_codes_equals_encoding_the_pooled_tensor(lib, dev, 
     gen = torch.Generator(device=dev).manual_seed(23 + qbits)
     ka = 0.23
     cases = (((3, 128, 54, 54), (3, 2, 0)), ((2, 256, 27, 27), (3, 2, 0)), ((2, 12, 27, 27), (3, 2, 0)), ((2, 16, 4, 4), (2, 3, 0)),
-             ((2, 16, 3, 5), (2, 3, 0)), ((2, 32, 10, 11), (3, 2, 1)))
+             ((2, 16, 3, 5), (2, 3, 0)), ((2, 32, 10, 11), (3, 2, 1)),
+             # window, stride and padding as (h, w) pairs on non-square inputs
+             ((2, 16, 13, 22), ((3, 2), (2, 1), (1, 0))), ((2, 12, 22, 13), ((2, 3), (1, 2), (0, 1))))
     for (n, c, h, w), (k, st, pd) in cases:
         for signed in (False, True):
             x = torch.randn((n, c, h, w), generator=gen, device=dev) * (5.0 * ka)
@@ -274,7 +288,8 @@ def test_ceil_mode_maxpool_on_codes_equals_encoding_the_pooled_tensor(lib, dev, 
             floor = hip_maxpool_codes(xc, k, st, pd, qbits)
             assert torch.equal(floor, enc(F.max_pool2d(x, k, st, pd)))
             y0 = torch.empty_like(floor)
-            lib.check(L.slfp_maxpool2d_codes_ex(xc.data_ptr(), y0.data_ptr(), n, h, w, c, k, k, st, st, pd, pd, qbits, 0, _stream()))
+            (kh, kw), (sh, sw), (ph, pw) = _hw(k), _hw(st), _hw(pd)
+            lib.check(L.slfp_maxpool2d_codes_ex(xc.data_ptr(), y0.data_ptr(), n, h, w, c, kh, kw, sh, sw, ph, pw, qbits, 0, _stream()))
             assert torch.equal(y0, floor)
     assert tuple(F.max_pool2d(torch.zeros(1, 1, 4, 4), 2, 3, ceil_mode=True).shape[2:]) == (2, 2)
 

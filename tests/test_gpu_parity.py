@@ -814,13 +814,16 @@ def test_fused_depthwise_pointwise_block_is_bit_identical(dev):
     cf.options.dwpw_all = True   # every supported pair, not only the ones where the one-kernel form is the faster choice
     g = torch.Generator(device=dev).manual_seed(5)
     #        C    N   stride  H   batch
-    cases = [(32, 64, 1, 28, 3), (64, 128, 2, 30, 2), (128, 128, 1, 14, 2), (128, 256, 2, 28, 2), (32, 64, 1, 33, 2), (64, 64, 2, 15, 1)]
+    cases = [(32, 64, 1, 28, 3), (64, 128, 2, 30, 2), (128, 128, 1, 14, 2), (128, 256, 2, 28, 2), (32, 64, 1, 33, 2), (64, 64, 2, 15, 1),
+             # H x W inputs at both strides the block supports: tiles_h and tiles_w differ
+             (32, 64, 1, (20, 33), 2), (32, 64, 1, (33, 20), 2), (64, 128, 2, (20, 33), 2), (64, 128, 2, (33, 20), 2)]
     for (C, N, S, H, B) in cases:
+        H, W = H if isinstance(H, tuple) else (H, H)
         Ka1, Kw1, Ka2, Kw2 = np.float64(0.21), np.float64(0.11), np.float64(0.33), np.float64(0.07)
         # the convs' initial weights come from the global generator, whose seed differs from process to process: seed it
         # per case (and put it back) so that the weights, like the inputs and BN parameters drawn from g, are the same every run
         with torch.random.fork_rng(devices=[]):
-            torch.manual_seed(C * 100000 + N * 1000 + S * 100 + H)
+            torch.manual_seed(C * 100000 + N * 1000 + S * 100 + H + (0 if W == H else 7 * W))
             dw = cf.conv2d_Q(8, Kw1, Ka1)(C, C, 3, Kw1, Ka1, S, 1, groups=C, bias=False)
             pw = cf.conv2d_Q(8, Kw2, Ka2)(C, N, 1, Kw2, Ka2, 1, 0, bias=False)
         m = torch.nn.Sequential(dw, torch.nn.BatchNorm2d(C), torch.nn.ReLU(inplace=True), pw, torch.nn.BatchNorm2d(N), torch.nn.ReLU(inplace=True)).to(dev).eval()
@@ -832,7 +835,7 @@ def test_fused_depthwise_pointwise_block_is_bit_identical(dev):
                 bn.bias.normal_(0.1, 0.2, generator=g)
             dw.weight.mul_(3.0)
         m = m.to(memory_format=torch.channels_last)
-        x = (torch.randn((B, C, H, H), generator=g, device=dev).abs() * 1.5).contiguous(memory_format=torch.channels_last)
+        x = (torch.randn((B, C, H, W), generator=g, device=dev).abs() * 1.5).contiguous(memory_format=torch.channels_last)
         with torch.no_grad():
             y_stock = m(x).clone()
             mid_stock = m[2](m[1](m[0](x))).clone()
@@ -841,8 +844,9 @@ def test_fused_depthwise_pointwise_block_is_bit_identical(dev):
             assert fusion.fuse_dw_pw(m) == 1
             y_one = m(x).clone()
             blk = [mod for mod in m if isinstance(mod, fusion.DwPwBlock)][0]
-            assert blk._last_kernel == "dwpw_fused_f16x1", (C, N, S, H, blk._last_kernel)
-        assert torch.equal(y_one, y_two), (C, N, S, H, float((y_one - y_two).abs().max()))
+            assert blk._last_kernel == "dwpw_fused_f16x1", (C, N, S, H, W, blk._last_kernel)
+            assert tuple(y_one.shape) == (B, N, (H - 1) // S + 1, (W - 1) // S + 1)
+        assert torch.equal(y_one, y_two), (C, N, S, H, W, float((y_one - y_two).abs().max()))
         # BN folded into one fma vs the stock modules (a third-party kernel whose rounding can differ by an ulp between runs:
         # this assertion was order-dependent at 1e-5): one ulp in front of the pointwise layer's quantizer can flip a code, which
         # moves a few outputs by ~1e-3 of the tensor's maximum.  Bars: the l2 error and the fraction of moved elements stay tiny.

@@ -44,10 +44,10 @@ def _stream():
 
 
 class _Spec:
-    """A 1x1 stride-1 layer: c_in -> c_out on hw x hw pixels with the scales of a ResNet-50 conv3."""
+    """A 1x1 stride-1 layer: c_in -> c_out on hw x hw pixels (hw x w with `w`) with the scales of a ResNet-50 conv3."""
 
-    def __init__(self, c_in, c_out, hw, Ka=0.14, Kw=0.0196):
-        self.c_in, self.c_out, self.h, self.w, self.Ka, self.Kw = c_in, c_out, hw, hw, Ka, Kw
+    def __init__(self, c_in, c_out, hw, Ka=0.14, Kw=0.0196, w=None):
+        self.c_in, self.c_out, self.h, self.w, self.Ka, self.Kw = c_in, c_out, hw, hw if w is None else w, Ka, Kw
 
 
 def _conv3_specs():
@@ -194,6 +194,22 @@ def test_widths_that_are_not_a_multiple_of_16(lib, dev):
             _check_equal(lay, x, x_codes, gen)
             ran += 1
     assert ran >= 1, "slfp_conv2d_res_supported accepts no width with C_out % 16 != 0"
+
+
+@pytest.mark.parametrize("form", ["float32 in", "codes in", "f16x3"])
+@pytest.mark.parametrize("width", [(64, 256), (256, 1024)])
+def test_non_square_images(lib, dev, width, form):
+    """6 x 15 and 15 x 6 pixels (every other residual case is square), n = 3: 270 rows, not a multiple of any row tile; the
+    stream kernel (64 -> 256) and the tiled one (256 -> 1024), each with float32 input, code input and in the f16x3 mode."""
+    gen = torch.Generator(device=dev).manual_seed(400 + width[0] + len(form))
+    x_codes = form == "codes in"
+    for h, w in ((6, 15), (15, 6)):
+        s = _Spec(width[0], width[1], h, w=w)
+        lay = _Layer(lib, s, 3, 8, dev, gen, passes=lib.MFMA_F16X3 if form == "f16x3" else None)
+        assert lay.kernel == ("pw_mfma_f16x3" if form == "f16x3" else "pw_mfma_f16x1") and lay.supported(x_codes) == 1
+        assert lay.out_shape() == (3, h, w, width[1])
+        x, _ = _input(lib, s, 3, dev, gen, x_codes, 8)
+        _check_equal(lay, x, x_codes, gen)
 
 
 # ------------------------------------------------------------------ 2. at the size BASELINE config 4 runs

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN, rel_errors, same_bits
+from golden_parts import MAX_PART_BYTES
 from oracle import slfp_oracle as so
 from oracle import torch_port as tp
 
@@ -116,6 +117,41 @@ def test_conv_golden_c_oracle_and_port(conv_golden):
                                s, p, 1, g, np.float64(Ka), np.float64(Kw), q)
         assert rel_errors(yt.numpy(), ref)[0] < 1e-6, key  # same ATen kernels as the reference
     assert worst < 2e-6
+
+
+def test_conv_aniso_golden_c_oracle_and_port():
+    """Non-square inputs, kh != kw, pad_h != pad_w, stride_h != stride_w, dil_h != dil_w, 1 < groups < C, both bias classes,
+    Qbits 8 and 7 (tests/golden/make_golden_aniso.py): the reference's Conv2d_Q outputs and stashes against the oracle's (h, w)
+    pairs, with the assertions the generator made."""
+    with np.load(os.path.join(GOLDEN, "conv_aniso_golden.npz")) as z:
+        g = {k: z[k] for k in z.files}
+    keys = [str(k) for k in g["case_keys"]]
+    seen = set()
+    for key in keys:
+        name, q = key.rsplit("_q", 1)
+        q = int(q)
+        N, C, H, W, O, kh, kw, sh, sw, ph, pw, dh, dw, grp, has_b = [int(v) for v in g[name + "_meta"]]
+        Ka, Kw = g[name + "_scales"]
+        x, w = g[name + "_x"], g[name + "_w"]
+        assert x.shape == (N, C, H, W) and w.shape == (O, C // grp, kh, kw)
+        b = g[name + "_b"] if has_b else None
+        y, xq, wq = so.conv2d(x, w, b, (sh, sw), (ph, pw), (dh, dw), grp, Ka, Kw, q, want_q=True)
+        ref = g[key + "_y"]
+        assert y.shape == ref.shape, key
+        assert same_bits(xq, g[key + "_xq"]), key
+        assert same_bits(wq, g[key + "_wq"]), key
+        assert float(np.abs(y - ref).max() / np.abs(ref).max()) < 2e-6, key
+        yt, xqt, wqt = tp.conv2d_q(torch.from_numpy(x.copy()), torch.from_numpy(w), None if b is None else torch.from_numpy(b),
+                                   (sh, sw), (ph, pw), (dh, dw), grp, np.float64(Ka), np.float64(Kw), q)
+        assert same_bits(xqt.numpy(), g[key + "_xq"]) and same_bits(wqt.numpy(), g[key + "_wq"]), key
+        assert np.array_equal(yt.numpy(), ref), key   # the port runs the reference's own ATen convolution: bit-equal
+        seen |= {("H<W", H < W), ("H>W", H > W), ("k", kh != kw), ("p", ph != pw), ("s", sh != sw), ("d", dh != dw),
+                 ("g", 1 < grp < C), ("bias", bool(has_b)), ("nobias", not has_b), ("q", q)}
+    # the fixture covers what it was written for
+    for want in [("H<W", True), ("H>W", True), ("k", True), ("p", True), ("s", True), ("d", True), ("g", True), ("bias", True),
+                 ("nobias", True), ("q", 8), ("q", 7)]:
+        assert want in seen, want
+    assert os.path.getsize(os.path.join(GOLDEN, "conv_aniso_golden.npz")) < MAX_PART_BYTES
 
 
 def test_linear_golden(conv_golden):
