@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(_HERE, "libslfp_hip.so")
 OK, ERR_BAD_ARG, ERR_SHAPE, ERR_UNSUPPORTED, ERR_ALIGNMENT, ERR_HIP = 0, -1, -2, -3, -4, -5
 FMT_ACT8, FMT_W8, FMT_SFP7, FMT_EXT = 0, 1, 2, 4
 LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
+BWD_DENSE = 1  # slfp_conv2d_bwd_*_ex flags: SLFP_BWD_DENSE
 MFMA_DEFAULT, MFMA_F16X1, MFMA_F16X3 = 0, 1, 3
 OPT_SGD, OPT_DSGD, OPT_SSGD = 0, 1, 2
 
@@ -28,6 +29,7 @@ SYMBOLS = (
     "slfp_conv2d_codes_supported", "slfp_conv2d_fwd_codes", "slfp_conv2d_fwd_codes_ws", "slfp_maxpool2d_codes", "slfp_debug_code_mismatches", "slfp_debug_reload_switches",
     "slfp_debug_enc_hl_mismatches", "slfp_sgd_step_f32", "slfp_debug_dw3x3_variant",
     "slfp_conv2d_bwd_supported", "slfp_conv2d_bwd_kernel_name", "slfp_conv2d_bwd_workspace_bytes", "slfp_conv2d_bwd",
+    "slfp_conv2d_bwd_supported_ex", "slfp_conv2d_bwd_kernel_name_ex", "slfp_conv2d_bwd_workspace_bytes_ex", "slfp_conv2d_bwd_ex",
     "slfp_conv2d_res_supported", "slfp_conv2d_fwd_res",
     "slfp_conv2d_codes_slice_supported", "slfp_conv2d_fwd_codes_slice", "slfp_maxpool2d_codes_ex", "slfp_maxpool2d_out_shape",
 )
@@ -125,6 +127,10 @@ def load():
         "slfp_conv2d_bwd_kernel_name": (ctypes.c_char_p, [dp]),
         "slfp_conv2d_bwd_workspace_bytes": (sz, [dp, ci, ci]),
         "slfp_conv2d_bwd": (ci, [dp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "slfp_conv2d_bwd_supported_ex": (ci, [dp, ctypes.c_uint]),
+        "slfp_conv2d_bwd_kernel_name_ex": (ctypes.c_char_p, [dp, ctypes.c_uint]),
+        "slfp_conv2d_bwd_workspace_bytes_ex": (sz, [dp, ctypes.c_uint, ci, ci]),
+        "slfp_conv2d_bwd_ex": (ci, [dp, ctypes.c_uint, vp, vp, vp, vp, vp, vp, vp, vp]),
         "slfp_conv2d_res_supported": (ci, [dp, ctypes.POINTER(ConvIo), ci, ci]),
         "slfp_conv2d_fwd_res": (ci, [dp, ctypes.POINTER(ConvIo), vp, vp, vp, vp, vp, ci, vp, vp, vp, vp]),
         "slfp_conv2d_codes_slice_supported": (ci, [dp, ctypes.POINTER(ConvIo), ci, ci, i64]),

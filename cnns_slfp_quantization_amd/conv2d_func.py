@@ -32,7 +32,10 @@ reference's passthrough).  Autograd: forward is always the HIP kernel.  Backward
 `options.backward`: "composite" (the default) is the reference's STE composite on the GPU
 (torch.nn.grad on the quantized operands); "hip" runs the 3x3 depthwise, stride-1 1x1 and
 Linear_Q layers through one slfp_conv2d_bwd call each (float32 accumulation, deterministic;
-`module._last_bwd_kernel` names what ran) and keeps every other layer on the composite.
+`module._last_bwd_kernel` names what ran) and keeps every other layer on the composite;
+"hip_all" is "hip" plus SLFP_BWD_DENSE: every other groups-1, dilation-1 layer (dense k x k,
+strided 1x1, the C_in = 3 stems) runs on the implicit-GEMM family `dense_bwd_mfma_f32`, and
+only grouped non-depthwise and dilated layers stay on the composite.
 """
 import contextlib
 import ctypes
@@ -62,6 +65,7 @@ class _Options:
                                      # not only where it measured faster than two kernels
     dwpw_pairs = {(32, 1)}           # (depthwise channels, stride) pairs that run as one kernel by default
     backward = "composite"           # "composite": the reference's STE composite; "hip": slfp_conv2d_bwd where it covers the layer
+                                     # (3x3 depthwise, stride-1 1x1, Linear_Q); "hip_all": also the dense family (SLFP_BWD_DENSE)
 
     def __setattr__(self, name, value):
         if name == "backward" and value not in _BACKWARDS:
@@ -69,7 +73,7 @@ class _Options:
         super().__setattr__(name, value)
 
 
-_BACKWARDS = ("composite", "hip")
+_BACKWARDS = ("composite", "hip", "hip_all")
 options = _Options()
 
 
@@ -481,11 +485,12 @@ def _aligned(t):
 
 
 def _hip_backward(mod, desc, x, w, gy, needs):
-    """One slfp_conv2d_bwd call on dense NCHW / NHWC operands (the layouts `desc` names), or None where the library does
-    not cover the layer.  needs = (gx, gw, gb wanted); returns (gx, gw, gb) with None for what was not asked: gx has x's
+    """One slfp_conv2d_bwd_ex call on dense NCHW / NHWC operands (the layouts `desc` names), or None where the library does
+    not cover the layer under options.backward's flags ("hip_all": SLFP_BWD_DENSE).  needs = (gx, gw, gb wanted); returns (gx, gw, gb) with None for what was not asked: gx has x's
     memory format, gw is contiguous like `w`."""
     L = _lib.load()
-    if not L.slfp_conv2d_bwd_supported(ctypes.byref(desc)):
+    flags = _lib.BWD_DENSE if options.backward == "hip_all" else 0
+    if not L.slfp_conv2d_bwd_supported_ex(ctypes.byref(desc), flags):
         return None
     need_gx, need_gw, need_gb = needs
     x, gy = _aligned(x), _aligned(gy)
@@ -497,13 +502,13 @@ def _hip_backward(mod, desc, x, w, gy, needs):
     gw = torch.empty(w.shape, dtype=torch.float32, device=x.device) if run_gw else None
     gb = torch.empty(desc.c_out, dtype=torch.float32, device=x.device) if need_gb else None
     with _on_device(x.device):
-        nbytes = L.slfp_conv2d_bwd_workspace_bytes(ctypes.byref(desc), int(need_gx), int(run_gw))
+        nbytes = L.slfp_conv2d_bwd_workspace_bytes_ex(ctypes.byref(desc), flags, int(need_gx), int(run_gw))
         ws = _workspace(x.device, nbytes) if nbytes else None
-        _lib.check(L.slfp_conv2d_bwd(ctypes.byref(desc), x.data_ptr(), w.data_ptr(), gy.data_ptr(),
-                                     gx.data_ptr() if gx is not None else None, gw.data_ptr() if gw is not None else None,
-                                     gb.data_ptr() if gb is not None else None, ws.data_ptr() if ws is not None else None,
-                                     _stream_handle(x)))
-    mod._last_bwd_kernel = L.slfp_conv2d_bwd_kernel_name(ctypes.byref(desc)).decode()
+        _lib.check(L.slfp_conv2d_bwd_ex(ctypes.byref(desc), flags, x.data_ptr(), w.data_ptr(), gy.data_ptr(),
+                                        gx.data_ptr() if gx is not None else None, gw.data_ptr() if gw is not None else None,
+                                        gb.data_ptr() if gb is not None else None, ws.data_ptr() if ws is not None else None,
+                                        _stream_handle(x)))
+    mod._last_bwd_kernel = L.slfp_conv2d_bwd_kernel_name_ex(ctypes.byref(desc), flags).decode()
     return gx, gw if need_gw else None, gb
 
 
@@ -541,7 +546,7 @@ def _conv_backward_hip(ctx, gy):
 class _SlfpConv2dFn(torch.autograd.Function):
     """HIP forward; backward = the reference's composite (STE through both quantizers:
     utils/sfp_quant.py:50-53, :99-102; conv gradients from torch.nn.grad on the GPU), or the HIP kernels of
-    slfp_conv2d_bwd with options.backward = "hip"."""
+    slfp_conv2d_bwd with options.backward = "hip" / "hip_all"."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, mod, scaled_bias):
@@ -554,7 +559,7 @@ class _SlfpConv2dFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         mod = ctx.mod
-        if options.backward == "hip":
+        if options.backward in ("hip", "hip_all"):
             res = _conv_backward_hip(ctx, gy)
             if res is not None:
                 return res[0], res[1], res[2], None, None
@@ -804,7 +809,7 @@ class _SlfpLinearFn(torch.autograd.Function):
     def backward(ctx, gy):
         mod = ctx.mod
         x, weight = ctx.saved_tensors
-        if options.backward == "hip" and x.is_cuda and x.numel() > 0:
+        if options.backward in ("hip", "hip_all") and x.is_cuda and x.numel() > 0:
             # the pointwise kernels with rows = the product of the leading dims and H = W = 1
             I, O = x.shape[-1], weight.shape[0]
             x2, gy2 = x.detach().reshape(-1, I).contiguous(), gy.reshape(-1, O).contiguous()

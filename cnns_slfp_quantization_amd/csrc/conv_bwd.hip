@@ -1,5 +1,5 @@
 // conv_bwd.hip -- quantization-aware backward of Conv2d_Q / Linear_Q for the depthwise 3x3 and pointwise 1x1 families
-// (include/slfp.h: slfp_conv2d_bwd).
+// (include/slfp.h: slfp_conv2d_bwd) and, under SLFP_BWD_DENSE (slfp_conv2d_bwd_ex), every other groups-1 dilation-1 layer.
 //
 // The reference's forward is y = conv(QA(x/Ka), QW(w/Kw)) * Ka * Kw with straight-through estimators in both quantizers
 // (utils/sfp_quant.py:50-53, 99-102), so its backward is
@@ -392,8 +392,362 @@ __global__ __launch_bounds__(256) void k_gemm_f32(const GemmArgs ga, const EncAr
     if (do_gb && tid < BM && m0 + tid < M) ga.gbpart[(int64_t)blockIdx.z * M + m0 + tid] = gbs;
 }
 
+// ---- dense k x k / strided / stem layers (groups 1, dilation 1): implicit GEMM on the same 4-wave MFMA tile ------------
+// k_dense_gx: GX[(n,h,w)][ci] = Kw * sum_{tap,co} GY[n, (h+pad_h-kh)/stride_h, (w+pad_w-kw)/stride_w, co] * WT[tap][co][ci].
+// The rows of a workgroup lie in one (h mod stride_h, w mod stride_w) phase, so a tap either reaches every row of the tile
+// or none; the taps that reach none are skipped.  GEMM K runs over (tap, co) with each tap's co run padded to whole BK
+// (zeros), so a k-chunk never straddles two taps.  The A tile is gathered from NHWC gy: unconditional clamped loads and a
+// select to zero.  A phase no tap reaches (1x1 stride 2: three of four) gets exact zeros.
+// k_dense_gw: GWp[z][co][(tap,ci)] = sum_{m=(n,ho,wo) in split z} GY[m][co] * QA(X[n, ho*stride_h-pad_h+kh, wo*stride_w-pad_w+kw, ci]/Ka),
+// xq encoded on load as in k_gemm_f32 (never materialised); k_reduce_dense adds the splits in a fixed order, applies Ka and
+// writes OIHW.
+struct DenseGeom {
+    int N, H, W, Cin, Ho, Wo, Cout, KH, KW, sh, sw, padh, padw;
+};
+
+// rows (input pixels) of phase (a, b): n x ceil((H - a) / sh) x ceil((W - b) / sw)
+__host__ __device__ __forceinline__ int dense_phase_extent(int extent, int phase, int stride) {
+    return (extent - phase + stride - 1) / stride;
+}
+
+template <int TN, bool VEC>
+__global__ __launch_bounds__(256) void k_dense_gx(const float* __restrict__ gy, const float* __restrict__ wt,
+                                                   float* __restrict__ gx, const DenseGeom g, const float scale) {
+    constexpr int TM = 2, BM = 64 * TM, BN = 64 * TN, BK = kGemmBK;
+    constexpr int BMP = BM + 2;   // the scalar stores of a lane group land on distinct banks
+    __shared__ float sA[BK][BMP];
+    __shared__ __attribute__((aligned(16))) float sB[BK][BN];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int Cin = g.Cin, Cout = g.Cout, Ho = g.Ho, Wo = g.Wo, T = g.KH * g.KW;
+
+    // the workgroup's phase and its row tile inside the phase (workgroup-uniform)
+    int bx = blockIdx.x, ph = 0, pw = 0, Hp = 0, Wp = 0, rows = 0;   // N*H*W < 2^31 (dense_ok)
+    for (int a = 0, found = 0; a < g.sh && !found; ++a)
+        for (int b = 0; b < g.sw; ++b) {
+            const int hp = dense_phase_extent(g.H, a, g.sh), wp = dense_phase_extent(g.W, b, g.sw);
+            const int r = g.N * hp * wp;
+            const int cnt = r / BM + (r % BM != 0);
+            if (bx < cnt) { ph = a; pw = b; Hp = hp; Wp = wp; rows = r; found = 1; break; }
+            bx -= cnt;
+        }
+    const int r0 = bx * BM;
+    const int n0 = blockIdx.y * BN;
+    const int HWp = Hp * Wp;
+
+    constexpr int AV = BM * BK / 4 / 256, BV = BN * BK / 4 / 256;
+    float4 ra[AV], rb[BV];
+    // the A rows of this thread: fixed for the whole K loop
+    int a_nb[AV], a_h[AV], a_w[AV];
+    bool a_ok[AV];
+#pragma unroll
+    for (int i = 0; i < AV; ++i) {
+        const int r = r0 + (tid + i * 256) / (BK / 4);
+        a_ok[i] = r < rows;
+        const int rc = a_ok[i] ? r : 0;
+        const int n = rc / HWp, rem = rc - n * HWp;
+        a_nb[i] = n * Ho; a_h[i] = rem / Wp; a_w[i] = rem - a_h[i] * Wp;
+    }
+    // first tap at or after t that reaches this phase; T if none
+    auto next_tap = [&](int t) -> int {
+        for (; t < T; ++t) {
+            const int th = ph + g.padh - t / g.KW, tw = pw + g.padw - t % g.KW;
+            if (th % g.sh == 0 && tw % g.sw == 0) break;
+        }
+        return t;
+    };
+    auto load_tiles = [&](int t, int c0) {
+        const int dh = (ph + g.padh - t / g.KW) / g.sh, dw = (pw + g.padw - t % g.KW) / g.sw;   // exact
+#pragma unroll
+        for (int i = 0; i < AV; ++i) {
+            const int co = c0 + ((tid + i * 256) % (BK / 4)) * 4;
+            const int ho = a_h[i] + dh, wo = a_w[i] + dw;
+            const bool ok = a_ok[i] && (unsigned)ho < (unsigned)Ho && (unsigned)wo < (unsigned)Wo;
+            const int64_t base = ok ? ((int64_t)(a_nb[i] + ho) * Wo + wo) * Cout : 0;
+            if constexpr (VEC) {
+                const bool ok4 = ok && co < Cout;
+                const float4 v = *reinterpret_cast<const float4*>(gy + (ok4 ? base + co : 0));
+                ra[i] = ok4 ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+            } else {
+                float e[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const bool okj = ok && co + j < Cout;
+                    const float v = gy[okj ? base + co + j : 0];
+                    e[j] = okj ? v : 0.f;
+                }
+                ra[i] = make_float4(e[0], e[1], e[2], e[3]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < BV; ++i) {
+            const int e = tid + i * 256;
+            const int co = c0 + e / (BN / 4), ci = n0 + (e % (BN / 4)) * 4;
+            const int64_t base = ((int64_t)t * Cout + co) * Cin;
+            if constexpr (VEC) {
+                const bool ok = co < Cout && ci < Cin;
+                const float4 v = *reinterpret_cast<const float4*>(wt + (ok ? base + ci : 0));
+                rb[i] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+            } else {
+                float q[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const bool okj = co < Cout && ci + j < Cin;
+                    const float v = wt[okj ? base + ci + j : 0];
+                    q[j] = okj ? v : 0.f;
+                }
+                rb[i] = make_float4(q[0], q[1], q[2], q[3]);
+            }
+        }
+    };
+    auto store_tiles = [&]() {
+#pragma unroll
+        for (int i = 0; i < AV; ++i) {
+            const int e = tid + i * 256;
+            const int mm = e / (BK / 4), kk = (e % (BK / 4)) * 4;
+            sA[kk][mm] = ra[i].x; sA[kk + 1][mm] = ra[i].y; sA[kk + 2][mm] = ra[i].z; sA[kk + 3][mm] = ra[i].w;
+        }
+#pragma unroll
+        for (int i = 0; i < BV; ++i) {
+            const int e = tid + i * 256;
+            *reinterpret_cast<float4*>(&sB[e / (BN / 4)][(e % (BN / 4)) * 4]) = rb[i];
+        }
+    };
+
+    f32x16 acc[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
+
+    int t = next_tap(0), c0 = 0;
+    if (t < T) load_tiles(t, c0);
+    while (t < T) {
+        store_tiles();
+        __syncthreads();
+        int t1 = t, c1 = c0 + BK;
+        if (c1 >= Cout) { c1 = 0; t1 = next_tap(t + 1); }
+        if (t1 < T) load_tiles(t1, c1);   // in flight while the MFMAs run
+#pragma unroll
+        for (int kk = 0; kk < BK; kk += 2) {
+            float a[TM], b[TN];
+#pragma unroll
+            for (int i = 0; i < TM; ++i) a[i] = sA[kk + (lane >> 5)][(wm * TM + i) * 32 + (lane & 31)];
+#pragma unroll
+            for (int j = 0; j < TN; ++j) b[j] = sB[kk + (lane >> 5)][(wn * TN + j) * 32 + (lane & 31)];
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
+        }
+        __syncthreads();
+        t = t1; c0 = c1;
+    }
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int r = r0 + (wm * TM + i) * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+            if (r >= rows) continue;
+            const int n = r / HWp, rem = r - n * HWp;
+            const int hh = rem / Wp, ww = rem - hh * Wp;
+            float* dst = gx + (((int64_t)n * g.H + ph + hh * g.sh) * g.W + pw + ww * g.sw) * Cin;
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const int col = n0 + (wn * TN + j) * 32 + (lane & 31);
+                if (col < Cin) dst[col] = acc[i][j][q] * scale;
+            }
+        }
+}
+
+template <int TM, int TN, int AF, bool VEC>
+__global__ __launch_bounds__(256) void k_dense_gw(const float* __restrict__ gy, const float* __restrict__ x,
+                                                   float* __restrict__ part, float* __restrict__ gbpart, const DenseGeom g,
+                                                   const int64_t K, const int kps, const EncArgs t, const ScaleDiv sd) {
+    constexpr int BM = 64 * TM, BN = 64 * TN, BK = kGemmBK;
+    __shared__ __attribute__((aligned(16))) float sA[BK][BM];
+    __shared__ __attribute__((aligned(16))) float sB[BK][BN];
+    __shared__ __attribute__((aligned(16))) uint2 sE[AF == kEncTabQ ? kEncEntries + 1 : 1];
+    __shared__ uint32_t sT[16];
+    if constexpr (AF == kEncTabQ) enc_fill<256>(sE, t);
+    else lut_fill<AF>(sT);
+    const unsigned char* tb = reinterpret_cast<const unsigned char*>(sE);
+    const float r1 = t.r1, lo = t.lo, hi = t.hi;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int Cin = g.Cin, Cout = g.Cout, Ho = g.Ho, Wo = g.Wo, H = g.H, W = g.W;
+    const int M = Cout, N = g.KH * g.KW * Cin;   // GEMM rows and columns
+    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
+    const int64_t kb = (int64_t)blockIdx.z * kps;
+    const int64_t ke = kb + kps < K ? kb + kps : K;
+    const int HWo = Ho * Wo;
+    const bool do_gb = gbpart != nullptr && blockIdx.y == 0;
+
+    constexpr int AV = BM * BK / 4 / 256, BV = BN * BK / 4 / 256;
+    static_assert(256 % (BN / 4) == 0, "a thread keeps its B columns over the K loop");
+    float4 ra[AV], rb[BV];
+    // the B columns (tap, ci) of this thread: fixed for the whole K loop.  VEC: C_in % 4 == 0, so the four lie in one tap.
+    constexpr int NC = VEC ? 1 : 4;
+    int b_kh[NC], b_kw[NC], b_ci[NC];
+    bool b_ok[NC];
+#pragma unroll
+    for (int j = 0; j < NC; ++j) {
+        const int c = n0 + (tid % (BN / 4)) * 4 + j;
+        b_ok[j] = c < N;
+        const int cc = b_ok[j] ? c : 0;
+        const int tap = cc / Cin;
+        b_ci[j] = cc - tap * Cin; b_kh[j] = tap / g.KW - g.padh; b_kw[j] = tap % g.KW - g.padw;
+    }
+    auto load_tiles = [&](int64_t k0) {
+#pragma unroll
+        for (int i = 0; i < AV; ++i) {   // GY^T: [k = m][co], co contiguous
+            const int e = tid + i * 256;
+            const int64_t k = k0 + e / (BM / 4);
+            const int co = m0 + (e % (BM / 4)) * 4;
+            const bool okk = k < ke;
+            const int64_t base = okk ? k * Cout : 0;
+            if constexpr (VEC) {
+                const bool ok = okk && co < M;
+                const float4 v = *reinterpret_cast<const float4*>(gy + (ok ? base + co : 0));
+                ra[i] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+            } else {
+                float q[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const bool okj = okk && co + j < M;
+                    const float v = gy[okj ? base + co + j : 0];
+                    q[j] = okj ? v : 0.f;
+                }
+                ra[i] = make_float4(q[0], q[1], q[2], q[3]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < BV; ++i) {   // X gathered at the shifted pixel; padding and rows past the split are zero
+            const int64_t k = k0 + (tid + i * 256) / (BN / 4);
+            const bool okk = k < ke;
+            const int64_t kc = okk ? k : 0;
+            const int n = (int)(kc / HWo), rem = (int)(kc - (int64_t)n * HWo);
+            const int ho = rem / Wo, wo = rem - ho * Wo;
+            const int hs = ho * g.sh, ws = wo * g.sw;
+            if constexpr (VEC) {
+                const int hi_ = hs + b_kh[0], wi = ws + b_kw[0];
+                const bool ok = okk && b_ok[0] && (unsigned)hi_ < (unsigned)H && (unsigned)wi < (unsigned)W;
+                const float4 v = *reinterpret_cast<const float4*>(x + (ok ? (((int64_t)n * H + hi_) * W + wi) * Cin + b_ci[0] : 0));
+                rb[i] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+            } else {
+                float q[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int hi_ = hs + b_kh[j], wi = ws + b_kw[j];
+                    const bool ok = okk && b_ok[j] && (unsigned)hi_ < (unsigned)H && (unsigned)wi < (unsigned)W;
+                    const float v = x[ok ? (((int64_t)n * H + hi_) * W + wi) * Cin + b_ci[j] : 0];
+                    q[j] = ok ? v : 0.f;
+                }
+                rb[i] = make_float4(q[0], q[1], q[2], q[3]);
+            }
+        }
+    };
+    auto store_tiles = [&]() {
+#pragma unroll
+        for (int i = 0; i < AV; ++i) {
+            const int e = tid + i * 256;
+            *reinterpret_cast<float4*>(&sA[e / (BM / 4)][(e % (BM / 4)) * 4]) = ra[i];
+        }
+#pragma unroll
+        for (int i = 0; i < BV; ++i) {
+            const int e = tid + i * 256;
+            float4 v = rb[i];   // QA(x / Ka) on load; the zeros of the padding stay zero (Q(0) == 0)
+            v.x = qa1<AF>(v.x, r1, lo, hi, tb, sd, sT); v.y = qa1<AF>(v.y, r1, lo, hi, tb, sd, sT);
+            v.z = qa1<AF>(v.z, r1, lo, hi, tb, sd, sT); v.w = qa1<AF>(v.w, r1, lo, hi, tb, sd, sT);
+            *reinterpret_cast<float4*>(&sB[e / (BN / 4)][(e % (BN / 4)) * 4]) = v;
+        }
+    };
+
+    f32x16 acc[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
+    float gbs = 0.f;
+
+    __syncthreads();   // the encode table is in LDS
+    if (kb < ke) load_tiles(kb);
+    for (int64_t k0 = kb; k0 < ke; k0 += BK) {
+        store_tiles();
+        __syncthreads();
+        if (k0 + BK < ke) load_tiles(k0 + BK);   // in flight while the MFMAs run
+        if (do_gb && tid < BM) {
+#pragma unroll
+            for (int kk = 0; kk < BK; ++kk) gbs += sA[kk][tid];
+        }
+#pragma unroll
+        for (int kk = 0; kk < BK; kk += 2) {
+            float a[TM], b[TN];
+#pragma unroll
+            for (int i = 0; i < TM; ++i) a[i] = sA[kk + (lane >> 5)][(wm * TM + i) * 32 + (lane & 31)];
+#pragma unroll
+            for (int j = 0; j < TN; ++j) b[j] = sB[kk + (lane >> 5)][(wn * TN + j) * 32 + (lane & 31)];
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+    float* dstz = part + (int64_t)blockIdx.z * M * N;
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int col = n0 + (wn * TN + j) * 32 + (lane & 31);
+            if (col >= N) continue;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int row = m0 + (wm * TM + i) * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+                if (row < M) dstz[(int64_t)row * N + col] = acc[i][j][q];
+            }
+        }
+    if (do_gb && tid < BM && m0 + tid < M) gbpart[(int64_t)blockIdx.z * M + m0 + tid] = gbs;
+}
+
+// wt[tap][co][ci] = wq[co][ci][tap]
+__global__ __launch_bounds__(256) void k_oihw_to_tap(const float* __restrict__ wq, float* __restrict__ wt, int Cout, int Cin, int T) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;   // over wt
+    if (i >= (int64_t)Cout * Cin * T) return;
+    const int ci = (int)(i % Cin);
+    const int64_t r = i / Cin;
+    const int co = (int)(r % Cout), tap = (int)(r / Cout);
+    wt[i] = wq[((int64_t)co * Cin + ci) * T + tap];
+}
+
+// gw[co][ci][tap] = scale * sum_p part[p][co][tap][ci], p = 0 .. P-1 in the order of k_reduce_parts
+__global__ __launch_bounds__(kRedCols * kRedRows) void k_reduce_dense(const float* __restrict__ part, int P, int64_t ncols,
+                                                                       float scale, int Cin, int T, float* __restrict__ gw) {
+    __shared__ float s[kRedRows][kRedCols];
+    const int tc = threadIdx.x % kRedCols, tr = threadIdx.x / kRedCols;
+    const int64_t col = (int64_t)blockIdx.x * kRedCols + tc;
+    float a = 0.f;
+    if (col < ncols)
+        for (int p = tr; p < P; p += kRedRows) a += part[(int64_t)p * ncols + col];
+    s[tr][tc] = a;
+    __syncthreads();
+    if (tr != 0 || col >= ncols) return;
+    float sum = 0.f;
+    for (int q = 0; q < kRedRows; ++q) sum += s[q][tc];
+    const int ci = (int)(col % Cin);
+    const int64_t r = col / Cin;
+    const int tap = (int)(r % T);
+    const int64_t co = r / T;
+    gw[(co * Cin + ci) * T + tap] = sum * scale;
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------
-enum BwdKind { kBwdNone = 0, kBwdDw = 1, kBwdPw = 2 };
+enum BwdKind { kBwdNone = 0, kBwdDw = 1, kBwdPw = 2, kBwdDense = 3 };
 
 static BwdKind bwd_kind(const slfp_conv2d_desc& d) {
     if (d.groups == d.c_in && d.c_out == d.c_in && d.kh == 3 && d.kw == 3 && d.stride_h == d.stride_w &&
@@ -403,6 +757,19 @@ static BwdKind bwd_kind(const slfp_conv2d_desc& d) {
         d.dil_h == 1 && d.dil_w == 1)
         return kBwdPw;
     return kBwdNone;
+}
+
+// The dense family (SLFP_BWD_DENSE) takes what bwd_kind leaves: groups 1, dilation 1, any kernel size / stride / padding.
+static bool dense_ok(const slfp_conv2d_desc& d, const ConvPlan& p) {
+    if (d.groups != 1 || d.dil_h != 1 || d.dil_w != 1) return false;
+    const int64_t lim = 0x7FFFFFFF;   // the kernels index rows and GEMM columns in 32 bits
+    return d.n * d.h * d.w < lim && d.n * p.h_out * p.w_out < lim && (int64_t)d.kh * d.kw * d.c_in < lim;
+}
+
+static BwdKind bwd_kind_ex(const slfp_conv2d_desc& d, const ConvPlan& p, unsigned flags) {
+    const BwdKind k = bwd_kind(d);
+    if (k == kBwdNone && (flags & SLFP_BWD_DENSE) && dense_ok(d, p)) return kBwdDense;
+    return k;
 }
 
 static size_t r256(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -457,8 +824,50 @@ static PwShape pw_shape(const slfp_conv2d_desc& d) {
     return s;
 }
 
+struct DenseShape {
+    int64_t M;       // rows of the gw contraction = N*Ho*Wo
+    int64_t ncol;    // gw GEMM columns = taps * C_in
+    int tn_x;        // GX tiling (TM = 2)
+    int tm_w, tn_w;  // GW tiling
+    int splits, kps; // GW split of M
+};
+
+static DenseShape dense_shape(const slfp_conv2d_desc& d, const ConvPlan& p) {
+    DenseShape s;
+    s.M = d.n * p.h_out * p.w_out;
+    s.ncol = (int64_t)d.kh * d.kw * d.c_in;
+    const int64_t cout = d.c_out;
+    const bool vec = d.c_in % 4 == 0 && cout % 4 == 0;   // the scalar-gather instantiations exist at 64 x 64 only
+    s.tn_x = vec && d.c_in >= 128 ? 2 : 1;
+    s.tm_w = vec && cout >= 128 ? 2 : 1; s.tn_w = vec && s.ncol >= 128 ? 2 : 1;
+    const int64_t tiles = ceil_div(cout, 64 * s.tm_w) * ceil_div(s.ncol, 64 * s.tn_w);
+    int64_t sp = ceil_div(8 * kBwdCUs, tiles);                 // ~8 workgroups per CU
+    sp = std::min<int64_t>(sp, std::max<int64_t>(1, s.M / 256)); // at least 256 rows per split
+    sp = std::min<int64_t>(sp, std::max<int64_t>(1, kPartCapFloats / (cout * s.ncol + cout)));
+    sp = std::min<int64_t>(sp, kMaxParts);
+    if (sp < 1) sp = 1;
+    const int64_t kps = ceil_div(ceil_div(s.M, sp), kGemmBK) * kGemmBK;
+    s.kps = (int)kps;
+    s.splits = (int)ceil_div(s.M, kps);
+    return s;
+}
+
+static DenseGeom dense_geom(const slfp_conv2d_desc& d, const ConvPlan& p) {
+    return DenseGeom{(int)d.n, (int)d.h, (int)d.w, (int)d.c_in, (int)p.h_out, (int)p.w_out, (int)d.c_out, (int)d.kh, (int)d.kw,
+                     (int)d.stride_h, (int)d.stride_w, (int)d.pad_h, (int)d.pad_w};
+}
+
+// workgroups of k_dense_gx along x: the 128-row tiles of every (h mod stride_h, w mod stride_w) phase
+static int64_t dense_gx_tiles(const DenseGeom& g) {
+    int64_t tiles = 0;
+    for (int a = 0; a < g.sh; ++a)
+        for (int b = 0; b < g.sw; ++b)
+            tiles += ceil_div((int64_t)g.N * dense_phase_extent(g.H, a, g.sh) * dense_phase_extent(g.W, b, g.sw), 128);
+    return tiles;
+}
+
 struct BwdLayout {  // byte offsets into the workspace
-    size_t x_nhwc, gy_nhwc, gx_nhwc, wq, part, gbpart, total;
+    size_t x_nhwc, gy_nhwc, gx_nhwc, wq, wt, part, gbpart, total;
 };
 
 static BwdLayout bwd_layout(const slfp_conv2d_desc& d, const ConvPlan& p, BwdKind kind, bool need_gx, bool need_gw) {
@@ -470,6 +879,7 @@ static BwdLayout bwd_layout(const slfp_conv2d_desc& d, const ConvPlan& p, BwdKin
     L.gy_nhwc = off; if (d.y_layout == SLFP_LAYOUT_NCHW) off += r256(yb);
     L.gx_nhwc = off; if (need_gx && d.x_layout == SLFP_LAYOUT_NCHW) off += r256(xb);
     L.wq = off; if (need_gx) off += r256((size_t)d.c_out * (d.c_in / d.groups) * d.kh * d.kw * sizeof(float));
+    L.wt = off; if (need_gx && kind == kBwdDense) off += r256((size_t)d.c_out * d.c_in * d.kh * d.kw * sizeof(float));   // [tap][co][ci]
     L.part = off;
     L.gbpart = off;
     if (kind == kBwdDw && need_gw) {
@@ -478,6 +888,11 @@ static BwdLayout bwd_layout(const slfp_conv2d_desc& d, const ConvPlan& p, BwdKin
     } else if (kind == kBwdPw && need_gw) {
         const PwShape s = pw_shape(d);
         if (s.splits > 1) off += r256((size_t)s.splits * d.c_out * d.c_in * sizeof(float));
+        L.gbpart = off;
+        off += r256((size_t)s.splits * d.c_out * sizeof(float));
+    } else if (kind == kBwdDense && need_gw) {
+        const DenseShape s = dense_shape(d, p);
+        off += r256((size_t)s.splits * d.c_out * s.ncol * sizeof(float));   // [split][co][tap][ci], reduced into OIHW
         L.gbpart = off;
         off += r256((size_t)s.splits * d.c_out * sizeof(float));
     }
@@ -510,14 +925,37 @@ static void launch_gemm_t(const GemmArgs& a, int tm, int tn, hipStream_t st, con
     else launch_gemm_v<1, 1, A_KMAJ, AF>(a, grid, st, t, sd, vec);
 }
 
-static int run_bwd(const slfp_conv2d_desc* d, const float* x, const float* w, const float* gy, float* gx, float* gw,
+template <bool VEC>
+static void launch_dense_gx(const DenseGeom& g, int tn, hipStream_t st, const float* gy, const float* wt, float* gx, float scale) {
+    const dim3 grid((unsigned)dense_gx_tiles(g), (unsigned)ceil_div(g.Cin, 64 * tn));
+    if (tn == 2) hipLaunchKernelGGL((k_dense_gx<2, VEC>), grid, dim3(256), 0, st, gy, wt, gx, g, scale);
+    else hipLaunchKernelGGL((k_dense_gx<1, VEC>), grid, dim3(256), 0, st, gy, wt, gx, g, scale);
+}
+
+template <int AF>
+static void launch_dense_gw(const DenseGeom& g, const DenseShape& s, bool vec, hipStream_t st, const float* gy, const float* x,
+                            float* part, float* gbp, const EncArgs& t, const ScaleDiv& sd) {
+    const dim3 grid((unsigned)ceil_div(g.Cout, 64 * s.tm_w), (unsigned)ceil_div(s.ncol, 64 * s.tn_w), (unsigned)s.splits);
+#define SLFP_DENSE_GW(TM, TN, V) \
+    hipLaunchKernelGGL((k_dense_gw<TM, TN, AF, V>), grid, dim3(256), 0, st, gy, x, part, gbp, g, s.M, s.kps, t, sd)
+    if (!vec) SLFP_DENSE_GW(1, 1, false);
+    else if (s.tm_w == 2 && s.tn_w == 2) SLFP_DENSE_GW(2, 2, true);
+    else if (s.tm_w == 2) SLFP_DENSE_GW(2, 1, true);
+    else if (s.tn_w == 2) SLFP_DENSE_GW(1, 2, true);
+    else SLFP_DENSE_GW(1, 1, true);
+#undef SLFP_DENSE_GW
+}
+
+static int run_bwd(const slfp_conv2d_desc* d, unsigned flags, const float* x, const float* w, const float* gy, float* gx, float* gw,
                    float* gb, void* workspace, void* stream) {
     ConvPlan p;
     int rc = make_plan(d, &p);
     if (rc != SLFP_OK) return rc;
-    const BwdKind kind = bwd_kind(*d);
+    const BwdKind kind = bwd_kind_ex(*d, p, flags);
     if (kind == kBwdNone)
-        return fail(SLFP_ERR_UNSUPPORTED, "slfp_conv2d_bwd: only 3x3 depthwise (stride 1/2, pad 1) and stride-1 1x1 layers");
+        return fail(SLFP_ERR_UNSUPPORTED, flags & SLFP_BWD_DENSE
+                        ? "slfp_conv2d_bwd: only 3x3 depthwise (stride 1/2, pad 1) and groups-1 dilation-1 layers"
+                        : "slfp_conv2d_bwd: only 3x3 depthwise (stride 1/2, pad 1) and stride-1 1x1 layers");
     if (!gy) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_bwd: null gy");
     if (gx && !w) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_bwd: gx needs the weights");
     if (gw && !x) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_bwd: gw needs the input");
@@ -569,6 +1007,38 @@ static int run_bwd(const slfp_conv2d_desc* d, const float* x, const float* w, co
                                ncols, d->ka, g.C, gw, gb);
             if ((rc = check_launch("slfp backward reduction kernel")) != SLFP_OK) return rc;
         }
+    } else if (kind == kBwdDense) {
+        const DenseShape s = dense_shape(*d, p);
+        const DenseGeom g = dense_geom(*d, p);
+        const int T = g.KH * g.KW;
+        // every operand is 16-byte aligned (checked at the entry point; workspace offsets are multiples of 256)
+        const bool vec = (Cin % 4) == 0 && (Cout % 4) == 0;
+        if (need_gx) {
+            float* wt = reinterpret_cast<float*>(ws + L.wt);
+            const int64_t nw = Cout * Cin * T;
+            hipLaunchKernelGGL(k_oihw_to_tap, dim3((unsigned)ceil_div(nw, 256)), dim3(256), 0, st, wq, wt, (int)Cout, (int)Cin, T);
+            if ((rc = check_launch("slfp dense backward weight re-layout kernel")) != SLFP_OK) return rc;
+            if (vec) launch_dense_gx<true>(g, s.tn_x, st, gy_n, wt, gx_n, d->kw_scale);
+            else launch_dense_gx<false>(g, 1, st, gy_n, wt, gx_n, d->kw_scale);
+            if ((rc = check_launch("slfp dense backward (gx) kernel")) != SLFP_OK) return rc;
+        }
+        if (need_gw) {
+            float* part = reinterpret_cast<float*>(ws + L.part);
+            float* gbp = need_gb ? reinterpret_cast<float*>(ws + L.gbpart) : nullptr;
+            if (tab) launch_dense_gw<kEncTabQ>(g, s, vec, st, gy_n, x_n, part, gbp, *tab, sd);
+            else if (p.fmt_act == kFmtAct8) launch_dense_gw<kFmtAct8>(g, s, vec, st, gy_n, x_n, part, gbp, kNone, sd);
+            else launch_dense_gw<kFmtSfp7>(g, s, vec, st, gy_n, x_n, part, gbp, kNone, sd);
+            if ((rc = check_launch("slfp dense backward (gw) kernel")) != SLFP_OK) return rc;
+            const int64_t ncols = Cout * s.ncol;
+            hipLaunchKernelGGL(k_reduce_dense, dim3((unsigned)ceil_div(ncols, kRedCols)), dim3(kRedCols * kRedRows), 0, st, part,
+                               s.splits, ncols, d->ka, (int)Cin, T, gw);
+            if ((rc = check_launch("slfp backward reduction kernel")) != SLFP_OK) return rc;
+            if (need_gb) {
+                hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)ceil_div(Cout, kRedCols)), dim3(kRedCols * kRedRows), 0, st,
+                                   gbp, s.splits, Cout, 1.0f, 0, gb, nullptr);
+                if ((rc = check_launch("slfp backward reduction kernel")) != SLFP_OK) return rc;
+            }
+        }
     } else {
         const PwShape s = pw_shape(*d);
         const bool vec = (Cin % 4) == 0 && (Cout % 4) == 0 && aligned16(gy_n) && (!need_gw || aligned16(x_n)) &&
@@ -611,32 +1081,52 @@ using namespace slfp;
 
 extern "C" {
 
-int slfp_conv2d_bwd_supported(const slfp_conv2d_desc* d) {
+int slfp_conv2d_bwd_supported_ex(const slfp_conv2d_desc* d, unsigned flags) {
     ConvPlan p;
-    if (!d || make_plan(d, &p) != SLFP_OK) return 0;
-    return bwd_kind(*d) != kBwdNone ? 1 : 0;
+    if (!d || (flags & ~SLFP_BWD_DENSE) || make_plan(d, &p) != SLFP_OK) return 0;
+    return bwd_kind_ex(*d, p, flags) != kBwdNone ? 1 : 0;
 }
 
-const char* slfp_conv2d_bwd_kernel_name(const slfp_conv2d_desc* d) {
-    if (!slfp_conv2d_bwd_supported(d)) return "composite";
-    return bwd_kind(*d) == kBwdDw ? "dw3x3_bwd" : "pw_bwd_mfma_f32";
+const char* slfp_conv2d_bwd_kernel_name_ex(const slfp_conv2d_desc* d, unsigned flags) {
+    ConvPlan p;
+    if (!d || (flags & ~SLFP_BWD_DENSE) || make_plan(d, &p) != SLFP_OK) return "composite";
+    switch (bwd_kind_ex(*d, p, flags)) {
+        case kBwdDw: return "dw3x3_bwd";
+        case kBwdPw: return "pw_bwd_mfma_f32";
+        case kBwdDense: return "dense_bwd_mfma_f32";
+        default: return "composite";
+    }
 }
 
-size_t slfp_conv2d_bwd_workspace_bytes(const slfp_conv2d_desc* d, int need_gx, int need_gw) {
+size_t slfp_conv2d_bwd_workspace_bytes_ex(const slfp_conv2d_desc* d, unsigned flags, int need_gx, int need_gw) {
     ConvPlan p;
-    if (!d || make_plan(d, &p) != SLFP_OK) return 0;
-    const BwdKind kind = bwd_kind(*d);
+    if (!d || (flags & ~SLFP_BWD_DENSE) || make_plan(d, &p) != SLFP_OK) return 0;
+    const BwdKind kind = bwd_kind_ex(*d, p, flags);
     if (kind == kBwdNone) return 0;
     return bwd_layout(*d, p, kind, need_gx != 0, need_gw != 0).total;
 }
 
-int slfp_conv2d_bwd(const slfp_conv2d_desc* d, const float* x, const float* w_oihw, const float* gy, float* gx,
-                    float* gw_oihw, float* gb, void* workspace, void* stream) {
+int slfp_conv2d_bwd_ex(const slfp_conv2d_desc* d, unsigned flags, const float* x, const float* w_oihw, const float* gy,
+                       float* gx, float* gw_oihw, float* gb, void* workspace, void* stream) {
     if (!d) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_bwd: null descriptor");
+    if (flags & ~SLFP_BWD_DENSE) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_bwd: unknown flag bits 0x%x", flags & ~SLFP_BWD_DENSE);
     if ((x && !aligned16(x)) || (w_oihw && !aligned16(w_oihw)) || (gy && !aligned16(gy)) || (gx && !aligned16(gx)) ||
         (gw_oihw && !aligned16(gw_oihw)) || (gb && !aligned16(gb)))
         return fail(SLFP_ERR_ALIGNMENT, "slfp_conv2d_bwd: tensors must be 16-byte aligned");
-    return run_bwd(d, x, w_oihw, gy, gx, gw_oihw, gb, workspace, stream);
+    return run_bwd(d, flags, x, w_oihw, gy, gx, gw_oihw, gb, workspace, stream);
+}
+
+int slfp_conv2d_bwd_supported(const slfp_conv2d_desc* d) { return slfp_conv2d_bwd_supported_ex(d, 0u); }
+
+const char* slfp_conv2d_bwd_kernel_name(const slfp_conv2d_desc* d) { return slfp_conv2d_bwd_kernel_name_ex(d, 0u); }
+
+size_t slfp_conv2d_bwd_workspace_bytes(const slfp_conv2d_desc* d, int need_gx, int need_gw) {
+    return slfp_conv2d_bwd_workspace_bytes_ex(d, 0u, need_gx, need_gw);
+}
+
+int slfp_conv2d_bwd(const slfp_conv2d_desc* d, const float* x, const float* w_oihw, const float* gy, float* gx,
+                    float* gw_oihw, float* gb, void* workspace, void* stream) {
+    return slfp_conv2d_bwd_ex(d, 0u, x, w_oihw, gy, gx, gw_oihw, gb, workspace, stream);
 }
 
 }  // extern "C"

@@ -334,6 +334,18 @@ size_t slfp_conv2d_bwd_workspace_bytes(const slfp_conv2d_desc* d, int need_gx, i
 int slfp_conv2d_bwd(const slfp_conv2d_desc* d, const float* x, const float* w_oihw, const float* gy, float* gx, float* gw_oihw,
                     float* gb, void* workspace, void* stream);
 
+/* The same four with a `flags` word; flags == 0 is exactly the functions above.  SLFP_BWD_DENSE adds the implicit-GEMM
+ * family "dense_bwd_mfma_f32" (float32 MFMA, xq encoded on load and never materialised, deterministic) for every
+ * groups == 1, dilation 1 layer the two families above do not take: any kernel size, stride and padding, any channel
+ * count (3x3 / 5x5 / 7x7 / 11x11, strided 1x1, C_in = 3 stems).  Grouped non-depthwise and dilated layers stay
+ * unsupported; unknown flag bits are SLFP_ERR_BAD_ARG (not supported / "composite" / 0 bytes in the queries). */
+#define SLFP_BWD_DENSE 1u   /* also cover groups == 1, dilation 1 layers of any kernel size / stride / padding */
+int slfp_conv2d_bwd_supported_ex(const slfp_conv2d_desc* d, unsigned flags);
+const char* slfp_conv2d_bwd_kernel_name_ex(const slfp_conv2d_desc* d, unsigned flags);
+size_t slfp_conv2d_bwd_workspace_bytes_ex(const slfp_conv2d_desc* d, unsigned flags, int need_gx, int need_gw);
+int slfp_conv2d_bwd_ex(const slfp_conv2d_desc* d, unsigned flags, const float* x, const float* w_oihw, const float* gy,
+                       float* gx, float* gw_oihw, float* gb, void* workspace, void* stream);
+
 /* ---- layout helpers (the reference is NCHW; the kernels are NHWC) -------------------- */
 int slfp_nchw_to_nhwc_f32(const float* x, float* y, int64_t n, int64_t c, int64_t h, int64_t w, void* stream);
 int slfp_nhwc_to_nchw_f32(const float* x, float* y, int64_t n, int64_t c, int64_t h, int64_t w, void* stream);
