@@ -24,22 +24,40 @@
 #include "slfp_device.hpp"
 #include "slfp_enc.hpp"
 #include "slfp_host.hpp"
+#include <type_traits>
 
 namespace slfp {
 
 constexpr int kEncTabQ = -1;   // AF template argument: the threshold table (otherwise kFmtAct8 / kFmtSfp7: the long form)
 constexpr int kNoEnc = -2;     // AF: the operand is used as is
 
-// QA(x / Ka), bit-identical to slfp_quantize_f32 (codec.hip: k_quantize_tab / k_codec)
+// A kernel's activation encoder: q(x) = QA(x / Ka), bit-identical to slfp_quantize_f32 (codec.hip: k_quantize_tab / k_codec).
+// act_enc fills the workgroup's threshold table sE (AF == kEncTabQ) or the long form's LUT sT with NT threads; the
+// caller's next __syncthreads() publishes them.
 template <int AF>
-__device__ __forceinline__ float qa1(float x, const float r1, const float lo, const float hi, const unsigned char* __restrict__ tb,
-                                     const ScaleDiv sd, const uint32_t* __restrict__ sT) {
-    if constexpr (AF == kEncTabQ) {
-        const float r = enc_f32(x, r1, lo, hi, tb) + 0.0f;
-        return x != x ? __uint_as_float(kBitsQNaN) : r;
-    } else {
-        return quantize_scaled<AF>(x, sd, sT);
+struct ActEnc {
+    const unsigned char* tb;
+    const uint32_t* sT;
+    float r1, lo, hi;
+    ScaleDiv sd;
+    __device__ __forceinline__ float q(float x) const {
+        if constexpr (AF == kNoEnc) {
+            return x;
+        } else if constexpr (AF == kEncTabQ) {
+            const float r = enc_f32(x, r1, lo, hi, tb) + 0.0f;
+            return x != x ? __uint_as_float(kBitsQNaN) : r;
+        } else {
+            return quantize_scaled<AF>(x, sd, sT);
+        }
     }
+    __device__ __forceinline__ float4 q4(float4 v) const { return make_float4(q(v.x), q(v.y), q(v.z), q(v.w)); }
+};
+
+template <int AF, int NT>
+__device__ __forceinline__ ActEnc<AF> act_enc(uint2* sE, uint32_t* sT, const EncArgs& t, const ScaleDiv& sd) {
+    if constexpr (AF == kEncTabQ) enc_fill<NT>(sE, t);
+    else if constexpr (AF != kNoEnc) lut_fill<AF>(sT);
+    return ActEnc<AF>{reinterpret_cast<const unsigned char*>(sE), sT, t.r1, t.lo, t.hi, sd};
 }
 
 // ---- depthwise 3x3, pad 1 ----------------------------------------------------------------------------------------------
@@ -63,11 +81,8 @@ __global__ __launch_bounds__(kDwThreads) void k_dw3x3_bwd(const float* __restric
     __shared__ __attribute__((aligned(16))) uint2 sE[kEncEntries + 1];
     __shared__ uint32_t sT[16];
     __shared__ float sRed[kDwThreads * kDwParts];
-    if constexpr (AF == kEncTabQ) enc_fill<kDwThreads>(sE, t);
-    else lut_fill<AF>(sT);
+    const ActEnc<AF> enc = act_enc<AF, kDwThreads>(sE, sT, t, sd);
     __syncthreads();
-    const unsigned char* tb = reinterpret_cast<const unsigned char*>(sE);
-    const float r1 = t.r1, lo = t.lo, hi = t.hi;
 
     const int cl = threadIdx.x % g.cw, r = threadIdx.x / g.cw;
     const int c = blockIdx.y * g.cw + cl;
@@ -94,7 +109,7 @@ __global__ __launch_bounds__(kDwThreads) void k_dw3x3_bwd(const float* __restric
         const int gr0 = S == 1 ? oh0 - 1 : oh0;         // first gy row
         auto ldx = [&](int row, int col) -> float {
             if (row < 0 || row >= H || col < 0 || col >= W) return 0.f;   // zero padding of xq
-            return qa1<AF>(xn[((int64_t)row * W + col) * C], r1, lo, hi, tb, sd, sT);
+            return enc.q(xn[((int64_t)row * W + col) * C]);
         };
         auto ldg = [&](int row, int col) -> float {
             if (row < 0 || row >= Ho || col < 0 || col >= Wo) return 0.f;
@@ -210,12 +225,15 @@ __global__ __launch_bounds__(kDwThreads) void k_dw3x3_bwd(const float* __restric
     }
 }
 
-// dst[col] = scale * sum_p part[p][col] over p = 0 .. P-1, in a fixed order.  dwC > 0: the depthwise layout col = k*C + c,
-// k < 9 -> gw[c*9 + k] * scale, k == 9 -> gb[c] (unscaled); dwC == 0: gw[col] * scale.
+// sum[col] = sum_p part[p][col] over p = 0 .. P-1, in a fixed order: thread row tr adds p = tr, tr + 16, ... in increasing p,
+// row 0 then adds the 16 row sums in order.  Where it goes:
+//   dwC > 0: the depthwise layout col = k*C + c, k < 9 -> gw[c*9 + k] = sum * scale, k == 9 -> gb[c] = sum;
+//   T > 0:   the dense layout col = (co*T + tap)*Cin + ci -> gw[(co*Cin + ci)*T + tap] = sum * scale (OIHW);
+//   else:    gw[col] = sum * scale.
 constexpr int kRedCols = 16, kRedRows = 16;
 __global__ __launch_bounds__(kRedCols * kRedRows) void k_reduce_parts(const float* __restrict__ part, int P, int64_t ncols,
-                                                                       float scale, int dwC, float* __restrict__ gw,
-                                                                       float* __restrict__ gb) {
+                                                                       float scale, int dwC, int Cin, int T,
+                                                                       float* __restrict__ gw, float* __restrict__ gb) {
     __shared__ float s[kRedRows][kRedCols];
     const int tc = threadIdx.x % kRedCols, tr = threadIdx.x / kRedCols;
     const int64_t col = (int64_t)blockIdx.x * kRedCols + tc;
@@ -238,19 +256,136 @@ __global__ __launch_bounds__(kRedCols * kRedRows) void k_reduce_parts(const floa
         const int k = (int)(col / dwC), c = (int)(col - (int64_t)k * dwC);
         if (k < 9) { if (gw) gw[(int64_t)c * 9 + k] = sum * scale; }
         else if (gb) gb[c] = sum;
+    } else if (T > 0) {
+        const int ci = (int)(col % Cin);
+        const int64_t r = col / Cin;
+        gw[(r / T * Cin + ci) * T + r % T] = sum * scale;
     } else {
         gw[col] = sum * scale;
     }
 }
 
-// ---- float32 MFMA GEMM: C[M x N] = scale * A[M x K] * B[K x N] ---------------------------------------------------------
-// A_KMAJ: A is stored [K][M] (m contiguous, lda = row pitch), else [M][K] (k contiguous).  B is stored [K][N].
-// 4 waves in a 2 x 2 grid, each owning TM x TN tiles of 32 x 32; BK = 16.  blockIdx.z: a split of K (kps rows each);
-// C then points at the split's partial [z][M][N].  gbpart != null (A_KMAJ only): the first column of workgroups also writes
-// the sums of A over its K range per m, gbpart[z][m] (the bias gradient: A = GY^T).
+// ---- the float32 MFMA tile core of k_gemm_f32, k_dense_gx and k_dense_gw ------------------------------------------------
+// 4 waves in a 2 x 2 grid (wm, wn), each owning TM x TN accumulators of 32 x 32 (v_mfma_f32_32x32x2_f32); the workgroup's
+// 64 TM x 64 TN tile advances BK = 16 per k-step through two k-major LDS tiles sA[BK][BM or more], sB[BK][BN].  The LDS
+// arrays are passed by reference to array, so their row pitch (k_dense_gx pads sA) is a compile-time constant.
 constexpr int kGemmBK = 16;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+template <int TM, int TN>
+__device__ __forceinline__ void acc_zero(f32x16 (&acc)[TM][TN]) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
+}
+
+// acc += sA^T * sB over the BK staged k rows
+template <int TM, int TN, int PA, int PB>
+__device__ __forceinline__ void mfma_chunk(f32x16 (&acc)[TM][TN], const float (&sA)[kGemmBK][PA], const float (&sB)[kGemmBK][PB],
+                                           int wm, int wn, int lane) {
+#pragma unroll
+    for (int kk = 0; kk < kGemmBK; kk += 2) {
+        float a[TM], b[TN];
+#pragma unroll
+        for (int i = 0; i < TM; ++i) a[i] = sA[kk + (lane >> 5)][(wm * TM + i) * 32 + (lane & 31)];
+#pragma unroll
+        for (int j = 0; j < TN; ++j) b[j] = sB[kk + (lane >> 5)][(wn * TN + j) * 32 + (lane & 31)];
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
+    }
+}
+
+// The epilogue.  C/D map of the 32x32 f32 MFMA: col = lane & 31, row = (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5).
+// row(r) gives the address of tile row r at the tile's first column, or null for a row outside the matrix; ncols: the
+// matrix columns from the tile's first one on.
+template <int TM, int TN, class Row>
+__device__ __forceinline__ void store_acc(const f32x16 (&acc)[TM][TN], int wm, int wn, int lane, int ncols, float scale, Row row) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            float* dst = row((wm * TM + i) * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5));
+            if (!dst) continue;
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const int col = (wn * TN + j) * 32 + (lane & 31);
+                if (col < ncols) dst[col] = acc[i][j][q] * scale;
+            }
+        }
+}
+
+// The software-pipelined K loop: load(s) fetches k-step s into registers, store() stages them in LDS, and the loads of
+// step next(s) are in flight while staged() (the bias sums) and the MFMAs run on step s.  live(s): s is a step.
+template <int TM, int TN, int PA, int PB, class Step, class Live, class Next, class Load, class Store, class Staged>
+__device__ __forceinline__ void tile_loop(f32x16 (&acc)[TM][TN], const float (&sA)[kGemmBK][PA], const float (&sB)[kGemmBK][PB],
+                                          int wm, int wn, int lane, Step s, Live live, Next next, Load load, Store store,
+                                          Staged staged) {
+    acc_zero(acc);
+    if (live(s)) load(s);
+    while (live(s)) {
+        store();
+        __syncthreads();
+        const Step s1 = next(s);
+        if (live(s1)) load(s1);
+        staged();
+        mfma_chunk(acc, sA, sB, wm, wn, lane);
+        __syncthreads();
+        s = s1;
+    }
+}
+
+// Float4 group e of a tile into LDS: k-major as it is (row e / (P/4)), or transposed from m-major (row e / (BK/4) of the
+// matrix holds four consecutive k)
+template <int P>
+__device__ __forceinline__ void st4_kmaj(float (&s)[kGemmBK][P], int e, float4 v) {
+    *reinterpret_cast<float4*>(&s[e / (P / 4)][(e % (P / 4)) * 4]) = v;
+}
+template <int P>
+__device__ __forceinline__ void st4_mmaj(float (&s)[kGemmBK][P], int e, float4 v) {
+    const int mm = e / (kGemmBK / 4), kk = (e % (kGemmBK / 4)) * 4;
+    s[kk][mm] = v.x; s[kk + 1][mm] = v.y; s[kk + 2][mm] = v.z; s[kk + 3][mm] = v.w;
+}
+
+// Guarded loads of the gathered tiles: the address is clamped to p where the element is out of range, the load is
+// unconditional and the value selected, so no branch surrounds a global load.  ld4_guard: p[off .. off+3], of which
+// the first n exist (n <= 0: none; VEC: n is 0 or at least 4 and off is a multiple of 4).
+__device__ __forceinline__ float ld_guard(const float* __restrict__ p, int64_t off, bool ok) {
+    const float v = p[ok ? off : 0];
+    return ok ? v : 0.f;
+}
+template <bool VEC>
+__device__ __forceinline__ float4 ld4_guard(const float* __restrict__ p, int64_t off, bool ok, int n) {
+    if constexpr (VEC) {
+        const bool ok4 = ok && n > 0;
+        const float4 v = *reinterpret_cast<const float4*>(p + (ok4 ? off : 0));
+        return ok4 ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+        return make_float4(ld_guard(p, off, ok && n > 0), ld_guard(p, off + 1, ok && n > 1), ld_guard(p, off + 2, ok && n > 2),
+                           ld_guard(p, off + 3, ok && n > 3));
+    }
+}
+
+// The bias gradient from the staged GY^T tiles: thread tid < BM sums column tid of sA (on: it does)
+template <int P>
+__device__ __forceinline__ void gb_add(float& gbs, const float (&sA)[kGemmBK][P], bool on) {
+    if (!on) return;
+#pragma unroll
+    for (int kk = 0; kk < kGemmBK; ++kk) gbs += sA[kk][threadIdx.x];
+}
+__device__ __forceinline__ void gb_store(float* __restrict__ gbpart, int M, int m0, float gbs, bool on) {
+    if (on && m0 + (int)threadIdx.x < M) gbpart[(int64_t)blockIdx.z * M + m0 + threadIdx.x] = gbs;
+}
+
+// ---- C[M x N] = scale * A[M x K] * B[K x N] ------------------------------------------------------------------------------
+// A_KMAJ: A is stored [K][M] (m contiguous, lda = row pitch), else [M][K] (k contiguous).  B is stored [K][N] and goes
+// through the encoder AF on the way into LDS.  blockIdx.z: a split of K (kps rows each); C then points at the split's
+// partial [z][M][N].  gbpart != null (A_KMAJ only): the first column of workgroups also writes the sums of A over its K range
+// per m, gbpart[z][m] (the bias gradient: A = GY^T).
 struct GemmArgs {
     const float* A;
     const float* B;
@@ -269,10 +404,7 @@ __global__ __launch_bounds__(256) void k_gemm_f32(const GemmArgs ga, const EncAr
     __shared__ __attribute__((aligned(16))) float sB[BK][BN];
     __shared__ __attribute__((aligned(16))) uint2 sE[AF == kEncTabQ ? kEncEntries + 1 : 1];
     __shared__ uint32_t sT[16];
-    if constexpr (AF == kEncTabQ) enc_fill<256>(sE, t);
-    else if constexpr (AF != kNoEnc) lut_fill<AF>(sT);
-    const unsigned char* tb = reinterpret_cast<const unsigned char*>(sE);
-    const float r1 = t.r1, lo = t.lo, hi = t.hi;
+    const ActEnc<AF> enc = act_enc<AF, 256>(sE, sT, t, sd);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
@@ -280,7 +412,7 @@ __global__ __launch_bounds__(256) void k_gemm_f32(const GemmArgs ga, const EncAr
     const int kb = blockIdx.z * ga.kps;
     const int ke = min(ga.K, kb + ga.kps);
     const int M = ga.M, N = ga.N;
-    const bool do_gb = ga.gbpart != nullptr && blockIdx.y == 0;
+    const bool gb_on = ga.gbpart != nullptr && blockIdx.y == 0 && tid < BM;
 
     // global -> register staging: BK x BM of A and BK x BN of B as float4 groups (4 consecutive elements along the
     // contiguous dimension), zero outside the matrix
@@ -321,86 +453,33 @@ __global__ __launch_bounds__(256) void k_gemm_f32(const GemmArgs ga, const EncAr
     auto store_tiles = [&]() {
 #pragma unroll
         for (int i = 0; i < AV; ++i) {
-            const int e = tid + i * 256;
-            if constexpr (A_KMAJ) {
-                const int kk = e / (BM / 4), mm = (e % (BM / 4)) * 4;
-                *reinterpret_cast<float4*>(&sA[kk][mm]) = ra[i];
-            } else {
-                const int mm = e / (BK / 4), kk = (e % (BK / 4)) * 4;
-                sA[kk][mm] = ra[i].x; sA[kk + 1][mm] = ra[i].y; sA[kk + 2][mm] = ra[i].z; sA[kk + 3][mm] = ra[i].w;
-            }
+            if constexpr (A_KMAJ) st4_kmaj(sA, tid + i * 256, ra[i]);
+            else st4_mmaj(sA, tid + i * 256, ra[i]);
         }
 #pragma unroll
-        for (int i = 0; i < BV; ++i) {
-            const int e = tid + i * 256;
-            const int kk = e / (BN / 4), nn = (e % (BN / 4)) * 4;
-            float4 v = rb[i];
-            if constexpr (AF != kNoEnc) {   // QA(x / Ka) on load; padding zeros stay zero (Q(0) == 0)
-                v.x = qa1<AF>(v.x, r1, lo, hi, tb, sd, sT); v.y = qa1<AF>(v.y, r1, lo, hi, tb, sd, sT);
-                v.z = qa1<AF>(v.z, r1, lo, hi, tb, sd, sT); v.w = qa1<AF>(v.w, r1, lo, hi, tb, sd, sT);
-            }
-            *reinterpret_cast<float4*>(&sB[kk][nn]) = v;
-        }
+        for (int i = 0; i < BV; ++i) st4_kmaj(sB, tid + i * 256, enc.q4(rb[i]));   // padding zeros stay zero (Q(0) == 0)
     };
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
     float gbs = 0.f;
-
     __syncthreads();   // the encode table is in LDS
-    if (kb < ke) load_tiles(kb);
-    for (int k0 = kb; k0 < ke; k0 += BK) {
-        store_tiles();
-        __syncthreads();
-        if (k0 + BK < ke) load_tiles(k0 + BK);   // in flight while the MFMAs run
-        if (do_gb && tid < BM) {
-#pragma unroll
-            for (int kk = 0; kk < BK; ++kk) gbs += sA[kk][tid];
-        }
-#pragma unroll
-        for (int kk = 0; kk < BK; kk += 2) {
-            float a[TM], b[TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) a[i] = sA[kk + (lane >> 5)][(wm * TM + i) * 32 + (lane & 31)];
-#pragma unroll
-            for (int j = 0; j < TN; ++j) b[j] = sB[kk + (lane >> 5)][(wn * TN + j) * 32 + (lane & 31)];
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-    // C/D map of the 32x32 f32 MFMA: col = lane & 31, row = (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5)
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int col = n0 + (wn * TN + j) * 32 + (lane & 31);
-            if (col >= N) continue;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int row = m0 + (wm * TM + i) * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
-                if (row < M) ga.C[(int64_t)blockIdx.z * M * N + (int64_t)row * ga.ldc + col] = acc[i][j][q] * ga.scale;
-            }
-        }
-    if (do_gb && tid < BM && m0 + tid < M) ga.gbpart[(int64_t)blockIdx.z * M + m0 + tid] = gbs;
+    tile_loop(acc, sA, sB, wm, wn, lane, kb, [&](int k0) { return k0 < ke; }, [](int k0) { return k0 + BK; }, load_tiles,
+              store_tiles, [&]() { gb_add(gbs, sA, gb_on); });
+    float* cz = ga.C + (int64_t)blockIdx.z * M * N + n0;
+    store_acc(acc, wm, wn, lane, N - n0, ga.scale,
+              [&](int r) -> float* { return m0 + r < M ? cz + (int64_t)(m0 + r) * ga.ldc : nullptr; });
+    gb_store(ga.gbpart, M, m0, gbs, gb_on);
 }
 
-// ---- dense k x k / strided / stem layers (groups 1, dilation 1): implicit GEMM on the same 4-wave MFMA tile ------------
+// ---- dense k x k / strided / stem layers (groups 1, dilation 1): implicit GEMM on the same tile core --------------------
 // k_dense_gx: GX[(n,h,w)][ci] = Kw * sum_{tap,co} GY[n, (h+pad_h-kh)/stride_h, (w+pad_w-kw)/stride_w, co] * WT[tap][co][ci].
 // The rows of a workgroup lie in one (h mod stride_h, w mod stride_w) phase, so a tap either reaches every row of the tile
 // or none; the taps that reach none are skipped.  GEMM K runs over (tap, co) with each tap's co run padded to whole BK
-// (zeros), so a k-chunk never straddles two taps.  The A tile is gathered from NHWC gy: unconditional clamped loads and a
-// select to zero.  A phase no tap reaches (1x1 stride 2: three of four) gets exact zeros.
+// (zeros), so a k-chunk never straddles two taps.  The A tile is gathered from NHWC gy.  A phase no tap reaches (1x1
+// stride 2: three of four) gets exact zeros.
 // k_dense_gw: GWp[z][co][(tap,ci)] = sum_{m=(n,ho,wo) in split z} GY[m][co] * QA(X[n, ho*stride_h-pad_h+kh, wo*stride_w-pad_w+kw, ci]/Ka),
-// xq encoded on load as in k_gemm_f32 (never materialised); k_reduce_dense adds the splits in a fixed order, applies Ka and
-// writes OIHW.
+// xq encoded on load as in k_gemm_f32 (never materialised), which it differs from in the B-tile gather only;
+// k_reduce_parts adds the splits in a fixed order, applies Ka and writes OIHW.
 struct DenseGeom {
     int N, H, W, Cin, Ho, Wo, Cout, KH, KW, sh, sw, padh, padw;
 };
@@ -409,6 +488,8 @@ struct DenseGeom {
 __host__ __device__ __forceinline__ int dense_phase_extent(int extent, int phase, int stride) {
     return (extent - phase + stride - 1) / stride;
 }
+
+struct TapStep { int t, c0; };   // a k-step of k_dense_gx: BK output channels from c0 of tap t
 
 template <int TN, bool VEC>
 __global__ __launch_bounds__(256) void k_dense_gx(const float* __restrict__ gy, const float* __restrict__ wt,
@@ -456,7 +537,12 @@ __global__ __launch_bounds__(256) void k_dense_gx(const float* __restrict__ gy, 
         }
         return t;
     };
-    auto load_tiles = [&](int t, int c0) {
+    auto next_step = [&](TapStep s) -> TapStep {
+        if (s.c0 + BK < Cout) return TapStep{s.t, s.c0 + BK};
+        return TapStep{next_tap(s.t + 1), 0};
+    };
+    auto load_tiles = [&](TapStep s) {
+        const int t = s.t, c0 = s.c0;
         const int dh = (ph + g.padh - t / g.KW) / g.sh, dw = (pw + g.padw - t % g.KW) / g.sw;   // exact
 #pragma unroll
         for (int i = 0; i < AV; ++i) {
@@ -464,102 +550,32 @@ __global__ __launch_bounds__(256) void k_dense_gx(const float* __restrict__ gy, 
             const int ho = a_h[i] + dh, wo = a_w[i] + dw;
             const bool ok = a_ok[i] && (unsigned)ho < (unsigned)Ho && (unsigned)wo < (unsigned)Wo;
             const int64_t base = ok ? ((int64_t)(a_nb[i] + ho) * Wo + wo) * Cout : 0;
-            if constexpr (VEC) {
-                const bool ok4 = ok && co < Cout;
-                const float4 v = *reinterpret_cast<const float4*>(gy + (ok4 ? base + co : 0));
-                ra[i] = ok4 ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-            } else {
-                float e[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const bool okj = ok && co + j < Cout;
-                    const float v = gy[okj ? base + co + j : 0];
-                    e[j] = okj ? v : 0.f;
-                }
-                ra[i] = make_float4(e[0], e[1], e[2], e[3]);
-            }
+            ra[i] = ld4_guard<VEC>(gy, base + co, ok, Cout - co);
         }
 #pragma unroll
         for (int i = 0; i < BV; ++i) {
             const int e = tid + i * 256;
             const int co = c0 + e / (BN / 4), ci = n0 + (e % (BN / 4)) * 4;
-            const int64_t base = ((int64_t)t * Cout + co) * Cin;
-            if constexpr (VEC) {
-                const bool ok = co < Cout && ci < Cin;
-                const float4 v = *reinterpret_cast<const float4*>(wt + (ok ? base + ci : 0));
-                rb[i] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-            } else {
-                float q[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const bool okj = co < Cout && ci + j < Cin;
-                    const float v = wt[okj ? base + ci + j : 0];
-                    q[j] = okj ? v : 0.f;
-                }
-                rb[i] = make_float4(q[0], q[1], q[2], q[3]);
-            }
+            rb[i] = ld4_guard<VEC>(wt, ((int64_t)t * Cout + co) * Cin + ci, co < Cout, Cin - ci);
         }
     };
     auto store_tiles = [&]() {
 #pragma unroll
-        for (int i = 0; i < AV; ++i) {
-            const int e = tid + i * 256;
-            const int mm = e / (BK / 4), kk = (e % (BK / 4)) * 4;
-            sA[kk][mm] = ra[i].x; sA[kk + 1][mm] = ra[i].y; sA[kk + 2][mm] = ra[i].z; sA[kk + 3][mm] = ra[i].w;
-        }
+        for (int i = 0; i < AV; ++i) st4_mmaj(sA, tid + i * 256, ra[i]);
 #pragma unroll
-        for (int i = 0; i < BV; ++i) {
-            const int e = tid + i * 256;
-            *reinterpret_cast<float4*>(&sB[e / (BN / 4)][(e % (BN / 4)) * 4]) = rb[i];
-        }
+        for (int i = 0; i < BV; ++i) st4_kmaj(sB, tid + i * 256, rb[i]);
     };
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
-
-    int t = next_tap(0), c0 = 0;
-    if (t < T) load_tiles(t, c0);
-    while (t < T) {
-        store_tiles();
-        __syncthreads();
-        int t1 = t, c1 = c0 + BK;
-        if (c1 >= Cout) { c1 = 0; t1 = next_tap(t + 1); }
-        if (t1 < T) load_tiles(t1, c1);   // in flight while the MFMAs run
-#pragma unroll
-        for (int kk = 0; kk < BK; kk += 2) {
-            float a[TM], b[TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) a[i] = sA[kk + (lane >> 5)][(wm * TM + i) * 32 + (lane & 31)];
-#pragma unroll
-            for (int j = 0; j < TN; ++j) b[j] = sB[kk + (lane >> 5)][(wn * TN + j) * 32 + (lane & 31)];
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
-        }
-        __syncthreads();
-        t = t1; c0 = c1;
-    }
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int r = r0 + (wm * TM + i) * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
-            if (r >= rows) continue;
-            const int n = r / HWp, rem = r - n * HWp;
-            const int hh = rem / Wp, ww = rem - hh * Wp;
-            float* dst = gx + (((int64_t)n * g.H + ph + hh * g.sh) * g.W + pw + ww * g.sw) * Cin;
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int col = n0 + (wn * TN + j) * 32 + (lane & 31);
-                if (col < Cin) dst[col] = acc[i][j][q] * scale;
-            }
-        }
+    tile_loop(acc, sA, sB, wm, wn, lane, TapStep{next_tap(0), 0}, [&](TapStep s) { return s.t < T; }, next_step, load_tiles,
+              store_tiles, []() {});
+    store_acc(acc, wm, wn, lane, Cin - n0, scale, [&](int tr) -> float* {
+        const int r = r0 + tr;
+        if (r >= rows) return nullptr;
+        const int n = r / HWp, rem = r - n * HWp;
+        const int hh = rem / Wp, ww = rem - hh * Wp;
+        return gx + (((int64_t)n * g.H + ph + hh * g.sh) * g.W + pw + ww * g.sw) * Cin + n0;
+    });
 }
 
 template <int TM, int TN, int AF, bool VEC>
@@ -571,10 +587,7 @@ __global__ __launch_bounds__(256) void k_dense_gw(const float* __restrict__ gy, 
     __shared__ __attribute__((aligned(16))) float sB[BK][BN];
     __shared__ __attribute__((aligned(16))) uint2 sE[AF == kEncTabQ ? kEncEntries + 1 : 1];
     __shared__ uint32_t sT[16];
-    if constexpr (AF == kEncTabQ) enc_fill<256>(sE, t);
-    else lut_fill<AF>(sT);
-    const unsigned char* tb = reinterpret_cast<const unsigned char*>(sE);
-    const float r1 = t.r1, lo = t.lo, hi = t.hi;
+    const ActEnc<AF> enc = act_enc<AF, 256>(sE, sT, t, sd);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
@@ -584,7 +597,7 @@ __global__ __launch_bounds__(256) void k_dense_gw(const float* __restrict__ gy, 
     const int64_t kb = (int64_t)blockIdx.z * kps;
     const int64_t ke = kb + kps < K ? kb + kps : K;
     const int HWo = Ho * Wo;
-    const bool do_gb = gbpart != nullptr && blockIdx.y == 0;
+    const bool gb_on = gbpart != nullptr && blockIdx.y == 0 && tid < BM;
 
     constexpr int AV = BM * BK / 4 / 256, BV = BN * BK / 4 / 256;
     static_assert(256 % (BN / 4) == 0, "a thread keeps its B columns over the K loop");
@@ -608,21 +621,7 @@ __global__ __launch_bounds__(256) void k_dense_gw(const float* __restrict__ gy, 
             const int64_t k = k0 + e / (BM / 4);
             const int co = m0 + (e % (BM / 4)) * 4;
             const bool okk = k < ke;
-            const int64_t base = okk ? k * Cout : 0;
-            if constexpr (VEC) {
-                const bool ok = okk && co < M;
-                const float4 v = *reinterpret_cast<const float4*>(gy + (ok ? base + co : 0));
-                ra[i] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-            } else {
-                float q[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const bool okj = okk && co + j < M;
-                    const float v = gy[okj ? base + co + j : 0];
-                    q[j] = okj ? v : 0.f;
-                }
-                ra[i] = make_float4(q[0], q[1], q[2], q[3]);
-            }
+            ra[i] = ld4_guard<VEC>(gy, (okk ? k * Cout : 0) + co, okk, M - co);
         }
 #pragma unroll
         for (int i = 0; i < BV; ++i) {   // X gathered at the shifted pixel; padding and rows past the split are zero
@@ -631,88 +630,34 @@ __global__ __launch_bounds__(256) void k_dense_gw(const float* __restrict__ gy, 
             const int64_t kc = okk ? k : 0;
             const int n = (int)(kc / HWo), rem = (int)(kc - (int64_t)n * HWo);
             const int ho = rem / Wo, wo = rem - ho * Wo;
-            const int hs = ho * g.sh, ws = wo * g.sw;
-            if constexpr (VEC) {
-                const int hi_ = hs + b_kh[0], wi = ws + b_kw[0];
-                const bool ok = okk && b_ok[0] && (unsigned)hi_ < (unsigned)H && (unsigned)wi < (unsigned)W;
-                const float4 v = *reinterpret_cast<const float4*>(x + (ok ? (((int64_t)n * H + hi_) * W + wi) * Cin + b_ci[0] : 0));
-                rb[i] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-            } else {
-                float q[4];
+            int64_t off[NC];
+            bool ok[NC];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int hi_ = hs + b_kh[j], wi = ws + b_kw[j];
-                    const bool ok = okk && b_ok[j] && (unsigned)hi_ < (unsigned)H && (unsigned)wi < (unsigned)W;
-                    const float v = x[ok ? (((int64_t)n * H + hi_) * W + wi) * Cin + b_ci[j] : 0];
-                    q[j] = ok ? v : 0.f;
-                }
-                rb[i] = make_float4(q[0], q[1], q[2], q[3]);
+            for (int j = 0; j < NC; ++j) {
+                const int hi_ = ho * g.sh + b_kh[j], wi = wo * g.sw + b_kw[j];
+                ok[j] = okk && b_ok[j] && (unsigned)hi_ < (unsigned)H && (unsigned)wi < (unsigned)W;
+                off[j] = (((int64_t)n * H + hi_) * W + wi) * Cin + b_ci[j];
             }
+            if constexpr (VEC) rb[i] = ld4_guard<true>(x, off[0], ok[0], 4);
+            else rb[i] = make_float4(ld_guard(x, off[0], ok[0]), ld_guard(x, off[1], ok[1]), ld_guard(x, off[2], ok[2]),
+                                     ld_guard(x, off[3], ok[3]));
         }
     };
     auto store_tiles = [&]() {
 #pragma unroll
-        for (int i = 0; i < AV; ++i) {
-            const int e = tid + i * 256;
-            *reinterpret_cast<float4*>(&sA[e / (BM / 4)][(e % (BM / 4)) * 4]) = ra[i];
-        }
+        for (int i = 0; i < AV; ++i) st4_kmaj(sA, tid + i * 256, ra[i]);
 #pragma unroll
-        for (int i = 0; i < BV; ++i) {
-            const int e = tid + i * 256;
-            float4 v = rb[i];   // QA(x / Ka) on load; the zeros of the padding stay zero (Q(0) == 0)
-            v.x = qa1<AF>(v.x, r1, lo, hi, tb, sd, sT); v.y = qa1<AF>(v.y, r1, lo, hi, tb, sd, sT);
-            v.z = qa1<AF>(v.z, r1, lo, hi, tb, sd, sT); v.w = qa1<AF>(v.w, r1, lo, hi, tb, sd, sT);
-            *reinterpret_cast<float4*>(&sB[e / (BN / 4)][(e % (BN / 4)) * 4]) = v;
-        }
+        for (int i = 0; i < BV; ++i) st4_kmaj(sB, tid + i * 256, enc.q4(rb[i]));   // padding zeros stay zero (Q(0) == 0)
     };
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
     float gbs = 0.f;
-
     __syncthreads();   // the encode table is in LDS
-    if (kb < ke) load_tiles(kb);
-    for (int64_t k0 = kb; k0 < ke; k0 += BK) {
-        store_tiles();
-        __syncthreads();
-        if (k0 + BK < ke) load_tiles(k0 + BK);   // in flight while the MFMAs run
-        if (do_gb && tid < BM) {
-#pragma unroll
-            for (int kk = 0; kk < BK; ++kk) gbs += sA[kk][tid];
-        }
-#pragma unroll
-        for (int kk = 0; kk < BK; kk += 2) {
-            float a[TM], b[TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) a[i] = sA[kk + (lane >> 5)][(wm * TM + i) * 32 + (lane & 31)];
-#pragma unroll
-            for (int j = 0; j < TN; ++j) b[j] = sB[kk + (lane >> 5)][(wn * TN + j) * 32 + (lane & 31)];
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-    float* dstz = part + (int64_t)blockIdx.z * M * N;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int col = n0 + (wn * TN + j) * 32 + (lane & 31);
-            if (col >= N) continue;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int row = m0 + (wm * TM + i) * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
-                if (row < M) dstz[(int64_t)row * N + col] = acc[i][j][q];
-            }
-        }
-    if (do_gb && tid < BM && m0 + tid < M) gbpart[(int64_t)blockIdx.z * M + m0 + tid] = gbs;
+    tile_loop(acc, sA, sB, wm, wn, lane, kb, [&](int64_t k0) { return k0 < ke; }, [](int64_t k0) { return k0 + BK; }, load_tiles,
+              store_tiles, [&]() { gb_add(gbs, sA, gb_on); });
+    float* dstz = part + (int64_t)blockIdx.z * M * N + n0;
+    store_acc(acc, wm, wn, lane, N - n0, 1.0f, [&](int r) -> float* { return m0 + r < M ? dstz + (int64_t)(m0 + r) * N : nullptr; });
+    gb_store(gbpart, M, m0, gbs, gb_on);
 }
 
 // wt[tap][co][ci] = wq[co][ci][tap]
@@ -723,27 +668,6 @@ __global__ __launch_bounds__(256) void k_oihw_to_tap(const float* __restrict__ w
     const int64_t r = i / Cin;
     const int co = (int)(r % Cout), tap = (int)(r / Cout);
     wt[i] = wq[((int64_t)co * Cin + ci) * T + tap];
-}
-
-// gw[co][ci][tap] = scale * sum_p part[p][co][tap][ci], p = 0 .. P-1 in the order of k_reduce_parts
-__global__ __launch_bounds__(kRedCols * kRedRows) void k_reduce_dense(const float* __restrict__ part, int P, int64_t ncols,
-                                                                       float scale, int Cin, int T, float* __restrict__ gw) {
-    __shared__ float s[kRedRows][kRedCols];
-    const int tc = threadIdx.x % kRedCols, tr = threadIdx.x / kRedCols;
-    const int64_t col = (int64_t)blockIdx.x * kRedCols + tc;
-    float a = 0.f;
-    if (col < ncols)
-        for (int p = tr; p < P; p += kRedRows) a += part[(int64_t)p * ncols + col];
-    s[tr][tc] = a;
-    __syncthreads();
-    if (tr != 0 || col >= ncols) return;
-    float sum = 0.f;
-    for (int q = 0; q < kRedRows; ++q) sum += s[q][tc];
-    const int ci = (int)(col % Cin);
-    const int64_t r = col / Cin;
-    const int tap = (int)(r % T);
-    const int64_t co = r / T;
-    gw[(co * Cin + ci) * T + tap] = sum * scale;
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------
@@ -799,11 +723,27 @@ static int dw_blocks(const DwGeom& g) {
     return (int)(pb < 1 ? 1 : pb);
 }
 
+// The split of a GW contraction over its M rows: ~8 workgroups per CU, at least 256 rows per split, partials (cout x ncol
+// and the cout bias sums per split) within kPartCapFloats, at most kMaxParts splits of whole k-steps.
+struct GwSplit {
+    int splits, kps;
+};
+
+static GwSplit gw_split(int64_t M, int64_t cout, int64_t ncol, int64_t tiles) {
+    int64_t sp = ceil_div(8 * kBwdCUs, tiles);
+    sp = std::min<int64_t>(sp, std::max<int64_t>(1, M / 256));
+    sp = std::min<int64_t>(sp, std::max<int64_t>(1, kPartCapFloats / (cout * ncol + cout)));
+    sp = std::min<int64_t>(sp, kMaxParts);
+    if (sp < 1) sp = 1;
+    const int64_t kps = ceil_div(ceil_div(M, sp), kGemmBK) * kGemmBK;
+    return GwSplit{(int)ceil_div(M, kps), (int)kps};
+}
+
 struct PwShape {
     int64_t M;       // rows = N*H*W
     int tm_x, tn_x;  // GX tiling
     int tm_w, tn_w;  // GW tiling
-    int splits, kps; // GW split of M
+    int splits, kps; // GW split of M (gw_split)
 };
 
 static PwShape pw_shape(const slfp_conv2d_desc& d) {
@@ -812,15 +752,8 @@ static PwShape pw_shape(const slfp_conv2d_desc& d) {
     const int64_t cin = d.c_in, cout = d.c_out;
     s.tm_x = s.M >= 128 ? 2 : 1;  s.tn_x = cin >= 128 ? 2 : 1;
     s.tm_w = cout >= 128 ? 2 : 1; s.tn_w = cin >= 128 ? 2 : 1;
-    const int64_t tiles = ceil_div(cout, 64 * s.tm_w) * ceil_div(cin, 64 * s.tn_w);
-    int64_t sp = ceil_div(8 * kBwdCUs, tiles);                 // ~8 workgroups per CU
-    sp = std::min<int64_t>(sp, std::max<int64_t>(1, s.M / 256)); // at least 256 rows per split
-    sp = std::min<int64_t>(sp, std::max<int64_t>(1, kPartCapFloats / (cout * cin + cout)));
-    sp = std::min<int64_t>(sp, kMaxParts);
-    if (sp < 1) sp = 1;
-    int64_t kps = ceil_div(ceil_div(s.M, sp), kGemmBK) * kGemmBK;
-    s.kps = (int)kps;
-    s.splits = (int)ceil_div(s.M, kps);
+    const GwSplit sp = gw_split(s.M, cout, cin, ceil_div(cout, 64 * s.tm_w) * ceil_div(cin, 64 * s.tn_w));
+    s.splits = sp.splits; s.kps = sp.kps;
     return s;
 }
 
@@ -829,7 +762,7 @@ struct DenseShape {
     int64_t ncol;    // gw GEMM columns = taps * C_in
     int tn_x;        // GX tiling (TM = 2)
     int tm_w, tn_w;  // GW tiling
-    int splits, kps; // GW split of M
+    int splits, kps; // GW split of M (gw_split)
 };
 
 static DenseShape dense_shape(const slfp_conv2d_desc& d, const ConvPlan& p) {
@@ -840,15 +773,8 @@ static DenseShape dense_shape(const slfp_conv2d_desc& d, const ConvPlan& p) {
     const bool vec = d.c_in % 4 == 0 && cout % 4 == 0;   // the scalar-gather instantiations exist at 64 x 64 only
     s.tn_x = vec && d.c_in >= 128 ? 2 : 1;
     s.tm_w = vec && cout >= 128 ? 2 : 1; s.tn_w = vec && s.ncol >= 128 ? 2 : 1;
-    const int64_t tiles = ceil_div(cout, 64 * s.tm_w) * ceil_div(s.ncol, 64 * s.tn_w);
-    int64_t sp = ceil_div(8 * kBwdCUs, tiles);                 // ~8 workgroups per CU
-    sp = std::min<int64_t>(sp, std::max<int64_t>(1, s.M / 256)); // at least 256 rows per split
-    sp = std::min<int64_t>(sp, std::max<int64_t>(1, kPartCapFloats / (cout * s.ncol + cout)));
-    sp = std::min<int64_t>(sp, kMaxParts);
-    if (sp < 1) sp = 1;
-    const int64_t kps = ceil_div(ceil_div(s.M, sp), kGemmBK) * kGemmBK;
-    s.kps = (int)kps;
-    s.splits = (int)ceil_div(s.M, kps);
+    const GwSplit sp = gw_split(s.M, cout, s.ncol, ceil_div(cout, 64 * s.tm_w) * ceil_div(s.ncol, 64 * s.tn_w));
+    s.splits = sp.splits; s.kps = sp.kps;
     return s;
 }
 
@@ -900,50 +826,71 @@ static BwdLayout bwd_layout(const slfp_conv2d_desc& d, const ConvPlan& p, BwdKin
     return L;
 }
 
-template <int S>
-static void launch_dw_s(dim3 grid, hipStream_t st, const float* x, const float* gy, const float* wq, float* gx, float* part,
-                        const DwGeom& g, float kws, int ngx, int ngw, const EncArgs* tab, int fmt_act, const ScaleDiv& sd) {
-    static const EncArgs kNone{};
-    const EncArgs& t = tab ? *tab : kNone;
-    if (tab) hipLaunchKernelGGL((k_dw3x3_bwd<S, kEncTabQ>), grid, dim3(kDwThreads), 0, st, x, gy, wq, gx, part, g, kws, ngx, ngw, t, sd);
-    else if (fmt_act == kFmtAct8) hipLaunchKernelGGL((k_dw3x3_bwd<S, kFmtAct8>), grid, dim3(kDwThreads), 0, st, x, gy, wq, gx, part, g, kws, ngx, ngw, t, sd);
-    else hipLaunchKernelGGL((k_dw3x3_bwd<S, kFmtSfp7>), grid, dim3(kDwThreads), 0, st, x, gy, wq, gx, part, g, kws, ngx, ngw, t, sd);
+// A runtime choice as a template argument: fn gets a std::integral_constant to read ::value from.
+template <int V>
+using Int = std::integral_constant<int, V>;
+
+static const EncArgs kNone{};   // the table argument of a kernel that uses none
+
+// The activation encode: the threshold table where act_table has one, else the long form of the format.
+template <class F>
+static void with_act_enc(const EncArgs* tab, int fmt_act, F fn) {
+    if (tab) fn(Int<kEncTabQ>{}, *tab);
+    else if (fmt_act == kFmtAct8) fn(Int<kFmtAct8>{}, kNone);
+    else fn(Int<kFmtSfp7>{}, kNone);
 }
 
-template <int TM, int TN, bool A_KMAJ, int AF>
-static void launch_gemm_v(const GemmArgs& a, dim3 grid, hipStream_t st, const EncArgs& t, const ScaleDiv& sd, bool vec) {
-    if (vec) hipLaunchKernelGGL((k_gemm_f32<TM, TN, A_KMAJ, AF, true>), grid, dim3(256), 0, st, a, t, sd);
-    else hipLaunchKernelGGL((k_gemm_f32<TM, TN, A_KMAJ, AF, false>), grid, dim3(256), 0, st, a, t, sd);
+template <class F>
+static void with_1_or_2(int v, F fn) {   // TM, TN, the depthwise stride
+    if (v == 2) fn(Int<2>{});
+    else fn(Int<1>{});
+}
+
+template <class F>
+static void with_bool(bool b, F fn) {
+    if (b) fn(std::true_type{});
+    else fn(std::false_type{});
 }
 
 template <bool A_KMAJ, int AF>
-static void launch_gemm_t(const GemmArgs& a, int tm, int tn, hipStream_t st, const EncArgs& t, const ScaleDiv& sd, bool vec) {
+static void launch_gemm(const GemmArgs& a, int tm, int tn, bool vec, hipStream_t st, const EncArgs& t, const ScaleDiv& sd) {
     const dim3 grid((unsigned)ceil_div(a.M, 64 * tm), (unsigned)ceil_div(a.N, 64 * tn), (unsigned)ceil_div(a.K, a.kps));
-    if (tm == 2 && tn == 2) launch_gemm_v<2, 2, A_KMAJ, AF>(a, grid, st, t, sd, vec);
-    else if (tm == 2) launch_gemm_v<2, 1, A_KMAJ, AF>(a, grid, st, t, sd, vec);
-    else if (tn == 2) launch_gemm_v<1, 2, A_KMAJ, AF>(a, grid, st, t, sd, vec);
-    else launch_gemm_v<1, 1, A_KMAJ, AF>(a, grid, st, t, sd, vec);
+    with_1_or_2(tm, [&](auto TM) { with_1_or_2(tn, [&](auto TN) { with_bool(vec, [&](auto VEC) {
+        hipLaunchKernelGGL((k_gemm_f32<decltype(TM)::value, decltype(TN)::value, A_KMAJ, AF, decltype(VEC)::value>), grid, dim3(256),
+                           0, st, a, t, sd);
+    }); }); });
 }
 
-template <bool VEC>
-static void launch_dense_gx(const DenseGeom& g, int tn, hipStream_t st, const float* gy, const float* wt, float* gx, float scale) {
+static void launch_dense_gx(const DenseGeom& g, int tn, bool vec, hipStream_t st, const float* gy, const float* wt, float* gx,
+                            float scale) {
     const dim3 grid((unsigned)dense_gx_tiles(g), (unsigned)ceil_div(g.Cin, 64 * tn));
-    if (tn == 2) hipLaunchKernelGGL((k_dense_gx<2, VEC>), grid, dim3(256), 0, st, gy, wt, gx, g, scale);
-    else hipLaunchKernelGGL((k_dense_gx<1, VEC>), grid, dim3(256), 0, st, gy, wt, gx, g, scale);
+    with_1_or_2(tn, [&](auto TN) { with_bool(vec, [&](auto VEC) {
+        hipLaunchKernelGGL((k_dense_gx<decltype(TN)::value, decltype(VEC)::value>), grid, dim3(256), 0, st, gy, wt, gx, g, scale);
+    }); });
 }
 
 template <int AF>
 static void launch_dense_gw(const DenseGeom& g, const DenseShape& s, bool vec, hipStream_t st, const float* gy, const float* x,
                             float* part, float* gbp, const EncArgs& t, const ScaleDiv& sd) {
     const dim3 grid((unsigned)ceil_div(g.Cout, 64 * s.tm_w), (unsigned)ceil_div(s.ncol, 64 * s.tn_w), (unsigned)s.splits);
-#define SLFP_DENSE_GW(TM, TN, V) \
-    hipLaunchKernelGGL((k_dense_gw<TM, TN, AF, V>), grid, dim3(256), 0, st, gy, x, part, gbp, g, s.M, s.kps, t, sd)
-    if (!vec) SLFP_DENSE_GW(1, 1, false);
-    else if (s.tm_w == 2 && s.tn_w == 2) SLFP_DENSE_GW(2, 2, true);
-    else if (s.tm_w == 2) SLFP_DENSE_GW(2, 1, true);
-    else if (s.tn_w == 2) SLFP_DENSE_GW(1, 2, true);
-    else SLFP_DENSE_GW(1, 1, true);
-#undef SLFP_DENSE_GW
+    auto go = [&](auto TM, auto TN, auto VEC) {
+        hipLaunchKernelGGL((k_dense_gw<decltype(TM)::value, decltype(TN)::value, AF, decltype(VEC)::value>), grid, dim3(256), 0, st,
+                           gy, x, part, gbp, g, s.M, s.kps, t, sd);
+    };
+    if (!vec) go(Int<1>{}, Int<1>{}, std::false_type{});   // the scalar gather exists at 64 x 64 only (dense_shape)
+    else with_1_or_2(s.tm_w, [&](auto TM) { with_1_or_2(s.tn_w, [&](auto TN) { go(TM, TN, std::true_type{}); }); });
+}
+
+static int reduce_parts(hipStream_t st, const float* part, int P, int64_t ncols, float scale, int dwC, int Cin, int T, float* gw,
+                        float* gb) {
+    hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)ceil_div(ncols, kRedCols)), dim3(kRedCols * kRedRows), 0, st, part, P, ncols,
+                       scale, dwC, Cin, T, gw, gb);
+    return check_launch("slfp backward reduction kernel");
+}
+
+// gb[co] = sum over the splits of the GW kernels' bias partials
+static int reduce_gb(hipStream_t st, const float* gbpart, int splits, int64_t cout, float* gb) {
+    return reduce_parts(st, gbpart, splits, cout, 1.0f, 0, 0, 0, gb, nullptr);
 }
 
 static int run_bwd(const slfp_conv2d_desc* d, unsigned flags, const float* x, const float* w, const float* gy, float* gx, float* gw,
@@ -990,23 +937,18 @@ static int run_bwd(const slfp_conv2d_desc* d, unsigned flags, const float* x, co
     }
     const EncArgs* tab = act_table(d->ka, p.fmt_act, kEncF32);
     const ScaleDiv sd = make_scale_div(d->ka);
-    static const EncArgs kNone{};
 
     if (kind == kBwdDw) {
         const DwGeom g = dw_geom(*d, p);
         const int pb = dw_blocks(g);
         float* part = reinterpret_cast<float*>(ws + L.part);
-        const bool parts = need_gw;
         const dim3 grid((unsigned)pb, (unsigned)ceil_div(g.C, g.cw));
-        if (d->stride_h == 1) launch_dw_s<1>(grid, st, x_n, gy_n, wq, gx_n, part, g, d->kw_scale, need_gx, parts, tab, p.fmt_act, sd);
-        else launch_dw_s<2>(grid, st, x_n, gy_n, wq, gx_n, part, g, d->kw_scale, need_gx, parts, tab, p.fmt_act, sd);
+        with_act_enc(tab, p.fmt_act, [&](auto AF, const EncArgs& t) { with_1_or_2((int)d->stride_h, [&](auto S) {
+            hipLaunchKernelGGL((k_dw3x3_bwd<decltype(S)::value, decltype(AF)::value>), grid, dim3(kDwThreads), 0, st, x_n, gy_n, wq,
+                               gx_n, part, g, d->kw_scale, (int)need_gx, (int)need_gw, t, sd);
+        }); });
         if ((rc = check_launch("slfp depthwise backward kernel")) != SLFP_OK) return rc;
-        if (parts) {
-            const int64_t ncols = (int64_t)kDwParts * g.C;
-            hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)ceil_div(ncols, kRedCols)), dim3(kRedCols * kRedRows), 0, st, part, pb,
-                               ncols, d->ka, g.C, gw, gb);
-            if ((rc = check_launch("slfp backward reduction kernel")) != SLFP_OK) return rc;
-        }
+        if (need_gw && (rc = reduce_parts(st, part, pb, (int64_t)kDwParts * g.C, d->ka, g.C, 0, 0, gw, gb)) != SLFP_OK) return rc;
     } else if (kind == kBwdDense) {
         const DenseShape s = dense_shape(*d, p);
         const DenseGeom g = dense_geom(*d, p);
@@ -1018,26 +960,18 @@ static int run_bwd(const slfp_conv2d_desc* d, unsigned flags, const float* x, co
             const int64_t nw = Cout * Cin * T;
             hipLaunchKernelGGL(k_oihw_to_tap, dim3((unsigned)ceil_div(nw, 256)), dim3(256), 0, st, wq, wt, (int)Cout, (int)Cin, T);
             if ((rc = check_launch("slfp dense backward weight re-layout kernel")) != SLFP_OK) return rc;
-            if (vec) launch_dense_gx<true>(g, s.tn_x, st, gy_n, wt, gx_n, d->kw_scale);
-            else launch_dense_gx<false>(g, 1, st, gy_n, wt, gx_n, d->kw_scale);
+            launch_dense_gx(g, s.tn_x, vec, st, gy_n, wt, gx_n, d->kw_scale);
             if ((rc = check_launch("slfp dense backward (gx) kernel")) != SLFP_OK) return rc;
         }
         if (need_gw) {
             float* part = reinterpret_cast<float*>(ws + L.part);
             float* gbp = need_gb ? reinterpret_cast<float*>(ws + L.gbpart) : nullptr;
-            if (tab) launch_dense_gw<kEncTabQ>(g, s, vec, st, gy_n, x_n, part, gbp, *tab, sd);
-            else if (p.fmt_act == kFmtAct8) launch_dense_gw<kFmtAct8>(g, s, vec, st, gy_n, x_n, part, gbp, kNone, sd);
-            else launch_dense_gw<kFmtSfp7>(g, s, vec, st, gy_n, x_n, part, gbp, kNone, sd);
+            with_act_enc(tab, p.fmt_act, [&](auto AF, const EncArgs& t) {
+                launch_dense_gw<decltype(AF)::value>(g, s, vec, st, gy_n, x_n, part, gbp, t, sd);
+            });
             if ((rc = check_launch("slfp dense backward (gw) kernel")) != SLFP_OK) return rc;
-            const int64_t ncols = Cout * s.ncol;
-            hipLaunchKernelGGL(k_reduce_dense, dim3((unsigned)ceil_div(ncols, kRedCols)), dim3(kRedCols * kRedRows), 0, st, part,
-                               s.splits, ncols, d->ka, (int)Cin, T, gw);
-            if ((rc = check_launch("slfp backward reduction kernel")) != SLFP_OK) return rc;
-            if (need_gb) {
-                hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)ceil_div(Cout, kRedCols)), dim3(kRedCols * kRedRows), 0, st,
-                                   gbp, s.splits, Cout, 1.0f, 0, gb, nullptr);
-                if ((rc = check_launch("slfp backward reduction kernel")) != SLFP_OK) return rc;
-            }
+            if ((rc = reduce_parts(st, part, s.splits, Cout * s.ncol, d->ka, 0, (int)Cin, T, gw, nullptr)) != SLFP_OK) return rc;
+            if (need_gb && (rc = reduce_gb(st, gbp, s.splits, Cout, gb)) != SLFP_OK) return rc;
         }
     } else {
         const PwShape s = pw_shape(*d);
@@ -1046,7 +980,7 @@ static int run_bwd(const slfp_conv2d_desc* d, unsigned flags, const float* x, co
         if (need_gx) {
             GemmArgs a{gy_n, wq, gx_n, nullptr, (int)s.M, (int)Cin, (int)Cout, Cout, Cin, Cin, (int)Cout, d->kw_scale};
             a.kps = (int)ceil_div(Cout, kGemmBK) * kGemmBK;
-            launch_gemm_t<false, kNoEnc>(a, s.tm_x, s.tn_x, st, kNone, sd, vec);
+            launch_gemm<false, kNoEnc>(a, s.tm_x, s.tn_x, vec, st, kNone, sd);
             if ((rc = check_launch("slfp pointwise backward (gx) kernel")) != SLFP_OK) return rc;
         }
         if (need_gw) {
@@ -1054,21 +988,12 @@ static int run_bwd(const slfp_conv2d_desc* d, unsigned flags, const float* x, co
             float* gbp = reinterpret_cast<float*>(ws + L.gbpart);
             GemmArgs a{gy_n, x_n, part, need_gb ? gbp : nullptr, (int)Cout, (int)Cin, (int)s.M, Cout, Cin, Cin, s.kps,
                        s.splits > 1 ? 1.0f : d->ka};
-            if (tab) launch_gemm_t<true, kEncTabQ>(a, s.tm_w, s.tn_w, st, *tab, sd, vec);
-            else if (p.fmt_act == kFmtAct8) launch_gemm_t<true, kFmtAct8>(a, s.tm_w, s.tn_w, st, kNone, sd, vec);
-            else launch_gemm_t<true, kFmtSfp7>(a, s.tm_w, s.tn_w, st, kNone, sd, vec);
+            with_act_enc(tab, p.fmt_act, [&](auto AF, const EncArgs& t) {
+                launch_gemm<true, decltype(AF)::value>(a, s.tm_w, s.tn_w, vec, st, t, sd);
+            });
             if ((rc = check_launch("slfp pointwise backward (gw) kernel")) != SLFP_OK) return rc;
-            if (s.splits > 1) {
-                const int64_t ncols = Cout * Cin;
-                hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)ceil_div(ncols, kRedCols)), dim3(kRedCols * kRedRows), 0, st,
-                                   part, s.splits, ncols, d->ka, 0, gw, nullptr);
-                if ((rc = check_launch("slfp backward reduction kernel")) != SLFP_OK) return rc;
-            }
-            if (need_gb) {
-                hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)ceil_div(Cout, kRedCols)), dim3(kRedCols * kRedRows), 0, st,
-                                   gbp, s.splits, Cout, 1.0f, 0, gb, nullptr);
-                if ((rc = check_launch("slfp backward reduction kernel")) != SLFP_OK) return rc;
-            }
+            if (s.splits > 1 && (rc = reduce_parts(st, part, s.splits, Cout * Cin, d->ka, 0, 0, 0, gw, nullptr)) != SLFP_OK) return rc;
+            if (need_gb && (rc = reduce_gb(st, gbp, s.splits, Cout, gb)) != SLFP_OK) return rc;
         }
     }
     if (need_gx && d->x_layout == SLFP_LAYOUT_NCHW) rc = slfp_nhwc_to_nchw_f32(gx_n, gx, N, Cin, H, W, stream);
@@ -1130,3 +1055,4 @@ int slfp_conv2d_bwd(const slfp_conv2d_desc* d, const float* x, const float* w_oi
 }
 
 }  // extern "C"
+

@@ -1,17 +1,21 @@
 """GPU: the HIP backward of Conv2d_Q / Linear_Q (options.backward = "hip", slfp_conv2d_bwd) against a float64 reference
 built from the C oracle's quantized operands, next to the composite's error on the same inputs; module-level behaviour,
 determinism and a short fine-tune of the MobileNetV1-CIFAR stack."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
+import _bwd_cases
+from _bwd_cases import DEV, _conv_grads, _errors, _make, _reference, _x_values
 from oracle import slfp_oracle
 from cnns_slfp_quantization_amd import layer_specs, optimizer as O
 from cnns_slfp_quantization_amd import conv2d_func as cf
-from cnns_slfp_quantization_amd.conv2d_func import conv2d_Q, conv2d_Q_bias, linear_Q
+from cnns_slfp_quantization_amd.conv2d_func import conv2d_Q, linear_Q
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
+_check_case = functools.partial(_bwd_cases._check_case, mode="hip", kernels=("dw3x3_bwd", "pw_bwd_mfma_f32"))
 
 
 @pytest.fixture(autouse=True)
@@ -40,96 +44,6 @@ def _geometries():
 
 
 GEOMS = _geometries()
-
-
-def _x_values(shape, ka, gen, relu=False):
-    """Every code range: below 0.0625*Ka, the log range, above the clamp, negatives, exact zeros."""
-    mag = torch.exp2(torch.empty(shape).uniform_(-9, 5, generator=gen)) * ka
-    sign = torch.where(torch.rand(shape, generator=gen) < 0.5, -1.0, 1.0) if not relu else 1.0
-    x = mag * sign
-    x[torch.rand(shape, generator=gen) < 0.05] = 0.0
-    return x.float()
-
-
-def _reference(x, w, gy, mod):
-    """(gx, gw, gb) and the same contractions over absolute values, in float64 from the oracle's quantized operands."""
-    q = mod.q_bit
-    ka, kw = cf._f32(mod.Ka), cf._f32(mod.Kw)
-    xq = torch.from_numpy(slfp_oracle.quantize(x.numpy(), ka, 0 if q == 8 else 2)).double()
-    wq = torch.from_numpy(slfp_oracle.quantize(w.numpy(), kw, 1 if q == 8 else 2)).double()
-    g = gy.double()
-    args = (mod.stride, mod.padding, mod.dilation, mod.groups)
-    gx = torch.nn.grad.conv2d_input(x.shape, wq, g, *args) * kw
-    ax = torch.nn.grad.conv2d_input(x.shape, wq.abs(), g.abs(), *args) * kw
-    gw = torch.nn.grad.conv2d_weight(xq, w.shape, g, *args) * ka
-    aw = torch.nn.grad.conv2d_weight(xq.abs(), w.shape, g.abs(), *args) * ka
-    gb = g.sum(dim=(0, 2, 3))
-    ab = g.abs().sum(dim=(0, 2, 3))
-    return (gx, ax), (gw, aw), (gb, ab)
-
-
-def _errors(got, ref):
-    """(max |g - ref| / abs64 elementwise, tensor-relative L2)."""
-    r, a = ref
-    d = (got.double().cpu() - r).abs()
-    elem = torch.where(a > 0, d / a.clamp_min(1e-300), torch.where(d > 0, torch.inf, 0.0)).max().item()
-    l2 = (d.norm() / r.norm().clamp_min(1e-300)).item()
-    return elem, l2
-
-
-def _conv_grads(mod, x, gy, mode, need=(True, True, True)):
-    cf.options.backward = mode
-    xi = x.detach().clone().requires_grad_(need[0])
-    mod.weight.requires_grad_(need[1])
-    if mod.bias is not None:
-        mod.bias.requires_grad_(need[2])
-    mod.zero_grad(set_to_none=True)
-    out = mod(xi)
-    out.backward(gy)
-    gb = mod.bias.grad if mod.bias is not None else None
-    return xi.grad, mod.weight.grad, gb, out
-
-
-def _make(spec, q, scaled, gen, bias=True):
-    cls = conv2d_Q_bias if scaled else conv2d_Q
-    mod = cls(q, spec.Kw, spec.Ka)(spec.c_in, spec.c_out, spec.k, stride=spec.stride, padding=spec.pad,
-                                   groups=spec.groups, bias=bias).to(DEV)
-    with torch.no_grad():
-        fan = spec.c_in // spec.groups * spec.k[0] * spec.k[1]
-        mod.weight.copy_((torch.randn(mod.weight.shape, generator=gen) * (2.0 / fan) ** 0.5).to(DEV))
-        if mod.bias is not None:
-            mod.bias.copy_((torch.randn(spec.c_out, generator=gen) * 0.1).to(DEV))
-    return mod
-
-
-def _check_case(spec, n, q, scaled, gen, channels_last, sparse=False, label=""):
-    mod = _make(spec, q, scaled, gen)
-    x = _x_values((n, spec.c_in, spec.h, spec.w), spec.Ka, gen)
-    gy = torch.randn((n, spec.c_out, spec.h_out, spec.w_out), generator=gen)
-    if sparse:
-        keep = torch.zeros_like(gy, dtype=torch.bool).view(n, spec.c_out, -1)
-        for c in range(spec.c_out):
-            idx = torch.randperm(keep.shape[0] * keep.shape[2], generator=gen)[:2]
-            keep[idx // keep.shape[2], c, idx % keep.shape[2]] = True
-        gy = gy * keep.view_as(gy)
-    fmt = torch.channels_last if channels_last else torch.contiguous_format
-    xd = x.to(DEV).contiguous(memory_format=fmt)
-    gyd = gy.to(DEV).contiguous(memory_format=fmt)
-    refs = _reference(x, mod.weight.detach().cpu(), gy, mod)
-    res = {}
-    for mode in ("hip", "composite"):
-        gx, gw, gb, _ = _conv_grads(mod, xd, gyd, mode)
-        res[mode] = [_errors(gx, refs[0]), _errors(gw, refs[1])]
-        if mod.bias is not None and scaled:
-            res[mode].append(_errors(gb, refs[2]))
-        if mode == "hip":
-            assert mod._last_bwd_kernel in ("dw3x3_bwd", "pw_bwd_mfma_f32"), mod._last_bwd_kernel
-            assert gx.is_contiguous(memory_format=fmt)
-    print(f"{label} {spec.c_in}->{spec.c_out} k{spec.k[0]} s{spec.stride[0]} @{spec.h} n={n} q{q} "
-          f"{'scaled' if scaled else 'raw'} {'nhwc' if channels_last else 'nchw'}: "
-          f"hip {[(f'{e:.2e}', f'{l:.2e}') for e, l in res['hip']]}  composite {[(f'{e:.2e}', f'{l:.2e}') for e, l in res['composite']]}")
-    for e, l in res["hip"]:
-        assert e <= 1e-5 and l <= 1e-6, res["hip"]
 
 
 @pytest.mark.parametrize("i", range(len(GEOMS)), ids=[f"{n}-{s.c_in}x{s.c_out}k{s.k[0]}s{s.stride[0]}@{s.h}" for n, s in GEOMS])

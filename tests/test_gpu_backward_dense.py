@@ -1,20 +1,25 @@
 """GPU: the dense backward family (options.backward = "hip_all", SLFP_BWD_DENSE, kernel dense_bwd_mfma_f32) against the
-float64 reference of tests/test_gpu_backward.py (torch.nn.grad on the C oracle's xq / wq), with that file's error measures and
-bars: elementwise |g - ref| / sum|terms| <= 1e-5 and tensor-relative L2 <= 1e-6 for gx, gw and gb.  The composite's error on
+float64 reference that tests/test_gpu_backward.py uses (tests/_bwd_cases.py: torch.nn.grad on the C oracle's xq / wq), with the
+same error measures and bars: elementwise |g - ref| / sum|terms| <= 1e-5 and tensor-relative L2 <= 1e-6 for gx, gw and gb.  The composite's error on
 the same inputs is printed next to it."""
+import functools
+import os
+
 import numpy as np
 import pytest
 import torch
 
 import _aniso_cases as A
+import _bwd_cases
+from _bwd_cases import DEV, _contractions, _conv_grads, _errors, _make, _reference, _x_values
 from oracle import slfp_oracle
-from cnns_slfp_quantization_amd import layer_specs, optimizer as O
+from cnns_slfp_quantization_amd import _lib, layer_specs, optimizer as O
 from cnns_slfp_quantization_amd import conv2d_func as cf
-from cnns_slfp_quantization_amd.conv2d_func import conv2d_Q, conv2d_Q_bias, linear_Q
+from cnns_slfp_quantization_amd.conv2d_func import conv2d_Q, linear_Q
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 DENSE = "dense_bwd_mfma_f32"
+_check_case = functools.partial(_bwd_cases._check_case, mode="hip_all", kernels=(DENSE,))
 
 
 @pytest.fixture(autouse=True)
@@ -33,112 +38,6 @@ def _spec(c_in, c_out, k, s, p, h, w=None, ka=0.2, kw=0.1):
     w = h if w is None else w
     ho, wo = (h + 2 * p[0] - k[0]) // s[0] + 1, (w + 2 * p[1] - k[1]) // s[1] + 1
     return layer_specs.ConvSpec(c_in, c_out, k, s, p, 1, False, h, w, ho, wo, ka, kw)
-
-
-def _x_values(shape, ka, gen, relu=False):
-    """Every code range: below 0.0625*Ka, the log range, above the clamp, negatives, exact zeros."""
-    mag = torch.exp2(torch.empty(shape).uniform_(-9, 5, generator=gen)) * ka
-    sign = torch.where(torch.rand(shape, generator=gen) < 0.5, -1.0, 1.0) if not relu else 1.0
-    x = mag * sign
-    x[torch.rand(shape, generator=gen) < 0.05] = 0.0
-    return x.float()
-
-
-def _contractions(xq, wq, gy, mod, x_shape, w_shape):
-    """(gx, gw, gb), each with the same contraction over absolute values, in float64."""
-    ka, kw = cf._f32(mod.Ka), cf._f32(mod.Kw)
-    g = gy.double()
-    args = (mod.stride, mod.padding, mod.dilation, mod.groups)
-    gx = torch.nn.grad.conv2d_input(x_shape, wq, g, *args) * kw
-    ax = torch.nn.grad.conv2d_input(x_shape, wq.abs(), g.abs(), *args) * kw
-    gw = torch.nn.grad.conv2d_weight(xq, w_shape, g, *args) * ka
-    aw = torch.nn.grad.conv2d_weight(xq.abs(), w_shape, g.abs(), *args) * ka
-    return (gx, ax), (gw, aw), (g.sum(dim=(0, 2, 3)), g.abs().sum(dim=(0, 2, 3)))
-
-
-def _reference(x, w, gy, mod):
-    q = mod.q_bit
-    xq = torch.from_numpy(slfp_oracle.quantize(x.numpy(), cf._f32(mod.Ka), 0 if q == 8 else 2)).double()
-    wq = torch.from_numpy(slfp_oracle.quantize(w.numpy(), cf._f32(mod.Kw), 1 if q == 8 else 2)).double()
-    return _contractions(xq, wq, gy, mod, x.shape, w.shape)
-
-
-def _errors(got, ref):
-    """(max |g - ref| / abs64 elementwise, tensor-relative L2)."""
-    r, a = ref
-    d = (got.double().cpu() - r).abs()
-    elem = torch.where(a > 0, d / a.clamp_min(1e-300), torch.where(d > 0, torch.inf, 0.0)).max().item()
-    l2 = (d.norm() / r.norm().clamp_min(1e-300)).item()
-    return elem, l2
-
-
-def _conv_grads(mod, x, gy, mode, need=(True, True, True)):
-    cf.options.backward = mode
-    xi = x.detach().clone().requires_grad_(need[0])
-    mod.weight.requires_grad_(need[1])
-    if mod.bias is not None:
-        mod.bias.requires_grad_(need[2])
-    mod.zero_grad(set_to_none=True)
-    out = mod(xi)
-    out.backward(gy)
-    gb = mod.bias.grad if mod.bias is not None else None
-    return xi.grad, mod.weight.grad, gb, out
-
-
-def _make(spec, q, scaled, gen, bias=True):
-    cls = conv2d_Q_bias if scaled else conv2d_Q
-    mod = cls(q, spec.Kw, spec.Ka)(spec.c_in, spec.c_out, spec.k, stride=spec.stride, padding=spec.pad,
-                                   groups=spec.groups, bias=bias).to(DEV)
-    with torch.no_grad():
-        fan = spec.c_in // spec.groups * spec.k[0] * spec.k[1]
-        mod.weight.copy_((torch.randn(mod.weight.shape, generator=gen) * (2.0 / fan) ** 0.5).to(DEV))
-        if mod.bias is not None:
-            mod.bias.copy_((torch.randn(spec.c_out, generator=gen) * 0.1).to(DEV))
-    return mod
-
-
-def _sparse(gy, gen):
-    """Two non-zeros per channel."""
-    n, c = gy.shape[:2]
-    keep = torch.zeros_like(gy, dtype=torch.bool).view(n, c, -1)
-    for ch in range(c):
-        idx = torch.randperm(n * keep.shape[2], generator=gen)[:2]
-        keep[idx // keep.shape[2], ch, idx % keep.shape[2]] = True
-    return gy * keep.view_as(gy)
-
-
-def _check_case(spec, n, q, scaled, gen, channels_last, sparse=False, label=""):
-    mod = _make(spec, q, scaled, gen)
-    x = _x_values((n, spec.c_in, spec.h, spec.w), spec.Ka, gen)
-    gy = torch.randn((n, spec.c_out, spec.h_out, spec.w_out), generator=gen)
-    if sparse:
-        gy = _sparse(gy, gen)
-    fmt = torch.channels_last if channels_last else torch.contiguous_format
-    xd = x.to(DEV).contiguous(memory_format=fmt)
-    gyd = gy.to(DEV).contiguous(memory_format=fmt)
-    refs = _reference(x, mod.weight.detach().cpu(), gy, mod)
-    res = {}
-    for mode in ("hip_all", "composite"):
-        gx, gw, gb, _ = _conv_grads(mod, xd, gyd, mode)
-        res[mode] = [_errors(gx, refs[0]), _errors(gw, refs[1])]
-        if mod.bias is not None and scaled:
-            res[mode].append(_errors(gb, refs[2]))
-        if mode == "hip_all":
-            assert mod._last_bwd_kernel == DENSE, mod._last_bwd_kernel
-            assert gx.shape == x.shape and gx.is_contiguous(memory_format=fmt)
-            assert gw.shape == mod.weight.shape and gw.is_contiguous()
-            if spec.k == (1, 1) and spec.stride == (2, 2) and spec.pad == (0, 0):
-                # the three phases no output position reads: exact zeros, and written
-                live = torch.zeros(spec.h, spec.w, dtype=torch.bool)
-                live[::2, ::2] = True
-                assert (gx.cpu()[:, :, ~live] == 0).all()
-                assert (gx.cpu()[:, :, live] != 0).any()
-    fmt_e = lambda r: [(f"{e:.2e}", f"{l:.2e}") for e, l in r]
-    print(f"{label} {spec.c_in}->{spec.c_out} k{spec.k} s{spec.stride} p{spec.pad} @{spec.h}x{spec.w} n={n} q{q} "
-          f"{'scaled' if scaled else 'raw'} {'nhwc' if channels_last else 'nchw'}: "
-          f"hip_all {fmt_e(res['hip_all'])}  composite {fmt_e(res['composite'])}")
-    for e, l in res["hip_all"]:
-        assert e <= 1e-5 and l <= 1e-6, res["hip_all"]
 
 
 # ---- 1. the geometry table ------------------------------------------------------------------------------------------------
@@ -406,3 +305,38 @@ def test_finetune_bottleneck_every_step_matches_composite():
         losses.append(loss["hip_all"])
     print("losses", losses)
     assert all(np.isfinite(losses))
+
+
+# ---- 9. every instantiation, on both encodes ------------------------------------------------------------------------------
+# The smallest shape that selects each (TM, TN, VEC) of k_gemm_f32, k_dense_gx and k_dense_gw (pw_shape / dense_shape in
+# csrc/conv_bwd.hip): 128 channels or rows pick the 128-wide tile, 6 -> 10 the scalar loads.
+INSTANTIATIONS = (
+    [("hip", _spec(ci, co, 1, 1, 0, 8)) for ci, co in ((64, 64), (128, 64), (64, 128), (128, 128))]   # M = 128: tm_x = 2
+    + [("hip", _spec(64, 64, 1, 1, 0, 4)),                                                            # M = 32: tm_x = 1
+       ("hip", _spec(6, 10, 1, 1, 0, 8))]
+    + [("hip_all", _spec(ci, co, 3, 1, 1, 6, 5)) for ci, co in ((8, 8), (16, 16), (8, 128), (16, 128), (128, 8), (6, 10))])
+
+
+@pytest.mark.parametrize("q", [8, 7])
+@pytest.mark.parametrize("mode,spec", INSTANTIATIONS, ids=[f"{m}-{s.c_in}x{s.c_out}k{s.k[0]}@{s.h}x{s.w}" for m, s in INSTANTIATIONS])
+def test_every_instantiation_on_the_table_and_the_long_encode(mode, spec, q):
+    """Each tile shape of the pointwise and dense families, once on the threshold table and once on the long-form encode
+    (SLFP_LONG_ENCODE, which no other backward test reaches): both meet the float64 bars, and since both encodes are
+    bit-identical to slfp_quantize_f32 and the sums and their order are the same, gx, gw and gb are equal bit for bit."""
+    L = _lib.load()
+    kernels = (DENSE,) if mode == "hip_all" else ("pw_bwd_mfma_f32",)
+    runs = []
+    try:
+        for long_form in (False, True):
+            os.environ.pop("SLFP_LONG_ENCODE", None)
+            if long_form:
+                os.environ["SLFP_LONG_ENCODE"] = "1"
+            L.slfp_debug_reload_switches()
+            gen = torch.Generator().manual_seed(9000 + spec.c_in * 131 + spec.c_out + q)
+            runs.append(_bwd_cases._check_case(spec, 2, q, True, gen, True, mode, kernels, composite=False,
+                                               label="long form" if long_form else "table"))
+    finally:
+        os.environ.pop("SLFP_LONG_ENCODE", None)
+        L.slfp_debug_reload_switches()
+    for name, a, b in zip(("gx", "gw", "gb"), *runs):
+        assert torch.equal(a, b), name
