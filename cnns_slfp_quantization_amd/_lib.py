@@ -32,6 +32,7 @@ SYMBOLS = (
     "slfp_conv2d_bwd_supported_ex", "slfp_conv2d_bwd_kernel_name_ex", "slfp_conv2d_bwd_workspace_bytes_ex", "slfp_conv2d_bwd_ex",
     "slfp_conv2d_res_supported", "slfp_conv2d_fwd_res",
     "slfp_conv2d_codes_slice_supported", "slfp_conv2d_fwd_codes_slice", "slfp_maxpool2d_codes_ex", "slfp_maxpool2d_out_shape",
+    "slfp_conv2d_entry_supported", "slfp_conv2d_fwd_entry",
 )
 
 
@@ -137,6 +138,8 @@ def load():
         "slfp_conv2d_fwd_codes_slice": (ci, [dp, ctypes.POINTER(ConvIo), vp, vp, vp, vp, vp, ci, vp, i64, vp, vp]),
         "slfp_maxpool2d_codes_ex": (ci, [vp, vp, i64, i64, i64, i64, ci, ci, ci, ci, ci, ci, ci, ci, vp]),
         "slfp_maxpool2d_out_shape": (ci, [i64, i64, ci, ci, ci, ci, ci, ci, ci, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
+        "slfp_conv2d_entry_supported": (ci, [dp, ctypes.POINTER(ConvIo), ci, ci]),
+        "slfp_conv2d_fwd_entry": (ci, [dp, ctypes.POINTER(ConvIo), vp, vp, vp, vp, vp, ci, vp, vp]),
     }
     assert set(sigs) == set(SYMBOLS)
     for name, (res, args) in sigs.items():

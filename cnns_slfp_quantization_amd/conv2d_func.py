@@ -219,11 +219,11 @@ def _conv_weights(mod, desc, weight, stream, cache, kernel=None, want_weight_q=F
 class _Plan:
     """What one (module, input shape, layout, scales, precision) combination resolves to in the C ABI; for the code path
     also its io struct and whether libslfp_hip has a kernel for the combination."""
-    __slots__ = ("desc", "y_shape", "ws_bytes", "kernel", "io", "codes_ok", "res_ok", "slice_ok")
+    __slots__ = ("desc", "y_shape", "ws_bytes", "kernel", "io", "codes_ok", "res_ok", "slice_ok", "entry_ok")
 
     def __init__(self, desc, y_shape, ws_bytes, kernel):
         self.desc, self.y_shape, self.ws_bytes, self.kernel = desc, y_shape, ws_bytes, kernel
-        self.io, self.codes_ok, self.res_ok, self.slice_ok = None, False, False, False
+        self.io, self.codes_ok, self.res_ok, self.slice_ok, self.entry_ok = None, False, False, False, False
 
 
 def _plan(mod, x, weight, nhwc_in, nhwc_out, codes=None, bias=None):
@@ -231,7 +231,7 @@ def _plan(mod, x, weight, nhwc_in, nhwc_out, codes=None, bias=None):
     distinct key and kept on the module: descriptor, output shape, workspace size, kernel name.  codes: None for the
     float32 interface, ("codes", does x hold codes, mod._code_out) for slfp_conv2d_fwd_codes, ("res", does x hold codes, ReLU
     after the add) for slfp_conv2d_fwd_res, ("slice", does x hold codes, mod._code_out, channel count of the wider tensor) for
-    slfp_conv2d_fwd_codes_slice."""
+    slfp_conv2d_fwd_codes_slice, ("entry", mod._code_out) for slfp_conv2d_fwd_entry (float32 in, codes out)."""
     shape = x.shape
     key = (codes, shape, nhwc_in, nhwc_out, _scale_key(mod.Ka, "Ka"), _scale_key(mod.Kw, "Kw"), options.mfma_passes,
            mod.stride, mod.padding, mod.dilation, weight.shape)
@@ -257,6 +257,12 @@ def _plan(mod, x, weight, nhwc_in, nhwc_out, codes=None, bias=None):
             flags = int(mod._post[2]) if mod._post is not None else 0
             plan.slice_ok = bool(L.slfp_conv2d_codes_slice_supported(ctypes.byref(d), ctypes.byref(plan.io),
                                                                      1 if bias is not None else 0, flags, int(codes[3])))
+        elif codes is not None and codes[0] == "entry":
+            plan.io = _conv_io(False, codes[1])
+            flags = int(mod._post[2]) if mod._post is not None else 0
+            plan.entry_ok = bool(L.slfp_conv2d_entry_supported(ctypes.byref(d), ctypes.byref(plan.io),
+                                                               1 if bias is not None else 0, flags))
+            plan.ws_bytes = 0   # the pointwise family needs no workspace
         elif codes is not None:
             plan.io = _conv_io(codes[1], codes[2])
             flags = int(mod._post[2]) if mod._post is not None else 0
@@ -353,7 +359,9 @@ def _hip_conv2d_codes(mod, x, weight, bias):
     """Conv2d_Q.forward inside a chain linked by fusion.link_codes: `x` is float32 or the uint8 codes the previous layer
     wrote for THIS module's Ka / q_bit; the result is uint8 codes for the next layer (mod._code_out = (Ka_next, q_bit_next))
     or float32.  One slfp_conv2d_fwd_codes call where libslfp_hip has a kernel for the combination; otherwise the same
-    values through the float32 interface plus slfp_encode_f32 / slfp_decode_f32 (always correct, never faster)."""
+    values through the float32 interface plus slfp_encode_f32 / slfp_decode_f32 (always correct, never faster).  A module with
+    `_code_entry` set that reads float32 and writes codes asks slfp_conv2d_entry_supported first and, where that says yes, runs
+    ONE slfp_conv2d_fwd_entry call (the 1x1 layer at which a chain of codes begins)."""
     x_codes = x.dtype == torch.uint8
     out = mod._code_out
     if not x_codes:
@@ -367,6 +375,25 @@ def _hip_conv2d_codes(mod, x, weight, bias):
 
     if x.dim() != 4 or not x.is_contiguous(memory_format=torch.channels_last):
         return float32_interface()   # the code path is NHWC only; anything else takes the float32 interface
+    if not x_codes and out is not None and mod._code_entry:
+        plan = _plan(mod, x, weight, True, True, ("entry", out), bias)
+        if plan.entry_ok:
+            L = _lib.load()
+            d = plan.desc
+            with _on_device(x.device):
+                stream = torch.cuda.current_stream(x.device)
+                blob = _conv_weights(mod, d, weight, stream, True, plan.kernel)
+                y = torch.empty(plan.y_shape, dtype=torch.uint8, device=x.device, memory_format=torch.channels_last)
+                b, ps, psh, flags = _epilogue_args(mod, bias, x.device)
+                _lib.check(L.slfp_conv2d_fwd_entry(ctypes.byref(d), ctypes.byref(plan.io), x.data_ptr(), blob.data_ptr(),
+                                                   b.data_ptr() if b is not None else None,
+                                                   ps.data_ptr() if ps is not None else None,
+                                                   psh.data_ptr() if psh is not None else None, flags, y.data_ptr(),
+                                                   stream.cuda_stream))
+            mod._last_kernel = plan.kernel + "+codes_out"
+            mod._last_input, mod._last_codes = x.detach(), None
+            mod._input_q = None
+            return y
     plan = _plan(mod, x, weight, True, True, ("codes", x_codes, out), bias)
     if not plan.codes_ok:
         return float32_interface()
@@ -626,6 +653,7 @@ def _conv_class(q_bit, Kw, Ka, bias_default, scaled_bias):
             self._last_bwd_kernel = None   # what the last backward ran: a slfp_conv2d_bwd kernel name or "composite"
             self._post = None  # (scale, shift, relu): fused eval-BN + ReLU epilogue (fusion.fuse_bn_relu)
             self._code_out = None   # (Ka, q_bit) of the next Conv2d_Q: hand it 1-byte codes (fusion.link_codes)
+            self._code_entry = False   # with _code_out on a float32 input: ONE slfp_conv2d_fwd_entry launch where the library has it
             self._last_codes = None
             self.residual_relu = False   # forward(x, residual=r): a ReLU follows the add (fusion.fuse_residual sets it)
             self._scaled_bias = scaled_bias

@@ -533,6 +533,55 @@ static int fwd_codes_any(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, co
     return launch_stem_codes(*d, p, reinterpret_cast<const float*>(x), reinterpret_cast<const float*>(wprep), bias, post, y, cio, st);
 }
 
+// ---- the layer at which a chain of codes begins: pointwise, float32 in -> codes out (include/slfp.h: slfp_conv2d_fwd_entry) ----
+// A query and an entry point of their own: slfp_conv2d_codes_supported keeps answering 0 for this combination (codes_route above
+// is unchanged), so every link count that rests on it stays what it was.
+static bool entry_route(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int relu, ConvPlan* p) {
+    if (!d || !io) return false;
+    if (io->x_codes != 0 || io->y_codes != 1) return false;
+    if (make_plan(d, p) != SLFP_OK) return false;
+    if (d->x_layout != SLFP_LAYOUT_NHWC || d->y_layout != SLFP_LAYOUT_NHWC) return false;
+    if ((relu & ~(SLFP_POST_RELU | SLFP_POST_LAYEROUT)) != 0 || (relu & SLFP_POST_LAYEROUT)) return false;
+    if (io->y_qbits != 8 && io->y_qbits != 7) return false;
+    if (!(io->y_ka > 0.f) || !scale_div_ok(io->y_ka)) return false;
+    if (long_encode_forced()) return false;
+    return pointwise_entry_applicable(*d, *p, relu, io->y_ka, io->y_qbits == 8 ? kFmtAct8 : kFmtSfp7);
+}
+
+extern "C" int slfp_conv2d_entry_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int relu) {
+    (void)has_bias;   // both kernels take a bias
+    ConvPlan p;
+    return entry_route(d, io, relu, &p) ? 1 : 0;
+}
+
+extern "C" int slfp_conv2d_fwd_entry(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const float* x, const void* wprep,
+                                     const float* bias, const float* post_scale, const float* post_shift, int relu,
+                                     void* y_codes, void* stream) {
+    if (!d || !io) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_entry: null descriptor");
+    ConvPlan p;
+    int rc = make_plan(d, &p);
+    if (rc != SLFP_OK) return rc;
+    if (!x || !wprep || !y_codes) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_entry: null pointer");
+    if ((post_scale == nullptr) != (post_shift == nullptr))
+        return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_entry: post_scale and post_shift must be given together");
+    if (!aligned16(x) || !aligned16(y_codes) || !aligned16(wprep) || (bias && !aligned16(bias)) ||
+        (post_scale && (!aligned16(post_scale) || !aligned16(post_shift))))
+        return fail(SLFP_ERR_ALIGNMENT, "slfp_conv2d_fwd_entry: pointers must be 16-byte aligned");
+    if (io->x_codes != 0 || io->y_codes != 1)
+        return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_entry: reads float32 and writes codes (io->x_codes == 0, io->y_codes == 1; "
+                                      "slfp_conv2d_entry_supported)");
+    if (io->y_qbits != 8 && io->y_qbits != 7)
+        return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_entry: io->y_qbits must be 8 or 7, got %d (slfp_conv2d_entry_supported)", io->y_qbits);
+    if (!(io->y_ka > 0.f) || !scale_div_ok(io->y_ka))
+        return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_entry: io->y_ka must be a positive scale within [1e-30, 1e30] (slfp_conv2d_entry_supported)");
+    if (!entry_route(d, io, relu, &p))
+        return fail(SLFP_ERR_UNSUPPORTED, "slfp_conv2d_fwd_entry: this layer / io combination has no float32 -> codes kernel "
+                                          "(slfp_conv2d_entry_supported); use slfp_conv2d_fwd_post and slfp_encode_f32");
+    const PostOp post{post_scale, post_shift, (relu & SLFP_POST_RELU) ? 1 : 0, 0};
+    const CodeIo cio{false, true, io->y_ka, io->y_qbits == 7 ? kFmtSfp7 : kFmtAct8};
+    return launch_pointwise_entry(*d, p, x, wprep, bias, post, y_codes, cio, as_stream(stream));
+}
+
 // ---- residual operand in the pointwise epilogue (include/slfp.h: slfp_conv2d_fwd_res) ----
 static bool res_route(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, bool has_bias, int relu, ConvPlan* p) {
     if (!d || !io) return false;

@@ -48,9 +48,15 @@
 // switch on both kernels' store path adds p.res to the finished value -- one float32 add after the affine's fma, the ReLU
 // after it -- with every 16 bytes of the residual loaded in the layout of the store they pair with and requested one tile ahead
 // of the values they are added to.  The instantiations without it are unchanged.
+// Code output (slfp_conv2d_fwd_entry; the layer at which a chain of 1-byte codes begins): a compile-time YC switch on both kernels
+// (single-pass table forms only) turns the finished float4 into 4 code bytes of the CONSUMER's quantizer -- the store path of
+// conv_pw_codes.hip under this file's load path: the dwords of four channel tiles go through rows_transpose4 and every lane stores
+// 16 consecutive channel codes of its pixel.  The consumer's code table rides in PwParams::enc_lo in compact form (the single-pass
+// forms do not use that slot).  The instantiations without it are unchanged.
 #include <cstdlib>
 #include "slfp_device.hpp"
 #include "slfp_enc.hpp"
+#include "slfp_codes.hpp"
 #include "slfp_host.hpp"
 #include "conv_pw_params.hpp"
 
@@ -110,6 +116,17 @@ __device__ __forceinline__ void encode4(const float4 v, const ScaleDiv sd, const
     }
 }
 
+// YC kernels with the ReLU folded into the code quantizer: the float32 interface's fmaxf(NaN, 0) is 0, whose code is that of exact
+// zero, while enc4_code_relu gives a NaN the code slfp_encode_f32 gives it (0x00).  NaN -> 0 on a cold branch keeps the bytes equal
+// to slfp_encode_f32 of the float32 interface's output for NaN inputs too.
+__device__ __forceinline__ float4 relu_of_nan4(float4 r) {
+    if (__builtin_expect(enc_has_nan4(r), 0)) {
+        r.x = r.x != r.x ? 0.f : r.x; r.y = r.y != r.y ? 0.f : r.y;
+        r.z = r.z != r.z ? 0.f : r.z; r.w = r.w != r.w ? 0.f : r.w;
+    }
+    return r;
+}
+
 __device__ __forceinline__ half8 join(const half4 a, const half4 b) {
     return half8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
 }
@@ -130,12 +147,15 @@ constexpr int kStreamThreads = 512;
 // 16 channels): HBM writes of 64-byte pieces run at about half the rate (profiles/micro/bw_patterns.hip).
 // RES (with TAB): y = relu?(affine(conv) + res) (slfp_conv2d_fwd_res).  Each piece of p.res is loaded with the address pattern
 // of the store it pairs with, one tile (STG: one pair of tiles) ahead of the MFMA sweep that produces the values it is added to.
-template <int FMT, int PASSES, int KS, bool KFULL, bool A8 = false, bool TAB = false, bool STG = false, bool RES = false>
+// YC (with TAB, single pass): the output leaves as the consumer's 1-byte codes (p.yc; N a multiple of 16), four channel tiles per
+// 16-byte store as in k_pwc_stream; the ReLU, if any, is the code quantizer's (enc4_code_relu).
+template <int FMT, int PASSES, int KS, bool KFULL, bool A8 = false, bool TAB = false, bool STG = false, bool RES = false, bool YC = false>
 __global__ __launch_bounds__(kStreamThreads) void k_pw_stream(const PwParams p) {
     static_assert(!STG || (TAB && !A8), "staged stores: table kernels with 16-byte channel alignment");
     static_assert(!RES || (TAB && !A8), "residual operand: table kernels with 16-byte channel alignment");
+    static_assert(!YC || (TAB && !A8 && !STG && !RES && PASSES == 1), "code output: single-pass table kernels, 16-byte channel alignment");
     constexpr int TABB = TAB ? kPwTab : 64;
-    constexpr int TABL = (TAB && PASSES == 3) ? kPwTab : 16;   // three-pass table kernels: the residual plane's table
+    constexpr int TABL = (TAB && (PASSES == 3 || YC)) ? kPwTab : 16;   // three-pass table kernels: the residual plane's table; YC: the code table
     // The quantizer's table is STATIC LDS: its address is a compile-time constant, so a lookup is `ds_read_b64 v, bin`
     // with no add of the (link-time) dynamic-LDS base -- hipcc emitted one VALU add per lookup (33 in the depthwise kernel).
     __shared__ __attribute__((aligned(16))) unsigned char stab[TABB];
@@ -147,7 +167,7 @@ __global__ __launch_bounds__(kStreamThreads) void k_pw_stream(const PwParams p) 
     _Float16* wl_lo = wl_hi + (size_t)wfrags * 512;
     if constexpr (TAB) enc_fill<kStreamThreads>(reinterpret_cast<uint2*>(stab), p.enc);
     else lut_fill<FMT>(sT);
-    if constexpr (TAB && PASSES == 3) enc_fill_compact<kStreamThreads>(reinterpret_cast<uint2*>(stab_lo), p.enc_lo);
+    if constexpr (TAB && (PASSES == 3 || YC)) enc_fill_compact<kStreamThreads>(reinterpret_cast<uint2*>(stab_lo), p.enc_lo);
     // W blob -> LDS (same fragment order), 16 bytes per thread per step
     for (int i = threadIdx.x; i < wfrags * 64; i += kStreamThreads) {
         reinterpret_cast<half8*>(wl_hi)[i] = reinterpret_cast<const half8*>(p.whi)[i];
@@ -270,17 +290,35 @@ __global__ __launch_bounds__(kStreamThreads) void k_pw_stream(const PwParams p) 
                 if (p.post.scale) {
                     r.x = __builtin_fmaf(r.x, sc.x, sh.x); r.y = __builtin_fmaf(r.y, sc.y, sh.y);
                     r.z = __builtin_fmaf(r.z, sc.z, sh.z); r.w = __builtin_fmaf(r.w, sc.w, sh.w);
-                    if (p.post.layerout) r = layerout4(r);
+                    if constexpr (!YC) {   // (no layer-output quantizer in front of a code output: refused on the host)
+                        if (p.post.layerout) r = layerout4(r);
+                    }
                 }
             } else {
                 r = epilogue(acc, make_float4(0.f, 0.f, 0.f, 0.f), p.s1x, p.s2);
             }
-            if constexpr (!RES) {   // with a residual the ReLU follows the add (res_add)
+            if constexpr (!RES && !YC) {   // with a residual the ReLU follows the add (res_add); with code output it is the quantizer's
                 if (p.post.relu) { r.x = fmaxf(r.x, 0.f); r.y = fmaxf(r.y, 0.f); r.z = fmaxf(r.z, 0.f); r.w = fmaxf(r.w, 0.f); }
             }
             return r;
         };
-        if constexpr (STG) {
+        if constexpr (YC) {
+            uint8_t* yr = p.yc + (size_t)m * p.N;
+            const float r1 = p.enc_lo.r1, lo = p.enc_lo.lo, hi = p.enc_lo.hi;
+            for (int j0 = 0; j0 < p.n_tiles; j0 += 4) {   // n_tiles is a multiple of 4 (the blob is padded to 64 channels)
+                uint32_t c[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float4 r = tile_out(j0 + j);
+                    if (p.sgn) c[j] = code_sign4(enc4_code<false>(r, r1, lo, hi, stab_lo), r, p.fmt_out);
+                    else c[j] = enc4_code_relu(relu_of_nan4(r), r1, lo, hi, stab_lo);
+                }
+                rows_transpose4(c[0], c[1], c[2], c[3]);   // lane-quarter kq now holds channels 16 (j0 + kq) + 0..15
+                const int n = (j0 + kq) * 16;
+                typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+                if (live && n < p.N) *reinterpret_cast<u32x4*>(yr + n) = u32x4{c[0], c[1], c[2], c[3]};
+            }
+        } else if constexpr (STG) {
             // per-unit descriptor: rows beyond M and channels beyond N get an out-of-range offset (store dropped)
             const uint32_t ybytes = (uint32_t)(((uint64_t)(p.M - g * 16) * p.N * 4) > 0xFFFFFFFFull ? 0xFFFFFFFFull : ((uint64_t)(p.M - g * 16) * p.N * 4));
             const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(p.y + (size_t)g * 16 * p.N, 0, ybytes, 0x00020000);
@@ -354,12 +392,15 @@ __global__ __launch_bounds__(kStreamThreads) void k_pw_stream(const PwParams p) 
 // (4 pixel rows x the wave's 64 adjacent channels) instead of 64-byte pieces, with the nt hint (SLFP_NT_PW_STG).
 // RES (with STG): y = relu?(affine(conv) + res) (slfp_conv2d_fwd_res).  The residual is loaded in the staged layout (the 16 bytes
 // each staged store writes), one 16-row tile ahead: the first tile row's pieces are requested before the last MFMA sweep.
-template <int FMT, int PASSES, int WM, int WN, int MT, int NT, bool KFULL, bool TAB = false, bool STG = false, bool RES = false>
+// YC (with TAB, single pass, NT == 4): the output leaves as the consumer's 1-byte codes (p.yc; N a multiple of 16): per tile row
+// the wave's four channel tiles are the four dwords of k_pwc_tiled's code epilogue; no staging area.
+template <int FMT, int PASSES, int WM, int WN, int MT, int NT, bool KFULL, bool TAB = false, bool STG = false, bool RES = false, bool YC = false>
 __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pw_tiled(const PwParams p) {
     static_assert(!STG || NT == 4, "the staged epilogue stores a wave's 64 channels per row");
     static_assert(!RES || STG, "residual operand: staged epilogue only");
+    static_assert(!YC || (TAB && !STG && !RES && PASSES == 1 && NT == 4), "code output: single-pass table kernels, four channel tiles per wave");
     constexpr int TABB = TAB ? kPwTab : 64;
-    constexpr int TABL = (TAB && PASSES == 3) ? kPwTab : 16;
+    constexpr int TABL = (TAB && (PASSES == 3 || YC)) ? kPwTab : 16;
     constexpr int T = 64 * WM * WN;
     constexpr int BM = WM * MT * 16;
     constexpr int BN = WN * NT * 16;
@@ -374,7 +415,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pw_til
     unsigned char* xs = smem;  // [2 buffers][hi, lo][BM rows][128 B]
     if constexpr (TAB) enc_fill<T>(reinterpret_cast<uint2*>(stab), p.enc);
     else lut_fill<FMT>(sT);
-    if constexpr (TAB && PASSES == 3) enc_fill_compact<T>(reinterpret_cast<uint2*>(stab_lo), p.enc_lo);
+    if constexpr (TAB && (PASSES == 3 || YC)) enc_fill_compact<T>(reinterpret_cast<uint2*>(stab_lo), p.enc_lo);
 
     const uint32_t b = xcd_remap(blockIdx.x, p.nblocks);
     const uint32_t nb = b % p.n_blocks, mb = b / p.n_blocks;
@@ -596,6 +637,34 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pw_til
         __syncthreads();
     }
     SLFP_STAMP(13);
+    if constexpr (YC) {
+        const float r1 = p.enc_lo.r1, lo = p.enc_lo.lo, hi = p.enc_lo.hi;
+#pragma unroll
+        for (int i = 0; i < MT; ++i) {
+            uint32_t c[NT];
+#pragma unroll
+            for (int j = 0; j < NT; ++j) {
+                const int n = (ntile0 + j) * 16 + kq * 4;
+                const bool in = n < p.N;   // channel tiles past C_out: computed from clamped weights, never stored
+                float4 r = epilogue(acc[i][j], in ? bias_q256(p, n) : make_float4(0.f, 0.f, 0.f, 0.f), p.s1x, p.s2);
+                if (p.post.scale) {
+                    const float4 sc = *reinterpret_cast<const float4*>(lsc + (in ? n - n_lo : 0));
+                    const float4 sh = *reinterpret_cast<const float4*>(lsh + (in ? n - n_lo : 0));
+                    r.x = __builtin_fmaf(r.x, sc.x, sh.x); r.y = __builtin_fmaf(r.y, sc.y, sh.y);
+                    r.z = __builtin_fmaf(r.z, sc.z, sh.z); r.w = __builtin_fmaf(r.w, sc.w, sh.w);
+                }
+                if (p.sgn) c[j] = code_sign4(enc4_code<false>(r, r1, lo, hi, stab_lo), r, p.fmt_out);
+                else c[j] = enc4_code_relu(relu_of_nan4(r), r1, lo, hi, stab_lo);   // the ReLU is the quantizer's
+            }
+            rows_transpose4(c[0], c[1], c[2], c[3]);   // lane-quarter kq: channels 16 (ntile0 + kq) + 0..15 of pixel row `col`
+            const int row = (wm * MT + i) * 16 + col;
+            const int n = (ntile0 + kq) * 16;
+            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+            if (row < p.rb && m0 + row < p.M && n < p.N)
+                *reinterpret_cast<u32x4*>(p.yc + (size_t)(m0 + row) * p.N + n) = u32x4{c[0], c[1], c[2], c[3]};
+        }
+        return;
+    }
     if constexpr (STG) {
         unsigned char* stg = xs + 2 * (PASSES == 3 ? 2 : 1) * XBYTES + wave * (16 * kStgRow);   // private to this wave
         const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(p.y + (size_t)m0 * p.N, 0, ybytes, 0x00020000);
@@ -686,6 +755,19 @@ static int launch_tiled_k(PwParams& p, hipStream_t stream) {
     const int64_t nblocks = (int64_t)p.m_blocks * p.n_blocks;
     if (nblocks > 0x7FFFFFFF) return fail(SLFP_ERR_UNSUPPORTED, "pointwise: grid too large");
     p.nblocks = (uint32_t)nblocks;
+    if (p.yc) {   // code output: the single-pass table form with four channel tiles per wave only (pointwise_entry_applicable)
+        if constexpr (NT == 4 && PASSES == 1) {
+            if (p.enc.valid && p.enc_lo.valid && !p.res) {
+                const size_t lds = (size_t)2 * BM * 128;   // dynamic part (both tables are static LDS; no staging area)
+                auto fn = k_pw_tiled<FMT, 1, WM, WN, MT, NT, KFULL, true, false, false, true>;
+                int rc = set_lds_limit(reinterpret_cast<const void*>(fn), lds);
+                if (rc != SLFP_OK) return rc;
+                hipLaunchKernelGGL(fn, dim3(p.nblocks), dim3(T), lds, stream, p);
+                return check_launch("slfp pointwise (tiled, code output) kernel");
+            }
+        }
+        return fail(SLFP_ERR_UNSUPPORTED, "pointwise: no code-output form of this kernel variant");
+    }
     if (p.res) {   // residual operand: the table quantizer + staged epilogue form only (pointwise_res_applicable asks for both)
         if constexpr (NT == 4) {
             if (p.enc.valid && (PASSES == 1 || p.enc_lo.valid) && !switches().pw_nostg) {
@@ -735,6 +817,25 @@ static int launch_tiled(PwParams& p, hipStream_t stream) {
 
 template <int FMT, int PASSES, int KS>
 static int launch_stream_ks(PwParams& p, hipStream_t stream) {
+    if (p.yc) {   // code output: the single-pass table form, 16-byte channel alignment (pointwise_entry_applicable)
+        if constexpr (PASSES == 1) {
+            if (p.enc.valid && p.enc_lo.valid && !p.res && !(p.K % 4 || p.N % 16)) {
+                const size_t lds = (size_t)p.n_tiles * p.KS * 1024 + (size_t)3 * p.n_tiles * 16 * sizeof(float);   // dynamic part
+                auto fn = (p.K % 32 == 0) ? k_pw_stream<FMT, 1, KS, true, false, true, false, false, true>
+                                          : k_pw_stream<FMT, 1, KS, false, false, true, false, false, true>;
+                int rc = set_lds_limit(reinterpret_cast<const void*>(fn), lds);
+                if (rc != SLFP_OK) return rc;
+                int per_cu = resident_blocks_per_cu(reinterpret_cast<const void*>(fn), kStreamThreads, lds);
+                per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
+                int64_t grid = (int64_t)device_cu_count() * per_cu;
+                const int64_t need = ceil_div((p.M + 15) / 16, kStreamThreads / 64);
+                if (grid > need) grid = need;
+                hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kStreamThreads), lds, stream, p);
+                return check_launch("slfp pointwise (stream, code output) kernel");
+            }
+        }
+        return fail(SLFP_ERR_UNSUPPORTED, "pointwise: no code-output form of this kernel variant");
+    }
     const bool tab = p.enc.valid != 0 && (PASSES == 1 || p.enc_lo.valid != 0);
     // staged 128-byte stores (with the nt hint) pay where stores dominate and follow each other closely (K <= 64: pw1
     // -14 %, pw2 -13 %) and at K = 256 (256->256 @28: 113 -> 97-105 us).  At K = 128 the layer itself loses 5-8 % (profiles/
@@ -827,11 +928,38 @@ bool pointwise_res_applicable(const slfp_conv2d_desc& d, const ConvPlan& plan) {
     return true;
 }
 
+// Does the code-output form (YC) of the kernel launch_pointwise would pick exist for this layer and this consumer?  Host-only.
+bool pointwise_entry_applicable(const slfp_conv2d_desc& d, const ConvPlan& plan, int post_flags, float y_ka, int y_fmt) {
+    if (plan.family != kPointwise || plan.repad || plan.passes != 1) return false;
+    if (post_flags & SLFP_POST_LAYEROUT) return false;
+    if (d.c_out % 16 || d.c_in % 4) return false;
+    if (switches().pw_notab || !act_table(d.ka, plan.fmt_act, kEncF16P)) return false;
+    const EncArgs* t = enc_table(y_ka, y_fmt, kEncCode);
+    return t->valid && enc_compact_covers(*t);   // the code table travels in PwParams::enc_lo's compact form
+}
+
+static int launch_pointwise_any(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x, const void* wfrag, const float* bias,
+                                const PostOp& post, float* y, hipStream_t stream, const float* res, uint8_t* yc, float y_ka, int y_fmt);
+
 int launch_pointwise(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x, const void* wfrag,
                      const float* bias, const PostOp& post, float* y, hipStream_t stream, const float* res) {
+    return launch_pointwise_any(d, plan, x, wfrag, bias, post, y, stream, res, nullptr, 1.f, kFmtAct8);
+}
+
+int launch_pointwise_entry(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x, const void* wfrag, const float* bias,
+                           const PostOp& post, void* y_codes, const CodeIo& io, hipStream_t stream) {
+    // applicability is the caller's check (pointwise_entry_applicable at the ABI boundary); the table is looked up once, below
+    if (!y_codes || io.x_codes || !io.y_codes || io.y_ld || post.layerout || plan.family != kPointwise || plan.repad || d.c_out % 16)
+        return fail(SLFP_ERR_UNSUPPORTED, "pointwise: no float32 -> codes kernel for this layer (slfp_conv2d_entry_supported)");
+    return launch_pointwise_any(d, plan, x, wfrag, bias, post, nullptr, stream, nullptr, reinterpret_cast<uint8_t*>(y_codes), io.y_ka, io.y_fmt);
+}
+
+static int launch_pointwise_any(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x, const void* wfrag, const float* bias,
+                                const PostOp& post, float* y, hipStream_t stream, const float* res, uint8_t* yc, float y_ka, int y_fmt) {
     PwParams p;
     p.post = post;
     p.x = x; p.bias = bias; p.y = y; p.res = res;
+    p.yc = yc; p.sgn = post.relu ? 0 : 1; p.fmt_out = y_fmt;
     p.K = (int)d.c_in; p.N = (int)d.c_out;
     p.KS = (int)(plan.k_pad / 32);
     p.n_tiles = (int)(plan.n_pad / 16);
@@ -851,6 +979,12 @@ int launch_pointwise(const slfp_conv2d_desc& d, const ConvPlan& plan, const floa
             if (const EncArgs* t = act_table(d.ka, plan.fmt_act, kEncF16LO)) p.enc_lo = enc_compact(*t);
             else p.enc.valid = 0;
         }
+    }
+    if (yc) {   // the consumer's code table in the slot the single-pass forms leave unused
+        const EncArgs* t = enc_table(y_ka, y_fmt, kEncCode);
+        if (plan.passes != 1 || !p.enc.valid || !t->valid || !enc_compact_covers(*t))
+            return fail(SLFP_ERR_UNSUPPORTED, "pointwise: no code table for the consumer's scale %g in the single-pass table form", (double)y_ka);
+        p.enc_lo = enc_compact(*t);
     }
     p.s1 = plan.s1; p.s2 = plan.s2; p.s1x = plan.s1 * (1.0f / 256.0f);
     {   // staged stores always carry the nt hint: a size threshold as in conv_dw2.hip (plain stores for outputs that fit the

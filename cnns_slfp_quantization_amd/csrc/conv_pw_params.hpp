@@ -31,11 +31,17 @@ struct PwParams {
     const float* res;     // RES kernels: the residual operand, NHWC like y (y = relu?(affine(conv) + res)); nullptr otherwise
     PostOp post;
     EncArgs enc;          // threshold table of fp16(16 * QA(x / Ka)) (TAB kernels; slfp_enc.hpp)
-    EncArgsCompact enc_lo;   // three-pass TAB kernels: the residual plane's table (kEncF16LO) of the same scale
+    EncArgsCompact enc_lo;   // three-pass TAB kernels: the residual plane's table (kEncF16LO) of the same scale;
+                             // YC kernels (single-pass): the code table of the consumer's Ka (kEncCode), same compact form
 #ifdef SLFP_PW_STAMPS
     unsigned long long* dbg;   // diagnostic builds only (profiles/stamps_tiled.py): 16 x s_memrealtime per workgroup
 #endif
+    int sgn;              // YC: no ReLU in front of the output quantizer: codes carry a sign
+    int fmt_out;          // YC: format of the output codes (kFmtAct8 | kFmtSfp7)
+    uint8_t* yc;          // YC kernels (slfp_conv2d_fwd_entry): the uint8 code tensor, NHWC, C_out bytes per pixel; nullptr otherwise
 };
+// passed by value: the kernel-argument segment holds 4 KiB.  A second full EncArgs (2 KiB) would not fit next to `enc`.
+static_assert(sizeof(PwParams) <= 4096, "PwParams must fit the 4 KiB kernel-argument segment");
 
 #ifdef SLFP_PW_STAMPS
 #define SLFP_STAMP(i) do { if (p.dbg && threadIdx.x == 0) p.dbg[(size_t)blockIdx.x * 16 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)

@@ -70,6 +70,19 @@ inline EncArgsCompact enc_compact(const EncArgs& a) {
     return c;
 }
 
+// Does the compact form hold everything build() populated?  (bins 50..159 must be the untouched {kEncNever, 0} and the clamp
+// range must be the one the compact bins cover.)  Callers that carry a table in compact form refuse the layer otherwise.
+inline bool enc_compact_covers(const EncArgs& a) {
+    uint32_t lb, hb;
+    __builtin_memcpy(&lb, &a.lo, 4);
+    __builtin_memcpy(&hb, &a.hi, 4);
+    const uint32_t bl = (lb >> 19) & 0xFFu, bh = (hb >> 19) & 0xFFu;   // first and last bin a clamped quotient can index
+    if (bl < 160u || bh > 48u) return false;                            // (the successor of the last bin, bh + 1, is read too)
+    for (int i = 50; i < 160; ++i)
+        if (a.e[i].x != kEncNever || a.e[i].y != 0u) return false;
+    return a.e[256].x == a.e[0].x && a.e[256].y == a.e[0].y;
+}
+
 template <int NT>
 __device__ __forceinline__ void enc_fill_compact(uint2* sTab, const EncArgsCompact& a) {
     for (int i = threadIdx.x; i < kEncCompact; i += NT) sTab[i < 96 ? 160 + i : i - 96] = a.e[i];

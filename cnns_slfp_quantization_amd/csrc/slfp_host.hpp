@@ -142,6 +142,11 @@ struct CodeIo {
 int resident_blocks_per_cu(const void* fn, int block_threads, size_t dynamic_lds);
 // Number of compute units of the current device (cached per device; 256 on MI355X): persistent grids are sized from it.
 int device_cu_count();
+// pointwise, float32 in -> codes out (conv_pw.hip's YC forms; slfp_conv2d_fwd_entry): the layer at which a chain of codes begins.
+// Single-pass table forms, C_out a multiple of 16, C_in a multiple of 4, no channel re-padding, no layer-output quantizer.
+bool pointwise_entry_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, int post_flags, float y_ka, int y_fmt);
+int launch_pointwise_entry(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const void* wfrag, const float* bias,
+                           const PostOp& post, void* y_codes, const CodeIo& io, hipStream_t stream);
 // pointwise on codes (conv_pw_codes.hpp): codes in, codes or float32 out; the SAME prepared blob as launch_pointwise
 bool pwc_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, int post_flags, bool y_codes);
 int launch_pwc(const slfp_conv2d_desc& d, const ConvPlan& p, const uint8_t* x, const void* wfrag, const float* bias,

@@ -331,6 +331,15 @@ def _codes_kernel_exists(m, shape, x_codes, out, flags):
     return bool(_lib.load().slfp_conv2d_codes_supported(ctypes.byref(d), ctypes.byref(io), 1 if m.bias is not None else 0, flags))
 
 
+def _entry_kernel_exists(m, shape, out, flags):
+    """Does libslfp_hip run Conv2d_Q `m` on a float32 channels_last input of `shape` with codes out for the layer `out` = (Ka,
+    q_bit) describes, in ONE launch (slfp_conv2d_fwd_entry: the 1x1 layer at which a chain of codes begins)?"""
+    from . import _lib
+    from .conv2d_func import _conv_desc, _conv_io
+    d, io = _conv_desc(m, shape), _conv_io(False, out)
+    return bool(_lib.load().slfp_conv2d_entry_supported(ctypes.byref(d), ctypes.byref(io), 1 if m.bias is not None else 0, flags))
+
+
 def link_codes(model, example_input=None):
     """After fuse_bn_relu: wherever a Conv2d_Q's (fused BN + ReLU) output feeds the next Conv2d_Q of an nn.Sequential
     directly (only nn.Identity in between -- nets_imgnet/mobilenetv1.py:24-33 after fusion), link the two: the producer's
@@ -416,7 +425,7 @@ def link_codes(model, example_input=None):
     return n_links
 
 
-def link_codes_traced(model, example_input):
+def link_codes_traced(model, example_input, entries=False):
     """link_codes for blocks that wire their layers by hand in forward() (the reference's ResNet-50 Bottleneck,
     nets_imgnet/resnet50.py:74-100: conv1 -> bn1 -> relu -> conv2 -> bn2 -> relu -> conv3 -> bn3 -> (+ identity) -> relu, with ONE
     shared nn.ReLU).  One forward records the tensors: a Conv2d_Q `b` whose input IS the output of a Conv2d_Q `a` -- directly or
@@ -425,7 +434,11 @@ def link_codes_traced(model, example_input):
     codes.  Links are made only where libslfp_hip has both kernels (slfp_conv2d_codes_supported), never for a producer with
     two consumers, and the whole set is VERIFIED: the linked model must reproduce the unlinked output bit for bit on
     `example_input`, otherwise (a functional use of the tensor that hooks cannot see, e.g. a torch.cat) everything is rolled
-    back and 0 is returned.  Inference only; unlink_codes undoes it.  Returns the number of links."""
+    back and 0 is returned.  Inference only; unlink_codes undoes it.  Returns the number of links.
+    entries=True: a producer `a` that reads float32 and has no kernel under slfp_conv2d_codes_supported is accepted as well where
+    slfp_conv2d_entry_supported says yes (a 1x1 layer: conv1 of every Bottleneck, which reads the float32 trunk); it gets
+    `_code_entry = True` and runs slfp_conv2d_fwd_entry.  Everything else -- one consumer only, ReLU folding, pools, verification,
+    roll-back -- is the same; the default keeps every link count what it was."""
     from .conv2d_func import _scalar_scale
     conv_io, relu_io, pool_io, order, keep = {}, [], [], [], []
     hooks = []
@@ -501,9 +514,16 @@ def link_codes_traced(model, example_input):
         out = (float(_scalar_scale(b.Ka, "Ka")), int(b.q_bit))
         bflags = int(b._post[2]) if b._post is not None else 0
         a_in = a in reads_codes or conv_io[a][0].dtype == torch.uint8   # does `a` itself read codes (an earlier link)?
-        if not supported(a, a_in, out, flags) or not supported(b, True, b._code_out, bflags):
+        entry = False
+        if not supported(a, a_in, out, flags):
+            entry = (entries and not a_in and conv_io[a][0].dim() == 4
+                     and _entry_kernel_exists(a, conv_io[a][0].shape, out, flags))
+            if not entry:
+                continue
+        if not supported(b, True, b._code_out, bflags):
             continue
         made.append((a, a._post))
+        a._code_entry = entry
         a._post = ((a._post[0], a._post[1]) if a._post is not None else (None, None)) + (flags,)
         a._code_out = out
         a._pre_link_post = made[-1][1]
@@ -525,7 +545,7 @@ def link_codes_traced(model, example_input):
         ok = False
     if not ok:
         for a, post in made:
-            a._post, a._code_out = post, None
+            a._post, a._code_out, a._code_entry = post, None, False
             del a._pre_link_post
         for parent, name, pm in wrapped:
             parent._modules[name] = pm
@@ -543,6 +563,7 @@ def unlink_codes(model):
     for m in model.modules():
         if _is_conv_q(m) and m._code_out is not None:
             m._code_out = None
+            m._code_entry = False
             if hasattr(m, "_pre_link_post"):
                 m._post = m._pre_link_post
                 del m._pre_link_post
@@ -676,10 +697,11 @@ def _fire_forward(self, x):
         raise RuntimeError("fuse_fire: a rewritten Fire module is inference-only; call fusion.unfuse_fire(model) to train")
     sq, e1, e3 = self.squeeze, self.expand1x1, self.expand3x3
     with torch.no_grad():
-        if x.dtype != torch.uint8:   # head of the chain (the pooled float32 stem output): one slfp_encode_f32 pass
+        if x.dtype != torch.uint8:   # head of the chain (the pooled float32 stem output)
             if not x.is_contiguous(memory_format=torch.channels_last):
                 x = x.contiguous(memory_format=torch.channels_last)
-            x = hip_encode(x, _f32(sq.Ka), _act_fmt(sq.q_bit))
+            if not sq._code_entry:   # one slfp_encode_f32 pass; with _code_entry `squeeze` reads the float32 tensor itself
+                x = hip_encode(x, _f32(sq.Ka), _act_fmt(sq.q_bit))
         h = sq(x)
         buf = torch.empty((h.shape[0], e1.out_channels + e3.out_channels, h.shape[2], h.shape[3]), dtype=torch.uint8,
                           device=h.device, memory_format=torch.channels_last)
@@ -712,13 +734,13 @@ def _restore_fire(blk):
     st = blk.__dict__.pop("_fire_fused")
     del blk.__dict__["forward"]
     for conv, post in st["posts"]:
-        conv._post, conv._code_out = post, None
+        conv._post, conv._code_out, conv._code_entry = post, None, False
     for parent, name, pool in st["pools"]:
         if isinstance(parent._modules.get(name), CodeMaxPool2d) and parent._modules[name].pool is pool:
             parent._modules[name] = pool
 
 
-def fuse_fire(model, example_input):
+def fuse_fire(model, example_input, entries=False):
     """SqueezeNet's Fire modules (nets_imgnet/squeezenet1_0.py:20-46; any non-Sequential block with the six children squeeze /
     squeeze_activation / expand1x1 / expand1x1_activation / expand3x3 / expand3x3_activation, Conv2d_Q and nn.ReLU) on 1-byte
     codes: the block gets an instance-level forward in which the three ReLUs are folded into the conv epilogues, `squeeze` writes
@@ -733,7 +755,10 @@ def fuse_fire(model, example_input):
     that do not are restored one by one.  An exception while verifying is a refusal too, with a warning that names it -- except an
     error status from libslfp_hip itself (_lib.SlfpError), which restores the blocks and is re-raised: a kernel that fails where the
     support queries said yes must not pass as a skipped block.  Inference only; composes with graph.GraphedModule.  Returns the number of blocks
-    rewritten; unfuse_fire undoes it."""
+    rewritten; unfuse_fire undoes it.
+    entries=True: a rewritten block whose input arrives as float32 hands it straight to `squeeze` where libslfp_hip has the
+    float32 -> codes form of that layer (slfp_conv2d_entry_supported; `squeeze._code_entry`): no slfp_encode_f32 pass at the head of
+    the chain.  The verification is the same."""
     import types
     import warnings
     from .conv2d_func import _scalar_scale, _conv_desc, _conv_io, _f32, _act_fmt
@@ -830,6 +855,8 @@ def fuse_fire(model, example_input):
         for c in (sq, e1, e3):
             c._post = ((c._post[0], c._post[1]) if c._post is not None else (None, None)) + (1,)
         sq._code_out, e1._code_out, e3._code_out = out_e, out_n, out_n
+        sq._code_entry = bool(entries and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)
+                              and _entry_kernel_exists(sq, tuple(x.shape), out_e, 1))
         blk.__dict__["_fire_fused"] = st
         blk.__dict__["forward"] = types.MethodType(_fire_forward, blk)
         ok = False

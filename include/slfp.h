@@ -214,6 +214,23 @@ int slfp_conv2d_codes_slice_supported(const slfp_conv2d_desc* d, const slfp_conv
 int slfp_conv2d_fwd_codes_slice(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
                                 const float* bias, const float* post_scale, const float* post_shift, int relu, void* y,
                                 int64_t y_ld, void* workspace, void* stream);
+/* ---- entry: the layer at which a chain of codes begins, for the 1x1 layers of the pw_mfma_* family ------------------------------
+ * slfp_conv2d_fwd_entry reads the float32 tensor x (as slfp_conv2d_fwd_post does) and writes, per output element, the byte
+ *     slfp_encode_f32(y, io->y_ka, fmt(io->y_qbits) | SLFP_FMT_EXT)
+ * of the float32 value y that slfp_conv2d_fwd_post writes for the same d, x, wprep, bias, post_scale, post_shift and relu -- bit
+ * for bit, in ONE launch: conv1 of a ResNet-50 Bottleneck (nets_imgnet/resnet50.py:76-80) reads the float32 trunk and hands conv2
+ * 1-byte codes; the first Fire squeeze of SqueezeNet reads the pooled float32 stem output.  Requires io->x_codes == 0 and
+ * io->y_codes == 1.  wprep: the blob of slfp_conv2d_prepare_weights, unchanged.  y_codes: uint8 NHWC, C_out bytes per pixel.  x,
+ * y_codes, wprep, bias, post_scale and post_shift 16-byte aligned; post_scale / post_shift given together or both NULL.
+ * Supported (slfp_conv2d_entry_supported: 1 / 0, host only): 1x1, groups 1, any stride the float32 interface takes, both layouts
+ * NHWC, C_out a multiple of 16, C_in a multiple of 4, the single-pass operand modes (F16X1 / default, SFP<3,3>), relu 0 or
+ * SLFP_POST_RELU, y_qbits 8 or 7, y_ka > 0 with a code table.  Everything else -- F16X3, NCHW, SLFP_POST_LAYEROUT, other channel
+ * counts, dense / depthwise / stem layers -- returns SLFP_ERR_UNSUPPORTED.  slfp_conv2d_codes_supported and slfp_conv2d_fwd_codes
+ * keep refusing this combination: the two interfaces do not overlap. */
+int slfp_conv2d_entry_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int relu);
+int slfp_conv2d_fwd_entry(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const float* x, const void* wprep,
+                          const float* bias, const float* post_scale, const float* post_shift, int relu,
+                          void* y_codes, void* stream);
 /* ---- residual operand: y = relu?(affine(conv(x)) + res) in ONE launch -------------------------------------------------
  * The tail of every residual block, out = relu(bn3(conv3(h)) + identity) (nets_imgnet/resnet50.py:82-88), for the 1x1
  * stride-1 layers of the pw_mfma_* family.  Per output element, in this order, every step rounded to float32:
