@@ -208,7 +208,7 @@ def _conv_weights(mod, desc, weight, stream, cache, kernel=None, want_weight_q=F
         blob = torch.empty(L.slfp_conv2d_wprep_bytes(ctypes.byref(desc)), dtype=torch.uint8, device=weight.device)
         wq = torch.empty_like(w) if want_weight_q else None
         _lib.check(L.slfp_conv2d_prepare_weights(ctypes.byref(desc), w.data_ptr(), blob.data_ptr(),
-                                                 wq.data_ptr() if wq is not None else None, h))
+                                                 _ptr(wq), h))
         return blob, wq
 
     key = (weight.device, weight.data_ptr(), weight._version, weight.shape, desc.qbits, desc.kw_scale,
@@ -216,22 +216,47 @@ def _conv_weights(mod, desc, weight, stream, cache, kernel=None, want_weight_q=F
     return mod._prep.get(key, stream, cache, make, want_weight_q)
 
 
+# What a forward can be asked for besides the float32 interface (kind None): kind -> (support query, forward entry point).
+_KINDS = {
+    None: (None, "slfp_conv2d_fwd_post"),
+    "codes": ("slfp_conv2d_codes_supported", "slfp_conv2d_fwd_codes_ws"),          # codes on either side
+    "slice": ("slfp_conv2d_codes_slice_supported", "slfp_conv2d_fwd_codes_slice"),  # codes into a channel slice of a wider tensor
+    "entry": ("slfp_conv2d_entry_supported", "slfp_conv2d_fwd_entry"),              # float32 in, codes out, pointwise
+    "res": ("slfp_conv2d_res_supported", "slfp_conv2d_fwd_res"),                    # a residual operand in the epilogue
+}
+
+
+def _ptr(t):
+    """A tensor's address for the C ABI; None (NULL) for an absent one."""
+    return t.data_ptr() if t is not None else None
+
+
+def _supported(mod, shape, kind, x_codes, out, flags, y_ld=None, desc=None, io=None):
+    """Does libslfp_hip run Conv2d_Q `mod` on a channels_last input of `shape` as `kind` (a key of _KINDS): codes in (x_codes) /
+    codes out for the layer `out` = (Ka, q_bit) describes (None: float32 out), `flags` in its epilogue ("res": the ReLU behind the
+    add), "slice": into a `y_ld`-channel tensor?  desc / io: the structs, where the caller has built them already."""
+    d = desc if desc is not None else _conv_desc(mod, shape)
+    io = io if io is not None else _conv_io(x_codes, out)
+    tail = (int(y_ld),) if kind == "slice" else ()
+    query = getattr(_lib.load(), _KINDS[kind][0])
+    return bool(query(ctypes.byref(d), ctypes.byref(io), 1 if mod.bias is not None else 0, int(flags), *tail))
+
+
 class _Plan:
-    """What one (module, input shape, layout, scales, precision) combination resolves to in the C ABI; for the code path
-    also its io struct and whether libslfp_hip has a kernel for the combination."""
-    __slots__ = ("desc", "y_shape", "ws_bytes", "kernel", "io", "codes_ok", "res_ok", "slice_ok", "entry_ok")
+    """What one (module, input shape, layout, scales, precision, kind) combination resolves to in the C ABI; for the kinds of
+    _KINDS also the io struct and whether libslfp_hip has a kernel for the combination (`ok`)."""
+    __slots__ = ("desc", "y_shape", "ws_bytes", "kernel", "kind", "io", "ok", "label")
 
     def __init__(self, desc, y_shape, ws_bytes, kernel):
         self.desc, self.y_shape, self.ws_bytes, self.kernel = desc, y_shape, ws_bytes, kernel
-        self.io, self.codes_ok, self.res_ok, self.slice_ok, self.entry_ok = None, False, False, False, False
+        self.kind, self.io, self.ok, self.label = None, None, True, kernel   # label: what `_last_kernel` reports
 
 
-def _plan(mod, x, weight, nhwc_in, nhwc_out, codes=None, bias=None):
+def _plan(mod, x, weight, nhwc_in, nhwc_out, codes=None):
     """Everything that depends only on (module geometry, input shape, layouts, scales, precision) is computed once per
     distinct key and kept on the module: descriptor, output shape, workspace size, kernel name.  codes: None for the
-    float32 interface, ("codes", does x hold codes, mod._code_out) for slfp_conv2d_fwd_codes, ("res", does x hold codes, ReLU
-    after the add) for slfp_conv2d_fwd_res, ("slice", does x hold codes, mod._code_out, channel count of the wider tensor) for
-    slfp_conv2d_fwd_codes_slice, ("entry", mod._code_out) for slfp_conv2d_fwd_entry (float32 in, codes out)."""
+    float32 interface, else (kind of _KINDS, does x hold codes, mod._code_out or None, extra) with extra = the channel count of the
+    wider tensor for "slice", whether a ReLU follows the add for "res"."""
     shape = x.shape
     key = (codes, shape, nhwc_in, nhwc_out, _scale_key(mod.Ka, "Ka"), _scale_key(mod.Kw, "Kw"), options.mfma_passes,
            mod.stride, mod.padding, mod.dilation, weight.shape)
@@ -246,30 +271,19 @@ def _plan(mod, x, weight, nhwc_in, nhwc_out, codes=None, bias=None):
         _lib.check(L.slfp_conv2d_out_shape(ctypes.byref(d), ctypes.byref(ho), ctypes.byref(wo)))
         plan = _Plan(d, (d.n, d.c_out, ho.value, wo.value), L.slfp_conv2d_workspace_bytes(ctypes.byref(d)),
                      L.slfp_conv2d_kernel_name(ctypes.byref(d)).decode())
-        if codes is not None and codes[0] == "res":
-            plan.io = _conv_io(codes[1], None)
+        if codes is not None:
+            kind, x_codes, out, extra = codes
             flags = int(mod._post[2]) if mod._post is not None else 0
-            # an epilogue ReLU or layer-output quantizer would sit BEFORE the add: not what the residual kernels compute
-            plan.res_ok = flags == 0 and bool(L.slfp_conv2d_res_supported(ctypes.byref(d), ctypes.byref(plan.io),
-                                                                          1 if bias is not None else 0, 1 if codes[2] else 0))
-        elif codes is not None and codes[0] == "slice":
-            plan.io = _conv_io(codes[1], codes[2])
-            flags = int(mod._post[2]) if mod._post is not None else 0
-            plan.slice_ok = bool(L.slfp_conv2d_codes_slice_supported(ctypes.byref(d), ctypes.byref(plan.io),
-                                                                     1 if bias is not None else 0, flags, int(codes[3])))
-        elif codes is not None and codes[0] == "entry":
-            plan.io = _conv_io(False, codes[1])
-            flags = int(mod._post[2]) if mod._post is not None else 0
-            plan.entry_ok = bool(L.slfp_conv2d_entry_supported(ctypes.byref(d), ctypes.byref(plan.io),
-                                                               1 if bias is not None else 0, flags))
-            plan.ws_bytes = 0   # the pointwise family needs no workspace
-        elif codes is not None:
-            plan.io = _conv_io(codes[1], codes[2])
-            flags = int(mod._post[2]) if mod._post is not None else 0
-            plan.codes_ok = bool(L.slfp_conv2d_codes_supported(ctypes.byref(d), ctypes.byref(plan.io),
-                                                               1 if bias is not None else 0, flags))
-            if not plan.codes_ok:   # the layer goes through the float32 interface, whose own plan sizes its workspace
-                plan.ws_bytes = 0
+            plan.kind, plan.io = kind, _conv_io(x_codes, out)
+            if kind == "res":
+                # an epilogue ReLU or layer-output quantizer would sit BEFORE the add: not what the residual kernels compute
+                plan.ok = flags == 0 and _supported(mod, shape, kind, x_codes, None, 1 if extra else 0, desc=d, io=plan.io)
+            else:
+                plan.ok = _supported(mod, shape, kind, x_codes, out, flags, extra, d, plan.io)
+            if kind == "entry" or (kind == "codes" and not plan.ok):
+                plan.ws_bytes = 0   # pointwise: no workspace; refused: the float32 interface's own plan sizes its workspace
+            plan.label += (("+codes_in" if x_codes else "") + ("+codes_out" if out is not None else "")
+                           + {"slice": "+slice", "res": "+res"}.get(kind, ""))
         if len(mod._plans) >= 64:   # a net fed ever-changing shapes: do not grow without bound
             mod._plans.clear()
         mod._plans[key] = plan
@@ -316,6 +330,42 @@ def _workspace(device, nbytes):
     return buf
 
 
+def _launch(mod, plan, x, weight, bias, y=None, cache=True, res=None, relu=None, y_ld=None):
+    """The one call into libslfp_hip of a Conv2d_Q forward: plan.kind's entry point (_KINDS) on input `x`.  y: the output tensor --
+    allocated here (channels_last; uint8 where the plan's io writes codes) when None -- or, for "slice", the address of the
+    slice's first channel in a y_ld-channel tensor; "res": + `res`, with `relu` behind the add.  Does the device guard, the
+    stream, the module's weight blob (cache: it may come from the module's cache), the epilogue arguments and the workspace, then
+    the module's bookkeeping: `_last_kernel`, exactly one of `_last_input` / `_last_codes`, and `_input_q` (stored by the float32
+    interface under options.eager_stash, otherwise made on first read).  Returns y."""
+    kind, d = plan.kind, plan.desc
+    stash = kind is None and options.eager_stash
+    with _on_device(x.device):
+        stream = torch.cuda.current_stream(x.device)
+        # cache the prepared weights only where they cannot change unseen: inference (see the module docstring)
+        blob = _conv_weights(mod, d, weight, stream, cache, plan.kernel, want_weight_q=stash)
+        if y is None:
+            y = torch.empty(plan.y_shape, dtype=torch.uint8 if plan.io.y_codes else torch.float32, device=x.device,
+                            memory_format=torch.channels_last)
+        ws = _workspace(x.device, plan.ws_bytes) if plan.ws_bytes else None
+        b, ps, psh, flags = _epilogue_args(mod, bias, x.device)
+        xq = torch.empty_like(x) if stash else None
+        head = (x.data_ptr(), blob.data_ptr(), _ptr(b), _ptr(ps), _ptr(psh))
+        if kind is None:
+            args = (ctypes.byref(d),) + head + (flags, y.data_ptr(), _ptr(xq), _ptr(ws))
+        elif kind == "slice":
+            args = (ctypes.byref(d), ctypes.byref(plan.io)) + head + (flags, y, y_ld, _ptr(ws))
+        elif kind == "res":
+            args = (ctypes.byref(d), ctypes.byref(plan.io)) + head + (1 if relu else 0, res.data_ptr(), y.data_ptr(), None)
+        else:   # "codes" takes a workspace, "entry" does not
+            args = (ctypes.byref(d), ctypes.byref(plan.io)) + head + (flags, y.data_ptr()) + ((_ptr(ws),) if kind == "codes" else ())
+        _lib.check(getattr(_lib.load(), _KINDS[kind][1])(*args, stream.cuda_stream))
+    x_codes = x.dtype == torch.uint8
+    # plain attributes, written in one go (nn.Module.__setattr__ costs microseconds per name, on every layer of every forward)
+    mod.__dict__.update(_last_kernel=plan.label, _last_input=None if x_codes else x.detach(),
+                        _last_codes=x.detach() if x_codes else None, _input_q=xq)
+    return y
+
+
 def _hip_conv2d(mod, x, weight, bias, cache_ok=False):
     """One slfp_conv2d_fwd call for module `mod` (an nn.Conv2d subclass below).  cache_ok: the prepared weights may
     come from the module's cache (decided by the caller: grad mode is off inside autograd.Function.forward)."""
@@ -327,31 +377,14 @@ def _hip_conv2d(mod, x, weight, bias, cache_ok=False):
         x = x.unsqueeze(0)
     if x.dim() != 4:
         raise RuntimeError(f"Expected 3D (unbatched) or 4D (batched) input to conv2d, but got input of size: {list(x.shape)}")
-    L = _lib.load()
     nhwc_in = x.is_contiguous(memory_format=torch.channels_last)
     if not nhwc_in and not x.is_contiguous():
         x = x.contiguous()
     nhwc_out = nhwc_in or options.output_layout == "nhwc"
     plan = _plan(mod, x, weight, nhwc_in, nhwc_out)
-    d = plan.desc
-    with _on_device(x.device):
-        stream = torch.cuda.current_stream(x.device)
-        # cache the prepared weights only where they cannot change unseen: inference (see the module docstring)
-        blob = _conv_weights(mod, d, weight, stream, cache_ok, plan.kernel, want_weight_q=options.eager_stash)
-        y = torch.empty(plan.y_shape, dtype=torch.float32, device=x.device,
-                        memory_format=torch.channels_last if nhwc_out else torch.contiguous_format)
-        ws = _workspace(x.device, plan.ws_bytes) if plan.ws_bytes else None
-        b, ps, psh, flags = _epilogue_args(mod, bias, x.device)
-        xq = torch.empty_like(x) if options.eager_stash else None
-        _lib.check(L.slfp_conv2d_fwd_post(ctypes.byref(d), x.data_ptr(), blob.data_ptr(),
-                                          b.data_ptr() if b is not None else None,
-                                          ps.data_ptr() if ps is not None else None,
-                                          psh.data_ptr() if psh is not None else None, flags, y.data_ptr(),
-                                          xq.data_ptr() if xq is not None else None,
-                                          ws.data_ptr() if ws is not None else None, stream.cuda_stream))
-    mod._last_kernel = plan.kernel
-    mod._last_input = x.detach()
-    mod._input_q = xq
+    y = torch.empty(plan.y_shape, dtype=torch.float32, device=x.device,
+                    memory_format=torch.channels_last if nhwc_out else torch.contiguous_format)
+    _launch(mod, plan, x, weight, bias, y, cache=cache_ok)
     return y.squeeze(0) if squeeze else y
 
 
@@ -368,56 +401,17 @@ def _hip_conv2d_codes(mod, x, weight, bias):
         _require_gpu_f32(x, "Conv2d_Q")
     elif not x.is_cuda:
         raise RuntimeError("Conv2d_Q: code tensors live on the ROCm device")
-
-    def float32_interface():
-        y = _hip_conv2d(mod, hip_decode(x, _act_fmt(mod.q_bit)) if x_codes else x, weight, bias, cache_ok=True)
-        return hip_encode(y, out[0], _act_fmt(out[1])) if out is not None else y
-
-    if x.dim() != 4 or not x.is_contiguous(memory_format=torch.channels_last):
-        return float32_interface()   # the code path is NHWC only; anything else takes the float32 interface
-    if not x_codes and out is not None and mod._code_entry:
-        plan = _plan(mod, x, weight, True, True, ("entry", out), bias)
-        if plan.entry_ok:
-            L = _lib.load()
-            d = plan.desc
-            with _on_device(x.device):
-                stream = torch.cuda.current_stream(x.device)
-                blob = _conv_weights(mod, d, weight, stream, True, plan.kernel)
-                y = torch.empty(plan.y_shape, dtype=torch.uint8, device=x.device, memory_format=torch.channels_last)
-                b, ps, psh, flags = _epilogue_args(mod, bias, x.device)
-                _lib.check(L.slfp_conv2d_fwd_entry(ctypes.byref(d), ctypes.byref(plan.io), x.data_ptr(), blob.data_ptr(),
-                                                   b.data_ptr() if b is not None else None,
-                                                   ps.data_ptr() if ps is not None else None,
-                                                   psh.data_ptr() if psh is not None else None, flags, y.data_ptr(),
-                                                   stream.cuda_stream))
-            mod._last_kernel = plan.kernel + "+codes_out"
-            mod._last_input, mod._last_codes = x.detach(), None
-            mod._input_q = None
-            return y
-    plan = _plan(mod, x, weight, True, True, ("codes", x_codes, out), bias)
-    if not plan.codes_ok:
-        return float32_interface()
-    L = _lib.load()
-    d = plan.desc
-    with _on_device(x.device):
-        stream = torch.cuda.current_stream(x.device)
-        blob = _conv_weights(mod, d, weight, stream, True, plan.kernel)
-        y = torch.empty(plan.y_shape, dtype=torch.uint8 if out is not None else torch.float32, device=x.device,
-                        memory_format=torch.channels_last)
-        b, ps, psh, flags = _epilogue_args(mod, bias, x.device)
-        ws = _workspace(x.device, plan.ws_bytes) if plan.ws_bytes else None   # dense k x k layers: the fp16 operand copy
-        _lib.check(L.slfp_conv2d_fwd_codes_ws(ctypes.byref(d), ctypes.byref(plan.io), x.data_ptr(), blob.data_ptr(),
-                                              b.data_ptr() if b is not None else None,
-                                              ps.data_ptr() if ps is not None else None,
-                                              psh.data_ptr() if psh is not None else None, flags, y.data_ptr(),
-                                              ws.data_ptr() if ws is not None else None, stream.cuda_stream))
-    mod._last_kernel = plan.kernel + ("+codes_in" if x_codes else "") + ("+codes_out" if out is not None else "")
-    if x_codes:
-        mod._last_input, mod._last_codes = None, x.detach()
-    else:
-        mod._last_input, mod._last_codes = x.detach(), None
-    mod._input_q = None
-    return y
+    if x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last):   # the code path is NHWC only
+        if not x_codes and out is not None and mod._code_entry:
+            plan = _plan(mod, x, weight, True, True, ("entry", False, out, None))
+            if plan.ok:
+                return _launch(mod, plan, x, weight, bias)
+        plan = _plan(mod, x, weight, True, True, ("codes", x_codes, out, None))
+        if plan.ok:
+            return _launch(mod, plan, x, weight, bias)
+    # anything else takes the float32 interface
+    y = _hip_conv2d(mod, hip_decode(x, _act_fmt(mod.q_bit)) if x_codes else x, weight, bias, cache_ok=True)
+    return hip_encode(y, out[0], _act_fmt(out[1])) if out is not None else y
 
 
 def _hip_conv2d_slice(mod, x, weight, bias, out_slice):
@@ -439,32 +433,15 @@ def _hip_conv2d_slice(mod, x, weight, bias, out_slice):
             and buf.is_contiguous(memory_format=nhwc)):
         raise RuntimeError("Conv2d_Q: out_slice's buffer must be a 4-d uint8 channels_last tensor on the input's device")
     ld = buf.shape[1]
-    plan = _plan(mod, x, weight, True, True, ("slice", x_codes, mod._code_out, ld), bias)
+    plan = _plan(mod, x, weight, True, True, ("slice", x_codes, mod._code_out, ld))
     n, c_out, ho, wo = plan.y_shape
     if (buf.shape[0], buf.shape[2], buf.shape[3]) != (n, ho, wo) or c_off < 0 or c_off + c_out > ld:
         raise RuntimeError(f"Conv2d_Q: out_slice channels [{c_off}, {c_off + c_out}) of a buffer of shape {list(buf.shape)} do not "
                            f"hold this layer's output {list(plan.y_shape)}")
-    if not plan.slice_ok or c_off % 16 or buf.data_ptr() % 16:
+    if not plan.ok or c_off % 16 or buf.data_ptr() % 16:
         raise RuntimeError(f"Conv2d_Q: no kernel writes this layer's codes into channels {c_off}.. of a {ld}-channel tensor "
                            "(slfp_conv2d_codes_slice_supported; offset and width are multiples of 16)")
-    L = _lib.load()
-    d = plan.desc
-    with _on_device(x.device):
-        stream = torch.cuda.current_stream(x.device)
-        blob = _conv_weights(mod, d, weight, stream, True, plan.kernel)
-        b, ps, psh, flags = _epilogue_args(mod, bias, x.device)
-        ws = _workspace(x.device, plan.ws_bytes) if plan.ws_bytes else None
-        _lib.check(L.slfp_conv2d_fwd_codes_slice(ctypes.byref(d), ctypes.byref(plan.io), x.data_ptr(), blob.data_ptr(),
-                                                 b.data_ptr() if b is not None else None,
-                                                 ps.data_ptr() if ps is not None else None,
-                                                 psh.data_ptr() if psh is not None else None, flags, buf.data_ptr() + c_off, ld,
-                                                 ws.data_ptr() if ws is not None else None, stream.cuda_stream))
-    mod._last_kernel = plan.kernel + ("+codes_in" if x_codes else "") + "+codes_out+slice"
-    if x_codes:
-        mod._last_input, mod._last_codes = None, x.detach()
-    else:
-        mod._last_input, mod._last_codes = x.detach(), None
-    mod._input_q = None
+    _launch(mod, plan, x, weight, bias, buf.data_ptr() + c_off, y_ld=ld)
     return buf
 
 
@@ -478,32 +455,14 @@ def _hip_conv2d_res(mod, x, weight, bias, residual, relu):
     if not (x.is_cuda and x.dim() == 4 and (x_codes or x.dtype == torch.float32) and x.is_contiguous(memory_format=nhwc)
             and weight.device == x.device):
         return None
-    plan = _plan(mod, x, weight, True, True, ("res", x_codes, bool(relu)), bias)
-    if not plan.res_ok:
+    plan = _plan(mod, x, weight, True, True, ("res", x_codes, None, bool(relu)))
+    if not plan.ok:
         return None
     r = residual
     if not (torch.is_tensor(r) and r.dtype == torch.float32 and r.device == x.device and tuple(r.shape) == tuple(plan.y_shape)
             and r.is_contiguous(memory_format=nhwc) and r.data_ptr() % 16 == 0):
         return None
-    L = _lib.load()
-    d = plan.desc
-    with _on_device(x.device):
-        stream = torch.cuda.current_stream(x.device)
-        blob = _conv_weights(mod, d, weight, stream, True, plan.kernel)   # the same blob (and cache entry) as the other paths
-        y = torch.empty(plan.y_shape, dtype=torch.float32, device=x.device, memory_format=nhwc)
-        b, ps, psh, _ = _epilogue_args(mod, bias, x.device)
-        _lib.check(L.slfp_conv2d_fwd_res(ctypes.byref(d), ctypes.byref(plan.io), x.data_ptr(), blob.data_ptr(),
-                                         b.data_ptr() if b is not None else None,
-                                         ps.data_ptr() if ps is not None else None,
-                                         psh.data_ptr() if psh is not None else None, 1 if relu else 0,
-                                         r.data_ptr(), y.data_ptr(), None, stream.cuda_stream))
-    mod._last_kernel = plan.kernel + ("+codes_in" if x_codes else "") + "+res"
-    if x_codes:
-        mod._last_input, mod._last_codes = None, x.detach()
-    else:
-        mod._last_input, mod._last_codes = x.detach(), None
-    mod._input_q = None
-    return y
+    return _launch(mod, plan, x, weight, bias, res=r, relu=relu)   # the same blob (and cache entry) as the other paths
 
 
 def _aligned(t):
@@ -531,10 +490,8 @@ def _hip_backward(mod, desc, x, w, gy, needs):
     with _on_device(x.device):
         nbytes = L.slfp_conv2d_bwd_workspace_bytes_ex(ctypes.byref(desc), flags, int(need_gx), int(run_gw))
         ws = _workspace(x.device, nbytes) if nbytes else None
-        _lib.check(L.slfp_conv2d_bwd_ex(ctypes.byref(desc), flags, x.data_ptr(), w.data_ptr(), gy.data_ptr(),
-                                        gx.data_ptr() if gx is not None else None, gw.data_ptr() if gw is not None else None,
-                                        gb.data_ptr() if gb is not None else None, ws.data_ptr() if ws is not None else None,
-                                        _stream_handle(x)))
+        _lib.check(L.slfp_conv2d_bwd_ex(ctypes.byref(desc), flags, x.data_ptr(), w.data_ptr(), gy.data_ptr(), _ptr(gx), _ptr(gw),
+                                        _ptr(gb), _ptr(ws), _stream_handle(x)))
     mod._last_bwd_kernel = L.slfp_conv2d_bwd_kernel_name_ex(ctypes.byref(desc), flags).decode()
     return gx, gw if need_gw else None, gb
 
@@ -820,8 +777,8 @@ def _hip_linear(mod, x, weight, bias, cache_ok=False):
         key = (w.device, w.data_ptr(), weight._version, tuple(w.shape), mod.q_bit, kw, options.mfma_passes)
         stream = torch.cuda.current_stream(x.device)
         blob = mod._prep.get(key, stream, cache_ok, make)
-        _lib.check(L.slfp_linear_fwd_prepared(x2.data_ptr(), blob.data_ptr(), b.data_ptr() if b is not None else None,
-                                              y.data_ptr(), B, I, O, ka, kw, mod.q_bit, options.mfma_passes, stream.cuda_stream))
+        _lib.check(L.slfp_linear_fwd_prepared(x2.data_ptr(), blob.data_ptr(), _ptr(b), y.data_ptr(), B, I, O, ka, kw, mod.q_bit,
+                                              options.mfma_passes, stream.cuda_stream))
     return y.reshape(*lead, O)
 
 

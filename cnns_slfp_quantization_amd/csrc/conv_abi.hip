@@ -282,45 +282,215 @@ size_t slfp_conv2d_wprep_bytes(const slfp_conv2d_desc* d) {
     return p.wprep_bytes;
 }
 
-int slfp_conv2d_prepare_weights(const slfp_conv2d_desc* d, const float* w_oihw, void* wprep, float* weight_q_oihw,
-                                void* stream) {
+static int prepare_weights(const char* fn, const slfp_conv2d_desc* d, const void* w, void* wprep, float* weight_q_oihw, void* stream,
+                           bool codes) {
     ConvPlan p;
     const int rc = make_plan(d, &p);
     if (rc != SLFP_OK) return rc;
-    if (!w_oihw || !wprep) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_prepare_weights: null pointer");
-    if (!aligned16(wprep)) return fail(SLFP_ERR_ALIGNMENT, "slfp_conv2d_prepare_weights: wprep must be 16-byte aligned");
-    return launch_prepare_weights(*d, p, w_oihw, wprep, weight_q_oihw, as_stream(stream));
+    if (!w || !wprep) return fail(SLFP_ERR_BAD_ARG, "%s: null pointer", fn);
+    if (!aligned16(wprep)) return fail(SLFP_ERR_ALIGNMENT, "%s: wprep must be 16-byte aligned", fn);
+    return launch_prepare_weights(*d, p, reinterpret_cast<const float*>(w), wprep, weight_q_oihw, as_stream(stream), codes);
+}
+
+int slfp_conv2d_prepare_weights(const slfp_conv2d_desc* d, const float* w_oihw, void* wprep, float* weight_q_oihw,
+                                void* stream) {
+    return prepare_weights("slfp_conv2d_prepare_weights", d, w_oihw, wprep, weight_q_oihw, stream, false);
 }
 
 int slfp_conv2d_prepare_weights_codes(const slfp_conv2d_desc* d, const uint8_t* codes_oihw, void* wprep, float* weight_q_oihw,
                                       void* stream) {
-    ConvPlan p;
-    const int rc = make_plan(d, &p);
-    if (rc != SLFP_OK) return rc;
-    if (!codes_oihw || !wprep) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_prepare_weights_codes: null pointer");
-    if (!aligned16(wprep)) return fail(SLFP_ERR_ALIGNMENT, "slfp_conv2d_prepare_weights_codes: wprep must be 16-byte aligned");
-    return launch_prepare_weights(*d, p, reinterpret_cast<const float*>(codes_oihw), wprep, weight_q_oihw, as_stream(stream), true);
+    return prepare_weights("slfp_conv2d_prepare_weights_codes", d, codes_oihw, wprep, weight_q_oihw, stream, true);
 }
 
-static size_t workspace_bytes_for(const slfp_conv2d_desc* d, const ConvPlan& p) {
-    size_t b = 0;
-    if (d->x_layout == SLFP_LAYOUT_NCHW) b += round256((size_t)d->n * d->c_in * d->h * d->w * sizeof(float));
-    if (d->y_layout == SLFP_LAYOUT_NCHW) b += round256((size_t)d->n * d->c_out * p.h_out * p.w_out * sizeof(float));
-    if (p.family == kDenseMfma) b += dense_mfma_workspace_bytes(*d, p.passes);  // the input encoded once to fp16
-    if (p.family == kStemMfma) b += stem_mfma_workspace_bytes(*d, p.w_out);
-    if (p.repad) {
-        if (p.cpi != d->c_in) b += round256((size_t)d->n * d->h * d->w * p.cpi * sizeof(float));
-        if (p.cpo != d->c_out) b += round256((size_t)d->n * p.h_out * p.w_out * p.cpo * sizeof(float));
-        b += 3 * round256((size_t)p.cpo * sizeof(float));  // bias / post_scale / post_shift, padded
-    }
-    return b;
+}  // extern "C"
+
+// Where each part of the workspace lies: byte offsets in this order, the copies rounded up to 256 bytes; a part the call does
+// not need takes no room.  slfp_conv2d_workspace_bytes reports `total`, the forward carves the buffer by the same offsets.
+struct WsLayout {
+    size_t x_nhwc, y_nhwc;   // NCHW <-> NHWC copies of x and y
+    size_t operand;          // dense k x k: the input encoded once to fp16; large-kernel stem: the im2row'ed input
+    size_t x_pad, y_pad;     // channel-padded copies (ConvPlan::repad)
+    size_t vec[3];           // bias / post_scale / post_shift, padded (read 16 bytes at a time)
+    size_t total;
+};
+
+static WsLayout ws_layout(const slfp_conv2d_desc* d, const ConvPlan& p) {
+    WsLayout l;
+    size_t at = 0;
+    auto take = [&at](bool needed, size_t bytes) { const size_t off = at; if (needed) at += bytes; return off; };
+    l.x_nhwc = take(d->x_layout == SLFP_LAYOUT_NCHW, round256((size_t)d->n * d->c_in * d->h * d->w * sizeof(float)));
+    l.y_nhwc = take(d->y_layout == SLFP_LAYOUT_NCHW, round256((size_t)d->n * d->c_out * p.h_out * p.w_out * sizeof(float)));
+    l.operand = at;
+    if (p.family == kDenseMfma) at += dense_mfma_workspace_bytes(*d, p.passes);
+    if (p.family == kStemMfma) at += stem_mfma_workspace_bytes(*d, p.w_out);
+    l.x_pad = take(p.repad && p.cpi != d->c_in, round256((size_t)d->n * d->h * d->w * p.cpi * sizeof(float)));
+    l.y_pad = take(p.repad && p.cpo != d->c_out, round256((size_t)d->n * p.h_out * p.w_out * p.cpo * sizeof(float)));
+    for (size_t& v : l.vec) v = take(p.repad, round256((size_t)p.cpo * sizeof(float)));
+    l.total = at;
+    return l;
 }
 
-size_t slfp_conv2d_workspace_bytes(const slfp_conv2d_desc* d) {
+extern "C" size_t slfp_conv2d_workspace_bytes(const slfp_conv2d_desc* d) {
     ConvPlan p;
     if (make_plan(d, &p) != SLFP_OK) return 0;
-    return workspace_bytes_for(d, p);
+    return ws_layout(d, p).total;
 }
+
+// ---- 1-byte activation codes between layers (include/slfp.h; csrc/slfp_codes.hpp) ----
+// The kernel a call with codes on either side goes to.
+enum CodeRoute {
+    kRouteNone = 0,    // no code-path kernel for the layer / io combination
+    kRouteDwc,         // depthwise 3x3 on codes
+    kRoutePwc,         // pointwise on codes
+    kRouteStemCodes,   // the image stem with code output
+    kRouteDense,       // dense k x k (needs the workspace)
+    kRouteStemSmall,   // the small-K MFMA stem with code output
+};
+
+static int y_fmt_of(int y_qbits) { return y_qbits == 7 ? kFmtSfp7 : kFmtAct8; }
+
+// Is the consumer's quantizer in `io` (format and scale of the codes to write) one the kernels can apply?
+static bool consumer_quant_ok(const slfp_conv2d_io* io) {
+    return (io->y_qbits == 8 || io->y_qbits == 7) && io->y_ka > 0.f && scale_div_ok(io->y_ka);
+}
+
+// What all code-path kernels share: NHWC on both sides, known flag bits, no layer-output quantizer, the threshold tables in use.
+static bool code_path_ok(const slfp_conv2d_desc* d, int relu) {
+    if (d->x_layout != SLFP_LAYOUT_NHWC || d->y_layout != SLFP_LAYOUT_NHWC) return false;
+    if ((relu & ~(SLFP_POST_RELU | SLFP_POST_LAYEROUT)) != 0 || (relu & SLFP_POST_LAYEROUT)) return false;
+    return !long_encode_forced();
+}
+
+// The three route functions take the plan make_plan built for `d`.
+static CodeRoute codes_route(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, bool has_bias, int relu, const ConvPlan& p) {
+    if (!code_path_ok(d, relu)) return kRouteNone;
+    if (io->y_codes && (!consumer_quant_ok(io) || !enc_table(io->y_ka, y_fmt_of(io->y_qbits), kEncCode)->valid)) return kRouteNone;
+    if (io->x_codes) {
+        if (dwc_applicable(*d, p, has_bias ? reinterpret_cast<const float*>(1) : nullptr, relu)) return kRouteDwc;
+        if (pwc_applicable(*d, p, relu, io->y_codes != 0)) return kRoutePwc;
+        if (dense_codes_applicable(*d, p, relu, io->y_codes != 0)) return kRouteDense;
+        return kRouteNone;
+    }
+    if (!io->y_codes) return kRouteNone;
+    if (stem_codes_applicable(*d, p, relu)) return kRouteStemCodes;
+    if (dense_codes_applicable(*d, p, relu, true)) return kRouteDense;
+    if (stem_small_codes_applicable(*d, p, relu)) return kRouteStemSmall;
+    return kRouteNone;
+}
+
+// The kernels whose code store takes a pixel stride (a channel slice of a wider tensor): pw_mfma_* on codes, the dense code epilogue.
+static bool slice_route(CodeRoute route) { return route == kRoutePwc || route == kRouteDense; }
+static bool y_ld_ok(const slfp_conv2d_desc* d, int64_t y_ld) { return y_ld >= d->c_out && y_ld % 16 == 0 && y_ld <= 0x7FFFFFFF; }
+
+// Pointwise, float32 in -> codes out: the layer at which a chain of codes begins (slfp_conv2d_fwd_entry).  A query and an entry
+// point of their own: slfp_conv2d_codes_supported keeps answering 0 for this combination, so every link count that rests on it stays.
+static bool entry_route(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int relu, const ConvPlan& p) {
+    if (io->x_codes != 0 || io->y_codes != 1 || !code_path_ok(d, relu) || !consumer_quant_ok(io)) return false;
+    return pointwise_entry_applicable(*d, p, relu, io->y_ka, y_fmt_of(io->y_qbits));
+}
+
+// A residual operand in the pointwise epilogue (slfp_conv2d_fwd_res): float32 out, no layer-output quantizer.
+static bool res_route(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, bool has_bias, int relu, const ConvPlan& p) {
+    if ((relu & ~SLFP_POST_RELU) != 0 || io->y_codes || !code_path_ok(d, relu)) return false;
+    if (!io->x_codes) return pointwise_res_applicable(*d, p);
+    const slfp_conv2d_io cio{1, 0, 1.f, 8};
+    return p.family == kPointwise && d->stride_h == 1 && d->stride_w == 1 && codes_route(d, &cio, has_bias, relu, p) == kRoutePwc;
+}
+
+// ---- the one argument check of the forward entry points ----
+struct FwdArgs {   // what a forward entry point was handed; io / res / y_ld / workspace: null or 0 where it has none
+    const slfp_conv2d_desc* d; const slfp_conv2d_io* io;
+    const void* x; const void* wprep; const float* bias; const float* post_scale; const float* post_shift; int relu;
+    void* y; const float* res; int64_t y_ld; void* workspace;
+};
+enum FwdKind { kFwdPost, kFwdCodes, kFwdSlice, kFwdEntry, kFwdRes };
+struct Resolved { ConvPlan p; PostOp post; CodeIo cio; CodeRoute route; };
+
+static int need_workspace(const char* fn, const FwdArgs& a, const ConvPlan& p) {
+    const size_t ws_need = ws_layout(a.d, p).total;
+    if (ws_need && (!a.workspace || !aligned16(a.workspace)))
+        return fail(SLFP_ERR_BAD_ARG, "%s: %zu bytes of 16-byte aligned workspace required (slfp_conv2d_workspace_bytes)", fn, ws_need);
+    return SLFP_OK;
+}
+
+// Checks everything that precedes device work, in the order that decides which status a call with several defects gets, and
+// resolves the call ONCE: plan, route, PostOp and CodeIo.  Nothing is launched before this returns SLFP_OK.
+static int resolve(FwdKind kind, const char* fn, const FwdArgs& a, Resolved* r) {
+    const slfp_conv2d_desc* d = a.d;
+    const slfp_conv2d_io* io = a.io;
+    if (kind != kFwdPost && (!d || !io)) return fail(SLFP_ERR_BAD_ARG, "%s: null descriptor", fn);
+    const int rc = make_plan(d, &r->p);
+    if (rc != SLFP_OK) return rc;
+    if (!a.x || !a.wprep || !a.y || (kind == kFwdRes && !a.res)) return fail(SLFP_ERR_BAD_ARG, "%s: null pointer", fn);
+    const bool has_bias = a.bias != nullptr;
+    r->route = kRouteNone;
+    if (kind == kFwdSlice) {   // the slice's own arguments come first
+        if (!io->y_codes) return fail(SLFP_ERR_BAD_ARG, "%s: a channel slice is written as codes (io->y_codes == 1)", fn);
+        if (!aligned16(a.y)) return fail(SLFP_ERR_ALIGNMENT, "%s: y (the slice's first channel) must be 16-byte aligned", fn);
+        if (!y_ld_ok(d, a.y_ld))
+            return fail(SLFP_ERR_BAD_ARG, "%s: y_ld = %lld must be a multiple of 16, >= C_out = %lld", fn, (long long)a.y_ld, (long long)d->c_out);
+        r->route = codes_route(d, io, has_bias, a.relu, r->p);
+        if (!slice_route(r->route))
+            return fail(SLFP_ERR_UNSUPPORTED, "%s: this layer / io combination has no code kernel with a channel-slice store "
+                                              "(slfp_conv2d_codes_slice_supported)", fn);
+    }
+    if ((a.post_scale == nullptr) != (a.post_shift == nullptr))
+        return fail(SLFP_ERR_BAD_ARG, "%s: post_scale and post_shift must be given together", fn);
+    if (a.post_scale && (!aligned16(a.post_scale) || !aligned16(a.post_shift)))
+        return fail(SLFP_ERR_ALIGNMENT, "%s: post_scale / post_shift must be 16-byte aligned", fn);
+    if (kind == kFwdPost) {   // on the code paths these two are a refusal of the route
+        if ((a.relu & ~(SLFP_POST_RELU | SLFP_POST_LAYEROUT)) != 0) return fail(SLFP_ERR_BAD_ARG, "%s: unknown flag bits in `relu`", fn);
+        if ((a.relu & SLFP_POST_LAYEROUT) && !a.post_scale)
+            return fail(SLFP_ERR_BAD_ARG, "%s: SLFP_POST_LAYEROUT needs post_scale / post_shift", fn);
+    }
+    if (!aligned16(a.x) || !aligned16(a.y) || !aligned16(a.wprep) || !aligned16(a.bias) || !aligned16(a.res))
+        return fail(SLFP_ERR_ALIGNMENT, "%s: x, y, wprep, bias and res must be 16-byte aligned", fn);
+    r->post = PostOp{a.post_scale, a.post_shift, (a.relu & SLFP_POST_RELU) ? 1 : 0, (kind == kFwdPost && (a.relu & SLFP_POST_LAYEROUT)) ? 1 : 0};
+    if (kind == kFwdPost) return need_workspace(fn, a, r->p);
+    r->cio = CodeIo{io->x_codes != 0, io->y_codes != 0, io->y_ka, y_fmt_of(io->y_qbits), a.y_ld};
+    if (kind == kFwdEntry) {
+        if (io->x_codes != 0 || io->y_codes != 1)
+            return fail(SLFP_ERR_BAD_ARG, "%s: reads float32 and writes codes (io->x_codes == 0, io->y_codes == 1; "
+                                          "slfp_conv2d_entry_supported)", fn);
+        if (!consumer_quant_ok(io))
+            return fail(SLFP_ERR_BAD_ARG, "%s: io->y_qbits must be 8 or 7 (got %d) and io->y_ka a positive scale within [1e-30, 1e30] "
+                                          "(slfp_conv2d_entry_supported)", fn, io->y_qbits);
+        if (!entry_route(d, io, a.relu, r->p))
+            return fail(SLFP_ERR_UNSUPPORTED, "%s: this layer / io combination has no float32 -> codes kernel "
+                                              "(slfp_conv2d_entry_supported); use slfp_conv2d_fwd_post and slfp_encode_f32", fn);
+        return SLFP_OK;
+    }
+    if (kind == kFwdRes) {   // res is read while y is written, in a different order by different workgroups: the two must not overlap
+        const uintptr_t nbytes = (uintptr_t)d->n * (uintptr_t)d->c_out * (uintptr_t)r->p.h_out * (uintptr_t)r->p.w_out * sizeof(float);
+        const uintptr_t ra = reinterpret_cast<uintptr_t>(a.res), ya = reinterpret_cast<uintptr_t>(a.y);
+        if (ra < ya + nbytes && ya < ra + nbytes) return fail(SLFP_ERR_BAD_ARG, "%s: res and y overlap", fn);
+        if (!res_route(d, io, has_bias, a.relu, r->p))
+            return fail(SLFP_ERR_UNSUPPORTED, "%s: this layer / io combination has no residual kernel "
+                                              "(slfp_conv2d_res_supported); use slfp_conv2d_fwd_post and add the residual afterwards", fn);
+        return SLFP_OK;
+    }
+    if (kind == kFwdCodes) r->route = codes_route(d, io, has_bias, a.relu, r->p);
+    if (r->route == kRouteNone)
+        return fail(SLFP_ERR_UNSUPPORTED, "%s: this layer / io combination has no code-path kernel "
+                                          "(slfp_conv2d_codes_supported); use slfp_conv2d_fwd_post", fn);
+    return r->route == kRouteDense ? need_workspace(fn, a, r->p) : SLFP_OK;
+}
+
+// slfp_conv2d_fwd_codes[_ws] and slfp_conv2d_fwd_codes_slice once resolved.
+static int launch_codes(const FwdArgs& a, const Resolved& r, hipStream_t st) {
+    const slfp_conv2d_desc& d = *a.d;
+    const float* xf = reinterpret_cast<const float*>(a.x);
+    const uint8_t* xc = reinterpret_cast<const uint8_t*>(a.x);
+    switch (r.route) {
+        case kRouteDwc: return launch_dwc(d, r.p, xc, reinterpret_cast<const float*>(a.wprep), r.post, a.y, r.cio, st);
+        case kRoutePwc: return launch_pwc(d, r.p, xc, a.wprep, a.bias, r.post, a.y, r.cio, st);
+        case kRouteDense: return launch_dense_mfma_io(d, r.p, a.x, a.wprep, a.bias, r.post, a.y, a.workspace, r.cio, st);
+        case kRouteStemSmall: return launch_stem_small_io(d, r.p, xf, a.wprep, a.bias, r.post, a.y, r.cio, st);
+        default: return launch_stem_codes(d, r.p, xf, reinterpret_cast<const float*>(a.wprep), a.bias, r.post, a.y, r.cio, st);
+    }
+}
+
+extern "C" {
 
 int slfp_conv2d_fwd(const slfp_conv2d_desc* d, const float* x, const void* wprep, const float* bias, float* y,
                     float* input_q, void* workspace, void* stream) {
@@ -330,64 +500,44 @@ int slfp_conv2d_fwd(const slfp_conv2d_desc* d, const float* x, const void* wprep
 int slfp_conv2d_fwd_post(const slfp_conv2d_desc* d, const float* x, const void* wprep, const float* bias,
                          const float* post_scale, const float* post_shift, int relu, float* y, float* input_q,
                          void* workspace, void* stream) {
-    ConvPlan p;
-    int rc = make_plan(d, &p);
+    const FwdArgs a{d, nullptr, x, wprep, bias, post_scale, post_shift, relu, y, nullptr, 0, workspace};
+    Resolved r;
+    int rc = resolve(kFwdPost, "slfp_conv2d_fwd_post", a, &r);
     if (rc != SLFP_OK) return rc;
-    if (!x || !wprep || !y) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd: null pointer");
-    if ((post_scale == nullptr) != (post_shift == nullptr))
-        return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_post: post_scale and post_shift must be given together");
-    if (post_scale && (!aligned16(post_scale) || !aligned16(post_shift)))
-        return fail(SLFP_ERR_ALIGNMENT, "slfp_conv2d_fwd_post: post_scale / post_shift must be 16-byte aligned");
-    if ((relu & ~(SLFP_POST_RELU | SLFP_POST_LAYEROUT)) != 0)
-        return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_post: unknown flag bits in `relu`");
-    if ((relu & SLFP_POST_LAYEROUT) && !post_scale)
-        return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_post: SLFP_POST_LAYEROUT needs post_scale / post_shift");
-    const PostOp post{post_scale, post_shift, (relu & SLFP_POST_RELU) ? 1 : 0, (relu & SLFP_POST_LAYEROUT) ? 1 : 0};
-    if (!aligned16(x) || !aligned16(y) || !aligned16(wprep) || (bias && !aligned16(bias)))
-        return fail(SLFP_ERR_ALIGNMENT, "slfp_conv2d_fwd: x, y, wprep and bias must be 16-byte aligned");
+    const ConvPlan& p = r.p;
+    const PostOp& post = r.post;
     hipStream_t st = as_stream(stream);
     if (input_q) {  // the reference's self.input_q (utils/conv2d_func.py:21), in x's layout
         rc = launch_quantize(x, input_q, (size_t)d->n * d->c_in * d->h * d->w, d->ka, p.fmt_act, st);
         if (rc != SLFP_OK) return rc;
     }
-    const size_t ws_need = workspace_bytes_for(d, p);   // the plan is built once per call
-    if (ws_need && (!workspace || !aligned16(workspace)))
-        return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd: %zu bytes of 16-byte aligned workspace required (slfp_conv2d_workspace_bytes)", ws_need);
+    const WsLayout l = ws_layout(d, p);
     unsigned char* ws = reinterpret_cast<unsigned char*>(workspace);
     const float* x_nhwc = x;
     float* y_nhwc = y;
     if (d->x_layout == SLFP_LAYOUT_NCHW) {
-        float* t = reinterpret_cast<float*>(ws);
-        ws += round256((size_t)d->n * d->c_in * d->h * d->w * sizeof(float));
+        float* t = reinterpret_cast<float*>(ws + l.x_nhwc);
         rc = slfp_nchw_to_nhwc_f32(x, t, d->n, d->c_in, d->h, d->w, stream);
         if (rc != SLFP_OK) return rc;
         x_nhwc = t;
     }
-    if (d->y_layout == SLFP_LAYOUT_NCHW) {
-        y_nhwc = reinterpret_cast<float*>(ws);
-        ws += round256((size_t)d->n * d->c_out * p.h_out * p.w_out * sizeof(float));
-    }
+    if (d->y_layout == SLFP_LAYOUT_NCHW) y_nhwc = reinterpret_cast<float*>(ws + l.y_nhwc);
     if (p.repad) {
         slfp_conv2d_desc d2;
         padded_desc(*d, &d2);
         const float* xin = x_nhwc;
         float* yout = y_nhwc;
         if (p.cpi != d->c_in) {
-            float* xp = reinterpret_cast<float*>(ws);
-            ws += round256((size_t)d->n * d->h * d->w * p.cpi * sizeof(float));
+            float* xp = reinterpret_cast<float*>(ws + l.x_pad);
             rc = launch_repad(x_nhwc, xp, d->n * d->h * d->w, d->c_in, p.cpi, st);
             if (rc != SLFP_OK) return rc;
             xin = xp;
         }
-        if (p.cpo != d->c_out) {
-            yout = reinterpret_cast<float*>(ws);
-            ws += round256((size_t)d->n * p.h_out * p.w_out * p.cpo * sizeof(float));
-        }
+        if (p.cpo != d->c_out) yout = reinterpret_cast<float*>(ws + l.y_pad);
         const float* vec[3] = {bias, post_scale, post_shift};  // per-channel vectors are read 16 bytes at a time
         for (int i = 0; i < 3; ++i) {
-            float* vp = reinterpret_cast<float*>(ws);
-            ws += round256((size_t)p.cpo * sizeof(float));
             if (!vec[i] || p.cpo == d->c_out) continue;
+            float* vp = reinterpret_cast<float*>(ws + l.vec[i]);
             rc = launch_repad(vec[i], vp, 1, d->c_out, p.cpo, st);
             if (rc != SLFP_OK) return rc;
             vec[i] = vp;
@@ -397,252 +547,92 @@ int slfp_conv2d_fwd_post(const slfp_conv2d_desc* d, const float* x, const void* 
         else rc = launch_pointwise(d2, p, xin, wprep, vec[0], post2, yout, st);
         if (rc != SLFP_OK) return rc;
         if (p.cpo != d->c_out) rc = launch_repad(yout, y_nhwc, d->n * p.h_out * p.w_out, p.cpo, d->c_out, st);
-        if (rc != SLFP_OK) return rc;
-        if (d->y_layout == SLFP_LAYOUT_NCHW) rc = slfp_nhwc_to_nchw_f32(y_nhwc, y, d->n, d->c_out, p.h_out, p.w_out, stream);
-        return rc;
-    }
-    switch (p.family) {
-        case kDw3x3: rc = launch_dw3x3(*d, p, x_nhwc, reinterpret_cast<const float*>(wprep), bias, post, y_nhwc, st); break;
-        case kPointwise: rc = launch_pointwise(*d, p, x_nhwc, wprep, bias, post, y_nhwc, st); break;
-        case kDenseMfma: rc = launch_dense_mfma(*d, p, x_nhwc, wprep, bias, post, y_nhwc, ws, st); break;
-        case kStemMfma: rc = launch_stem_mfma(*d, p, x_nhwc, wprep, bias, post, y_nhwc, ws, st); break;
-        case kStemSmall: rc = launch_stem_small(*d, p, x_nhwc, wprep, bias, post, y_nhwc, st); break;
-        default: rc = launch_direct(*d, p, x_nhwc, reinterpret_cast<const float*>(wprep), bias, post, y_nhwc, st); break;
+    } else {
+        switch (p.family) {
+            case kDw3x3: rc = launch_dw3x3(*d, p, x_nhwc, reinterpret_cast<const float*>(wprep), bias, post, y_nhwc, st); break;
+            case kPointwise: rc = launch_pointwise(*d, p, x_nhwc, wprep, bias, post, y_nhwc, st); break;
+            case kDenseMfma: rc = launch_dense_mfma(*d, p, x_nhwc, wprep, bias, post, y_nhwc, ws + l.operand, st); break;
+            case kStemMfma: rc = launch_stem_mfma(*d, p, x_nhwc, wprep, bias, post, y_nhwc, ws + l.operand, st); break;
+            case kStemSmall: rc = launch_stem_small(*d, p, x_nhwc, wprep, bias, post, y_nhwc, st); break;
+            default: rc = launch_direct(*d, p, x_nhwc, reinterpret_cast<const float*>(wprep), bias, post, y_nhwc, st); break;
+        }
     }
     if (rc != SLFP_OK) return rc;
     if (d->y_layout == SLFP_LAYOUT_NCHW) rc = slfp_nhwc_to_nchw_f32(y_nhwc, y, d->n, d->c_out, p.h_out, p.w_out, stream);
     return rc;
 }
 
-}  // extern "C"
-
-// ---- 1-byte activation codes between layers (include/slfp.h; csrc/slfp_codes.hpp) ----
-static int codes_route(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, bool has_bias, int relu, ConvPlan* p) {
-    // 0: unsupported; 1: depthwise on codes; 2: pointwise on codes; 3: image stem with code output; 4: dense k x k (needs workspace); 5: small-K MFMA stem with code output
-    if (!d || !io) return 0;
-    if (make_plan(d, p) != SLFP_OK) return 0;
-    if (d->x_layout != SLFP_LAYOUT_NHWC || d->y_layout != SLFP_LAYOUT_NHWC) return 0;
-    if ((relu & ~(SLFP_POST_RELU | SLFP_POST_LAYEROUT)) != 0 || (relu & SLFP_POST_LAYEROUT)) return 0;
-    if (io->y_codes) {
-        if (io->y_qbits != 8 && io->y_qbits != 7) return 0;
-        if (!(io->y_ka > 0.f) || !scale_div_ok(io->y_ka)) return 0;
-        if (!enc_table(io->y_ka, io->y_qbits == 8 ? kFmtAct8 : kFmtSfp7, kEncCode)->valid) return 0;
-    }
-    if (long_encode_forced()) return 0;
-    if (io->x_codes) {
-        if (dwc_applicable(*d, *p, has_bias ? reinterpret_cast<const float*>(1) : nullptr, relu)) return 1;
-        if (pwc_applicable(*d, *p, relu, io->y_codes != 0)) return 2;
-        if (dense_codes_applicable(*d, *p, relu, io->y_codes != 0)) return 4;
-        return 0;
-    }
-    if (io->y_codes && stem_codes_applicable(*d, *p, relu)) return 3;
-    if (io->y_codes && dense_codes_applicable(*d, *p, relu, true)) return 4;
-    if (io->y_codes && stem_small_codes_applicable(*d, *p, relu)) return 5;
-    return 0;
-}
-
-extern "C" int slfp_conv2d_codes_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int relu) {
+// The four queries: the route functions behind a null check and make_plan.
+int slfp_conv2d_codes_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int relu) {
     ConvPlan p;
-    return codes_route(d, io, has_bias != 0, relu, &p) != 0 ? 1 : 0;
+    return d && io && make_plan(d, &p) == SLFP_OK && codes_route(d, io, has_bias != 0, relu, p) != kRouteNone;
 }
 
-extern "C" int slfp_conv2d_fwd_codes(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
-                                     const float* bias, const float* post_scale, const float* post_shift, int relu, void* y,
-                                     void* stream) {
+int slfp_conv2d_codes_slice_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int relu, int64_t y_ld) {
+    ConvPlan p;
+    return d && io && io->y_codes && make_plan(d, &p) == SLFP_OK && slice_route(codes_route(d, io, has_bias != 0, relu, p)) && y_ld_ok(d, y_ld);
+}
+
+int slfp_conv2d_entry_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int relu) {
+    (void)has_bias;   // both kernels take a bias
+    ConvPlan p;
+    return d && io && make_plan(d, &p) == SLFP_OK && entry_route(d, io, relu, p);
+}
+
+int slfp_conv2d_res_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int relu) {
+    ConvPlan p;
+    return d && io && make_plan(d, &p) == SLFP_OK && res_route(d, io, has_bias != 0, relu, p);
+}
+
+int slfp_conv2d_fwd_codes(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
+                          const float* bias, const float* post_scale, const float* post_shift, int relu, void* y, void* stream) {
     return slfp_conv2d_fwd_codes_ws(d, io, x, wprep, bias, post_scale, post_shift, relu, y, nullptr, stream);
 }
 
-// y_ld: 0 = y is a dense tensor (slfp_conv2d_fwd_codes_ws); else the channel count of the wider code tensor y is a slice of
-static int fwd_codes_any(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
-                         const float* bias, const float* post_scale, const float* post_shift, int relu, void* y, int64_t y_ld,
-                         void* workspace, void* stream);
-
-extern "C" int slfp_conv2d_fwd_codes_ws(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
-                                        const float* bias, const float* post_scale, const float* post_shift, int relu, void* y,
-                                        void* workspace, void* stream) {
-    return fwd_codes_any(d, io, x, wprep, bias, post_scale, post_shift, relu, y, 0, workspace, stream);
+int slfp_conv2d_fwd_codes_ws(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
+                             const float* bias, const float* post_scale, const float* post_shift, int relu, void* y,
+                             void* workspace, void* stream) {
+    const FwdArgs a{d, io, x, wprep, bias, post_scale, post_shift, relu, y, nullptr, 0, workspace};
+    Resolved r;
+    const int rc = resolve(kFwdCodes, "slfp_conv2d_fwd_codes_ws", a, &r);
+    return rc != SLFP_OK ? rc : launch_codes(a, r, as_stream(stream));
 }
 
-// ---- code output into a channel slice of a wider NHWC code tensor (include/slfp.h: slfp_conv2d_fwd_codes_slice) ----
-// The kernels whose code store takes a pixel stride: the pw_mfma_* code kernels (route 2) and the dense k x k code epilogue (route 4).
-static bool slice_route(int route) { return route == 2 || route == 4; }
-
-extern "C" int slfp_conv2d_codes_slice_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int relu,
-                                                 int64_t y_ld) {
-    ConvPlan p;
-    if (!d || !io || !io->y_codes) return 0;
-    if (!slice_route(codes_route(d, io, has_bias != 0, relu, &p))) return 0;
-    return (y_ld >= d->c_out && y_ld % 16 == 0 && y_ld <= 0x7FFFFFFF) ? 1 : 0;
+// y_ld: the channel count of the wider NHWC code tensor that y is a channel slice of
+int slfp_conv2d_fwd_codes_slice(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
+                                const float* bias, const float* post_scale, const float* post_shift, int relu, void* y,
+                                int64_t y_ld, void* workspace, void* stream) {
+    const FwdArgs a{d, io, x, wprep, bias, post_scale, post_shift, relu, y, nullptr, y_ld, workspace};
+    Resolved r;
+    const int rc = resolve(kFwdSlice, "slfp_conv2d_fwd_codes_slice", a, &r);
+    return rc != SLFP_OK ? rc : launch_codes(a, r, as_stream(stream));
 }
 
-extern "C" int slfp_conv2d_fwd_codes_slice(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
-                                           const float* bias, const float* post_scale, const float* post_shift, int relu, void* y,
-                                           int64_t y_ld, void* workspace, void* stream) {
-    if (!d || !io) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_codes_slice: null descriptor");
-    ConvPlan p;
-    const int rc = make_plan(d, &p);
-    if (rc != SLFP_OK) return rc;
-    if (!x || !wprep || !y) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_codes_slice: null pointer");
-    if (!io->y_codes) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_codes_slice: a channel slice is written as codes (io->y_codes == 1)");
-    if (!aligned16(y)) return fail(SLFP_ERR_ALIGNMENT, "slfp_conv2d_fwd_codes_slice: y (the slice's first channel) must be 16-byte aligned");
-    if (y_ld < d->c_out || y_ld % 16 != 0 || y_ld > 0x7FFFFFFF)
-        return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_codes_slice: y_ld = %lld must be a multiple of 16, >= C_out = %lld", (long long)y_ld,
-                    (long long)d->c_out);
-    if (!slice_route(codes_route(d, io, bias != nullptr, relu, &p)))
-        return fail(SLFP_ERR_UNSUPPORTED, "slfp_conv2d_fwd_codes_slice: this layer / io combination has no code kernel with a channel-slice "
-                                          "store (slfp_conv2d_codes_slice_supported)");
-    return fwd_codes_any(d, io, x, wprep, bias, post_scale, post_shift, relu, y, y_ld, workspace, stream);
+int slfp_conv2d_fwd_entry(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const float* x, const void* wprep,
+                          const float* bias, const float* post_scale, const float* post_shift, int relu, void* y_codes, void* stream) {
+    const FwdArgs a{d, io, x, wprep, bias, post_scale, post_shift, relu, y_codes, nullptr, 0, nullptr};
+    Resolved r;
+    const int rc = resolve(kFwdEntry, "slfp_conv2d_fwd_entry", a, &r);
+    return rc != SLFP_OK ? rc : launch_pointwise_entry(*d, r.p, x, wprep, bias, r.post, y_codes, r.cio, as_stream(stream));
 }
 
-static int fwd_codes_any(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
-                         const float* bias, const float* post_scale, const float* post_shift, int relu, void* y, int64_t y_ld,
-                         void* workspace, void* stream) {
-    if (!d || !io) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_codes: null descriptor");
-    ConvPlan p;
-    int rc = make_plan(d, &p);
-    if (rc != SLFP_OK) return rc;
-    if (!x || !wprep || !y) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_codes: null pointer");
-    if ((post_scale == nullptr) != (post_shift == nullptr))
-        return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_codes: post_scale and post_shift must be given together");
-    if (!aligned16(x) || !aligned16(y) || !aligned16(wprep) || (bias && !aligned16(bias)) ||
-        (post_scale && (!aligned16(post_scale) || !aligned16(post_shift))))
-        return fail(SLFP_ERR_ALIGNMENT, "slfp_conv2d_fwd_codes: pointers must be 16-byte aligned");
-    const int route = codes_route(d, io, bias != nullptr, relu, &p);
-    if (route == 0)
-        return fail(SLFP_ERR_UNSUPPORTED, "slfp_conv2d_fwd_codes: this layer / io combination has no code-path kernel "
-                                          "(slfp_conv2d_codes_supported); use slfp_conv2d_fwd_post");
-    const PostOp post{post_scale, post_shift, (relu & SLFP_POST_RELU) ? 1 : 0, 0};
-    const int y_fmt = io->y_qbits == 7 ? kFmtSfp7 : kFmtAct8;
-    hipStream_t st = as_stream(stream);
-    if (route == 1 && y_ld) return fail(SLFP_ERR_UNSUPPORTED, "slfp_conv2d_fwd_codes_slice: no channel-slice store in this kernel family");
-    if (route == 1)
-        return launch_dwc(*d, p, reinterpret_cast<const uint8_t*>(x), reinterpret_cast<const float*>(wprep), post, y,
-                          io->y_codes != 0, io->y_ka, y_fmt, st);
-    if (route == 2)
-        return launch_pwc(*d, p, reinterpret_cast<const uint8_t*>(x), wprep, bias, post, y, io->y_codes != 0, io->y_ka, y_fmt, st, nullptr, y_ld);
-    if (route == 4) {
-        const size_t ws_need = workspace_bytes_for(d, p);
-        if (ws_need && (!workspace || !aligned16(workspace)))
-            return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_codes_ws: %zu bytes of 16-byte aligned workspace required (slfp_conv2d_workspace_bytes)", ws_need);
-        const CodeIo cio{io->x_codes != 0, io->y_codes != 0, io->y_ka, y_fmt, y_ld};
-        return launch_dense_mfma_io(*d, p, x, wprep, bias, post, y, workspace, cio, st);
-    }
-    if (y_ld) return fail(SLFP_ERR_UNSUPPORTED, "slfp_conv2d_fwd_codes_slice: no channel-slice store in this kernel family");
-    const CodeIo cio{false, true, io->y_ka, y_fmt};
-    if (route == 5) return launch_stem_small_io(*d, p, reinterpret_cast<const float*>(x), wprep, bias, post, y, cio, st);
-    return launch_stem_codes(*d, p, reinterpret_cast<const float*>(x), reinterpret_cast<const float*>(wprep), bias, post, y, cio, st);
-}
-
-// ---- the layer at which a chain of codes begins: pointwise, float32 in -> codes out (include/slfp.h: slfp_conv2d_fwd_entry) ----
-// A query and an entry point of their own: slfp_conv2d_codes_supported keeps answering 0 for this combination (codes_route above
-// is unchanged), so every link count that rests on it stays what it was.
-static bool entry_route(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int relu, ConvPlan* p) {
-    if (!d || !io) return false;
-    if (io->x_codes != 0 || io->y_codes != 1) return false;
-    if (make_plan(d, p) != SLFP_OK) return false;
-    if (d->x_layout != SLFP_LAYOUT_NHWC || d->y_layout != SLFP_LAYOUT_NHWC) return false;
-    if ((relu & ~(SLFP_POST_RELU | SLFP_POST_LAYEROUT)) != 0 || (relu & SLFP_POST_LAYEROUT)) return false;
-    if (io->y_qbits != 8 && io->y_qbits != 7) return false;
-    if (!(io->y_ka > 0.f) || !scale_div_ok(io->y_ka)) return false;
-    if (long_encode_forced()) return false;
-    return pointwise_entry_applicable(*d, *p, relu, io->y_ka, io->y_qbits == 8 ? kFmtAct8 : kFmtSfp7);
-}
-
-extern "C" int slfp_conv2d_entry_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int relu) {
-    (void)has_bias;   // both kernels take a bias
-    ConvPlan p;
-    return entry_route(d, io, relu, &p) ? 1 : 0;
-}
-
-extern "C" int slfp_conv2d_fwd_entry(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const float* x, const void* wprep,
-                                     const float* bias, const float* post_scale, const float* post_shift, int relu,
-                                     void* y_codes, void* stream) {
-    if (!d || !io) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_entry: null descriptor");
-    ConvPlan p;
-    int rc = make_plan(d, &p);
-    if (rc != SLFP_OK) return rc;
-    if (!x || !wprep || !y_codes) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_entry: null pointer");
-    if ((post_scale == nullptr) != (post_shift == nullptr))
-        return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_entry: post_scale and post_shift must be given together");
-    if (!aligned16(x) || !aligned16(y_codes) || !aligned16(wprep) || (bias && !aligned16(bias)) ||
-        (post_scale && (!aligned16(post_scale) || !aligned16(post_shift))))
-        return fail(SLFP_ERR_ALIGNMENT, "slfp_conv2d_fwd_entry: pointers must be 16-byte aligned");
-    if (io->x_codes != 0 || io->y_codes != 1)
-        return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_entry: reads float32 and writes codes (io->x_codes == 0, io->y_codes == 1; "
-                                      "slfp_conv2d_entry_supported)");
-    if (io->y_qbits != 8 && io->y_qbits != 7)
-        return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_entry: io->y_qbits must be 8 or 7, got %d (slfp_conv2d_entry_supported)", io->y_qbits);
-    if (!(io->y_ka > 0.f) || !scale_div_ok(io->y_ka))
-        return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_entry: io->y_ka must be a positive scale within [1e-30, 1e30] (slfp_conv2d_entry_supported)");
-    if (!entry_route(d, io, relu, &p))
-        return fail(SLFP_ERR_UNSUPPORTED, "slfp_conv2d_fwd_entry: this layer / io combination has no float32 -> codes kernel "
-                                          "(slfp_conv2d_entry_supported); use slfp_conv2d_fwd_post and slfp_encode_f32");
-    const PostOp post{post_scale, post_shift, (relu & SLFP_POST_RELU) ? 1 : 0, 0};
-    const CodeIo cio{false, true, io->y_ka, io->y_qbits == 7 ? kFmtSfp7 : kFmtAct8};
-    return launch_pointwise_entry(*d, p, x, wprep, bias, post, y_codes, cio, as_stream(stream));
-}
-
-// ---- residual operand in the pointwise epilogue (include/slfp.h: slfp_conv2d_fwd_res) ----
-static bool res_route(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, bool has_bias, int relu, ConvPlan* p) {
-    if (!d || !io) return false;
-    if (make_plan(d, p) != SLFP_OK) return false;
-    if (d->x_layout != SLFP_LAYOUT_NHWC || d->y_layout != SLFP_LAYOUT_NHWC) return false;
-    if ((relu & ~SLFP_POST_RELU) != 0 || io->y_codes) return false;   // no layer-output quantizer, float32 out
-    if (long_encode_forced()) return false;
-    if (io->x_codes) {
-        const slfp_conv2d_io cio{1, 0, 1.f, 8};
-        ConvPlan q;
-        return p->family == kPointwise && d->stride_h == 1 && d->stride_w == 1 && codes_route(d, &cio, has_bias, relu, &q) == 2;
-    }
-    return pointwise_res_applicable(*d, *p);
-}
-
-extern "C" int slfp_conv2d_res_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int relu) {
-    ConvPlan p;
-    return res_route(d, io, has_bias != 0, relu, &p) ? 1 : 0;
-}
-
-extern "C" int slfp_conv2d_fwd_res(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
-                                   const float* bias, const float* post_scale, const float* post_shift, int relu,
-                                   const float* res, float* y, void* workspace, void* stream) {
+int slfp_conv2d_fwd_res(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
+                        const float* bias, const float* post_scale, const float* post_shift, int relu,
+                        const float* res, float* y, void* workspace, void* stream) {
     (void)workspace;
-    if (!d || !io) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_res: null descriptor");
-    ConvPlan p;
-    int rc = make_plan(d, &p);
+    const FwdArgs a{d, io, x, wprep, bias, post_scale, post_shift, relu, y, res, 0, nullptr};
+    Resolved r;
+    const int rc = resolve(kFwdRes, "slfp_conv2d_fwd_res", a, &r);
     if (rc != SLFP_OK) return rc;
-    if (!x || !wprep || !y || !res) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_res: null pointer");
-    if ((post_scale == nullptr) != (post_shift == nullptr))
-        return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_res: post_scale and post_shift must be given together");
-    if (!aligned16(x) || !aligned16(y) || !aligned16(res) || !aligned16(wprep) || (bias && !aligned16(bias)) ||
-        (post_scale && (!aligned16(post_scale) || !aligned16(post_shift))))
-        return fail(SLFP_ERR_ALIGNMENT, "slfp_conv2d_fwd_res: pointers must be 16-byte aligned");
-    {   // res is read while y is written, in a different order by different workgroups: the two must not overlap
-        const uintptr_t nbytes = (uintptr_t)d->n * (uintptr_t)d->c_out * (uintptr_t)p.h_out * (uintptr_t)p.w_out * sizeof(float);
-        const uintptr_t a = reinterpret_cast<uintptr_t>(res), b = reinterpret_cast<uintptr_t>(y);
-        if (a < b + nbytes && b < a + nbytes) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_fwd_res: res and y overlap");
-    }
-    if (!res_route(d, io, bias != nullptr, relu, &p))
-        return fail(SLFP_ERR_UNSUPPORTED, "slfp_conv2d_fwd_res: this layer / io combination has no residual kernel "
-                                          "(slfp_conv2d_res_supported); use slfp_conv2d_fwd_post and add the residual afterwards");
-    const PostOp post{post_scale, post_shift, (relu & SLFP_POST_RELU) ? 1 : 0, 0};
     hipStream_t st = as_stream(stream);
-    if (io->x_codes)
-        return launch_pwc(*d, p, reinterpret_cast<const uint8_t*>(x), wprep, bias, post, y, false, 1.f, kFmtAct8, st, res);
-    return launch_pointwise(*d, p, reinterpret_cast<const float*>(x), wprep, bias, post, y, st, res);
+    if (!io->x_codes) return launch_pointwise(*d, r.p, reinterpret_cast<const float*>(x), wprep, bias, r.post, y, st, res);
+    const CodeIo codes_in{true, false, 1.f, kFmtAct8};
+    return launch_pwc(*d, r.p, reinterpret_cast<const uint8_t*>(x), wprep, bias, r.post, y, codes_in, st, res);
 }
+
+}  // extern "C"
 
 extern "C" {
-
-size_t slfp_linear_workspace_bytes(int64_t batch, int64_t in_f, int64_t out_f) {
-    slfp_conv2d_desc d;
-    memset(&d, 0, sizeof(d));
-    d.n = batch; d.c_in = in_f; d.h = 1; d.w = 1; d.c_out = out_f; d.kh = 1; d.kw = 1;
-    d.stride_h = d.stride_w = d.dil_h = d.dil_w = d.groups = 1;
-    d.x_layout = d.y_layout = SLFP_LAYOUT_NHWC; d.qbits = 8; d.ka = d.kw_scale = 1.f;
-    ConvPlan p;
-    if (make_plan_core(&d, &p) != SLFP_OK) return 0;  // the plan slfp_linear_fwd uses (no channel re-padding)
-    return p.wprep_bytes;
-}
 
 static void linear_desc(slfp_conv2d_desc* d, int64_t batch, int64_t in_f, int64_t out_f, float ka, float kw_scale,
                         int qbits, int mfma_passes) {
@@ -653,6 +643,14 @@ static void linear_desc(slfp_conv2d_desc* d, int64_t batch, int64_t in_f, int64_
     d->stride_h = d->stride_w = d->dil_h = d->dil_w = d->groups = 1;
     d->x_layout = d->y_layout = SLFP_LAYOUT_NHWC; d->qbits = qbits; d->ka = ka; d->kw_scale = kw_scale;
     d->mfma_passes = mfma_passes;
+}
+
+size_t slfp_linear_workspace_bytes(int64_t batch, int64_t in_f, int64_t out_f) {
+    slfp_conv2d_desc d;
+    linear_desc(&d, batch, in_f, out_f, 1.f, 1.f, 8, SLFP_MFMA_DEFAULT);
+    ConvPlan p;
+    if (make_plan_core(&d, &p) != SLFP_OK) return 0;  // the plan slfp_linear_fwd uses (no channel re-padding)
+    return p.wprep_bytes;
 }
 
 int slfp_linear_prepare_weights(const float* w, void* wprep, int64_t in_f, int64_t out_f, float kw_scale, int qbits,

@@ -187,9 +187,10 @@ bool dwc_applicable(const slfp_conv2d_desc& d, const ConvPlan& plan, const float
     return in_b < (1ull << 30) && out_b < (1ull << 30);   // offsets: bit 30 / 31 mark an invalid column / row
 }
 
-// y_codes: output codes for a consumer with scale y_ka and format y_fmt (kFmtAct8 | kFmtSfp7); else float32
+// io.y_codes: output codes for a consumer with scale io.y_ka and format io.y_fmt (kFmtAct8 | kFmtSfp7); else float32
 int launch_dwc(const slfp_conv2d_desc& d, const ConvPlan& plan, const uint8_t* x, const float* wq9c, const PostOp& post,
-               void* y, bool y_codes, float y_ka, int y_fmt, hipStream_t stream) {
+               void* y, const CodeIo& io, hipStream_t stream) {
+    const bool y_codes = io.y_codes;
     DwcParams p;
     p.N = (int)d.n; p.H = (int)d.h; p.W = (int)d.w; p.C = (int)d.c_in;
     p.Ho = (int)plan.h_out; p.Wo = (int)plan.w_out; p.pad = d.pad_h;
@@ -206,14 +207,14 @@ int launch_dwc(const slfp_conv2d_desc& d, const ConvPlan& plan, const uint8_t* x
     p.ntasks = (uint32_t)ntasks;
     p.nblocks = (uint32_t)nblocks;
     p.fmt_in = plan.fmt_act;
-    p.fmt_out = y_fmt;
+    p.fmt_out = io.y_fmt;
     p.ka = d.ka; p.kw = d.kw_scale;
     p.relu = post.relu;
     p.post_scale = post.scale; p.post_shift = post.shift;
     p.enc.valid = 0;
     if (y_codes) {
-        const EncArgs* t = enc_table(y_ka, y_fmt, kEncCode);
-        if (!t->valid) return fail(SLFP_ERR_UNSUPPORTED, "dw3x3 (codes): no code table for the consumer's scale %g", (double)y_ka);
+        const EncArgs* t = enc_table(io.y_ka, io.y_fmt, kEncCode);
+        if (!t->valid) return fail(SLFP_ERR_UNSUPPORTED, "dw3x3 (codes): no code table for the consumer's scale %g", (double)io.y_ka);
         p.enc = *t;
     }
     const bool has_post = post.scale != nullptr;

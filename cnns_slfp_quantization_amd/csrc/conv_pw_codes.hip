@@ -700,7 +700,9 @@ static int launch_pwc_fmt(PwcParams& p, const ConvPlan& plan, bool y_codes, hipS
 }
 
 int launch_pwc(const slfp_conv2d_desc& d, const ConvPlan& plan, const uint8_t* x, const void* wfrag, const float* bias,
-               const PostOp& post, void* y, bool y_codes, float y_ka, int y_fmt, hipStream_t stream, const float* res, int64_t y_ld) {
+               const PostOp& post, void* y, const CodeIo& io, hipStream_t stream, const float* res) {
+    const bool y_codes = io.y_codes;
+    const int64_t y_ld = io.y_ld;
     if (res && y_codes) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): a residual operand needs float32 output");
     if (y_ld && (!y_codes || y_ld < d.c_out || y_ld % 16 || y_ld > 0x7FFFFFFF))
         return fail(SLFP_ERR_BAD_ARG, "pointwise (codes): a channel-slice output needs code output and a pixel stride that is a multiple of 16, >= C_out");
@@ -716,11 +718,11 @@ int launch_pwc(const slfp_conv2d_desc& d, const ConvPlan& plan, const uint8_t* x
     p.M = d.n * plan.h_out * plan.w_out;
     p.s1 = plan.s1; p.s2 = plan.s2; p.s1x = plan.s1 * (1.0f / 256.0f);
     p.sgn = post.relu ? 0 : 1;
-    p.fmt_out = y_fmt;
+    p.fmt_out = io.y_fmt;
     p.enc.valid = 0;
     if (y_codes) {
-        const EncArgs* t = enc_table(y_ka, y_fmt, kEncCode);
-        if (!t->valid) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): no code table for the consumer's scale %g", (double)y_ka);
+        const EncArgs* t = enc_table(io.y_ka, io.y_fmt, kEncCode);
+        if (!t->valid) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): no code table for the consumer's scale %g", (double)io.y_ka);
         p.enc = *t;
     }
     if (plan.fmt_act == kFmtSfp7) return launch_pwc_fmt<kFmtSfp7>(p, plan, y_codes, stream);

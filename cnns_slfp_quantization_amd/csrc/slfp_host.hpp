@@ -150,8 +150,7 @@ int launch_pointwise_entry(const slfp_conv2d_desc& d, const ConvPlan& p, const f
 // pointwise on codes (conv_pw_codes.hpp): codes in, codes or float32 out; the SAME prepared blob as launch_pointwise
 bool pwc_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, int post_flags, bool y_codes);
 int launch_pwc(const slfp_conv2d_desc& d, const ConvPlan& p, const uint8_t* x, const void* wfrag, const float* bias,
-               const PostOp& post, void* y, bool y_codes, float y_ka, int y_fmt, hipStream_t stream, const float* res = nullptr,
-               int64_t y_ld = 0);   // y_ld: code output into a channel slice (see CodeIo::y_ld); 0: dense
+               const PostOp& post, void* y, const CodeIo& io, hipStream_t stream, const float* res = nullptr);
 // the MobileNetV1 image stem with code output (conv_direct.hip)
 bool stem_codes_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, int post_flags);
 int launch_stem_codes(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const float* wq_hwio, const float* bias,
@@ -159,7 +158,7 @@ int launch_stem_codes(const slfp_conv2d_desc& d, const ConvPlan& p, const float*
 // depthwise 3x3 on codes (conv_dwc.hip): codes in, codes or float32 out
 bool dwc_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, const float* bias, int post_flags);
 int launch_dwc(const slfp_conv2d_desc& d, const ConvPlan& p, const uint8_t* x, const float* wq9c, const PostOp& post,
-               void* y, bool y_codes, float y_ka, int y_fmt, hipStream_t stream);
+               void* y, const CodeIo& io, hipStream_t stream);
 int launch_direct(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const float* wq_hwio,
                   const float* bias, const PostOp& post, float* y, hipStream_t stream);
 bool stem_applicable(const slfp_conv2d_desc& d);  // direct family: the small-C_in stem kernel takes it

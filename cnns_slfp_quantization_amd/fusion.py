@@ -200,7 +200,7 @@ class DwPwBlock(nn.Module):
 
     def forward(self, x):
         from . import _lib
-        from .conv2d_func import _conv_desc, _conv_weights, _epilogue_args, options
+        from .conv2d_func import _conv_desc, _conv_weights, _epilogue_args, _ptr, options
         dw, pw = self.dw, self.pw
         ok = (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)
               and not self.training and not torch.is_grad_enabled() and options.mfma_passes in (_lib.MFMA_DEFAULT, _lib.MFMA_F16X1)
@@ -233,9 +233,7 @@ class DwPwBlock(nn.Module):
             y = torch.empty((N, pw.out_channels, ho.value, wo.value), dtype=torch.float32, device=x.device,
                             memory_format=torch.channels_last)
             _lib.check(L.slfp_dwpw_fwd(ctypes.byref(d1), ctypes.byref(d2), x.data_ptr(), b1.data_ptr(), s1.data_ptr(), h1.data_ptr(),
-                                       f1 & 1, b2.data_ptr(), bias2.data_ptr() if bias2 is not None else None,
-                                       s2.data_ptr() if s2 is not None else None, h2.data_ptr() if s2 is not None else None,
-                                       f2 & 1, y.data_ptr(), stream.cuda_stream))
+                                       f1 & 1, b2.data_ptr(), _ptr(bias2), _ptr(s2), _ptr(h2), f2 & 1, y.data_ptr(), stream.cuda_stream))
         self._last_kernel = "dwpw_fused_f16x1" if dw.q_bit == 8 else "dwpw_fused_f16_exact"
         dw._last_input, dw._input_q = x.detach(), None
         pw._last_input, pw._input_q = None, None   # the pointwise input never exists as a tensor
@@ -322,24 +320,6 @@ def _poolable(m):
             and (m.dilation == 1 or m.dilation == (1, 1)))
 
 
-def _codes_kernel_exists(m, shape, x_codes, out, flags):
-    """Does libslfp_hip run Conv2d_Q `m` on a channels_last input of `shape` with codes in (x_codes) / codes out for the
-    layer `out` = (Ka, q_bit) describes (None: float32 out), with `flags` in its epilogue?"""
-    from . import _lib
-    from .conv2d_func import _conv_desc, _conv_io
-    d, io = _conv_desc(m, shape), _conv_io(x_codes, out)
-    return bool(_lib.load().slfp_conv2d_codes_supported(ctypes.byref(d), ctypes.byref(io), 1 if m.bias is not None else 0, flags))
-
-
-def _entry_kernel_exists(m, shape, out, flags):
-    """Does libslfp_hip run Conv2d_Q `m` on a float32 channels_last input of `shape` with codes out for the layer `out` = (Ka,
-    q_bit) describes, in ONE launch (slfp_conv2d_fwd_entry: the 1x1 layer at which a chain of codes begins)?"""
-    from . import _lib
-    from .conv2d_func import _conv_desc, _conv_io
-    d, io = _conv_desc(m, shape), _conv_io(False, out)
-    return bool(_lib.load().slfp_conv2d_entry_supported(ctypes.byref(d), ctypes.byref(io), 1 if m.bias is not None else 0, flags))
-
-
 def link_codes(model, example_input=None):
     """After fuse_bn_relu: wherever a Conv2d_Q's (fused BN + ReLU) output feeds the next Conv2d_Q of an nn.Sequential
     directly (only nn.Identity in between -- nets_imgnet/mobilenetv1.py:24-33 after fusion), link the two: the producer's
@@ -349,7 +329,7 @@ def link_codes(model, example_input=None):
     With `example_input` (a channels_last ROCm batch) only links for which both kernels exist are made (one forward
     records the shapes); without it every candidate is linked and combinations without a kernel run through the float32
     interface plus an encode / decode pass (correct, slower).  Inference only.  Returns the number of links."""
-    from .conv2d_func import _scalar_scale
+    from .conv2d_func import _scalar_scale, _supported
     shapes = {}
     if example_input is not None:
         hooks = []
@@ -370,7 +350,7 @@ def link_codes(model, example_input=None):
         shp = shapes.get(m)
         if shp is None or len(shp) != 4:
             return False
-        return _codes_kernel_exists(m, shp, x_codes, out, int(m._post[2]) if m._post is not None else 0)
+        return _supported(m, shp, "codes", x_codes, out, int(m._post[2]) if m._post is not None else 0)
 
     def eligible(m):
         return (_is_conv_q(m) and m.q_bit in (8, 7) and not m.training and isinstance(m.padding, tuple)
@@ -439,7 +419,7 @@ def link_codes_traced(model, example_input, entries=False):
     slfp_conv2d_entry_supported says yes (a 1x1 layer: conv1 of every Bottleneck, which reads the float32 trunk); it gets
     `_code_entry = True` and runs slfp_conv2d_fwd_entry.  Everything else -- one consumer only, ReLU folding, pools, verification,
     roll-back -- is the same; the default keeps every link count what it was."""
-    from .conv2d_func import _scalar_scale
+    from .conv2d_func import _scalar_scale, _supported
     conv_io, relu_io, pool_io, order, keep = {}, [], [], [], []
     hooks = []
     for m in model.modules():
@@ -484,7 +464,7 @@ def link_codes_traced(model, example_input, entries=False):
         xin = conv_io[m][0]
         if xin.dim() != 4:
             return False
-        return _codes_kernel_exists(m, xin.shape, x_codes, out, flags)
+        return _supported(m, xin.shape, "codes", x_codes, out, flags)
 
     cand = {}
     for b in order:
@@ -517,7 +497,7 @@ def link_codes_traced(model, example_input, entries=False):
         entry = False
         if not supported(a, a_in, out, flags):
             entry = (entries and not a_in and conv_io[a][0].dim() == 4
-                     and _entry_kernel_exists(a, conv_io[a][0].shape, out, flags))
+                     and _supported(a, conv_io[a][0].shape, "entry", False, out, flags))
             if not entry:
                 continue
         if not supported(b, True, b._code_out, bflags):
@@ -761,7 +741,7 @@ def fuse_fire(model, example_input, entries=False):
     the chain.  The verification is the same."""
     import types
     import warnings
-    from .conv2d_func import _scalar_scale, _conv_desc, _conv_io, _f32, _act_fmt
+    from .conv2d_func import _scalar_scale, _supported, _f32, _act_fmt
     from .sfp_quant import hip_encode
     from . import _lib
     cands = [m for m in model.modules() if _fire_candidate(m)]
@@ -816,15 +796,6 @@ def fuse_fire(model, example_input, entries=False):
             return None
         return found[0]
 
-    L = _lib.load()
-
-    def kernel_exists(m, shape, x_codes, out, flags, y_ld=None):
-        d, io = _conv_desc(m, shape), _conv_io(x_codes, out)
-        hb = 1 if m.bias is not None else 0
-        if y_ld is None:
-            return bool(L.slfp_conv2d_codes_supported(ctypes.byref(d), ctypes.byref(io), hb, flags))
-        return bool(L.slfp_conv2d_codes_slice_supported(ctypes.byref(d), ctypes.byref(io), hb, flags, y_ld))
-
     done = []
     for blk in cands:
         calls = rec.get(blk, [])
@@ -848,15 +819,15 @@ def fuse_fire(model, example_input, entries=False):
         hshape = (x.shape[0], sq.out_channels, x.shape[2], x.shape[3])
         nshape = (x.shape[0], nxt.in_channels) + tuple(next(xin for mod, xin in conv_in if mod is nxt).shape[2:])
         nflags = int(nxt._post[2]) if nxt._post is not None else 0
-        if not (kernel_exists(sq, tuple(x.shape), True, out_e, 1) and kernel_exists(e1, hshape, True, out_n, 1, ld)
-                and kernel_exists(e3, hshape, True, out_n, 1, ld) and kernel_exists(nxt, nshape, True, None, nflags)):
+        if not (_supported(sq, tuple(x.shape), "codes", True, out_e, 1) and _supported(e1, hshape, "slice", True, out_n, 1, ld)
+                and _supported(e3, hshape, "slice", True, out_n, 1, ld) and _supported(nxt, nshape, "codes", True, None, nflags)):
             continue
         st = {"posts": [(c, c._post) for c in (sq, e1, e3)], "pools": []}
         for c in (sq, e1, e3):
             c._post = ((c._post[0], c._post[1]) if c._post is not None else (None, None)) + (1,)
         sq._code_out, e1._code_out, e3._code_out = out_e, out_n, out_n
         sq._code_entry = bool(entries and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)
-                              and _entry_kernel_exists(sq, tuple(x.shape), out_e, 1))
+                              and _supported(sq, tuple(x.shape), "entry", False, out_e, 1))
         blk.__dict__["_fire_fused"] = st
         blk.__dict__["forward"] = types.MethodType(_fire_forward, blk)
         ok = False
