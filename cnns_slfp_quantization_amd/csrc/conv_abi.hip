@@ -345,6 +345,7 @@ enum CodeRoute {
     kRouteStemCodes,   // the image stem with code output
     kRouteDense,       // dense k x k (needs the workspace)
     kRouteStemSmall,   // the small-K MFMA stem with code output
+    kRouteStemMfma,    // the large-kernel MFMA stem with code output (its two-kernel form needs the workspace)
 };
 
 static int y_fmt_of(int y_qbits) { return y_qbits == 7 ? kFmtSfp7 : kFmtAct8; }
@@ -375,6 +376,7 @@ static CodeRoute codes_route(const slfp_conv2d_desc* d, const slfp_conv2d_io* io
     if (stem_codes_applicable(*d, p, relu)) return kRouteStemCodes;
     if (dense_codes_applicable(*d, p, relu, true)) return kRouteDense;
     if (stem_small_codes_applicable(*d, p, relu)) return kRouteStemSmall;
+    if (stem_mfma_codes_applicable(*d, p, relu)) return kRouteStemMfma;
     return kRouteNone;
 }
 
@@ -473,7 +475,8 @@ static int resolve(FwdKind kind, const char* fn, const FwdArgs& a, Resolved* r) 
     if (r->route == kRouteNone)
         return fail(SLFP_ERR_UNSUPPORTED, "%s: this layer / io combination has no code-path kernel "
                                           "(slfp_conv2d_codes_supported); use slfp_conv2d_fwd_post", fn);
-    return r->route == kRouteDense ? need_workspace(fn, a, r->p) : SLFP_OK;
+    if (r->route == kRouteStemMfma && !stem_mfma_uses_workspace(*d, true)) return SLFP_OK;   // k_stem_rows: everything in LDS
+    return r->route == kRouteDense || r->route == kRouteStemMfma ? need_workspace(fn, a, r->p) : SLFP_OK;
 }
 
 // slfp_conv2d_fwd_codes[_ws] and slfp_conv2d_fwd_codes_slice once resolved.
@@ -486,6 +489,7 @@ static int launch_codes(const FwdArgs& a, const Resolved& r, hipStream_t st) {
         case kRoutePwc: return launch_pwc(d, r.p, xc, a.wprep, a.bias, r.post, a.y, r.cio, st);
         case kRouteDense: return launch_dense_mfma_io(d, r.p, a.x, a.wprep, a.bias, r.post, a.y, a.workspace, r.cio, st);
         case kRouteStemSmall: return launch_stem_small_io(d, r.p, xf, a.wprep, a.bias, r.post, a.y, r.cio, st);
+        case kRouteStemMfma: return launch_stem_mfma_io(d, r.p, xf, a.wprep, a.bias, r.post, a.y, a.workspace, r.cio, st);
         default: return launch_stem_codes(d, r.p, xf, reinterpret_cast<const float*>(a.wprep), a.bias, r.post, a.y, r.cio, st);
     }
 }

@@ -18,6 +18,7 @@
 //      padding are skipped (wave-uniform).
 // Precision: single-pass fp16 (SLFP<3,4>) / exact (SFP<3,3>), as conv_dense.hip.
 #include "slfp_device.hpp"
+#include "slfp_codes.hpp"
 #include "slfp_host.hpp"
 
 namespace slfp {
@@ -26,6 +27,50 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 constexpr int kSmThreads = 512;
+
+// ---- 1-byte codes out (the YC forms of k_stem_rows / k_stem_mfma; slfp_codes.hpp) ----------------------------------
+// The consumer's quantizer runs in the epilogue: the chain of codes starts at the image.  C_out is a multiple of 16.
+struct StemCodeOut {
+    uint8_t* yc;          // [N][Ho][Wo][O] codes
+    int y_sgn, y_fmt;     // y_sgn: no ReLU ends the epilogue, the codes carry a sign
+    uint32_t enc_off;     // byte offset of the kEncCode table inside the dynamic LDS (behind W)
+    EncArgs enc_out;
+};
+
+// The finished float4 of every channel tile -> its four codes; the dwords of four tiles regrouped so that lane (pixel, kq)
+// holds the 16 consecutive channel codes of tile g + kq; one 16-byte store.  NT = 6: the second group holds tiles 4 and 5 and
+// two dead operands.  Every lane of the wave runs the transposes; `live` only guards the stores.
+template <int NT>
+__device__ __forceinline__ void stem_store_codes(const floatx4 (&acc)[NT], const float4 (&bqv)[NT], const PostVec (&pvv)[NT],
+                                                 PostOp po, const float s1x, const float s2, const StemCodeOut& co,
+                                                 const unsigned char* __restrict__ senc, uint8_t* __restrict__ yp, const int O,
+                                                 const int kq, const bool live) {
+    po.relu = 0;   // folded into the quantizer
+    const float r1 = co.enc_out.r1, lo = co.enc_out.lo, hi = co.enc_out.hi;
+#pragma unroll
+    for (int g = 0; g < NT; g += 4) {
+        uint32_t c[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (g + i >= NT) continue;
+            const float4 bq = bqv[g + i];
+            float4 r;
+            r.x = ((acc[g + i][0] + bq.x) * s1x) * s2;
+            r.y = ((acc[g + i][1] + bq.y) * s1x) * s2;
+            r.z = ((acc[g + i][2] + bq.z) * s1x) * s2;
+            r.w = ((acc[g + i][3] + bq.w) * s1x) * s2;
+            r = post_apply_v(r, po, pvv[g + i]);
+            if (co.y_sgn) c[i] = code_sign4(enc4_code<false>(r, r1, lo, hi, senc), r, co.y_fmt);
+            else c[i] = enc4_code_relu(relu_of_nan4(r), r1, lo, hi, senc);
+        }
+        rows_transpose4(c[0], c[1], c[2], c[3]);
+        const int ch = (g + kq) * 16;
+        if (live && g + kq < NT && ch < O) {
+            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+            *reinterpret_cast<u32x4*>(yp + ch) = u32x4{c[0], c[1], c[2], c[3]};
+        }
+    }
+}
 
 struct StemMfmaParams {
     const _Float16* xe;  // [N][H][Wo][Rp]
@@ -39,7 +84,9 @@ struct StemMfmaParams {
     int64_t units;       // N * Ho * segs
     float s1, s2, s1x;
     PostOp post;
+    StemCodeOut co;      // YC forms only
 };
+static_assert(sizeof(StemMfmaParams) <= 4096, "StemMfmaParams must fit the 4 KiB kernel-argument segment");
 
 template <int FMT>
 __global__ __launch_bounds__(256) void k_stem_im2row(const float* __restrict__ x, _Float16* __restrict__ xe,
@@ -77,9 +124,11 @@ __global__ __launch_bounds__(256) void k_stem_im2row(const float* __restrict__ x
 }
 
 // NT = 16-channel tiles (4: C_out <= 64, 6: C_out <= 96).  KB = k-steps whose B fragments are in flight.
-template <int NT, int KB>
+// YC: the output leaves as 1-byte codes of the consumer's quantizer (StemCodeOut) instead of float32.
+template <int NT, int KB, bool YC = false>
 __global__ __launch_bounds__(kSmThreads, 2) void k_stem_mfma(const StemMfmaParams p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // W: [KS][NT][1 KiB]
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // W: [KS][NT][1 KiB]; YC: + the kEncCode table
+    if constexpr (YC) enc_fill<kSmThreads>(reinterpret_cast<uint2*>(smem + p.co.enc_off), p.co.enc_out);   // published by the barrier below
     {
         const int n16 = p.KS * NT * 64;
         const uint4* src = reinterpret_cast<const uint4*>(p.w);
@@ -149,7 +198,10 @@ __global__ __launch_bounds__(kSmThreads, 2) void k_stem_mfma(const StemMfmaParam
                 }
             }
         }
-        if (ow < p.Wo) {
+        if constexpr (YC) {
+            stem_store_codes<NT>(acc, bqv, pvv, p.post, p.s1x, p.s2, p.co, smem + p.co.enc_off,
+                                 p.co.yc + (((int64_t)n * p.Ho + oh) * p.Wo + owc) * p.O, p.O, kq, ow < p.Wo);
+        } else if (ow < p.Wo) {
             float* yp = p.y + (((int64_t)n * p.Ho + oh) * p.Wo + ow) * p.O;
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
@@ -193,14 +245,17 @@ struct StemRowsParams {
     float s1, s2, s1x;
     PostOp post;
     uint32_t nblocks;
+    StemCodeOut co;      // YC forms only
 };
+static_assert(sizeof(StemRowsParams) <= 4096, "StemRowsParams must fit the 4 KiB kernel-argument segment");
 
-template <int FMT, int NT>
+template <int FMT, int NT, bool YC = false>
 __global__ __launch_bounds__(kSrThreads) void k_stem_rows(const StemRowsParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint32_t* sT = reinterpret_cast<uint32_t*>(smem);
     _Float16* tile = reinterpret_cast<_Float16*>(smem + 64);   // [IH][row_h]
     lut_fill<FMT>(sT);
+    if constexpr (YC) enc_fill<kSrThreads>(reinterpret_cast<uint2*>(smem + p.co.enc_off), p.co.enc_out);   // published by the barriers below
     {   // W: all k-steps resident
         const int n16 = p.KS * NT * 64;
         const uint4* src = reinterpret_cast<const uint4*>(p.w);
@@ -289,7 +344,11 @@ __global__ __launch_bounds__(kSrThreads) void k_stem_rows(const StemRowsParams p
                 }
             }
         }
-        if (goh < p.Ho && gow < p.Wo) {
+        if constexpr (YC) {
+            const bool live = goh < p.Ho && gow < p.Wo;
+            stem_store_codes<NT>(acc, bqv, pvv, p.post, p.s1x, p.s2, p.co, smem + p.co.enc_off,
+                                 p.co.yc + (live ? (((size_t)n * p.Ho + goh) * p.Wo + gow) * p.O : 0), p.O, kq, live);
+        } else if (goh < p.Ho && gow < p.Wo) {
             float* yp = p.y + (((size_t)n * p.Ho + goh) * p.Wo + gow) * p.O;
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
@@ -331,17 +390,23 @@ size_t stem_mfma_workspace_bytes(const slfp_conv2d_desc& d, int64_t w_out) {
     return (((size_t)d.n * d.h * w_out * stem_rp(d) * sizeof(_Float16)) + 255) & ~(size_t)255;
 }
 
-template <int NT>
+template <int NT, bool YC>
 static int launch_stem_mfma_t(const StemMfmaParams& p, size_t lds, unsigned grid, hipStream_t stream) {
-    auto fn = k_stem_mfma<NT, 8>;
+    auto fn = k_stem_mfma<NT, 8, YC>;
     const int rc = raise_lds_limit(reinterpret_cast<const void*>(fn), 160 * 1024);  // once per (device, kernel)
     if (rc != SLFP_OK) return rc;
     hipLaunchKernelGGL(fn, dim3(grid), dim3(kSmThreads), lds, stream, p);
     return check_launch("slfp MFMA stem kernel");
 }
 
-// the fused form: even S*C (4-byte aligned fragment reads), everything in one workgroup's LDS
-static bool stem_rows_geometry(const slfp_conv2d_desc& d, StemRowsParams* p, size_t* lds, int* nt_out) {
+template <int FMT, bool YC>
+static void launch_stem_rows_t(const StemRowsParams& q, int nt, size_t lds, hipStream_t stream) {
+    if (nt == 4) hipLaunchKernelGGL((k_stem_rows<FMT, 4, YC>), dim3(q.nblocks), dim3(kSrThreads), lds, stream, q);
+    else hipLaunchKernelGGL((k_stem_rows<FMT, 6, YC>), dim3(q.nblocks), dim3(kSrThreads), lds, stream, q);
+}
+
+// the fused form: even S*C (4-byte aligned fragment reads), everything in one workgroup's LDS (yc: the code table as well)
+static bool stem_rows_geometry(const slfp_conv2d_desc& d, bool yc, StemRowsParams* p, size_t* lds, int* nt_out) {
     if ((d.stride_w * d.c_in) % 2) return false;
     int ksub, nt;
     stem_mfma_blob_shape(d, &ksub, &nt);
@@ -354,17 +419,58 @@ static bool stem_rows_geometry(const slfp_conv2d_desc& d, StemRowsParams* p, siz
     p->RL = rl;
     p->w_off = (uint32_t)((64 + (size_t)p->IH * p->row_h * sizeof(_Float16) + 15) & ~(size_t)15);
     *lds = p->w_off + (size_t)p->KS * nt * 1024;
+    p->co.enc_off = (uint32_t)*lds;   // W ends on a 1 KiB step of a 16-byte aligned offset
+    if (yc) *lds += (size_t)kEncEntries * 8;
     *nt_out = nt;
     return *lds <= 64 * 1024 && (int64_t)d.h * d.w * d.c_in < (1ll << 30);
 }
 
+static bool stem_rows_form(const slfp_conv2d_desc& d, bool yc, StemRowsParams* q, size_t* lds, int* nt) {
+    return !switches().stem_im2row && stem_rows_geometry(d, yc, q, lds, nt);
+}
+
+// code output: whole 16-channel tiles (the 16-byte store of a lane), no layer-output quantizer
+bool stem_mfma_codes_applicable(const slfp_conv2d_desc& d, const ConvPlan& plan, int post_flags) {
+    return plan.family == kStemMfma && !plan.repad && d.c_out % 16 == 0 && !(post_flags & SLFP_POST_LAYEROUT);
+}
+
+// does the call run the two-kernel form, which reads the im2row copy from the workspace?
+bool stem_mfma_uses_workspace(const slfp_conv2d_desc& d, bool y_codes) {
+    StemRowsParams q;
+    size_t lds;
+    int nt;
+    return !stem_rows_form(d, y_codes, &q, &lds, &nt);
+}
+
 int launch_stem_mfma(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x, const void* wblob,
                      const float* bias, const PostOp& post, float* y, void* workspace, hipStream_t stream) {
+    const CodeIo io{false, false, 1.f, kFmtAct8};
+    return launch_stem_mfma_io(d, plan, x, wblob, bias, post, y, workspace, io, stream);
+}
+
+int launch_stem_mfma_io(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x, const void* wblob,
+                        const float* bias, const PostOp& post, void* y_any, void* workspace, const CodeIo& io,
+                        hipStream_t stream) {
+    const bool yc = io.y_codes;
+    float* y = yc ? nullptr : reinterpret_cast<float*>(y_any);
+    StemCodeOut co = {};   // float32 out: a zeroed table travels in the kernel arguments, no YC form reads it
+    co.y_fmt = kFmtAct8;
+    if (yc) {
+        const EncArgs* t = enc_table(io.y_ka, io.y_fmt, kEncCode);
+        if (!t->valid || d.c_out % 16) return fail(SLFP_ERR_UNSUPPORTED, "MFMA stem: no code output for this layer");
+        co.enc_out = *t;
+        co.yc = reinterpret_cast<uint8_t*>(y_any);
+        co.y_sgn = post.relu ? 0 : 1;
+        co.y_fmt = io.y_fmt;
+    }
+    const bool a8 = plan.fmt_act == kFmtAct8;
     {
         StemRowsParams q;
         size_t lds;
         int nt;
-        if (!switches().stem_im2row && stem_rows_geometry(d, &q, &lds, &nt)) {
+        if (stem_rows_form(d, yc, &q, &lds, &nt)) {
+            co.enc_off = q.co.enc_off;
+            q.co = co;
             q.x = x; q.w = reinterpret_cast<const _Float16*>(wblob); q.bias = bias; q.y = y; q.post = post;
             q.N = (int)d.n; q.H = (int)d.h; q.W = (int)d.w; q.C = (int)d.c_in; q.O = (int)d.c_out; q.KH = (int)d.kh;
             q.S = d.stride_h; q.ph = d.pad_h; q.pw = d.pad_w; q.Ho = (int)plan.h_out; q.Wo = (int)plan.w_out;
@@ -374,13 +480,12 @@ int launch_stem_mfma(const slfp_conv2d_desc& d, const ConvPlan& plan, const floa
             const int64_t nblocks = (int64_t)q.N * q.tiles_h * q.tiles_w;
             if (nblocks > 0x7FFFFFFF) return fail(SLFP_ERR_UNSUPPORTED, "MFMA stem: grid too large");
             q.nblocks = (uint32_t)nblocks;
-            const bool a8 = plan.fmt_act == kFmtAct8;
-            if (nt == 4) {
-                if (a8) hipLaunchKernelGGL((k_stem_rows<kFmtAct8, 4>), dim3(q.nblocks), dim3(kSrThreads), lds, stream, q);
-                else hipLaunchKernelGGL((k_stem_rows<kFmtSfp7, 4>), dim3(q.nblocks), dim3(kSrThreads), lds, stream, q);
+            if (yc) {
+                if (a8) launch_stem_rows_t<kFmtAct8, true>(q, nt, lds, stream);
+                else launch_stem_rows_t<kFmtSfp7, true>(q, nt, lds, stream);
             } else {
-                if (a8) hipLaunchKernelGGL((k_stem_rows<kFmtAct8, 6>), dim3(q.nblocks), dim3(kSrThreads), lds, stream, q);
-                else hipLaunchKernelGGL((k_stem_rows<kFmtSfp7, 6>), dim3(q.nblocks), dim3(kSrThreads), lds, stream, q);
+                if (a8) launch_stem_rows_t<kFmtAct8, false>(q, nt, lds, stream);
+                else launch_stem_rows_t<kFmtSfp7, false>(q, nt, lds, stream);
             }
             return check_launch("slfp MFMA stem (rows in LDS) kernel");
         }
@@ -394,7 +499,7 @@ int launch_stem_mfma(const slfp_conv2d_desc& d, const ConvPlan& plan, const floa
     const ScaleDiv sd = make_scale_div(d.ka, 4);
     const unsigned egrid = (unsigned)ceil_div(n_chunks16, 256);
     const int RL = (int)(d.kw * d.c_in);
-    if (plan.fmt_act == kFmtAct8)
+    if (a8)
         hipLaunchKernelGGL((k_stem_im2row<kFmtAct8>), dim3(egrid), dim3(256), 0, stream, x, xe, n_chunks16, (int)d.h, (int)d.w,
                            (int)d.c_in, (int)plan.w_out, d.stride_w, d.pad_w, RL, rp_shift, sd);
     else
@@ -410,10 +515,14 @@ int launch_stem_mfma(const slfp_conv2d_desc& d, const ConvPlan& plan, const floa
     p.segs = (int)ceil_div(p.Wo, 16);
     p.units = (int64_t)p.N * p.Ho * p.segs;
     p.s1 = plan.s1; p.s2 = plan.s2; p.s1x = plan.s1 * (1.0f / 256.0f);
-    const size_t lds = (size_t)p.KS * nt * 1024;
+    size_t lds = (size_t)p.KS * nt * 1024;
+    co.enc_off = (uint32_t)lds;
+    p.co = co;
+    if (yc) lds += (size_t)kEncEntries * 8;   // W <= 150 KiB: room under the 160 KiB limit
     const int occ = (int)std::max<size_t>(1, std::min<size_t>(2, (160 * 1024) / lds));
     const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(p.units, kSmThreads / 64), (int64_t)device_cu_count() * occ);
-    return nt == 4 ? launch_stem_mfma_t<4>(p, lds, grid, stream) : launch_stem_mfma_t<6>(p, lds, grid, stream);
+    if (yc) return nt == 4 ? launch_stem_mfma_t<4, true>(p, lds, grid, stream) : launch_stem_mfma_t<6, true>(p, lds, grid, stream);
+    return nt == 4 ? launch_stem_mfma_t<4, false>(p, lds, grid, stream) : launch_stem_mfma_t<6, false>(p, lds, grid, stream);
 }
 
 }  // namespace slfp

@@ -185,6 +185,17 @@ __device__ __forceinline__ uint32_t enc4_code_relu(const float4 x, const float r
     return d;
 }
 
+// YC kernels with the ReLU folded into the code quantizer: the float32 interface's fmaxf(NaN, 0) is 0, whose code is that of exact
+// zero, while enc4_code_relu gives a NaN the code slfp_encode_f32 gives it (0x00).  NaN -> 0 on a cold branch keeps the bytes equal
+// to slfp_encode_f32 of the float32 interface's output for NaN inputs too.
+__device__ __forceinline__ float4 relu_of_nan4(float4 r) {
+    if (__builtin_expect(enc_has_nan4(r), 0)) {
+        r.x = r.x != r.x ? 0.f : r.x; r.y = r.y != r.y ? 0.f : r.y;
+        r.z = r.z != r.z ? 0.f : r.z; r.w = r.w != r.w ? 0.f : r.w;
+    }
+    return r;
+}
+
 // SFP<3,3> codes carry the sign in bit 6: enc4_code<true> puts it in bit 7; move it.
 template <int FMT, bool SIGNED>
 __device__ __forceinline__ uint32_t enc4_code_fmt(const float4 x, const float r1, const float lo, const float hi,

@@ -186,6 +186,13 @@ void stem_mfma_blob_shape(const slfp_conv2d_desc& d, int* ksub, int* nt);
 size_t stem_mfma_workspace_bytes(const slfp_conv2d_desc& d, int64_t w_out);
 int launch_stem_mfma(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const void* wblob,
                      const float* bias, const PostOp& post, float* y, void* workspace, hipStream_t stream);
+// float32 in -> codes out (the YC forms): C_out a multiple of 16, no channel re-padding, no layer-output quantizer
+bool stem_mfma_codes_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, int post_flags);
+// does the call run k_stem_im2row + k_stem_mfma (workspace needed) instead of k_stem_rows?  The code table counts in the
+// rows form's LDS, so the answer can differ between float32 and code output.
+bool stem_mfma_uses_workspace(const slfp_conv2d_desc& d, bool y_codes);
+int launch_stem_mfma_io(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const void* wblob, const float* bias,
+                        const PostOp& post, void* y_any, void* workspace, const CodeIo& io, hipStream_t stream);
 
 // 3x3-class image stems whose whole contraction is one MFMA k-step (conv_stem_small.hip);
 // wblob = [o/16][64][8] fp16 with k = (kh*KW + kw)*C_in + c

@@ -315,6 +315,19 @@ class CodeMaxPool2d(nn.Module):
         return self.pool(x)
 
 
+class CodeReLU(nn.Module):
+    """An nn.ReLU behind a stem linked by link_stem: the ReLU is folded into the stem's code quantizer, so on uint8 codes the
+    module hands its input through without a launch (torch.relu on codes would be an identity pass over the whole tensor);
+    anything else goes to the original module, which this wrapper keeps (`relu`)."""
+
+    def __init__(self, relu):
+        super().__init__()
+        self.relu = relu
+
+    def forward(self, x):
+        return x if x.dtype == torch.uint8 else self.relu(x)
+
+
 def _poolable(m):
     return (isinstance(m, nn.MaxPool2d) and not m.ceil_mode and not m.return_indices
             and (m.dilation == 1 or m.dilation == (1, 1)))
@@ -534,19 +547,175 @@ def link_codes_traced(model, example_input, entries=False):
 
 
 def unlink_codes(model):
-    """Undo link_codes / link_codes_traced."""
+    """Undo link_codes / link_codes_traced / link_stem."""
     n = 0
     for parent in model.modules():
         for name, child in list(parent._modules.items()):
             if isinstance(child, CodeMaxPool2d):
                 parent._modules[name] = child.pool
+            elif isinstance(child, CodeReLU):
+                parent._modules[name] = child.relu
     for m in model.modules():
         if _is_conv_q(m) and m._code_out is not None:
             m._code_out = None
             m._code_entry = False
+            m.__dict__.pop("_stem_link", None)   # link_stem's record: its pools and ReLUs are unwrapped above
             if hasattr(m, "_pre_link_post"):
                 m._post = m._pre_link_post
                 del m._pre_link_post
+            n += 1
+    return n
+
+
+# ------------------------------------------------------------------ the image stem writes the first code tensor of the net
+def _restore_stem(stem):
+    st = stem.__dict__.pop("_stem_link")
+    stem._post, stem._code_out = stem._pre_link_post, None
+    del stem._pre_link_post
+    for parent, name, pool in st["pools"]:
+        if isinstance(parent._modules.get(name), CodeMaxPool2d) and parent._modules[name].pool is pool:
+            parent._modules[name] = pool
+    for parent, name, relu in st["relus"]:
+        if isinstance(parent._modules.get(name), CodeReLU) and parent._modules[name].relu is relu:
+            parent._modules[name] = relu
+
+
+def link_stem(model, example_input):
+    """The chain of 1-byte codes starts at the image: the large-kernel image stem (7x7 / 11x11, `stem_mfma_*`: ResNet-50,
+    SqueezeNet 1.0, AlexNet) writes the codes of the layer(s) behind it instead of its float32 output -- the largest activation
+    of these nets.  One traced forward on `example_input` finds the stem (the first-executed Conv2d_Q with in_channels <= 4 and a
+    4-d float32 input) and follows its output to every Conv2d_Q that reads it, through nn.Identity (a folded BatchNorm), nn.ReLU
+    modules (in place or not) and nn.MaxPool2d in floor or ceil mode (no return_indices, dilation 1, C % 4 == 0, each run once).
+    The link is made only if every reader is such a conv and no other module takes the tensor, all readers share (Ka, q_bit) --
+    ONE code tensor serves them, as it serves the two expands of a Fire module (ResNet-50's layer1.0.conv1 and
+    layer1.0.downsample.0) --, each reader has a code-input kernel in its present state (linked by link_codes_traced, rewritten by
+    fuse_fire, or plain) and the stem has the code-output kernel (slfp_conv2d_codes_supported).  The stem then gets the ReLU
+    folded, `_code_out` and `_pre_link_post`, the pools become CodeMaxPool2d, the ReLU modules CodeReLU (no pass over the codes), and
+    the model must reproduce its recorded output
+    with torch.equal; otherwise (a functional use hooks cannot see, e.g. a torch.cat) everything is rolled back.  An exception is a
+    refusal too, but an error status of libslfp_hip itself (_lib.SlfpError) is re-raised after the roll-back, as in fuse_fire.
+    Run it after fuse_bn_relu / fuse_named_bn, fuse_fire(entries=True), link_codes_traced(entries=True) and fuse_residual; it
+    composes with all of them and with graph.GraphedModule.  Inference only.  Returns 1 or 0; unlink_stem undoes exactly this
+    link, unlink_codes undoes it as it undoes every link."""
+    from .conv2d_func import _scalar_scale, _supported
+    from . import _lib
+    if model.training or not any(_is_conv_q(m) for m in model.modules()):
+        return 0
+    calls, keep, hooks = [], [], []
+    for m in model.modules():
+        if _is_conv_q(m) or not m._modules:   # leaves; containers only hand their input on
+            def _rec(mod, inp, out):
+                calls.append((mod, inp[0] if inp else None, out))
+                keep.append((inp, out))
+            hooks.append(m.register_forward_hook(_rec))
+    try:
+        with torch.no_grad():
+            y0 = model(example_input)
+    finally:
+        for h in hooks:
+            h.remove()
+    if not torch.is_tensor(y0):
+        return 0
+
+    def same(a, b):   # every recorded tensor is kept alive, so an address names one tensor
+        return a is b or (torch.is_tensor(a) and torch.is_tensor(b) and a.data_ptr() == b.data_ptr() and a.shape == b.shape
+                          and a.dtype == b.dtype and a.stride() == b.stride())
+
+    def eligible(m):
+        return (m.q_bit in (8, 7) and not m.training and isinstance(m.padding, tuple)
+                and (m.bias is None or getattr(m, "_scaled_bias", False)) and not (m._post is not None and (int(m._post[2]) & 2)))
+
+    stem = next((c for c in calls if _is_conv_q(c[0]) and c[0].in_channels <= 4 and torch.is_tensor(c[1]) and c[1].dim() == 4
+                 and c[1].dtype == torch.float32), None)
+    if stem is None or stem is not next(c for c in calls if _is_conv_q(c[0])):
+        return 0
+    stem, x_stem, t0 = stem
+    n_runs = {}
+    for mod, _, _ in calls:
+        n_runs[mod] = n_runs.get(mod, 0) + 1
+    if (n_runs[stem] != 1 or not eligible(stem) or stem._code_out is not None or getattr(stem, "_in_residual", False)
+            or not torch.is_tensor(t0) or t0.dim() != 4):
+        return 0
+    # follow the tensor in execution order: live = [tensor, has a ReLU module run on it or on the way to it]
+    live, readers, pools, relus = [[t0, False]], [], [], []
+
+    def note(t, relu):
+        for e in live:
+            if same(e[0], t):   # nn.Identity, an in-place ReLU: the same tensor again
+                e[1] = e[1] or relu
+                return
+        live.append([t, relu])
+
+    for mod, xin, out in calls[next(i for i, c in enumerate(calls) if c[0] is stem) + 1:]:
+        src = next((e for e in live if same(e[0], xin)), None)
+        if src is None:
+            continue
+        if n_runs[mod] != 1 or not torch.is_tensor(out):
+            return 0
+        if _is_conv_q(mod):
+            readers.append((mod, xin, src[1]))
+        elif isinstance(mod, nn.Identity):
+            note(out, src[1])
+        elif isinstance(mod, nn.ReLU):
+            relus.append(mod)
+            note(out, True)
+        elif (isinstance(mod, nn.MaxPool2d) and not mod.return_indices and _pair2(mod.dilation) == (1, 1)
+              and stem.out_channels % 4 == 0):
+            pools.append(mod)
+            note(out, src[1])
+        else:
+            return 0   # another module takes the tensor
+    if not readers or len({r for _, _, r in readers}) != 1:
+        return 0   # one code tensor: with the ReLU folded for every reader, or for none
+    if len({(float(_scalar_scale(b.Ka, "Ka")), int(b.q_bit)) for b, _, _ in readers}) != 1:
+        return 0
+    b0, _, via_relu = readers[0]
+    out = (float(_scalar_scale(b0.Ka, "Ka")), int(b0.q_bit))
+    flags = (int(stem._post[2]) if stem._post is not None else 0) | (1 if via_relu else 0)
+    for b, xin, _ in readers:
+        bflags = int(b._post[2]) if b._post is not None else 0
+        if (not eligible(b) or xin.dtype != torch.float32 or xin.dim() != 4
+                or not _supported(b, tuple(xin.shape), "codes", True, b._code_out, bflags)):
+            return 0
+    if not _supported(stem, tuple(x_stem.shape), "codes", False, out, flags):
+        return 0
+    st = {"pools": [], "relus": []}
+    stem._pre_link_post = stem._post
+    stem._post = ((stem._post[0], stem._post[1]) if stem._post is not None else (None, None)) + (flags,)
+    stem._code_out = out
+    stem.__dict__["_stem_link"] = st
+    # the pools between the stem and its readers now see codes; the ReLUs (each runs once, on this tensor only) are the quantizer's
+    for parent in [m for m in model.modules() if not isinstance(m, (CodeMaxPool2d, CodeReLU))]:
+        for name, child in list(parent._modules.items()):
+            if any(child is pm for pm in pools):
+                parent._modules[name] = CodeMaxPool2d(child, out[1])
+                st["pools"].append((parent, name, child))
+            elif any(child is rm for rm in relus):
+                parent._modules[name] = CodeReLU(child)
+                st["relus"].append((parent, name, child))
+    calls.clear(); keep.clear()
+    ok = False
+    try:
+        with torch.no_grad():
+            y1 = model(example_input)
+        ok = torch.is_tensor(y1) and y1.dtype == y0.dtype and y1.shape == y0.shape and torch.equal(y1, y0)
+    except _lib.SlfpError:
+        _restore_stem(stem)
+        raise   # libslfp_hip refused or failed a call the support queries had granted: a defect, not an ordinary refusal
+    except Exception:   # e.g. a functional op on the tensor that cannot take codes
+        ok = False
+    if not ok:
+        _restore_stem(stem)
+        return 0
+    return 1
+
+
+def unlink_stem(model):
+    """Undo link_stem."""
+    n = 0
+    for m in list(model.modules()):
+        if "_stem_link" in m.__dict__:
+            _restore_stem(m)
             n += 1
     return n
 

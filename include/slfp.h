@@ -178,8 +178,10 @@ int slfp_dwpw_fwd(const slfp_conv2d_desc* dw, const slfp_conv2d_desc* pw, const 
  * slfp_encode_f32).  Both tensors are NHWC; x, y and wprep 16-byte aligned; wprep is the blob of
  * slfp_conv2d_prepare_weights for the same descriptor.  Supported: 3x3 depthwise (x_codes), 1x1 (x_codes; C_in a
  * multiple of 32, or 16 or 48; C_out a multiple of 16 with y_codes), and the 3x3 stride-2 RGB stem -> 32 channels (float32 in, y_codes):
- * every layer of nets_imgnet/mobilenetv1.py:43-57; the 3x3 RGB stem -> 64 channels of VGG-16 (float32 in, y_codes); dense k x k
- * layers through slfp_conv2d_fwd_codes_ws (below).
+ * every layer of nets_imgnet/mobilenetv1.py:43-57; the 3x3 RGB stem -> 64 channels of VGG-16 (float32 in, y_codes); the
+ * large-kernel image stems of the "stem_mfma_*" family (float32 in, y_codes; C_out a multiple of 16: ResNet-50's 7x7 s2 3 -> 64,
+ * SqueezeNet's 7x7 s2 3 -> 96, AlexNet's 11x11 s4 3 -> 64) -- the stems that keep their encoded rows in LDS here, the others
+ * (AlexNet's, odd stride * C_in) through slfp_conv2d_fwd_codes_ws; dense k x k layers through slfp_conv2d_fwd_codes_ws (below).
  * slfp_conv2d_codes_supported answers 1 / 0 without device work. */
 typedef struct slfp_conv2d_io {
     int32_t x_codes;  /* 0: x is float32 (as slfp_conv2d_fwd); 1: x is uint8 codes of QA(. / d->ka), format of d->qbits */
@@ -193,7 +195,8 @@ int slfp_conv2d_fwd_codes(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, c
                           const float* bias, const float* post_scale, const float* post_shift, int relu, void* y,
                           void* stream);
 /* The same with a workspace, for the layers whose float32 form needs one: dense k x k convolutions on the matrix cores
- * (VGG-16 / ResNet-50 3x3, SqueezeNet expand3x3; x_codes and / or y_codes; C_out a multiple of 16 with y_codes).  `workspace`:
+ * (VGG-16 / ResNet-50 3x3, SqueezeNet expand3x3; x_codes and / or y_codes; C_out a multiple of 16 with y_codes) and the
+ * large-kernel image stems that run as two kernels (the im2row copy lies in it; float32 in, y_codes).  `workspace`:
  * slfp_conv2d_workspace_bytes(d) bytes, 16-byte aligned; may be NULL for the layers slfp_conv2d_fwd_codes takes.  The codes
  * are decoded into the same fp16 operand copy the float32 interface builds from its input: results are bit-identical. */
 int slfp_conv2d_fwd_codes_ws(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
