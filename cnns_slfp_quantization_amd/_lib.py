@@ -33,6 +33,7 @@ SYMBOLS = (
     "slfp_conv2d_res_supported", "slfp_conv2d_fwd_res",
     "slfp_conv2d_codes_slice_supported", "slfp_conv2d_fwd_codes_slice", "slfp_maxpool2d_codes_ex", "slfp_maxpool2d_out_shape",
     "slfp_conv2d_entry_supported", "slfp_conv2d_fwd_entry",
+    "slfp_conv2d_res_codes_supported", "slfp_conv2d_fwd_res_codes",
 )
 
 
@@ -140,6 +141,8 @@ def load():
         "slfp_maxpool2d_out_shape": (ci, [i64, i64, ci, ci, ci, ci, ci, ci, ci, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
         "slfp_conv2d_entry_supported": (ci, [dp, ctypes.POINTER(ConvIo), ci, ci]),
         "slfp_conv2d_fwd_entry": (ci, [dp, ctypes.POINTER(ConvIo), vp, vp, vp, vp, vp, ci, vp, vp]),
+        "slfp_conv2d_res_codes_supported": (ci, [dp, ctypes.POINTER(ConvIo), ci, ci]),
+        "slfp_conv2d_fwd_res_codes": (ci, [dp, ctypes.POINTER(ConvIo), vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp]),
     }
     assert set(sigs) == set(SYMBOLS)
     for name, (res, args) in sigs.items():

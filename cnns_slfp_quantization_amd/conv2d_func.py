@@ -223,6 +223,7 @@ _KINDS = {
     "slice": ("slfp_conv2d_codes_slice_supported", "slfp_conv2d_fwd_codes_slice"),  # codes into a channel slice of a wider tensor
     "entry": ("slfp_conv2d_entry_supported", "slfp_conv2d_fwd_entry"),              # float32 in, codes out, pointwise
     "res": ("slfp_conv2d_res_supported", "slfp_conv2d_fwd_res"),                    # a residual operand in the epilogue
+    "res_codes": ("slfp_conv2d_res_codes_supported", "slfp_conv2d_fwd_res_codes"),  # the same, and the next block's codes next to y
 }
 
 
@@ -256,7 +257,7 @@ def _plan(mod, x, weight, nhwc_in, nhwc_out, codes=None):
     """Everything that depends only on (module geometry, input shape, layouts, scales, precision) is computed once per
     distinct key and kept on the module: descriptor, output shape, workspace size, kernel name.  codes: None for the
     float32 interface, else (kind of _KINDS, does x hold codes, mod._code_out or None, extra) with extra = the channel count of the
-    wider tensor for "slice", whether a ReLU follows the add for "res"."""
+    wider tensor for "slice", whether a ReLU follows the add for "res" and "res_codes" (whose `out` is mod._trunk_code_out)."""
     shape = x.shape
     key = (codes, shape, nhwc_in, nhwc_out, _scale_key(mod.Ka, "Ka"), _scale_key(mod.Kw, "Kw"), options.mfma_passes,
            mod.stride, mod.padding, mod.dilation, weight.shape)
@@ -275,15 +276,15 @@ def _plan(mod, x, weight, nhwc_in, nhwc_out, codes=None):
             kind, x_codes, out, extra = codes
             flags = int(mod._post[2]) if mod._post is not None else 0
             plan.kind, plan.io = kind, _conv_io(x_codes, out)
-            if kind == "res":
+            if kind in ("res", "res_codes"):
                 # an epilogue ReLU or layer-output quantizer would sit BEFORE the add: not what the residual kernels compute
-                plan.ok = flags == 0 and _supported(mod, shape, kind, x_codes, None, 1 if extra else 0, desc=d, io=plan.io)
+                plan.ok = flags == 0 and _supported(mod, shape, kind, x_codes, out, 1 if extra else 0, desc=d, io=plan.io)
             else:
                 plan.ok = _supported(mod, shape, kind, x_codes, out, flags, extra, d, plan.io)
             if kind == "entry" or (kind == "codes" and not plan.ok):
                 plan.ws_bytes = 0   # pointwise: no workspace; refused: the float32 interface's own plan sizes its workspace
-            plan.label += (("+codes_in" if x_codes else "") + ("+codes_out" if out is not None else "")
-                           + {"slice": "+slice", "res": "+res"}.get(kind, ""))
+            plan.label += (("+codes_in" if x_codes else "") + ("+codes_out" if out is not None and kind != "res_codes" else "")
+                           + {"slice": "+slice", "res": "+res", "res_codes": "+res+trunk_codes"}.get(kind, ""))
         if len(mod._plans) >= 64:   # a net fed ever-changing shapes: do not grow without bound
             mod._plans.clear()
         mod._plans[key] = plan
@@ -333,7 +334,8 @@ def _workspace(device, nbytes):
 def _launch(mod, plan, x, weight, bias, y=None, cache=True, res=None, relu=None, y_ld=None):
     """The one call into libslfp_hip of a Conv2d_Q forward: plan.kind's entry point (_KINDS) on input `x`.  y: the output tensor --
     allocated here (channels_last; uint8 where the plan's io writes codes) when None -- or, for "slice", the address of the
-    slice's first channel in a y_ld-channel tensor; "res": + `res`, with `relu` behind the add.  Does the device guard, the
+    slice's first channel in a y_ld-channel tensor; "res" / "res_codes": + `res`, with `relu` behind the add ("res_codes": y is float32
+    and the codes go into a uint8 tensor of their own, returned with y as a pair).  Does the device guard, the
     stream, the module's weight blob (cache: it may come from the module's cache), the epilogue arguments and the workspace, then
     the module's bookkeeping: `_last_kernel`, exactly one of `_last_input` / `_last_codes`, and `_input_q` (stored by the float32
     interface under options.eager_stash, otherwise made on first read).  Returns y."""
@@ -344,8 +346,10 @@ def _launch(mod, plan, x, weight, bias, y=None, cache=True, res=None, relu=None,
         # cache the prepared weights only where they cannot change unseen: inference (see the module docstring)
         blob = _conv_weights(mod, d, weight, stream, cache, plan.kernel, want_weight_q=stash)
         if y is None:
-            y = torch.empty(plan.y_shape, dtype=torch.uint8 if plan.io.y_codes else torch.float32, device=x.device,
-                            memory_format=torch.channels_last)
+            y = torch.empty(plan.y_shape, dtype=torch.uint8 if plan.io.y_codes and kind != "res_codes" else torch.float32,
+                            device=x.device, memory_format=torch.channels_last)
+        yc = (torch.empty(plan.y_shape, dtype=torch.uint8, device=x.device, memory_format=torch.channels_last)
+              if kind == "res_codes" else None)
         ws = _workspace(x.device, plan.ws_bytes) if plan.ws_bytes else None
         b, ps, psh, flags = _epilogue_args(mod, bias, x.device)
         xq = torch.empty_like(x) if stash else None
@@ -356,6 +360,8 @@ def _launch(mod, plan, x, weight, bias, y=None, cache=True, res=None, relu=None,
             args = (ctypes.byref(d), ctypes.byref(plan.io)) + head + (flags, y, y_ld, _ptr(ws))
         elif kind == "res":
             args = (ctypes.byref(d), ctypes.byref(plan.io)) + head + (1 if relu else 0, res.data_ptr(), y.data_ptr(), None)
+        elif kind == "res_codes":
+            args = (ctypes.byref(d), ctypes.byref(plan.io)) + head + (1 if relu else 0, res.data_ptr(), y.data_ptr(), yc.data_ptr(), None)
         else:   # "codes" takes a workspace, "entry" does not
             args = (ctypes.byref(d), ctypes.byref(plan.io)) + head + (flags, y.data_ptr()) + ((_ptr(ws),) if kind == "codes" else ())
         _lib.check(getattr(_lib.load(), _KINDS[kind][1])(*args, stream.cuda_stream))
@@ -363,7 +369,7 @@ def _launch(mod, plan, x, weight, bias, y=None, cache=True, res=None, relu=None,
     # plain attributes, written in one go (nn.Module.__setattr__ costs microseconds per name, on every layer of every forward)
     mod.__dict__.update(_last_kernel=plan.label, _last_input=None if x_codes else x.detach(),
                         _last_codes=x.detach() if x_codes else None, _input_q=xq)
-    return y
+    return y if yc is None else (y, yc)
 
 
 def _hip_conv2d(mod, x, weight, bias, cache_ok=False):
@@ -445,24 +451,34 @@ def _hip_conv2d_slice(mod, x, weight, bias, out_slice):
     return buf
 
 
-def _hip_conv2d_res(mod, x, weight, bias, residual, relu):
+def _hip_conv2d_res(mod, x, weight, bias, residual, relu, trunk=None):
     """Conv2d_Q.forward(x, residual=r) as ONE slfp_conv2d_fwd_res call: relu?(epilogue(conv(x)) + r), bit-identical to the
     module's ordinary forward followed by torch.add and torch.relu.  `x` is float32 or the uint8 codes a linked producer
     wrote for this module.  Returns None where the library has no residual kernel for the combination (layer geometry,
-    layouts, an epilogue ReLU in front of the add): the caller then computes the same values with ATen."""
+    layouts, an epilogue ReLU in front of the add): the caller then computes the same values with ATen.
+    trunk = (Ka, q_bit) of the Conv2d_Q layers that read the result (mod._trunk_code_out, fusion.link_trunk): where
+    slfp_conv2d_res_codes_supported says yes the ONE call is slfp_conv2d_fwd_res_codes, which also writes those readers' codes; the
+    float32 tensor returned -- the same bits -- then carries them as `_trunk_codes = (codes, Ka, q_bit)`.  An attribute of that one
+    tensor object: whatever an op makes of it has none, and a reader checks the scale before it decodes (Conv2d_Q.forward)."""
     x_codes = x.dtype == torch.uint8
     nhwc = torch.channels_last
     if not (x.is_cuda and x.dim() == 4 and (x_codes or x.dtype == torch.float32) and x.is_contiguous(memory_format=nhwc)
             and weight.device == x.device):
         return None
-    plan = _plan(mod, x, weight, True, True, ("res", x_codes, None, bool(relu)))
+    plan = _plan(mod, x, weight, True, True, ("res_codes", x_codes, trunk, bool(relu))) if trunk is not None and x_codes else None
+    if plan is None or not plan.ok:
+        plan = _plan(mod, x, weight, True, True, ("res", x_codes, None, bool(relu)))
     if not plan.ok:
         return None
     r = residual
     if not (torch.is_tensor(r) and r.dtype == torch.float32 and r.device == x.device and tuple(r.shape) == tuple(plan.y_shape)
             and r.is_contiguous(memory_format=nhwc) and r.data_ptr() % 16 == 0):
         return None
-    return _launch(mod, plan, x, weight, bias, res=r, relu=relu)   # the same blob (and cache entry) as the other paths
+    out = _launch(mod, plan, x, weight, bias, res=r, relu=relu)   # the same blob (and cache entry) as the other paths
+    if plan.kind == "res_codes":
+        out, codes = out
+        out._trunk_codes = (codes, trunk[0], trunk[1])
+    return out
 
 
 def _aligned(t):
@@ -611,6 +627,8 @@ def _conv_class(q_bit, Kw, Ka, bias_default, scaled_bias):
             self._post = None  # (scale, shift, relu): fused eval-BN + ReLU epilogue (fusion.fuse_bn_relu)
             self._code_out = None   # (Ka, q_bit) of the next Conv2d_Q: hand it 1-byte codes (fusion.link_codes)
             self._code_entry = False   # with _code_out on a float32 input: ONE slfp_conv2d_fwd_entry launch where the library has it
+            self._trunk_code_out = None   # forward(x, residual=r): (Ka, q_bit) of the Conv2d_Q layers that read the result; it then
+                                          # carries their codes (fusion.link_trunk).  Not `_code_out`: the result stays float32
             self._last_codes = None
             self.residual_relu = False   # forward(x, residual=r): a ReLU follows the add (fusion.fuse_residual sets it)
             self._scaled_bias = scaled_bias
@@ -656,7 +674,7 @@ def _conv_class(q_bit, Kw, Ka, bias_default, scaled_bias):
                     and (self.bias is None or scaled_bias)):
                 if self._grouped_stash:
                     self._grouped_stash = False
-                out = _hip_conv2d_res(self, input, self.weight, self.bias, residual, self.residual_relu)
+                out = _hip_conv2d_res(self, input, self.weight, self.bias, residual, self.residual_relu, self._trunk_code_out)
             if out is None:   # training, NCHW, q_bit 32, a layer without a residual kernel: the same values with ATen
                 out = self.forward(input, order) + residual
                 if self.residual_relu:
@@ -687,11 +705,18 @@ def _conv_class(q_bit, Kw, Ka, bias_default, scaled_bias):
             residual block.  In inference on channels_last ROCm tensors, where libslfp_hip has a residual kernel for the
             layer, that is ONE launch (slfp_conv2d_fwd_res; `_last_kernel` then ends in "+res"); otherwise the add and the
             ReLU run as ATen ops after the ordinary forward.  Both give the same bits.  With a residual `self.output` is
-            the tensor AFTER the add (and ReLU), not the convolution's own output."""
+            the tensor AFTER the add (and ReLU), not the convolution's own output.  With `_trunk_code_out` set (fusion.link_trunk)
+            and code input the launch is slfp_conv2d_fwd_res_codes (`_last_kernel` ends in "+codes_in+res+trunk_codes"): the same
+            float32 tensor, which also carries the 1-byte codes of the layers that read it."""
             if residual is not None:
                 return self._forward_residual(input, order, residual)
             if self._grouped_stash:
                 self._grouped_stash = False
+            tc = input.__dict__.get("_trunk_codes") if type(input) is torch.Tensor else None
+            if tc is not None and not self.training and self.q_bit in (8, 7) and tc[1:] == (float(self.Ka), self.q_bit):
+                # the float32 trunk of a block linked by fusion.link_trunk carries the codes written for THIS module's present
+                # quantizer: read those (a stale or foreign scale is never decoded: the float32 tensor is read instead)
+                input = tc[0]
             if self.q_bit == 32:
                 # identity quantizers (utils/sfp_quant.py:11-12, :60-61): stock ATen, any device
                 self._input_q = input / self.Ka

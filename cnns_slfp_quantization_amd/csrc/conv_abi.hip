@@ -399,13 +399,23 @@ static bool res_route(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, bool 
     return p.family == kPointwise && d->stride_h == 1 && d->stride_w == 1 && codes_route(d, &cio, has_bias, relu, p) == kRoutePwc;
 }
 
+// The residual epilogue on codes that also writes the next block's codes (slfp_conv2d_fwd_res_codes): exactly where the residual route
+// takes the layer with code input and float32 output, C_out is whole 16-channel tiles and the reader's quantizer has a code table.  A
+// query and an entry point of their own: slfp_conv2d_res_supported keeps refusing y_codes.
+static bool res_codes_route(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, bool has_bias, int relu, const ConvPlan& p) {
+    if (io->x_codes != 1 || io->y_codes != 1 || d->c_out % 16 != 0 || !consumer_quant_ok(io)) return false;
+    const slfp_conv2d_io rio{1, 0, 1.f, 8};
+    return res_route(d, &rio, has_bias, relu, p) && enc_table(io->y_ka, y_fmt_of(io->y_qbits), kEncCode)->valid;
+}
+
 // ---- the one argument check of the forward entry points ----
 struct FwdArgs {   // what a forward entry point was handed; io / res / y_ld / workspace: null or 0 where it has none
     const slfp_conv2d_desc* d; const slfp_conv2d_io* io;
     const void* x; const void* wprep; const float* bias; const float* post_scale; const float* post_shift; int relu;
     void* y; const float* res; int64_t y_ld; void* workspace;
+    void* y_codes = nullptr;   // slfp_conv2d_fwd_res_codes: the second, uint8 output
 };
-enum FwdKind { kFwdPost, kFwdCodes, kFwdSlice, kFwdEntry, kFwdRes };
+enum FwdKind { kFwdPost, kFwdCodes, kFwdSlice, kFwdEntry, kFwdRes, kFwdResCodes };
 struct Resolved { ConvPlan p; PostOp post; CodeIo cio; CodeRoute route; };
 
 static int need_workspace(const char* fn, const FwdArgs& a, const ConvPlan& p) {
@@ -423,7 +433,8 @@ static int resolve(FwdKind kind, const char* fn, const FwdArgs& a, Resolved* r) 
     if (kind != kFwdPost && (!d || !io)) return fail(SLFP_ERR_BAD_ARG, "%s: null descriptor", fn);
     const int rc = make_plan(d, &r->p);
     if (rc != SLFP_OK) return rc;
-    if (!a.x || !a.wprep || !a.y || (kind == kFwdRes && !a.res)) return fail(SLFP_ERR_BAD_ARG, "%s: null pointer", fn);
+    const bool with_res = kind == kFwdRes || kind == kFwdResCodes;
+    if (!a.x || !a.wprep || !a.y || (with_res && !a.res) || (kind == kFwdResCodes && !a.y_codes)) return fail(SLFP_ERR_BAD_ARG, "%s: null pointer", fn);
     const bool has_bias = a.bias != nullptr;
     r->route = kRouteNone;
     if (kind == kFwdSlice) {   // the slice's own arguments come first
@@ -447,6 +458,7 @@ static int resolve(FwdKind kind, const char* fn, const FwdArgs& a, Resolved* r) 
     }
     if (!aligned16(a.x) || !aligned16(a.y) || !aligned16(a.wprep) || !aligned16(a.bias) || !aligned16(a.res))
         return fail(SLFP_ERR_ALIGNMENT, "%s: x, y, wprep, bias and res must be 16-byte aligned", fn);
+    if (!aligned16(a.y_codes)) return fail(SLFP_ERR_ALIGNMENT, "%s: y_codes must be 16-byte aligned", fn);
     r->post = PostOp{a.post_scale, a.post_shift, (a.relu & SLFP_POST_RELU) ? 1 : 0, (kind == kFwdPost && (a.relu & SLFP_POST_LAYEROUT)) ? 1 : 0};
     if (kind == kFwdPost) return need_workspace(fn, a, r->p);
     r->cio = CodeIo{io->x_codes != 0, io->y_codes != 0, io->y_ka, y_fmt_of(io->y_qbits), a.y_ld};
@@ -462,10 +474,19 @@ static int resolve(FwdKind kind, const char* fn, const FwdArgs& a, Resolved* r) 
                                               "(slfp_conv2d_entry_supported); use slfp_conv2d_fwd_post and slfp_encode_f32", fn);
         return SLFP_OK;
     }
-    if (kind == kFwdRes) {   // res is read while y is written, in a different order by different workgroups: the two must not overlap
+    if (with_res) {   // res is read while y is written, in a different order by different workgroups: the two must not overlap
         const uintptr_t nbytes = (uintptr_t)d->n * (uintptr_t)d->c_out * (uintptr_t)r->p.h_out * (uintptr_t)r->p.w_out * sizeof(float);
         const uintptr_t ra = reinterpret_cast<uintptr_t>(a.res), ya = reinterpret_cast<uintptr_t>(a.y);
         if (ra < ya + nbytes && ya < ra + nbytes) return fail(SLFP_ERR_BAD_ARG, "%s: res and y overlap", fn);
+        if (kind == kFwdResCodes) {   // nor may the code tensor (1 B per element) lie in either of them
+            const uintptr_t ca = reinterpret_cast<uintptr_t>(a.y_codes), cbytes = nbytes / sizeof(float);
+            if ((ca < ya + nbytes && ya < ca + cbytes) || (ca < ra + nbytes && ra < ca + cbytes))
+                return fail(SLFP_ERR_BAD_ARG, "%s: y_codes overlaps y or res", fn);
+            if (!res_codes_route(d, io, has_bias, a.relu, r->p))
+                return fail(SLFP_ERR_UNSUPPORTED, "%s: this layer / io combination has no residual kernel that also writes codes "
+                                                  "(slfp_conv2d_res_codes_supported); use slfp_conv2d_fwd_res and slfp_encode_f32", fn);
+            return SLFP_OK;
+        }
         if (!res_route(d, io, has_bias, a.relu, r->p))
             return fail(SLFP_ERR_UNSUPPORTED, "%s: this layer / io combination has no residual kernel "
                                               "(slfp_conv2d_res_supported); use slfp_conv2d_fwd_post and add the residual afterwards", fn);
@@ -588,6 +609,11 @@ int slfp_conv2d_res_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* i
     return d && io && make_plan(d, &p) == SLFP_OK && res_route(d, io, has_bias != 0, relu, p);
 }
 
+int slfp_conv2d_res_codes_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int relu) {
+    ConvPlan p;
+    return d && io && make_plan(d, &p) == SLFP_OK && res_codes_route(d, io, has_bias != 0, relu, p);
+}
+
 int slfp_conv2d_fwd_codes(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
                           const float* bias, const float* post_scale, const float* post_shift, int relu, void* y, void* stream) {
     return slfp_conv2d_fwd_codes_ws(d, io, x, wprep, bias, post_scale, post_shift, relu, y, nullptr, stream);
@@ -632,6 +658,19 @@ int slfp_conv2d_fwd_res(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, con
     if (!io->x_codes) return launch_pointwise(*d, r.p, reinterpret_cast<const float*>(x), wprep, bias, r.post, y, st, res);
     const CodeIo codes_in{true, false, 1.f, kFmtAct8};
     return launch_pwc(*d, r.p, reinterpret_cast<const uint8_t*>(x), wprep, bias, r.post, y, codes_in, st, res);
+}
+
+int slfp_conv2d_fwd_res_codes(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
+                              const float* bias, const float* post_scale, const float* post_shift, int relu,
+                              const float* res, float* y, void* y_codes, void* workspace, void* stream) {
+    (void)workspace;
+    const FwdArgs a{d, io, x, wprep, bias, post_scale, post_shift, relu, y, res, 0, nullptr, y_codes};
+    Resolved r;
+    const int rc = resolve(kFwdResCodes, "slfp_conv2d_fwd_res_codes", a, &r);
+    if (rc != SLFP_OK) return rc;
+    // float32 out as slfp_conv2d_fwd_res launches it; y_ka / y_fmt describe the reader of y_codes
+    const CodeIo codes_in{true, false, io->y_ka, y_fmt_of(io->y_qbits)};
+    return launch_pwc(*d, r.p, reinterpret_cast<const uint8_t*>(x), wprep, bias, r.post, y, codes_in, as_stream(stream), res, y_codes);
 }
 
 }  // extern "C"

@@ -22,6 +22,8 @@
 // k_pwc_tiled (W fragments streamed from L2, X tile decoded once into the swizzled LDS image).
 // The float32-output forms of all three take a residual operand (RES; slfp_conv2d_fwd_res with io->x_codes = 1): conv3 of a
 // ResNet block that reads conv2's codes and adds the float32 trunk, as in conv_pw.hip.
+// The residual forms have a DUAL form each (slfp_conv2d_fwd_res_codes): the float32 trunk is stored as before and the value is also
+// coded for the NEXT block's quantizer into a second, uint8 tensor, so the next conv1 / downsample.0 never read the float32 trunk.
 #include "slfp_device.hpp"
 #include "slfp_enc.hpp"
 #include "slfp_codes.hpp"
@@ -47,6 +49,8 @@ struct PwcParams {
     PostOp post;
     EncArgs enc;          // YC: code table of the consumer's Ka (kEncCode)
     int y_ld;             // YC: bytes from one pixel's codes to the next (N: a dense tensor; more: a channel slice of a wider one)
+    uint8_t* yc;          // DUAL (RES kernels, slfp_conv2d_fwd_res_codes): the second, uint8 output, NHWC, N bytes per pixel; sgn / fmt_out / enc
+                          // describe its reader as they do for YC; nullptr otherwise
 };
 
 typedef uint32_t u32x4c __attribute__((ext_vector_type(4)));
@@ -76,18 +80,22 @@ constexpr int kPwcThreads = 512;
 // k-step exist.  Its second dword -- channels 16..31, which would be the NEXT pixel's codes, or past the tensor for the last
 // pixel -- is not loaded: that half of the fragment is the fp16 zero (the blob holds zero weights there; the float32
 // interface's k_pw_stream feeds the same zeros), so the accumulators are the same bit for bit.
-template <int FMT, int KS, bool XW, bool YC, bool RES = false, bool HALF = false>
+// DUAL (RES only, N a multiple of 16; slfp_conv2d_fwd_res_codes): the finished float32 value -- after the add and the ReLU -- is stored as
+// in the RES form AND coded for the next block's quantizer (p.enc / p.sgn / p.fmt_out, as YC) into p.yc: the 4 tiles of a group are
+// swept as before, their code dwords go through rows_transpose4 and leave as one 16-byte store per lane.
+template <int FMT, int KS, bool XW, bool YC, bool RES = false, bool HALF = false, bool DUAL = false>
 __global__ __launch_bounds__(kPwcThreads) void k_pwc_stream(const PwcParams p) {
     static_assert(!XW || KS % 2 == 0, "16-byte code loads cover two k-steps");
     static_assert(!RES || !YC, "residual operand: float32 output only");
     static_assert(!HALF || !XW, "a half-live last k-step is loaded dword by dword");
+    static_assert(!DUAL || RES, "the second, code output belongs to the residual forms");
     __shared__ __attribute__((aligned(16))) uint32_t sdec[256];
-    __shared__ __attribute__((aligned(16))) unsigned char senc[YC ? kPwTab : 16];
+    __shared__ __attribute__((aligned(16))) unsigned char senc[(YC || DUAL) ? kPwTab : 16];
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     _Float16* wl = reinterpret_cast<_Float16*>(smem);
     const int wfrags = p.n_tiles * p.KS;  // 1 KiB each
     dec_fill<FMT, kDecF16D, kPwcThreads>(sdec);
-    if constexpr (YC) enc_fill<kPwcThreads>(reinterpret_cast<uint2*>(senc), p.enc);
+    if constexpr (YC || DUAL) enc_fill<kPwcThreads>(reinterpret_cast<uint2*>(senc), p.enc);
     for (int i = threadIdx.x; i < wfrags * 64; i += kPwcThreads)
         reinterpret_cast<half8*>(wl)[i] = reinterpret_cast<const half8*>(p.whi)[i];
     float* ep = reinterpret_cast<float*>(smem + (size_t)wfrags * 1024);   // [256 * bias/s1/s2 | post scale | post shift]
@@ -191,20 +199,43 @@ __global__ __launch_bounds__(kPwcThreads) void k_pwc_stream(const PwcParams p) {
             const float* rrow = (RES ? p.res : reinterpret_cast<const float*>(p.y)) + (size_t)(live ? m : p.M - 1) * p.N;
             float4 rn;
             if constexpr (RES) rn = ld_stream4<SLFP_NT_PW_RES>(rrow + (kq * 4 < p.N ? kq * 4 : 0));
-            for (int j = 0; j < p.n_tiles; ++j) {
-                float4 rc;
-                if constexpr (RES) {
-                    rc = rn;
-                    const int n1 = (j + 1) * 16 + kq * 4;
-                    rn = ld_stream4<SLFP_NT_PW_RES>(rrow + (n1 < p.N ? n1 : 0));
+            if constexpr (DUAL) {
+                uint8_t* ycr = p.yc + (size_t)m * p.N;
+                for (int j0 = 0; j0 < p.n_tiles; j0 += 4) {   // n_tiles is a multiple of 4 (the blob is padded to 64 channels)
+                    uint32_t c[4];
+#pragma unroll
+                    for (int jj = 0; jj < 4; ++jj) {
+                        const int j = j0 + jj;
+                        const float4 rc = rn;
+                        const int n1 = (j + 1) * 16 + kq * 4;
+                        rn = ld_stream4<SLFP_NT_PW_RES>(rrow + (n1 < p.N ? n1 : 0));
+                        const float4 r = res_add(tile_out(j), rc, p.post.relu);
+                        if (live && j * 16 + kq * 4 < p.N) *reinterpret_cast<float4*>(yr + j * 16) = r;
+                        // the codes of the value just stored (the ReLU, where there is one, has run: enc4_code_relu sees r >= 0)
+                        if (p.sgn) c[jj] = code_sign4(enc4_code<false>(r, r1, lo, hi, senc), r, p.fmt_out);
+                        else c[jj] = enc4_code_relu(r, r1, lo, hi, senc);
+                    }
+                    rows_transpose4(c[0], c[1], c[2], c[3]);   // lane-quarter kq now holds channels 16 (j0 + kq) + 0..15
+                    const int n = (j0 + kq) * 16;
+                    if (live && n < p.N) *reinterpret_cast<u32x4c*>(ycr + n) = u32x4c{c[0], c[1], c[2], c[3]};
                 }
-                float4 r = tile_out(j);
-                if constexpr (RES) r = res_add(r, rc, p.post.relu);
-                if (live && j * 16 + kq * 4 < p.N) *reinterpret_cast<float4*>(yr + j * 16) = r;
+            } else {
+                for (int j = 0; j < p.n_tiles; ++j) {
+                    float4 rc;
+                    if constexpr (RES) {
+                        rc = rn;
+                        const int n1 = (j + 1) * 16 + kq * 4;
+                        rn = ld_stream4<SLFP_NT_PW_RES>(rrow + (n1 < p.N ? n1 : 0));
+                    }
+                    float4 r = tile_out(j);
+                    if constexpr (RES) r = res_add(r, rc, p.post.relu);
+                    if (live && j * 16 + kq * 4 < p.N) *reinterpret_cast<float4*>(yr + j * 16) = r;
+                }
             }
         }
     }
 }
+
 
 // ======================================================================================
 // k_pwc_slice: deep layers (K = 256 ... 1024).  W does not fit LDS, but a SLICE of output channels does: a workgroup keeps
@@ -224,15 +255,18 @@ __global__ __launch_bounds__(kPwcThreads) void k_pwc_stream(const PwcParams p) {
 // RES (float32 out): y = relu?(affine(conv) + res); the first RP tiles' 16-byte pieces of p.res are requested before the unit's K
 // sweep, RP more right after it (in the registers the decoded X fragments leave), then one per tile stored: the kernel has to
 // stay within 128 VGPRs (two workgroups per CU).
+// DUAL (RES only): as in k_pwc_stream, the codes of the stored value leave per group of 4 tiles.
 constexpr int kSliceThreads = 512;
-template <int FMT, int NTS, bool YC, bool RES = false>
-__global__ __launch_bounds__(kSliceThreads, RES ? 4 : 1) void k_pwc_slice(const PwcParams p) {   // RES: 4 waves per SIMD = the 128 VGPRs of two workgroups per CU
+constexpr int kSliceDualWaves = 4;   // DUAL: fits the 128 VGPRs too
+template <int FMT, int NTS, bool YC, bool RES = false, bool DUAL = false>
+__global__ __launch_bounds__(kSliceThreads, RES ? (DUAL ? kSliceDualWaves : 4) : 1) void k_pwc_slice(const PwcParams p) {   // RES: 4 waves per SIMD = the 128 VGPRs of two workgroups per CU
     static_assert(!RES || !YC, "residual operand: float32 output only");
+    static_assert(!DUAL || RES, "the second, code output belongs to the residual forms");
     constexpr int KC = 8;   // k-steps per chunk = 256 channels = 4 x 16-byte code loads per lane
     constexpr int RP = 2;   // RES: residual pieces in flight under the K sweep
     static_assert(NTS % 4 == 0, "code output leaves in groups of 4 channel tiles");
     __shared__ __attribute__((aligned(16))) uint32_t sdec[256];
-    __shared__ __attribute__((aligned(16))) unsigned char senc[YC ? kPwTab : 16];
+    __shared__ __attribute__((aligned(16))) unsigned char senc[(YC || DUAL) ? kPwTab : 16];
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     _Float16* wl = reinterpret_cast<_Float16*>(smem);
     const int n_slices = p.n_tiles / NTS;
@@ -243,7 +277,7 @@ __global__ __launch_bounds__(kSliceThreads, RES ? 4 : 1) void k_pwc_slice(const 
     const int n_ranks = 8 * ((int)(gridDim.x >> 3) / n_slices);
     const int wfrags = NTS * p.KS;  // 1 KiB each
     dec_fill<FMT, kDecF16D, kSliceThreads>(sdec);
-    if constexpr (YC) enc_fill<kSliceThreads>(reinterpret_cast<uint2*>(senc), p.enc);
+    if constexpr (YC || DUAL) enc_fill<kSliceThreads>(reinterpret_cast<uint2*>(senc), p.enc);
     {
         const half8* src = reinterpret_cast<const half8*>(p.whi) + (size_t)slice * wfrags * 64;
         for (int i = threadIdx.x; i < wfrags * 64; i += kSliceThreads) reinterpret_cast<half8*>(wl)[i] = src[i];
@@ -362,18 +396,39 @@ __global__ __launch_bounds__(kSliceThreads, RES ? 4 : 1) void k_pwc_slice(const 
 #pragma unroll
                 for (int j = RP; j < 2 * RP && j < NTS; ++j) rq[j] = res_at(j);
             }
+            if constexpr (DUAL) {
+                uint8_t* ycr = p.yc + (size_t)m * p.N + n_lo;
 #pragma unroll
-            for (int j = 0; j < NTS; ++j) {
-                float4 r = finish(j);
-                if constexpr (RES) {
-                    r = res_add(r, rq[j], p.post.relu);
-                    if (j + 2 * RP < NTS) rq[j + 2 * RP] = res_at(j + 2 * RP);   // 2 RP pieces in flight: the consumed one's registers
+                for (int j0 = 0; j0 < NTS; j0 += 4) {
+                    uint32_t c[4];
+#pragma unroll
+                    for (int jj = 0; jj < 4; ++jj) {
+                        const int j = j0 + jj;
+                        const float4 r = res_add(finish(j), rq[j], p.post.relu);
+                        if (j + 2 * RP < NTS) rq[j + 2 * RP] = res_at(j + 2 * RP);
+                        if (live && n_lo + j * 16 + kq * 4 < p.N) *reinterpret_cast<float4*>(yr + j * 16) = r;
+                        if (p.sgn) c[jj] = code_sign4(enc4_code<false>(r, r1, lo, hi, senc), r, p.fmt_out);
+                        else c[jj] = enc4_code_relu(r, r1, lo, hi, senc);
+                    }
+                    rows_transpose4(c[0], c[1], c[2], c[3]);
+                    const int n = (j0 + kq) * 16;
+                    if (live && n_lo + n < p.N) *reinterpret_cast<u32x4c*>(ycr + n) = u32x4c{c[0], c[1], c[2], c[3]};
                 }
-                if (live && n_lo + j * 16 + kq * 4 < p.N) *reinterpret_cast<float4*>(yr + j * 16) = r;
+            } else {
+#pragma unroll
+                for (int j = 0; j < NTS; ++j) {
+                    float4 r = finish(j);
+                    if constexpr (RES) {
+                        r = res_add(r, rq[j], p.post.relu);
+                        if (j + 2 * RP < NTS) rq[j + 2 * RP] = res_at(j + 2 * RP);   // 2 RP pieces in flight: the consumed one's registers
+                    }
+                    if (live && n_lo + j * 16 + kq * 4 < p.N) *reinterpret_cast<float4*>(yr + j * 16) = r;
+                }
             }
         }
     }
 }
+
 
 // ======================================================================================
 // k_pwc_tiled: codes -> swizzled fp16 LDS tile (decoded once), W fragments straight from L2.
@@ -381,9 +436,12 @@ __global__ __launch_bounds__(kSliceThreads, RES ? 4 : 1) void k_pwc_slice(const 
 // K a multiple of 64; NT = 4 channel tiles per wave.  STG-style float32 epilogue as in conv_pw.hip's k_pw_tiled.
 // RES (float32 out): y = relu?(affine(conv) + res), the residual loaded in the staged layout one 16-row tile ahead, the first
 // tile row's pieces in front of the staging barrier, while the last sweep's MFMAs drain.
-template <int FMT, int WM, int WN, int MT, bool YC, bool RES = false>
+// DUAL (RES only): the residual is added in the staged layout, where a lane holds 4 consecutive channels of one pixel: their 4 codes
+// are one dword, stored by the lane itself -- the 16 lanes of a pixel row write the wave's 64 channels as 64 contiguous bytes.
+template <int FMT, int WM, int WN, int MT, bool YC, bool RES = false, bool DUAL = false>
 __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_tiled(const PwcParams p) {
     static_assert(!RES || !YC, "residual operand: float32 output only");
+    static_assert(!DUAL || RES, "the second, code output belongs to the residual forms");
     constexpr int NT = 4;
     constexpr int T = 64 * WM * WN;
     constexpr int BM = WM * MT * 16;
@@ -393,11 +451,11 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_ti
     constexpr int XBYTES = BM * 128;
 
     __shared__ __attribute__((aligned(16))) uint32_t sdec[256];
-    __shared__ __attribute__((aligned(16))) unsigned char senc[YC ? kPwTab : 16];
+    __shared__ __attribute__((aligned(16))) unsigned char senc[(YC || DUAL) ? kPwTab : 16];
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* xs = smem;  // [2 buffers][BM rows][128 B]
     dec_fill<FMT, kDecF16D, T>(sdec);
-    if constexpr (YC) enc_fill<T>(reinterpret_cast<uint2*>(senc), p.enc);
+    if constexpr (YC || DUAL) enc_fill<T>(reinterpret_cast<uint2*>(senc), p.enc);
     const unsigned char* dtab = reinterpret_cast<const unsigned char*>(sdec);
 
     const uint32_t b = xcd_remap(blockIdx.x, p.nblocks);
@@ -572,6 +630,11 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_ti
         // float32 out: staged through a per-wave LDS area into 256-byte runs (4 rows x the wave's 64 channels per store)
         unsigned char* stg = xs + 2 * XBYTES + wave * (16 * kStgRow);
         const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(p.y) + (size_t)m0 * p.N, 0, ybytes, 0x00020000);
+        // DUAL: the workgroup's own rows of the code tensor and nothing more (offsets are relative to row m0)
+        const uint64_t cleft = (uint64_t)(p.M - m0 < BM ? p.M - m0 : BM) * p.N;
+        const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc((DUAL ? p.yc : reinterpret_cast<uint8_t*>(p.y)) + (size_t)m0 * p.N, 0,
+                                                                            (uint32_t)cleft, 0x00020000);
+        const float r1 = p.enc.r1, lo = p.enc.lo, hi = p.enc.hi;
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
 #pragma unroll
@@ -588,6 +651,15 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_ti
                 uint32_t so = ok ? (uint32_t)(row * p.N + n_st) * 4u : 0xFFFFFFF0u;
                 asm volatile("" : "+v"(so));
                 __builtin_amdgcn_raw_buffer_store_b128(v, ry, so, 0, 0);
+                if constexpr (DUAL) {
+                    const float4 f = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
+                    uint32_t c;
+                    if (p.sgn) c = code_sign4(enc4_code<false>(f, r1, lo, hi, senc), f, p.fmt_out);
+                    else c = enc4_code_relu(f, r1, lo, hi, senc);
+                    uint32_t co = ok ? (uint32_t)(row * p.N + n_st) : 0xFFFFFFF0u;   // out of range: dropped
+                    asm volatile("" : "+v"(co));
+                    __builtin_amdgcn_raw_buffer_store_b32(c, rc, co, 0, 0);
+                }
             }
         }
     }
@@ -613,8 +685,9 @@ bool pwc_applicable(const slfp_conv2d_desc& d, const ConvPlan& plan, int post_fl
 template <int FMT, int KS, bool XW, bool HALF = false>
 static int launch_pwc_stream(PwcParams& p, bool y_codes, hipStream_t stream) {
     const size_t lds = (size_t)p.n_tiles * p.KS * 1024 + (size_t)3 * p.n_tiles * 16 * sizeof(float);
-    const size_t lds_total = lds + 1024 + (y_codes ? kPwTab : 16);
-    auto fn = y_codes ? k_pwc_stream<FMT, KS, XW, true, false, HALF> : (p.res ? k_pwc_stream<FMT, KS, XW, false, true, HALF> : k_pwc_stream<FMT, KS, XW, false, false, HALF>);
+    const size_t lds_total = lds + 1024 + ((y_codes || p.yc) ? kPwTab : 16);
+    auto fn = y_codes ? k_pwc_stream<FMT, KS, XW, true, false, HALF>
+                      : (p.yc ? k_pwc_stream<FMT, KS, XW, false, true, HALF, true> : (p.res ? k_pwc_stream<FMT, KS, XW, false, true, HALF> : k_pwc_stream<FMT, KS, XW, false, false, HALF>));
     int rc = raise_lds_limit(reinterpret_cast<const void*>(fn), lds);
     if (rc != SLFP_OK) return rc;
     int per_cu = resident_blocks_per_cu(reinterpret_cast<const void*>(fn), kPwcThreads, lds);
@@ -638,7 +711,8 @@ static int launch_pwc_tiled(PwcParams& p, bool y_codes, hipStream_t stream) {
     if (nblocks > 0x7FFFFFFF) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): grid too large");
     p.nblocks = (uint32_t)nblocks;
     const size_t lds = (size_t)2 * BM * 128 + (y_codes ? 0 : (size_t)(T / 64) * 16 * kStgRow);
-    auto fn = y_codes ? k_pwc_tiled<FMT, WM, WN, MT, true> : (p.res ? k_pwc_tiled<FMT, WM, WN, MT, false, true> : k_pwc_tiled<FMT, WM, WN, MT, false>);
+    auto fn = y_codes ? k_pwc_tiled<FMT, WM, WN, MT, true>
+                      : (p.yc ? k_pwc_tiled<FMT, WM, WN, MT, false, true, true> : (p.res ? k_pwc_tiled<FMT, WM, WN, MT, false, true> : k_pwc_tiled<FMT, WM, WN, MT, false>));
     int rc = raise_lds_limit(reinterpret_cast<const void*>(fn), lds);
     if (rc != SLFP_OK) return rc;
     hipLaunchKernelGGL(fn, dim3(p.nblocks), dim3(T), lds, stream, p);
@@ -657,7 +731,8 @@ static int pwc_slice_nts(const PwcParams& p) {
 template <int FMT, int NTS>
 static int launch_pwc_slice(PwcParams& p, bool y_codes, hipStream_t stream) {
     const size_t lds = (size_t)NTS * p.KS * 1024 + (size_t)3 * NTS * 16 * sizeof(float);
-    auto fn = y_codes ? k_pwc_slice<FMT, NTS, true> : (p.res ? k_pwc_slice<FMT, NTS, false, true> : k_pwc_slice<FMT, NTS, false>);
+    auto fn = y_codes ? k_pwc_slice<FMT, NTS, true>
+                      : (p.yc ? k_pwc_slice<FMT, NTS, false, true, true> : (p.res ? k_pwc_slice<FMT, NTS, false, true> : k_pwc_slice<FMT, NTS, false>));
     int rc = raise_lds_limit(reinterpret_cast<const void*>(fn), lds);
     if (rc != SLFP_OK) return rc;
     int per_cu = resident_blocks_per_cu(reinterpret_cast<const void*>(fn), kSliceThreads, lds);
@@ -700,15 +775,17 @@ static int launch_pwc_fmt(PwcParams& p, const ConvPlan& plan, bool y_codes, hipS
 }
 
 int launch_pwc(const slfp_conv2d_desc& d, const ConvPlan& plan, const uint8_t* x, const void* wfrag, const float* bias,
-               const PostOp& post, void* y, const CodeIo& io, hipStream_t stream, const float* res) {
+               const PostOp& post, void* y, const CodeIo& io, hipStream_t stream, const float* res, void* res_codes) {
     const bool y_codes = io.y_codes;
     const int64_t y_ld = io.y_ld;
     if (res && y_codes) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): a residual operand needs float32 output");
+    if (res_codes && (!res || d.c_out % 16 != 0))
+        return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): the second, code output needs a residual operand and C_out a multiple of 16");
     if (y_ld && (!y_codes || y_ld < d.c_out || y_ld % 16 || y_ld > 0x7FFFFFFF))
         return fail(SLFP_ERR_BAD_ARG, "pointwise (codes): a channel-slice output needs code output and a pixel stride that is a multiple of 16, >= C_out");
     PwcParams p;
     p.post = post;
-    p.x = x; p.bias = bias; p.y = y; p.res = res;
+    p.x = x; p.bias = bias; p.y = y; p.res = res; p.yc = reinterpret_cast<uint8_t*>(res_codes);
     p.K = (int)d.c_in; p.N = (int)d.c_out;
     p.y_ld = y_ld ? (int)y_ld : p.N;
     p.KS = (int)(plan.k_pad / 32);
@@ -720,7 +797,7 @@ int launch_pwc(const slfp_conv2d_desc& d, const ConvPlan& plan, const uint8_t* x
     p.sgn = post.relu ? 0 : 1;
     p.fmt_out = io.y_fmt;
     p.enc.valid = 0;
-    if (y_codes) {
+    if (y_codes || res_codes) {   // io.y_ka / io.y_fmt: the reader of the codes, in y or (DUAL) next to the float32 y
         const EncArgs* t = enc_table(io.y_ka, io.y_fmt, kEncCode);
         if (!t->valid) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): no code table for the consumer's scale %g", (double)io.y_ka);
         p.enc = *t;

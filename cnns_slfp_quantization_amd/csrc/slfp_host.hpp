@@ -150,7 +150,9 @@ int launch_pointwise_entry(const slfp_conv2d_desc& d, const ConvPlan& p, const f
 // pointwise on codes (conv_pw_codes.hpp): codes in, codes or float32 out; the SAME prepared blob as launch_pointwise
 bool pwc_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, int post_flags, bool y_codes);
 int launch_pwc(const slfp_conv2d_desc& d, const ConvPlan& p, const uint8_t* x, const void* wfrag, const float* bias,
-               const PostOp& post, void* y, const CodeIo& io, hipStream_t stream, const float* res = nullptr);
+               const PostOp& post, void* y, const CodeIo& io, hipStream_t stream, const float* res = nullptr, void* res_codes = nullptr);
+// res_codes (with res, float32 y, C_out a multiple of 16; slfp_conv2d_fwd_res_codes): the uint8 tensor that receives, next to y, the codes
+// of y for the reader io.y_ka / io.y_fmt describe
 // the MobileNetV1 image stem with code output (conv_direct.hip)
 bool stem_codes_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, int post_flags);
 int launch_stem_codes(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const float* wq_hwio, const float* bias,

@@ -547,8 +547,9 @@ def link_codes_traced(model, example_input, entries=False):
 
 
 def unlink_codes(model):
-    """Undo link_codes / link_codes_traced / link_stem."""
+    """Undo link_codes / link_codes_traced / link_stem (and, uncounted, every link of link_trunk: its producers read codes)."""
     n = 0
+    unlink_trunk(model)
     for parent in model.modules():
         for name, child in list(parent._modules.items()):
             if isinstance(child, CodeMaxPool2d):
@@ -758,6 +759,8 @@ def _restore_block(blk):
     del blk.__dict__["_residual_fused"]
     blk.conv3.residual_relu = False
     del blk.conv3._in_residual
+    if "_trunk_link" in blk.conv3.__dict__:   # link_trunk: no trunk consumer outlives the residual route
+        _restore_trunk(blk.conv3)
 
 
 def fuse_residual(model, example_input):
@@ -828,6 +831,151 @@ def unfuse_residual(model):
     for blk in model.modules():
         if blk.__dict__.get("_residual_fused"):
             _restore_block(blk)
+            n += 1
+    return n
+
+
+# ------------------------------------------------------------------ the residual epilogue writes the next block's codes too
+def _restore_trunk(conv3):
+    conv3.__dict__.pop("_trunk_link", None)
+    conv3._trunk_code_out = None
+
+
+def link_trunk(model, example_input):
+    """The trunk of a residual net leaves each block as float32 AND as the next block's 1-byte codes: conv3 of a block rewritten by
+    fuse_residual, which reads conv2's codes (link_codes_traced), applies the quantizer of the Conv2d_Q layers that read its result
+    -- the next block's conv1, and downsample.0 at a stage boundary -- to the value it holds after the add and the ReLU and
+    stores the byte next to the float32 value (slfp_conv2d_fwd_res_codes).  Those readers then take the codes (conv1 keeps
+    `_code_entry` and simply receives uint8) and never read the float32 tensor; the next block's residual add, an avgpool or anything
+    else still gets the plain float32 tensor, which carries the codes as an attribute (Conv2d_Q.forward).  One traced forward on
+    `example_input` finds, for every residual-fused block, the Conv2d_Q layers whose input IS its output.  A link is made only if
+    all of them share (float(Ka), q_bit) -- one code tensor serves them --, each has a code-input kernel in its present state, and
+    slfp_conv2d_res_codes_supported says yes for conv3.  Each linked block must reproduce its recorded output with torch.equal, hand
+    on exactly slfp_encode_f32 of it, and the block that reads it must reproduce its own recorded output from it; then the model
+    must reproduce its logits with torch.equal.  A link that fails is taken back alone, a model that fails takes all of them back;
+    an error status of libslfp_hip itself (_lib.SlfpError) is re-raised after the roll-back, as in link_stem.  Run it after
+    fuse_named_bn, fuse_residual and link_codes_traced(entries=True) (with none of them there is nothing to link: 0); composes with
+    link_stem and graph.GraphedModule.  Inference only, never a default.  Returns the number of links; unlink_trunk undoes exactly
+    these, unlink_codes and unfuse_residual take them along."""
+    from .conv2d_func import _scalar_scale, _supported, _f32, _act_fmt
+    from .sfp_quant import hip_encode
+    from . import _lib
+    blocks = [m for m in model.modules() if m.__dict__.get("_residual_fused")]
+    if model.training or not blocks:
+        return 0
+    rec, conv_in, keep, hooks = {}, [], [], []
+    for m in model.modules():
+        if m.__dict__.get("_residual_fused"):
+            hooks.append(m.register_forward_hook(lambda mod, inp, out: rec.__setitem__(mod, rec.get(mod, []) + [(inp, out)])))
+        elif _is_conv_q(m):
+            def _rec_conv(mod, inp, out):
+                conv_in.append((mod, inp[0] if inp else None))
+                keep.append((inp, out))
+            hooks.append(m.register_forward_hook(_rec_conv))
+    try:
+        with torch.no_grad():
+            y0 = model(example_input)
+    finally:
+        for h in hooks:
+            h.remove()
+    if not torch.is_tensor(y0):
+        return 0
+
+    def same(a, b):   # every recorded tensor is kept alive, so an address names one tensor
+        return a is b or (torch.is_tensor(a) and torch.is_tensor(b) and a.data_ptr() == b.data_ptr() and a.shape == b.shape
+                          and a.dtype == b.dtype and a.stride() == b.stride())
+
+    def eligible(m):
+        return (m.q_bit in (8, 7) and not m.training and isinstance(m.padding, tuple)
+                and (m.bias is None or getattr(m, "_scaled_bias", False)) and not (m._post is not None and (int(m._post[2]) & 2)))
+
+    def one_call(blk):
+        calls = rec.get(blk, [])
+        if len(calls) != 1 or len(calls[0][0]) != 1 or not torch.is_tensor(calls[0][0][0]) or not torch.is_tensor(calls[0][1]):
+            return None
+        return calls[0][0][0], calls[0][1]
+
+    n_runs = {}
+    for mod, _ in conv_in:
+        n_runs[mod] = n_runs.get(mod, 0) + 1
+    nhwc = torch.channels_last
+    made = []
+
+    def take_back(conv3):
+        _restore_trunk(conv3)
+        made.remove(conv3)
+
+    for blk in blocks:
+        io = one_call(blk)
+        c3 = blk._modules.get("conv3")
+        if io is None or not _is_conv_q(c3) or c3._trunk_code_out is not None or n_runs.get(c3) != 1:
+            continue
+        x_blk, want = io
+        if want.dim() != 4 or want.dtype != torch.float32 or not want.is_contiguous(memory_format=nhwc):
+            continue
+        readers = [(b, xin) for b, xin in conv_in if same(xin, want)]
+        if not readers or any(n_runs[b] != 1 or b is c3 for b, _ in readers):
+            continue
+        scales = {(float(_scalar_scale(b.Ka, "Ka")), int(b.q_bit)) for b, _ in readers}
+        if len(scales) != 1:
+            continue   # one code tensor serves every reader
+        out = next(iter(scales))
+        if not all(eligible(b) and _supported(b, tuple(want.shape), "codes", True, b._code_out,
+                                              int(b._post[2]) if b._post is not None else 0) for b, _ in readers):
+            continue   # a reader without a code-input kernel in its present state
+        x3 = next(xin for b, xin in conv_in if b is c3)
+        flags3 = int(c3._post[2]) if c3._post is not None else 0
+        if (not eligible(c3) or c3._code_out is not None or flags3 != 0 or not torch.is_tensor(x3) or x3.dtype != torch.uint8
+                or x3.dim() != 4 or not _supported(c3, tuple(x3.shape), "res_codes", True, out, 1 if c3.residual_relu else 0)):
+            continue
+        c3._trunk_code_out = out
+        c3.__dict__["_trunk_link"] = True
+        made.append(c3)
+        nxt = next((b for b in blocks if b is not blk and one_call(b) is not None and same(one_call(b)[0], want)), None)
+        ok = False
+        try:
+            with torch.no_grad():
+                got = blk(x_blk)
+                tc = got.__dict__.get("_trunk_codes") if torch.is_tensor(got) else None
+                ok = (tc is not None and got.dtype == want.dtype and got.shape == want.shape and torch.equal(got, want)
+                      and tc[1:] == out and torch.equal(tc[0], hip_encode(want, _f32(out[0]), _act_fmt(out[1]))))
+                if ok and nxt is not None:
+                    ok = torch.equal(nxt(got), one_call(nxt)[1])
+        except _lib.SlfpError:
+            while made:
+                take_back(made[-1])
+            raise   # libslfp_hip refused or failed a call the support queries had granted: a defect, not an ordinary refusal
+        except Exception:
+            ok = False
+        if not ok:
+            take_back(c3)
+    rec.clear(); conv_in.clear(); keep.clear()
+    if not made:
+        return 0
+    ok = False
+    try:
+        with torch.no_grad():
+            y1 = model(example_input)
+        ok = torch.is_tensor(y1) and y1.dtype == y0.dtype and y1.shape == y0.shape and torch.equal(y1, y0)
+    except _lib.SlfpError:
+        while made:
+            take_back(made[-1])
+        raise
+    except Exception:
+        ok = False
+    if not ok:
+        while made:
+            take_back(made[-1])
+        return 0
+    return len(made)
+
+
+def unlink_trunk(model):
+    """Undo link_trunk."""
+    n = 0
+    for m in model.modules():
+        if "_trunk_link" in m.__dict__:
+            _restore_trunk(m)
             n += 1
     return n
 

@@ -253,6 +253,23 @@ int slfp_conv2d_res_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* i
 int slfp_conv2d_fwd_res(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
                         const float* bias, const float* post_scale, const float* post_shift, int relu,
                         const float* res, float* y, void* workspace, void* stream);
+/* ---- the residual epilogue also writes the next block's codes ------------------------------------------------------------
+ * slfp_conv2d_fwd_res on codes (io->x_codes == 1) with a second output: y is written exactly as slfp_conv2d_fwd_res writes it for
+ * the same arguments with io->y_codes = 0, and y_codes (uint8 NHWC, C_out bytes per pixel) receives, per element, the byte
+ *     slfp_encode_f32(y, io->y_ka, fmt(io->y_qbits) | SLFP_FMT_EXT)
+ * of that y -- in the same launch, from the value the kernel holds after the add and the ReLU: the float32 trunk of a ResNet
+ * goes on to the next block's residual add, its codes to the next block's conv1 (and downsample.0), which then never read the
+ * float32 tensor.  Both hold for every input, NaN, +-inf and -0.0 in res included (NaN has no code: 0x00).  Requires
+ * io->x_codes == 1 and io->y_codes == 1 (y_ka / y_qbits describe the reader of y_codes); y_codes non-NULL, 16-byte aligned and not
+ * overlapping y or res (SLFP_ERR_BAD_ARG / SLFP_ERR_ALIGNMENT as for y).  Supported (slfp_conv2d_res_codes_supported: 1 / 0, host
+ * only) exactly where slfp_conv2d_res_supported says yes for {x_codes = 1, y_codes = 0}, C_out is a multiple of 16 and the reader's
+ * quantizer is valid (y_qbits 8 or 7, y_ka > 0 with a code table).  Everything else -- float32 input, SLFP_POST_LAYEROUT, NCHW,
+ * strided, dense, depthwise and stem layers, F16X3 at qbits 8 -- returns SLFP_ERR_UNSUPPORTED before any device work.
+ * slfp_conv2d_res_supported keeps refusing y_codes.  `workspace` is reserved; pass NULL. */
+int slfp_conv2d_res_codes_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int relu);
+int slfp_conv2d_fwd_res_codes(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
+                              const float* bias, const float* post_scale, const float* post_shift, int relu,
+                              const float* res, float* y, void* y_codes, void* workspace, void* stream);
 
 /* nn.MaxPool2d (floor mode, dilation 1) on a tensor of activation codes (NHWC, C a multiple of 4; 16-byte aligned): the class
  * of a window's largest input is the highest class among its codes in the order of the classes' pre-images (the clamp literal
