@@ -276,6 +276,12 @@ const char* slfp_debug_dw3x3_variant(const slfp_conv2d_desc* d, int has_post) {
     return dw3x3_tile_applicable(*d, p, nullptr, post) ? "tile" : "general";
 }
 
+const char* slfp_debug_dense_variant(const slfp_conv2d_desc* d, int x_codes) {
+    ConvPlan p;
+    if (make_plan(d, &p) != SLFP_OK) return "none";
+    return dense_variant_name(*d, p, x_codes != 0);
+}
+
 size_t slfp_conv2d_wprep_bytes(const slfp_conv2d_desc* d) {
     ConvPlan p;
     if (make_plan(d, &p) != SLFP_OK) return 0;

@@ -902,44 +902,89 @@ size_t dense_mfma_workspace_bytes(const slfp_conv2d_desc& d, int passes) {
     return 256 + (size_t)dense_planes(d, passes) * dense_plane_bytes(d);
 }
 
-template <int WM, int WN, int MT, int PASSES, int NSLOT>
-static int launch_dense_tps(DenseParams& p, size_t lds, hipStream_t stream, int nwb = 2) {
-    auto fn = k_dense_mfma<WM, WN, MT, PASSES, NSLOT>;
-    if constexpr (PASSES == 1) { if (nwb == 3) fn = k_dense_mfma<WM, WN, MT, PASSES, NSLOT, 3>; }
-    if constexpr (PASSES == 1 && NSLOT <= 8 && MT != 2) {
-        // 3x3 stride 1 with one halo slice per tap: the unrolled kernel (same staging plan, same results).  Not for the MT = 2
-        // tilings: two workgroups per CU cap them at 128 registers and the unrolled body spills there (measured slower).
-        if (p.KH == 3 && p.KW == 3 && p.S == 1 && p.x_per_tap == 1 && ceil_div(p.x_pieces, 8) <= NSLOT && !switches().dense_generic) {
-            fn = nwb == 3 ? k_dense3x3<WM, WN, MT, NSLOT, 3> : k_dense3x3<WM, WN, MT, NSLOT, 2>;
-        }
-    }
-    const int rc = raise_lds_limit(reinterpret_cast<const void*>(fn), 160 * 1024);  // once per (device, kernel)
-    if (rc != SLFP_OK) return rc;
-    hipLaunchKernelGGL(fn, dim3(p.nblocks), dim3(kDnThreads), lds, stream, p);
-    return check_launch("slfp dense MFMA conv kernel");
-}
-
-template <int WM, int WN, int MT, int PASSES>
-static int launch_dense_tp(DenseParams& p, size_t lds, hipStream_t stream, int nwb) {
-    const int slots = (int)ceil_div(p.x_pieces, 8);
-    if (slots <= 3) return launch_dense_tps<WM, WN, MT, PASSES, 3>(p, lds, stream, nwb);
-    if (slots <= 6 && p.KH == 3 && p.KW == 3 && p.S == 1) return launch_dense_tps<WM, WN, MT, PASSES, 6>(p, lds, stream, nwb);
-    return launch_dense_tps<WM, WN, MT, PASSES, kMaxSlots>(p, lds, stream, nwb);
-}
-
-template <int WM, int WN, int MT>
-static int launch_dense_t(DenseParams& p, size_t lds, int planes, hipStream_t stream, int nwb) {
-    return planes == 2 ? launch_dense_tp<WM, WN, MT, 3>(p, lds, stream, 2) : launch_dense_tp<WM, WN, MT, 1>(p, lds, stream, nwb);
-}
-
 // ---- the weights-resident persistent form (k_dense3x3_res)
 static bool dense_res_applicable(const slfp_conv2d_desc& d, int planes, int cp) {
     return planes == 1 && cp == 64 && d.kh == 3 && d.kw == 3 && d.stride_h == 1 && d.pad_h <= 1 && d.pad_w <= 1 &&
            !switches().dense_generic && switches().dense_res && switches().dense_cfg == 0;
 }
 
+// Everything a dense launch decides, worked out in ONE place (dense_select): the launchers below only dispatch on it and
+// dense_variant_name (slfp_debug_dense_variant) prints it, so the reported string cannot drift from what runs.
+enum DenseBody { kBodyGen = 0, kBody3x3, kBodyRes };   // k_dense_mfma / k_dense3x3 / k_dense3x3_res
+struct DenseSel {
+    DenseGeom g;      // the tiling dense_choose picked, its halo geometry and LDS bytes (per-tile bodies)
+    int planes;       // operand planes: 2 in float32-equivalent mode (PASSES == 3)
+    int body;
+    int nwb, nslot;   // template arguments NWB / NSLOT of the body
+    int res_mt;       // kBodyRes: MFMA rows per wave (2: 16-row tiles, 1: 8-row tiles)
+    bool encx;        // kBodyRes: the float32 halo is encoded where it is staged (no pre-pass)
+};
+
+static bool dense_select(const slfp_conv2d_desc& d, int passes, int64_t h_out, int64_t w_out, bool x_codes, DenseSel* s) {
+    s->planes = dense_planes(d, passes);
+    s->body = kBodyGen; s->nwb = 2; s->nslot = kMaxSlots; s->res_mt = 0; s->encx = false;
+    if (!dense_choose(d, s->planes, h_out, w_out, &s->g)) return false;
+    if (dense_res_applicable(d, s->planes, (int)dense_cp(d))) {
+        s->body = kBodyRes;
+        // 16-row tiles (two MFMA rows per W fragment read) unless they pad the image noticeably more than 8-row tiles
+        const int64_t pad16 = ceil_div(h_out, 16) * 16, pad8 = ceil_div(h_out, 8) * 8;
+        const bool rows16 = pad16 * 100 <= pad8 * 108;
+        s->res_mt = rows16 ? 2 : 1;
+        s->nslot = rows16 ? 6 : 3;
+        // float32 input of exactly one 64-channel chunk, one channel slice -> encoded where the halo is staged
+        s->encx = !x_codes && d.c_in == 64 && d.c_out <= 64 && switches().dense_encx;
+        return true;
+    }
+    const bool k3s1 = d.kh == 3 && d.kw == 3 && d.stride_h == 1;
+    const int slots = (int)ceil_div(s->g.pieces, 8);
+    s->nslot = slots <= 3 ? 3 : (slots <= 6 && k3s1 ? 6 : kMaxSlots);
+    s->nwb = s->planes == 2 ? 2 : s->g.nwb;
+    // 3x3 stride 1 with one halo slice per tap: the unrolled kernel (same staging plan, same results).  Not for the MT = 2
+    // tilings: two workgroups per CU cap them at 128 registers and the unrolled body spills there (measured slower).
+    if (s->planes == 1 && s->nslot <= 8 && s->g.cfg.mt != 2 && k3s1 && s->g.per_tap == 1 && slots <= s->nslot && !switches().dense_generic)
+        s->body = kBody3x3;
+    return true;
+}
+
+const char* dense_variant_name(const slfp_conv2d_desc& d, const ConvPlan& plan, bool x_codes) {
+    static thread_local char buf[48];
+    DenseSel s;
+    if (plan.family != kDenseMfma || !dense_select(d, plan.passes, plan.h_out, plan.w_out, x_codes, &s)) return "none";
+    if (s.body == kBodyRes)
+        snprintf(buf, sizeof buf, "res/mt%d/ns%d%s", s.res_mt, s.nslot, s.encx ? "/encx" : "");
+    else
+        snprintf(buf, sizeof buf, "%d%d%d/%s/nwb%d/ns%d/p%d", s.g.cfg.wm, s.g.cfg.wn, s.g.cfg.mt, s.body == kBody3x3 ? "k3x3" : "gen",
+                 s.nwb, s.nslot, s.planes);
+    return buf;
+}
+
+template <int WM, int WN, int MT, int PASSES, int NSLOT>
+static int launch_dense_tps(DenseParams& p, const DenseSel& s, hipStream_t stream) {
+    auto fn = k_dense_mfma<WM, WN, MT, PASSES, NSLOT>;
+    if constexpr (PASSES == 1) { if (s.nwb == 3) fn = k_dense_mfma<WM, WN, MT, PASSES, NSLOT, 3>; }
+    if constexpr (PASSES == 1 && NSLOT <= 8 && MT != 2) {
+        if (s.body == kBody3x3) fn = s.nwb == 3 ? k_dense3x3<WM, WN, MT, NSLOT, 3> : k_dense3x3<WM, WN, MT, NSLOT, 2>;
+    }
+    const int rc = raise_lds_limit(reinterpret_cast<const void*>(fn), 160 * 1024);  // once per (device, kernel)
+    if (rc != SLFP_OK) return rc;
+    hipLaunchKernelGGL(fn, dim3(p.nblocks), dim3(kDnThreads), s.g.lds, stream, p);
+    return check_launch("slfp dense MFMA conv kernel");
+}
+
+template <int WM, int WN, int MT, int PASSES>
+static int launch_dense_tp(DenseParams& p, const DenseSel& s, hipStream_t stream) {
+    if (s.nslot == 3) return launch_dense_tps<WM, WN, MT, PASSES, 3>(p, s, stream);
+    if (s.nslot == 6) return launch_dense_tps<WM, WN, MT, PASSES, 6>(p, s, stream);
+    return launch_dense_tps<WM, WN, MT, PASSES, kMaxSlots>(p, s, stream);
+}
+
+template <int WM, int WN, int MT>
+static int launch_dense_t(DenseParams& p, const DenseSel& s, hipStream_t stream) {
+    return s.planes == 2 ? launch_dense_tp<WM, WN, MT, 3>(p, s, stream) : launch_dense_tp<WM, WN, MT, 1>(p, s, stream);
+}
+
 template <int MT, int NSLOT>
-static int launch_dense_res_t(DenseParams& p, hipStream_t stream) {
+static int launch_dense_res_t(DenseParams& p, const DenseSel& s, hipStream_t stream) {
     constexpr int TH = 8 * MT, PIECES = ((TH + 2) * (kDnTW + 2) + 7) / 8;
     const size_t lds = 9 * 8192 + 2 * (size_t)PIECES * 1024 + 2 * ((kEncEntries * 8 + 63) & ~63);
     p.tiles_h = (int)ceil_div(p.Ho, TH);
@@ -949,7 +994,7 @@ static int launch_dense_res_t(DenseParams& p, hipStream_t stream) {
     int64_t gs = std::min<int64_t>(T, std::max<int64_t>(1, device_cu_count() / p.n_blocks));   // one workgroup per CU (LDS)
     if (gs >= 8) gs -= gs % 8;
     auto fn = k_dense3x3_res<MT, NSLOT, false>;
-    if (p.x32) fn = k_dense3x3_res<MT, NSLOT, true>;
+    if (s.encx) fn = k_dense3x3_res<MT, NSLOT, true>;
     const int rc = raise_lds_limit(reinterpret_cast<const void*>(fn), 160 * 1024);
     if (rc != SLFP_OK) return rc;
     p.nblocks = (uint32_t)(gs * p.n_blocks);
@@ -957,11 +1002,9 @@ static int launch_dense_res_t(DenseParams& p, hipStream_t stream) {
     return check_launch("slfp dense MFMA conv kernel (resident weights)");
 }
 
-static int launch_dense_res(DenseParams& p, hipStream_t stream) {
-    // 16-row tiles (two MFMA rows per W fragment read) unless they pad the image noticeably more than 8-row tiles
-    const int64_t pad16 = ceil_div(p.Ho, 16) * 16, pad8 = ceil_div(p.Ho, 8) * 8;
-    if (pad16 * 100 <= pad8 * 108) return launch_dense_res_t<2, 6>(p, stream);
-    return launch_dense_res_t<1, 3>(p, stream);
+static int launch_dense_res(DenseParams& p, const DenseSel& s, hipStream_t stream) {
+    if (s.res_mt == 2) return launch_dense_res_t<2, 6>(p, s, stream);
+    return launch_dense_res_t<1, 3>(p, s, stream);
 }
 
 // code interface: is there a dense kernel for this layer with code input / output?  (the float32-interface kernel with a decode
@@ -983,14 +1026,13 @@ int launch_dense_mfma_io(const slfp_conv2d_desc& d, const ConvPlan& plan, const 
                          const float* bias, const PostOp& post, void* y_any, void* workspace, const CodeIo& io, hipStream_t stream) {
     const float* x = reinterpret_cast<const float*>(x_any);
     float* y = reinterpret_cast<float*>(y_any);
-    DenseGeom g;
-    const int planes = dense_planes(d, plan.passes);
-    if (!dense_choose(d, planes, plan.h_out, plan.w_out, &g)) return fail(SLFP_ERR_UNSUPPORTED, "dense MFMA conv: no tiling fits");
+    DenseSel sel;
+    if (!dense_select(d, plan.passes, plan.h_out, plan.w_out, io.x_codes, &sel)) return fail(SLFP_ERR_UNSUPPORTED, "dense MFMA conv: no tiling fits");
+    const DenseGeom& g = sel.g;
+    const int planes = sel.planes;
     if (!workspace) return fail(SLFP_ERR_BAD_ARG, "dense MFMA conv: workspace required (slfp_conv2d_workspace_bytes)");
-    // k_dense3x3_res<ENCX>: float32 input of exactly one 64-channel chunk, one channel slice -> encoded where the halo is staged
-    const EncArgs* tx = nullptr;
-    if (!io.x_codes && planes == 1 && d.c_in == 64 && d.c_out <= 64 && switches().dense_encx && dense_res_applicable(d, planes, (int)dense_cp(d)))
-        tx = act_table(d.ka, plan.fmt_act, kEncF16P);
+    // k_dense3x3_res<ENCX>: the float32 input is encoded where the halo is staged (dense_select)
+    const EncArgs* tx = sel.encx ? act_table(d.ka, plan.fmt_act, kEncF16P) : nullptr;
     // ---- pass 1: encode the input once (every element is reused KH*KW * C_out times by pass 2)
     unsigned char* zero_page = reinterpret_cast<unsigned char*>(workspace);
     _Float16* xe = reinterpret_cast<_Float16*>(zero_page + 256);
@@ -1044,14 +1086,14 @@ int launch_dense_mfma_io(const slfp_conv2d_desc& d, const ConvPlan& plan, const 
     const int64_t nblocks = (int64_t)p.N * p.tiles_h * p.tiles_w * p.n_blocks;
     if (nblocks > 0x7FFFFFFF) return fail(SLFP_ERR_UNSUPPORTED, "dense MFMA conv: grid too large");
     p.nblocks = (uint32_t)nblocks;
-    if (dense_res_applicable(d, planes, cp)) return launch_dense_res(p, stream);
+    if (sel.body == kBodyRes) return launch_dense_res(p, sel, stream);
     switch (g.cfg.wm * 100 + g.cfg.wn * 10 + g.cfg.mt) {
-        case 244: return launch_dense_t<2, 4, 4>(p, g.lds, planes, stream, g.nwb);
-        case 424: return launch_dense_t<4, 2, 4>(p, g.lds, planes, stream, g.nwb);
-        case 422: return launch_dense_t<4, 2, 2>(p, g.lds, planes, stream, g.nwb);
-        case 421: return launch_dense_t<4, 2, 1>(p, g.lds, planes, stream, g.nwb);
-        case 812: return launch_dense_t<8, 1, 2>(p, g.lds, planes, stream, g.nwb);
-        default: return launch_dense_t<8, 1, 1>(p, g.lds, planes, stream, g.nwb);
+        case 244: return launch_dense_t<2, 4, 4>(p, sel, stream);
+        case 424: return launch_dense_t<4, 2, 4>(p, sel, stream);
+        case 422: return launch_dense_t<4, 2, 2>(p, sel, stream);
+        case 421: return launch_dense_t<4, 2, 1>(p, sel, stream);
+        case 812: return launch_dense_t<8, 1, 2>(p, sel, stream);
+        default: return launch_dense_t<8, 1, 1>(p, sel, stream);
     }
 }
 

@@ -177,6 +177,9 @@ int launch_dense_mfma(const slfp_conv2d_desc& d, const ConvPlan& p, const float*
 bool dense_codes_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, int post_flags, bool y_codes);
 int launch_dense_mfma_io(const slfp_conv2d_desc& d, const ConvPlan& p, const void* x_any, const void* wblob, const float* bias,
                          const PostOp& post, void* y_any, void* workspace, const CodeIo& io, hipStream_t stream);
+// what launch_dense_mfma_io decides for this layer under the switches read at load, printed from the selection it consumes
+// (slfp_debug_dense_variant; host only).  "none" outside the family; valid until the next call on the same thread.
+const char* dense_variant_name(const slfp_conv2d_desc& d, const ConvPlan& p, bool x_codes);
 // codes: `w_oihw` points at 1-byte extended weight codes (slfp_encode_f32 | SLFP_FMT_EXT) instead of float32 weights
 int launch_prepare_weights(const slfp_conv2d_desc& d, const ConvPlan& p, const float* w_oihw, void* wprep,
                            float* weight_q_oihw, hipStream_t stream, bool codes = false);

@@ -107,6 +107,14 @@ const char* slfp_conv2d_kernel_name(const slfp_conv2d_desc* d);
  * "tile" (csrc/conv_dw2.hip), "general" (csrc/conv_dw.hip), or "none" when the descriptor is not of the dw3x3 family.
  * Host only: no device is touched. */
 const char* slfp_debug_dw3x3_variant(const slfp_conv2d_desc* d, int has_post);
+/* Which dense k x k kernel (csrc/conv_dense.hip) a forward of this descriptor launches under the switches read at load, with
+ * float32 (x_codes == 0) or 1-byte codes (x_codes != 0) on the input side; "none" when the descriptor is not of the dense_mfma_*
+ * family.  Per-tile kernels: "<wm><wn><mt>/<body>/nwb<N>/ns<N>/p<N>" = tiling, body ("k3x3": the unrolled 3x3 stride-1
+ * kernel, "gen": the general one), weight buffers, halo slots per wave, operand planes, e.g. "424/k3x3/nwb3/ns6/p1".  The
+ * weights-resident persistent kernel: "res/mt<N>/ns<N>", with "/encx" when it encodes the float32 input itself.  The string
+ * is printed from the selection the launch consumes.  Host only: no device is touched.  The pointer stays valid
+ * until the next call on the same thread. */
+const char* slfp_debug_dense_variant(const slfp_conv2d_desc* d, int x_codes);
 
 /* Bytes of the prepared-weight blob for this layer (device memory the caller owns). */
 size_t slfp_conv2d_wprep_bytes(const slfp_conv2d_desc* d);
