@@ -27,7 +27,7 @@ SYMBOLS = (
     "slfp_nchw_to_nhwc_f32", "slfp_nhwc_to_nchw_f32", "slfp_debug_div_mismatches",
     "slfp_debug_enc_mismatches", "slfp_enc_table_ok", "slfp_dwpw_supported", "slfp_dwpw_fwd",
     "slfp_conv2d_codes_supported", "slfp_conv2d_fwd_codes", "slfp_conv2d_fwd_codes_ws", "slfp_maxpool2d_codes", "slfp_debug_code_mismatches", "slfp_debug_reload_switches",
-    "slfp_debug_enc_hl_mismatches", "slfp_sgd_step_f32", "slfp_debug_dw3x3_variant", "slfp_debug_dense_variant",
+    "slfp_debug_enc_hl_mismatches", "slfp_sgd_step_f32", "slfp_debug_dw3x3_variant", "slfp_debug_dense_variant", "slfp_debug_pw_variant",
     "slfp_conv2d_bwd_supported", "slfp_conv2d_bwd_kernel_name", "slfp_conv2d_bwd_workspace_bytes", "slfp_conv2d_bwd",
     "slfp_conv2d_bwd_supported_ex", "slfp_conv2d_bwd_kernel_name_ex", "slfp_conv2d_bwd_workspace_bytes_ex", "slfp_conv2d_bwd_ex",
     "slfp_conv2d_res_supported", "slfp_conv2d_fwd_res",
@@ -101,6 +101,7 @@ def load():
         "slfp_conv2d_kernel_name": (ctypes.c_char_p, [dp]),
         "slfp_debug_dw3x3_variant": (ctypes.c_char_p, [dp, ci]),
         "slfp_debug_dense_variant": (ctypes.c_char_p, [dp, ci]),
+        "slfp_debug_pw_variant": (ctypes.c_char_p, [dp, ctypes.POINTER(ConvIo), ci, ci, i64]),
         "slfp_conv2d_wprep_bytes": (sz, [dp]),
         "slfp_conv2d_prepare_weights": (ci, [dp, vp, vp, vp, vp]),
         "slfp_conv2d_prepare_weights_codes": (ci, [dp, vp, vp, vp, vp]),

@@ -80,6 +80,8 @@ static Switches read_switches() {
     w.dense_encx = std::getenv("SLFP_DENSE_NOENCX") == nullptr;
     w.stem_im2row = std::getenv("SLFP_STEM_IM2ROW") != nullptr;
     w.dw_rows = parse_dw_rows(std::getenv("SLFP_DW_ROWS"));
+    e = std::getenv("SLFP_PW_GRID");
+    w.pw_grid = e ? (atoi(e) > 0 ? atoi(e) : 0) : 0;
     e = std::getenv("SLFP_PW_STREAM_MAX_KB");
     w.pw_stream_max_kb = e ? atoi(e) : 30;   // round 3 (profiles/ab_env_long.sh): W above 30 KiB runs on the tiled kernel -- MobileNetV1 +0.3-0.4 % (128->128, 128->256, 256->256), ShuffleNetV2 14.8 -> 17.5 k images/s (its 116- / 232-channel layers), ResNet-50 / SqueezeNet unchanged
     return w;

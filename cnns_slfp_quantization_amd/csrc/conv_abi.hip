@@ -250,6 +250,8 @@ static const char* family_name(const ConvPlan& p, const slfp_conv2d_desc& d) {
 
 using namespace slfp;
 
+static const char* pw_variant(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, bool has_res, bool has_res_codes, int64_t y_ld);
+
 extern "C" {
 
 int slfp_conv2d_out_shape(const slfp_conv2d_desc* d, int64_t* h_out, int64_t* w_out) {
@@ -280,6 +282,10 @@ const char* slfp_debug_dense_variant(const slfp_conv2d_desc* d, int x_codes) {
     ConvPlan p;
     if (make_plan(d, &p) != SLFP_OK) return "none";
     return dense_variant_name(*d, p, x_codes != 0);
+}
+
+const char* slfp_debug_pw_variant(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_res, int has_res_codes, int64_t y_ld) {
+    return pw_variant(d, io, has_res != 0, has_res_codes != 0, y_ld);
 }
 
 size_t slfp_conv2d_wprep_bytes(const slfp_conv2d_desc* d) {
@@ -412,6 +418,41 @@ static bool res_codes_route(const slfp_conv2d_desc* d, const slfp_conv2d_io* io,
     if (io->x_codes != 1 || io->y_codes != 1 || d->c_out % 16 != 0 || !consumer_quant_ok(io)) return false;
     const slfp_conv2d_io rio{1, 0, 1.f, 8};
     return res_route(d, &rio, has_bias, relu, p) && enc_table(io->y_ka, y_fmt_of(io->y_qbits), kEncCode)->valid;
+}
+
+// slfp_debug_pw_variant: the route the matching forward entry point takes (refused: "none"), then the launcher's own selection.
+static const char* pw_variant(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, bool has_res, bool has_res_codes, int64_t y_ld) {
+    ConvPlan p;
+    if (!d || make_plan(d, &p) != SLFP_OK || p.family != kPointwise) return "none";
+    const slfp_conv2d_io f32{0, 0, 1.f, 8};
+    if (!io) io = &f32;
+    const int y_fmt = y_fmt_of(io->y_qbits);
+    if (has_res_codes) {   // slfp_conv2d_fwd_res_codes
+        if (!has_res || y_ld || !res_codes_route(d, io, false, 0, p)) return "none";
+        return pwc_variant_name(*d, p, false, true, true);
+    }
+    if (has_res) {         // slfp_conv2d_fwd_res
+        if (y_ld || !res_route(d, io, false, 0, p)) return "none";
+        return io->x_codes ? pwc_variant_name(*d, p, false, true, false) : pw_variant_name(*d, p, true, false, 1.f, kFmtAct8);
+    }
+    if (y_ld) {            // slfp_conv2d_fwd_codes_slice
+        if (!io->y_codes || !y_ld_ok(d, y_ld) || codes_route(d, io, false, 0, p) != kRoutePwc) return "none";
+        return pwc_variant_name(*d, p, true, false, false);
+    }
+    if (io->x_codes) {     // slfp_conv2d_fwd_codes
+        if (codes_route(d, io, false, 0, p) != kRoutePwc) return "none";
+        return pwc_variant_name(*d, p, io->y_codes != 0, false, false);
+    }
+    if (io->y_codes) {     // slfp_conv2d_fwd_entry
+        if (!entry_route(d, io, 0, p)) return "none";
+        return pw_variant_name(*d, p, false, true, io->y_ka, y_fmt);
+    }
+    if (p.repad) {         // slfp_conv2d_fwd_post on channel-padded copies: the padded descriptor is what launches
+        slfp_conv2d_desc d2;
+        padded_desc(*d, &d2);
+        return pw_variant_name(d2, p, false, false, 1.f, kFmtAct8);
+    }
+    return pw_variant_name(*d, p, false, false, 1.f, kFmtAct8);
 }
 
 // ---- the one argument check of the forward entry points ----

@@ -126,7 +126,7 @@ __device__ __forceinline__ half8 join(const half4 a, const half4 b) {
 constexpr int kStreamThreads = 512;
 
 // KS = number of 32-deep k-steps actually swept (ceil(K/32)); the blob's stride is p.KS.
-// KFULL: K is a multiple of 32.  A8: K and N are even but not both multiples of 4 (ShuffleNetV2's
+// KFULL: K == 32 * KS, every k-step swept holds real channels (its loads carry no bound).  A8: K and N are even but not both multiples of 4 (ShuffleNetV2's
 // 58-channel branches): pixel rows are only 8-byte aligned, so every 16-byte access becomes two
 // 8-byte ones and the per-channel vectors are read with bounds.
 // TAB (single-pass modes only): the quantizer is the threshold table of slfp_enc.hpp, which yields the packed fp16
@@ -732,136 +732,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pw_til
 // once per (device, kernel), not per launch (round 1 re-armed the attribute on every launch)
 static int set_lds_limit(const void* fn, size_t lds) { return raise_lds_limit(fn, lds); }
 
-template <int FMT, int PASSES, int WM, int WN, int MT, int NT, bool KFULL>
-static int launch_tiled_k(PwParams& p, hipStream_t stream) {
-    constexpr int BM = WM * MT * 16, BN = WN * NT * 16, T = 64 * WM * WN;
-    p.n_blocks = (uint32_t)ceil_div((int64_t)p.N, BN);
-    // (Workgroups that own fewer rows than their tile -- 49 = a quarter image instead of 64, for an integral number of
-    // rounds on the 512 resident slots -- were measured: no gain, 61-64 vs 60 us on 512->512.  A workgroup's time is set
-    // by streaming all of W from L2, not by its rows.)
-    p.rb = BM;
-    p.m_blocks = (uint32_t)ceil_div(p.M, p.rb);
-    const int64_t nblocks = (int64_t)p.m_blocks * p.n_blocks;
-    if (nblocks > 0x7FFFFFFF) return fail(SLFP_ERR_UNSUPPORTED, "pointwise: grid too large");
-    p.nblocks = (uint32_t)nblocks;
-    if (p.yc) {   // code output: the single-pass table form with four channel tiles per wave only (pointwise_entry_applicable)
-        if constexpr (NT == 4 && PASSES == 1) {
-            if (p.enc.valid && p.enc_lo.valid && !p.res) {
-                const size_t lds = (size_t)2 * BM * 128;   // dynamic part (both tables are static LDS; no staging area)
-                auto fn = k_pw_tiled<FMT, 1, WM, WN, MT, NT, KFULL, true, false, false, true>;
-                int rc = set_lds_limit(reinterpret_cast<const void*>(fn), lds);
-                if (rc != SLFP_OK) return rc;
-                hipLaunchKernelGGL(fn, dim3(p.nblocks), dim3(T), lds, stream, p);
-                return check_launch("slfp pointwise (tiled, code output) kernel");
-            }
-        }
-        return fail(SLFP_ERR_UNSUPPORTED, "pointwise: no code-output form of this kernel variant");
-    }
-    if (p.res) {   // residual operand: the table quantizer + staged epilogue form only (pointwise_res_applicable asks for both)
-        if constexpr (NT == 4) {
-            if (p.enc.valid && (PASSES == 1 || p.enc_lo.valid) && !switches().pw_nostg) {
-                const size_t lds = (size_t)2 * (PASSES == 3 ? 2 : 1) * BM * 128 + (size_t)(T / 64) * 16 * kStgRow;
-                auto fn = k_pw_tiled<FMT, PASSES, WM, WN, MT, NT, KFULL, true, true, true>;
-                int rc = set_lds_limit(reinterpret_cast<const void*>(fn), lds);
-                if (rc != SLFP_OK) return rc;
-                hipLaunchKernelGGL(fn, dim3(p.nblocks), dim3(T), lds, stream, p);
-                return check_launch("slfp pointwise (tiled, residual) kernel");
-            }
-        }
-        return fail(SLFP_ERR_UNSUPPORTED, "pointwise: no residual form of this kernel variant");
-    }
-    {
-        if (p.enc.valid && (PASSES == 1 || p.enc_lo.valid)) {
-            if constexpr (NT == 4) {
-                if (!switches().pw_nostg) {   // experiment switch (slfp_host.hpp), read once at load
-                    const size_t lds = (size_t)2 * (PASSES == 3 ? 2 : 1) * BM * 128 + (size_t)(T / 64) * 16 * kStgRow;   // dynamic part (the tables are static LDS)
-                    auto fn = k_pw_tiled<FMT, PASSES, WM, WN, MT, NT, KFULL, true, true>;
-                    int rc = set_lds_limit(reinterpret_cast<const void*>(fn), lds);
-                    if (rc != SLFP_OK) return rc;
-                    hipLaunchKernelGGL(fn, dim3(p.nblocks), dim3(T), lds, stream, p);
-                    return check_launch("slfp pointwise (tiled) kernel");
-                }
-            }
-            const size_t lds = (size_t)2 * (PASSES == 3 ? 2 : 1) * BM * 128;
-            auto fn = k_pw_tiled<FMT, PASSES, WM, WN, MT, NT, KFULL, true>;
-            int rc = set_lds_limit(reinterpret_cast<const void*>(fn), lds);
-            if (rc != SLFP_OK) return rc;
-            hipLaunchKernelGGL(fn, dim3(p.nblocks), dim3(T), lds, stream, p);
-            return check_launch("slfp pointwise (tiled) kernel");
-        }
-    }
-    const size_t lds = (size_t)2 * (PASSES == 3 ? 2 : 1) * BM * 128;   // dynamic part (the lookup table is static LDS)
-    auto fn = k_pw_tiled<FMT, PASSES, WM, WN, MT, NT, KFULL>;
-    int rc = set_lds_limit(reinterpret_cast<const void*>(fn), lds);
-    if (rc != SLFP_OK) return rc;
-    hipLaunchKernelGGL(fn, dim3(p.nblocks), dim3(T), lds, stream, p);
-    return check_launch("slfp pointwise (tiled) kernel");
-}
-
-template <int FMT, int PASSES, int WM, int WN, int MT, int NT>
-static int launch_tiled(PwParams& p, hipStream_t stream) {
-    if (p.K % 64 == 0) return launch_tiled_k<FMT, PASSES, WM, WN, MT, NT, true>(p, stream);
-    return launch_tiled_k<FMT, PASSES, WM, WN, MT, NT, false>(p, stream);
-}
-
-template <int FMT, int PASSES, int KS>
-static int launch_stream_ks(PwParams& p, hipStream_t stream) {
-    if (p.yc) {   // code output: the single-pass table form, 16-byte channel alignment (pointwise_entry_applicable)
-        if constexpr (PASSES == 1) {
-            if (p.enc.valid && p.enc_lo.valid && !p.res && !(p.K % 4 || p.N % 16)) {
-                const size_t lds = (size_t)p.n_tiles * p.KS * 1024 + (size_t)3 * p.n_tiles * 16 * sizeof(float);   // dynamic part
-                auto fn = (p.K % 32 == 0) ? k_pw_stream<FMT, 1, KS, true, false, true, false, false, true>
-                                          : k_pw_stream<FMT, 1, KS, false, false, true, false, false, true>;
-                int rc = set_lds_limit(reinterpret_cast<const void*>(fn), lds);
-                if (rc != SLFP_OK) return rc;
-                int per_cu = resident_blocks_per_cu(reinterpret_cast<const void*>(fn), kStreamThreads, lds);
-                per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
-                int64_t grid = (int64_t)device_cu_count() * per_cu;
-                const int64_t need = ceil_div((p.M + 15) / 16, kStreamThreads / 64);
-                if (grid > need) grid = need;
-                hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kStreamThreads), lds, stream, p);
-                return check_launch("slfp pointwise (stream, code output) kernel");
-            }
-        }
-        return fail(SLFP_ERR_UNSUPPORTED, "pointwise: no code-output form of this kernel variant");
-    }
-    const bool tab = p.enc.valid != 0 && (PASSES == 1 || p.enc_lo.valid != 0);
-    // staged 128-byte stores (with the nt hint) pay where stores dominate and follow each other closely (K <= 64: pw1
-    // -14 %, pw2 -13 %) and at K = 256 (256->256 @28: 113 -> 97-105 us).  At K = 128 the layer itself loses 5-8 % (profiles/
-    // variants.py --var SLFP_PW_STG_MAXKS=4 / 8) but the depthwise layer that reads its output gains more (whole step, 200-step
-    // same-box A/B profiles/ab_env_long.sh, 3 rounds: depthwise family 1.035 -> 0.997 ms, pointwise 1.098 -> 1.112, step -1 %):
-    // staged everywhere since round 3.  K = 160 / 192 (KS 5..6: no MobileNetV1 layer) keep the direct stores they were measured with
-    const int mk = switches().pw_stg_maxks;   // experiment switch (slfp_host.hpp), read once at load
-    constexpr bool kStgDefault = KS <= 4 || KS == 8;
-    const bool stg_ks = (mk >= 0 && !p.res) ? KS <= mk : kStgDefault;   // the residual forms exist for the default rule only
-    const bool stg = tab && stg_ks && !(p.K % 4 || p.N % 4) && !switches().pw_nostg;
-    if (p.res && (!tab || (p.K % 4 || p.N % 4) || stg != kStgDefault))
-        return fail(SLFP_ERR_UNSUPPORTED, "pointwise: no residual form of this kernel variant");
-    const size_t lds = (size_t)(PASSES == 3 ? 2 : 1) * p.n_tiles * p.KS * 1024 + (size_t)3 * p.n_tiles * 16 * sizeof(float) +
-                       (stg ? (size_t)(kStreamThreads / 64) * 2048 : 0);   // dynamic part; the table (2 KiB / 64 B) is static LDS
-    const size_t lds_total = lds + (tab ? kPwTab * (PASSES == 3 ? 2 : 1) : 64);
-    auto fn = (p.K % 4 || p.N % 4) ? k_pw_stream<FMT, PASSES, KS, false, true>
-              : (p.K % 32 == 0)    ? k_pw_stream<FMT, PASSES, KS, true> : k_pw_stream<FMT, PASSES, KS, false>;
-    {
-        if (tab) fn = (p.K % 4 || p.N % 4) ? k_pw_stream<FMT, PASSES, KS, false, true, true>
-                      : (p.K % 32 == 0)    ? k_pw_stream<FMT, PASSES, KS, true, false, true> : k_pw_stream<FMT, PASSES, KS, false, false, true>;
-        if (stg) fn = (p.K % 32 == 0) ? k_pw_stream<FMT, PASSES, KS, true, false, true, true> : k_pw_stream<FMT, PASSES, KS, false, false, true, true>;
-        if (p.res) fn = (p.K % 32 == 0) ? k_pw_stream<FMT, PASSES, KS, true, false, true, kStgDefault, true> : k_pw_stream<FMT, PASSES, KS, false, false, true, kStgDefault, true>;
-    }
-    int rc = set_lds_limit(reinterpret_cast<const void*>(fn), lds);
-    if (rc != SLFP_OK) return rc;
-    // persistent grid: as many workgroups per CU as LDS and registers allow (<= 4), on every CU of the device
-    int per_cu = resident_blocks_per_cu(reinterpret_cast<const void*>(fn), kStreamThreads, lds);
-    per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
-    (void)lds_total;
-    const int64_t groups = (p.M + 15) / 16;
-    int64_t grid = (int64_t)device_cu_count() * per_cu;
-    const int64_t need = ceil_div(groups, kStreamThreads / 64);
-    if (grid > need) grid = need;
-    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kStreamThreads), lds, stream, p);
-    return check_launch("slfp pointwise (stream) kernel");
-}
-
 // CAN the LDS-resident stream kernel take this layer (W next to the tables and the staging area)?  Also what the planner asks
 // for channel counts that are even but not multiples of 4 (only that kernel has the 8-byte access path).
 bool pointwise_stream_fits(int64_t k_pad, int64_t n_pad, int passes) {
@@ -877,33 +747,197 @@ static bool stream_fits(const ConvPlan& plan, int passes, const PwParams& p) {
     return w <= (size_t)(passes == 3 ? 100 : switches().pw_stream_max_kb) * 1024;
 }
 
-template <int FMT, int PASSES>
-static int launch_pw(PwParams& p, const ConvPlan& plan, hipStream_t stream) {
-    if (stream_fits(plan, PASSES, p)) {
-        switch ((p.K + 31) / 32) {  // k-steps that hold real channels (the blob is zero-padded to p.KS)
-            case 1: return launch_stream_ks<FMT, PASSES, 1>(p, stream);
-            case 2: return launch_stream_ks<FMT, PASSES, 2>(p, stream);
-            case 3: return launch_stream_ks<FMT, PASSES, 3>(p, stream);
-            case 4: return launch_stream_ks<FMT, PASSES, 4>(p, stream);
-            case 5: case 6: return launch_stream_ks<FMT, PASSES, 6>(p, stream);
-            case 7: case 8: return launch_stream_ks<FMT, PASSES, 8>(p, stream);
-            default: break;
+// Everything a float32-input pointwise launch decides, worked out in ONE place (pw_select): the launchers below only dispatch on
+// it and pw_variant_name (slfp_debug_pw_variant) prints it, so the reported string cannot drift from what runs.
+enum PwKernel { kPwStream = 0, kPwTiled };
+struct PwSel {
+    int kernel;
+    int fmt, passes;         // template arguments FMT / PASSES
+    bool kfull;              // stream: K == 32 * KS; tiled: K % 64 == 0
+    bool tab, stg, res, yc;  // template arguments TAB / STG / RES / YC
+    int ks; bool a8;         // k_pw_stream: KS instance (1, 2, 3, 4, 6, 8), A8
+    int wm, wn, mt;          // k_pw_tiled: tiling (NT = 4 throughout)
+    int grid_cap;            // k_pw_stream: SLFP_PW_GRID, the most workgroups the persistent grid may have (0: no cap)
+};
+// staged 128-byte stores (with the nt hint) pay where stores dominate and follow each other closely (K <= 64: pw1
+// -14 %, pw2 -13 %) and at K = 256 (256->256 @28: 113 -> 97-105 us).  At K = 128 the layer itself loses 5-8 % (profiles/
+// variants.py --var SLFP_PW_STG_MAXKS=4 / 8) but the depthwise layer that reads its output gains more (whole step, 200-step
+// same-box A/B profiles/ab_env_long.sh, 3 rounds: depthwise family 1.035 -> 0.997 ms, pointwise 1.098 -> 1.112, step -1 %):
+// staged everywhere since round 3.  K = 160 / 192 (KS 5..6: no MobileNetV1 layer) keep the direct stores they were measured with
+constexpr bool stream_stg_default(int ks) { return ks <= 4 || ks == 8; }
+
+// p: K, N, res, yc and the tables (enc / enc_lo) as launch_pointwise_any fills them.  SLFP_OK, or the refusal (error text recorded).
+static int pw_select(const PwParams& p, const ConvPlan& plan, PwSel* s) {
+    *s = PwSel{};
+    s->fmt = plan.fmt_act;
+    const int passes = s->passes = (plan.fmt_act != kFmtSfp7 && plan.passes == 3) ? 3 : 1;   // SFP<3,3>: exact in fp16
+    const bool tab = p.enc.valid != 0 && (passes == 1 || p.enc_lo.valid != 0);
+    const int steps = (p.K + 31) / 32;   // k-steps that hold real channels (the blob is zero-padded to p.KS)
+    if (stream_fits(plan, passes, p) && steps >= 1 && steps <= 8) {
+        s->kernel = kPwStream;
+        s->ks = steps <= 4 ? steps : (steps <= 6 ? 6 : 8);   // the instances: 1, 2, 3, 4, 6 (five or six steps), 8 (seven or eight)
+        s->a8 = p.K % 4 || p.N % 4;
+        // KFULL loads every one of the KS k-steps without a bound: only when all of them hold real channels.  (K = 160 and 224 are
+        // multiples of 32 that fill five of six / seven of eight: the guarded form)
+        s->kfull = !s->a8 && p.K == 32 * s->ks;
+        s->grid_cap = switches().pw_grid;
+        if (p.yc) {   // code output: the single-pass table form, 16-byte channel alignment (pointwise_entry_applicable)
+            if (passes != 1 || !p.enc.valid || !p.enc_lo.valid || p.res || p.K % 4 || p.N % 16)
+                return fail(SLFP_ERR_UNSUPPORTED, "pointwise: no code-output form of this kernel variant");
+            s->tab = s->yc = true;
+            return SLFP_OK;
         }
+        const int mk = switches().pw_stg_maxks;   // experiment switch (slfp_host.hpp), read once at load
+        const bool stg_ks = (mk >= 0 && !p.res) ? s->ks <= mk : stream_stg_default(s->ks);   // the residual forms exist for the default rule only
+        s->tab = tab;
+        s->stg = tab && stg_ks && !s->a8 && !switches().pw_nostg;
+        s->res = p.res != nullptr;
+        if (p.res && (!tab || s->a8 || s->stg != stream_stg_default(s->ks)))
+            return fail(SLFP_ERR_UNSUPPORTED, "pointwise: no residual form of this kernel variant");
+        return SLFP_OK;
     }
     if (p.K % 4 || p.N % 4) return fail(SLFP_ERR_UNSUPPORTED, "pointwise: channel counts not a multiple of 4 need the stream kernel");
-    if constexpr (PASSES == 3) {
-        if (p.N > 128) return launch_tiled<FMT, 3, 1, 4, 4, 4>(p, stream);  // 64 px x 256 ch
-        if (p.N > 64) return launch_tiled<FMT, 3, 2, 2, 2, 4>(p, stream);   // 64 px x 128 ch
-        return launch_tiled<FMT, 3, 4, 1, 1, 4>(p, stream);                  // 64 px x  64 ch
-    } else {
-        // widest channel tile: fewest re-reads / re-encodes of X.  (Narrower tiles for the small-M, deep-K
-        // layers of ResNet-50's last stages -- 49-196 pixel tiles at batch 64 -- were measured: more
-        // workgroups, but the redundant encode costs more than the idle CUs did.)
-        if (p.N > 256) return launch_tiled<FMT, 1, 1, 8, 4, 4>(p, stream);  // 64 px x 512 ch, 8 waves, 2 workgroups/CU
-        if (p.N > 128) return launch_tiled<FMT, 1, 1, 4, 4, 4>(p, stream);  // 64 px x 256 ch
-        if (p.N > 64) return launch_tiled<FMT, 1, 2, 2, 2, 4>(p, stream);   // 64 px x 128 ch
-        return launch_tiled<FMT, 1, 4, 1, 1, 4>(p, stream);                  // 64 px x  64 ch
+    s->kernel = kPwTiled;
+    // widest channel tile: fewest re-reads / re-encodes of X.  (Narrower tiles for the small-M, deep-K
+    // layers of ResNet-50's last stages -- 49-196 pixel tiles at batch 64 -- were measured: more
+    // workgroups, but the redundant encode costs more than the idle CUs did.)
+    if (p.N > 256 && passes == 1) { s->wm = 1; s->wn = 8; s->mt = 4; }   // 64 px x 512 ch, 8 waves, 2 workgroups/CU
+    else if (p.N > 128) { s->wm = 1; s->wn = 4; s->mt = 4; }             // 64 px x 256 ch
+    else if (p.N > 64) { s->wm = 2; s->wn = 2; s->mt = 2; }              // 64 px x 128 ch
+    else { s->wm = 4; s->wn = 1; s->mt = 1; }                            // 64 px x  64 ch
+    s->kfull = p.K % 64 == 0;
+    if (p.yc) {   // code output: the single-pass table form only (pointwise_entry_applicable)
+        if (passes != 1 || !p.enc.valid || !p.enc_lo.valid || p.res)
+            return fail(SLFP_ERR_UNSUPPORTED, "pointwise: no code-output form of this kernel variant");
+        s->tab = s->yc = true;
+        return SLFP_OK;
     }
+    s->tab = tab;
+    s->stg = tab && !switches().pw_nostg;   // experiment switch (slfp_host.hpp), read once at load
+    s->res = p.res != nullptr;
+    if (p.res && !s->stg)   // residual operand: the table quantizer + staged epilogue form only (pointwise_res_applicable asks for both)
+        return fail(SLFP_ERR_UNSUPPORTED, "pointwise: no residual form of this kernel variant");
+    return SLFP_OK;
+}
+
+static const char* fmt_word(int fmt) { return fmt == kFmtSfp7 ? "sfp7" : "act8"; }
+
+static const char* pw_sel_name(const PwSel& s) {
+    static thread_local char buf[80];
+    const char* tail = s.res ? "/res" : (s.yc ? "/yc" : "");
+    int n;
+    if (s.kernel == kPwStream)
+        n = snprintf(buf, sizeof buf, "stream/ks%d/%s/%s/%s/p%d/%s%s", s.ks, s.a8 ? "a8" : (s.kfull ? "kfull" : "kpart"), s.tab ? "tab" : "long",
+                     s.stg ? "stg" : "dir", s.passes, fmt_word(s.fmt), tail);
+    else
+        n = snprintf(buf, sizeof buf, "tiled/%d%d%d/%s/%s/%s/p%d/%s%s", s.wm, s.wn, s.mt, s.kfull ? "kfull" : "kpart", s.tab ? "tab" : "long",
+                     s.stg ? "stg" : "dir", s.passes, fmt_word(s.fmt), tail);
+    if (s.kernel == kPwStream && s.grid_cap > 0) snprintf(buf + n, sizeof buf - n, "/grid%d", s.grid_cap);
+    return buf;
+}
+
+// dry (here and in the launchers below): stop once the instance is found, before anything touches a device -- pw_variant_name's check
+// that the launcher has the instance the selection names
+template <int FMT, int PASSES, int WM, int WN, int MT, bool KFULL>
+static int launch_tiled_k(PwParams& p, const PwSel& s, hipStream_t stream, bool dry) {
+    constexpr int NT = 4;
+    constexpr int BM = WM * MT * 16, BN = WN * NT * 16, T = 64 * WM * WN;
+    void (*fn)(const PwParams) = nullptr;
+    if (s.yc) {
+        if constexpr (PASSES == 1) fn = k_pw_tiled<FMT, 1, WM, WN, MT, NT, KFULL, true, false, false, true>;
+    } else if (s.res) {
+        fn = k_pw_tiled<FMT, PASSES, WM, WN, MT, NT, KFULL, true, true, true>;
+    } else if (s.stg) {
+        fn = k_pw_tiled<FMT, PASSES, WM, WN, MT, NT, KFULL, true, true>;
+    } else if (s.tab) {
+        fn = k_pw_tiled<FMT, PASSES, WM, WN, MT, NT, KFULL, true>;
+    } else {
+        fn = k_pw_tiled<FMT, PASSES, WM, WN, MT, NT, KFULL>;
+    }
+    if (!fn) return fail(SLFP_ERR_UNSUPPORTED, "pointwise: no tiled kernel instance for %s", pw_sel_name(s));
+    if (dry) return SLFP_OK;
+    p.n_blocks = (uint32_t)ceil_div((int64_t)p.N, BN);
+    // (Workgroups that own fewer rows than their tile -- 49 = a quarter image instead of 64, for an integral number of
+    // rounds on the 512 resident slots -- were measured: no gain, 61-64 vs 60 us on 512->512.  A workgroup's time is set
+    // by streaming all of W from L2, not by its rows.)
+    p.rb = BM;
+    p.m_blocks = (uint32_t)ceil_div(p.M, p.rb);
+    const int64_t nblocks = (int64_t)p.m_blocks * p.n_blocks;
+    if (nblocks > 0x7FFFFFFF) return fail(SLFP_ERR_UNSUPPORTED, "pointwise: grid too large");
+    p.nblocks = (uint32_t)nblocks;
+    // dynamic part (the tables are static LDS): the X double buffer, and the per-wave staging area of the staged epilogue
+    const size_t lds = (size_t)2 * (PASSES == 3 ? 2 : 1) * BM * 128 + (s.stg ? (size_t)(T / 64) * 16 * kStgRow : 0);
+    int rc = set_lds_limit(reinterpret_cast<const void*>(fn), lds);
+    if (rc != SLFP_OK) return rc;
+    hipLaunchKernelGGL(fn, dim3(p.nblocks), dim3(T), lds, stream, p);
+    return check_launch("slfp pointwise (tiled) kernel");
+}
+
+template <int FMT, int PASSES, int WM, int WN, int MT>
+static int launch_tiled(PwParams& p, const PwSel& s, hipStream_t stream, bool dry) {
+    if (s.kfull) return launch_tiled_k<FMT, PASSES, WM, WN, MT, true>(p, s, stream, dry);
+    return launch_tiled_k<FMT, PASSES, WM, WN, MT, false>(p, s, stream, dry);
+}
+
+template <int FMT, int PASSES, int KS>
+static int launch_stream_ks(PwParams& p, const PwSel& s, hipStream_t stream, bool dry) {
+    constexpr bool kStgDefault = stream_stg_default(KS);
+    void (*fn)(const PwParams) = nullptr;
+    if (s.yc) {
+        if constexpr (PASSES == 1)
+            fn = s.kfull ? k_pw_stream<FMT, 1, KS, true, false, true, false, false, true> : k_pw_stream<FMT, 1, KS, false, false, true, false, false, true>;
+    } else if (s.res) {
+        if (s.stg == kStgDefault)
+            fn = s.kfull ? k_pw_stream<FMT, PASSES, KS, true, false, true, kStgDefault, true> : k_pw_stream<FMT, PASSES, KS, false, false, true, kStgDefault, true>;
+    } else if (s.a8) {
+        fn = s.tab ? k_pw_stream<FMT, PASSES, KS, false, true, true> : k_pw_stream<FMT, PASSES, KS, false, true>;
+    } else if (s.stg) {
+        fn = s.kfull ? k_pw_stream<FMT, PASSES, KS, true, false, true, true> : k_pw_stream<FMT, PASSES, KS, false, false, true, true>;
+    } else if (s.tab) {
+        fn = s.kfull ? k_pw_stream<FMT, PASSES, KS, true, false, true> : k_pw_stream<FMT, PASSES, KS, false, false, true>;
+    } else {
+        fn = s.kfull ? k_pw_stream<FMT, PASSES, KS, true> : k_pw_stream<FMT, PASSES, KS, false>;
+    }
+    if (!fn) return fail(SLFP_ERR_UNSUPPORTED, "pointwise: no stream kernel instance for %s", pw_sel_name(s));
+    if (dry) return SLFP_OK;
+    const size_t lds = (size_t)(PASSES == 3 ? 2 : 1) * p.n_tiles * p.KS * 1024 + (size_t)3 * p.n_tiles * 16 * sizeof(float) +
+                       (s.stg ? (size_t)(kStreamThreads / 64) * 2048 : 0);   // dynamic part; the tables are static LDS
+    int rc = set_lds_limit(reinterpret_cast<const void*>(fn), lds);
+    if (rc != SLFP_OK) return rc;
+    // persistent grid: as many workgroups per CU as LDS and registers allow (<= 4), on every CU of the device
+    int per_cu = resident_blocks_per_cu(reinterpret_cast<const void*>(fn), kStreamThreads, lds);
+    per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
+    const int64_t groups = (p.M + 15) / 16;
+    int64_t grid = (int64_t)device_cu_count() * per_cu;
+    const int64_t need = ceil_div(groups, kStreamThreads / 64);
+    if (grid > need) grid = need;
+    if (s.grid_cap > 0 && grid > s.grid_cap) grid = s.grid_cap;   // SLFP_PW_GRID: several trips of the persistent loop at small shapes
+    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kStreamThreads), lds, stream, p);
+    return check_launch("slfp pointwise (stream) kernel");
+}
+
+template <int FMT, int PASSES>
+static int launch_pw(PwParams& p, const PwSel& s, hipStream_t stream, bool dry) {
+    if (s.kernel == kPwStream) {
+        switch (s.ks) {
+            case 1: return launch_stream_ks<FMT, PASSES, 1>(p, s, stream, dry);
+            case 2: return launch_stream_ks<FMT, PASSES, 2>(p, s, stream, dry);
+            case 3: return launch_stream_ks<FMT, PASSES, 3>(p, s, stream, dry);
+            case 4: return launch_stream_ks<FMT, PASSES, 4>(p, s, stream, dry);
+            case 6: return launch_stream_ks<FMT, PASSES, 6>(p, s, stream, dry);
+            case 8: return launch_stream_ks<FMT, PASSES, 8>(p, s, stream, dry);
+            default: break;
+        }
+        return fail(SLFP_ERR_UNSUPPORTED, "pointwise: no stream kernel instance for %s", pw_sel_name(s));
+    }
+    const int t = s.wm * 100 + s.wn * 10 + s.mt;
+    if constexpr (PASSES == 1) {
+        if (t == 184) return launch_tiled<FMT, 1, 1, 8, 4>(p, s, stream, dry);
+    }
+    if (t == 144) return launch_tiled<FMT, PASSES, 1, 4, 4>(p, s, stream, dry);
+    if (t == 222) return launch_tiled<FMT, PASSES, 2, 2, 2>(p, s, stream, dry);
+    if (t == 411) return launch_tiled<FMT, PASSES, 4, 1, 1>(p, s, stream, dry);
+    return fail(SLFP_ERR_UNSUPPORTED, "pointwise: no tiled kernel instance for %s", pw_sel_name(s));
 }
 
 // Does a residual form of the kernel launch_pointwise would pick exist?  Host-only: the planner's answer, the quantizer table
@@ -943,23 +977,19 @@ int launch_pointwise_entry(const slfp_conv2d_desc& d, const ConvPlan& plan, cons
     return launch_pointwise_any(d, plan, x, wfrag, bias, post, nullptr, stream, nullptr, reinterpret_cast<uint8_t*>(y_codes), io.y_ka, io.y_fmt);
 }
 
-static int launch_pointwise_any(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x, const void* wfrag, const float* bias,
-                                const PostOp& post, float* y, hipStream_t stream, const float* res, uint8_t* yc, float y_ka, int y_fmt) {
-    PwParams p;
-    p.post = post;
-    p.x = x; p.bias = bias; p.y = y; p.res = res;
-    p.yc = yc; p.sgn = post.relu ? 0 : 1; p.fmt_out = y_fmt;
+static int pw_dispatch(PwParams& p, const PwSel& s, hipStream_t stream, bool dry) {
+    if (s.fmt == kFmtSfp7) return launch_pw<kFmtSfp7, 1>(p, s, stream, dry);  // exact in fp16
+    if (s.passes == 3) return launch_pw<kFmtAct8, 3>(p, s, stream, dry);
+    return launch_pw<kFmtAct8, 1>(p, s, stream, dry);
+}
+
+// The host-side part of PwParams that the selection reads: channel counts, which operands are present, the quantizer tables.
+static int pw_host_params(PwParams& p, const slfp_conv2d_desc& d, const ConvPlan& plan, const float* res, uint8_t* yc, float y_ka, int y_fmt) {
+    p.res = res;
+    p.yc = yc; p.fmt_out = y_fmt;
     p.K = (int)d.c_in; p.N = (int)d.c_out;
     p.KS = (int)(plan.k_pad / 32);
     p.n_tiles = (int)(plan.n_pad / 16);
-    p.whi = reinterpret_cast<const _Float16*>(wfrag);
-    p.wlo = p.whi + (size_t)plan.n_pad * plan.k_pad;
-    p.H = (int)d.h; p.W = (int)d.w; p.Ho = (int)plan.h_out; p.Wo = (int)plan.w_out; p.S = d.stride_h;
-    p.M = d.n * plan.h_out * plan.w_out;
-    p.sd = make_scale_div(d.ka, 4);  // x / (Ka/16) == 16 * (x / Ka)
-#ifdef SLFP_PW_STAMPS
-    { const char* e = getenv("SLFP_PW_DBG"); p.dbg = e ? reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 16)) : nullptr; }
-#endif
     p.enc.valid = 0;
     p.enc_lo.valid = 0;
     if (!switches().pw_notab) {   // experiment switch (slfp_host.hpp), read once at load
@@ -975,15 +1005,46 @@ static int launch_pointwise_any(const slfp_conv2d_desc& d, const ConvPlan& plan,
             return fail(SLFP_ERR_UNSUPPORTED, "pointwise: no code table for the consumer's scale %g in the single-pass table form", (double)y_ka);
         p.enc_lo = enc_compact(*t);
     }
+    return SLFP_OK;
+}
+
+const char* pw_variant_name(const slfp_conv2d_desc& d, const ConvPlan& plan, bool has_res, bool y_codes, float y_ka, int y_fmt) {
+    if (plan.family != kPointwise) return "none";
+    PwParams p = {};   // only the presence of res / yc matters: nothing is dereferenced
+    static float some_res;
+    static uint8_t some_codes;
+    PwSel s;
+    if (pw_host_params(p, d, plan, has_res ? &some_res : nullptr, y_codes ? &some_codes : nullptr, y_ka, y_fmt) != SLFP_OK) return "none";
+    if (pw_select(p, plan, &s) != SLFP_OK || pw_dispatch(p, s, nullptr, true) != SLFP_OK) return "none";
+    return pw_sel_name(s);
+}
+
+static int launch_pointwise_any(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x, const void* wfrag, const float* bias,
+                                const PostOp& post, float* y, hipStream_t stream, const float* res, uint8_t* yc, float y_ka, int y_fmt) {
+    PwParams p;
+    p.post = post;
+    p.x = x; p.bias = bias; p.y = y;
+    p.sgn = post.relu ? 0 : 1;
+    int rc = pw_host_params(p, d, plan, res, yc, y_ka, y_fmt);
+    if (rc != SLFP_OK) return rc;
+    p.whi = reinterpret_cast<const _Float16*>(wfrag);
+    p.wlo = p.whi + (size_t)plan.n_pad * plan.k_pad;
+    p.H = (int)d.h; p.W = (int)d.w; p.Ho = (int)plan.h_out; p.Wo = (int)plan.w_out; p.S = d.stride_h;
+    p.M = d.n * plan.h_out * plan.w_out;
+    p.sd = make_scale_div(d.ka, 4);  // x / (Ka/16) == 16 * (x / Ka)
+#ifdef SLFP_PW_STAMPS
+    { const char* e = getenv("SLFP_PW_DBG"); p.dbg = e ? reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 16)) : nullptr; }
+#endif
     p.s1 = plan.s1; p.s2 = plan.s2; p.s1x = plan.s1 * (1.0f / 256.0f);
     {   // staged stores always carry the nt hint: a size threshold as in conv_dw2.hip (plain stores for outputs that fit the
         // Infinity Cache) measured 1.5 % SLOWER on the whole net here (profiles/ab_env_wn.sh); SLFP_PW_NT_MIN_MB: experiment switch
         const int64_t min_mb = switches().pw_nt_min_mb;
         p.nt_out = ((SLFP_NT_PW_STG & 2) && p.M * p.N * 4 >= (min_mb << 20)) ? 1 : 0;
     }
-    if (plan.fmt_act == kFmtSfp7) return launch_pw<kFmtSfp7, 1>(p, plan, stream);  // exact in fp16
-    if (plan.passes == 3) return launch_pw<kFmtAct8, 3>(p, plan, stream);
-    return launch_pw<kFmtAct8, 1>(p, plan, stream);
+    PwSel s;
+    rc = pw_select(p, plan, &s);
+    if (rc != SLFP_OK) return rc;
+    return pw_dispatch(p, s, stream, false);
 }
 
 }  // namespace slfp

@@ -682,27 +682,88 @@ bool pwc_applicable(const slfp_conv2d_desc& d, const ConvPlan& plan, int post_fl
     return d.c_in % 64 == 0;
 }
 
+// Everything a code-input pointwise launch decides, worked out in ONE place (pwc_select): the launchers below only dispatch on it
+// and pwc_variant_name (slfp_debug_pw_variant) prints it, so the reported string cannot drift from what runs.
+enum PwcKernel { kPwcStream = 0, kPwcSlice, kPwcTiled };
+struct PwcSel {
+    int kernel;
+    int fmt;                 // template argument FMT
+    bool yc, res, dual;      // template arguments YC / RES / DUAL
+    int ks; bool xw, half;   // k_pwc_stream: KS, XW, HALF
+    int nts;                 // k_pwc_slice: NTS (4 or 8)
+    int wm, wn, mt;          // k_pwc_tiled: tiling
+    int grid_cap;            // SLFP_PW_GRID: k_pwc_stream: the most workgroups; k_pwc_slice: the most rank groups (0: no cap)
+};
+
+// slice kernel: K a multiple of 256, the slice's W (NTS tiles x K) <= 128 KiB, N a multiple of 16 * NTS
+static int pwc_slice_nts(int K, int N, int n_tiles) {
+    if (K != 256 || !switches().pwc_slice) return 0;   // see k_pwc_slice: deeper layers stay on k_pwc_tiled
+    for (int nts : {8, 4}) {
+        if ((size_t)nts * 16 * K * 2 <= 128 * 1024 && N % (nts * 16) == 0 && n_tiles % nts == 0) return nts;
+    }
+    return 0;
+}
+
+static int pwc_select(int K, int N, const ConvPlan& plan, bool y_codes, bool has_res, bool has_dual, PwcSel* s) {
+    *s = PwcSel{};
+    s->fmt = plan.fmt_act == kFmtSfp7 ? kFmtSfp7 : kFmtAct8;
+    s->yc = y_codes; s->dual = !y_codes && has_dual; s->res = !y_codes && (has_res || has_dual);
+    if (const int nts = pwc_slice_nts(K, N, (int)(plan.n_pad / 16))) {
+        s->kernel = kPwcSlice;
+        s->nts = nts;
+        s->grid_cap = switches().pw_grid;
+        return SLFP_OK;
+    }
+    if (pwc_stream_fits(plan)) {
+        s->kernel = kPwcStream;
+        s->grid_cap = switches().pw_grid;
+        if (K == 16 || K == 48) { s->ks = (K + 16) / 32; s->half = true; return SLFP_OK; }
+        s->ks = K / 32;
+        s->xw = s->ks % 2 == 0;   // K a multiple of 64: 16-byte code loads + transpose
+        if (K % 32 == 0 && (s->ks == 1 || s->ks == 2 || s->ks == 3 || s->ks == 4 || s->ks == 8)) return SLFP_OK;
+        return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): unsupported channel count %d", K);
+    }
+    s->kernel = kPwcTiled;
+    if (N > 256) { s->wm = 1; s->wn = 8; s->mt = 4; }        // 64 px x 512 ch
+    else if (N > 128) { s->wm = 1; s->wn = 4; s->mt = 4; }   // 64 px x 256 ch
+    else if (N > 64) { s->wm = 2; s->wn = 2; s->mt = 2; }    // 64 px x 128 ch
+    else { s->wm = 4; s->wn = 1; s->mt = 1; }                // 64 px x  64 ch
+    return SLFP_OK;
+}
+
+static const char* pwc_sel_name(const PwcSel& s) {
+    static thread_local char buf[64];
+    const char* fmt = s.fmt == kFmtSfp7 ? "sfp7" : "act8";
+    const char* form = s.yc ? "yc" : (s.dual ? "res/dual" : (s.res ? "res" : "f32"));
+    int n;
+    if (s.kernel == kPwcStream) n = snprintf(buf, sizeof buf, "pwc-stream/ks%d/%s/%s/%s", s.ks, s.half ? "half" : (s.xw ? "xw" : "dw"), fmt, form);
+    else if (s.kernel == kPwcSlice) n = snprintf(buf, sizeof buf, "slice/nts%d/%s/%s", s.nts, fmt, form);
+    else n = snprintf(buf, sizeof buf, "pwc-tiled/%d%d%d/%s/%s", s.wm, s.wn, s.mt, fmt, form);
+    if (s.kernel != kPwcTiled && s.grid_cap > 0) snprintf(buf + n, sizeof buf - n, "/grid%d", s.grid_cap);
+    return buf;
+}
+
 template <int FMT, int KS, bool XW, bool HALF = false>
-static int launch_pwc_stream(PwcParams& p, bool y_codes, hipStream_t stream) {
+static int launch_pwc_stream(PwcParams& p, const PwcSel& s, hipStream_t stream, bool dry) {
     const size_t lds = (size_t)p.n_tiles * p.KS * 1024 + (size_t)3 * p.n_tiles * 16 * sizeof(float);
-    const size_t lds_total = lds + 1024 + ((y_codes || p.yc) ? kPwTab : 16);
-    auto fn = y_codes ? k_pwc_stream<FMT, KS, XW, true, false, HALF>
-                      : (p.yc ? k_pwc_stream<FMT, KS, XW, false, true, HALF, true> : (p.res ? k_pwc_stream<FMT, KS, XW, false, true, HALF> : k_pwc_stream<FMT, KS, XW, false, false, HALF>));
+    auto fn = s.yc ? k_pwc_stream<FMT, KS, XW, true, false, HALF>
+                   : (s.dual ? k_pwc_stream<FMT, KS, XW, false, true, HALF, true> : (s.res ? k_pwc_stream<FMT, KS, XW, false, true, HALF> : k_pwc_stream<FMT, KS, XW, false, false, HALF>));
+    if (dry) return SLFP_OK;   // the instance exists: pwc_variant_name's check, before anything touches a device
     int rc = raise_lds_limit(reinterpret_cast<const void*>(fn), lds);
     if (rc != SLFP_OK) return rc;
     int per_cu = resident_blocks_per_cu(reinterpret_cast<const void*>(fn), kPwcThreads, lds);
     per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
-    (void)lds_total;
     const int64_t groups = (p.M + 15) / 16;
     int64_t grid = (int64_t)device_cu_count() * per_cu;
     const int64_t need = ceil_div(groups, kPwcThreads / 64);
     if (grid > need) grid = need;
+    if (s.grid_cap > 0 && grid > s.grid_cap) grid = s.grid_cap;   // SLFP_PW_GRID: several trips of the persistent loop at small shapes
     hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kPwcThreads), lds, stream, p);
     return check_launch("slfp pointwise (codes, stream) kernel");
 }
 
 template <int FMT, int WM, int WN, int MT>
-static int launch_pwc_tiled(PwcParams& p, bool y_codes, hipStream_t stream) {
+static int launch_pwc_tiled(PwcParams& p, const PwcSel& s, hipStream_t stream, bool dry) {
     constexpr int BM = WM * MT * 16, BN = WN * 4 * 16, T = 64 * WM * WN;
     p.n_blocks = (uint32_t)ceil_div((int64_t)p.N, BN);
     p.rb = BM;
@@ -710,29 +771,22 @@ static int launch_pwc_tiled(PwcParams& p, bool y_codes, hipStream_t stream) {
     const int64_t nblocks = (int64_t)p.m_blocks * p.n_blocks;
     if (nblocks > 0x7FFFFFFF) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): grid too large");
     p.nblocks = (uint32_t)nblocks;
-    const size_t lds = (size_t)2 * BM * 128 + (y_codes ? 0 : (size_t)(T / 64) * 16 * kStgRow);
-    auto fn = y_codes ? k_pwc_tiled<FMT, WM, WN, MT, true>
-                      : (p.yc ? k_pwc_tiled<FMT, WM, WN, MT, false, true, true> : (p.res ? k_pwc_tiled<FMT, WM, WN, MT, false, true> : k_pwc_tiled<FMT, WM, WN, MT, false>));
+    const size_t lds = (size_t)2 * BM * 128 + (s.yc ? 0 : (size_t)(T / 64) * 16 * kStgRow);
+    auto fn = s.yc ? k_pwc_tiled<FMT, WM, WN, MT, true>
+                   : (s.dual ? k_pwc_tiled<FMT, WM, WN, MT, false, true, true> : (s.res ? k_pwc_tiled<FMT, WM, WN, MT, false, true> : k_pwc_tiled<FMT, WM, WN, MT, false>));
+    if (dry) return SLFP_OK;   // the instance exists: pwc_variant_name's check, before anything touches a device
     int rc = raise_lds_limit(reinterpret_cast<const void*>(fn), lds);
     if (rc != SLFP_OK) return rc;
     hipLaunchKernelGGL(fn, dim3(p.nblocks), dim3(T), lds, stream, p);
     return check_launch("slfp pointwise (codes, tiled) kernel");
 }
 
-// slice kernel: K a multiple of 256, the slice's W (NTS tiles x K) <= 128 KiB, N a multiple of 16 * NTS
-static int pwc_slice_nts(const PwcParams& p) {
-    if (p.K != 256 || !switches().pwc_slice) return 0;   // see k_pwc_slice: deeper layers stay on k_pwc_tiled
-    for (int nts : {8, 4}) {
-        if ((size_t)nts * 16 * p.K * 2 <= 128 * 1024 && p.N % (nts * 16) == 0 && p.n_tiles % nts == 0) return nts;
-    }
-    return 0;
-}
-
 template <int FMT, int NTS>
-static int launch_pwc_slice(PwcParams& p, bool y_codes, hipStream_t stream) {
+static int launch_pwc_slice(PwcParams& p, const PwcSel& s, hipStream_t stream, bool dry) {
     const size_t lds = (size_t)NTS * p.KS * 1024 + (size_t)3 * NTS * 16 * sizeof(float);
-    auto fn = y_codes ? k_pwc_slice<FMT, NTS, true>
-                      : (p.yc ? k_pwc_slice<FMT, NTS, false, true, true> : (p.res ? k_pwc_slice<FMT, NTS, false, true> : k_pwc_slice<FMT, NTS, false>));
+    auto fn = s.yc ? k_pwc_slice<FMT, NTS, true>
+                   : (s.dual ? k_pwc_slice<FMT, NTS, false, true, true> : (s.res ? k_pwc_slice<FMT, NTS, false, true> : k_pwc_slice<FMT, NTS, false>));
+    if (dry) return SLFP_OK;   // the instance exists: pwc_variant_name's check, before anything touches a device
     int rc = raise_lds_limit(reinterpret_cast<const void*>(fn), lds);
     if (rc != SLFP_OK) return rc;
     int per_cu = resident_blocks_per_cu(reinterpret_cast<const void*>(fn), kSliceThreads, lds);
@@ -745,33 +799,39 @@ static int launch_pwc_slice(PwcParams& p, bool y_codes, hipStream_t stream) {
     const int64_t units = (p.M + 15) / 16;
     const int64_t need = ceil_div(units, (int64_t)8 * (kSliceThreads / 64));   // ranks needed, in multiples of 8 (one per XCD)
     if (groups > need) groups = need < 1 ? 1 : need;
+    if (s.grid_cap > 0 && groups > s.grid_cap) groups = s.grid_cap;   // SLFP_PW_GRID: the grid stays a multiple of 8 * n_slices
     const int64_t grid = groups * 8 * n_slices;
     hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kSliceThreads), lds, stream, p);
     return check_launch("slfp pointwise (codes, slice) kernel");
 }
 
 template <int FMT>
-static int launch_pwc_fmt(PwcParams& p, const ConvPlan& plan, bool y_codes, hipStream_t stream) {
-    if (const int nts = pwc_slice_nts(p)) {
-        if (nts == 8) return launch_pwc_slice<FMT, 8>(p, y_codes, stream);
-        return launch_pwc_slice<FMT, 4>(p, y_codes, stream);
-    }
-    if (pwc_stream_fits(plan)) {
-        if (p.K == 16) return launch_pwc_stream<FMT, 1, false, true>(p, y_codes, stream);
-        if (p.K == 48) return launch_pwc_stream<FMT, 2, false, true>(p, y_codes, stream);
-        switch (p.K / 32) {
-            case 1: return launch_pwc_stream<FMT, 1, false>(p, y_codes, stream);
-            case 2: return launch_pwc_stream<FMT, 2, true>(p, y_codes, stream);
-            case 3: return launch_pwc_stream<FMT, 3, false>(p, y_codes, stream);
-            case 4: return launch_pwc_stream<FMT, 4, true>(p, y_codes, stream);
-            case 8: return launch_pwc_stream<FMT, 8, true>(p, y_codes, stream);
-            default: return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): unsupported channel count %d", p.K);
+static int launch_pwc_fmt(PwcParams& p, const PwcSel& s, hipStream_t stream, bool dry) {
+    if (s.kernel == kPwcSlice) {
+        if (s.nts == 8) return launch_pwc_slice<FMT, 8>(p, s, stream, dry);
+        if (s.nts == 4) return launch_pwc_slice<FMT, 4>(p, s, stream, dry);
+    } else if (s.kernel == kPwcStream) {
+        if (s.half) {
+            if (s.ks == 1) return launch_pwc_stream<FMT, 1, false, true>(p, s, stream, dry);
+            if (s.ks == 2) return launch_pwc_stream<FMT, 2, false, true>(p, s, stream, dry);
+        } else {
+            switch (s.ks * 2 + (s.xw ? 1 : 0)) {
+                case 2: return launch_pwc_stream<FMT, 1, false>(p, s, stream, dry);
+                case 5: return launch_pwc_stream<FMT, 2, true>(p, s, stream, dry);
+                case 6: return launch_pwc_stream<FMT, 3, false>(p, s, stream, dry);
+                case 9: return launch_pwc_stream<FMT, 4, true>(p, s, stream, dry);
+                case 17: return launch_pwc_stream<FMT, 8, true>(p, s, stream, dry);
+                default: break;
+            }
         }
+    } else {
+        const int t = s.wm * 100 + s.wn * 10 + s.mt;
+        if (t == 184) return launch_pwc_tiled<FMT, 1, 8, 4>(p, s, stream, dry);
+        if (t == 144) return launch_pwc_tiled<FMT, 1, 4, 4>(p, s, stream, dry);
+        if (t == 222) return launch_pwc_tiled<FMT, 2, 2, 2>(p, s, stream, dry);
+        if (t == 411) return launch_pwc_tiled<FMT, 4, 1, 1>(p, s, stream, dry);
     }
-    if (p.N > 256) return launch_pwc_tiled<FMT, 1, 8, 4>(p, y_codes, stream);   // 64 px x 512 ch
-    if (p.N > 128) return launch_pwc_tiled<FMT, 1, 4, 4>(p, y_codes, stream);   // 64 px x 256 ch
-    if (p.N > 64) return launch_pwc_tiled<FMT, 2, 2, 2>(p, y_codes, stream);    // 64 px x 128 ch
-    return launch_pwc_tiled<FMT, 4, 1, 1>(p, y_codes, stream);                   // 64 px x  64 ch
+    return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): no kernel instance for %s", pwc_sel_name(s));
 }
 
 int launch_pwc(const slfp_conv2d_desc& d, const ConvPlan& plan, const uint8_t* x, const void* wfrag, const float* bias,
@@ -802,8 +862,19 @@ int launch_pwc(const slfp_conv2d_desc& d, const ConvPlan& plan, const uint8_t* x
         if (!t->valid) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): no code table for the consumer's scale %g", (double)io.y_ka);
         p.enc = *t;
     }
-    if (plan.fmt_act == kFmtSfp7) return launch_pwc_fmt<kFmtSfp7>(p, plan, y_codes, stream);
-    return launch_pwc_fmt<kFmtAct8>(p, plan, y_codes, stream);
+    PwcSel s;
+    const int rc = pwc_select(p.K, p.N, plan, y_codes, res != nullptr, res_codes != nullptr, &s);
+    if (rc != SLFP_OK) return rc;
+    if (s.fmt == kFmtSfp7) return launch_pwc_fmt<kFmtSfp7>(p, s, stream, false);
+    return launch_pwc_fmt<kFmtAct8>(p, s, stream, false);
+}
+
+const char* pwc_variant_name(const slfp_conv2d_desc& d, const ConvPlan& plan, bool y_codes, bool has_res, bool has_dual) {
+    PwcParams p = {};   // the dry dispatch reads none of the pointers
+    PwcSel s;
+    if (plan.family != kPointwise || pwc_select((int)d.c_in, (int)d.c_out, plan, y_codes, has_res, has_dual, &s) != SLFP_OK) return "none";
+    if ((s.fmt == kFmtSfp7 ? launch_pwc_fmt<kFmtSfp7>(p, s, nullptr, true) : launch_pwc_fmt<kFmtAct8>(p, s, nullptr, true)) != SLFP_OK) return "none";
+    return pwc_sel_name(s);
 }
 
 }  // namespace slfp

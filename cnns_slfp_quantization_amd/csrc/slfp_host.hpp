@@ -46,6 +46,8 @@ inline ScaleDiv make_scale_div(float d, int esh = 0) {
 //   SLFP_PW_NOSTG       pointwise kernels without the LDS-staged whole-line stores
 //   SLFP_PW_NOTAB       pointwise kernels on the long-form quantizer
 //   SLFP_PW_STG_MAXKS   stream kernel: staged stores up to this many k-steps (default: 1, 2 and 8)
+//   SLFP_PW_GRID=<n>    persistent pointwise kernels: at most n workgroups (k_pw_stream, k_pwc_stream) / n rank groups of 8 x n_slices
+//                       workgroups (k_pwc_slice), so that a small layer runs several trips of the persistent loop (tests); unset: no cap
 //   SLFP_PW_NT_MIN_MB / SLFP_DW_NT_MIN_MB   output size from which staged / depthwise stores carry the nt hint
 //   SLFP_DW_ROWS        0: stride-2 depthwise layers stay on the tile kernel (conv_dw2.hip); unset: the measured rule
 //                       (dw3x3_rows_applicable); any other value: a mask of size classes that take conv_dw3.hip (A/B runs)
@@ -63,6 +65,7 @@ struct Switches {
     bool dense_res;           // SLFP_DENSE_NORES unsets it: 3x3 stride-1 layers with C_in <= 64 on the persistent weights-resident k_dense3x3_res
     bool stem_im2row;         // SLFP_STEM_IM2ROW: large-kernel stems through the im2row workspace (the round-1 form; A/B of k_stem_rows)
     int dw_rows;              // SLFP_DW_ROWS: -1 (unset) the measured rule, 0 never, else bit k = size class k (dw_rows_class) on k_dw3x3_rows
+    int pw_grid;              // SLFP_PW_GRID: cap of the persistent pointwise grids (0: unset, no cap)
     int pw_stream_max_kb;     // SLFP_PW_STREAM_MAX_KB: largest W (KiB, fp16) the float32-interface path gives to the LDS-resident stream kernel (default 30; its capacity is 128)
 };
 const Switches& switches();
@@ -128,6 +131,10 @@ inline int dw_rows_class(int64_t h_out, int64_t w_out) {
 int launch_pointwise(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const void* wfrag,
                      const float* bias, const PostOp& post, float* y, hipStream_t stream, const float* res = nullptr);
 bool pointwise_res_applicable(const slfp_conv2d_desc& d, const ConvPlan& p);
+// what launch_pointwise (has_res: with a residual operand) / launch_pointwise_entry (y_codes: for the reader y_ka, y_fmt) decide for
+// this layer under the switches read at load, printed from the selection they consume (slfp_debug_pw_variant; host only).  "none"
+// outside the family or where the launch would be refused; valid until the next call on the same thread.
+const char* pw_variant_name(const slfp_conv2d_desc& d, const ConvPlan& p, bool has_res, bool y_codes, float y_ka, int y_fmt);
 // ---- 1-byte activation codes between layers (slfp_codes.hpp; slfp_conv2d_fwd_codes) ----
 // How a layer's input arrives and its output leaves: float32, or the extended codes of QA(. / ka) in format fmt.
 struct CodeIo {
@@ -151,6 +158,8 @@ int launch_pointwise_entry(const slfp_conv2d_desc& d, const ConvPlan& p, const f
 bool pwc_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, int post_flags, bool y_codes);
 int launch_pwc(const slfp_conv2d_desc& d, const ConvPlan& p, const uint8_t* x, const void* wfrag, const float* bias,
                const PostOp& post, void* y, const CodeIo& io, hipStream_t stream, const float* res = nullptr, void* res_codes = nullptr);
+// the same for launch_pwc (codes in): code or float32 output, residual operand, second (code) output
+const char* pwc_variant_name(const slfp_conv2d_desc& d, const ConvPlan& p, bool y_codes, bool has_res, bool has_dual);
 // res_codes (with res, float32 y, C_out a multiple of 16; slfp_conv2d_fwd_res_codes): the uint8 tensor that receives, next to y, the codes
 // of y for the reader io.y_ka / io.y_fmt describe
 // the MobileNetV1 image stem with code output (conv_direct.hip)

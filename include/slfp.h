@@ -115,6 +115,20 @@ const char* slfp_debug_dw3x3_variant(const slfp_conv2d_desc* d, int has_post);
  * is printed from the selection the launch consumes.  Host only: no device is touched.  The pointer stays valid
  * until the next call on the same thread. */
 const char* slfp_debug_dense_variant(const slfp_conv2d_desc* d, int x_codes);
+/* Which pointwise (1x1) kernel instance (csrc/conv_pw.hip, csrc/conv_pw_codes.hip) the matching forward entry point launches for
+ * this descriptor under the switches read at load; "none" outside the pw_mfma_* family or where that entry point refuses the
+ * call.  io (NULL: float32 on both sides) says whether codes come in and go out and describes the reader of output codes; has_res:
+ * slfp_conv2d_fwd_res; has_res_codes (with has_res): slfp_conv2d_fwd_res_codes, io->y_ka / y_qbits describing the reader of the second
+ * output; y_ld != 0: slfp_conv2d_fwd_codes_slice.  The string names the kernel and every template argument the launcher chose:
+ *   stream/ks<N>/<kfull|kpart|a8>/<tab|long>/<stg|dir>/p<1|3>/<act8|sfp7>[/res|/yc][/grid<n>]      k_pw_stream
+ *   tiled/<wm><wn><mt>/<kfull|kpart>/<tab|long>/<stg|dir>/p<1|3>/<act8|sfp7>[/res|/yc]             k_pw_tiled
+ *   pwc-stream/ks<N>/<xw|dw|half>/<act8|sfp7>/<f32|yc|res|res/dual>[/grid<n>]                      k_pwc_stream
+ *   slice/nts<4|8>/<act8|sfp7>/<f32|yc|res|res/dual>[/grid<n>]                                     k_pwc_slice
+ *   pwc-tiled/<wm><wn><mt>/<act8|sfp7>/<f32|yc|res|res/dual>                                       k_pwc_tiled
+ * (/grid<n>: SLFP_PW_GRID caps the persistent grid.)  It is printed from the selection the launch consumes (DESIGN.md section
+ * 19).  Host only: no device is touched.  The pointer stays valid until the next call on the same thread. */
+struct slfp_conv2d_io;   /* defined below */
+const char* slfp_debug_pw_variant(const slfp_conv2d_desc* d, const struct slfp_conv2d_io* io, int has_res, int has_res_codes, int64_t y_ld);
 
 /* Bytes of the prepared-weight blob for this layer (device memory the caller owns). */
 size_t slfp_conv2d_wprep_bytes(const slfp_conv2d_desc* d);
