@@ -1,21 +1,38 @@
-"""Inference-time fusion of the eval-mode BatchNorm2d (+ ReLU) that follows every Conv2d_Q in the
-reference nets into the conv kernels' epilogue.
+"""Inference-time rewrites of a model built from Conv2d_Q modules: BatchNorm / ReLU folded into the conv epilogues, layers paired into
+one kernel, and activations handed from layer to layer as 1-byte codes.  Call everything AFTER load_state_dict and model.eval().
 
-The reference runs  Conv2d_Q -> nn.BatchNorm2d -> nn.ReLU(inplace)  as three modules
-(nets_imgnet/mobilenetv1.py:24-41); stock BN + ReLU move 16 B per conv output element, twice the
-hot path's own traffic.  `fuse_bn_relu(model)` rewrites every such run inside an nn.Sequential:
-the BatchNorm2d's running statistics and affine are folded into a per-channel (scale, shift) that
-the HIP epilogue applies after the reference's (out*Ka)*Kw roundings (slfp_conv2d_fwd_post), and
-the BN / ReLU modules are replaced by nn.Identity.  Call it AFTER load_state_dict and model.eval().
-Nets that wire conv->bn by hand in forward() (ResNet-50 blocks) use `fuse_named_bn(model, example_input)` (folds every
-conv<k>/bn<k> pair by name and verifies itself against the example input) or `fuse_pair(conv, bn, relu)` per pair.
+The passes, in the order a pipeline applies them.  "Needs" = what must have run before; "sets" = the module state it writes; every
+undo function restores exactly that state; "also undone by" = the other undo functions that take the pass along.
 
-`fuse_dw_pw(model)` goes one step further for MobileNet blocks (second half): an adjacent
-[depthwise Conv2d_Q + BN + ReLU] -> [pointwise Conv2d_Q (+ BN + ReLU)] pair that libslfp_hip can run as ONE kernel
-(slfp_dwpw_fwd: the depthwise result is quantized for the pointwise layer where it is produced and never goes to HBM)
-is replaced by a `DwPwBlock`; the result is bit-identical to the two fused convs run separately.
+  pass                             needs                              sets                                          undo / also undone by
+  fuse_pair(conv, bn, relu)        --                                 conv._post                                    (set _post = None)
+  fuse_bn_relu(model)              --                                 _post, _fused_modules; bn / relu slots        unfuse
+                                                                      of an nn.Sequential -> nn.Identity
+  fuse_named_bn(model, x)          --                                 _post, _named_bn; the bn<k> slot of a hand-   unfuse_named_bn
+                                                                      wired block -> nn.Identity
+  fuse_dw_pw(model)                fuse_bn_relu                       DwPwBlock (._dw_slot) in the pointwise slot,  unfuse_dw_pw / unfuse
+                                                                      nn.Identity in the depthwise slot
+  link_codes(model, x)             fuse_bn_relu                       _code_out; pools -> CodeMaxPool2d             unlink_codes
+  fuse_residual(model, x)          fuse_named_bn                      block: instance forward, _residual_fused;     unfuse_residual
+                                                                      conv3: residual_relu, _in_residual
+  fuse_fire(model, x)              --                                 block: instance forward, _fire_fused; its     unfuse_fire
+                                                                      convs: _post, _code_out, _code_entry; pools
+                                                                      -> CodeMaxPool2d
+  link_codes_traced(model, x)      fuse_named_bn / fuse_bn_relu;      _code_out, _code_entry, _post with the ReLU   unlink_codes
+                                   before or after fuse_residual      bit, _pre_link_post; pools -> CodeMaxPool2d
+  link_stem(model, x)              the folds, fuse_fire(entries=True) stem: _code_out, _post, _pre_link_post,       unlink_stem / unlink_codes
+                                   or link_codes_traced(entries=      _stem_link; pools -> CodeMaxPool2d, ReLUs
+                                   True), fuse_residual               -> CodeReLU
+  link_trunk(model, x)             fuse_named_bn, fuse_residual,      conv3: _trunk_code_out, _trunk_link           unlink_trunk / unlink_codes,
+                                   link_codes_traced(entries=True)                                                  unfuse_residual
+
+The passes that take an example input share one forward trace (`_Trace`), one rule for "the same tensor" (`_Trace.same`), one
+eligibility predicate (`_code_eligible`), one record of wrapped children (`_wrap_children` / `_unwrap_children`) and one
+verify-or-roll-back step (`_verified`): DESIGN section 20.
 """
+import collections
 import ctypes
+import warnings
 
 import numpy as np
 import torch
@@ -130,18 +147,11 @@ def fuse_named_bn(model, example_input=None, rtol=None):
     y0 = None
     conv_out, bn_in = {}, {}
     if example_input is not None:
-        hooks = []
-        for m in model.modules():
-            if _is_conv_q(m):
-                hooks.append(m.register_forward_hook(lambda mod, inp, out: conv_out.__setitem__(mod, out)))
-            elif isinstance(m, nn.BatchNorm2d):
-                hooks.append(m.register_forward_pre_hook(lambda mod, inp: bn_in.__setitem__(mod, inp[0])))
-        try:
-            with torch.no_grad():
-                y0 = model(example_input)
-        finally:
-            for h in hooks:
-                h.remove()
+        tr = _Trace(model, example_input)
+        y0 = tr.output
+        conv_out = {c.mod: c.out for c in tr.calls if _is_conv_q(c.mod)}
+        bn_in = {c.mod: c.x for c in tr.calls if isinstance(c.mod, nn.BatchNorm2d)}
+        tr.release()
     done = []
     for parent in model.modules():
         if isinstance(parent, nn.Sequential):
@@ -155,6 +165,7 @@ def fuse_named_bn(model, example_input=None, rtol=None):
                 continue
             if conv.bias is not None and not getattr(conv, "_scaled_bias", False):
                 continue
+            # `is`, not _Trace.same: this pass has no bit-exact verification behind it
             if example_input is not None and (conv not in conv_out or bn_in.get(bn) is not conv_out[conv]):
                 continue   # forward() does not apply this bn to this conv's output
             fuse_pair(conv, bn, relu=False)
@@ -333,6 +344,153 @@ def _poolable(m):
             and (m.dilation == 1 or m.dilation == (1, 1)))
 
 
+# ------------------------------------------------------------------ what the passes that take an example input share
+class _Call(collections.namedtuple("_Call", "mod inp out")):
+    """One recorded module call: the module, its positional inputs, its output."""
+    __slots__ = ()
+
+    @property
+    def x(self):
+        """The first positional input, or None."""
+        return self.inp[0] if self.inp else None
+
+
+class _Trace:
+    """One no_grad forward of `model` on `example_input`, recorded.  `calls` holds, in execution order, a _Call for every Conv2d_Q
+    (not a leaf: it owns its quantizer children), every leaf module and every module in `blocks`; containers only hand their input on.
+    `output` is what the model returned.  Every recorded tensor is kept alive until release(), so an address names one tensor: that
+    is what `same` rests on.  A pass calls release() before it runs the model again -- a trace holds every activation of the net --
+    and keeps `output` for the comparison."""
+
+    def __init__(self, model, example_input, blocks=()):
+        self.calls, self._of, self._made, self._read = [], {}, {}, {}
+        blocks = set(blocks)
+        hooks = [m.register_forward_hook(lambda mod, inp, out: self.calls.append(_Call(mod, inp, out)))
+                 for m in model.modules() if _is_conv_q(m) or not m._modules or m in blocks]
+        try:
+            with torch.no_grad():
+                self.output = model(example_input)
+        finally:
+            for h in hooks:
+                h.remove()
+        for c in self.calls:
+            self._of.setdefault(c.mod, []).append(c)
+            if torch.is_tensor(c.out):
+                self._made.setdefault(self._key(c.out), []).append(c)
+            if torch.is_tensor(c.x):
+                self._read.setdefault(self._key(c.x), []).append(c)
+
+    @staticmethod
+    def _key(t):
+        return (t.data_ptr(), t.shape, t.dtype, t.stride())
+
+    def release(self):
+        """Drop every recorded call and with it the recorded tensors; `output` stays."""
+        self.calls.clear(); self._of.clear(); self._made.clear(); self._read.clear()
+
+    def same(self, a, b):
+        """Is `b` the tensor `a`: the same object, or the same address, shape, dtype and strides (what nn.Identity or an in-place
+        ReLU returns; a pooled or computed tensor never is)."""
+        return a is b or (torch.is_tensor(a) and torch.is_tensor(b) and self._key(a) == self._key(b))
+
+    def of(self, mod):
+        """The recorded calls of `mod`; runs(mod) is their number."""
+        return self._of.get(mod, [])
+
+    def runs(self, mod):
+        return len(self.of(mod))
+
+    def io(self, mod):
+        """(input, output) of `mod`, or None unless it ran exactly once with one positional input, tensor in and tensor out."""
+        calls = self.of(mod)
+        if len(calls) != 1 or len(calls[0].inp) != 1 or not torch.is_tensor(calls[0].x) or not torch.is_tensor(calls[0].out):
+            return None
+        return calls[0].x, calls[0].out
+
+    def readers(self, t):
+        """The calls whose first input is `t`, in execution order."""
+        return self._read.get(self._key(t), []) if torch.is_tensor(t) else []
+
+    def producer(self, t, kind):
+        """The first call of a module with kind(module) whose output is `t`, or None.  `kind` is needed because an in-place ReLU
+        behind nn.Identity behind a conv makes three calls return one tensor."""
+        return next((c for c in (self._made.get(self._key(t), []) if torch.is_tensor(t) else []) if kind(c.mod)), None)
+
+
+def _post_flags(m):
+    """The SLFP_POST_* bits of Conv2d_Q `m`'s epilogue (1 = ReLU, 2 = layer-output quantizer); 0 without one."""
+    return int(m._post[2]) if m._post is not None else 0
+
+
+def _fold_flags(m, flags):
+    """Give Conv2d_Q `m`'s epilogue these flag bits, keeping its (scale, shift)."""
+    m._post = ((m._post[0], m._post[1]) if m._post is not None else (None, None)) + (flags,)
+
+
+def _reader_quant(b):
+    """(float(Ka), q_bit): the quantizer of Conv2d_Q `b`, which a producer that writes b's codes applies."""
+    from .conv2d_func import _scalar_scale
+    return float(_scalar_scale(b.Ka, "Ka")), int(b.q_bit)
+
+
+def _code_eligible(m, producer_side=False):
+    """Can Conv2d_Q `m` read codes: 8 / 7 bit, eval mode, numeric padding, no raw bias, no layer-output quantizer.  producer_side: can
+    it be given codes to write: also no `_code_out` yet, and not the conv3 of a fuse_residual block."""
+    if not _is_conv_q(m) or producer_side and (m._code_out is not None or getattr(m, "_in_residual", False)):
+        return False   # _in_residual: the module's output is the block's float32 trunk (conv + identity), not a conv output
+    return (m.q_bit in (8, 7) and not m.training and isinstance(m.padding, tuple)
+            and (m.bias is None or getattr(m, "_scaled_bias", False)) and not (_post_flags(m) & 2))
+
+
+def _wrap_children(model, pools, q_bit, relus=()):
+    """Replace every child slot of `model` that holds one of `pools` / `relus` by CodeMaxPool2d(pool, q_bit) / CodeReLU(relu).
+    Returns the (parent, name, original) records that _unwrap_children takes."""
+    recs = []
+    for parent in [m for m in model.modules() if not isinstance(m, (CodeMaxPool2d, CodeReLU))]:
+        for name, child in list(parent._modules.items()):
+            if any(child is pm for pm in pools):
+                parent._modules[name] = CodeMaxPool2d(child, q_bit)
+            elif any(child is rm for rm in relus):
+                parent._modules[name] = CodeReLU(child)
+            else:
+                continue
+            recs.append((parent, name, child))
+    return recs
+
+
+def _unwrap_children(recs):
+    """The inverse of _wrap_children; a slot that no longer holds the wrapper of its original is left alone."""
+    for parent, name, orig in recs:
+        now = parent._modules.get(name)
+        if isinstance(now, CodeMaxPool2d) and now.pool is orig or isinstance(now, CodeReLU) and now.relu is orig:
+            parent._modules[name] = orig
+
+
+def _verified(fn, want, undo, reraise=False, warn=None):
+    """Run fn() under no_grad and return True if the result is a tensor of `want`'s dtype and shape with torch.equal(result, want)
+    (`want`: a tensor, or a function that makes it after fn has run).  Anything else is a refusal: undo() is called and False
+    returned -- also for an exception, e.g. a functional op on the tensor that cannot take codes (`warn`: a text with one {} for
+    "<type>: <message>", issued as a warning).  reraise: an _lib.SlfpError is not a refusal -- libslfp_hip refused or failed a call
+    the support queries had granted, a defect -- and propagates after undo().  DESIGN section 20 lists which pass sets it."""
+    from . import _lib
+    ok = False
+    try:
+        with torch.no_grad():
+            got = fn()
+            ref = want() if callable(want) else want
+        ok = torch.is_tensor(got) and got.dtype == ref.dtype and got.shape == ref.shape and torch.equal(got, ref)
+    except _lib.SlfpError:
+        if reraise:
+            undo()
+            raise
+    except Exception as e:
+        if warn is not None:
+            warnings.warn(warn.format(f"{type(e).__name__}: {e}"), stacklevel=2)   # the pass is the one that warns
+    if not ok:
+        undo()
+    return ok
+
+
 def link_codes(model, example_input=None):
     """After fuse_bn_relu: wherever a Conv2d_Q's (fused BN + ReLU) output feeds the next Conv2d_Q of an nn.Sequential
     directly (only nn.Identity in between -- nets_imgnet/mobilenetv1.py:24-33 after fusion), link the two: the producer's
@@ -342,20 +500,12 @@ def link_codes(model, example_input=None):
     With `example_input` (a channels_last ROCm batch) only links for which both kernels exist are made (one forward
     records the shapes); without it every candidate is linked and combinations without a kernel run through the float32
     interface plus an encode / decode pass (correct, slower).  Inference only.  Returns the number of links."""
-    from .conv2d_func import _scalar_scale, _supported
+    from .conv2d_func import _supported
     shapes = {}
     if example_input is not None:
-        hooks = []
-        for m in model.modules():
-            if _is_conv_q(m):
-                hooks.append(m.register_forward_pre_hook(lambda mod, inp: shapes.__setitem__(mod, tuple(inp[0].shape))))
-        was = [(m, m._code_out) for m in model.modules() if _is_conv_q(m)]
-        try:
-            with torch.no_grad():
-                model(example_input)
-        finally:
-            for h in hooks:
-                h.remove()
+        tr = _Trace(model, example_input)
+        shapes = {c.mod: tuple(c.x.shape) for c in tr.calls if _is_conv_q(c.mod)}
+        tr.release()
 
     def supported(m, x_codes, out):
         if example_input is None:
@@ -363,11 +513,7 @@ def link_codes(model, example_input=None):
         shp = shapes.get(m)
         if shp is None or len(shp) != 4:
             return False
-        return _supported(m, shp, "codes", x_codes, out, int(m._post[2]) if m._post is not None else 0)
-
-    def eligible(m):
-        return (_is_conv_q(m) and m.q_bit in (8, 7) and not m.training and isinstance(m.padding, tuple)
-                and (m.bias is None or getattr(m, "_scaled_bias", False)) and not (m._post is not None and (int(m._post[2]) & 2)))
+        return _supported(m, shp, "codes", x_codes, out, _post_flags(m))
 
     def flat(seq):   # an nn.Sequential of nn.Sequentials runs its leaves in order (conv_bn / conv_dw blocks of the reference nets)
         for m in seq._modules.values():
@@ -384,22 +530,22 @@ def link_codes(model, example_input=None):
         # remember which ones sit behind each conv
         mods, pools_after = [], {}
         for m in allm:
-            if _poolable(m) and mods and eligible(mods[-1]):
+            if _poolable(m) and mods and _code_eligible(mods[-1]):
                 pools_after.setdefault(len(mods) - 1, []).append(m)
             else:
                 mods.append(m)
         # candidate links: consecutive eligible convs
-        cand = [i for i in range(len(mods) - 1) if eligible(mods[i]) and eligible(mods[i + 1])]
+        cand = [i for i in range(len(mods) - 1) if _code_eligible(mods[i]) and _code_eligible(mods[i + 1])]
         # a conv can consume codes only if its producer link exists; walk left to right and keep links whose two sides have kernels
         linked_in = set()
         for i in cand:
             a, b = mods[i], mods[i + 1]
-            out = (float(_scalar_scale(b.Ka, "Ka")), int(b.q_bit))
+            out = _reader_quant(b)
             a_in = i in linked_in                       # does `a` itself read codes?
             if not supported(a, a_in, out):
                 # head of a run without a float32 -> codes kernel: enter the chain through one slfp_encode_f32 pass if at least
                 # two more layers then run on codes
-                if a_in or not (i + 1 in cand and supported(b, True, (float(_scalar_scale(mods[i + 2].Ka, "Ka")), int(mods[i + 2].q_bit)))):
+                if a_in or not (i + 1 in cand and supported(b, True, _reader_quant(mods[i + 2]))):
                     continue
             # b with codes in: it may or may not write codes itself; require the float32-out form here (the code-out form is
             # checked when its own link is made; if that fails b keeps float32 out)
@@ -410,11 +556,7 @@ def link_codes(model, example_input=None):
             a._code_out = out
             linked_in.add(i + 1)
             n_links += 1
-            for pm in pools_after.get(i, []):   # the pools between a and b now see codes
-                for parent in [m for m in model.modules() if not isinstance(m, CodeMaxPool2d)]:
-                    for name, child in list(parent._modules.items()):
-                        if child is pm:
-                            parent._modules[name] = CodeMaxPool2d(pm, b.q_bit)
+            _wrap_children(model, pools_after.get(i, ()), b.q_bit)   # the pools between a and b now see codes
     return n_links
 
 
@@ -432,68 +574,38 @@ def link_codes_traced(model, example_input, entries=False):
     slfp_conv2d_entry_supported says yes (a 1x1 layer: conv1 of every Bottleneck, which reads the float32 trunk); it gets
     `_code_entry = True` and runs slfp_conv2d_fwd_entry.  Everything else -- one consumer only, ReLU folding, pools, verification,
     roll-back -- is the same; the default keeps every link count what it was."""
-    from .conv2d_func import _scalar_scale, _supported
-    conv_io, relu_io, pool_io, order, keep = {}, [], [], [], []
-    hooks = []
-    for m in model.modules():
-        if _is_conv_q(m):
-            def _rec(mod, inp, out):
-                conv_io[mod] = (inp[0], out)
-                order.append(mod)
-                keep.append((inp[0], out))
-            hooks.append(m.register_forward_hook(_rec))
-        elif isinstance(m, nn.ReLU):
-            def _rec_relu(mod, inp, out):   # (returns None: a hook's return value would replace the module's output)
-                relu_io.append((inp[0], out))
-                keep.append((inp[0], out))
-            hooks.append(m.register_forward_hook(_rec_relu))
-        elif _poolable(m):
-            def _rec_pool(mod, inp, out):
-                pool_io.append((inp[0], out, mod))
-                keep.append((inp[0], out))
-            hooks.append(m.register_forward_hook(_rec_pool))
-    try:
-        with torch.no_grad():
-            y0 = model(example_input)
-    finally:
-        for h in hooks:
-            h.remove()
+    from .conv2d_func import _supported
+    tr = _Trace(model, example_input)
+    y0 = tr.output
+    order = [c.mod for c in tr.calls if _is_conv_q(c.mod)]
     if len(order) != len(set(order)):
         return 0   # a module that runs twice per forward has no single producer / consumer
-    producer = {id(out): c for c, (_, out) in conv_io.items()}
-    relu_src = {id(out): inp for inp, out in relu_io}
-    pool_src = {id(out): (inp, mod) for inp, out, mod in pool_io}
-    pool_uses = {}
-    for _, _, mod in pool_io:
-        pool_uses[mod] = pool_uses.get(mod, 0) + 1
 
-    def eligible(m, producer_side=False):
-        if producer_side and getattr(m, "_in_residual", False):
-            return False   # fuse_residual: the module's output is the block's float32 trunk (conv + identity), not a conv output
-        return (m.q_bit in (8, 7) and not m.training and isinstance(m.padding, tuple) and (m._code_out is None or not producer_side)
-                and (m.bias is None or getattr(m, "_scaled_bias", False)) and not (m._post is not None and (int(m._post[2]) & 2)))
+    def x_of(m):
+        return tr.of(m)[0].x
 
     def supported(m, x_codes, out, flags):
-        xin = conv_io[m][0]
-        if xin.dim() != 4:
+        if x_of(m).dim() != 4:
             return False
-        return _supported(m, xin.shape, "codes", x_codes, out, flags)
+        return _supported(m, x_of(m).shape, "codes", x_codes, out, flags)
 
     cand = {}
     for b in order:
-        t, via_relu, pools = conv_io[b][0], False, []
+        t, via_relu, pools = x_of(b), False, []
         for _ in range(4):   # look back through nn.ReLU / nn.MaxPool2d modules (a ReLU'd tensor pools the same either way)
-            if id(t) in relu_src:
-                t, via_relu = relu_src[id(t)], True
-            elif id(t) in pool_src and pool_uses[pool_src[id(t)][1]] == 1:
-                t, pm = pool_src[id(t)]
-                pools.append(pm)
+            relu, pool = tr.producer(t, lambda m: isinstance(m, nn.ReLU)), tr.producer(t, _poolable)
+            if relu is not None:
+                t, via_relu = relu.x, True
+            elif pool is not None and tr.runs(pool.mod) == 1:
+                t = pool.x
+                pools.append(pool.mod)
             else:
                 break
-        a = producer.get(id(t))
-        if a is None or a is b or not eligible(a, producer_side=True) or not eligible(b):
+        a = tr.producer(t, _is_conv_q)
+        a = a.mod if a is not None else None
+        if a is None or a is b or not _code_eligible(a, producer_side=True) or not _code_eligible(b):
             continue
-        if conv_io[b][0].dtype == torch.uint8:
+        if x_of(b).dtype == torch.uint8:
             continue   # already linked
         if pools and a.out_channels % 4:
             continue   # slfp_maxpool2d_codes needs C % 4 == 0
@@ -503,47 +615,35 @@ def link_codes_traced(model, example_input, entries=False):
         if a not in cand or len(cand[a]) != 1:
             continue
         b, via_relu, pools = cand[a][0]
-        flags = (int(a._post[2]) if a._post is not None else 0) | (1 if via_relu else 0)
-        out = (float(_scalar_scale(b.Ka, "Ka")), int(b.q_bit))
-        bflags = int(b._post[2]) if b._post is not None else 0
-        a_in = a in reads_codes or conv_io[a][0].dtype == torch.uint8   # does `a` itself read codes (an earlier link)?
+        flags = _post_flags(a) | (1 if via_relu else 0)
+        out = _reader_quant(b)
+        a_in = a in reads_codes or x_of(a).dtype == torch.uint8   # does `a` itself read codes (an earlier link)?
         entry = False
         if not supported(a, a_in, out, flags):
-            entry = (entries and not a_in and conv_io[a][0].dim() == 4
-                     and _supported(a, conv_io[a][0].shape, "entry", False, out, flags))
+            entry = (entries and not a_in and x_of(a).dim() == 4
+                     and _supported(a, x_of(a).shape, "entry", False, out, flags))
             if not entry:
                 continue
-        if not supported(b, True, b._code_out, bflags):
+        if not supported(b, True, b._code_out, _post_flags(b)):
             continue
         made.append((a, a._post))
         a._code_entry = entry
-        a._post = ((a._post[0], a._post[1]) if a._post is not None else (None, None)) + (flags,)
+        a._pre_link_post = a._post
+        _fold_flags(a, flags)
         a._code_out = out
-        a._pre_link_post = made[-1][1]
         reads_codes.add(b)
-        for pm in pools:   # the pools between a and b now see codes
-            for parent in [m for m in model.modules() if not isinstance(m, CodeMaxPool2d)]:
-                for name, child in list(parent._modules.items()):
-                    if child is pm:
-                        parent._modules[name] = CodeMaxPool2d(pm, b.q_bit)
-                        wrapped.append((parent, name, pm))
+        wrapped += _wrap_children(model, pools, b.q_bit)   # the pools between a and b now see codes
     if not made:
         return 0
-    ok = False
-    try:
-        with torch.no_grad():
-            y1 = model(example_input)
-        ok = y1.dtype == y0.dtype and torch.equal(y1, y0)
-    except Exception:
-        ok = False
-    if not ok:
+    tr.release()
+
+    def undo():
         for a, post in made:
             a._post, a._code_out, a._code_entry = post, None, False
             del a._pre_link_post
-        for parent, name, pm in wrapped:
-            parent._modules[name] = pm
-        return 0
-    return len(made)
+        _unwrap_children(wrapped)
+
+    return len(made) if _verified(lambda: model(example_input), y0, undo) else 0
 
 
 def unlink_codes(model):
@@ -570,15 +670,9 @@ def unlink_codes(model):
 
 # ------------------------------------------------------------------ the image stem writes the first code tensor of the net
 def _restore_stem(stem):
-    st = stem.__dict__.pop("_stem_link")
+    _unwrap_children(stem.__dict__.pop("_stem_link"))
     stem._post, stem._code_out = stem._pre_link_post, None
     del stem._pre_link_post
-    for parent, name, pool in st["pools"]:
-        if isinstance(parent._modules.get(name), CodeMaxPool2d) and parent._modules[name].pool is pool:
-            parent._modules[name] = pool
-    for parent, name, relu in st["relus"]:
-        if isinstance(parent._modules.get(name), CodeReLU) and parent._modules[name].relu is relu:
-            parent._modules[name] = relu
 
 
 def link_stem(model, example_input):
@@ -598,60 +692,37 @@ def link_stem(model, example_input):
     Run it after fuse_bn_relu / fuse_named_bn, fuse_fire(entries=True), link_codes_traced(entries=True) and fuse_residual; it
     composes with all of them and with graph.GraphedModule.  Inference only.  Returns 1 or 0; unlink_stem undoes exactly this
     link, unlink_codes undoes it as it undoes every link."""
-    from .conv2d_func import _scalar_scale, _supported
-    from . import _lib
+    from .conv2d_func import _supported
     if model.training or not any(_is_conv_q(m) for m in model.modules()):
         return 0
-    calls, keep, hooks = [], [], []
-    for m in model.modules():
-        if _is_conv_q(m) or not m._modules:   # leaves; containers only hand their input on
-            def _rec(mod, inp, out):
-                calls.append((mod, inp[0] if inp else None, out))
-                keep.append((inp, out))
-            hooks.append(m.register_forward_hook(_rec))
-    try:
-        with torch.no_grad():
-            y0 = model(example_input)
-    finally:
-        for h in hooks:
-            h.remove()
+    tr = _Trace(model, example_input)
+    y0 = tr.output
     if not torch.is_tensor(y0):
         return 0
-
-    def same(a, b):   # every recorded tensor is kept alive, so an address names one tensor
-        return a is b or (torch.is_tensor(a) and torch.is_tensor(b) and a.data_ptr() == b.data_ptr() and a.shape == b.shape
-                          and a.dtype == b.dtype and a.stride() == b.stride())
-
-    def eligible(m):
-        return (m.q_bit in (8, 7) and not m.training and isinstance(m.padding, tuple)
-                and (m.bias is None or getattr(m, "_scaled_bias", False)) and not (m._post is not None and (int(m._post[2]) & 2)))
-
-    stem = next((c for c in calls if _is_conv_q(c[0]) and c[0].in_channels <= 4 and torch.is_tensor(c[1]) and c[1].dim() == 4
-                 and c[1].dtype == torch.float32), None)
-    if stem is None or stem is not next(c for c in calls if _is_conv_q(c[0])):
+    first = next((i for i, c in enumerate(tr.calls) if _is_conv_q(c.mod)), None)
+    if first is None:
         return 0
-    stem, x_stem, t0 = stem
-    n_runs = {}
-    for mod, _, _ in calls:
-        n_runs[mod] = n_runs.get(mod, 0) + 1
-    if (n_runs[stem] != 1 or not eligible(stem) or stem._code_out is not None or getattr(stem, "_in_residual", False)
-            or not torch.is_tensor(t0) or t0.dim() != 4):
+    stem, x_stem, t0 = tr.calls[first].mod, tr.calls[first].x, tr.calls[first].out
+    if not (stem.in_channels <= 4 and torch.is_tensor(x_stem) and x_stem.dim() == 4 and x_stem.dtype == torch.float32):
+        return 0   # the first-executed Conv2d_Q is no image stem
+    if (tr.runs(stem) != 1 or not _code_eligible(stem, producer_side=True) or not torch.is_tensor(t0) or t0.dim() != 4):
         return 0
     # follow the tensor in execution order: live = [tensor, has a ReLU module run on it or on the way to it]
     live, readers, pools, relus = [[t0, False]], [], [], []
 
     def note(t, relu):
         for e in live:
-            if same(e[0], t):   # nn.Identity, an in-place ReLU: the same tensor again
+            if tr.same(e[0], t):   # nn.Identity, an in-place ReLU: the same tensor again
                 e[1] = e[1] or relu
                 return
         live.append([t, relu])
 
-    for mod, xin, out in calls[next(i for i, c in enumerate(calls) if c[0] is stem) + 1:]:
-        src = next((e for e in live if same(e[0], xin)), None)
+    for mod, inp, out in tr.calls[first + 1:]:
+        xin = inp[0] if inp else None
+        src = next((e for e in live if tr.same(e[0], xin)), None)
         if src is None:
             continue
-        if n_runs[mod] != 1 or not torch.is_tensor(out):
+        if tr.runs(mod) != 1 or not torch.is_tensor(out):
             return 0
         if _is_conv_q(mod):
             readers.append((mod, xin, src[1]))
@@ -668,47 +739,24 @@ def link_stem(model, example_input):
             return 0   # another module takes the tensor
     if not readers or len({r for _, _, r in readers}) != 1:
         return 0   # one code tensor: with the ReLU folded for every reader, or for none
-    if len({(float(_scalar_scale(b.Ka, "Ka")), int(b.q_bit)) for b, _, _ in readers}) != 1:
+    if len({_reader_quant(b) for b, _, _ in readers}) != 1:
         return 0
     b0, _, via_relu = readers[0]
-    out = (float(_scalar_scale(b0.Ka, "Ka")), int(b0.q_bit))
-    flags = (int(stem._post[2]) if stem._post is not None else 0) | (1 if via_relu else 0)
+    out = _reader_quant(b0)
+    flags = _post_flags(stem) | (1 if via_relu else 0)
     for b, xin, _ in readers:
-        bflags = int(b._post[2]) if b._post is not None else 0
-        if (not eligible(b) or xin.dtype != torch.float32 or xin.dim() != 4
-                or not _supported(b, tuple(xin.shape), "codes", True, b._code_out, bflags)):
+        if (not _code_eligible(b) or xin.dtype != torch.float32 or xin.dim() != 4
+                or not _supported(b, tuple(xin.shape), "codes", True, b._code_out, _post_flags(b))):
             return 0
     if not _supported(stem, tuple(x_stem.shape), "codes", False, out, flags):
         return 0
-    st = {"pools": [], "relus": []}
     stem._pre_link_post = stem._post
-    stem._post = ((stem._post[0], stem._post[1]) if stem._post is not None else (None, None)) + (flags,)
+    _fold_flags(stem, flags)
     stem._code_out = out
-    stem.__dict__["_stem_link"] = st
     # the pools between the stem and its readers now see codes; the ReLUs (each runs once, on this tensor only) are the quantizer's
-    for parent in [m for m in model.modules() if not isinstance(m, (CodeMaxPool2d, CodeReLU))]:
-        for name, child in list(parent._modules.items()):
-            if any(child is pm for pm in pools):
-                parent._modules[name] = CodeMaxPool2d(child, out[1])
-                st["pools"].append((parent, name, child))
-            elif any(child is rm for rm in relus):
-                parent._modules[name] = CodeReLU(child)
-                st["relus"].append((parent, name, child))
-    calls.clear(); keep.clear()
-    ok = False
-    try:
-        with torch.no_grad():
-            y1 = model(example_input)
-        ok = torch.is_tensor(y1) and y1.dtype == y0.dtype and y1.shape == y0.shape and torch.equal(y1, y0)
-    except _lib.SlfpError:
-        _restore_stem(stem)
-        raise   # libslfp_hip refused or failed a call the support queries had granted: a defect, not an ordinary refusal
-    except Exception:   # e.g. a functional op on the tensor that cannot take codes
-        ok = False
-    if not ok:
-        _restore_stem(stem)
-        return 0
-    return 1
+    stem.__dict__["_stem_link"] = _wrap_children(model, pools, out[1], relus)
+    tr.release()
+    return int(_verified(lambda: model(example_input), y0, lambda: _restore_stem(stem), reraise=True))
 
 
 def unlink_stem(model):
@@ -778,51 +826,29 @@ def fuse_residual(model, example_input):
     cands = [m for m in model.modules() if _residual_candidate(m)]
     if not cands:
         return 0
-    rec, hooks = {}, []
-    for blk in cands:
-        hooks.append(blk.register_forward_hook(lambda mod, inp, out: rec.__setitem__(mod, rec.get(mod, []) + [(inp, out)])))
-    try:
-        with torch.no_grad():
-            y0 = model(example_input)
-    finally:
-        for h in hooks:
-            h.remove()
+    tr = _Trace(model, example_input, blocks=cands)
+    y0 = tr.output
     done = []
     for blk in cands:
-        calls = rec.get(blk, [])
-        if len(calls) != 1 or len(calls[0][0]) != 1 or not torch.is_tensor(calls[0][0][0]) or not torch.is_tensor(calls[0][1]):
+        io = tr.io(blk)
+        if io is None:
             continue   # not run, run twice, or not a tensor -> tensor block
-        x, want = calls[0][0][0], calls[0][1]
+        x, want = io
         blk.conv3.residual_relu = True
         blk.conv3._in_residual = True
         blk.__dict__["_residual_fused"] = True
         blk.__dict__["forward"] = types.MethodType(_bottleneck_forward, blk)
-        ok = False
-        try:
-            with torch.no_grad():
-                got = blk(x)
-            ok = torch.is_tensor(got) and got.dtype == want.dtype and got.shape == want.shape and torch.equal(got, want)
-        except Exception:
-            ok = False
-        if ok:
+        if _verified(lambda: blk(x), want, lambda: _restore_block(blk)):
             done.append(blk)
-        else:
-            _restore_block(blk)
-    rec.clear()
+    tr.release()
     if not done:
         return 0
-    ok = False
-    try:
-        with torch.no_grad():
-            y1 = model(example_input)
-        ok = y1.dtype == y0.dtype and torch.equal(y1, y0)
-    except Exception:
-        ok = False
-    if not ok:
+
+    def undo():
         for blk in done:
             _restore_block(blk)
-        return 0
-    return len(done)
+
+    return len(done) if _verified(lambda: model(example_input), y0, undo) else 0
 
 
 def unfuse_residual(model):
@@ -857,47 +883,16 @@ def link_trunk(model, example_input):
     fuse_named_bn, fuse_residual and link_codes_traced(entries=True) (with none of them there is nothing to link: 0); composes with
     link_stem and graph.GraphedModule.  Inference only, never a default.  Returns the number of links; unlink_trunk undoes exactly
     these, unlink_codes and unfuse_residual take them along."""
-    from .conv2d_func import _scalar_scale, _supported, _f32, _act_fmt
+    from .conv2d_func import _supported, _f32, _act_fmt
     from .sfp_quant import hip_encode
     from . import _lib
     blocks = [m for m in model.modules() if m.__dict__.get("_residual_fused")]
     if model.training or not blocks:
         return 0
-    rec, conv_in, keep, hooks = {}, [], [], []
-    for m in model.modules():
-        if m.__dict__.get("_residual_fused"):
-            hooks.append(m.register_forward_hook(lambda mod, inp, out: rec.__setitem__(mod, rec.get(mod, []) + [(inp, out)])))
-        elif _is_conv_q(m):
-            def _rec_conv(mod, inp, out):
-                conv_in.append((mod, inp[0] if inp else None))
-                keep.append((inp, out))
-            hooks.append(m.register_forward_hook(_rec_conv))
-    try:
-        with torch.no_grad():
-            y0 = model(example_input)
-    finally:
-        for h in hooks:
-            h.remove()
+    tr = _Trace(model, example_input, blocks=blocks)
+    y0 = tr.output
     if not torch.is_tensor(y0):
         return 0
-
-    def same(a, b):   # every recorded tensor is kept alive, so an address names one tensor
-        return a is b or (torch.is_tensor(a) and torch.is_tensor(b) and a.data_ptr() == b.data_ptr() and a.shape == b.shape
-                          and a.dtype == b.dtype and a.stride() == b.stride())
-
-    def eligible(m):
-        return (m.q_bit in (8, 7) and not m.training and isinstance(m.padding, tuple)
-                and (m.bias is None or getattr(m, "_scaled_bias", False)) and not (m._post is not None and (int(m._post[2]) & 2)))
-
-    def one_call(blk):
-        calls = rec.get(blk, [])
-        if len(calls) != 1 or len(calls[0][0]) != 1 or not torch.is_tensor(calls[0][0][0]) or not torch.is_tensor(calls[0][1]):
-            return None
-        return calls[0][0][0], calls[0][1]
-
-    n_runs = {}
-    for mod, _ in conv_in:
-        n_runs[mod] = n_runs.get(mod, 0) + 1
     nhwc = torch.channels_last
     made = []
 
@@ -905,69 +900,55 @@ def link_trunk(model, example_input):
         _restore_trunk(conv3)
         made.remove(conv3)
 
+    def take_all_back():
+        while made:
+            take_back(made[-1])
+
     for blk in blocks:
-        io = one_call(blk)
+        io = tr.io(blk)
         c3 = blk._modules.get("conv3")
-        if io is None or not _is_conv_q(c3) or c3._trunk_code_out is not None or n_runs.get(c3) != 1:
+        if io is None or not _is_conv_q(c3) or c3._trunk_code_out is not None or tr.runs(c3) != 1:
             continue
         x_blk, want = io
         if want.dim() != 4 or want.dtype != torch.float32 or not want.is_contiguous(memory_format=nhwc):
             continue
-        readers = [(b, xin) for b, xin in conv_in if same(xin, want)]
-        if not readers or any(n_runs[b] != 1 or b is c3 for b, _ in readers):
+        readers = [c.mod for c in tr.readers(want) if _is_conv_q(c.mod)]
+        if not readers or any(tr.runs(b) != 1 or b is c3 for b in readers):
             continue
-        scales = {(float(_scalar_scale(b.Ka, "Ka")), int(b.q_bit)) for b, _ in readers}
+        scales = {_reader_quant(b) for b in readers}
         if len(scales) != 1:
             continue   # one code tensor serves every reader
         out = next(iter(scales))
-        if not all(eligible(b) and _supported(b, tuple(want.shape), "codes", True, b._code_out,
-                                              int(b._post[2]) if b._post is not None else 0) for b, _ in readers):
+        if not all(_code_eligible(b) and _supported(b, tuple(want.shape), "codes", True, b._code_out, _post_flags(b)) for b in readers):
             continue   # a reader without a code-input kernel in its present state
-        x3 = next(xin for b, xin in conv_in if b is c3)
-        flags3 = int(c3._post[2]) if c3._post is not None else 0
-        if (not eligible(c3) or c3._code_out is not None or flags3 != 0 or not torch.is_tensor(x3) or x3.dtype != torch.uint8
-                or x3.dim() != 4 or not _supported(c3, tuple(x3.shape), "res_codes", True, out, 1 if c3.residual_relu else 0)):
+        x3 = tr.of(c3)[0].x
+        if (not _code_eligible(c3) or c3._code_out is not None or _post_flags(c3) != 0 or not torch.is_tensor(x3)
+                or x3.dtype != torch.uint8 or x3.dim() != 4
+                or not _supported(c3, tuple(x3.shape), "res_codes", True, out, 1 if c3.residual_relu else 0)):
             continue
         c3._trunk_code_out = out
         c3.__dict__["_trunk_link"] = True
         made.append(c3)
-        nxt = next((b for b in blocks if b is not blk and one_call(b) is not None and same(one_call(b)[0], want)), None)
-        ok = False
+        nxt = next((b for b in blocks if b is not blk and tr.io(b) is not None and tr.same(tr.io(b)[0], want)), None)
+
+        def relinked():
+            """the block's output, or None unless it hands on exactly slfp_encode_f32 of its recorded output and the block that reads
+            it reproduces its own recorded output from it"""
+            got = blk(x_blk)
+            tc = got.__dict__.get("_trunk_codes") if torch.is_tensor(got) else None
+            if tc is None or tc[1:] != out or not torch.equal(tc[0], hip_encode(want, _f32(out[0]), _act_fmt(out[1]))):
+                return None
+            return got if nxt is None or torch.equal(nxt(got), tr.io(nxt)[1]) else None
+
         try:
-            with torch.no_grad():
-                got = blk(x_blk)
-                tc = got.__dict__.get("_trunk_codes") if torch.is_tensor(got) else None
-                ok = (tc is not None and got.dtype == want.dtype and got.shape == want.shape and torch.equal(got, want)
-                      and tc[1:] == out and torch.equal(tc[0], hip_encode(want, _f32(out[0]), _act_fmt(out[1]))))
-                if ok and nxt is not None:
-                    ok = torch.equal(nxt(got), one_call(nxt)[1])
+            _verified(relinked, want, lambda: take_back(c3), reraise=True)   # a link that fails is taken back alone
         except _lib.SlfpError:
-            while made:
-                take_back(made[-1])
-            raise   # libslfp_hip refused or failed a call the support queries had granted: a defect, not an ordinary refusal
-        except Exception:
-            ok = False
-        if not ok:
-            take_back(c3)
-    rec.clear(); conv_in.clear(); keep.clear()
+            take_all_back()   # a defect takes back every link
+            raise
+    tr.release()
     if not made:
         return 0
-    ok = False
-    try:
-        with torch.no_grad():
-            y1 = model(example_input)
-        ok = torch.is_tensor(y1) and y1.dtype == y0.dtype and y1.shape == y0.shape and torch.equal(y1, y0)
-    except _lib.SlfpError:
-        while made:
-            take_back(made[-1])
-        raise
-    except Exception:
-        ok = False
-    if not ok:
-        while made:
-            take_back(made[-1])
-        return 0
-    return len(made)
+    return len(made) if _verified(lambda: model(example_input), y0, take_all_back, reraise=True) else 0
 
 
 def unlink_trunk(model):
@@ -1014,13 +995,11 @@ def _fire_candidate(blk):
     if any(ch.get(k) is None for k in _FIRE_CHILDREN):
         return False
     sq, e1, e3 = ch["squeeze"], ch["expand1x1"], ch["expand3x3"]
-    if not all(_is_conv_q(c) for c in (sq, e1, e3)) or not all(isinstance(ch[k + "_activation"], nn.ReLU) for k in ("squeeze", "expand1x1", "expand3x3")):
+    if not all(isinstance(ch[k + "_activation"], nn.ReLU) for k in ("squeeze", "expand1x1", "expand3x3")):
         return False
-    for c in (sq, e1, e3):
-        if (c.q_bit not in (8, 7) or c.training or not isinstance(c.padding, tuple) or c._code_out is not None or c.groups != 1
-                or (c.bias is not None and not getattr(c, "_scaled_bias", False)) or (c._post is not None and int(c._post[2]) != 0)
-                or getattr(c, "_in_residual", False)):
-            return False
+    # every leg will write codes; stricter than the shared predicate: no epilogue at all yet (the rewrite puts the ReLU there), dense
+    if not all(_code_eligible(c, producer_side=True) and _post_flags(c) == 0 and c.groups == 1 for c in (sq, e1, e3)):
+        return False
     same_size = all(tuple(c.stride) == (1, 1) and tuple(_pair2(c.dilation)) == (1, 1)
                     and tuple(k - 1 for k in c.kernel_size) == tuple(2 * p for p in c.padding) for c in (sq, e1, e3))
     return (same_size and e1.in_channels == e3.in_channels == sq.out_channels and e1.out_channels % 16 == 0
@@ -1032,9 +1011,7 @@ def _restore_fire(blk):
     del blk.__dict__["forward"]
     for conv, post in st["posts"]:
         conv._post, conv._code_out, conv._code_entry = post, None, False
-    for parent, name, pool in st["pools"]:
-        if isinstance(parent._modules.get(name), CodeMaxPool2d) and parent._modules[name].pool is pool:
-            parent._modules[name] = pool
+    _unwrap_children(st["pools"])
 
 
 def fuse_fire(model, example_input, entries=False):
@@ -1057,68 +1034,47 @@ def fuse_fire(model, example_input, entries=False):
     float32 -> codes form of that layer (slfp_conv2d_entry_supported; `squeeze._code_entry`): no slfp_encode_f32 pass at the head of
     the chain.  The verification is the same."""
     import types
-    import warnings
-    from .conv2d_func import _scalar_scale, _supported, _f32, _act_fmt
+    from .conv2d_func import _supported, _f32, _act_fmt
     from .sfp_quant import hip_encode
     from . import _lib
     cands = [m for m in model.modules() if _fire_candidate(m)]
     if not cands or model.training:
         return 0
-    rec, conv_in, thru, keep, hooks = {}, [], [], [], []
-    for m in model.modules():
-        if m in cands:
-            hooks.append(m.register_forward_hook(lambda mod, inp, out: rec.__setitem__(mod, rec.get(mod, []) + [(inp, out)])))
-        elif _is_conv_q(m):
-            def _rec_conv(mod, inp, out):
-                conv_in.append((mod, inp[0]))
-                keep.append(inp[0])
-            hooks.append(m.register_forward_hook(_rec_conv))
-        elif isinstance(m, (nn.MaxPool2d, nn.Dropout, nn.Identity)):
-            def _rec_thru(mod, inp, out):
-                thru.append((mod, inp[0], out))
-                keep.extend((inp[0], out))
-            hooks.append(m.register_forward_hook(_rec_thru))
-    try:
-        with torch.no_grad():
-            y0 = model(example_input)
-    finally:
-        for h in hooks:
-            h.remove()
-
-    def same(a, b):   # every recorded tensor is kept alive, so an address names one tensor
-        return a is b or (torch.is_tensor(a) and torch.is_tensor(b) and a.data_ptr() == b.data_ptr() and a.shape == b.shape
-                          and a.dtype == b.dtype and a.stride() == b.stride())
+    tr = _Trace(model, example_input, blocks=cands)
+    y0 = tr.output
+    conv_in = [c for c in tr.calls if _is_conv_q(c.mod)]
+    thru = [c for c in tr.calls if isinstance(c.mod, (nn.MaxPool2d, nn.Dropout, nn.Identity))]
 
     def consumer_of(t):
         """(the single Conv2d_Q that reads `t`, the pools on the way) or None."""
         found = []
-        for mod, xin in conv_in:
-            cur, pools, ok = xin, [], False
+        for c in conv_in:
+            cur, pools, ok = c.x, [], False
             for _ in range(6):
-                if same(cur, t):
+                if tr.same(cur, t):
                     ok = True
                     break
-                src = [(m_, i_) for m_, i_, o_ in thru if same(o_, cur)]
+                src = [s for s in thru if tr.same(s.out, cur)]
                 if len(src) != 1:
                     break
-                m_, cur = src[0]
-                if isinstance(m_, nn.MaxPool2d):
-                    pools.append(m_)
+                cur = src[0].x
+                if isinstance(src[0].mod, nn.MaxPool2d):
+                    pools.append(src[0].mod)
             if ok:
-                found.append((mod, pools))
+                found.append((c.mod, pools))
         # any other module that takes `t` (or a pooled / passed-through copy) without ending in that conv is a second use
         # (a module that hands its input through -- nn.Dropout in eval mode, nn.Identity -- is not a use of its own)
-        direct = sum(1 for m_, i_, o_ in thru if same(i_, t) and not same(o_, t)) + sum(1 for mod, xin in conv_in if same(xin, t))
+        direct = sum(1 for s in thru if tr.same(s.x, t) and not tr.same(s.out, t)) + sum(1 for c in conv_in if tr.same(c.x, t))
         if len(found) != 1 or direct != 1:
             return None
         return found[0]
 
     done = []
     for blk in cands:
-        calls = rec.get(blk, [])
-        if len(calls) != 1 or len(calls[0][0]) != 1 or not torch.is_tensor(calls[0][0][0]) or not torch.is_tensor(calls[0][1]):
+        io = tr.io(blk)
+        if io is None:
             continue   # not run, run twice, or not a tensor -> tensor block
-        x, want = calls[0][0][0], calls[0][1]
+        x, want = io
         sq, e1, e3 = blk.squeeze, blk.expand1x1, blk.expand3x3
         ld = e1.out_channels + e3.out_channels
         if (x.dim() != 4 or want.dim() != 4 or want.shape[1] != ld or not x.is_cuda
@@ -1128,64 +1084,42 @@ def fuse_fire(model, example_input, entries=False):
         if cons is None:
             continue
         nxt, pools = cons
+        # the reader: of _code_eligible only the conditions on the quantizer, the mode and the bias are asked here; a layer-output
+        # epilogue is the support query's to refuse, below
         if (nxt.q_bit not in (8, 7) or nxt.training or (nxt.bias is not None and not getattr(nxt, "_scaled_bias", False))
                 or any(p.return_indices or _pair2(p.dilation) != (1, 1) or ld % 4 for p in pools)):
             continue
-        out_e = (float(_scalar_scale(e1.Ka, "Ka")), int(e1.q_bit))
-        out_n = (float(_scalar_scale(nxt.Ka, "Ka")), int(nxt.q_bit))
+        out_e, out_n = _reader_quant(e1), _reader_quant(nxt)
         hshape = (x.shape[0], sq.out_channels, x.shape[2], x.shape[3])
-        nshape = (x.shape[0], nxt.in_channels) + tuple(next(xin for mod, xin in conv_in if mod is nxt).shape[2:])
-        nflags = int(nxt._post[2]) if nxt._post is not None else 0
+        nshape = (x.shape[0], nxt.in_channels) + tuple(tr.of(nxt)[0].x.shape[2:])
         if not (_supported(sq, tuple(x.shape), "codes", True, out_e, 1) and _supported(e1, hshape, "slice", True, out_n, 1, ld)
-                and _supported(e3, hshape, "slice", True, out_n, 1, ld) and _supported(nxt, nshape, "codes", True, None, nflags)):
+                and _supported(e3, hshape, "slice", True, out_n, 1, ld)
+                and _supported(nxt, nshape, "codes", True, None, _post_flags(nxt))):
             continue
         st = {"posts": [(c, c._post) for c in (sq, e1, e3)], "pools": []}
         for c in (sq, e1, e3):
-            c._post = ((c._post[0], c._post[1]) if c._post is not None else (None, None)) + (1,)
+            _fold_flags(c, 1)
         sq._code_out, e1._code_out, e3._code_out = out_e, out_n, out_n
         sq._code_entry = bool(entries and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)
                               and _supported(sq, tuple(x.shape), "entry", False, out_e, 1))
         blk.__dict__["_fire_fused"] = st
         blk.__dict__["forward"] = types.MethodType(_fire_forward, blk)
-        ok = False
-        try:
-            with torch.no_grad():
-                got = blk(x)
-                ref = hip_encode(want, _f32(out_n[0]), _act_fmt(out_n[1]))
-            ok = torch.is_tensor(got) and got.dtype == torch.uint8 and got.shape == ref.shape and torch.equal(got, ref)
-        except _lib.SlfpError:
-            _restore_fire(blk)
-            raise   # libslfp_hip refused or failed a call the support queries had granted: a defect, not an ordinary refusal
-        except Exception as e:   # e.g. a block whose own forward() does more than the six children say
-            warnings.warn(f"fuse_fire: {type(blk).__name__} left as it was: its rewritten form raised {type(e).__name__}: {e}")
-            ok = False
-        if not ok:
-            _restore_fire(blk)
+        # e.g. a block whose own forward() does more than the six children say
+        if not _verified(lambda: blk(x), lambda: hip_encode(want, _f32(out_n[0]), _act_fmt(out_n[1])), lambda: _restore_fire(blk),
+                         reraise=True, warn=f"fuse_fire: {type(blk).__name__} left as it was: its rewritten form raised {{}}"):
             continue
-        for pm in pools:   # the pools between the block and its consumer now see codes
-            for parent in [m for m in model.modules() if not isinstance(m, CodeMaxPool2d)]:
-                for name, child in list(parent._modules.items()):
-                    if child is pm:
-                        parent._modules[name] = CodeMaxPool2d(pm, nxt.q_bit)
-                        st["pools"].append((parent, name, pm))
+        st["pools"] = _wrap_children(model, pools, nxt.q_bit)   # the pools between the block and its consumer now see codes
         done.append(blk)
-    rec.clear(); conv_in.clear(); thru.clear(); keep.clear()
-
-    def model_ok():
-        try:
-            with torch.no_grad():
-                y1 = model(example_input)
-            return y1.dtype == y0.dtype and y1.shape == y0.shape and torch.equal(y1, y0)
-        except _lib.SlfpError:
-            while done:
-                _restore_fire(done.pop())
-            raise
-        except Exception as e:   # e.g. a functional op behind a block that cannot take its codes
-            warnings.warn(f"fuse_fire: the rewritten model raised {type(e).__name__}: {e}; restoring the last rewritten block")
-            return False
-
-    while done and not model_ok():   # restored one by one, last block first, until the logits are the recorded ones again
-        _restore_fire(done.pop())
+    tr.release()
+    del conv_in[:], thru[:]
+    try:   # restored one by one, last block first, until the logits are the recorded ones again
+        while done and not _verified(lambda: model(example_input), y0, lambda: _restore_fire(done.pop()), reraise=True,
+                                     warn="fuse_fire: the rewritten model raised {}; restoring the last rewritten block"):
+            pass   # e.g. a functional op behind a block that cannot take its codes
+    except _lib.SlfpError:
+        while done:   # a defect restores every block
+            _restore_fire(done.pop())
+        raise
     return len(done)
 
 
