@@ -16,6 +16,7 @@ LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
 BWD_DENSE = 1  # slfp_conv2d_bwd_*_ex flags: SLFP_BWD_DENSE
 MFMA_DEFAULT, MFMA_F16X1, MFMA_F16X3 = 0, 1, 3
 OPT_SGD, OPT_DSGD, OPT_SSGD = 0, 1, 2
+LAYEROUT_LUT_BYTES = 4928  # SLFP_LAYEROUT_LUT_BYTES
 
 # every symbol include/slfp.h declares (tests check the .so exports exactly these)
 SYMBOLS = (
@@ -34,6 +35,8 @@ SYMBOLS = (
     "slfp_conv2d_codes_slice_supported", "slfp_conv2d_fwd_codes_slice", "slfp_maxpool2d_codes_ex", "slfp_maxpool2d_out_shape",
     "slfp_conv2d_entry_supported", "slfp_conv2d_fwd_entry",
     "slfp_conv2d_res_codes_supported", "slfp_conv2d_fwd_res_codes",
+    "slfp_layerout_lut_classes", "slfp_layerout_lut_values", "slfp_layerout_lut_index", "slfp_conv2d_codes_lut_supported",
+    "slfp_conv2d_fwd_codes_lut", "slfp_debug_layerout_lut_mismatches",
 )
 
 
@@ -145,6 +148,12 @@ def load():
         "slfp_conv2d_fwd_entry": (ci, [dp, ctypes.POINTER(ConvIo), vp, vp, vp, vp, vp, ci, vp, vp]),
         "slfp_conv2d_res_codes_supported": (ci, [dp, ctypes.POINTER(ConvIo), ci, ci]),
         "slfp_conv2d_fwd_res_codes": (ci, [dp, ctypes.POINTER(ConvIo), vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp]),
+        "slfp_layerout_lut_classes": (ci, []),
+        "slfp_layerout_lut_values": (ci, [vp, ci]),
+        "slfp_layerout_lut_index": (ci, [cf]),
+        "slfp_conv2d_codes_lut_supported": (ci, [dp, ctypes.POINTER(ConvIo), ci, i64]),
+        "slfp_conv2d_fwd_codes_lut": (ci, [dp, ctypes.POINTER(ConvIo), vp, vp, vp, vp, vp, vp, vp, i64, vp, vp]),
+        "slfp_debug_layerout_lut_mismatches": (ci, [vp, vp]),
     }
     assert set(sigs) == set(SYMBOLS)
     for name, (res, args) in sigs.items():

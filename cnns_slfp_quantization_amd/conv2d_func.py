@@ -224,6 +224,10 @@ _KINDS = {
     "entry": ("slfp_conv2d_entry_supported", "slfp_conv2d_fwd_entry"),              # float32 in, codes out, pointwise
     "res": ("slfp_conv2d_res_supported", "slfp_conv2d_fwd_res"),                    # a residual operand in the epilogue
     "res_codes": ("slfp_conv2d_res_codes_supported", "slfp_conv2d_fwd_res_codes"),  # the same, and the next block's codes next to y
+    "lut": ("slfp_conv2d_codes_lut_supported", "slfp_conv2d_fwd_codes_lut"),        # codes behind the layer-output quantizer: a byte table
+    # codes in, float32 out, for a layer whose epilogue ends in the layer-output quantizer (no ReLU behind it): the code kernel runs
+    # the affine, slfp_quantize_layerout_f32 the quantizer -- the last layer of a chain linked by fusion.link_layerout
+    "codes_lo": ("slfp_conv2d_codes_supported", "slfp_conv2d_fwd_codes_ws"),
 }
 
 
@@ -240,6 +244,8 @@ def _supported(mod, shape, kind, x_codes, out, flags, y_ld=None, desc=None, io=N
     io = io if io is not None else _conv_io(x_codes, out)
     tail = (int(y_ld),) if kind == "slice" else ()
     query = getattr(_lib.load(), _KINDS[kind][0])
+    if kind == "lut":   # the table absorbs the flags; the query takes the pixel stride of the code tensor (C_out: a dense one)
+        return bool(query(ctypes.byref(d), ctypes.byref(io), 1 if mod.bias is not None else 0, int(d.c_out)))
     return bool(query(ctypes.byref(d), ctypes.byref(io), 1 if mod.bias is not None else 0, int(flags), *tail))
 
 
@@ -279,12 +285,18 @@ def _plan(mod, x, weight, nhwc_in, nhwc_out, codes=None):
             if kind in ("res", "res_codes"):
                 # an epilogue ReLU or layer-output quantizer would sit BEFORE the add: not what the residual kernels compute
                 plan.ok = flags == 0 and _supported(mod, shape, kind, x_codes, out, 1 if extra else 0, desc=d, io=plan.io)
+            elif kind == "codes_lo":
+                # fma(r, scale, shift) from the code kernel, then the quantizer: what the fused float32 epilogue computes, step for step
+                plan.ok = flags == 2 and mod._post[0] is not None and _supported(mod, shape, kind, True, None, 0, desc=d, io=plan.io)
+            elif kind == "lut":
+                # the table stands for layer-output quantizer + activation + the reader's quantizer: the epilogue must carry the former
+                plan.ok = bool(flags & 2) and mod._post[0] is not None and _supported(mod, shape, kind, x_codes, out, flags, desc=d, io=plan.io)
             else:
                 plan.ok = _supported(mod, shape, kind, x_codes, out, flags, extra, d, plan.io)
             if kind == "entry" or (kind == "codes" and not plan.ok):
                 plan.ws_bytes = 0   # pointwise: no workspace; refused: the float32 interface's own plan sizes its workspace
             plan.label += (("+codes_in" if x_codes else "") + ("+codes_out" if out is not None and kind != "res_codes" else "")
-                           + {"slice": "+slice", "res": "+res", "res_codes": "+res+trunk_codes"}.get(kind, ""))
+                           + {"slice": "+slice", "res": "+res", "res_codes": "+res+trunk_codes", "lut": "+lut", "codes_lo": "+layerout_pass"}.get(kind, ""))
         if len(mod._plans) >= 64:   # a net fed ever-changing shapes: do not grow without bound
             mod._plans.clear()
         mod._plans[key] = plan
@@ -352,6 +364,8 @@ def _launch(mod, plan, x, weight, bias, y=None, cache=True, res=None, relu=None,
               if kind == "res_codes" else None)
         ws = _workspace(x.device, plan.ws_bytes) if plan.ws_bytes else None
         b, ps, psh, flags = _epilogue_args(mod, bias, x.device)
+        if kind == "codes_lo":
+            flags = 0   # the kernel stops behind the affine; the quantizer is the pass below
         xq = torch.empty_like(x) if stash else None
         head = (x.data_ptr(), blob.data_ptr(), _ptr(b), _ptr(ps), _ptr(psh))
         if kind is None:
@@ -362,9 +376,14 @@ def _launch(mod, plan, x, weight, bias, y=None, cache=True, res=None, relu=None,
             args = (ctypes.byref(d), ctypes.byref(plan.io)) + head + (1 if relu else 0, res.data_ptr(), y.data_ptr(), None)
         elif kind == "res_codes":
             args = (ctypes.byref(d), ctypes.byref(plan.io)) + head + (1 if relu else 0, res.data_ptr(), y.data_ptr(), yc.data_ptr(), None)
+        elif kind == "lut":   # no flags: the ReLU bit is part of the table
+            args = (ctypes.byref(d), ctypes.byref(plan.io)) + head + (mod._code_lut.data_ptr(), y.data_ptr(), int(d.c_out), _ptr(ws))
         else:   # "codes" takes a workspace, "entry" does not
-            args = (ctypes.byref(d), ctypes.byref(plan.io)) + head + (flags, y.data_ptr()) + ((_ptr(ws),) if kind == "codes" else ())
+            args = (ctypes.byref(d), ctypes.byref(plan.io)) + head + (flags, y.data_ptr()) + ((_ptr(ws),) if kind != "entry" else ())
         _lib.check(getattr(_lib.load(), _KINDS[kind][1])(*args, stream.cuda_stream))
+        if kind == "codes_lo":
+            t, y = y, torch.empty_like(y)
+            _lib.check(_lib.load().slfp_quantize_layerout_f32(t.data_ptr(), y.data_ptr(), t.numel(), stream.cuda_stream))
     x_codes = x.dtype == torch.uint8
     # plain attributes, written in one go (nn.Module.__setattr__ costs microseconds per name, on every layer of every forward)
     mod.__dict__.update(_last_kernel=plan.label, _last_input=None if x_codes else x.detach(),
@@ -407,6 +426,19 @@ def _hip_conv2d_codes(mod, x, weight, bias):
         _require_gpu_f32(x, "Conv2d_Q")
     elif not x.is_cuda:
         raise RuntimeError("Conv2d_Q: code tensors live on the ROCm device")
+    lut = mod._code_lut if out is not None else None
+    if lut is not None:
+        # a link of fusion.link_layerout: the table holds activation + reader's quantizer of every layer-output class, and the
+        # activation modules behind this layer pass codes through.  There is no second way to compute that: no kernel is an error.
+        if lut.device != x.device or lut.dtype != torch.uint8 or lut.numel() != _lib.LAYEROUT_LUT_BYTES:
+            raise RuntimeError("Conv2d_Q: `_code_lut` must be a uint8 tensor of SLFP_LAYEROUT_LUT_BYTES bytes on the input's device")
+        plan = None
+        if x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last):
+            plan = _plan(mod, x, weight, True, True, ("lut", x_codes, out, None))
+        if plan is None or not plan.ok:
+            raise RuntimeError("Conv2d_Q: no kernel writes this layer's codes through a layer-output table "
+                               "(slfp_conv2d_codes_lut_supported); call fusion.unlink_codes(model)")
+        return _launch(mod, plan, x, weight, bias)
     if x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last):   # the code path is NHWC only
         if not x_codes and out is not None and mod._code_entry:
             plan = _plan(mod, x, weight, True, True, ("entry", False, out, None))
@@ -415,6 +447,10 @@ def _hip_conv2d_codes(mod, x, weight, bias):
         plan = _plan(mod, x, weight, True, True, ("codes", x_codes, out, None))
         if plan.ok:
             return _launch(mod, plan, x, weight, bias)
+        if x_codes and out is None and mod._post is not None and int(mod._post[2]) == 2:
+            plan = _plan(mod, x, weight, True, True, ("codes_lo", True, None, None))
+            if plan.ok:
+                return _launch(mod, plan, x, weight, bias)
     # anything else takes the float32 interface
     y = _hip_conv2d(mod, hip_decode(x, _act_fmt(mod.q_bit)) if x_codes else x, weight, bias, cache_ok=True)
     return hip_encode(y, out[0], _act_fmt(out[1])) if out is not None else y
@@ -627,6 +663,10 @@ def _conv_class(q_bit, Kw, Ka, bias_default, scaled_bias):
             self._post = None  # (scale, shift, relu): fused eval-BN + ReLU epilogue (fusion.fuse_bn_relu)
             self._code_out = None   # (Ka, q_bit) of the next Conv2d_Q: hand it 1-byte codes (fusion.link_codes)
             self._code_entry = False   # with _code_out on a float32 input: ONE slfp_conv2d_fwd_entry launch where the library has it
+            # with _code_out behind a layer-output epilogue: the uint8 table of SLFP_LAYEROUT_LUT_BYTES entries that maps a
+            # layer-output class to the reader's code (fusion.link_layerout); slfp_conv2d_fwd_codes_lut then runs.  A buffer, so
+            # that it follows the module across devices; not persistent: the state dict keeps the reference's keys
+            self.register_buffer("_code_lut", None, persistent=False)
             self._trunk_code_out = None   # forward(x, residual=r): (Ka, q_bit) of the Conv2d_Q layers that read the result; it then
                                           # carries their codes (fusion.link_trunk).  Not `_code_out`: the result stays float32
             self._last_codes = None

@@ -3,6 +3,7 @@
 #include <cstring>
 #include "slfp_device.hpp"
 #include "slfp_codes.hpp"
+#include "slfp_layerout_lut.hpp"
 #include "slfp_host.hpp"
 
 namespace slfp {
@@ -375,9 +376,10 @@ static bool code_path_ok(const slfp_conv2d_desc* d, int relu) {
 }
 
 // The three route functions take the plan make_plan built for `d`.
-static CodeRoute codes_route(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, bool has_bias, int relu, const ConvPlan& p) {
+// need_table: the producer applies the reader's quantizer through its threshold table (not the table epilogue: lut_route).
+static CodeRoute codes_route(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, bool has_bias, int relu, const ConvPlan& p, bool need_table = true) {
     if (!code_path_ok(d, relu)) return kRouteNone;
-    if (io->y_codes && (!consumer_quant_ok(io) || !enc_table(io->y_ka, y_fmt_of(io->y_qbits), kEncCode)->valid)) return kRouteNone;
+    if (io->y_codes && (!consumer_quant_ok(io) || (need_table && !enc_table(io->y_ka, y_fmt_of(io->y_qbits), kEncCode)->valid))) return kRouteNone;
     if (io->x_codes) {
         if (dwc_applicable(*d, p, has_bias ? reinterpret_cast<const float*>(1) : nullptr, relu)) return kRouteDwc;
         if (pwc_applicable(*d, p, relu, io->y_codes != 0)) return kRoutePwc;
@@ -420,6 +422,22 @@ static bool res_codes_route(const slfp_conv2d_desc* d, const slfp_conv2d_io* io,
     return res_route(d, &rio, has_bias, relu, p) && enc_table(io->y_ka, y_fmt_of(io->y_qbits), kEncCode)->valid;
 }
 
+// The table epilogue (slfp_conv2d_fwd_codes_lut): the code route of the same layer without the layer-output bit, where the
+// selected kernel has a table instance: depthwise 3x3 and 1x1 on codes, dense 3x3 (codes or float32 in), the two 3x3 RGB stems.
+// Large-kernel stems, the entry kernel and the residual forms have none.  A query and an entry point of their own: the four
+// older queries keep refusing SLFP_POST_LAYEROUT.
+static CodeRoute lut_route(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, bool has_bias, const ConvPlan& p) {
+    if (io->y_codes != 1 || (io->x_codes != 0 && io->x_codes != 1) || !consumer_quant_ok(io)) return kRouteNone;
+    // the reader's scale and format are validated as for slfp_conv2d_fwd_codes; its threshold table is not needed
+    const CodeRoute route = codes_route(d, io, has_bias, 0, p, false);
+    switch (route) {
+        case kRouteDwc: case kRouteStemCodes: case kRouteStemSmall: return route;
+        case kRoutePwc: return strcmp(pwc_variant_name(*d, p, true, false, false, true), "none") != 0 ? route : kRouteNone;
+        case kRouteDense: return dense_lut_applicable(*d, p, io->x_codes != 0) ? route : kRouteNone;
+        default: return kRouteNone;
+    }
+}
+
 // slfp_debug_pw_variant: the route the matching forward entry point takes (refused: "none"), then the launcher's own selection.
 static const char* pw_variant(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, bool has_res, bool has_res_codes, int64_t y_ld) {
     ConvPlan p;
@@ -455,14 +473,29 @@ static const char* pw_variant(const slfp_conv2d_desc* d, const slfp_conv2d_io* i
     return pw_variant_name(*d, p, false, false, 1.f, kFmtAct8);
 }
 
+// slfp_debug_layerout_lut_mismatches: every float32 pattern through layerout_bits, its class and back
+__global__ __launch_bounds__(256) void k_layerout_lut_check(unsigned long long* __restrict__ out) {
+    unsigned long long bad = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < (1ull << 32); i += stride) {
+        const uint32_t v = layerout_bits((uint32_t)i);
+        const uint32_t c = layerout_class(v);
+        const uint32_t w = layerout_value(c);
+        const bool vnan = (v & 0x7FFFFFFFu) > 0x7F800000u, wnan = (w & 0x7FFFFFFFu) > 0x7F800000u;   // all NaNs are one class
+        if (c >= (uint32_t)kLayeroutClasses || (vnan ? !wnan : w != v)) ++bad;
+    }
+    if (bad) atomicAdd(out, bad);
+}
+
 // ---- the one argument check of the forward entry points ----
 struct FwdArgs {   // what a forward entry point was handed; io / res / y_ld / workspace: null or 0 where it has none
     const slfp_conv2d_desc* d; const slfp_conv2d_io* io;
     const void* x; const void* wprep; const float* bias; const float* post_scale; const float* post_shift; int relu;
     void* y; const float* res; int64_t y_ld; void* workspace;
     void* y_codes = nullptr;   // slfp_conv2d_fwd_res_codes: the second, uint8 output
+    const uint8_t* lut = nullptr;   // slfp_conv2d_fwd_codes_lut: the byte table of the layer-output classes
 };
-enum FwdKind { kFwdPost, kFwdCodes, kFwdSlice, kFwdEntry, kFwdRes, kFwdResCodes };
+enum FwdKind { kFwdPost, kFwdCodes, kFwdSlice, kFwdEntry, kFwdRes, kFwdResCodes, kFwdLut };
 struct Resolved { ConvPlan p; PostOp post; CodeIo cio; CodeRoute route; };
 
 static int need_workspace(const char* fn, const FwdArgs& a, const ConvPlan& p) {
@@ -484,6 +517,19 @@ static int resolve(FwdKind kind, const char* fn, const FwdArgs& a, Resolved* r) 
     if (!a.x || !a.wprep || !a.y || (with_res && !a.res) || (kind == kFwdResCodes && !a.y_codes)) return fail(SLFP_ERR_BAD_ARG, "%s: null pointer", fn);
     const bool has_bias = a.bias != nullptr;
     r->route = kRouteNone;
+    if (kind == kFwdLut) {   // the table epilogue's own arguments come first
+        if (!a.lut || !a.post_scale || !a.post_shift)
+            return fail(SLFP_ERR_BAD_ARG, "%s: lut, post_scale and post_shift are required (the table is indexed by the layer-output class of the affine's result)", fn);
+        if (!aligned16(a.lut)) return fail(SLFP_ERR_ALIGNMENT, "%s: lut must be 16-byte aligned", fn);
+        if (io->y_codes != 1) return fail(SLFP_ERR_BAD_ARG, "%s: the table epilogue writes codes (io->y_codes == 1)", fn);
+        if (!consumer_quant_ok(io))
+            return fail(SLFP_ERR_BAD_ARG, "%s: io->y_qbits must be 8 or 7 (got %d) and io->y_ka a positive scale within [1e-30, 1e30]", fn, io->y_qbits);
+        if (a.y_ld != d->c_out && !y_ld_ok(d, a.y_ld))
+            return fail(SLFP_ERR_BAD_ARG, "%s: y_ld = %lld must be C_out = %lld or a multiple of 16 above it", fn, (long long)a.y_ld, (long long)d->c_out);
+        r->route = lut_route(d, io, has_bias, r->p);
+        if (r->route == kRouteNone || (a.y_ld != d->c_out && !slice_route(r->route)))
+            return fail(SLFP_ERR_UNSUPPORTED, "%s: this layer / io combination has no table-epilogue kernel (slfp_conv2d_codes_lut_supported)", fn);
+    }
     if (kind == kFwdSlice) {   // the slice's own arguments come first
         if (!io->y_codes) return fail(SLFP_ERR_BAD_ARG, "%s: a channel slice is written as codes (io->y_codes == 1)", fn);
         if (!aligned16(a.y)) return fail(SLFP_ERR_ALIGNMENT, "%s: y (the slice's first channel) must be 16-byte aligned", fn);
@@ -509,6 +555,11 @@ static int resolve(FwdKind kind, const char* fn, const FwdArgs& a, Resolved* r) 
     r->post = PostOp{a.post_scale, a.post_shift, (a.relu & SLFP_POST_RELU) ? 1 : 0, (kind == kFwdPost && (a.relu & SLFP_POST_LAYEROUT)) ? 1 : 0};
     if (kind == kFwdPost) return need_workspace(fn, a, r->p);
     r->cio = CodeIo{io->x_codes != 0, io->y_codes != 0, io->y_ka, y_fmt_of(io->y_qbits), a.y_ld};
+    if (kind == kFwdLut) {
+        r->cio.lut = a.lut;
+        if (a.y_ld == d->c_out) r->cio.y_ld = 0;   // a dense tensor
+        return r->route == kRouteDense ? need_workspace(fn, a, r->p) : SLFP_OK;
+    }
     if (kind == kFwdEntry) {
         if (io->x_codes != 0 || io->y_codes != 1)
             return fail(SLFP_ERR_BAD_ARG, "%s: reads float32 and writes codes (io->x_codes == 0, io->y_codes == 1; "
@@ -632,6 +683,52 @@ int slfp_conv2d_fwd_post(const slfp_conv2d_desc* d, const float* x, const void* 
     if (rc != SLFP_OK) return rc;
     if (d->y_layout == SLFP_LAYOUT_NCHW) rc = slfp_nhwc_to_nchw_f32(y_nhwc, y, d->n, d->c_out, p.h_out, p.w_out, stream);
     return rc;
+}
+
+// ---- the table epilogue: codes behind the layer-output quantizer (csrc/slfp_layerout_lut.hpp) ----
+int slfp_layerout_lut_classes(void) { return kLayeroutClasses; }
+
+int slfp_layerout_lut_values(float* out, int n) {
+    if (!out || n < 0) return fail(SLFP_ERR_BAD_ARG, "slfp_layerout_lut_values: bad argument");
+    for (int i = 0; i < n; ++i) {
+        const uint32_t v = layerout_value((uint32_t)i);
+        memcpy(out + i, &v, 4);
+    }
+    return SLFP_OK;
+}
+
+int slfp_layerout_lut_index(float v) {
+    uint32_t b;
+    memcpy(&b, &v, 4);
+    const uint32_t i = layerout_class(b);
+    if (i == 0u) return (b & 0x7FFFFFFFu) > 0x7F800000u ? 0 : -1;
+    return (i < (uint32_t)kLayeroutClasses && layerout_value(i) == b) ? (int)i : -1;   // -1: not a value of the quantizer
+}
+
+int slfp_debug_layerout_lut_mismatches(unsigned long long* out1, void* stream) {
+    if (!out1) return fail(SLFP_ERR_BAD_ARG, "slfp_debug_layerout_lut_mismatches: null pointer");
+    hipStream_t st = as_stream(stream);
+    if (hipMemsetAsync(out1, 0, sizeof(unsigned long long), st) != hipSuccess) return check_launch("hipMemsetAsync");
+    hipLaunchKernelGGL(k_layerout_lut_check, dim3(256 * 16), dim3(256), 0, st, out1);
+    return check_launch("slfp layer-output class self-check kernel");
+}
+
+int slfp_conv2d_codes_lut_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int64_t y_ld) {
+    ConvPlan p;
+    if (!d || !io || make_plan(d, &p) != SLFP_OK) return 0;
+    const CodeRoute route = lut_route(d, io, has_bias != 0, p);
+    if (route == kRouteNone) return 0;
+    return y_ld == d->c_out || (slice_route(route) && y_ld_ok(d, y_ld));
+}
+
+int slfp_conv2d_fwd_codes_lut(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
+                              const float* bias, const float* post_scale, const float* post_shift, const uint8_t* lut, void* y,
+                              int64_t y_ld, void* workspace, void* stream) {
+    FwdArgs a{d, io, x, wprep, bias, post_scale, post_shift, 0, y, nullptr, y_ld, workspace};
+    a.lut = lut;
+    Resolved r;
+    const int rc = resolve(kFwdLut, "slfp_conv2d_fwd_codes_lut", a, &r);
+    return rc != SLFP_OK ? rc : launch_codes(a, r, as_stream(stream));
 }
 
 // The four queries: the route functions behind a null check and make_plan.

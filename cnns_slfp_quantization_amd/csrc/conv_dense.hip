@@ -27,6 +27,7 @@
 // layers, whose halo tiles do not fit twice in LDS, stay on k_direct in that mode).
 #include "slfp_device.hpp"
 #include "slfp_codes.hpp"
+#include "slfp_layerout_lut.hpp"
 #include "slfp_host.hpp"
 
 namespace slfp {
@@ -179,14 +180,20 @@ __device__ __forceinline__ void dense_epilogue_consts(const DenseParams& p, int 
 
 // TAB_READY: the code table already sits at `smem` (k_dense3x3_res keeps it next to its operand tiles); otherwise it is filled
 // over the dead operand tiles here.
-template <int MT, bool TAB_READY = false>
+// LUTQ (code output; slfp_conv2d_fwd_codes_lut): the codes come from the byte table of the layer-output classes
+// (slfp_layerout_lut.hpp).  The per-tile kernels copy it over the dead operand tiles as they do the threshold table (4.8 KiB
+// instead of 2 KiB of at least 48); k_dense3x3_res (TAB_READY) has 2 KiB per table and less than 2 KiB of the CU's 160 KiB
+// left, so there the table is read from global memory through the vector cache.  (Neither compared with the other placement.)
+template <int MT, bool TAB_READY = false, bool LUTQ = false>
 __device__ __forceinline__ void dense_epilogue_apply(const DenseParams& p, const floatx4 (&acc)[MT][4], unsigned char* smem, int n, int th,
                                                      int tw, int TH, int wm, int wn, int nt0, int col, int kq, const EpiConsts& k) {
     const int gow = tw * kDnTW + col;
-    if (p.yc) {
+    if (LUTQ || p.yc) {
+        const lut_gptr lutg = LUTQ ? enc_carried_ptr(p.enc_out) : nullptr;
         if constexpr (!TAB_READY) {
             __syncthreads();   // every wave has left the main loop: the operand tiles in LDS are dead
-            enc_fill<kDnThreads>(reinterpret_cast<uint2*>(smem), p.enc_out);
+            if constexpr (LUTQ) layerout_lut_fill<kDnThreads>(smem, lutg);
+            else enc_fill<kDnThreads>(reinterpret_cast<uint2*>(smem), p.enc_out);
             __syncthreads();
         }
         const float r1 = p.enc_out.r1, lo = p.enc_out.lo, hi = p.enc_out.hi;
@@ -206,7 +213,9 @@ __device__ __forceinline__ void dense_epilogue_apply(const DenseParams& p, const
                 r.z = ((acc[i][j][2] + k.bq[j].z) * p.s1x) * p.s2;
                 r.w = ((acc[i][j][3] + k.bq[j].w) * p.s1x) * p.s2;
                 r = post_apply_v(r, po, k.pv[j]);
-                if (p.y_sgn) c[j] = code_sign4(enc4_code<false>(r, r1, lo, hi, smem), r, p.y_fmt);
+                if constexpr (LUTQ && TAB_READY) c[j] = lut4_code(r, lutg);
+                else if constexpr (LUTQ) c[j] = lut4_code(r, smem);
+                else if (p.y_sgn) c[j] = code_sign4(enc4_code<false>(r, r1, lo, hi, smem), r, p.y_fmt);
                 else c[j] = enc4_code_relu(r, r1, lo, hi, smem);
             }
             rows_transpose4(c[0], c[1], c[2], c[3]);
@@ -239,12 +248,12 @@ __device__ __forceinline__ void dense_epilogue_apply(const DenseParams& p, const
 // float32 stores (16 bytes per lane: 4 consecutive channels of one pixel) or the consumer's 1-byte codes.  Code output: the 4
 // channel tiles of a wave are encoded, transposed across the lane quarters (rows_transpose4) so that a lane holds 16
 // CONSECUTIVE channels of its pixel, and stored as one 16-byte piece.
-template <int MT>
+template <int MT, bool LUTQ = false>
 __device__ __forceinline__ void dense_epilogue(const DenseParams& p, const floatx4 (&acc)[MT][4], unsigned char* smem, int n, int th,
                                                int tw, int TH, int wm, int wn, int nt0, int col, int kq) {
     EpiConsts k;
     dense_epilogue_consts(p, wn, nt0, kq, k);
-    dense_epilogue_apply<MT, false>(p, acc, smem, n, th, tw, TH, wm, wn, nt0, col, kq, k);
+    dense_epilogue_apply<MT, false, LUTQ>(p, acc, smem, n, th, tw, TH, wm, wn, nt0, col, kq, k);
 }
 
 // WM x WN = 8 waves; MT = output rows per wave.  Both operands arrive by LDS-DMA: no VALU work
@@ -258,7 +267,8 @@ __device__ __forceinline__ void dense_epilogue(const DenseParams& p, const float
 // 3 (round 3): the tile THREE taps ahead is requested; a tap's wait leaves the requests of the previous tap in flight
 // (counted vmcnt: they are the youngest -- the halo pieces of a tap are issued before its weight pieces), so every request has
 // two taps to land.
-template <int WM, int WN, int MT, int PASSES, int NSLOT, int NWB = 2>
+// LUTQ: the table epilogue (dense_epilogue_apply).
+template <int WM, int WN, int MT, int PASSES, int NSLOT, int NWB = 2, bool LUTQ = false>
 __global__ __launch_bounds__(kDnThreads, (MT == 4 || PASSES == 3 ? 2 : 4)) void k_dense_mfma(const DenseParams p) {
     static_assert(WM * WN == 8, "8 waves");
     static_assert(NWB == 2 || NWB == 3, "two or three weight buffers");
@@ -429,7 +439,7 @@ __global__ __launch_bounds__(kDnThreads, (MT == 4 || PASSES == 3 ? 2 : 4)) void 
         xb ^= 1;
     }
 
-    dense_epilogue<MT>(p, acc, smem, n, th, tw, TH, wm, wn, nt0, col, kq);
+    dense_epilogue<MT, LUTQ>(p, acc, smem, n, th, tw, TH, wm, wn, nt0, col, kq);
 }
 
 // ======================================================================================
@@ -441,7 +451,7 @@ __global__ __launch_bounds__(kDnThreads, (MT == 4 || PASSES == 3 ? 2 : 4)) void 
 // computed ONCE per workgroup; per tap what is left is one add per fragment (the halo buffer of the chunk) and one XOR for
 // the second k-step (the swizzle moves bit 6 with it).  Same staging, same waits, same MFMA order: bit-identical results.
 // ======================================================================================
-template <int WM, int WN, int MT, int NSLOT, int NWB>
+template <int WM, int WN, int MT, int NSLOT, int NWB, bool LUTQ = false>
 __global__ __launch_bounds__(kDnThreads, (MT == 4 ? 2 : 4)) void k_dense3x3(const DenseParams p) {
     static_assert(WM * WN == 8, "8 waves");
     constexpr int TH = WM * MT, BN = WN * 64, WT = BN * 128;
@@ -581,7 +591,7 @@ __global__ __launch_bounds__(kDnThreads, (MT == 4 ? 2 : 4)) void k_dense3x3(cons
         xb ^= 1;
     }
 
-    dense_epilogue<MT>(p, acc, smem, n, th, tw, TH, wm, wn, nt0, col, kq);
+    dense_epilogue<MT, LUTQ>(p, acc, smem, n, th, tw, TH, wm, wn, nt0, col, kq);
 }
 
 // ======================================================================================
@@ -600,7 +610,7 @@ __global__ __launch_bounds__(kDnThreads, (MT == 4 ? 2 : 4)) void k_dense3x3(cons
 // LDS tile -- the loads of the NEXT tile are issued before the MFMAs of the current one and consumed behind them.  Saves the
 // pre-pass (64 -> 64 @224 at batch 128: 1.64 GB read + 0.82 GB written + 1.04 GB read back, 427 us) for ~50 VALU
 // instructions per 16-byte chunk.
-template <int MT, int NSLOT, bool ENCX>
+template <int MT, int NSLOT, bool ENCX, bool LUTQ = false>
 __global__ __launch_bounds__(kDnThreads, 2) void k_dense3x3_res(const DenseParams p) {
     constexpr int TH = 8 * MT, WT = 64 * 128;
     constexpr int IW = kDnTW + 2, IH = TH + 2, NPIX = IH * IW, PIECES = (NPIX + 7) / 8;
@@ -730,7 +740,9 @@ __global__ __launch_bounds__(kDnThreads, 2) void k_dense3x3_res(const DenseParam
     } else {
         stage_tile(tile, 0);
     }
-    if (p.yc) enc_fill<kDnThreads>(reinterpret_cast<uint2*>(tab), p.enc_out);
+    if constexpr (!LUTQ) {
+        if (p.yc) enc_fill<kDnThreads>(reinterpret_cast<uint2*>(tab), p.enc_out);
+    }
 
     uint32_t xo[MT + 2][3];
 #pragma unroll
@@ -816,7 +828,7 @@ __global__ __launch_bounds__(kDnThreads, 2) void k_dense3x3_res(const DenseParam
 #ifdef SLFP_RES_NOST
             if (acc[0][0][0] == 12345.678f)   // never true for these inputs: the epilogue and its stores are skipped
 #endif
-            dense_epilogue_apply<MT, true>(p, acc, tab, n, th, tw, TH, wave, 0, nt0, col, kq, epi);
+            dense_epilogue_apply<MT, true, LUTQ>(p, acc, tab, n, th, tw, TH, wave, 0, nt0, col, kq, epi);
         }
         if (!has_next) break;
         tile = next;
@@ -918,11 +930,12 @@ struct DenseSel {
     int nwb, nslot;   // template arguments NWB / NSLOT of the body
     int res_mt;       // kBodyRes: MFMA rows per wave (2: 16-row tiles, 1: 8-row tiles)
     bool encx;        // kBodyRes: the float32 halo is encoded where it is staged (no pre-pass)
+    bool lut;         // template argument LUTQ: set by the launcher after dense_select; the tiling does not depend on it
 };
 
 static bool dense_select(const slfp_conv2d_desc& d, int passes, int64_t h_out, int64_t w_out, bool x_codes, DenseSel* s) {
     s->planes = dense_planes(d, passes);
-    s->body = kBodyGen; s->nwb = 2; s->nslot = kMaxSlots; s->res_mt = 0; s->encx = false;
+    s->body = kBodyGen; s->nwb = 2; s->nslot = kMaxSlots; s->res_mt = 0; s->encx = false; s->lut = false;
     if (!dense_choose(d, s->planes, h_out, w_out, &s->g)) return false;
     if (dense_res_applicable(d, s->planes, (int)dense_cp(d))) {
         s->body = kBodyRes;
@@ -958,13 +971,33 @@ const char* dense_variant_name(const slfp_conv2d_desc& d, const ConvPlan& plan, 
     return buf;
 }
 
+// The table-epilogue instances of the per-tile kernels: what dense_select picks for the 3x3 stride-1 layers of the layerout nets
+// (VGG16_gelu at 32 x 32: 128 -> 128 / 256 at 16 x 16 and 8 x 8, 256 / 512 -> 512 at 4 x 4 and 2 x 2) and for small test shapes.
+constexpr bool dense_lut_instance(int wm, int wn, int mt, int passes, int nslot, int body, int nwb) {
+    if (passes != 1) return false;
+    const int t = wm * 100 + wn * 10 + mt;
+    return (t == 424 && body == kBody3x3 && nwb == 3 && nslot == 6) || (t == 422 && body == kBodyGen && nwb == 2 && nslot == 3) ||
+           ((t == 421 || t == 811) && body == kBody3x3 && nwb == 2 && nslot == 3);
+}
+
 template <int WM, int WN, int MT, int PASSES, int NSLOT>
-static int launch_dense_tps(DenseParams& p, const DenseSel& s, hipStream_t stream) {
+static int launch_dense_tps(DenseParams& p, const DenseSel& s, hipStream_t stream, bool dry = false) {
     auto fn = k_dense_mfma<WM, WN, MT, PASSES, NSLOT>;
     if constexpr (PASSES == 1) { if (s.nwb == 3) fn = k_dense_mfma<WM, WN, MT, PASSES, NSLOT, 3>; }
     if constexpr (PASSES == 1 && NSLOT <= 8 && MT != 2) {
         if (s.body == kBody3x3) fn = s.nwb == 3 ? k_dense3x3<WM, WN, MT, NSLOT, 3> : k_dense3x3<WM, WN, MT, NSLOT, 2>;
     }
+    if (s.lut) {
+        bool found = false;
+        if constexpr (dense_lut_instance(WM, WN, MT, PASSES, NSLOT, kBodyGen, 2)) { if (s.body == kBodyGen && s.nwb == 2) { fn = k_dense_mfma<WM, WN, MT, PASSES, NSLOT, 2, true>; found = true; } }
+        if constexpr (dense_lut_instance(WM, WN, MT, PASSES, NSLOT, kBodyGen, 3)) { if (s.body == kBodyGen && s.nwb == 3) { fn = k_dense_mfma<WM, WN, MT, PASSES, NSLOT, 3, true>; found = true; } }
+        if constexpr (NSLOT <= 8 && MT != 2) {
+            if constexpr (dense_lut_instance(WM, WN, MT, PASSES, NSLOT, kBody3x3, 2)) { if (s.body == kBody3x3 && s.nwb == 2) { fn = k_dense3x3<WM, WN, MT, NSLOT, 2, true>; found = true; } }
+            if constexpr (dense_lut_instance(WM, WN, MT, PASSES, NSLOT, kBody3x3, 3)) { if (s.body == kBody3x3 && s.nwb == 3) { fn = k_dense3x3<WM, WN, MT, NSLOT, 3, true>; found = true; } }
+        }
+        if (!found) return fail(SLFP_ERR_UNSUPPORTED, "dense MFMA conv: no table-epilogue instance for this tiling");
+    }
+    if (dry) return SLFP_OK;
     const int rc = raise_lds_limit(reinterpret_cast<const void*>(fn), 160 * 1024);  // once per (device, kernel)
     if (rc != SLFP_OK) return rc;
     hipLaunchKernelGGL(fn, dim3(p.nblocks), dim3(kDnThreads), s.g.lds, stream, p);
@@ -972,15 +1005,15 @@ static int launch_dense_tps(DenseParams& p, const DenseSel& s, hipStream_t strea
 }
 
 template <int WM, int WN, int MT, int PASSES>
-static int launch_dense_tp(DenseParams& p, const DenseSel& s, hipStream_t stream) {
-    if (s.nslot == 3) return launch_dense_tps<WM, WN, MT, PASSES, 3>(p, s, stream);
-    if (s.nslot == 6) return launch_dense_tps<WM, WN, MT, PASSES, 6>(p, s, stream);
-    return launch_dense_tps<WM, WN, MT, PASSES, kMaxSlots>(p, s, stream);
+static int launch_dense_tp(DenseParams& p, const DenseSel& s, hipStream_t stream, bool dry) {
+    if (s.nslot == 3) return launch_dense_tps<WM, WN, MT, PASSES, 3>(p, s, stream, dry);
+    if (s.nslot == 6) return launch_dense_tps<WM, WN, MT, PASSES, 6>(p, s, stream, dry);
+    return launch_dense_tps<WM, WN, MT, PASSES, kMaxSlots>(p, s, stream, dry);
 }
 
 template <int WM, int WN, int MT>
-static int launch_dense_t(DenseParams& p, const DenseSel& s, hipStream_t stream) {
-    return s.planes == 2 ? launch_dense_tp<WM, WN, MT, 3>(p, s, stream) : launch_dense_tp<WM, WN, MT, 1>(p, s, stream);
+static int launch_dense_t(DenseParams& p, const DenseSel& s, hipStream_t stream, bool dry) {
+    return s.planes == 2 ? launch_dense_tp<WM, WN, MT, 3>(p, s, stream, dry) : launch_dense_tp<WM, WN, MT, 1>(p, s, stream, dry);
 }
 
 template <int MT, int NSLOT>
@@ -995,6 +1028,7 @@ static int launch_dense_res_t(DenseParams& p, const DenseSel& s, hipStream_t str
     if (gs >= 8) gs -= gs % 8;
     auto fn = k_dense3x3_res<MT, NSLOT, false>;
     if (s.encx) fn = k_dense3x3_res<MT, NSLOT, true>;
+    if (s.lut) fn = s.encx ? k_dense3x3_res<MT, NSLOT, true, true> : k_dense3x3_res<MT, NSLOT, false, true>;
     const int rc = raise_lds_limit(reinterpret_cast<const void*>(fn), 160 * 1024);
     if (rc != SLFP_OK) return rc;
     p.nblocks = (uint32_t)(gs * p.n_blocks);
@@ -1005,6 +1039,18 @@ static int launch_dense_res_t(DenseParams& p, const DenseSel& s, hipStream_t str
 static int launch_dense_res(DenseParams& p, const DenseSel& s, hipStream_t stream) {
     if (s.res_mt == 2) return launch_dense_res_t<2, 6>(p, s, stream);
     return launch_dense_res_t<1, 3>(p, s, stream);
+}
+
+static int launch_dense_cfg(DenseParams& p, const DenseSel& sel, hipStream_t stream, bool dry) {
+    const DenseCfg& c = sel.g.cfg;
+    switch (c.wm * 100 + c.wn * 10 + c.mt) {
+        case 244: return launch_dense_t<2, 4, 4>(p, sel, stream, dry);
+        case 424: return launch_dense_t<4, 2, 4>(p, sel, stream, dry);
+        case 422: return launch_dense_t<4, 2, 2>(p, sel, stream, dry);
+        case 421: return launch_dense_t<4, 2, 1>(p, sel, stream, dry);
+        case 812: return launch_dense_t<8, 1, 2>(p, sel, stream, dry);
+        default: return launch_dense_t<8, 1, 1>(p, sel, stream, dry);
+    }
 }
 
 // code interface: is there a dense kernel for this layer with code input / output?  (the float32-interface kernel with a decode
@@ -1062,7 +1108,15 @@ int launch_dense_mfma_io(const slfp_conv2d_desc& d, const ConvPlan& plan, const 
     p.yc = nullptr; p.y_sgn = 0; p.y_fmt = kFmtAct8; p.enc_out.valid = 0;
     p.x32 = nullptr; p.enc_in.valid = 0;
     if (tx) { p.x32 = x; p.enc_in = enc_compact(*tx); }
-    if (io.y_codes) {
+    if (io.lut) {
+        if (!io.y_codes || !post.scale) return fail(SLFP_ERR_BAD_ARG, "dense MFMA conv: the table epilogue needs code output and post_scale / post_shift");
+        enc_carry_ptr(p.enc_out, io.lut);
+        sel.lut = true;
+        p.yc = reinterpret_cast<uint8_t*>(y_any);
+        p.y = nullptr;
+        p.y_sgn = 1;
+        p.y_fmt = io.y_fmt;
+    } else if (io.y_codes) {
         const EncArgs* t = enc_table(io.y_ka, io.y_fmt, kEncCode);
         if (!t->valid) return fail(SLFP_ERR_UNSUPPORTED, "dense MFMA conv: no code table for the consumer's scale");
         p.enc_out = *t;
@@ -1087,14 +1141,17 @@ int launch_dense_mfma_io(const slfp_conv2d_desc& d, const ConvPlan& plan, const 
     if (nblocks > 0x7FFFFFFF) return fail(SLFP_ERR_UNSUPPORTED, "dense MFMA conv: grid too large");
     p.nblocks = (uint32_t)nblocks;
     if (sel.body == kBodyRes) return launch_dense_res(p, sel, stream);
-    switch (g.cfg.wm * 100 + g.cfg.wn * 10 + g.cfg.mt) {
-        case 244: return launch_dense_t<2, 4, 4>(p, sel, stream);
-        case 424: return launch_dense_t<4, 2, 4>(p, sel, stream);
-        case 422: return launch_dense_t<4, 2, 2>(p, sel, stream);
-        case 421: return launch_dense_t<4, 2, 1>(p, sel, stream);
-        case 812: return launch_dense_t<8, 1, 2>(p, sel, stream);
-        default: return launch_dense_t<8, 1, 1>(p, sel, stream);
-    }
+    return launch_dense_cfg(p, sel, stream, false);
+}
+
+// Is there a table-epilogue instance (slfp_conv2d_fwd_codes_lut) of the kernel dense_select picks for this layer?  Host only.
+bool dense_lut_applicable(const slfp_conv2d_desc& d, const ConvPlan& plan, bool x_codes) {
+    DenseSel sel;
+    if (!dense_codes_applicable(d, plan, 0, true) || !dense_select(d, plan.passes, plan.h_out, plan.w_out, x_codes, &sel)) return false;
+    if (sel.body == kBodyRes) return true;
+    sel.lut = true;
+    DenseParams p = {};   // the dry dispatch reads nothing of it
+    return launch_dense_cfg(p, sel, nullptr, true) == SLFP_OK;
 }
 
 }  // namespace slfp

@@ -11,6 +11,7 @@
 #include "slfp_device.hpp"
 #include "slfp_enc.hpp"
 #include "slfp_codes.hpp"
+#include "slfp_layerout_lut.hpp"
 #include "slfp_host.hpp"
 
 namespace slfp {
@@ -273,7 +274,9 @@ __global__ __launch_bounds__(256) void k_stem(const float* __restrict__ x, const
 // TH: output rows per workgroup (16 for the table variant: the 2 KiB table + 3.4 KiB of weights a workgroup stages are
 // then paid once per 32 KiB of output instead of once per 16 KiB).
 // YC: the output leaves as the 1-byte codes of the next layer's QA(. / Ka) (slfp_codes.hpp): a lane's 4 channels are one dword.
-template <int FMT, int KH, int KW, int C, int S, int O, bool TAB = false, int TH = kStemTH, bool YC = false>
+// LUTQ (YC; slfp_conv2d_fwd_codes_lut): the codes come from the byte table of the layer-output classes (slfp_layerout_lut.hpp),
+// kept in LDS in the reader's threshold table's place: 4.8 KiB next to the 18 KiB of weights, halo tile and input table.
+template <int FMT, int KH, int KW, int C, int S, int O, bool TAB = false, int TH = kStemTH, bool YC = false, bool LUTQ = false>
 __global__ __launch_bounds__(256) void k_stem_fixed(const float* __restrict__ x, const float* __restrict__ wq,
                                                     const float* __restrict__ bias, float* __restrict__ y,
                                                     const StemParams p) {
@@ -284,10 +287,12 @@ __global__ __launch_bounds__(256) void k_stem_fixed(const float* __restrict__ x,
     __shared__ __attribute__((aligned(16))) float sW[NW];
     __shared__ __attribute__((aligned(16))) float tile[IH * IWC];
     __shared__ __attribute__((aligned(16))) uint32_t sT[TAB ? 2 * (kEncEntries + 1) : 16];
-    __shared__ __attribute__((aligned(16))) unsigned char senc[YC ? ((kEncEntries * 8 + 15) & ~15) : 16];
+    static_assert(!LUTQ || YC, "the table epilogue belongs to the code-writing forms");
+    __shared__ __attribute__((aligned(16))) unsigned char senc[LUTQ ? kLayeroutLutBytes : (YC ? ((kEncEntries * 8 + 15) & ~15) : 16)];
     if constexpr (TAB) enc_fill<256>(reinterpret_cast<uint2*>(sT), p.enc);
     else lut_fill<FMT>(sT);
-    if constexpr (YC) enc_fill_compact<256>(reinterpret_cast<uint2*>(senc), p.enc_out);
+    if constexpr (LUTQ) layerout_lut_fill<256>(senc, enc_carried_ptr(p.enc_out));
+    else if constexpr (YC) enc_fill_compact<256>(reinterpret_cast<uint2*>(senc), p.enc_out);
     for (int i = threadIdx.x * 4; i < NW; i += 256 * 4)
         *reinterpret_cast<float4*>(sW + i) = *reinterpret_cast<const float4*>(wq + i);
 
@@ -391,6 +396,10 @@ __global__ __launch_bounds__(256) void k_stem_fixed(const float* __restrict__ x,
                 PostOp po = p.post;
                 po.relu = 0;   // with code output the ReLU is the quantizer's (enc4_code_relu)
                 r = post_apply_v(r, po, pv);
+                if constexpr (LUTQ) {
+                    *reinterpret_cast<uint32_t*>(yc + (uint32_t)(q * p.Wo * O)) = lut4_code(r, senc);
+                    continue;
+                }
                 uint32_t code = p.sgn ? enc4_code<false>(r, p.enc_out.r1, p.enc_out.lo, p.enc_out.hi, senc)
                                       : enc4_code_relu(r, p.enc_out.r1, p.enc_out.lo, p.enc_out.hi, senc);
                 if (p.sgn) {
@@ -452,7 +461,8 @@ __global__ __launch_bounds__(256) void k_stem_fixed(const float* __restrict__ x,
 //   code output (YC) is one 8-byte store per lane (a wave: 512 contiguous bytes).
 // One workgroup = one image, a 16 x 16 output tile; a wave owns 4 tile rows = 4 units of 16 pixels.
 // ======================================================================================
-template <bool YC>
+// LUTQ (YC): as in k_stem_fixed, the table of the layer-output classes in LDS in the reader's threshold table's place.
+template <bool YC, bool LUTQ = false>
 __global__ __launch_bounds__(256) void k_stem_mx(const float* __restrict__ x, const float* __restrict__ wq,
                                                  const float* __restrict__ bias, float* __restrict__ y, const StemParams p) {
     constexpr int KH = 3, KW = 3, C = 3, S = 2, O = 32, TH = 16;
@@ -461,11 +471,13 @@ __global__ __launch_bounds__(256) void k_stem_mx(const float* __restrict__ x, co
     typedef float f32x4m __attribute__((ext_vector_type(4)));
     __shared__ __attribute__((aligned(16))) float tile[N_IN + 1];   // [IH][IWC] + one zero word (the 28th tap)
     __shared__ __attribute__((aligned(16))) uint32_t sT[2 * (kEncEntries + 1)];
-    __shared__ __attribute__((aligned(16))) unsigned char senc[YC ? ((kEncEntries * 8 + 15) & ~15) : 16];
+    static_assert(!LUTQ || YC, "the table epilogue belongs to the code-writing forms");
+    __shared__ __attribute__((aligned(16))) unsigned char senc[LUTQ ? kLayeroutLutBytes : (YC ? ((kEncEntries * 8 + 15) & ~15) : 16)];
     constexpr int SP = 36;   // staging row pitch in floats: 128 B of channels + 16 B, so the 16 pixels' float4 writes spread over the banks
     __shared__ __attribute__((aligned(16))) float stg[YC ? 4 : 4 * 16 * SP];   // float32 output: one 16-pixel unit per wave
     enc_fill<256>(reinterpret_cast<uint2*>(sT), p.enc);
-    if constexpr (YC) enc_fill_compact<256>(reinterpret_cast<uint2*>(senc), p.enc_out);
+    if constexpr (LUTQ) layerout_lut_fill<256>(senc, enc_carried_ptr(p.enc_out));
+    else if constexpr (YC) enc_fill_compact<256>(reinterpret_cast<uint2*>(senc), p.enc_out);
     if (threadIdx.x == 0) tile[N_IN] = 0.f;
 
     uint32_t b = xcd_remap(blockIdx.x, p.nblocks);
@@ -573,7 +585,10 @@ __global__ __launch_bounds__(256) void k_stem_mx(const float* __restrict__ x, co
         if constexpr (YC) {
             uint32_t cA, cB;
             const float4 ra = make_float4(r[0], r[1], r[2], r[3]), rb = make_float4(r[4], r[5], r[6], r[7]);
-            if (p.sgn) {
+            if constexpr (LUTQ) {
+                cA = lut4_code(ra, senc);
+                cB = lut4_code(rb, senc);
+            } else if (p.sgn) {
                 cA = enc4_code<true>(ra, p.enc_out.r1, p.enc_out.lo, p.enc_out.hi, senc);
                 cB = enc4_code<true>(rb, p.enc_out.r1, p.enc_out.lo, p.enc_out.hi, senc);
                 if (p.fmt_out == kFmtSfp7) {
@@ -657,6 +672,16 @@ static int try_launch_stem(const slfp_conv2d_desc& d, const ConvPlan& plan, cons
             if (mx && !(io && io->y_codes)) {
                 hipLaunchKernelGGL((k_stem_mx<false>), dim3(p.nblocks), dim3(256), 0, stream, x, wq_hwio, bias, y, p);
                 return check_launch("slfp stem conv kernel (3x3x3 s2 -> 32, float32 MFMA)");
+            }
+            if (io && io->lut) {       // the table epilogue (slfp_conv2d_fwd_codes_lut)
+                if (!io->y_codes || !post.scale) return fail(SLFP_ERR_BAD_ARG, "stem (codes): the table epilogue needs code output and post_scale / post_shift");
+                p.enc_out.valid = 0;
+                enc_carry_ptr(p.enc_out, io->lut);
+                p.sgn = 1;
+                p.fmt_out = io->y_fmt;
+                if (mx) hipLaunchKernelGGL((k_stem_mx<true, true>), dim3(p.nblocks), dim3(256), 0, stream, x, wq_hwio, bias, y, p);
+                else hipLaunchKernelGGL((k_stem_fixed<kFmtAct8, 3, 3, 3, 2, 32, true, TH, true, true>), dim3(p.nblocks), dim3(256), 0, stream, x, wq_hwio, bias, y, p);
+                return check_launch("slfp stem conv kernel (3x3x3 s2 -> 32, table epilogue)");
             }
             if (io && io->y_codes) {   // output as the next layer's codes (slfp_conv2d_fwd_codes)
                 const EncArgs* tc = enc_table(io->y_ka, io->y_fmt, kEncCode);

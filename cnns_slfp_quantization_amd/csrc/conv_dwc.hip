@@ -22,6 +22,7 @@
 #include "slfp_device.hpp"
 #include "slfp_enc.hpp"
 #include "slfp_codes.hpp"
+#include "slfp_layerout_lut.hpp"
 #include "slfp_host.hpp"
 
 namespace slfp {
@@ -50,17 +51,22 @@ typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
 
 // S: stride; LCS: log2(lanes across channels) = 3 / 4 / 5 for C = 32 / 64 / >= 128; TH x TW: output rows x columns per lane;
 // YC: output as codes (else float32); POST: fused per-channel scale / shift; SIGNED: no ReLU before the output quantizer.
+// LUTQ (YC, POST; slfp_conv2d_fwd_codes_lut): the code is the byte table's entry for the layer-output class of the affine's
+// result (slfp_layerout_lut.hpp); the table (4.8 KiB) takes the place of the reader's threshold table in LDS -- the kernel
+// keeps 1 KiB besides it, and a lookup is one ds_read_u8 next to the decode lookups it already issues.
 // VALU-issue-bound (profiles/r03c*): what is counted is instructions per output element.  A lane's TW adjacent columns
 // share TW + 2 decoded input columns; row / column validity is one select each on the row and the column part of the
 // offset (the parts are >= 2^30 when invalid, so their sum is out of the descriptor's range: tensors are < 1 GiB).
-template <int S, int LCS, int TH, int TW, bool YC, bool POST, bool SIGNED>
+template <int S, int LCS, int TH, int TW, bool YC, bool POST, bool SIGNED, bool LUTQ = false>
 __global__ __launch_bounds__(kDwcThreads) void k_dwc(const uint8_t* __restrict__ x, const float* __restrict__ wq,
                                                      void* __restrict__ y, const DwcParams p) {
     constexpr int LC = 1 << LCS;
     constexpr int NR = (TH - 1) * S + 3, NC = (TW - 1) * S + 3;
-    __shared__ __attribute__((aligned(16))) unsigned char senc[YC ? ((kEncEntries * 8 + 15) & ~15) : 16];
+    static_assert(!LUTQ || (YC && POST && SIGNED), "the table epilogue writes codes behind an affine; the ReLU lies in the table");
+    __shared__ __attribute__((aligned(16))) unsigned char senc[LUTQ ? kLayeroutLutBytes : (YC ? ((kEncEntries * 8 + 15) & ~15) : 16)];
     __shared__ __attribute__((aligned(16))) uint32_t sdec[256];
-    if constexpr (YC) enc_fill<kDwcThreads>(reinterpret_cast<uint2*>(senc), p.enc);
+    if constexpr (LUTQ) layerout_lut_fill<kDwcThreads>(senc, enc_carried_ptr(p.enc));
+    else if constexpr (YC) enc_fill<kDwcThreads>(reinterpret_cast<uint2*>(senc), p.enc);
     if (p.fmt_in == kFmtSfp7) dec_fill<kFmtSfp7, kDecF32, kDwcThreads>(sdec);
     else dec_fill<kFmtAct8, kDecF32, kDwcThreads>(sdec);
     const unsigned char* dtab = reinterpret_cast<const unsigned char*>(sdec);
@@ -162,7 +168,9 @@ __global__ __launch_bounds__(kDwcThreads) void k_dwc(const uint8_t* __restrict__
             const uint32_t so = ocol[q] + orow;
             if constexpr (YC) {
                 uint32_t code;
-                if constexpr (SIGNED) {
+                if constexpr (LUTQ) {
+                    code = lut4_code(make_float4(rr[0], rr[1], rr[2], rr[3]), senc);
+                } else if constexpr (SIGNED) {
                     code = enc4_code<true>(make_float4(rr[0], rr[1], rr[2], rr[3]), r1, lo, hi, senc);
                     if (p.fmt_out == kFmtSfp7) code = (code & 0x3F3F3F3Fu) | ((code & 0x80808080u) >> 1);
                 } else {
@@ -212,24 +220,30 @@ int launch_dwc(const slfp_conv2d_desc& d, const ConvPlan& plan, const uint8_t* x
     p.relu = post.relu;
     p.post_scale = post.scale; p.post_shift = post.shift;
     p.enc.valid = 0;
-    if (y_codes) {
+    if (io.lut) {
+        if (!y_codes || !post.scale) return fail(SLFP_ERR_BAD_ARG, "dw3x3 (codes): the table epilogue needs code output and post_scale / post_shift");
+        enc_carry_ptr(p.enc, io.lut);
+    } else if (y_codes) {
         const EncArgs* t = enc_table(io.y_ka, io.y_fmt, kEncCode);
         if (!t->valid) return fail(SLFP_ERR_UNSUPPORTED, "dw3x3 (codes): no code table for the consumer's scale %g", (double)io.y_ka);
         p.enc = *t;
     }
     const bool has_post = post.scale != nullptr;
     const bool sgn = !post.relu;
-#define SLFP_DWC_L(SS, LL, TT, WW, YY, PP, GG) \
-    hipLaunchKernelGGL((k_dwc<SS, LL, TT, WW, YY, PP, GG>), dim3(p.nblocks), dim3(kDwcThreads), 0, stream, x, wq9c, y, p)
+#define SLFP_DWC_L(SS, LL, TT, WW, YY, PP, GG, ...) \
+    hipLaunchKernelGGL((k_dwc<SS, LL, TT, WW, YY, PP, GG, ##__VA_ARGS__>), dim3(p.nblocks), dim3(kDwcThreads), 0, stream, x, wq9c, y, p)
 #define SLFP_DWC_P(SS, LL, TT, WW) \
     do { if (y_codes) { if (has_post) { if (sgn) SLFP_DWC_L(SS, LL, TT, WW, true, true, true); else SLFP_DWC_L(SS, LL, TT, WW, true, true, false); } \
                         else { if (sgn) SLFP_DWC_L(SS, LL, TT, WW, true, false, true); else SLFP_DWC_L(SS, LL, TT, WW, true, false, false); } } \
          else { if (has_post) SLFP_DWC_L(SS, LL, TT, WW, false, true, false); else SLFP_DWC_L(SS, LL, TT, WW, false, false, false); } } while (0)
+#define SLFP_DWC_T(SS, LL, TT, WW) \
+    do { if (io.lut) SLFP_DWC_L(SS, LL, TT, WW, true, true, true, true); else SLFP_DWC_P(SS, LL, TT, WW); } while (0)
 #define SLFP_DWC_S(SS, TT, WW) \
-    do { if (lcs == 5) SLFP_DWC_P(SS, 5, TT, WW); else if (lcs == 4) SLFP_DWC_P(SS, 4, TT, WW); else SLFP_DWC_P(SS, 3, TT, WW); } while (0)
+    do { if (lcs == 5) SLFP_DWC_T(SS, 5, TT, WW); else if (lcs == 4) SLFP_DWC_T(SS, 4, TT, WW); else SLFP_DWC_T(SS, 3, TT, WW); } while (0)
     if (S == 2) SLFP_DWC_S(2, 4, 1);
     else SLFP_DWC_S(1, 7, 2);
 #undef SLFP_DWC_S
+#undef SLFP_DWC_T
 #undef SLFP_DWC_P
 #undef SLFP_DWC_L
     return check_launch("slfp dw3x3 (codes) kernel");

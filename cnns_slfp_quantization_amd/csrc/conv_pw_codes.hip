@@ -27,6 +27,7 @@
 #include "slfp_device.hpp"
 #include "slfp_enc.hpp"
 #include "slfp_codes.hpp"
+#include "slfp_layerout_lut.hpp"
 #include "slfp_host.hpp"
 #include "conv_pw_params.hpp"
 
@@ -83,19 +84,25 @@ constexpr int kPwcThreads = 512;
 // DUAL (RES only, N a multiple of 16; slfp_conv2d_fwd_res_codes): the finished float32 value -- after the add and the ReLU -- is stored as
 // in the RES form AND coded for the next block's quantizer (p.enc / p.sgn / p.fmt_out, as YC) into p.yc: the 4 tiles of a group are
 // swept as before, their code dwords go through rows_transpose4 and leave as one 16-byte store per lane.
-template <int FMT, int KS, bool XW, bool YC, bool RES = false, bool HALF = false, bool DUAL = false>
+// LUTQ (YC only; slfp_conv2d_fwd_codes_lut): the 4 code bytes of a tile come from the byte table of the layer-output classes
+// (slfp_layerout_lut.hpp) instead of the reader's threshold table.  The table is read from global memory through the vector cache
+// (4.8 KiB, resident in every CU's L1 after the first units): this kernel's LDS holds W up to its capacity and serves a 1 KiB
+// fragment read per MFMA, so the lookups go to the pipe that idles during the epilogue.  (Unmeasured against an LDS copy.)
+template <int FMT, int KS, bool XW, bool YC, bool RES = false, bool HALF = false, bool DUAL = false, bool LUTQ = false>
 __global__ __launch_bounds__(kPwcThreads) void k_pwc_stream(const PwcParams p) {
     static_assert(!XW || KS % 2 == 0, "16-byte code loads cover two k-steps");
     static_assert(!RES || !YC, "residual operand: float32 output only");
     static_assert(!HALF || !XW, "a half-live last k-step is loaded dword by dword");
     static_assert(!DUAL || RES, "the second, code output belongs to the residual forms");
+    static_assert(!LUTQ || (YC && !HALF), "the table epilogue belongs to the code-writing forms");
     __shared__ __attribute__((aligned(16))) uint32_t sdec[256];
-    __shared__ __attribute__((aligned(16))) unsigned char senc[(YC || DUAL) ? kPwTab : 16];
+    __shared__ __attribute__((aligned(16))) unsigned char senc[((YC && !LUTQ) || DUAL) ? kPwTab : 16];
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     _Float16* wl = reinterpret_cast<_Float16*>(smem);
     const int wfrags = p.n_tiles * p.KS;  // 1 KiB each
     dec_fill<FMT, kDecF16D, kPwcThreads>(sdec);
-    if constexpr (YC || DUAL) enc_fill<kPwcThreads>(reinterpret_cast<uint2*>(senc), p.enc);
+    if constexpr ((YC && !LUTQ) || DUAL) enc_fill<kPwcThreads>(reinterpret_cast<uint2*>(senc), p.enc);
+    const lut_gptr lutg = LUTQ ? enc_carried_ptr(p.enc) : nullptr;
     for (int i = threadIdx.x; i < wfrags * 64; i += kPwcThreads)
         reinterpret_cast<half8*>(wl)[i] = reinterpret_cast<const half8*>(p.whi)[i];
     float* ep = reinterpret_cast<float*>(smem + (size_t)wfrags * 1024);   // [256 * bias/s1/s2 | post scale | post shift]
@@ -186,7 +193,8 @@ __global__ __launch_bounds__(kPwcThreads) void k_pwc_stream(const PwcParams p) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const float4 r = tile_out(j0 + j);
-                    if (p.sgn) c[j] = code_sign4(enc4_code<false>(r, r1, lo, hi, senc), r, p.fmt_out);
+                    if constexpr (LUTQ) c[j] = lut4_code(r, lutg);
+                    else if (p.sgn) c[j] = code_sign4(enc4_code<false>(r, r1, lo, hi, senc), r, p.fmt_out);
                     else c[j] = enc4_code_relu(r, r1, lo, hi, senc);
                 }
                 rows_transpose4(c[0], c[1], c[2], c[3]);   // lane-quarter kq now holds channels 16 (j0 + kq) + 0..15
@@ -258,17 +266,20 @@ __global__ __launch_bounds__(kPwcThreads) void k_pwc_stream(const PwcParams p) {
 // DUAL (RES only): as in k_pwc_stream, the codes of the stored value leave per group of 4 tiles.
 constexpr int kSliceThreads = 512;
 constexpr int kSliceDualWaves = 4;   // DUAL: fits the 128 VGPRs too
-template <int FMT, int NTS, bool YC, bool RES = false, bool DUAL = false>
+// LUTQ (YC only): the table epilogue, read from global memory as in k_pwc_stream and for the same reason (the slice's W fills LDS).
+template <int FMT, int NTS, bool YC, bool RES = false, bool DUAL = false, bool LUTQ = false>
 __global__ __launch_bounds__(kSliceThreads, RES ? (DUAL ? kSliceDualWaves : 4) : 1) void k_pwc_slice(const PwcParams p) {   // RES: 4 waves per SIMD = the 128 VGPRs of two workgroups per CU
     static_assert(!RES || !YC, "residual operand: float32 output only");
     static_assert(!DUAL || RES, "the second, code output belongs to the residual forms");
+    static_assert(!LUTQ || YC, "the table epilogue belongs to the code-writing forms");
     constexpr int KC = 8;   // k-steps per chunk = 256 channels = 4 x 16-byte code loads per lane
     constexpr int RP = 2;   // RES: residual pieces in flight under the K sweep
     static_assert(NTS % 4 == 0, "code output leaves in groups of 4 channel tiles");
     __shared__ __attribute__((aligned(16))) uint32_t sdec[256];
-    __shared__ __attribute__((aligned(16))) unsigned char senc[(YC || DUAL) ? kPwTab : 16];
+    __shared__ __attribute__((aligned(16))) unsigned char senc[((YC && !LUTQ) || DUAL) ? kPwTab : 16];
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     _Float16* wl = reinterpret_cast<_Float16*>(smem);
+    const lut_gptr lutg = LUTQ ? enc_carried_ptr(p.enc) : nullptr;
     const int n_slices = p.n_tiles / NTS;
     // blocks b and b + 8 share an XCD: the slices of one pixel range sit on consecutive (b / 8)
     const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
@@ -277,7 +288,7 @@ __global__ __launch_bounds__(kSliceThreads, RES ? (DUAL ? kSliceDualWaves : 4) :
     const int n_ranks = 8 * ((int)(gridDim.x >> 3) / n_slices);
     const int wfrags = NTS * p.KS;  // 1 KiB each
     dec_fill<FMT, kDecF16D, kSliceThreads>(sdec);
-    if constexpr (YC || DUAL) enc_fill<kSliceThreads>(reinterpret_cast<uint2*>(senc), p.enc);
+    if constexpr ((YC && !LUTQ) || DUAL) enc_fill<kSliceThreads>(reinterpret_cast<uint2*>(senc), p.enc);
     {
         const half8* src = reinterpret_cast<const half8*>(p.whi) + (size_t)slice * wfrags * 64;
         for (int i = threadIdx.x; i < wfrags * 64; i += kSliceThreads) reinterpret_cast<half8*>(wl)[i] = src[i];
@@ -383,7 +394,8 @@ __global__ __launch_bounds__(kSliceThreads, RES ? (DUAL ? kSliceDualWaves : 4) :
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const float4 r = finish(j0 + j);
-                    if (p.sgn) c[j] = code_sign4(enc4_code<false>(r, r1, lo, hi, senc), r, p.fmt_out);
+                    if constexpr (LUTQ) c[j] = lut4_code(r, lutg);
+                    else if (p.sgn) c[j] = code_sign4(enc4_code<false>(r, r1, lo, hi, senc), r, p.fmt_out);
                     else c[j] = enc4_code_relu(r, r1, lo, hi, senc);
                 }
                 rows_transpose4(c[0], c[1], c[2], c[3]);
@@ -438,10 +450,13 @@ __global__ __launch_bounds__(kSliceThreads, RES ? (DUAL ? kSliceDualWaves : 4) :
 // tile row's pieces in front of the staging barrier, while the last sweep's MFMAs drain.
 // DUAL (RES only): the residual is added in the staged layout, where a lane holds 4 consecutive channels of one pixel: their 4 codes
 // are one dword, stored by the lane itself -- the 16 lanes of a pixel row write the wave's 64 channels as 64 contiguous bytes.
-template <int FMT, int WM, int WN, int MT, bool YC, bool RES = false, bool DUAL = false>
+// LUTQ (YC only): the table epilogue with the table in LDS, where the reader's threshold table lay (4.8 KiB instead of 2 KiB next to
+// the 16 KiB X tile): W streams through the vector memory pipe here, LDS is idle in the epilogue.  (Unmeasured against global reads.)
+template <int FMT, int WM, int WN, int MT, bool YC, bool RES = false, bool DUAL = false, bool LUTQ = false>
 __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_tiled(const PwcParams p) {
     static_assert(!RES || !YC, "residual operand: float32 output only");
     static_assert(!DUAL || RES, "the second, code output belongs to the residual forms");
+    static_assert(!LUTQ || YC, "the table epilogue belongs to the code-writing forms");
     constexpr int NT = 4;
     constexpr int T = 64 * WM * WN;
     constexpr int BM = WM * MT * 16;
@@ -451,11 +466,12 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_ti
     constexpr int XBYTES = BM * 128;
 
     __shared__ __attribute__((aligned(16))) uint32_t sdec[256];
-    __shared__ __attribute__((aligned(16))) unsigned char senc[(YC || DUAL) ? kPwTab : 16];
+    __shared__ __attribute__((aligned(16))) unsigned char senc[LUTQ ? kLayeroutLutBytes : ((YC || DUAL) ? kPwTab : 16)];
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* xs = smem;  // [2 buffers][BM rows][128 B]
     dec_fill<FMT, kDecF16D, T>(sdec);
-    if constexpr (YC || DUAL) enc_fill<T>(reinterpret_cast<uint2*>(senc), p.enc);
+    if constexpr (LUTQ) layerout_lut_fill<T>(senc, enc_carried_ptr(p.enc));
+    else if constexpr (YC || DUAL) enc_fill<T>(reinterpret_cast<uint2*>(senc), p.enc);
     const unsigned char* dtab = reinterpret_cast<const unsigned char*>(sdec);
 
     const uint32_t b = xcd_remap(blockIdx.x, p.nblocks);
@@ -617,7 +633,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_ti
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
                 const float4 r = out_tile(i, j);
-                if (p.sgn) c[j] = code_sign4(enc4_code<false>(r, r1, lo, hi, senc), r, p.fmt_out);
+                if constexpr (LUTQ) c[j] = lut4_code(r, senc);
+                else if (p.sgn) c[j] = code_sign4(enc4_code<false>(r, r1, lo, hi, senc), r, p.fmt_out);
                 else c[j] = enc4_code_relu(r, r1, lo, hi, senc);
             }
             rows_transpose4(c[0], c[1], c[2], c[3]);   // lane-quarter kq: channels 16 (ntile0 + kq) + 0..15 of pixel row `col`
@@ -693,6 +710,7 @@ struct PwcSel {
     int nts;                 // k_pwc_slice: NTS (4 or 8)
     int wm, wn, mt;          // k_pwc_tiled: tiling
     int grid_cap;            // SLFP_PW_GRID: k_pwc_stream: the most workgroups; k_pwc_slice: the most rank groups (0: no cap)
+    bool lut;                // template argument LUTQ (yc only): set by the caller after pwc_select; the tiling does not depend on it
 };
 
 // slice kernel: K a multiple of 256, the slice's W (NTS tiles x K) <= 128 KiB, N a multiple of 16 * NTS
@@ -734,7 +752,7 @@ static int pwc_select(int K, int N, const ConvPlan& plan, bool y_codes, bool has
 static const char* pwc_sel_name(const PwcSel& s) {
     static thread_local char buf[64];
     const char* fmt = s.fmt == kFmtSfp7 ? "sfp7" : "act8";
-    const char* form = s.yc ? "yc" : (s.dual ? "res/dual" : (s.res ? "res" : "f32"));
+    const char* form = s.yc ? (s.lut ? "yc-lut" : "yc") : (s.dual ? "res/dual" : (s.res ? "res" : "f32"));
     int n;
     if (s.kernel == kPwcStream) n = snprintf(buf, sizeof buf, "pwc-stream/ks%d/%s/%s/%s", s.ks, s.half ? "half" : (s.xw ? "xw" : "dw"), fmt, form);
     else if (s.kernel == kPwcSlice) n = snprintf(buf, sizeof buf, "slice/nts%d/%s/%s", s.nts, fmt, form);
@@ -746,7 +764,10 @@ static const char* pwc_sel_name(const PwcSel& s) {
 template <int FMT, int KS, bool XW, bool HALF = false>
 static int launch_pwc_stream(PwcParams& p, const PwcSel& s, hipStream_t stream, bool dry) {
     const size_t lds = (size_t)p.n_tiles * p.KS * 1024 + (size_t)3 * p.n_tiles * 16 * sizeof(float);
-    auto fn = s.yc ? k_pwc_stream<FMT, KS, XW, true, false, HALF>
+    // the table epilogue: the whole-tile k-step counts the layerout nets' 1x1 layers have (32 / 64 / 128 input channels)
+    constexpr bool LUT_OK = !HALF && (KS == 1 || KS == 2 || KS == 4);
+    if (s.lut && !LUT_OK) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): no table-epilogue instance for %s", pwc_sel_name(s));
+    auto fn = s.yc ? (s.lut ? k_pwc_stream<FMT, KS, XW, true, false, HALF, false, LUT_OK> : k_pwc_stream<FMT, KS, XW, true, false, HALF>)
                    : (s.dual ? k_pwc_stream<FMT, KS, XW, false, true, HALF, true> : (s.res ? k_pwc_stream<FMT, KS, XW, false, true, HALF> : k_pwc_stream<FMT, KS, XW, false, false, HALF>));
     if (dry) return SLFP_OK;   // the instance exists: pwc_variant_name's check, before anything touches a device
     int rc = raise_lds_limit(reinterpret_cast<const void*>(fn), lds);
@@ -772,7 +793,9 @@ static int launch_pwc_tiled(PwcParams& p, const PwcSel& s, hipStream_t stream, b
     if (nblocks > 0x7FFFFFFF) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): grid too large");
     p.nblocks = (uint32_t)nblocks;
     const size_t lds = (size_t)2 * BM * 128 + (s.yc ? 0 : (size_t)(T / 64) * 16 * kStgRow);
-    auto fn = s.yc ? k_pwc_tiled<FMT, WM, WN, MT, true>
+    constexpr bool LUT_OK = WM == 1 && WN == 8 && MT == 4;   // the table epilogue: the deep layers (C_out > 256)
+    if (s.lut && !LUT_OK) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): no table-epilogue instance for %s", pwc_sel_name(s));
+    auto fn = s.yc ? (s.lut ? k_pwc_tiled<FMT, WM, WN, MT, true, false, false, LUT_OK> : k_pwc_tiled<FMT, WM, WN, MT, true>)
                    : (s.dual ? k_pwc_tiled<FMT, WM, WN, MT, false, true, true> : (s.res ? k_pwc_tiled<FMT, WM, WN, MT, false, true> : k_pwc_tiled<FMT, WM, WN, MT, false>));
     if (dry) return SLFP_OK;   // the instance exists: pwc_variant_name's check, before anything touches a device
     int rc = raise_lds_limit(reinterpret_cast<const void*>(fn), lds);
@@ -784,7 +807,9 @@ static int launch_pwc_tiled(PwcParams& p, const PwcSel& s, hipStream_t stream, b
 template <int FMT, int NTS>
 static int launch_pwc_slice(PwcParams& p, const PwcSel& s, hipStream_t stream, bool dry) {
     const size_t lds = (size_t)NTS * p.KS * 1024 + (size_t)3 * NTS * 16 * sizeof(float);
-    auto fn = s.yc ? k_pwc_slice<FMT, NTS, true>
+    constexpr bool LUT_OK = NTS == 8;   // the table epilogue: 256 -> 256 / 512
+    if (s.lut && !LUT_OK) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): no table-epilogue instance for %s", pwc_sel_name(s));
+    auto fn = s.yc ? (s.lut ? k_pwc_slice<FMT, NTS, true, false, false, LUT_OK> : k_pwc_slice<FMT, NTS, true>)
                    : (s.dual ? k_pwc_slice<FMT, NTS, false, true, true> : (s.res ? k_pwc_slice<FMT, NTS, false, true> : k_pwc_slice<FMT, NTS, false>));
     if (dry) return SLFP_OK;   // the instance exists: pwc_variant_name's check, before anything touches a device
     int rc = raise_lds_limit(reinterpret_cast<const void*>(fn), lds);
@@ -857,7 +882,10 @@ int launch_pwc(const slfp_conv2d_desc& d, const ConvPlan& plan, const uint8_t* x
     p.sgn = post.relu ? 0 : 1;
     p.fmt_out = io.y_fmt;
     p.enc.valid = 0;
-    if (y_codes || res_codes) {   // io.y_ka / io.y_fmt: the reader of the codes, in y or (DUAL) next to the float32 y
+    if (io.lut) {
+        if (!y_codes || res || !post.scale) return fail(SLFP_ERR_BAD_ARG, "pointwise (codes): the table epilogue needs code output and post_scale / post_shift");
+        enc_carry_ptr(p.enc, io.lut);
+    } else if (y_codes || res_codes) {   // io.y_ka / io.y_fmt: the reader of the codes, in y or (DUAL) next to the float32 y
         const EncArgs* t = enc_table(io.y_ka, io.y_fmt, kEncCode);
         if (!t->valid) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): no code table for the consumer's scale %g", (double)io.y_ka);
         p.enc = *t;
@@ -865,14 +893,16 @@ int launch_pwc(const slfp_conv2d_desc& d, const ConvPlan& plan, const uint8_t* x
     PwcSel s;
     const int rc = pwc_select(p.K, p.N, plan, y_codes, res != nullptr, res_codes != nullptr, &s);
     if (rc != SLFP_OK) return rc;
+    s.lut = io.lut != nullptr;
     if (s.fmt == kFmtSfp7) return launch_pwc_fmt<kFmtSfp7>(p, s, stream, false);
     return launch_pwc_fmt<kFmtAct8>(p, s, stream, false);
 }
 
-const char* pwc_variant_name(const slfp_conv2d_desc& d, const ConvPlan& plan, bool y_codes, bool has_res, bool has_dual) {
+const char* pwc_variant_name(const slfp_conv2d_desc& d, const ConvPlan& plan, bool y_codes, bool has_res, bool has_dual, bool lut) {
     PwcParams p = {};   // the dry dispatch reads none of the pointers
     PwcSel s;
     if (plan.family != kPointwise || pwc_select((int)d.c_in, (int)d.c_out, plan, y_codes, has_res, has_dual, &s) != SLFP_OK) return "none";
+    s.lut = lut;
     if ((s.fmt == kFmtSfp7 ? launch_pwc_fmt<kFmtSfp7>(p, s, nullptr, true) : launch_pwc_fmt<kFmtAct8>(p, s, nullptr, true)) != SLFP_OK) return "none";
     return pwc_sel_name(s);
 }

@@ -18,6 +18,7 @@
 // Precision: single-pass fp16 (SLFP<3,4>) / exact (SFP<3,3>); the float32-equivalent mode keeps k_stem.
 #include "slfp_device.hpp"
 #include "slfp_codes.hpp"
+#include "slfp_layerout_lut.hpp"
 #include "slfp_host.hpp"
 
 namespace slfp {
@@ -48,13 +49,18 @@ struct StemSmallParams {
     EncArgs enc_out;
 };
 
-template <int FMT, int NT>
+// LUTQ (code output, NT == 4; slfp_conv2d_fwd_codes_lut): the codes come from the byte table of the layer-output classes
+// (slfp_layerout_lut.hpp), copied into the dynamic LDS where the reader's threshold table lies otherwise (4.8 KiB behind a halo
+// tile of at most 4 KiB; the kernel reads nothing else from LDS in its epilogue).  (Unmeasured against global reads.)
+template <int FMT, int NT, bool LUTQ = false>
 __global__ __launch_bounds__(kSsThreads) void k_stem_small(const StemSmallParams p) {
+    static_assert(!LUTQ || NT == 4, "code output: the 64-channel form");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint32_t* sT = reinterpret_cast<uint32_t*>(smem);
     _Float16* tile = reinterpret_cast<_Float16*>(smem + 64);   // [IH][row_h] + one zero slot at the end
     lut_fill<FMT>(sT);
-    if (p.yc) enc_fill<kSsThreads>(reinterpret_cast<uint2*>(smem + p.enc_off), p.enc_out);   // published by the barrier below
+    if constexpr (LUTQ) layerout_lut_fill<kSsThreads>(smem + p.enc_off, enc_carried_ptr(p.enc_out));   // published by the barrier below
+    else if (p.yc) enc_fill<kSsThreads>(reinterpret_cast<uint2*>(smem + p.enc_off), p.enc_out);   // published by the barrier below
 
     uint32_t b = xcd_remap(blockIdx.x, p.nblocks);
     const int tw = b % p.tiles_w; b /= p.tiles_w;
@@ -154,7 +160,8 @@ __global__ __launch_bounds__(kSsThreads) void k_stem_small(const StemSmallParams
                     r.z = ((acc[j][2] + bq.z) * p.s1x) * p.s2;
                     r.w = ((acc[j][3] + bq.w) * p.s1x) * p.s2;
                     r = post_apply_v(r, po, pvv[j]);
-                    if (p.y_sgn) c[j] = code_sign4(enc4_code<false>(r, p.enc_out.r1, p.enc_out.lo, p.enc_out.hi, senc), r, p.y_fmt);
+                    if constexpr (LUTQ) c[j] = lut4_code(r, senc);
+                    else if (p.y_sgn) c[j] = code_sign4(enc4_code<false>(r, p.enc_out.r1, p.enc_out.lo, p.enc_out.hi, senc), r, p.y_fmt);
                     else c[j] = enc4_code_relu(r, p.enc_out.r1, p.enc_out.lo, p.enc_out.hi, senc);
                 }
                 rows_transpose4(c[0], c[1], c[2], c[3]);
@@ -241,6 +248,21 @@ int launch_stem_small_io(const slfp_conv2d_desc& d, const ConvPlan& plan, const 
     p.nblocks = (uint32_t)nblocks;
     size_t lds = 64 + ((size_t)p.IH * p.row_h + 8) * sizeof(_Float16);
     const int nt = stem_small_tiles(d);
+    if (io.lut) {   // the table epilogue: k_stem_small<FMT, 4, true>
+        if (!io.y_codes || !post.scale) return fail(SLFP_ERR_BAD_ARG, "small stem: the table epilogue needs code output and post_scale / post_shift");
+        if (nt != 4 || d.c_out != 64) return fail(SLFP_ERR_UNSUPPORTED, "small stem: no code output for this layer");
+        enc_carry_ptr(p.enc_out, io.lut);
+        p.yc = reinterpret_cast<uint8_t*>(y_any);
+        p.y = nullptr;
+        p.y_sgn = 1;
+        p.y_fmt = io.y_fmt;
+        p.enc_off = (uint32_t)((lds + 15) & ~(size_t)15);
+        lds = p.enc_off + (size_t)kLayeroutLutBytes;
+        if (lds > 64 * 1024) return fail(SLFP_ERR_UNSUPPORTED, "small stem: halo tile needs %zu B of LDS", lds);
+        if (plan.fmt_act == kFmtAct8) hipLaunchKernelGGL((k_stem_small<kFmtAct8, 4, true>), dim3(p.nblocks), dim3(kSsThreads), lds, stream, p);
+        else hipLaunchKernelGGL((k_stem_small<kFmtSfp7, 4, true>), dim3(p.nblocks), dim3(kSsThreads), lds, stream, p);
+        return check_launch("slfp small-K MFMA stem kernel (table epilogue)");
+    }
     if (io.y_codes) {
         const EncArgs* t = enc_table(io.y_ka, io.y_fmt, kEncCode);
         if (!t->valid || nt != 4 || d.c_out != 64) return fail(SLFP_ERR_UNSUPPORTED, "small stem: no code output for this layer");

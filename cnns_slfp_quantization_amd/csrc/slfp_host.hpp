@@ -143,6 +143,8 @@ struct CodeIo {
     float y_ka;
     int y_fmt;        // kFmtAct8 | kFmtSfp7
     int64_t y_ld = 0; // y_codes: channel count of the (wider) NHWC code tensor y is a channel slice of; 0: y is dense (C_out)
+    const uint8_t* lut = nullptr;   // slfp_conv2d_fwd_codes_lut (y_codes, post_scale / post_shift): the byte table of the layer-output
+                                    // classes (slfp_layerout_lut.hpp), device memory, 16-byte aligned; y_ka / y_fmt are then not read
 };
 // Workgroups of `fn` (block size, dynamic LDS) that fit one CU at once (hipOccupancyMaxActiveBlocksPerMultiprocessor, cached
 // per device / function / LDS size): how persistent grids are sized.  >= 1.
@@ -159,7 +161,8 @@ bool pwc_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, int post_flags
 int launch_pwc(const slfp_conv2d_desc& d, const ConvPlan& p, const uint8_t* x, const void* wfrag, const float* bias,
                const PostOp& post, void* y, const CodeIo& io, hipStream_t stream, const float* res = nullptr, void* res_codes = nullptr);
 // the same for launch_pwc (codes in): code or float32 output, residual operand, second (code) output
-const char* pwc_variant_name(const slfp_conv2d_desc& d, const ConvPlan& p, bool y_codes, bool has_res, bool has_dual);
+const char* pwc_variant_name(const slfp_conv2d_desc& d, const ConvPlan& p, bool y_codes, bool has_res, bool has_dual, bool lut = false);
+// lut (y_codes only): the table-epilogue instance of the selected kernel (slfp_conv2d_fwd_codes_lut); "none" where none is built
 // res_codes (with res, float32 y, C_out a multiple of 16; slfp_conv2d_fwd_res_codes): the uint8 tensor that receives, next to y, the codes
 // of y for the reader io.y_ka / io.y_fmt describe
 // the MobileNetV1 image stem with code output (conv_direct.hip)
@@ -189,6 +192,8 @@ int launch_dense_mfma_io(const slfp_conv2d_desc& d, const ConvPlan& p, const voi
 // what launch_dense_mfma_io decides for this layer under the switches read at load, printed from the selection it consumes
 // (slfp_debug_dense_variant; host only).  "none" outside the family; valid until the next call on the same thread.
 const char* dense_variant_name(const slfp_conv2d_desc& d, const ConvPlan& p, bool x_codes);
+// is there a table-epilogue instance (CodeIo::lut) of the kernel launch_dense_mfma_io picks for this layer?  Host only.
+bool dense_lut_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, bool x_codes);
 // codes: `w_oihw` points at 1-byte extended weight codes (slfp_encode_f32 | SLFP_FMT_EXT) instead of float32 weights
 int launch_prepare_weights(const slfp_conv2d_desc& d, const ConvPlan& p, const float* w_oihw, void* wprep,
                            float* weight_q_oihw, hipStream_t stream, bool codes = false);

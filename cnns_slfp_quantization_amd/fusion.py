@@ -25,6 +25,8 @@ undo function restores exactly that state; "also undone by" = the other undo fun
                                    True), fuse_residual               -> CodeReLU
   link_trunk(model, x)             fuse_named_bn, fuse_residual,      conv3: _trunk_code_out, _trunk_link           unlink_trunk / unlink_codes,
                                    link_codes_traced(entries=True)                                                  unfuse_residual
+  link_layerout(model, x)          fuse_bn_relu                       _code_out, _code_lut; pools -> CodeMaxPool2d, unlink_codes
+                                                                      activation modules -> CodeAct
 
 The passes that take an example input share one forward trace (`_Trace`), one rule for "the same tensor" (`_Trace.same`), one
 eligibility predicate (`_code_eligible`), one record of wrapped children (`_wrap_children` / `_unwrap_children`) and one
@@ -339,6 +341,19 @@ class CodeReLU(nn.Module):
         return x if x.dtype == torch.uint8 else self.relu(x)
 
 
+class CodeAct(nn.Module):
+    """An elementwise activation module (Swish, nn.GELU, ...) behind a producer linked by link_layerout: the activation is part of
+    the producer's byte table, so uint8 codes pass through without a launch; anything else goes to the original module, which this
+    wrapper keeps (`act`; the activations have no parameters, the state dict does not change)."""
+
+    def __init__(self, act):
+        super().__init__()
+        self.act = act
+
+    def forward(self, x):
+        return x if x.dtype == torch.uint8 else self.act(x)
+
+
 def _poolable(m):
     return (isinstance(m, nn.MaxPool2d) and not m.ceil_mode and not m.return_indices
             and (m.dilation == 1 or m.dilation == (1, 1)))
@@ -442,16 +457,18 @@ def _code_eligible(m, producer_side=False):
             and (m.bias is None or getattr(m, "_scaled_bias", False)) and not (_post_flags(m) & 2))
 
 
-def _wrap_children(model, pools, q_bit, relus=()):
-    """Replace every child slot of `model` that holds one of `pools` / `relus` by CodeMaxPool2d(pool, q_bit) / CodeReLU(relu).
-    Returns the (parent, name, original) records that _unwrap_children takes."""
+def _wrap_children(model, pools, q_bit, relus=(), acts=()):
+    """Replace every child slot of `model` that holds one of `pools` / `relus` / `acts` by CodeMaxPool2d(pool, q_bit) / CodeReLU(relu) /
+    CodeAct(act).  Returns the (parent, name, original) records that _unwrap_children takes."""
     recs = []
-    for parent in [m for m in model.modules() if not isinstance(m, (CodeMaxPool2d, CodeReLU))]:
+    for parent in [m for m in model.modules() if not isinstance(m, (CodeMaxPool2d, CodeReLU, CodeAct))]:
         for name, child in list(parent._modules.items()):
             if any(child is pm for pm in pools):
                 parent._modules[name] = CodeMaxPool2d(child, q_bit)
             elif any(child is rm for rm in relus):
                 parent._modules[name] = CodeReLU(child)
+            elif any(child is am for am in acts):
+                parent._modules[name] = CodeAct(child)
             else:
                 continue
             recs.append((parent, name, child))
@@ -462,7 +479,8 @@ def _unwrap_children(recs):
     """The inverse of _wrap_children; a slot that no longer holds the wrapper of its original is left alone."""
     for parent, name, orig in recs:
         now = parent._modules.get(name)
-        if isinstance(now, CodeMaxPool2d) and now.pool is orig or isinstance(now, CodeReLU) and now.relu is orig:
+        if (isinstance(now, CodeMaxPool2d) and now.pool is orig or isinstance(now, CodeReLU) and now.relu is orig
+                or isinstance(now, CodeAct) and now.act is orig):
             parent._modules[name] = orig
 
 
@@ -647,7 +665,8 @@ def link_codes_traced(model, example_input, entries=False):
 
 
 def unlink_codes(model):
-    """Undo link_codes / link_codes_traced / link_stem (and, uncounted, every link of link_trunk: its producers read codes)."""
+    """Undo link_codes / link_codes_traced / link_stem / link_layerout (and, uncounted, every link of link_trunk: its producers read
+    codes)."""
     n = 0
     unlink_trunk(model)
     for parent in model.modules():
@@ -656,16 +675,152 @@ def unlink_codes(model):
                 parent._modules[name] = child.pool
             elif isinstance(child, CodeReLU):
                 parent._modules[name] = child.relu
+            elif isinstance(child, CodeAct):
+                parent._modules[name] = child.act
     for m in model.modules():
         if _is_conv_q(m) and m._code_out is not None:
             m._code_out = None
             m._code_entry = False
+            m._code_lut = None   # link_layerout's table
             m.__dict__.pop("_stem_link", None)   # link_stem's record: its pools and ReLUs are unwrapped above
             if hasattr(m, "_pre_link_post"):
                 m._post = m._pre_link_post
                 del m._pre_link_post
             n += 1
     return n
+
+
+# ------------------------------------------------------------------ codes behind the layer-output quantizer: the activation as a table
+def _lut_act(m):
+    """An elementwise activation module link_layerout can put into a producer's table: the stock ones and the reference's mirrors
+    (activation_func.py).  Each is a pure per-element function without state."""
+    from . import activation_func as af
+    return isinstance(m, (nn.ReLU, nn.GELU, nn.SiLU, nn.Sigmoid, af.Swish, af.Sigmoid, af.STL))
+
+
+def _layerout_producer(m):
+    """Can Conv2d_Q `m` be given a table to write codes through: _code_eligible's producer side, WITH the layer-output quantizer
+    (and the BatchNorm it needs) in its epilogue."""
+    if not _is_conv_q(m) or m._code_out is not None or getattr(m, "_in_residual", False):
+        return False
+    return (m.q_bit in (8, 7) and not m.training and isinstance(m.padding, tuple) and (m.bias is None or getattr(m, "_scaled_bias", False))
+            and bool(_post_flags(m) & 2) and m._post[0] is not None)
+
+
+def _layerout_table(a, acts, out, device):
+    """The uint8 table of producer `a` for the reader `out` = (Ka, q_bit): per layer-output class (slfp_layerout_lut_values) the
+    reader's extended code of act_k(... act_1(relu?(value)) ...), computed by the stock modules themselves on `device`.  relu? is
+    the ReLU folded into a's epilogue with the kernels' semantics: fmaxf(NaN, 0) is 0 (torch.relu would keep the NaN)."""
+    from . import _lib
+    from .conv2d_func import _act_fmt
+    from .sfp_quant import hip_encode
+    n = _lib.LAYEROUT_LUT_BYTES
+    vals = np.zeros(n, dtype=np.float32)
+    _lib.check(_lib.load().slfp_layerout_lut_values(vals.ctypes.data, n))
+    with torch.no_grad():
+        v = torch.from_numpy(vals).to(device)
+        if _post_flags(a) & 1:
+            v = torch.where(v > 0, v, torch.zeros_like(v))
+        for act in acts:
+            v = act(v.clone())
+        if not torch.is_tensor(v) or v.shape != (n,) or v.dtype != torch.float32:
+            raise RuntimeError("link_layerout: an activation module did not return an elementwise float32 result")
+        return hip_encode(v.contiguous(), out[0], _act_fmt(out[1]))   # NaN -> 0x00, as everywhere on the code path
+
+
+def link_layerout(model, example_input):
+    """link_codes_traced for the blocks [Conv2d_Q, BatchNorm2d, layerout_quantize_func, ReLU | Swish | GELU] of MobileNetV1_swish /
+    VGG16_gelu (nets_cifar/mobilenetv1.py:196-231, nets_cifar/vgg16.py:186-293), after fuse_bn_relu.  Opt-in.  A producer `a` whose
+    epilogue carries the layer-output quantizer is linked to the one Conv2d_Q `b` that reads its output through nothing but
+    nn.Identity, elementwise activation modules (_lut_act) and nn.MaxPool2d modules behind them: after the quantizer a value is one
+    of a few thousand, so activation and b's quantize_act(. / Ka) become ONE byte table (`a._code_lut`, built by running the modules
+    themselves over every value: bit-identical for any of them) that a's kernel indexes (slfp_conv2d_fwd_codes_lut); the
+    activation modules then pass the codes through (CodeAct), the pools pool codes (CodeMaxPool2d), b decodes.  The float32
+    activation tensor and the activation pass are gone.  Links are made only where `a` has a table kernel for its shape, never
+    for a producer with two consumers, and only where `b` can read codes: as the producer of the next link (its table kernel with
+    code input) or, the last layer of a chain, through its code kernel with float32 output -- for a layer-output epilogue without a
+    folded ReLU that is the code kernel up to the affine and slfp_quantize_layerout_f32 behind it (the same values step for step;
+    the older code entry points keep refusing the layer-output bit, and a ReLU behind the quantizer has no such split).  The
+    whole set is verified bit for bit against the unlinked output on `example_input` and rolled back otherwise (returns 0).
+    Inference only; unlink_codes undoes it.  Returns the number of links."""
+    from .conv2d_func import _supported
+    tr = _Trace(model, example_input)
+    y0 = tr.output
+    order = [c.mod for c in tr.calls if _is_conv_q(c.mod)]
+    if len(order) != len(set(order)):
+        return 0   # a module that runs twice per forward has no single producer / consumer
+
+    def x_of(m):
+        return tr.of(m)[0].x
+
+    cand = {}
+    for b in order:
+        t, acts, pools, seen = x_of(b), [], [], set()
+        if not torch.is_tensor(t) or t.dim() != 4 or t.dtype != torch.float32:
+            continue
+        for _ in range(8):   # back from b: pools first, then the activations (a pool IN FRONT of an activation does not commute with it)
+            fresh = lambda m: m not in seen   # noqa: E731
+            act = tr.producer(t, lambda m: fresh(m) and _lut_act(m))
+            pool = tr.producer(t, lambda m: fresh(m) and _poolable(m)) if not acts else None
+            hit = act if act is not None else pool
+            if hit is None or tr.runs(hit.mod) != 1 or not torch.is_tensor(hit.x):
+                break
+            seen.add(hit.mod)
+            (acts if hit is act else pools).append(hit.mod)
+            t = hit.x
+        a = tr.producer(t, _is_conv_q)
+        a = a.mod if a is not None else None
+        if a is None or a is b or not _layerout_producer(a) or not _code_eligible_reader(b):
+            continue
+        if pools and a.out_channels % 4:
+            continue   # slfp_maxpool2d_codes needs C % 4 == 0
+        cand.setdefault(a, []).append((b, acts[::-1], pools))
+    link_of = {a: cand[a][0] for a in order if a in cand and len(cand[a]) == 1}
+
+    def table_kernel(a, a_in):
+        return x_of(a).dim() == 4 and _supported(a, x_of(a).shape, "lut", a_in, _reader_quant(link_of[a][0]), _post_flags(a))
+
+    def float_out_on_codes(b):   # b with codes in and float32 out
+        fl = _post_flags(b)
+        if x_of(b).dim() != 4:
+            return False
+        if fl & 2:
+            return fl == 2 and _supported(b, x_of(b).shape, "codes_lo", True, None, 0)
+        return _supported(b, x_of(b).shape, "codes", True, None, fl)
+
+    can_read = {}   # can a conv read codes: with float32 out, or as the producer of a link that will be made (decided back to front)
+    for m in reversed(order):
+        can_read[m] = float_out_on_codes(m) or (m in link_of and table_kernel(m, True) and can_read.get(link_of[m][0], False))
+    made, reads_codes, wrapped = [], set(), []
+    for a in order:   # execution order: whether `a` itself reads codes is known when its own link is decided
+        if a not in link_of:
+            continue
+        b, acts, pools = link_of[a]
+        out = _reader_quant(b)
+        if not table_kernel(a, a in reads_codes) or not can_read[b]:
+            continue
+        a._code_lut = _layerout_table(a, acts, out, x_of(a).device)
+        a._code_out = out
+        made.append(a)
+        reads_codes.add(b)
+        wrapped += _wrap_children(model, pools, b.q_bit, acts=acts)
+    if not made:
+        return 0
+    tr.release()
+
+    def undo():
+        for a in made:
+            a._code_out, a._code_lut = None, None
+        _unwrap_children(wrapped)
+
+    return len(made) if _verified(lambda: model(example_input), y0, undo) else 0
+
+
+def _code_eligible_reader(m):
+    """_code_eligible for the consumer of a link_layerout link: its own epilogue may carry the layer-output quantizer (it is then
+    the producer of the next link, or the chain's last layer)."""
+    return (_is_conv_q(m) and m.q_bit in (8, 7) and not m.training and isinstance(m.padding, tuple)
+            and (m.bias is None or getattr(m, "_scaled_bias", False)))
 
 
 # ------------------------------------------------------------------ the image stem writes the first code tensor of the net

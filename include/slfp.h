@@ -293,6 +293,39 @@ int slfp_conv2d_fwd_res_codes(const slfp_conv2d_desc* d, const slfp_conv2d_io* i
                               const float* bias, const float* post_scale, const float* post_shift, int relu,
                               const float* res, float* y, void* y_codes, void* workspace, void* stream);
 
+/* ---- codes behind the layer-output quantizer: the activation as a byte table ------------------------------------------------
+ * The blocks of MobileNetV1_swish / VGG16_gelu are [Conv2d_Q, BatchNorm2d, layerout_quantize_func, ReLU | Swish | GELU]
+ * (nets_cifar/mobilenetv1.py:196-231, nets_cifar/vgg16.py:186-293).  After the layer-output quantizer a float32 has 5 significant
+ * bits and |v| <= 248: slfp_layerout_lut_classes() values in all (NaN, which the quantizer returns for an exact zero, is one of
+ * them).  Whatever lies between that value and the next layer's code -- a ReLU, any elementwise activation module, the reader's
+ * quantize_act(. / Ka) -- is a function of it, so slfp_conv2d_fwd_codes_lut stores, per output element, the byte
+ *     lut[class(layerout(fma(r, post_scale[c], post_shift[c])))]
+ * with r exactly what slfp_conv2d_fwd_post computes, layerout = slfp_quantize_layerout_f32 and class the index documented in
+ * csrc/slfp_layerout_lut.hpp.  The caller builds the table: slfp_layerout_lut_values gives the float32 value of every index
+ * (index 0: NaN; indices from slfp_layerout_lut_classes() on: padding, 0), the caller applies the activation and
+ * slfp_encode_f32(., Ka, fmt | SLFP_FMT_EXT) to them (fusion.link_layerout).  The result is then bit-identical to
+ * slfp_conv2d_fwd_post(relu = SLFP_POST_LAYEROUT) + activation + slfp_encode_f32 for ANY elementwise activation.
+ * lut: device memory, SLFP_LAYEROUT_LUT_BYTES bytes, 16-byte aligned.  io->y_codes must be 1, io->x_codes 0 or 1 as the layer's
+ * family allows on slfp_conv2d_fwd_codes; io->y_ka / y_qbits are validated as there, though the kernel reads only the table.
+ * post_scale / post_shift are required.  y_ld == C_out: a dense code tensor; otherwise a channel slice under the rules of
+ * slfp_conv2d_fwd_codes_slice.  workspace: as slfp_conv2d_fwd_codes_ws.
+ * Supported (slfp_conv2d_codes_lut_supported: 1 / 0, host only): 3x3 depthwise on codes, 1x1 on codes (C_in 32 / 64 / 128 / 256
+ * and, with C_out > 256, the multiples of 64 above), dense 3x3 stride 1 (codes or float32 in) and the two 3x3 RGB stems
+ * (3 -> 32 stride 2, 3 -> 64 stride 1; float32 in) -- the layers of the two nets above.  The residual forms, the entry kernel
+ * and the large-kernel stems have no table form: SLFP_ERR_UNSUPPORTED.  The older entry points keep refusing SLFP_POST_LAYEROUT.
+ * slfp_layerout_lut_index (host): the index of a value of the quantizer, -1 for any other float32.
+ * slfp_debug_layerout_lut_mismatches sweeps ALL 2^32 float32 inputs on the device: *out1 (device memory) = inputs whose
+ * layer-output value differs in bits from the value of its class (all NaNs counted as equal).  Must be 0. */
+#define SLFP_LAYEROUT_LUT_BYTES 4928
+int slfp_layerout_lut_classes(void);
+int slfp_layerout_lut_values(float* out, int n);
+int slfp_layerout_lut_index(float v);
+int slfp_conv2d_codes_lut_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int64_t y_ld);
+int slfp_conv2d_fwd_codes_lut(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
+                              const float* bias, const float* post_scale, const float* post_shift, const uint8_t* lut, void* y,
+                              int64_t y_ld, void* workspace, void* stream);
+int slfp_debug_layerout_lut_mismatches(unsigned long long* out1, void* stream);
+
 /* nn.MaxPool2d (floor mode, dilation 1) on a tensor of activation codes (NHWC, C a multiple of 4; 16-byte aligned): the class
  * of a window's largest input is the highest class among its codes in the order of the classes' pre-images (the clamp literal
  * of Qbits 8 ranks above the top regular code, "tiny" above exact zero, signed codes by decreasing magnitude), so
