@@ -29,12 +29,12 @@
 #include "slfp_codes.hpp"
 #include "slfp_layerout_lut.hpp"
 #include "slfp_host.hpp"
+#include "slfp_epilogue.hpp"
 
 namespace slfp {
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 constexpr int kDnThreads = 512;
 constexpr int kDnTW = 16;  // output columns per tile = one MFMA pixel tile
@@ -168,11 +168,7 @@ __device__ __forceinline__ void dense_epilogue_consts(const DenseParams& p, int 
         k.pv[j].sc = make_float4(1.f, 1.f, 1.f, 1.f);
         k.pv[j].sh = make_float4(0.f, 0.f, 0.f, 0.f);
         if (ch < p.O) {
-            if (p.bias) {
-                const float4 bb = *reinterpret_cast<const float4*>(p.bias + ch);
-                k.bq[j] = make_float4(256.f * ((bb.x / p.s1) / p.s2), 256.f * ((bb.y / p.s1) / p.s2),
-                                      256.f * ((bb.z / p.s1) / p.s2), 256.f * ((bb.w / p.s1) / p.s2));
-            }
+            k.bq[j] = bias_q256(p.bias, ch, p.s1, p.s2);
             k.pv[j] = post_load(p.post, ch);
         }
     }
@@ -196,7 +192,7 @@ __device__ __forceinline__ void dense_epilogue_apply(const DenseParams& p, const
             else enc_fill<kDnThreads>(reinterpret_cast<uint2*>(smem), p.enc_out);
             __syncthreads();
         }
-        const float r1 = p.enc_out.r1, lo = p.enc_out.lo, hi = p.enc_out.hi;
+        const CodeQuant cq{p.enc_out.r1, p.enc_out.lo, p.enc_out.hi, p.y_sgn, p.y_fmt};
         const int chw = (nt0 + wn * 4) * 16;   // this wave's 64 channels
         PostOp po = p.post;
         po.relu = 0;   // the ReLU is folded into the quantizer (enc4_code_relu)
@@ -207,20 +203,12 @@ __device__ __forceinline__ void dense_epilogue_apply(const DenseParams& p, const
             uint32_t c[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                float4 r;
-                r.x = ((acc[i][j][0] + k.bq[j].x) * p.s1x) * p.s2;
-                r.y = ((acc[i][j][1] + k.bq[j].y) * p.s1x) * p.s2;
-                r.z = ((acc[i][j][2] + k.bq[j].z) * p.s1x) * p.s2;
-                r.w = ((acc[i][j][3] + k.bq[j].w) * p.s1x) * p.s2;
-                r = post_apply_v(r, po, k.pv[j]);
-                if constexpr (LUTQ && TAB_READY) c[j] = lut4_code(r, lutg);
-                else if constexpr (LUTQ) c[j] = lut4_code(r, smem);
-                else if (p.y_sgn) c[j] = code_sign4(enc4_code<false>(r, r1, lo, hi, smem), r, p.y_fmt);
-                else c[j] = enc4_code_relu(r, r1, lo, hi, smem);
+                const float4 r = post_apply_v(epilogue(acc[i][j], k.bq[j], p.s1x, p.s2), po, k.pv[j]);
+                if constexpr (LUTQ && TAB_READY) c[j] = code4<true, false>(r, cq, smem, lutg);
+                else c[j] = code4<LUTQ, false>(r, cq, smem, smem);
             }
             rows_transpose4(c[0], c[1], c[2], c[3]);
             if (goh < p.Ho && gow < p.Wo && chs < p.O) {
-                typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
                 *reinterpret_cast<u32x4*>(p.yc + (((size_t)n * p.Ho + goh) * p.Wo + gow) * p.y_ld + chs) = u32x4{c[0], c[1], c[2], c[3]};
             }
         }
@@ -234,11 +222,7 @@ __device__ __forceinline__ void dense_epilogue_apply(const DenseParams& p, const
         for (int i = 0; i < MT; ++i) {
             const int goh = th * TH + wm * MT + i;
             if (goh >= p.Ho || gow >= p.Wo) continue;
-            float4 r;
-            r.x = ((acc[i][j][0] + k.bq[j].x) * p.s1x) * p.s2;
-            r.y = ((acc[i][j][1] + k.bq[j].y) * p.s1x) * p.s2;
-            r.z = ((acc[i][j][2] + k.bq[j].z) * p.s1x) * p.s2;
-            r.w = ((acc[i][j][3] + k.bq[j].w) * p.s1x) * p.s2;
+            const float4 r = epilogue(acc[i][j], k.bq[j], p.s1x, p.s2);
             st_stream4<SLFP_NT_DENSE>(p.y + (((size_t)n * p.Ho + goh) * p.Wo + gow) * p.O + ch, post_apply_v(r, p.post, k.pv[j]));
         }
     }
@@ -712,7 +696,6 @@ __global__ __launch_bounds__(kDnThreads, 2) void k_dense3x3_res(const DenseParam
             const bool live = (xlive >> j) & 1u;
             const uint2 e0 = enc4_f16(xa[j], r1, lo, hi, tabx);
             const uint2 e1 = enc4_f16(xb4[j], r1, lo, hi, tabx);
-            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
             const u32x4 v = live ? u32x4{e0.x, e0.y, e1.x, e1.y} : u32x4{0u, 0u, 0u, 0u};
             if (q < NPIX * 8) *reinterpret_cast<u32x4*>(xsb + (size_t)buf * xbytes + dn_x_off(q >> 3, q & 7)) = v;
         }

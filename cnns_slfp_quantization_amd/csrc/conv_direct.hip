@@ -13,6 +13,7 @@
 #include "slfp_codes.hpp"
 #include "slfp_layerout_lut.hpp"
 #include "slfp_host.hpp"
+#include "slfp_epilogue.hpp"
 
 namespace slfp {
 

@@ -28,13 +28,12 @@
 #include "slfp_device.hpp"
 #include "slfp_enc.hpp"
 #include "slfp_host.hpp"
+#include "slfp_epilogue.hpp"
 
 namespace slfp {
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kFTab = (kEncEntries * 8 + 15) & ~15;
@@ -94,7 +93,7 @@ __global__ __launch_bounds__(kFT, 2) void k_dwpw(const DwPwParams p) {
         *reinterpret_cast<u32x4*>(wl + (size_t)i * 16) = *reinterpret_cast<const u32x4*>(p.wpw + ((size_t)j * p.KSb + ks) * 512 + l * 8);
     }
     for (int i = threadIdx.x; i < NT * 16; i += kFT) {
-        ep[i] = p.bias2 ? 256.f * ((p.bias2[i] / p.s1) / p.s2) : 0.f;
+        ep[i] = p.bias2 ? bias_q256_1(p.bias2[i], p.s1, p.s2) : 0.f;
         ep[NT * 16 + i] = p.sc2 ? p.sc2[i] : 1.f;
         ep[2 * NT * 16 + i] = p.sc2 ? p.sh2[i] : 0.f;
     }
@@ -241,10 +240,9 @@ __global__ __launch_bounds__(kFT, 2) void k_dwpw(const DwPwParams p) {
                     if (p.sc2) {
                         const float4 sc = *reinterpret_cast<const float4*>(ep + NT * 16 + nl);
                         const float4 sh = *reinterpret_cast<const float4*>(ep + 2 * NT * 16 + nl);
-                        r.x = __builtin_fmaf(r.x, sc.x, sh.x); r.y = __builtin_fmaf(r.y, sc.y, sh.y);
-                        r.z = __builtin_fmaf(r.z, sc.z, sh.z); r.w = __builtin_fmaf(r.w, sc.w, sh.w);
+                        r = affine4(r, sc, sh);
                     }
-                    if (p.relu2) { r.x = fmaxf(r.x, 0.f); r.y = fmaxf(r.y, 0.f); r.z = fmaxf(r.z, 0.f); r.w = fmaxf(r.w, 0.f); }
+                    if (p.relu2) r = relu4(r);
                     *reinterpret_cast<float4*>(stg + col * 128 + jj * 64 + kq * 16) = r;
                 }
                 // LDS operations of one wave execute in order: reads see the writes, the next writes follow the reads

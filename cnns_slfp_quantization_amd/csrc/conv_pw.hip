@@ -65,19 +65,16 @@ namespace slfp {
 // two float4 (k = kq*4.., 16 + kq*4..) -> one MFMA B fragment through the threshold table; NaNs not patched
 __device__ __forceinline__ half8 enc_frag(const float4 a, const float4 b, const EncArgs& e, const unsigned char* tb) {
     const uint2 pa = enc4_f16_raw(a, e.r1, e.lo, e.hi, tb), pb = enc4_f16_raw(b, e.r1, e.lo, e.hi, tb);
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     return __builtin_bit_cast(half8, u32x4{pa.x, pa.y, pb.x, pb.y});
 }
 __device__ __forceinline__ half8 enc_frag_nan(const float4 a, const float4 b, const EncArgs& e, const unsigned char* tb) {
     const uint2 pa = enc4_f16(a, e.r1, e.lo, e.hi, tb), pb = enc4_f16(b, e.r1, e.lo, e.hi, tb);
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     return __builtin_bit_cast(half8, u32x4{pa.x, pa.y, pb.x, pb.y});
 }
 
 // the same for the three-pass mode: hi and lo fragments from the two tables (NaN: patched by the caller's cold branch)
 __device__ __forceinline__ void enc_frag_hl(const float4 a, const float4 b, const EncArgs& e, const unsigned char* tb,
                                             const unsigned char* tl, half8& h, half8& l) {
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     uint32_t h0, h1, h2, h3, l0, l1, l2, l3;
     enc2_f16_hl(a.x, a.y, e.r1, e.lo, e.hi, tb, tl, h0, l0);
     enc2_f16_hl(a.z, a.w, e.r1, e.lo, e.hi, tb, tl, h1, l1);
@@ -172,7 +169,7 @@ __global__ __launch_bounds__(kStreamThreads) void k_pw_stream(const PwParams p) 
     if (has_vec) {
         for (int i = threadIdx.x; i < n_pad; i += kStreamThreads) {
             const bool in = i < p.N;
-            ep[i] = (p.bias && in) ? 256.f * ((p.bias[i] / p.s1) / p.s2) : 0.f;
+            ep[i] = (p.bias && in) ? bias_q256_1(p.bias[i], p.s1, p.s2) : 0.f;
             ep[n_pad + i] = (p.post.scale && in) ? p.post.scale[i] : 1.f;
             ep[2 * n_pad + i] = (p.post.scale && in) ? p.post.shift[i] : 0.f;
         }
@@ -277,8 +274,7 @@ __global__ __launch_bounds__(kStreamThreads) void k_pw_stream(const PwParams p) 
                 const float4 sh = *reinterpret_cast<const float4*>(ep + 2 * n_pad + n);
                 r = epilogue(acc, bq, p.s1x, p.s2);
                 if (p.post.scale) {
-                    r.x = __builtin_fmaf(r.x, sc.x, sh.x); r.y = __builtin_fmaf(r.y, sc.y, sh.y);
-                    r.z = __builtin_fmaf(r.z, sc.z, sh.z); r.w = __builtin_fmaf(r.w, sc.w, sh.w);
+                    r = affine4(r, sc, sh);
                     if constexpr (!YC) {   // (no layer-output quantizer in front of a code output: refused on the host)
                         if (p.post.layerout) r = layerout4(r);
                     }
@@ -287,25 +283,22 @@ __global__ __launch_bounds__(kStreamThreads) void k_pw_stream(const PwParams p) 
                 r = epilogue(acc, make_float4(0.f, 0.f, 0.f, 0.f), p.s1x, p.s2);
             }
             if constexpr (!RES && !YC) {   // with a residual the ReLU follows the add (res_add); with code output it is the quantizer's
-                if (p.post.relu) { r.x = fmaxf(r.x, 0.f); r.y = fmaxf(r.y, 0.f); r.z = fmaxf(r.z, 0.f); r.w = fmaxf(r.w, 0.f); }
+                if (p.post.relu) r = relu4(r);
             }
             return r;
         };
         if constexpr (YC) {
             uint8_t* yr = p.yc + (size_t)m * p.N;
-            const float r1 = p.enc_lo.r1, lo = p.enc_lo.lo, hi = p.enc_lo.hi;
+            const CodeQuant cq{p.enc_lo.r1, p.enc_lo.lo, p.enc_lo.hi, p.sgn, p.fmt_out};
             for (int j0 = 0; j0 < p.n_tiles; j0 += 4) {   // n_tiles is a multiple of 4 (the blob is padded to 64 channels)
                 uint32_t c[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const float4 r = tile_out(j0 + j);
-                    if (p.sgn) c[j] = code_sign4(enc4_code<false>(r, r1, lo, hi, stab_lo), r, p.fmt_out);
-                    else c[j] = enc4_code_relu(relu_of_nan4(r), r1, lo, hi, stab_lo);
+                    c[j] = code4<false, true>(r, cq, stab_lo);
                 }
-                rows_transpose4(c[0], c[1], c[2], c[3]);   // lane-quarter kq now holds channels 16 (j0 + kq) + 0..15
-                const int n = (j0 + kq) * 16;
-                typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-                if (live && n < p.N) *reinterpret_cast<u32x4*>(yr + n) = u32x4{c[0], c[1], c[2], c[3]};
+                const int n = (j0 + kq) * 16;   // after the transpose lane-quarter kq holds channels 16 (j0 + kq) + 0..15
+                store_codes16(c, yr + n, live && n < p.N);
             }
         } else if constexpr (STG) {
             // per-unit descriptor: rows beyond M and channels beyond N get an out-of-range offset (store dropped)
@@ -317,10 +310,10 @@ __global__ __launch_bounds__(kStreamThreads) void k_pw_stream(const PwParams p) 
             auto piece = [&](int j0, int h) {
                 return (j0 * 16 + sch * 4) < p.N ? (uint32_t)((spx + 8 * h) * p.N + j0 * 16 + sch * 4) * 4u : 0xFFFFFFF0u;
             };
-            u32x4r rq[2];   // RES: the residual pieces of the NEXT pair, in flight under this pair's MFMAs
+            u32x4 rq[2];   // RES: the residual pieces of the NEXT pair, in flight under this pair's MFMAs
             if constexpr (RES) { rq[0] = res_load_stg(rr, piece(0, 0)); rq[1] = res_load_stg(rr, piece(0, 1)); }
             for (int j0 = 0; j0 < p.n_tiles; j0 += 2) {
-                u32x4r rc[2];
+                u32x4 rc[2];
                 if constexpr (RES) {
                     rc[0] = rq[0]; rc[1] = rq[1];
                     rq[0] = res_load_stg(rr, piece(j0 + 2, 0)); rq[1] = res_load_stg(rr, piece(j0 + 2, 1));   // past the last pair: out of range
@@ -332,7 +325,6 @@ __global__ __launch_bounds__(kStreamThreads) void k_pw_stream(const PwParams p) 
                 const bool ch_ok = (j0 * 16 + sch * 4) < p.N;
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
-                    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
                     u32x4 v = *reinterpret_cast<const u32x4*>(stg + lane * 16 + h * 1024);
                     if constexpr (RES) v = res_add_stg(v, rc[h], p.post.relu);
                     uint32_t so = ch_ok ? (uint32_t)((spx + 8 * h) * p.N + j0 * 16 + sch * 4) * 4u : 0xFFFFFFF0u;
@@ -518,7 +510,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pw_til
 #endif
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
-            typedef uint32_t u32x4w __attribute__((ext_vector_type(4)));
             const uint32_t so = wsoff[j] + (uint32_t)kstep * 1024u;
             wh[j] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rwh, wvoff, so, 0));
             if constexpr (PASSES == 3) wl[j] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rwl, wvoff, so, 0));
@@ -597,7 +588,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pw_til
         return ok ? (uint32_t)(row * p.N + n_st) * 4u : 0xFFFFFFF0u;
     };
     const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(RES ? p.res : p.y) + (size_t)m0 * p.N, 0, ybytes, 0x00020000);
-    u32x4r rq[4];   // RES: four residual pieces in flight (16 registers): piece h of the tile row that is stored next
+    u32x4 rq[4];   // RES: four residual pieces in flight (16 registers): piece h of the tile row that is stored next
     {   // last stage: nothing left to prefetch
         const int t = KT - 1, buf = t & 1;
         load_w(t * 2);
@@ -627,7 +618,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pw_til
     }
     SLFP_STAMP(13);
     if constexpr (YC) {
-        const float r1 = p.enc_lo.r1, lo = p.enc_lo.lo, hi = p.enc_lo.hi;
+        const CodeQuant cq{p.enc_lo.r1, p.enc_lo.lo, p.enc_lo.hi, p.sgn, p.fmt_out};
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
             uint32_t c[NT];
@@ -639,18 +630,13 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pw_til
                 if (p.post.scale) {
                     const float4 sc = *reinterpret_cast<const float4*>(lsc + (in ? n - n_lo : 0));
                     const float4 sh = *reinterpret_cast<const float4*>(lsh + (in ? n - n_lo : 0));
-                    r.x = __builtin_fmaf(r.x, sc.x, sh.x); r.y = __builtin_fmaf(r.y, sc.y, sh.y);
-                    r.z = __builtin_fmaf(r.z, sc.z, sh.z); r.w = __builtin_fmaf(r.w, sc.w, sh.w);
+                    r = affine4(r, sc, sh);
                 }
-                if (p.sgn) c[j] = code_sign4(enc4_code<false>(r, r1, lo, hi, stab_lo), r, p.fmt_out);
-                else c[j] = enc4_code_relu(relu_of_nan4(r), r1, lo, hi, stab_lo);   // the ReLU is the quantizer's
+                c[j] = code4<false, true>(r, cq, stab_lo);   // the ReLU, if any, is the quantizer's
             }
-            rows_transpose4(c[0], c[1], c[2], c[3]);   // lane-quarter kq: channels 16 (ntile0 + kq) + 0..15 of pixel row `col`
             const int row = (wm * MT + i) * 16 + col;
-            const int n = (ntile0 + kq) * 16;
-            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-            if (row < p.rb && m0 + row < p.M && n < p.N)
-                *reinterpret_cast<u32x4*>(p.yc + (size_t)(m0 + row) * p.N + n) = u32x4{c[0], c[1], c[2], c[3]};
+            const int n = (ntile0 + kq) * 16;   // after the transpose lane-quarter kq: channels 16 (ntile0 + kq) + 0..15 of pixel row `col`
+            store_codes16(c, p.yc + (size_t)(m0 + row) * p.N + n, row < p.rb && m0 + row < p.M && n < p.N);
         }
         return;
     }
@@ -667,19 +653,17 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pw_til
                 if (p.post.scale) {
                     const float4 sc = *reinterpret_cast<const float4*>(lsc + (in ? n - n_lo : 0));
                     const float4 sh = *reinterpret_cast<const float4*>(lsh + (in ? n - n_lo : 0));
-                    r.x = __builtin_fmaf(r.x, sc.x, sh.x); r.y = __builtin_fmaf(r.y, sc.y, sh.y);
-                    r.z = __builtin_fmaf(r.z, sc.z, sh.z); r.w = __builtin_fmaf(r.w, sc.w, sh.w);
+                    r = affine4(r, sc, sh);
                     if (p.post.layerout) r = layerout4(r);
                 }
                 if constexpr (!RES) {   // with a residual the ReLU follows the add (res_add_stg)
-                    if (p.post.relu) { r.x = fmaxf(r.x, 0.f); r.y = fmaxf(r.y, 0.f); r.z = fmaxf(r.z, 0.f); r.w = fmaxf(r.w, 0.f); }
+                    if (p.post.relu) r = relu4(r);
                 }
                 *reinterpret_cast<float4*>(stg + col * kStgRow + j * 64 + kq * 16) = r;
             }
             // LDS operations of one wave execute in order: the reads see the writes, the next tile's writes follow the reads
 #pragma unroll
             for (int h = 0; h < 4; ++h) {
-                typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
                 const int row = (wm * MT + i) * 16 + h * 4 + srow;
                 u32x4 v = *reinterpret_cast<const u32x4*>(stg + (h * 4 + srow) * kStgRow + sch * 16);
                 if constexpr (RES) {
@@ -717,11 +701,10 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pw_til
             if (p.post.scale) {
                 const float4 sc = *reinterpret_cast<const float4*>(lsc + (n - n_lo));
                 const float4 sh = *reinterpret_cast<const float4*>(lsh + (n - n_lo));
-                r.x = __builtin_fmaf(r.x, sc.x, sh.x); r.y = __builtin_fmaf(r.y, sc.y, sh.y);
-                r.z = __builtin_fmaf(r.z, sc.z, sh.z); r.w = __builtin_fmaf(r.w, sc.w, sh.w);
+                r = affine4(r, sc, sh);
                 if (p.post.layerout) r = layerout4(r);
             }
-            if (p.post.relu) { r.x = fmaxf(r.x, 0.f); r.y = fmaxf(r.y, 0.f); r.z = fmaxf(r.z, 0.f); r.w = fmaxf(r.w, 0.f); }
+            if (p.post.relu) r = relu4(r);
             st_stream4<SLFP_NT_PW>(p.y + (size_t)m * p.N + n, r);
         }
     }

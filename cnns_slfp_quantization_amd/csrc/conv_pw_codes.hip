@@ -54,8 +54,6 @@ struct PwcParams {
                           // describe its reader as they do for YC; nullptr otherwise
 };
 
-typedef uint32_t u32x4c __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ size_t xc_row_offset(const PwcParams& p, int64_t m) {
     if (p.S == 1) return (size_t)m * p.K;
     const int64_t hw = (int64_t)p.Ho * p.Wo;
@@ -66,7 +64,7 @@ __device__ __forceinline__ size_t xc_row_offset(const PwcParams& p, int64_t m) {
 
 __device__ __forceinline__ half8 dec_frag(uint32_t ca, uint32_t cb, const unsigned char* dtab) {
     const uint2 pa = dec4_f16(ca, dtab), pb = dec4_f16(cb, dtab);
-    return __builtin_bit_cast(half8, u32x4c{pa.x, pa.y, pb.x, pb.y});
+    return __builtin_bit_cast(half8, u32x4{pa.x, pa.y, pb.x, pb.y});
 }
 
 // ======================================================================================
@@ -111,14 +109,14 @@ __global__ __launch_bounds__(kPwcThreads) void k_pwc_stream(const PwcParams p) {
     if (has_vec) {
         for (int i = threadIdx.x; i < n_pad; i += kPwcThreads) {
             const bool in = i < p.N;
-            ep[i] = (p.bias && in) ? 256.f * ((p.bias[i] / p.s1) / p.s2) : 0.f;
+            ep[i] = (p.bias && in) ? bias_q256_1(p.bias[i], p.s1, p.s2) : 0.f;
             ep[n_pad + i] = (p.post.scale && in) ? p.post.scale[i] : 1.f;
             ep[2 * n_pad + i] = (p.post.scale && in) ? p.post.shift[i] : 0.f;
         }
     }
     __syncthreads();
     const unsigned char* dtab = reinterpret_cast<const unsigned char*>(sdec);
-    const float r1 = p.enc.r1, lo = p.enc.lo, hi = p.enc.hi;
+    const CodeQuant cq{p.enc.r1, p.enc.lo, p.enc.hi, p.sgn, p.fmt_out};
 
     const int lane = threadIdx.x & 63;
     const int col = lane & 15, kq = lane >> 4;
@@ -132,9 +130,9 @@ __global__ __launch_bounds__(kPwcThreads) void k_pwc_stream(const PwcParams p) {
         const uint8_t* xr = p.x + xc_row_offset(p, live ? m : p.M - 1);   // rows past the end: clamped, computed, dropped
         uint32_t cw[KS][2];
         if constexpr (XW) {
-            u32x4c v[KS / 2];
+            u32x4 v[KS / 2];
 #pragma unroll
-            for (int c2 = 0; c2 < KS / 2; ++c2) v[c2] = *reinterpret_cast<const u32x4c*>(xr + c2 * 64 + kq * 16);
+            for (int c2 = 0; c2 < KS / 2; ++c2) v[c2] = *reinterpret_cast<const u32x4*>(xr + c2 * 64 + kq * 16);
 #pragma unroll
             for (int c2 = 0; c2 < KS / 2; ++c2) {
                 uint32_t a0 = v[c2][0], a1 = v[c2][1], a2 = v[c2][2], a3 = v[c2][3];
@@ -153,7 +151,7 @@ __global__ __launch_bounds__(kPwcThreads) void k_pwc_stream(const PwcParams p) {
         for (int ks = 0; ks < KS; ++ks) {
             if (HALF && ks + 1 == KS) {
                 const uint2 pa = dec4_f16(cw[ks][0], dtab);
-                xh[ks] = __builtin_bit_cast(half8, u32x4c{pa.x, pa.y, 0u, 0u});
+                xh[ks] = __builtin_bit_cast(half8, u32x4{pa.x, pa.y, 0u, 0u});
             } else {
                 xh[ks] = dec_frag(cw[ks][0], cw[ks][1], dtab);
             }
@@ -174,15 +172,12 @@ __global__ __launch_bounds__(kPwcThreads) void k_pwc_stream(const PwcParams p) {
                 const float4 sc = *reinterpret_cast<const float4*>(ep + n_pad + n);
                 const float4 sh = *reinterpret_cast<const float4*>(ep + 2 * n_pad + n);
                 r = epilogue(acc, bq, p.s1x, p.s2);
-                if (p.post.scale) {
-                    r.x = __builtin_fmaf(r.x, sc.x, sh.x); r.y = __builtin_fmaf(r.y, sc.y, sh.y);
-                    r.z = __builtin_fmaf(r.z, sc.z, sh.z); r.w = __builtin_fmaf(r.w, sc.w, sh.w);
-                }
+                if (p.post.scale) r = affine4(r, sc, sh);
             } else {
                 r = epilogue(acc, make_float4(0.f, 0.f, 0.f, 0.f), p.s1x, p.s2);
             }
             if constexpr (!YC && !RES) {   // with code output the ReLU is the quantizer's (enc4_code_relu); with a residual it follows the add
-                if (p.post.relu) { r.x = fmaxf(r.x, 0.f); r.y = fmaxf(r.y, 0.f); r.z = fmaxf(r.z, 0.f); r.w = fmaxf(r.w, 0.f); }
+                if (p.post.relu) r = relu4(r);
             }
             return r;
         };
@@ -193,13 +188,10 @@ __global__ __launch_bounds__(kPwcThreads) void k_pwc_stream(const PwcParams p) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const float4 r = tile_out(j0 + j);
-                    if constexpr (LUTQ) c[j] = lut4_code(r, lutg);
-                    else if (p.sgn) c[j] = code_sign4(enc4_code<false>(r, r1, lo, hi, senc), r, p.fmt_out);
-                    else c[j] = enc4_code_relu(r, r1, lo, hi, senc);
+                    c[j] = code4<LUTQ, false>(r, cq, senc, lutg);
                 }
-                rows_transpose4(c[0], c[1], c[2], c[3]);   // lane-quarter kq now holds channels 16 (j0 + kq) + 0..15
-                const int n = (j0 + kq) * 16;
-                if (live && n < p.N) *reinterpret_cast<u32x4c*>(yr + n) = u32x4c{c[0], c[1], c[2], c[3]};
+                const int n = (j0 + kq) * 16;   // after the transpose lane-quarter kq holds channels 16 (j0 + kq) + 0..15
+                store_codes16(c, yr + n, live && n < p.N);
             }
         } else {
             float* yr = reinterpret_cast<float*>(p.y) + (size_t)m * p.N + kq * 4;
@@ -220,12 +212,10 @@ __global__ __launch_bounds__(kPwcThreads) void k_pwc_stream(const PwcParams p) {
                         const float4 r = res_add(tile_out(j), rc, p.post.relu);
                         if (live && j * 16 + kq * 4 < p.N) *reinterpret_cast<float4*>(yr + j * 16) = r;
                         // the codes of the value just stored (the ReLU, where there is one, has run: enc4_code_relu sees r >= 0)
-                        if (p.sgn) c[jj] = code_sign4(enc4_code<false>(r, r1, lo, hi, senc), r, p.fmt_out);
-                        else c[jj] = enc4_code_relu(r, r1, lo, hi, senc);
+                        c[jj] = code4<false, false>(r, cq, senc);
                     }
-                    rows_transpose4(c[0], c[1], c[2], c[3]);   // lane-quarter kq now holds channels 16 (j0 + kq) + 0..15
-                    const int n = (j0 + kq) * 16;
-                    if (live && n < p.N) *reinterpret_cast<u32x4c*>(ycr + n) = u32x4c{c[0], c[1], c[2], c[3]};
+                    const int n = (j0 + kq) * 16;   // after the transpose lane-quarter kq holds channels 16 (j0 + kq) + 0..15
+                    store_codes16(c, ycr + n, live && n < p.N);
                 }
             } else {
                 for (int j = 0; j < p.n_tiles; ++j) {
@@ -300,14 +290,14 @@ __global__ __launch_bounds__(kSliceThreads, RES ? (DUAL ? kSliceDualWaves : 4) :
     if (has_vec) {
         for (int i = threadIdx.x; i < NCH; i += kSliceThreads) {
             const bool in = n_lo + i < p.N;
-            ep[i] = (p.bias && in) ? 256.f * ((p.bias[n_lo + i] / p.s1) / p.s2) : 0.f;
+            ep[i] = (p.bias && in) ? bias_q256_1(p.bias[n_lo + i], p.s1, p.s2) : 0.f;
             ep[NCH + i] = (p.post.scale && in) ? p.post.scale[n_lo + i] : 1.f;
             ep[2 * NCH + i] = (p.post.scale && in) ? p.post.shift[n_lo + i] : 0.f;
         }
     }
     __syncthreads();
     const unsigned char* dtab = reinterpret_cast<const unsigned char*>(sdec);
-    const float r1 = p.enc.r1, lo = p.enc.lo, hi = p.enc.hi;
+    const CodeQuant cq{p.enc.r1, p.enc.lo, p.enc.hi, p.sgn, p.fmt_out};
 
     const int lane = threadIdx.x & 63;
     const int col = lane & 15, kq = lane >> 4;
@@ -315,13 +305,13 @@ __global__ __launch_bounds__(kSliceThreads, RES ? (DUAL ? kSliceDualWaves : 4) :
     const int64_t stride = (int64_t)n_ranks * (kSliceThreads / 64);
     const int n_chunks = p.KS / KC;
 
-    u32x4c v[KC / 2];
+    u32x4 v[KC / 2];
     {
         const int64_t g0 = (int64_t)rank * (kSliceThreads / 64) + (threadIdx.x >> 6);
         const int64_t m0 = (g0 < n_groups ? g0 : n_groups - 1) * 16 + col;
         const uint8_t* x0 = p.x + xc_row_offset(p, m0 < p.M ? m0 : p.M - 1) + kq * 16;
 #pragma unroll
-        for (int c2 = 0; c2 < KC / 2; ++c2) v[c2] = *reinterpret_cast<const u32x4c*>(x0 + c2 * 64);
+        for (int c2 = 0; c2 < KC / 2; ++c2) v[c2] = *reinterpret_cast<const u32x4*>(x0 + c2 * 64);
     }
     for (int64_t g = (int64_t)rank * (kSliceThreads / 64) + (threadIdx.x >> 6); g < n_groups; g += stride) {
         const int64_t m = g * 16 + col;
@@ -354,7 +344,7 @@ __global__ __launch_bounds__(kSliceThreads, RES ? (DUAL ? kSliceDualWaves : 4) :
             {   // the next chunk's codes -- after the last chunk: the next unit's first -- fly during this chunk's MFMAs
                 const uint8_t* nx = kc + 1 < n_chunks ? xr + (kc + 1) * (KC * 32) : xrn;
 #pragma unroll
-                for (int c2 = 0; c2 < KC / 2; ++c2) v[c2] = *reinterpret_cast<const u32x4c*>(nx + c2 * 64);
+                for (int c2 = 0; c2 < KC / 2; ++c2) v[c2] = *reinterpret_cast<const u32x4*>(nx + c2 * 64);
             }
             const _Float16* wk = wl + (size_t)(kc * KC) * 512 + lane * 8;
 #pragma unroll
@@ -374,15 +364,12 @@ __global__ __launch_bounds__(kSliceThreads, RES ? (DUAL ? kSliceDualWaves : 4) :
                 const float4 sc = *reinterpret_cast<const float4*>(ep + NCH + n);
                 const float4 sh = *reinterpret_cast<const float4*>(ep + 2 * NCH + n);
                 r = epilogue(acc[j], bq, p.s1x, p.s2);
-                if (p.post.scale) {
-                    r.x = __builtin_fmaf(r.x, sc.x, sh.x); r.y = __builtin_fmaf(r.y, sc.y, sh.y);
-                    r.z = __builtin_fmaf(r.z, sc.z, sh.z); r.w = __builtin_fmaf(r.w, sc.w, sh.w);
-                }
+                if (p.post.scale) r = affine4(r, sc, sh);
             } else {
                 r = epilogue(acc[j], make_float4(0.f, 0.f, 0.f, 0.f), p.s1x, p.s2);
             }
             if constexpr (!YC && !RES) {   // with a residual the ReLU follows the add
-                if (p.post.relu) { r.x = fmaxf(r.x, 0.f); r.y = fmaxf(r.y, 0.f); r.z = fmaxf(r.z, 0.f); r.w = fmaxf(r.w, 0.f); }
+                if (p.post.relu) r = relu4(r);
             }
             return r;
         };
@@ -394,13 +381,10 @@ __global__ __launch_bounds__(kSliceThreads, RES ? (DUAL ? kSliceDualWaves : 4) :
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const float4 r = finish(j0 + j);
-                    if constexpr (LUTQ) c[j] = lut4_code(r, lutg);
-                    else if (p.sgn) c[j] = code_sign4(enc4_code<false>(r, r1, lo, hi, senc), r, p.fmt_out);
-                    else c[j] = enc4_code_relu(r, r1, lo, hi, senc);
+                    c[j] = code4<LUTQ, false>(r, cq, senc, lutg);
                 }
-                rows_transpose4(c[0], c[1], c[2], c[3]);
                 const int n = (j0 + kq) * 16;
-                if (live && n_lo + n < p.N) *reinterpret_cast<u32x4c*>(yr + n) = u32x4c{c[0], c[1], c[2], c[3]};
+                store_codes16(c, yr + n, live && n_lo + n < p.N);
             }
         } else {
             float* yr = reinterpret_cast<float*>(p.y) + (size_t)m * p.N + n_lo + kq * 4;
@@ -419,12 +403,10 @@ __global__ __launch_bounds__(kSliceThreads, RES ? (DUAL ? kSliceDualWaves : 4) :
                         const float4 r = res_add(finish(j), rq[j], p.post.relu);
                         if (j + 2 * RP < NTS) rq[j + 2 * RP] = res_at(j + 2 * RP);
                         if (live && n_lo + j * 16 + kq * 4 < p.N) *reinterpret_cast<float4*>(yr + j * 16) = r;
-                        if (p.sgn) c[jj] = code_sign4(enc4_code<false>(r, r1, lo, hi, senc), r, p.fmt_out);
-                        else c[jj] = enc4_code_relu(r, r1, lo, hi, senc);
+                        c[jj] = code4<false, false>(r, cq, senc);
                     }
-                    rows_transpose4(c[0], c[1], c[2], c[3]);
                     const int n = (j0 + kq) * 16;
-                    if (live && n_lo + n < p.N) *reinterpret_cast<u32x4c*>(ycr + n) = u32x4c{c[0], c[1], c[2], c[3]};
+                    store_codes16(c, ycr + n, live && n_lo + n < p.N);
                 }
             } else {
 #pragma unroll
@@ -537,8 +519,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_ti
     auto load_w = [&](int kstep, int b) {
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
-            typedef uint32_t u32x4w __attribute__((ext_vector_type(4)));
-            const u32x4w v = __builtin_amdgcn_raw_buffer_load_b128(rw, wvoff, wsoff[j] + (uint32_t)kstep * 1024u, 0);
+            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rw, wvoff, wsoff[j] + (uint32_t)kstep * 1024u, 0);
             whb[b][j] = __builtin_bit_cast(half8, v);
         }
     };
@@ -581,7 +562,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_ti
         return ok ? (uint32_t)(row * p.N + n_st) * 4u : 0xFFFFFFF0u;
     };
     const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(RES ? p.res : reinterpret_cast<const float*>(p.y)) + (size_t)m0 * p.N, 0, ybytes, 0x00020000);
-    u32x4r rq[4];   // RES: four residual pieces in flight (16 registers): piece h of the tile row that is stored next
+    u32x4 rq[4];   // RES: four residual pieces in flight (16 registers): piece h of the tile row that is stored next
     {
         const int t = KT - 1, buf = t & 1;
         load_w(t * 2 + 1, 1);
@@ -610,22 +591,19 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_ti
     auto out_tile = [&](int i, int j) {
         const int n = (ntile0 + j) * 16 + kq * 4;
         const bool in = n < p.N;
-        float4 r = epilogue(acc[i][j], (in && p.bias) ? make_float4(256.f * ((p.bias[n] / p.s1) / p.s2), 256.f * ((p.bias[n + 1] / p.s1) / p.s2),
-                                                                     256.f * ((p.bias[n + 2] / p.s1) / p.s2), 256.f * ((p.bias[n + 3] / p.s1) / p.s2))
-                                                      : make_float4(0.f, 0.f, 0.f, 0.f), p.s1x, p.s2);
+        float4 r = epilogue(acc[i][j], bias_q256(in ? p.bias : nullptr, n, p.s1, p.s2), p.s1x, p.s2);
         if (p.post.scale) {
             const float4 sc = *reinterpret_cast<const float4*>(lsc + (in ? n - n_lo : 0));
             const float4 sh = *reinterpret_cast<const float4*>(lsh + (in ? n - n_lo : 0));
-            r.x = __builtin_fmaf(r.x, sc.x, sh.x); r.y = __builtin_fmaf(r.y, sc.y, sh.y);
-            r.z = __builtin_fmaf(r.z, sc.z, sh.z); r.w = __builtin_fmaf(r.w, sc.w, sh.w);
+            r = affine4(r, sc, sh);
         }
         if constexpr (!YC && !RES) {   // with a residual the ReLU follows the add
-            if (p.post.relu) { r.x = fmaxf(r.x, 0.f); r.y = fmaxf(r.y, 0.f); r.z = fmaxf(r.z, 0.f); r.w = fmaxf(r.w, 0.f); }
+            if (p.post.relu) r = relu4(r);
         }
         return r;
     };
     if constexpr (YC) {
-        const float r1 = p.enc.r1, lo = p.enc.lo, hi = p.enc.hi;
+        const CodeQuant cq{p.enc.r1, p.enc.lo, p.enc.hi, p.sgn, p.fmt_out};
         uint8_t* yb = reinterpret_cast<uint8_t*>(p.y);
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
@@ -633,15 +611,11 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_ti
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
                 const float4 r = out_tile(i, j);
-                if constexpr (LUTQ) c[j] = lut4_code(r, senc);
-                else if (p.sgn) c[j] = code_sign4(enc4_code<false>(r, r1, lo, hi, senc), r, p.fmt_out);
-                else c[j] = enc4_code_relu(r, r1, lo, hi, senc);
+                c[j] = code4<LUTQ, false>(r, cq, senc, senc);
             }
-            rows_transpose4(c[0], c[1], c[2], c[3]);   // lane-quarter kq: channels 16 (ntile0 + kq) + 0..15 of pixel row `col`
             const int row = (wm * MT + i) * 16 + col;
-            const int n = (ntile0 + kq) * 16;
-            if (row < p.rb && m0 + row < p.M && n < p.N)
-                *reinterpret_cast<u32x4c*>(yb + (size_t)(m0 + row) * p.y_ld + n) = u32x4c{c[0], c[1], c[2], c[3]};
+            const int n = (ntile0 + kq) * 16;   // after the transpose lane-quarter kq: channels 16 (ntile0 + kq) + 0..15 of pixel row `col`
+            store_codes16(c, yb + (size_t)(m0 + row) * p.y_ld + n, row < p.rb && m0 + row < p.M && n < p.N);
         }
     } else {
         // float32 out: staged through a per-wave LDS area into 256-byte runs (4 rows x the wave's 64 channels per store)
@@ -651,7 +625,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_ti
         const uint64_t cleft = (uint64_t)(p.M - m0 < BM ? p.M - m0 : BM) * p.N;
         const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc((DUAL ? p.yc : reinterpret_cast<uint8_t*>(p.y)) + (size_t)m0 * p.N, 0,
                                                                             (uint32_t)cleft, 0x00020000);
-        const float r1 = p.enc.r1, lo = p.enc.lo, hi = p.enc.hi;
+        const CodeQuant cq{p.enc.r1, p.enc.lo, p.enc.hi, p.sgn, p.fmt_out};
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
 #pragma unroll
@@ -659,7 +633,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_ti
 #pragma unroll
             for (int h = 0; h < 4; ++h) {
                 const int row = (wm * MT + i) * 16 + h * 4 + srow;
-                u32x4c v = *reinterpret_cast<const u32x4c*>(stg + (h * 4 + srow) * kStgRow + sch * 16);
+                u32x4 v = *reinterpret_cast<const u32x4*>(stg + (h * 4 + srow) * kStgRow + sch * 16);
                 if constexpr (RES) {
                     v = res_add_stg(v, rq[h], p.post.relu);
                     if (i + 1 < MT) rq[h] = res_load_stg(rr, piece(i + 1, h));   // the next tile row's piece takes the register over
@@ -670,9 +644,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_ti
                 __builtin_amdgcn_raw_buffer_store_b128(v, ry, so, 0, 0);
                 if constexpr (DUAL) {
                     const float4 f = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
-                    uint32_t c;
-                    if (p.sgn) c = code_sign4(enc4_code<false>(f, r1, lo, hi, senc), f, p.fmt_out);
-                    else c = enc4_code_relu(f, r1, lo, hi, senc);
+                    const uint32_t c = code4<false, false>(f, cq, senc);
                     uint32_t co = ok ? (uint32_t)(row * p.N + n_st) : 0xFFFFFFF0u;   // out of range: dropped
                     asm volatile("" : "+v"(co));
                     __builtin_amdgcn_raw_buffer_store_b32(c, rc, co, 0, 0);

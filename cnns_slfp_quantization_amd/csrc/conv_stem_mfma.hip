@@ -20,11 +20,11 @@
 #include "slfp_device.hpp"
 #include "slfp_codes.hpp"
 #include "slfp_host.hpp"
+#include "slfp_epilogue.hpp"
 
 namespace slfp {
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 constexpr int kSmThreads = 512;
 
@@ -46,29 +46,18 @@ __device__ __forceinline__ void stem_store_codes(const floatx4 (&acc)[NT], const
                                                  const unsigned char* __restrict__ senc, uint8_t* __restrict__ yp, const int O,
                                                  const int kq, const bool live) {
     po.relu = 0;   // folded into the quantizer
-    const float r1 = co.enc_out.r1, lo = co.enc_out.lo, hi = co.enc_out.hi;
+    const CodeQuant cq{co.enc_out.r1, co.enc_out.lo, co.enc_out.hi, co.y_sgn, co.y_fmt};
 #pragma unroll
     for (int g = 0; g < NT; g += 4) {
         uint32_t c[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             if (g + i >= NT) continue;
-            const float4 bq = bqv[g + i];
-            float4 r;
-            r.x = ((acc[g + i][0] + bq.x) * s1x) * s2;
-            r.y = ((acc[g + i][1] + bq.y) * s1x) * s2;
-            r.z = ((acc[g + i][2] + bq.z) * s1x) * s2;
-            r.w = ((acc[g + i][3] + bq.w) * s1x) * s2;
-            r = post_apply_v(r, po, pvv[g + i]);
-            if (co.y_sgn) c[i] = code_sign4(enc4_code<false>(r, r1, lo, hi, senc), r, co.y_fmt);
-            else c[i] = enc4_code_relu(relu_of_nan4(r), r1, lo, hi, senc);
+            const float4 r = post_apply_v(epilogue(acc[g + i], bqv[g + i], s1x, s2), po, pvv[g + i]);
+            c[i] = code4<false, true>(r, cq, senc);
         }
-        rows_transpose4(c[0], c[1], c[2], c[3]);
         const int ch = (g + kq) * 16;
-        if (live && g + kq < NT && ch < O) {
-            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-            *reinterpret_cast<u32x4*>(yp + ch) = u32x4{c[0], c[1], c[2], c[3]};
-        }
+        store_codes16(c, yp + ch, live && g + kq < NT && ch < O);
     }
 }
 
@@ -155,11 +144,7 @@ __global__ __launch_bounds__(kSmThreads, 2) void k_stem_mfma(const StemMfmaParam
         bqv[j] = make_float4(0.f, 0.f, 0.f, 0.f);
         pvv[j] = PostVec{make_float4(1.f, 1.f, 1.f, 1.f), make_float4(0.f, 0.f, 0.f, 0.f)};
         if (ch < p.O) {
-            if (p.bias) {
-                const float4 bb = *reinterpret_cast<const float4*>(p.bias + ch);
-                bqv[j] = make_float4(256.f * ((bb.x / p.s1) / p.s2), 256.f * ((bb.y / p.s1) / p.s2),
-                                     256.f * ((bb.z / p.s1) / p.s2), 256.f * ((bb.w / p.s1) / p.s2));
-            }
+            bqv[j] = bias_q256(p.bias, ch, p.s1, p.s2);
             pvv[j] = post_load(p.post, ch);
         }
     }
@@ -207,12 +192,7 @@ __global__ __launch_bounds__(kSmThreads, 2) void k_stem_mfma(const StemMfmaParam
             for (int j = 0; j < NT; ++j) {
                 const int ch = j * 16 + kq * 4;
                 if (ch >= p.O) continue;
-                const float4 bq = bqv[j];
-                float4 r;
-                r.x = ((acc[j][0] + bq.x) * p.s1x) * p.s2;
-                r.y = ((acc[j][1] + bq.y) * p.s1x) * p.s2;
-                r.z = ((acc[j][2] + bq.z) * p.s1x) * p.s2;
-                r.w = ((acc[j][3] + bq.w) * p.s1x) * p.s2;
+                const float4 r = epilogue(acc[j], bqv[j], p.s1x, p.s2);
                 st_stream4<SLFP_NT_STEM_MFMA>(yp + ch, post_apply_v(r, p.post, pvv[j]));
             }
         }
@@ -303,11 +283,7 @@ __global__ __launch_bounds__(kSrThreads) void k_stem_rows(const StemRowsParams p
         bqv[j] = make_float4(0.f, 0.f, 0.f, 0.f);
         pvv[j] = PostVec{make_float4(1.f, 1.f, 1.f, 1.f), make_float4(0.f, 0.f, 0.f, 0.f)};
         if (ch < p.O) {
-            if (p.bias) {
-                const float4 bb = *reinterpret_cast<const float4*>(p.bias + ch);
-                bqv[j] = make_float4(256.f * ((bb.x / p.s1) / p.s2), 256.f * ((bb.y / p.s1) / p.s2),
-                                     256.f * ((bb.z / p.s1) / p.s2), 256.f * ((bb.w / p.s1) / p.s2));
-            }
+            bqv[j] = bias_q256(p.bias, ch, p.s1, p.s2);
             pvv[j] = post_load(p.post, ch);
         }
     }
@@ -333,8 +309,7 @@ __global__ __launch_bounds__(kSrThreads) void k_stem_rows(const StemRowsParams p
         for (int kh = 0; kh < p.KH; ++kh) {
             for (int sub = 0; sub < p.ksub; ++sub) {
                 const uint32_t* src = origin + ((kh * p.row_h + sub * 32) >> 1);
-                typedef uint32_t u32x4r __attribute__((ext_vector_type(4)));
-                const half8 xf = __builtin_bit_cast(half8, u32x4r{src[0] & rmask[sub][0], src[1] & rmask[sub][1],
+                const half8 xf = __builtin_bit_cast(half8, u32x4{src[0] & rmask[sub][0], src[1] & rmask[sub][1],
                                                                   src[2] & rmask[sub][2], src[3] & rmask[sub][3]});
                 const unsigned char* wt = wl + (size_t)((kh * p.ksub + sub) * NT) * 1024;
 #pragma unroll
@@ -354,12 +329,7 @@ __global__ __launch_bounds__(kSrThreads) void k_stem_rows(const StemRowsParams p
             for (int j = 0; j < NT; ++j) {
                 const int ch = j * 16 + kq * 4;
                 if (ch >= p.O) continue;
-                const float4 bq = bqv[j];
-                float4 r;
-                r.x = ((acc[j][0] + bq.x) * p.s1x) * p.s2;
-                r.y = ((acc[j][1] + bq.y) * p.s1x) * p.s2;
-                r.z = ((acc[j][2] + bq.z) * p.s1x) * p.s2;
-                r.w = ((acc[j][3] + bq.w) * p.s1x) * p.s2;
+                const float4 r = epilogue(acc[j], bqv[j], p.s1x, p.s2);
                 st_stream4<SLFP_NT_STEM_MFMA>(yp + ch, post_apply_v(r, p.post, pvv[j]));
             }
         }

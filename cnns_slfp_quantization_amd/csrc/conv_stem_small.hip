@@ -20,11 +20,11 @@
 #include "slfp_codes.hpp"
 #include "slfp_layerout_lut.hpp"
 #include "slfp_host.hpp"
+#include "slfp_epilogue.hpp"
 
 namespace slfp {
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 constexpr int kSsThreads = 256;
 constexpr int kSsTH = 8, kSsTW = 32;   // output tile
@@ -125,11 +125,7 @@ __global__ __launch_bounds__(kSsThreads) void k_stem_small(const StemSmallParams
         bqv[j] = make_float4(0.f, 0.f, 0.f, 0.f);
         pvv[j] = PostVec{make_float4(1.f, 1.f, 1.f, 1.f), make_float4(0.f, 0.f, 0.f, 0.f)};
         if (ch < p.O) {
-            if (p.bias) {
-                const float4 bb = *reinterpret_cast<const float4*>(p.bias + ch);
-                bqv[j] = make_float4(256.f * ((bb.x / p.s1) / p.s2), 256.f * ((bb.y / p.s1) / p.s2),
-                                     256.f * ((bb.z / p.s1) / p.s2), 256.f * ((bb.w / p.s1) / p.s2));
-            }
+            bqv[j] = bias_q256(p.bias, ch, p.s1, p.s2);
             pvv[j] = post_load(p.post, ch);
         }
     }
@@ -153,22 +149,12 @@ __global__ __launch_bounds__(kSsThreads) void k_stem_small(const StemSmallParams
                 uint32_t c[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const float4 bq = bqv[j];
-                    float4 r;
-                    r.x = ((acc[j][0] + bq.x) * p.s1x) * p.s2;
-                    r.y = ((acc[j][1] + bq.y) * p.s1x) * p.s2;
-                    r.z = ((acc[j][2] + bq.z) * p.s1x) * p.s2;
-                    r.w = ((acc[j][3] + bq.w) * p.s1x) * p.s2;
-                    r = post_apply_v(r, po, pvv[j]);
+                    const float4 r = post_apply_v(epilogue(acc[j], bqv[j], p.s1x, p.s2), po, pvv[j]);
                     if constexpr (LUTQ) c[j] = lut4_code(r, senc);
                     else if (p.y_sgn) c[j] = code_sign4(enc4_code<false>(r, p.enc_out.r1, p.enc_out.lo, p.enc_out.hi, senc), r, p.y_fmt);
                     else c[j] = enc4_code_relu(r, p.enc_out.r1, p.enc_out.lo, p.enc_out.hi, senc);
                 }
-                rows_transpose4(c[0], c[1], c[2], c[3]);
-                if (goh < p.Ho && gow < p.Wo && kq * 16 < p.O) {
-                    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-                    *reinterpret_cast<u32x4*>(p.yc + (((size_t)n * p.Ho + goh) * p.Wo + gow) * p.O + kq * 16) = u32x4{c[0], c[1], c[2], c[3]};
-                }
+                store_codes16(c, p.yc + (((size_t)n * p.Ho + goh) * p.Wo + gow) * p.O + kq * 16, goh < p.Ho && gow < p.Wo && kq * 16 < p.O);
                 continue;
             }
         }
@@ -178,12 +164,7 @@ __global__ __launch_bounds__(kSsThreads) void k_stem_small(const StemSmallParams
             for (int j = 0; j < NT; ++j) {
                 const int ch = j * 16 + kq * 4;
                 if (ch >= p.O) continue;
-                const float4 bq = bqv[j];
-                float4 r;
-                r.x = ((acc[j][0] + bq.x) * p.s1x) * p.s2;
-                r.y = ((acc[j][1] + bq.y) * p.s1x) * p.s2;
-                r.z = ((acc[j][2] + bq.z) * p.s1x) * p.s2;
-                r.w = ((acc[j][3] + bq.w) * p.s1x) * p.s2;
+                const float4 r = epilogue(acc[j], bqv[j], p.s1x, p.s2);
                 st_stream4<SLFP_NT_STEM_MFMA>(yp + ch, post_apply_v(r, p.post, pvv[j]));
             }
         }

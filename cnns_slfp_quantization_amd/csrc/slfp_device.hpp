@@ -287,53 +287,7 @@ __device__ __forceinline__ float4 layerout4(float4 r) {
     return make_float4(layerout1(r.x), layerout1(r.y), layerout1(r.z), layerout1(r.w));
 }
 
-__device__ __forceinline__ float4 post_apply(float4 r, const PostOp po, int c) {
-    if (po.scale) {
-        const float4 sc = *reinterpret_cast<const float4*>(po.scale + c);
-        const float4 sh = *reinterpret_cast<const float4*>(po.shift + c);
-        r.x = __builtin_fmaf(r.x, sc.x, sh.x); r.y = __builtin_fmaf(r.y, sc.y, sh.y);
-        r.z = __builtin_fmaf(r.z, sc.z, sh.z); r.w = __builtin_fmaf(r.w, sc.w, sh.w);
-    }
-    if (po.relu) { r.x = fmaxf(r.x, 0.f); r.y = fmaxf(r.y, 0.f); r.z = fmaxf(r.z, 0.f); r.w = fmaxf(r.w, 0.f); }
-    return r;
-}
-
-// The same split in two, so that kernels whose lanes keep their channels for many outputs load the
-// per-channel vectors ONCE: fetched inside the store loop, the two loads sit on the critical path of
-// every store (measured: +12-38 % on the pointwise kernels, +5-8 % on depthwise, bench.py --post).
-struct PostVec {
-    float4 sc, sh;
-};
-
-__device__ __forceinline__ PostVec post_load(const PostOp po, int c) {
-    PostVec v;
-    v.sc = make_float4(1.f, 1.f, 1.f, 1.f);
-    v.sh = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (po.scale) {
-        v.sc = *reinterpret_cast<const float4*>(po.scale + c);
-        v.sh = *reinterpret_cast<const float4*>(po.shift + c);
-    }
-    return v;
-}
-
-__device__ __forceinline__ float4 post_apply_v(float4 r, const PostOp po, const PostVec& v) {
-    if (po.scale) {
-        r.x = __builtin_fmaf(r.x, v.sc.x, v.sh.x); r.y = __builtin_fmaf(r.y, v.sc.y, v.sh.y);
-        r.z = __builtin_fmaf(r.z, v.sc.z, v.sh.z); r.w = __builtin_fmaf(r.w, v.sc.w, v.sh.w);
-        if (po.layerout) r = layerout4(r);
-    }
-    if (po.relu) { r.x = fmaxf(r.x, 0.f); r.y = fmaxf(r.y, 0.f); r.z = fmaxf(r.z, 0.f); r.w = fmaxf(r.w, 0.f); }
-    return r;
-}
-
-__device__ __forceinline__ float post_apply1(float r, const PostOp po, int c) {
-    if (po.scale) {
-        r = __builtin_fmaf(r, po.scale[c], po.shift[c]);
-        if (po.layerout) r = layerout1(r);
-    }
-    if (po.relu) r = fmaxf(r, 0.f);
-    return r;
-}
+// post_apply / post_apply_v / post_apply1, the PostOp forms of affine -> layerout -> ReLU: slfp_epilogue.hpp
 
 // 2^ESH * Q_FMT(x / Ka) as float32, where s divides by Ka / 2^ESH.
 template <int FMT, int ESH = 0>
