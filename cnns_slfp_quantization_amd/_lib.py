@@ -37,6 +37,7 @@ SYMBOLS = (
     "slfp_conv2d_res_codes_supported", "slfp_conv2d_fwd_res_codes",
     "slfp_layerout_lut_classes", "slfp_layerout_lut_values", "slfp_layerout_lut_index", "slfp_conv2d_codes_lut_supported",
     "slfp_conv2d_fwd_codes_lut", "slfp_debug_layerout_lut_mismatches",
+    "slfp_dwpw_codes_supported", "slfp_dwpw_fwd_codes",
 )
 
 
@@ -154,6 +155,8 @@ def load():
         "slfp_conv2d_codes_lut_supported": (ci, [dp, ctypes.POINTER(ConvIo), ci, i64]),
         "slfp_conv2d_fwd_codes_lut": (ci, [dp, ctypes.POINTER(ConvIo), vp, vp, vp, vp, vp, vp, vp, i64, vp, vp]),
         "slfp_debug_layerout_lut_mismatches": (ci, [vp, vp]),
+        "slfp_dwpw_codes_supported": (ci, [dp, dp, ctypes.POINTER(ConvIo), ci, ci, ci]),
+        "slfp_dwpw_fwd_codes": (ci, [dp, dp, ctypes.POINTER(ConvIo), vp, vp, vp, vp, ci, vp, vp, vp, vp, ci, vp, vp]),
     }
     assert set(sigs) == set(SYMBOLS)
     for name, (res, args) in sigs.items():

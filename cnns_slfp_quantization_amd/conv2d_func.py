@@ -64,6 +64,8 @@ class _Options:
     dwpw_all = False                 # True: fusion.DwPwBlock uses the one-kernel form wherever the library supports it,
                                      # not only where it measured faster than two kernels
     dwpw_pairs = {(32, 1)}           # (depthwise channels, stride) pairs that run as one kernel by default
+    dwpw_codes_pairs = set()         # the same for a linked pair on 1-byte codes (slfp_dwpw_fwd_codes): none by default, see the
+                                     # measurements of profiles/dwpw_codes_bench.py; dwpw_all forces every supported pair here too
     backward = "composite"           # "composite": the reference's STE composite; "hip": slfp_conv2d_bwd where it covers the layer
                                      # (3x3 depthwise, stride-1 1x1, Linear_Q); "hip_all": also the dense family (SLFP_BWD_DENSE)
 

@@ -10,8 +10,10 @@ undo function restores exactly that state; "also undone by" = the other undo fun
                                                                       of an nn.Sequential -> nn.Identity
   fuse_named_bn(model, x)          --                                 _post, _named_bn; the bn<k> slot of a hand-   unfuse_named_bn
                                                                       wired block -> nn.Identity
-  fuse_dw_pw(model)                fuse_bn_relu                       DwPwBlock (._dw_slot) in the pointwise slot,  unfuse_dw_pw / unfuse
-                                                                      nn.Identity in the depthwise slot
+  fuse_dw_pw(model)                fuse_bn_relu; link_codes first     DwPwBlock (._dw_slot) in the pointwise slot,  unfuse_dw_pw / unfuse
+                                   where the blocks are to run on     nn.Identity in the depthwise slot
+                                   codes (fuse_bn_relu -> link_codes
+                                   -> fuse_dw_pw)
   link_codes(model, x)             fuse_bn_relu                       _code_out; pools -> CodeMaxPool2d             unlink_codes
   fuse_residual(model, x)          fuse_named_bn                      block: instance forward, _residual_fused;     unfuse_residual
                                                                       conv3: residual_relu, _in_residual
@@ -203,7 +205,12 @@ def unfuse_named_bn(model):
 class DwPwBlock(nn.Module):
     """[Conv2d_Q 3x3 depthwise, BN, ReLU, Conv2d_Q 1x1, (BN), (ReLU)] as one launch (csrc/conv_dwpw.hip).  Holds the two
     original conv modules (parameters, state-dict keys and scales unchanged: `dw`, `pw`); inference only.  Falls back
-    to running them one after the other when the input is not a channels_last ROCm tensor of a supported size."""
+    to running them one after the other when the input is not a channels_last ROCm tensor of a supported size.
+    A block whose two convs were linked by link_codes BEFORE fuse_dw_pw paired them (the supported order: fuse_bn_relu ->
+    link_codes(model, example) -> fuse_dw_pw) reads uint8 codes and runs as one kernel on codes (csrc/conv_dwpw_codes.hip,
+    `_forward_codes`) for the pairs in options.dwpw_codes_pairs -- empty by default -- or all supported ones under
+    options.dwpw_all; `_last_kernel` then ends in "+codes_in" or "+codes_in+codes_out".  Otherwise its two convs run their
+    code kernels."""
 
     def __init__(self, dw, pw):
         super().__init__()
@@ -215,6 +222,12 @@ class DwPwBlock(nn.Module):
         from . import _lib
         from .conv2d_func import _conv_desc, _conv_weights, _epilogue_args, _ptr, options
         dw, pw = self.dw, self.pw
+        if x.dtype == torch.uint8:
+            y = self._forward_codes(x)
+            if y is None:
+                self._last_kernel = None
+                y = pw(dw(x))
+            return y
         ok = (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)
               and not self.training and not torch.is_grad_enabled() and options.mfma_passes in (_lib.MFMA_DEFAULT, _lib.MFMA_F16X1)
               and dw.q_bit in (8, 7) and dw._post is not None and dw._post[0] is not None and not (int(dw._post[2]) & 2)
@@ -255,6 +268,57 @@ class DwPwBlock(nn.Module):
                 m._grouped_stash = False
         return y
 
+    def _forward_codes(self, x):
+        """The pair inside a chain of codes (link_codes before fuse_dw_pw): `x` holds the depthwise layer's input codes and the
+        depthwise layer writes this pointwise layer's codes.  ONE slfp_dwpw_fwd_codes launch (csrc/conv_dwpw_codes.hip) -> the next
+        layer's codes (pw._code_out) or float32, bit-identical to the two code kernels; None where the pair does not take it: not
+        linked to each other, a layer-output table, a raw bias, a pair outside options.dwpw_codes_pairs (options.dwpw_all: every
+        pair), or one slfp_dwpw_codes_supported refuses."""
+        from . import _lib
+        from .conv2d_func import _conv_desc, _conv_io, _conv_weights, _epilogue_args, _ptr, options
+        dw, pw = self.dw, self.pw
+        out = pw._code_out
+        ok = (x.is_cuda and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)
+              and not self.training and not torch.is_grad_enabled() and dw.q_bit in (8, 7)
+              and dw._post is not None and dw._post[0] is not None and dw.bias is None
+              and dw._code_out is not None and dw._code_out == _reader_quant(pw)
+              and (out is None or (isinstance(out, tuple) and len(out) == 2))
+              and dw._code_lut is None and pw._code_lut is None
+              and (pw.bias is None or getattr(pw, "_scaled_bias", False)))
+        if ok and not getattr(options, "dwpw_all", False):
+            ok = (dw.in_channels, int(dw.stride[0])) in options.dwpw_codes_pairs
+        if not ok:
+            return None
+        L = _lib.load()
+        N = x.shape[0]
+        d1 = _conv_desc(dw, x.shape)
+        io = _conv_io(True, out)
+        ho, wo = ctypes.c_int64(), ctypes.c_int64()
+        with torch.cuda.device(x.device):
+            if L.slfp_conv2d_out_shape(ctypes.byref(d1), ctypes.byref(ho), ctypes.byref(wo)) != _lib.OK:
+                return None
+            d2 = _conv_desc(pw, (N, dw.out_channels, ho.value, wo.value))
+            _, s1, h1, f1 = _epilogue_args(dw, None, x.device)
+            bias2, s2, h2, f2 = _epilogue_args(pw, pw.bias, x.device)
+            if not L.slfp_dwpw_codes_supported(ctypes.byref(d1), ctypes.byref(d2), ctypes.byref(io), 1 if bias2 is not None else 0, f1, f2):
+                return None
+            stream = torch.cuda.current_stream(x.device)
+            b1 = _conv_weights(dw, d1, dw.weight, stream, True)
+            b2 = _conv_weights(pw, d2, pw.weight, stream, True)
+            y = torch.empty((N, pw.out_channels, ho.value, wo.value), dtype=torch.uint8 if out is not None else torch.float32,
+                            device=x.device, memory_format=torch.channels_last)
+            _lib.check(L.slfp_dwpw_fwd_codes(ctypes.byref(d1), ctypes.byref(d2), ctypes.byref(io), x.data_ptr(), b1.data_ptr(),
+                                             s1.data_ptr(), h1.data_ptr(), f1, b2.data_ptr(), _ptr(bias2), _ptr(s2), _ptr(h2), f2,
+                                             y.data_ptr(), stream.cuda_stream))
+        self._last_kernel = (("dwpw_fused_f16x1" if dw.q_bit == 8 else "dwpw_fused_f16_exact") + "+codes_in"
+                             + ("+codes_out" if out is not None else ""))
+        dw.__dict__.update(_last_codes=x.detach(), _last_input=None, _input_q=None)
+        pw.__dict__.update(_last_codes=None, _last_input=None, _input_q=None)   # the pointwise input never exists as a tensor
+        for m in (dw, pw):
+            if m._grouped_stash:
+                m._grouped_stash = False
+        return y
+
 
 def _is_dw(m):
     return _is_conv_q(m) and m.groups == m.in_channels == m.out_channels and tuple(m.kernel_size) == (3, 3)
@@ -268,7 +332,12 @@ def fuse_dw_pw(model):
     """After fuse_bn_relu: replace every [depthwise Conv2d_Q (+BN+ReLU folded), Identity..., pointwise Conv2d_Q (+BN+ReLU
     folded)] run of an nn.Sequential by one DwPwBlock (the pointwise slot; the depthwise slot becomes nn.Identity).
     Whether a pair really runs as one kernel is decided per call (input layout, size, libslfp_hip's
-    slfp_dwpw_supported); otherwise the block runs its two convs as before.  Returns the number of blocks formed."""
+    slfp_dwpw_supported); otherwise the block runs its two convs as before.  Returns the number of blocks formed.
+    With 1-byte codes the supported order is fuse_bn_relu -> link_codes(model, example) -> fuse_dw_pw: the links are made on the
+    plain convs, and a block whose depthwise conv writes its pointwise conv's codes may then run as one kernel on codes
+    (DwPwBlock._forward_codes; options.dwpw_codes_pairs / dwpw_all).  unfuse_dw_pw and unfuse put the linked convs back as they
+    are; unlink_codes reaches blk.dw / blk.pw through model.modules(), and the block then takes float32 again.  link_codes on a
+    model that already holds DwPwBlocks does what it did before: it does not look inside them."""
     n = 0
     for seq in [m for m in model.modules() if isinstance(m, nn.Sequential)]:
         names = list(seq._modules.keys())
@@ -517,7 +586,9 @@ def link_codes(model, example_input=None):
     the unlinked fused net (single-pass MFMA mode / SFP<3,3>), activations cross HBM as 1 B per element instead of 4.
     With `example_input` (a channels_last ROCm batch) only links for which both kernels exist are made (one forward
     records the shapes); without it every candidate is linked and combinations without a kernel run through the float32
-    interface plus an encode / decode pass (correct, slower).  Inference only.  Returns the number of links."""
+    interface plus an encode / decode pass (correct, slower).  Inference only.  Returns the number of links.
+    Call it BEFORE fuse_dw_pw (fuse_bn_relu -> link_codes -> fuse_dw_pw): a DwPwBlock is not a Conv2d_Q, so a block formed earlier
+    is neither linked to its neighbours nor inside."""
     from .conv2d_func import _supported
     shapes = {}
     if example_input is not None:

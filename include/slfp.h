@@ -224,6 +224,24 @@ int slfp_conv2d_fwd_codes(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, c
 int slfp_conv2d_fwd_codes_ws(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
                              const float* bias, const float* post_scale, const float* post_shift, int relu, void* y,
                              void* workspace, void* stream);
+/* ---- one MobileNet block in one launch, on codes ------------------------------------------------------------------------------
+ * slfp_dwpw_fwd's pair of layers inside a chain of codes: x holds the depthwise layer's input codes (io->x_codes must be 1: codes
+ * of QA(. / dw->ka) in the format of dw->qbits), y receives float32 (io->y_codes = 0) or the codes of the reader io->y_ka /
+ * io->y_qbits describe (io->y_codes = 1).  The depthwise result goes through the pointwise layer's quantizer straight into the
+ * matrix cores' fp16 operand in LDS: no code is formed for it and it never reaches HBM.  Bit-identical to slfp_conv2d_fwd_codes(dw, codes ->
+ * codes for pw->ka) followed by slfp_conv2d_fwd_codes(pw, codes -> y).  The other arguments are slfp_dwpw_fwd's (post1_* required;
+ * bias_pw / post2_* may be NULL; relu*: 0 / 1; every pointer 16-byte aligned).
+ * slfp_dwpw_codes_supported answers 1 / 0 without device work: 1 where slfp_dwpw_supported takes the pair (3x3 depthwise, stride
+ * 1 / 2, C in {32, 64, 128}, N in {64, 128, 256}, C * N * 2 B <= 64 KiB, NHWC, single-pass mode or SFP<3,3>, one q_bit), the
+ * depthwise layer alone is one slfp_conv2d_fwd_codes takes, the reader's quantizer is valid (y_qbits 8 or 7, y_ka > 0 with a code
+ * table), relu1 / relu2 are 0 or 1 (no SLFP_POST_LAYEROUT) and the kernel's LDS (<= 160 KiB) and offsets fit; K >= 256 blocks,
+ * float32 input, the three-pass mode and everything else: 0, and slfp_dwpw_fwd_codes then returns SLFP_ERR_UNSUPPORTED. */
+int slfp_dwpw_codes_supported(const slfp_conv2d_desc* dw, const slfp_conv2d_desc* pw, const slfp_conv2d_io* io,
+                              int has_bias_pw, int relu1, int relu2);
+int slfp_dwpw_fwd_codes(const slfp_conv2d_desc* dw, const slfp_conv2d_desc* pw, const slfp_conv2d_io* io, const void* x,
+                        const void* wprep_dw, const float* post1_scale, const float* post1_shift, int relu1,
+                        const void* wprep_pw, const float* bias_pw, const float* post2_scale, const float* post2_shift,
+                        int relu2, void* y, void* stream);
 /* ---- code output into a channel slice: a concat without the copy ------------------------------------------------------------
  * slfp_conv2d_fwd_codes_ws with the code output written into a channel slice of a WIDER NHWC code tensor: y points at the
  * slice's first channel of pixel 0, y_ld is the wider tensor's channel count = the byte distance between two pixels.  The two
