@@ -38,6 +38,7 @@ SYMBOLS = (
     "slfp_layerout_lut_classes", "slfp_layerout_lut_values", "slfp_layerout_lut_index", "slfp_conv2d_codes_lut_supported",
     "slfp_conv2d_fwd_codes_lut", "slfp_debug_layerout_lut_mismatches",
     "slfp_dwpw_codes_supported", "slfp_dwpw_fwd_codes",
+    "slfp_linear_fc_supported", "slfp_linear_fc_workspace_bytes", "slfp_linear_fwd_fc", "slfp_debug_linear_fc_tiles",
 )
 
 
@@ -157,6 +158,10 @@ def load():
         "slfp_debug_layerout_lut_mismatches": (ci, [vp, vp]),
         "slfp_dwpw_codes_supported": (ci, [dp, dp, ctypes.POINTER(ConvIo), ci, ci, ci]),
         "slfp_dwpw_fwd_codes": (ci, [dp, dp, ctypes.POINTER(ConvIo), vp, vp, vp, vp, ci, vp, vp, vp, vp, ci, vp, vp]),
+        "slfp_linear_fc_supported": (ci, [i64, i64, i64, ci, ci, ctypes.POINTER(ConvIo), ci, ci]),
+        "slfp_linear_fc_workspace_bytes": (sz, [i64, i64, i64, ctypes.POINTER(ConvIo)]),
+        "slfp_linear_fwd_fc": (ci, [vp, vp, vp, vp, i64, i64, i64, cf, cf, ci, ci, ctypes.POINTER(ConvIo), ci, vp, vp]),
+        "slfp_debug_linear_fc_tiles": (ci, [ci, ci]),
     }
     assert set(sigs) == set(SYMBOLS)
     for name, (res, args) in sigs.items():

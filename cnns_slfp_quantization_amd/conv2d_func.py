@@ -68,14 +68,20 @@ class _Options:
                                      # measurements of profiles/dwpw_codes_bench.py; dwpw_all forces every supported pair here too
     backward = "composite"           # "composite": the reference's STE composite; "hip": slfp_conv2d_bwd where it covers the layer
                                      # (3x3 depthwise, stride-1 1x1, Linear_Q); "hip_all": also the dense family (SLFP_BWD_DENSE)
+    linear_kernel = "pointwise"      # "pointwise": Linear_Q in inference is a 1x1 convolution over the batch (slfp_linear_fwd_prepared);
+                                     # "fc": the weight-streaming kernel (slfp_linear_fwd_fc) wherever slfp_linear_fc_supported
+                                     # says yes -- the same bits.  A Linear_Q linked by fusion.link_head runs "fc" either way
 
     def __setattr__(self, name, value):
         if name == "backward" and value not in _BACKWARDS:
             raise ValueError(f"options.backward must be one of {_BACKWARDS}, got {value!r}")
+        if name == "linear_kernel" and value not in _LINEAR_KERNELS:
+            raise ValueError(f"options.linear_kernel must be one of {_LINEAR_KERNELS}, got {value!r}")
         super().__setattr__(name, value)
 
 
 _BACKWARDS = ("composite", "hip", "hip_all")
+_LINEAR_KERNELS = ("pointwise", "fc")
 options = _Options()
 
 
@@ -813,8 +819,15 @@ def conv2d_Q_bias(q_bit, Kw, Ka):
     return _conv_class(q_bit, Kw, Ka, bias_default=True, scaled_bias=True)
 
 
-def _hip_linear(mod, x, weight, bias, cache_ok=False):
-    _require_gpu_f32(x, "Linear_Q")
+def _hip_linear(mod, x, weight, bias, cache_ok=False, fc=False):
+    """One Linear_Q forward on libslfp_hip.  fc: run the weight-streaming kernel (slfp_linear_fwd_fc) where the library has it for
+    this layer -- the caller asks for it only in inference; `x` may then be the uint8 codes a fusion.link_head producer wrote, and
+    mod._code_out / mod._code_relu describe the codes (and the folded ReLU) to write."""
+    if x.dtype == torch.uint8 and fc:
+        if not x.is_cuda:
+            raise RuntimeError("Linear_Q: code tensors live on the ROCm device")
+    else:
+        _require_gpu_f32(x, "Linear_Q")
     L = _lib.load()
     lead = x.shape[:-1]
     x2 = x.reshape(-1, x.shape[-1])
@@ -829,24 +842,73 @@ def _hip_linear(mod, x, weight, bias, cache_ok=False):
     if bias is not None:
         b = bias.detach()
         b = b if b.is_contiguous() else b.contiguous()
-    y = torch.empty((B, O), dtype=torch.float32, device=x.device)
     ka, kw = _f32(_scalar_scale(mod.Ka, "Ka")), _f32(_scalar_scale(mod.Kw, "Kw"))
+    x_codes = x2.dtype == torch.uint8
+    out, relu = mod._code_out, 1 if mod._code_relu else 0
+    fc = (fc and B > 0 and mod.q_bit in (8, 7) and
+          bool(L.slfp_linear_fc_supported(B, I, O, mod.q_bit, options.mfma_passes, ctypes.byref(_conv_io(x_codes, out)), 1, relu)))
+    if not fc and (x_codes or out is not None or relu):
+        # a linked layer without the kernel (F16X3, an empty batch): the float32 interface between slfp_decode_f32 and slfp_encode_f32
+        # (never faster).  decode(codes) is input_q = QA(x / Ka), a class value without the scale, and the float32 interface divides
+        # by Ka and quantizes again: it is handed input_q * Ka.  QA((q * Ka) / Ka) == q for every class value q: the product and the
+        # quotient are each correctly rounded, so the result is within 2 ulp of q, while the quantizer's steps lie midway between
+        # classes that are 2^(1/16) (SFP<3,3>: 2^(1/8)) apart; the clamp literal stays above the clamp's threshold, exact zero stays
+        # zero, and the "tiny" class stays below the smallest step (should the product underflow to 0, tiny and zero are both the
+        # operand +-0).  So the kernel sees the operands the codes stand for: the bits of the unlinked layer in the same mode.
+        xf = hip_decode(x2, _act_fmt(mod.q_bit)) * ka if x_codes else x2
+        y = _hip_linear_f32(mod, L, xf, w, weight, b, ka, kw, cache_ok)
+        y = torch.relu(y) if relu else y
+        y = hip_encode(y, out[0], _act_fmt(out[1])) if out is not None else y
+    elif fc:
+        y = _hip_linear_fc(mod, L, x2, w, weight, b, ka, kw, cache_ok, out, relu)
+    else:
+        y = _hip_linear_f32(mod, L, x2, w, weight, b, ka, kw, cache_ok)
+    return y.reshape(*lead, O)
+
+
+def _linear_blob(mod, L, w, weight, kw, stream, cache_ok):
+    """The prepared weights of a Linear_Q (slfp_linear_prepare_weights): quantized once per weight version (the reference
+    re-quantizes on every forward, utils/conv2d_func.py:62: AlexNet's 9216x4096 / VGG-16's 25088x4096 layers make that the dominant
+    cost of their classifiers); cached only where cache_ok, see the module docstring.  Both linear kernels read this blob."""
+    O, I = w.shape
 
     def make(h):
-        blob = torch.empty(max(L.slfp_linear_workspace_bytes(1, I, O), 16), dtype=torch.uint8, device=x.device)
+        blob = torch.empty(max(L.slfp_linear_workspace_bytes(1, I, O), 16), dtype=torch.uint8, device=w.device)
         _lib.check(L.slfp_linear_prepare_weights(w.data_ptr(), blob.data_ptr(), I, O, kw, mod.q_bit, options.mfma_passes, h))
         return blob, None
 
-    with _on_device(x.device):
-        # quantize the weights once per weight version (the reference re-quantizes on every forward,
-        # utils/conv2d_func.py:62: AlexNet's 9216x4096 / VGG-16's 25088x4096 layers make that the
-        # dominant cost of their classifiers); cached only where cache_ok, see the module docstring
-        key = (w.device, w.data_ptr(), weight._version, tuple(w.shape), mod.q_bit, kw, options.mfma_passes)
-        stream = torch.cuda.current_stream(x.device)
-        blob = mod._prep.get(key, stream, cache_ok, make)
+    key = (w.device, w.data_ptr(), weight._version, tuple(w.shape), mod.q_bit, kw, options.mfma_passes)
+    return mod._prep.get(key, stream, cache_ok, make)
+
+
+def _hip_linear_f32(mod, L, x2, w, weight, b, ka, kw, cache_ok):
+    """slfp_linear_fwd_prepared: the layer as a 1x1 convolution over the rows of x2 (float32, contiguous)."""
+    (B, I), O = x2.shape, w.shape[0]
+    y = torch.empty((B, O), dtype=torch.float32, device=x2.device)
+    with _on_device(x2.device):
+        stream = torch.cuda.current_stream(x2.device)
+        blob = _linear_blob(mod, L, w, weight, kw, stream, cache_ok)
         _lib.check(L.slfp_linear_fwd_prepared(x2.data_ptr(), blob.data_ptr(), _ptr(b), y.data_ptr(), B, I, O, ka, kw, mod.q_bit,
                                               options.mfma_passes, stream.cuda_stream))
-    return y.reshape(*lead, O)
+    mod.__dict__["_last_kernel"] = "linear_pointwise"
+    return y
+
+
+def _hip_linear_fc(mod, L, x2, w, weight, b, ka, kw, cache_ok, out, relu):
+    """slfp_linear_fwd_fc (the caller has asked slfp_linear_fc_supported): x2 is float32 or the uint8 codes written for this module's
+    Ka / q_bit; the result is float32 or, with `out` = (Ka, q_bit) of the Linear_Q that reads it, that layer's codes."""
+    (B, I), O = x2.shape, w.shape[0]
+    io = _conv_io(x2.dtype == torch.uint8, out)
+    y = torch.empty((B, O), dtype=torch.uint8 if out is not None else torch.float32, device=x2.device)
+    with _on_device(x2.device):
+        stream = torch.cuda.current_stream(x2.device)
+        blob = _linear_blob(mod, L, w, weight, kw, stream, cache_ok)
+        ws_bytes = L.slfp_linear_fc_workspace_bytes(B, I, O, ctypes.byref(io))
+        ws = _workspace(x2.device, ws_bytes) if ws_bytes else None
+        _lib.check(L.slfp_linear_fwd_fc(x2.data_ptr(), blob.data_ptr(), _ptr(b), y.data_ptr(), B, I, O, ka, kw, mod.q_bit,
+                                        options.mfma_passes, ctypes.byref(io), relu, _ptr(ws), stream.cuda_stream))
+    mod.__dict__["_last_kernel"] = "linear_fc" + ("+codes_in" if io.x_codes else "") + ("+codes_out" if io.y_codes else "")
+    return y
 
 
 class _SlfpLinearFn(torch.autograd.Function):
@@ -897,8 +959,14 @@ def linear_Q(q_bit, Kw, Ka):
             self._input_q = None
             self._weight_q = None
             self.bias_q = None
+            self._last_kernel = None       # what the last forward ran: "linear_pointwise" or "linear_fc[+codes_in][+codes_out]"
             self._last_bwd_kernel = None
             self._grouped_stash = False   # the stash is one image group's (mark_grouped_stash)
+            # fusion.link_head: the classifier head on 1-byte codes (inference only)
+            self._code_in = False     # a producer writes this layer's codes: only then is a uint8 input taken as codes
+            self._code_out = None     # (Ka, q_bit) of the Linear_Q that reads the result: hand it 1-byte codes
+            self._code_relu = False   # the ReLU between this layer and its reader, folded into the epilogue
+            self._last_codes = None
 
         # The reference stores input_q / weight_q / bias_q on every forward (utils/conv2d_func.py:60-64) and its nets
         # read them back afterwards (nets_cifar/mobilenetv1.py:169-170, resnet50.py:353-354, alexnet.py:107-114);
@@ -908,11 +976,14 @@ def linear_Q(q_bit, Kw, Ka):
             _check_stash(self)
             if self.q_bit != 32 and self._input_q is None and self._last_input is not None:
                 self._input_q = hip_quantize(self._last_input, _f32(self.Ka), _act_fmt(self.q_bit))
+            elif self.q_bit != 32 and self._input_q is None and self._last_codes is not None:
+                # behind a link the input arrived already quantized: input_q = decode(codes), bit for bit
+                self._input_q = hip_decode(self._last_codes, _act_fmt(self.q_bit))
             return self._input_q
 
         @property
         def weight_q(self):
-            if self.q_bit != 32 and self._weight_q is None and self._last_input is not None:
+            if self.q_bit != 32 and self._weight_q is None and (self._last_input is not None or self._last_codes is not None):
                 self._weight_q = hip_quantize(self.weight.detach().contiguous(), _f32(self.Kw), _w_fmt(self.q_bit))
             return self._weight_q
 
@@ -937,14 +1008,29 @@ def linear_Q(q_bit, Kw, Ka):
                 raise UnboundLocalError("q_bit must be 32, 8 or 7 (utils/sfp_quant.py:142-147)")
             if self.bias is None:
                 raise TypeError("unsupported operand type(s) for /: 'NoneType' and 'Tensor'")  # as the reference
-            self._last_input = input.detach()
+            x_codes = input.dtype == torch.uint8
+            if x_codes and not self._code_in:
+                # only a layer that fusion.link_head marked as a reader takes bytes as codes: anything else (a raw uint8 batch)
+                # would be decoded into silently wrong activations
+                raise TypeError("Linear_Q: expected float32, got torch.uint8 (1-byte codes are read only by a layer that "
+                                "fusion.link_head linked to their producer)")
+            self._last_input = None if x_codes else input.detach()
+            self._last_codes = input.detach() if x_codes else None
             self._input_q = None
             self._weight_q = None
             self.bias_q = self.bias / self.Kw / self.Ka      # utils/conv2d_func.py:63 (the kernel applies the same two divisions)
+            if x_codes or self._code_out is not None or self._code_relu:
+                # a link of fusion.link_head: 1-byte codes on one or both sides (inference only)
+                if self.training:
+                    raise RuntimeError("Linear_Q: code links (fusion.link_head) are inference-only; call fusion.unlink_head(model)")
+                with torch.no_grad():
+                    return _hip_linear(self, input, self.weight, self.bias, cache_ok=True, fc=True)
             need_grad = torch.is_grad_enabled() and (input.requires_grad or self.weight.requires_grad or
                                                      self.bias.requires_grad)
             if need_grad:
                 return _SlfpLinearFn.apply(input, self.weight, self.bias, self)
-            return _hip_linear(self, input, self.weight, self.bias, cache_ok=not self.training and not torch.is_grad_enabled())
+            inference = not self.training and not torch.is_grad_enabled()
+            return _hip_linear(self, input, self.weight, self.bias, cache_ok=inference,
+                               fc=inference and options.linear_kernel == "fc")
 
     return Linear_Q

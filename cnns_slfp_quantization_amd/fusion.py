@@ -29,6 +29,10 @@ undo function restores exactly that state; "also undone by" = the other undo fun
                                    link_codes_traced(entries=True)                                                  unfuse_residual
   link_layerout(model, x)          fuse_bn_relu                       _code_out, _code_lut; pools -> CodeMaxPool2d, unlink_codes
                                                                       activation modules -> CodeAct
+  link_head(model, x)              fuse_bn_relu / link_codes          Linear_Q: _code_in, _code_out, _code_relu;    unlink_head / unlink_codes
+                                                                      last conv: _code_out, _post; _head_link;
+                                                                      pools -> CodeMaxPool2d, ReLUs -> CodeReLU,
+                                                                      identity avg-pools -> CodePass
 
 The passes that take an example input share one forward trace (`_Trace`), one rule for "the same tensor" (`_Trace.same`), one
 eligibility predicate (`_code_eligible`), one record of wrapped children (`_wrap_children` / `_unwrap_children`) and one
@@ -740,6 +744,7 @@ def unlink_codes(model):
     codes)."""
     n = 0
     unlink_trunk(model)
+    unlink_head(model)   # (uncounted, as link_trunk's: a head link's producer may be the last conv of a chain)
     for parent in model.modules():
         for name, child in list(parent._modules.items()):
             if isinstance(child, CodeMaxPool2d):
@@ -1355,5 +1360,221 @@ def unfuse_fire(model):
     for blk in list(model.modules()):
         if "_fire_fused" in blk.__dict__:
             _restore_fire(blk)
+            n += 1
+    return n
+
+
+# ------------------------------------------------------------------ the classifier head on 1-byte codes
+class CodePass(nn.Module):
+    """A module that is the identity on the tensor link_head follows (an nn.AdaptiveAvgPool2d whose output size equals its input
+    size) inside a linked head: uint8 codes pass through without a launch; anything else goes to the original module, which this
+    wrapper keeps (`mod`; it has no parameters, the state dict does not change)."""
+
+    def __init__(self, mod):
+        super().__init__()
+        self.mod = mod
+
+    def forward(self, x):
+        return x if x.dtype == torch.uint8 else self.mod(x)
+
+
+def _is_linear_q(m):
+    return isinstance(m, nn.Linear) and hasattr(m, "q_bit") and hasattr(m, "Ka") and hasattr(m, "_code_in")
+
+
+def _head_eligible(m):
+    """Can Linear_Q `m` take part in a head link: 8 / 7 bit, eval mode, a bias (the reference dereferences it)."""
+    return _is_linear_q(m) and m.q_bit in (8, 7) and not m.training and m.bias is not None
+
+
+def _eval_dropout(m):
+    return isinstance(m, (nn.Dropout, nn.Dropout2d)) and not m.training
+
+
+def _restore_head(a):
+    """Take back the link whose producer is `a` (a Linear_Q or a Conv2d_Q): every slot and attribute link_head wrote for it."""
+    rec = a.__dict__.pop("_head_link")
+    for parent, name, orig in rec["slots"]:
+        now = parent._modules.get(name)
+        if (isinstance(now, CodeMaxPool2d) and now.pool is orig or isinstance(now, CodeReLU) and now.relu is orig
+                or isinstance(now, CodePass) and now.mod is orig):
+            parent._modules[name] = orig
+    a._code_out = None
+    if _is_conv_q(a):
+        a._post = rec["post"]
+    else:
+        a._code_relu = False
+    rec["reader"]._code_in = False
+
+
+def _wrap_head(model, pools, relus, passes, q_bit):
+    """_wrap_children plus CodePass for `passes`; the records _restore_head takes."""
+    recs = _wrap_children(model, pools, q_bit, relus)
+    for parent in [m for m in model.modules() if not isinstance(m, (CodeMaxPool2d, CodeReLU, CodeAct, CodePass))]:
+        for name, child in list(parent._modules.items()):
+            if any(child is pm for pm in passes):
+                parent._modules[name] = CodePass(child)
+                recs.append((parent, name, child))
+    return recs
+
+
+def link_head(model, example_input):
+    """The classifier head on 1-byte codes: after fuse_bn_relu / link_codes, the Linear_Q layers at the end of AlexNet / VGG16_Q
+    (utils/conv2d_func.py:50-66) hand their activations on as codes and run the weight-streaming kernel (slfp_linear_fwd_fc).
+    One traced forward on `example_input` finds two kinds of link:
+      (a) Linear_Q -> Linear_Q with only nn.ReLU, nn.Dropout in eval mode or nn.Identity modules between them (each run once, no
+          other module reading the tensor): the producer folds the ReLU (`_code_relu`) and writes the reader's codes (`_code_out`),
+          the ReLU slots become CodeReLU, the reader is marked (`_code_in`);
+      (b) Conv2d_Q -> the first Linear_Q, where the Linear's recorded input equals, value for value, t.flatten(1) of a recorded 4-d
+          tensor t that comes from a code-eligible Conv2d_Q through only its fused ReLU, nn.ReLU modules, floor-mode nn.MaxPool2d
+          (-> CodeMaxPool2d), eval Dropout, nn.Identity and an nn.AdaptiveAvgPool2d whose output size equals its input size (-> CodePass);
+          nn.Flatten / reshape / flatten between t and the Linear work on the code tensor as they stand.  The conv gets the
+          Linear's (Ka, q_bit) as `_code_out`, with the ReLU folded.
+    Links are made only where slfp_linear_fc_supported has the reader's (and, for (a), the producer's) kernel.  Each link is verified
+    on its own -- the reader's output on the recorded input must be torch.equal to the recorded one -- and a link that fails is
+    taken back alone; then the whole model must reproduce its recorded output, or every link is taken back.  Any exception (a
+    functional `view` that cannot take a channels_last code tensor, arithmetic on the flattened tensor) is a refusal with a
+    warning.  Inference only.  Returns the number of links; unlink_head undoes them (unlink_codes takes them along)."""
+    from .conv2d_func import _supported, _conv_io, _scalar_scale, options
+    from .sfp_quant import hip_maxpool_codes
+    from . import _lib
+    if (model.training or not torch.is_tensor(example_input) or not example_input.is_cuda
+            or not any(_head_eligible(m) for m in model.modules())):
+        return 0
+    # (a Linear_Q owns its quantizer children, so it is no leaf: it is recorded as a block)
+    tr = _Trace(model, example_input, blocks=[m for m in model.modules() if _is_linear_q(m)])
+    y0 = tr.output
+    if not torch.is_tensor(y0):
+        return 0
+    index = {id(c): i for i, c in enumerate(tr.calls)}
+
+    def lin_quant(b):
+        return float(_scalar_scale(b.Ka, "Ka")), int(b.q_bit)
+
+    def fc_ok(m, x, x_codes, out, relu):
+        rows = x.numel() // x.shape[-1]
+        io = _conv_io(x_codes, out)
+        return bool(_lib.load().slfp_linear_fc_supported(rows, m.in_features, m.out_features, m.q_bit, options.mfma_passes,
+                                                         ctypes.byref(io), 1, 1 if relu else 0))
+
+    lins = [c for c in tr.calls if _is_linear_q(c.mod)]
+    plans = []   # (producer, reader, pools, relus, passes, via_relu, x of the producer, x / out of the reader), execution order
+    linked_readers = set()
+    for cb in lins:
+        b = cb.mod
+        if (not _head_eligible(b) or tr.runs(b) != 1 or b._code_in or not torch.is_tensor(cb.x) or cb.x.dtype != torch.float32
+                or not torch.is_tensor(cb.out)):
+            continue
+        # walk back from the reader's input through modules that hand the tensor on
+        t, via_relu, pools, relus, passes, seen, flat = cb.x, False, [], [], [], {b}, cb.x.dim() == 2
+        a, on_the_way = None, []   # every tensor between the producer and the reader
+        for _ in range(16):
+            on_the_way.append(t)
+            made = [c for c in tr._made.get(tr._key(t), []) if c.mod not in seen and index[id(c)] < index[id(cb)]]
+            step = next((c for c in reversed(made) if tr.runs(c.mod) == 1 and len(c.inp) == 1 and torch.is_tensor(c.x) and (
+                isinstance(c.mod, (nn.ReLU, nn.Identity, nn.Flatten)) or _eval_dropout(c.mod) or
+                (t.dim() == 4 and (_poolable(c.mod) or isinstance(c.mod, nn.AdaptiveAvgPool2d) and c.x.shape == c.out.shape)))), None)
+            if step is not None:
+                seen.add(step.mod)
+                if isinstance(step.mod, nn.ReLU):
+                    via_relu = True
+                    relus.append(step.mod)
+                elif isinstance(step.mod, nn.MaxPool2d):
+                    pools.append(step.mod)
+                elif isinstance(step.mod, nn.AdaptiveAvgPool2d):
+                    passes.append(step.mod)
+                t = step.x
+                continue
+            prod = next((c for c in made if _is_linear_q(c.mod) or _is_conv_q(c.mod)), None)
+            if prod is not None:
+                a = prod
+                break
+            if t.dim() == 2 and flat:
+                # a functional flatten / view / reshape: the latest recorded 4-d tensor with these values
+                flat = False
+                src = next((c.out for c in reversed(tr.calls[:index[id(cb)]]) if torch.is_tensor(c.out) and c.out.dim() == 4
+                            and c.out.dtype == t.dtype and c.out.shape[0] == t.shape[0] and c.out.numel() == t.numel()
+                            and torch.equal(c.out.flatten(1), t)), None)
+                if src is not None:
+                    t = src
+                    continue
+            break
+        if a is None or tr.runs(a.mod) != 1:
+            continue
+        am = a.mod
+        # nothing else may read the tensors on the way: every recorded reader of them is part of the chain
+        chain = seen | {am}
+        if any(c.mod not in chain for tt in on_the_way + [a.out] for c in tr.readers(tt)):
+            continue
+        out = lin_quant(b)
+        if _is_linear_q(am):
+            if (pools or passes or not _head_eligible(am) or am._code_out is not None or a.out.dim() != cb.x.dim()
+                    or not torch.is_tensor(a.x)):
+                continue
+            a_in = am in linked_readers or a.x.dtype == torch.uint8
+            if not fc_ok(am, a.x, a_in, out, via_relu) or not fc_ok(b, cb.x, True, None, False):
+                continue
+        else:
+            if (not _code_eligible(am, producer_side=True) or a.out.dim() != 4 or not torch.is_tensor(a.x) or a.x.dim() != 4
+                    or (pools and am.out_channels % 4) or not fc_ok(b, cb.x, True, None, False)):
+                continue
+            flags = _post_flags(am) | (1 if via_relu else 0)
+            a_in = a.x.dtype == torch.uint8
+            if a_in and not _supported(am, tuple(a.x.shape), "codes", True, out, flags):
+                continue   # (a float32 reader without the kernel enters the chain through one slfp_encode_f32 pass, as in link_codes)
+        plans.append((am, b, pools[::-1], relus, passes, via_relu, a.x, cb.x, cb.out))
+        linked_readers.add(b)
+    tr.release()
+    if not plans:
+        return 0
+
+    made = []
+
+    def take_all_back():
+        for am in made:
+            _restore_head(am)
+
+    for am, b, pools, relus, passes, via_relu, x_a, x_b, want in plans:
+        rec = {"reader": b, "post": am._post if _is_conv_q(am) else None, "slots": _wrap_head(model, pools, relus, passes, b.q_bit)}
+        am.__dict__["_head_link"] = rec
+        if _is_conv_q(am):
+            _fold_flags(am, _post_flags(am) | (1 if via_relu else 0))
+        else:
+            am._code_relu = via_relu
+        am._code_out = lin_quant(b)
+        b._code_in = True
+
+        def relinked(am=am, b=b, pools=pools, x_a=x_a, x_b=x_b):
+            t = am(x_a)
+            for p in pools:
+                t = hip_maxpool_codes(t, p.kernel_size, p.stride, p.padding, b.q_bit)
+            return b(t.reshape(x_b.shape))
+
+        # b is not a producer yet (execution order): its output is the recorded float32 one
+        try:
+            ok = _verified(relinked, want, lambda am=am: _restore_head(am), reraise=True)
+        except _lib.SlfpError:
+            take_all_back()   # the links made so far have not seen the whole-model check: none of them stays
+            raise
+        if ok:
+            made.append(am)
+        else:
+            warnings.warn("link_head: a link did not reproduce its reader's output and was taken back", stacklevel=2)
+    if not made:
+        return 0
+    if not _verified(lambda: model(example_input), y0, take_all_back, reraise=True):
+        # e.g. arithmetic on the flattened tensor, or a functional view that cannot take a channels_last code tensor
+        warnings.warn("link_head: the linked model did not reproduce its output on the example input (a functional op between the "
+                      "linked layers?); every link was taken back", stacklevel=2)
+        return 0
+    return len(made)
+
+
+def unlink_head(model):
+    """Undo link_head: every slot and attribute it wrote."""
+    n = 0
+    for m in list(model.modules()):
+        if "_head_link" in m.__dict__:
+            _restore_head(m)
             n += 1
     return n

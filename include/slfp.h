@@ -385,6 +385,35 @@ int slfp_linear_fwd_prepared(const float* x, const void* wprep, const float* bia
                              int64_t in_f, int64_t out_f, float ka, float kw_scale, int qbits,
                              int mfma_passes, void* stream);
 
+/* ---- linear on 1-byte codes: the weight-streaming kernel (csrc/linear_fc.hip) ----------------------------------------
+ * Linear_Q.forward (utils/conv2d_func.py:60-65) for classifier layers, whose cost is the stream of W rather than of the
+ * activations: one wave per workgroup owns 1, 2 or 4 of the blob's 16-channel tiles and 16, 32 or 64 rows and streams its share of W
+ * (the blob of slfp_linear_prepare_weights, unchanged) straight into registers with two chunks of k-steps in flight; the grid is
+ * sized from (batch, out_f) so that it covers the compute units wherever out_f allows, and is never split over in_f.
+ *   io->x_codes 0: x is float32 [batch, in_f]; it is encoded once -- slfp_encode_f32(x, ka, fmt(qbits) | SLFP_FMT_EXT) -- into
+ *                  `workspace` (slfp_linear_fc_workspace_bytes bytes of device memory)
+ *   io->x_codes 1: x holds those codes, as for slfp_conv2d_fwd_codes; `workspace` may be NULL (0 bytes)
+ *   io->y_codes 0: y is float32 [batch, out_f]:  t = linear(QA(x/Ka), QW(w/Kw), bias/Kw/Ka) * Kw * Ka, bit for bit what
+ *                  slfp_linear_fwd_prepared writes for the same arguments;  y = (relu & SLFP_POST_RELU) ? max(t, 0) : t
+ *   io->y_codes 1: y is uint8 [batch, out_f] = slfp_encode_f32(that y, io->y_ka, fmt(io->y_qbits) | SLFP_FMT_EXT): what the
+ *                  Linear_Q behind this one (its Ka, its q_bit) reads with x_codes = 1
+ * relu: 0 or SLFP_POST_RELU.  x, wprep, y, bias and workspace 16-byte aligned.  Supported (slfp_linear_fc_supported: 1 / 0, host
+ * only): qbits 8 in the single-pass operand modes (SLFP_MFMA_DEFAULT / SLFP_MFMA_F16X1) and qbits 7, in_f a multiple of 32, out_f a
+ * multiple of 4 (of 16 with y_codes), batch >= 1, y_qbits 8 or 7 and y_ka > 0 with a code table.  Everything else -- SLFP_MFMA_F16X3
+ * at qbits 8, feature counts that take the direct kernel, other qbits -- returns SLFP_ERR_UNSUPPORTED before any device work.  NaN
+ * inputs are outside the bit-identity: codes have no NaN (slfp_encode_f32 gives 0x00), the float32 interface propagates it.
+ * slfp_debug_linear_fc_tiles(n_tiles, row_tiles) forces the 16-channel tiles / 16-row tiles per workgroup (1, 2 or 4 each; 0: the
+ * rule): measurements only (profiles/linear_fc_bench.py).  The switch is process-wide, not scoped to a thread or a stream: it changes
+ * the tiling (never the result) of every later slfp_linear_fwd_fc call on every thread until it is set again, so a caller resets it
+ * with slfp_debug_linear_fc_tiles(0, 0) when the measurement is done. */
+int slfp_linear_fc_supported(int64_t batch, int64_t in_f, int64_t out_f, int qbits, int mfma_passes,
+                             const slfp_conv2d_io* io, int has_bias, int relu);
+size_t slfp_linear_fc_workspace_bytes(int64_t batch, int64_t in_f, int64_t out_f, const slfp_conv2d_io* io);
+int slfp_linear_fwd_fc(const void* x, const void* wprep, const float* bias, void* y, int64_t batch, int64_t in_f,
+                       int64_t out_f, float ka, float kw_scale, int qbits, int mfma_passes,
+                       const slfp_conv2d_io* io, int relu, void* workspace, void* stream);
+int slfp_debug_linear_fc_tiles(int n_tiles, int row_tiles);
+
 /* ---- self-check ------------------------------------------------------------------------
  * The kernels compute x / scale_div with an FMA correction chain on a host-computed
  * reciprocal instead of the IEEE division macro (csrc/slfp_device.hpp, ScaleDiv).  This
