@@ -39,6 +39,7 @@ SYMBOLS = (
     "slfp_conv2d_fwd_codes_lut", "slfp_debug_layerout_lut_mismatches",
     "slfp_dwpw_codes_supported", "slfp_dwpw_fwd_codes",
     "slfp_linear_fc_supported", "slfp_linear_fc_workspace_bytes", "slfp_linear_fwd_fc", "slfp_debug_linear_fc_tiles",
+    "slfp_global_avgpool_supported", "slfp_global_avgpool_f32",
 )
 
 
@@ -162,6 +163,8 @@ def load():
         "slfp_linear_fc_workspace_bytes": (sz, [i64, i64, i64, ctypes.POINTER(ConvIo)]),
         "slfp_linear_fwd_fc": (ci, [vp, vp, vp, vp, i64, i64, i64, cf, cf, ci, ci, ctypes.POINTER(ConvIo), ci, vp, vp]),
         "slfp_debug_linear_fc_tiles": (ci, [ci, ci]),
+        "slfp_global_avgpool_supported": (ci, [i64, i64, i64, i64, ci, ctypes.POINTER(ConvIo)]),
+        "slfp_global_avgpool_f32": (ci, [vp, vp, i64, i64, i64, i64, ci, ci, ctypes.POINTER(ConvIo), vp]),
     }
     assert set(sigs) == set(SYMBOLS)
     for name, (res, args) in sigs.items():

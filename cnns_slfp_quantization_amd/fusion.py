@@ -33,6 +33,10 @@ undo function restores exactly that state; "also undone by" = the other undo fun
                                                                       last conv: _code_out, _post; _head_link;
                                                                       pools -> CodeMaxPool2d, ReLUs -> CodeReLU,
                                                                       identity avg-pools -> CodePass
+  use_device_avgpool(model, x)     --                                 global average pools -> GlobalAvgPool2d,      restore_avgpool
+                                                                      a ReLU in front -> FoldedReLU (pool._relu)
+  link_pool_head(model, x)         use_device_avgpool; before         pool: _code_out, _pool_link; Linear_Q:        unlink_pool_head /
+                                   link_head                          _code_in                                      restore_avgpool
 
 The passes that take an example input share one forward trace (`_Trace`), one rule for "the same tensor" (`_Trace.same`), one
 eligibility predicate (`_code_eligible`), one record of wrapped children (`_wrap_children` / `_unwrap_children`) and one
@@ -1576,5 +1580,266 @@ def unlink_head(model):
     for m in list(model.modules()):
         if "_head_link" in m.__dict__:
             _restore_head(m)
+            n += 1
+    return n
+
+
+# ------------------------------------------------------------------ the global average pool in front of the classifier
+class FoldedReLU(nn.Module):
+    """An nn.ReLU in front of a GlobalAvgPool2d that applies it (`_relu`): the identity, in the style of CodeReLU.  The original is
+    kept (`relu`); it has no parameters, the state dict does not change."""
+
+    def __init__(self, relu):
+        super().__init__()
+        self.relu = relu
+
+    def forward(self, x):
+        return x
+
+
+def _avgpool_candidate(m):
+    """Is `m` a pooling module that can be a global average pool: nn.AdaptiveAvgPool2d to 1 x 1, or a floor-mode nn.AvgPool2d without
+    padding or divisor override (whether its window is the whole map depends on the input: _avgpool_global)."""
+    if isinstance(m, nn.AdaptiveAvgPool2d):
+        return m.output_size in (1, (1, 1), [1, 1])
+    return (isinstance(m, nn.AvgPool2d) and not m.ceil_mode and m.divisor_override is None
+            and _pair2(m.padding) == (0, 0))
+
+
+def _avgpool_global(m, x):
+    """Does candidate `m` reduce the 4-d tensor `x` to one window per channel?"""
+    if not torch.is_tensor(x) or x.dim() != 4 or x.shape[2] < 1 or x.shape[3] < 1:
+        return False
+    return isinstance(m, nn.AdaptiveAvgPool2d) or _pair2(m.kernel_size) == (x.shape[2], x.shape[3])
+
+
+def _avgpool_bound_ok(got, want, x):
+    """|got - want| <= 2 (HW + 1) 2^-24 mean64(|x|) per element: two float32 summations of HW terms plus one division each differ by
+    at most that, whatever their orders.  `x` is the pooled tensor (after the ReLU, if one is folded)."""
+    if not (torch.is_tensor(got) and got.dtype == want.dtype and got.shape == want.shape):
+        return False
+    hw = x.shape[2] * x.shape[3]
+    bound = 2.0 * (hw + 1) * 2.0 ** -24 * x.double().abs().mean(dim=(2, 3), keepdim=True)
+    return bool(((got.double() - want.double()).abs() <= bound).all())
+
+
+class GlobalAvgPool2d(nn.Module):
+    """A global average pool (nn.AdaptiveAvgPool2d to 1 x 1, or an nn.AvgPool2d whose window is the whole map) on libslfp_hip's
+    kernel (slfp_global_avgpool_f32): float32 sums in one fixed order, so a row of the result does not depend on the batch it
+    is computed in.  In eval mode under no_grad, on a ROCm float32 tensor the library takes (channels_last with C a multiple of 4,
+    or contiguous NCHW) the kernel runs; anything else -- CPU, grad enabled, training, another window -- goes to the original
+    module, which this wrapper keeps (`mod`; it has no parameters, the state dict does not change).
+      _relu       use_device_avgpool folded the nn.ReLU in front: the mean of max(x, 0), on either path
+      _code_out   (Ka, q_bit) of the Linear_Q that reads the result (link_pool_head): uint8 codes instead of float32
+      _last_kernel   "global_avgpool[+relu][+codes_out]", or "aten" """
+
+    def __init__(self, mod):
+        super().__init__()
+        self.mod = mod
+        self.training = mod.training
+        self._relu = False
+        self._code_out = None
+        self._last_kernel = None
+        self._asked = {}
+
+    def forward(self, x):
+        from .sfp_quant import hip_global_avgpool, global_avgpool_supported, hip_encode
+        out = self._code_out
+        if (not self.training and not torch.is_grad_enabled() and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32
+                and x.dim() == 4):
+            key = (x.shape, x.stride(), out)   # the query is host only, but it is a ctypes call per forward: asked once per geometry
+            ok = self._asked.get(key)
+            if ok is None:
+                if len(self._asked) >= 64:
+                    self._asked.clear()
+                ok = self._asked[key] = _avgpool_global(self.mod, x) and global_avgpool_supported(x, out)
+            if ok:
+                self._last_kernel = "global_avgpool" + ("+relu" if self._relu else "") + ("+codes_out" if out is not None else "")
+                return hip_global_avgpool(x, relu=self._relu, code_out=out)
+        self._last_kernel = "aten"
+        y = self.mod(torch.relu(x) if self._relu else x)
+        if out is not None:
+            if self.training or torch.is_grad_enabled() or not y.is_cuda:
+                raise RuntimeError("GlobalAvgPool2d: code links (fusion.link_pool_head) are inference-only on the ROCm device; "
+                                   "call fusion.unlink_pool_head(model)")
+            from .conv2d_func import _act_fmt
+            y = hip_encode(y.contiguous(), out[0], _act_fmt(out[1]))
+        return y
+
+
+def _slots_of(model, child):
+    return [(parent, name) for parent in model.modules() for name, c in parent._modules.items() if c is child]
+
+
+def use_device_avgpool(model, example_input):
+    """Run the global average pools of `model` on libslfp_hip's kernel: one traced forward on `example_input` finds every module,
+    run once, that is an nn.AdaptiveAvgPool2d with output size 1 / (1, 1) or an nn.AvgPool2d whose recorded input is exactly one
+    window (kernel == (H, W), no padding, floor mode, no divisor override), on a ROCm float32 tensor the kernel takes, and puts a
+    GlobalAvgPool2d wrapper in its slot.  An nn.ReLU directly in front of the pool in the same nn.Sequential is folded into the
+    kernel (`_relu`; the ReLU's slot becomes FoldedReLU) where nothing else can read its result: it is run once, and if it is
+    in-place its input is a tensor the module in front of it in that nn.Sequential made.  Each swap is checked alone: the
+    wrapper's result on the recorded input must lie within 2 (HW + 1) 2^-24 mean64(|x|) of the recorded ATen result (the orders of
+    summation differ, so the two are not bit-identical), or the swap is taken back.  Functional F.adaptive_avg_pool2d /
+    F.avg_pool2d calls in a forward (ShuffleNetV2) are out of reach of a pass over modules.  Inference only; the default path of
+    every module is unchanged.  Returns the number of pools swapped; restore_avgpool undoes them."""
+    from .sfp_quant import global_avgpool_supported
+    if model.training or not torch.is_tensor(example_input) or not example_input.is_cuda:
+        return 0
+    if not any(_avgpool_candidate(m) for m in model.modules()):
+        return 0
+    tr = _Trace(model, example_input)
+    plans = []
+    for c in tr.calls:
+        m = c.mod
+        if (not _avgpool_candidate(m) or tr.io(m) is None or c.x.dtype != torch.float32 or not c.x.is_cuda
+                or not _avgpool_global(m, c.x) or not global_avgpool_supported(c.x)):
+            continue
+        relu = None
+        for seq in (s for s in model.modules() if isinstance(s, nn.Sequential)):
+            kids = list(seq._modules.values())
+            i = next((k for k, kid in enumerate(kids) if kid is m), None)
+            if i is None or i == 0 or type(kids[i - 1]) is not nn.ReLU:
+                continue
+            r = kids[i - 1]
+            rio = tr.io(r)
+            if rio is None or not tr.same(rio[1], c.x) or len(_slots_of(model, r)) != 1 or len(_slots_of(model, m)) != 1:
+                continue
+            if tr.same(rio[0], rio[1]):   # in place: the tensor must be one the Sequential's previous module made
+                pio = tr.io(kids[i - 2]) if i >= 2 else None
+                if pio is None or not tr.same(pio[1], rio[0]) or tr.same(pio[0], pio[1]):
+                    continue
+            relu = r
+        plans.append((m, relu, c.x, c.out))
+    done = 0
+    for m, relu, x, want in plans:
+        slots = _slots_of(model, m)
+        if not slots:
+            continue
+        wrap = GlobalAvgPool2d(m)
+        wrap._relu = relu is not None   # (x is the ReLU's result: max(., 0) once more changes nothing)
+        ok = False
+        try:
+            with torch.no_grad():
+                got = wrap(x)
+            ok = wrap._last_kernel != "aten" and _avgpool_bound_ok(got, want, x)
+        except Exception as e:
+            warnings.warn(f"use_device_avgpool: {type(e).__name__}: {e}", stacklevel=2)
+        if not ok:
+            warnings.warn("use_device_avgpool: a pool did not reproduce its recorded output within the summation bound and stays "
+                          "on ATen", stacklevel=2)
+            continue
+        for parent, name in slots:
+            parent._modules[name] = wrap
+        if relu is not None:
+            for parent, name in _slots_of(model, relu):
+                parent._modules[name] = FoldedReLU(relu)
+        done += 1
+    tr.release()
+    return done
+
+
+def restore_avgpool(model):
+    """Undo use_device_avgpool (and, first, link_pool_head): every slot gets its original module back."""
+    unlink_pool_head(model)
+    n = 0
+    for parent in list(model.modules()):
+        for name, child in list(parent._modules.items()):
+            if isinstance(child, GlobalAvgPool2d):
+                parent._modules[name] = child.mod
+                n += 1
+            elif isinstance(child, FoldedReLU):
+                parent._modules[name] = child.relu
+    return n
+
+
+def _restore_pool_link(pool):
+    rec = pool.__dict__.pop("_pool_link")
+    pool._code_out = None
+    rec["reader"]._code_in = False
+
+
+def link_pool_head(model, example_input):
+    """After use_device_avgpool: where a GlobalAvgPool2d's result reaches a Linear_Q through nn.Flatten, a functional flatten / view /
+    reshape, eval-mode Dropout or nn.Identity only, the pool writes that layer's 1-byte codes (`_code_out` = the reader's (Ka,
+    q_bit)) and the reader takes them (`_code_in`) and runs the weight-streaming kernel on them (slfp_linear_fwd_fc): ResNet-50's
+    and the CIFAR MobileNetV1 nets' avgpool -> flatten -> fc.  One traced forward finds the links: every recorded reader of the
+    pooled values (a module input with the pooled tensor's storage and element count) must be such a pass-through module or the
+    one Linear_Q, which must be eligible for a head link and have the kernel (slfp_linear_fc_supported with x_codes = 1).  Each
+    link is verified alone -- the reader's output on the pool's recorded input must be torch.equal to the recorded one -- then the
+    whole model must reproduce the output of the un-linked model (with the device pool) on the example input, or every link is
+    taken back with a warning.  link_head may run afterwards: it passes readers that are already linked.  Inference only.
+    Returns the number of links; unlink_pool_head undoes them."""
+    from .conv2d_func import _conv_io, _scalar_scale, options
+    from .sfp_quant import global_avgpool_supported
+    from . import _lib
+    pools = [m for m in model.modules() if isinstance(m, GlobalAvgPool2d) and m._code_out is None]
+    if (model.training or not torch.is_tensor(example_input) or not example_input.is_cuda or not pools
+            or not any(_head_eligible(m) for m in model.modules())):
+        return 0
+    tr = _Trace(model, example_input, blocks=pools + [m for m in model.modules() if _is_linear_q(m)])
+    y0 = tr.output
+    if not torch.is_tensor(y0):
+        return 0
+    plans = []
+    for i, cp in enumerate(tr.calls):
+        p = cp.mod
+        if (not isinstance(p, GlobalAvgPool2d) or p not in pools or tr.runs(p) != 1 or p._last_kernel == "aten"
+                or not torch.is_tensor(cp.x) or not torch.is_tensor(cp.out) or cp.out.dtype != torch.float32):
+            continue
+        t = cp.out
+        later = [c for c in tr.calls[i + 1:] if torch.is_tensor(c.x) and c.x.data_ptr() == t.data_ptr() and c.x.numel() == t.numel()]
+        lins = [c for c in later if _is_linear_q(c.mod)]
+        passed = [c for c in later if not _is_linear_q(c.mod)]
+        if len(lins) != 1 or any(
+                not (isinstance(c.mod, (nn.Flatten, nn.Identity)) or _eval_dropout(c.mod)) or tr.runs(c.mod) != 1
+                or not torch.is_tensor(c.out) or c.out.data_ptr() != t.data_ptr() or c.out.numel() != t.numel() for c in passed):
+            continue
+        cb = lins[0]
+        b = cb.mod
+        if (not _head_eligible(b) or tr.runs(b) != 1 or b._code_in or cb.x.dim() != 2 or cb.x.dtype != torch.float32
+                or cb.x.shape != (t.shape[0], t.shape[1]) or not torch.is_tensor(cb.out)):
+            continue
+        out = (float(_scalar_scale(b.Ka, "Ka")), int(b.q_bit))
+        io = _conv_io(True, None)
+        if not _lib.load().slfp_linear_fc_supported(cb.x.shape[0], b.in_features, b.out_features, b.q_bit, options.mfma_passes,
+                                                    ctypes.byref(io), 1, 0) or not global_avgpool_supported(cp.x, out):
+            continue
+        plans.append((p, b, out, cp.x, cb.x.shape, cb.out))
+    tr.release()
+    made = []
+
+    def take_all_back():
+        for p in made:
+            _restore_pool_link(p)
+
+    for p, b, out, x_p, shape_b, want in plans:
+        p.__dict__["_pool_link"] = {"reader": b}
+        p._code_out = out
+        b._code_in = True
+        try:
+            ok = _verified(lambda p=p, b=b, x_p=x_p, shape_b=shape_b: b(p(x_p).reshape(shape_b)), want,
+                           lambda p=p: _restore_pool_link(p), reraise=True)
+        except _lib.SlfpError:
+            take_all_back()
+            raise
+        if ok:
+            made.append(p)
+        else:
+            warnings.warn("link_pool_head: a link did not reproduce its reader's output and was taken back", stacklevel=2)
+    if not made:
+        return 0
+    if not _verified(lambda: model(example_input), y0, take_all_back, reraise=True):
+        warnings.warn("link_pool_head: the linked model did not reproduce its output on the example input (a functional op on the "
+                      "pooled tensor?); every link was taken back", stacklevel=2)
+        return 0
+    return len(made)
+
+
+def unlink_pool_head(model):
+    """Undo link_pool_head: every attribute it wrote."""
+    n = 0
+    for m in list(model.modules()):
+        if "_pool_link" in m.__dict__:
+            _restore_pool_link(m)
             n += 1
     return n

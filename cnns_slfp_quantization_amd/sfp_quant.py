@@ -19,6 +19,8 @@ quantize_layerout (SFP<4,4> output quantizer, :105-133) runs on the device as we
 (slfp_quantize_layerout_f32, bit-identical including the reference's XOR quirks) and can be
 fused into the conv epilogue by fusion.fuse_bn_relu; like every quantized op it needs a ROCm tensor.
 """
+import ctypes
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -111,6 +113,46 @@ def hip_maxpool_codes(codes, kernel_size, stride, padding, q_bit, ceil_mode=Fals
             _lib.check(L.slfp_maxpool2d_codes(codes.data_ptr(), y.data_ptr(), n, h, w, c, kh, kw, sh, sw, ph, pw, int(q_bit),
                                               _stream_handle(codes)))
     return y
+
+
+def _avgpool_io(code_out):
+    """slfp_global_avgpool_f32's io struct: float32 out, or the codes of the reader (Ka, q_bit)."""
+    if code_out is None:
+        return _lib.ConvIo(x_codes=0, y_codes=0, y_ka=1.0, y_qbits=8)
+    return _lib.ConvIo(x_codes=0, y_codes=1, y_ka=float(np.float32(code_out[0])), y_qbits=int(code_out[1]))
+
+
+def global_avgpool_supported(x, code_out=None):
+    """Does libslfp_hip have the global average pool kernel for the 4-d tensor `x` as it lies in memory (channels_last, or
+    contiguous NCHW) and this output kind?  slfp_global_avgpool_supported; host only."""
+    if x.dim() != 4 or x.numel() == 0:
+        return False
+    n, c, h, w = x.shape
+    nhwc = x.is_contiguous(memory_format=torch.channels_last) and c % 4 == 0
+    if not nhwc and not x.is_contiguous():
+        return False   # (hip_global_avgpool would copy it)
+    return bool(_lib.load().slfp_global_avgpool_supported(n, h, w, c, _lib.LAYOUT_NHWC if nhwc else _lib.LAYOUT_NCHW,
+                                                          ctypes.byref(_avgpool_io(code_out))))
+
+
+def hip_global_avgpool(x, relu=False, code_out=None):
+    """The mean over H x W of a 4-d ROCm float32 tensor (slfp_global_avgpool_f32), [N, C, 1, 1]: float32, or with code_out =
+    (Ka, q_bit) the uint8 codes slfp_encode_f32 gives that float32 result for the Linear_Q that reads it.  relu: the mean of
+    max(x, 0).  A channels_last `x` is read as NHWC, a contiguous one as NCHW (anything else is made contiguous first); the sum
+    runs in the fixed order of include/slfp.h, so both give the same bits and a row does not depend on the batch."""
+    _require_gpu_f32(x, "slfp global average pool")
+    if x.dim() != 4:
+        raise TypeError("slfp global average pool: expected a 4-d tensor")
+    n, c, h, w = x.shape
+    nhwc = x.is_contiguous(memory_format=torch.channels_last) and c % 4 == 0
+    if not nhwc and not x.is_contiguous():
+        x = x.contiguous()
+    L = _lib.load()
+    y = torch.empty((n, c), dtype=torch.float32 if code_out is None else torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(L.slfp_global_avgpool_f32(x.data_ptr(), y.data_ptr(), n, h, w, c, _lib.LAYOUT_NHWC if nhwc else _lib.LAYOUT_NCHW,
+                                             1 if relu else 0, ctypes.byref(_avgpool_io(code_out)), _stream_handle(x)))
+    return y.view(n, c, 1, 1)
 
 
 def _make_qfn(fmt):

@@ -14,7 +14,8 @@ group's kernel has the CUs.  Splitting INSIDE every layer (fork / join per Conv2
 It pays where the launch path is cheap -- the C ABI called in a loop (bench.py), a hipGraph replay per group: through EAGER
 Python modules the host issues every launch twice and becomes the bottleneck (whole MobileNetV1, linked, batch 256: 175 k
 images/s in two groups vs 212 k in one).  Note that torch's own reductions (adaptive_avg_pool2d) may round differently at
-N / G images than at N: logits can differ in the last bits although every Conv2d_Q output is identical.
+N / G images than at N: logits can differ in the last bits although every Conv2d_Q output is identical, unless
+`fusion.use_device_avgpool` was applied.
 
 The reference has nothing comparable (one CUDA stream, utils/conv2d_func.py:20-25 is called layer by layer on the whole batch)."""
 import torch

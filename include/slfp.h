@@ -414,6 +414,31 @@ int slfp_linear_fwd_fc(const void* x, const void* wprep, const float* bias, void
                        const slfp_conv2d_io* io, int relu, void* workspace, void* stream);
 int slfp_debug_linear_fc_tiles(int n_tiles, int row_tiles);
 
+/* ---- global average pool (csrc/pool_avg.hip) -------------------------------------------------------------------------
+ * The pool between the last convolution and the classifier: nn.AdaptiveAvgPool2d((1, 1)) -> flatten -> Linear_Q
+ * (nets_imgnet/resnet50.py:146-147, 244-245), nn.AdaptiveAvgPool2d(1) -> view(-1, 1024) -> Linear_Q
+ * (nets_cifar/mobilenetv1.py:62-86, 248-272), nn.AvgPool2d(7) on a 7 x 7 map (nets_imgnet/mobilenetv1.py:58) and conv -> ReLU ->
+ * nn.AdaptiveAvgPool2d((1, 1)) (nets_imgnet/squeezenet1_0.py:85).
+ *   y[n, c] = mean over the h * w pixels of x[n, :, :, c],   x float32 in x_layout (SLFP_LAYOUT_NHWC or SLFP_LAYOUT_NCHW).
+ * The summation runs in float32 in ONE fixed order, which is part of this interface:
+ *   p   = row * w + col                        the row-major pixel index, 0 .. h * w - 1
+ *   v_p = relu ? max(x_p, 0) : x_p
+ *   s_j = the sum of v_p over p == j (mod 4), p ascending, each s_j starting from +0.0f        (j = 0, 1, 2, 3)
+ *   y   = ((s_0 + s_1) + (s_2 + s_3)) / (float)(h * w)          IEEE float32 division, not a multiply by a reciprocal
+ * so a row of y is a pure function of one image's values: the same bits whatever n, the grid, the stream or the layout (the two
+ * layouts give the same bits for the same values).  No atomics.
+ *   io->y_codes 0: y is float32 [n, c]
+ *   io->y_codes 1: y is uint8 [n, c] = slfp_encode_f32(that float32 y, io->y_ka, fmt(io->y_qbits) | SLFP_FMT_EXT): what the
+ *                  Linear_Q behind the pool (its Ka, its q_bit) reads with x_codes = 1; signed classes, no ReLU behind the pool
+ * io->x_codes must be 0; relu is 0 or 1.  Supported (slfp_global_avgpool_supported: 1 / 0, host only): h, w >= 1, c >= 1; NHWC
+ * needs c a multiple of 4 and 16-byte aligned x and y; NCHW takes any c and 4-byte alignment; code output needs c a multiple of
+ * 4, y_qbits 8 or 7 and y_ka > 0 with a code table.  Null (SLFP_ERR_BAD_ARG), shape (SLFP_ERR_SHAPE), unsupported
+ * (SLFP_ERR_UNSUPPORTED) and alignment (SLFP_ERR_ALIGNMENT) refusals happen before any device work and leave y untouched; n == 0
+ * returns SLFP_OK.  NaN inputs are outside the code contract, as in slfp_linear_fwd_fc. */
+int slfp_global_avgpool_supported(int64_t n, int64_t h, int64_t w, int64_t c, int x_layout, const slfp_conv2d_io* io);
+int slfp_global_avgpool_f32(const float* x, void* y, int64_t n, int64_t h, int64_t w, int64_t c, int x_layout, int relu,
+                            const slfp_conv2d_io* io, void* stream);
+
 /* ---- self-check ------------------------------------------------------------------------
  * The kernels compute x / scale_div with an FMA correction chain on a host-computed
  * reciprocal instead of the IEEE division macro (csrc/slfp_device.hpp, ScaleDiv).  This
