@@ -40,6 +40,7 @@ SYMBOLS = (
     "slfp_dwpw_codes_supported", "slfp_dwpw_fwd_codes",
     "slfp_linear_fc_supported", "slfp_linear_fc_workspace_bytes", "slfp_linear_fwd_fc", "slfp_debug_linear_fc_tiles",
     "slfp_global_avgpool_supported", "slfp_global_avgpool_f32",
+    "slfp_debug_dw3x3_instance", "slfp_debug_code_relu_mismatches",
 )
 
 
@@ -106,6 +107,8 @@ def load():
         "slfp_conv2d_out_shape": (ci, [dp, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
         "slfp_conv2d_kernel_name": (ctypes.c_char_p, [dp]),
         "slfp_debug_dw3x3_variant": (ctypes.c_char_p, [dp, ci]),
+        "slfp_debug_dw3x3_instance": (ctypes.c_char_p, [dp, ctypes.POINTER(ConvIo), ci, ci, ci]),
+        "slfp_debug_code_relu_mismatches": (ci, [cf, ci, vp, vp]),
         "slfp_debug_dense_variant": (ctypes.c_char_p, [dp, ci]),
         "slfp_debug_pw_variant": (ctypes.c_char_p, [dp, ctypes.POINTER(ConvIo), ci, ci, i64]),
         "slfp_conv2d_wprep_bytes": (sz, [dp]),

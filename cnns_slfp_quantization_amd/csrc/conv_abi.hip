@@ -252,6 +252,7 @@ static const char* family_name(const ConvPlan& p, const slfp_conv2d_desc& d) {
 using namespace slfp;
 
 static const char* pw_variant(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, bool has_res, bool has_res_codes, int64_t y_ld);
+static const char* dw3x3_instance(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, bool has_bias, int post_flags, bool has_post);
 
 extern "C" {
 
@@ -277,6 +278,10 @@ const char* slfp_debug_dw3x3_variant(const slfp_conv2d_desc* d, int has_post) {
     const PostOp post = {has_post ? &one : nullptr, has_post ? &one : nullptr, 0, 0};
     if (dw3x3_rows_applicable(*d, p, nullptr, post)) return "rows";
     return dw3x3_tile_applicable(*d, p, nullptr, post) ? "tile" : "general";
+}
+
+const char* slfp_debug_dw3x3_instance(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int post_flags, int has_post) {
+    return dw3x3_instance(d, io, has_bias != 0, post_flags, has_post != 0);
 }
 
 const char* slfp_debug_dense_variant(const slfp_conv2d_desc* d, int x_codes) {
@@ -471,6 +476,34 @@ static const char* pw_variant(const slfp_conv2d_desc* d, const slfp_conv2d_io* i
         return pw_variant_name(d2, p, false, false, 1.f, kFmtAct8);
     }
     return pw_variant_name(*d, p, false, false, 1.f, kFmtAct8);
+}
+
+// slfp_debug_dw3x3_instance: the route the matching forward entry point takes (refused: "none"), then the launcher's own selection.
+static const char* dw3x3_instance(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, bool has_bias, int post_flags, bool has_post) {
+    ConvPlan p;
+    if (!d || make_plan(d, &p) != SLFP_OK || p.family != kDw3x3) return "none";
+    if ((post_flags & ~(SLFP_POST_RELU | SLFP_POST_LAYEROUT)) != 0) return "none";
+    static const float one = 1.f;   // the selections only ask whether a scale / shift pair is present
+    const float* vec = has_post ? &one : nullptr;
+    if (!io || (!io->x_codes && !io->y_codes)) {   // slfp_conv2d_fwd / slfp_conv2d_fwd_post
+        if ((post_flags & SLFP_POST_LAYEROUT) && !has_post) return "none";
+        const PostOp post{vec, vec, (post_flags & SLFP_POST_RELU) ? 1 : 0, (post_flags & SLFP_POST_LAYEROUT) ? 1 : 0};
+        if (p.repad) {   // on channel-padded copies: the padded descriptor is what launches
+            slfp_conv2d_desc d2;
+            padded_desc(*d, &d2);
+            return dw3x3_instance_name(d2, p, has_bias, post);
+        }
+        return dw3x3_instance_name(*d, p, has_bias, post);
+    }
+    const PostOp post{vec, vec, (post_flags & SLFP_POST_RELU) ? 1 : 0, 0};
+    CodeIo cio{io->x_codes != 0, io->y_codes != 0, io->y_ka, y_fmt_of(io->y_qbits), 0};
+    if (post_flags & SLFP_POST_LAYEROUT) {   // slfp_conv2d_fwd_codes_lut: the layer-output quantizer on codes is the table epilogue
+        if (!has_post || (post_flags & SLFP_POST_RELU) || lut_route(d, io, has_bias, p) != kRouteDwc) return "none";
+        cio.lut = reinterpret_cast<const uint8_t*>(&one);   // dwc_select only asks whether there is a table
+        return dwc_instance_name(*d, p, post, cio);
+    }
+    if (codes_route(d, io, has_bias, post_flags, p) != kRouteDwc) return "none";   // slfp_conv2d_fwd_codes
+    return dwc_instance_name(*d, p, post, cio);
 }
 
 // slfp_debug_layerout_lut_mismatches: every float32 pattern through layerout_bits, its class and back

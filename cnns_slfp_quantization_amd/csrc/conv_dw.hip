@@ -226,11 +226,20 @@ __global__ __launch_bounds__(kDwThreads) void k_dw3x3(const float* __restrict__ 
     }
 }
 
-int launch_dw3x3(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x, const float* wq9c,
-                 const float* bias, const PostOp& post, float* y, hipStream_t stream) {
-    if (dw3x3_rows_applicable(d, plan, bias, post)) return launch_dw3x3_rows(d, plan, x, wq9c, post, y, stream);
-    if (dw3x3_tile_applicable(d, plan, bias, post)) return launch_dw3x3_tile(d, plan, x, wq9c, post, y, stream);
-    DwParams p;
+// Everything launch_dw3x3 decides for k_dw3x3, worked out in ONE place (dw_select): the launcher only dispatches on it and
+// dw3x3_instance_name (slfp_debug_dw3x3_instance) prints it, so the reported string cannot drift from what runs.
+struct DwSel {
+    int s;          // stride: template argument S
+    int cbt, iwt;   // CBT / IWT: 32,16 | 64,9 | 32,15 for the geometry-specialised forms, 0,0 for the generic one
+    int v;          // V: 4 (16-byte lanes) or 2
+    bool tab;       // TAB: threshold-table quantizer (else the long form)
+    bool lo;        // LO: the fused layer-output quantizer
+    bool a8;        // FMT: Act8 (else SFP7)
+    size_t lds;     // dynamic LDS bytes
+};
+
+static int dw_select(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post, DwParams* pp, DwSel* sel) {
+    DwParams& p = *pp;
     p.post = post;
     p.N = (int)d.n; p.H = (int)d.h; p.W = (int)d.w; p.C = (int)d.c_in;
     p.Ho = (int)plan.h_out; p.Wo = (int)plan.w_out;
@@ -271,32 +280,71 @@ int launch_dw3x3(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x
     p.nblocks = (uint32_t)nblocks;
     const EncArgs* tab = act_table(d.ka, plan.fmt_act, kEncF32);
     if (tab) p.enc = *tab;
-    const size_t lds = (tab ? ((kEncEntries * 8 + 15) & ~15) : 64) + (size_t)p.IH * p.IW * p.CB * sizeof(float);
-    if (lds > 64 * 1024) return fail(SLFP_ERR_UNSUPPORTED, "dw3x3: tile needs %zu B of LDS", lds);
-    const bool a8 = plan.fmt_act == kFmtAct8;
+    sel->lds = (tab ? ((kEncEntries * 8 + 15) & ~15) : 64) + (size_t)p.IH * p.IW * p.CB * sizeof(float);
+    if (sel->lds > 64 * 1024) return fail(SLFP_ERR_UNSUPPORTED, "dw3x3: tile needs %zu B of LDS", sel->lds);
+    sel->s = S; sel->v = v2 ? 2 : 4; sel->tab = tab != nullptr; sel->a8 = plan.fmt_act == kFmtAct8;
+    sel->lo = p.post.layerout && p.post.scale;   // fused layer-output quantizer: the generic-geometry instantiations only
+    sel->cbt = sel->iwt = 0;
+    if (!sel->lo) {
+        if (S == 1 && p.CB == 32 && p.IW == 16) { sel->cbt = 32; sel->iwt = 16; }                   // 14x14 tiles (112..14 px layers)
+        else if (!v2 && S == 1 && p.CB == 64 && p.IW == 9) { sel->cbt = 64; sel->iwt = 9; }    // 7x7 images, >= 64 channels
+        else if (!v2 && S == 2 && p.CB == 32 && p.IW == 15) { sel->cbt = 32; sel->iwt = 15; }  // 7x7 output tiles of stride-2 layers
+    }
+    return SLFP_OK;
+}
+
+static const char* dw_general_name(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post) {
+    static thread_local char buf[64];
+    DwParams p;
+    DwSel s;
+    if (dw_select(d, plan, post, &p, &s) != SLFP_OK) return "none";
+    snprintf(buf, sizeof buf, "general/s%d/%s/v%d/%s/%s%s", s.s,
+             s.cbt == 0 ? "gen" : (s.cbt == 64 ? "cb64iw9" : (s.iwt == 16 ? "cb32iw16" : "cb32iw15")), s.v, s.tab ? "tab" : "long",
+             s.a8 ? "act8" : "sfp7", s.lo ? "/lo" : "");
+    return buf;
+}
+
+const char* dw3x3_instance_name(const slfp_conv2d_desc& d, const ConvPlan& plan, bool has_bias, const PostOp& post) {
+    if (plan.family != kDw3x3) return "none";
+    const float* bias = has_bias ? reinterpret_cast<const float*>(16) : nullptr;   // the predicates only ask whether there is one
+    if (dw3x3_rows_applicable(d, plan, bias, post)) return dw3x3_rows_name(d, plan, post);
+    if (dw3x3_tile_applicable(d, plan, bias, post)) return dw3x3_tile_name(d, plan, post);
+    return dw_general_name(d, plan, post);
+}
+
+int launch_dw3x3(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x, const float* wq9c,
+                 const float* bias, const PostOp& post, float* y, hipStream_t stream) {
+    if (dw3x3_rows_applicable(d, plan, bias, post)) return launch_dw3x3_rows(d, plan, x, wq9c, post, y, stream);
+    if (dw3x3_tile_applicable(d, plan, bias, post)) return launch_dw3x3_tile(d, plan, x, wq9c, post, y, stream);
+    DwParams p;
+    DwSel s;
+    const int rc = dw_select(d, plan, post, &p, &s);
+    if (rc != SLFP_OK) return rc;
+    const size_t lds = s.lds;
 #define SLFP_DW_LAUNCH(FMT, SS, CBT, IWT, VV) \
-    do { if (tab) hipLaunchKernelGGL((k_dw3x3<FMT, SS, CBT, IWT, VV, false, true>), dim3(p.nblocks), dim3(kDwThreads), lds, stream, x, wq9c, bias, y, p); \
+    do { if (s.tab) hipLaunchKernelGGL((k_dw3x3<FMT, SS, CBT, IWT, VV, false, true>), dim3(p.nblocks), dim3(kDwThreads), lds, stream, x, wq9c, bias, y, p); \
          else hipLaunchKernelGGL((k_dw3x3<FMT, SS, CBT, IWT, VV>), dim3(p.nblocks), dim3(kDwThreads), lds, stream, x, wq9c, bias, y, p); } while (0)
 #define SLFP_DW_LAUNCH_LO(FMT, SS, VV) \
-    do { if (tab) hipLaunchKernelGGL((k_dw3x3<FMT, SS, 0, 0, VV, true, true>), dim3(p.nblocks), dim3(kDwThreads), lds, stream, x, wq9c, bias, y, p); \
+    do { if (s.tab) hipLaunchKernelGGL((k_dw3x3<FMT, SS, 0, 0, VV, true, true>), dim3(p.nblocks), dim3(kDwThreads), lds, stream, x, wq9c, bias, y, p); \
          else hipLaunchKernelGGL((k_dw3x3<FMT, SS, 0, 0, VV, true>), dim3(p.nblocks), dim3(kDwThreads), lds, stream, x, wq9c, bias, y, p); } while (0)
 #define SLFP_DW_BY_FMT(SS, CBT, IWT, VV) \
-    do { if (a8) SLFP_DW_LAUNCH(kFmtAct8, SS, CBT, IWT, VV); else SLFP_DW_LAUNCH(kFmtSfp7, SS, CBT, IWT, VV); } while (0)
-    if (p.post.layerout && p.post.scale) {   // fused layer-output quantizer: the generic-geometry instantiations only
-        if (a8) { if (S == 1) { if (v2) SLFP_DW_LAUNCH_LO(kFmtAct8, 1, 2); else SLFP_DW_LAUNCH_LO(kFmtAct8, 1, 4); }
-                  else        { if (v2) SLFP_DW_LAUNCH_LO(kFmtAct8, 2, 2); else SLFP_DW_LAUNCH_LO(kFmtAct8, 2, 4); } }
-        else    { if (S == 1) { if (v2) SLFP_DW_LAUNCH_LO(kFmtSfp7, 1, 2); else SLFP_DW_LAUNCH_LO(kFmtSfp7, 1, 4); }
-                  else        { if (v2) SLFP_DW_LAUNCH_LO(kFmtSfp7, 2, 2); else SLFP_DW_LAUNCH_LO(kFmtSfp7, 2, 4); } }
+    do { if (s.a8) SLFP_DW_LAUNCH(kFmtAct8, SS, CBT, IWT, VV); else SLFP_DW_LAUNCH(kFmtSfp7, SS, CBT, IWT, VV); } while (0)
+    const bool v2 = s.v == 2;
+    if (s.lo) {
+        if (s.a8) { if (s.s == 1) { if (v2) SLFP_DW_LAUNCH_LO(kFmtAct8, 1, 2); else SLFP_DW_LAUNCH_LO(kFmtAct8, 1, 4); }
+                    else          { if (v2) SLFP_DW_LAUNCH_LO(kFmtAct8, 2, 2); else SLFP_DW_LAUNCH_LO(kFmtAct8, 2, 4); } }
+        else      { if (s.s == 1) { if (v2) SLFP_DW_LAUNCH_LO(kFmtSfp7, 1, 2); else SLFP_DW_LAUNCH_LO(kFmtSfp7, 1, 4); }
+                    else          { if (v2) SLFP_DW_LAUNCH_LO(kFmtSfp7, 2, 2); else SLFP_DW_LAUNCH_LO(kFmtSfp7, 2, 4); } }
     }
     else if (v2) {
-        if (S == 1 && p.CB == 32 && p.IW == 16) SLFP_DW_BY_FMT(1, 32, 16, 2);
-        else if (S == 1) SLFP_DW_BY_FMT(1, 0, 0, 2);
+        if (s.cbt == 32 && s.iwt == 16) SLFP_DW_BY_FMT(1, 32, 16, 2);
+        else if (s.s == 1) SLFP_DW_BY_FMT(1, 0, 0, 2);
         else SLFP_DW_BY_FMT(2, 0, 0, 2);
     }
-    else if (S == 1 && p.CB == 32 && p.IW == 16) SLFP_DW_BY_FMT(1, 32, 16, 4);      // 14x14 tiles (112..14 px layers)
-    else if (S == 1 && p.CB == 64 && p.IW == 9) SLFP_DW_BY_FMT(1, 64, 9, 4);  // 7x7 images, >= 64 channels
-    else if (S == 2 && p.CB == 32 && p.IW == 15) SLFP_DW_BY_FMT(2, 32, 15, 4); // 7x7 output tiles of stride-2 layers
-    else if (S == 1) SLFP_DW_BY_FMT(1, 0, 0, 4);
+    else if (s.cbt == 32 && s.iwt == 16) SLFP_DW_BY_FMT(1, 32, 16, 4);
+    else if (s.cbt == 64 && s.iwt == 9) SLFP_DW_BY_FMT(1, 64, 9, 4);
+    else if (s.cbt == 32 && s.iwt == 15) SLFP_DW_BY_FMT(2, 32, 15, 4);
+    else if (s.s == 1) SLFP_DW_BY_FMT(1, 0, 0, 4);
     else SLFP_DW_BY_FMT(2, 0, 0, 4);
 #undef SLFP_DW_BY_FMT
 #undef SLFP_DW_LAUNCH_LO

@@ -194,13 +194,24 @@ bool dw3x3_tile_applicable(const slfp_conv2d_desc& d, const ConvPlan& plan, cons
     return act_table(d.ka, plan.fmt_act, kEncF32) != nullptr;
 }
 
+// What launch_dw3x3_tile chooses among k_dw3x3_tile's instances: the launcher dispatches on it, dw3x3_tile_name prints it.
+struct Dw2Sel { int s; bool post; };   // template arguments S (TH = TW = 14 / 7 follow from it) and POST
+static Dw2Sel dw2_select(const slfp_conv2d_desc& d, const PostOp& post) { return Dw2Sel{d.stride_h == 2 ? 2 : 1, post.scale != nullptr}; }
+
+const char* dw3x3_tile_name(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post) {
+    const Dw2Sel s = dw2_select(d, post);
+    if (s.s == 2) return s.post ? "tile/s2/post" : "tile/s2/plain";
+    return s.post ? "tile/s1/post" : "tile/s1/plain";
+}
+
 int launch_dw3x3_tile(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x, const float* wq9c,
                       const PostOp& post, float* y, hipStream_t stream) {
     Dw2Params p;
+    const Dw2Sel sel = dw2_select(d, post);
     p.post = post;
     p.N = (int)d.n; p.H = (int)d.h; p.W = (int)d.w; p.C = (int)d.c_in;
     p.Ho = (int)plan.h_out; p.Wo = (int)plan.w_out;
-    const int S = d.stride_h;
+    const int S = sel.s;
     const int TH = S == 2 ? 7 : 14, TW = TH;
     p.tiles_h = (int)ceil_div(p.Ho, TH);
     p.tiles_w = (int)ceil_div(p.Wo, TW);
@@ -217,7 +228,7 @@ int launch_dw3x3_tile(const slfp_conv2d_desc& d, const ConvPlan& plan, const flo
     }
     p.enc = *act_table(d.ka, plan.fmt_act, kEncF32);
 #define SLFP_DW2(SS, TT) \
-    do { if (post.scale) hipLaunchKernelGGL((k_dw3x3_tile<SS, TT, TT, true>), dim3(p.nblocks), dim3(kDw2Threads), 0, stream, x, wq9c, y, p); \
+    do { if (sel.post) hipLaunchKernelGGL((k_dw3x3_tile<SS, TT, TT, true>), dim3(p.nblocks), dim3(kDw2Threads), 0, stream, x, wq9c, y, p); \
          else hipLaunchKernelGGL((k_dw3x3_tile<SS, TT, TT, false>), dim3(p.nblocks), dim3(kDw2Threads), 0, stream, x, wq9c, y, p); } while (0)
     if (S == 2) SLFP_DW2(2, 7);
     else SLFP_DW2(1, 14);

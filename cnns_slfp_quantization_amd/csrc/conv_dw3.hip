@@ -203,9 +203,18 @@ bool dw3x3_rows_applicable(const slfp_conv2d_desc& d, const ConvPlan& plan, cons
     return (((sw < 0) ? kDwrRule : sw) >> dw_rows_class(plan.h_out, plan.w_out)) & 1;
 }
 
+// What launch_dw3x3_rows chooses among k_dw3x3_rows' instances: the launcher dispatches on it, dw3x3_rows_name prints it.
+struct DwrSel { bool post; };   // template argument POST (TH is kDwrTile)
+static DwrSel dwr_select(const PostOp& post) { return DwrSel{post.scale != nullptr}; }
+
+const char* dw3x3_rows_name(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post) {
+    return dwr_select(post).post ? "rows/post" : "rows/plain";
+}
+
 int launch_dw3x3_rows(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x, const float* wq9c,
                       const PostOp& post, float* y, hipStream_t stream) {
     DwrParams p;
+    const DwrSel sel = dwr_select(post);
     p.post = post;
     p.N = (int)d.n; p.H = (int)d.h; p.W = (int)d.w; p.C = (int)d.c_in;
     p.Ho = (int)plan.h_out; p.Wo = (int)plan.w_out; p.pad = d.pad_h;
@@ -219,7 +228,7 @@ int launch_dw3x3_rows(const slfp_conv2d_desc& d, const ConvPlan& plan, const flo
     p.ka = d.ka; p.kw = d.kw_scale;
     p.nt_out = ((SLFP_NT_DW & 2) && (int64_t)p.N * p.Ho * p.Wo * p.C * 4 >= (switches().dw_nt_min_mb << 20)) ? 1 : 0;
     p.enc = *act_table(d.ka, plan.fmt_act, kEncF32);
-    if (post.scale) hipLaunchKernelGGL((k_dw3x3_rows<kDwrTile, true>), dim3(p.nblocks), dim3(kDwrThreads), 0, stream, x, wq9c, y, p);
+    if (sel.post) hipLaunchKernelGGL((k_dw3x3_rows<kDwrTile, true>), dim3(p.nblocks), dim3(kDwrThreads), 0, stream, x, wq9c, y, p);
     else hipLaunchKernelGGL((k_dw3x3_rows<kDwrTile, false>), dim3(p.nblocks), dim3(kDwrThreads), 0, stream, x, wq9c, y, p);
     return check_launch("slfp dw3x3 (rows) kernel");
 }

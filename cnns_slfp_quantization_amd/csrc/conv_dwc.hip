@@ -174,8 +174,9 @@ __global__ __launch_bounds__(kDwcThreads) void k_dwc(const uint8_t* __restrict__
                     code = enc4_code<true>(make_float4(rr[0], rr[1], rr[2], rr[3]), r1, lo, hi, senc);
                     if (p.fmt_out == kFmtSfp7) code = (code & 0x3F3F3F3Fu) | ((code & 0x80808080u) >> 1);
                 } else {
-                    // the ReLU is the quantizer's: a negative value selects the lowest bin and fails its compare = the zero code
-                    code = enc4_code_relu(make_float4(rr[0], rr[1], rr[2], rr[3]), r1, lo, hi, senc);
+                    // the ReLU is the quantizer's: a negative value selects the lowest bin and fails its compare = the zero code;
+                    // a NaN takes that code too (the float32 form's fmaxf(NaN, 0) == 0), on the encoder's cold branch (NANZERO)
+                    code = enc4_code_relu<true>(make_float4(rr[0], rr[1], rr[2], rr[3]), r1, lo, hi, senc);
                 }
                 __builtin_amdgcn_raw_buffer_store_b32(code, ry, so, 0, 0);
             } else {
@@ -195,16 +196,50 @@ bool dwc_applicable(const slfp_conv2d_desc& d, const ConvPlan& plan, const float
     return in_b < (1ull << 30) && out_b < (1ull << 30);   // offsets: bit 30 / 31 mark an invalid column / row
 }
 
+// What launch_dwc chooses among k_dwc's instances (and the one runtime format word): the launcher dispatches on it, dwc_instance_name
+// (slfp_debug_dw3x3_instance) prints it.
+struct DwcSel {
+    int s;          // S; TH x TW = 7 x 2 (stride 1) / 4 x 1 (stride 2) follow from it
+    int lcs;        // LCS
+    bool yc, post, sgn, lut;   // YC, POST, SIGNED, LUTQ
+    int fmt_in;     // DwcParams::fmt_in (not a template argument: the decode table is filled by it)
+};
+
+static int dwc_select(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post, const CodeIo& io, DwcSel* s) {
+    s->s = d.stride_h == 2 ? 2 : 1;
+    s->lcs = d.c_in >= 128 ? 5 : (d.c_in == 64 ? 4 : 3);
+    s->lut = io.lut != nullptr;
+    if (s->lut && (!io.y_codes || !post.scale))
+        return fail(SLFP_ERR_BAD_ARG, "dw3x3 (codes): the table epilogue needs code output and post_scale / post_shift");
+    s->yc = io.y_codes;
+    s->post = post.scale != nullptr;
+    s->sgn = s->lut || (s->yc && !post.relu);   // float32 output: the ReLU is a runtime flag of the SIGNED = false instance
+    s->fmt_in = plan.fmt_act;
+    return SLFP_OK;
+}
+
+const char* dwc_instance_name(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post, const CodeIo& io) {
+    static thread_local char buf[64];
+    DwcSel s;
+    if (plan.family != kDw3x3 || dwc_select(d, plan, post, io, &s) != SLFP_OK) return "none";
+    snprintf(buf, sizeof buf, "dwc/s%d/lc%d/%s/%s/%s", s.s, s.lcs, s.lut ? "lut" : (!s.yc ? "f32" : (s.sgn ? "yc-signed" : "yc")),
+             s.post ? "post" : "plain", s.fmt_in == kFmtSfp7 ? "sfp7" : "act8");
+    return buf;
+}
+
 // io.y_codes: output codes for a consumer with scale io.y_ka and format io.y_fmt (kFmtAct8 | kFmtSfp7); else float32
 int launch_dwc(const slfp_conv2d_desc& d, const ConvPlan& plan, const uint8_t* x, const float* wq9c, const PostOp& post,
                void* y, const CodeIo& io, hipStream_t stream) {
-    const bool y_codes = io.y_codes;
+    DwcSel sel;
+    const int src = dwc_select(d, plan, post, io, &sel);
+    if (src != SLFP_OK) return src;
+    const bool y_codes = sel.yc;
     DwcParams p;
     p.N = (int)d.n; p.H = (int)d.h; p.W = (int)d.w; p.C = (int)d.c_in;
     p.Ho = (int)plan.h_out; p.Wo = (int)plan.w_out; p.pad = d.pad_h;
-    const int S = d.stride_h;
+    const int S = sel.s;
     const int TH = S == 2 ? 4 : 7, TW = S == 2 ? 1 : 2;
-    const int lcs = p.C >= 128 ? 5 : (p.C == 64 ? 4 : 3);
+    const int lcs = sel.lcs;
     p.cgs = p.C / (4 << lcs);
     p.row_tiles = (int)ceil_div(p.Ho, TH);
     p.col_tiles = (int)ceil_div(p.Wo, TW);
@@ -214,22 +249,21 @@ int launch_dwc(const slfp_conv2d_desc& d, const ConvPlan& plan, const uint8_t* x
     if (ntasks > 0x7FFFFFFF) return fail(SLFP_ERR_UNSUPPORTED, "dw3x3 (codes): grid too large");
     p.ntasks = (uint32_t)ntasks;
     p.nblocks = (uint32_t)nblocks;
-    p.fmt_in = plan.fmt_act;
+    p.fmt_in = sel.fmt_in;
     p.fmt_out = io.y_fmt;
     p.ka = d.ka; p.kw = d.kw_scale;
     p.relu = post.relu;
     p.post_scale = post.scale; p.post_shift = post.shift;
     p.enc.valid = 0;
-    if (io.lut) {
-        if (!y_codes || !post.scale) return fail(SLFP_ERR_BAD_ARG, "dw3x3 (codes): the table epilogue needs code output and post_scale / post_shift");
+    if (sel.lut) {
         enc_carry_ptr(p.enc, io.lut);
     } else if (y_codes) {
         const EncArgs* t = enc_table(io.y_ka, io.y_fmt, kEncCode);
         if (!t->valid) return fail(SLFP_ERR_UNSUPPORTED, "dw3x3 (codes): no code table for the consumer's scale %g", (double)io.y_ka);
         p.enc = *t;
     }
-    const bool has_post = post.scale != nullptr;
-    const bool sgn = !post.relu;
+    const bool has_post = sel.post;
+    const bool sgn = sel.sgn;
 #define SLFP_DWC_L(SS, LL, TT, WW, YY, PP, GG, ...) \
     hipLaunchKernelGGL((k_dwc<SS, LL, TT, WW, YY, PP, GG, ##__VA_ARGS__>), dim3(p.nblocks), dim3(kDwcThreads), 0, stream, x, wq9c, y, p)
 #define SLFP_DWC_P(SS, LL, TT, WW) \
@@ -237,7 +271,7 @@ int launch_dwc(const slfp_conv2d_desc& d, const ConvPlan& plan, const uint8_t* x
                         else { if (sgn) SLFP_DWC_L(SS, LL, TT, WW, true, false, true); else SLFP_DWC_L(SS, LL, TT, WW, true, false, false); } } \
          else { if (has_post) SLFP_DWC_L(SS, LL, TT, WW, false, true, false); else SLFP_DWC_L(SS, LL, TT, WW, false, false, false); } } while (0)
 #define SLFP_DWC_T(SS, LL, TT, WW) \
-    do { if (io.lut) SLFP_DWC_L(SS, LL, TT, WW, true, true, true, true); else SLFP_DWC_P(SS, LL, TT, WW); } while (0)
+    do { if (sel.lut) SLFP_DWC_L(SS, LL, TT, WW, true, true, true, true); else SLFP_DWC_P(SS, LL, TT, WW); } while (0)
 #define SLFP_DWC_S(SS, TT, WW) \
     do { if (lcs == 5) SLFP_DWC_T(SS, 5, TT, WW); else if (lcs == 4) SLFP_DWC_T(SS, 4, TT, WW); else SLFP_DWC_T(SS, 3, TT, WW); } while (0)
     if (S == 2) SLFP_DWC_S(2, 4, 1);

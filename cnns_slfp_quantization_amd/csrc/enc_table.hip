@@ -242,8 +242,9 @@ __global__ __launch_bounds__(256) void k_enc_check(const ScaleDiv sd, const EncA
 
 // ---- exhaustive self-check of the code representation (slfp_codes.hpp): all 2^32 inputs -----------------------------
 // out[0] = #x whose byte from enc4_code_fmt<FMT, true> differs from quant_code<FMT>(x / Ka, ext) -- the byte
-//          slfp_encode_f32(.., fmt | SLFP_FMT_EXT) stores;  out[1] = the same for the unsigned variant (what a producer
-//          with a ReLU epilogue runs) over the inputs it can see: x >= +0 and x == -0;
+//          slfp_encode_f32(.., fmt | SLFP_FMT_EXT) stores;  out[1] = the same for enc4_code_fmt<FMT, false>, the unsigned variant
+//          (its callers apply the sign themselves: code_sign4), over x >= +0 and x == -0.  Neither counter sweeps enc4_code_relu, the
+//          encoder of the ReLU-epilogue producers: that is k_code_relu_check below;
 // out[2] = #codes c (0..255, counted once) whose decode-table entries differ from decode_bits / fp16(16 * decode_bits).
 template <int FMT>
 __global__ __launch_bounds__(256) void k_code_check(const ScaleDiv sd, const EncArgs t, unsigned long long* __restrict__ out) {
@@ -289,6 +290,44 @@ __global__ __launch_bounds__(256) void k_code_check(const ScaleDiv sd, const Enc
     if (bad_s) atomicAdd(out, bad_s);
     if (bad_u) atomicAdd(out + 1, bad_u);
     if (bad_d) atomicAdd(out + 2, bad_d);
+}
+
+// ---- exhaustive self-check of the ReLU-folded code encoder (slfp_codes.hpp: enc4_code_relu): all 2^32 inputs ---------
+// out[0] = #x whose byte from enc4_code_relu(x) differs from quant_code<FMT>(max(x, 0) / Ka, ext): NaN -> 0x00 (what
+//          slfp_encode_f32 gives it), -0, negatives and -inf -> the code of exact zero;
+// out[1] = the same for enc4_code_relu(relu_of_nan4(x)), the NANFIX form, and for enc4_code_relu<true>(x), the same patch on the
+//          encoder's own cold branch (k_dwc): NaN -> the code of exact zero as well; an input either form gets wrong counts once.
+template <int FMT>
+__global__ __launch_bounds__(256) void k_code_relu_check(const ScaleDiv sd, const EncArgs t, unsigned long long* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) uint2 sE[kEncEntries + 1];
+    enc_fill<256>(sE, t);
+    __syncthreads();
+    const unsigned char* tb = reinterpret_cast<const unsigned char*>(sE);
+    unsigned long long bad_r = 0, bad_n = 0;
+    const uint32_t zero_code = quant_code<FMT>(0u, 0u, true);
+    const uint64_t stride = (uint64_t)gridDim.x * 256 * 4;
+    for (uint64_t i = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < (1ull << 32); i += stride) {
+        float4 x;
+        x.x = __uint_as_float((uint32_t)i); x.y = __uint_as_float((uint32_t)i + 1u);
+        x.z = __uint_as_float((uint32_t)i + 2u); x.w = __uint_as_float((uint32_t)i + 3u);
+        const float xs[4] = {x.x, x.y, x.z, x.w};
+        const uint32_t cr = enc4_code_relu(x, t.r1, t.lo, t.hi, tb);
+        const uint32_t cn = enc4_code_relu(relu_of_nan4(x), t.r1, t.lo, t.hi, tb);
+        const uint32_t cz = enc4_code_relu<true>(x, t.r1, t.lo, t.hi, tb);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const uint32_t ux = __float_as_uint(xs[e]);
+            const bool nan = (ux & 0x7FFFFFFFu) > 0x7F800000u;
+            uint32_t ref = zero_code;                                   // -0, negatives, -inf: max(x, 0) == +0
+            if (nan) ref = 0u;
+            else if (ux < 0x80000000u) ref = quant_code<FMT>(__float_as_uint(div_const(xs[e], sd)), ux, true);
+            if (((cr >> (8 * e)) & 0xFFu) != ref) ++bad_r;
+            const uint32_t ref_n = nan ? zero_code : ref;
+            if (((cn >> (8 * e)) & 0xFFu) != ref_n || ((cz >> (8 * e)) & 0xFFu) != ref_n) ++bad_n;
+        }
+    }
+    if (bad_r) atomicAdd(out, bad_r);
+    if (bad_n) atomicAdd(out + 1, bad_n);
 }
 
 // ---- exhaustive self-check of the hi / lo pair (three-pass MFMA mode): all 2^32 inputs -------------------------------
@@ -361,8 +400,26 @@ extern "C" int slfp_enc_table_ok(float scale_div, int fmt) {
     return (enc_table(scale_div, fmt, kEncF32)->valid && enc_table(scale_div, fmt, kEncF16P)->valid) ? 1 : 0;
 }
 
+// The ReLU-folded code encoder (enc4_code_relu: k_dwc, the tile epilogue, the stems, the dense epilogue) over ALL 2^32 float32
+// inputs, plain (out2[0]) and behind relu_of_nan4 (out2[1]); see k_code_relu_check.  Both must be 0.
+extern "C" int slfp_debug_code_relu_mismatches(float scale_div, int fmt, unsigned long long* out2, void* stream) {
+    if (!out2 || !(scale_div > 0.f)) return fail(SLFP_ERR_BAD_ARG, "slfp_debug_code_relu_mismatches: bad argument");
+    if (fmt != SLFP_FMT_ACT8 && fmt != SLFP_FMT_SFP7) return fail(SLFP_ERR_BAD_ARG, "slfp_debug_code_relu_mismatches: fmt must be ACT8 or SFP7");
+    if (!scale_div_ok(scale_div)) return fail(SLFP_ERR_UNSUPPORTED, "scale must be within [1e-30, 1e30]");
+    const EncArgs* t = enc_table(scale_div, fmt, kEncCode);
+    if (!t->valid) return fail(SLFP_ERR_UNSUPPORTED, "no code table for scale %g (one-step-per-bin property not provable)", (double)scale_div);
+    hipStream_t st = as_stream(stream);
+    if (hipMemsetAsync(out2, 0, 2 * sizeof(unsigned long long), st) != hipSuccess) return check_launch("hipMemsetAsync");
+    const ScaleDiv sd = make_scale_div(scale_div);
+    if (fmt == SLFP_FMT_ACT8) hipLaunchKernelGGL((k_code_relu_check<kFmtAct8>), dim3(256 * 16), dim3(256), 0, st, sd, *t, out2);
+    else hipLaunchKernelGGL((k_code_relu_check<kFmtSfp7>), dim3(256 * 16), dim3(256), 0, st, sd, *t, out2);
+    return check_launch("slfp ReLU-folded code encoder self-check kernel");
+}
+
 // The producer side of the 1-byte inter-layer format (csrc/slfp_codes.hpp): sweeps ALL 2^32 float32 inputs and compares
-// the table-driven code with the long form behind slfp_encode_f32(.., fmt | SLFP_FMT_EXT); also checks both decode tables.
+// the table-driven code of enc4_code_fmt<FMT, true> (out3[0]) and enc4_code_fmt<FMT, false> (out3[1], over x >= +0 and -0) with the
+// long form behind slfp_encode_f32(.., fmt | SLFP_FMT_EXT); also checks both decode tables (out3[2]).  enc4_code_relu, the encoder
+// the ReLU-epilogue producers actually run, is a separate function: slfp_debug_code_relu_mismatches sweeps it.
 extern "C" int slfp_debug_code_mismatches(float scale_div, int fmt, unsigned long long* out3, void* stream) {
     if (!out3 || !(scale_div > 0.f)) return fail(SLFP_ERR_BAD_ARG, "slfp_debug_code_mismatches: bad argument");
     if (fmt != SLFP_FMT_ACT8 && fmt != SLFP_FMT_SFP7) return fail(SLFP_ERR_BAD_ARG, "slfp_debug_code_mismatches: fmt must be ACT8 or SFP7");

@@ -150,6 +150,9 @@ __device__ __forceinline__ uint32_t enc4_code(const float4 x, const float r1, co
 // The same for a producer whose epilogue ends in a ReLU, with the ReLU folded into the quantizer: the bin estimate and the
 // compare use x itself instead of |x|, so a negative x (and -0) clamps into the lowest bin and fails its compare = the
 // class of exact zero (0x01) -- exactly the code of max(x, 0).  No v_max, and the two multiplies of a pair are one v_pk_mul.
+// NANZERO: a NaN takes the code of exact zero instead of 0x00 -- enc4_code_relu(relu_of_nan4(x)) with the patch made on the cold
+// branch this function has anyway (k_dwc: nothing is added to the hot path).
+template <bool NANZERO = false>
 __device__ __forceinline__ uint32_t enc4_code_relu(const float4 x, const float r1, const float lo, const float hi,
                                                    const unsigned char* __restrict__ sTab) {
     typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -177,10 +180,11 @@ __device__ __forceinline__ uint32_t enc4_code_relu(const float4 x, const float r
           "v"(x.w), "v"(e3.x), "v"(e3.y)
         : "vcc");
     if (__builtin_expect(enc_has_nan4(x), 0)) {
-        if (x.x != x.x) d &= 0xFFFFFF00u;
-        if (x.y != x.y) d &= 0xFFFF00FFu;
-        if (x.z != x.z) d &= 0xFF00FFFFu;
-        if (x.w != x.w) d &= 0x00FFFFFFu;
+        constexpr uint32_t z = NANZERO ? 0x01u : 0x00u;
+        if (x.x != x.x) d = (d & 0xFFFFFF00u) | z;
+        if (x.y != x.y) d = (d & 0xFFFF00FFu) | (z << 8);
+        if (x.z != x.z) d = (d & 0xFF00FFFFu) | (z << 16);
+        if (x.w != x.w) d = (d & 0x00FFFFFFu) | (z << 24);
     }
     return d;
 }

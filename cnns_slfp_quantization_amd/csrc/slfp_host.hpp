@@ -116,6 +116,12 @@ int launch_dw3x3_tile(const slfp_conv2d_desc& d, const ConvPlan& p, const float*
 bool dw3x3_rows_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, const float* bias, const PostOp& post);
 int launch_dw3x3_rows(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const float* wq9c,
                       const PostOp& post, float* y, hipStream_t stream);
+// which template instance launch_dw3x3 runs for this layer (the rows, tile or general kernel) under the switches read at load,
+// printed from the selection each launcher consumes (slfp_debug_dw3x3_instance; host only; grammar in include/slfp.h).  "none"
+// outside the family or where the launch would be refused; valid until the next call on the same thread.
+const char* dw3x3_instance_name(const slfp_conv2d_desc& d, const ConvPlan& p, bool has_bias, const PostOp& post);
+const char* dw3x3_tile_name(const slfp_conv2d_desc& d, const ConvPlan& p, const PostOp& post);
+const char* dw3x3_rows_name(const slfp_conv2d_desc& d, const ConvPlan& p, const PostOp& post);
 // SLFP_DW_ROWS as the environment gives it (nullptr: unset) -> Switches::dw_rows
 inline int parse_dw_rows(const char* e) {
     if (!e || !*e) return -1;
@@ -173,6 +179,8 @@ int launch_stem_codes(const slfp_conv2d_desc& d, const ConvPlan& p, const float*
 bool dwc_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, const float* bias, int post_flags);
 int launch_dwc(const slfp_conv2d_desc& d, const ConvPlan& p, const uint8_t* x, const float* wq9c, const PostOp& post,
                void* y, const CodeIo& io, hipStream_t stream);
+// the k_dwc instance launch_dwc runs, printed from the selection it consumes (slfp_debug_dw3x3_instance; host only)
+const char* dwc_instance_name(const slfp_conv2d_desc& d, const ConvPlan& p, const PostOp& post, const CodeIo& io);
 int launch_direct(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const float* wq_hwio,
                   const float* bias, const PostOp& post, float* y, hipStream_t stream);
 bool stem_applicable(const slfp_conv2d_desc& d);  // direct family: the small-C_in stem kernel takes it

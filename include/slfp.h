@@ -128,6 +128,34 @@ const char* slfp_debug_dense_variant(const slfp_conv2d_desc* d, int x_codes);
  * (/grid<n>: SLFP_PW_GRID caps the persistent grid.)  It is printed from the selection the launch consumes (DESIGN.md section
  * 19).  Host only: no device is touched.  The pointer stays valid until the next call on the same thread. */
 struct slfp_conv2d_io;   /* defined below */
+/* Which depthwise 3x3 template instance (csrc/conv_dw.hip, conv_dw2.hip, conv_dw3.hip, conv_dwc.hip) the matching forward entry
+ * point launches for this descriptor under the switches read at load; "none" outside the dw3x3 family or where that entry point
+ * refuses the call.  io == NULL (or codes on neither side): slfp_conv2d_fwd / slfp_conv2d_fwd_post; codes on the input side:
+ * slfp_conv2d_fwd_codes, or, with SLFP_POST_LAYEROUT in post_flags, slfp_conv2d_fwd_codes_lut (the layer-output quantizer on codes
+ * is the table epilogue).  has_bias / has_post: a bias / a post_scale + post_shift pair is passed; post_flags: the `relu` argument
+ * (SLFP_POST_RELU | SLFP_POST_LAYEROUT).  One word per template argument the launcher chooses:
+ *   general/s<1|2>/<cb32iw16|cb64iw9|cb32iw15|gen>/v<4|2>/<tab|long>/<act8|sfp7>[/lo]        k_dw3x3<FMT, S, CBT, IWT, V, LO, TAB>
+ *   tile/s<1|2>/<plain|post>                                                                k_dw3x3_tile<S, 14 | 7, 14 | 7, POST>
+ *   rows/<plain|post>                                                                       k_dw3x3_rows<7, POST>
+ *   dwc/s<1|2>/lc<3|4|5>/<f32|yc|yc-signed|lut>/<plain|post>/<act8|sfp7>                     k_dwc<S, LCS, 7 | 4, 2 | 1, YC, POST, SIGNED, LUTQ>
+ * (cb<N>iw<N>: the geometry-specialised channel-group / halo-width forms, gen: the generic one; v<N>: floats per lane; tab / long:
+ * threshold-table / long-form input quantizer; /lo: the fused layer-output quantizer; f32 / yc / yc-signed / lut: float32 out,
+ * codes with the ReLU folded into the quantizer, signed codes, the table epilogue; the last word of a dwc string is the format
+ * of the input codes, a runtime argument of that kernel.)  The string is printed from the selection the launch consumes
+ * (DESIGN.md section 26).  Host only: no device is touched.  The pointer stays valid until the next call on the same thread.
+ *
+ * Arithmetic of the depthwise 3x3 kernels.  All five kernels compute every output element by the same float32 steps, so their
+ * results are equal bit for bit (a NaN equals a NaN) to one another and to the CPU restatement oracle/slfp_oracle.c:
+ * slfp_oracle_dw3x3_f32:
+ *   1. xq = QA(x / Ka) (code input: the decoded code), wq = QW(w / Kw);
+ *   2. acc = +0, or bq = (bias / Ka) / Kw -- two IEEE float32 divisions -- when there is a bias;
+ *   3. nine acc = fmaf(xq, wq, acc) in (kh, kw) order; a padded tap contributes fmaf(+0, wq, acc);
+ *   4. t = (acc * Ka) * Kw, two roundings;
+ *   5. with post_scale / post_shift: t = fmaf(t, scale[c], shift[c]);
+ *   6. with SLFP_POST_LAYEROUT: t = the layer-output quantizer of t (slfp_quantize_layerout_f32);
+ *   7. with SLFP_POST_RELU: t = fmaxf(t, 0) (a NaN gives 0).
+ * Code output is the extended code of QA(t / y_ka) of that float32 t; the table epilogue is the byte table's entry for step 6's class. */
+const char* slfp_debug_dw3x3_instance(const slfp_conv2d_desc* d, const struct slfp_conv2d_io* io, int has_bias, int post_flags, int has_post);
 const char* slfp_debug_pw_variant(const slfp_conv2d_desc* d, const struct slfp_conv2d_io* io, int has_res, int has_res_codes, int64_t y_ld);
 
 /* Bytes of the prepared-weight blob for this layer (device memory the caller owns). */
@@ -360,10 +388,16 @@ int slfp_maxpool2d_codes_ex(const uint8_t* x, uint8_t* y, int64_t n, int64_t h, 
 int slfp_maxpool2d_out_shape(int64_t h, int64_t w, int kh, int kw, int sh, int sw, int ph, int pw, int ceil_mode, int64_t* h_out,
                              int64_t* w_out);
 /* Self-check of the producer side: sweeps ALL 2^32 float32 inputs on the device; out3[0] = inputs whose table-driven code
- * (signed variant) differs from slfp_encode_f32(.., fmt | SLFP_FMT_EXT), out3[1] = the same for the unsigned variant a
- * producer with a ReLU epilogue runs (inputs >= +0 and -0), out3[2] = code bytes whose decode-table entries (float32 and
- * fp16 operand) differ from slfp_decode_f32.  All three must be 0.  fmt: SLFP_FMT_ACT8 or SLFP_FMT_SFP7. */
+ * (enc4_code_fmt, signed variant) differs from slfp_encode_f32(.., fmt | SLFP_FMT_EXT), out3[1] = the same for its unsigned
+ * variant (inputs >= +0 and -0; the callers apply the sign themselves), out3[2] = code bytes whose decode-table entries (float32
+ * and fp16 operand) differ from slfp_decode_f32.  All three must be 0.  fmt: SLFP_FMT_ACT8 or SLFP_FMT_SFP7.  The encoder with the
+ * ReLU folded in, which the ReLU-epilogue producers run, is swept by slfp_debug_code_relu_mismatches. */
 int slfp_debug_code_mismatches(float scale_div, int fmt, unsigned long long* out3, void* stream);
+/* The same sweep for the ReLU-folded encoder (enc4_code_relu: the depthwise code kernel, the tile epilogue, the stems, the dense
+ * epilogue): out2[0] = inputs x whose code differs from the extended code of max(x, 0) -- NaN gives 0x00 as slfp_encode_f32 does;
+ * -0, negatives and -inf give the code of exact zero; out2[1] = the same behind relu_of_nan4 and for the encoder's own NaN-to-zero
+ * form (the forms the kernels run), where a NaN gives the code of exact zero as well.  Both must be 0. */
+int slfp_debug_code_relu_mismatches(float scale_div, int fmt, unsigned long long* out2, void* stream);
 
 /* ---- linear: replaces Linear_Q.forward (utils/conv2d_func.py:60-65) -------------------
  * out = linear(QA(x/Ka), QW(w/Kw), bias/Kw/Ka) * Kw * Ka   (note the Kw-first order).

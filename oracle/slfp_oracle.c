@@ -306,4 +306,71 @@ void slfp_oracle_layerout(const float* x, float* y, size_t n) {
     }
 }
 
+static float layerout_one(float t) {
+    float r;
+    slfp_oracle_layerout(&t, &r, 1);
+    return r;
+}
+
+/*
+ * The depthwise 3x3 family's stated arithmetic (include/slfp.h, "Arithmetic of the depthwise 3x3 kernels"), float32 step for
+ * step, so that a device result can be compared as bits.  NHWC activations, weights [C][3][3] (OIHW with one input channel
+ * per group), stride 1 / 2, square zero padding.  Per output element:
+ *   1. xq = QA(x / Ka) (x_codes: the decoded extended code), wq = QW(w / Kw);
+ *   2. acc = +0, or bq = (bias / Ka) / Kw (two float32 divisions);
+ *   3. nine fmaf(xq, wq, acc) in (kh, kw) order; a padded tap is fmaf(+0, wq, acc);
+ *   4. t = (acc * Ka) * Kw;
+ *   5. scale / shift given: t = fmaf(t, scale[c], shift[c]);
+ *   6. layerout: t = the layer-output quantizer (slfp_oracle_layerout);
+ *   7. relu: t = max(t, +0) with max(NaN, 0) = 0 and max(-0, +0) = +0.
+ * Compiled with -ffp-contract=off: no product below is fused that is not written as fmaf.  Returns 0, or -1 on bad arguments.
+ */
+int slfp_oracle_dw3x3_f32(const void* x, int x_codes, int64_t N, int64_t H, int64_t W, int64_t C, const float* w,
+                          const float* bias, int stride, int pad, float Ka, float Kw, int qbits, const float* scale,
+                          const float* shift, int layerout, int relu, float* y) {
+    if ((qbits != 8 && qbits != 7) || (stride != 1 && stride != 2) || pad < 0 || (scale == NULL) != (shift == NULL)) return -1;
+    const int64_t Ho = (H + 2 * pad - 3) / stride + 1, Wo = (W + 2 * pad - 3) / stride + 1;
+    if (H + 2 * pad < 3 || W + 2 * pad < 3) return -1;
+    const int fa = qbits == 8 ? SLFP_FMT_ACT8 : SLFP_FMT_SFP7, fw = qbits == 8 ? SLFP_FMT_W8 : SLFP_FMT_SFP7;
+#pragma omp parallel for collapse(2) schedule(static)
+    for (int64_t n = 0; n < N; ++n) {
+        for (int64_t ho = 0; ho < Ho; ++ho) {
+            for (int64_t wo = 0; wo < Wo; ++wo) {
+                for (int64_t c = 0; c < C; ++c) {
+                    volatile float acc = 0.0f;
+                    if (bias) {
+                        volatile float b1 = bias[c] / Ka;
+                        acc = b1 / Kw;
+                    }
+                    for (int kh = 0; kh < 3; ++kh) {
+                        for (int kw = 0; kw < 3; ++kw) {
+                            const int64_t hi = ho * stride - pad + kh, wi = wo * stride - pad + kw;
+                            float xq = 0.0f;
+                            if (hi >= 0 && hi < H && wi >= 0 && wi < W) {
+                                const size_t at = (size_t)(((n * H + hi) * W + wi) * C + c);
+                                if (x_codes) {
+                                    xq = decode_one(((const uint8_t*)x)[at], fa | SLFP_FMT_EXT);
+                                } else {
+                                    volatile float q = ((const float*)x)[at] / Ka;
+                                    xq = u2f(quant_one(q, fa).value_bits);
+                                }
+                            }
+                            volatile float qw = w[c * 9 + kh * 3 + kw] / Kw;
+                            const float wq = u2f(quant_one(qw, fw).value_bits);
+                            acc = fmaf(xq, wq, acc);
+                        }
+                    }
+                    volatile float t = acc * Ka;
+                    t = t * Kw;
+                    if (scale) t = fmaf(t, scale[c], shift[c]);
+                    if (layerout) t = layerout_one(t);
+                    if (relu) t = t > 0.0f ? t : 0.0f;
+                    y[(size_t)(((n * Ho + ho) * Wo + wo) * C + c)] = t;
+                }
+            }
+        }
+    }
+    return 0;
+}
+
 int slfp_oracle_version(void) { return 1; }

@@ -49,6 +49,9 @@ def lib():
         L.slfp_oracle_linear.argtypes = [fp, i64, i64, fp, i64, fp, ctypes.c_float,
                                          ctypes.c_float, ci, fp, fp]
         L.slfp_oracle_linear.restype = ci
+        L.slfp_oracle_dw3x3_f32.argtypes = [ctypes.c_void_p, ci, i64, i64, i64, i64, fp, fp, ci, ci, ctypes.c_float, ctypes.c_float,
+                                            ci, fp, fp, ci, ci, fp]
+        L.slfp_oracle_dw3x3_f32.restype = ci
         _lib = L
     return _lib
 
@@ -116,6 +119,23 @@ def conv2d(x, w, bias, stride, padding, dilation, groups, Ka, Kw, qbits, want_q=
     if rc != 0:
         raise ValueError("slfp_oracle_conv2d: bad arguments")
     return (y, xq, wq) if want_q else y
+
+
+def dw3x3_f32(x, w, bias, stride, pad, Ka, Kw, qbits, scale=None, shift=None, layerout=False, relu=False):
+    """The depthwise 3x3 family's stated arithmetic (include/slfp.h), float32 step for step: to be compared as bits.
+    x: NHWC float32, or NHWC uint8 extended codes of QA(x / Ka); w: [C, 1, 3, 3] or [C, 3, 3]; returns NHWC float32."""
+    codes = x.dtype == np.uint8
+    x = np.ascontiguousarray(x) if codes else _f32(x)
+    N, H, W, C = x.shape
+    w = _f32(w).reshape(C, 9)
+    b, sc, sh = (_f32(v) if v is not None else None for v in (bias, scale, shift))
+    Ho, Wo = (H + 2 * pad - 3) // stride + 1, (W + 2 * pad - 3) // stride + 1
+    y = np.empty((N, Ho, Wo, C), dtype=np.float32)
+    rc = lib().slfp_oracle_dw3x3_f32(x.ctypes.data, int(codes), N, H, W, C, _p(w), _p(b), int(stride), int(pad), np.float32(Ka),
+                                     np.float32(Kw), qbits, _p(sc), _p(sh), int(bool(layerout)), int(bool(relu)), _p(y))
+    if rc != 0:
+        raise ValueError("slfp_oracle_dw3x3_f32: bad arguments")
+    return y
 
 
 def linear(x, w, bias, Ka, Kw, qbits):

@@ -134,6 +134,20 @@ def test_code_tables_equal_long_form_for_all_2_32_inputs(lib, dev):
             assert out.tolist() == [0, 0, 0], (fmt, k, out.tolist())
 
 
+def test_relu_folded_code_encoder_equals_long_form_for_all_2_32_inputs(lib, dev):
+    """enc4_code_relu, the encoder every ReLU-epilogue code producer runs (a function of its own: no fabs, a packed multiply, a compare
+    that relies on negatives failing), plain and behind relu_of_nan4, vs the long form of max(x, 0): every float32 pattern, on the
+    device, at the scales of the test above."""
+    L = lib.load()
+    scales = [1.0, 0.171, 15.5 / 3.0, 2.0 ** -7, 0.4277248690205236, 1e-3, 37.25]
+    out = torch.zeros(2, dtype=torch.int64, device=dev)
+    for fmt in (lib.FMT_ACT8, lib.FMT_SFP7):
+        for k in scales:
+            lib.check(L.slfp_debug_code_relu_mismatches(float(np.float32(k)), fmt, out.data_ptr(), _stream()))
+            torch.cuda.synchronize()
+            assert out.tolist() == [0, 0], (fmt, k, out.tolist())
+
+
 def _mobilenet_specs():
     from cnns_slfp_quantization_amd import layer_specs
     return layer_specs.conv_layers("mobilenetv1_imagenet224")
