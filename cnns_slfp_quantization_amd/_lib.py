@@ -41,6 +41,7 @@ SYMBOLS = (
     "slfp_linear_fc_supported", "slfp_linear_fc_workspace_bytes", "slfp_linear_fwd_fc", "slfp_debug_linear_fc_tiles",
     "slfp_global_avgpool_supported", "slfp_global_avgpool_f32",
     "slfp_debug_dw3x3_instance", "slfp_debug_code_relu_mismatches",
+    "slfp_bn_train_supported", "slfp_bn_train_workspace_bytes", "slfp_bn_train_fwd", "slfp_bn_train_bwd", "slfp_debug_bn_split",
 )
 
 
@@ -168,6 +169,11 @@ def load():
         "slfp_debug_linear_fc_tiles": (ci, [ci, ci]),
         "slfp_global_avgpool_supported": (ci, [i64, i64, i64, i64, ci, ctypes.POINTER(ConvIo)]),
         "slfp_global_avgpool_f32": (ci, [vp, vp, i64, i64, i64, i64, ci, ci, ctypes.POINTER(ConvIo), vp]),
+        "slfp_bn_train_supported": (ci, [i64, i64, i64, i64, ci]),
+        "slfp_bn_train_workspace_bytes": (sz, [i64, i64, i64, i64]),
+        "slfp_bn_train_fwd": (ci, [vp, vp, vp, vp, vp, cf, cf, ci, vp, vp, vp, i64, i64, i64, i64, ci, vp, sz, vp]),
+        "slfp_bn_train_bwd": (ci, [vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, i64, i64, i64, i64, ci, vp, sz, vp]),
+        "slfp_debug_bn_split": (ci, [i64, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
     }
     assert set(sigs) == set(SYMBOLS)
     for name, (res, args) in sigs.items():

@@ -37,6 +37,8 @@ undo function restores exactly that state; "also undone by" = the other undo fun
                                                                       a ReLU in front -> FoldedReLU (pool._relu)
   link_pool_head(model, x)         use_device_avgpool; before         pool: _code_out, _pool_link; Linear_Q:        unlink_pool_head /
                                    link_head                          _code_in                                      restore_avgpool
+  use_device_bn_train(model)       -- (a TRAINING pass: before or     nn.BatchNorm2d -> TrainBatchNorm2d, a ReLU    restore_bn_train
+                                   after model.train())               behind it -> FoldedReLU (bn._relu)
 
 The passes that take an example input share one forward trace (`_Trace`), one rule for "the same tensor" (`_Trace.same`), one
 eligibility predicate (`_code_eligible`), one record of wrapped children (`_wrap_children` / `_unwrap_children`) and one
@@ -1747,7 +1749,7 @@ def restore_avgpool(model):
             if isinstance(child, GlobalAvgPool2d):
                 parent._modules[name] = child.mod
                 n += 1
-            elif isinstance(child, FoldedReLU):
+            elif isinstance(child, FoldedReLU) and not getattr(child, "_bn_train", False):   # (use_device_bn_train's stay)
                 parent._modules[name] = child.relu
     return n
 
@@ -1842,4 +1844,119 @@ def unlink_pool_head(model):
         if "_pool_link" in m.__dict__:
             _restore_pool_link(m)
             n += 1
+    return n
+
+
+# ------------------------------------------------------------------ training-mode BatchNorm2d (+ReLU) on the device kernels
+_BN_NAMES = ("running_mean", "running_var", "num_batches_tracked")
+
+
+class TrainBatchNorm2d(nn.Module):
+    """An affine nn.BatchNorm2d (momentum not None) whose training-mode forward and backward run on libslfp_hip's kernels
+    (slfp_bn_train_fwd / slfp_bn_train_bwd), with the nn.ReLU behind it folded in (`_relu`).  It registers the
+    SAME Parameter and buffer objects under the same names, so state-dict keys do not change and an optimizer built before the swap
+    keeps working; the original module is kept outside _modules (`_bn`).  Deliberately not a subclass of nn.BatchNorm2d: the
+    eval-mode passes (fuse_bn_relu, fuse_named_bn) match by isinstance and so never fold a BN whose ReLU lives inside it.
+    The kernels run in training mode on a ROCm float32 4-d channels_last tensor that slfp_bn_train_supported accepts and that
+    has at least `min_elements` elements (None: batchnorm.MIN_ELEMENTS, below which the stock modules measured no slower); eval
+    mode, CPU tensors, autocast, other dtypes or layouts, smaller tensors and a module without running-statistics buffers go to
+    F.batch_norm with the same buffers (then relu, if folded), which is what the stock modules compute.  The output is saved
+    for the backward only with a folded ReLU; without one it may be changed in place behind the module (`out += identity`, a
+    shared in-place ReLU), as behind the stock module.
+      _last_kernel   "bn_train[+relu]", or "aten" """
+    _version = 2   # nn.BatchNorm2d's state-dict version (num_batches_tracked)
+
+    def __init__(self, bn, min_elements=None):
+        super().__init__()
+        object.__setattr__(self, "_bn", bn)
+        self.min_elements = min_elements
+        self.training = bn.training
+        self.num_features, self.eps, self.momentum = bn.num_features, bn.eps, bn.momentum
+        self.affine, self.track_running_stats = bn.affine, bn.track_running_stats
+        self.register_parameter("weight", bn.weight)
+        self.register_parameter("bias", bn.bias)
+        for name in _BN_NAMES:
+            self.register_buffer(name, getattr(bn, name))
+        self._relu = False
+        self._last_kernel = None
+
+    def extra_repr(self):
+        return f"{self.num_features}, eps={self.eps}, momentum={self.momentum}, relu={self._relu}"
+
+    def forward(self, x):
+        from .batchnorm import hip_bn_train, bn_train_supported
+        if x.dim() != 4:
+            raise ValueError(f"expected 4D input (got {x.dim()}D input)")
+        if self.training and self.track_running_stats and self.num_batches_tracked is not None:
+            self.num_batches_tracked.add_(1)
+        if (self.training and self.running_mean is not None and self.running_var is not None and x.is_cuda
+                and x.dtype == torch.float32 and self.weight.dtype == torch.float32 and not torch.is_autocast_enabled()
+                and bn_train_supported(x, self.min_elements)):
+            self._last_kernel = "bn_train+relu" if self._relu else "bn_train"
+            return hip_bn_train.apply(x, self.weight, self.bias, self.running_mean, self.running_var, self.momentum, self.eps,
+                                      self._relu)
+        self._last_kernel = "aten"
+        stats = self.training or (self.running_mean is None and self.running_var is None)
+        keep = not self.training or self.track_running_stats
+        y = torch.nn.functional.batch_norm(x, self.running_mean if keep else None, self.running_var if keep else None, self.weight,
+                                           self.bias, stats, self.momentum, self.eps)
+        return torch.relu(y) if self._relu else y
+
+
+def _bn_train_candidate(m):
+    return type(m) is nn.BatchNorm2d and m.affine and m.momentum is not None
+
+
+def use_device_bn_train(model, min_elements=None):
+    """Run the training-mode BatchNorm2d modules of `model` on libslfp_hip's kernels: every affine nn.BatchNorm2d with a momentum
+    gets a TrainBatchNorm2d in its slot(s).  Where the module behind it in the same nn.Sequential is a plain nn.ReLU (in place or
+    not) and both are held in exactly one slot, the ReLU is folded into the kernels (`_relu`; its slot becomes FoldedReLU).  A
+    hand-wired BN (ResNet-50's bn1..3, whose ReLU module is shared) is swapped without a ReLU, and a layerout_quantize_func
+    between BN and ReLU keeps the ReLU out.  Opt-in; eval mode and everything the kernels do not take run what the stock
+    modules run, and so do tensors of fewer than `min_elements` elements (None: batchnorm.MIN_ELEMENTS, the measured rule of
+    DESIGN section 27; 0: every size).  Returns the number of modules swapped; restore_bn_train undoes them."""
+    todo = [(m, _slots_of(model, m)) for m in model.modules() if _bn_train_candidate(m)]
+    done = 0
+    for bn, slots in todo:
+        if not slots:   # `model` itself
+            continue
+        relu = None
+        if len(slots) == 1 and isinstance(slots[0][0], nn.Sequential):
+            kids = list(slots[0][0]._modules.values())
+            i = next(k for k, kid in enumerate(kids) if kid is bn)
+            if i + 1 < len(kids) and type(kids[i + 1]) is nn.ReLU and len(_slots_of(model, kids[i + 1])) == 1:
+                relu = kids[i + 1]
+        wrap = TrainBatchNorm2d(bn, min_elements)
+        wrap._relu = relu is not None
+        for parent, name in slots:
+            parent._modules[name] = wrap
+        if relu is not None:
+            folded = FoldedReLU(relu)
+            folded._bn_train = True
+            for parent, name in _slots_of(model, relu):
+                parent._modules[name] = folded
+        done += 1
+    return done
+
+
+def restore_bn_train(model):
+    """Undo use_device_bn_train: every slot gets its original module back; the originals are pointed at the current parameters
+    and buffers (the model may have been moved or cast in between) and take the wrapper's training flag."""
+    n = 0
+    seen = set()
+    for parent in list(model.modules()):
+        for name, child in list(parent._modules.items()):
+            if isinstance(child, TrainBatchNorm2d):
+                bn = child._bn
+                if id(child) not in seen:
+                    seen.add(id(child))
+                    n += 1
+                    for key in ("weight", "bias"):
+                        bn._parameters[key] = child._parameters[key]
+                    for key in _BN_NAMES:
+                        bn._buffers[key] = child._buffers[key]
+                    bn.training = child.training
+                parent._modules[name] = bn
+            elif isinstance(child, FoldedReLU) and getattr(child, "_bn_train", False):
+                parent._modules[name] = child.relu
     return n

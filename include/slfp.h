@@ -473,6 +473,59 @@ int slfp_global_avgpool_supported(int64_t n, int64_t h, int64_t w, int64_t c, in
 int slfp_global_avgpool_f32(const float* x, void* y, int64_t n, int64_t h, int64_t w, int64_t c, int x_layout, int relu,
                             const slfp_conv2d_io* io, void* stream);
 
+/* ---- training-mode BatchNorm2d (+ReLU), forward and backward (csrc/bn_train.hip) ---------------------------------------
+ * The nn.BatchNorm2d behind every Conv2d_Q of the training nets and the nn.ReLU(inplace=True) that mostly follows it
+ * (nets_cifar/mobilenetv1.py:30-45, nets_imgnet/mobilenetv1.py:24-41), in training mode: batch statistics, the running
+ * statistics' update, and the gradients.  float32, x_layout SLFP_LAYOUT_NHWC only: x, y, gy, gx are [M][c] with M = n * h * w
+ * rows; any c >= 1 (c % 4 == 0: 16-byte accesses; otherwise 4-byte ones).  Contiguous NCHW is not built.
+ * No atomics.  Every result is a pure function of the inputs and of (M, c); two calls give the same bits.  The summation
+ * contract (every operation float32 and rounded on its own unless float64 is named):
+ *   split      slfp_debug_bn_split(M, c) cuts the rows into S <= 1024 slabs of R rows, R (S - 1) < M <= R S, the last one
+ *              ragged.  With V = 4 if c % 4 == 0 else 1, TX = the power of two >= min(c / V, 64) and TY = 256 / TX, lane ty
+ *              of a slab that begins at row r0 owns rows r0 + ty, r0 + ty + TY, ...
+ *   statistics k = x[r0], the slab's first row.  Per lane, from +0.0f, rows ascending:  d = x - k;  s1 = s1 + d;
+ *              s2 = s2 + d * d.  The lanes' partials are added ty = 0, 1, ..., TY - 1: one (count, k, s1, s2) per (slab, channel).
+ *              (The shift by k keeps the variance where |mean| >> sigma, which a plain E[x^2] - E[x]^2 loses.)
+ *   finalize   in float64, per slab  mean_b = k + s1 / n_b,  M2_b = s2 - s1 * s1 / n_b,  then Chan's formula in slab order
+ *              with n_a rows in front:  n = n_a + n_b;  delta = mean_b - mean;  mean = mean + delta * (n_b / n);
+ *              M2 = (M2 + M2_b) + (delta * delta) * (n_a * n_b / n).   var = M2 / M (biased), or 0 where rounding left it below 0.
+ *              save_mean = f32(mean);  save_invstd = f32(1 / sqrt(var + eps)), computed in float64 and rounded once;
+ *              lo = f32(mean - save_mean), the part of the mean that float32 cannot hold (kept in the workspace).
+ *              running_mean = f32((1 - momentum) * running_mean + momentum * mean) and running_var = f32((1 - momentum) *
+ *              running_var + momentum * (var * M / (M - 1))) in float64, in place; both NULL: no update.
+ *   apply      sc = save_invstd * gamma;  y = (((x - save_mean) - lo) * sc) + beta;  relu: y = y < 0 ? 0 : y  (a NaN stays a
+ *              NaN).  x - save_mean is exact for x within a factor 2 of the mean, so y keeps float32 accuracy relative to the
+ *              centred value where |mean| >> sigma.
+ *   backward   g = relu ? (y > 0 ? gy : 0) : gy  -- the mask is read from the forward's own output y, never recomputed from x.
+ *              Per lane, from +0.0f, rows ascending:  d = x - save_mean;  sg = sg + g;  sx = sx + g * (d * save_invstd);
+ *              sd = sd + d;  lanes added as above; the slabs' sums are added in slab order in float64 to SG, SX, SD.
+ *              lo = SD / M is what the float32 save_mean lost of the mean;  SX = SX - (lo * save_invstd) * SG, the sum of g * xh
+ *              for xh = ((x - save_mean) - lo) * save_invstd.   gbeta = f32(SG),  ggamma = f32(SX),  mb = f32(SG / M),
+ *              mg = f32(SX / M).   a = gamma * save_invstd;  gx = a * ((g - mb) - (xh * mg))  with lo rounded to float32.
+ *              ggamma and gbeta may be NULL (not needed); the sums are computed all the same, gx needs them.
+ * relu is 0 or 1; with relu == 0 the backward does not read y (it must still be a valid pointer).  y may not alias x, gx neither
+ * x nor y.  workspace: slfp_bn_train_workspace_bytes(n, h, w, c) bytes, 16-byte aligned, the same for both directions; its
+ * contents need not survive from the forward to the backward.  Supported (slfp_bn_train_supported: 1 / 0, host only): NHWC,
+ * h, w, c >= 1, M < 2^31, c <= 2^21, and M != 1 -- one value per channel has no variance ("Expected more than 1 value per
+ * channel").  Refusals happen before any device work and leave the outputs untouched: null pointers, a bad layout enum or relu
+ * (SLFP_ERR_BAD_ARG), bad geometry (SLFP_ERR_SHAPE), NCHW or M == 1 (SLFP_ERR_UNSUPPORTED), pointers not aligned to 16 bytes
+ * (c % 4 == 0) or 4 bytes (SLFP_ERR_ALIGNMENT), a workspace that is NULL, misaligned or smaller than required
+ * (SLFP_ERR_BAD_ARG, as the conv workspace).  n == 0 returns SLFP_OK.
+ * slfp_bn_train_supported answers what the kernels can run, not what is worth running: measured against MIOpen's BatchNorm and
+ * ATen's ReLU (profiles/bn_train_bench.json), forward + backward of tensors of fewer than about 16 M elements was not reliably
+ * faster, and below 3.2 M elements slower; a caller of this interface gets 1 for those shapes all the same and applies a size rule
+ * of its own, as the Python module does (batchnorm.MIN_ELEMENTS). */
+int slfp_bn_train_supported(int64_t n, int64_t h, int64_t w, int64_t c, int x_layout);
+size_t slfp_bn_train_workspace_bytes(int64_t n, int64_t h, int64_t w, int64_t c);
+int slfp_bn_train_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                      float momentum, float eps, int relu, float* y, float* save_mean, float* save_invstd, int64_t n, int64_t h,
+                      int64_t w, int64_t c, int x_layout, void* workspace, size_t ws_bytes, void* stream);
+int slfp_bn_train_bwd(const float* x, const float* y, const float* gy, const float* gamma, const float* save_mean,
+                      const float* save_invstd, int relu, float* gx, float* ggamma, float* gbeta, int64_t n, int64_t h, int64_t w,
+                      int64_t c, int x_layout, void* workspace, size_t ws_bytes, void* stream);
+/* host only: the split above for M = m rows of c channels (SLFP_ERR_SHAPE: m < 1 or c < 1 or beyond the supported range) */
+int slfp_debug_bn_split(int64_t m, int64_t c, int64_t* rows_per_slab, int64_t* slabs);
+
 /* ---- self-check ------------------------------------------------------------------------
  * The kernels compute x / scale_div with an FMA correction chain on a host-computed
  * reciprocal instead of the IEEE division macro (csrc/slfp_device.hpp, ScaleDiv).  This
