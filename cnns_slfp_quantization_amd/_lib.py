@@ -42,6 +42,7 @@ SYMBOLS = (
     "slfp_global_avgpool_supported", "slfp_global_avgpool_f32",
     "slfp_debug_dw3x3_instance", "slfp_debug_code_relu_mismatches",
     "slfp_bn_train_supported", "slfp_bn_train_workspace_bytes", "slfp_bn_train_fwd", "slfp_bn_train_bwd", "slfp_debug_bn_split",
+    "slfp_debug_dwpw_instance",
 )
 
 
@@ -174,6 +175,7 @@ def load():
         "slfp_bn_train_fwd": (ci, [vp, vp, vp, vp, vp, cf, cf, ci, vp, vp, vp, i64, i64, i64, i64, ci, vp, sz, vp]),
         "slfp_bn_train_bwd": (ci, [vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, i64, i64, i64, i64, ci, vp, sz, vp]),
         "slfp_debug_bn_split": (ci, [i64, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
+        "slfp_debug_dwpw_instance": (ctypes.c_char_p, [dp, dp, ctypes.POINTER(ConvIo), ci, ci, ci]),
     }
     assert set(sigs) == set(SYMBOLS)
     for name, (res, args) in sigs.items():

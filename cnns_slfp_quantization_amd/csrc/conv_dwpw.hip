@@ -283,28 +283,39 @@ static size_t dwpw_lds(int S, int KS, int NT) {
            (size_t)3 * NT * 16 * 4;
 }
 
+// What slfp_dwpw_fwd chooses among k_dwpw's instances; slfp_dwpw_supported is this function's answer.
+bool dwpw_select(const slfp_conv2d_desc* dw, const slfp_conv2d_desc* pw, DwPwSel* s) {
+    if (!dw || !pw || long_encode_forced()) return false;
+    ConvPlan p1, p2;
+    if (make_plan(dw, &p1) != SLFP_OK || make_plan(pw, &p2) != SLFP_OK) return false;
+    if (p1.family != kDw3x3 || p2.family != kPointwise || p1.repad || p2.repad || p2.passes != 1) return false;
+    if (pw->n != dw->n || pw->h != p1.h_out || pw->w != p1.w_out) return false;
+    int ks, nt;
+    if (!dwpw_shape(*dw, *pw, &ks, &nt)) return false;
+    if (!dwpw_instance_built(dw->stride_h, ks, nt)) return false;
+    if (dwpw_lds(dw->stride_h, ks, nt) > 160 * 1024) return false;
+    if (!act_table(dw->ka, p1.fmt_act, kEncF32) || !act_table(pw->ka, p2.fmt_act, kEncF16P)) return false;
+    s->s = dw->stride_h; s->ks = ks; s->nt = nt;
+    s->fmt_in = p1.fmt_act; s->yc = false;   // not k_dwpw's: float32 in and out
+    return true;
+}
+
 }  // namespace slfp
 
 using namespace slfp;
 
 extern "C" int slfp_dwpw_supported(const slfp_conv2d_desc* dw, const slfp_conv2d_desc* pw) {
-    if (!dw || !pw || long_encode_forced()) return 0;
-    ConvPlan p1, p2;
-    if (make_plan(dw, &p1) != SLFP_OK || make_plan(pw, &p2) != SLFP_OK) return 0;
-    if (p1.family != kDw3x3 || p2.family != kPointwise || p1.repad || p2.repad || p2.passes != 1) return 0;
-    if (pw->n != dw->n || pw->h != p1.h_out || pw->w != p1.w_out) return 0;
-    int ks, nt;
-    if (!dwpw_shape(*dw, *pw, &ks, &nt)) return 0;
-    if (dwpw_lds(dw->stride_h, ks, nt) > 160 * 1024) return 0;
-    if (!act_table(dw->ka, p1.fmt_act, kEncF32) || !act_table(pw->ka, p2.fmt_act, kEncF16P)) return 0;
-    return 1;
+    DwPwSel sel;
+    return dwpw_select(dw, pw, &sel) ? 1 : 0;
 }
 
 extern "C" int slfp_dwpw_fwd(const slfp_conv2d_desc* dw, const slfp_conv2d_desc* pw, const float* x, const void* wprep_dw,
                              const float* post1_scale, const float* post1_shift, int relu1, const void* wprep_pw,
                              const float* bias_pw, const float* post2_scale, const float* post2_shift, int relu2, float* y,
                              void* stream) {
-    if (!slfp_dwpw_supported(dw, pw)) return fail(SLFP_ERR_UNSUPPORTED, "slfp_dwpw_fwd: this pair of layers is not fusable (slfp_dwpw_supported)");
+    if ((relu1 & ~1) != 0 || (relu2 & ~1) != 0) return fail(SLFP_ERR_BAD_ARG, "slfp_dwpw_fwd: relu1 / relu2 are 0 or 1");
+    DwPwSel sel;
+    if (!dwpw_select(dw, pw, &sel)) return fail(SLFP_ERR_UNSUPPORTED, "slfp_dwpw_fwd: this pair of layers is not fusable (slfp_dwpw_supported)");
     if (!x || !wprep_dw || !wprep_pw || !y || !post1_scale || !post1_shift)
         return fail(SLFP_ERR_BAD_ARG, "slfp_dwpw_fwd: null pointer (the depthwise layer's folded BatchNorm is required)");
     if ((post2_scale == nullptr) != (post2_shift == nullptr)) return fail(SLFP_ERR_BAD_ARG, "slfp_dwpw_fwd: post2_scale and post2_shift go together");
@@ -313,16 +324,15 @@ extern "C" int slfp_dwpw_fwd(const slfp_conv2d_desc* dw, const slfp_conv2d_desc*
     ConvPlan p1, p2;
     make_plan(dw, &p1);
     make_plan(pw, &p2);
-    int ks, nt;
-    dwpw_shape(*dw, *pw, &ks, &nt);
+    const int ks = sel.ks, nt = sel.nt;
     DwPwParams p;
     p.x = x; p.wdw = reinterpret_cast<const float*>(wprep_dw); p.sc1 = post1_scale; p.sh1 = post1_shift;
     p.wpw = reinterpret_cast<const _Float16*>(wprep_pw); p.bias2 = bias_pw; p.sc2 = post2_scale; p.sh2 = post2_shift; p.y = y;
     p.N = (int)dw->n; p.H = (int)dw->h; p.W = (int)dw->w; p.C = (int)dw->c_in; p.Ho = (int)p1.h_out; p.Wo = (int)p1.w_out; p.O = (int)pw->c_out;
-    const int S = dw->stride_h, TH = S == 2 ? 7 : 14;
+    const int S = sel.s, TH = S == 2 ? 7 : 14;
     p.tiles_h = (int)ceil_div(p.Ho, TH); p.tiles_w = (int)ceil_div(p.Wo, TH); p.pad = dw->pad_h;
     p.KSb = (int)(p2.k_pad / 32);
-    p.relu1 = relu1 ? 1 : 0; p.relu2 = relu2 ? 1 : 0;
+    p.relu1 = relu1; p.relu2 = relu2;
     p.ka1 = dw->ka; p.kw1 = dw->kw_scale;
     p.s1 = p2.s1; p.s2 = p2.s2; p.s1x = p2.s1 * (1.0f / 256.0f);
     const int64_t nblocks = (int64_t)p.N * p.tiles_h * p.tiles_w;
@@ -342,8 +352,7 @@ extern "C" int slfp_dwpw_fwd(const slfp_conv2d_desc* dw, const slfp_conv2d_desc*
         hipLaunchKernelGGL(fn, dim3(p.nblocks), dim3(kFT), lds, st, p);                                             \
         return check_launch("slfp fused depthwise + pointwise kernel");                                             \
     }
-    SLFP_F(1, 1, 4) SLFP_F(2, 2, 8) SLFP_F(1, 4, 8) SLFP_F(2, 4, 16)
-    SLFP_F(1, 2, 8) SLFP_F(2, 1, 4) SLFP_F(1, 1, 8) SLFP_F(2, 4, 8) SLFP_F(1, 2, 4) SLFP_F(1, 4, 16) SLFP_F(2, 2, 4) SLFP_F(1, 4, 4) SLFP_F(2, 1, 8) SLFP_F(2, 2, 16) SLFP_F(1, 2, 16) SLFP_F(2, 4, 4)
+    SLFP_DWPW_INSTANCES(SLFP_F)
 #undef SLFP_F
-    return fail(SLFP_ERR_UNSUPPORTED, "slfp_dwpw_fwd: no instantiation for this shape");
+    return fail(SLFP_ERR_UNSUPPORTED, "slfp_dwpw_fwd: no instantiation for this shape");   // not reached: dwpw_select admits SLFP_DWPW_INSTANCES only
 }

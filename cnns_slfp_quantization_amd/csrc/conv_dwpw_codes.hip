@@ -298,6 +298,28 @@ static const EncArgs* dwpw_codes_reader(const slfp_conv2d_io& io) {
     return t->valid && enc_compact_covers(*t) ? t : nullptr;
 }
 
+// What slfp_dwpw_fwd_codes chooses among k_dwpw_codes' instances; slfp_dwpw_codes_supported is this function's answer.
+bool dwpw_codes_select(const slfp_conv2d_desc* dw, const slfp_conv2d_desc* pw, const slfp_conv2d_io* io, int relu1, int relu2, DwPwSel* s) {
+    if (!dw || !pw || !io) return false;
+    if (io->x_codes != 1 || (io->y_codes != 0 && io->y_codes != 1)) return false;
+    if ((relu1 & ~1) != 0 || (relu2 & ~1) != 0) return false;   // 0 / 1 only: no SLFP_POST_LAYEROUT
+    if (!dwpw_select(dw, pw, s)) return false;   // geometry, a built (S, KS, NT), single-pass mode, tables in use (not the long form)
+    ConvPlan p1, p2;
+    if (make_plan(dw, &p1) != SLFP_OK || make_plan(pw, &p2) != SLFP_OK) return false;
+    if (dw->y_layout != SLFP_LAYOUT_NHWC || pw->x_layout != SLFP_LAYOUT_NHWC) return false;
+    if (!dwc_applicable(*dw, p1, nullptr, 0)) return false;
+    const EncArgs* t2 = act_table(pw->ka, p2.fmt_act, kEncF16P);
+    if (!t2 || !enc_compact_covers(*t2)) return false;
+    if (io->y_codes && !dwpw_codes_reader(*io)) return false;
+    if (dwpw_codes_lds(s->s, s->ks, s->nt) > 160 * 1024) return false;
+    const int TH = s->s == 2 ? 7 : 14;
+    const int64_t nblocks = dw->n * ceil_div(p1.h_out, TH) * ceil_div(p1.w_out, TH);
+    if (nblocks > 0x7FFFFFFF || dw->h * dw->w * dw->c_in >= (1ll << 29) || p1.h_out * p1.w_out * pw->c_out >= (1ll << 29)) return false;
+    s->fmt_in = p1.fmt_act;
+    s->yc = io->y_codes != 0;
+    return true;
+}
+
 }  // namespace slfp
 
 using namespace slfp;
@@ -305,22 +327,24 @@ using namespace slfp;
 extern "C" int slfp_dwpw_codes_supported(const slfp_conv2d_desc* dw, const slfp_conv2d_desc* pw, const slfp_conv2d_io* io,
                                          int has_bias_pw, int relu1, int relu2) {
     (void)has_bias_pw;   // a bias of the pointwise layer is the kernel's epilogue vector: every pair takes one
-    if (!dw || !pw || !io) return 0;
-    if (io->x_codes != 1 || (io->y_codes != 0 && io->y_codes != 1)) return 0;
-    if ((relu1 & ~1) != 0 || (relu2 & ~1) != 0) return 0;   // 0 / 1 only: no SLFP_POST_LAYEROUT
-    if (!slfp_dwpw_supported(dw, pw)) return 0;              // geometry, single-pass mode, tables in use (not the long form)
-    ConvPlan p1, p2;
-    if (make_plan(dw, &p1) != SLFP_OK || make_plan(pw, &p2) != SLFP_OK) return 0;
-    if (dw->y_layout != SLFP_LAYOUT_NHWC || pw->x_layout != SLFP_LAYOUT_NHWC) return 0;
-    if (!dwc_applicable(*dw, p1, nullptr, 0)) return 0;
-    const EncArgs* t2 = act_table(pw->ka, p2.fmt_act, kEncF16P);
-    if (!t2 || !enc_compact_covers(*t2)) return 0;
-    if (io->y_codes && !dwpw_codes_reader(*io)) return 0;
-    if (dwpw_codes_lds(dw->stride_h, (int)(dw->c_in / 32), (int)(pw->c_out / 16)) > 160 * 1024) return 0;
-    const int TH = dw->stride_h == 2 ? 7 : 14;
-    const int64_t nblocks = dw->n * ceil_div(p1.h_out, TH) * ceil_div(p1.w_out, TH);
-    if (nblocks > 0x7FFFFFFF || dw->h * dw->w * dw->c_in >= (1ll << 29) || p1.h_out * p1.w_out * pw->c_out >= (1ll << 29)) return 0;
-    return 1;
+    DwPwSel sel;
+    return dwpw_codes_select(dw, pw, io, relu1, relu2, &sel) ? 1 : 0;
+}
+
+// Host only: the instance slfp_dwpw_fwd (io == NULL) / slfp_dwpw_fwd_codes would run, printed from the selection they consume.
+extern "C" const char* slfp_debug_dwpw_instance(const slfp_conv2d_desc* dw, const slfp_conv2d_desc* pw, const slfp_conv2d_io* io,
+                                                int has_bias_pw, int relu1, int relu2) {
+    (void)has_bias_pw;
+    static thread_local char buf[64];
+    DwPwSel s;
+    if (!io) {
+        if ((relu1 & ~1) != 0 || (relu2 & ~1) != 0 || !dwpw_select(dw, pw, &s)) return "none";
+        snprintf(buf, sizeof buf, "f32/s%d/k%d/n%d", s.s, s.ks, s.nt);
+        return buf;
+    }
+    if (!dwpw_codes_select(dw, pw, io, relu1, relu2, &s)) return "none";
+    snprintf(buf, sizeof buf, "codes/s%d/k%d/n%d/%s/%s", s.s, s.ks, s.nt, s.fmt_in == kFmtSfp7 ? "sfp7" : "act8", s.yc ? "yc" : "f32");
+    return buf;
 }
 
 template <int S, int KS, int NT>
@@ -338,7 +362,8 @@ extern "C" int slfp_dwpw_fwd_codes(const slfp_conv2d_desc* dw, const slfp_conv2d
                                    const void* wprep_pw, const float* bias_pw, const float* post2_scale, const float* post2_shift,
                                    int relu2, void* y, void* stream) {
     if (!dw || !pw || !io) return fail(SLFP_ERR_BAD_ARG, "slfp_dwpw_fwd_codes: null descriptor");
-    if (!slfp_dwpw_codes_supported(dw, pw, io, bias_pw != nullptr, relu1, relu2))
+    DwPwSel sel;
+    if (!dwpw_codes_select(dw, pw, io, relu1, relu2, &sel))
         return fail(SLFP_ERR_UNSUPPORTED, "slfp_dwpw_fwd_codes: this pair of layers does not run as one kernel on codes (slfp_dwpw_codes_supported)");
     if (!x || !wprep_dw || !wprep_pw || !y || !post1_scale || !post1_shift)
         return fail(SLFP_ERR_BAD_ARG, "slfp_dwpw_fwd_codes: null pointer (the depthwise layer's folded BatchNorm is required)");
@@ -349,8 +374,8 @@ extern "C" int slfp_dwpw_fwd_codes(const slfp_conv2d_desc* dw, const slfp_conv2d
     ConvPlan p1, p2;
     make_plan(dw, &p1);
     make_plan(pw, &p2);
-    const int S = dw->stride_h, TH = S == 2 ? 7 : 14;
-    const int ks = (int)(dw->c_in / 32), nt = (int)(pw->c_out / 16);
+    const int S = sel.s, TH = S == 2 ? 7 : 14;
+    const int ks = sel.ks, nt = sel.nt;
     DwPwCodesParams p;
     p.x = reinterpret_cast<const uint8_t*>(x); p.wdw = reinterpret_cast<const float*>(wprep_dw); p.sc1 = post1_scale; p.sh1 = post1_shift;
     p.wpw = reinterpret_cast<const _Float16*>(wprep_pw); p.bias2 = bias_pw; p.sc2 = post2_scale; p.sh2 = post2_shift; p.y = y;
@@ -366,12 +391,11 @@ extern "C" int slfp_dwpw_fwd_codes(const slfp_conv2d_desc* dw, const slfp_conv2d
     p.encY = io->y_codes ? enc_compact(*dwpw_codes_reader(*io)) : p.enc2;   // float32 out: not read
     static_assert(sizeof(DwPwCodesParams) <= 4096, "kernel arguments must fit the 4 KiB kernarg segment");
     const size_t lds = dwpw_codes_lds(S, ks, nt);
-    const bool sfp7 = p1.fmt_act == kFmtSfp7, yc = io->y_codes != 0;
+    const bool sfp7 = sel.fmt_in == kFmtSfp7, yc = sel.yc;
     hipStream_t st = as_stream(stream);
 #define SLFP_FC(SS, KK, NN) \
     if (S == SS && ks == KK && nt == NN) return launch_dwpw_codes<SS, KK, NN>(p, sfp7, yc, lds, st);
-    SLFP_FC(1, 1, 4) SLFP_FC(1, 1, 8) SLFP_FC(1, 1, 16) SLFP_FC(1, 2, 4) SLFP_FC(1, 2, 8) SLFP_FC(1, 2, 16) SLFP_FC(1, 4, 4) SLFP_FC(1, 4, 8) SLFP_FC(1, 4, 16)
-    SLFP_FC(2, 1, 4) SLFP_FC(2, 1, 8) SLFP_FC(2, 1, 16) SLFP_FC(2, 2, 4) SLFP_FC(2, 2, 8) SLFP_FC(2, 2, 16) SLFP_FC(2, 4, 4) SLFP_FC(2, 4, 8) SLFP_FC(2, 4, 16)
+    SLFP_DWPW_INSTANCES(SLFP_FC)
 #undef SLFP_FC
-    return fail(SLFP_ERR_UNSUPPORTED, "slfp_dwpw_fwd_codes: no instantiation for this shape");
+    return fail(SLFP_ERR_UNSUPPORTED, "slfp_dwpw_fwd_codes: no instantiation for this shape");   // not reached: dwpw_select admits SLFP_DWPW_INSTANCES only
 }

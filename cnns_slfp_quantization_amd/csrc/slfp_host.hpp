@@ -181,6 +181,29 @@ int launch_dwc(const slfp_conv2d_desc& d, const ConvPlan& p, const uint8_t* x, c
                void* y, const CodeIo& io, hipStream_t stream);
 // the k_dwc instance launch_dwc runs, printed from the selection it consumes (slfp_debug_dw3x3_instance; host only)
 const char* dwc_instance_name(const slfp_conv2d_desc& d, const ConvPlan& p, const PostOp& post, const CodeIo& io);
+// ---- one depthwise -> pointwise block in one kernel (conv_dwpw.hip: k_dwpw, conv_dwpw_codes.hip: k_dwpw_codes) ----
+// The (S, KS, NT) instances both kernels are built for.  The selections behind the queries (through dwpw_instance_built) and the two
+// launchers' dispatch expand this one list, so a pair a query accepts always has a kernel to run.
+#define SLFP_DWPW_INSTANCES(X)                                                                                   \
+    X(1, 1, 4) X(1, 1, 8) X(1, 1, 16) X(1, 2, 4) X(1, 2, 8) X(1, 2, 16) X(1, 4, 4) X(1, 4, 8) X(1, 4, 16)        \
+    X(2, 1, 4) X(2, 1, 8) X(2, 1, 16) X(2, 2, 4) X(2, 2, 8) X(2, 2, 16) X(2, 4, 4) X(2, 4, 8) X(2, 4, 16)
+// What the launchers choose among the instances: slfp_dwpw_supported / slfp_dwpw_codes_supported answer 1 exactly where the
+// selection below succeeds, slfp_dwpw_fwd / slfp_dwpw_fwd_codes dispatch on it, slfp_debug_dwpw_instance prints it.
+struct DwPwSel {
+    int s, ks, nt;   // S (depthwise stride), KS = K / 32, NT = N / 16
+    int fmt_in;      // k_dwpw_codes: FMT, what the input codes are (kFmtAct8 | kFmtSfp7)
+    bool yc;         // k_dwpw_codes: YC, code output
+};
+inline bool dwpw_instance_built(int s, int ks, int nt) {
+#define SLFP_DWPW_HAS(SS, KK, NN) if (s == SS && ks == KK && nt == NN) return true;
+    SLFP_DWPW_INSTANCES(SLFP_DWPW_HAS)
+#undef SLFP_DWPW_HAS
+    return false;
+}
+// the float32 interface's selection (conv_dwpw.hip); false: the pair does not run as one kernel.  Host only.
+bool dwpw_select(const slfp_conv2d_desc* dw, const slfp_conv2d_desc* pw, DwPwSel* s);
+// the code interface's (conv_dwpw_codes.hip)
+bool dwpw_codes_select(const slfp_conv2d_desc* dw, const slfp_conv2d_desc* pw, const slfp_conv2d_io* io, int relu1, int relu2, DwPwSel* s);
 int launch_direct(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const float* wq_hwio,
                   const float* bias, const PostOp& post, float* y, hipStream_t stream);
 bool stem_applicable(const slfp_conv2d_desc& d);  // direct family: the small-C_in stem kernel takes it

@@ -207,7 +207,8 @@ int slfp_conv2d_fwd_post(const slfp_conv2d_desc* d, const float* x, const void* 
  * to the matrix cores through LDS as fp16: the intermediate tensor never goes to HBM.  Bit-identical to
  * slfp_conv2d_fwd_post(dw) followed by slfp_conv2d_fwd_post(pw) in the single-pass MFMA mode.  `dw` / `pw` are the two
  * layers' descriptors (NHWC; pw's input size = dw's output size), wprep_* their prepared weights, post1_* the folded
- * BatchNorm of the depthwise layer (required), post2_* that of the pointwise layer (or NULL), relu*: 0 / 1.
+ * BatchNorm of the depthwise layer (required), post2_* that of the pointwise layer (or NULL), relu*: 0 / 1 (anything else:
+ * SLFP_ERR_BAD_ARG before any other argument is looked at).
  * slfp_dwpw_supported: 1 if the pair can be fused (3x3 depthwise stride 1 / 2, C in {32, 64, 128}, N in {64, 128, 256},
  * C * N * 2 B <= 64 KiB, single-pass mode, threshold tables available for both Ka), else 0. */
 int slfp_dwpw_supported(const slfp_conv2d_desc* dw, const slfp_conv2d_desc* pw);
@@ -270,6 +271,17 @@ int slfp_dwpw_fwd_codes(const slfp_conv2d_desc* dw, const slfp_conv2d_desc* pw, 
                         const void* wprep_dw, const float* post1_scale, const float* post1_shift, int relu1,
                         const void* wprep_pw, const float* bias_pw, const float* post2_scale, const float* post2_shift,
                         int relu2, void* y, void* stream);
+/* Which template instance of the one-kernel block a call would run.  io == NULL: slfp_dwpw_fwd's k_dwpw<S, KS, NT>, as
+ *   f32/s<1|2>/k<1|2|4>/n<4|8|16>
+ * otherwise slfp_dwpw_fwd_codes' k_dwpw_codes<S, KS, NT, FMT, YC>, as
+ *   codes/s<1|2>/k<1|2|4>/n<4|8|16>/<act8|sfp7>/<f32|yc>
+ * (s: the depthwise stride; k: C / 32; n: pointwise C_out / 16; act8 / sfp7: the format of the input codes; f32 / yc: float32 or
+ * code output).  "none" wherever slfp_dwpw_supported / slfp_dwpw_codes_supported answers 0 (null descriptors and relu bits other
+ * than 0 / 1 included).  The string is printed from the selection the queries and the launchers consume, so a query answers 1
+ * exactly where its launcher has an instance.  Host only: no device is touched.  The pointer stays valid until the next call on
+ * the same thread. */
+const char* slfp_debug_dwpw_instance(const slfp_conv2d_desc* dw, const slfp_conv2d_desc* pw, const slfp_conv2d_io* io,
+                                     int has_bias_pw, int relu1, int relu2);
 /* ---- code output into a channel slice: a concat without the copy ------------------------------------------------------------
  * slfp_conv2d_fwd_codes_ws with the code output written into a channel slice of a WIDER NHWC code tensor: y points at the
  * slice's first channel of pixel 0, y_ld is the wider tensor's channel count = the byte distance between two pixels.  The two
