@@ -9,115 +9,56 @@
 // (4 B written + 4 B read per element = 40 % of the block's traffic for 32->64 at 112x112).
 //
 // Arithmetic is EXACTLY the two separate kernels' (conv_dw2.hip, conv_pw.hip: k_pw_stream), step for step, so the
-// output is bit-identical to running them back to back: input quantized through the threshold table, float32 FMAs in
-// (kh, kw) order, (acc * Ka) * Kw, fma(scale, shift), max(0), threshold-table quantizer in its packed-fp16 form,
-// v_mfma_f32_16x16x32_f16 over k in blob order, ((acc + 256 bq) * s1/256) * s2, fma, max.
-//
-//   workgroup (512 threads) = one image x one 14x14 (stride 1) or 7x7 (stride 2) tile of depthwise outputs x ALL channels:
-//   phase 1, per 32-channel group: halo tile -> LDS (as conv_dw2.hip; the loads of the next group are issued before
-//            this group is convolved), 3x3 conv, BN/ReLU, quantize -> fp16 row [pixel][K] in LDS;
-//   phase 2: the tile's 13 (4) sixteen-pixel units x all output channels on the matrix cores, W resident in LDS
-//            (K * N * 2 B <= 64 KiB: MobileNetV1's first four blocks, which carry 70 % of the net's conv traffic),
-//            outputs staged to 128-byte pieces (the staging area reuses the halo tile).
+// output is bit-identical to running them back to back.  The workgroup's plan, the geometry, the parameters and the
+// steps shared with k_dwpw_codes (conv_dwpw_codes.hip) are in conv_dwpw_core.hpp.  This kernel's own:
+//   input       float32 halo by 16-byte buffer loads, quantized through the threshold table (enc4_f32_raw), a NaN stays a NaN;
+//   hand-over   the threshold-table quantizer in its packed-fp16 form with conv_pw.hip's NaN policy (enc4_f16);
+//   epilogue    ((acc + 256 bq) * s1/256) * s2 with a branch around the bias add for a pair without epilogue vectors (it
+//               decides the kernel's SGPR count, so it is not slfp_epilogue.hpp's epilogue(): DESIGN.md section 29), fma, max.
 //
 // Measured (profiles/dwpw_bench.py, batch 256, cold): the kernel removes 40 % (32->64) to 33 % of the pair's HBM
 // traffic but runs 1-2 workgroups per CU with its phases in series, so it only breaks even on 32@112->64
 // (399 vs 407 us) and is slower on the K = 64 / 128 pairs (412 vs 352, 420 vs 337, 316 vs 204 us).  fusion.fuse_dw_pw is
 // therefore opt-in; DESIGN.md lists what the next version needs (fp16 halo tile, k-outer accumulation, >= 3 workgroups/CU).
 #include <cstdlib>
-#include "slfp_device.hpp"
-#include "slfp_enc.hpp"
-#include "slfp_host.hpp"
-#include "slfp_epilogue.hpp"
+#include "conv_dwpw_core.hpp"
 
 namespace slfp {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int kFTab = (kEncEntries * 8 + 15) & ~15;
-constexpr uint32_t kOobF = 0xFFFFFFF0u;
-
-struct DwPwParams {
-    const float* x;        // depthwise input, NHWC
-    const float* wdw;      // [9][C] quantized depthwise weights (slfp_conv2d_prepare_weights of the dw layer)
-    const float* sc1;      // BatchNorm 1 folded: scale / shift [C]
-    const float* sh1;
-    const _Float16* wpw;   // pointwise blob (hi plane), tile (nt, ks) at (nt * KSb + ks) * 512 halves
-    const float* bias2;    // pointwise bias or nullptr
-    const float* sc2;      // BatchNorm 2 folded or nullptr
-    const float* sh2;
-    float* y;              // pointwise output, NHWC
-    int N, H, W, C, Ho, Wo, O;   // images, dw input size, channels, dw output size, pointwise channels
-    int tiles_h, tiles_w, pad;
-    int KSb;               // k-steps per tile in the pointwise blob
-    int relu1, relu2;
-    float ka1, kw1;        // depthwise scales
-    float s1, s2, s1x;     // pointwise epilogue (Ka2, Kw2, Ka2 / 256)
-    uint32_t nblocks;
+struct DwPwParams : DwPwBase {
     EncArgsCompact enc1;   // QA(x / Ka_dw) as float32
     EncArgsCompact enc2;   // fp16(16 * QA(. / Ka_pw)), packed pairs (two tables: compact form, 4 KiB of kernel arguments in all)
 };
 
-constexpr int kFT = 512;                         // threads: 64 pixel slots x 8 channel quads in phase 1, 8 waves in phase 2
-
-// S: depthwise stride; KS: K / 32 (1, 2, 4); NT: N / 16 channel tiles (4, 8, 16)
+// S, KS, NT: DwPwGeom's
 template <int S, int KS, int NT>
-__global__ __launch_bounds__(kFT, 2) void k_dwpw(const DwPwParams p) {
-    constexpr int TH = S == 2 ? 7 : 14, TW = TH;
-    constexpr int IH = (TH - 1) * S + 3, IW = IH;
-    constexpr int RPL = kFT / 8 / 16;            // halo rows loaded per step (4)
-    constexpr int NI = (IH + RPL - 1) / RPL;
-    constexpr int ROWB = 16 * 32 * 4;
-    constexpr int NPX = TH * TW;                 // depthwise outputs of the tile = pointwise pixels
-    constexpr int NU = (NPX + 15) / 16;          // 16-pixel MFMA units (13 / 4)
-    constexpr int NWV = kFT / 64;
-    constexpr int UW = (NU + NWV - 1) / NWV;     // units per wave
-    constexpr int K = KS * 32;
-    constexpr int XROW = K * 2 + 16;             // bytes per pixel row of the fp16 image (+16: conflict-free fragment reads)
-    constexpr int CW = TW > 8 ? 16 : 8, RPI = (kFT / 8) / CW, NO = (TH + RPI - 1) / RPI;
+__global__ __launch_bounds__(kDwPwT, 2) void k_dwpw(const DwPwParams p) {
+    using G = DwPwGeom<S, KS, NT>;
+    constexpr int TH = G::TH, TW = G::TW, IH = G::IH, RPL = G::RPL, NI = G::NI, ROWB = G::ROWB, NPX = G::NPX, NU = G::NU, NWV = G::NWV, UW = G::UW;
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char* tab2 = smem + kFTab;
-    unsigned char* tile = tab2 + kFTab;                        // [RPL * NI rows][16 slots][32 ch] float32
-    unsigned char* x16 = tile + RPL * NI * ROWB;               // [NU * 16 rows][XROW]
-    unsigned char* wl = x16 + NU * 16 * XROW;                  // [tile j][k-step][lane] 16 B
-    float* ep = reinterpret_cast<float*>(wl + NT * KS * 1024);  // [3][NT * 16]
-    unsigned char* stg_all = tile;   // [8 waves][2 KiB]: phase 2 reuses the (then idle) halo tile
+    unsigned char* tab2 = smem + kDwPwTab;
+    unsigned char* lds = tab2 + kDwPwTab;
+    unsigned char *tile = lds + G::tile, *x16 = lds + G::x16, *wl = lds + G::wl;
+    float* ep = reinterpret_cast<float*>(lds + G::ep);
 
-    enc_fill_compact<kFT>(reinterpret_cast<uint2*>(smem), p.enc1);
-    enc_fill_compact<kFT>(reinterpret_cast<uint2*>(tab2), p.enc2);
-    for (int i = threadIdx.x; i < NT * KS * 64; i += kFT) {     // W -> LDS, 16 bytes per thread
+    enc_fill_compact<kDwPwT>(reinterpret_cast<uint2*>(smem), p.enc1);
+    enc_fill_compact<kDwPwT>(reinterpret_cast<uint2*>(tab2), p.enc2);
+    for (int i = threadIdx.x; i < NT * KS * 64; i += kDwPwT) {     // W -> LDS, 16 bytes per thread
         const int l = i & 63, t = i >> 6, ks = t % KS, j = t / KS;
         *reinterpret_cast<u32x4*>(wl + (size_t)i * 16) = *reinterpret_cast<const u32x4*>(p.wpw + ((size_t)j * p.KSb + ks) * 512 + l * 8);
     }
-    for (int i = threadIdx.x; i < NT * 16; i += kFT) {
-        ep[i] = p.bias2 ? bias_q256_1(p.bias2[i], p.s1, p.s2) : 0.f;
-        ep[NT * 16 + i] = p.sc2 ? p.sc2[i] : 1.f;
-        ep[2 * NT * 16 + i] = p.sc2 ? p.sh2[i] : 0.f;
-    }
-    for (int i = threadIdx.x; i < (NU * 16 - NPX) * (XROW / 8); i += kFT)   // rows beyond the tile's pixels: zeros
-        reinterpret_cast<uint2*>(x16 + NPX * XROW)[i] = make_uint2(0u, 0u);
-
-    const uint32_t lb = xcd_remap(blockIdx.x, p.nblocks);
-    const uint32_t tiles_per_img = (uint32_t)(p.tiles_h * p.tiles_w);
-    const uint32_t n = lb / tiles_per_img, tr = lb - n * tiles_per_img;
-    const int th = (int)(tr / (uint32_t)p.tiles_w), tw = (int)(tr - (uint32_t)th * p.tiles_w);
-
-    const int c4 = threadIdx.x & 7, slot = threadIdx.x >> 3;
-    const int iw = slot & 15, ihh = slot >> 4;
-    const int colslot = (S == 2) ? ((iw & 1) * 8 + (iw >> 1)) : iw;
-    const uint32_t lds_w = (uint32_t)((ihh * 16 + colslot) * 128 + c4 * 16);
-    const bool col_live = iw < IW;
-    const int ow = slot & (CW - 1), ohb = slot / CW;
-    const bool ocol_live = ow < TW;
-    const uint32_t lds_r0 = (uint32_t)(((ohb * S) * 16 + ow) * 128 + c4 * 16);
+    dwpw_fill_ep_zero<G>(ep, x16, p);
+    const DwPwIdx d = dwpw_index<G>(p);
+    // in locals: read through `d` at the sites, the values reach the scheduler in another order and the register counts move
+    const uint32_t n = d.n, lds_w = d.lds_w, lds_r0 = d.lds_r0;
+    const int th = d.th, tw = d.tw, c4 = d.c4, iw = d.iw, ihh = d.ihh;
+    const bool col_live = d.col_live;
     const float r1 = p.enc1.r1, lo1 = p.enc1.lo, hi1 = p.enc1.hi;
     const float r2 = p.enc2.r1, lo2 = p.enc2.lo, hi2 = p.enc2.hi;
 
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x) + (size_t)n * p.H * p.W * p.C, 0,
-                                                                         (uint32_t)p.H * p.W * p.C * 4u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(reinterpret_cast<const float*>(p.x)) + (size_t)n * p.H * p.W * p.C, 0, (uint32_t)p.H * p.W * p.C * 4u, 0x00020000);
     const int gw = tw * TW * S - p.pad + iw;
     const int gh0 = th * TH * S - p.pad + ihh;
     const bool w_ok = col_live && (unsigned)gw < (unsigned)p.W;
@@ -127,14 +68,14 @@ __global__ __launch_bounds__(kFT, 2) void k_dwpw(const DwPwParams p) {
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
         const bool ok = w_ok && (unsigned)(gh0 + RPL * i) < (unsigned)p.H && (RPL * i + ihh) < IH;
-        voff[i] = ok ? off0 + (uint32_t)i * step : kOobF;
+        voff[i] = ok ? off0 + (uint32_t)i * step : kDwPwOob;
         asm volatile("" : "+v"(voff[i]));
     }
-    f32x4 v[NI];
+    floatx4 v[NI];
     auto issue = [&](int cg) {   // halo tile of channel group cg: soffset moves along the channel axis
 #pragma unroll
         for (int i = 0; i < NI; ++i)
-            v[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff[i], (uint32_t)cg * 128u, 0));
+            v[i] = __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff[i], (uint32_t)cg * 128u, 0));
     };
 
     // ================= phase 1: depthwise, one 32-channel group at a time =================
@@ -143,11 +84,11 @@ __global__ __launch_bounds__(kFT, 2) void k_dwpw(const DwPwParams p) {
 #pragma unroll 1
     for (int cg = 0; cg < KS; ++cg) {
         const int c = cg * 32 + c4 * 4;
-        f32x4 wt[9];
+        floatx4 wt[9];
 #pragma unroll
-        for (int k = 0; k < 9; ++k) wt[k] = *reinterpret_cast<const f32x4*>(p.wdw + (size_t)k * p.C + c);
-        const f32x4 psc = *reinterpret_cast<const f32x4*>(p.sc1 + c);
-        const f32x4 psh = *reinterpret_cast<const f32x4*>(p.sh1 + c);
+        for (int k = 0; k < 9; ++k) wt[k] = *reinterpret_cast<const floatx4*>(p.wdw + (size_t)k * p.C + c);
+        const floatx4 psc = *reinterpret_cast<const floatx4*>(p.sc1 + c);
+        const floatx4 psh = *reinterpret_cast<const floatx4*>(p.sh1 + c);
         bool any_nan = false;
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
@@ -165,31 +106,21 @@ __global__ __launch_bounds__(kFT, 2) void k_dwpw(const DwPwParams p) {
         __syncthreads();
         if (cg + 1 < KS) issue(cg + 1);   // in flight under the convolution below
 #pragma unroll
-        for (int j = 0; j < NO; ++j) {
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < G::NO; ++j) {   // conv_dw2.hip's epilogue, then conv_pw.hip's quantizer
+            floatx4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int kh = 0; kh < 3; ++kh) {
 #pragma unroll
                 for (int kw = 0; kw < 3; ++kw) {
-                    const int tap = j * RPI * S * ROWB + ((S == 1) ? (kh * ROWB + kw * 128) : (kh * ROWB + ((kw & 1) * 8 + (kw >> 1)) * 128));
-                    const f32x4 a = *reinterpret_cast<const f32x4*>(tile + lds_r0 + tap);
-                    const f32x4 w = wt[kh * 3 + kw];
+                    const int tap = j * G::RPI * S * ROWB + ((S == 1) ? (kh * ROWB + kw * 128) : (kh * ROWB + ((kw & 1) * 8 + (kw >> 1)) * 128));
+                    const floatx4 a = *reinterpret_cast<const floatx4*>(tile + lds_r0 + tap);
+                    const floatx4 w = wt[kh * 3 + kw];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) acc[e] = fmaf(a[e], w[e], acc[e]);
                 }
             }
-            float4 rr;   // conv_dw2.hip's epilogue, then conv_pw.hip's quantizer
-            {
-                float u0 = (acc[0] * p.ka1) * p.kw1, u1 = (acc[1] * p.ka1) * p.kw1, u2 = (acc[2] * p.ka1) * p.kw1, u3 = (acc[3] * p.ka1) * p.kw1;
-                u0 = __builtin_fmaf(u0, psc[0], psh[0]); u1 = __builtin_fmaf(u1, psc[1], psh[1]);
-                u2 = __builtin_fmaf(u2, psc[2], psh[2]); u3 = __builtin_fmaf(u3, psc[3], psh[3]);
-                if (p.relu1) { u0 = fmaxf(u0, 0.f); u1 = fmaxf(u1, 0.f); u2 = fmaxf(u2, 0.f); u3 = fmaxf(u3, 0.f); }
-                rr = make_float4(u0, u1, u2, u3);
-            }
-            const uint2 q = enc4_f16(rr, r2, lo2, hi2, tab2);
-            const int oh = ohb + j * RPI;
-            if (ocol_live && oh < TH)
-                *reinterpret_cast<uint2*>(x16 + (uint32_t)(oh * TW + ow) * XROW + (uint32_t)(cg * 64 + c4 * 8)) = q;
+            const float4 rr = dwpw_bn1(acc, psc, psh, p);
+            dwpw_put_quad<G>(x16, d, j, cg, enc4_f16(rr, r2, lo2, hi2, tab2));
         }
         __syncthreads();   // the tile is free for the next group; after the last group: the fp16 image is complete
     }
@@ -200,18 +131,12 @@ __global__ __launch_bounds__(kFT, 2) void k_dwpw(const DwPwParams p) {
     half8 xh[UW][KS];
 #pragma unroll
     for (int ui = 0; ui < UW; ++ui) {
-        const int u = wv + NWV * ui;
-        const unsigned char* row = x16 + (uint32_t)((u < NU ? u : NU - 1) * 16 + col) * XROW + kq * 8;
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const u32x2 a = *reinterpret_cast<const u32x2*>(row + ks * 64);
-            const u32x2 b = *reinterpret_cast<const u32x2*>(row + ks * 64 + 32);
-            xh[ui][ks] = __builtin_bit_cast(half8, u32x4{a[0], a[1], b[0], b[1]});
-        }
+        for (int ks = 0; ks < KS; ++ks) xh[ui][ks] = dwpw_frag<G>(x16, wv + NWV * ui, col, kq, ks);
     }
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(p.y + (size_t)n * p.Ho * p.Wo * p.O, 0,
+    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(p.y) + (size_t)n * p.Ho * p.Wo * p.O, 0,
                                                                          (uint32_t)p.Ho * p.Wo * p.O * 4u, 0x00020000);
-    unsigned char* stg = stg_all + wv * 2048;
+    unsigned char* stg = tile + wv * 2048;   // [8 waves][2 KiB]: phase 2 reuses the (then idle) halo tile
     const int spx = lane >> 3, sch = lane & 7;
     const bool has_vec = p.bias2 != nullptr || p.sc2 != nullptr;
     const int oh0 = th * TH, ow0 = tw * TW;
@@ -224,12 +149,7 @@ __global__ __launch_bounds__(kFT, 2) void k_dwpw(const DwPwParams p) {
 #pragma unroll
                 for (int jj = 0; jj < 2; ++jj) {
                     const int j = j0 + jj;
-                    floatx4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int ks = 0; ks < KS; ++ks) {
-                        const half8 wf = *reinterpret_cast<const half8*>(wl + (uint32_t)((j * KS + ks) * 1024) + lane * 16);
-                        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf, xh[ui][ks], acc, 0, 0, 0);
-                    }
+                    const floatx4 acc = dwpw_mma<G>(wl, xh[ui], j, lane);
                     const int nl = j * 16 + kq * 4;
                     float4 r = make_float4(acc[0], acc[1], acc[2], acc[3]);
                     if (has_vec) {
@@ -252,7 +172,7 @@ __global__ __launch_bounds__(kFT, 2) void k_dwpw(const DwPwParams p) {
                     const int pix = u * 16 + spx + 8 * h;                      // pixel of the tile
                     const int oh = pix / TW, owp = pix - oh * TW;
                     const bool live = pix < NPX && (oh0 + oh) < p.Ho && (ow0 + owp) < p.Wo;
-                    uint32_t so = live ? (uint32_t)(((oh0 + oh) * p.Wo + ow0 + owp) * p.O + j0 * 16 + sch * 4) * 4u : kOobF;
+                    uint32_t so = live ? (uint32_t)(((oh0 + oh) * p.Wo + ow0 + owp) * p.O + j0 * 16 + sch * 4) * 4u : kDwPwOob;
                     asm volatile("" : "+v"(so));
                     __builtin_amdgcn_raw_buffer_store_b128(vv, ry, so, 0, 0);
                 }
@@ -277,11 +197,7 @@ static bool dwpw_shape(const slfp_conv2d_desc& dw, const slfp_conv2d_desc& pw, i
     return true;
 }
 
-static size_t dwpw_lds(int S, int KS, int NT) {
-    const int TH = S == 2 ? 7 : 14, IH = (TH - 1) * S + 3, NI = (IH + 3) / 4, NU = (TH * TH + 15) / 16;
-    return (size_t)2 * kFTab + (size_t)4 * NI * 16 * 32 * 4 + (size_t)NU * 16 * (KS * 64 + 16) + (size_t)NT * KS * 1024 +
-           (size_t)3 * NT * 16 * 4;
-}
+static size_t dwpw_lds(int S, int KS, int NT) { return (size_t)2 * kDwPwTab + dwpw_geom_bytes(S, KS, NT); }
 
 // What slfp_dwpw_fwd chooses among k_dwpw's instances; slfp_dwpw_supported is this function's answer.
 bool dwpw_select(const slfp_conv2d_desc* dw, const slfp_conv2d_desc* pw, DwPwSel* s) {
@@ -324,21 +240,12 @@ extern "C" int slfp_dwpw_fwd(const slfp_conv2d_desc* dw, const slfp_conv2d_desc*
     ConvPlan p1, p2;
     make_plan(dw, &p1);
     make_plan(pw, &p2);
-    const int ks = sel.ks, nt = sel.nt;
+    const int S = sel.s, ks = sel.ks, nt = sel.nt;
     DwPwParams p;
-    p.x = x; p.wdw = reinterpret_cast<const float*>(wprep_dw); p.sc1 = post1_scale; p.sh1 = post1_shift;
-    p.wpw = reinterpret_cast<const _Float16*>(wprep_pw); p.bias2 = bias_pw; p.sc2 = post2_scale; p.sh2 = post2_shift; p.y = y;
-    p.N = (int)dw->n; p.H = (int)dw->h; p.W = (int)dw->w; p.C = (int)dw->c_in; p.Ho = (int)p1.h_out; p.Wo = (int)p1.w_out; p.O = (int)pw->c_out;
-    const int S = sel.s, TH = S == 2 ? 7 : 14;
-    p.tiles_h = (int)ceil_div(p.Ho, TH); p.tiles_w = (int)ceil_div(p.Wo, TH); p.pad = dw->pad_h;
-    p.KSb = (int)(p2.k_pad / 32);
-    p.relu1 = relu1; p.relu2 = relu2;
-    p.ka1 = dw->ka; p.kw1 = dw->kw_scale;
-    p.s1 = p2.s1; p.s2 = p2.s2; p.s1x = p2.s1 * (1.0f / 256.0f);
-    const int64_t nblocks = (int64_t)p.N * p.tiles_h * p.tiles_w;
+    const int64_t nblocks = dwpw_fill_base(p, dw, pw, p1, p2, x, wprep_dw, post1_scale, post1_shift, relu1, wprep_pw, bias_pw, post2_scale,
+                                           post2_shift, relu2, y);
     if (nblocks > 0x7FFFFFFF || (int64_t)p.H * p.W * p.C >= (1ll << 29) || (int64_t)p.Ho * p.Wo * p.O >= (1ll << 29))
         return fail(SLFP_ERR_UNSUPPORTED, "slfp_dwpw_fwd: tensor too large");
-    p.nblocks = (uint32_t)nblocks;
     p.enc1 = enc_compact(*act_table(dw->ka, p1.fmt_act, kEncF32));
     p.enc2 = enc_compact(*act_table(pw->ka, p2.fmt_act, kEncF16P));
     static_assert(sizeof(DwPwParams) <= 4096, "kernel arguments must fit the 4 KiB kernarg segment");
@@ -349,7 +256,7 @@ extern "C" int slfp_dwpw_fwd(const slfp_conv2d_desc* dw, const slfp_conv2d_desc*
         auto fn = k_dwpw<SS, KK, NN>;                                                                               \
         const int rc = raise_lds_limit(reinterpret_cast<const void*>(fn), lds);                                     \
         if (rc != SLFP_OK) return rc;                                                                               \
-        hipLaunchKernelGGL(fn, dim3(p.nblocks), dim3(kFT), lds, st, p);                                             \
+        hipLaunchKernelGGL(fn, dim3(p.nblocks), dim3(kDwPwT), lds, st, p);                                          \
         return check_launch("slfp fused depthwise + pointwise kernel");                                             \
     }
     SLFP_DWPW_INSTANCES(SLFP_F)

@@ -16,113 +16,57 @@
 //   k_pwc_stream: v_mfma_f32_16x16x32_f16 over k in blob order from +0, the tile epilogue of slfp_epilogue.hpp, then the ReLU
 //                 (float32 out) or the reader's code quantizer (code4: the ReLU folded in, or signed codes).
 //
-//   workgroup (512 threads) = one image x one 14x14 (stride 1) or 7x7 (stride 2) tile of depthwise outputs x ALL channels, as k_dwpw:
-//   phase 1, per 32-channel group: the halo's codes by dword loads through a buffer descriptor (the next group's are issued before
-//            this group is convolved) -> decoded float32 halo tile in LDS -> 3x3 conv, BN / ReLU, quantize -> fp16 row [pixel][K];
-//   phase 2: the tile's 13 (4) sixteen-pixel units x all output channels on the matrix cores, W resident in LDS.  Float32 leaves
-//            staged to 128-byte pieces (the staging area reuses the halo tile); codes leave four channel tiles at a time through
-//            rows_transpose4, 16 bytes per lane = 64 contiguous bytes per pixel and wave.
+// The workgroup's plan, the geometry, the parameters and the steps shared with k_dwpw are in conv_dwpw_core.hpp.  This kernel's own:
+//   input       the halo's codes by dword loads through a buffer descriptor, decoded to the float32 halo tile (dec4_f32);
+//   hand-over   enc4_f16_raw and the NaN patch above;
+//   output      float32 staged to 128-byte pieces as in k_dwpw, or (YC) codes, four channel tiles at a time through
+//               rows_transpose4, 16 bytes per lane = 64 contiguous bytes per pixel and wave.
 // The K >= 256 blocks (W does not fit LDS) are not covered.  Measurements: profiles/dwpw_codes_bench.py, DESIGN.md section 23.
-#include "slfp_device.hpp"
-#include "slfp_enc.hpp"
 #include "slfp_codes.hpp"
-#include "slfp_host.hpp"
-#include "slfp_epilogue.hpp"
+#include "conv_dwpw_core.hpp"
 
 namespace slfp {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+constexpr uint32_t kDwPwOobLoad = 0x80000000u;   // code loads: past every tensor (< 2^29 bytes) with the channel group's offset added
 
-constexpr int kFcTab = (kEncEntries * 8 + 15) & ~15;
-constexpr uint32_t kFcOobLoad = 0x80000000u;    // code loads: past every tensor (< 2^29 bytes) with the channel group's offset added
-constexpr uint32_t kFcOobStore = 0xFFFFFFF0u;
-
-struct DwPwCodesParams {
-    const uint8_t* x;      // depthwise input: codes of QA(. / Ka_dw), NHWC
-    const float* wdw;      // [9][C] quantized depthwise weights (slfp_conv2d_prepare_weights of the dw layer)
-    const float* sc1;      // BatchNorm 1 folded: scale / shift [C]
-    const float* sh1;
-    const _Float16* wpw;   // pointwise blob (hi plane), tile (nt, ks) at (nt * KSb + ks) * 512 halves
-    const float* bias2;    // pointwise bias or nullptr
-    const float* sc2;      // BatchNorm 2 folded or nullptr
-    const float* sh2;
-    void* y;               // pointwise output, NHWC: float32, or (YC) codes of the reader's quantizer
-    int N, H, W, C, Ho, Wo, O;   // images, dw input size, channels, dw output size, pointwise channels
-    int tiles_h, tiles_w, pad;
-    int KSb;               // k-steps per tile in the pointwise blob
-    int relu1, relu2;
-    int fmt_out;           // YC: format of the output codes (kFmtAct8 | kFmtSfp7)
-    float ka1, kw1;        // depthwise scales
-    float s1, s2, s1x;     // pointwise epilogue (Ka2, Kw2, Ka2 / 256)
-    uint32_t nblocks;
+struct DwPwCodesParams : DwPwBase {   // fmt_out (DwPwBase) is set for YC
     EncArgsCompact enc2;   // fp16(16 * QA(. / Ka_pw)), packed pairs (kEncF16P)
     EncArgsCompact encY;   // YC: code table of the reader's Ka (kEncCode); two compact tables: 4 KiB of kernel arguments in all
 };
 
-constexpr int kFcT = 512;                        // threads: 64 pixel slots x 8 channel quads in phase 1, 8 waves in phase 2
-
-// S: depthwise stride; KS: K / 32 (1, 2, 4); NT: N / 16 channel tiles (4, 8, 16); FMT: what the input codes are (kFmtAct8 |
-// kFmtSfp7); YC: output as codes (else float32)
+// S, KS, NT: DwPwGeom's; FMT: what the input codes are (kFmtAct8 | kFmtSfp7); YC: output as codes (else float32)
 template <int S, int KS, int NT, int FMT, bool YC>
-__global__ __launch_bounds__(kFcT, 2) void k_dwpw_codes(const DwPwCodesParams p) {
-    constexpr int TH = S == 2 ? 7 : 14, TW = TH;
-    constexpr int IH = (TH - 1) * S + 3, IW = IH;
-    constexpr int RPL = kFcT / 8 / 16;           // halo rows loaded per step (4)
-    constexpr int NI = (IH + RPL - 1) / RPL;
-    constexpr int ROWB = 16 * 32 * 4;
-    constexpr int NPX = TH * TW;                 // depthwise outputs of the tile = pointwise pixels
-    constexpr int NU = (NPX + 15) / 16;          // 16-pixel MFMA units (13 / 4)
-    constexpr int NWV = kFcT / 64;
-    constexpr int UW = (NU + NWV - 1) / NWV;     // units per wave
-    constexpr int K = KS * 32;
-    constexpr int XROW = K * 2 + 16;             // bytes per pixel row of the fp16 image (+16: conflict-free fragment reads)
-    constexpr int CW = TW > 8 ? 16 : 8, RPI = (kFcT / 8) / CW, NO = (TH + RPI - 1) / RPI;
+__global__ __launch_bounds__(kDwPwT, 2) void k_dwpw_codes(const DwPwCodesParams p) {
+    using G = DwPwGeom<S, KS, NT>;
+    constexpr int TH = G::TH, TW = G::TW, IH = G::IH, RPL = G::RPL, NI = G::NI, ROWB = G::ROWB, NPX = G::NPX, NU = G::NU, NWV = G::NWV, UW = G::UW;
     static_assert(NT % 4 == 0, "code output leaves in groups of 4 channel tiles");
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* dtab = smem;                                // 256-entry decode table (kDecF32)
     unsigned char* tab2 = dtab + kDecBytes;                    // pointwise quantizer (kEncF16P)
-    unsigned char* tabY = tab2 + kFcTab;                       // reader's code table (YC)
-    unsigned char* tile = tabY + kFcTab;                       // [RPL * NI rows][16 slots][32 ch] float32
-    unsigned char* x16 = tile + RPL * NI * ROWB;               // [NU * 16 rows][XROW]
-    unsigned char* wl = x16 + NU * 16 * XROW;                  // [tile j][k-step][lane] 16 B
-    float* ep = reinterpret_cast<float*>(wl + NT * KS * 1024);  // [3][NT * 16]
-    unsigned char* stg_all = tile;   // float32 out: [8 waves][2 KiB], phase 2 reuses the (then idle) halo tile
+    unsigned char* tabY = tab2 + kDwPwTab;                     // reader's code table (YC)
+    unsigned char* lds = tabY + kDwPwTab;
+    unsigned char *tile = lds + G::tile, *x16 = lds + G::x16, *wl = lds + G::wl;
+    float* ep = reinterpret_cast<float*>(lds + G::ep);
 
-    dec_fill<FMT, kDecF32, kFcT>(reinterpret_cast<uint32_t*>(dtab));
-    enc_fill_compact<kFcT>(reinterpret_cast<uint2*>(tab2), p.enc2);
-    if constexpr (YC) enc_fill_compact<kFcT>(reinterpret_cast<uint2*>(tabY), p.encY);
-    for (int i = threadIdx.x; i < NT * KS * 64; i += kFcT) {     // W -> LDS, 16 bytes per thread
+    dec_fill<FMT, kDecF32, kDwPwT>(reinterpret_cast<uint32_t*>(dtab));
+    enc_fill_compact<kDwPwT>(reinterpret_cast<uint2*>(tab2), p.enc2);
+    if constexpr (YC) enc_fill_compact<kDwPwT>(reinterpret_cast<uint2*>(tabY), p.encY);
+    for (int i = threadIdx.x; i < NT * KS * 64; i += kDwPwT) {     // W -> LDS, 16 bytes per thread
         const int l = i & 63, t = i >> 6, ks = t % KS, j = t / KS;
         *reinterpret_cast<u32x4*>(wl + (size_t)i * 16) = *reinterpret_cast<const u32x4*>(p.wpw + ((size_t)j * p.KSb + ks) * 512 + l * 8);
     }
-    for (int i = threadIdx.x; i < NT * 16; i += kFcT) {
-        ep[i] = p.bias2 ? bias_q256_1(p.bias2[i], p.s1, p.s2) : 0.f;
-        ep[NT * 16 + i] = p.sc2 ? p.sc2[i] : 1.f;
-        ep[2 * NT * 16 + i] = p.sc2 ? p.sh2[i] : 0.f;
-    }
-    for (int i = threadIdx.x; i < (NU * 16 - NPX) * (XROW / 8); i += kFcT)   // rows beyond the tile's pixels: zeros
-        reinterpret_cast<uint2*>(x16 + NPX * XROW)[i] = make_uint2(0u, 0u);
-
-    const uint32_t lb = xcd_remap(blockIdx.x, p.nblocks);
-    const uint32_t tiles_per_img = (uint32_t)(p.tiles_h * p.tiles_w);
-    const uint32_t n = lb / tiles_per_img, tr = lb - n * tiles_per_img;
-    const int th = (int)(tr / (uint32_t)p.tiles_w), tw = (int)(tr - (uint32_t)th * p.tiles_w);
-
-    const int c4 = threadIdx.x & 7, slot = threadIdx.x >> 3;
-    const int iw = slot & 15, ihh = slot >> 4;
-    const int colslot = (S == 2) ? ((iw & 1) * 8 + (iw >> 1)) : iw;
-    const uint32_t lds_w = (uint32_t)((ihh * 16 + colslot) * 128 + c4 * 16);
-    const bool col_live = iw < IW;
-    const int ow = slot & (CW - 1), ohb = slot / CW;
-    const bool ocol_live = ow < TW;
-    const uint32_t lds_r0 = (uint32_t)(((ohb * S) * 16 + ow) * 128 + c4 * 16);
+    dwpw_fill_ep_zero<G>(ep, x16, p);
+    const DwPwIdx d = dwpw_index<G>(p);
+    // in locals, as in k_dwpw
+    const uint32_t n = d.n, lds_w = d.lds_w, lds_r0 = d.lds_r0;
+    const int th = d.th, tw = d.tw, c4 = d.c4, iw = d.iw, ihh = d.ihh;
+    const bool col_live = d.col_live;
     const float r2 = p.enc2.r1, lo2 = p.enc2.lo, hi2 = p.enc2.hi;
 
     // the image's codes, 1 B per element: a lane's dword = 4 channels of one halo pixel
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(p.x) + (size_t)n * p.H * p.W * p.C, 0,
-                                                                         (uint32_t)p.H * p.W * p.C, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<uint8_t*>(reinterpret_cast<const uint8_t*>(p.x)) + (size_t)n * p.H * p.W * p.C, 0, (uint32_t)p.H * p.W * p.C, 0x00020000);
     const int gw = tw * TW * S - p.pad + iw;
     const int gh0 = th * TH * S - p.pad + ihh;
     const bool w_ok = col_live && (unsigned)gw < (unsigned)p.W;
@@ -132,7 +76,7 @@ __global__ __launch_bounds__(kFcT, 2) void k_dwpw_codes(const DwPwCodesParams p)
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
         const bool ok = w_ok && (unsigned)(gh0 + RPL * i) < (unsigned)p.H && (RPL * i + ihh) < IH;
-        voff[i] = ok ? off0 + (uint32_t)i * step : kFcOobLoad;
+        voff[i] = ok ? off0 + (uint32_t)i * step : kDwPwOobLoad;
         asm volatile("" : "+v"(voff[i]));
     }
     uint32_t v[NI];
@@ -156,33 +100,26 @@ __global__ __launch_bounds__(kFcT, 2) void k_dwpw_codes(const DwPwCodesParams p)
         for (int i = 0; i < NI; ++i) {
             // zero padding (and the halo slots outside the tile's window) = the exact-zero code, as in k_dwc: the returned 0 would be
             // the code of the "tiny" class
-            const uint32_t codes = voff[i] == kFcOobLoad ? 0x01010101u : v[i];
+            const uint32_t codes = voff[i] == kDwPwOobLoad ? 0x01010101u : v[i];
             *reinterpret_cast<float4*>(tile + lds_w + (uint32_t)i * (uint32_t)(RPL * ROWB)) = dec4_f32(codes, dtab);
         }
         __syncthreads();
         if (cg + 1 < KS) issue(cg + 1);   // in flight under the convolution below
 #pragma unroll
-        for (int j = 0; j < NO; ++j) {
+        for (int j = 0; j < G::NO; ++j) {   // k_dwc's epilogue, then the pointwise layer's quantizer
             floatx4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int kh = 0; kh < 3; ++kh) {
 #pragma unroll
                 for (int kw = 0; kw < 3; ++kw) {
-                    const int tap = j * RPI * S * ROWB + ((S == 1) ? (kh * ROWB + kw * 128) : (kh * ROWB + ((kw & 1) * 8 + (kw >> 1)) * 128));
+                    const int tap = j * G::RPI * S * ROWB + ((S == 1) ? (kh * ROWB + kw * 128) : (kh * ROWB + ((kw & 1) * 8 + (kw >> 1)) * 128));
                     const floatx4 a = *reinterpret_cast<const floatx4*>(tile + lds_r0 + tap);
                     const floatx4 w = wt[kh * 3 + kw];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) acc[e] = fmaf(a[e], w[e], acc[e]);
                 }
             }
-            float4 rr;   // k_dwc's epilogue, then the pointwise layer's quantizer
-            {
-                float u0 = (acc[0] * p.ka1) * p.kw1, u1 = (acc[1] * p.ka1) * p.kw1, u2 = (acc[2] * p.ka1) * p.kw1, u3 = (acc[3] * p.ka1) * p.kw1;
-                u0 = __builtin_fmaf(u0, psc[0], psh[0]); u1 = __builtin_fmaf(u1, psc[1], psh[1]);
-                u2 = __builtin_fmaf(u2, psc[2], psh[2]); u3 = __builtin_fmaf(u3, psc[3], psh[3]);
-                if (p.relu1) { u0 = fmaxf(u0, 0.f); u1 = fmaxf(u1, 0.f); u2 = fmaxf(u2, 0.f); u3 = fmaxf(u3, 0.f); }
-                rr = make_float4(u0, u1, u2, u3);
-            }
+            const float4 rr = dwpw_bn1(acc, psc, psh, p);
             uint2 q = enc4_f16_raw(rr, r2, lo2, hi2, tab2);
             if (__builtin_expect(enc_has_nan4(rr), 0)) {   // no ReLU in front: k_dwc gives a NaN the code 0x00, whose operand is the fp16 zero
                 if (rr.x != rr.x) q.x &= 0xFFFF0000u;
@@ -190,9 +127,7 @@ __global__ __launch_bounds__(kFcT, 2) void k_dwpw_codes(const DwPwCodesParams p)
                 if (rr.z != rr.z) q.y &= 0xFFFF0000u;
                 if (rr.w != rr.w) q.y &= 0x0000FFFFu;
             }
-            const int oh = ohb + j * RPI;
-            if (ocol_live && oh < TH)
-                *reinterpret_cast<uint2*>(x16 + (uint32_t)(oh * TW + ow) * XROW + (uint32_t)(cg * 64 + c4 * 8)) = q;
+            dwpw_put_quad<G>(x16, d, j, cg, q);
         }
         __syncthreads();   // the tile is free for the next group; after the last group: the fp16 image is complete
     }
@@ -203,24 +138,13 @@ __global__ __launch_bounds__(kFcT, 2) void k_dwpw_codes(const DwPwCodesParams p)
     half8 xh[UW][KS];
 #pragma unroll
     for (int ui = 0; ui < UW; ++ui) {
-        const int u = wv + NWV * ui;
-        const unsigned char* row = x16 + (uint32_t)((u < NU ? u : NU - 1) * 16 + col) * XROW + kq * 8;
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const u32x2 a = *reinterpret_cast<const u32x2*>(row + ks * 64);
-            const u32x2 b = *reinterpret_cast<const u32x2*>(row + ks * 64 + 32);
-            xh[ui][ks] = __builtin_bit_cast(half8, u32x4{a[0], a[1], b[0], b[1]});
-        }
+        for (int ks = 0; ks < KS; ++ks) xh[ui][ks] = dwpw_frag<G>(x16, wv + NWV * ui, col, kq, ks);
     }
     const int oh0 = th * TH, ow0 = tw * TW;
     // the tile epilogue of k_pwc_stream: channels j * 16 + kq * 4 .. + 3 of pixel `col` of unit ui
     auto tile_out = [&](int ui, int j) {
-        floatx4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const half8 wf = *reinterpret_cast<const half8*>(wl + (uint32_t)((j * KS + ks) * 1024) + lane * 16);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf, xh[ui][ks], acc, 0, 0, 0);
-        }
+        const floatx4 acc = dwpw_mma<G>(wl, xh[ui], j, lane);
         const int nl = j * 16 + kq * 4;
         float4 r = epilogue(acc, *reinterpret_cast<const float4*>(ep + nl), p.s1x, p.s2);
         if (p.sc2) r = affine4(r, *reinterpret_cast<const float4*>(ep + NT * 16 + nl), *reinterpret_cast<const float4*>(ep + 2 * NT * 16 + nl));
@@ -247,7 +171,7 @@ __global__ __launch_bounds__(kFcT, 2) void k_dwpw_codes(const DwPwCodesParams p)
 #pragma unroll
                     for (int jj = 0; jj < 4; ++jj) c[jj] = code4<false, false>(tile_out(ui, j0 + jj), cq, tabY);
                     rows_transpose4(c[0], c[1], c[2], c[3]);   // lane-quarter kq now holds channels 16 (j0 + kq) + 0..15 of its pixel
-                    uint32_t so = live ? pixoff + (uint32_t)((j0 + kq) * 16) : kFcOobStore;
+                    uint32_t so = live ? pixoff + (uint32_t)((j0 + kq) * 16) : kDwPwOob;
                     asm volatile("" : "+v"(so));
                     __builtin_amdgcn_raw_buffer_store_b128(u32x4{c[0], c[1], c[2], c[3]}, ry, so, 0, 0);
                 }
@@ -256,7 +180,7 @@ __global__ __launch_bounds__(kFcT, 2) void k_dwpw_codes(const DwPwCodesParams p)
     } else {
         const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(p.y) + (size_t)n * p.Ho * p.Wo * p.O, 0,
                                                                              (uint32_t)p.Ho * p.Wo * p.O * 4u, 0x00020000);
-        unsigned char* stg = stg_all + wv * 2048;
+        unsigned char* stg = tile + wv * 2048;   // [8 waves][2 KiB]: phase 2 reuses the (then idle) halo tile
         const int spx = lane >> 3, sch = lane & 7;
 #pragma unroll 1
         for (int j0 = 0; j0 < NT; j0 += 2) {
@@ -274,7 +198,7 @@ __global__ __launch_bounds__(kFcT, 2) void k_dwpw_codes(const DwPwCodesParams p)
                         const int pix = u * 16 + spx + 8 * h;                      // pixel of the tile
                         const int oh = pix / TW, owp = pix - oh * TW;
                         const bool live = pix < NPX && (oh0 + oh) < p.Ho && (ow0 + owp) < p.Wo;
-                        uint32_t so = live ? (uint32_t)(((oh0 + oh) * p.Wo + ow0 + owp) * p.O + j0 * 16 + sch * 4) * 4u : kFcOobStore;
+                        uint32_t so = live ? (uint32_t)(((oh0 + oh) * p.Wo + ow0 + owp) * p.O + j0 * 16 + sch * 4) * 4u : kDwPwOob;
                         asm volatile("" : "+v"(so));
                         __builtin_amdgcn_raw_buffer_store_b128(vv, ry, so, 0, 0);
                     }
@@ -285,11 +209,7 @@ __global__ __launch_bounds__(kFcT, 2) void k_dwpw_codes(const DwPwCodesParams p)
 }
 
 // ---------------------------------------------------------------------------- host
-static size_t dwpw_codes_lds(int S, int KS, int NT) {
-    const int TH = S == 2 ? 7 : 14, IH = (TH - 1) * S + 3, NI = (IH + 3) / 4, NU = (TH * TH + 15) / 16;
-    return (size_t)kDecBytes + (size_t)2 * kFcTab + (size_t)4 * NI * 16 * 32 * 4 + (size_t)NU * 16 * (KS * 64 + 16) + (size_t)NT * KS * 1024 +
-           (size_t)3 * NT * 16 * 4;
-}
+static size_t dwpw_codes_lds(int S, int KS, int NT) { return (size_t)kDecBytes + (size_t)2 * kDwPwTab + dwpw_geom_bytes(S, KS, NT); }
 
 // the reader's quantizer of a code-writing call (conv_abi.hip: consumer_quant_ok), and its table in the form the kernel carries
 static const EncArgs* dwpw_codes_reader(const slfp_conv2d_io& io) {
@@ -312,7 +232,7 @@ bool dwpw_codes_select(const slfp_conv2d_desc* dw, const slfp_conv2d_desc* pw, c
     if (!t2 || !enc_compact_covers(*t2)) return false;
     if (io->y_codes && !dwpw_codes_reader(*io)) return false;
     if (dwpw_codes_lds(s->s, s->ks, s->nt) > 160 * 1024) return false;
-    const int TH = s->s == 2 ? 7 : 14;
+    const int TH = dwpw_th(s->s);
     const int64_t nblocks = dw->n * ceil_div(p1.h_out, TH) * ceil_div(p1.w_out, TH);
     if (nblocks > 0x7FFFFFFF || dw->h * dw->w * dw->c_in >= (1ll << 29) || p1.h_out * p1.w_out * pw->c_out >= (1ll << 29)) return false;
     s->fmt_in = p1.fmt_act;
@@ -353,7 +273,7 @@ static int launch_dwpw_codes(const DwPwCodesParams& p, bool sfp7, bool yc, size_
                    : (yc ? k_dwpw_codes<S, KS, NT, kFmtAct8, true> : k_dwpw_codes<S, KS, NT, kFmtAct8, false>);
     const int rc = raise_lds_limit(reinterpret_cast<const void*>(fn), lds);
     if (rc != SLFP_OK) return rc;
-    hipLaunchKernelGGL(fn, dim3(p.nblocks), dim3(kFcT), lds, st, p);
+    hipLaunchKernelGGL(fn, dim3(p.nblocks), dim3(kDwPwT), lds, st, p);
     return check_launch("slfp fused depthwise + pointwise kernel (codes)");
 }
 
@@ -374,19 +294,10 @@ extern "C" int slfp_dwpw_fwd_codes(const slfp_conv2d_desc* dw, const slfp_conv2d
     ConvPlan p1, p2;
     make_plan(dw, &p1);
     make_plan(pw, &p2);
-    const int S = sel.s, TH = S == 2 ? 7 : 14;
-    const int ks = sel.ks, nt = sel.nt;
+    const int S = sel.s, ks = sel.ks, nt = sel.nt;
     DwPwCodesParams p;
-    p.x = reinterpret_cast<const uint8_t*>(x); p.wdw = reinterpret_cast<const float*>(wprep_dw); p.sc1 = post1_scale; p.sh1 = post1_shift;
-    p.wpw = reinterpret_cast<const _Float16*>(wprep_pw); p.bias2 = bias_pw; p.sc2 = post2_scale; p.sh2 = post2_shift; p.y = y;
-    p.N = (int)dw->n; p.H = (int)dw->h; p.W = (int)dw->w; p.C = (int)dw->c_in; p.Ho = (int)p1.h_out; p.Wo = (int)p1.w_out; p.O = (int)pw->c_out;
-    p.tiles_h = (int)ceil_div(p.Ho, TH); p.tiles_w = (int)ceil_div(p.Wo, TH); p.pad = dw->pad_h;
-    p.KSb = (int)(p2.k_pad / 32);
-    p.relu1 = relu1; p.relu2 = relu2;
+    dwpw_fill_base(p, dw, pw, p1, p2, x, wprep_dw, post1_scale, post1_shift, relu1, wprep_pw, bias_pw, post2_scale, post2_shift, relu2, y);
     p.fmt_out = io->y_qbits == 7 ? kFmtSfp7 : kFmtAct8;
-    p.ka1 = dw->ka; p.kw1 = dw->kw_scale;
-    p.s1 = p2.s1; p.s2 = p2.s2; p.s1x = p2.s1 * (1.0f / 256.0f);
-    p.nblocks = (uint32_t)((int64_t)p.N * p.tiles_h * p.tiles_w);
     p.enc2 = enc_compact(*act_table(pw->ka, p2.fmt_act, kEncF16P));
     p.encY = io->y_codes ? enc_compact(*dwpw_codes_reader(*io)) : p.enc2;   // float32 out: not read
     static_assert(sizeof(DwPwCodesParams) <= 4096, "kernel arguments must fit the 4 KiB kernarg segment");

@@ -181,7 +181,8 @@ int launch_dwc(const slfp_conv2d_desc& d, const ConvPlan& p, const uint8_t* x, c
                void* y, const CodeIo& io, hipStream_t stream);
 // the k_dwc instance launch_dwc runs, printed from the selection it consumes (slfp_debug_dw3x3_instance; host only)
 const char* dwc_instance_name(const slfp_conv2d_desc& d, const ConvPlan& p, const PostOp& post, const CodeIo& io);
-// ---- one depthwise -> pointwise block in one kernel (conv_dwpw.hip: k_dwpw, conv_dwpw_codes.hip: k_dwpw_codes) ----
+// ---- one depthwise -> pointwise block in one kernel (conv_dwpw.hip: k_dwpw, conv_dwpw_codes.hip: k_dwpw_codes; their common
+// geometry, LDS size, parameters and device steps: conv_dwpw_core.hpp) ----
 // The (S, KS, NT) instances both kernels are built for.  The selections behind the queries (through dwpw_instance_built) and the two
 // launchers' dispatch expand this one list, so a pair a query accepts always has a kernel to run.
 #define SLFP_DWPW_INSTANCES(X)                                                                                   \
