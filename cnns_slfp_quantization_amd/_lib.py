@@ -40,7 +40,7 @@ SYMBOLS = (
     "slfp_dwpw_codes_supported", "slfp_dwpw_fwd_codes",
     "slfp_linear_fc_supported", "slfp_linear_fc_workspace_bytes", "slfp_linear_fwd_fc", "slfp_debug_linear_fc_tiles",
     "slfp_global_avgpool_supported", "slfp_global_avgpool_f32",
-    "slfp_debug_dw3x3_instance", "slfp_debug_code_relu_mismatches",
+    "slfp_debug_dw3x3_instance", "slfp_debug_stem_instance", "slfp_debug_code_relu_mismatches",
     "slfp_bn_train_supported", "slfp_bn_train_workspace_bytes", "slfp_bn_train_fwd", "slfp_bn_train_bwd", "slfp_debug_bn_split",
     "slfp_debug_dwpw_instance",
 )
@@ -110,6 +110,7 @@ def load():
         "slfp_conv2d_kernel_name": (ctypes.c_char_p, [dp]),
         "slfp_debug_dw3x3_variant": (ctypes.c_char_p, [dp, ci]),
         "slfp_debug_dw3x3_instance": (ctypes.c_char_p, [dp, ctypes.POINTER(ConvIo), ci, ci, ci]),
+        "slfp_debug_stem_instance": (ctypes.c_char_p, [dp, ctypes.POINTER(ConvIo), ci, ci, ci]),
         "slfp_debug_code_relu_mismatches": (ci, [cf, ci, vp, vp]),
         "slfp_debug_dense_variant": (ctypes.c_char_p, [dp, ci]),
         "slfp_debug_pw_variant": (ctypes.c_char_p, [dp, ctypes.POINTER(ConvIo), ci, ci, i64]),

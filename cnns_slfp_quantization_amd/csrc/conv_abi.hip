@@ -253,6 +253,7 @@ using namespace slfp;
 
 static const char* pw_variant(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, bool has_res, bool has_res_codes, int64_t y_ld);
 static const char* dw3x3_instance(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, bool has_bias, int post_flags, bool has_post);
+static const char* stem_instance(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, bool has_bias, int post_flags, bool has_post);
 
 extern "C" {
 
@@ -282,6 +283,10 @@ const char* slfp_debug_dw3x3_variant(const slfp_conv2d_desc* d, int has_post) {
 
 const char* slfp_debug_dw3x3_instance(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int post_flags, int has_post) {
     return dw3x3_instance(d, io, has_bias != 0, post_flags, has_post != 0);
+}
+
+const char* slfp_debug_stem_instance(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int post_flags, int has_post) {
+    return stem_instance(d, io, has_bias != 0, post_flags, has_post != 0);
 }
 
 const char* slfp_debug_dense_variant(const slfp_conv2d_desc* d, int x_codes) {
@@ -504,6 +509,41 @@ static const char* dw3x3_instance(const slfp_conv2d_desc* d, const slfp_conv2d_i
     }
     if (codes_route(d, io, has_bias, post_flags, p) != kRouteDwc) return "none";   // slfp_conv2d_fwd_codes
     return dwc_instance_name(*d, p, post, cio);
+}
+
+// slfp_debug_stem_instance: the route the matching forward entry point takes (refused: "none"), then the launcher's own selection.
+static const char* stem_instance(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, bool has_bias, int post_flags, bool has_post) {
+    ConvPlan p;
+    if (!d || make_plan(d, &p) != SLFP_OK || p.repad) return "none";
+    if (p.family != kDirect && p.family != kStemSmall && p.family != kStemMfma) return "none";
+    if ((post_flags & ~(SLFP_POST_RELU | SLFP_POST_LAYEROUT)) != 0) return "none";
+    static const float one = 1.f;   // the selections only ask whether a scale / shift pair is present
+    const float* vec = has_post ? &one : nullptr;
+    if (!io || (!io->x_codes && !io->y_codes)) {   // slfp_conv2d_fwd / slfp_conv2d_fwd_post
+        if ((post_flags & SLFP_POST_LAYEROUT) && !has_post) return "none";
+        const PostOp post{vec, vec, (post_flags & SLFP_POST_RELU) ? 1 : 0, (post_flags & SLFP_POST_LAYEROUT) ? 1 : 0};
+        const CodeIo f32{false, false, 1.f, kFmtAct8};
+        if (p.family == kStemSmall) return stem_small_instance_name(*d, p, post, f32);
+        if (p.family == kStemMfma) return stem_mfma_instance_name(*d, p, post, f32);
+        return direct_instance_name(*d, p, post, nullptr);
+    }
+    if (io->x_codes) return "none";   // the image stems and the direct kernel read float32
+    const PostOp post{vec, vec, (post_flags & SLFP_POST_RELU) ? 1 : 0, 0};
+    CodeIo cio{false, true, io->y_ka, y_fmt_of(io->y_qbits), 0};
+    CodeRoute route;
+    if (post_flags & SLFP_POST_LAYEROUT) {   // slfp_conv2d_fwd_codes_lut: the layer-output quantizer in front of codes is the table epilogue
+        if (!has_post || (post_flags & SLFP_POST_RELU)) return "none";
+        route = lut_route(d, io, has_bias, p);
+        cio.lut = reinterpret_cast<const uint8_t*>(&one);   // the selections only ask whether there is a table
+    } else {
+        route = codes_route(d, io, has_bias, post_flags, p);   // slfp_conv2d_fwd_codes / slfp_conv2d_fwd_codes_ws
+    }
+    switch (route) {
+        case kRouteStemCodes: return direct_instance_name(*d, p, post, &cio);
+        case kRouteStemSmall: return stem_small_instance_name(*d, p, post, cio);
+        case kRouteStemMfma: return stem_mfma_instance_name(*d, p, post, cio);
+        default: return "none";
+    }
 }
 
 // slfp_debug_layerout_lut_mismatches: every float32 pattern through layerout_bits, its class and back

@@ -635,12 +635,25 @@ bool stem_applicable(const slfp_conv2d_desc& d) {
     return 64 + (((n_w + 3) & ~(size_t)3) + ih * iwc) * sizeof(float) <= 64 * 1024;
 }
 
-// Returns SLFP_OK if it launched, 1 if this geometry is not a stem (caller falls back).
-static int try_launch_stem(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x, const float* wq_hwio,
-                           const float* bias, const PostOp& post, float* y, hipStream_t stream, const CodeIo* io = nullptr) {
+// Everything try_launch_stem and launch_direct decide, worked out in ONE place each (stem_select, direct_select): the launchers only
+// dispatch on the selection and direct_instance_name (slfp_debug_stem_instance) prints it, so the reported string cannot drift from
+// what runs; stem_codes_applicable (behind slfp_conv2d_codes_supported / slfp_conv2d_codes_lut_supported) asks the same selection.
+enum StemKernel { kStemGen = 0, kStemFixedLong, kStemFixedTab, kStemMx };
+enum StemOut { kStemOutF32 = 0, kStemOutYc, kStemOutYcSigned, kStemOutLut };
+struct StemSel {
+    int kernel;   // StemKernel: k_stem<FMT> | k_stem_fixed<FMT, 3, 3, 3, 2, 32> | k_stem_fixed<.., TAB, 16, YC, LUTQ> | k_stem_mx<YC, LUTQ>
+    bool a8;      // FMT of k_stem and of the long-form k_stem_fixed: Act8 (else SFP7)
+    int P;        // k_stem: output rows per thread (2 / 4 / 8 for O = 16 / 32 / 64)
+    int out;      // StemOut: float32, codes with the ReLU folded into the quantizer, signed codes, the table epilogue
+    size_t lds;   // k_stem: dynamic LDS bytes
+};
+
+// SLFP_OK: `p` and `sel` describe the launch; 1: this geometry is not a stem (caller falls back); < 0: refused (error text recorded).
+// io (may be null): the code interface's arguments; only whether io->lut is set is looked at, not what it points to.
+static int stem_select(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post, const CodeIo* io, StemParams* pp, StemSel* sel) {
+    StemParams& p = *pp;
     const int O = (int)d.c_out, C = (int)d.c_in;
     if (!stem_applicable(d)) return 1;
-    StemParams p;
     p.post = post;
     p.N = (int)d.n; p.H = (int)d.h; p.W = (int)d.w; p.C = C; p.O = O; p.KH = (int)d.kh; p.KW = (int)d.kw;
     p.s = d.stride_h; p.ph = d.pad_h; p.pw = d.pad_w;
@@ -653,14 +666,18 @@ static int try_launch_stem(const slfp_conv2d_desc& d, const ConvPlan& plan, cons
     p.P = kStemTH / (groups / kStemTW);             // 2, 4 or 8 rows per thread
     p.step_h = 256 / p.IWC; p.step_j = 256 % p.IWC;
     p.sd = make_scale_div(d.ka); p.s1 = plan.s1; p.s2 = plan.s2;
+    p.sgn = 0; p.fmt_out = kFmtAct8; p.enc_out.valid = 0;
     const size_t n_w = (size_t)p.KH * p.KW * C * O;
     const size_t lds = 64 + (((n_w + 3) & ~(size_t)3) + (size_t)p.IH * p.IWC) * sizeof(float);
     if (lds > 64 * 1024) return 1;
     const int64_t nblocks = (int64_t)p.N * p.tiles_h * p.tiles_w;
     if (nblocks > 0x7FFFFFFF) return 1;
     p.nblocks = (uint32_t)nblocks;
+    sel->kernel = kStemGen; sel->a8 = plan.fmt_act == kFmtAct8; sel->P = p.P; sel->out = kStemOutF32; sel->lds = lds;
     if (p.KH == 3 && p.KW == 3 && C == 3 && p.s == 2 && O == 32 && (int64_t)p.H * p.W * C < (1ll << 30)) {
         // the MobileNetV1 stem (nets_imgnet/mobilenetv1.py:44): fully specialised variant
+        sel->lds = 0;
+        sel->kernel = kStemFixedLong;
         if (const EncArgs* t = act_table(d.ka, plan.fmt_act, kEncF32)) {
             p.enc = *t;
             constexpr int TH = 16;
@@ -668,52 +685,80 @@ static int try_launch_stem(const slfp_conv2d_desc& d, const ConvPlan& plan, cons
             p.nblocks = (uint32_t)((int64_t)p.N * p.tiles_h * p.tiles_w);
             // float32 matrix-core stem (k_stem_mx) with aligned 16-byte halo loads: measured (round 3, same box, us per launch at
             // batch 256) 111.8 vs 123.0 for the vector kernel with float32 output, 117.8 vs 131.4 with code output ->
-            // the default for both; SLFP_STEM_OLD keeps the vector kernel.  Bit-identical either way (tests/test_gpu_parity.py).
-            const bool mx = !switches().stem_old && (p.W * C) % 4 == 0;   // k_stem_mx loads aligned float4 pieces of the image rows
-            if (mx && !(io && io->y_codes)) {
-                hipLaunchKernelGGL((k_stem_mx<false>), dim3(p.nblocks), dim3(256), 0, stream, x, wq_hwio, bias, y, p);
-                return check_launch("slfp stem conv kernel (3x3x3 s2 -> 32, float32 MFMA)");
-            }
-            if (io && io->lut) {       // the table epilogue (slfp_conv2d_fwd_codes_lut)
-                if (!io->y_codes || !post.scale) return fail(SLFP_ERR_BAD_ARG, "stem (codes): the table epilogue needs code output and post_scale / post_shift");
-                p.enc_out.valid = 0;
-                enc_carry_ptr(p.enc_out, io->lut);
-                p.sgn = 1;
-                p.fmt_out = io->y_fmt;
-                if (mx) hipLaunchKernelGGL((k_stem_mx<true, true>), dim3(p.nblocks), dim3(256), 0, stream, x, wq_hwio, bias, y, p);
-                else hipLaunchKernelGGL((k_stem_fixed<kFmtAct8, 3, 3, 3, 2, 32, true, TH, true, true>), dim3(p.nblocks), dim3(256), 0, stream, x, wq_hwio, bias, y, p);
-                return check_launch("slfp stem conv kernel (3x3x3 s2 -> 32, table epilogue)");
-            }
-            if (io && io->y_codes) {   // output as the next layer's codes (slfp_conv2d_fwd_codes)
-                const EncArgs* tc = enc_table(io->y_ka, io->y_fmt, kEncCode);
-                if (!tc->valid) return fail(SLFP_ERR_UNSUPPORTED, "stem (codes): no code table for the consumer's scale %g", (double)io->y_ka);
-                p.enc_out = enc_compact(*tc);
-                p.sgn = post.relu ? 0 : 1;
-                p.fmt_out = io->y_fmt;
-                if (mx) hipLaunchKernelGGL((k_stem_mx<true>), dim3(p.nblocks), dim3(256), 0, stream, x, wq_hwio, bias, y, p);
-                else hipLaunchKernelGGL((k_stem_fixed<kFmtAct8, 3, 3, 3, 2, 32, true, TH, true>), dim3(p.nblocks), dim3(256), 0, stream, x, wq_hwio, bias, y, p);
-                return check_launch("slfp stem conv kernel (3x3x3 s2 -> 32, codes out)");
-            }
-            hipLaunchKernelGGL((k_stem_fixed<kFmtAct8, 3, 3, 3, 2, 32, true, TH>), dim3(p.nblocks), dim3(256), 0, stream, x, wq_hwio, bias, y, p);
-        } else if (plan.fmt_act == kFmtAct8)
-            hipLaunchKernelGGL((k_stem_fixed<kFmtAct8, 3, 3, 3, 2, 32>), dim3(p.nblocks), dim3(256), 0, stream, x, wq_hwio, bias, y, p);
-        else
-            hipLaunchKernelGGL((k_stem_fixed<kFmtSfp7, 3, 3, 3, 2, 32>), dim3(p.nblocks), dim3(256), 0, stream, x, wq_hwio, bias, y, p);
-        return check_launch("slfp stem conv kernel (3x3x3 s2 -> 32)");
+            // the default for both; SLFP_STEM_OLD keeps the vector kernel.  Bit-identical either way (tests/test_gpu_stem_variants.py).
+            // k_stem_mx loads aligned float4 pieces of the 100-float superset of a halo row that starts at float (tw 32 - pad_w) 3 - 1
+            // of the image row: a float4 lies wholly inside or outside the row only when W * C is a multiple of 4, and the superset
+            // starts on a multiple of 4 only when pad_w = 1 (mod 4).  Every other padding stays on k_stem_fixed, whose guarded
+            // dword / buffer loads are general in it.
+            const bool mx = !switches().stem_old && (p.W * C) % 4 == 0 && p.pw % 4 == 1;
+            sel->kernel = mx ? kStemMx : kStemFixedTab;
+        }
     }
-    if (plan.fmt_act == kFmtAct8)
-        hipLaunchKernelGGL((k_stem<kFmtAct8>), dim3(p.nblocks), dim3(256), lds, stream, x, wq_hwio, bias, y, p);
+    if (!io || (!io->y_codes && !io->lut)) return SLFP_OK;
+    // code output: the two table kernels of the MobileNetV1 stem only, on SLFP<3,4> input
+    if ((sel->kernel != kStemMx && sel->kernel != kStemFixedTab) || plan.fmt_act != kFmtAct8)
+        return fail(SLFP_ERR_UNSUPPORTED, "stem (codes): unsupported geometry");
+    if (io->lut) {       // the table epilogue (slfp_conv2d_fwd_codes_lut)
+        if (!io->y_codes || !post.scale) return fail(SLFP_ERR_BAD_ARG, "stem (codes): the table epilogue needs code output and post_scale / post_shift");
+        p.enc_out.valid = 0;
+        enc_carry_ptr(p.enc_out, io->lut);
+        p.sgn = 1;
+        p.fmt_out = io->y_fmt;
+        sel->out = kStemOutLut;
+        return SLFP_OK;
+    }
+    // output as the next layer's codes (slfp_conv2d_fwd_codes)
+    const EncArgs* tc = enc_table(io->y_ka, io->y_fmt, kEncCode);
+    if (!tc->valid) return fail(SLFP_ERR_UNSUPPORTED, "stem (codes): no code table for the consumer's scale %g", (double)io->y_ka);
+    p.enc_out = enc_compact(*tc);
+    p.sgn = post.relu ? 0 : 1;
+    p.fmt_out = io->y_fmt;
+    sel->out = post.relu ? kStemOutYc : kStemOutYcSigned;
+    return SLFP_OK;
+}
+
+// Returns SLFP_OK if it launched, 1 if this geometry is not a stem (caller falls back).
+static int try_launch_stem(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x, const float* wq_hwio,
+                           const float* bias, const PostOp& post, float* y, hipStream_t stream, const CodeIo* io = nullptr) {
+    StemParams p;
+    StemSel s;
+    const int rc = stem_select(d, plan, post, io, &p, &s);
+    if (rc != SLFP_OK) return rc;
+    const dim3 grid(p.nblocks), block(256);
+    constexpr int TH = 16;
+#define SLFP_STEM_ARGS grid, block, 0, stream, x, wq_hwio, bias, y, p
+    switch (s.kernel) {
+        case kStemMx:
+            if (s.out == kStemOutF32) hipLaunchKernelGGL((k_stem_mx<false>), SLFP_STEM_ARGS);
+            else if (s.out == kStemOutLut) hipLaunchKernelGGL((k_stem_mx<true, true>), SLFP_STEM_ARGS);
+            else hipLaunchKernelGGL((k_stem_mx<true>), SLFP_STEM_ARGS);
+            return check_launch("slfp stem conv kernel (3x3x3 s2 -> 32, float32 MFMA)");
+        case kStemFixedTab:
+            if (s.out == kStemOutF32) hipLaunchKernelGGL((k_stem_fixed<kFmtAct8, 3, 3, 3, 2, 32, true, TH>), SLFP_STEM_ARGS);
+            else if (s.out == kStemOutLut) hipLaunchKernelGGL((k_stem_fixed<kFmtAct8, 3, 3, 3, 2, 32, true, TH, true, true>), SLFP_STEM_ARGS);
+            else hipLaunchKernelGGL((k_stem_fixed<kFmtAct8, 3, 3, 3, 2, 32, true, TH, true>), SLFP_STEM_ARGS);
+            return check_launch("slfp stem conv kernel (3x3x3 s2 -> 32)");
+        case kStemFixedLong:
+            if (s.a8) hipLaunchKernelGGL((k_stem_fixed<kFmtAct8, 3, 3, 3, 2, 32>), SLFP_STEM_ARGS);
+            else hipLaunchKernelGGL((k_stem_fixed<kFmtSfp7, 3, 3, 3, 2, 32>), SLFP_STEM_ARGS);
+            return check_launch("slfp stem conv kernel (3x3x3 s2 -> 32)");
+        default: break;
+    }
+#undef SLFP_STEM_ARGS
+    if (s.a8)
+        hipLaunchKernelGGL((k_stem<kFmtAct8>), grid, block, s.lds, stream, x, wq_hwio, bias, y, p);
     else
-        hipLaunchKernelGGL((k_stem<kFmtSfp7>), dim3(p.nblocks), dim3(256), lds, stream, x, wq_hwio, bias, y, p);
+        hipLaunchKernelGGL((k_stem<kFmtSfp7>), grid, block, s.lds, stream, x, wq_hwio, bias, y, p);
     return check_launch("slfp stem conv kernel");
 }
 
-// The MobileNetV1 stem (float32 image in) writing the next layer's codes: only the fully specialised table variant.
+// The MobileNetV1 stem (float32 image in) writing the next layer's codes: where the selection picks one of the two table kernels.
 bool stem_codes_applicable(const slfp_conv2d_desc& d, const ConvPlan& plan, int post_flags) {
-    if (plan.family != kDirect || !stem_applicable(d) || (post_flags & SLFP_POST_LAYEROUT)) return false;
-    if (!(d.kh == 3 && d.kw == 3 && d.c_in == 3 && d.stride_h == 2 && d.c_out == 32 && plan.fmt_act == kFmtAct8)) return false;
-    if ((int64_t)d.h * d.w * d.c_in >= (1ll << 30)) return false;
-    return act_table(d.ka, plan.fmt_act, kEncF32) != nullptr;
+    if (plan.family != kDirect || (post_flags & SLFP_POST_LAYEROUT) || plan.fmt_act != kFmtAct8) return false;
+    StemParams p;
+    StemSel s;
+    const PostOp none{nullptr, nullptr, 0, 0};
+    return stem_select(d, plan, none, nullptr, &p, &s) == SLFP_OK && (s.kernel == kStemMx || s.kernel == kStemFixedTab);
 }
 
 int launch_stem_codes(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x, const float* wq_hwio, const float* bias,
@@ -722,13 +767,17 @@ int launch_stem_codes(const slfp_conv2d_desc& d, const ConvPlan& plan, const flo
     return rc == 1 ? fail(SLFP_ERR_UNSUPPORTED, "stem (codes): unsupported geometry") : rc;
 }
 
-int launch_direct(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x, const float* wq_hwio,
-                  const float* bias, const PostOp& post, float* y, hipStream_t stream) {
-    {
-        const int rc = try_launch_stem(d, plan, x, wq_hwio, bias, post, y, stream);
-        if (rc <= 0) return rc;  // launched (0) or failed (<0); 1 = not a stem geometry
-    }
-    DirParams p;
+struct DirSel {
+    bool a8;        // FMT: Act8 (else SFP7)
+    int cc;         // CC: input channels per LDS chunk (<= 32, <= Cg, cut by the 48 KiB halo budget); a runtime argument
+    int oc_chunks;  // 64-channel output chunks per group; a runtime argument
+    int lanes;      // what the kernel's threads decide from O and Og: 0 every live thread takes the 16-byte weight loads and stores,
+                    // 1 none does (C_out no multiple of 4), 2 both kinds (C_out a multiple of 4, C_out / groups not)
+    size_t lds;
+};
+
+static int direct_select(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post, DirParams* pp, DirSel* sel) {
+    DirParams& p = *pp;
     p.post = post;
     p.N = (int)d.n; p.H = (int)d.h; p.W = (int)d.w; p.C = (int)d.c_in; p.O = (int)d.c_out;
     p.KH = (int)d.kh; p.KW = (int)d.kw;
@@ -750,12 +799,57 @@ int launch_direct(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* 
     const int64_t nblocks = (int64_t)p.N * p.tiles_h * p.tiles_w * p.groups * p.oc_chunks;
     if (nblocks > 0x7FFFFFFF) return fail(SLFP_ERR_UNSUPPORTED, "direct conv: grid too large");
     p.nblocks = (uint32_t)nblocks;
-    const size_t lds = 64 + (size_t)p.IH * p.IW * p.CC * sizeof(float);
-    if (plan.fmt_act == kFmtAct8)
-        hipLaunchKernelGGL((k_direct<kFmtAct8>), dim3(p.nblocks), dim3(kDirThreads), lds, stream, x, wq_hwio, bias, y, p);
+    sel->a8 = plan.fmt_act == kFmtAct8;
+    sel->cc = p.CC; sel->oc_chunks = p.oc_chunks;
+    sel->lanes = (p.O & 3) ? 1 : ((p.Og & 3) ? 2 : 0);
+    sel->lds = 64 + (size_t)p.IH * p.IW * p.CC * sizeof(float);
+    return SLFP_OK;
+}
+
+int launch_direct(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x, const float* wq_hwio,
+                  const float* bias, const PostOp& post, float* y, hipStream_t stream) {
+    {
+        const int rc = try_launch_stem(d, plan, x, wq_hwio, bias, post, y, stream);
+        if (rc <= 0) return rc;  // launched (0) or failed (<0); 1 = not a stem geometry
+    }
+    DirParams p;
+    DirSel s;
+    const int rc = direct_select(d, plan, post, &p, &s);
+    if (rc != SLFP_OK) return rc;
+    if (s.a8)
+        hipLaunchKernelGGL((k_direct<kFmtAct8>), dim3(p.nblocks), dim3(kDirThreads), s.lds, stream, x, wq_hwio, bias, y, p);
     else
-        hipLaunchKernelGGL((k_direct<kFmtSfp7>), dim3(p.nblocks), dim3(kDirThreads), lds, stream, x, wq_hwio, bias, y, p);
+        hipLaunchKernelGGL((k_direct<kFmtSfp7>), dim3(p.nblocks), dim3(kDirThreads), s.lds, stream, x, wq_hwio, bias, y, p);
     return check_launch("slfp direct conv kernel");
+}
+
+const char* direct_instance_name(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post, const CodeIo* io) {
+    static thread_local char buf[64];
+    if (plan.family != kDirect || plan.repad) return "none";
+    static const char* const kOut[] = {"f32", "yc", "yc-signed", "lut"};
+    {
+        StemParams p;
+        StemSel s;
+        const int rc = stem_select(d, plan, post, io, &p, &s);
+        if (rc < 0) return "none";
+        if (rc == SLFP_OK) {
+            const char* fmt = s.a8 ? "act8" : "sfp7";
+            switch (s.kernel) {
+                case kStemMx: snprintf(buf, sizeof buf, "stem/mx/%s", kOut[s.out]); break;
+                case kStemFixedTab: snprintf(buf, sizeof buf, "stem/fixed/tab/%s", kOut[s.out]); break;
+                case kStemFixedLong: snprintf(buf, sizeof buf, "stem/fixed/%s/long", fmt); break;
+                default: snprintf(buf, sizeof buf, "stem/gen/%s/p%d", fmt, s.P); break;
+            }
+            return buf;
+        }
+    }
+    if (io && (io->y_codes || io->lut)) return "none";   // k_direct writes float32 only
+    DirParams p;
+    DirSel s;
+    if (direct_select(d, plan, post, &p, &s) != SLFP_OK) return "none";
+    snprintf(buf, sizeof buf, "direct/%s/cc%d/oc%d/%s", s.a8 ? "act8" : "sfp7", s.cc, s.oc_chunks,
+             s.lanes == 0 ? "vec" : (s.lanes == 1 ? "scalar" : "mixed"));
+    return buf;
 }
 
 }  // namespace slfp

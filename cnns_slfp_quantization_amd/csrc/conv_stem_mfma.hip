@@ -418,52 +418,92 @@ int launch_stem_mfma(const slfp_conv2d_desc& d, const ConvPlan& plan, const floa
     return launch_stem_mfma_io(d, plan, x, wblob, bias, post, y, workspace, io, stream);
 }
 
-int launch_stem_mfma_io(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x, const void* wblob,
-                        const float* bias, const PostOp& post, void* y_any, void* workspace, const CodeIo& io,
-                        hipStream_t stream) {
+// Everything launch_stem_mfma_io decides, worked out in ONE place (stem_mfma_select): the launcher only dispatches on it and
+// stem_mfma_instance_name (slfp_debug_stem_instance) prints it, so the reported string cannot drift from what runs.
+struct StemMfmaSel {
+    bool rows;    // k_stem_rows<FMT, NT, YC> (everything in one workgroup's LDS); else k_stem_im2row<FMT> + k_stem_mfma<NT, 8, YC>
+    int nt;       // NT: 4 or 6 16-channel tiles
+    bool a8;      // FMT: Act8 (else SFP7)
+    int out;      // 0 float32, 1 codes with the ReLU folded into the quantizer, 2 signed codes (YC; the sign is the runtime co.y_sgn)
+    size_t lds;   // rows form: dynamic LDS bytes
+};
+
+// q: the rows form's geometry (filled when sel->rows); co: the code-output arguments but for the output pointer.
+static int stem_mfma_select(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post, const CodeIo& io, StemRowsParams* q,
+                            StemCodeOut* co, StemMfmaSel* sel) {
     const bool yc = io.y_codes;
-    float* y = yc ? nullptr : reinterpret_cast<float*>(y_any);
-    StemCodeOut co = {};   // float32 out: a zeroed table travels in the kernel arguments, no YC form reads it
-    co.y_fmt = kFmtAct8;
+    *co = {};   // float32 out: a zeroed table travels in the kernel arguments, no YC form reads it
+    co->y_fmt = kFmtAct8;
+    sel->out = 0;
     if (yc) {
         const EncArgs* t = enc_table(io.y_ka, io.y_fmt, kEncCode);
         if (!t->valid || d.c_out % 16) return fail(SLFP_ERR_UNSUPPORTED, "MFMA stem: no code output for this layer");
-        co.enc_out = *t;
-        co.yc = reinterpret_cast<uint8_t*>(y_any);
-        co.y_sgn = post.relu ? 0 : 1;
-        co.y_fmt = io.y_fmt;
+        co->enc_out = *t;
+        co->y_sgn = post.relu ? 0 : 1;
+        co->y_fmt = io.y_fmt;
+        sel->out = post.relu ? 1 : 2;
     }
-    const bool a8 = plan.fmt_act == kFmtAct8;
+    sel->a8 = plan.fmt_act == kFmtAct8;
+    sel->lds = 0;
+    sel->rows = stem_rows_form(d, yc, q, &sel->lds, &sel->nt);
+    if (!sel->rows) {
+        int ksub;
+        stem_mfma_blob_shape(d, &ksub, &sel->nt);
+    }
+    return SLFP_OK;
+}
+
+const char* stem_mfma_instance_name(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post, const CodeIo& io) {
+    static thread_local char buf[64];
+    static const char* const kOut[] = {"f32", "yc", "yc-signed"};
+    if (plan.family != kStemMfma || plan.repad || io.lut) return "none";
+    StemRowsParams q;
+    StemCodeOut co;
+    StemMfmaSel s;
+    if (stem_mfma_select(d, plan, post, io, &q, &co, &s) != SLFP_OK) return "none";
+    snprintf(buf, sizeof buf, "%s/nt%d/%s/%s", s.rows ? "rows" : "im2row", s.nt, s.a8 ? "act8" : "sfp7", kOut[s.out]);
+    return buf;
+}
+
+int launch_stem_mfma_io(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x, const void* wblob,
+                        const float* bias, const PostOp& post, void* y_any, void* workspace, const CodeIo& io,
+                        hipStream_t stream) {
+    StemRowsParams q;
+    StemCodeOut co;
+    StemMfmaSel s;
     {
-        StemRowsParams q;
-        size_t lds;
-        int nt;
-        if (stem_rows_form(d, yc, &q, &lds, &nt)) {
-            co.enc_off = q.co.enc_off;
-            q.co = co;
-            q.x = x; q.w = reinterpret_cast<const _Float16*>(wblob); q.bias = bias; q.y = y; q.post = post;
-            q.N = (int)d.n; q.H = (int)d.h; q.W = (int)d.w; q.C = (int)d.c_in; q.O = (int)d.c_out; q.KH = (int)d.kh;
-            q.S = d.stride_h; q.ph = d.pad_h; q.pw = d.pad_w; q.Ho = (int)plan.h_out; q.Wo = (int)plan.w_out;
-            q.tiles_h = (int)ceil_div(q.Ho, kSrTH); q.tiles_w = (int)ceil_div(q.Wo, kSrTW);
-            q.sd = make_scale_div(d.ka, 4);
-            q.s1 = plan.s1; q.s2 = plan.s2; q.s1x = plan.s1 * (1.0f / 256.0f);
-            const int64_t nblocks = (int64_t)q.N * q.tiles_h * q.tiles_w;
-            if (nblocks > 0x7FFFFFFF) return fail(SLFP_ERR_UNSUPPORTED, "MFMA stem: grid too large");
-            q.nblocks = (uint32_t)nblocks;
-            if (yc) {
-                if (a8) launch_stem_rows_t<kFmtAct8, true>(q, nt, lds, stream);
-                else launch_stem_rows_t<kFmtSfp7, true>(q, nt, lds, stream);
-            } else {
-                if (a8) launch_stem_rows_t<kFmtAct8, false>(q, nt, lds, stream);
-                else launch_stem_rows_t<kFmtSfp7, false>(q, nt, lds, stream);
-            }
-            return check_launch("slfp MFMA stem (rows in LDS) kernel");
+        const int rc = stem_mfma_select(d, plan, post, io, &q, &co, &s);
+        if (rc != SLFP_OK) return rc;
+    }
+    const bool yc = s.out != 0;
+    float* y = yc ? nullptr : reinterpret_cast<float*>(y_any);
+    if (yc) co.yc = reinterpret_cast<uint8_t*>(y_any);
+    const bool a8 = s.a8;
+    const int nt = s.nt;
+    if (s.rows) {
+        co.enc_off = q.co.enc_off;
+        q.co = co;
+        q.x = x; q.w = reinterpret_cast<const _Float16*>(wblob); q.bias = bias; q.y = y; q.post = post;
+        q.N = (int)d.n; q.H = (int)d.h; q.W = (int)d.w; q.C = (int)d.c_in; q.O = (int)d.c_out; q.KH = (int)d.kh;
+        q.S = d.stride_h; q.ph = d.pad_h; q.pw = d.pad_w; q.Ho = (int)plan.h_out; q.Wo = (int)plan.w_out;
+        q.tiles_h = (int)ceil_div(q.Ho, kSrTH); q.tiles_w = (int)ceil_div(q.Wo, kSrTW);
+        q.sd = make_scale_div(d.ka, 4);
+        q.s1 = plan.s1; q.s2 = plan.s2; q.s1x = plan.s1 * (1.0f / 256.0f);
+        const int64_t nblocks = (int64_t)q.N * q.tiles_h * q.tiles_w;
+        if (nblocks > 0x7FFFFFFF) return fail(SLFP_ERR_UNSUPPORTED, "MFMA stem: grid too large");
+        q.nblocks = (uint32_t)nblocks;
+        if (yc) {
+            if (a8) launch_stem_rows_t<kFmtAct8, true>(q, nt, s.lds, stream);
+            else launch_stem_rows_t<kFmtSfp7, true>(q, nt, s.lds, stream);
+        } else {
+            if (a8) launch_stem_rows_t<kFmtAct8, false>(q, nt, s.lds, stream);
+            else launch_stem_rows_t<kFmtSfp7, false>(q, nt, s.lds, stream);
         }
+        return check_launch("slfp MFMA stem (rows in LDS) kernel");
     }
     if (!workspace) return fail(SLFP_ERR_BAD_ARG, "MFMA stem: workspace required (slfp_conv2d_workspace_bytes)");
     const int rp = stem_rp(d), rp_shift = rp == 32 ? 5 : 6;
-    int ksub, nt;
-    stem_mfma_blob_shape(d, &ksub, &nt);
+    const int ksub = rp / 32;
     _Float16* xe = reinterpret_cast<_Float16*>(workspace);
     const int64_t n_chunks16 = d.n * d.h * plan.w_out * (rp / 8);
     const ScaleDiv sd = make_scale_div(d.ka, 4);

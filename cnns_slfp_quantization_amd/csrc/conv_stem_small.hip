@@ -208,11 +208,20 @@ int launch_stem_small(const slfp_conv2d_desc& d, const ConvPlan& plan, const flo
     return launch_stem_small_io(d, plan, x, wblob, bias, post, y, io, stream);
 }
 
-int launch_stem_small_io(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x, const void* wblob,
-                         const float* bias, const PostOp& post, void* y_any, const CodeIo& io, hipStream_t stream) {
-    float* y = reinterpret_cast<float*>(y_any);
-    StemSmallParams p;
-    p.x = x; p.w = reinterpret_cast<const _Float16*>(wblob); p.bias = bias; p.y = y; p.post = post;
+// Everything launch_stem_small_io decides, worked out in ONE place (stem_small_select): the launcher only dispatches on it and
+// stem_small_instance_name (slfp_debug_stem_instance) prints it, so the reported string cannot drift from what runs.
+struct StemSmallSel {
+    int nt;       // NT: 16-channel tiles (1..4)
+    bool a8;      // FMT: Act8 (else SFP7)
+    int out;      // 0 float32, 1 codes with the ReLU folded into the quantizer, 2 signed codes (both: the runtime p.yc / p.y_sgn of
+                  // k_stem_small<FMT, 4>), 3 the table epilogue (LUTQ)
+    size_t lds;   // dynamic LDS bytes
+};
+
+static int stem_small_select(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post, const CodeIo& io, StemSmallParams* pp,
+                             StemSmallSel* sel) {
+    StemSmallParams& p = *pp;
+    p.post = post;
     p.yc = nullptr; p.y_sgn = 0; p.y_fmt = kFmtAct8; p.enc_off = 0; p.enc_out.valid = 0;
     p.N = (int)d.n; p.H = (int)d.h; p.W = (int)d.w; p.C = (int)d.c_in; p.O = (int)d.c_out;
     p.KH = (int)d.kh; p.KW = (int)d.kw; p.S = d.stride_h; p.ph = d.pad_h; p.pw = d.pad_w;
@@ -229,35 +238,57 @@ int launch_stem_small_io(const slfp_conv2d_desc& d, const ConvPlan& plan, const 
     p.nblocks = (uint32_t)nblocks;
     size_t lds = 64 + ((size_t)p.IH * p.row_h + 8) * sizeof(_Float16);
     const int nt = stem_small_tiles(d);
+    sel->nt = nt; sel->a8 = plan.fmt_act == kFmtAct8; sel->out = 0;
     if (io.lut) {   // the table epilogue: k_stem_small<FMT, 4, true>
         if (!io.y_codes || !post.scale) return fail(SLFP_ERR_BAD_ARG, "small stem: the table epilogue needs code output and post_scale / post_shift");
         if (nt != 4 || d.c_out != 64) return fail(SLFP_ERR_UNSUPPORTED, "small stem: no code output for this layer");
         enc_carry_ptr(p.enc_out, io.lut);
-        p.yc = reinterpret_cast<uint8_t*>(y_any);
-        p.y = nullptr;
         p.y_sgn = 1;
         p.y_fmt = io.y_fmt;
         p.enc_off = (uint32_t)((lds + 15) & ~(size_t)15);
         lds = p.enc_off + (size_t)kLayeroutLutBytes;
-        if (lds > 64 * 1024) return fail(SLFP_ERR_UNSUPPORTED, "small stem: halo tile needs %zu B of LDS", lds);
-        if (plan.fmt_act == kFmtAct8) hipLaunchKernelGGL((k_stem_small<kFmtAct8, 4, true>), dim3(p.nblocks), dim3(kSsThreads), lds, stream, p);
-        else hipLaunchKernelGGL((k_stem_small<kFmtSfp7, 4, true>), dim3(p.nblocks), dim3(kSsThreads), lds, stream, p);
-        return check_launch("slfp small-K MFMA stem kernel (table epilogue)");
-    }
-    if (io.y_codes) {
+        sel->out = 3;
+    } else if (io.y_codes) {
         const EncArgs* t = enc_table(io.y_ka, io.y_fmt, kEncCode);
         if (!t->valid || nt != 4 || d.c_out != 64) return fail(SLFP_ERR_UNSUPPORTED, "small stem: no code output for this layer");
         p.enc_out = *t;
-        p.yc = reinterpret_cast<uint8_t*>(y_any);
-        p.y = nullptr;
         p.y_sgn = post.relu ? 0 : 1;
         p.y_fmt = io.y_fmt;
         p.enc_off = (uint32_t)((lds + 15) & ~(size_t)15);
         lds = p.enc_off + (size_t)kEncEntries * 8;
+        sel->out = post.relu ? 1 : 2;
     }
     if (lds > 64 * 1024) return fail(SLFP_ERR_UNSUPPORTED, "small stem: halo tile needs %zu B of LDS", lds);
-    return plan.fmt_act == kFmtAct8 ? launch_stem_small_f<kFmtAct8>(p, nt, lds, stream)
-                                    : launch_stem_small_f<kFmtSfp7>(p, nt, lds, stream);
+    sel->lds = lds;
+    return SLFP_OK;
+}
+
+const char* stem_small_instance_name(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post, const CodeIo& io) {
+    static thread_local char buf[64];
+    static const char* const kOut[] = {"f32", "yc", "yc-signed", "lut"};
+    if (plan.family != kStemSmall || plan.repad) return "none";
+    StemSmallParams p;
+    StemSmallSel s;
+    if (stem_small_select(d, plan, post, io, &p, &s) != SLFP_OK) return "none";
+    snprintf(buf, sizeof buf, "small/nt%d/%s/%s", s.nt, s.a8 ? "act8" : "sfp7", kOut[s.out]);
+    return buf;
+}
+
+int launch_stem_small_io(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x, const void* wblob,
+                         const float* bias, const PostOp& post, void* y_any, const CodeIo& io, hipStream_t stream) {
+    StemSmallParams p;
+    StemSmallSel s;
+    const int rc = stem_small_select(d, plan, post, io, &p, &s);
+    if (rc != SLFP_OK) return rc;
+    p.x = x; p.w = reinterpret_cast<const _Float16*>(wblob); p.bias = bias;
+    p.y = s.out == 0 ? reinterpret_cast<float*>(y_any) : nullptr;
+    p.yc = s.out == 0 ? nullptr : reinterpret_cast<uint8_t*>(y_any);
+    if (s.out == 3) {
+        if (s.a8) hipLaunchKernelGGL((k_stem_small<kFmtAct8, 4, true>), dim3(p.nblocks), dim3(kSsThreads), s.lds, stream, p);
+        else hipLaunchKernelGGL((k_stem_small<kFmtSfp7, 4, true>), dim3(p.nblocks), dim3(kSsThreads), s.lds, stream, p);
+        return check_launch("slfp small-K MFMA stem kernel (table epilogue)");
+    }
+    return s.a8 ? launch_stem_small_f<kFmtAct8>(p, s.nt, s.lds, stream) : launch_stem_small_f<kFmtSfp7>(p, s.nt, s.lds, stream);
 }
 
 }  // namespace slfp

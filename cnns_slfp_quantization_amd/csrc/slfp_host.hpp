@@ -208,6 +208,10 @@ bool dwpw_codes_select(const slfp_conv2d_desc* dw, const slfp_conv2d_desc* pw, c
 int launch_direct(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const float* wq_hwio,
                   const float* bias, const PostOp& post, float* y, hipStream_t stream);
 bool stem_applicable(const slfp_conv2d_desc& d);  // direct family: the small-C_in stem kernel takes it
+// which instance of k_direct / k_stem / k_stem_fixed / k_stem_mx launch_direct (io == nullptr) or launch_stem_codes runs, printed from
+// the selection the launch consumes (slfp_debug_stem_instance; host only; grammar in include/slfp.h).  "none" outside the family or
+// where the launch would be refused; valid until the next call on the same thread.
+const char* direct_instance_name(const slfp_conv2d_desc& d, const ConvPlan& p, const PostOp& post, const CodeIo* io);
 // pointwise: does W (padded) fit the LDS-resident stream kernel?  (that kernel also takes even channel
 // counts that are not a multiple of 4, with 8-byte accesses)
 bool pointwise_stream_fits(int64_t k_pad, int64_t n_pad, int passes);
@@ -244,6 +248,8 @@ bool stem_mfma_codes_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, in
 bool stem_mfma_uses_workspace(const slfp_conv2d_desc& d, bool y_codes);
 int launch_stem_mfma_io(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const void* wblob, const float* bias,
                         const PostOp& post, void* y_any, void* workspace, const CodeIo& io, hipStream_t stream);
+// the k_stem_rows or k_stem_im2row + k_stem_mfma instance it runs, printed from the selection it consumes (slfp_debug_stem_instance)
+const char* stem_mfma_instance_name(const slfp_conv2d_desc& d, const ConvPlan& p, const PostOp& post, const CodeIo& io);
 
 // 3x3-class image stems whose whole contraction is one MFMA k-step (conv_stem_small.hip);
 // wblob = [o/16][64][8] fp16 with k = (kh*KW + kw)*C_in + c
@@ -254,6 +260,8 @@ int launch_stem_small(const slfp_conv2d_desc& d, const ConvPlan& p, const float*
 bool stem_small_codes_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, int post_flags);   // float32 in -> codes out (C_out == 64)
 int launch_stem_small_io(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const void* wblob, const float* bias,
                          const PostOp& post, void* y_any, const CodeIo& io, hipStream_t stream);
+// the k_stem_small instance it runs, printed from the selection it consumes (slfp_debug_stem_instance)
+const char* stem_small_instance_name(const slfp_conv2d_desc& d, const ConvPlan& p, const PostOp& post, const CodeIo& io);
 
 // XCD-aware block remap (MI355X: 8 XCDs, blocks are dealt round-robin over them, so
 // blocks b and b+8 share an L2).  Maps the hardware block id to a logical id such that

@@ -157,6 +157,47 @@ struct slfp_conv2d_io;   /* defined below */
  * Code output is the extended code of QA(t / y_ka) of that float32 t; the table epilogue is the byte table's entry for step 6's class. */
 const char* slfp_debug_dw3x3_instance(const slfp_conv2d_desc* d, const struct slfp_conv2d_io* io, int has_bias, int post_flags, int has_post);
 const char* slfp_debug_pw_variant(const slfp_conv2d_desc* d, const struct slfp_conv2d_io* io, int has_res, int has_res_codes, int64_t y_ld);
+/* Which image-stem or direct kernel instance (csrc/conv_direct.hip, conv_stem_small.hip, conv_stem_mfma.hip) the matching forward
+ * entry point launches for this descriptor under the switches read at load; "none" for a null descriptor, outside the direct_nhwc /
+ * stem_nhwc / stem_small_mfma_* / stem_mfma_* families, on channel-padded copies, or where that entry point refuses the call.
+ * io == NULL (or codes on neither side): slfp_conv2d_fwd / slfp_conv2d_fwd_post; io->y_codes: slfp_conv2d_fwd_codes[_ws], or, with
+ * SLFP_POST_LAYEROUT in post_flags, slfp_conv2d_fwd_codes_lut (these kernels read float32: io->x_codes gives "none").  has_bias /
+ * has_post / post_flags as for slfp_debug_dw3x3_instance.  One word per template argument or runtime form a launcher chooses:
+ *   direct/<act8|sfp7>/cc<CC>/oc<chunks>/<vec|scalar|mixed>     k_direct<FMT>; CC input channels per LDS chunk, 64-channel output
+ *                                                               chunks per group, and what the threads decide from C_out and
+ *                                                               C_out / groups: 16-byte weight loads and stores in every live
+ *                                                               thread, in none (C_out % 4 != 0), or in some (C_out / groups % 4 != 0)
+ *   stem/gen/<act8|sfp7>/p<2|4|8>                               k_stem<FMT>, P output rows per thread (C_out = 16 / 32 / 64)
+ *   stem/fixed/<act8|sfp7>/long                                 k_stem_fixed<FMT, 3, 3, 3, 2, 32>: the long-form quantizer
+ *   stem/fixed/tab/<f32|yc|yc-signed|lut>                       k_stem_fixed<Act8, 3, 3, 3, 2, 32, TAB, 16, YC, LUTQ>
+ *   stem/mx/<f32|yc|yc-signed|lut>                              k_stem_mx<YC, LUTQ>
+ *   small/nt<1|2|3|4>/<act8|sfp7>/<f32|yc|yc-signed|lut>        k_stem_small<FMT, NT, LUTQ>
+ *   rows/nt<4|6>/<act8|sfp7>/<f32|yc|yc-signed>                 k_stem_rows<FMT, NT, YC>
+ *   im2row/nt<4|6>/<act8|sfp7>/<f32|yc|yc-signed>               k_stem_im2row<FMT> + k_stem_mfma<NT, 8, YC>
+ * (f32 / yc / yc-signed / lut as for the dwc strings; yc against yc-signed is a runtime argument of the YC instance.)  k_stem_mx is
+ * selected only where its aligned 16-byte halo loads are valid: W * 3 a multiple of 4 AND pad_w = 1 (mod 4); every other 3x3 stride-2
+ * 3 -> 32 layer with a threshold table runs stem/fixed/tab.  The string is printed from the selection the launch consumes, and
+ * slfp_conv2d_codes_supported / slfp_conv2d_codes_lut_supported ask the same selection.  Host only: no device is touched.  The pointer
+ * stays valid until the next call on the same thread.
+ *
+ * Arithmetic of the float32 kernels (k_direct, k_stem, k_stem_fixed, k_stem_mx).  They compute every output element by the same
+ * float32 steps, so their results equal the CPU restatement oracle/slfp_oracle.c: slfp_oracle_conv_f32 bit for bit (a NaN equals a NaN):
+ *   1. xq = QA(x / Ka) as float32, wq = QW(w / Kw);
+ *   2. acc = +0; one acc = fmaf(xq, wq, acc) per tap: k_direct in input-channel chunks of CC outermost, then (kh, kw, c) inside a
+ *      chunk; the stems in (kh, kw, c) order; a padded tap contributes fmaf(+0, wq, acc).  k_stem_mx (the float32 matrix core, which
+ *      multiplies exactly and accumulates in k order) appends a 28th tap fmaf(+0, +0, acc).  That tap changes no bit: it could only
+ *      turn a -0 accumulator into +0, and an accumulator that starts at +0 is never -0 (in round-to-nearest a -0 product added to
+ *      +0 gives +0, an exact cancellation gives +0, and the quantized operands are too large for a non-zero sum to underflow);
+ *      a NaN stays a NaN;
+ *   3. t = ((acc + (bias / Ka) / Kw) * Ka) * Kw -- two IEEE float32 divisions, one addition (no bias: acc + +0), two roundings;
+ *   4. with post_scale / post_shift: t = fmaf(t, scale[c], shift[c]);
+ *   5. with SLFP_POST_LAYEROUT (and the affine): t = the layer-output quantizer of t (slfp_quantize_layerout_f32);
+ *   6. with SLFP_POST_RELU: t = fmaxf(t, 0) (a NaN gives 0);
+ *   7. code output as for the depthwise family: the extended code of QA(t / y_ka) of step 5's float32 t, the ReLU folded into the
+ *      quantizer; the table epilogue is the byte table's entry for the class of step 5's value.
+ * The fp16 matrix-core stems (small, rows, im2row) contract float16(16 xq) with float16(16 wq) on the matrix cores, whose internal
+ * order is not specified: they are held to an operand-level reference within a rounding-count bound (tests/test_gpu_stem_variants.py). */
+const char* slfp_debug_stem_instance(const slfp_conv2d_desc* d, const struct slfp_conv2d_io* io, int has_bias, int post_flags, int has_post);
 
 /* Bytes of the prepared-weight blob for this layer (device memory the caller owns). */
 size_t slfp_conv2d_wprep_bytes(const slfp_conv2d_desc* d);

@@ -373,4 +373,74 @@ int slfp_oracle_dw3x3_f32(const void* x, int x_codes, int64_t N, int64_t H, int6
     return 0;
 }
 
+/*
+ * The float32 direct / stem kernels' stated arithmetic (include/slfp.h, "Arithmetic of the float32 kernels": k_direct, k_stem,
+ * k_stem_fixed, k_stem_mx), float32 step for step, so that a device result can be compared as bits.  NHWC activations, OIHW
+ * weights [O][C/groups][KH][KW]; any groups, dilation, stride, padding (per axis) and kernel size.  Per output element:
+ *   1. xq = QA(x / Ka), wq = QW(w / Kw);
+ *   2. acc = +0; one fmaf(xq, wq, acc) per tap, input channels in chunks of `chunk` outermost (chunk <= 0 or >= C/groups: one
+ *      chunk, the stems' (kh, kw, c) order), then (kh, kw, c) inside a chunk; a padded tap is fmaf(+0, wq, acc).  (k_stem_mx's
+ *      28th tap fmaf(+0, +0, acc) changes no bit of an accumulator that started at +0 and is not restated.)
+ *   3. t = ((acc + (bias / Ka) / Kw) * Ka) * Kw, acc + +0 without a bias;
+ *   4. scale / shift given: t = fmaf(t, scale[o], shift[o]);
+ *   5. layerout (needs the affine): t = the layer-output quantizer;
+ *   6. relu: t = max(t, +0) with max(NaN, 0) = 0.
+ * Compiled with -ffp-contract=off.  Returns 0, or -1 on bad arguments.
+ */
+int slfp_oracle_conv_f32(const float* x, int64_t N, int64_t H, int64_t W, int64_t C, const float* w, int64_t O, int64_t KH,
+                         int64_t KW, const float* bias, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
+                         int groups, int chunk, float Ka, float Kw, int qbits, const float* scale, const float* shift, int layerout,
+                         int relu, float* y, float* scratch /* >= N*H*W*C + O*(C/groups)*KH*KW */) {
+    if (groups <= 0 || C % groups || O % groups || (qbits != 8 && qbits != 7)) return -1;
+    if ((scale == NULL) != (shift == NULL) || (layerout && !scale)) return -1;
+    if (stride_h <= 0 || stride_w <= 0 || dil_h <= 0 || dil_w <= 0 || pad_h < 0 || pad_w < 0) return -1;
+    const int64_t Cg = C / groups, Og = O / groups;
+    const int64_t eh = H + 2 * pad_h - dil_h * (KH - 1) - 1, ew = W + 2 * pad_w - dil_w * (KW - 1) - 1;
+    if (eh < 0 || ew < 0) return -1;
+    const int64_t Ho = eh / stride_h + 1, Wo = ew / stride_w + 1;
+    const int64_t CC = (chunk <= 0 || chunk > Cg) ? Cg : chunk;
+    const size_t nx = (size_t)(N * H * W * C), nw = (size_t)(O * Cg * KH * KW);
+    float* xq = scratch;
+    float* wq = scratch + nx;
+    slfp_oracle_quantize(x, xq, nx, Ka, qbits == 8 ? SLFP_FMT_ACT8 : SLFP_FMT_SFP7);
+    slfp_oracle_quantize(w, wq, nw, Kw, qbits == 8 ? SLFP_FMT_W8 : SLFP_FMT_SFP7);
+#pragma omp parallel for collapse(2) schedule(static)
+    for (int64_t n = 0; n < N; ++n) {
+        for (int64_t ho = 0; ho < Ho; ++ho) {
+            for (int64_t wo = 0; wo < Wo; ++wo) {
+                for (int64_t o = 0; o < O; ++o) {
+                    const int64_t g = o / Og;
+                    volatile float acc = 0.0f;
+                    for (int64_t c0 = 0; c0 < Cg; c0 += CC) {
+                        const int64_t c1 = c0 + CC < Cg ? c0 + CC : Cg;
+                        for (int64_t kh = 0; kh < KH; ++kh) {
+                            for (int64_t kw = 0; kw < KW; ++kw) {
+                                const int64_t hi = ho * stride_h - pad_h + kh * dil_h, wi = wo * stride_w - pad_w + kw * dil_w;
+                                const int inside = hi >= 0 && hi < H && wi >= 0 && wi < W;
+                                for (int64_t c = c0; c < c1; ++c) {
+                                    const float a = inside ? xq[((n * H + hi) * W + wi) * C + g * Cg + c] : 0.0f;
+                                    acc = fmaf(a, wq[((o * Cg + c) * KH + kh) * KW + kw], acc);
+                                }
+                            }
+                        }
+                    }
+                    volatile float bq = 0.0f;
+                    if (bias) {
+                        volatile float b1 = bias[o] / Ka;
+                        bq = b1 / Kw;
+                    }
+                    volatile float t = acc + bq;
+                    t = t * Ka;
+                    t = t * Kw;
+                    if (scale) t = fmaf(t, scale[o], shift[o]);
+                    if (layerout) t = layerout_one(t);
+                    if (relu) t = t > 0.0f ? t : 0.0f;
+                    y[((n * Ho + ho) * Wo + wo) * O + o] = t;
+                }
+            }
+        }
+    }
+    return 0;
+}
+
 int slfp_oracle_version(void) { return 1; }

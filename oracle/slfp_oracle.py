@@ -52,6 +52,9 @@ def lib():
         L.slfp_oracle_dw3x3_f32.argtypes = [ctypes.c_void_p, ci, i64, i64, i64, i64, fp, fp, ci, ci, ctypes.c_float, ctypes.c_float,
                                             ci, fp, fp, ci, ci, fp]
         L.slfp_oracle_dw3x3_f32.restype = ci
+        L.slfp_oracle_conv_f32.argtypes = [fp, i64, i64, i64, i64, fp, i64, i64, i64, fp, ci, ci, ci, ci, ci, ci, ci, ci,
+                                           ctypes.c_float, ctypes.c_float, ci, fp, fp, ci, ci, fp, fp]
+        L.slfp_oracle_conv_f32.restype = ci
         _lib = L
     return _lib
 
@@ -135,6 +138,30 @@ def dw3x3_f32(x, w, bias, stride, pad, Ka, Kw, qbits, scale=None, shift=None, la
                                      np.float32(Kw), qbits, _p(sc), _p(sh), int(bool(layerout)), int(bool(relu)), _p(y))
     if rc != 0:
         raise ValueError("slfp_oracle_dw3x3_f32: bad arguments")
+    return y
+
+
+def conv_f32(x, w, bias, stride, padding, dilation, groups, Ka, Kw, qbits, chunk=0, scale=None, shift=None, layerout=False, relu=False):
+    """The float32 direct / stem kernels' stated arithmetic (include/slfp.h), float32 step for step: to be compared as bits.
+    x: NHWC float32; w: OIHW [O, C / groups, KH, KW]; chunk: input channels per chunk of k_direct's order (0: one chunk, the stems'
+    order); returns NHWC float32."""
+    x, w = _f32(x), _f32(w)
+    N, H, W, C = x.shape
+    O, Cg, KH, KW = w.shape
+    assert Cg * groups == C, (x.shape, w.shape, groups)
+    b, sc, sf = (_f32(v) if v is not None else None for v in (bias, scale, shift))
+    sh, sw = _pair(stride)
+    ph, pw = _pair(padding)
+    dh, dw = _pair(dilation)
+    Ho = (H + 2 * ph - dh * (KH - 1) - 1) // sh + 1
+    Wo = (W + 2 * pw - dw * (KW - 1) - 1) // sw + 1
+    y = np.empty((N, Ho, Wo, O), dtype=np.float32)
+    scratch = np.empty(x.size + w.size, dtype=np.float32)
+    rc = lib().slfp_oracle_conv_f32(_p(x), N, H, W, C, _p(w), O, KH, KW, _p(b), sh, sw, ph, pw, dh, dw, int(groups), int(chunk),
+                                    np.float32(Ka), np.float32(Kw), qbits, _p(sc), _p(sf), int(bool(layerout)), int(bool(relu)), _p(y),
+                                    _p(scratch))
+    if rc != 0:
+        raise ValueError("slfp_oracle_conv_f32: bad arguments")
     return y
 
 
