@@ -10,5 +10,6 @@ conv2d forward path behind the operator API of happyxtt/CNNs_SLFP_quantization.
     sharding.py      batch-axis sharding + one-time weight broadcast (torch.distributed / RCCL)
     fusion.py        eval-BN + ReLU folded into the conv epilogues
     calibration.py   device-side max|.| statistics for Ka / Kw
+    image_u8.py      uint8 pixels in front of the stems: normalisation as a float32 table (fusion.link_image_u8)
 """
 __version__ = "0.1.0"

@@ -43,6 +43,7 @@ SYMBOLS = (
     "slfp_debug_dw3x3_instance", "slfp_debug_stem_instance", "slfp_debug_code_relu_mismatches",
     "slfp_bn_train_supported", "slfp_bn_train_workspace_bytes", "slfp_bn_train_fwd", "slfp_bn_train_bwd", "slfp_debug_bn_split",
     "slfp_debug_dwpw_instance",
+    "slfp_conv2d_u8_supported", "slfp_conv2d_fwd_u8", "slfp_debug_stem_u8_instance", "slfp_image_u8_expand_f32",
 )
 
 
@@ -177,6 +178,10 @@ def load():
         "slfp_bn_train_bwd": (ci, [vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, i64, i64, i64, i64, ci, vp, sz, vp]),
         "slfp_debug_bn_split": (ci, [i64, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
         "slfp_debug_dwpw_instance": (ctypes.c_char_p, [dp, dp, ctypes.POINTER(ConvIo), ci, ci, ci]),
+        "slfp_conv2d_u8_supported": (ci, [dp, ctypes.POINTER(ConvIo), ci, ci]),
+        "slfp_conv2d_fwd_u8": (ci, [dp, ctypes.POINTER(ConvIo), vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]),
+        "slfp_debug_stem_u8_instance": (ctypes.c_char_p, [dp, ctypes.POINTER(ConvIo), ci, ci, ci]),
+        "slfp_image_u8_expand_f32": (ci, [vp, vp, vp, i64, ci, vp]),
     }
     assert set(sigs) == set(SYMBOLS)
     for name, (res, args) in sigs.items():

@@ -236,6 +236,8 @@ _KINDS = {
     # codes in, float32 out, for a layer whose epilogue ends in the layer-output quantizer (no ReLU behind it): the code kernel runs
     # the affine, slfp_quantize_layerout_f32 the quantizer -- the last layer of a chain linked by fusion.link_layerout
     "codes_lo": ("slfp_conv2d_codes_supported", "slfp_conv2d_fwd_codes_ws"),
+    # uint8 pixels + the module's pixel table in (fusion.link_image_u8), float32 or codes out
+    "u8": ("slfp_conv2d_u8_supported", "slfp_conv2d_fwd_u8"),
 }
 
 
@@ -260,11 +262,12 @@ def _supported(mod, shape, kind, x_codes, out, flags, y_ld=None, desc=None, io=N
 class _Plan:
     """What one (module, input shape, layout, scales, precision, kind) combination resolves to in the C ABI; for the kinds of
     _KINDS also the io struct and whether libslfp_hip has a kernel for the combination (`ok`)."""
-    __slots__ = ("desc", "y_shape", "ws_bytes", "kernel", "kind", "io", "ok", "label")
+    __slots__ = ("desc", "y_shape", "ws_bytes", "kernel", "kind", "io", "ok", "label", "u8_family")
 
     def __init__(self, desc, y_shape, ws_bytes, kernel):
         self.desc, self.y_shape, self.ws_bytes, self.kernel = desc, y_shape, ws_bytes, kernel
         self.kind, self.io, self.ok, self.label = None, None, True, kernel   # label: what `_last_kernel` reports
+        self.u8_family = None   # kind "u8": the stem family of the byte form ("stem", "small", "rows", "im2row")
 
 
 def _plan(mod, x, weight, nhwc_in, nhwc_out, codes=None):
@@ -304,7 +307,13 @@ def _plan(mod, x, weight, nhwc_in, nhwc_out, codes=None):
             if kind == "entry" or (kind == "codes" and not plan.ok):
                 plan.ws_bytes = 0   # pointwise: no workspace; refused: the float32 interface's own plan sizes its workspace
             plan.label += (("+codes_in" if x_codes else "") + ("+codes_out" if out is not None and kind != "res_codes" else "")
-                           + {"slice": "+slice", "res": "+res", "res_codes": "+res+trunk_codes", "lut": "+lut", "codes_lo": "+layerout_pass"}.get(kind, ""))
+                           + {"slice": "+slice", "res": "+res", "res_codes": "+res+trunk_codes", "lut": "+lut", "codes_lo": "+layerout_pass",
+                              "u8": "+u8"}.get(kind, ""))
+            if kind == "u8" and plan.ok:   # what the launch consumes, from the library's own selection
+                inst = L.slfp_debug_stem_u8_instance(ctypes.byref(d), ctypes.byref(plan.io), 1 if mod.bias is not None else 0, flags,
+                                                     1 if mod._post is not None and mod._post[0] is not None else 0).decode()
+                plan.label += ":" + inst
+                plan.u8_family = inst.split("/", 1)[0]
         if len(mod._plans) >= 64:   # a net fed ever-changing shapes: do not grow without bound
             mod._plans.clear()
         mod._plans[key] = plan
@@ -384,6 +393,8 @@ def _launch(mod, plan, x, weight, bias, y=None, cache=True, res=None, relu=None,
             args = (ctypes.byref(d), ctypes.byref(plan.io)) + head + (1 if relu else 0, res.data_ptr(), y.data_ptr(), None)
         elif kind == "res_codes":
             args = (ctypes.byref(d), ctypes.byref(plan.io)) + head + (1 if relu else 0, res.data_ptr(), y.data_ptr(), yc.data_ptr(), None)
+        elif kind == "u8":   # x: pixel bytes, then the module's pixel table
+            args = (ctypes.byref(d), ctypes.byref(plan.io), x.data_ptr(), mod._image_table.data_ptr()) + head[1:] + (flags, y.data_ptr(), _ptr(ws))
         elif kind == "lut":   # no flags: the ReLU bit is part of the table
             args = (ctypes.byref(d), ctypes.byref(plan.io)) + head + (mod._code_lut.data_ptr(), y.data_ptr(), int(d.c_out), _ptr(ws))
         else:   # "codes" takes a workspace, "entry" does not
@@ -392,10 +403,10 @@ def _launch(mod, plan, x, weight, bias, y=None, cache=True, res=None, relu=None,
         if kind == "codes_lo":
             t, y = y, torch.empty_like(y)
             _lib.check(_lib.load().slfp_quantize_layerout_f32(t.data_ptr(), y.data_ptr(), t.numel(), stream.cuda_stream))
-    x_codes = x.dtype == torch.uint8
+    x_codes = x.dtype == torch.uint8 and kind != "u8"
     # plain attributes, written in one go (nn.Module.__setattr__ costs microseconds per name, on every layer of every forward)
-    mod.__dict__.update(_last_kernel=plan.label, _last_input=None if x_codes else x.detach(),
-                        _last_codes=x.detach() if x_codes else None, _input_q=xq)
+    mod.__dict__.update(_last_kernel=plan.label, _last_input=None if x.dtype == torch.uint8 else x.detach(),
+                        _last_codes=x.detach() if x_codes else None, _last_pixels=x.detach() if kind == "u8" else None, _input_q=xq)
     return y if yc is None else (y, yc)
 
 
@@ -462,6 +473,54 @@ def _hip_conv2d_codes(mod, x, weight, bias):
     # anything else takes the float32 interface
     y = _hip_conv2d(mod, hip_decode(x, _act_fmt(mod.q_bit)) if x_codes else x, weight, bias, cache_ok=True)
     return hip_encode(y, out[0], _act_fmt(out[1])) if out is not None else y
+
+
+def _hip_conv2d_u8(mod, x, weight, bias, order=None):
+    """Conv2d_Q.forward of a stem marked by fusion.link_image_u8 on a uint8 batch: `x` holds PIXELS (never codes), logical (N, C, H, W)
+    in channels_last on the weights' device; mod._image_table is the float32 [C][256] table of their values.  In inference, where
+    slfp_conv2d_u8_supported says yes (and image_u8_supported keeps the stem's family), ONE slfp_conv2d_fwd_u8 launch: float32 out, or
+    the codes mod._code_out describes.  Everywhere else -- training, autograd recording, q_bit 32, a stem without a byte form, a table
+    epilogue -- the bytes are expanded on the device (slfp_image_u8_expand_f32) and the module's ordinary forward runs on that float32
+    tensor, so gradients and every stash are exactly the float32 path's; `_last_kernel` then reads "u8-expand+<what ran>".  Both give
+    the bits of the unlinked module on the expanded tensor."""
+    from . import image_u8
+    table = mod._image_table
+    image_u8.check_pixels(x, table, "Conv2d_Q (image_u8)")
+    if weight.device != x.device:
+        raise TypeError(f"Conv2d_Q (image_u8): pixels are on {x.device} but the weights on {weight.device}")
+    need_grad = torch.is_grad_enabled() and (weight.requires_grad or (mod.bias is not None and mod.bias.requires_grad))
+    plan = None
+    if (mod.q_bit in (8, 7) and not mod.training and not need_grad and (mod._code_out is None or mod._code_lut is None)
+            and (mod.bias is None or mod._scaled_bias) and x.numel()):
+        plan = _plan(mod, x, weight, True, True, ("u8", False, mod._code_out, None))
+        if not (plan.ok and image_u8_supported(plan.u8_family)):
+            plan = None
+    if plan is None:
+        out = mod.forward(image_u8.expand(x, table), order)
+        if mod.q_bit in (8, 7):
+            mod.__dict__["_last_kernel"] = "u8-expand+" + str(mod._last_kernel)
+        return out
+    with torch.no_grad():
+        out = _launch(mod, plan, x, weight, bias, cache=not torch.is_grad_enabled())
+    mod.output = out
+    return out
+
+
+# Stem families (the first word of slfp_debug_stem_u8_instance's string: "stem", "small", "rows", "im2row") whose byte form the default
+# does NOT take: a marked stem of such a family runs "u8-expand" (slfp_image_u8_expand_f32 + the float32 kernel).  Two conditions,
+# read from profiles/image_u8_bench.json, both over every row of the family: the rule of DESIGN section 12 -- the byte form (C) is
+# below ATen normalisation + the float32 stem (B) by more than B's round-to-round spread -- and the byte form is not slower than the
+# library's own expansion path (E) by more than E's spread: of its two ways to read bytes the default takes the faster one.
+# Measured on an MI355X: `rows` misses the first (SqueezeNet's stem, float32 out: C 1.10 x B) and the second (C 1.04-1.40 x E);
+# `small` misses the second (VGG-16: C 1.09-1.10 x E); `im2row` misses the second with float32 out (C 1.05 x E) and would gain 2 % with
+# code out; `stem` (k_stem_fixed) meets both (C 0.84-0.94 x E).  The C query keeps answering what the kernels can run; a test or a benchmark empties this set to run
+# every form.
+IMAGE_U8_OFF = {"small", "rows", "im2row"}
+
+
+def image_u8_supported(family):
+    """Does the default take the byte form of stem family `family` (_Plan.u8_family)?"""
+    return family not in IMAGE_U8_OFF
 
 
 def _hip_conv2d_slice(mod, x, weight, bias, out_slice):
@@ -675,6 +734,10 @@ def _conv_class(q_bit, Kw, Ka, bias_default, scaled_bias):
             # layer-output class to the reader's code (fusion.link_layerout); slfp_conv2d_fwd_codes_lut then runs.  A buffer, so
             # that it follows the module across devices; not persistent: the state dict keeps the reference's keys
             self.register_buffer("_code_lut", None, persistent=False)
+            # fusion.link_image_u8: the float32 [C_in][256] table that gives this stem's uint8 input the meaning "pixels"; None: a
+            # uint8 input is codes, as ever.  A non-persistent buffer like _code_lut
+            self.register_buffer("_image_table", None, persistent=False)
+            self._last_pixels = None
             self._trunk_code_out = None   # forward(x, residual=r): (Ka, q_bit) of the Conv2d_Q layers that read the result; it then
                                           # carries their codes (fusion.link_trunk).  Not `_code_out`: the result stays float32
             self._last_codes = None
@@ -690,6 +753,10 @@ def _conv_class(q_bit, Kw, Ka, bias_default, scaled_bias):
             _check_stash(self)
             if self.q_bit == 32:
                 return self._input_q
+            if self._input_q is None and self._last_input is None and self.__dict__.get("_last_pixels") is not None:
+                # a byte-input stem (fusion.link_image_u8): the float32 tensor its pixels stand for, made on first read
+                from . import image_u8
+                self._last_input = image_u8.expand(self._last_pixels, self._image_table)
             if self._input_q is None and self._last_input is not None:
                 self._input_q = hip_quantize(self._last_input, _f32(self.Ka), _act_fmt(self.q_bit))
             elif self._input_q is None and self._last_codes is not None:
@@ -701,7 +768,7 @@ def _conv_class(q_bit, Kw, Ka, bias_default, scaled_bias):
         def weight_q(self):
             if self.q_bit == 32:
                 return self._weight_q32
-            if self._last_input is None and self._last_codes is None:
+            if self._last_input is None and self._last_codes is None and self.__dict__.get("_last_pixels") is None:
                 return None
             stale = self._prep.weight_q is None or self._prep.weight_version != self.weight._version
             if stale or self.training or torch.is_grad_enabled():   # p.data updates are invisible to _version
@@ -760,6 +827,10 @@ def _conv_class(q_bit, Kw, Ka, bias_default, scaled_bias):
                 return self._forward_residual(input, order, residual)
             if self._grouped_stash:
                 self._grouped_stash = False
+            if self._image_table is not None and torch.is_tensor(input) and input.dtype == torch.uint8:
+                # a stem marked by fusion.link_image_u8: uint8 is pixels here, never codes
+                self.output = _hip_conv2d_u8(self, input, self.weight, self.bias if scaled_bias else None, order)
+                return self.output
             tc = input.__dict__.get("_trunk_codes") if type(input) is torch.Tensor else None
             if tc is not None and not self.training and self.q_bit in (8, 7) and tc[1:] == (float(self.Ka), self.q_bit):
                 # the float32 trunk of a block linked by fusion.link_trunk carries the codes written for THIS module's present

@@ -1,5 +1,6 @@
 // conv_abi.hip -- C ABI for the quantized conv2d / linear forward (include/slfp.h):
 // descriptor validation, kernel selection, weight preparation, dispatch.
+#include <algorithm>
 #include <cstring>
 #include "slfp_device.hpp"
 #include "slfp_codes.hpp"
@@ -888,6 +889,128 @@ int slfp_conv2d_fwd_res_codes(const slfp_conv2d_desc* d, const slfp_conv2d_io* i
     // float32 out as slfp_conv2d_fwd_res launches it; y_ka / y_fmt describe the reader of y_codes
     const CodeIo codes_in{true, false, io->y_ka, y_fmt_of(io->y_qbits)};
     return launch_pwc(*d, r.p, reinterpret_cast<const uint8_t*>(x), wprep, bias, r.post, y, codes_in, as_stream(stream), res, y_codes);
+}
+
+}  // extern "C"
+
+// ---- image stems on uint8 pixels + a float32 pixel table (include/slfp.h: slfp_conv2d_fwd_u8) ----
+enum U8Route { kU8None = 0, kU8Fixed, kU8Small, kU8Mfma };
+
+// One selection behind the query, the entry point and the reporter.  cio: the code interface's arguments of the launch.
+static U8Route u8_route(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int post_flags, const ConvPlan& p, CodeIo* cio) {
+    if (io && (io->x_codes != 0 || (io->y_codes != 0 && io->y_codes != 1))) return kU8None;
+    const bool yc = io && io->y_codes == 1;
+    if (d->x_layout != SLFP_LAYOUT_NHWC || d->y_layout != SLFP_LAYOUT_NHWC || d->groups != 1 || d->c_in > 4 || p.repad) return kU8None;
+    if ((post_flags & ~(SLFP_POST_RELU | SLFP_POST_LAYEROUT)) != 0) return kU8None;
+    if (d->qbits == 8 && d->mfma_passes == SLFP_MFMA_F16X3) return kU8None;
+    *cio = CodeIo{false, yc, yc ? io->y_ka : 1.f, yc ? y_fmt_of(io->y_qbits) : (int)kFmtAct8};
+    if (yc) {   // the reader's quantizer as slfp_conv2d_fwd_codes validates it; the layer-output quantizer has no code form here
+        if (!code_path_ok(d, post_flags) || !consumer_quant_ok(io) || !enc_table(io->y_ka, cio->y_fmt, kEncCode)->valid) return kU8None;
+    }
+    const PostOp post{nullptr, nullptr, (post_flags & SLFP_POST_RELU) ? 1 : 0, 0};   // the selections read the ReLU bit only
+    switch (p.family) {
+        case kDirect: return stem_u8_applicable(*d, p, post, yc ? cio : nullptr) ? kU8Fixed : kU8None;
+        case kStemSmall: return !yc || stem_small_codes_applicable(*d, p, post_flags) ? kU8Small : kU8None;
+        case kStemMfma: return !yc || stem_mfma_codes_applicable(*d, p, post_flags) ? kU8Mfma : kU8None;
+        default: return kU8None;
+    }
+}
+
+// y[e] = pix[(e % C)][x[e]] over n_el = n_pixels * C elements, four per lane (one 16-byte store); the table in LDS.
+__global__ __launch_bounds__(256) void k_image_u8_expand(const uint8_t* __restrict__ x, const float* __restrict__ pix, float* __restrict__ y,
+                                                         int64_t n_el, int C) {
+    __shared__ float sP[256 * 4];
+    for (int i = threadIdx.x; i < 256 * C; i += 256) sP[i] = pix[i];
+    __syncthreads();
+    const int64_t stride = (int64_t)gridDim.x * 256 * 4;
+    for (int64_t e = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; e < n_el; e += stride) {
+        int c = (int)(e % C);
+        if (e + 4 <= n_el) {
+            float r[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                r[k] = sP[c * 256 + x[e + k]];
+                c = c + 1 == C ? 0 : c + 1;
+            }
+            *reinterpret_cast<float4*>(y + e) = make_float4(r[0], r[1], r[2], r[3]);
+        } else {
+            for (int64_t k = e; k < n_el; ++k) {
+                y[k] = sP[c * 256 + x[k]];
+                c = c + 1 == C ? 0 : c + 1;
+            }
+        }
+    }
+}
+
+extern "C" {
+
+int slfp_conv2d_u8_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int post_flags) {
+    (void)has_bias;   // every stem kernel takes a bias
+    ConvPlan p;
+    CodeIo cio;
+    return d && make_plan(d, &p) == SLFP_OK && u8_route(d, io, post_flags, p, &cio) != kU8None;
+}
+
+const char* slfp_debug_stem_u8_instance(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int post_flags, int has_post) {
+    (void)has_bias;
+    ConvPlan p;
+    CodeIo cio{false, false, 1.f, kFmtAct8};
+    if (!d || make_plan(d, &p) != SLFP_OK) return "none";
+    if ((post_flags & SLFP_POST_LAYEROUT) && !has_post) return "none";
+    const U8Route route = u8_route(d, io, post_flags, p, &cio);
+    static const float one = 1.f;   // the selections only ask whether a scale / shift pair is present
+    const float* vec = has_post ? &one : nullptr;
+    const PostOp post{vec, vec, (post_flags & SLFP_POST_RELU) ? 1 : 0, (!cio.y_codes && (post_flags & SLFP_POST_LAYEROUT)) ? 1 : 0};
+    switch (route) {
+        case kU8Fixed: return direct_instance_name(*d, p, post, cio.y_codes ? &cio : nullptr, true);
+        case kU8Small: return stem_small_instance_name(*d, p, post, cio, true);
+        case kU8Mfma: return stem_mfma_instance_name(*d, p, post, cio, true);
+        default: return "none";
+    }
+}
+
+int slfp_conv2d_fwd_u8(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const uint8_t* x, const float* pix_table,
+                       const void* wprep, const float* bias, const float* post_scale, const float* post_shift,
+                       int post_flags, void* y, void* workspace, void* stream) {
+    const char* fn = "slfp_conv2d_fwd_u8";
+    if (!d) return fail(SLFP_ERR_BAD_ARG, "%s: null descriptor", fn);
+    ConvPlan p;
+    const int rc = make_plan(d, &p);
+    if (rc != SLFP_OK) return rc;
+    if (!x || !pix_table || !wprep || !y) return fail(SLFP_ERR_BAD_ARG, "%s: null pointer", fn);
+    if ((post_scale == nullptr) != (post_shift == nullptr))
+        return fail(SLFP_ERR_BAD_ARG, "%s: post_scale and post_shift must be given together", fn);
+    CodeIo cio;
+    const U8Route route = u8_route(d, io, post_flags, p, &cio);
+    if (route == kU8None)
+        return fail(SLFP_ERR_UNSUPPORTED, "%s: this layer / io combination has no byte-input stem kernel (slfp_conv2d_u8_supported); "
+                                          "use slfp_image_u8_expand_f32 and the float32 entry point", fn);
+    if ((post_flags & SLFP_POST_LAYEROUT) && !post_scale) return fail(SLFP_ERR_BAD_ARG, "%s: SLFP_POST_LAYEROUT needs post_scale / post_shift", fn);
+    if (!aligned16(pix_table) || !aligned16(y) || !aligned16(wprep) || !aligned16(bias) || !aligned16(post_scale) || !aligned16(post_shift))
+        return fail(SLFP_ERR_ALIGNMENT, "%s: pix_table, y, wprep, bias, post_scale and post_shift must be 16-byte aligned (x: any alignment)", fn);
+    const bool needs_ws = route == kU8Mfma && stem_mfma_uses_workspace(*d, cio.y_codes, true);
+    if (needs_ws && (!workspace || !aligned16(workspace)))
+        return fail(SLFP_ERR_BAD_ARG, "%s: %zu bytes of 16-byte aligned workspace required (slfp_conv2d_workspace_bytes)", fn, ws_layout(d, p).total);
+    const PostOp post{post_scale, post_shift, (post_flags & SLFP_POST_RELU) ? 1 : 0, (post_flags & SLFP_POST_LAYEROUT) ? 1 : 0};
+    hipStream_t st = as_stream(stream);
+    const float* xf = reinterpret_cast<const float*>(x);   // the U8 forms read it as bytes
+    unsigned char* ws = reinterpret_cast<unsigned char*>(workspace);
+    switch (route) {
+        case kU8Fixed: return launch_stem_u8(*d, p, x, pix_table, reinterpret_cast<const float*>(wprep), bias, post, y, cio.y_codes ? &cio : nullptr, st);
+        case kU8Small: return launch_stem_small_io(*d, p, xf, wprep, bias, post, y, cio, st, pix_table);
+        default: return launch_stem_mfma_io(*d, p, xf, wprep, bias, post, y, needs_ws ? ws + ws_layout(d, p).operand : nullptr, cio, st, pix_table);
+    }
+}
+
+int slfp_image_u8_expand_f32(const uint8_t* x, const float* pix_table, float* y, int64_t n_pixels, int c, void* stream) {
+    if (!x || !pix_table || !y) return fail(SLFP_ERR_BAD_ARG, "slfp_image_u8_expand_f32: null pointer");
+    if (c < 1 || c > 4 || n_pixels < 0) return fail(SLFP_ERR_SHAPE, "slfp_image_u8_expand_f32: 1 <= c <= 4 and n_pixels >= 0 required");
+    if (!aligned16(pix_table) || !aligned16(y)) return fail(SLFP_ERR_ALIGNMENT, "slfp_image_u8_expand_f32: pix_table and y must be 16-byte aligned");
+    if (n_pixels == 0) return SLFP_OK;
+    const int64_t n_el = n_pixels * c;
+    const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(n_el, 256 * 4), 4096);
+    hipLaunchKernelGGL(k_image_u8_expand, dim3(grid), dim3(256), 0, as_stream(stream), x, pix_table, y, n_el, c);
+    return check_launch("slfp image byte expansion kernel");
 }
 
 }  // extern "C"

@@ -164,6 +164,7 @@ struct StemParams {
     EncArgs enc;         // threshold table of QA(x / Ka) (k_stem_fixed<.., TAB>; slfp_enc.hpp)
     EncArgsCompact enc_out;  // YC: code table of the consumer's Ka (kEncCode; slfp_codes.hpp)
     int sgn, fmt_out;        // YC: codes carry a sign (no ReLU in front of the quantizer); their format
+    const float* pix;        // U8: the caller's float32 pixel table [C][256] (slfp_conv2d_fwd_u8); nullptr otherwise
 };
 
 template <int FMT>
@@ -277,7 +278,13 @@ __global__ __launch_bounds__(256) void k_stem(const float* __restrict__ x, const
 // YC: the output leaves as the 1-byte codes of the next layer's QA(. / Ka) (slfp_codes.hpp): a lane's 4 channels are one dword.
 // LUTQ (YC; slfp_conv2d_fwd_codes_lut): the codes come from the byte table of the layer-output classes (slfp_layerout_lut.hpp),
 // kept in LDS in the reader's threshold table's place: 4.8 KiB next to the 18 KiB of weights, halo tile and input table.
-template <int FMT, int KH, int KW, int C, int S, int O, bool TAB = false, int TH = kStemTH, bool YC = false, bool LUTQ = false>
+// U8 (TAB; slfp_conv2d_fwd_u8): `x` holds NHWC bytes (any alignment) and p.pix the float32 value of every (channel, byte).  The
+// workgroup runs the float32 form's own encode (enc_f32 + its NaN rule) over the 256 * C table entries into LDS, and the halo fill
+// becomes: byte load, one LDS lookup at c * 256 + byte, +0 for an element outside the image (byte 0 is not operand 0).  The tile
+// holds what the float32 form computes from x32 = pix[c][byte], so everything behind the fill is unchanged.  Plain byte loads: a
+// halo row is contiguous, consecutive lanes read consecutive bytes; no load is wider than the byte it needs.
+template <int FMT, int KH, int KW, int C, int S, int O, bool TAB = false, int TH = kStemTH, bool YC = false, bool LUTQ = false,
+          bool U8 = false>
 __global__ __launch_bounds__(256) void k_stem_fixed(const float* __restrict__ x, const float* __restrict__ wq,
                                                     const float* __restrict__ bias, float* __restrict__ y,
                                                     const StemParams p) {
@@ -309,7 +316,33 @@ __global__ __launch_bounds__(256) void k_stem_fixed(const float* __restrict__ x,
         const float* xn = x + (size_t)n * p.H * p.W * C;
         const int j_lo = -w_in0 * C, j_hi = (p.W - w_in0) * C;
         float v[U];
-        if constexpr (TAB) {
+        if constexpr (U8) {
+            static_assert(TAB && !LUTQ, "the byte form is built on the threshold-table quantizer");
+            __shared__ __attribute__((aligned(16))) float sPix[256 * C];
+            const uint8_t* xb = reinterpret_cast<const uint8_t*>(x) + (size_t)n * p.H * p.W * C;
+            int li[U];   // index into sPix, or -1: the operand +0 (outside the image / the tile)
+#pragma unroll
+            for (int u = 0; u < U; ++u) {   // the byte loads first: they are in flight while the table is encoded
+                const int idx = threadIdx.x + u * 256;
+                const int ih = idx / IWC, j = idx - ih * IWC;  // compile-time divisor
+                const int gh = h_in0 + ih;
+                const bool ok = idx < N_IN && (unsigned)gh < (unsigned)p.H && j >= j_lo && j < j_hi;
+                const int byte = xb[ok ? (gh * p.W + w_in0) * C + j : 0];   // clamped: always inside the image
+                li[u] = ok ? (j % C) * 256 + byte : -1;
+            }
+            const unsigned char* tb = reinterpret_cast<const unsigned char*>(sT);
+            for (int i = threadIdx.x; i < 256 * C; i += 256) {
+                const float t = p.pix[i];
+                const float q = enc_f32(t, p.enc.r1, p.enc.lo, p.enc.hi, tb);
+                sPix[i] = t != t ? __uint_as_float(kBitsQNaN) : q;   // NaN in -> NaN out
+            }
+            __syncthreads();
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int idx = threadIdx.x + u * 256;
+                if (idx < N_IN) tile[idx] = li[u] >= 0 ? sPix[li[u]] : 0.f;
+            }
+        } else if constexpr (TAB) {
             const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xn), 0, (uint32_t)p.H * p.W * C * 4u, 0x00020000);
             uint32_t vo[U];
 #pragma unroll
@@ -650,7 +683,10 @@ struct StemSel {
 
 // SLFP_OK: `p` and `sel` describe the launch; 1: this geometry is not a stem (caller falls back); < 0: refused (error text recorded).
 // io (may be null): the code interface's arguments; only whether io->lut is set is looked at, not what it points to.
-static int stem_select(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post, const CodeIo* io, StemParams* pp, StemSel* sel) {
+// u8 (slfp_conv2d_fwd_u8): byte input; only k_stem_fixed<.., TAB> has that form, so k_stem_mx's geometry goes there too.  A layer on any
+// other kernel is answered 1 (not applicable), like a geometry that is no stem.
+static int stem_select(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post, const CodeIo* io, StemParams* pp, StemSel* sel,
+                       bool u8 = false) {
     StemParams& p = *pp;
     const int O = (int)d.c_out, C = (int)d.c_in;
     if (!stem_applicable(d)) return 1;
@@ -666,7 +702,7 @@ static int stem_select(const slfp_conv2d_desc& d, const ConvPlan& plan, const Po
     p.P = kStemTH / (groups / kStemTW);             // 2, 4 or 8 rows per thread
     p.step_h = 256 / p.IWC; p.step_j = 256 % p.IWC;
     p.sd = make_scale_div(d.ka); p.s1 = plan.s1; p.s2 = plan.s2;
-    p.sgn = 0; p.fmt_out = kFmtAct8; p.enc_out.valid = 0;
+    p.sgn = 0; p.fmt_out = kFmtAct8; p.enc_out.valid = 0; p.pix = nullptr;
     const size_t n_w = (size_t)p.KH * p.KW * C * O;
     const size_t lds = 64 + (((n_w + 3) & ~(size_t)3) + (size_t)p.IH * p.IWC) * sizeof(float);
     if (lds > 64 * 1024) return 1;
@@ -690,10 +726,11 @@ static int stem_select(const slfp_conv2d_desc& d, const ConvPlan& plan, const Po
             // of the image row: a float4 lies wholly inside or outside the row only when W * C is a multiple of 4, and the superset
             // starts on a multiple of 4 only when pad_w = 1 (mod 4).  Every other padding stays on k_stem_fixed, whose guarded
             // dword / buffer loads are general in it.
-            const bool mx = !switches().stem_old && (p.W * C) % 4 == 0 && p.pw % 4 == 1;
+            const bool mx = !u8 && !switches().stem_old && (p.W * C) % 4 == 0 && p.pw % 4 == 1;
             sel->kernel = mx ? kStemMx : kStemFixedTab;
         }
     }
+    if (u8 && (sel->kernel != kStemFixedTab || (io && io->lut))) return 1;   // no byte form: not applicable (a query records no error)
     if (!io || (!io->y_codes && !io->lut)) return SLFP_OK;
     // code output: the two table kernels of the MobileNetV1 stem only, on SLFP<3,4> input
     if ((sel->kernel != kStemMx && sel->kernel != kStemFixedTab) || plan.fmt_act != kFmtAct8)
@@ -719,11 +756,13 @@ static int stem_select(const slfp_conv2d_desc& d, const ConvPlan& plan, const Po
 
 // Returns SLFP_OK if it launched, 1 if this geometry is not a stem (caller falls back).
 static int try_launch_stem(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x, const float* wq_hwio,
-                           const float* bias, const PostOp& post, float* y, hipStream_t stream, const CodeIo* io = nullptr) {
+                           const float* bias, const PostOp& post, float* y, hipStream_t stream, const CodeIo* io = nullptr,
+                           const float* pix = nullptr) {
     StemParams p;
     StemSel s;
-    const int rc = stem_select(d, plan, post, io, &p, &s);
+    const int rc = stem_select(d, plan, post, io, &p, &s, pix != nullptr);
     if (rc != SLFP_OK) return rc;
+    p.pix = pix;
     const dim3 grid(p.nblocks), block(256);
     constexpr int TH = 16;
 #define SLFP_STEM_ARGS grid, block, 0, stream, x, wq_hwio, bias, y, p
@@ -734,6 +773,11 @@ static int try_launch_stem(const slfp_conv2d_desc& d, const ConvPlan& plan, cons
             else hipLaunchKernelGGL((k_stem_mx<true>), SLFP_STEM_ARGS);
             return check_launch("slfp stem conv kernel (3x3x3 s2 -> 32, float32 MFMA)");
         case kStemFixedTab:
+            if (pix) {   // `x` holds bytes (launch_stem_u8)
+                if (s.out == kStemOutF32) hipLaunchKernelGGL((k_stem_fixed<kFmtAct8, 3, 3, 3, 2, 32, true, TH, false, false, true>), SLFP_STEM_ARGS);
+                else hipLaunchKernelGGL((k_stem_fixed<kFmtAct8, 3, 3, 3, 2, 32, true, TH, true, false, true>), SLFP_STEM_ARGS);
+                return check_launch("slfp stem conv kernel (3x3x3 s2 -> 32, byte input)");
+            }
             if (s.out == kStemOutF32) hipLaunchKernelGGL((k_stem_fixed<kFmtAct8, 3, 3, 3, 2, 32, true, TH>), SLFP_STEM_ARGS);
             else if (s.out == kStemOutLut) hipLaunchKernelGGL((k_stem_fixed<kFmtAct8, 3, 3, 3, 2, 32, true, TH, true, true>), SLFP_STEM_ARGS);
             else hipLaunchKernelGGL((k_stem_fixed<kFmtAct8, 3, 3, 3, 2, 32, true, TH, true>), SLFP_STEM_ARGS);
@@ -765,6 +809,21 @@ int launch_stem_codes(const slfp_conv2d_desc& d, const ConvPlan& plan, const flo
                       const PostOp& post, void* y, const CodeIo& io, hipStream_t stream) {
     const int rc = try_launch_stem(d, plan, x, wq_hwio, bias, post, reinterpret_cast<float*>(y), stream, &io);
     return rc == 1 ? fail(SLFP_ERR_UNSUPPORTED, "stem (codes): unsupported geometry") : rc;
+}
+
+// The 3x3 s2 3 -> 32 stem on NHWC bytes + a pixel table (slfp_conv2d_fwd_u8): where the selection, asked for the byte form, lands on
+// k_stem_fixed<.., TAB>.  io: nullptr for float32 out.
+bool stem_u8_applicable(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post, const CodeIo* io) {
+    if (plan.family != kDirect || plan.repad) return false;
+    StemParams p;
+    StemSel s;
+    return stem_select(d, plan, post, io, &p, &s, true) == SLFP_OK;
+}
+
+int launch_stem_u8(const slfp_conv2d_desc& d, const ConvPlan& plan, const uint8_t* x, const float* pix, const float* wq_hwio,
+                   const float* bias, const PostOp& post, void* y, const CodeIo* io, hipStream_t stream) {
+    const int rc = try_launch_stem(d, plan, reinterpret_cast<const float*>(x), wq_hwio, bias, post, reinterpret_cast<float*>(y), stream, io, pix);
+    return rc == 1 ? fail(SLFP_ERR_UNSUPPORTED, "stem (u8): unsupported geometry") : rc;
 }
 
 struct DirSel {
@@ -823,20 +882,20 @@ int launch_direct(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* 
     return check_launch("slfp direct conv kernel");
 }
 
-const char* direct_instance_name(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post, const CodeIo* io) {
+const char* direct_instance_name(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post, const CodeIo* io, bool u8) {
     static thread_local char buf[64];
     if (plan.family != kDirect || plan.repad) return "none";
     static const char* const kOut[] = {"f32", "yc", "yc-signed", "lut"};
     {
         StemParams p;
         StemSel s;
-        const int rc = stem_select(d, plan, post, io, &p, &s);
-        if (rc < 0) return "none";
+        const int rc = stem_select(d, plan, post, io, &p, &s, u8);
+        if (rc < 0 || (u8 && rc != SLFP_OK)) return "none";
         if (rc == SLFP_OK) {
             const char* fmt = s.a8 ? "act8" : "sfp7";
             switch (s.kernel) {
                 case kStemMx: snprintf(buf, sizeof buf, "stem/mx/%s", kOut[s.out]); break;
-                case kStemFixedTab: snprintf(buf, sizeof buf, "stem/fixed/tab/%s", kOut[s.out]); break;
+                case kStemFixedTab: snprintf(buf, sizeof buf, u8 ? "stem/fixed/tab/u8/%s" : "stem/fixed/tab/%s", kOut[s.out]); break;
                 case kStemFixedLong: snprintf(buf, sizeof buf, "stem/fixed/%s/long", fmt); break;
                 default: snprintf(buf, sizeof buf, "stem/gen/%s/p%d", fmt, s.P); break;
             }

@@ -77,13 +77,23 @@ struct StemMfmaParams {
 };
 static_assert(sizeof(StemMfmaParams) <= 4096, "StemMfmaParams must fit the 4 KiB kernel-argument segment");
 
-template <int FMT>
+// U8 (slfp_conv2d_fwd_u8): `x` holds NHWC bytes and `pix` the float32 value of every (channel, byte); the workgroup makes the table
+// of their 256 * C fp16 operands with the float32 form's own per-element encode and the load-and-encode step is a byte load + one LDS
+// lookup.  The run / chunk arithmetic is the float32 form's.
+template <int FMT, bool U8 = false>
 __global__ __launch_bounds__(256) void k_stem_im2row(const float* __restrict__ x, _Float16* __restrict__ xe,
                                                      int64_t n_chunks16, int H, int W, int C, int Wo, int S, int pw,
-                                                     int RL, int rp_shift, const ScaleDiv sd) {
+                                                     int RL, int rp_shift, const ScaleDiv sd, const float* __restrict__ pix) {
     __shared__ uint32_t sT[16];
     lut_fill<FMT>(sT);
     __syncthreads();
+    const _Float16* opq = nullptr;   // U8: operand of (channel, byte) at c * 256 + byte
+    if constexpr (U8) {
+        __shared__ _Float16 sPix[256 * 4];
+        for (int i = threadIdx.x; i < 256 * C; i += 256) sPix[i] = (_Float16)quantize_scaled<FMT, 4>(pix[i], sd, sT);
+        __syncthreads();
+        opq = sPix;
+    }
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= n_chunks16) return;
     const int cps = rp_shift - 3;                       // log2(16-byte chunks per run)
@@ -91,22 +101,37 @@ __global__ __launch_bounds__(256) void k_stem_im2row(const float* __restrict__ x
     const int64_t run = idx >> cps;                     // (n*H + ih)*Wo + ow
     const int ow = (int)(run % Wo);
     const int64_t row = run / Wo;                       // n*H + ih
-    const float* xr = x + row * (int64_t)W * C;
     const int e0 = (ow * S - pw) * C + cj * 8;          // element offset inside the input row
     half8 h = half8{0, 0, 0, 0, 0, 0, 0, 0};
     if (cj * 8 < RL) {                                   // chunks that are all padding just store zeros
         const int last = W * C - 1;
-        float v[8];
+        if constexpr (U8) {
+            const uint8_t* xr = reinterpret_cast<const uint8_t*>(x) + row * (int64_t)W * C;
+            int b[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {                    // unconditional (clamped) loads: all 8 in flight
-            const int e = e0 + j;
-            v[j] = xr[e < 0 ? 0 : (e > last ? last : e)];
-        }
+            for (int j = 0; j < 8; ++j) {                // unconditional (clamped) byte loads: inside this image row
+                const int e = e0 + j;
+                b[j] = xr[e < 0 ? 0 : (e > last ? last : e)];
+            }
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int r = cj * 8 + j, e = e0 + j;
-            const float q = quantize_scaled<FMT, 4>(v[j], sd, sT);
-            h[j] = (_Float16)((r < RL && e >= 0 && e <= last) ? q : 0.f);
+            for (int j = 0; j < 8; ++j) {
+                const int r = cj * 8 + j, e = e0 + j;    // the run starts on a pixel: r % C is the channel
+                h[j] = (r < RL && e >= 0 && e <= last) ? opq[(r % C) * 256 + b[j]] : (_Float16)0.f;
+            }
+        } else {
+            const float* xr = x + row * (int64_t)W * C;
+            float v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {                // unconditional (clamped) loads: all 8 in flight
+                const int e = e0 + j;
+                v[j] = xr[e < 0 ? 0 : (e > last ? last : e)];
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int r = cj * 8 + j, e = e0 + j;
+                const float q = quantize_scaled<FMT, 4>(v[j], sd, sT);
+                h[j] = (_Float16)((r < RL && e >= 0 && e <= last) ? q : 0.f);
+            }
         }
     }
     *reinterpret_cast<half8*>(xe + idx * 8) = h;
@@ -226,10 +251,15 @@ struct StemRowsParams {
     PostOp post;
     uint32_t nblocks;
     StemCodeOut co;      // YC forms only
+    // U8 (slfp_conv2d_fwd_u8): x holds NHWC bytes; the caller's float32 pixel table [C][256] and where its fp16 operands lie in LDS
+    const float* pix;
+    uint32_t pix_off;
 };
 static_assert(sizeof(StemRowsParams) <= 4096, "StemRowsParams must fit the 4 KiB kernel-argument segment");
 
-template <int FMT, int NT, bool YC = false>
+// U8: the halo fill reads bytes and looks the operand up in a table of 256 * C fp16 entries that the workgroup makes from p.pix with
+// the float32 form's own per-element encode; an element outside the image or in the pitch's tail is the operand +0.
+template <int FMT, int NT, bool YC = false, bool U8 = false>
 __global__ __launch_bounds__(kSrThreads) void k_stem_rows(const StemRowsParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint32_t* sT = reinterpret_cast<uint32_t*>(smem);
@@ -250,6 +280,33 @@ __global__ __launch_bounds__(kSrThreads) void k_stem_rows(const StemRowsParams p
     const int col = lane & 15, kq = lane >> 4;
     const int h_in0 = th * kSrTH * p.S - p.ph, w_in0 = tw * kSrTW * p.S - p.pw;
     __syncthreads();  // LUT visible
+    if constexpr (U8) {   // halo rows from bytes: operand table first, then byte loads and one lookup per element
+        _Float16* sPix = reinterpret_cast<_Float16*>(smem + p.pix_off);
+        for (int i = threadIdx.x; i < 256 * p.C; i += kSrThreads) sPix[i] = (_Float16)quantize_scaled<FMT, 4>(p.pix[i], p.sd, sT);
+        __syncthreads();
+        const uint8_t* xb = reinterpret_cast<const uint8_t*>(p.x) + (size_t)n * p.H * p.W * p.C;
+        const int n_el = p.IH * p.row_h;
+        const int e_w0 = w_in0 * p.C;
+        const int row_el = p.W * p.C;
+        constexpr int U = 8;
+        for (int base = threadIdx.x; base < n_el; base += kSrThreads * U) {
+            int li[U], dst[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int i = base + u * kSrThreads;
+                const int ih = i / p.row_h, e = i - ih * p.row_h;
+                const int gh = h_in0 + ih, ge = e_w0 + e;
+                const bool live = i < n_el;
+                const bool inb = live && e < p.IWC && (unsigned)gh < (unsigned)p.H && ge >= 0 && ge < row_el;
+                dst[u] = live ? i : -1;
+                const int byte = xb[inb ? gh * row_el + ge : 0];   // unconditional (clamped) load
+                li[u] = inb ? (e % p.C) * 256 + byte : -1;         // e_w0 is a multiple of C: e % C is the channel
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (dst[u] >= 0) tile[dst[u]] = li[u] >= 0 ? sPix[li[u]] : (_Float16)0.f;
+        }
+    } else
     {   // halo rows: coalesced dword loads, encode once, fp16 to LDS; the pitch's tail and out-of-image elements are zero
         const float* xn = p.x + (size_t)n * p.H * p.W * p.C;
         const int n_el = p.IH * p.row_h;
@@ -369,14 +426,14 @@ static int launch_stem_mfma_t(const StemMfmaParams& p, size_t lds, unsigned grid
     return check_launch("slfp MFMA stem kernel");
 }
 
-template <int FMT, bool YC>
+template <int FMT, bool YC, bool U8 = false>
 static void launch_stem_rows_t(const StemRowsParams& q, int nt, size_t lds, hipStream_t stream) {
-    if (nt == 4) hipLaunchKernelGGL((k_stem_rows<FMT, 4, YC>), dim3(q.nblocks), dim3(kSrThreads), lds, stream, q);
-    else hipLaunchKernelGGL((k_stem_rows<FMT, 6, YC>), dim3(q.nblocks), dim3(kSrThreads), lds, stream, q);
+    if (nt == 4) hipLaunchKernelGGL((k_stem_rows<FMT, 4, YC, U8>), dim3(q.nblocks), dim3(kSrThreads), lds, stream, q);
+    else hipLaunchKernelGGL((k_stem_rows<FMT, 6, YC, U8>), dim3(q.nblocks), dim3(kSrThreads), lds, stream, q);
 }
 
 // the fused form: even S*C (4-byte aligned fragment reads), everything in one workgroup's LDS (yc: the code table as well)
-static bool stem_rows_geometry(const slfp_conv2d_desc& d, bool yc, StemRowsParams* p, size_t* lds, int* nt_out) {
+static bool stem_rows_geometry(const slfp_conv2d_desc& d, bool yc, StemRowsParams* p, size_t* lds, int* nt_out, bool u8 = false) {
     if ((d.stride_w * d.c_in) % 2) return false;
     int ksub, nt;
     stem_mfma_blob_shape(d, &ksub, &nt);
@@ -391,12 +448,15 @@ static bool stem_rows_geometry(const slfp_conv2d_desc& d, bool yc, StemRowsParam
     *lds = p->w_off + (size_t)p->KS * nt * 1024;
     p->co.enc_off = (uint32_t)*lds;   // W ends on a 1 KiB step of a 16-byte aligned offset
     if (yc) *lds += (size_t)kEncEntries * 8;
+    p->pix = nullptr;
+    p->pix_off = (uint32_t)((*lds + 15) & ~(size_t)15);   // the byte form's operand table: 256 * C fp16 behind everything else
+    if (u8) *lds = p->pix_off + (size_t)256 * d.c_in * sizeof(_Float16);
     *nt_out = nt;
     return *lds <= 64 * 1024 && (int64_t)d.h * d.w * d.c_in < (1ll << 30);
 }
 
-static bool stem_rows_form(const slfp_conv2d_desc& d, bool yc, StemRowsParams* q, size_t* lds, int* nt) {
-    return !switches().stem_im2row && stem_rows_geometry(d, yc, q, lds, nt);
+static bool stem_rows_form(const slfp_conv2d_desc& d, bool yc, StemRowsParams* q, size_t* lds, int* nt, bool u8 = false) {
+    return !switches().stem_im2row && stem_rows_geometry(d, yc, q, lds, nt, u8);
 }
 
 // code output: whole 16-channel tiles (the 16-byte store of a lane), no layer-output quantizer
@@ -405,11 +465,11 @@ bool stem_mfma_codes_applicable(const slfp_conv2d_desc& d, const ConvPlan& plan,
 }
 
 // does the call run the two-kernel form, which reads the im2row copy from the workspace?
-bool stem_mfma_uses_workspace(const slfp_conv2d_desc& d, bool y_codes) {
+bool stem_mfma_uses_workspace(const slfp_conv2d_desc& d, bool y_codes, bool u8) {
     StemRowsParams q;
     size_t lds;
     int nt;
-    return !stem_rows_form(d, y_codes, &q, &lds, &nt);
+    return !stem_rows_form(d, y_codes, &q, &lds, &nt, u8);
 }
 
 int launch_stem_mfma(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x, const void* wblob,
@@ -430,7 +490,7 @@ struct StemMfmaSel {
 
 // q: the rows form's geometry (filled when sel->rows); co: the code-output arguments but for the output pointer.
 static int stem_mfma_select(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post, const CodeIo& io, StemRowsParams* q,
-                            StemCodeOut* co, StemMfmaSel* sel) {
+                            StemCodeOut* co, StemMfmaSel* sel, bool u8 = false) {
     const bool yc = io.y_codes;
     *co = {};   // float32 out: a zeroed table travels in the kernel arguments, no YC form reads it
     co->y_fmt = kFmtAct8;
@@ -445,7 +505,7 @@ static int stem_mfma_select(const slfp_conv2d_desc& d, const ConvPlan& plan, con
     }
     sel->a8 = plan.fmt_act == kFmtAct8;
     sel->lds = 0;
-    sel->rows = stem_rows_form(d, yc, q, &sel->lds, &sel->nt);
+    sel->rows = stem_rows_form(d, yc, q, &sel->lds, &sel->nt, u8);
     if (!sel->rows) {
         int ksub;
         stem_mfma_blob_shape(d, &ksub, &sel->nt);
@@ -453,26 +513,26 @@ static int stem_mfma_select(const slfp_conv2d_desc& d, const ConvPlan& plan, con
     return SLFP_OK;
 }
 
-const char* stem_mfma_instance_name(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post, const CodeIo& io) {
+const char* stem_mfma_instance_name(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post, const CodeIo& io, bool u8) {
     static thread_local char buf[64];
     static const char* const kOut[] = {"f32", "yc", "yc-signed"};
     if (plan.family != kStemMfma || plan.repad || io.lut) return "none";
     StemRowsParams q;
     StemCodeOut co;
     StemMfmaSel s;
-    if (stem_mfma_select(d, plan, post, io, &q, &co, &s) != SLFP_OK) return "none";
-    snprintf(buf, sizeof buf, "%s/nt%d/%s/%s", s.rows ? "rows" : "im2row", s.nt, s.a8 ? "act8" : "sfp7", kOut[s.out]);
+    if (stem_mfma_select(d, plan, post, io, &q, &co, &s, u8) != SLFP_OK) return "none";
+    snprintf(buf, sizeof buf, u8 ? "%s/nt%d/%s/u8/%s" : "%s/nt%d/%s/%s", s.rows ? "rows" : "im2row", s.nt, s.a8 ? "act8" : "sfp7", kOut[s.out]);
     return buf;
 }
 
 int launch_stem_mfma_io(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x, const void* wblob,
                         const float* bias, const PostOp& post, void* y_any, void* workspace, const CodeIo& io,
-                        hipStream_t stream) {
+                        hipStream_t stream, const float* pix) {
     StemRowsParams q;
     StemCodeOut co;
     StemMfmaSel s;
     {
-        const int rc = stem_mfma_select(d, plan, post, io, &q, &co, &s);
+        const int rc = stem_mfma_select(d, plan, post, io, &q, &co, &s, pix != nullptr);
         if (rc != SLFP_OK) return rc;
     }
     const bool yc = s.out != 0;
@@ -492,6 +552,17 @@ int launch_stem_mfma_io(const slfp_conv2d_desc& d, const ConvPlan& plan, const f
         const int64_t nblocks = (int64_t)q.N * q.tiles_h * q.tiles_w;
         if (nblocks > 0x7FFFFFFF) return fail(SLFP_ERR_UNSUPPORTED, "MFMA stem: grid too large");
         q.nblocks = (uint32_t)nblocks;
+        q.pix = pix;
+        if (pix) {   // `x` holds bytes
+            if (yc) {
+                if (a8) launch_stem_rows_t<kFmtAct8, true, true>(q, nt, s.lds, stream);
+                else launch_stem_rows_t<kFmtSfp7, true, true>(q, nt, s.lds, stream);
+            } else {
+                if (a8) launch_stem_rows_t<kFmtAct8, false, true>(q, nt, s.lds, stream);
+                else launch_stem_rows_t<kFmtSfp7, false, true>(q, nt, s.lds, stream);
+            }
+            return check_launch("slfp MFMA stem (rows in LDS, byte input) kernel");
+        }
         if (yc) {
             if (a8) launch_stem_rows_t<kFmtAct8, true>(q, nt, s.lds, stream);
             else launch_stem_rows_t<kFmtSfp7, true>(q, nt, s.lds, stream);
@@ -509,12 +580,17 @@ int launch_stem_mfma_io(const slfp_conv2d_desc& d, const ConvPlan& plan, const f
     const ScaleDiv sd = make_scale_div(d.ka, 4);
     const unsigned egrid = (unsigned)ceil_div(n_chunks16, 256);
     const int RL = (int)(d.kw * d.c_in);
-    if (a8)
-        hipLaunchKernelGGL((k_stem_im2row<kFmtAct8>), dim3(egrid), dim3(256), 0, stream, x, xe, n_chunks16, (int)d.h, (int)d.w,
-                           (int)d.c_in, (int)plan.w_out, d.stride_w, d.pad_w, RL, rp_shift, sd);
-    else
-        hipLaunchKernelGGL((k_stem_im2row<kFmtSfp7>), dim3(egrid), dim3(256), 0, stream, x, xe, n_chunks16, (int)d.h, (int)d.w,
-                           (int)d.c_in, (int)plan.w_out, d.stride_w, d.pad_w, RL, rp_shift, sd);
+#define SLFP_IM2ROW_ARGS dim3(egrid), dim3(256), 0, stream, x, xe, n_chunks16, (int)d.h, (int)d.w, (int)d.c_in, (int)plan.w_out, d.stride_w, \
+                         d.pad_w, RL, rp_shift, sd, pix
+    if (pix) {   // `x` holds bytes
+        if (a8) hipLaunchKernelGGL((k_stem_im2row<kFmtAct8, true>), SLFP_IM2ROW_ARGS);
+        else hipLaunchKernelGGL((k_stem_im2row<kFmtSfp7, true>), SLFP_IM2ROW_ARGS);
+    } else if (a8) {
+        hipLaunchKernelGGL((k_stem_im2row<kFmtAct8>), SLFP_IM2ROW_ARGS);
+    } else {
+        hipLaunchKernelGGL((k_stem_im2row<kFmtSfp7>), SLFP_IM2ROW_ARGS);
+    }
+#undef SLFP_IM2ROW_ARGS
     int rc = check_launch("slfp stem im2row kernel");
     if (rc != SLFP_OK) return rc;
     StemMfmaParams p;

@@ -47,12 +47,17 @@ struct StemSmallParams {
     int y_sgn, y_fmt;
     uint32_t enc_off;     // byte offset of the kEncCode table inside the dynamic LDS (behind the halo tile)
     EncArgs enc_out;
+    // U8 (slfp_conv2d_fwd_u8): x holds NHWC bytes; the caller's float32 pixel table [C][256] and where its fp16 operands lie in LDS
+    const float* pix;
+    uint32_t pix_off;
 };
 
 // LUTQ (code output, NT == 4; slfp_conv2d_fwd_codes_lut): the codes come from the byte table of the layer-output classes
 // (slfp_layerout_lut.hpp), copied into the dynamic LDS where the reader's threshold table lies otherwise (4.8 KiB behind a halo
 // tile of at most 4 KiB; the kernel reads nothing else from LDS in its epilogue).  (Unmeasured against global reads.)
-template <int FMT, int NT, bool LUTQ = false>
+// U8: the halo fill reads bytes and looks the operand up in a table of 256 * C fp16 entries that the workgroup makes from p.pix with
+// the float32 form's own per-element encode; an element outside the image is the operand +0.  Plain byte loads (rows are contiguous).
+template <int FMT, int NT, bool LUTQ = false, bool U8 = false>
 __global__ __launch_bounds__(kSsThreads) void k_stem_small(const StemSmallParams p) {
     static_assert(!LUTQ || NT == 4, "code output: the 64-channel form");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -87,6 +92,34 @@ __global__ __launch_bounds__(kSsThreads) void k_stem_small(const StemSmallParams
     }
     __syncthreads();  // LUT visible
 
+    if constexpr (U8) {   // ---- halo tile from bytes: operand table first, then byte loads and one lookup per element
+        _Float16* sPix = reinterpret_cast<_Float16*>(smem + p.pix_off);
+        for (int i = threadIdx.x; i < 256 * p.C; i += kSsThreads) sPix[i] = (_Float16)quantize_scaled<FMT, 4>(p.pix[i], p.sd, sT);
+        __syncthreads();
+        const uint8_t* xb = reinterpret_cast<const uint8_t*>(p.x) + (size_t)n * p.H * p.W * p.C;
+        const int n_el = p.IH * p.IWC;
+        const int e_w0 = w_in0 * p.C;
+        const int row_el = p.W * p.C;
+        if (threadIdx.x == 0) tile[zero_slot] = (_Float16)0.f;
+        constexpr int U = 8;
+        for (int base = threadIdx.x; base < n_el; base += kSsThreads * U) {
+            int li[U], dst[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int i = base + u * kSsThreads;
+                const int ih = i / p.IWC, e = i - ih * p.IWC;
+                const int gh = h_in0 + ih, ge = e_w0 + e;
+                const bool live = i < n_el;
+                const bool inb = live && (unsigned)gh < (unsigned)p.H && ge >= 0 && ge < row_el;
+                dst[u] = live ? ih * p.row_h + e : -1;
+                const int byte = xb[inb ? gh * row_el + ge : 0];   // unconditional (clamped) load
+                li[u] = inb ? (e % p.C) * 256 + byte : -1;         // e_w0 is a multiple of C: e % C is the channel
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (dst[u] >= 0) tile[dst[u]] = li[u] >= 0 ? sPix[li[u]] : (_Float16)0.f;
+        }
+    } else
     // ---- halo tile: coalesced dword loads, encode once, fp16 to LDS
     {
         const float* xn = p.x + (size_t)n * p.H * p.W * p.C;
@@ -186,13 +219,13 @@ bool stem_small_applicable(const slfp_conv2d_desc& d, int passes) {
 
 int stem_small_tiles(const slfp_conv2d_desc& d) { return (int)ceil_div(d.c_out, 16); }
 
-template <int FMT>
+template <int FMT, bool U8 = false>
 static int launch_stem_small_f(const StemSmallParams& p, int nt, size_t lds, hipStream_t stream) {
     switch (nt) {
-        case 1: hipLaunchKernelGGL((k_stem_small<FMT, 1>), dim3(p.nblocks), dim3(kSsThreads), lds, stream, p); break;
-        case 2: hipLaunchKernelGGL((k_stem_small<FMT, 2>), dim3(p.nblocks), dim3(kSsThreads), lds, stream, p); break;
-        case 3: hipLaunchKernelGGL((k_stem_small<FMT, 3>), dim3(p.nblocks), dim3(kSsThreads), lds, stream, p); break;
-        default: hipLaunchKernelGGL((k_stem_small<FMT, 4>), dim3(p.nblocks), dim3(kSsThreads), lds, stream, p); break;
+        case 1: hipLaunchKernelGGL((k_stem_small<FMT, 1, false, U8>), dim3(p.nblocks), dim3(kSsThreads), lds, stream, p); break;
+        case 2: hipLaunchKernelGGL((k_stem_small<FMT, 2, false, U8>), dim3(p.nblocks), dim3(kSsThreads), lds, stream, p); break;
+        case 3: hipLaunchKernelGGL((k_stem_small<FMT, 3, false, U8>), dim3(p.nblocks), dim3(kSsThreads), lds, stream, p); break;
+        default: hipLaunchKernelGGL((k_stem_small<FMT, 4, false, U8>), dim3(p.nblocks), dim3(kSsThreads), lds, stream, p); break;
     }
     return check_launch("slfp small-K MFMA stem kernel");
 }
@@ -219,10 +252,11 @@ struct StemSmallSel {
 };
 
 static int stem_small_select(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post, const CodeIo& io, StemSmallParams* pp,
-                             StemSmallSel* sel) {
+                             StemSmallSel* sel, bool u8 = false) {
     StemSmallParams& p = *pp;
     p.post = post;
     p.yc = nullptr; p.y_sgn = 0; p.y_fmt = kFmtAct8; p.enc_off = 0; p.enc_out.valid = 0;
+    p.pix = nullptr; p.pix_off = 0;
     p.N = (int)d.n; p.H = (int)d.h; p.W = (int)d.w; p.C = (int)d.c_in; p.O = (int)d.c_out;
     p.KH = (int)d.kh; p.KW = (int)d.kw; p.S = d.stride_h; p.ph = d.pad_h; p.pw = d.pad_w;
     p.Ho = (int)plan.h_out; p.Wo = (int)plan.w_out;
@@ -239,6 +273,11 @@ static int stem_small_select(const slfp_conv2d_desc& d, const ConvPlan& plan, co
     size_t lds = 64 + ((size_t)p.IH * p.row_h + 8) * sizeof(_Float16);
     const int nt = stem_small_tiles(d);
     sel->nt = nt; sel->a8 = plan.fmt_act == kFmtAct8; sel->out = 0;
+    if (u8) {   // the byte form's operand table: 256 * C fp16 behind the halo tile
+        if (io.lut) return fail(SLFP_ERR_UNSUPPORTED, "small stem (u8): no table epilogue with byte input");
+        p.pix_off = (uint32_t)((lds + 15) & ~(size_t)15);
+        lds = p.pix_off + (size_t)256 * p.C * sizeof(_Float16);
+    }
     if (io.lut) {   // the table epilogue: k_stem_small<FMT, 4, true>
         if (!io.y_codes || !post.scale) return fail(SLFP_ERR_BAD_ARG, "small stem: the table epilogue needs code output and post_scale / post_shift");
         if (nt != 4 || d.c_out != 64) return fail(SLFP_ERR_UNSUPPORTED, "small stem: no code output for this layer");
@@ -263,23 +302,24 @@ static int stem_small_select(const slfp_conv2d_desc& d, const ConvPlan& plan, co
     return SLFP_OK;
 }
 
-const char* stem_small_instance_name(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post, const CodeIo& io) {
+const char* stem_small_instance_name(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post, const CodeIo& io, bool u8) {
     static thread_local char buf[64];
     static const char* const kOut[] = {"f32", "yc", "yc-signed", "lut"};
     if (plan.family != kStemSmall || plan.repad) return "none";
     StemSmallParams p;
     StemSmallSel s;
-    if (stem_small_select(d, plan, post, io, &p, &s) != SLFP_OK) return "none";
-    snprintf(buf, sizeof buf, "small/nt%d/%s/%s", s.nt, s.a8 ? "act8" : "sfp7", kOut[s.out]);
+    if (stem_small_select(d, plan, post, io, &p, &s, u8) != SLFP_OK) return "none";
+    snprintf(buf, sizeof buf, u8 ? "small/nt%d/%s/u8/%s" : "small/nt%d/%s/%s", s.nt, s.a8 ? "act8" : "sfp7", kOut[s.out]);
     return buf;
 }
 
 int launch_stem_small_io(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x, const void* wblob,
-                         const float* bias, const PostOp& post, void* y_any, const CodeIo& io, hipStream_t stream) {
+                         const float* bias, const PostOp& post, void* y_any, const CodeIo& io, hipStream_t stream, const float* pix) {
     StemSmallParams p;
     StemSmallSel s;
-    const int rc = stem_small_select(d, plan, post, io, &p, &s);
+    const int rc = stem_small_select(d, plan, post, io, &p, &s, pix != nullptr);
     if (rc != SLFP_OK) return rc;
+    p.pix = pix;
     p.x = x; p.w = reinterpret_cast<const _Float16*>(wblob); p.bias = bias;
     p.y = s.out == 0 ? reinterpret_cast<float*>(y_any) : nullptr;
     p.yc = s.out == 0 ? nullptr : reinterpret_cast<uint8_t*>(y_any);
@@ -288,6 +328,7 @@ int launch_stem_small_io(const slfp_conv2d_desc& d, const ConvPlan& plan, const 
         else hipLaunchKernelGGL((k_stem_small<kFmtSfp7, 4, true>), dim3(p.nblocks), dim3(kSsThreads), s.lds, stream, p);
         return check_launch("slfp small-K MFMA stem kernel (table epilogue)");
     }
+    if (pix) return s.a8 ? launch_stem_small_f<kFmtAct8, true>(p, s.nt, s.lds, stream) : launch_stem_small_f<kFmtSfp7, true>(p, s.nt, s.lds, stream);
     return s.a8 ? launch_stem_small_f<kFmtAct8>(p, s.nt, s.lds, stream) : launch_stem_small_f<kFmtSfp7>(p, s.nt, s.lds, stream);
 }
 

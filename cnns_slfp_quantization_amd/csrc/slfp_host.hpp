@@ -211,7 +211,12 @@ bool stem_applicable(const slfp_conv2d_desc& d);  // direct family: the small-C_
 // which instance of k_direct / k_stem / k_stem_fixed / k_stem_mx launch_direct (io == nullptr) or launch_stem_codes runs, printed from
 // the selection the launch consumes (slfp_debug_stem_instance; host only; grammar in include/slfp.h).  "none" outside the family or
 // where the launch would be refused; valid until the next call on the same thread.
-const char* direct_instance_name(const slfp_conv2d_desc& d, const ConvPlan& p, const PostOp& post, const CodeIo* io);
+const char* direct_instance_name(const slfp_conv2d_desc& d, const ConvPlan& p, const PostOp& post, const CodeIo* io, bool u8 = false);
+// ---- image stems on NHWC bytes + a float32 pixel table [C_in][256] (slfp_conv2d_fwd_u8): the U8 form of the four stem kernels' fill
+// step.  `pix` / `u8` on the launchers and name functions of the stem families select it; `x` then points at bytes of any alignment.
+bool stem_u8_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, const PostOp& post, const CodeIo* io);
+int launch_stem_u8(const slfp_conv2d_desc& d, const ConvPlan& p, const uint8_t* x, const float* pix, const float* wq_hwio,
+                   const float* bias, const PostOp& post, void* y, const CodeIo* io, hipStream_t stream);
 // pointwise: does W (padded) fit the LDS-resident stream kernel?  (that kernel also takes even channel
 // counts that are not a multiple of 4, with 8-byte accesses)
 bool pointwise_stream_fits(int64_t k_pad, int64_t n_pad, int passes);
@@ -245,11 +250,11 @@ int launch_stem_mfma(const slfp_conv2d_desc& d, const ConvPlan& p, const float* 
 bool stem_mfma_codes_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, int post_flags);
 // does the call run k_stem_im2row + k_stem_mfma (workspace needed) instead of k_stem_rows?  The code table counts in the
 // rows form's LDS, so the answer can differ between float32 and code output.
-bool stem_mfma_uses_workspace(const slfp_conv2d_desc& d, bool y_codes);
+bool stem_mfma_uses_workspace(const slfp_conv2d_desc& d, bool y_codes, bool u8 = false);
 int launch_stem_mfma_io(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const void* wblob, const float* bias,
-                        const PostOp& post, void* y_any, void* workspace, const CodeIo& io, hipStream_t stream);
+                        const PostOp& post, void* y_any, void* workspace, const CodeIo& io, hipStream_t stream, const float* pix = nullptr);
 // the k_stem_rows or k_stem_im2row + k_stem_mfma instance it runs, printed from the selection it consumes (slfp_debug_stem_instance)
-const char* stem_mfma_instance_name(const slfp_conv2d_desc& d, const ConvPlan& p, const PostOp& post, const CodeIo& io);
+const char* stem_mfma_instance_name(const slfp_conv2d_desc& d, const ConvPlan& p, const PostOp& post, const CodeIo& io, bool u8 = false);
 
 // 3x3-class image stems whose whole contraction is one MFMA k-step (conv_stem_small.hip);
 // wblob = [o/16][64][8] fp16 with k = (kh*KW + kw)*C_in + c
@@ -259,9 +264,9 @@ int launch_stem_small(const slfp_conv2d_desc& d, const ConvPlan& p, const float*
                       const float* bias, const PostOp& post, float* y, hipStream_t stream);
 bool stem_small_codes_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, int post_flags);   // float32 in -> codes out (C_out == 64)
 int launch_stem_small_io(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const void* wblob, const float* bias,
-                         const PostOp& post, void* y_any, const CodeIo& io, hipStream_t stream);
+                         const PostOp& post, void* y_any, const CodeIo& io, hipStream_t stream, const float* pix = nullptr);
 // the k_stem_small instance it runs, printed from the selection it consumes (slfp_debug_stem_instance)
-const char* stem_small_instance_name(const slfp_conv2d_desc& d, const ConvPlan& p, const PostOp& post, const CodeIo& io);
+const char* stem_small_instance_name(const slfp_conv2d_desc& d, const ConvPlan& p, const PostOp& post, const CodeIo& io, bool u8 = false);
 
 // XCD-aware block remap (MI355X: 8 XCDs, blocks are dealt round-robin over them, so
 // blocks b and b+8 share an L2).  Maps the hardware block id to a logical id such that

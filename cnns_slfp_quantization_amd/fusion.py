@@ -716,7 +716,8 @@ def link_codes_traced(model, example_input, entries=False):
         b, via_relu, pools = cand[a][0]
         flags = _post_flags(a) | (1 if via_relu else 0)
         out = _reader_quant(b)
-        a_in = a in reads_codes or x_of(a).dtype == torch.uint8   # does `a` itself read codes (an earlier link)?
+        # does `a` itself read codes (an earlier link)?  uint8 into a stem marked by link_image_u8 is pixels, not codes
+        a_in = a in reads_codes or (x_of(a).dtype == torch.uint8 and a._image_table is None)
         entry = False
         if not supported(a, a_in, out, flags):
             entry = (entries and not a_in and x_of(a).dim() == 4
@@ -1002,6 +1003,68 @@ def unlink_stem(model):
     for m in list(model.modules()):
         if "_stem_link" in m.__dict__:
             _restore_stem(m)
+            n += 1
+    return n
+
+
+# ------------------------------------------------------------------ the image stem reads uint8 pixels
+def _mark_image_stem(stem, table):
+    """Give Conv2d_Q `stem` the pixel table (float32 [C_in][256], moved to the weights' device): from now on a uint8 input is pixels."""
+    from . import image_u8
+    table = image_u8.check_table(table)
+    if stem.groups != 1 or stem.in_channels != table.shape[0]:
+        raise ValueError(f"link_image_u8: the stem reads {stem.in_channels} channels in {stem.groups} group(s), the table has {table.shape[0]}")
+    stem._image_table = table.to(stem.weight.device)   # a registered, non-persistent buffer: the state dict keeps its keys
+
+
+def _restore_image_stem(stem):
+    stem._image_table = None
+    stem.__dict__["_last_pixels"] = None
+
+
+def link_image_u8(model, table, example_input):
+    """The net reads uint8 pixels: `table` (image_u8.pixel_table: float32 [C][256], ToTensor + Normalize or any per-channel elementwise
+    preprocessing as data) and `example_input`, a uint8 batch of logical shape (N, C, H, W) in channels_last on the model's device.  One
+    traced forward on the expanded batch (image_u8.expand) finds the Conv2d_Q that reads the model input; it must run once, have
+    groups == 1 and C_in == C.  It gets the table as the non-persistent buffer `_image_table`, which gives uint8 input the meaning
+    "pixels" at this one module: in inference, where the library has a byte form of the stem's kernel (slfp_conv2d_u8_supported), one
+    slfp_conv2d_fwd_u8 launch reads the bytes -- float32 out or, linked by link_stem / link_codes[_traced], codes out --; in training,
+    under autograd, or for a stem without that form the bytes are expanded on the device and the ordinary path runs
+    (`_last_kernel`: "u8-expand+..."), so gradients and `input_q` are exactly the float32 path's.  float32 input keeps working as before;
+    NCHW-contiguous bytes, CPU bytes or another channel count raise TypeError.  The model must then reproduce, with torch.equal, its
+    output on the expanded batch; otherwise the mark is rolled back with a warning.  Run it after the other passes (their example
+    input is float32) or before them; it composes with all of them and is undone by unlink_image_u8.  Returns 1 or 0."""
+    from . import image_u8
+    table = image_u8.check_table(table)
+    if not (torch.is_tensor(example_input) and example_input.dtype == torch.uint8 and example_input.dim() == 4):
+        raise TypeError("link_image_u8: example_input must be a 4-d torch.uint8 pixel batch")
+    if example_input.shape[1] != table.shape[0] or not any(_is_conv_q(m) for m in model.modules()):
+        return 0
+    if example_input.is_cuda:
+        x32 = image_u8.expand(example_input, table.to(example_input.device))
+    else:   # no kernel runs on the CPU: only a q_bit 32 model traces there, and the verification below then refuses the link
+        x32 = table[torch.arange(table.shape[0]).view(1, -1, 1, 1), example_input.long()].contiguous(memory_format=torch.channels_last)
+    tr = _Trace(model, x32)
+    y0 = tr.output
+    readers = [c for c in tr.readers(x32) if _is_conv_q(c.mod)]
+    others = [c for c in tr.readers(x32) if not _is_conv_q(c.mod) and not isinstance(c.mod, nn.Identity)]
+    if not torch.is_tensor(y0) or len(readers) != 1 or others or tr.runs(readers[0].mod) != 1:
+        return 0   # no single Conv2d_Q takes the image
+    stem = readers[0].mod
+    if stem.groups != 1 or stem.in_channels != table.shape[0] or stem._image_table is not None:
+        return 0
+    tr.release()
+    _mark_image_stem(stem, table)
+    return int(_verified(lambda: model(example_input), y0, lambda: _restore_image_stem(stem), reraise=True,
+                         warn="link_image_u8: the model does not take the uint8 batch ({}); rolled back"))
+
+
+def unlink_image_u8(model):
+    """Undo link_image_u8: the stems read float32 only (and uint8 as codes) again.  Returns the number of stems unmarked."""
+    n = 0
+    for m in model.modules():
+        if _is_conv_q(m) and m._image_table is not None:
+            _restore_image_stem(m)
             n += 1
     return n
 

@@ -425,6 +425,38 @@ int slfp_conv2d_fwd_codes_lut(const slfp_conv2d_desc* d, const slfp_conv2d_io* i
                               int64_t y_ld, void* workspace, void* stream);
 int slfp_debug_layerout_lut_mismatches(unsigned long long* out1, void* stream);
 
+/* ---- Image stems that read uint8 pixels ----
+ * A decoded image is HWC bytes; ToTensor() + Normalize(mean, std) -- or any per-channel elementwise preprocessing -- maps byte v of
+ * channel c to one of 256 float32 values, pix_table[c][v].  slfp_conv2d_fwd_u8 takes the bytes and that table.
+ * Contract: the result is bit for bit what the matching float32 entry point (slfp_conv2d_fwd_post, or slfp_conv2d_fwd_codes[_ws]
+ * with io->y_codes == 1) returns for the float32 tensor x32[n,h,w,c] = pix_table[c][x[n,h,w,c]], from the same kernel instance
+ * family, the same prepared blob (slfp_conv2d_prepare_weights) and the same epilogue.  Each workgroup applies the kernel's own
+ * per-element encode to the 256 * C_in table entries once (LDS) and the fill step becomes a byte load and a lookup; a padded tap
+ * contributes the operand +0 as before (not pix_table[c][0]); NaN / inf entries follow the float32 kernels' rules.
+ *   x          NHWC bytes, N*H*W*C_in, dense, ANY byte alignment (plain byte loads; nothing outside [x, x + N*H*W*C_in) is read)
+ *   pix_table  device float32 [C_in][256], 16-byte aligned
+ *   io         NULL or io->y_codes == 0: float32 out, post_flags as slfp_conv2d_fwd_post (SLFP_POST_LAYEROUT included);
+ *              io->y_codes == 1: the reader's codes (ReLU folded, or signed), y_qbits 8 or 7
+ *   workspace  as the float32 entry point of the layer (slfp_conv2d_workspace_bytes); NULL where that is 0
+ * Supported (slfp_conv2d_u8_supported: 1 / 0, host only): the 3x3 s2 3 -> 32 stem on k_stem_fixed's threshold-table form (the byte
+ * entry sends k_stem_mx's geometry there too: both equal the CPU restatement bit for bit), the small-K matrix-core stems
+ * (k_stem_small) and the large-kernel stems (k_stem_rows; k_stem_im2row's pre-pass reads the bytes).  Refused with
+ * SLFP_ERR_UNSUPPORTED before any device work: io->x_codes == 1, the table epilogue, SLFP_POST_LAYEROUT with code output, NCHW on
+ * either side, groups != 1, C_in > 4, every layer whose float32 form runs k_direct, the generic k_stem or k_stem_fixed without a
+ * threshold table, and qbits 8 with SLFP_MFMA_F16X3.  NULL x / pix_table / y / wprep: SLFP_ERR_BAD_ARG.
+ * slfp_debug_stem_u8_instance: the instance the launch consumes, from the same selection, in slfp_debug_stem_instance's grammar
+ * with a `u8` word in front of the output form ("stem/fixed/tab/u8/yc", "small/nt4/act8/u8/f32", "rows/nt6/sfp7/u8/yc-signed",
+ * "im2row/nt4/act8/u8/f32"); "none" where the query says 0.
+ * slfp_image_u8_expand_f32: y[p][c] = pix_table[c][x[p][c]] for n_pixels pixels of c = 1..4 channels in one pass (x: any alignment;
+ * y: 16-byte aligned, 16-byte stores) -- the float32 tensor of the contract above, for every layer without a byte form and for
+ * training. */
+int slfp_conv2d_u8_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int post_flags);
+int slfp_conv2d_fwd_u8(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const uint8_t* x, const float* pix_table,
+                       const void* wprep, const float* bias, const float* post_scale, const float* post_shift,
+                       int post_flags, void* y, void* workspace, void* stream);
+const char* slfp_debug_stem_u8_instance(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int post_flags, int has_post);
+int slfp_image_u8_expand_f32(const uint8_t* x, const float* pix_table, float* y, int64_t n_pixels, int c, void* stream);
+
 /* nn.MaxPool2d (floor mode, dilation 1) on a tensor of activation codes (NHWC, C a multiple of 4; 16-byte aligned): the class
  * of a window's largest input is the highest class among its codes in the order of the classes' pre-images (the clamp literal
  * of Qbits 8 ranks above the top regular code, "tiny" above exact zero, signed codes by decreasing magnitude), so
