@@ -17,6 +17,7 @@ BWD_DENSE = 1  # slfp_conv2d_bwd_*_ex flags: SLFP_BWD_DENSE
 MFMA_DEFAULT, MFMA_F16X1, MFMA_F16X3 = 0, 1, 3
 OPT_SGD, OPT_DSGD, OPT_SSGD = 0, 1, 2
 LAYEROUT_LUT_BYTES = 4928  # SLFP_LAYEROUT_LUT_BYTES
+LAYEROUT_TABLE_FLOATS = LAYEROUT_LUT_BYTES  # SLFP_LAYEROUT_TABLE_FLOATS: one float32 per layer-output class, padded alike
 
 # every symbol include/slfp.h declares (tests check the .so exports exactly these)
 SYMBOLS = (
@@ -44,6 +45,7 @@ SYMBOLS = (
     "slfp_bn_train_supported", "slfp_bn_train_workspace_bytes", "slfp_bn_train_fwd", "slfp_bn_train_bwd", "slfp_debug_bn_split",
     "slfp_debug_dwpw_instance",
     "slfp_conv2d_u8_supported", "slfp_conv2d_fwd_u8", "slfp_debug_stem_u8_instance", "slfp_image_u8_expand_f32",
+    "slfp_bn_lut_train_fwd", "slfp_bn_lut_train_bwd",
 )
 
 
@@ -176,6 +178,8 @@ def load():
         "slfp_bn_train_workspace_bytes": (sz, [i64, i64, i64, i64]),
         "slfp_bn_train_fwd": (ci, [vp, vp, vp, vp, vp, cf, cf, ci, vp, vp, vp, i64, i64, i64, i64, ci, vp, sz, vp]),
         "slfp_bn_train_bwd": (ci, [vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, i64, i64, i64, i64, ci, vp, sz, vp]),
+        "slfp_bn_lut_train_fwd": (ci, [vp, vp, vp, vp, vp, cf, cf, vp, vp, vp, vp, vp, i64, i64, i64, i64, ci, vp, sz, vp]),
+        "slfp_bn_lut_train_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, ci, vp, sz, vp]),
         "slfp_debug_bn_split": (ci, [i64, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
         "slfp_debug_dwpw_instance": (ctypes.c_char_p, [dp, dp, ctypes.POINTER(ConvIo), ci, ci, ci]),
         "slfp_conv2d_u8_supported": (ci, [dp, ctypes.POINTER(ConvIo), ci, ci]),

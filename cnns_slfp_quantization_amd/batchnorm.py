@@ -1,7 +1,9 @@
 """Training-mode BatchNorm2d (+ReLU) on libslfp_hip's kernels (csrc/bn_train.hip; include/slfp.h states the order of every
 sum): the autograd Function behind fusion.TrainBatchNorm2d.  float32 channels_last tensors on the ROCm device only; there is no
 fallback in here -- the module decides with bn_train_supported() and otherwise runs ATen's batch_norm itself."""
+import numpy as np
 import torch
+import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib
@@ -92,3 +94,106 @@ class hip_bn_train(torch.autograd.Function):
                                            save_invstd.data_ptr(), 1 if ctx.relu else 0, gx.data_ptr(), _ptr(ggamma), _ptr(gbeta),
                                            n, h, w, c, _lib.LAYOUT_NHWC, ws.data_ptr(), nbytes, _stream_handle(x)))
         return gx if ctx.needs_input_grad[0] else None, ggamma, gbeta, None, None, None, None, None
+
+
+# ---- BatchNorm2d -> layerout_quantize_func -> activation (slfp_bn_lut_train_fwd / _bwd) -------------------
+# The size rule of the table form, read from profiles/bn_layerout_train_bench.json with the spread rule of sections 12 and 27: a
+# size class is on the kernels by default only if forward + backward of the swapped block beat the stock modules by more than
+# the stock leg's round-to-round spread.  Every shape of 12.25 M elements (N C H W) and more did, by 1.9x to 3.4x.  Below, both
+# legs sit on the host's launch floor (0.10 ms for the block's six launches, 0.11-0.26 ms for the stock dozen): the block was
+# faster on most shapes (up to 2.4x at 6 M elements), but the floor itself moved between 0.10 and 0.19 ms from one round to
+# the next, and over three runs of the benchmark shapes of 0.5, 1, 2, 3, 4 and 8 M elements each missed the rule in one run or
+# another (the two earlier runs: profiles/bn_layerout_train_bench_earlier.json).  The module leaves those tensors to ATen unless told otherwise (min_elements=0).
+LUT_MIN_ELEMENTS = 12 << 20
+
+
+def _lut_act_types():
+    from . import activation_func as af
+    return (nn.ReLU, nn.GELU, nn.SiLU, nn.Sigmoid, af.Swish, af.Sigmoid)
+
+
+def layerout_act_tables(acts, device):
+    """(F, D) for the activation modules `acts` behind a layer-output quantizer: two float32 tensors of _lib.LAYEROUT_TABLE_FLOATS
+    entries on `device` (a CPU device too), indexed by layer-output class (slfp_layerout_lut_values; index 0 is NaN).  F is the
+    stock modules applied in order to the class values, D the modules' own derivative there: autograd's gradient of F.sum().
+    Padding slots are 0 in both.  Accepted, by exact type: nn.ReLU, nn.GELU, nn.SiLU, nn.Sigmoid, activation_func.Swish /
+    Sigmoid.  activation_func.STL is refused: its backward is a function of the incoming gradient, not a derivative at the
+    input.  As a guard the gradient is taken with ones and with twos upstream; the second must be twice the first wherever both
+    are finite, or the modules' backward is no multiplication by a table."""
+    acts = list(acts)
+    for act in acts:
+        if type(act) not in _lut_act_types():
+            raise TypeError(f"layerout_act_tables: {type(act).__name__} is not an elementwise activation with a derivative table "
+                            "(nn.ReLU, nn.GELU, nn.SiLU, nn.Sigmoid, activation_func.Swish, activation_func.Sigmoid)")
+    n = _lib.LAYEROUT_TABLE_FLOATS
+    L = _lib.load()
+    vals = np.zeros(n, dtype=np.float32)
+    _lib.check(L.slfp_layerout_lut_values(vals.ctypes.data, n))
+    classes = L.slfp_layerout_lut_classes()
+    v = torch.from_numpy(vals).to(device).requires_grad_(True)
+    with torch.enable_grad():
+        f = v.clone()
+        for act in acts:
+            f = act(f.clone())   # (an in-place module writes into the copy)
+        if not torch.is_tensor(f) or f.shape != (n,) or f.dtype != torch.float32:
+            raise RuntimeError("layerout_act_tables: an activation module did not return an elementwise float32 result")
+        if acts:
+            d1, = torch.autograd.grad(f, v, torch.ones_like(f), retain_graph=True)
+            d2, = torch.autograd.grad(f, v, torch.full_like(f, 2.0))
+        else:
+            d1, d2 = torch.ones_like(f), torch.full_like(f, 2.0)
+    both = torch.isfinite(d1) & torch.isfinite(d2)
+    if not torch.equal(d2[both], (2.0 * d1)[both]):
+        raise RuntimeError("layerout_act_tables: the modules' backward is not linear in the incoming gradient")
+    F, D = f.detach().clone(), d1.detach().clone()
+    F[classes:] = 0
+    D[classes:] = 0
+    return F.contiguous(), D.contiguous()
+
+
+class hip_bn_lut_train(torch.autograd.Function):
+    """y = act(layerout(batch_norm(x))) with batch statistics, the activation as the table `ftab` over the layer-output class and
+    its derivative as `dtab` (layerout_act_tables, on x's device); running_mean / running_var are updated in place.  x:
+    channels_last float32 that bn_train_supported() accepts.  Saved for the backward: x, weight, bias, save_mean, save_invstd and
+    save_lo -- never y (the class is recomputed from x), so the caller may change y in place behind the module."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, ftab, dtab):
+        L = _lib.load()
+        n, c, h, w = x.shape
+        x = x.detach()
+        gamma, beta = _vec(weight), _vec(bias)
+        y = torch.empty_like(x)   # keeps the channels_last strides
+        save_mean = torch.empty(c, dtype=torch.float32, device=x.device)
+        save_invstd = torch.empty(c, dtype=torch.float32, device=x.device)
+        save_lo = torch.empty(c, dtype=torch.float32, device=x.device)
+        with _on_device(x.device):
+            nbytes = L.slfp_bn_train_workspace_bytes(n, h, w, c)
+            ws = _workspace(x.device, nbytes)
+            _lib.check(L.slfp_bn_lut_train_fwd(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(running_mean), _ptr(running_var),
+                                               float(momentum), float(eps), ftab.data_ptr(), y.data_ptr(), save_mean.data_ptr(),
+                                               save_invstd.data_ptr(), save_lo.data_ptr(), n, h, w, c, _lib.LAYOUT_NHWC,
+                                               ws.data_ptr(), nbytes, _stream_handle(x)))
+        ctx.dtab = dtab
+        ctx.save_for_backward(x, weight, bias, save_mean, save_invstd, save_lo)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        L = _lib.load()
+        x, weight, bias, save_mean, save_invstd, save_lo = ctx.saved_tensors
+        n, c, h, w = x.shape
+        gy = _nhwc(gy)
+        gamma, beta = _vec(weight), _vec(bias)
+        gx = torch.empty_like(x)
+        ggamma = torch.empty_like(save_mean) if ctx.needs_input_grad[1] else None
+        gbeta = torch.empty_like(save_mean) if ctx.needs_input_grad[2] else None
+        with _on_device(x.device):
+            nbytes = L.slfp_bn_train_workspace_bytes(n, h, w, c)
+            ws = _workspace(x.device, nbytes)
+            _lib.check(L.slfp_bn_lut_train_bwd(x.data_ptr(), gy.data_ptr(), gamma.data_ptr(), beta.data_ptr(), save_mean.data_ptr(),
+                                               save_invstd.data_ptr(), save_lo.data_ptr(), ctx.dtab.data_ptr(), gx.data_ptr(),
+                                               _ptr(ggamma), _ptr(gbeta), n, h, w, c, _lib.LAYOUT_NHWC, ws.data_ptr(), nbytes,
+                                               _stream_handle(x)))
+        return gx if ctx.needs_input_grad[0] else None, ggamma, gbeta, None, None, None, None, None, None

@@ -27,10 +27,19 @@
 //                      xh = ((x - save_mean) - lo) * invstd);  gbeta = f32(SG), ggamma = f32(SX), and for the last pass
 //                      mb = f32(SG / M), mg = f32(SX / M), f32(lo)
 //   k_bn_bwd_dx        a = gamma * invstd;  xh = ((x - save_mean) - lo) * invstd;  gx = a * ((g - mb) - (xh * mg))
+// The LUT forms (k_bn_apply, k_bn_bwd_reduce, k_bn_bwd_dx with LUT = true; slfp_bn_lut_train_fwd / _bwd) put the layer-output
+// quantizer and the activation behind it into the same passes, for the training blocks [Conv2d_Q, BatchNorm2d,
+// layerout_quantize_func, ReLU | Swish | GELU].  After the quantizer a value is one of kLayeroutClasses, so the activation is a
+// float32 table over the class (act_table) and its derivative another (dact_table):
+//   forward    t = the apply above with relu = 0;  y = act_table[layerout_class(layerout_bits(t))]
+//   backward   the class is recomputed from x with the forward's own expression (save_lo is the forward's lo, handed over
+//              bit for bit);  g = gy * dact_table[class]  (the quantizer is a straight-through estimator);  the rest as above.
+// Each workgroup copies its table (19 712 B) into LDS once; a lookup is one ds_read_b32 at a random address.
 // The two finalize kernels stage the records of 256 slabs x 8 channels in LDS with all 256 lanes (and the per-slab weights
 // n_b / n and n_a n_b / n, which depend on the slab index alone), then one lane per channel runs the serial chain.
 #include "slfp_device.hpp"
 #include "slfp_host.hpp"
+#include "slfp_layerout_lut.hpp"
 
 #include <algorithm>
 
@@ -41,6 +50,8 @@ constexpr int kBnTargetWgs = 512;    // two workgroups per CU on 256 CUs
 constexpr int kBnMaxSlabs = 1024;
 constexpr int kBnFinCh = 8;          // channels per finalize workgroup
 constexpr int kBnFinChunk = 256;     // slabs staged in LDS at a time
+constexpr int kBnTableFloats = SLFP_LAYEROUT_TABLE_FLOATS;   // one float32 per layer-output class, padded
+static_assert(kBnTableFloats % 4 == 0 && kBnTableFloats >= kLayeroutClasses, "the table is copied 16 bytes at a time");
 
 struct BnSplit {
     int64_t rows, slabs;   // R, S: R (S - 1) < M <= R S
@@ -95,6 +106,8 @@ struct BnArgs {
     float4* rec;           // forward workspace: [S][C] (count bits, k, s1, s2)
     float4* part;          // backward workspace: [S][C] (sg, sx, sd, 0)
     float* gmean;          // workspace behind the records: backward [3][C] mb, mg, lo; forward [C] lo = f32(mean - save_mean)
+    const float* lo_fwd;   // LUT backward: the forward's lo (save_lo)
+    const float* table;    // LUT forms: act_table (forward) / dact_table (backward), kBnTableFloats floats
     int64_t m, c, rows;
     int slabs, tx_log2, relu;
 };
@@ -122,6 +135,26 @@ template <int V> __device__ __forceinline__ Pack<V> bn_fill(float f) {
 #pragma unroll
     for (int e = 0; e < V; ++e) r.v[e] = f;
     return r;
+}
+
+// LUT forms: the workgroup's copy of the table in LDS, published by the barrier (every lane of the workgroup calls this).  The
+// plain forms get no LDS and a null pointer they never read.
+template <bool LUT> __device__ __forceinline__ const float* bn_table_lds(const float* g) {
+    if constexpr (LUT) {
+        __shared__ __attribute__((aligned(16))) float sTab[kBnTableFloats];
+        for (int i = threadIdx.x; i < kBnTableFloats / 4; i += kBnThreads)
+            reinterpret_cast<float4*>(sTab)[i] = reinterpret_cast<const float4*>(g)[i];
+        __syncthreads();
+        return sTab;
+    } else {
+        return nullptr;
+    }
+}
+
+// LUT forms: the class of one element, from the forward's own expression (sc = invstd * gamma)
+__device__ __forceinline__ uint32_t bn_class(const float x, const float mean, const float lo, const float sc, const float beta) {
+    const float t = (((x - mean) - lo) * sc) + beta;
+    return layerout_class(layerout_bits(__float_as_uint(t)));
 }
 
 // Where a lane stands: its first channel, whether that channel exists, its rows [first, r1) with stride nty.
@@ -250,9 +283,10 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_finalize(const BnArgs a, floa
     if (running_var) running_var[l.c] = (float)((1.0 - mo) * (double)running_var[l.c] + mo * (var * cnt / (cnt - 1.0)));
 }
 
-template <int V>
+template <int V, bool LUT = false>
 __global__ __launch_bounds__(kBnThreads) void k_bn_apply(const BnArgs a) {
     const BnLane<V> l(a);
+    const float* const sTab = bn_table_lds<LUT>(a.table);
     if (!l.live) return;
     const size_t ld = (size_t)a.c;
     const Pack<V> mean = bn_ld<V>(a.mean + l.ch), lo = bn_ld<V>(a.gmean + l.ch), beta = bn_ld<V>(a.beta + l.ch);
@@ -266,9 +300,13 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_apply(const BnArgs a) {
     auto f = [&](Pack<V> v) {
 #pragma unroll
         for (int e = 0; e < V; ++e) {
-            float t = (((v.v[e] - mean.v[e]) - lo.v[e]) * sc.v[e]) + beta.v[e];
-            if (relu) t = t < 0.f ? 0.f : t;
-            v.v[e] = t;
+            if constexpr (LUT) {
+                v.v[e] = sTab[bn_class(v.v[e], mean.v[e], lo.v[e], sc.v[e], beta.v[e])];
+            } else {
+                float t = (((v.v[e] - mean.v[e]) - lo.v[e]) * sc.v[e]) + beta.v[e];
+                if (relu) t = t < 0.f ? 0.f : t;
+                v.v[e] = t;
+            }
         }
         return v;
     };
@@ -287,13 +325,24 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_apply(const BnArgs a) {
 // g of one element: the ReLU's mask is read from the forward's own output
 __device__ __forceinline__ float bn_g(const float gy, const float y, const int relu) { return relu ? (y > 0.f ? gy : 0.f) : gy; }
 
-template <int V>
+template <int V, bool LUT = false>
 __global__ __launch_bounds__(kBnThreads) void k_bn_bwd_reduce(const BnArgs a) {
     const BnLane<V> l(a);
+    const float* const sTab = bn_table_lds<LUT>(a.table);
     const size_t ld = (size_t)a.c;
     const size_t c0 = l.live ? (size_t)l.ch : 0;
     const Pack<V> mean = l.live ? bn_ld<V>(a.mean + c0) : bn_fill<V>(0.f);
     const Pack<V> invstd = l.live ? bn_ld<V>(a.invstd + c0) : bn_fill<V>(0.f);
+    Pack<V> lof = bn_fill<V>(0.f), sc = bn_fill<V>(0.f), beta = bn_fill<V>(0.f);   // LUT: the forward's lo, invstd * gamma, beta
+    if constexpr (LUT) {
+        if (l.live) {
+            const Pack<V> gamma = bn_ld<V>(a.gamma + c0);
+            lof = bn_ld<V>(a.lo_fwd + c0);
+            beta = bn_ld<V>(a.beta + c0);
+#pragma unroll
+            for (int e = 0; e < V; ++e) sc.v[e] = invstd.v[e] * gamma.v[e];
+        }
+    }
     const float* px = a.x + c0;
     const float* pg = a.gy + c0;
     const float* py = a.y + c0;   // read with relu only
@@ -302,7 +351,9 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_bwd_reduce(const BnArgs a) {
     auto add = [&](const Pack<V>& x, const Pack<V>& gy, const Pack<V>& y) {
 #pragma unroll
         for (int e = 0; e < V; ++e) {
-            const float g = bn_g(gy.v[e], y.v[e], relu);
+            float g;
+            if constexpr (LUT) g = gy.v[e] * sTab[bn_class(x.v[e], mean.v[e], lof.v[e], sc.v[e], beta.v[e])];
+            else g = bn_g(gy.v[e], y.v[e], relu);
             const float d = x.v[e] - mean.v[e];
             s[0].v[e] = s[0].v[e] + g;
             s[1].v[e] = s[1].v[e] + g * (d * invstd.v[e]);
@@ -372,9 +423,10 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_bwd_finalize(const BnArgs a, 
     a.gmean[2 * (size_t)a.c + (size_t)l.c] = (float)lo;
 }
 
-template <int V>
+template <int V, bool LUT = false>
 __global__ __launch_bounds__(kBnThreads) void k_bn_bwd_dx(const BnArgs a) {
     const BnLane<V> l(a);
+    const float* const sTab = bn_table_lds<LUT>(a.table);
     if (!l.live) return;
     const size_t ld = (size_t)a.c;
     const Pack<V> mean = bn_ld<V>(a.mean + l.ch), invstd = bn_ld<V>(a.invstd + l.ch), gamma = bn_ld<V>(a.gamma + l.ch);
@@ -382,6 +434,11 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_bwd_dx(const BnArgs a) {
     Pack<V> sc;
 #pragma unroll
     for (int e = 0; e < V; ++e) sc.v[e] = gamma.v[e] * invstd.v[e];
+    Pack<V> lof = bn_fill<V>(0.f), beta = bn_fill<V>(0.f);   // LUT: the forward's lo and beta (its invstd * gamma is sc)
+    if constexpr (LUT) {
+        lof = bn_ld<V>(a.lo_fwd + l.ch);
+        beta = bn_ld<V>(a.beta + l.ch);
+    }
     const float* px = a.x + l.ch;
     const float* pg = a.gy + l.ch;
     const float* py = a.y + l.ch;   // read with relu only
@@ -391,7 +448,9 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_bwd_dx(const BnArgs a) {
         Pack<V> o;
 #pragma unroll
         for (int e = 0; e < V; ++e) {
-            const float g = bn_g(gy.v[e], y.v[e], relu);
+            float g;
+            if constexpr (LUT) g = gy.v[e] * sTab[bn_class(x.v[e], mean.v[e], lof.v[e], sc.v[e], beta.v[e])];
+            else g = bn_g(gy.v[e], y.v[e], relu);
             const float xh = ((x.v[e] - mean.v[e]) - lo.v[e]) * invstd.v[e];
             o.v[e] = sc.v[e] * ((g - mb.v[e]) - (xh * mg.v[e]));
         }
@@ -419,12 +478,15 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_bwd_dx(const BnArgs a) {
 }
 
 // The refusals both entry points share, in the order of include/slfp.h; *m receives N H W.
+// `table`: the LUT entry points' act_table / dact_table (has_table), 16-byte aligned whatever c is.
 static int bn_check(const char* fn, int64_t n, int64_t h, int64_t w, int64_t c, int x_layout, int relu, const void* const* big,
-                    int nbig, const void* const* small, int nsmall, const void* workspace, size_t ws_bytes, int64_t* m) {
+                    int nbig, const void* const* small, int nsmall, const void* workspace, size_t ws_bytes, int64_t* m,
+                    bool has_table = false, const void* table = nullptr) {
     for (int i = 0; i < nbig; ++i)
         if (!big[i]) return fail(SLFP_ERR_BAD_ARG, "%s: null pointer", fn);
     for (int i = 0; i < nsmall; ++i)
         if (!small[i]) return fail(SLFP_ERR_BAD_ARG, "%s: null pointer", fn);
+    if (has_table && !table) return fail(SLFP_ERR_BAD_ARG, "%s: null pointer (the table)", fn);
     if (x_layout != SLFP_LAYOUT_NHWC && x_layout != SLFP_LAYOUT_NCHW) return fail(SLFP_ERR_BAD_ARG, "%s: bad layout", fn);
     if (relu != 0 && relu != 1) return fail(SLFP_ERR_BAD_ARG, "%s: relu must be 0 or 1", fn);
     if (n < 0 || h < 1 || w < 1 || c < 1) return fail(SLFP_ERR_SHAPE, "%s: bad geometry", fn);
@@ -439,6 +501,7 @@ static int bn_check(const char* fn, int64_t n, int64_t h, int64_t w, int64_t c, 
     for (int i = 0; i < nsmall; ++i)
         if (reinterpret_cast<uintptr_t>(small[i]) & mask)
             return fail(SLFP_ERR_ALIGNMENT, "%s: the per-channel arrays must be %d-byte aligned", fn, (int)mask + 1);
+    if (has_table && !aligned16(table)) return fail(SLFP_ERR_ALIGNMENT, "%s: the table must be 16-byte aligned", fn);
     const size_t need = bn_workspace_bytes(*m, c);
     if (need && (!workspace || ws_bytes < need || !aligned16(workspace)))
         return fail(SLFP_ERR_BAD_ARG, "%s: %zu bytes of 16-byte aligned workspace required (slfp_bn_train_workspace_bytes)", fn, need);
@@ -536,6 +599,69 @@ int slfp_bn_train_bwd(const float* x, const float* y, const float* gy, const flo
     if (e != SLFP_OK) return e;
     hipLaunchKernelGGL(s.vec == 4 ? k_bn_bwd_dx<4> : k_bn_bwd_dx<1>, grid, block, 0, st, a);
     return check_launch("slfp batch-norm backward dx kernel");
+}
+
+int slfp_bn_lut_train_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                          float momentum, float eps, const float* act_table, float* y, float* save_mean, float* save_invstd,
+                          float* save_lo, int64_t n, int64_t h, int64_t w, int64_t c, int x_layout, void* workspace,
+                          size_t ws_bytes, void* stream) {
+    const char* fn = "slfp_bn_lut_train_fwd";
+    const void* big[] = {x, y};
+    const void* small[] = {gamma, beta, save_mean, save_invstd, save_lo};
+    int64_t m = 0;
+    const int rc = bn_check(fn, n, h, w, c, x_layout, 0, big, 2, small, 5, workspace, ws_bytes, &m, true, act_table);
+    if (rc != SLFP_OK) return rc;
+    if ((running_mean == nullptr) != (running_var == nullptr))
+        return fail(SLFP_ERR_BAD_ARG, "%s: running_mean and running_var are given together or not at all", fn);
+    if ((reinterpret_cast<uintptr_t>(running_mean) | reinterpret_cast<uintptr_t>(running_var)) & 3)
+        return fail(SLFP_ERR_ALIGNMENT, "%s: the running statistics must be 4-byte aligned", fn);
+    if (x == y) return fail(SLFP_ERR_BAD_ARG, "%s: y may not alias x (the backward reads x)", fn);
+    if (m == 0) return SLFP_OK;
+    const BnSplit s = bn_split(m, c);
+    BnArgs a = bn_args(s, m, c, 0, workspace);
+    a.x = x; a.out = y; a.gamma = gamma; a.beta = beta; a.mean = save_mean; a.invstd = save_invstd; a.table = act_table;
+    a.gmean = save_lo;   // the finalize kernel's lo goes to the caller instead of the workspace; the apply reads it there
+    const dim3 grid((unsigned)s.slabs, (unsigned)s.tiles), block(kBnThreads);
+    const hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(s.vec == 4 ? k_bn_stats<4> : k_bn_stats<1>, grid, block, 0, st, a);
+    int e = check_launch("slfp batch-norm statistics kernel");
+    if (e != SLFP_OK) return e;
+    hipLaunchKernelGGL(k_bn_finalize, dim3((unsigned)ceil_div(c, kBnFinCh)), block, 0, st, a, running_mean, running_var, momentum,
+                       eps, save_mean, save_invstd);
+    e = check_launch("slfp batch-norm finalize kernel");
+    if (e != SLFP_OK) return e;
+    hipLaunchKernelGGL((s.vec == 4 ? k_bn_apply<4, true> : k_bn_apply<1, true>), grid, block, 0, st, a);
+    return check_launch("slfp batch-norm table apply kernel");
+}
+
+int slfp_bn_lut_train_bwd(const float* x, const float* gy, const float* gamma, const float* beta, const float* save_mean,
+                          const float* save_invstd, const float* save_lo, const float* dact_table, float* gx, float* ggamma,
+                          float* gbeta, int64_t n, int64_t h, int64_t w, int64_t c, int x_layout, void* workspace,
+                          size_t ws_bytes, void* stream) {
+    const char* fn = "slfp_bn_lut_train_bwd";
+    const void* big[] = {x, gy, gx};
+    const void* small[] = {gamma, beta, save_mean, save_invstd, save_lo};
+    int64_t m = 0;
+    const int rc = bn_check(fn, n, h, w, c, x_layout, 0, big, 3, small, 5, workspace, ws_bytes, &m, true, dact_table);
+    if (rc != SLFP_OK) return rc;
+    if ((reinterpret_cast<uintptr_t>(ggamma) | reinterpret_cast<uintptr_t>(gbeta)) & 3)
+        return fail(SLFP_ERR_ALIGNMENT, "%s: ggamma and gbeta must be 4-byte aligned", fn);
+    if (gx == x) return fail(SLFP_ERR_BAD_ARG, "%s: gx may not alias x", fn);
+    if (m == 0) return SLFP_OK;
+    const BnSplit s = bn_split(m, c);
+    BnArgs a = bn_args(s, m, c, 0, workspace);
+    a.x = x; a.y = x; a.gy = gy; a.out = gx; a.gamma = gamma; a.beta = beta; a.mean = save_mean; a.invstd = save_invstd;
+    a.lo_fwd = save_lo; a.table = dact_table;
+    const dim3 grid((unsigned)s.slabs, (unsigned)s.tiles), block(kBnThreads);
+    const hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL((s.vec == 4 ? k_bn_bwd_reduce<4, true> : k_bn_bwd_reduce<1, true>), grid, block, 0, st, a);
+    int e = check_launch("slfp batch-norm table backward reduce kernel");
+    if (e != SLFP_OK) return e;
+    hipLaunchKernelGGL(k_bn_bwd_finalize, dim3((unsigned)ceil_div(c, kBnFinCh)), block, 0, st, a, ggamma, gbeta);
+    e = check_launch("slfp batch-norm backward finalize kernel");
+    if (e != SLFP_OK) return e;
+    hipLaunchKernelGGL((s.vec == 4 ? k_bn_bwd_dx<4, true> : k_bn_bwd_dx<1, true>), grid, block, 0, st, a);
+    return check_launch("slfp batch-norm table backward dx kernel");
 }
 
 }  // extern "C"

@@ -2023,3 +2023,159 @@ def restore_bn_train(model):
             elif isinstance(child, FoldedReLU) and getattr(child, "_bn_train", False):
                 parent._modules[name] = child.relu
     return n
+
+
+# ------------------------------------------------------------------ training-mode BatchNorm2d -> layer-output quantizer -> activation
+class FoldedTail(nn.Module):
+    """The slot of a layerout_quantize_func or of an activation module that a TrainBatchNormLayerout2d in front of it applies:
+    the identity, in the style of FoldedReLU.  The original is kept outside _modules (`mod`); it has no parameters, the state
+    dict does not change."""
+
+    def __init__(self, mod):
+        super().__init__()
+        object.__setattr__(self, "mod", mod)
+        self.training = mod.training
+
+    def extra_repr(self):
+        return type(self.mod).__name__
+
+    def forward(self, x):
+        return x
+
+
+class TrainBatchNormLayerout2d(nn.Module):
+    """The tail [BatchNorm2d, layerout_quantize_func(q_bit 7 or 8), activation(s)] of a training block of MobileNetV1_swish /
+    VGG16_gelu on libslfp_hip's kernels (slfp_bn_lut_train_fwd / slfp_bn_lut_train_bwd): behind the quantizer a
+    value is one of a few thousand classes, so the activation and its derivative are two float32 tables
+    (batchnorm.layerout_act_tables, built by the stock modules themselves, lazily per device).  As TrainBatchNorm2d it registers
+    the SAME Parameter and buffer objects under the same names and keeps the original modules outside _modules (`_bn`,
+    `_layerout`, `_acts`); it is not an nn.BatchNorm2d subclass.  The kernels run in training mode on a ROCm float32 4-d
+    channels_last tensor that slfp_bn_train_supported accepts and that has at least `min_elements` elements (None:
+    batchnorm.LUT_MIN_ELEMENTS, the measured rule), with weight, bias and the running statistics float32 on its device.  Eval mode, CPU tensors, autocast, other dtypes or layouts and smaller tensors
+    run F.batch_norm on the same buffers, then the kept quantizer module, then the kept activation modules: bit for bit what the
+    stock modules compute.  The output is never saved for the backward; it may be changed in place behind the module.
+      _last_kernel   "bn_lut_train", or "aten" """
+    _version = 2   # nn.BatchNorm2d's state-dict version (num_batches_tracked)
+
+    def __init__(self, bn, layerout, acts, min_elements=None):
+        super().__init__()
+        from .batchnorm import _lut_act_types
+        if isinstance(bn, TrainBatchNorm2d):
+            if bn._relu:
+                raise ValueError("TrainBatchNormLayerout2d: the TrainBatchNorm2d has a ReLU folded in")
+            # The wrapper holds the current Parameters and buffers: a move or a cast since the swap (.cuda(), .double()) replaced
+            # them on it alone, its stock module sits outside _modules.  Re-point the stock module first, as restore_bn_train does.
+            wrap, bn = bn, bn._bn
+            for key in ("weight", "bias"):
+                bn._parameters[key] = wrap._parameters[key]
+            for key in _BN_NAMES:
+                bn._buffers[key] = wrap._buffers[key]
+            bn.training = wrap.training
+        acts = tuple(acts)
+        for act in acts:
+            if type(act) not in _lut_act_types():
+                raise TypeError(f"TrainBatchNormLayerout2d: {type(act).__name__} has no derivative table")
+        object.__setattr__(self, "_bn", bn)
+        object.__setattr__(self, "_layerout", layerout)
+        object.__setattr__(self, "_acts", acts)
+        self.min_elements = min_elements
+        self.training = bn.training
+        self.num_features, self.eps, self.momentum = bn.num_features, bn.eps, bn.momentum
+        self.affine, self.track_running_stats = bn.affine, bn.track_running_stats
+        self.register_parameter("weight", bn.weight)
+        self.register_parameter("bias", bn.bias)
+        for name in _BN_NAMES:
+            self.register_buffer(name, getattr(bn, name))
+        self._tables = {}
+        self._last_kernel = None
+
+    def extra_repr(self):
+        return (f"{self.num_features}, eps={self.eps}, momentum={self.momentum}, layerout={self._layerout.q_bit}, "
+                f"acts={[type(a).__name__ for a in self._acts]}")
+
+    def tables(self, device):
+        """(F, D) of batchnorm.layerout_act_tables on `device`, built once per device."""
+        key = str(device)
+        t = self._tables.get(key)
+        if t is None:
+            from .batchnorm import layerout_act_tables
+            t = self._tables[key] = layerout_act_tables(self._acts, device)
+        return t
+
+    def forward(self, x):
+        from .batchnorm import hip_bn_lut_train, bn_train_supported, LUT_MIN_ELEMENTS
+        if x.dim() != 4:
+            raise ValueError(f"expected 4D input (got {x.dim()}D input)")
+        if self.training and self.track_running_stats and self.num_batches_tracked is not None:
+            self.num_batches_tracked.add_(1)
+        if (self.training and self.running_mean is not None and self.running_var is not None and x.is_cuda
+                and x.dtype == torch.float32 and not torch.is_autocast_enabled()
+                and all(t.device == x.device and t.dtype == torch.float32   # the kernels are handed these addresses
+                        for t in (self.weight, self.bias, self.running_mean, self.running_var))
+                and bn_train_supported(x, LUT_MIN_ELEMENTS if self.min_elements is None else self.min_elements)):
+            ftab, dtab = self.tables(x.device)
+            self._last_kernel = "bn_lut_train"
+            return hip_bn_lut_train.apply(x, self.weight, self.bias, self.running_mean, self.running_var, self.momentum, self.eps,
+                                          ftab, dtab)
+        self._last_kernel = "aten"
+        stats = self.training or (self.running_mean is None and self.running_var is None)
+        keep = not self.training or self.track_running_stats
+        y = torch.nn.functional.batch_norm(x, self.running_mean if keep else None, self.running_var if keep else None, self.weight,
+                                           self.bias, stats, self.momentum, self.eps)
+        y = self._layerout(y)
+        for act in self._acts:
+            y = act(y)
+        return y
+
+
+def _bn_lut_candidate(m):
+    return _bn_train_candidate(m) or (isinstance(m, TrainBatchNorm2d) and not m._relu)
+
+
+def use_device_bn_layerout_train(model, min_elements=None):
+    """Run the training blocks [BatchNorm2d, layerout_quantize_func, ReLU | Swish | GELU | ...] of `model` on libslfp_hip's table
+    kernels: inside an nn.Sequential, an affine nn.BatchNorm2d with a momentum (or a TrainBatchNorm2d without a folded ReLU, so
+    this pass and use_device_bn_train may run in either order), directly followed by a layerout_quantize_func with q_bit 7 or 8
+    and by one activation module batchnorm.layerout_act_tables accepts, each held in exactly one slot, becomes a
+    TrainBatchNormLayerout2d; the quantizer's and the activation's slots become FoldedTail placeholders.  q_bit == 32 (no
+    quantizer: no table), activation_func.STL, a shared module and a hand-wired block are skipped.  Opt-in; eval mode and everything
+    the kernels do not take run what the stock modules run, and so do tensors of fewer than `min_elements` elements (None:
+    batchnorm.LUT_MIN_ELEMENTS, the measured rule of DESIGN section 32; 0: every size).  Returns the number of blocks taken;
+    restore_bn_layerout_train undoes them."""
+    from .batchnorm import _lut_act_types
+    done = 0
+    for seq in [s for s in model.modules() if isinstance(s, nn.Sequential)]:
+        names = list(seq._modules.keys())
+        for i in range(len(names) - 2):
+            bn, lo, act = (seq._modules[k] for k in names[i:i + 3])
+            if not (_bn_lut_candidate(bn) and _is_layerout(lo) and type(act) in _lut_act_types()):
+                continue
+            if any(len(_slots_of(model, m)) != 1 for m in (bn, lo, act)):
+                continue
+            seq._modules[names[i]] = TrainBatchNormLayerout2d(bn, lo, (act,), min_elements)
+            seq._modules[names[i + 1]] = FoldedTail(lo)
+            seq._modules[names[i + 2]] = FoldedTail(act)
+            done += 1
+    return done
+
+
+def restore_bn_layerout_train(model):
+    """Undo use_device_bn_layerout_train: every slot gets its original module back (the stock nn.BatchNorm2d, also where a
+    TrainBatchNorm2d stood in the slot); the originals are pointed at the current parameters and buffers (the model may have been
+    moved or cast in between) and take the placeholders' training flags."""
+    n = 0
+    for parent in list(model.modules()):
+        for name, child in list(parent._modules.items()):
+            if isinstance(child, TrainBatchNormLayerout2d):
+                bn = child._bn
+                for key in ("weight", "bias"):
+                    bn._parameters[key] = child._parameters[key]
+                for key in _BN_NAMES:
+                    bn._buffers[key] = child._buffers[key]
+                bn.training = child.training
+                parent._modules[name] = bn
+                n += 1
+            elif isinstance(child, FoldedTail):
+                child.mod.training = child.training
+                parent._modules[name] = child.mod
+    return n

@@ -611,6 +611,42 @@ int slfp_bn_train_bwd(const float* x, const float* y, const float* gy, const flo
 /* host only: the split above for M = m rows of c channels (SLFP_ERR_SHAPE: m < 1 or c < 1 or beyond the supported range) */
 int slfp_debug_bn_split(int64_t m, int64_t c, int64_t* rows_per_slab, int64_t* slabs);
 
+/* ---- training-mode BatchNorm2d -> layer-output quantizer -> activation (csrc/bn_train.hip, the LUT forms) ------------------
+ * The tail [BatchNorm2d, layerout_quantize_func, ReLU | Swish | GELU] of the training blocks of MobileNetV1_swish / VGG16_gelu
+ * (nets_cifar/mobilenetv1.py:196-231, nets_cifar/vgg16.py:186-293), in training mode.  Behind the SFP<4,4> layer-output quantizer
+ * a value is one of slfp_layerout_lut_classes() classes, so an elementwise activation is a float32 table over the class index and
+ * its derivative another.  act_table, dact_table: device memory, SLFP_LAYEROUT_TABLE_FLOATS float32 each, 16-byte aligned; index i
+ * is the class of slfp_layerout_lut_values / layerout_class (csrc/slfp_layerout_lut.hpp), index 0 the NaN class; the caller
+ * builds both (act_table[i] = act(value_i), dact_table[i] = act'(value_i)).  The contract is exact:
+ *   statistics save_mean, save_invstd and the running statistics are exactly those of slfp_bn_train_fwd on the same x: the same
+ *              split, the same sums, the same finalize.  save_lo[c] = lo = f32(mean - save_mean), which slfp_bn_train_fwd keeps
+ *              in its workspace, is an output here: the backward must reproduce the forward's values bit for bit.
+ *   forward    t = (((x - save_mean) - save_lo) * (save_invstd * gamma)) + beta, the apply above with relu = 0;
+ *              q = layerout_bits(t), what slfp_quantize_layerout_f32 computes;  y = act_table[layerout_class(q)].  So y is
+ *              bit-identical to slfp_bn_train_fwd(relu = 0), then slfp_quantize_layerout_f32, then a gather from the table.
+ *              The apply pass reads x once and writes y once.
+ *   backward   the class of every element is recomputed from x, gamma, beta, save_mean, save_invstd and save_lo with the
+ *              forward's expression; a saved y is never read (Swish and GELU are not injective: the class is what matters).
+ *              g = gy * dact_table[class], one float32 multiply (the quantizer is a straight-through estimator: it passes the
+ *              gradient unchanged).  From there on gx, ggamma and gbeta are bit-identical to slfp_bn_train_bwd(relu = 0) called
+ *              with g in place of gy, the lo it recovers itself from SD / M included.  ggamma and gbeta may be NULL.  The
+ *              reduce pass reads x and gy; the dx pass reads x and gy and writes gx.
+ * No atomics; two calls give the same bits.  A NaN or an inf stays in its channel (a NaN's class is 0, an inf's +-248).  The
+ * denormal branch of layerout_class stays a cold branch.  Both take the supported set of slfp_bn_train_supported and the
+ * workspace of slfp_bn_train_workspace_bytes, and make the refusals of slfp_bn_train_fwd / slfp_bn_train_bwd in the same order
+ * before any device work; save_lo counts among the per-channel arrays, a NULL act_table, dact_table or save_lo is
+ * SLFP_ERR_BAD_ARG and a table address not aligned to 16 bytes SLFP_ERR_ALIGNMENT (after the per-channel arrays').  y may not
+ * alias x, gx not x. */
+#define SLFP_LAYEROUT_TABLE_FLOATS SLFP_LAYEROUT_LUT_BYTES   /* 4928 */
+int slfp_bn_lut_train_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                          float momentum, float eps, const float* act_table, float* y, float* save_mean, float* save_invstd,
+                          float* save_lo, int64_t n, int64_t h, int64_t w, int64_t c, int x_layout,
+                          void* workspace, size_t ws_bytes, void* stream);
+int slfp_bn_lut_train_bwd(const float* x, const float* gy, const float* gamma, const float* beta, const float* save_mean,
+                          const float* save_invstd, const float* save_lo, const float* dact_table, float* gx,
+                          float* ggamma, float* gbeta, int64_t n, int64_t h, int64_t w, int64_t c, int x_layout,
+                          void* workspace, size_t ws_bytes, void* stream);
+
 /* ---- self-check ------------------------------------------------------------------------
  * The kernels compute x / scale_div with an FMA correction chain on a host-computed
  * reciprocal instead of the IEEE division macro (csrc/slfp_device.hpp, ScaleDiv).  This
