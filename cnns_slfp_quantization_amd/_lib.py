@@ -46,6 +46,7 @@ SYMBOLS = (
     "slfp_debug_dwpw_instance",
     "slfp_conv2d_u8_supported", "slfp_conv2d_fwd_u8", "slfp_debug_stem_u8_instance", "slfp_image_u8_expand_f32",
     "slfp_bn_lut_train_fwd", "slfp_bn_lut_train_bwd",
+    "slfp_bn_res_train_fwd", "slfp_bn_res_train_bwd",
 )
 
 
@@ -180,6 +181,8 @@ def load():
         "slfp_bn_train_bwd": (ci, [vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, i64, i64, i64, i64, ci, vp, sz, vp]),
         "slfp_bn_lut_train_fwd": (ci, [vp, vp, vp, vp, vp, cf, cf, vp, vp, vp, vp, vp, i64, i64, i64, i64, ci, vp, sz, vp]),
         "slfp_bn_lut_train_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, ci, vp, sz, vp]),
+        "slfp_bn_res_train_fwd": (ci, [vp, vp, vp, vp, vp, vp, cf, cf, ci, vp, vp, vp, i64, i64, i64, i64, ci, vp, sz, vp]),
+        "slfp_bn_res_train_bwd": (ci, [vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, i64, i64, i64, i64, ci, vp, sz, vp]),
         "slfp_debug_bn_split": (ci, [i64, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
         "slfp_debug_dwpw_instance": (ctypes.c_char_p, [dp, dp, ctypes.POINTER(ConvIo), ci, ci, ci]),
         "slfp_conv2d_u8_supported": (ci, [dp, ctypes.POINTER(ConvIo), ci, ci]),

@@ -96,6 +96,82 @@ class hip_bn_train(torch.autograd.Function):
         return gx if ctx.needs_input_grad[0] else None, ggamma, gbeta, None, None, None, None, None
 
 
+# ---- BatchNorm2d -> residual add -> ReLU (slfp_bn_res_train_fwd / _bwd) -----------------------------------
+# The size rule of the residual form, by the spread rule of sections 27 and 32: the smallest size class from which this class and
+# every larger measured one beat the stock tail (BatchNorm, `+=`, ReLU) by more than the stock leg's round-to-round spread.
+# Read from profiles/bn_res_train_bench.json (forward + backward of the tail, ResNet-50's trunk shapes at batch 64 and 128):
+#   elements (N C H W)   rows                                   stock ms         kernels ms       speed-up     beyond spread
+#   98.00 M              128 x 56x56x256                        1.259            0.979            1.29         yes
+#   49.00 M              64 x 56x56x256, 128 x 28x28x512        0.638, 0.605     0.540, 0.500     1.18, 1.21   yes, yes
+#   24.50 M              64 x 28x28x512, 128 x 14x14x1024       0.264, 0.274     0.235, 0.225     1.12, 1.22   yes, yes
+#   12.25 M              64 x 14x14x1024, 128 x 7x7x2048        0.152, 0.176     0.218, 0.121     0.70, 1.46   no, yes
+#    6.12 M              64 x 7x7x2048                          0.151            0.218            0.69         no
+# (M = 2^20.)  A second run (profiles/bn_res_train_bench_second.json) repeated the three classes from 24.5 M on within 4 % and had
+# both 12.25 M rows ahead (1.20x, 1.56x) and 6.12 M behind (0.93x): at 12.25 M and below the six launches issued from Python sit on
+# the host's floor, 0.11-0.22 ms from one round to the next, and a class that missed in one run of two stays out.  So the module
+# leaves tails of fewer than 24 M elements to ATen unless told otherwise (min_elements=0): of ResNet-50's trunk at batch 64 that
+# admits layer1 and layer2, at batch 128 layer3 too.
+RES_MIN_ELEMENTS = 24 << 20
+
+
+class hip_bn_res_train(torch.autograd.Function):
+    """y = relu?(batch_norm(x) + res) with batch statistics: the tail of a Bottleneck (bn3, `out += identity`, the shared ReLU) in
+    the two passes of hip_bn_train; running_mean / running_var are updated in place.  x, res: float32 of one shape, x channels_last
+    as bn_train_supported() accepts it (res is made so).  Saved for the backward: x, weight, save_mean, save_invstd and, with
+    `relu`, y (the mask is read from it).  The residual's gradient is g = relu ? (y > 0 ? gy : 0) : gy: with relu it is a second
+    store of the dx pass, asked for only if res needs a gradient; without, gy itself is handed on."""
+
+    @staticmethod
+    def forward(ctx, x, res, weight, bias, running_mean, running_var, momentum, eps, relu):
+        L = _lib.load()
+        n, c, h, w = x.shape
+        if res.shape != x.shape or res.dtype != x.dtype or res.device != x.device:
+            raise ValueError("hip_bn_res_train: the residual must have x's shape, dtype and device")
+        x = x.detach()
+        res = _nhwc(res.detach())
+        gamma, beta = _vec(weight), _vec(bias)
+        y = torch.empty_like(x)   # keeps the channels_last strides
+        save_mean = torch.empty(c, dtype=torch.float32, device=x.device)
+        save_invstd = torch.empty(c, dtype=torch.float32, device=x.device)
+        with _on_device(x.device):
+            nbytes = L.slfp_bn_train_workspace_bytes(n, h, w, c)
+            ws = _workspace(x.device, nbytes)
+            _lib.check(L.slfp_bn_res_train_fwd(x.data_ptr(), res.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(running_mean),
+                                               _ptr(running_var), float(momentum), float(eps), 1 if relu else 0, y.data_ptr(),
+                                               save_mean.data_ptr(), save_invstd.data_ptr(), n, h, w, c, _lib.LAYOUT_NHWC,
+                                               ws.data_ptr(), nbytes, _stream_handle(x)))
+        ctx.relu = bool(relu)
+        if ctx.relu:
+            ctx.save_for_backward(x, weight, save_mean, save_invstd, y)
+        else:
+            ctx.save_for_backward(x, weight, save_mean, save_invstd)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        L = _lib.load()
+        x, weight, save_mean, save_invstd = ctx.saved_tensors[:4]
+        y = ctx.saved_tensors[4] if ctx.relu else x   # relu == 0: y is not read; any valid pointer stands in
+        n, c, h, w = x.shape
+        gy = _nhwc(gy)
+        gamma = _vec(weight)
+        gx = torch.empty_like(x)
+        gres = None
+        if ctx.needs_input_grad[1]:
+            gres = torch.empty_like(x) if ctx.relu else gy   # relu == 0: g is gy itself, no copy is asked of the kernel
+        ggamma = torch.empty_like(save_mean) if ctx.needs_input_grad[2] else None
+        gbeta = torch.empty_like(save_mean) if ctx.needs_input_grad[3] else None
+        with _on_device(x.device):
+            nbytes = L.slfp_bn_train_workspace_bytes(n, h, w, c)
+            ws = _workspace(x.device, nbytes)
+            _lib.check(L.slfp_bn_res_train_bwd(x.data_ptr(), y.data_ptr(), gy.data_ptr(), gamma.data_ptr(), save_mean.data_ptr(),
+                                               save_invstd.data_ptr(), 1 if ctx.relu else 0, gx.data_ptr(),
+                                               _ptr(gres) if ctx.relu else None, _ptr(ggamma), _ptr(gbeta), n, h, w, c,
+                                               _lib.LAYOUT_NHWC, ws.data_ptr(), nbytes, _stream_handle(x)))
+        return gx if ctx.needs_input_grad[0] else None, gres, ggamma, gbeta, None, None, None, None, None
+
+
 # ---- BatchNorm2d -> layerout_quantize_func -> activation (slfp_bn_lut_train_fwd / _bwd; DESIGN section 32) -------------------
 # The size rule of the table form, read from profiles/bn_layerout_train_bench.json with the spread rule of sections 12 and 27: a
 # size class is on the kernels by default only if forward + backward of the swapped block beat the stock modules by more than

@@ -35,6 +35,11 @@
 //   backward   the class is recomputed from x with the forward's own expression (save_lo is the forward's lo, handed over
 //              bit for bit);  g = gy * dact_table[class]  (the quantizer is a straight-through estimator);  the rest as above.
 // Each workgroup copies its table (19 712 B) into LDS once; a lookup is one ds_read_b32 at a random address.
+// The residual forms (k_bn_apply, k_bn_bwd_dx with RES = true, never with LUT; slfp_bn_res_train_fwd / _bwd) carry the tail of a
+// Bottleneck, out = bn3(out); out += identity; out = relu(out) (nets_imgnet/resnet50.py:85-90), in the same passes:
+//   forward    t = the apply above with relu = 0;  z = t + res;  relu: y = z < 0 ? 0 : z  (a NaN stays a NaN)
+//   backward   g as above, the mask read from y;  gx as above;  gres = g, a second store of the dx pass (skipped when NULL)
+// The statistics, both finalize kernels and the reduce pass are the plain ones.
 // The two finalize kernels stage the records of 256 slabs x 8 channels in LDS with all 256 lanes (and the per-slab weights
 // n_b / n and n_a n_b / n, which depend on the slab index alone), then one lane per channel runs the serial chain.
 #include "slfp_device.hpp"
@@ -108,6 +113,8 @@ struct BnArgs {
     float* gmean;          // workspace behind the records: backward [3][C] mb, mg, lo; forward [C] lo = f32(mean - save_mean)
     const float* lo_fwd;   // LUT backward: the forward's lo (save_lo)
     const float* table;    // LUT forms: act_table (forward) / dact_table (backward), kBnTableFloats floats
+    const float* res;      // residual forward: the operand added behind the affine map
+    float* gres;           // residual backward: the residual's gradient g, or null
     int64_t m, c, rows;
     int slabs, tx_log2, relu;
 };
@@ -283,8 +290,9 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_finalize(const BnArgs a, floa
     if (running_var) running_var[l.c] = (float)((1.0 - mo) * (double)running_var[l.c] + mo * (var * cnt / (cnt - 1.0)));
 }
 
-template <int V, bool LUT = false>
+template <int V, bool LUT = false, bool RES = false>
 __global__ __launch_bounds__(kBnThreads) void k_bn_apply(const BnArgs a) {
+    static_assert(!(LUT && RES), "the residual form has no table");
     const BnLane<V> l(a);
     const float* const sTab = bn_table_lds<LUT>(a.table);
     if (!l.live) return;
@@ -312,14 +320,43 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_apply(const BnArgs a) {
     };
     const int64_t st = l.nty;
     int64_t r = l.first;
-    for (; r + 3 * st < l.r1; r += 4 * st) {
-        Pack<V> v[4];
+    if constexpr (RES) {
+        const float* pr = a.res + l.ch;
+        auto fr = [&](Pack<V> v, const Pack<V>& q) {   // the add is rounded on its own, the ReLU comes behind it
 #pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = bn_ld<V>(px + (size_t)(r + i * st) * ld);
+            for (int e = 0; e < V; ++e) {
+                const float t = (((v.v[e] - mean.v[e]) - lo.v[e]) * sc.v[e]) + beta.v[e];
+                float z = t + q.v[e];
+                if (relu) z = z < 0.f ? 0.f : z;
+                v.v[e] = z;
+            }
+            return v;
+        };
+        for (; r + 3 * st < l.r1; r += 4 * st) {
+            Pack<V> v[4], q[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) bn_st<V>(py + (size_t)(r + i * st) * ld, f(v[i]));
+            for (int i = 0; i < 4; ++i) {
+                const size_t o = (size_t)(r + i * st) * ld;
+                v[i] = bn_ld<V>(px + o);
+                q[i] = bn_ld<V>(pr + o);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) bn_st<V>(py + (size_t)(r + i * st) * ld, fr(v[i], q[i]));
+        }
+        for (; r < l.r1; r += st) {
+            const size_t o = (size_t)r * ld;
+            bn_st<V>(py + o, fr(bn_ld<V>(px + o), bn_ld<V>(pr + o)));
+        }
+    } else {
+        for (; r + 3 * st < l.r1; r += 4 * st) {
+            Pack<V> v[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[i] = bn_ld<V>(px + (size_t)(r + i * st) * ld);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) bn_st<V>(py + (size_t)(r + i * st) * ld, f(v[i]));
+        }
+        for (; r < l.r1; r += st) bn_st<V>(py + (size_t)r * ld, f(bn_ld<V>(px + (size_t)r * ld)));
     }
-    for (; r < l.r1; r += st) bn_st<V>(py + (size_t)r * ld, f(bn_ld<V>(px + (size_t)r * ld)));
 }
 
 // g of one element: the ReLU's mask is read from the forward's own output
@@ -423,8 +460,9 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_bwd_finalize(const BnArgs a, 
     a.gmean[2 * (size_t)a.c + (size_t)l.c] = (float)lo;
 }
 
-template <int V, bool LUT = false>
+template <int V, bool LUT = false, bool RES = false>
 __global__ __launch_bounds__(kBnThreads) void k_bn_bwd_dx(const BnArgs a) {
+    static_assert(!(LUT && RES), "the residual form has no table");
     const BnLane<V> l(a);
     const float* const sTab = bn_table_lds<LUT>(a.table);
     if (!l.live) return;
@@ -458,6 +496,39 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_bwd_dx(const BnArgs a) {
     };
     const int64_t st = l.nty;
     int64_t r = l.first;
+    if constexpr (RES) {
+        float* pq = a.gres ? a.gres + l.ch : nullptr;   // the residual's gradient: g itself, stored where gx is
+        auto gq = [&](const Pack<V>& gy, const Pack<V>& y) {
+            Pack<V> o;
+#pragma unroll
+            for (int e = 0; e < V; ++e) o.v[e] = bn_g(gy.v[e], y.v[e], relu);
+            return o;
+        };
+        for (; r + 3 * st < l.r1; r += 4 * st) {
+            Pack<V> x[4], g[4], y[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const size_t o = (size_t)(r + i * st) * ld;
+                x[i] = bn_ld<V>(px + o);
+                g[i] = bn_ld<V>(pg + o);
+                y[i] = relu ? bn_ld<V>(py + o) : g[i];
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const size_t o = (size_t)(r + i * st) * ld;
+                bn_st<V>(po + o, f(x[i], g[i], y[i]));
+                if (pq) bn_st<V>(pq + o, gq(g[i], y[i]));
+            }
+        }
+        for (; r < l.r1; r += st) {
+            const size_t o = (size_t)r * ld;
+            const Pack<V> g = bn_ld<V>(pg + o);
+            const Pack<V> y = relu ? bn_ld<V>(py + o) : g;
+            bn_st<V>(po + o, f(bn_ld<V>(px + o), g, y));
+            if (pq) bn_st<V>(pq + o, gq(g, y));
+        }
+        return;
+    }
     for (; r + 3 * st < l.r1; r += 4 * st) {
         Pack<V> x[4], g[4], y[4];
 #pragma unroll
@@ -599,6 +670,69 @@ int slfp_bn_train_bwd(const float* x, const float* y, const float* gy, const flo
     if (e != SLFP_OK) return e;
     hipLaunchKernelGGL(s.vec == 4 ? k_bn_bwd_dx<4> : k_bn_bwd_dx<1>, grid, block, 0, st, a);
     return check_launch("slfp batch-norm backward dx kernel");
+}
+
+int slfp_bn_res_train_fwd(const float* x, const float* res, const float* gamma, const float* beta, float* running_mean,
+                          float* running_var, float momentum, float eps, int relu, float* y, float* save_mean, float* save_invstd,
+                          int64_t n, int64_t h, int64_t w, int64_t c, int x_layout, void* workspace, size_t ws_bytes, void* stream) {
+    const char* fn = "slfp_bn_res_train_fwd";
+    const void* big[] = {x, res, y};
+    const void* small[] = {gamma, beta, save_mean, save_invstd};
+    int64_t m = 0;
+    const int rc = bn_check(fn, n, h, w, c, x_layout, relu, big, 3, small, 4, workspace, ws_bytes, &m);
+    if (rc != SLFP_OK) return rc;
+    if ((running_mean == nullptr) != (running_var == nullptr))
+        return fail(SLFP_ERR_BAD_ARG, "%s: running_mean and running_var are given together or not at all", fn);
+    if ((reinterpret_cast<uintptr_t>(running_mean) | reinterpret_cast<uintptr_t>(running_var)) & 3)
+        return fail(SLFP_ERR_ALIGNMENT, "%s: the running statistics must be 4-byte aligned", fn);
+    if (y == x || y == res) return fail(SLFP_ERR_BAD_ARG, "%s: y may alias neither x nor res (the backward reads x and y)", fn);
+    if (m == 0) return SLFP_OK;
+    const BnSplit s = bn_split(m, c);
+    BnArgs a = bn_args(s, m, c, relu, workspace);
+    a.x = x; a.res = res; a.out = y; a.gamma = gamma; a.beta = beta; a.mean = save_mean; a.invstd = save_invstd;
+    const dim3 grid((unsigned)s.slabs, (unsigned)s.tiles), block(kBnThreads);
+    const hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(s.vec == 4 ? k_bn_stats<4> : k_bn_stats<1>, grid, block, 0, st, a);
+    int e = check_launch("slfp batch-norm statistics kernel");
+    if (e != SLFP_OK) return e;
+    hipLaunchKernelGGL(k_bn_finalize, dim3((unsigned)ceil_div(c, kBnFinCh)), block, 0, st, a, running_mean, running_var, momentum,
+                       eps, save_mean, save_invstd);
+    e = check_launch("slfp batch-norm finalize kernel");
+    if (e != SLFP_OK) return e;
+    hipLaunchKernelGGL((s.vec == 4 ? k_bn_apply<4, false, true> : k_bn_apply<1, false, true>), grid, block, 0, st, a);
+    return check_launch("slfp batch-norm residual apply kernel");
+}
+
+int slfp_bn_res_train_bwd(const float* x, const float* y, const float* gy, const float* gamma, const float* save_mean,
+                          const float* save_invstd, int relu, float* gx, float* gres, float* ggamma, float* gbeta, int64_t n,
+                          int64_t h, int64_t w, int64_t c, int x_layout, void* workspace, size_t ws_bytes, void* stream) {
+    const char* fn = "slfp_bn_res_train_bwd";
+    const void* big[] = {x, y, gy, gx};
+    const void* small[] = {gamma, save_mean, save_invstd};
+    int64_t m = 0;
+    const int rc = bn_check(fn, n, h, w, c, x_layout, relu, big, 4, small, 3, workspace, ws_bytes, &m);
+    if (rc != SLFP_OK) return rc;
+    if (reinterpret_cast<uintptr_t>(gres) & (c % 4 == 0 ? 15 : 3))
+        return fail(SLFP_ERR_ALIGNMENT, "%s: gres must be %d-byte aligned", fn, c % 4 == 0 ? 16 : 4);
+    if ((reinterpret_cast<uintptr_t>(ggamma) | reinterpret_cast<uintptr_t>(gbeta)) & 3)
+        return fail(SLFP_ERR_ALIGNMENT, "%s: ggamma and gbeta must be 4-byte aligned", fn);
+    if (gx == x || gx == y || gx == gy) return fail(SLFP_ERR_BAD_ARG, "%s: gx may not alias x, y or gy", fn);
+    if (gres && (gres == x || gres == y || gres == gy || gres == gx))
+        return fail(SLFP_ERR_BAD_ARG, "%s: gres may not alias x, y, gy or gx", fn);
+    if (m == 0) return SLFP_OK;
+    const BnSplit s = bn_split(m, c);
+    BnArgs a = bn_args(s, m, c, relu, workspace);
+    a.x = x; a.y = y; a.gy = gy; a.out = gx; a.gres = gres; a.gamma = gamma; a.mean = save_mean; a.invstd = save_invstd;
+    const dim3 grid((unsigned)s.slabs, (unsigned)s.tiles), block(kBnThreads);
+    const hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(s.vec == 4 ? k_bn_bwd_reduce<4> : k_bn_bwd_reduce<1>, grid, block, 0, st, a);
+    int e = check_launch("slfp batch-norm backward reduce kernel");
+    if (e != SLFP_OK) return e;
+    hipLaunchKernelGGL(k_bn_bwd_finalize, dim3((unsigned)ceil_div(c, kBnFinCh)), block, 0, st, a, ggamma, gbeta);
+    e = check_launch("slfp batch-norm backward finalize kernel");
+    if (e != SLFP_OK) return e;
+    hipLaunchKernelGGL((s.vec == 4 ? k_bn_bwd_dx<4, false, true> : k_bn_bwd_dx<1, false, true>), grid, block, 0, st, a);
+    return check_launch("slfp batch-norm residual backward dx kernel");
 }
 
 int slfp_bn_lut_train_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,

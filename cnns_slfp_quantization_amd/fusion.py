@@ -1926,7 +1926,10 @@ class TrainBatchNorm2d(nn.Module):
     F.batch_norm with the same buffers (then relu, if folded), which is what the stock modules compute.  The output is saved
     for the backward only with a folded ReLU; without one it may be changed in place behind the module (`out += identity`, a
     shared in-place ReLU), as behind the stock module.
-      _last_kernel   "bn_train[+relu]", or "aten" """
+    A block's forward may ask more of one call (use_device_bottleneck_train): forward(x, relu=True) applies a ReLU the module does
+    not own, forward(x, residual=identity, relu=True) the tail of a Bottleneck on slfp_bn_res_train_fwd / _bwd (DESIGN section 33);
+    where the kernels do not run, that call computes F.batch_norm, `+= residual`, relu with ATen as the stock block does.
+      _last_kernel   "bn_train[+relu]", "bn_res_train[+relu]", or "aten" """
     _version = 2   # nn.BatchNorm2d's state-dict version (num_batches_tracked)
 
     def __init__(self, bn, min_elements=None):
@@ -1946,24 +1949,43 @@ class TrainBatchNorm2d(nn.Module):
     def extra_repr(self):
         return f"{self.num_features}, eps={self.eps}, momentum={self.momentum}, relu={self._relu}"
 
-    def forward(self, x):
-        from .batchnorm import hip_bn_train, bn_train_supported
+    def forward(self, x, *, relu=None, residual=None):
+        """relu: None -- the module's own folded ReLU (`_relu`); True / False -- what a block's forward asks of this call
+        (use_device_bottleneck_train).  residual: a tensor of x's shape added behind the affine map and in front of the ReLU, the
+        `out += identity` of a Bottleneck; on the kernels it is slfp_bn_res_train_fwd / _bwd, under a size
+        rule of its own (batchnorm.RES_MIN_ELEMENTS where min_elements is None)."""
+        from .batchnorm import hip_bn_train, hip_bn_res_train, bn_train_supported, RES_MIN_ELEMENTS
         if x.dim() != 4:
             raise ValueError(f"expected 4D input (got {x.dim()}D input)")
+        relu = self._relu if relu is None else bool(relu)
         if self.training and self.track_running_stats and self.num_batches_tracked is not None:
             self.num_batches_tracked.add_(1)
-        if (self.training and self.running_mean is not None and self.running_var is not None and x.is_cuda
+        floor = self.min_elements
+        if residual is not None:
+            if floor is None:
+                floor = RES_MIN_ELEMENTS
+            on_kernels = (torch.is_tensor(residual) and residual.shape == x.shape and residual.dtype == x.dtype
+                          and residual.device == x.device)
+        else:
+            on_kernels = True
+        if (on_kernels and self.training and self.running_mean is not None and self.running_var is not None and x.is_cuda
                 and x.dtype == torch.float32 and self.weight.dtype == torch.float32 and not torch.is_autocast_enabled()
-                and bn_train_supported(x, self.min_elements)):
-            self._last_kernel = "bn_train+relu" if self._relu else "bn_train"
+                and bn_train_supported(x, floor)):
+            if residual is not None:
+                self._last_kernel = "bn_res_train+relu" if relu else "bn_res_train"
+                return hip_bn_res_train.apply(x, residual, self.weight, self.bias, self.running_mean, self.running_var,
+                                              self.momentum, self.eps, relu)
+            self._last_kernel = "bn_train+relu" if relu else "bn_train"
             return hip_bn_train.apply(x, self.weight, self.bias, self.running_mean, self.running_var, self.momentum, self.eps,
-                                      self._relu)
+                                      relu)
         self._last_kernel = "aten"
         stats = self.training or (self.running_mean is None and self.running_var is None)
         keep = not self.training or self.track_running_stats
         y = torch.nn.functional.batch_norm(x, self.running_mean if keep else None, self.running_var if keep else None, self.weight,
                                            self.bias, stats, self.momentum, self.eps)
-        return torch.relu(y) if self._relu else y
+        if residual is not None:
+            y += residual   # the stock block's own statements: out = bn3(out); out += identity; out = relu(out)
+        return torch.relu(y) if relu else y
 
 
 def _bn_train_candidate(m):
@@ -2004,7 +2026,10 @@ def use_device_bn_train(model, min_elements=None):
 
 def restore_bn_train(model):
     """Undo use_device_bn_train: every slot gets its original module back; the originals are pointed at the current parameters
-    and buffers (the model may have been moved or cast in between) and take the wrapper's training flag."""
+    and buffers (the model may have been moved or cast in between) and take the wrapper's training flag.  Blocks rewritten by
+    use_device_bottleneck_train are restored first (restore_bottleneck_train): their instance-level forward calls bn1..3 with
+    keywords a stock BatchNorm does not take."""
+    restore_bottleneck_train(model)
     n = 0
     seen = set()
     for parent in list(model.modules()):
@@ -2022,6 +2047,126 @@ def restore_bn_train(model):
                 parent._modules[name] = bn
             elif isinstance(child, FoldedReLU) and getattr(child, "_bn_train", False):
                 parent._modules[name] = child.relu
+    return n
+
+
+# ------------------------------------------------------------------ training-mode Bottleneck tails: BN + ReLU, BN + add + ReLU
+_BN_BOTTLENECK_BNS = ("bn1", "bn2", "bn3")
+
+
+def _bn_bottleneck_forward(self, x):
+    """The dataflow of the Bottleneck the reference copies (nets_imgnet/resnet50.py:71-90) with each ReLU, and the add in front of
+    the last one, handed to the TrainBatchNorm2d in front of it."""
+    out = self.bn1(self.conv1(x), relu=True)
+    out = self.bn2(self.conv2(out), relu=True)
+    identity = x if getattr(self, "downsample", None) is None else self.downsample(x)
+    return self.bn3(self.conv3(out), residual=identity, relu=True)
+
+
+def _bn_wrappable(m):
+    """A BatchNorm a later pass may take: the stock module use_device_bn_train takes, or its wrapper without a folded ReLU."""
+    return _bn_train_candidate(m) or (isinstance(m, TrainBatchNorm2d) and not m._relu)
+
+
+def _bn_bottleneck_candidate(blk):
+    if isinstance(blk, nn.Sequential) or "forward" in blk.__dict__:
+        return False
+    ch = blk._modules
+    if any(ch.get(k) is None for k in _BOTTLENECK_CHILDREN + ("bn3",)) or "downsample" not in ch and not hasattr(blk, "downsample"):
+        return False
+    return type(ch["relu"]) is nn.ReLU and all(_bn_wrappable(ch[k]) for k in _BN_BOTTLENECK_BNS)
+
+
+def _repoint_bn(wrap):
+    """The stock module of a TrainBatchNorm2d, pointed at the wrapper's current parameters, buffers and training flag."""
+    bn = wrap._bn
+    for key in ("weight", "bias"):
+        bn._parameters[key] = wrap._parameters[key]
+    for key in _BN_NAMES:
+        bn._buffers[key] = wrap._buffers[key]
+    bn.training = wrap.training
+    return bn
+
+
+def _restore_bn_bottleneck(blk):
+    """Take the instance-level forward off `blk` and put back the stock module wherever this pass created the wrapper."""
+    created = blk.__dict__.pop("_bn_bottleneck")
+    del blk.__dict__["forward"]
+    for name, wrap in created.items():
+        if blk._modules.get(name) is wrap:
+            blk._modules[name] = _repoint_bn(wrap)
+
+
+def use_device_bottleneck_train(model, example_input, min_elements=None):
+    """Run the three tails of every training-mode Bottleneck of `model` on libslfp_hip's kernels: relu(bn1(.)) and relu(bn2(.)) as
+    slfp_bn_train_fwd / _bwd with the ReLU folded, and out = bn3(out); out += identity; out = relu(out) as slfp_bn_res_train_fwd /
+    _bwd.  A candidate is a non-Sequential module without an instance-level forward that has the children
+    conv1 / bn1 / conv2 / bn2 / conv3 / bn3 / relu and a `downsample` attribute (None allowed), bn1..3 each an affine
+    nn.BatchNorm2d with a momentum held in that one slot, or a TrainBatchNorm2d without a folded ReLU, and relu a plain nn.ReLU;
+    the convolutions may be any module and are not touched.  It gets TrainBatchNorm2d wrappers in the three slots (wrappers that
+    are there already are reused) and an instance-level forward with the block's dataflow.  A name is only a convention, so -- the
+    rule of fuse_residual -- the pass verifies: it puts the model in eval mode (there every BatchNorm is F.batch_norm with the
+    running statistics and nothing is updated, so the rewritten dataflow must equal the stock one exactly), traces one no_grad
+    forward on `example_input`, and each rewritten block must reproduce its recorded output bit for bit on its recorded input
+    (otherwise it is restored and not counted); then the rewritten model must reproduce the recorded output bit for bit
+    (otherwise everything is restored and 0 is returned).  The training flags are put back in every case.  Parameters, buffers
+    and state-dict keys do not change.  Composes with use_device_bn_train in either order (a BatchNorm inside `downsample` is that
+    pass's).  Tensors of fewer than `min_elements` elements run what the stock block runs (None: batchnorm.MIN_ELEMENTS for
+    bn1 / bn2, batchnorm.RES_MIN_ELEMENTS for bn3; 0: every size).  Returns the number of blocks rewritten;
+    restore_bottleneck_train undoes them."""
+    import types
+    cands = [m for m in model.modules() if _bn_bottleneck_candidate(m)
+             and all(isinstance(m._modules[k], TrainBatchNorm2d) or len(_slots_of(model, m._modules[k])) == 1
+                     for k in _BN_BOTTLENECK_BNS)]
+    if not cands:
+        return 0
+    flags = [(m, m.training) for m in model.modules()]
+    made = []
+    model.eval()
+    try:
+        tr = _Trace(model, example_input, blocks=cands)
+        y0 = tr.output
+        done = []
+        for blk in cands:
+            io = tr.io(blk)
+            if io is None:
+                continue   # not run, run twice, or not a tensor -> tensor block
+            x, want = io
+            created = {}
+            for name in _BN_BOTTLENECK_BNS:
+                bn = blk._modules[name]
+                if not isinstance(bn, TrainBatchNorm2d):
+                    created[name] = blk._modules[name] = TrainBatchNorm2d(bn, min_elements)
+            made += created.values()
+            blk.__dict__["_bn_bottleneck"] = created
+            blk.__dict__["forward"] = types.MethodType(_bn_bottleneck_forward, blk)
+            if _verified(lambda: blk(x), want, lambda: _restore_bn_bottleneck(blk)):
+                done.append(blk)
+        tr.release()
+        if not done:
+            return 0
+
+        def undo():
+            for blk in done:
+                _restore_bn_bottleneck(blk)
+
+        return len(done) if _verified(lambda: model(example_input), y0, undo) else 0
+    finally:
+        for m, t in flags:
+            m.training = t
+        for wrap in made:   # created in eval mode: the stock module's flag is the slot's
+            wrap.training = wrap._bn.training
+
+
+def restore_bottleneck_train(model):
+    """Undo use_device_bottleneck_train: the blocks lose their instance-level forward and exactly the wrappers that pass created
+    give their slots back to the stock modules (pointed at the current parameters and buffers); wrappers that were there before
+    it stay.  Returns the number of blocks restored."""
+    n = 0
+    for blk in list(model.modules()):
+        if "_bn_bottleneck" in blk.__dict__:
+            _restore_bn_bottleneck(blk)
+            n += 1
     return n
 
 
@@ -2129,7 +2274,7 @@ class TrainBatchNormLayerout2d(nn.Module):
 
 
 def _bn_lut_candidate(m):
-    return _bn_train_candidate(m) or (isinstance(m, TrainBatchNorm2d) and not m._relu)
+    return _bn_wrappable(m)
 
 
 def use_device_bn_layerout_train(model, min_elements=None):

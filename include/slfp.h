@@ -647,6 +647,38 @@ int slfp_bn_lut_train_bwd(const float* x, const float* gy, const float* gamma, c
                           float* ggamma, float* gbeta, int64_t n, int64_t h, int64_t w, int64_t c, int x_layout,
                           void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- training-mode BatchNorm2d -> residual add -> ReLU (csrc/bn_train.hip, the residual forms) -----------------------------
+ * The tail of a Bottleneck, out = bn3(out); out += identity; out = relu(out) (nets_imgnet/resnet50.py:85-90), in training mode,
+ * in the two passes slfp_bn_train_fwd / _bwd already make over the tensor.  res: the identity, float32 [M][c] like x.  The
+ * contract is exact:
+ *   statistics save_mean, save_invstd and the running statistics are exactly those of slfp_bn_train_fwd on the same x: the same
+ *              split, the same sums, the same finalize.
+ *   forward    t = (((x - save_mean) - lo) * (save_invstd * gamma)) + beta, the apply above with relu = 0;  z = t + res, one
+ *              float32 add rounded on its own;  relu: y = z < 0 ? 0 : z  (a NaN stays a NaN);  otherwise y = z.  So y is
+ *              bit-identical to slfp_bn_train_fwd(relu = 0), then a float32 add of res, then where(z < 0, 0, z).  The apply pass
+ *              reads x and res once and writes y once.
+ *   backward   g = relu ? (y > 0 ? gy : 0) : gy  with y the forward's own output (behind the add and the ReLU).  gx, ggamma
+ *              and gbeta are bit-identical to slfp_bn_train_bwd(relu) given the same x, y, gy.  gres = g, the residual's
+ *              gradient, is a second store of the dx pass; gres == NULL: not needed, the store is skipped and nothing else
+ *              changes.  ggamma and gbeta may be NULL.  The reduce pass reads x, gy and (relu) y; the dx pass reads the same
+ *              and writes gx and gres.
+ * No atomics; two calls give the same bits; a NaN or an inf in res stays in its own element of y.  Both take the supported set
+ * of slfp_bn_train_supported and the workspace of slfp_bn_train_workspace_bytes (no more), and make the refusals of
+ * slfp_bn_train_fwd / slfp_bn_train_bwd in the same order before any device work; res counts among the big arrays (NULL:
+ * SLFP_ERR_BAD_ARG; not aligned to 16 bytes (c % 4 == 0) or 4 bytes: SLFP_ERR_ALIGNMENT), a misaligned gres is
+ * SLFP_ERR_ALIGNMENT (behind the workspace check, with ggamma / gbeta).  y may alias neither x nor res; gx and gres may alias
+ * neither each other nor x, y or gy.  n == 0 returns SLFP_OK. */
+int slfp_bn_res_train_fwd(const float* x, const float* res, const float* gamma, const float* beta,
+                          float* running_mean, float* running_var, float momentum, float eps, int relu,
+                          float* y, float* save_mean, float* save_invstd,
+                          int64_t n, int64_t h, int64_t w, int64_t c, int x_layout,
+                          void* workspace, size_t ws_bytes, void* stream);
+int slfp_bn_res_train_bwd(const float* x, const float* y, const float* gy, const float* gamma,
+                          const float* save_mean, const float* save_invstd, int relu,
+                          float* gx, float* gres, float* ggamma, float* gbeta,
+                          int64_t n, int64_t h, int64_t w, int64_t c, int x_layout,
+                          void* workspace, size_t ws_bytes, void* stream);
+
 /* ---- self-check ------------------------------------------------------------------------
  * The kernels compute x / scale_div with an FMA correction chain on a host-computed
  * reciprocal instead of the IEEE division macro (csrc/slfp_device.hpp, ScaleDiv).  This
