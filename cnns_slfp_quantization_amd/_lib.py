@@ -47,6 +47,7 @@ SYMBOLS = (
     "slfp_conv2d_u8_supported", "slfp_conv2d_fwd_u8", "slfp_debug_stem_u8_instance", "slfp_image_u8_expand_f32",
     "slfp_bn_lut_train_fwd", "slfp_bn_lut_train_bwd",
     "slfp_bn_res_train_fwd", "slfp_bn_res_train_bwd",
+    "slfp_conv2d_codes_x3_supported", "slfp_conv2d_fwd_codes_x3", "slfp_debug_pwc_x3_variant",
 )
 
 
@@ -189,6 +190,9 @@ def load():
         "slfp_conv2d_fwd_u8": (ci, [dp, ctypes.POINTER(ConvIo), vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]),
         "slfp_debug_stem_u8_instance": (ctypes.c_char_p, [dp, ctypes.POINTER(ConvIo), ci, ci, ci]),
         "slfp_image_u8_expand_f32": (ci, [vp, vp, vp, i64, ci, vp]),
+        "slfp_conv2d_codes_x3_supported": (ci, [dp, ctypes.POINTER(ConvIo), ci, ci]),
+        "slfp_conv2d_fwd_codes_x3": (ci, [dp, ctypes.POINTER(ConvIo), vp, vp, vp, vp, vp, ci, vp, vp]),
+        "slfp_debug_pwc_x3_variant": (ctypes.c_char_p, [dp, ctypes.POINTER(ConvIo)]),
     }
     assert set(sigs) == set(SYMBOLS)
     for name, (res, args) in sigs.items():

@@ -238,6 +238,9 @@ _KINDS = {
     "codes_lo": ("slfp_conv2d_codes_supported", "slfp_conv2d_fwd_codes_ws"),
     # uint8 pixels + the module's pixel table in (fusion.link_image_u8), float32 or codes out
     "u8": ("slfp_conv2d_u8_supported", "slfp_conv2d_fwd_u8"),
+    # codes in, float32 or codes out, for a 1x1 layer in the float32-equivalent mode (options.mfma_passes = 3), which "codes" refuses;
+    # tried only on a module fusion.link_codes(x3=True) marked (`_code_x3`)
+    "codes_x3": ("slfp_conv2d_codes_x3_supported", "slfp_conv2d_fwd_codes_x3"),
 }
 
 
@@ -304,11 +307,11 @@ def _plan(mod, x, weight, nhwc_in, nhwc_out, codes=None):
                 plan.ok = bool(flags & 2) and mod._post[0] is not None and _supported(mod, shape, kind, x_codes, out, flags, desc=d, io=plan.io)
             else:
                 plan.ok = _supported(mod, shape, kind, x_codes, out, flags, extra, d, plan.io)
-            if kind == "entry" or (kind == "codes" and not plan.ok):
+            if kind in ("entry", "codes_x3") or (kind == "codes" and not plan.ok):
                 plan.ws_bytes = 0   # pointwise: no workspace; refused: the float32 interface's own plan sizes its workspace
             plan.label += (("+codes_in" if x_codes else "") + ("+codes_out" if out is not None and kind != "res_codes" else "")
                            + {"slice": "+slice", "res": "+res", "res_codes": "+res+trunk_codes", "lut": "+lut", "codes_lo": "+layerout_pass",
-                              "u8": "+u8"}.get(kind, ""))
+                              "u8": "+u8", "codes_x3": "+x3"}.get(kind, ""))
             if kind == "u8" and plan.ok:   # what the launch consumes, from the library's own selection
                 inst = L.slfp_debug_stem_u8_instance(ctypes.byref(d), ctypes.byref(plan.io), 1 if mod.bias is not None else 0, flags,
                                                      1 if mod._post is not None and mod._post[0] is not None else 0).decode()
@@ -397,8 +400,8 @@ def _launch(mod, plan, x, weight, bias, y=None, cache=True, res=None, relu=None,
             args = (ctypes.byref(d), ctypes.byref(plan.io), x.data_ptr(), mod._image_table.data_ptr()) + head[1:] + (flags, y.data_ptr(), _ptr(ws))
         elif kind == "lut":   # no flags: the ReLU bit is part of the table
             args = (ctypes.byref(d), ctypes.byref(plan.io)) + head + (mod._code_lut.data_ptr(), y.data_ptr(), int(d.c_out), _ptr(ws))
-        else:   # "codes" takes a workspace, "entry" does not
-            args = (ctypes.byref(d), ctypes.byref(plan.io)) + head + (flags, y.data_ptr()) + ((_ptr(ws),) if kind != "entry" else ())
+        else:   # "codes" takes a workspace, "entry" and "codes_x3" do not
+            args = (ctypes.byref(d), ctypes.byref(plan.io)) + head + (flags, y.data_ptr()) + ((_ptr(ws),) if kind not in ("entry", "codes_x3") else ())
         _lib.check(getattr(_lib.load(), _KINDS[kind][1])(*args, stream.cuda_stream))
         if kind == "codes_lo":
             t, y = y, torch.empty_like(y)
@@ -438,7 +441,9 @@ def _hip_conv2d_codes(mod, x, weight, bias):
     or float32.  One slfp_conv2d_fwd_codes call where libslfp_hip has a kernel for the combination; otherwise the same
     values through the float32 interface plus slfp_encode_f32 / slfp_decode_f32 (always correct, never faster).  A module with
     `_code_entry` set that reads float32 and writes codes asks slfp_conv2d_entry_supported first and, where that says yes, runs
-    ONE slfp_conv2d_fwd_entry call (the 1x1 layer at which a chain of codes begins)."""
+    ONE slfp_conv2d_fwd_entry call (the 1x1 layer at which a chain of codes begins).  A module marked `_code_x3` that reads codes and
+    is refused by slfp_conv2d_fwd_codes (a 1x1 layer under options.mfma_passes = 3) asks slfp_conv2d_codes_x3_supported next and runs
+    ONE slfp_conv2d_fwd_codes_x3 call."""
     x_codes = x.dtype == torch.uint8
     out = mod._code_out
     if not x_codes:
@@ -466,6 +471,10 @@ def _hip_conv2d_codes(mod, x, weight, bias):
         plan = _plan(mod, x, weight, True, True, ("codes", x_codes, out, None))
         if plan.ok:
             return _launch(mod, plan, x, weight, bias)
+        if x_codes and mod._code_x3:
+            plan = _plan(mod, x, weight, True, True, ("codes_x3", True, out, None))
+            if plan.ok:
+                return _launch(mod, plan, x, weight, bias)
         if x_codes and out is None and mod._post is not None and int(mod._post[2]) == 2:
             plan = _plan(mod, x, weight, True, True, ("codes_lo", True, None, None))
             if plan.ok:
@@ -730,6 +739,7 @@ def _conv_class(q_bit, Kw, Ka, bias_default, scaled_bias):
             self._post = None  # (scale, shift, relu): fused eval-BN + ReLU epilogue (fusion.fuse_bn_relu)
             self._code_out = None   # (Ka, q_bit) of the next Conv2d_Q: hand it 1-byte codes (fusion.link_codes)
             self._code_entry = False   # with _code_out on a float32 input: ONE slfp_conv2d_fwd_entry launch where the library has it
+            self._code_x3 = False   # on a code input that "codes" refuses: slfp_conv2d_fwd_codes_x3 (fusion.link_codes(x3=True))
             # with _code_out behind a layer-output epilogue: the uint8 table of SLFP_LAYEROUT_LUT_BYTES entries that maps a
             # layer-output class to the reader's code (fusion.link_layerout); slfp_conv2d_fwd_codes_lut then runs.  A buffer, so
             # that it follows the module across devices; not persistent: the state dict keeps the reference's keys

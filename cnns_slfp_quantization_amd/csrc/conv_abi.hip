@@ -449,6 +449,16 @@ static CodeRoute lut_route(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, 
     }
 }
 
+// Pointwise on codes in the float32-equivalent (three-pass) mode (slfp_conv2d_fwd_codes_x3): SLFP<3,4> codes in, float32 or codes out.
+// A query and an entry point of their own: the older queries keep answering 0 for three-pass descriptors with codes on either side
+// of a 1x1 layer, so every link count that rests on them stays.
+static bool x3_route(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int relu, const ConvPlan& p) {
+    if (io->x_codes != 1 || (io->y_codes != 0 && io->y_codes != 1) || !code_path_ok(d, relu)) return false;
+    if (d->qbits != 8 || d->mfma_passes != SLFP_MFMA_F16X3 || d->groups != 1) return false;
+    if (io->y_codes && (!consumer_quant_ok(io) || !enc_table(io->y_ka, y_fmt_of(io->y_qbits), kEncCode)->valid)) return false;
+    return pwc_x3_applicable(*d, p, relu, io->y_codes != 0);
+}
+
 // slfp_debug_pw_variant: the route the matching forward entry point takes (refused: "none"), then the launcher's own selection.
 static const char* pw_variant(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, bool has_res, bool has_res_codes, int64_t y_ld) {
     ConvPlan p;
@@ -569,7 +579,7 @@ struct FwdArgs {   // what a forward entry point was handed; io / res / y_ld / w
     void* y_codes = nullptr;   // slfp_conv2d_fwd_res_codes: the second, uint8 output
     const uint8_t* lut = nullptr;   // slfp_conv2d_fwd_codes_lut: the byte table of the layer-output classes
 };
-enum FwdKind { kFwdPost, kFwdCodes, kFwdSlice, kFwdEntry, kFwdRes, kFwdResCodes, kFwdLut };
+enum FwdKind { kFwdPost, kFwdCodes, kFwdSlice, kFwdEntry, kFwdRes, kFwdResCodes, kFwdLut, kFwdCodesX3 };
 struct Resolved { ConvPlan p; PostOp post; CodeIo cio; CodeRoute route; };
 
 static int need_workspace(const char* fn, const FwdArgs& a, const ConvPlan& p) {
@@ -644,6 +654,12 @@ static int resolve(FwdKind kind, const char* fn, const FwdArgs& a, Resolved* r) 
         if (!entry_route(d, io, a.relu, r->p))
             return fail(SLFP_ERR_UNSUPPORTED, "%s: this layer / io combination has no float32 -> codes kernel "
                                               "(slfp_conv2d_entry_supported); use slfp_conv2d_fwd_post and slfp_encode_f32", fn);
+        return SLFP_OK;
+    }
+    if (kind == kFwdCodesX3) {
+        if (!x3_route(d, io, a.relu, r->p))
+            return fail(SLFP_ERR_UNSUPPORTED, "%s: this layer / io combination has no three-pass pointwise kernel on codes "
+                                              "(slfp_conv2d_codes_x3_supported); use slfp_conv2d_fwd_post", fn);
         return SLFP_OK;
     }
     if (with_res) {   // res is read while y is written, in a different order by different workgroups: the two must not overlap
@@ -830,6 +846,26 @@ int slfp_conv2d_res_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* i
 int slfp_conv2d_res_codes_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int relu) {
     ConvPlan p;
     return d && io && make_plan(d, &p) == SLFP_OK && res_codes_route(d, io, has_bias != 0, relu, p);
+}
+
+int slfp_conv2d_codes_x3_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int relu) {
+    (void)has_bias;   // both kernels take a bias
+    ConvPlan p;
+    return d && io && make_plan(d, &p) == SLFP_OK && x3_route(d, io, relu, p);
+}
+
+int slfp_conv2d_fwd_codes_x3(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
+                             const float* bias, const float* post_scale, const float* post_shift, int relu, void* y, void* stream) {
+    const FwdArgs a{d, io, x, wprep, bias, post_scale, post_shift, relu, y, nullptr, 0, nullptr};
+    Resolved r;
+    const int rc = resolve(kFwdCodesX3, "slfp_conv2d_fwd_codes_x3", a, &r);
+    return rc != SLFP_OK ? rc : launch_pwc_x3(*d, r.p, reinterpret_cast<const uint8_t*>(x), wprep, bias, r.post, y, r.cio, as_stream(stream));
+}
+
+const char* slfp_debug_pwc_x3_variant(const slfp_conv2d_desc* d, const slfp_conv2d_io* io) {
+    ConvPlan p;
+    if (!d || !io || make_plan(d, &p) != SLFP_OK || !x3_route(d, io, 0, p)) return "none";
+    return pwc_x3_variant_name(*d, p, io->y_codes != 0);
 }
 
 int slfp_conv2d_fwd_codes(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,

@@ -24,6 +24,8 @@
 // ResNet block that reads conv2's codes and adds the float32 trunk, as in conv_pw.hip.
 // The residual forms have a DUAL form each (slfp_conv2d_fwd_res_codes): the float32 trunk is stored as before and the value is also
 // coded for the NEXT block's quantizer into a second, uint8 tensor, so the next conv1 / downsample.0 never read the float32 trunk.
+// k_pwc_stream and k_pwc_tiled also have a float32-equivalent form (PASSES = 3; slfp_conv2d_fwd_codes_x3, launch_pwc_x3): hi + lo
+// planes on both operands, three MFMAs per k-step in the order of conv_pw.hip's three-pass kernels, bit-identical to those.
 #include "slfp_device.hpp"
 #include "slfp_enc.hpp"
 #include "slfp_codes.hpp"
@@ -36,6 +38,7 @@ namespace slfp {
 struct PwcParams {
     const uint8_t* x;
     const _Float16* whi;
+    const _Float16* wlo;  // PASSES == 3: the residual plane of the same blob (n_tiles * KS * 512 halves after whi); nullptr otherwise
     const float* bias;
     void* y;
     const float* res;     // RES kernels (float32 out): the residual operand, NHWC like y; nullptr otherwise
@@ -67,6 +70,15 @@ __device__ __forceinline__ half8 dec_frag(uint32_t ca, uint32_t cb, const unsign
     return __builtin_bit_cast(half8, u32x4{pa.x, pa.y, pb.x, pb.y});
 }
 
+// float32-equivalent mode (kDecF16HL table): both planes of the same fragment
+__device__ __forceinline__ void dec_frag_hl(uint32_t ca, uint32_t cb, const unsigned char* dtab, half8& xh, half8& xl) {
+    uint2 ha, la, hb, lb;
+    dec4_f16hl(ca, dtab, ha, la);
+    dec4_f16hl(cb, dtab, hb, lb);
+    xh = __builtin_bit_cast(half8, u32x4{ha.x, ha.y, hb.x, hb.y});
+    xl = __builtin_bit_cast(half8, u32x4{la.x, la.y, lb.x, lb.y});
+}
+
 // ======================================================================================
 // k_pwc_stream: W resident in LDS, codes straight into MFMA fragments, 16-pixel work units.
 // ======================================================================================
@@ -86,8 +98,13 @@ constexpr int kPwcThreads = 512;
 // (slfp_layerout_lut.hpp) instead of the reader's threshold table.  The table is read from global memory through the vector cache
 // (4.8 KiB, resident in every CU's L1 after the first units): this kernel's LDS holds W up to its capacity and serves a 1 KiB
 // fragment read per MFMA, so the lookups go to the pipe that idles during the epilogue.  (Unmeasured against an LDS copy.)
-template <int FMT, int KS, bool XW, bool YC, bool RES = false, bool HALF = false, bool DUAL = false, bool LUTQ = false>
+// PASSES == 3 (SLFP<3,4> codes, plain float32 / code output only; slfp_conv2d_fwd_codes_x3): the float32-equivalent mode.  Both planes
+// of W are resident (the blob's lo plane follows its hi plane, so one copy loop takes both), the table is kDecF16HL and every k-step
+// issues (w_lo, x_hi), (w_hi, x_lo), (w_hi, x_hi) as conv_pw.hip's three-pass k_pw_stream does: the same accumulators bit for bit.
+template <int FMT, int KS, bool XW, bool YC, bool RES = false, bool HALF = false, bool DUAL = false, bool LUTQ = false, int PASSES = 1>
 __global__ __launch_bounds__(kPwcThreads) void k_pwc_stream(const PwcParams p) {
+    static_assert(PASSES == 1 || (PASSES == 3 && FMT == kFmtAct8 && !RES && !HALF && !DUAL && !LUTQ), "three passes: SLFP<3,4>, plain float32 or code output");
+    constexpr int PL = PASSES == 3 ? 2 : 1;   // planes of W
     static_assert(!XW || KS % 2 == 0, "16-byte code loads cover two k-steps");
     static_assert(!RES || !YC, "residual operand: float32 output only");
     static_assert(!HALF || !XW, "a half-live last k-step is loaded dword by dword");
@@ -98,12 +115,12 @@ __global__ __launch_bounds__(kPwcThreads) void k_pwc_stream(const PwcParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     _Float16* wl = reinterpret_cast<_Float16*>(smem);
     const int wfrags = p.n_tiles * p.KS;  // 1 KiB each
-    dec_fill<FMT, kDecF16D, kPwcThreads>(sdec);
+    dec_fill<FMT, PASSES == 3 ? kDecF16HL : kDecF16D, kPwcThreads>(sdec);
     if constexpr ((YC && !LUTQ) || DUAL) enc_fill<kPwcThreads>(reinterpret_cast<uint2*>(senc), p.enc);
     const lut_gptr lutg = LUTQ ? enc_carried_ptr(p.enc) : nullptr;
-    for (int i = threadIdx.x; i < wfrags * 64; i += kPwcThreads)
+    for (int i = threadIdx.x; i < PL * wfrags * 64; i += kPwcThreads)
         reinterpret_cast<half8*>(wl)[i] = reinterpret_cast<const half8*>(p.whi)[i];
-    float* ep = reinterpret_cast<float*>(smem + (size_t)wfrags * 1024);   // [256 * bias/s1/s2 | post scale | post shift]
+    float* ep = reinterpret_cast<float*>(smem + (size_t)PL * wfrags * 1024);   // [256 * bias/s1/s2 | post scale | post shift]
     const int n_pad = p.n_tiles * 16;
     const bool has_vec = p.bias != nullptr || p.post.scale != nullptr;   // wave-uniform
     if (has_vec) {
@@ -146,10 +163,12 @@ __global__ __launch_bounds__(kPwcThreads) void k_pwc_stream(const PwcParams p) {
                 if (!HALF || ks + 1 < KS) cw[ks][1] = *reinterpret_cast<const uint32_t*>(xr + ks * 32 + 16 + kq * 4);
             }
         }
-        half8 xh[KS];
+        half8 xh[KS], xl[PASSES == 3 ? KS : 1];
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-            if (HALF && ks + 1 == KS) {
+            if constexpr (PASSES == 3) {
+                dec_frag_hl(cw[ks][0], cw[ks][1], dtab, xh[ks], xl[ks]);
+            } else if (HALF && ks + 1 == KS) {
                 const uint2 pa = dec4_f16(cw[ks][0], dtab);
                 xh[ks] = __builtin_bit_cast(half8, u32x4{pa.x, pa.y, 0u, 0u});
             } else {
@@ -163,6 +182,11 @@ __global__ __launch_bounds__(kPwcThreads) void k_pwc_stream(const PwcParams p) {
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
                 const half8 wh = *reinterpret_cast<const half8*>(wj + ks * 512);
+                if constexpr (PASSES == 3) {
+                    const half8 wlo = *reinterpret_cast<const half8*>(wj + (size_t)wfrags * 512 + ks * 512);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wlo, xh[ks], acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xl[ks], acc, 0, 0, 0);
+                }
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xh[ks], acc, 0, 0, 0);
             }
             const int n = j * 16 + kq * 4;
@@ -434,8 +458,14 @@ __global__ __launch_bounds__(kSliceThreads, RES ? (DUAL ? kSliceDualWaves : 4) :
 // are one dword, stored by the lane itself -- the 16 lanes of a pixel row write the wave's 64 channels as 64 contiguous bytes.
 // LUTQ (YC only): the table epilogue with the table in LDS, where the reader's threshold table lay (4.8 KiB instead of 2 KiB next to
 // the 16 KiB X tile): W streams through the vector memory pipe here, LDS is idle in the epilogue.  (Unmeasured against global reads.)
-template <int FMT, int WM, int WN, int MT, bool YC, bool RES = false, bool DUAL = false, bool LUTQ = false>
+// PASSES == 3 (SLFP<3,4> codes, plain float32 / code output only; slfp_conv2d_fwd_codes_x3): the float32-equivalent mode.  A buffer of
+// the X tile holds the hi plane, then the lo plane (one kDecF16HL lookup per element fills both); the lo fragments of W (p.wlo) are
+// double-buffered next to the hi ones; per k-step and accumulator (w_lo, x_hi), (w_hi, x_lo), (w_hi, x_hi) as conv_pw.hip's three-pass
+// k_pw_tiled: the same accumulators bit for bit.
+template <int FMT, int WM, int WN, int MT, bool YC, bool RES = false, bool DUAL = false, bool LUTQ = false, int PASSES = 1>
 __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_tiled(const PwcParams p) {
+    static_assert(PASSES == 1 || (PASSES == 3 && FMT == kFmtAct8 && !RES && !DUAL && !LUTQ && WM * WN <= 4), "three passes: SLFP<3,4>, plain float32 or code output, 4 waves");
+    constexpr int PL = PASSES == 3 ? 2 : 1;   // planes of X per LDS buffer
     static_assert(!RES || !YC, "residual operand: float32 output only");
     static_assert(!DUAL || RES, "the second, code output belongs to the residual forms");
     static_assert(!LUTQ || YC, "the table epilogue belongs to the code-writing forms");
@@ -450,8 +480,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_ti
     __shared__ __attribute__((aligned(16))) uint32_t sdec[256];
     __shared__ __attribute__((aligned(16))) unsigned char senc[LUTQ ? kLayeroutLutBytes : ((YC || DUAL) ? kPwTab : 16)];
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char* xs = smem;  // [2 buffers][BM rows][128 B]
-    dec_fill<FMT, kDecF16D, T>(sdec);
+    unsigned char* xs = smem;  // [2 buffers][PL planes][BM rows][128 B]
+    dec_fill<FMT, PASSES == 3 ? kDecF16HL : kDecF16D, T>(sdec);
     if constexpr (LUTQ) layerout_lut_fill<T>(senc, enc_carried_ptr(p.enc));
     else if constexpr (YC || DUAL) enc_fill<T>(reinterpret_cast<uint2*>(senc), p.enc);
     const unsigned char* dtab = reinterpret_cast<const unsigned char*>(sdec);
@@ -481,11 +511,18 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_ti
         for (int i = 0; i < NLD; ++i) st[i] = *reinterpret_cast<const uint32_t*>(src[i] + t * 64);
     };
     auto decode_store = [&](int buf) {
-        unsigned char* hi = xs + (size_t)buf * XBYTES;
+        unsigned char* hi = xs + (size_t)buf * PL * XBYTES;
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
             const int row = (threadIdx.x >> 4) + i * (T / 16);
-            *reinterpret_cast<uint2*>(hi + lds_x_off(row, st_chunk) + st_sub) = dec4_f16(st[i], dtab);
+            if constexpr (PASSES == 3) {
+                uint2 ph, pl;
+                dec4_f16hl(st[i], dtab, ph, pl);
+                *reinterpret_cast<uint2*>(hi + lds_x_off(row, st_chunk) + st_sub) = ph;
+                *reinterpret_cast<uint2*>(hi + XBYTES + lds_x_off(row, st_chunk) + st_sub) = pl;
+            } else {
+                *reinterpret_cast<uint2*>(hi + lds_x_off(row, st_chunk) + st_sub) = dec4_f16(st[i], dtab);
+            }
         }
     };
 
@@ -516,21 +553,36 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_ti
     // k-step's MFMAs have read its buffer.  Every vmcnt wait is then for loads issued at least half a stage earlier, and no W
     // wait sits behind X loads that have not been waited for already (loads retire in order through one counter).
     half8 whb[2][NT];
+    half8 wlb[2][PASSES == 3 ? NT : 1];   // PASSES == 3: the lo plane's fragments, same offsets behind p.wlo
+    const __amdgpu_buffer_rsrc_t rwl = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(PASSES == 3 ? p.wlo : p.whi), 0,
+                                                                         (uint32_t)(wbytes > 0xFFFFFFFFull ? 0xFFFFFFFFull : wbytes), 0x00020000);
     auto load_w = [&](int kstep, int b) {
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
             const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rw, wvoff, wsoff[j] + (uint32_t)kstep * 1024u, 0);
             whb[b][j] = __builtin_bit_cast(half8, v);
+            if constexpr (PASSES == 3)
+                wlb[b][j] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rwl, wvoff, wsoff[j] + (uint32_t)kstep * 1024u, 0));
         }
     };
     auto mfma_step = [&](int buf, int ks, int b) {
-        const unsigned char* hi = xs + (size_t)buf * XBYTES;
+        const unsigned char* hi = xs + (size_t)buf * PL * XBYTES;
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
             const int row = (wm * MT + i) * 16 + col;
             const half8 xh = *reinterpret_cast<const half8*>(hi + lds_x_off(row, ks * 4 + kq));
+            if constexpr (PASSES == 3) {
+                const half8 xl = *reinterpret_cast<const half8*>(hi + XBYTES + lds_x_off(row, ks * 4 + kq));
 #pragma unroll
-            for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(whb[b][j], xh, acc[i][j], 0, 0, 0);
+                for (int j = 0; j < NT; ++j) {
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wlb[b][j], xh, acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(whb[b][j], xl, acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(whb[b][j], xh, acc[i][j], 0, 0, 0);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(whb[b][j], xh, acc[i][j], 0, 0, 0);
+            }
         }
     };
 
@@ -619,7 +671,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_ti
         }
     } else {
         // float32 out: staged through a per-wave LDS area into 256-byte runs (4 rows x the wave's 64 channels per store)
-        unsigned char* stg = xs + 2 * XBYTES + wave * (16 * kStgRow);
+        unsigned char* stg = xs + 2 * PL * XBYTES + wave * (16 * kStgRow);
         const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(p.y) + (size_t)m0 * p.N, 0, ybytes, 0x00020000);
         // DUAL: the workgroup's own rows of the code tensor and nothing more (offsets are relative to row m0)
         const uint64_t cleft = (uint64_t)(p.M - m0 < BM ? p.M - m0 : BM) * p.N;
@@ -683,6 +735,7 @@ struct PwcSel {
     int wm, wn, mt;          // k_pwc_tiled: tiling
     int grid_cap;            // SLFP_PW_GRID: k_pwc_stream: the most workgroups; k_pwc_slice: the most rank groups (0: no cap)
     bool lut;                // template argument LUTQ (yc only): set by the caller after pwc_select; the tiling does not depend on it
+    int passes;              // template argument PASSES: 3 from pwc_x3_select (slfp_conv2d_fwd_codes_x3), else 1 (0 reads as 1)
 };
 
 // slice kernel: K a multiple of 256, the slice's W (NTS tiles x K) <= 128 KiB, N a multiple of 16 * NTS
@@ -729,18 +782,25 @@ static const char* pwc_sel_name(const PwcSel& s) {
     if (s.kernel == kPwcStream) n = snprintf(buf, sizeof buf, "pwc-stream/ks%d/%s/%s/%s", s.ks, s.half ? "half" : (s.xw ? "xw" : "dw"), fmt, form);
     else if (s.kernel == kPwcSlice) n = snprintf(buf, sizeof buf, "slice/nts%d/%s/%s", s.nts, fmt, form);
     else n = snprintf(buf, sizeof buf, "pwc-tiled/%d%d%d/%s/%s", s.wm, s.wn, s.mt, fmt, form);
+    if (s.passes == 3) n += snprintf(buf + n, sizeof buf - n, "/p3");
     if (s.kernel != kPwcTiled && s.grid_cap > 0) snprintf(buf + n, sizeof buf - n, "/grid%d", s.grid_cap);
     return buf;
 }
 
-template <int FMT, int KS, bool XW, bool HALF = false>
+template <int FMT, int KS, bool XW, bool HALF = false, int PASSES = 1>
 static int launch_pwc_stream(PwcParams& p, const PwcSel& s, hipStream_t stream, bool dry) {
-    const size_t lds = (size_t)p.n_tiles * p.KS * 1024 + (size_t)3 * p.n_tiles * 16 * sizeof(float);
+    const size_t lds = (size_t)(PASSES == 3 ? 2 : 1) * p.n_tiles * p.KS * 1024 + (size_t)3 * p.n_tiles * 16 * sizeof(float);
     // the table epilogue: the whole-tile k-step counts the layerout nets' 1x1 layers have (32 / 64 / 128 input channels)
-    constexpr bool LUT_OK = !HALF && (KS == 1 || KS == 2 || KS == 4);
+    constexpr bool LUT_OK = PASSES == 1 && !HALF && (KS == 1 || KS == 2 || KS == 4);
     if (s.lut && !LUT_OK) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): no table-epilogue instance for %s", pwc_sel_name(s));
-    auto fn = s.yc ? (s.lut ? k_pwc_stream<FMT, KS, XW, true, false, HALF, false, LUT_OK> : k_pwc_stream<FMT, KS, XW, true, false, HALF>)
-                   : (s.dual ? k_pwc_stream<FMT, KS, XW, false, true, HALF, true> : (s.res ? k_pwc_stream<FMT, KS, XW, false, true, HALF> : k_pwc_stream<FMT, KS, XW, false, false, HALF>));
+    void (*fn)(const PwcParams);
+    if constexpr (PASSES == 3) {
+        if (s.res || s.dual) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): no three-pass residual instance for %s", pwc_sel_name(s));
+        fn = s.yc ? k_pwc_stream<FMT, KS, XW, true, false, false, false, false, 3> : k_pwc_stream<FMT, KS, XW, false, false, false, false, false, 3>;
+    } else {
+        fn = s.yc ? (s.lut ? k_pwc_stream<FMT, KS, XW, true, false, HALF, false, LUT_OK> : k_pwc_stream<FMT, KS, XW, true, false, HALF>)
+                  : (s.dual ? k_pwc_stream<FMT, KS, XW, false, true, HALF, true> : (s.res ? k_pwc_stream<FMT, KS, XW, false, true, HALF> : k_pwc_stream<FMT, KS, XW, false, false, HALF>));
+    }
     if (dry) return SLFP_OK;   // the instance exists: pwc_variant_name's check, before anything touches a device
     int rc = raise_lds_limit(reinterpret_cast<const void*>(fn), lds);
     if (rc != SLFP_OK) return rc;
@@ -755,7 +815,7 @@ static int launch_pwc_stream(PwcParams& p, const PwcSel& s, hipStream_t stream, 
     return check_launch("slfp pointwise (codes, stream) kernel");
 }
 
-template <int FMT, int WM, int WN, int MT>
+template <int FMT, int WM, int WN, int MT, int PASSES = 1>
 static int launch_pwc_tiled(PwcParams& p, const PwcSel& s, hipStream_t stream, bool dry) {
     constexpr int BM = WM * MT * 16, BN = WN * 4 * 16, T = 64 * WM * WN;
     p.n_blocks = (uint32_t)ceil_div((int64_t)p.N, BN);
@@ -764,11 +824,17 @@ static int launch_pwc_tiled(PwcParams& p, const PwcSel& s, hipStream_t stream, b
     const int64_t nblocks = (int64_t)p.m_blocks * p.n_blocks;
     if (nblocks > 0x7FFFFFFF) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): grid too large");
     p.nblocks = (uint32_t)nblocks;
-    const size_t lds = (size_t)2 * BM * 128 + (s.yc ? 0 : (size_t)(T / 64) * 16 * kStgRow);
-    constexpr bool LUT_OK = WM == 1 && WN == 8 && MT == 4;   // the table epilogue: the deep layers (C_out > 256)
+    const size_t lds = (size_t)2 * (PASSES == 3 ? 2 : 1) * BM * 128 + (s.yc ? 0 : (size_t)(T / 64) * 16 * kStgRow);
+    constexpr bool LUT_OK = PASSES == 1 && WM == 1 && WN == 8 && MT == 4;   // the table epilogue: the deep layers (C_out > 256)
     if (s.lut && !LUT_OK) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): no table-epilogue instance for %s", pwc_sel_name(s));
-    auto fn = s.yc ? (s.lut ? k_pwc_tiled<FMT, WM, WN, MT, true, false, false, LUT_OK> : k_pwc_tiled<FMT, WM, WN, MT, true>)
-                   : (s.dual ? k_pwc_tiled<FMT, WM, WN, MT, false, true, true> : (s.res ? k_pwc_tiled<FMT, WM, WN, MT, false, true> : k_pwc_tiled<FMT, WM, WN, MT, false>));
+    void (*fn)(const PwcParams);
+    if constexpr (PASSES == 3) {
+        if (s.res || s.dual) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): no three-pass residual instance for %s", pwc_sel_name(s));
+        fn = s.yc ? k_pwc_tiled<FMT, WM, WN, MT, true, false, false, false, 3> : k_pwc_tiled<FMT, WM, WN, MT, false, false, false, false, 3>;
+    } else {
+        fn = s.yc ? (s.lut ? k_pwc_tiled<FMT, WM, WN, MT, true, false, false, LUT_OK> : k_pwc_tiled<FMT, WM, WN, MT, true>)
+                  : (s.dual ? k_pwc_tiled<FMT, WM, WN, MT, false, true, true> : (s.res ? k_pwc_tiled<FMT, WM, WN, MT, false, true> : k_pwc_tiled<FMT, WM, WN, MT, false>));
+    }
     if (dry) return SLFP_OK;   // the instance exists: pwc_variant_name's check, before anything touches a device
     int rc = raise_lds_limit(reinterpret_cast<const void*>(fn), lds);
     if (rc != SLFP_OK) return rc;
@@ -831,6 +897,100 @@ static int launch_pwc_fmt(PwcParams& p, const PwcSel& s, hipStream_t stream, boo
     return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): no kernel instance for %s", pwc_sel_name(s));
 }
 
+// ---- float32-equivalent (three-pass) mode: slfp_conv2d_fwd_codes_x3 ----
+// The selection, as pwc_select with two planes of W: the LDS-resident kernel where both planes fit and it has the k-step count, else
+// the tiled kernel (K a multiple of 64; also what the single-pass path gives to k_pwc_slice or to the 8-wave tiling: three passes
+// hold the lo fragments in registers next to the hi ones, which the 128-VGPR forms have no room for).
+static int pwc_x3_select(int K, int N, const ConvPlan& plan, bool y_codes, PwcSel* s) {
+    *s = PwcSel{};
+    s->fmt = kFmtAct8; s->yc = y_codes; s->passes = 3;
+    if (K % 32 != 0) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes, three passes): unsupported channel count %d", K);
+    const int ks = K / 32;
+    if (pointwise_stream_fits(plan.k_pad, plan.n_pad, 3) && (ks == 1 || ks == 2 || ks == 3 || ks == 4 || ks == 8)) {
+        s->kernel = kPwcStream;
+        s->grid_cap = switches().pw_grid;
+        s->ks = ks;
+        s->xw = ks % 2 == 0;
+        return SLFP_OK;
+    }
+    if (K % 64 != 0) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes, three passes): unsupported channel count %d", K);
+    s->kernel = kPwcTiled;
+    if (N > 128) { s->wm = 1; s->wn = 4; s->mt = 4; }        // 64 px x 256 ch
+    else if (N > 64) { s->wm = 2; s->wn = 2; s->mt = 2; }    // 64 px x 128 ch
+    else { s->wm = 4; s->wn = 1; s->mt = 1; }                // 64 px x  64 ch
+    return SLFP_OK;
+}
+
+static int launch_pwc_x3_sel(PwcParams& p, const PwcSel& s, hipStream_t stream, bool dry) {
+    if (s.kernel == kPwcStream) {
+        switch (s.ks) {
+            case 1: return launch_pwc_stream<kFmtAct8, 1, false, false, 3>(p, s, stream, dry);
+            case 2: return launch_pwc_stream<kFmtAct8, 2, true, false, 3>(p, s, stream, dry);
+            case 3: return launch_pwc_stream<kFmtAct8, 3, false, false, 3>(p, s, stream, dry);
+            case 4: return launch_pwc_stream<kFmtAct8, 4, true, false, 3>(p, s, stream, dry);
+            case 8: return launch_pwc_stream<kFmtAct8, 8, true, false, 3>(p, s, stream, dry);
+            default: break;
+        }
+    } else {
+        const int t = s.wm * 100 + s.wn * 10 + s.mt;
+        if (t == 144) return launch_pwc_tiled<kFmtAct8, 1, 4, 4, 3>(p, s, stream, dry);
+        if (t == 222) return launch_pwc_tiled<kFmtAct8, 2, 2, 2, 3>(p, s, stream, dry);
+        if (t == 411) return launch_pwc_tiled<kFmtAct8, 4, 1, 1, 3>(p, s, stream, dry);
+    }
+    return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): no kernel instance for %s", pwc_sel_name(s));
+}
+
+const char* pwc_x3_variant_name(const slfp_conv2d_desc& d, const ConvPlan& plan, bool y_codes) {
+    PwcParams p = {};   // the dry dispatch reads none of the pointers
+    PwcSel s;
+    if (plan.family != kPointwise || plan.passes != 3 || pwc_x3_select((int)d.c_in, (int)d.c_out, plan, y_codes, &s) != SLFP_OK) return "none";
+    if (launch_pwc_x3_sel(p, s, nullptr, true) != SLFP_OK) return "none";
+    return pwc_sel_name(s);
+}
+
+bool pwc_x3_applicable(const slfp_conv2d_desc& d, const ConvPlan& plan, int post_flags, bool y_codes) {
+    if (plan.family != kPointwise || plan.repad || plan.passes != 3 || plan.fmt_act != kFmtAct8) return false;
+    if (post_flags & SLFP_POST_LAYEROUT) return false;
+    if (y_codes ? (d.c_out % 16 != 0) : (d.c_out % 4 != 0)) return false;
+    return strcmp(pwc_x3_variant_name(d, plan, y_codes), "none") != 0;
+}
+
+// What every code-input pointwise launch takes from the descriptor and the plan.
+static void pwc_fill(PwcParams& p, const slfp_conv2d_desc& d, const ConvPlan& plan, const uint8_t* x, const void* wfrag, const float* bias,
+                     const PostOp& post, void* y, const CodeIo& io) {
+    p.post = post;
+    p.x = x; p.bias = bias; p.y = y; p.res = nullptr; p.yc = nullptr;
+    p.K = (int)d.c_in; p.N = (int)d.c_out;
+    p.y_ld = io.y_ld ? (int)io.y_ld : p.N;
+    p.KS = (int)(plan.k_pad / 32);
+    p.n_tiles = (int)(plan.n_pad / 16);
+    p.whi = reinterpret_cast<const _Float16*>(wfrag);
+    p.wlo = plan.passes == 3 ? p.whi + (size_t)plan.n_pad * plan.k_pad : nullptr;
+    p.H = (int)d.h; p.W = (int)d.w; p.Ho = (int)plan.h_out; p.Wo = (int)plan.w_out; p.S = d.stride_h;
+    p.M = d.n * plan.h_out * plan.w_out;
+    p.s1 = plan.s1; p.s2 = plan.s2; p.s1x = plan.s1 * (1.0f / 256.0f);
+    p.sgn = post.relu ? 0 : 1;
+    p.fmt_out = io.y_fmt;
+    p.enc.valid = 0;
+}
+
+int launch_pwc_x3(const slfp_conv2d_desc& d, const ConvPlan& plan, const uint8_t* x, const void* wfrag, const float* bias,
+                  const PostOp& post, void* y, const CodeIo& io, hipStream_t stream) {
+    if (plan.passes != 3) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes, three passes): a float32-equivalent SLFP<3,4> descriptor is required");
+    if (io.y_ld || io.lut) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes, three passes): no channel-slice or table-epilogue form");
+    PwcParams p;
+    pwc_fill(p, d, plan, x, wfrag, bias, post, y, io);
+    if (io.y_codes) {
+        const EncArgs* t = enc_table(io.y_ka, io.y_fmt, kEncCode);
+        if (!t->valid) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): no code table for the consumer's scale %g", (double)io.y_ka);
+        p.enc = *t;
+    }
+    PwcSel s;
+    const int rc = pwc_x3_select(p.K, p.N, plan, io.y_codes, &s);
+    if (rc != SLFP_OK) return rc;
+    return launch_pwc_x3_sel(p, s, stream, false);
+}
+
 int launch_pwc(const slfp_conv2d_desc& d, const ConvPlan& plan, const uint8_t* x, const void* wfrag, const float* bias,
                const PostOp& post, void* y, const CodeIo& io, hipStream_t stream, const float* res, void* res_codes) {
     const bool y_codes = io.y_codes;
@@ -841,19 +1001,8 @@ int launch_pwc(const slfp_conv2d_desc& d, const ConvPlan& plan, const uint8_t* x
     if (y_ld && (!y_codes || y_ld < d.c_out || y_ld % 16 || y_ld > 0x7FFFFFFF))
         return fail(SLFP_ERR_BAD_ARG, "pointwise (codes): a channel-slice output needs code output and a pixel stride that is a multiple of 16, >= C_out");
     PwcParams p;
-    p.post = post;
-    p.x = x; p.bias = bias; p.y = y; p.res = res; p.yc = reinterpret_cast<uint8_t*>(res_codes);
-    p.K = (int)d.c_in; p.N = (int)d.c_out;
-    p.y_ld = y_ld ? (int)y_ld : p.N;
-    p.KS = (int)(plan.k_pad / 32);
-    p.n_tiles = (int)(plan.n_pad / 16);
-    p.whi = reinterpret_cast<const _Float16*>(wfrag);
-    p.H = (int)d.h; p.W = (int)d.w; p.Ho = (int)plan.h_out; p.Wo = (int)plan.w_out; p.S = d.stride_h;
-    p.M = d.n * plan.h_out * plan.w_out;
-    p.s1 = plan.s1; p.s2 = plan.s2; p.s1x = plan.s1 * (1.0f / 256.0f);
-    p.sgn = post.relu ? 0 : 1;
-    p.fmt_out = io.y_fmt;
-    p.enc.valid = 0;
+    pwc_fill(p, d, plan, x, wfrag, bias, post, y, io);
+    p.res = res; p.yc = reinterpret_cast<uint8_t*>(res_codes);
     if (io.lut) {
         if (!y_codes || res || !post.scale) return fail(SLFP_ERR_BAD_ARG, "pointwise (codes): the table epilogue needs code output and post_scale / post_shift");
         enc_carry_ptr(p.enc, io.lut);

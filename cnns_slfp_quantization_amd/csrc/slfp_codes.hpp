@@ -29,6 +29,8 @@ constexpr int kEncCode = 2;   // EncArgs representation: V = code(lower class) |
 
 constexpr int kDecF32 = 0;    // decode table entry = float32 bits of the class value
 constexpr int kDecF16D = 1;   // entry = fp16(16 * value) in BOTH halves (a pair is assembled with one v_bfi / v_perm)
+constexpr int kDecF16HL = 2;  // float32-equivalent (three-pass) mode: hi = fp16(16 * value) in the low half, lo = fp16(16 * value - hi)
+                              // in the high half -- the two planes encode4<FMT, 3> / the kEncF16P + kEncF16LO tables give the class
 constexpr int kDecBytes = 1024;
 
 // float32 bits of extended code `code` (Qbits 8: FMT = kFmtAct8, Qbits 7: kFmtSfp7), without an LDS table
@@ -58,6 +60,14 @@ __device__ __forceinline__ void dec_fill(uint32_t* sDec) {
         const uint32_t v = decode_ext_bits<FMT>((uint32_t)i);
         if constexpr (REP == kDecF32) {
             sDec[i] = v;
+        } else if constexpr (REP == kDecF16HL) {
+            const float v16 = 16.0f * __uint_as_float(v);   // exact (a power of two); the tiny class gives 0 / 0
+            const _Float16 h = (_Float16)v16;
+            const _Float16 l = (_Float16)(v16 - (float)h);
+            uint16_t hb, lb;
+            __builtin_memcpy(&hb, &h, 2);
+            __builtin_memcpy(&lb, &l, 2);
+            sDec[i] = (uint32_t)hb | ((uint32_t)lb << 16);
         } else {
             const _Float16 h = (_Float16)(16.0f * __uint_as_float(v));   // the tiny class flushes to 0 as on the float32 path
             uint16_t hb;
@@ -92,6 +102,17 @@ __device__ __forceinline__ uint2 dec4_f16(uint32_t codes, const unsigned char* _
     p.x = (e0 & 0xFFFFu) | (e1 & 0xFFFF0000u);   // one v_bfi_b32 each
     p.y = (e2 & 0xFFFFu) | (e3 & 0xFFFF0000u);
     return p;
+}
+
+// 4 codes -> both planes of the float32-equivalent mode (kDecF16HL table): one LDS read per element yields hi and lo, a pair
+// of either plane is one byte-permute of two entries.  Element 0 in the low half of .x, as dec4_f16.
+__device__ __forceinline__ void dec4_f16hl(uint32_t codes, const unsigned char* __restrict__ sDec, uint2& hi, uint2& lo) {
+    const uint32_t e0 = dec_entry<0>(codes, sDec), e1 = dec_entry<1>(codes, sDec);
+    const uint32_t e2 = dec_entry<2>(codes, sDec), e3 = dec_entry<3>(codes, sDec);
+    hi.x = (e0 & 0xFFFFu) | (e1 << 16);
+    hi.y = (e2 & 0xFFFFu) | (e3 << 16);
+    lo.x = (e0 >> 16) | (e1 & 0xFFFF0000u);
+    lo.y = (e2 >> 16) | (e3 & 0xFFFF0000u);
 }
 
 // 4 float32 values -> their 4 extended codes for a consumer with scale Ka (kEncCode table of that Ka), packed.

@@ -171,6 +171,13 @@ const char* pwc_variant_name(const slfp_conv2d_desc& d, const ConvPlan& p, bool 
 // lut (y_codes only): the table-epilogue instance of the selected kernel (slfp_conv2d_fwd_codes_lut); "none" where none is built
 // res_codes (with res, float32 y, C_out a multiple of 16; slfp_conv2d_fwd_res_codes): the uint8 tensor that receives, next to y, the codes
 // of y for the reader io.y_ka / io.y_fmt describe
+// pointwise on codes in the float32-equivalent (three-pass) mode (slfp_conv2d_fwd_codes_x3): SLFP<3,4> codes in, codes or float32 out,
+// both planes of the SAME prepared blob; no residual, table-epilogue, channel-slice or half-live form.  The name comes from the
+// selection the launcher dispatches on ("none" where the launch would be refused; valid until the next call on the same thread).
+bool pwc_x3_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, int post_flags, bool y_codes);
+int launch_pwc_x3(const slfp_conv2d_desc& d, const ConvPlan& p, const uint8_t* x, const void* wfrag, const float* bias,
+                  const PostOp& post, void* y, const CodeIo& io, hipStream_t stream);
+const char* pwc_x3_variant_name(const slfp_conv2d_desc& d, const ConvPlan& p, bool y_codes);
 // the MobileNetV1 image stem with code output (conv_direct.hip)
 bool stem_codes_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, int post_flags);
 int launch_stem_codes(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const float* wq_hwio, const float* bias,

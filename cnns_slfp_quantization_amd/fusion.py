@@ -14,14 +14,16 @@ undo function restores exactly that state; "also undone by" = the other undo fun
                                    where the blocks are to run on     nn.Identity in the depthwise slot
                                    codes (fuse_bn_relu -> link_codes
                                    -> fuse_dw_pw)
-  link_codes(model, x)             fuse_bn_relu                       _code_out; pools -> CodeMaxPool2d             unlink_codes
+  link_codes(model, x)             fuse_bn_relu                       _code_out (x3=True: _code_x3); pools ->       unlink_codes
+                                                                      CodeMaxPool2d
   fuse_residual(model, x)          fuse_named_bn                      block: instance forward, _residual_fused;     unfuse_residual
                                                                       conv3: residual_relu, _in_residual
   fuse_fire(model, x)              --                                 block: instance forward, _fire_fused; its     unfuse_fire
                                                                       convs: _post, _code_out, _code_entry; pools
                                                                       -> CodeMaxPool2d
   link_codes_traced(model, x)      fuse_named_bn / fuse_bn_relu;      _code_out, _code_entry, _post with the ReLU   unlink_codes
-                                   before or after fuse_residual      bit, _pre_link_post; pools -> CodeMaxPool2d
+                                   before or after fuse_residual      bit, _pre_link_post (x3=True: _code_x3);
+                                                                      pools -> CodeMaxPool2d
   link_stem(model, x)              the folds, fuse_fire(entries=True) stem: _code_out, _post, _pre_link_post,       unlink_stem / unlink_codes
                                    or link_codes_traced(entries=      _stem_link; pools -> CodeMaxPool2d, ReLUs
                                    True), fuse_residual               -> CodeReLU
@@ -588,7 +590,7 @@ def _verified(fn, want, undo, reraise=False, warn=None):
     return ok
 
 
-def link_codes(model, example_input=None):
+def link_codes(model, example_input=None, x3=False):
     """After fuse_bn_relu: wherever a Conv2d_Q's (fused BN + ReLU) output feeds the next Conv2d_Q of an nn.Sequential
     directly (only nn.Identity in between -- nets_imgnet/mobilenetv1.py:24-33 after fusion), link the two: the producer's
     epilogue applies the CONSUMER's quantize_act(. / Ka) (utils/conv2d_func.py:21) and stores 1-byte codes, the consumer
@@ -598,7 +600,11 @@ def link_codes(model, example_input=None):
     records the shapes); without it every candidate is linked and combinations without a kernel run through the float32
     interface plus an encode / decode pass (correct, slower).  Inference only.  Returns the number of links.
     Call it BEFORE fuse_dw_pw (fuse_bn_relu -> link_codes -> fuse_dw_pw): a DwPwBlock is not a Conv2d_Q, so a block formed earlier
-    is neither linked to its neighbours nor inside."""
+    is neither linked to its neighbours nor inside.
+    x3=True (options.mfma_passes = 3, the float32-equivalent mode): a side of a candidate link that reads codes and that
+    slfp_conv2d_codes_supported refuses -- every 1x1 layer in that mode -- is accepted where slfp_conv2d_codes_x3_supported says yes;
+    the module is marked `_code_x3` and runs slfp_conv2d_fwd_codes_x3 (`_last_kernel` ends in "+x3"), bit-identical to the unlinked
+    three-pass net.  The default marks nothing and keeps every link count what it was."""
     from .conv2d_func import _supported
     shapes = {}
     if example_input is not None:
@@ -606,13 +612,19 @@ def link_codes(model, example_input=None):
         shapes = {c.mod: tuple(c.x.shape) for c in tr.calls if _is_conv_q(c.mod)}
         tr.release()
 
-    def supported(m, x_codes, out):
+    def supported(m, x_codes, out):   # False, or what takes the layer: True ("codes") / "codes_x3"
         if example_input is None:
             return True
         shp = shapes.get(m)
         if shp is None or len(shp) != 4:
             return False
-        return _supported(m, shp, "codes", x_codes, out, _post_flags(m))
+        if _supported(m, shp, "codes", x_codes, out, _post_flags(m)):
+            return True
+        return "codes_x3" if x3 and x_codes and _supported(m, shp, "codes_x3", True, out, _post_flags(m)) else False
+
+    def mark(m, how):   # without shapes every code reader may try the three-pass entry point ("codes" is asked first)
+        if how == "codes_x3" or (x3 and example_input is None):
+            m._code_x3 = True
 
     def flat(seq):   # an nn.Sequential of nn.Sequentials runs its leaves in order (conv_bn / conv_dw blocks of the reference nets)
         for m in seq._modules.values():
@@ -641,17 +653,22 @@ def link_codes(model, example_input=None):
             a, b = mods[i], mods[i + 1]
             out = _reader_quant(b)
             a_in = i in linked_in                       # does `a` itself read codes?
-            if not supported(a, a_in, out):
+            how_a = supported(a, a_in, out)
+            if not how_a:
                 # head of a run without a float32 -> codes kernel: enter the chain through one slfp_encode_f32 pass if at least
                 # two more layers then run on codes
                 if a_in or not (i + 1 in cand and supported(b, True, _reader_quant(mods[i + 2]))):
                     continue
             # b with codes in: it may or may not write codes itself; require the float32-out form here (the code-out form is
             # checked when its own link is made; if that fails b keeps float32 out)
-            if not supported(b, True, None):
+            how_b = supported(b, True, None)
+            if not how_b:
                 continue
             if pools_after.get(i) and a.out_channels % 4:
                 continue   # slfp_maxpool2d_codes needs C % 4 == 0
+            if a_in:
+                mark(a, how_a)
+            mark(b, how_b)
             a._code_out = out
             linked_in.add(i + 1)
             n_links += 1
@@ -659,7 +676,7 @@ def link_codes(model, example_input=None):
     return n_links
 
 
-def link_codes_traced(model, example_input, entries=False):
+def link_codes_traced(model, example_input, entries=False, x3=False):
     """link_codes for blocks that wire their layers by hand in forward() (the reference's ResNet-50 Bottleneck,
     nets_imgnet/resnet50.py:74-100: conv1 -> bn1 -> relu -> conv2 -> bn2 -> relu -> conv3 -> bn3 -> (+ identity) -> relu, with ONE
     shared nn.ReLU).  One forward records the tensors: a Conv2d_Q `b` whose input IS the output of a Conv2d_Q `a` -- directly or
@@ -672,7 +689,10 @@ def link_codes_traced(model, example_input, entries=False):
     entries=True: a producer `a` that reads float32 and has no kernel under slfp_conv2d_codes_supported is accepted as well where
     slfp_conv2d_entry_supported says yes (a 1x1 layer: conv1 of every Bottleneck, which reads the float32 trunk); it gets
     `_code_entry = True` and runs slfp_conv2d_fwd_entry.  Everything else -- one consumer only, ReLU folding, pools, verification,
-    roll-back -- is the same; the default keeps every link count what it was."""
+    roll-back -- is the same; the default keeps every link count what it was.
+    x3=True: as link_codes(x3=True) -- a code-reading side that slfp_conv2d_codes_supported refuses is accepted where
+    slfp_conv2d_codes_x3_supported says yes (the 1x1 layers in the float32-equivalent mode: conv2 -> conv3 of every Bottleneck) and
+    marked `_code_x3`; verification and roll-back are the same."""
     from .conv2d_func import _supported
     tr = _Trace(model, example_input)
     y0 = tr.output
@@ -683,10 +703,12 @@ def link_codes_traced(model, example_input, entries=False):
     def x_of(m):
         return tr.of(m)[0].x
 
-    def supported(m, x_codes, out, flags):
+    def supported(m, x_codes, out, flags):   # False, or what takes the layer: True ("codes") / "codes_x3"
         if x_of(m).dim() != 4:
             return False
-        return _supported(m, x_of(m).shape, "codes", x_codes, out, flags)
+        if _supported(m, x_of(m).shape, "codes", x_codes, out, flags):
+            return True
+        return "codes_x3" if x3 and x_codes and _supported(m, x_of(m).shape, "codes_x3", True, out, flags) else False
 
     cand = {}
     for b in order:
@@ -709,7 +731,7 @@ def link_codes_traced(model, example_input, entries=False):
         if pools and a.out_channels % 4:
             continue   # slfp_maxpool2d_codes needs C % 4 == 0
         cand.setdefault(a, []).append((b, via_relu, pools))
-    made, reads_codes, wrapped = [], set(), []
+    made, reads_codes, wrapped, marked = [], set(), [], []
     for a in order:   # execution order: whether `a` itself reads codes is known when its own link is decided
         if a not in cand or len(cand[a]) != 1:
             continue
@@ -719,13 +741,19 @@ def link_codes_traced(model, example_input, entries=False):
         # does `a` itself read codes (an earlier link)?  uint8 into a stem marked by link_image_u8 is pixels, not codes
         a_in = a in reads_codes or (x_of(a).dtype == torch.uint8 and a._image_table is None)
         entry = False
-        if not supported(a, a_in, out, flags):
+        how_a = supported(a, a_in, out, flags)
+        if not how_a:
             entry = (entries and not a_in and x_of(a).dim() == 4
                      and _supported(a, x_of(a).shape, "entry", False, out, flags))
             if not entry:
                 continue
-        if not supported(b, True, b._code_out, _post_flags(b)):
+        how_b = supported(b, True, b._code_out, _post_flags(b))
+        if not how_b:
             continue
+        for m, how in ((a, how_a), (b, how_b)):
+            if how == "codes_x3" and not m._code_x3:
+                m._code_x3 = True
+                marked.append(m)
         made.append((a, a._post))
         a._code_entry = entry
         a._pre_link_post = a._post
@@ -741,6 +769,8 @@ def link_codes_traced(model, example_input, entries=False):
         for a, post in made:
             a._post, a._code_out, a._code_entry = post, None, False
             del a._pre_link_post
+        for m in marked:
+            m._code_x3 = False
         _unwrap_children(wrapped)
 
     return len(made) if _verified(lambda: model(example_input), y0, undo) else 0
@@ -761,6 +791,8 @@ def unlink_codes(model):
             elif isinstance(child, CodeAct):
                 parent._modules[name] = child.act
     for m in model.modules():
+        if _is_conv_q(m):
+            m._code_x3 = False   # the mark of link_codes(x3=True): also on a chain's last reader, which has no _code_out
         if _is_conv_q(m) and m._code_out is not None:
             m._code_out = None
             m._code_entry = False

@@ -355,6 +355,30 @@ int slfp_conv2d_entry_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io*
 int slfp_conv2d_fwd_entry(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const float* x, const void* wprep,
                           const float* bias, const float* post_scale, const float* post_shift, int relu,
                           void* y_codes, void* stream);
+/* ---- float32-equivalent (three-pass) mode on codes, for the 1x1 layers of the pw_mfma_f16x3 family -------------------------------
+ * slfp_conv2d_fwd_codes_x3 reads the uint8 codes slfp_conv2d_fwd_codes takes (io->x_codes == 1: QA(x / d->ka) as SLFP<3,4> extended
+ * codes) and writes float32 (io->y_codes == 0) or the reader's codes (io->y_codes == 1, io->y_ka / io->y_qbits as for
+ * slfp_conv2d_fwd_codes) with a descriptor whose mfma_passes is SLFP_MFMA_F16X3.  Each code expands to the hi + lo fp16 pair of its
+ * class (hi = fp16(16 v), lo = fp16(16 v - hi)); every 32-deep k-step issues (w_lo, x_hi), (w_hi, x_lo), (w_hi, x_hi) in the order of
+ * the float32-interface three-pass kernels and the epilogue is theirs, so the float32 output equals, bit for bit, what
+ * slfp_conv2d_fwd_post writes for the same descriptor on the decoded tensor, and the code output is slfp_encode_f32 of that.
+ * wprep: the blob of slfp_conv2d_prepare_weights for the same descriptor (both planes), unchanged.  x, y, wprep, bias, post_scale and
+ * post_shift 16-byte aligned; post_scale / post_shift given together or both NULL.
+ * Supported (slfp_conv2d_codes_x3_supported: 1 / 0, host only): qbits 8 with SLFP_MFMA_F16X3, 1x1, groups 1, stride 1 or 2 as the
+ * single-pass kernels take it, both layouts NHWC, no channel re-padding, relu 0 or SLFP_POST_RELU, C_in a multiple of 32 (a multiple
+ * of 64 where both planes of W exceed the LDS-resident kernel: C_in / 32 not in {1, 2, 3, 4, 8} or 4 * C_in * C_out(padded to 64) >
+ * 128 KiB), C_out a multiple of 4 (float32 out) or 16 (code out); code out needs y_qbits 8 or 7 and y_ka > 0 with a code table.
+ * There is no residual, second-output, table-epilogue (SLFP_POST_LAYEROUT), channel-slice, float32-in or C_in = 16 / 48 form: those
+ * return SLFP_ERR_UNSUPPORTED and the caller stays on slfp_conv2d_fwd_post.  The older queries and entry points keep refusing
+ * three-pass descriptors on 1x1 layers: the interfaces do not overlap.
+ * slfp_debug_pwc_x3_variant names what runs ("none" where the query says 0), from the selection the launcher dispatches on:
+ *   pwc-stream/ks<KS>/<xw|dw>/act8/<f32|yc>/p3      k_pwc_stream<kFmtAct8, KS, XW, YC, ..., PASSES = 3> (/grid<N> under SLFP_PW_GRID)
+ *   pwc-tiled/<WM><WN><MT>/act8/<f32|yc>/p3         k_pwc_tiled<kFmtAct8, WM, WN, MT, YC, ..., PASSES = 3>: 144, 222 or 411 */
+int slfp_conv2d_codes_x3_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int relu);
+int slfp_conv2d_fwd_codes_x3(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x, const void* wprep,
+                             const float* bias, const float* post_scale, const float* post_shift, int relu,
+                             void* y, void* stream);
+const char* slfp_debug_pwc_x3_variant(const slfp_conv2d_desc* d, const slfp_conv2d_io* io);
 /* ---- residual operand: y = relu?(affine(conv(x)) + res) in ONE launch -------------------------------------------------
  * The tail of every residual block, out = relu(bn3(conv3(h)) + identity) (nets_imgnet/resnet50.py:82-88), for the 1x1
  * stride-1 layers of the pw_mfma_* family.  Per output element, in this order, every step rounded to float32:
