@@ -46,6 +46,30 @@ def _vec(t):
     return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
+def _call(entry, x, *args):
+    """One entry point of csrc/bn_train.hip on x's device and stream: `args` in its order (addresses, None for a null pointer,
+    numbers; the caller keeps the tensors behind them alive), then the tail every entry point ends with: geometry, layout,
+    workspace and stream."""
+    L = _lib.load()
+    n, c, h, w = x.shape
+    with _on_device(x.device):
+        nbytes = L.slfp_bn_train_workspace_bytes(n, h, w, c)
+        ws = _workspace(x.device, nbytes)
+        _lib.check(getattr(L, entry)(*args, n, h, w, c, _lib.LAYOUT_NHWC, ws.data_ptr(), nbytes, _stream_handle(x)))
+
+
+def _outputs(x, saves):
+    """y (x's channels_last strides) and `saves` per-channel float32 arrays for the forward to fill (x is float32)."""
+    c = x.shape[1]
+    return [torch.empty_like(x)] + [x.new_empty(c) for _ in range(saves)]
+
+
+def _grads(ctx, x, save_mean, iw):
+    """gx, and ggamma / gbeta where the weight (input `iw`) and the bias behind it need them (None: a null pointer)."""
+    need = ctx.needs_input_grad
+    return torch.empty_like(x), torch.empty_like(save_mean) if need[iw] else None, torch.empty_like(save_mean) if need[iw + 1] else None
+
+
 class hip_bn_train(torch.autograd.Function):
     """y = relu?(batch_norm(x)) with batch statistics; running_mean / running_var (both or neither) are updated in place.
     x: channels_last float32 that bn_train_supported() accepts; weight, bias: float32 [C].  Returns y (channels_last).  The
@@ -54,45 +78,24 @@ class hip_bn_train(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, relu):
-        L = _lib.load()
-        n, c, h, w = x.shape
         x = x.detach()
         gamma, beta = _vec(weight), _vec(bias)
-        y = torch.empty_like(x)   # keeps the channels_last strides
-        save_mean = torch.empty(c, dtype=torch.float32, device=x.device)
-        save_invstd = torch.empty(c, dtype=torch.float32, device=x.device)
-        with _on_device(x.device):
-            nbytes = L.slfp_bn_train_workspace_bytes(n, h, w, c)
-            ws = _workspace(x.device, nbytes)
-            _lib.check(L.slfp_bn_train_fwd(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(running_mean), _ptr(running_var),
-                                           float(momentum), float(eps), 1 if relu else 0, y.data_ptr(), save_mean.data_ptr(),
-                                           save_invstd.data_ptr(), n, h, w, c, _lib.LAYOUT_NHWC, ws.data_ptr(), nbytes,
-                                           _stream_handle(x)))
+        y, save_mean, save_invstd = _outputs(x, 2)
+        _call("slfp_bn_train_fwd", x, x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(running_mean), _ptr(running_var),
+              float(momentum), float(eps), 1 if relu else 0, y.data_ptr(), save_mean.data_ptr(), save_invstd.data_ptr())
         ctx.relu = bool(relu)
-        if ctx.relu:
-            ctx.save_for_backward(x, weight, save_mean, save_invstd, y)
-        else:
-            ctx.save_for_backward(x, weight, save_mean, save_invstd)
+        ctx.save_for_backward(x, weight, save_mean, save_invstd, *((y,) if ctx.relu else ()))
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        L = _lib.load()
         x, weight, save_mean, save_invstd = ctx.saved_tensors[:4]
         y = ctx.saved_tensors[4] if ctx.relu else x   # relu == 0: y is not read; any valid pointer stands in
-        n, c, h, w = x.shape
-        gy = _nhwc(gy)
-        gamma = _vec(weight)
-        gx = torch.empty_like(x)
-        ggamma = torch.empty_like(save_mean) if ctx.needs_input_grad[1] else None
-        gbeta = torch.empty_like(save_mean) if ctx.needs_input_grad[2] else None
-        with _on_device(x.device):
-            nbytes = L.slfp_bn_train_workspace_bytes(n, h, w, c)
-            ws = _workspace(x.device, nbytes)
-            _lib.check(L.slfp_bn_train_bwd(x.data_ptr(), y.data_ptr(), gy.data_ptr(), gamma.data_ptr(), save_mean.data_ptr(),
-                                           save_invstd.data_ptr(), 1 if ctx.relu else 0, gx.data_ptr(), _ptr(ggamma), _ptr(gbeta),
-                                           n, h, w, c, _lib.LAYOUT_NHWC, ws.data_ptr(), nbytes, _stream_handle(x)))
+        gy, gamma = _nhwc(gy), _vec(weight)
+        gx, ggamma, gbeta = _grads(ctx, x, save_mean, 1)
+        _call("slfp_bn_train_bwd", x, x.data_ptr(), y.data_ptr(), gy.data_ptr(), gamma.data_ptr(), save_mean.data_ptr(),
+              save_invstd.data_ptr(), 1 if ctx.relu else 0, gx.data_ptr(), _ptr(ggamma), _ptr(gbeta))
         return gx if ctx.needs_input_grad[0] else None, ggamma, gbeta, None, None, None, None, None
 
 
@@ -123,52 +126,32 @@ class hip_bn_res_train(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, res, weight, bias, running_mean, running_var, momentum, eps, relu):
-        L = _lib.load()
-        n, c, h, w = x.shape
         if res.shape != x.shape or res.dtype != x.dtype or res.device != x.device:
             raise ValueError("hip_bn_res_train: the residual must have x's shape, dtype and device")
         x = x.detach()
         res = _nhwc(res.detach())
         gamma, beta = _vec(weight), _vec(bias)
-        y = torch.empty_like(x)   # keeps the channels_last strides
-        save_mean = torch.empty(c, dtype=torch.float32, device=x.device)
-        save_invstd = torch.empty(c, dtype=torch.float32, device=x.device)
-        with _on_device(x.device):
-            nbytes = L.slfp_bn_train_workspace_bytes(n, h, w, c)
-            ws = _workspace(x.device, nbytes)
-            _lib.check(L.slfp_bn_res_train_fwd(x.data_ptr(), res.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(running_mean),
-                                               _ptr(running_var), float(momentum), float(eps), 1 if relu else 0, y.data_ptr(),
-                                               save_mean.data_ptr(), save_invstd.data_ptr(), n, h, w, c, _lib.LAYOUT_NHWC,
-                                               ws.data_ptr(), nbytes, _stream_handle(x)))
+        y, save_mean, save_invstd = _outputs(x, 2)
+        _call("slfp_bn_res_train_fwd", x, x.data_ptr(), res.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(running_mean),
+              _ptr(running_var), float(momentum), float(eps), 1 if relu else 0, y.data_ptr(), save_mean.data_ptr(),
+              save_invstd.data_ptr())
         ctx.relu = bool(relu)
-        if ctx.relu:
-            ctx.save_for_backward(x, weight, save_mean, save_invstd, y)
-        else:
-            ctx.save_for_backward(x, weight, save_mean, save_invstd)
+        ctx.save_for_backward(x, weight, save_mean, save_invstd, *((y,) if ctx.relu else ()))
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        L = _lib.load()
         x, weight, save_mean, save_invstd = ctx.saved_tensors[:4]
         y = ctx.saved_tensors[4] if ctx.relu else x   # relu == 0: y is not read; any valid pointer stands in
-        n, c, h, w = x.shape
-        gy = _nhwc(gy)
-        gamma = _vec(weight)
-        gx = torch.empty_like(x)
+        gy, gamma = _nhwc(gy), _vec(weight)
+        gx, ggamma, gbeta = _grads(ctx, x, save_mean, 2)
         gres = None
         if ctx.needs_input_grad[1]:
             gres = torch.empty_like(x) if ctx.relu else gy   # relu == 0: g is gy itself, no copy is asked of the kernel
-        ggamma = torch.empty_like(save_mean) if ctx.needs_input_grad[2] else None
-        gbeta = torch.empty_like(save_mean) if ctx.needs_input_grad[3] else None
-        with _on_device(x.device):
-            nbytes = L.slfp_bn_train_workspace_bytes(n, h, w, c)
-            ws = _workspace(x.device, nbytes)
-            _lib.check(L.slfp_bn_res_train_bwd(x.data_ptr(), y.data_ptr(), gy.data_ptr(), gamma.data_ptr(), save_mean.data_ptr(),
-                                               save_invstd.data_ptr(), 1 if ctx.relu else 0, gx.data_ptr(),
-                                               _ptr(gres) if ctx.relu else None, _ptr(ggamma), _ptr(gbeta), n, h, w, c,
-                                               _lib.LAYOUT_NHWC, ws.data_ptr(), nbytes, _stream_handle(x)))
+        _call("slfp_bn_res_train_bwd", x, x.data_ptr(), y.data_ptr(), gy.data_ptr(), gamma.data_ptr(), save_mean.data_ptr(),
+              save_invstd.data_ptr(), 1 if ctx.relu else 0, gx.data_ptr(), _ptr(gres) if ctx.relu else None, _ptr(ggamma),
+              _ptr(gbeta))
         return gx if ctx.needs_input_grad[0] else None, gres, ggamma, gbeta, None, None, None, None, None
 
 
@@ -235,21 +218,12 @@ class hip_bn_lut_train(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, ftab, dtab):
-        L = _lib.load()
-        n, c, h, w = x.shape
         x = x.detach()
         gamma, beta = _vec(weight), _vec(bias)
-        y = torch.empty_like(x)   # keeps the channels_last strides
-        save_mean = torch.empty(c, dtype=torch.float32, device=x.device)
-        save_invstd = torch.empty(c, dtype=torch.float32, device=x.device)
-        save_lo = torch.empty(c, dtype=torch.float32, device=x.device)
-        with _on_device(x.device):
-            nbytes = L.slfp_bn_train_workspace_bytes(n, h, w, c)
-            ws = _workspace(x.device, nbytes)
-            _lib.check(L.slfp_bn_lut_train_fwd(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(running_mean), _ptr(running_var),
-                                               float(momentum), float(eps), ftab.data_ptr(), y.data_ptr(), save_mean.data_ptr(),
-                                               save_invstd.data_ptr(), save_lo.data_ptr(), n, h, w, c, _lib.LAYOUT_NHWC,
-                                               ws.data_ptr(), nbytes, _stream_handle(x)))
+        y, save_mean, save_invstd, save_lo = _outputs(x, 3)
+        _call("slfp_bn_lut_train_fwd", x, x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(running_mean), _ptr(running_var),
+              float(momentum), float(eps), ftab.data_ptr(), y.data_ptr(), save_mean.data_ptr(), save_invstd.data_ptr(),
+              save_lo.data_ptr())
         ctx.dtab = dtab
         ctx.save_for_backward(x, weight, bias, save_mean, save_invstd, save_lo)
         return y
@@ -257,19 +231,9 @@ class hip_bn_lut_train(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        L = _lib.load()
         x, weight, bias, save_mean, save_invstd, save_lo = ctx.saved_tensors
-        n, c, h, w = x.shape
-        gy = _nhwc(gy)
-        gamma, beta = _vec(weight), _vec(bias)
-        gx = torch.empty_like(x)
-        ggamma = torch.empty_like(save_mean) if ctx.needs_input_grad[1] else None
-        gbeta = torch.empty_like(save_mean) if ctx.needs_input_grad[2] else None
-        with _on_device(x.device):
-            nbytes = L.slfp_bn_train_workspace_bytes(n, h, w, c)
-            ws = _workspace(x.device, nbytes)
-            _lib.check(L.slfp_bn_lut_train_bwd(x.data_ptr(), gy.data_ptr(), gamma.data_ptr(), beta.data_ptr(), save_mean.data_ptr(),
-                                               save_invstd.data_ptr(), save_lo.data_ptr(), ctx.dtab.data_ptr(), gx.data_ptr(),
-                                               _ptr(ggamma), _ptr(gbeta), n, h, w, c, _lib.LAYOUT_NHWC, ws.data_ptr(), nbytes,
-                                               _stream_handle(x)))
+        gy, gamma, beta = _nhwc(gy), _vec(weight), _vec(bias)
+        gx, ggamma, gbeta = _grads(ctx, x, save_mean, 1)
+        _call("slfp_bn_lut_train_bwd", x, x.data_ptr(), gy.data_ptr(), gamma.data_ptr(), beta.data_ptr(), save_mean.data_ptr(),
+              save_invstd.data_ptr(), save_lo.data_ptr(), ctx.dtab.data_ptr(), gx.data_ptr(), _ptr(ggamma), _ptr(gbeta))
         return gx if ctx.needs_input_grad[0] else None, ggamma, gbeta, None, None, None, None, None, None

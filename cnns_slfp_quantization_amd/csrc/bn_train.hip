@@ -42,6 +42,10 @@
 // The statistics, both finalize kernels and the reduce pass are the plain ones.
 // The two finalize kernels stage the records of 256 slabs x 8 channels in LDS with all 256 lanes (and the per-slab weights
 // n_b / n and n_a n_b / n, which depend on the slab index alone), then one lane per channel runs the serial chain.
+// Each of these is written once: bn_walk is the lane's walk over its rows (all five streaming kernels), bn_affine the apply's
+// expression (the apply of every form, and through bn_class the backward's recomputed class), bn_g the g of one element
+// (reduce, dx and the gres store), bn_forward / bn_backward the refusals and the three launches of a direction; the six entry
+// points state their pointers and the refusals of their own form.
 #include "slfp_device.hpp"
 #include "slfp_host.hpp"
 #include "slfp_layerout_lut.hpp"
@@ -158,10 +162,17 @@ template <bool LUT> __device__ __forceinline__ const float* bn_table_lds(const f
     }
 }
 
-// LUT forms: the class of one element, from the forward's own expression (sc = invstd * gamma)
-__device__ __forceinline__ uint32_t bn_class(const float x, const float mean, const float lo, const float sc, const float beta) {
-    const float t = (((x - mean) - lo) * sc) + beta;
-    return layerout_class(layerout_bits(__float_as_uint(t)));
+// The forward's affine map of a lane's V channels: sc = invstd * gamma; lo is f32(mean - save_mean)
+template <int V> struct BnMap { Pack<V> mean, lo, sc, beta; };
+
+// The apply's expression, channel e of the lane.  The backward of the LUT forms recomputes the class through this very function.
+template <int V> __device__ __forceinline__ float bn_affine(const float x, const BnMap<V>& m, const int e) {
+    return (((x - m.mean.v[e]) - m.lo.v[e]) * m.sc.v[e]) + m.beta.v[e];
+}
+
+// LUT forms: the class of one element
+template <int V> __device__ __forceinline__ uint32_t bn_class(const float x, const BnMap<V>& m, const int e) {
+    return layerout_class(layerout_bits(__float_as_uint(bn_affine<V>(x, m, e))));
 }
 
 // Where a lane stands: its first channel, whether that channel exists, its rows [first, r1) with stride nty.
@@ -198,6 +209,26 @@ template <int V, int K> __device__ __forceinline__ void bn_meet(Pack<V> (&p)[K],
     }
 }
 
+// What a lane loads of one row: N operands of V channels each
+template <int V, int N> struct BnRow { Pack<V> p[N]; };
+
+// A lane's walk over rows r, r + st, ... < end of pitch ld: load(offset) of AHEAD rows are all issued before use(offset, row)
+// of the first of them; then a one-row tail.  The uses run in row order.
+template <int AHEAD, class Load, class Use>
+__device__ __forceinline__ void bn_walk(int64_t r, const int64_t end, const int64_t st, const size_t ld, Load load, Use use) {
+    for (; r + (AHEAD - 1) * st < end; r += AHEAD * st) {
+        decltype(load((size_t)0)) b[AHEAD];
+#pragma unroll
+        for (int i = 0; i < AHEAD; ++i) b[i] = load((size_t)(r + i * st) * ld);
+#pragma unroll
+        for (int i = 0; i < AHEAD; ++i) use((size_t)(r + i * st) * ld, b[i]);
+    }
+    for (; r < end; r += st) {
+        const size_t o = (size_t)r * ld;
+        use(o, load(o));
+    }
+}
+
 template <int V> __device__ __forceinline__ void bn_stat_add(Pack<V> (&s)[2], const Pack<V>& v, const Pack<V>& k) {
 #pragma unroll
     for (int e = 0; e < V; ++e) {
@@ -214,16 +245,9 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_stats(const BnArgs a) {
     const float* px = a.x + (l.live ? l.ch : 0);
     const Pack<V> k = l.live ? bn_ld<V>(px + (size_t)l.r0 * ld) : bn_fill<V>(0.f);
     Pack<V> s[2] = {bn_fill<V>(0.f), bn_fill<V>(0.f)};   // s1, s2
-    const int64_t st = l.nty;
-    int64_t r = l.first;
-    for (; r + 7 * st < l.r1; r += 8 * st) {   // eight loads ahead of the adds of this lane's one chain per channel
-        Pack<V> v[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = bn_ld<V>(px + (size_t)(r + i * st) * ld);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) bn_stat_add<V>(s, v[i], k);
-    }
-    for (; r < l.r1; r += st) bn_stat_add<V>(s, bn_ld<V>(px + (size_t)r * ld), k);
+    // eight loads ahead of the adds of this lane's one chain per channel
+    bn_walk<8>(l.first, l.r1, l.nty, ld, [&](const size_t o) { return BnRow<V, 1>{{bn_ld<V>(px + o)}}; },
+               [&](const size_t, const BnRow<V, 1>& b) { bn_stat_add<V>(s, b.p[0], k); });
     bn_meet<V, 2>(s, l, a.tx_log2);
     if (l.ty != 0 || !l.live) return;
     const float cnt = __int_as_float((int)(l.r1 - l.r0));
@@ -297,70 +321,57 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_apply(const BnArgs a) {
     const float* const sTab = bn_table_lds<LUT>(a.table);
     if (!l.live) return;
     const size_t ld = (size_t)a.c;
-    const Pack<V> mean = bn_ld<V>(a.mean + l.ch), lo = bn_ld<V>(a.gmean + l.ch), beta = bn_ld<V>(a.beta + l.ch);
-    Pack<V> sc = bn_ld<V>(a.invstd + l.ch);
+    BnMap<V> map = {bn_ld<V>(a.mean + l.ch), bn_ld<V>(a.gmean + l.ch), bn_ld<V>(a.invstd + l.ch), bn_ld<V>(a.beta + l.ch)};
     const Pack<V> gamma = bn_ld<V>(a.gamma + l.ch);
 #pragma unroll
-    for (int e = 0; e < V; ++e) sc.v[e] = sc.v[e] * gamma.v[e];
+    for (int e = 0; e < V; ++e) map.sc.v[e] = map.sc.v[e] * gamma.v[e];
     const float* px = a.x + l.ch;
+    const float* pr = RES ? a.res + l.ch : nullptr;
     float* py = a.out + l.ch;
     const int relu = a.relu;
-    auto f = [&](Pack<V> v) {
+    constexpr int N = RES ? 2 : 1;
+    bn_walk<4>(l.first, l.r1, l.nty, ld,
+               [&](const size_t o) {
+                   BnRow<V, N> b;
+                   b.p[0] = bn_ld<V>(px + o);
+                   if constexpr (RES) b.p[1] = bn_ld<V>(pr + o);
+                   return b;
+               },
+               [&](const size_t o, const BnRow<V, N>& b) {
+                   Pack<V> v;
 #pragma unroll
-        for (int e = 0; e < V; ++e) {
-            if constexpr (LUT) {
-                v.v[e] = sTab[bn_class(v.v[e], mean.v[e], lo.v[e], sc.v[e], beta.v[e])];
-            } else {
-                float t = (((v.v[e] - mean.v[e]) - lo.v[e]) * sc.v[e]) + beta.v[e];
-                if (relu) t = t < 0.f ? 0.f : t;
-                v.v[e] = t;
-            }
-        }
-        return v;
-    };
-    const int64_t st = l.nty;
-    int64_t r = l.first;
-    if constexpr (RES) {
-        const float* pr = a.res + l.ch;
-        auto fr = [&](Pack<V> v, const Pack<V>& q) {   // the add is rounded on its own, the ReLU comes behind it
-#pragma unroll
-            for (int e = 0; e < V; ++e) {
-                const float t = (((v.v[e] - mean.v[e]) - lo.v[e]) * sc.v[e]) + beta.v[e];
-                float z = t + q.v[e];
-                if (relu) z = z < 0.f ? 0.f : z;
-                v.v[e] = z;
-            }
-            return v;
-        };
-        for (; r + 3 * st < l.r1; r += 4 * st) {
-            Pack<V> v[4], q[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const size_t o = (size_t)(r + i * st) * ld;
-                v[i] = bn_ld<V>(px + o);
-                q[i] = bn_ld<V>(pr + o);
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) bn_st<V>(py + (size_t)(r + i * st) * ld, fr(v[i], q[i]));
-        }
-        for (; r < l.r1; r += st) {
-            const size_t o = (size_t)r * ld;
-            bn_st<V>(py + o, fr(bn_ld<V>(px + o), bn_ld<V>(pr + o)));
-        }
-    } else {
-        for (; r + 3 * st < l.r1; r += 4 * st) {
-            Pack<V> v[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = bn_ld<V>(px + (size_t)(r + i * st) * ld);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) bn_st<V>(py + (size_t)(r + i * st) * ld, f(v[i]));
-        }
-        for (; r < l.r1; r += st) bn_st<V>(py + (size_t)r * ld, f(bn_ld<V>(px + (size_t)r * ld)));
-    }
+                   for (int e = 0; e < V; ++e) {
+                       if constexpr (LUT) {
+                           v.v[e] = sTab[bn_class<V>(b.p[0].v[e], map, e)];
+                       } else {
+                           float t = bn_affine<V>(b.p[0].v[e], map, e);
+                           if constexpr (RES) t = t + b.p[1].v[e];   // the add is rounded on its own, the ReLU comes behind it
+                           if (relu) t = t < 0.f ? 0.f : t;
+                           v.v[e] = t;
+                       }
+                   }
+                   bn_st<V>(py + o, v);
+               });
 }
 
-// g of one element: the ReLU's mask is read from the forward's own output
-__device__ __forceinline__ float bn_g(const float gy, const float y, const int relu) { return relu ? (y > 0.f ? gy : 0.f) : gy; }
+// What the backward loads of one row: x, gy and the forward's y (with relu only: otherwise y is never read)
+template <int V> __device__ __forceinline__ BnRow<V, 3> bn_ld_bwd(const float* px, const float* pg, const float* py, const size_t o,
+                                                                  const int relu) {
+    BnRow<V, 3> b;
+    b.p[0] = bn_ld<V>(px + o);
+    b.p[1] = bn_ld<V>(pg + o);
+    b.p[2] = relu ? bn_ld<V>(py + o) : b.p[1];
+    return b;
+}
+
+// g of channel e of a row.  The ReLU's mask is read from the forward's own output; the LUT forms multiply by the derivative
+// table at the class recomputed from x (map: the forward's own mean, lo, sc and beta).
+template <int V, bool LUT>
+__device__ __forceinline__ float bn_g(const BnRow<V, 3>& b, const int e, const int relu, const float* sTab, const BnMap<V>& map) {
+    const float gy = b.p[1].v[e];
+    if constexpr (LUT) return gy * sTab[bn_class<V>(b.p[0].v[e], map, e)];
+    else return relu ? (b.p[2].v[e] > 0.f ? gy : 0.f) : gy;
+}
 
 template <int V, bool LUT = false>
 __global__ __launch_bounds__(kBnThreads) void k_bn_bwd_reduce(const BnArgs a) {
@@ -370,14 +381,14 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_bwd_reduce(const BnArgs a) {
     const size_t c0 = l.live ? (size_t)l.ch : 0;
     const Pack<V> mean = l.live ? bn_ld<V>(a.mean + c0) : bn_fill<V>(0.f);
     const Pack<V> invstd = l.live ? bn_ld<V>(a.invstd + c0) : bn_fill<V>(0.f);
-    Pack<V> lof = bn_fill<V>(0.f), sc = bn_fill<V>(0.f), beta = bn_fill<V>(0.f);   // LUT: the forward's lo, invstd * gamma, beta
+    BnMap<V> map = {mean, bn_fill<V>(0.f), bn_fill<V>(0.f), bn_fill<V>(0.f)};   // LUT: the forward's lo, invstd * gamma, beta
     if constexpr (LUT) {
         if (l.live) {
             const Pack<V> gamma = bn_ld<V>(a.gamma + c0);
-            lof = bn_ld<V>(a.lo_fwd + c0);
-            beta = bn_ld<V>(a.beta + c0);
+            map.lo = bn_ld<V>(a.lo_fwd + c0);
+            map.beta = bn_ld<V>(a.beta + c0);
 #pragma unroll
-            for (int e = 0; e < V; ++e) sc.v[e] = invstd.v[e] * gamma.v[e];
+            for (int e = 0; e < V; ++e) map.sc.v[e] = invstd.v[e] * gamma.v[e];
         }
     }
     const float* px = a.x + c0;
@@ -385,37 +396,17 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_bwd_reduce(const BnArgs a) {
     const float* py = a.y + c0;   // read with relu only
     const int relu = a.relu;
     Pack<V> s[3] = {bn_fill<V>(0.f), bn_fill<V>(0.f), bn_fill<V>(0.f)};   // sg, sx, sd
-    auto add = [&](const Pack<V>& x, const Pack<V>& gy, const Pack<V>& y) {
+    bn_walk<4>(l.first, l.r1, l.nty, ld, [&](const size_t o) { return bn_ld_bwd<V>(px, pg, py, o, relu); },
+               [&](const size_t, const BnRow<V, 3>& b) {
 #pragma unroll
-        for (int e = 0; e < V; ++e) {
-            float g;
-            if constexpr (LUT) g = gy.v[e] * sTab[bn_class(x.v[e], mean.v[e], lof.v[e], sc.v[e], beta.v[e])];
-            else g = bn_g(gy.v[e], y.v[e], relu);
-            const float d = x.v[e] - mean.v[e];
-            s[0].v[e] = s[0].v[e] + g;
-            s[1].v[e] = s[1].v[e] + g * (d * invstd.v[e]);
-            s[2].v[e] = s[2].v[e] + d;
-        }
-    };
-    const int64_t st = l.nty;
-    int64_t r = l.first;
-    for (; r + 3 * st < l.r1; r += 4 * st) {
-        Pack<V> x[4], g[4], y[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const size_t o = (size_t)(r + i * st) * ld;
-            x[i] = bn_ld<V>(px + o);
-            g[i] = bn_ld<V>(pg + o);
-            y[i] = relu ? bn_ld<V>(py + o) : g[i];
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) add(x[i], g[i], y[i]);
-    }
-    for (; r < l.r1; r += st) {
-        const size_t o = (size_t)r * ld;
-        const Pack<V> g = bn_ld<V>(pg + o);
-        add(bn_ld<V>(px + o), g, relu ? bn_ld<V>(py + o) : g);
-    }
+                   for (int e = 0; e < V; ++e) {
+                       const float g = bn_g<V, LUT>(b, e, relu, sTab, map);
+                       const float d = b.p[0].v[e] - mean.v[e];
+                       s[0].v[e] = s[0].v[e] + g;
+                       s[1].v[e] = s[1].v[e] + g * (d * invstd.v[e]);
+                       s[2].v[e] = s[2].v[e] + d;
+                   }
+               });
     bn_meet<V, 3>(s, l, a.tx_log2);
     if (l.ty != 0 || !l.live) return;
     float4* part = a.part + (size_t)blockIdx.x * ld + (size_t)l.ch;
@@ -469,83 +460,33 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_bwd_dx(const BnArgs a) {
     const size_t ld = (size_t)a.c;
     const Pack<V> mean = bn_ld<V>(a.mean + l.ch), invstd = bn_ld<V>(a.invstd + l.ch), gamma = bn_ld<V>(a.gamma + l.ch);
     const Pack<V> mb = bn_ld<V>(a.gmean + l.ch), mg = bn_ld<V>(a.gmean + ld + l.ch), lo = bn_ld<V>(a.gmean + 2 * ld + l.ch);
-    Pack<V> sc;
+    BnMap<V> map = {mean, bn_fill<V>(0.f), bn_fill<V>(0.f), bn_fill<V>(0.f)};   // sc = gamma * invstd, the forward's too
 #pragma unroll
-    for (int e = 0; e < V; ++e) sc.v[e] = gamma.v[e] * invstd.v[e];
-    Pack<V> lof = bn_fill<V>(0.f), beta = bn_fill<V>(0.f);   // LUT: the forward's lo and beta (its invstd * gamma is sc)
-    if constexpr (LUT) {
-        lof = bn_ld<V>(a.lo_fwd + l.ch);
-        beta = bn_ld<V>(a.beta + l.ch);
+    for (int e = 0; e < V; ++e) map.sc.v[e] = gamma.v[e] * invstd.v[e];
+    if constexpr (LUT) {   // the forward's lo and beta
+        map.lo = bn_ld<V>(a.lo_fwd + l.ch);
+        map.beta = bn_ld<V>(a.beta + l.ch);
     }
     const float* px = a.x + l.ch;
     const float* pg = a.gy + l.ch;
     const float* py = a.y + l.ch;   // read with relu only
     float* po = a.out + l.ch;
+    float* pq = RES && a.gres ? a.gres + l.ch : nullptr;   // the residual's gradient: g itself, stored where gx is
     const int relu = a.relu;
-    auto f = [&](const Pack<V>& x, const Pack<V>& gy, const Pack<V>& y) {
-        Pack<V> o;
+    bn_walk<4>(l.first, l.r1, l.nty, ld, [&](const size_t o) { return bn_ld_bwd<V>(px, pg, py, o, relu); },
+               [&](const size_t o, const BnRow<V, 3>& b) {
+                   Pack<V> gx, g;
 #pragma unroll
-        for (int e = 0; e < V; ++e) {
-            float g;
-            if constexpr (LUT) g = gy.v[e] * sTab[bn_class(x.v[e], mean.v[e], lof.v[e], sc.v[e], beta.v[e])];
-            else g = bn_g(gy.v[e], y.v[e], relu);
-            const float xh = ((x.v[e] - mean.v[e]) - lo.v[e]) * invstd.v[e];
-            o.v[e] = sc.v[e] * ((g - mb.v[e]) - (xh * mg.v[e]));
-        }
-        return o;
-    };
-    const int64_t st = l.nty;
-    int64_t r = l.first;
-    if constexpr (RES) {
-        float* pq = a.gres ? a.gres + l.ch : nullptr;   // the residual's gradient: g itself, stored where gx is
-        auto gq = [&](const Pack<V>& gy, const Pack<V>& y) {
-            Pack<V> o;
-#pragma unroll
-            for (int e = 0; e < V; ++e) o.v[e] = bn_g(gy.v[e], y.v[e], relu);
-            return o;
-        };
-        for (; r + 3 * st < l.r1; r += 4 * st) {
-            Pack<V> x[4], g[4], y[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const size_t o = (size_t)(r + i * st) * ld;
-                x[i] = bn_ld<V>(px + o);
-                g[i] = bn_ld<V>(pg + o);
-                y[i] = relu ? bn_ld<V>(py + o) : g[i];
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const size_t o = (size_t)(r + i * st) * ld;
-                bn_st<V>(po + o, f(x[i], g[i], y[i]));
-                if (pq) bn_st<V>(pq + o, gq(g[i], y[i]));
-            }
-        }
-        for (; r < l.r1; r += st) {
-            const size_t o = (size_t)r * ld;
-            const Pack<V> g = bn_ld<V>(pg + o);
-            const Pack<V> y = relu ? bn_ld<V>(py + o) : g;
-            bn_st<V>(po + o, f(bn_ld<V>(px + o), g, y));
-            if (pq) bn_st<V>(pq + o, gq(g, y));
-        }
-        return;
-    }
-    for (; r + 3 * st < l.r1; r += 4 * st) {
-        Pack<V> x[4], g[4], y[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const size_t o = (size_t)(r + i * st) * ld;
-            x[i] = bn_ld<V>(px + o);
-            g[i] = bn_ld<V>(pg + o);
-            y[i] = relu ? bn_ld<V>(py + o) : g[i];
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) bn_st<V>(po + (size_t)(r + i * st) * ld, f(x[i], g[i], y[i]));
-    }
-    for (; r < l.r1; r += st) {
-        const size_t o = (size_t)r * ld;
-        const Pack<V> g = bn_ld<V>(pg + o);
-        bn_st<V>(po + o, f(bn_ld<V>(px + o), g, relu ? bn_ld<V>(py + o) : g));
-    }
+                   for (int e = 0; e < V; ++e) {
+                       g.v[e] = bn_g<V, LUT>(b, e, relu, sTab, map);
+                       const float xh = ((b.p[0].v[e] - mean.v[e]) - lo.v[e]) * invstd.v[e];
+                       gx.v[e] = map.sc.v[e] * ((g.v[e] - mb.v[e]) - (xh * mg.v[e]));
+                   }
+                   bn_st<V>(po + o, gx);
+                   if constexpr (RES) {
+                       if (pq) bn_st<V>(pq + o, g);
+                   }
+               });
 }
 
 // The refusals both entry points share, in the order of include/slfp.h; *m receives N H W.
@@ -579,14 +520,107 @@ static int bn_check(const char* fn, int64_t n, int64_t h, int64_t w, int64_t c, 
     return SLFP_OK;
 }
 
-static BnArgs bn_args(const BnSplit& s, int64_t m, int64_t c, int relu, void* workspace) {
-    BnArgs a = {};
+// The geometry and workspace pointers of a launch, into the entry point's own pointers.  A gmean the entry point has set stays
+// (the table forward sends the finalize kernel's lo to the caller's save_lo; the apply reads it there).
+static void bn_geometry(BnArgs& a, const BnSplit& s, int64_t m, int64_t c, int relu, void* workspace) {
     a.m = m; a.c = c; a.rows = s.rows;
     a.slabs = (int)s.slabs; a.tx_log2 = s.tx_log2; a.relu = relu;
     a.rec = reinterpret_cast<float4*>(workspace);
     a.part = reinterpret_cast<float4*>(workspace);
-    a.gmean = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + bn_gmean_offset(s, c));
-    return a;
+    if (!a.gmean) a.gmean = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + bn_gmean_offset(s, c));
+}
+
+enum BnForm { kBnPlain, kBnTable, kBnRes };
+
+// The streaming kernels of a (vec, form); the residual form's statistics and reduce pass are the plain ones.
+using BnKernel = void (*)(BnArgs);
+struct BnKernels { BnKernel stats, apply, reduce, dx; };
+template <int V> static BnKernels bn_kernels(BnForm form) {
+    switch (form) {
+        case kBnTable: return {k_bn_stats<V>, k_bn_apply<V, true>, k_bn_bwd_reduce<V, true>, k_bn_bwd_dx<V, true>};
+        case kBnRes: return {k_bn_stats<V>, k_bn_apply<V, false, true>, k_bn_bwd_reduce<V>, k_bn_bwd_dx<V, false, true>};
+        default: return {k_bn_stats<V>, k_bn_apply<V>, k_bn_bwd_reduce<V>, k_bn_bwd_dx<V>};
+    }
+}
+static BnKernels bn_kernels(int vec, BnForm form) { return vec == 4 ? bn_kernels<4>(form) : bn_kernels<1>(form); }
+
+// The tail of every entry point's argument list.
+struct BnCall {
+    int64_t n, h, w, c;
+    int x_layout;
+    void* workspace;
+    size_t ws_bytes;
+    void* stream;
+};
+
+// A failed launch names the entry point, hence the form, and the pass.
+static int bn_launched(const char* fn, const char* pass) {
+    char what[96];
+    snprintf(what, sizeof what, "%s: slfp batch-norm %s kernel", fn, pass);
+    return check_launch(what);
+}
+
+// The forward of every form.  `a` holds the entry point's pointers (x, out, gamma, beta, res, table; gmean = save_lo in the
+// table form); `aliased` is the entry point's own aliasing refusal, or null.
+static int bn_forward(const char* fn, BnForm form, BnArgs a, float* running_mean, float* running_var, float momentum, float eps,
+                      int relu, float* save_mean, float* save_invstd, const BnCall& g, const char* aliased) {
+    a.mean = save_mean; a.invstd = save_invstd;
+    const void* big[] = {a.x, a.out, a.res};
+    const void* small[] = {a.gamma, a.beta, save_mean, save_invstd, a.gmean};
+    int64_t m = 0;
+    const int rc = bn_check(fn, g.n, g.h, g.w, g.c, g.x_layout, relu, big, form == kBnRes ? 3 : 2, small, form == kBnTable ? 5 : 4,
+                            g.workspace, g.ws_bytes, &m, form == kBnTable, a.table);
+    if (rc != SLFP_OK) return rc;
+    if ((running_mean == nullptr) != (running_var == nullptr))
+        return fail(SLFP_ERR_BAD_ARG, "%s: running_mean and running_var are given together or not at all", fn);
+    if ((reinterpret_cast<uintptr_t>(running_mean) | reinterpret_cast<uintptr_t>(running_var)) & 3)
+        return fail(SLFP_ERR_ALIGNMENT, "%s: the running statistics must be 4-byte aligned", fn);
+    if (aliased) return fail(SLFP_ERR_BAD_ARG, "%s: %s", fn, aliased);
+    if (m == 0) return SLFP_OK;
+    const BnSplit s = bn_split(m, g.c);
+    bn_geometry(a, s, m, g.c, relu, g.workspace);
+    const BnKernels k = bn_kernels(s.vec, form);
+    const dim3 grid((unsigned)s.slabs, (unsigned)s.tiles), block(kBnThreads);
+    const hipStream_t st = as_stream(g.stream);
+    hipLaunchKernelGGL(k.stats, grid, block, 0, st, a);
+    int e = bn_launched(fn, "statistics");
+    if (e != SLFP_OK) return e;
+    hipLaunchKernelGGL(k_bn_finalize, dim3((unsigned)ceil_div(g.c, kBnFinCh)), block, 0, st, a, running_mean, running_var, momentum,
+                       eps, save_mean, save_invstd);
+    e = bn_launched(fn, "finalize");
+    if (e != SLFP_OK) return e;
+    hipLaunchKernelGGL(k.apply, grid, block, 0, st, a);
+    return bn_launched(fn, "apply");
+}
+
+// The backward of every form.  `a` holds the entry point's pointers (x, y, gy, out, gamma, mean, invstd, gres; beta, lo_fwd and
+// table in the table form, whose y is x: it is never read); `misaligned` and `aliased` are the entry point's own refusals, or null.
+static int bn_backward(const char* fn, BnForm form, BnArgs a, int relu, float* ggamma, float* gbeta, const BnCall& g,
+                       const char* misaligned, const char* aliased) {
+    const void* big[] = {a.x, a.y, a.gy, a.out};
+    const void* small[] = {a.gamma, a.mean, a.invstd, a.beta, a.lo_fwd};
+    int64_t m = 0;
+    const int rc = bn_check(fn, g.n, g.h, g.w, g.c, g.x_layout, relu, big, 4, small, form == kBnTable ? 5 : 3, g.workspace,
+                            g.ws_bytes, &m, form == kBnTable, a.table);
+    if (rc != SLFP_OK) return rc;
+    if (misaligned) return fail(SLFP_ERR_ALIGNMENT, "%s: %s", fn, misaligned);
+    if ((reinterpret_cast<uintptr_t>(ggamma) | reinterpret_cast<uintptr_t>(gbeta)) & 3)
+        return fail(SLFP_ERR_ALIGNMENT, "%s: ggamma and gbeta must be 4-byte aligned", fn);
+    if (aliased) return fail(SLFP_ERR_BAD_ARG, "%s: %s", fn, aliased);
+    if (m == 0) return SLFP_OK;
+    const BnSplit s = bn_split(m, g.c);
+    bn_geometry(a, s, m, g.c, relu, g.workspace);
+    const BnKernels k = bn_kernels(s.vec, form);
+    const dim3 grid((unsigned)s.slabs, (unsigned)s.tiles), block(kBnThreads);
+    const hipStream_t st = as_stream(g.stream);
+    hipLaunchKernelGGL(k.reduce, grid, block, 0, st, a);
+    int e = bn_launched(fn, "backward reduce");
+    if (e != SLFP_OK) return e;
+    hipLaunchKernelGGL(k_bn_bwd_finalize, dim3((unsigned)ceil_div(g.c, kBnFinCh)), block, 0, st, a, ggamma, gbeta);
+    e = bn_launched(fn, "backward finalize");
+    if (e != SLFP_OK) return e;
+    hipLaunchKernelGGL(k.dx, grid, block, 0, st, a);
+    return bn_launched(fn, "backward dx");
 }
 
 }  // namespace slfp
@@ -616,186 +650,67 @@ int slfp_debug_bn_split(int64_t m, int64_t c, int64_t* rows_per_slab, int64_t* s
 int slfp_bn_train_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
                       float momentum, float eps, int relu, float* y, float* save_mean, float* save_invstd, int64_t n, int64_t h,
                       int64_t w, int64_t c, int x_layout, void* workspace, size_t ws_bytes, void* stream) {
-    const char* fn = "slfp_bn_train_fwd";
-    const void* big[] = {x, y};
-    const void* small[] = {gamma, beta, save_mean, save_invstd};
-    int64_t m = 0;
-    const int rc = bn_check(fn, n, h, w, c, x_layout, relu, big, 2, small, 4, workspace, ws_bytes, &m);
-    if (rc != SLFP_OK) return rc;
-    if ((running_mean == nullptr) != (running_var == nullptr))
-        return fail(SLFP_ERR_BAD_ARG, "%s: running_mean and running_var are given together or not at all", fn);
-    if ((reinterpret_cast<uintptr_t>(running_mean) | reinterpret_cast<uintptr_t>(running_var)) & 3)
-        return fail(SLFP_ERR_ALIGNMENT, "%s: the running statistics must be 4-byte aligned", fn);
-    if (x == y) return fail(SLFP_ERR_BAD_ARG, "%s: y may not alias x (the backward reads both)", fn);
-    if (m == 0) return SLFP_OK;
-    const BnSplit s = bn_split(m, c);
-    BnArgs a = bn_args(s, m, c, relu, workspace);
-    a.x = x; a.out = y; a.gamma = gamma; a.beta = beta; a.mean = save_mean; a.invstd = save_invstd;
-    const dim3 grid((unsigned)s.slabs, (unsigned)s.tiles), block(kBnThreads);
-    const hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(s.vec == 4 ? k_bn_stats<4> : k_bn_stats<1>, grid, block, 0, st, a);
-    int e = check_launch("slfp batch-norm statistics kernel");
-    if (e != SLFP_OK) return e;
-    hipLaunchKernelGGL(k_bn_finalize, dim3((unsigned)ceil_div(c, kBnFinCh)), block, 0, st, a, running_mean, running_var, momentum,
-                       eps, save_mean, save_invstd);
-    e = check_launch("slfp batch-norm finalize kernel");
-    if (e != SLFP_OK) return e;
-    hipLaunchKernelGGL(s.vec == 4 ? k_bn_apply<4> : k_bn_apply<1>, grid, block, 0, st, a);
-    return check_launch("slfp batch-norm apply kernel");
+    BnArgs a = {};
+    a.x = x; a.out = y; a.gamma = gamma; a.beta = beta;
+    return bn_forward("slfp_bn_train_fwd", kBnPlain, a, running_mean, running_var, momentum, eps, relu, save_mean, save_invstd,
+                      {n, h, w, c, x_layout, workspace, ws_bytes, stream},
+                      x == y ? "y may not alias x (the backward reads both)" : nullptr);
 }
 
 int slfp_bn_train_bwd(const float* x, const float* y, const float* gy, const float* gamma, const float* save_mean,
                       const float* save_invstd, int relu, float* gx, float* ggamma, float* gbeta, int64_t n, int64_t h, int64_t w,
                       int64_t c, int x_layout, void* workspace, size_t ws_bytes, void* stream) {
-    const char* fn = "slfp_bn_train_bwd";
-    const void* big[] = {x, y, gy, gx};
-    const void* small[] = {gamma, save_mean, save_invstd};
-    int64_t m = 0;
-    const int rc = bn_check(fn, n, h, w, c, x_layout, relu, big, 4, small, 3, workspace, ws_bytes, &m);
-    if (rc != SLFP_OK) return rc;
-    if ((reinterpret_cast<uintptr_t>(ggamma) | reinterpret_cast<uintptr_t>(gbeta)) & 3)
-        return fail(SLFP_ERR_ALIGNMENT, "%s: ggamma and gbeta must be 4-byte aligned", fn);
-    if (gx == x || gx == y) return fail(SLFP_ERR_BAD_ARG, "%s: gx may not alias x or y", fn);
-    if (m == 0) return SLFP_OK;
-    const BnSplit s = bn_split(m, c);
-    BnArgs a = bn_args(s, m, c, relu, workspace);
+    BnArgs a = {};
     a.x = x; a.y = y; a.gy = gy; a.out = gx; a.gamma = gamma; a.mean = save_mean; a.invstd = save_invstd;
-    const dim3 grid((unsigned)s.slabs, (unsigned)s.tiles), block(kBnThreads);
-    const hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(s.vec == 4 ? k_bn_bwd_reduce<4> : k_bn_bwd_reduce<1>, grid, block, 0, st, a);
-    int e = check_launch("slfp batch-norm backward reduce kernel");
-    if (e != SLFP_OK) return e;
-    hipLaunchKernelGGL(k_bn_bwd_finalize, dim3((unsigned)ceil_div(c, kBnFinCh)), block, 0, st, a, ggamma, gbeta);
-    e = check_launch("slfp batch-norm backward finalize kernel");
-    if (e != SLFP_OK) return e;
-    hipLaunchKernelGGL(s.vec == 4 ? k_bn_bwd_dx<4> : k_bn_bwd_dx<1>, grid, block, 0, st, a);
-    return check_launch("slfp batch-norm backward dx kernel");
+    return bn_backward("slfp_bn_train_bwd", kBnPlain, a, relu, ggamma, gbeta, {n, h, w, c, x_layout, workspace, ws_bytes, stream},
+                       nullptr, gx == x || gx == y ? "gx may not alias x or y" : nullptr);
 }
 
 int slfp_bn_res_train_fwd(const float* x, const float* res, const float* gamma, const float* beta, float* running_mean,
                           float* running_var, float momentum, float eps, int relu, float* y, float* save_mean, float* save_invstd,
                           int64_t n, int64_t h, int64_t w, int64_t c, int x_layout, void* workspace, size_t ws_bytes, void* stream) {
-    const char* fn = "slfp_bn_res_train_fwd";
-    const void* big[] = {x, res, y};
-    const void* small[] = {gamma, beta, save_mean, save_invstd};
-    int64_t m = 0;
-    const int rc = bn_check(fn, n, h, w, c, x_layout, relu, big, 3, small, 4, workspace, ws_bytes, &m);
-    if (rc != SLFP_OK) return rc;
-    if ((running_mean == nullptr) != (running_var == nullptr))
-        return fail(SLFP_ERR_BAD_ARG, "%s: running_mean and running_var are given together or not at all", fn);
-    if ((reinterpret_cast<uintptr_t>(running_mean) | reinterpret_cast<uintptr_t>(running_var)) & 3)
-        return fail(SLFP_ERR_ALIGNMENT, "%s: the running statistics must be 4-byte aligned", fn);
-    if (y == x || y == res) return fail(SLFP_ERR_BAD_ARG, "%s: y may alias neither x nor res (the backward reads x and y)", fn);
-    if (m == 0) return SLFP_OK;
-    const BnSplit s = bn_split(m, c);
-    BnArgs a = bn_args(s, m, c, relu, workspace);
-    a.x = x; a.res = res; a.out = y; a.gamma = gamma; a.beta = beta; a.mean = save_mean; a.invstd = save_invstd;
-    const dim3 grid((unsigned)s.slabs, (unsigned)s.tiles), block(kBnThreads);
-    const hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(s.vec == 4 ? k_bn_stats<4> : k_bn_stats<1>, grid, block, 0, st, a);
-    int e = check_launch("slfp batch-norm statistics kernel");
-    if (e != SLFP_OK) return e;
-    hipLaunchKernelGGL(k_bn_finalize, dim3((unsigned)ceil_div(c, kBnFinCh)), block, 0, st, a, running_mean, running_var, momentum,
-                       eps, save_mean, save_invstd);
-    e = check_launch("slfp batch-norm finalize kernel");
-    if (e != SLFP_OK) return e;
-    hipLaunchKernelGGL((s.vec == 4 ? k_bn_apply<4, false, true> : k_bn_apply<1, false, true>), grid, block, 0, st, a);
-    return check_launch("slfp batch-norm residual apply kernel");
+    BnArgs a = {};
+    a.x = x; a.res = res; a.out = y; a.gamma = gamma; a.beta = beta;
+    return bn_forward("slfp_bn_res_train_fwd", kBnRes, a, running_mean, running_var, momentum, eps, relu, save_mean, save_invstd,
+                      {n, h, w, c, x_layout, workspace, ws_bytes, stream},
+                      y == x || y == res ? "y may alias neither x nor res (the backward reads x and y)" : nullptr);
 }
 
 int slfp_bn_res_train_bwd(const float* x, const float* y, const float* gy, const float* gamma, const float* save_mean,
                           const float* save_invstd, int relu, float* gx, float* gres, float* ggamma, float* gbeta, int64_t n,
                           int64_t h, int64_t w, int64_t c, int x_layout, void* workspace, size_t ws_bytes, void* stream) {
-    const char* fn = "slfp_bn_res_train_bwd";
-    const void* big[] = {x, y, gy, gx};
-    const void* small[] = {gamma, save_mean, save_invstd};
-    int64_t m = 0;
-    const int rc = bn_check(fn, n, h, w, c, x_layout, relu, big, 4, small, 3, workspace, ws_bytes, &m);
-    if (rc != SLFP_OK) return rc;
-    if (reinterpret_cast<uintptr_t>(gres) & (c % 4 == 0 ? 15 : 3))
-        return fail(SLFP_ERR_ALIGNMENT, "%s: gres must be %d-byte aligned", fn, c % 4 == 0 ? 16 : 4);
-    if ((reinterpret_cast<uintptr_t>(ggamma) | reinterpret_cast<uintptr_t>(gbeta)) & 3)
-        return fail(SLFP_ERR_ALIGNMENT, "%s: ggamma and gbeta must be 4-byte aligned", fn);
-    if (gx == x || gx == y || gx == gy) return fail(SLFP_ERR_BAD_ARG, "%s: gx may not alias x, y or gy", fn);
-    if (gres && (gres == x || gres == y || gres == gy || gres == gx))
-        return fail(SLFP_ERR_BAD_ARG, "%s: gres may not alias x, y, gy or gx", fn);
-    if (m == 0) return SLFP_OK;
-    const BnSplit s = bn_split(m, c);
-    BnArgs a = bn_args(s, m, c, relu, workspace);
+    BnArgs a = {};
     a.x = x; a.y = y; a.gy = gy; a.out = gx; a.gres = gres; a.gamma = gamma; a.mean = save_mean; a.invstd = save_invstd;
-    const dim3 grid((unsigned)s.slabs, (unsigned)s.tiles), block(kBnThreads);
-    const hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(s.vec == 4 ? k_bn_bwd_reduce<4> : k_bn_bwd_reduce<1>, grid, block, 0, st, a);
-    int e = check_launch("slfp batch-norm backward reduce kernel");
-    if (e != SLFP_OK) return e;
-    hipLaunchKernelGGL(k_bn_bwd_finalize, dim3((unsigned)ceil_div(c, kBnFinCh)), block, 0, st, a, ggamma, gbeta);
-    e = check_launch("slfp batch-norm backward finalize kernel");
-    if (e != SLFP_OK) return e;
-    hipLaunchKernelGGL((s.vec == 4 ? k_bn_bwd_dx<4, false, true> : k_bn_bwd_dx<1, false, true>), grid, block, 0, st, a);
-    return check_launch("slfp batch-norm residual backward dx kernel");
+    const char* misaligned = nullptr;
+    if (reinterpret_cast<uintptr_t>(gres) & (c % 4 == 0 ? 15 : 3))
+        misaligned = c % 4 == 0 ? "gres must be 16-byte aligned" : "gres must be 4-byte aligned";
+    const char* aliased = nullptr;
+    if (gx == x || gx == y || gx == gy) aliased = "gx may not alias x, y or gy";
+    else if (gres && (gres == x || gres == y || gres == gy || gres == gx)) aliased = "gres may not alias x, y, gy or gx";
+    return bn_backward("slfp_bn_res_train_bwd", kBnRes, a, relu, ggamma, gbeta, {n, h, w, c, x_layout, workspace, ws_bytes, stream},
+                       misaligned, aliased);
 }
 
 int slfp_bn_lut_train_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
                           float momentum, float eps, const float* act_table, float* y, float* save_mean, float* save_invstd,
                           float* save_lo, int64_t n, int64_t h, int64_t w, int64_t c, int x_layout, void* workspace,
                           size_t ws_bytes, void* stream) {
-    const char* fn = "slfp_bn_lut_train_fwd";
-    const void* big[] = {x, y};
-    const void* small[] = {gamma, beta, save_mean, save_invstd, save_lo};
-    int64_t m = 0;
-    const int rc = bn_check(fn, n, h, w, c, x_layout, 0, big, 2, small, 5, workspace, ws_bytes, &m, true, act_table);
-    if (rc != SLFP_OK) return rc;
-    if ((running_mean == nullptr) != (running_var == nullptr))
-        return fail(SLFP_ERR_BAD_ARG, "%s: running_mean and running_var are given together or not at all", fn);
-    if ((reinterpret_cast<uintptr_t>(running_mean) | reinterpret_cast<uintptr_t>(running_var)) & 3)
-        return fail(SLFP_ERR_ALIGNMENT, "%s: the running statistics must be 4-byte aligned", fn);
-    if (x == y) return fail(SLFP_ERR_BAD_ARG, "%s: y may not alias x (the backward reads x)", fn);
-    if (m == 0) return SLFP_OK;
-    const BnSplit s = bn_split(m, c);
-    BnArgs a = bn_args(s, m, c, 0, workspace);
-    a.x = x; a.out = y; a.gamma = gamma; a.beta = beta; a.mean = save_mean; a.invstd = save_invstd; a.table = act_table;
+    BnArgs a = {};
+    a.x = x; a.out = y; a.gamma = gamma; a.beta = beta; a.table = act_table;
     a.gmean = save_lo;   // the finalize kernel's lo goes to the caller instead of the workspace; the apply reads it there
-    const dim3 grid((unsigned)s.slabs, (unsigned)s.tiles), block(kBnThreads);
-    const hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(s.vec == 4 ? k_bn_stats<4> : k_bn_stats<1>, grid, block, 0, st, a);
-    int e = check_launch("slfp batch-norm statistics kernel");
-    if (e != SLFP_OK) return e;
-    hipLaunchKernelGGL(k_bn_finalize, dim3((unsigned)ceil_div(c, kBnFinCh)), block, 0, st, a, running_mean, running_var, momentum,
-                       eps, save_mean, save_invstd);
-    e = check_launch("slfp batch-norm finalize kernel");
-    if (e != SLFP_OK) return e;
-    hipLaunchKernelGGL((s.vec == 4 ? k_bn_apply<4, true> : k_bn_apply<1, true>), grid, block, 0, st, a);
-    return check_launch("slfp batch-norm table apply kernel");
+    return bn_forward("slfp_bn_lut_train_fwd", kBnTable, a, running_mean, running_var, momentum, eps, 0, save_mean, save_invstd,
+                      {n, h, w, c, x_layout, workspace, ws_bytes, stream}, x == y ? "y may not alias x (the backward reads x)" : nullptr);
 }
 
 int slfp_bn_lut_train_bwd(const float* x, const float* gy, const float* gamma, const float* beta, const float* save_mean,
                           const float* save_invstd, const float* save_lo, const float* dact_table, float* gx, float* ggamma,
                           float* gbeta, int64_t n, int64_t h, int64_t w, int64_t c, int x_layout, void* workspace,
                           size_t ws_bytes, void* stream) {
-    const char* fn = "slfp_bn_lut_train_bwd";
-    const void* big[] = {x, gy, gx};
-    const void* small[] = {gamma, beta, save_mean, save_invstd, save_lo};
-    int64_t m = 0;
-    const int rc = bn_check(fn, n, h, w, c, x_layout, 0, big, 3, small, 5, workspace, ws_bytes, &m, true, dact_table);
-    if (rc != SLFP_OK) return rc;
-    if ((reinterpret_cast<uintptr_t>(ggamma) | reinterpret_cast<uintptr_t>(gbeta)) & 3)
-        return fail(SLFP_ERR_ALIGNMENT, "%s: ggamma and gbeta must be 4-byte aligned", fn);
-    if (gx == x) return fail(SLFP_ERR_BAD_ARG, "%s: gx may not alias x", fn);
-    if (m == 0) return SLFP_OK;
-    const BnSplit s = bn_split(m, c);
-    BnArgs a = bn_args(s, m, c, 0, workspace);
+    BnArgs a = {};
     a.x = x; a.y = x; a.gy = gy; a.out = gx; a.gamma = gamma; a.beta = beta; a.mean = save_mean; a.invstd = save_invstd;
     a.lo_fwd = save_lo; a.table = dact_table;
-    const dim3 grid((unsigned)s.slabs, (unsigned)s.tiles), block(kBnThreads);
-    const hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL((s.vec == 4 ? k_bn_bwd_reduce<4, true> : k_bn_bwd_reduce<1, true>), grid, block, 0, st, a);
-    int e = check_launch("slfp batch-norm table backward reduce kernel");
-    if (e != SLFP_OK) return e;
-    hipLaunchKernelGGL(k_bn_bwd_finalize, dim3((unsigned)ceil_div(c, kBnFinCh)), block, 0, st, a, ggamma, gbeta);
-    e = check_launch("slfp batch-norm backward finalize kernel");
-    if (e != SLFP_OK) return e;
-    hipLaunchKernelGGL((s.vec == 4 ? k_bn_bwd_dx<4, true> : k_bn_bwd_dx<1, true>), grid, block, 0, st, a);
-    return check_launch("slfp batch-norm table backward dx kernel");
+    return bn_backward("slfp_bn_lut_train_bwd", kBnTable, a, 0, ggamma, gbeta, {n, h, w, c, x_layout, workspace, ws_bytes, stream},
+                       nullptr, gx == x ? "gx may not alias x" : nullptr);
 }
 
 }  // extern "C"

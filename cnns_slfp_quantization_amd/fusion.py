@@ -1946,25 +1946,13 @@ def unlink_pool_head(model):
 _BN_NAMES = ("running_mean", "running_var", "num_batches_tracked")
 
 
-class TrainBatchNorm2d(nn.Module):
-    """An affine nn.BatchNorm2d (momentum not None) whose training-mode forward and backward run on libslfp_hip's kernels
-    (slfp_bn_train_fwd / slfp_bn_train_bwd, DESIGN section 27), with the nn.ReLU behind it folded in (`_relu`).  It registers the
-    SAME Parameter and buffer objects under the same names, so state-dict keys do not change and an optimizer built before the swap
-    keeps working; the original module is kept outside _modules (`_bn`).  Deliberately not a subclass of nn.BatchNorm2d: the
-    eval-mode passes (fuse_bn_relu, fuse_named_bn) match by isinstance and so never fold a BN whose ReLU lives inside it.
-    The kernels run in training mode on a ROCm float32 4-d channels_last tensor that slfp_bn_train_supported accepts and that
-    has at least `min_elements` elements (None: batchnorm.MIN_ELEMENTS, below which the stock modules measured no slower); eval
-    mode, CPU tensors, autocast, other dtypes or layouts, smaller tensors and a module without running-statistics buffers go to
-    F.batch_norm with the same buffers (then relu, if folded), which is what the stock modules compute.  The output is saved
-    for the backward only with a folded ReLU; without one it may be changed in place behind the module (`out += identity`, a
-    shared in-place ReLU), as behind the stock module.
-    A block's forward may ask more of one call (use_device_bottleneck_train): forward(x, relu=True) applies a ReLU the module does
-    not own, forward(x, residual=identity, relu=True) the tail of a Bottleneck on slfp_bn_res_train_fwd / _bwd (DESIGN section 33);
-    where the kernels do not run, that call computes F.batch_norm, `+= residual`, relu with ATen as the stock block does.
-      _last_kernel   "bn_train[+relu]", "bn_res_train[+relu]", or "aten" """
+class _DeviceBatchNorm(nn.Module):
+    """What TrainBatchNorm2d and TrainBatchNormLayerout2d share: the stock nn.BatchNorm2d's attributes and the SAME Parameter and
+    buffer objects under the same names (the stock module itself is kept outside _modules, `_bn`), the num_batches_tracked tick,
+    the rule for when the kernels may run, and the F.batch_norm path on the same buffers for everything else."""
     _version = 2   # nn.BatchNorm2d's state-dict version (num_batches_tracked)
 
-    def __init__(self, bn, min_elements=None):
+    def __init__(self, bn, min_elements):
         super().__init__()
         object.__setattr__(self, "_bn", bn)
         self.min_elements = min_elements
@@ -1975,8 +1963,58 @@ class TrainBatchNorm2d(nn.Module):
         self.register_parameter("bias", bn.bias)
         for name in _BN_NAMES:
             self.register_buffer(name, getattr(bn, name))
-        self._relu = False
         self._last_kernel = None
+
+    def _begin(self, x):
+        """What every call does first: the stock module's refusal of a non-4-d input, and its num_batches_tracked tick."""
+        if x.dim() != 4:
+            raise ValueError(f"expected 4D input (got {x.dim()}D input)")
+        if self.training and self.track_running_stats and self.num_batches_tracked is not None:
+            self.num_batches_tracked.add_(1)
+
+    def _kernel_operands(self, x, min_elements):
+        """(weight, bias, running_mean, running_var) where the kernels may run this call, else None.  They may in training mode,
+        without autocast, on a ROCm float32 tensor batchnorm.bn_train_supported accepts at this size rule, with these four
+        float32 on its device: the kernels are handed their addresses and read and write float32 there."""
+        from .batchnorm import bn_train_supported
+        if not (self.training and x.is_cuda and x.dtype == torch.float32) or torch.is_autocast_enabled():
+            return None
+        ops = (self.weight, self.bias, self.running_mean, self.running_var)
+        for t in ops:
+            if t is None or t.dtype != torch.float32 or t.device != x.device:
+                return None
+        return ops if bn_train_supported(x, min_elements) else None
+
+    def _aten(self, x):
+        """F.batch_norm as the stock module calls it, on the same parameters and buffers."""
+        self._last_kernel = "aten"
+        stats = self.training or (self.running_mean is None and self.running_var is None)
+        keep = not self.training or self.track_running_stats
+        return torch.nn.functional.batch_norm(x, self.running_mean if keep else None, self.running_var if keep else None,
+                                              self.weight, self.bias, stats, self.momentum, self.eps)
+
+
+class TrainBatchNorm2d(_DeviceBatchNorm):
+    """An affine nn.BatchNorm2d (momentum not None) whose training-mode forward and backward run on libslfp_hip's kernels
+    (slfp_bn_train_fwd / slfp_bn_train_bwd, DESIGN section 27), with the nn.ReLU behind it folded in (`_relu`).  It registers the
+    SAME Parameter and buffer objects under the same names, so state-dict keys do not change and an optimizer built before the swap
+    keeps working; the original module is kept outside _modules (`_bn`).  Deliberately not a subclass of nn.BatchNorm2d: the
+    eval-mode passes (fuse_bn_relu, fuse_named_bn) match by isinstance and so never fold a BN whose ReLU lives inside it.
+    The kernels run in training mode on a ROCm float32 4-d channels_last tensor that slfp_bn_train_supported accepts and that
+    has at least `min_elements` elements (None: batchnorm.MIN_ELEMENTS, below which the stock modules measured no slower), with
+    weight, bias and the running statistics float32 on its device; eval mode, CPU tensors, autocast, other dtypes or layouts,
+    smaller tensors, parameters or buffers of another dtype or device and a module without running-statistics buffers go to
+    F.batch_norm with the same buffers (then relu, if folded), which is what the stock modules compute.  The output is saved
+    for the backward only with a folded ReLU; without one it may be changed in place behind the module (`out += identity`, a
+    shared in-place ReLU), as behind the stock module.
+    A block's forward may ask more of one call (use_device_bottleneck_train): forward(x, relu=True) applies a ReLU the module does
+    not own, forward(x, residual=identity, relu=True) the tail of a Bottleneck on slfp_bn_res_train_fwd / _bwd (DESIGN section 33);
+    where the kernels do not run, that call computes F.batch_norm, `+= residual`, relu with ATen as the stock block does.
+      _last_kernel   "bn_train[+relu]", "bn_res_train[+relu]", or "aten" """
+
+    def __init__(self, bn, min_elements=None):
+        super().__init__(bn, min_elements)
+        self._relu = False
 
     def extra_repr(self):
         return f"{self.num_features}, eps={self.eps}, momentum={self.momentum}, relu={self._relu}"
@@ -1986,35 +2024,22 @@ class TrainBatchNorm2d(nn.Module):
         (use_device_bottleneck_train).  residual: a tensor of x's shape added behind the affine map and in front of the ReLU, the
         `out += identity` of a Bottleneck; on the kernels it is slfp_bn_res_train_fwd / _bwd, under a size
         rule of its own (batchnorm.RES_MIN_ELEMENTS where min_elements is None)."""
-        from .batchnorm import hip_bn_train, hip_bn_res_train, bn_train_supported, RES_MIN_ELEMENTS
-        if x.dim() != 4:
-            raise ValueError(f"expected 4D input (got {x.dim()}D input)")
+        from .batchnorm import hip_bn_train, hip_bn_res_train, MIN_ELEMENTS, RES_MIN_ELEMENTS
+        self._begin(x)
         relu = self._relu if relu is None else bool(relu)
-        if self.training and self.track_running_stats and self.num_batches_tracked is not None:
-            self.num_batches_tracked.add_(1)
         floor = self.min_elements
-        if residual is not None:
-            if floor is None:
-                floor = RES_MIN_ELEMENTS
-            on_kernels = (torch.is_tensor(residual) and residual.shape == x.shape and residual.dtype == x.dtype
-                          and residual.device == x.device)
-        else:
-            on_kernels = True
-        if (on_kernels and self.training and self.running_mean is not None and self.running_var is not None and x.is_cuda
-                and x.dtype == torch.float32 and self.weight.dtype == torch.float32 and not torch.is_autocast_enabled()
-                and bn_train_supported(x, floor)):
+        if floor is None:
+            floor = MIN_ELEMENTS if residual is None else RES_MIN_ELEMENTS
+        fits = residual is None or (torch.is_tensor(residual) and residual.shape == x.shape and residual.dtype == x.dtype
+                                    and residual.device == x.device)
+        ops = self._kernel_operands(x, floor) if fits else None
+        if ops is not None:
             if residual is not None:
                 self._last_kernel = "bn_res_train+relu" if relu else "bn_res_train"
-                return hip_bn_res_train.apply(x, residual, self.weight, self.bias, self.running_mean, self.running_var,
-                                              self.momentum, self.eps, relu)
+                return hip_bn_res_train.apply(x, residual, *ops, self.momentum, self.eps, relu)
             self._last_kernel = "bn_train+relu" if relu else "bn_train"
-            return hip_bn_train.apply(x, self.weight, self.bias, self.running_mean, self.running_var, self.momentum, self.eps,
-                                      relu)
-        self._last_kernel = "aten"
-        stats = self.training or (self.running_mean is None and self.running_var is None)
-        keep = not self.training or self.track_running_stats
-        y = torch.nn.functional.batch_norm(x, self.running_mean if keep else None, self.running_var if keep else None, self.weight,
-                                           self.bias, stats, self.momentum, self.eps)
+            return hip_bn_train.apply(x, *ops, self.momentum, self.eps, relu)
+        y = self._aten(x)
         if residual is not None:
             y += residual   # the stock block's own statements: out = bn3(out); out += identity; out = relu(out)
         return torch.relu(y) if relu else y
@@ -2067,16 +2092,10 @@ def restore_bn_train(model):
     for parent in list(model.modules()):
         for name, child in list(parent._modules.items()):
             if isinstance(child, TrainBatchNorm2d):
-                bn = child._bn
                 if id(child) not in seen:
                     seen.add(id(child))
                     n += 1
-                    for key in ("weight", "bias"):
-                        bn._parameters[key] = child._parameters[key]
-                    for key in _BN_NAMES:
-                        bn._buffers[key] = child._buffers[key]
-                    bn.training = child.training
-                parent._modules[name] = bn
+                parent._modules[name] = _repoint_bn(child)
             elif isinstance(child, FoldedReLU) and getattr(child, "_bn_train", False):
                 parent._modules[name] = child.relu
     return n
@@ -2110,7 +2129,8 @@ def _bn_bottleneck_candidate(blk):
 
 
 def _repoint_bn(wrap):
-    """The stock module of a TrainBatchNorm2d, pointed at the wrapper's current parameters, buffers and training flag."""
+    """The stock module of a TrainBatchNorm2d or TrainBatchNormLayerout2d, pointed at the wrapper's current parameters, buffers and
+    training flag (a move or a cast since the swap replaced them on the wrapper alone: its stock module sits outside _modules)."""
     bn = wrap._bn
     for key in ("weight", "bias"):
         bn._parameters[key] = wrap._parameters[key]
@@ -2220,7 +2240,7 @@ class FoldedTail(nn.Module):
         return x
 
 
-class TrainBatchNormLayerout2d(nn.Module):
+class TrainBatchNormLayerout2d(_DeviceBatchNorm):
     """The tail [BatchNorm2d, layerout_quantize_func(q_bit 7 or 8), activation(s)] of a training block of MobileNetV1_swish /
     VGG16_gelu on libslfp_hip's kernels (slfp_bn_lut_train_fwd / slfp_bn_lut_train_bwd): behind the quantizer a
     value is one of a few thousand classes, so the activation and its derivative are two float32 tables
@@ -2232,39 +2252,21 @@ class TrainBatchNormLayerout2d(nn.Module):
     run F.batch_norm on the same buffers, then the kept quantizer module, then the kept activation modules: bit for bit what the
     stock modules compute.  The output is never saved for the backward; it may be changed in place behind the module.
       _last_kernel   "bn_lut_train", or "aten" """
-    _version = 2   # nn.BatchNorm2d's state-dict version (num_batches_tracked)
 
     def __init__(self, bn, layerout, acts, min_elements=None):
-        super().__init__()
         from .batchnorm import _lut_act_types
         if isinstance(bn, TrainBatchNorm2d):
             if bn._relu:
                 raise ValueError("TrainBatchNormLayerout2d: the TrainBatchNorm2d has a ReLU folded in")
-            # The wrapper holds the current Parameters and buffers: a move or a cast since the swap (.cuda(), .double()) replaced
-            # them on it alone, its stock module sits outside _modules.  Re-point the stock module first, as restore_bn_train does.
-            wrap, bn = bn, bn._bn
-            for key in ("weight", "bias"):
-                bn._parameters[key] = wrap._parameters[key]
-            for key in _BN_NAMES:
-                bn._buffers[key] = wrap._buffers[key]
-            bn.training = wrap.training
+            bn = _repoint_bn(bn)   # the wrapper holds the current Parameters and buffers
         acts = tuple(acts)
         for act in acts:
             if type(act) not in _lut_act_types():
                 raise TypeError(f"TrainBatchNormLayerout2d: {type(act).__name__} has no derivative table")
-        object.__setattr__(self, "_bn", bn)
+        super().__init__(bn, min_elements)
         object.__setattr__(self, "_layerout", layerout)
         object.__setattr__(self, "_acts", acts)
-        self.min_elements = min_elements
-        self.training = bn.training
-        self.num_features, self.eps, self.momentum = bn.num_features, bn.eps, bn.momentum
-        self.affine, self.track_running_stats = bn.affine, bn.track_running_stats
-        self.register_parameter("weight", bn.weight)
-        self.register_parameter("bias", bn.bias)
-        for name in _BN_NAMES:
-            self.register_buffer(name, getattr(bn, name))
         self._tables = {}
-        self._last_kernel = None
 
     def extra_repr(self):
         return (f"{self.num_features}, eps={self.eps}, momentum={self.momentum}, layerout={self._layerout.q_bit}, "
@@ -2280,33 +2282,17 @@ class TrainBatchNormLayerout2d(nn.Module):
         return t
 
     def forward(self, x):
-        from .batchnorm import hip_bn_lut_train, bn_train_supported, LUT_MIN_ELEMENTS
-        if x.dim() != 4:
-            raise ValueError(f"expected 4D input (got {x.dim()}D input)")
-        if self.training and self.track_running_stats and self.num_batches_tracked is not None:
-            self.num_batches_tracked.add_(1)
-        if (self.training and self.running_mean is not None and self.running_var is not None and x.is_cuda
-                and x.dtype == torch.float32 and not torch.is_autocast_enabled()
-                and all(t.device == x.device and t.dtype == torch.float32   # the kernels are handed these addresses
-                        for t in (self.weight, self.bias, self.running_mean, self.running_var))
-                and bn_train_supported(x, LUT_MIN_ELEMENTS if self.min_elements is None else self.min_elements)):
-            ftab, dtab = self.tables(x.device)
+        from .batchnorm import hip_bn_lut_train, LUT_MIN_ELEMENTS
+        self._begin(x)
+        ops = self._kernel_operands(x, LUT_MIN_ELEMENTS if self.min_elements is None else self.min_elements)
+        if ops is not None:
             self._last_kernel = "bn_lut_train"
-            return hip_bn_lut_train.apply(x, self.weight, self.bias, self.running_mean, self.running_var, self.momentum, self.eps,
-                                          ftab, dtab)
-        self._last_kernel = "aten"
-        stats = self.training or (self.running_mean is None and self.running_var is None)
-        keep = not self.training or self.track_running_stats
-        y = torch.nn.functional.batch_norm(x, self.running_mean if keep else None, self.running_var if keep else None, self.weight,
-                                           self.bias, stats, self.momentum, self.eps)
+            return hip_bn_lut_train.apply(x, *ops, self.momentum, self.eps, *self.tables(x.device))
+        y = self._aten(x)
         y = self._layerout(y)
         for act in self._acts:
             y = act(y)
         return y
-
-
-def _bn_lut_candidate(m):
-    return _bn_wrappable(m)
 
 
 def use_device_bn_layerout_train(model, min_elements=None):
@@ -2325,7 +2311,7 @@ def use_device_bn_layerout_train(model, min_elements=None):
         names = list(seq._modules.keys())
         for i in range(len(names) - 2):
             bn, lo, act = (seq._modules[k] for k in names[i:i + 3])
-            if not (_bn_lut_candidate(bn) and _is_layerout(lo) and type(act) in _lut_act_types()):
+            if not (_bn_wrappable(bn) and _is_layerout(lo) and type(act) in _lut_act_types()):
                 continue
             if any(len(_slots_of(model, m)) != 1 for m in (bn, lo, act)):
                 continue
@@ -2344,13 +2330,7 @@ def restore_bn_layerout_train(model):
     for parent in list(model.modules()):
         for name, child in list(parent._modules.items()):
             if isinstance(child, TrainBatchNormLayerout2d):
-                bn = child._bn
-                for key in ("weight", "bias"):
-                    bn._parameters[key] = child._parameters[key]
-                for key in _BN_NAMES:
-                    bn._buffers[key] = child._buffers[key]
-                bn.training = child.training
-                parent._modules[name] = bn
+                parent._modules[name] = _repoint_bn(child)
                 n += 1
             elif isinstance(child, FoldedTail):
                 child.mod.training = child.training

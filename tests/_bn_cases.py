@@ -110,18 +110,79 @@ def var_bar_ok(got, var64, tol):
     return bool((np.abs(np.asarray(got, dtype=np.float64) - var64) <= tol * var64).all())
 
 
-def kernel_order_stats(x):
-    """(mean, biased var) as float64, summed in float32 in the kernel's order: V, TX, TY and the slabs as include/slfp.h states
-    them, lane partials from +0.0f over rows r0 + ty, r0 + ty + TY, ..., lanes added ty ascending, slabs by Chan in float64."""
-    n, c, h, w = x.shape
-    xr = x.permute(0, 2, 3, 1).reshape(-1, c).numpy()
-    m = xr.shape[0]
+def rows32(t):
+    """[M, C] float32 view of an (N, C, H, W) tensor's values, rows in NHWC order."""
+    return t.permute(0, 2, 3, 1).reshape(-1, t.shape[1]).numpy()
+
+
+def lane_rows(m, c):
+    """(R, S, TY) of include/slfp.h's split: S slabs of R rows, TY row lanes per slab."""
     r, s = split(m, c)
     groups = c // 4 if c % 4 == 0 else c
     tx = 1
     while tx < 64 and tx < groups:
         tx *= 2
-    ty = 256 // tx
+    return r, s, 256 // tx
+
+
+def kernel_order_forward(x, gamma, beta, save_mean, save_invstd, relu):
+    """y [M, C] float32 as include/slfp.h states the apply pass, from the device's save_mean and save_invstd (float32 arrays):
+    lo = f32(mean64 - f64(save_mean)) with kernel_order_stats' float64 mean, every other operation float32 and rounded on its own."""
+    f32 = np.float32
+    xr = rows32(x)
+    save_mean, save_invstd = np.asarray(save_mean, f32), np.asarray(save_invstd, f32)
+    lo = (kernel_order_stats(x)[0] - save_mean.astype(np.float64)).astype(f32)
+    sc = save_invstd * gamma.numpy()
+    y = (((xr - save_mean) - lo) * sc) + beta.numpy()
+    assert y.dtype == f32
+    return np.where(y < 0, f32(0), y) if relu else y   # a NaN and a -0.0 stay
+
+
+def kernel_order_backward(x, gy, y, gamma, save_mean, save_invstd, relu):
+    """(gx [M, C], ggamma, gbeta) float32 as include/slfp.h states the backward: lane partials of sg, sx, sd from +0.0f over rows
+    r0 + ty, r0 + ty + TY, ..., lanes added ty ascending in float32, slabs in float64 in slab order, the finalize step in float64
+    with its float32 roundings, then gx.  y is the forward's output [M, C] (the ReLU's mask; unused with relu false)."""
+    f32, f64 = np.float32, np.float64
+    xr, g = rows32(x), rows32(gy)
+    m, c = xr.shape
+    save_mean, save_invstd = np.asarray(save_mean, f32), np.asarray(save_invstd, f32)
+    if relu:
+        g = np.where(np.asarray(y, f32) > 0, g, f32(0))
+    d = xr - save_mean
+    terms = (g, g * (d * save_invstd), d)
+    r, s, ty = lane_rows(m, c)
+    tot = [np.zeros(c, f64) for _ in terms]   # SG, SX, SD
+    for j in range(s):
+        r0, r1 = j * r, min((j + 1) * r, m)
+        for t, term in zip(tot, terms):
+            lanes = np.zeros((ty, c), f32)
+            for i in range(r0, r1, ty):       # one row per lane at a time
+                k = min(ty, r1 - i)
+                lanes[:k] = lanes[:k] + term[i:i + k]
+            a = lanes[0].copy()
+            for q in range(1, ty):
+                a = a + lanes[q]
+            assert a.dtype == f32
+            t += a.astype(f64)
+    sg, sx, sd = tot
+    lo = sd / m
+    sx = sx - (lo * save_invstd.astype(f64)) * sg
+    gbeta, ggamma = sg.astype(f32), sx.astype(f32)
+    mb, mg, lo = (sg / m).astype(f32), (sx / m).astype(f32), lo.astype(f32)
+    a = gamma.numpy() * save_invstd
+    xh = ((xr - save_mean) - lo) * save_invstd
+    gx = a * ((g - mb) - (xh * mg))
+    assert gx.dtype == f32
+    return gx, ggamma, gbeta
+
+
+def kernel_order_stats(x):
+    """(mean, biased var) as float64, summed in float32 in the kernel's order: V, TX, TY and the slabs as include/slfp.h states
+    them, lane partials from +0.0f over rows r0 + ty, r0 + ty + TY, ..., lanes added ty ascending, slabs by Chan in float64."""
+    n, c, h, w = x.shape
+    xr = rows32(x)
+    m = xr.shape[0]
+    r, s, ty = lane_rows(m, c)
     f32 = np.float32
     cnt, mean, m2 = 0.0, np.zeros(c), np.zeros(c)
     for j in range(s):

@@ -14,6 +14,7 @@ import torch.nn.functional as F
 
 import _bn_cases as B
 from _bars import TOL_EXACT
+from _bn_calls import _bars_ok, _sum_bars_ok
 from cnns_slfp_quantization_amd import _lib, fusion
 from cnns_slfp_quantization_amd.sfp_quant import layerout_quantize_func
 
@@ -138,6 +139,30 @@ def test_inputs_hold_the_statistics_bars_on_the_cpu(case):
         xr = x.permute(0, 2, 3, 1).reshape(-1, shape[3])
         naive = (xr * xr).mean(dim=0) - xr.mean(dim=0) ** 2    # float32
         assert np.median(np.abs(naive.double().numpy() - var64) / var64) > 100 * TOL_EXACT
+
+
+@pytest.mark.parametrize("relu", [False, True], ids=["plain", "relu"])
+@pytest.mark.parametrize("case", B.cases(), ids=B.case_id)
+def test_kernel_order_model_holds_the_float64_bars_on_the_cpu(case, relu):
+    """The float32 NumPy model of the apply and backward orders (the GPU test compares the kernels with it bit for bit), fed its
+    own statistics and f32(1 / sqrt(var + eps)): y, gx, ggamma and gbeta hold the bars of test_gpu_bn_train.py against float64."""
+    shape, offset = case
+    d = B.inputs(shape, offset)
+    x, gamma, beta = d["x"], d["gamma"], d["beta"]
+    km, kv = B.kernel_order_stats(x)
+    sm, si = km.astype(np.float32), (1.0 / np.sqrt(kv + B.EPS)).astype(np.float32)
+    y = B.kernel_order_forward(x, gamma, beta, sm, si, relu)
+    y64 = B.forward64(x, gamma, beta, relu)[2]
+    centred = B.forward64(x, gamma, beta, False)[2] - beta.double().numpy() if offset else None
+    assert _bars_ok(y, y64, centred)
+    for key in ("gy", "gy_sparse"):
+        gx, gg, gb = B.kernel_order_backward(x, d[key], y, gamma, sm, si, relu)
+        g = B.rows(d[key])
+        if relu:
+            g = g * (y > 0)
+        gx64, gg64, gb64, agg, agb = B.backward64(x, g, gamma)
+        assert _sum_bars_ok("ggamma", gg, gg64, agg) and _sum_bars_ok("gbeta", gb, gb64, agb), key
+        assert _bars_ok(gx, gx64), key
 
 
 class _Block(nn.Module):

@@ -11,7 +11,7 @@ import torch.nn as nn
 import _bn_cases as B
 from _bars import TOL_EXACT
 from test_bn_layerout_train_host import CLOSED
-from test_gpu_bn_train import _bars_ok, _bwd as _plain_bwd, _fwd as _plain_fwd, _stream, _ws
+from _bn_calls import _bars_ok, _bits, _bwd as _plain_bwd, _fwd as _plain_fwd, _lut_bwd, _lut_fwd, _same, _stream
 from cnns_slfp_quantization_amd import _lib, activation_func as af, batchnorm, fusion
 from cnns_slfp_quantization_amd import conv2d_func as cf
 from cnns_slfp_quantization_amd import layer_specs
@@ -19,7 +19,6 @@ from cnns_slfp_quantization_amd.sfp_quant import layerout_quantize_func
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
-NHWC = _lib.LAYOUT_NHWC
 ACTS = {"relu": nn.ReLU, "swish": af.Swish, "gelu": nn.GELU}
 NT = _lib.LAYEROUT_TABLE_FLOATS
 _cache = {}
@@ -40,14 +39,6 @@ def _tables(name):
     return _cache[name]
 
 
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _same(a, b):
-    return a.shape == b.shape and torch.equal(_bits(a), _bits(b))
-
-
 def _quantize(t):
     q = torch.empty_like(t)
     _lib.check(_lib.load().slfp_quantize_layerout_f32(t.data_ptr(), q.data_ptr(), t.numel(), _stream()))
@@ -63,31 +54,6 @@ def _classes(q):
     hit = sbits[pos] == qb
     assert bool((hit | torch.isnan(q).flatten()).all()), "a value outside the quantizer's image"
     return torch.where(hit, order[pos] + 1, torch.zeros_like(pos)).view(q.shape)
-
-
-def _lut_fwd(shape, ftab, x, gamma, beta, rm=None, rv=None):
-    """slfp_bn_lut_train_fwd on the current stream: y, save_mean, save_invstd, save_lo (rm / rv updated in place)."""
-    n, h, w, c = shape
-    y = torch.empty_like(x)
-    sm, si, lo = (torch.empty(c, device=DEV) for _ in range(3))
-    ws, nbytes = _ws(shape)
-    _lib.check(_lib.load().slfp_bn_lut_train_fwd(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), rm.data_ptr() if rm is not None else None,
-                                                 rv.data_ptr() if rv is not None else None, B.MOMENTUM, B.EPS, ftab.data_ptr(),
-                                                 y.data_ptr(), sm.data_ptr(), si.data_ptr(), lo.data_ptr(), n, h, w, c, NHWC,
-                                                 ws.data_ptr(), nbytes, _stream()))
-    return y, sm, si, lo
-
-
-def _lut_bwd(shape, dtab, x, gy, gamma, beta, sm, si, lo, params=True):
-    n, h, w, c = shape
-    gx = torch.empty_like(x)
-    gg, gb = (torch.empty(c, device=DEV), torch.empty(c, device=DEV)) if params else (None, None)
-    ws, nbytes = _ws(shape)
-    _lib.check(_lib.load().slfp_bn_lut_train_bwd(x.data_ptr(), gy.data_ptr(), gamma.data_ptr(), beta.data_ptr(), sm.data_ptr(),
-                                                 si.data_ptr(), lo.data_ptr(), dtab.data_ptr(), gx.data_ptr(),
-                                                 gg.data_ptr() if params else None, gb.data_ptr() if params else None, n, h, w, c,
-                                                 NHWC, ws.data_ptr(), nbytes, _stream()))
-    return gx, gg, gb
 
 
 def _dev(d):

@@ -16,12 +16,11 @@ import torch.nn as nn
 import _bn_cases as B
 import _bn_res_blocks as R
 from _bars import TOL_EXACT
-from test_gpu_bn_train import _bars_ok, _bwd as _plain_bwd, _fwd as _plain_fwd, _stream, _ws
-from cnns_slfp_quantization_amd import _lib, batchnorm, fusion
+from _bn_calls import _bars_ok, _bits, _bwd as _plain_bwd, _fwd as _plain_fwd, _res_bwd, _res_fwd, _same
+from cnns_slfp_quantization_amd import batchnorm, fusion
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
-NHWC = _lib.LAYOUT_NHWC
 
 
 @functools.lru_cache(None)
@@ -30,45 +29,6 @@ def _res(shape):
     n, h, w, c = shape
     g = torch.Generator().manual_seed(2000 + sum(shape))
     return torch.randn(n, c, h, w, generator=g).contiguous(memory_format=torch.channels_last)
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _same(a, b):
-    return a.shape == b.shape and torch.equal(_bits(a), _bits(b))
-
-
-def _res_fwd(shape, d, relu, res, rm=None, rv=None, x=None):
-    """slfp_bn_res_train_fwd on the current stream: y, save_mean, save_invstd (rm / rv updated in place)."""
-    n, h, w, c = shape
-    x = d["x"].to(DEV) if x is None else x
-    gamma, beta = d["gamma"].to(DEV), d["beta"].to(DEV)
-    y = torch.empty_like(x)
-    sm, si = torch.empty(c, device=DEV), torch.empty(c, device=DEV)
-    ws, nbytes = _ws(shape)
-    _lib.check(_lib.load().slfp_bn_res_train_fwd(x.data_ptr(), res.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                                 rm.data_ptr() if rm is not None else None, rv.data_ptr() if rv is not None else None,
-                                                 B.MOMENTUM, B.EPS, int(relu), y.data_ptr(), sm.data_ptr(), si.data_ptr(), n, h, w, c,
-                                                 NHWC, ws.data_ptr(), nbytes, _stream()))
-    return y, sm, si
-
-
-def _res_bwd(shape, d, relu, y, sm, si, gy, gres=True, params=True, x=None):
-    """slfp_bn_res_train_bwd: gx, gres, ggamma, gbeta (None where not asked for)."""
-    n, h, w, c = shape
-    x = d["x"].to(DEV) if x is None else x
-    gamma, gy = d["gamma"].to(DEV), gy.to(DEV)
-    gx = torch.empty_like(x)
-    gr = torch.empty_like(x) if gres else None
-    gg, gb = (torch.empty(c, device=DEV), torch.empty(c, device=DEV)) if params else (None, None)
-    ws, nbytes = _ws(shape)
-    _lib.check(_lib.load().slfp_bn_res_train_bwd(x.data_ptr(), y.data_ptr(), gy.data_ptr(), gamma.data_ptr(), sm.data_ptr(),
-                                                 si.data_ptr(), int(relu), gx.data_ptr(), gr.data_ptr() if gres else None,
-                                                 gg.data_ptr() if params else None, gb.data_ptr() if params else None, n, h, w, c,
-                                                 NHWC, ws.data_ptr(), nbytes, _stream()))
-    return gx, gr, gg, gb
 
 
 @pytest.mark.parametrize("relu", [False, True], ids=["plain", "relu"])
