@@ -48,6 +48,8 @@ SYMBOLS = (
     "slfp_bn_lut_train_fwd", "slfp_bn_lut_train_bwd",
     "slfp_bn_res_train_fwd", "slfp_bn_res_train_bwd",
     "slfp_conv2d_codes_x3_supported", "slfp_conv2d_fwd_codes_x3", "slfp_debug_pwc_x3_variant",
+    "slfp_bn_codes_train_supported", "slfp_bn_codes_train_fwd", "slfp_bn_codes_train_bwd",
+    "slfp_conv2d_bwd_codes_supported", "slfp_conv2d_bwd_codes",
 )
 
 
@@ -152,6 +154,8 @@ def load():
         "slfp_conv2d_bwd_kernel_name_ex": (ctypes.c_char_p, [dp, ctypes.c_uint]),
         "slfp_conv2d_bwd_workspace_bytes_ex": (sz, [dp, ctypes.c_uint, ci, ci]),
         "slfp_conv2d_bwd_ex": (ci, [dp, ctypes.c_uint, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "slfp_conv2d_bwd_codes_supported": (ci, [dp, ctypes.c_uint]),
+        "slfp_conv2d_bwd_codes": (ci, [dp, ctypes.c_uint, vp, vp, vp, vp, vp, vp, vp, vp]),
         "slfp_conv2d_res_supported": (ci, [dp, ctypes.POINTER(ConvIo), ci, ci]),
         "slfp_conv2d_fwd_res": (ci, [dp, ctypes.POINTER(ConvIo), vp, vp, vp, vp, vp, ci, vp, vp, vp, vp]),
         "slfp_conv2d_codes_slice_supported": (ci, [dp, ctypes.POINTER(ConvIo), ci, ci, i64]),
@@ -184,6 +188,9 @@ def load():
         "slfp_bn_lut_train_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, ci, vp, sz, vp]),
         "slfp_bn_res_train_fwd": (ci, [vp, vp, vp, vp, vp, vp, cf, cf, ci, vp, vp, vp, i64, i64, i64, i64, ci, vp, sz, vp]),
         "slfp_bn_res_train_bwd": (ci, [vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, i64, i64, i64, i64, ci, vp, sz, vp]),
+        "slfp_bn_codes_train_supported": (ci, [i64, i64, i64, i64, ci, cf, ci]),
+        "slfp_bn_codes_train_fwd": (ci, [vp, vp, vp, vp, vp, cf, cf, ci, cf, ci, vp, vp, vp, vp, i64, i64, i64, i64, ci, vp, sz, vp]),
+        "slfp_bn_codes_train_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, i64, i64, i64, i64, ci, vp, sz, vp]),
         "slfp_debug_bn_split": (ci, [i64, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
         "slfp_debug_dwpw_instance": (ctypes.c_char_p, [dp, dp, ctypes.POINTER(ConvIo), ci, ci, ci]),
         "slfp_conv2d_u8_supported": (ci, [dp, ctypes.POINTER(ConvIo), ci, ci]),

@@ -1,6 +1,7 @@
 """Training-mode BatchNorm2d (+ReLU) on libslfp_hip's kernels (csrc/bn_train.hip; include/slfp.h states the order of every
 sum): the autograd Function behind fusion.TrainBatchNorm2d.  float32 channels_last tensors on the ROCm device only; there is no
-fallback in here -- the module decides with bn_train_supported() and otherwise runs ATen's batch_norm itself."""
+fallback in here -- the module decides with bn_train_supported() and otherwise runs ATen's batch_norm itself.  Also the residual,
+table and code forms of the same kernels, and the Function that spans BatchNorm -> ReLU -> Conv2d_Q on 1-byte codes."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -237,3 +238,97 @@ class hip_bn_lut_train(torch.autograd.Function):
         _call("slfp_bn_lut_train_bwd", x, x.data_ptr(), gy.data_ptr(), gamma.data_ptr(), beta.data_ptr(), save_mean.data_ptr(),
               save_invstd.data_ptr(), save_lo.data_ptr(), ctx.dtab.data_ptr(), gx.data_ptr(), _ptr(ggamma), _ptr(gbeta))
         return gx if ctx.needs_input_grad[0] else None, ggamma, gbeta, None, None, None, None, None, None
+
+
+# ---- BatchNorm2d (+ReLU) -> the next Conv2d_Q on 1-byte codes, in a training step (slfp_bn_codes_train_fwd / _bwd and
+# slfp_conv2d_bwd_codes) --------------------------------------------------------------------------------------
+# The size rule of the code form, by the spread rule of DESIGN sections 27 and 32: the smallest size class from which this class and
+# every larger measured one beat the better of the two unlinked legs (today's kernels, the stock modules) by more than that leg's
+# run-to-run spread.  Read from profiles/bn_codes_train_bench.json and its earlier run (MobileNetV1-224's 26 hand-over shapes at
+# batch 128, forward + backward of [BN, ReLU, Conv2d_Q], options.backward = "hip"; M = 2^20 elements of the BatchNorm's tensor):
+#   98 M, 49 M            every row ahead in both runs, 1.08-1.35x
+#   24.5 M                every row ahead in both runs: by only 1.01-1.12x in the earlier, by 1.11-1.25x in the later
+#   12.25 M               the stride-2 depthwise row lost in both runs (0.965x, 0.997x), a 1x1 row in one (0.861x)
+#   6.12 M                the 7x7 depthwise row lost to the stock modules in both (0.83x), a 1x1 row in one (0.965x)
+#   3.06 M                its one row ahead in both (1.05x), under failing classes
+# So hand-overs of fewer than 24 M elements stay float32 unless told otherwise (min_elements=0): of MobileNetV1-224's 26 at batch
+# 128 the default links 10.  The whole step was fastest with all 26 linked (12.3 ms against 13.6 with the default and 15.1 without):
+# DESIGN section 35.
+CODES_MIN_ELEMENTS = 24 << 20
+
+
+class TrainLink:
+    """What a TrainBatchNormCodes2d hands its Conv2d_Q next to the code tensor (as the tensor attribute `_train_link`): the BN's
+    input with its graph, the BN's operands, the three per-channel arrays the forward saved, and the quantizer the codes were
+    written for.  The conv takes it off the tensor before it stashes the codes: a finished step must not keep x alive."""
+    __slots__ = ("x", "weight", "bias", "save_mean", "save_invstd", "save_lo", "relu", "ka", "q_bit", "conv")
+
+    def __init__(self, x, weight, bias, saves, relu, ka, q_bit, conv):
+        self.x, self.weight, self.bias = x, weight, bias
+        self.save_mean, self.save_invstd, self.save_lo = saves
+        self.relu, self.ka, self.q_bit, self.conv = bool(relu), ka, q_bit, conv
+
+    def made_for(self, conv):
+        """Were the codes written for `conv`'s present quantizer?"""
+        return conv is self.conv and conv.q_bit == self.q_bit and float(np.float32(float(conv.Ka))) == self.ka
+
+
+def bn_codes_train_supported(x, ka, q_bit, min_elements=None):
+    """bn_train_supported under the code form's size rule (None: CODES_MIN_ELEMENTS, which may leave everything out), and
+    slfp_bn_codes_train_supported for the reader's quantizer (ka: float32(Ka) as a Python float)."""
+    floor = CODES_MIN_ELEMENTS if min_elements is None else min_elements
+    if floor is None or not bn_train_supported(x, floor):
+        return False
+    n, c, h, w = x.shape
+    return bool(_lib.load().slfp_bn_codes_train_supported(n, h, w, c, _lib.LAYOUT_NHWC, ka, int(q_bit)))
+
+
+def bn_codes_train_fwd(x, weight, bias, running_mean, running_var, momentum, eps, relu, ka, q_bit):
+    """slfp_bn_codes_train_fwd on a tensor bn_codes_train_supported accepts, without recording: (codes, save_mean, save_invstd,
+    save_lo), codes a uint8 channels_last tensor of x's shape holding relu?(batch_norm(x)) as the extended codes of QA(. / ka);
+    the running statistics are updated in place."""
+    x = x.detach()
+    gamma, beta = _vec(weight), _vec(bias)
+    codes = torch.empty(x.shape, dtype=torch.uint8, device=x.device, memory_format=torch.channels_last)
+    saves = [x.new_empty(x.shape[1]) for _ in range(3)]
+    _call("slfp_bn_codes_train_fwd", x, x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(running_mean), _ptr(running_var),
+          float(momentum), float(eps), 1 if relu else 0, float(ka), int(q_bit), codes.data_ptr(), *(t.data_ptr() for t in saves))
+    return (codes, *saves)
+
+
+class hip_bn_codes_conv_train(torch.autograd.Function):
+    """conv(relu?(batch_norm(x))) for a pair linked by fusion.link_codes_train, as ONE Function: autograd cannot carry a gradient
+    through the uint8 tensor between the two, and the float32 gradient between their backward kernels is a temporary.  The inputs
+    are the BN's x, weight and bias and the conv's weight and (scaled) bias; `codes` and `link` (TrainLink) are what the BN wrapper
+    produced already.  The forward runs the conv's code-reading forward with freshly prepared weights (never the cache: an
+    optimizer steps `.data` unseen); saved are x, the codes, the three per-channel arrays and the weights -- 5 bytes per element
+    where the unlinked pair saves x and y.  The backward runs slfp_conv2d_bwd_codes, then slfp_bn_codes_train_bwd on its gx."""
+
+    @staticmethod
+    def forward(ctx, x, bn_weight, bn_bias, weight, bias, conv, codes, link):
+        from .conv2d_func import _launch, _plan
+        plan = _plan(conv, codes, weight, True, True, ("codes", True, None, None))
+        if not plan.ok:
+            raise RuntimeError("hip_bn_codes_conv_train: no code-reading forward for this layer (slfp_conv2d_codes_supported)")
+        y = _launch(conv, plan, codes, weight, bias, cache=False)
+        ctx.conv, ctx.relu, ctx.has_bias = conv, link.relu, bias is not None
+        ctx.save_for_backward(x, codes, bn_weight, bn_bias, link.save_mean, link.save_invstd, link.save_lo, weight)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        from .conv2d_func import _conv_desc, _hip_backward_codes
+        x, codes, bn_weight, bn_bias, save_mean, save_invstd, save_lo, weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        need_bn = need[0] or need[1] or need[2]
+        gy = _nhwc(gy)
+        g, gw, gb = _hip_backward_codes(ctx.conv, _conv_desc(ctx.conv, codes.shape, True, True), codes, weight, gy,
+                                        (need_bn, need[3], ctx.has_bias and need[4]))
+        gx = ggamma = gbeta = None
+        if need_bn:
+            gamma, beta = _vec(bn_weight), _vec(bn_bias)
+            gx, ggamma, gbeta = _grads(ctx, x, save_mean, 1)
+            _call("slfp_bn_codes_train_bwd", x, x.data_ptr(), g.data_ptr(), gamma.data_ptr(), beta.data_ptr(), save_mean.data_ptr(),
+                  save_invstd.data_ptr(), save_lo.data_ptr(), 1 if ctx.relu else 0, gx.data_ptr(), _ptr(ggamma), _ptr(gbeta))
+        return gx if need[0] else None, ggamma, gbeta, gw, gb, None, None, None

@@ -624,6 +624,45 @@ def _hip_backward(mod, desc, x, w, gy, needs):
     return gx, gw if need_gw else None, gb
 
 
+def _bwd_flags():
+    """The `flags` word of slfp_conv2d_bwd_*_ex under options.backward, or None where it names no HIP backward ("composite")."""
+    return {"hip": 0, "hip_all": _lib.BWD_DENSE}.get(options.backward)
+
+
+def _bwd_codes_supported(mod, shape):
+    """Does slfp_conv2d_bwd_codes cover Conv2d_Q `mod` on a channels_last code tensor of `shape` under options.backward?"""
+    flags = _bwd_flags()
+    if flags is None:
+        return False
+    return bool(_lib.load().slfp_conv2d_bwd_codes_supported(ctypes.byref(_conv_desc(mod, shape, True, True)), flags))
+
+
+def _hip_backward_codes(mod, desc, codes, w, gy, needs):
+    """_hip_backward with the activation operand as the 1-byte codes the layer read in its forward (slfp_conv2d_bwd_codes; NHWC):
+    (gx, gw, gb) for needs = (gx, gw, gb wanted).  The caller has asked _bwd_codes_supported: a layer without the kernel is an
+    error here, not a fallback."""
+    L = _lib.load()
+    flags = _bwd_flags()
+    if flags is None or not L.slfp_conv2d_bwd_codes_supported(ctypes.byref(desc), flags):
+        raise RuntimeError("Conv2d_Q: no backward kernel reads this layer's codes under options.backward = "
+                           f"{options.backward!r} (slfp_conv2d_bwd_codes_supported); call fusion.unlink_codes_train(model)")
+    need_gx, need_gw, need_gb = needs
+    gy = _aligned(gy)
+    w = w.detach()
+    w = _aligned(w if w.is_contiguous() else w.contiguous())   # OIHW
+    run_gw = need_gw or need_gb
+    gx = torch.empty(codes.shape, dtype=torch.float32, device=codes.device, memory_format=torch.channels_last) if need_gx else None
+    gw = torch.empty(w.shape, dtype=torch.float32, device=codes.device) if run_gw else None
+    gb = torch.empty(desc.c_out, dtype=torch.float32, device=codes.device) if need_gb else None
+    with _on_device(codes.device):
+        nbytes = L.slfp_conv2d_bwd_workspace_bytes_ex(ctypes.byref(desc), flags, int(need_gx), int(run_gw))
+        ws = _workspace(codes.device, nbytes) if nbytes else None
+        _lib.check(L.slfp_conv2d_bwd_codes(ctypes.byref(desc), flags, codes.data_ptr(), w.data_ptr(), gy.data_ptr(), _ptr(gx), _ptr(gw),
+                                           _ptr(gb), _ptr(ws), torch.cuda.current_stream(codes.device).cuda_stream))
+    mod._last_bwd_kernel = L.slfp_conv2d_bwd_kernel_name_ex(ctypes.byref(desc), flags).decode()
+    return gx, gw if need_gw else None, gb
+
+
 def _needs(ctx):
     """(gx, gw, gb) wanted by autograd from a Function whose inputs start with (x, weight, bias)."""
     return ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
@@ -807,6 +846,24 @@ def _conv_class(q_bit, Kw, Ka, bias_default, scaled_bias):
             self.output = out
             return out
 
+        def _forward_train_link(self, codes, link):
+            from .batchnorm import hip_bn_codes_conv_train
+            del codes.__dict__["_train_link"]   # a finished step must not keep the BN's input alive through a stash
+            bias = self.bias if scaled_bias else None
+            need_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad
+                                                        for t in (link.x, link.weight, link.bias, self.weight, bias))
+            if need_grad:
+                out = hip_bn_codes_conv_train.apply(link.x, link.weight, link.bias, self.weight, bias, self, codes, link)
+            else:
+                plan = _plan(self, codes, self.weight, True, True, ("codes", True, None, None))
+                if not plan.ok:
+                    raise RuntimeError("Conv2d_Q: no code-reading forward for this layer (slfp_conv2d_codes_supported); "
+                                       "call fusion.unlink_codes_train(model)")
+                with torch.no_grad():
+                    out = _launch(self, plan, codes, self.weight, bias, cache=False)
+            self.output = out
+            return out
+
         def forward_slice(self, input, out_slice):
             """`out_slice=(buffer, c_off)`: a linked code producer writes its codes into buffer[:, c_off:c_off + C_out] (uint8,
             channels_last, wider than this layer) in ONE launch (slfp_conv2d_fwd_codes_slice; `_last_kernel` ends in "+slice")
@@ -841,6 +898,11 @@ def _conv_class(q_bit, Kw, Ka, bias_default, scaled_bias):
                 # a stem marked by fusion.link_image_u8: uint8 is pixels here, never codes
                 self.output = _hip_conv2d_u8(self, input, self.weight, self.bias if scaled_bias else None, order)
                 return self.output
+            link = input.__dict__.get("_train_link") if type(input) is torch.Tensor and input.dtype == torch.uint8 else None
+            if link is not None and self.training and self.q_bit in (8, 7) and link.made_for(self):
+                # the codes a fusion.TrainBatchNormCodes2d wrote for THIS module's present quantizer, in a training step: BN -> ReLU ->
+                # conv as one autograd Function (or the bare code forward where nothing records).  The record leaves the tensor first
+                return self._forward_train_link(input, link)
             tc = input.__dict__.get("_trunk_codes") if type(input) is torch.Tensor else None
             if tc is not None and not self.training and self.q_bit in (8, 7) and tc[1:] == (float(self.Ka), self.q_bit):
                 # the float32 trunk of a block linked by fusion.link_trunk carries the codes written for THIS module's present

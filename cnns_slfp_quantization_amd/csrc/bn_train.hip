@@ -40,13 +40,21 @@
 //   forward    t = the apply above with relu = 0;  z = t + res;  relu: y = z < 0 ? 0 : z  (a NaN stays a NaN)
 //   backward   g as above, the mask read from y;  gx as above;  gres = g, a second store of the dx pass (skipped when NULL)
 // The statistics, both finalize kernels and the reduce pass are the plain ones.
+// The code forms (k_bn_apply_codes; k_bn_bwd_reduce, k_bn_bwd_dx with XM = true; slfp_bn_codes_train_fwd / _bwd) hand y to the
+// next Conv2d_Q as the 1-byte extended codes of that layer's own quantizer (slfp_codes.hpp), C % 4 == 0:
+//   forward    t = the apply above (with its ReLU);  a lane's four channels go through enc4_code_relu (behind a ReLU) or
+//              enc4_code_fmt<FMT, true> on the reader's kEncCode table in LDS and leave as one dword;  lo goes to save_lo
+//   backward   the ReLU's mask is t > 0 with t recomputed from x through bn_affine (y > 0 exactly where t > 0): no forward output
+//              is read;  the rest as the plain form
 // The two finalize kernels stage the records of 256 slabs x 8 channels in LDS with all 256 lanes (and the per-slab weights
 // n_b / n and n_a n_b / n, which depend on the slab index alone), then one lane per channel runs the serial chain.
 // Each of these is written once: bn_walk is the lane's walk over its rows (all five streaming kernels), bn_affine the apply's
 // expression (the apply of every form, and through bn_class the backward's recomputed class), bn_g the g of one element
-// (reduce, dx and the gres store), bn_forward / bn_backward the refusals and the three launches of a direction; the six entry
+// (reduce, dx and the gres store), bn_forward / bn_backward the refusals and the three launches of a direction; the eight entry
 // points state their pointers and the refusals of their own form.
 #include "slfp_device.hpp"
+#include "slfp_enc.hpp"
+#include "slfp_codes.hpp"
 #include "slfp_host.hpp"
 #include "slfp_layerout_lut.hpp"
 
@@ -119,6 +127,8 @@ struct BnArgs {
     const float* table;    // LUT forms: act_table (forward) / dact_table (backward), kBnTableFloats floats
     const float* res;      // residual forward: the operand added behind the affine map
     float* gres;           // residual backward: the residual's gradient g, or null
+    uint8_t* codes;        // code forward: y as the reader's extended codes, [M][C] bytes
+    int code_fmt;          // code forward: kFmtAct8 | kFmtSfp7, the format of those codes
     int64_t m, c, rows;
     int slabs, tx_log2, relu;
 };
@@ -157,6 +167,18 @@ template <bool LUT> __device__ __forceinline__ const float* bn_table_lds(const f
             reinterpret_cast<float4*>(sTab)[i] = reinterpret_cast<const float4*>(g)[i];
         __syncthreads();
         return sTab;
+    } else {
+        return nullptr;
+    }
+}
+
+// Code forms: the workgroup's copy of the reader's kEncCode threshold table in LDS, published by the barrier (every lane calls this).
+template <bool CODES> __device__ __forceinline__ const unsigned char* bn_enc_lds(const EncArgs* enc) {
+    if constexpr (CODES) {
+        __shared__ __attribute__((aligned(16))) uint2 sEnc[kEncEntries + 1];
+        enc_fill<kBnThreads>(sEnc, *enc);
+        __syncthreads();
+        return reinterpret_cast<const unsigned char*>(sEnc);
     } else {
         return nullptr;
     }
@@ -314,11 +336,14 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_finalize(const BnArgs a, floa
     if (running_var) running_var[l.c] = (float)((1.0 - mo) * (double)running_var[l.c] + mo * (var * cnt / (cnt - 1.0)));
 }
 
-template <int V, bool LUT = false, bool RES = false>
-__global__ __launch_bounds__(kBnThreads) void k_bn_apply(const BnArgs a) {
+// The apply pass of every form.  CODES (V == 4, neither LUT nor RES): `enc` is the reader's kEncCode table, copied to LDS.
+template <int V, bool LUT, bool RES, bool CODES>
+__device__ __forceinline__ void bn_apply(const BnArgs& a, const EncArgs* enc) {
     static_assert(!(LUT && RES), "the residual form has no table");
+    static_assert(!CODES || (V == 4 && !LUT && !RES), "codes leave four channels to a dword, behind the plain apply");
     const BnLane<V> l(a);
     const float* const sTab = bn_table_lds<LUT>(a.table);
+    const unsigned char* const sE = bn_enc_lds<CODES>(enc);
     if (!l.live) return;
     const size_t ld = (size_t)a.c;
     BnMap<V> map = {bn_ld<V>(a.mean + l.ch), bn_ld<V>(a.gmean + l.ch), bn_ld<V>(a.invstd + l.ch), bn_ld<V>(a.beta + l.ch)};
@@ -327,7 +352,7 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_apply(const BnArgs a) {
     for (int e = 0; e < V; ++e) map.sc.v[e] = map.sc.v[e] * gamma.v[e];
     const float* px = a.x + l.ch;
     const float* pr = RES ? a.res + l.ch : nullptr;
-    float* py = a.out + l.ch;
+    float* py = CODES ? nullptr : a.out + l.ch;
     const int relu = a.relu;
     constexpr int N = RES ? 2 : 1;
     bn_walk<4>(l.first, l.r1, l.nty, ld,
@@ -346,43 +371,67 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_apply(const BnArgs a) {
                        } else {
                            float t = bn_affine<V>(b.p[0].v[e], map, e);
                            if constexpr (RES) t = t + b.p[1].v[e];   // the add is rounded on its own, the ReLU comes behind it
-                           if (relu) t = t < 0.f ? 0.f : t;
+                           if constexpr (!CODES) {   // the code quantizers fold the ReLU: enc4_code_relu
+                               if (relu) t = t < 0.f ? 0.f : t;
+                           }
                            v.v[e] = t;
                        }
                    }
-                   bn_st<V>(py + o, v);
+                   if constexpr (CODES) {
+                       const float4 t4 = make_float4(v.v[0], v.v[1], v.v[2], v.v[3]);
+                       const float r1 = enc->r1, lo = enc->lo, hi = enc->hi;
+                       const uint32_t d = relu ? enc4_code_relu<>(t4, r1, lo, hi, sE)
+                                               : (a.code_fmt == kFmtSfp7 ? enc4_code_fmt<kFmtSfp7, true>(t4, r1, lo, hi, sE)
+                                                                         : enc4_code_fmt<kFmtAct8, true>(t4, r1, lo, hi, sE));
+                       *reinterpret_cast<uint32_t*>(a.codes + o + (size_t)l.ch) = d;
+                   } else {
+                       bn_st<V>(py + o, v);
+                   }
                });
 }
 
-// What the backward loads of one row: x, gy and the forward's y (with relu only: otherwise y is never read)
-template <int V> __device__ __forceinline__ BnRow<V, 3> bn_ld_bwd(const float* px, const float* pg, const float* py, const size_t o,
-                                                                  const int relu) {
+template <int V, bool LUT = false, bool RES = false>
+__global__ __launch_bounds__(kBnThreads) void k_bn_apply(const BnArgs a) {
+    bn_apply<V, LUT, RES, false>(a, nullptr);
+}
+
+__global__ __launch_bounds__(kBnThreads) void k_bn_apply_codes(const BnArgs a, const EncArgs enc) {
+    bn_apply<4, false, false, true>(a, &enc);
+}
+
+// What the backward loads of one row: x, gy and the forward's y (with relu only: otherwise y is never read; XM: never)
+template <int V, bool XM = false>
+__device__ __forceinline__ BnRow<V, 3> bn_ld_bwd(const float* px, const float* pg, const float* py, const size_t o, const int relu) {
     BnRow<V, 3> b;
     b.p[0] = bn_ld<V>(px + o);
     b.p[1] = bn_ld<V>(pg + o);
-    b.p[2] = relu ? bn_ld<V>(py + o) : b.p[1];
+    if constexpr (XM) b.p[2] = b.p[1];
+    else b.p[2] = relu ? bn_ld<V>(py + o) : b.p[1];
     return b;
 }
 
 // g of channel e of a row.  The ReLU's mask is read from the forward's own output; the LUT forms multiply by the derivative
-// table at the class recomputed from x (map: the forward's own mean, lo, sc and beta).
-template <int V, bool LUT>
+// table at the class recomputed from x (map: the forward's own mean, lo, sc and beta).  XM (the code forms): the mask is t > 0 with
+// t the forward's own expression of x, which holds exactly where the plain forward's y > 0 (a NaN is in neither).
+template <int V, bool LUT, bool XM = false>
 __device__ __forceinline__ float bn_g(const BnRow<V, 3>& b, const int e, const int relu, const float* sTab, const BnMap<V>& map) {
     const float gy = b.p[1].v[e];
     if constexpr (LUT) return gy * sTab[bn_class<V>(b.p[0].v[e], map, e)];
+    else if constexpr (XM) return relu ? (bn_affine<V>(b.p[0].v[e], map, e) > 0.f ? gy : 0.f) : gy;
     else return relu ? (b.p[2].v[e] > 0.f ? gy : 0.f) : gy;
 }
 
-template <int V, bool LUT = false>
+template <int V, bool LUT = false, bool XM = false>
 __global__ __launch_bounds__(kBnThreads) void k_bn_bwd_reduce(const BnArgs a) {
+    static_assert(!(LUT && XM), "the table forms have no ReLU mask");
     const BnLane<V> l(a);
     const float* const sTab = bn_table_lds<LUT>(a.table);
     const size_t ld = (size_t)a.c;
     const size_t c0 = l.live ? (size_t)l.ch : 0;
     const Pack<V> mean = l.live ? bn_ld<V>(a.mean + c0) : bn_fill<V>(0.f);
     const Pack<V> invstd = l.live ? bn_ld<V>(a.invstd + c0) : bn_fill<V>(0.f);
-    BnMap<V> map = {mean, bn_fill<V>(0.f), bn_fill<V>(0.f), bn_fill<V>(0.f)};   // LUT: the forward's lo, invstd * gamma, beta
-    if constexpr (LUT) {
+    BnMap<V> map = {mean, bn_fill<V>(0.f), bn_fill<V>(0.f), bn_fill<V>(0.f)};   // LUT, XM: the forward's lo, invstd * gamma, beta
+    if constexpr (LUT || XM) {
         if (l.live) {
             const Pack<V> gamma = bn_ld<V>(a.gamma + c0);
             map.lo = bn_ld<V>(a.lo_fwd + c0);
@@ -396,11 +445,11 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_bwd_reduce(const BnArgs a) {
     const float* py = a.y + c0;   // read with relu only
     const int relu = a.relu;
     Pack<V> s[3] = {bn_fill<V>(0.f), bn_fill<V>(0.f), bn_fill<V>(0.f)};   // sg, sx, sd
-    bn_walk<4>(l.first, l.r1, l.nty, ld, [&](const size_t o) { return bn_ld_bwd<V>(px, pg, py, o, relu); },
+    bn_walk<4>(l.first, l.r1, l.nty, ld, [&](const size_t o) { return bn_ld_bwd<V, XM>(px, pg, py, o, relu); },
                [&](const size_t, const BnRow<V, 3>& b) {
 #pragma unroll
                    for (int e = 0; e < V; ++e) {
-                       const float g = bn_g<V, LUT>(b, e, relu, sTab, map);
+                       const float g = bn_g<V, LUT, XM>(b, e, relu, sTab, map);
                        const float d = b.p[0].v[e] - mean.v[e];
                        s[0].v[e] = s[0].v[e] + g;
                        s[1].v[e] = s[1].v[e] + g * (d * invstd.v[e]);
@@ -451,9 +500,10 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_bwd_finalize(const BnArgs a, 
     a.gmean[2 * (size_t)a.c + (size_t)l.c] = (float)lo;
 }
 
-template <int V, bool LUT = false, bool RES = false>
+template <int V, bool LUT = false, bool RES = false, bool XM = false>
 __global__ __launch_bounds__(kBnThreads) void k_bn_bwd_dx(const BnArgs a) {
     static_assert(!(LUT && RES), "the residual form has no table");
+    static_assert(!XM || (!LUT && !RES), "the recomputed mask belongs to the code forms alone");
     const BnLane<V> l(a);
     const float* const sTab = bn_table_lds<LUT>(a.table);
     if (!l.live) return;
@@ -463,7 +513,7 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_bwd_dx(const BnArgs a) {
     BnMap<V> map = {mean, bn_fill<V>(0.f), bn_fill<V>(0.f), bn_fill<V>(0.f)};   // sc = gamma * invstd, the forward's too
 #pragma unroll
     for (int e = 0; e < V; ++e) map.sc.v[e] = gamma.v[e] * invstd.v[e];
-    if constexpr (LUT) {   // the forward's lo and beta
+    if constexpr (LUT || XM) {   // the forward's lo and beta
         map.lo = bn_ld<V>(a.lo_fwd + l.ch);
         map.beta = bn_ld<V>(a.beta + l.ch);
     }
@@ -473,12 +523,12 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_bwd_dx(const BnArgs a) {
     float* po = a.out + l.ch;
     float* pq = RES && a.gres ? a.gres + l.ch : nullptr;   // the residual's gradient: g itself, stored where gx is
     const int relu = a.relu;
-    bn_walk<4>(l.first, l.r1, l.nty, ld, [&](const size_t o) { return bn_ld_bwd<V>(px, pg, py, o, relu); },
+    bn_walk<4>(l.first, l.r1, l.nty, ld, [&](const size_t o) { return bn_ld_bwd<V, XM>(px, pg, py, o, relu); },
                [&](const size_t o, const BnRow<V, 3>& b) {
                    Pack<V> gx, g;
 #pragma unroll
                    for (int e = 0; e < V; ++e) {
-                       g.v[e] = bn_g<V, LUT>(b, e, relu, sTab, map);
+                       g.v[e] = bn_g<V, LUT, XM>(b, e, relu, sTab, map);
                        const float xh = ((b.p[0].v[e] - mean.v[e]) - lo.v[e]) * invstd.v[e];
                        gx.v[e] = map.sc.v[e] * ((g.v[e] - mb.v[e]) - (xh * mg.v[e]));
                    }
@@ -491,11 +541,18 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_bwd_dx(const BnArgs a) {
 
 // The refusals both entry points share, in the order of include/slfp.h; *m receives N H W.
 // `table`: the LUT entry points' act_table / dact_table (has_table), 16-byte aligned whatever c is.
+// `cc`: the code entry points' own part (null for every other form): what their supported set adds, and the forward's y_codes.
+struct BnCodeCheck {
+    bool ok;             // c % 4 == 0, and in the forward a y_ka and y_qbits with a proven code table (bn_codes_table)
+    bool has_codes;      // the forward: y_codes counts among the pointers, 4-byte aligned
+    const void* codes;
+};
 static int bn_check(const char* fn, int64_t n, int64_t h, int64_t w, int64_t c, int x_layout, int relu, const void* const* big,
                     int nbig, const void* const* small, int nsmall, const void* workspace, size_t ws_bytes, int64_t* m,
-                    bool has_table = false, const void* table = nullptr) {
+                    bool has_table = false, const void* table = nullptr, const BnCodeCheck* cc = nullptr) {
     for (int i = 0; i < nbig; ++i)
         if (!big[i]) return fail(SLFP_ERR_BAD_ARG, "%s: null pointer", fn);
+    if (cc && cc->has_codes && !cc->codes) return fail(SLFP_ERR_BAD_ARG, "%s: null pointer (y_codes)", fn);
     for (int i = 0; i < nsmall; ++i)
         if (!small[i]) return fail(SLFP_ERR_BAD_ARG, "%s: null pointer", fn);
     if (has_table && !table) return fail(SLFP_ERR_BAD_ARG, "%s: null pointer (the table)", fn);
@@ -505,11 +562,16 @@ static int bn_check(const char* fn, int64_t n, int64_t h, int64_t w, int64_t c, 
     if (!bn_supported(n, h, w, c, x_layout))
         return fail(SLFP_ERR_UNSUPPORTED, "%s: no kernel for this shape / layout (slfp_bn_train_supported): NHWC only, and more "
                                           "than 1 value per channel", fn);
+    if (cc && !cc->ok)
+        return fail(SLFP_ERR_UNSUPPORTED, "%s: no kernel for this shape / reader (slfp_bn_codes_train_supported): c %% 4 == 0, y_qbits "
+                                          "8 or 7, and a y_ka > 0 with a proven code table", fn);
     *m = n * h * w;
     const uintptr_t mask = c % 4 == 0 ? 15 : 3;
     for (int i = 0; i < nbig; ++i)
         if (reinterpret_cast<uintptr_t>(big[i]) & mask)
             return fail(SLFP_ERR_ALIGNMENT, "%s: x / y / gy / gx must be %d-byte aligned", fn, (int)mask + 1);
+    if (cc && cc->has_codes && (reinterpret_cast<uintptr_t>(cc->codes) & 3))
+        return fail(SLFP_ERR_ALIGNMENT, "%s: y_codes must be 4-byte aligned", fn);
     for (int i = 0; i < nsmall; ++i)
         if (reinterpret_cast<uintptr_t>(small[i]) & mask)
             return fail(SLFP_ERR_ALIGNMENT, "%s: the per-channel arrays must be %d-byte aligned", fn, (int)mask + 1);
@@ -530,16 +592,33 @@ static void bn_geometry(BnArgs& a, const BnSplit& s, int64_t m, int64_t c, int r
     if (!a.gmean) a.gmean = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + bn_gmean_offset(s, c));
 }
 
-enum BnForm { kBnPlain, kBnTable, kBnRes };
+enum BnForm { kBnPlain, kBnTable, kBnRes, kBnCodes };
 
-// The streaming kernels of a (vec, form); the residual form's statistics and reduce pass are the plain ones.
+// What the code forms add to the supported set, host only: the reader's quantizer and a proven table for it.  Returns that table
+// (the one the apply is then launched with), or null.
+static int bn_code_fmt(int y_qbits) { return y_qbits == 7 ? kFmtSfp7 : kFmtAct8; }
+static const EncArgs* bn_codes_table(int64_t c, float y_ka, int y_qbits) {
+    if (c % 4 != 0 || (y_qbits != 8 && y_qbits != 7)) return nullptr;
+    if (!(y_ka > 0.f) || !scale_div_ok(y_ka) || long_encode_forced()) return nullptr;
+    const EncArgs* t = enc_table(y_ka, bn_code_fmt(y_qbits), kEncCode);
+    return t->valid ? t : nullptr;
+}
+
+// The streaming kernels of a (vec, form); the residual form's statistics and reduce pass are the plain ones, the code form's
+// statistics too.  The code form's apply takes the reader's table by value behind the arguments (apply_codes; V == 4 only).
 using BnKernel = void (*)(BnArgs);
-struct BnKernels { BnKernel stats, apply, reduce, dx; };
+using BnCodeKernel = void (*)(BnArgs, EncArgs);
+struct BnKernels { BnKernel stats, apply, reduce, dx; BnCodeKernel apply_codes; };
 template <int V> static BnKernels bn_kernels(BnForm form) {
     switch (form) {
-        case kBnTable: return {k_bn_stats<V>, k_bn_apply<V, true>, k_bn_bwd_reduce<V, true>, k_bn_bwd_dx<V, true>};
-        case kBnRes: return {k_bn_stats<V>, k_bn_apply<V, false, true>, k_bn_bwd_reduce<V>, k_bn_bwd_dx<V, false, true>};
-        default: return {k_bn_stats<V>, k_bn_apply<V>, k_bn_bwd_reduce<V>, k_bn_bwd_dx<V>};
+        case kBnCodes:
+            if constexpr (V == 4)
+                return {k_bn_stats<V>, nullptr, k_bn_bwd_reduce<V, false, true>, k_bn_bwd_dx<V, false, false, true>, k_bn_apply_codes};
+            else
+                return {};   // no such kernels: bn_forward / bn_backward refuse a form without them
+        case kBnTable: return {k_bn_stats<V>, k_bn_apply<V, true>, k_bn_bwd_reduce<V, true>, k_bn_bwd_dx<V, true>, nullptr};
+        case kBnRes: return {k_bn_stats<V>, k_bn_apply<V, false, true>, k_bn_bwd_reduce<V>, k_bn_bwd_dx<V, false, true>, nullptr};
+        default: return {k_bn_stats<V>, k_bn_apply<V>, k_bn_bwd_reduce<V>, k_bn_bwd_dx<V>, nullptr};
     }
 }
 static BnKernels bn_kernels(int vec, BnForm form) { return vec == 4 ? bn_kernels<4>(form) : bn_kernels<1>(form); }
@@ -561,15 +640,20 @@ static int bn_launched(const char* fn, const char* pass) {
 }
 
 // The forward of every form.  `a` holds the entry point's pointers (x, out, gamma, beta, res, table; gmean = save_lo in the
-// table form); `aliased` is the entry point's own aliasing refusal, or null.
+// table and code forms; codes and code_fmt in the code form); `aliased` is the entry point's own aliasing refusal, or null; `y_ka`
+// is the code form's reader scale.
 static int bn_forward(const char* fn, BnForm form, BnArgs a, float* running_mean, float* running_var, float momentum, float eps,
-                      int relu, float* save_mean, float* save_invstd, const BnCall& g, const char* aliased) {
+                      int relu, float* save_mean, float* save_invstd, const BnCall& g, const char* aliased, float y_ka = 0.f,
+                      int y_qbits = 0) {
     a.mean = save_mean; a.invstd = save_invstd;
+    const bool codes = form == kBnCodes, has_lo = form == kBnTable || codes;
     const void* big[] = {a.x, a.out, a.res};
     const void* small[] = {a.gamma, a.beta, save_mean, save_invstd, a.gmean};
+    const EncArgs* const enc = codes ? bn_codes_table(g.c, y_ka, y_qbits) : nullptr;   // fetched once: checked here, launched below
+    const BnCodeCheck cc = {enc != nullptr, true, a.codes};
     int64_t m = 0;
-    const int rc = bn_check(fn, g.n, g.h, g.w, g.c, g.x_layout, relu, big, form == kBnRes ? 3 : 2, small, form == kBnTable ? 5 : 4,
-                            g.workspace, g.ws_bytes, &m, form == kBnTable, a.table);
+    const int rc = bn_check(fn, g.n, g.h, g.w, g.c, g.x_layout, relu, big, form == kBnRes ? 3 : (codes ? 1 : 2), small, has_lo ? 5 : 4,
+                            g.workspace, g.ws_bytes, &m, form == kBnTable, a.table, codes ? &cc : nullptr);
     if (rc != SLFP_OK) return rc;
     if ((running_mean == nullptr) != (running_var == nullptr))
         return fail(SLFP_ERR_BAD_ARG, "%s: running_mean and running_var are given together or not at all", fn);
@@ -580,6 +664,8 @@ static int bn_forward(const char* fn, BnForm form, BnArgs a, float* running_mean
     const BnSplit s = bn_split(m, g.c);
     bn_geometry(a, s, m, g.c, relu, g.workspace);
     const BnKernels k = bn_kernels(s.vec, form);
+    if (!k.stats || !(codes ? (k.apply_codes && enc) : (bool)k.apply))
+        return fail(SLFP_ERR_UNSUPPORTED, "%s: no kernels of this form for %d channel(s) per lane", fn, s.vec);
     const dim3 grid((unsigned)s.slabs, (unsigned)s.tiles), block(kBnThreads);
     const hipStream_t st = as_stream(g.stream);
     hipLaunchKernelGGL(k.stats, grid, block, 0, st, a);
@@ -589,19 +675,23 @@ static int bn_forward(const char* fn, BnForm form, BnArgs a, float* running_mean
                        eps, save_mean, save_invstd);
     e = bn_launched(fn, "finalize");
     if (e != SLFP_OK) return e;
-    hipLaunchKernelGGL(k.apply, grid, block, 0, st, a);
+    if (codes) hipLaunchKernelGGL(k.apply_codes, grid, block, 0, st, a, *enc);
+    else hipLaunchKernelGGL(k.apply, grid, block, 0, st, a);
     return bn_launched(fn, "apply");
 }
 
 // The backward of every form.  `a` holds the entry point's pointers (x, y, gy, out, gamma, mean, invstd, gres; beta, lo_fwd and
-// table in the table form, whose y is x: it is never read); `misaligned` and `aliased` are the entry point's own refusals, or null.
+// table in the table form, beta and lo_fwd in the code form; the y of both is x: it is never read); `misaligned` and `aliased` are
+// the entry point's own refusals, or null.
 static int bn_backward(const char* fn, BnForm form, BnArgs a, int relu, float* ggamma, float* gbeta, const BnCall& g,
                        const char* misaligned, const char* aliased) {
     const void* big[] = {a.x, a.y, a.gy, a.out};
     const void* small[] = {a.gamma, a.mean, a.invstd, a.beta, a.lo_fwd};
+    const bool codes = form == kBnCodes;
+    const BnCodeCheck cc = {g.c % 4 == 0, false, nullptr};
     int64_t m = 0;
-    const int rc = bn_check(fn, g.n, g.h, g.w, g.c, g.x_layout, relu, big, 4, small, form == kBnTable ? 5 : 3, g.workspace,
-                            g.ws_bytes, &m, form == kBnTable, a.table);
+    const int rc = bn_check(fn, g.n, g.h, g.w, g.c, g.x_layout, relu, big, 4, small, form == kBnTable || codes ? 5 : 3, g.workspace,
+                            g.ws_bytes, &m, form == kBnTable, a.table, codes ? &cc : nullptr);
     if (rc != SLFP_OK) return rc;
     if (misaligned) return fail(SLFP_ERR_ALIGNMENT, "%s: %s", fn, misaligned);
     if ((reinterpret_cast<uintptr_t>(ggamma) | reinterpret_cast<uintptr_t>(gbeta)) & 3)
@@ -611,6 +701,7 @@ static int bn_backward(const char* fn, BnForm form, BnArgs a, int relu, float* g
     const BnSplit s = bn_split(m, g.c);
     bn_geometry(a, s, m, g.c, relu, g.workspace);
     const BnKernels k = bn_kernels(s.vec, form);
+    if (!k.reduce || !k.dx) return fail(SLFP_ERR_UNSUPPORTED, "%s: no kernels of this form for %d channel(s) per lane", fn, s.vec);
     const dim3 grid((unsigned)s.slabs, (unsigned)s.tiles), block(kBnThreads);
     const hipStream_t st = as_stream(g.stream);
     hipLaunchKernelGGL(k.reduce, grid, block, 0, st, a);
@@ -710,6 +801,35 @@ int slfp_bn_lut_train_bwd(const float* x, const float* gy, const float* gamma, c
     a.x = x; a.y = x; a.gy = gy; a.out = gx; a.gamma = gamma; a.beta = beta; a.mean = save_mean; a.invstd = save_invstd;
     a.lo_fwd = save_lo; a.table = dact_table;
     return bn_backward("slfp_bn_lut_train_bwd", kBnTable, a, 0, ggamma, gbeta, {n, h, w, c, x_layout, workspace, ws_bytes, stream},
+                       nullptr, gx == x ? "gx may not alias x" : nullptr);
+}
+
+int slfp_bn_codes_train_supported(int64_t n, int64_t h, int64_t w, int64_t c, int x_layout, float y_ka, int y_qbits) {
+    return bn_supported(n, h, w, c, x_layout) && bn_codes_table(c, y_ka, y_qbits) ? 1 : 0;
+}
+
+int slfp_bn_codes_train_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                            float momentum, float eps, int relu, float y_ka, int y_qbits, uint8_t* y_codes, float* save_mean,
+                            float* save_invstd, float* save_lo, int64_t n, int64_t h, int64_t w, int64_t c, int x_layout,
+                            void* workspace, size_t ws_bytes, void* stream) {
+    BnArgs a = {};
+    a.x = x; a.codes = y_codes; a.code_fmt = bn_code_fmt(y_qbits); a.gamma = gamma; a.beta = beta;
+    a.gmean = save_lo;   // as the table form: the backward recomputes the forward's t from it
+    return bn_forward("slfp_bn_codes_train_fwd", kBnCodes, a, running_mean, running_var, momentum, eps, relu, save_mean, save_invstd,
+                      {n, h, w, c, x_layout, workspace, ws_bytes, stream},
+                      reinterpret_cast<const void*>(x) == reinterpret_cast<const void*>(y_codes)
+                          ? "y_codes may not alias x (the backward reads x)" : nullptr,
+                      y_ka, y_qbits);
+}
+
+int slfp_bn_codes_train_bwd(const float* x, const float* gy, const float* gamma, const float* beta, const float* save_mean,
+                            const float* save_invstd, const float* save_lo, int relu, float* gx, float* ggamma, float* gbeta,
+                            int64_t n, int64_t h, int64_t w, int64_t c, int x_layout, void* workspace, size_t ws_bytes,
+                            void* stream) {
+    BnArgs a = {};
+    a.x = x; a.y = x; a.gy = gy; a.out = gx; a.gamma = gamma; a.beta = beta; a.mean = save_mean; a.invstd = save_invstd;
+    a.lo_fwd = save_lo;
+    return bn_backward("slfp_bn_codes_train_bwd", kBnCodes, a, relu, ggamma, gbeta, {n, h, w, c, x_layout, workspace, ws_bytes, stream},
                        nullptr, gx == x ? "gx may not alias x" : nullptr);
 }
 

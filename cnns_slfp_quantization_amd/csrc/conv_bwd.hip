@@ -9,6 +9,9 @@
 // Everything accumulates in float32.  xq is never materialised: it is encoded on load with the forward's threshold table
 // (slfp_enc.hpp; the long form of slfp_device.hpp where the table is unavailable), bit-identical to slfp_quantize_f32.
 // wq is small: the caller quantizes it into the workspace first.
+// slfp_conv2d_bwd_codes: x arrives as the 1-byte extended codes of xq (slfp_codes.hpp; NHWC, C_in % 4 == 0) and every x load
+// becomes a byte load -- a dword of four channels where the float path loads a float4 -- decoded through the 256-entry kDecF32
+// table in LDS: decode(code) is xq bit for bit, so gw equals the float path's.  The gx half never reads x.
 //
 // Determinism: no atomics.  Each workgroup writes its gw / gb partial sums to the workspace and k_reduce_parts sums them
 // in a fixed order, so equal inputs give bitwise-equal gradients.
@@ -23,6 +26,7 @@
 // on load and the bias sum taken from the staged GY tiles of the first column of workgroups.
 #include "slfp_device.hpp"
 #include "slfp_enc.hpp"
+#include "slfp_codes.hpp"
 #include "slfp_host.hpp"
 #include <type_traits>
 
@@ -30,18 +34,30 @@ namespace slfp {
 
 constexpr int kEncTabQ = -1;   // AF template argument: the threshold table (otherwise kFmtAct8 / kFmtSfp7: the long form)
 constexpr int kNoEnc = -2;     // AF: the operand is used as is
+constexpr int kCodes8 = -3;    // AF: the operand is the 1-byte extended codes of QA(x / Ka), SLFP<3,4> (decoded, not encoded)
+constexpr int kCodes7 = -4;    // AF: the same, SFP<3,3>
+constexpr bool af_codes(int af) { return af == kCodes8 || af == kCodes7; }
+constexpr uint32_t kCodeZero4 = 0x01010101u;   // four codes of exact zero: what padding decodes from
+// LDS of a kernel's activation table, in uint2: the threshold table, the 1 KiB decode table of the code forms, or nothing
+constexpr int act_lds(int af) { return af == kEncTabQ ? kEncEntries + 1 : (af_codes(af) ? kDecBytes / 8 : 1); }
 
 // A kernel's activation encoder: q(x) = QA(x / Ka), bit-identical to slfp_quantize_f32 (codec.hip: k_quantize_tab / k_codec).
 // act_enc fills the workgroup's threshold table sE (AF == kEncTabQ) or the long form's LUT sT with NT threads; the
-// caller's next __syncthreads() publishes them.
+// caller's next __syncthreads() publishes them.  The code forms (af_codes) keep the decode table in sE instead: q of a byte and
+// q4 of a dword of four are lookups (dec4_f32), and cx() is the operand's address as bytes -- element offsets stay what they are.
 template <int AF>
 struct ActEnc {
+    static constexpr bool kCodes = af_codes(AF);
+    using X4 = std::conditional_t<kCodes, uint32_t, float4>;   // four consecutive channels as loaded
+    static __device__ __forceinline__ const uint8_t* cx(const float* x) { return reinterpret_cast<const uint8_t*>(x); }
+    __device__ __forceinline__ float q(uint8_t code) const { return __uint_as_float(*reinterpret_cast<const uint32_t*>(tb + 4u * code)); }
+    __device__ __forceinline__ float4 q4(uint32_t codes) const { return dec4_f32(codes, tb); }
     const unsigned char* tb;
     const uint32_t* sT;
     float r1, lo, hi;
     ScaleDiv sd;
     __device__ __forceinline__ float q(float x) const {
-        if constexpr (AF == kNoEnc) {
+        if constexpr (AF == kNoEnc || kCodes) {   // (the code forms never call this)
             return x;
         } else if constexpr (AF == kEncTabQ) {
             const float r = enc_f32(x, r1, lo, hi, tb) + 0.0f;
@@ -56,6 +72,8 @@ struct ActEnc {
 template <int AF, int NT>
 __device__ __forceinline__ ActEnc<AF> act_enc(uint2* sE, uint32_t* sT, const EncArgs& t, const ScaleDiv& sd) {
     if constexpr (AF == kEncTabQ) enc_fill<NT>(sE, t);
+    else if constexpr (AF == kCodes8) dec_fill<kFmtAct8, kDecF32, NT>(reinterpret_cast<uint32_t*>(sE));
+    else if constexpr (AF == kCodes7) dec_fill<kFmtSfp7, kDecF32, NT>(reinterpret_cast<uint32_t*>(sE));
     else if constexpr (AF != kNoEnc) lut_fill<AF>(sT);
     return ActEnc<AF>{reinterpret_cast<const unsigned char*>(sE), sT, t.r1, t.lo, t.hi, sd};
 }
@@ -103,13 +121,15 @@ __global__ __launch_bounds__(kDwThreads) void k_dw3x3_bwd(const float* __restric
         const int n = (int)(u / ((int64_t)g.nbh * g.nbw));
         const int rem = (int)(u - (int64_t)n * g.nbh * g.nbw);
         const int oh0 = (rem / g.nbw) * kDwTH, ow0 = (rem % g.nbw) * kDwTW;
-        const float* xn = x + (int64_t)n * H * W * C + c;
+        const int64_t xo = (int64_t)n * H * W * C + c;   // in elements: float32, or bytes in the code forms
+        const float* xn = x + xo;
         const float* gn = gy + (int64_t)n * Ho * Wo * C + c;
         const int xr0 = S * oh0 - 1;                    // first x row
         const int gr0 = S == 1 ? oh0 - 1 : oh0;         // first gy row
         auto ldx = [&](int row, int col) -> float {
             if (row < 0 || row >= H || col < 0 || col >= W) return 0.f;   // zero padding of xq
-            return enc.q(xn[((int64_t)row * W + col) * C]);
+            if constexpr (af_codes(AF)) return enc.q(enc.cx(x)[xo + ((int64_t)row * W + col) * C]);   // one byte per channel
+            else return enc.q(xn[((int64_t)row * W + col) * C]);
         };
         auto ldg = [&](int row, int col) -> float {
             if (row < 0 || row >= Ho || col < 0 || col >= Wo) return 0.f;
@@ -402,7 +422,7 @@ __global__ __launch_bounds__(256) void k_gemm_f32(const GemmArgs ga, const EncAr
     constexpr int BM = 64 * TM, BN = 64 * TN, BK = kGemmBK;
     __shared__ __attribute__((aligned(16))) float sA[BK][BM];
     __shared__ __attribute__((aligned(16))) float sB[BK][BN];
-    __shared__ __attribute__((aligned(16))) uint2 sE[AF == kEncTabQ ? kEncEntries + 1 : 1];
+    __shared__ __attribute__((aligned(16))) uint2 sE[act_lds(AF)];
     __shared__ uint32_t sT[16];
     const ActEnc<AF> enc = act_enc<AF, 256>(sE, sT, t, sd);
 
@@ -418,7 +438,8 @@ __global__ __launch_bounds__(256) void k_gemm_f32(const GemmArgs ga, const EncAr
     // contiguous dimension), zero outside the matrix
     constexpr int AV = BM * BK / 4 / 256, BV = BN * BK / 4 / 256;   // float4 groups per thread
     static_assert(AV >= 1 && BV >= 1, "tile too small for 256 threads");
-    float4 ra[AV], rb[BV];
+    float4 ra[AV];
+    typename ActEnc<AF>::X4 rb[BV];
     auto ld4 = [&](const float* base, int64_t ld, int row, int col, int rows_end, int cols_end) -> float4 {
         // element (row, col .. col+3) of a row-major [rows][cols] matrix
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -447,7 +468,13 @@ __global__ __launch_bounds__(256) void k_gemm_f32(const GemmArgs ga, const EncAr
         for (int i = 0; i < BV; ++i) {
             const int e = tid + i * 256;
             const int kk = e / (BN / 4), nn = (e % (BN / 4)) * 4;
-            rb[i] = ld4(ga.B, ga.ldb, k0 + kk, n0 + nn, ke, N);
+            if constexpr (af_codes(AF)) {   // N % 4 == 0: the four channels are all there or none is
+                const bool ok = k0 + kk < ke && n0 + nn < N;
+                const uint32_t v = *reinterpret_cast<const uint32_t*>(enc.cx(ga.B) + (ok ? (int64_t)(k0 + kk) * ga.ldb + n0 + nn : 0));
+                rb[i] = ok ? v : kCodeZero4;
+            } else {
+                rb[i] = ld4(ga.B, ga.ldb, k0 + kk, n0 + nn, ke, N);
+            }
         }
     };
     auto store_tiles = [&]() {
@@ -585,7 +612,7 @@ __global__ __launch_bounds__(256) void k_dense_gw(const float* __restrict__ gy, 
     constexpr int BM = 64 * TM, BN = 64 * TN, BK = kGemmBK;
     __shared__ __attribute__((aligned(16))) float sA[BK][BM];
     __shared__ __attribute__((aligned(16))) float sB[BK][BN];
-    __shared__ __attribute__((aligned(16))) uint2 sE[AF == kEncTabQ ? kEncEntries + 1 : 1];
+    __shared__ __attribute__((aligned(16))) uint2 sE[act_lds(AF)];
     __shared__ uint32_t sT[16];
     const ActEnc<AF> enc = act_enc<AF, 256>(sE, sT, t, sd);
 
@@ -601,7 +628,8 @@ __global__ __launch_bounds__(256) void k_dense_gw(const float* __restrict__ gy, 
 
     constexpr int AV = BM * BK / 4 / 256, BV = BN * BK / 4 / 256;
     static_assert(256 % (BN / 4) == 0, "a thread keeps its B columns over the K loop");
-    float4 ra[AV], rb[BV];
+    float4 ra[AV];
+    typename ActEnc<AF>::X4 rb[BV];
     // the B columns (tap, ci) of this thread: fixed for the whole K loop.  VEC: C_in % 4 == 0, so the four lie in one tap.
     constexpr int NC = VEC ? 1 : 4;
     int b_kh[NC], b_kw[NC], b_ci[NC];
@@ -638,7 +666,10 @@ __global__ __launch_bounds__(256) void k_dense_gw(const float* __restrict__ gy, 
                 ok[j] = okk && b_ok[j] && (unsigned)hi_ < (unsigned)H && (unsigned)wi < (unsigned)W;
                 off[j] = (((int64_t)n * H + hi_) * W + wi) * Cin + b_ci[j];
             }
-            if constexpr (VEC) rb[i] = ld4_guard<true>(x, off[0], ok[0], 4);
+            if constexpr (af_codes(AF)) {   // C_in % 4 == 0: the four columns lie in one tap, whatever VEC says of gy
+                const uint32_t v = *reinterpret_cast<const uint32_t*>(enc.cx(x) + (ok[0] ? off[0] : 0));
+                rb[i] = ok[0] ? v : kCodeZero4;
+            } else if constexpr (VEC) rb[i] = ld4_guard<true>(x, off[0], ok[0], 4);
             else rb[i] = make_float4(ld_guard(x, off[0], ok[0]), ld_guard(x, off[1], ok[1]), ld_guard(x, off[2], ok[2]),
                                      ld_guard(x, off[3], ok[3]));
         }
@@ -832,10 +863,13 @@ using Int = std::integral_constant<int, V>;
 
 static const EncArgs kNone{};   // the table argument of a kernel that uses none
 
-// The activation encode: the threshold table where act_table has one, else the long form of the format.
+// The activation encode: the threshold table where act_table has one, else the long form of the format; the decode of the
+// format's codes where x arrives as codes.
 template <class F>
-static void with_act_enc(const EncArgs* tab, int fmt_act, F fn) {
-    if (tab) fn(Int<kEncTabQ>{}, *tab);
+static void with_act_enc(const EncArgs* tab, int fmt_act, bool x_codes, F fn) {
+    if (x_codes && fmt_act == kFmtAct8) fn(Int<kCodes8>{}, kNone);
+    else if (x_codes) fn(Int<kCodes7>{}, kNone);
+    else if (tab) fn(Int<kEncTabQ>{}, *tab);
     else if (fmt_act == kFmtAct8) fn(Int<kFmtAct8>{}, kNone);
     else fn(Int<kFmtSfp7>{}, kNone);
 }
@@ -893,8 +927,12 @@ static int reduce_gb(hipStream_t st, const float* gbpart, int splits, int64_t co
     return reduce_parts(st, gbpart, splits, cout, 1.0f, 0, 0, 0, gb, nullptr);
 }
 
+// What the code entry point adds to the supported set: the codes are NHWC with whole dwords of channels.
+static bool codes_ok(const slfp_conv2d_desc& d) { return d.x_layout == SLFP_LAYOUT_NHWC && d.c_in % 4 == 0; }
+
+// x_codes: x points at the 1-byte extended codes of QA(x / Ka) (slfp_conv2d_bwd_codes) instead of float32 values.
 static int run_bwd(const slfp_conv2d_desc* d, unsigned flags, const float* x, const float* w, const float* gy, float* gx, float* gw,
-                   float* gb, void* workspace, void* stream) {
+                   float* gb, void* workspace, void* stream, bool x_codes = false) {
     ConvPlan p;
     int rc = make_plan(d, &p);
     if (rc != SLFP_OK) return rc;
@@ -903,6 +941,8 @@ static int run_bwd(const slfp_conv2d_desc* d, unsigned flags, const float* x, co
         return fail(SLFP_ERR_UNSUPPORTED, flags & SLFP_BWD_DENSE
                         ? "slfp_conv2d_bwd: only 3x3 depthwise (stride 1/2, pad 1) and groups-1 dilation-1 layers"
                         : "slfp_conv2d_bwd: only 3x3 depthwise (stride 1/2, pad 1) and stride-1 1x1 layers");
+    if (x_codes && !codes_ok(*d))
+        return fail(SLFP_ERR_UNSUPPORTED, "slfp_conv2d_bwd_codes: x_codes are NHWC with C_in a multiple of 4");
     if (!gy) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_bwd: null gy");
     if (gx && !w) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_bwd: gx needs the weights");
     if (gw && !x) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_bwd: gw needs the input");
@@ -943,7 +983,7 @@ static int run_bwd(const slfp_conv2d_desc* d, unsigned flags, const float* x, co
         const int pb = dw_blocks(g);
         float* part = reinterpret_cast<float*>(ws + L.part);
         const dim3 grid((unsigned)pb, (unsigned)ceil_div(g.C, g.cw));
-        with_act_enc(tab, p.fmt_act, [&](auto AF, const EncArgs& t) { with_1_or_2((int)d->stride_h, [&](auto S) {
+        with_act_enc(tab, p.fmt_act, x_codes, [&](auto AF, const EncArgs& t) { with_1_or_2((int)d->stride_h, [&](auto S) {
             hipLaunchKernelGGL((k_dw3x3_bwd<decltype(S)::value, decltype(AF)::value>), grid, dim3(kDwThreads), 0, st, x_n, gy_n, wq,
                                gx_n, part, g, d->kw_scale, (int)need_gx, (int)need_gw, t, sd);
         }); });
@@ -966,7 +1006,7 @@ static int run_bwd(const slfp_conv2d_desc* d, unsigned flags, const float* x, co
         if (need_gw) {
             float* part = reinterpret_cast<float*>(ws + L.part);
             float* gbp = need_gb ? reinterpret_cast<float*>(ws + L.gbpart) : nullptr;
-            with_act_enc(tab, p.fmt_act, [&](auto AF, const EncArgs& t) {
+            with_act_enc(tab, p.fmt_act, x_codes, [&](auto AF, const EncArgs& t) {
                 launch_dense_gw<decltype(AF)::value>(g, s, vec, st, gy_n, x_n, part, gbp, t, sd);
             });
             if ((rc = check_launch("slfp dense backward (gw) kernel")) != SLFP_OK) return rc;
@@ -975,8 +1015,8 @@ static int run_bwd(const slfp_conv2d_desc* d, unsigned flags, const float* x, co
         }
     } else {
         const PwShape s = pw_shape(*d);
-        const bool vec = (Cin % 4) == 0 && (Cout % 4) == 0 && aligned16(gy_n) && (!need_gw || aligned16(x_n)) &&
-                         (!need_gx || aligned16(wq));
+        const bool vec = (Cin % 4) == 0 && (Cout % 4) == 0 && aligned16(gy_n) && (!need_gw || x_codes || aligned16(x_n)) &&
+                         (!need_gx || aligned16(wq));   // (codes are read a dword at a time whatever vec says)
         if (need_gx) {
             GemmArgs a{gy_n, wq, gx_n, nullptr, (int)s.M, (int)Cin, (int)Cout, Cout, Cin, Cin, (int)Cout, d->kw_scale};
             a.kps = (int)ceil_div(Cout, kGemmBK) * kGemmBK;
@@ -988,7 +1028,7 @@ static int run_bwd(const slfp_conv2d_desc* d, unsigned flags, const float* x, co
             float* gbp = reinterpret_cast<float*>(ws + L.gbpart);
             GemmArgs a{gy_n, x_n, part, need_gb ? gbp : nullptr, (int)Cout, (int)Cin, (int)s.M, Cout, Cin, Cin, s.kps,
                        s.splits > 1 ? 1.0f : d->ka};
-            with_act_enc(tab, p.fmt_act, [&](auto AF, const EncArgs& t) {
+            with_act_enc(tab, p.fmt_act, x_codes, [&](auto AF, const EncArgs& t) {
                 launch_gemm<true, decltype(AF)::value>(a, s.tm_w, s.tn_w, vec, st, t, sd);
             });
             if ((rc = check_launch("slfp pointwise backward (gw) kernel")) != SLFP_OK) return rc;
@@ -1039,6 +1079,22 @@ int slfp_conv2d_bwd_ex(const slfp_conv2d_desc* d, unsigned flags, const float* x
         (gw_oihw && !aligned16(gw_oihw)) || (gb && !aligned16(gb)))
         return fail(SLFP_ERR_ALIGNMENT, "slfp_conv2d_bwd: tensors must be 16-byte aligned");
     return run_bwd(d, flags, x, w_oihw, gy, gx, gw_oihw, gb, workspace, stream);
+}
+
+int slfp_conv2d_bwd_codes_supported(const slfp_conv2d_desc* d, unsigned flags) {
+    return slfp_conv2d_bwd_supported_ex(d, flags) && codes_ok(*d) ? 1 : 0;
+}
+
+int slfp_conv2d_bwd_codes(const slfp_conv2d_desc* d, unsigned flags, const uint8_t* x_codes, const float* w_oihw, const float* gy,
+                          float* gx, float* gw_oihw, float* gb, void* workspace, void* stream) {
+    if (!d) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_bwd_codes: null descriptor");
+    if (flags & ~SLFP_BWD_DENSE) return fail(SLFP_ERR_BAD_ARG, "slfp_conv2d_bwd_codes: unknown flag bits 0x%x", flags & ~SLFP_BWD_DENSE);
+    if ((w_oihw && !aligned16(w_oihw)) || (gy && !aligned16(gy)) || (gx && !aligned16(gx)) || (gw_oihw && !aligned16(gw_oihw)) ||
+        (gb && !aligned16(gb)))
+        return fail(SLFP_ERR_ALIGNMENT, "slfp_conv2d_bwd_codes: tensors must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(x_codes) & 3) return fail(SLFP_ERR_ALIGNMENT, "slfp_conv2d_bwd_codes: x_codes must be 4-byte aligned");
+    // the kernels take x as one pointer type; the code forms read it as bytes at the same element offsets (ActEnc::cx)
+    return run_bwd(d, flags, reinterpret_cast<const float*>(x_codes), w_oihw, gy, gx, gw_oihw, gb, workspace, stream, true);
 }
 
 int slfp_conv2d_bwd_supported(const slfp_conv2d_desc* d) { return slfp_conv2d_bwd_supported_ex(d, 0u); }

@@ -41,6 +41,9 @@ undo function restores exactly that state; "also undone by" = the other undo fun
                                    link_head                          _code_in                                      restore_avgpool
   use_device_bn_train(model)       -- (a TRAINING pass: before or     nn.BatchNorm2d -> TrainBatchNorm2d, a ReLU    restore_bn_train
                                    after model.train())               behind it -> FoldedReLU (bn._relu)
+  link_codes_train(model)          -- (a TRAINING pass; before or     [BN, ReLU, Conv2d_Q]: the BN slot ->          unlink_codes_train
+                                   after use_device_bn_train)         TrainBatchNormCodes2d, a stock ReLU ->
+                                                                      FoldedReLU (_codes_train)
 
 The passes that take an example input share one forward trace (`_Trace`), one rule for "the same tensor" (`_Trace.same`), one
 eligibility predicate (`_code_eligible`), one record of wrapped children (`_wrap_children` / `_unwrap_children`) and one
@@ -1947,7 +1950,7 @@ _BN_NAMES = ("running_mean", "running_var", "num_batches_tracked")
 
 
 class _DeviceBatchNorm(nn.Module):
-    """What TrainBatchNorm2d and TrainBatchNormLayerout2d share: the stock nn.BatchNorm2d's attributes and the SAME Parameter and
+    """What TrainBatchNorm2d, TrainBatchNormLayerout2d and TrainBatchNormCodes2d share: the stock nn.BatchNorm2d's attributes and the SAME Parameter and
     buffer objects under the same names (the stock module itself is kept outside _modules, `_bn`), the num_batches_tracked tick,
     the rule for when the kernels may run, and the F.batch_norm path on the same buffers for everything else."""
     _version = 2   # nn.BatchNorm2d's state-dict version (num_batches_tracked)
@@ -2085,8 +2088,10 @@ def restore_bn_train(model):
     """Undo use_device_bn_train: every slot gets its original module back; the originals are pointed at the current parameters
     and buffers (the model may have been moved or cast in between) and take the wrapper's training flag.  Blocks rewritten by
     use_device_bottleneck_train are restored first (restore_bottleneck_train): their instance-level forward calls bn1..3 with
-    keywords a stock BatchNorm does not take."""
+    keywords a stock BatchNorm does not take.  Links of link_codes_train are undone first too (unlink_codes_train): a wrapper of
+    theirs would hand the restored nn.ReLU a uint8 tensor."""
     restore_bottleneck_train(model)
+    unlink_codes_train(model)
     n = 0
     seen = set()
     for parent in list(model.modules()):
@@ -2335,4 +2340,133 @@ def restore_bn_layerout_train(model):
             elif isinstance(child, FoldedTail):
                 child.mod.training = child.training
                 parent._modules[name] = child.mod
+    return n
+
+
+# ------------------------------------------------------------------ training-mode BatchNorm2d + ReLU -> the next Conv2d_Q on 1-byte codes
+class TrainBatchNormCodes2d(_DeviceBatchNorm):
+    """The BatchNorm2d of a run [BatchNorm2d, ReLU, Conv2d_Q] linked by link_codes_train: in a training step it
+    runs slfp_bn_codes_train_fwd without recording and returns relu(batch_norm(x)) as the uint8 channels_last codes of the
+    Conv2d_Q's own quantizer; the tensor carries a batchnorm.TrainLink (attribute `_train_link`: x with its graph, the operands,
+    the saves), the ReLU slot passes it through and the Conv2d_Q runs BN -> ReLU -> conv as one autograd Function on it
+    (batchnorm.hip_bn_codes_conv_train).  As TrainBatchNorm2d it registers the SAME Parameter and buffer objects under the same
+    names; what stood in the two slots is kept outside _modules (`_held`).
+    The code path is taken per call only where all of this holds: training mode, no autocast, a channels_last float32 ROCm input of
+    at least `min_elements` elements (None: batchnorm.CODES_MIN_ELEMENTS) with float32 parameters and buffers on its device;
+    slfp_bn_codes_train_supported; a code-reading float32-output forward for the conv under the current options;
+    slfp_conv2d_bwd_codes_supported under options.backward "hip" / "hip_all" ("composite" never takes it); and the conv still in
+    training mode with the Ka and q_bit the link was made for, nothing fused onto it.  Otherwise the call does what stood in the
+    slots does -- a TrainBatchNorm2d with its folded ReLU under its own size rule, or F.batch_norm and a ReLU -- and the conv
+    sees float32.
+      _last_kernel   "bn_codes_train+relu", or "bn_train+relu" / "aten" """
+
+    def __init__(self, held_bn, held_relu, conv, min_elements=None):
+        from .conv2d_func import _f32
+        kernels = isinstance(held_bn, TrainBatchNorm2d)
+        super().__init__(_repoint_bn(held_bn) if kernels else held_bn, min_elements)
+        object.__setattr__(self, "_held", (held_bn, held_relu))
+        object.__setattr__(self, "_conv", conv)
+        self._fallback = (kernels, held_bn.min_elements if kernels else None)   # what the slot ran: the kernels (+ size rule) or ATen
+        self._ka, self._q_bit = _f32(conv.Ka), conv.q_bit
+
+    def extra_repr(self):
+        return f"{self.num_features}, eps={self.eps}, momentum={self.momentum}, relu=True, codes for Ka={self._ka}, q_bit={self._q_bit}"
+
+    def _codes_ok(self, x):
+        from . import batchnorm as B
+        from .conv2d_func import _bwd_codes_supported, _f32, _plan
+        conv = self._conv
+        if not (conv.training and conv.q_bit == self._q_bit and _f32(conv.Ka) == self._ka and _link_conv_clean(conv)):
+            return False
+        if conv.weight.device != x.device or not B.bn_codes_train_supported(x, self._ka, self._q_bit, self.min_elements):
+            return False
+        return _plan(conv, x, conv.weight, True, True, ("codes", True, None, None)).ok and _bwd_codes_supported(conv, x.shape)
+
+    def forward(self, x):
+        from . import batchnorm as B
+        self._begin(x)
+        ops = self._kernel_operands(x, 0)
+        if ops is not None and self._codes_ok(x):
+            codes, *saves = B.bn_codes_train_fwd(x, *ops, self.momentum, self.eps, True, self._ka, self._q_bit)
+            codes._train_link = B.TrainLink(x, self.weight, self.bias, saves, True, self._ka, self._q_bit, self._conv)
+            self._last_kernel = "bn_codes_train+relu"
+            return codes
+        kernels, floor = self._fallback
+        ops = self._kernel_operands(x, B.MIN_ELEMENTS if floor is None else floor) if kernels else None
+        if ops is not None:
+            self._last_kernel = "bn_train+relu"
+            return B.hip_bn_train.apply(x, *ops, self.momentum, self.eps, True)
+        return torch.relu(self._aten(x))
+
+
+def _link_conv_clean(conv):
+    """A Conv2d_Q a training link may feed: q_bit 8 or 7, no raw (unscaled) bias, nothing fused or linked onto it."""
+    return (conv.q_bit in (8, 7) and (conv.bias is None or conv._scaled_bias) and conv._post is None and conv._code_out is None
+            and conv._image_table is None)
+
+
+def _flat_slots(seq, model, once=True):
+    """(parent, name, module, once) of the leaves of nested nn.Sequentials, in the order they run.  once: every nested Sequential
+    around the leaf sits in exactly one slot of `model`, so the leaf appears once in this order and has one successor."""
+    for name, m in seq._modules.items():
+        if isinstance(m, nn.Sequential):
+            yield from _flat_slots(m, model, once and len(_slots_of(model, m)) == 1)
+        else:
+            yield seq, name, m, once
+
+
+def link_codes_train(model, min_elements=None):
+    """Hand activations from BatchNorm to the next Conv2d_Q as 1-byte codes in a TRAINING step.  Candidates are
+    runs [BatchNorm2d | TrainBatchNorm2d with a folded ReLU, ReLU | FoldedReLU, Conv2d_Q] in the flattened leaf order of nested
+    nn.Sequentials, so a block's last ReLU meets the next block's first conv (nets_imgnet/mobilenetv1.py:24-41).  ATen is never
+    asked to read a uint8 tensor: each of the three sits in exactly one slot (and so does every nested Sequential around it: a
+    block held twice has two successors), the BN is affine with a momentum, the conv has q_bit 8
+    or 7, no raw bias and nothing fused onto it (_post, _code_out, _image_table).  Hand-wired blocks (Bottleneck, Fire, ShuffleNet
+    units) are left alone.  The BN's slot gets a TrainBatchNormCodes2d, a stock ReLU's slot a FoldedReLU; the conv is not touched
+    (Conv2d_Q.forward recognises the record on its input).  Opt-in: every call decides for itself (TrainBatchNormCodes2d), and
+    tensors of fewer than `min_elements` elements (None: batchnorm.CODES_MIN_ELEMENTS; 0: every size) stay float32.  Composes with
+    use_device_bn_train in either order.  Returns the number of links; unlink_codes_train undoes them."""
+    nested = {c for m in model.modules() if isinstance(m, nn.Sequential) for c in m._modules.values() if isinstance(c, nn.Sequential)}
+    done = 0
+    for seq in [m for m in model.modules() if isinstance(m, nn.Sequential) and m not in nested]:
+        leaves = list(_flat_slots(seq, model))
+        i = 0
+        while i + 2 < len(leaves):
+            (pb, nb, bn, o1), (pr, nr, relu, o2), (_, _, conv, o3) = leaves[i:i + 3]
+            stock = _bn_train_candidate(bn) and type(relu) is nn.ReLU
+            swapped = (isinstance(bn, TrainBatchNorm2d) and bn._relu and bn.momentum is not None and isinstance(relu, FoldedReLU)
+                       and getattr(relu, "_bn_train", False))
+            if not ((stock or swapped) and o1 and o2 and o3 and _is_conv_q(conv) and _link_conv_clean(conv)
+                    and all(len(_slots_of(model, m)) == 1 for m in (bn, relu, conv))):
+                i += 1
+                continue
+            pb._modules[nb] = TrainBatchNormCodes2d(bn, relu, conv, min_elements)
+            if stock:
+                folded = FoldedReLU(relu)
+                folded._codes_train = True
+                pr._modules[nr] = folded
+            done += 1
+            i += 3
+    return done
+
+
+def unlink_codes_train(model):
+    """Undo link_codes_train: every slot gets back what it held (the stock modules, or use_device_bn_train's wrappers), pointed at
+    the current parameters, buffers and training flag.  Returns the number of links undone."""
+    n = 0
+    for parent in list(model.modules()):
+        for name, child in list(parent._modules.items()):
+            if isinstance(child, TrainBatchNormCodes2d):
+                held = child._held[0]
+                stock = _repoint_bn(child)
+                if held is not stock:   # a TrainBatchNorm2d: the same Parameter and buffer objects again
+                    for key in ("weight", "bias"):
+                        held._parameters[key] = child._parameters[key]
+                    for key in _BN_NAMES:
+                        held._buffers[key] = child._buffers[key]
+                    held.training = child.training
+                parent._modules[name] = held
+                n += 1
+            elif isinstance(child, FoldedReLU) and getattr(child, "_codes_train", False):
+                parent._modules[name] = child.relu
     return n

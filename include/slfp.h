@@ -703,6 +703,43 @@ int slfp_bn_res_train_bwd(const float* x, const float* y, const float* gy, const
                           int64_t n, int64_t h, int64_t w, int64_t c, int x_layout,
                           void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- training-mode BatchNorm2d (+ReLU) that writes the next Conv2d_Q's codes (csrc/bn_train.hip, the code forms) -------------
+ * In conv -> BN -> ReLU -> conv (nets_imgnet/mobilenetv1.py:24-41) the next Conv2d_Q's first act is quantize_act(y / Ka)
+ * (utils/conv2d_func.py:21), a pure function of y; its weight gradient reads the same quantized value (the quantizers are
+ * straight-through estimators without a clipping mask, utils/sfp_quant.py:50-53, 99-102); and the BatchNorm backward needs of y
+ * only the ReLU's mask.  So the forward stores, instead of the float32 y, one byte per element: the extended code of the reader's
+ * quantizer (y_ka its Ka, y_qbits its q_bit, 8 or 7), and the backward recomputes the mask from x.  The contract is exact:
+ *   statistics save_mean, save_invstd and the running statistics are exactly those of slfp_bn_train_fwd on the same x: the same
+ *              split, the same sums, the same finalize.  save_lo[c] = f32(mean - save_mean) is an output, as in the LUT form.
+ *   forward    t = (((x - save_mean) - save_lo) * (save_invstd * gamma)) + beta, then relu: t < 0 ? 0 : t -- the y of
+ *              slfp_bn_train_fwd, bit for bit.  y_codes[i] = the byte slfp_encode_f32(y, y_ka, fmt(y_qbits) | SLFP_FMT_EXT) gives
+ *              element i, through the reader's threshold table (slfp_enc_table_ok(y_ka, fmt) must hold).  A NaN takes code 0x00,
+ *              as everywhere on the code path: the reader sees the tiny class where the float32 interface would hand it the NaN
+ *              (save_mean, save_invstd and the running statistics are NaN in the same places as in the plain form).  The apply
+ *              pass reads x once and writes one byte per element, a lane's four channels as one dword.
+ *   backward   g = relu ? (t > 0 ? gy : 0) : gy  with t recomputed from x, gamma, beta, save_mean, save_invstd and save_lo by the
+ *              forward's own expression; y > 0 holds exactly where t > 0, and no forward output is read.  From there gx, ggamma
+ *              and gbeta are bit-identical to slfp_bn_train_bwd(relu) given the plain forward's y.
+ *              ggamma and gbeta may be NULL.  The reduce pass reads x and gy; the dx pass reads x and gy and writes gx.
+ * No atomics; two calls give the same bits; a NaN or an inf stays in its channel.  Supported (slfp_bn_codes_train_supported: 1 / 0,
+ * host only): the set of slfp_bn_train_supported, and in addition c % 4 == 0, y_qbits 8 or 7, y_ka > 0 with a proven code table;
+ * everything else is SLFP_ERR_UNSUPPORTED (the backward, which is not told the reader, refuses c % 4 != 0).  Both take the
+ * workspace of slfp_bn_train_workspace_bytes and make the refusals of slfp_bn_train_fwd / slfp_bn_train_bwd in the same order
+ * before any device work, leaving the outputs untouched; save_lo counts among the per-channel arrays; y_codes (NULL:
+ * SLFP_ERR_BAD_ARG) needs 4-byte alignment (SLFP_ERR_ALIGNMENT, behind x).  y_codes may not alias x, gx not x.  n == 0 returns
+ * SLFP_OK.  Algorithmic traffic per element (computed from the code, not measured): forward 4 + 4 + 1 = 9 B against 12 B,
+ * backward 8 + 8 + 4 = 20 B against 28 B of the plain form. */
+int slfp_bn_codes_train_supported(int64_t n, int64_t h, int64_t w, int64_t c, int x_layout, float y_ka, int y_qbits);
+int slfp_bn_codes_train_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                            float momentum, float eps, int relu, float y_ka, int y_qbits, uint8_t* y_codes,
+                            float* save_mean, float* save_invstd, float* save_lo,
+                            int64_t n, int64_t h, int64_t w, int64_t c, int x_layout,
+                            void* workspace, size_t ws_bytes, void* stream);
+int slfp_bn_codes_train_bwd(const float* x, const float* gy, const float* gamma, const float* beta, const float* save_mean,
+                            const float* save_invstd, const float* save_lo, int relu, float* gx, float* ggamma, float* gbeta,
+                            int64_t n, int64_t h, int64_t w, int64_t c, int x_layout,
+                            void* workspace, size_t ws_bytes, void* stream);
+
 /* ---- self-check ------------------------------------------------------------------------
  * The kernels compute x / scale_div with an FMA correction chain on a host-computed
  * reciprocal instead of the IEEE division macro (csrc/slfp_device.hpp, ScaleDiv).  This
@@ -773,6 +810,19 @@ const char* slfp_conv2d_bwd_kernel_name_ex(const slfp_conv2d_desc* d, unsigned f
 size_t slfp_conv2d_bwd_workspace_bytes_ex(const slfp_conv2d_desc* d, unsigned flags, int need_gx, int need_gw);
 int slfp_conv2d_bwd_ex(const slfp_conv2d_desc* d, unsigned flags, const float* x, const float* w_oihw, const float* gy,
                        float* gx, float* gw_oihw, float* gb, void* workspace, void* stream);
+
+/* slfp_conv2d_bwd_ex with the activation operand as 1-byte codes: x_codes[i] = the byte slfp_encode_f32(x, d->ka,
+ * fmt(d->qbits) | SLFP_FMT_EXT) gives element i -- this layer's own Ka and q_bit, as a producer such as slfp_bn_codes_train_fwd
+ * stores them.  Both quantizers are pure straight-through estimators, so decode(code) is the operand of the weight gradient bit
+ * for bit: in all three families the x load becomes a byte load (a dword of four channels where the float path loads a float4)
+ * decoded through a 256-entry float32 table in LDS; the gx half never reads x.  gx, gw and gb are equal (as float32 values; +0
+ * and -0 alike) to slfp_conv2d_bwd_ex on any float32 x with these codes, except where x holds a NaN, which has no code (0x00,
+ * the tiny class).  New entry points, not a flag bit: `flags` means what it means for slfp_conv2d_bwd_ex, and the workspace and
+ * kernel names are those of the _ex queries.  x_codes: NHWC only, C_in % 4 == 0, 4-byte aligned (the other tensors 16-byte);
+ * NCHW x, C_in % 4 != 0 and whatever slfp_conv2d_bwd_ex refuses are SLFP_ERR_UNSUPPORTED / 0. */
+int slfp_conv2d_bwd_codes_supported(const slfp_conv2d_desc* d, unsigned flags);
+int slfp_conv2d_bwd_codes(const slfp_conv2d_desc* d, unsigned flags, const uint8_t* x_codes, const float* w_oihw,
+                          const float* gy, float* gx, float* gw_oihw, float* gb, void* workspace, void* stream);
 
 /* ---- layout helpers (the reference is NCHW; the kernels are NHWC) -------------------- */
 int slfp_nchw_to_nhwc_f32(const float* x, float* y, int64_t n, int64_t c, int64_t h, int64_t w, void* stream);
