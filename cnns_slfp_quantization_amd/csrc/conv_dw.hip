@@ -1,17 +1,15 @@
 // conv_dw.hip -- SLFP-quantized depthwise 3x3 convolution, NHWC, gfx950.
 //
-// Replaces Conv2d_Q.forward (utils/conv2d_func.py:20-25) for groups == C_in == C_out,
-// 3x3 kernels (the 13 "dw" layers of MobileNetV1, nets_imgnet/mobilenetv1.py:27).
-//
+// Replaces Conv2d_Q.forward (utils/conv2d_func.py:20-25) for groups == C_in == C_out, 3x3 kernels (the 13 "dw" layers of
+// MobileNetV1, nets_imgnet/mobilenetv1.py:27): the general kernel, every shape, bias and the fused layer-output quantizer.  The
+// arithmetic is stated in include/slfp.h, next to slfp_debug_dw3x3_instance; what the family shares is in conv_dw_core.hpp.
 // HBM-bound (1.7 flop/B): algorithmic traffic is 4 B read + 4 B written per element.
 //   * one workgroup = one (image, TH x TW output tile, CB-channel group);
 //   * LOAD phase: the (TH-1)*S+3 x (TW-1)*S+3 input halo tile is read from HBM with
 //     16-byte loads, channels across lanes (a pixel's CB channels are one contiguous
-//     128/256-byte segment), x/Ka + SLFP encode applied ONCE per element inline, and the
-//     dequantized float32 written to LDS (zero where the conv pads);
-//   * COMPUTE phase: every thread owns 4 channels (its 9x4 weights live in registers),
-//     reads 9 ds_read_b128 per output float4, FMAs in float32, rescales *Ka*Kw with the
-//     reference's two roundings, and stores 16 bytes.
+//     128/256-byte segment), quantized ONCE per element inline and written to LDS (zero where the conv pads);
+//   * COMPUTE phase: every thread owns 4 channels (its 9x4 weights live in registers), reads 9 ds_read_b128 per
+//     output float4 and stores 16 bytes.
 // For stride 2 the tile's columns are stored de-interleaved (even columns, then odd) so
 // that the 8 pixels a wave reads for one tap are contiguous in LDS (no bank conflicts).
 // Tried and dropped (same-box A/B, profiles/ab_compare.sh): keeping the 16-entry encode table in a VGPR and
@@ -20,8 +18,7 @@
 // compute loop by two (18 tap reads in flight per thread): 3 % slower at the same 94 VGPRs.
 // rocprof (profiles/r01a) showed HBM traffic already ideal (halo re-reads hit L2) and the
 // kernel VALU-bound, so all index arithmetic is incremental (no runtime div/mod in loops).
-#include "slfp_device.hpp"
-#include "slfp_host.hpp"
+#include "conv_dw_core.hpp"
 
 namespace slfp {
 
@@ -62,7 +59,7 @@ __global__ __launch_bounds__(kDwThreads) void k_dw3x3(const float* __restrict__ 
     constexpr int VSH = V == 4 ? 0 : 1;   // log2(4 / V): lanes per pixel double with 2-float lanes
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint32_t* sT = reinterpret_cast<uint32_t*>(smem);      // 16 dwords (long form) or the 2 KiB threshold table
-    constexpr int kTabBytes = TAB ? ((kEncEntries * 8 + 15) & ~15) : 64;
+    constexpr int kTabBytes = TAB ? kDwTabBytes : 64;
     float* tile = reinterpret_cast<float*>(smem + kTabBytes);     // [IH][IW][CB]
     if constexpr (TAB) enc_fill<kDwThreads>(reinterpret_cast<uint2*>(smem), p.enc);
     else lut_fill<FMT>(sT);
@@ -226,8 +223,9 @@ __global__ __launch_bounds__(kDwThreads) void k_dw3x3(const float* __restrict__ 
     }
 }
 
-// Everything launch_dw3x3 decides for k_dw3x3, worked out in ONE place (dw_select): the launcher only dispatches on it and
-// dw3x3_instance_name (slfp_debug_dw3x3_instance) prints it, so the reported string cannot drift from what runs.
+// Everything launch_dw3x3 decides for k_dw3x3, worked out in ONE place (dw_select).  dw_instance maps the selection to the kernel:
+// the launcher launches that pointer, and dw3x3_instance_name (slfp_debug_dw3x3_instance) asks for it before it prints, so a string
+// is only ever reported for an instance that exists and cannot drift from what runs.
 struct DwSel {
     int s;          // stride: template argument S
     int cbt, iwt;   // CBT / IWT: 32,16 | 64,9 | 32,15 for the geometry-specialised forms, 0,0 for the generic one
@@ -241,8 +239,7 @@ struct DwSel {
 static int dw_select(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post, DwParams* pp, DwSel* sel) {
     DwParams& p = *pp;
     p.post = post;
-    p.N = (int)d.n; p.H = (int)d.h; p.W = (int)d.w; p.C = (int)d.c_in;
-    p.Ho = (int)plan.h_out; p.Wo = (int)plan.w_out;
+    dw_fill_geom(p, d, plan);
     const int S = d.stride_h;
     // channel group: largest power-of-two multiple of 4 (<= 64) dividing C; channel counts that are
     // not a multiple of 32 (ShuffleNetV2: 24, 116, 232) get 32-wide groups with a ragged last one
@@ -266,21 +263,19 @@ static int dw_select(const slfp_conv2d_desc& d, const ConvPlan& plan, const Post
     p.cb4_shift = 0;   // log2(CB / 4); the 2-float kernels add 1
     while ((4 << p.cb4_shift) < CB) ++p.cb4_shift;
     p.cgroups = (int)ceil_div(p.C, CB);
-    p.pad = d.pad_h;
     p.IWh = (p.IW + 1) / 2;
     const bool v2 = (p.C % 4) != 0;   // even channel count (58): 8-byte lanes, twice as many lanes per pixel
     const int dp = kDwThreads >> (p.cb4_shift + (v2 ? 1 : 0));
     p.out_step_h = dp / p.TW; p.out_step_w = dp % p.TW;
     p.sd = make_scale_div(d.ka);
-    p.ka = d.ka; p.kw = d.kw_scale;
     if ((int64_t)p.H * p.W * p.C >= (1ll << 29) || (int64_t)p.Ho * p.Wo * p.C >= (1ll << 29))
         return fail(SLFP_ERR_UNSUPPORTED, "dw3x3: one image exceeds 2^29 elements");
     const int64_t nblocks = (int64_t)p.N * p.tiles_h * p.tiles_w * p.cgroups;
-    if (nblocks > 0x7FFFFFFF) return fail(SLFP_ERR_UNSUPPORTED, "dw3x3: grid too large");
+    if (const int rc = dw_grid_check(nblocks, "dw3x3")) return rc;
     p.nblocks = (uint32_t)nblocks;
     const EncArgs* tab = act_table(d.ka, plan.fmt_act, kEncF32);
     if (tab) p.enc = *tab;
-    sel->lds = (tab ? ((kEncEntries * 8 + 15) & ~15) : 64) + (size_t)p.IH * p.IW * p.CB * sizeof(float);
+    sel->lds = (tab ? kDwTabBytes : 64) + (size_t)p.IH * p.IW * p.CB * sizeof(float);
     if (sel->lds > 64 * 1024) return fail(SLFP_ERR_UNSUPPORTED, "dw3x3: tile needs %zu B of LDS", sel->lds);
     sel->s = S; sel->v = v2 ? 2 : 4; sel->tab = tab != nullptr; sel->a8 = plan.fmt_act == kFmtAct8;
     sel->lo = p.post.layerout && p.post.scale;   // fused layer-output quantizer: the generic-geometry instantiations only
@@ -293,15 +288,43 @@ static int dw_select(const slfp_conv2d_desc& d, const ConvPlan& plan, const Post
     return SLFP_OK;
 }
 
-static const char* dw_general_name(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post) {
+typedef void (*DwFn)(const float*, const float*, const float*, float*, const DwParams);
+template <int FMT, int S, int CBT, int IWT, int V, bool LO = false>
+static DwFn dw_instance_tab(const DwSel& s) { return s.tab ? k_dw3x3<FMT, S, CBT, IWT, V, LO, true> : k_dw3x3<FMT, S, CBT, IWT, V, LO>; }
+// one activation format, one lane width: the generic geometry with or without the fused layer-output quantizer at both strides, the
+// 14x14-tile form, and with 16-byte lanes the 7x7-image and the stride-2 form; each with the table and the long-form quantizer
+template <int FMT, int V>
+static DwFn dw_instance_geom(const DwSel& s) {
+    const int geom = s.s * 10000 + s.cbt * 100 + s.iwt;
+    if (s.lo) return geom == 10000 ? dw_instance_tab<FMT, 1, 0, 0, V, true>(s) : (geom == 20000 ? dw_instance_tab<FMT, 2, 0, 0, V, true>(s) : nullptr);
+    if (geom == 10000) return dw_instance_tab<FMT, 1, 0, 0, V>(s);
+    if (geom == 20000) return dw_instance_tab<FMT, 2, 0, 0, V>(s);
+    if (geom == 13216) return dw_instance_tab<FMT, 1, 32, 16, V>(s);
+    if constexpr (V == 4) {
+        if (geom == 16409) return dw_instance_tab<FMT, 1, 64, 9, 4>(s);
+        if (geom == 23215) return dw_instance_tab<FMT, 2, 32, 15, 4>(s);
+    }
+    return nullptr;
+}
+static DwFn dw_instance(const DwSel& s) {
+    if (s.v == 4) return s.a8 ? dw_instance_geom<kFmtAct8, 4>(s) : dw_instance_geom<kFmtSfp7, 4>(s);
+    if (s.v == 2) return s.a8 ? dw_instance_geom<kFmtAct8, 2>(s) : dw_instance_geom<kFmtSfp7, 2>(s);
+    return nullptr;
+}
+
+static const char* dw_sel_name(const DwSel& s) {
     static thread_local char buf[64];
-    DwParams p;
-    DwSel s;
-    if (dw_select(d, plan, post, &p, &s) != SLFP_OK) return "none";
     snprintf(buf, sizeof buf, "general/s%d/%s/v%d/%s/%s%s", s.s,
              s.cbt == 0 ? "gen" : (s.cbt == 64 ? "cb64iw9" : (s.iwt == 16 ? "cb32iw16" : "cb32iw15")), s.v, s.tab ? "tab" : "long",
              s.a8 ? "act8" : "sfp7", s.lo ? "/lo" : "");
     return buf;
+}
+
+static const char* dw_general_name(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post) {
+    DwParams p;
+    DwSel s;
+    if (dw_select(d, plan, post, &p, &s) != SLFP_OK || !dw_instance(s)) return "none";
+    return dw_sel_name(s);
 }
 
 const char* dw3x3_instance_name(const slfp_conv2d_desc& d, const ConvPlan& plan, bool has_bias, const PostOp& post) {
@@ -320,36 +343,7 @@ int launch_dw3x3(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x
     DwSel s;
     const int rc = dw_select(d, plan, post, &p, &s);
     if (rc != SLFP_OK) return rc;
-    const size_t lds = s.lds;
-#define SLFP_DW_LAUNCH(FMT, SS, CBT, IWT, VV) \
-    do { if (s.tab) hipLaunchKernelGGL((k_dw3x3<FMT, SS, CBT, IWT, VV, false, true>), dim3(p.nblocks), dim3(kDwThreads), lds, stream, x, wq9c, bias, y, p); \
-         else hipLaunchKernelGGL((k_dw3x3<FMT, SS, CBT, IWT, VV>), dim3(p.nblocks), dim3(kDwThreads), lds, stream, x, wq9c, bias, y, p); } while (0)
-#define SLFP_DW_LAUNCH_LO(FMT, SS, VV) \
-    do { if (s.tab) hipLaunchKernelGGL((k_dw3x3<FMT, SS, 0, 0, VV, true, true>), dim3(p.nblocks), dim3(kDwThreads), lds, stream, x, wq9c, bias, y, p); \
-         else hipLaunchKernelGGL((k_dw3x3<FMT, SS, 0, 0, VV, true>), dim3(p.nblocks), dim3(kDwThreads), lds, stream, x, wq9c, bias, y, p); } while (0)
-#define SLFP_DW_BY_FMT(SS, CBT, IWT, VV) \
-    do { if (s.a8) SLFP_DW_LAUNCH(kFmtAct8, SS, CBT, IWT, VV); else SLFP_DW_LAUNCH(kFmtSfp7, SS, CBT, IWT, VV); } while (0)
-    const bool v2 = s.v == 2;
-    if (s.lo) {
-        if (s.a8) { if (s.s == 1) { if (v2) SLFP_DW_LAUNCH_LO(kFmtAct8, 1, 2); else SLFP_DW_LAUNCH_LO(kFmtAct8, 1, 4); }
-                    else          { if (v2) SLFP_DW_LAUNCH_LO(kFmtAct8, 2, 2); else SLFP_DW_LAUNCH_LO(kFmtAct8, 2, 4); } }
-        else      { if (s.s == 1) { if (v2) SLFP_DW_LAUNCH_LO(kFmtSfp7, 1, 2); else SLFP_DW_LAUNCH_LO(kFmtSfp7, 1, 4); }
-                    else          { if (v2) SLFP_DW_LAUNCH_LO(kFmtSfp7, 2, 2); else SLFP_DW_LAUNCH_LO(kFmtSfp7, 2, 4); } }
-    }
-    else if (v2) {
-        if (s.cbt == 32 && s.iwt == 16) SLFP_DW_BY_FMT(1, 32, 16, 2);
-        else if (s.s == 1) SLFP_DW_BY_FMT(1, 0, 0, 2);
-        else SLFP_DW_BY_FMT(2, 0, 0, 2);
-    }
-    else if (s.cbt == 32 && s.iwt == 16) SLFP_DW_BY_FMT(1, 32, 16, 4);
-    else if (s.cbt == 64 && s.iwt == 9) SLFP_DW_BY_FMT(1, 64, 9, 4);
-    else if (s.cbt == 32 && s.iwt == 15) SLFP_DW_BY_FMT(2, 32, 15, 4);
-    else if (s.s == 1) SLFP_DW_BY_FMT(1, 0, 0, 4);
-    else SLFP_DW_BY_FMT(2, 0, 0, 4);
-#undef SLFP_DW_BY_FMT
-#undef SLFP_DW_LAUNCH_LO
-#undef SLFP_DW_LAUNCH
-    return check_launch("slfp dw3x3 kernel");
+    return dw_launch(dw_instance(s), "dw3x3", dw_sel_name(s), p.nblocks, kDwThreads, s.lds, stream, "slfp dw3x3 kernel", x, wq9c, bias, y, p);
 }
 
 }  // namespace slfp

@@ -1,9 +1,8 @@
 // conv_dw3.hip -- SLFP-quantized depthwise 3x3 convolution, stride 2, NHWC, gfx950: the register-window ("rows") kernel.
 //
-// Same layers and the same arithmetic as conv_dw2.hip (float32 in, float32 out, input quantized once per loaded element by
-// the threshold table, float32 FMAs from +0 in (kh, kw) order, (acc * Ka) * Kw, fused scale / shift, ReLU): outputs are
-// bit-identical to k_dw3x3_tile.  What differs is where the quantized values live.  Stride-2 windows overlap by one row and
-// one column only, so the LDS halo tile of conv_dw2.hip buys little reuse there and costs a 32 KiB tile (4 workgroups per CU),
+// The stride-2 layers of conv_dw2.hip, float32 in and out, outputs bit-identical to k_dw3x3_tile (arithmetic: include/slfp.h, next
+// to slfp_debug_dw3x3_instance; shared steps: conv_dw_core.hpp).  What differs is where the quantized values live.  Stride-2 windows
+// overlap by one row and one column only, so the LDS halo tile of conv_dw2.hip buys little reuse there and costs a 32 KiB tile (4 workgroups per CU),
 // two barriers, an LDS write per input and 9 LDS reads per output on top of the table lookups -- and the LDS is what that
 // kernel keeps busiest (profiles/r04a_summary.md).  Here, as in conv_dwc.hip, the window lives in registers:
 //   * one WAVE = one (image, 7 x 7 output tile, 32-channel group), the tile kernel's workgroup: lane = (column group g = 0..7,
@@ -19,15 +18,12 @@
 //   * loads and stores go through per-image buffer descriptors with out-of-range offsets for padding, ragged edges, the halo
 //     group and idle waves (Q(0) == 0: a padded tap takes the same path), so the body is one straight line, fully unrolled;
 //   * LDS holds the 2 KiB threshold table only; one barrier after its fill, none after.
-#include "slfp_device.hpp"
-#include "slfp_enc.hpp"
-#include "slfp_host.hpp"
+#include "conv_dw_core.hpp"
 
 namespace slfp {
 
 constexpr int kDwrThreads = 256;
 constexpr int kDwrWaves = kDwrThreads / 64;
-constexpr int kDwrTab = (kEncEntries * 8 + 15) & ~15;   // LDS bytes of the threshold table
 constexpr int kDwrTile = 7;                              // output tile: 7 x 7, as conv_dw2.hip at stride 2
 
 struct DwrParams {
@@ -42,12 +38,8 @@ struct DwrParams {
     EncArgs enc;
 };
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4r __attribute__((ext_vector_type(4)));
-
 // TH: output rows a wave walks down; POST: fused per-channel scale / shift.
-// Row / column validity is one select each on the row and the column part of the byte offset: the parts are >= 2^30 when
-// invalid, so their sum is beyond the descriptor (one image: at most 2^30 bytes, dw3x3_rows_applicable).
+// Row / column validity is one select each on the row and the column part of the byte offset (kDwBadRow / kDwBadCol).
 template <int TH, bool POST>
 __global__ __launch_bounds__(kDwrThreads, 4) void k_dw3x3_rows(const float* __restrict__ x, const float* __restrict__ wq,
                                                                float* __restrict__ y, const DwrParams p) {
@@ -56,7 +48,7 @@ __global__ __launch_bounds__(kDwrThreads, 4) void k_dw3x3_rows(const float* __re
     constexpr int RING = 3 + S;
 
     // static LDS at address 0: every table lookup is `ds_read_b64 v, bin` (conv_dw2.hip)
-    __shared__ __attribute__((aligned(16))) unsigned char smem[kDwrTab];
+    __shared__ __attribute__((aligned(16))) unsigned char smem[kDwTabBytes];
     enc_fill<kDwrThreads>(reinterpret_cast<uint2*>(smem), p.enc);
     const float r1 = p.enc.r1, lo = p.enc.lo, hi = p.enc.hi;
 
@@ -72,18 +64,13 @@ __global__ __launch_bounds__(kDwrThreads, 4) void k_dw3x3_rows(const float* __re
     const int c = cg * 32 + (lane & 7) * 4;
 
     // this lane's 4 channels x 9 taps, fused BN vectors (requested before the input rows: they return first)
-    f32x4 wt[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) wt[k] = *reinterpret_cast<const f32x4*>(wq + (uint32_t)(k * p.C + c));
-    f32x4 psc = {1.f, 1.f, 1.f, 1.f}, psh = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (POST) {
-        psc = *reinterpret_cast<const f32x4*>(p.post.scale + c);
-        psh = *reinterpret_cast<const f32x4*>(p.post.shift + c);
-    }
+    f32x4 wt[9], psc, psh;
+    dw_load_taps(wt, wq, (uint32_t)p.C, c);
+    dw_load_bn<POST>(psc, psh, p.post.scale, p.post.shift, c);
 
     const uint32_t img_in = (uint32_t)(p.H * p.W * p.C) * 4u, img_out = (uint32_t)(p.Ho * p.Wo * p.C) * 4u;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x + (size_t)n * (img_in / 4u)), 0, img_in, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(y + (size_t)n * (img_out / 4u), 0, img_out, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = dw_rsrc(x + (size_t)n * (img_in / 4u), img_in);
+    const __amdgpu_buffer_rsrc_t ry = dw_rsrc(y + (size_t)n * (img_out / 4u), img_out);
 
     // an idle wave starts so far above the image that none of its rows is in range
     const int ih0 = valid ? th * TH * S - p.pad : -0x40000000;
@@ -91,13 +78,13 @@ __global__ __launch_bounds__(kDwrThreads, 4) void k_dw3x3_rows(const float* __re
     const uint32_t rstep = (uint32_t)(p.W * p.C) * 4u;
     const uint32_t rowb = (uint32_t)ih0 * rstep + (uint32_t)c * 4u;   // wraps for negative rows: only used in range
     uint32_t coff[2];   // the halo group needs its first column only
-    coff[0] = (unsigned)iw0 < (unsigned)p.W ? (uint32_t)(iw0 * p.C) * 4u : 0x40000000u;
-    coff[1] = (g < TW && (unsigned)(iw0 + 1) < (unsigned)p.W) ? (uint32_t)((iw0 + 1) * p.C) * 4u : 0x40000000u;
+    coff[0] = (unsigned)iw0 < (unsigned)p.W ? (uint32_t)(iw0 * p.C) * 4u : kDwBadCol;
+    coff[1] = (g < TW && (unsigned)(iw0 + 1) < (unsigned)p.W) ? (uint32_t)((iw0 + 1) * p.C) * 4u : kDwBadCol;
     const int nb_addr = ((lane + 8) & 63) * 4;   // ds_bpermute address of the right neighbour's lane
 
     f32x4 win[RING][3];   // input row j lives in slot j % RING: columns 0 / 1 requested raw and quantized in place, column 2 fetched
     auto request = [&](const int j) {
-        const uint32_t roff = (unsigned)(ih0 + j) < (unsigned)p.H ? rowb + (uint32_t)j * rstep : 0x80000000u;
+        const uint32_t roff = (unsigned)(ih0 + j) < (unsigned)p.H ? rowb + (uint32_t)j * rstep : kDwBadRow;
 #pragma unroll
         for (int k = 0; k < 2; ++k)
             win[j % RING][k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, roff + coff[k], 0, (SLFP_NT_DW & 1) ? 2 : 0));
@@ -154,7 +141,7 @@ __global__ __launch_bounds__(kDwrThreads, 4) void k_dw3x3_rows(const float* __re
 
     const int oh0 = th * TH;
     const uint32_t ostep = (uint32_t)(p.Wo * p.C) * 4u;
-    const uint32_t ocol = (valid && g < TW && ow < p.Wo) ? (uint32_t)((oh0 * p.Wo + ow) * p.C + c) * 4u : 0x80000000u;
+    const uint32_t ocol = (valid && g < TW && ow < p.Wo) ? (uint32_t)((oh0 * p.Wo + ow) * p.C + c) * 4u : kDwBadRow;
 
     __syncthreads();   // threshold table visible
 
@@ -162,28 +149,9 @@ __global__ __launch_bounds__(kDwrThreads, 4) void k_dw3x3_rows(const float* __re
 #pragma unroll
     for (int r = 0; r < TH; ++r) {
         quantize(r * S + 3 - S, S);   // the S rows this step adds
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh) {
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-                const f32x4 a = win[(r * S + kh) % RING][kw];
-                const f32x4 w = wt[kh * 3 + kw];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[e] = fmaf(a[e], w[e], acc[e]);
-            }
-        }
-        f32x4 rr;   // (out * Ka) * Kw: two float32 roundings, as utils/conv2d_func.py:24; then the fused BN / ReLU
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float u = (acc[e] * p.ka) * p.kw;
-            if constexpr (POST) u = __builtin_fmaf(u, psc[e], psh[e]);
-            if (p.post.relu) u = fmaxf(u, 0.f);
-            rr[e] = u;
-        }
-        const uint32_t so = ocol + ((oh0 + r) < p.Ho ? (uint32_t)r * ostep : 0x40000000u);
-        if (p.nt_out) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4r, rr), ry, so, 0, 2);
-        else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4r, rr), ry, so, 0, 0);
+        const f32x4 acc = dw_mac9(wt, [&](const int kh, const int kw) { return win[(r * S + kh) % RING][kw]; });
+        const f32x4 rr = dw_finish<POST>(acc, p.ka, p.kw, psc, psh, p.post.relu);
+        dw_store16(rr, ry, ocol + ((oh0 + r) < p.Ho ? (uint32_t)r * ostep : kDwBadCol), p.nt_out);
         // rows r*S .. r*S + S - 1 are dead now: their slots take the rows of the step after the next
 #pragma unroll
         for (int j = r * S + RING; j < r * S + RING + S && j < NR; ++j) request(j);
@@ -203,12 +171,18 @@ bool dw3x3_rows_applicable(const slfp_conv2d_desc& d, const ConvPlan& plan, cons
     return (((sw < 0) ? kDwrRule : sw) >> dw_rows_class(plan.h_out, plan.w_out)) & 1;
 }
 
-// What launch_dw3x3_rows chooses among k_dw3x3_rows' instances: the launcher dispatches on it, dw3x3_rows_name prints it.
+// What launch_dw3x3_rows chooses among k_dw3x3_rows' instances.  dwr_instance maps it to the kernel: the launcher launches that
+// pointer and dw3x3_rows_name asks for it before it prints (conv_dw2.hip).
 struct DwrSel { bool post; };   // template argument POST (TH is kDwrTile)
 static DwrSel dwr_select(const PostOp& post) { return DwrSel{post.scale != nullptr}; }
 
+typedef void (*DwrFn)(const float*, const float*, float*, const DwrParams);
+static DwrFn dwr_instance(const DwrSel& s) { return s.post ? k_dw3x3_rows<kDwrTile, true> : k_dw3x3_rows<kDwrTile, false>; }
+static const char* dwr_sel_name(const DwrSel& s) { return s.post ? "rows/post" : "rows/plain"; }
+
 const char* dw3x3_rows_name(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post) {
-    return dwr_select(post).post ? "rows/post" : "rows/plain";
+    const DwrSel s = dwr_select(post);
+    return dwr_instance(s) ? dwr_sel_name(s) : "none";
 }
 
 int launch_dw3x3_rows(const slfp_conv2d_desc& d, const ConvPlan& plan, const float* x, const float* wq9c,
@@ -216,21 +190,18 @@ int launch_dw3x3_rows(const slfp_conv2d_desc& d, const ConvPlan& plan, const flo
     DwrParams p;
     const DwrSel sel = dwr_select(post);
     p.post = post;
-    p.N = (int)d.n; p.H = (int)d.h; p.W = (int)d.w; p.C = (int)d.c_in;
-    p.Ho = (int)plan.h_out; p.Wo = (int)plan.w_out; p.pad = d.pad_h;
+    dw_fill_geom(p, d, plan);
     p.cgs = p.C / 32;
     p.tiles_h = (int)ceil_div(p.Ho, kDwrTile);
     p.tiles_w = (int)ceil_div(p.Wo, kDwrTile);
     const int64_t ntasks = (int64_t)p.N * p.tiles_h * p.tiles_w * p.cgs;
-    if (ntasks > 0x7FFFFFFF) return fail(SLFP_ERR_UNSUPPORTED, "dw3x3 (rows): grid too large");
+    if (const int rc = dw_grid_check(ntasks, "dw3x3 (rows)")) return rc;
     p.ntasks = (uint32_t)ntasks;
     p.nblocks = (uint32_t)ceil_div(ntasks, kDwrWaves);
-    p.ka = d.ka; p.kw = d.kw_scale;
-    p.nt_out = ((SLFP_NT_DW & 2) && (int64_t)p.N * p.Ho * p.Wo * p.C * 4 >= (switches().dw_nt_min_mb << 20)) ? 1 : 0;
+    p.nt_out = dw_nt_out((int64_t)p.N * p.Ho * p.Wo * p.C * 4);
     p.enc = *act_table(d.ka, plan.fmt_act, kEncF32);
-    if (sel.post) hipLaunchKernelGGL((k_dw3x3_rows<kDwrTile, true>), dim3(p.nblocks), dim3(kDwrThreads), 0, stream, x, wq9c, y, p);
-    else hipLaunchKernelGGL((k_dw3x3_rows<kDwrTile, false>), dim3(p.nblocks), dim3(kDwrThreads), 0, stream, x, wq9c, y, p);
-    return check_launch("slfp dw3x3 (rows) kernel");
+    return dw_launch(dwr_instance(sel), "dw3x3 (rows)", dwr_sel_name(sel), p.nblocks, kDwrThreads, 0, stream, "slfp dw3x3 (rows) kernel",
+                     x, wq9c, y, p);
 }
 
 }  // namespace slfp

@@ -1,12 +1,10 @@
 // conv_dwc.hip -- SLFP-quantized depthwise 3x3 convolution on 1-byte activation codes, NHWC, gfx950.
 //
-// Replaces Conv2d_Q.forward (utils/conv2d_func.py:20-25) for groups == C_in == C_out, 3x3, stride 1 / 2 (the 13 "dw"
-// layers of MobileNetV1, nets_imgnet/mobilenetv1.py:27) when the layer sits INSIDE a chain of quantized convolutions
-// (csrc/slfp_codes.hpp): its input arrives as the codes the previous layer's epilogue wrote -- input_q = QA(x / Ka) is
-// already applied, utils/conv2d_func.py:21 -- and its output leaves as the codes of the NEXT layer's QA(. / Ka_next)
-// (or as float32 when it is the last of the chain).  Same arithmetic as conv_dw2.hip step for step: float32 FMAs over
-// the decoded values in (kh, kw) order from +0, (acc * Ka) * Kw, fused BatchNorm + ReLU; outputs are bit-identical to the
-// float32-interface kernel fed with the decoded tensor.
+// The depthwise 3x3 layers, stride 1 / 2 (the 13 "dw" layers of MobileNetV1, nets_imgnet/mobilenetv1.py:27), INSIDE a chain of
+// quantized convolutions (csrc/slfp_codes.hpp): the input arrives as the codes the previous layer's epilogue wrote (QA(x / Ka) is
+// already applied), the output leaves as the codes of the NEXT layer's QA(. / Ka_next), or as float32 at the end of the chain.
+// The arithmetic is the family's (include/slfp.h, next to slfp_debug_dw3x3_instance; shared steps: conv_dw_core.hpp) over the decoded
+// values: outputs are bit-identical to the float32-interface kernel fed with the decoded tensor.
 //
 // Structure: no LDS tile, no barrier after the prologue.  At 1 B per element a pixel's channels are too few bytes for the
 // (pixel slot, 32-channel group) lanes of conv_dw2.hip (32-byte pieces), so here a lane owns 4 channels of ONE output
@@ -19,16 +17,13 @@
 //   * decode = 1 VALU + 1 LDS lookup per element (256-entry table), encode = 5 VALU + 1 LDS (slfp_codes.hpp).
 // The 3 columns of a lane overlap its neighbours' (they hit the same lines in L1); the redundancy is in decode
 // instructions, not in HBM bytes.
-#include "slfp_device.hpp"
-#include "slfp_enc.hpp"
 #include "slfp_codes.hpp"
 #include "slfp_layerout_lut.hpp"
-#include "slfp_host.hpp"
+#include "conv_dw_core.hpp"
 
 namespace slfp {
 
 constexpr int kDwcThreads = 256;
-constexpr uint32_t kDwcOob = 0xFFFFFFF0u;
 
 struct DwcParams {
     int N, H, W, C, Ho, Wo, pad;
@@ -46,24 +41,20 @@ struct DwcParams {
     EncArgs enc;          // YC: code table of the consumer's Ka (kEncCode)
 };
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
-
 // S: stride; LCS: log2(lanes across channels) = 3 / 4 / 5 for C = 32 / 64 / >= 128; TH x TW: output rows x columns per lane;
 // YC: output as codes (else float32); POST: fused per-channel scale / shift; SIGNED: no ReLU before the output quantizer.
 // LUTQ (YC, POST; slfp_conv2d_fwd_codes_lut): the code is the byte table's entry for the layer-output class of the affine's
 // result (slfp_layerout_lut.hpp); the table (4.8 KiB) takes the place of the reader's threshold table in LDS -- the kernel
 // keeps 1 KiB besides it, and a lookup is one ds_read_u8 next to the decode lookups it already issues.
 // VALU-issue-bound (profiles/r03c*): what is counted is instructions per output element.  A lane's TW adjacent columns
-// share TW + 2 decoded input columns; row / column validity is one select each on the row and the column part of the
-// offset (the parts are >= 2^30 when invalid, so their sum is out of the descriptor's range: tensors are < 1 GiB).
+// share TW + 2 decoded input columns; row / column validity is one select each on the row and the column part of the offset.
 template <int S, int LCS, int TH, int TW, bool YC, bool POST, bool SIGNED, bool LUTQ = false>
 __global__ __launch_bounds__(kDwcThreads) void k_dwc(const uint8_t* __restrict__ x, const float* __restrict__ wq,
                                                      void* __restrict__ y, const DwcParams p) {
     constexpr int LC = 1 << LCS;
     constexpr int NR = (TH - 1) * S + 3, NC = (TW - 1) * S + 3;
     static_assert(!LUTQ || (YC && POST && SIGNED), "the table epilogue writes codes behind an affine; the ReLU lies in the table");
-    __shared__ __attribute__((aligned(16))) unsigned char senc[LUTQ ? kLayeroutLutBytes : (YC ? ((kEncEntries * 8 + 15) & ~15) : 16)];
+    __shared__ __attribute__((aligned(16))) unsigned char senc[LUTQ ? kLayeroutLutBytes : (YC ? kDwTabBytes : 16)];
     __shared__ __attribute__((aligned(16))) uint32_t sdec[256];
     if constexpr (LUTQ) layerout_lut_fill<kDwcThreads>(senc, enc_carried_ptr(p.enc));
     else if constexpr (YC) enc_fill<kDwcThreads>(reinterpret_cast<uint2*>(senc), p.enc);
@@ -85,7 +76,7 @@ __global__ __launch_bounds__(kDwcThreads) void k_dwc(const uint8_t* __restrict__
     uint32_t raw[NR][NC];
     {
         const uint32_t in_bytes = (uint32_t)p.N * p.H * p.W * p.C;
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(x), 0, in_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs = dw_rsrc(x, in_bytes);
         const int ih0 = rt * TH * S - p.pad, iw0 = ow0 * S - p.pad;
         const uint32_t rowb = (uint32_t)(n * p.H + ih0) * (uint32_t)(p.W * p.C) + (uint32_t)c;   // wraps for negative rows: only used in range
         const uint32_t rstep = (uint32_t)(p.W * p.C);
@@ -94,12 +85,12 @@ __global__ __launch_bounds__(kDwcThreads) void k_dwc(const uint8_t* __restrict__
 #pragma unroll
         for (int j = 0; j < NR; ++j) {
             rok[j] = valid && (unsigned)(ih0 + j) < (unsigned)p.H;
-            roff[j] = rok[j] ? rowb + (uint32_t)j * rstep : 0x80000000u;
+            roff[j] = rok[j] ? rowb + (uint32_t)j * rstep : kDwBadRow;
         }
 #pragma unroll
         for (int k = 0; k < NC; ++k) {
             cok[k] = (unsigned)(iw0 + k) < (unsigned)p.W;
-            coff[k] = cok[k] ? (uint32_t)((iw0 + k) * p.C) : 0x40000000u;
+            coff[k] = cok[k] ? (uint32_t)((iw0 + k) * p.C) : kDwBadCol;
         }
 #pragma unroll
         for (int j = 0; j < NR; ++j)
@@ -112,25 +103,20 @@ __global__ __launch_bounds__(kDwcThreads) void k_dwc(const uint8_t* __restrict__
     }
 
     // this lane's 4 channels x 9 taps, fused BN vectors
-    f32x4 wt[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) wt[k] = *reinterpret_cast<const f32x4*>(wq + (uint32_t)(k * p.C + c));
-    f32x4 psc = {1.f, 1.f, 1.f, 1.f}, psh = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (POST) {
-        psc = *reinterpret_cast<const f32x4*>(p.post_scale + c);
-        psh = *reinterpret_cast<const f32x4*>(p.post_shift + c);
-    }
+    f32x4 wt[9], psc, psh;
+    dw_load_taps(wt, wq, (uint32_t)p.C, c);
+    dw_load_bn<POST>(psc, psh, p.post_scale, p.post_shift, c);
     __syncthreads();   // tables visible
 
     const uint32_t out_bytes = (uint32_t)p.N * p.Ho * p.Wo * p.C * (YC ? 1u : 4u);
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(y, 0, out_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ry = dw_rsrc(y, out_bytes);
     const int oh0 = rt * TH;
     const uint32_t ostep = (uint32_t)(p.Wo * p.C) * (YC ? 1u : 4u);
     uint32_t ocol[TW];
 #pragma unroll
     for (int q = 0; q < TW; ++q)
         ocol[q] = (valid && ow0 + q < p.Wo) ? (((uint32_t)(n * p.Ho + oh0) * (uint32_t)p.Wo + (uint32_t)(ow0 + q)) * (uint32_t)p.C + (uint32_t)c) * (YC ? 1u : 4u)
-                                            : 0x80000000u;
+                                            : kDwBadRow;
     const float r1 = p.enc.r1, lo = p.enc.lo, hi = p.enc.hi;
 
     float4 win[3][NC];   // ring of decoded input rows: row j lives in slot j % 3
@@ -144,7 +130,7 @@ __global__ __launch_bounds__(kDwcThreads) void k_dwc(const uint8_t* __restrict__
         for (int j = r * S + 3 - S; j < r * S + 3; ++j)   // the S rows this step adds
 #pragma unroll
             for (int k = 0; k < NC; ++k) win[j % 3][k] = dec4_f32(raw[j][k], dtab);
-        const uint32_t orow = (oh0 + r) < p.Ho ? (uint32_t)r * ostep : 0x40000000u;
+        const uint32_t orow = (oh0 + r) < p.Ho ? (uint32_t)r * ostep : kDwBadCol;
 #pragma unroll
         for (int q = 0; q < TW; ++q) {
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -158,13 +144,8 @@ __global__ __launch_bounds__(kDwcThreads) void k_dwc(const uint8_t* __restrict__
                     acc[2] = fmaf(a.z, w[2], acc[2]); acc[3] = fmaf(a.w, w[3], acc[3]);
                 }
             }
-            f32x4 rr;   // (out * Ka) * Kw: two float32 roundings, as utils/conv2d_func.py:24; then the fused BN / ReLU
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float u = (acc[e] * p.ka) * p.kw;
-                if constexpr (POST) u = __builtin_fmaf(u, psc[e], psh[e]);
-                rr[e] = u;
-            }
+            // no ReLU here: with code output it is the quantizer's (or the table's); the float32 form keeps its branch around four max below
+            f32x4 rr = dw_finish<POST>(acc, p.ka, p.kw, psc, psh, 0);
             const uint32_t so = ocol[q] + orow;
             if constexpr (YC) {
                 uint32_t code;
@@ -181,7 +162,7 @@ __global__ __launch_bounds__(kDwcThreads) void k_dwc(const uint8_t* __restrict__
                 __builtin_amdgcn_raw_buffer_store_b32(code, ry, so, 0, 0);
             } else {
                 if (p.relu) { rr[0] = fmaxf(rr[0], 0.f); rr[1] = fmaxf(rr[1], 0.f); rr[2] = fmaxf(rr[2], 0.f); rr[3] = fmaxf(rr[3], 0.f); }
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, rr), ry, so, 0, 0);
+                dw_store16(rr, ry, so, 0);
             }
         }
     }
@@ -196,8 +177,8 @@ bool dwc_applicable(const slfp_conv2d_desc& d, const ConvPlan& plan, const float
     return in_b < (1ull << 30) && out_b < (1ull << 30);   // offsets: bit 30 / 31 mark an invalid column / row
 }
 
-// What launch_dwc chooses among k_dwc's instances (and the one runtime format word): the launcher dispatches on it, dwc_instance_name
-// (slfp_debug_dw3x3_instance) prints it.
+// What launch_dwc chooses among k_dwc's instances (and the one runtime format word).  dwc_instance maps it to the kernel: the
+// launcher launches that pointer and dwc_instance_name (slfp_debug_dw3x3_instance) asks for it before it prints.
 struct DwcSel {
     int s;          // S; TH x TW = 7 x 2 (stride 1) / 4 x 1 (stride 2) follow from it
     int lcs;        // LCS
@@ -218,13 +199,38 @@ static int dwc_select(const slfp_conv2d_desc& d, const ConvPlan& plan, const Pos
     return SLFP_OK;
 }
 
-const char* dwc_instance_name(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post, const CodeIo& io) {
+typedef void (*DwcFn)(const uint8_t*, const float*, void*, const DwcParams);
+// the 7 output forms of one (S, LCS) geometry: the table epilogue; codes with / without BatchNorm, signed / ReLU-folded; float32
+template <int S, int LCS, int TH, int TW>
+static DwcFn dwc_instance_form(const DwcSel& s) {
+    if (s.lut) return (s.yc && s.post && s.sgn) ? k_dwc<S, LCS, TH, TW, true, true, true, true> : nullptr;
+    if (!s.yc) return s.sgn ? nullptr : (s.post ? k_dwc<S, LCS, TH, TW, false, true, false> : k_dwc<S, LCS, TH, TW, false, false, false>);
+    if (s.post) return s.sgn ? k_dwc<S, LCS, TH, TW, true, true, true> : k_dwc<S, LCS, TH, TW, true, true, false>;
+    return s.sgn ? k_dwc<S, LCS, TH, TW, true, false, true> : k_dwc<S, LCS, TH, TW, true, false, false>;
+}
+static DwcFn dwc_instance(const DwcSel& s) {
+    switch (s.s * 10 + s.lcs) {   // TH x TW = 7 x 2 (stride 1) / 4 x 1 (stride 2), as launch_dwc's tile counts
+        case 13: return dwc_instance_form<1, 3, 7, 2>(s);
+        case 14: return dwc_instance_form<1, 4, 7, 2>(s);
+        case 15: return dwc_instance_form<1, 5, 7, 2>(s);
+        case 23: return dwc_instance_form<2, 3, 4, 1>(s);
+        case 24: return dwc_instance_form<2, 4, 4, 1>(s);
+        case 25: return dwc_instance_form<2, 5, 4, 1>(s);
+        default: return nullptr;
+    }
+}
+
+static const char* dwc_sel_name(const DwcSel& s) {
     static thread_local char buf[64];
-    DwcSel s;
-    if (plan.family != kDw3x3 || dwc_select(d, plan, post, io, &s) != SLFP_OK) return "none";
     snprintf(buf, sizeof buf, "dwc/s%d/lc%d/%s/%s/%s", s.s, s.lcs, s.lut ? "lut" : (!s.yc ? "f32" : (s.sgn ? "yc-signed" : "yc")),
              s.post ? "post" : "plain", s.fmt_in == kFmtSfp7 ? "sfp7" : "act8");
     return buf;
+}
+
+const char* dwc_instance_name(const slfp_conv2d_desc& d, const ConvPlan& plan, const PostOp& post, const CodeIo& io) {
+    DwcSel s;
+    if (plan.family != kDw3x3 || dwc_select(d, plan, post, io, &s) != SLFP_OK || !dwc_instance(s)) return "none";
+    return dwc_sel_name(s);
 }
 
 // io.y_codes: output codes for a consumer with scale io.y_ka and format io.y_fmt (kFmtAct8 | kFmtSfp7); else float32
@@ -233,54 +239,29 @@ int launch_dwc(const slfp_conv2d_desc& d, const ConvPlan& plan, const uint8_t* x
     DwcSel sel;
     const int src = dwc_select(d, plan, post, io, &sel);
     if (src != SLFP_OK) return src;
-    const bool y_codes = sel.yc;
     DwcParams p;
-    p.N = (int)d.n; p.H = (int)d.h; p.W = (int)d.w; p.C = (int)d.c_in;
-    p.Ho = (int)plan.h_out; p.Wo = (int)plan.w_out; p.pad = d.pad_h;
-    const int S = sel.s;
-    const int TH = S == 2 ? 4 : 7, TW = S == 2 ? 1 : 2;
-    const int lcs = sel.lcs;
-    p.cgs = p.C / (4 << lcs);
-    p.row_tiles = (int)ceil_div(p.Ho, TH);
-    p.col_tiles = (int)ceil_div(p.Wo, TW);
+    dw_fill_geom(p, d, plan);
+    p.cgs = p.C / (4 << sel.lcs);
+    p.row_tiles = (int)ceil_div(p.Ho, sel.s == 2 ? 4 : 7);
+    p.col_tiles = (int)ceil_div(p.Wo, sel.s == 2 ? 1 : 2);
     const int64_t ntasks = (int64_t)p.N * p.row_tiles * p.col_tiles * p.cgs;
-    const int tasks_per_block = kDwcThreads >> lcs;
-    const int64_t nblocks = ceil_div(ntasks, tasks_per_block);
-    if (ntasks > 0x7FFFFFFF) return fail(SLFP_ERR_UNSUPPORTED, "dw3x3 (codes): grid too large");
+    if (const int rc = dw_grid_check(ntasks, "dw3x3 (codes)")) return rc;
     p.ntasks = (uint32_t)ntasks;
-    p.nblocks = (uint32_t)nblocks;
+    p.nblocks = (uint32_t)ceil_div(ntasks, kDwcThreads >> sel.lcs);
     p.fmt_in = sel.fmt_in;
     p.fmt_out = io.y_fmt;
-    p.ka = d.ka; p.kw = d.kw_scale;
     p.relu = post.relu;
     p.post_scale = post.scale; p.post_shift = post.shift;
     p.enc.valid = 0;
     if (sel.lut) {
         enc_carry_ptr(p.enc, io.lut);
-    } else if (y_codes) {
+    } else if (sel.yc) {
         const EncArgs* t = enc_table(io.y_ka, io.y_fmt, kEncCode);
         if (!t->valid) return fail(SLFP_ERR_UNSUPPORTED, "dw3x3 (codes): no code table for the consumer's scale %g", (double)io.y_ka);
         p.enc = *t;
     }
-    const bool has_post = sel.post;
-    const bool sgn = sel.sgn;
-#define SLFP_DWC_L(SS, LL, TT, WW, YY, PP, GG, ...) \
-    hipLaunchKernelGGL((k_dwc<SS, LL, TT, WW, YY, PP, GG, ##__VA_ARGS__>), dim3(p.nblocks), dim3(kDwcThreads), 0, stream, x, wq9c, y, p)
-#define SLFP_DWC_P(SS, LL, TT, WW) \
-    do { if (y_codes) { if (has_post) { if (sgn) SLFP_DWC_L(SS, LL, TT, WW, true, true, true); else SLFP_DWC_L(SS, LL, TT, WW, true, true, false); } \
-                        else { if (sgn) SLFP_DWC_L(SS, LL, TT, WW, true, false, true); else SLFP_DWC_L(SS, LL, TT, WW, true, false, false); } } \
-         else { if (has_post) SLFP_DWC_L(SS, LL, TT, WW, false, true, false); else SLFP_DWC_L(SS, LL, TT, WW, false, false, false); } } while (0)
-#define SLFP_DWC_T(SS, LL, TT, WW) \
-    do { if (sel.lut) SLFP_DWC_L(SS, LL, TT, WW, true, true, true, true); else SLFP_DWC_P(SS, LL, TT, WW); } while (0)
-#define SLFP_DWC_S(SS, TT, WW) \
-    do { if (lcs == 5) SLFP_DWC_T(SS, 5, TT, WW); else if (lcs == 4) SLFP_DWC_T(SS, 4, TT, WW); else SLFP_DWC_T(SS, 3, TT, WW); } while (0)
-    if (S == 2) SLFP_DWC_S(2, 4, 1);
-    else SLFP_DWC_S(1, 7, 2);
-#undef SLFP_DWC_S
-#undef SLFP_DWC_T
-#undef SLFP_DWC_P
-#undef SLFP_DWC_L
-    return check_launch("slfp dw3x3 (codes) kernel");
+    return dw_launch(dwc_instance(sel), "dw3x3 (codes)", dwc_sel_name(sel), p.nblocks, kDwcThreads, 0, stream, "slfp dw3x3 (codes) kernel",
+                     x, wq9c, y, p);
 }
 
 }  // namespace slfp

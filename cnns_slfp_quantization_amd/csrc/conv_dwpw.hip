@@ -20,7 +20,6 @@
 // traffic but runs 1-2 workgroups per CU with its phases in series, so it only breaks even on 32@112->64
 // (399 vs 407 us) and is slower on the K = 64 / 128 pairs (412 vs 352, 420 vs 337, 316 vs 204 us).  fusion.fuse_dw_pw is
 // therefore opt-in; DESIGN.md lists what the next version needs (fp16 halo tile, k-outer accumulation, >= 3 workgroups/CU).
-#include <cstdlib>
 #include "conv_dwpw_core.hpp"
 
 namespace slfp {
@@ -37,8 +36,8 @@ __global__ __launch_bounds__(kDwPwT, 2) void k_dwpw(const DwPwParams p) {
     constexpr int TH = G::TH, TW = G::TW, IH = G::IH, RPL = G::RPL, NI = G::NI, ROWB = G::ROWB, NPX = G::NPX, NU = G::NU, NWV = G::NWV, UW = G::UW;
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char* tab2 = smem + kDwPwTab;
-    unsigned char* lds = tab2 + kDwPwTab;
+    unsigned char* tab2 = smem + kDwTabBytes;
+    unsigned char* lds = tab2 + kDwTabBytes;
     unsigned char *tile = lds + G::tile, *x16 = lds + G::x16, *wl = lds + G::wl;
     float* ep = reinterpret_cast<float*>(lds + G::ep);
 
@@ -57,8 +56,7 @@ __global__ __launch_bounds__(kDwPwT, 2) void k_dwpw(const DwPwParams p) {
     const float r1 = p.enc1.r1, lo1 = p.enc1.lo, hi1 = p.enc1.hi;
     const float r2 = p.enc2.r1, lo2 = p.enc2.lo, hi2 = p.enc2.hi;
 
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(reinterpret_cast<const float*>(p.x)) + (size_t)n * p.H * p.W * p.C, 0, (uint32_t)p.H * p.W * p.C * 4u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = dw_rsrc(reinterpret_cast<const float*>(p.x) + (size_t)n * p.H * p.W * p.C, (uint32_t)p.H * p.W * p.C * 4u);
     const int gw = tw * TW * S - p.pad + iw;
     const int gh0 = th * TH * S - p.pad + ihh;
     const bool w_ok = col_live && (unsigned)gw < (unsigned)p.W;
@@ -68,7 +66,7 @@ __global__ __launch_bounds__(kDwPwT, 2) void k_dwpw(const DwPwParams p) {
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
         const bool ok = w_ok && (unsigned)(gh0 + RPL * i) < (unsigned)p.H && (RPL * i + ihh) < IH;
-        voff[i] = ok ? off0 + (uint32_t)i * step : kDwPwOob;
+        voff[i] = ok ? off0 + (uint32_t)i * step : kDwOob;
         asm volatile("" : "+v"(voff[i]));
     }
     floatx4 v[NI];
@@ -87,38 +85,14 @@ __global__ __launch_bounds__(kDwPwT, 2) void k_dwpw(const DwPwParams p) {
         floatx4 wt[9];
 #pragma unroll
         for (int k = 0; k < 9; ++k) wt[k] = *reinterpret_cast<const floatx4*>(p.wdw + (size_t)k * p.C + c);
-        const floatx4 psc = *reinterpret_cast<const floatx4*>(p.sc1 + c);
-        const floatx4 psh = *reinterpret_cast<const floatx4*>(p.sh1 + c);
-        bool any_nan = false;
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            const float4 xi = make_float4(v[i][0], v[i][1], v[i][2], v[i][3]);
-            any_nan |= enc_has_nan4(xi);
-            *reinterpret_cast<float4*>(tile + lds_w + (uint32_t)i * (uint32_t)(RPL * ROWB)) = enc4_f32_raw(xi, r1, lo1, hi1, smem);
-        }
-        if (__builtin_expect(any_nan, 0)) {
-#pragma unroll
-            for (int i = 0; i < NI; ++i)
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (v[i][e] != v[i][e]) reinterpret_cast<uint32_t*>(tile + lds_w + (uint32_t)i * (uint32_t)(RPL * ROWB))[e] = kBitsQNaN;
-        }
+        floatx4 psc, psh;
+        dw_load_bn<true>(psc, psh, p.sc1, p.sh1, c);
+        dw_put_halo<NI, RPL * ROWB>(tile + lds_w, v, r1, lo1, hi1, smem);
         __syncthreads();
         if (cg + 1 < KS) issue(cg + 1);   // in flight under the convolution below
 #pragma unroll
         for (int j = 0; j < G::NO; ++j) {   // conv_dw2.hip's epilogue, then conv_pw.hip's quantizer
-            floatx4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kh = 0; kh < 3; ++kh) {
-#pragma unroll
-                for (int kw = 0; kw < 3; ++kw) {
-                    const int tap = j * G::RPI * S * ROWB + ((S == 1) ? (kh * ROWB + kw * 128) : (kh * ROWB + ((kw & 1) * 8 + (kw >> 1)) * 128));
-                    const floatx4 a = *reinterpret_cast<const floatx4*>(tile + lds_r0 + tap);
-                    const floatx4 w = wt[kh * 3 + kw];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[e] = fmaf(a[e], w[e], acc[e]);
-                }
-            }
+            const floatx4 acc = dw_mac9_lds<S, ROWB>(wt, tile + lds_r0 + j * G::RPI * S * ROWB);
             const float4 rr = dwpw_bn1(acc, psc, psh, p);
             dwpw_put_quad<G>(x16, d, j, cg, enc4_f16(rr, r2, lo2, hi2, tab2));
         }
@@ -134,8 +108,7 @@ __global__ __launch_bounds__(kDwPwT, 2) void k_dwpw(const DwPwParams p) {
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) xh[ui][ks] = dwpw_frag<G>(x16, wv + NWV * ui, col, kq, ks);
     }
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(p.y) + (size_t)n * p.Ho * p.Wo * p.O, 0,
-                                                                         (uint32_t)p.Ho * p.Wo * p.O * 4u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ry = dw_rsrc(reinterpret_cast<float*>(p.y) + (size_t)n * p.Ho * p.Wo * p.O, (uint32_t)p.Ho * p.Wo * p.O * 4u);
     unsigned char* stg = tile + wv * 2048;   // [8 waves][2 KiB]: phase 2 reuses the (then idle) halo tile
     const int spx = lane >> 3, sch = lane & 7;
     const bool has_vec = p.bias2 != nullptr || p.sc2 != nullptr;
@@ -172,7 +145,7 @@ __global__ __launch_bounds__(kDwPwT, 2) void k_dwpw(const DwPwParams p) {
                     const int pix = u * 16 + spx + 8 * h;                      // pixel of the tile
                     const int oh = pix / TW, owp = pix - oh * TW;
                     const bool live = pix < NPX && (oh0 + oh) < p.Ho && (ow0 + owp) < p.Wo;
-                    uint32_t so = live ? (uint32_t)(((oh0 + oh) * p.Wo + ow0 + owp) * p.O + j0 * 16 + sch * 4) * 4u : kDwPwOob;
+                    uint32_t so = live ? (uint32_t)(((oh0 + oh) * p.Wo + ow0 + owp) * p.O + j0 * 16 + sch * 4) * 4u : kDwOob;
                     asm volatile("" : "+v"(so));
                     __builtin_amdgcn_raw_buffer_store_b128(vv, ry, so, 0, 0);
                 }
@@ -197,7 +170,7 @@ static bool dwpw_shape(const slfp_conv2d_desc& dw, const slfp_conv2d_desc& pw, i
     return true;
 }
 
-static size_t dwpw_lds(int S, int KS, int NT) { return (size_t)2 * kDwPwTab + dwpw_geom_bytes(S, KS, NT); }
+static size_t dwpw_lds(int S, int KS, int NT) { return (size_t)2 * kDwTabBytes + dwpw_geom_bytes(S, KS, NT); }
 
 // What slfp_dwpw_fwd chooses among k_dwpw's instances; slfp_dwpw_supported is this function's answer.
 bool dwpw_select(const slfp_conv2d_desc* dw, const slfp_conv2d_desc* pw, DwPwSel* s) {

@@ -27,8 +27,6 @@
 
 namespace slfp {
 
-constexpr uint32_t kDwPwOobLoad = 0x80000000u;   // code loads: past every tensor (< 2^29 bytes) with the channel group's offset added
-
 struct DwPwCodesParams : DwPwBase {   // fmt_out (DwPwBase) is set for YC
     EncArgsCompact enc2;   // fp16(16 * QA(. / Ka_pw)), packed pairs (kEncF16P)
     EncArgsCompact encY;   // YC: code table of the reader's Ka (kEncCode); two compact tables: 4 KiB of kernel arguments in all
@@ -44,8 +42,8 @@ __global__ __launch_bounds__(kDwPwT, 2) void k_dwpw_codes(const DwPwCodesParams 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* dtab = smem;                                // 256-entry decode table (kDecF32)
     unsigned char* tab2 = dtab + kDecBytes;                    // pointwise quantizer (kEncF16P)
-    unsigned char* tabY = tab2 + kDwPwTab;                     // reader's code table (YC)
-    unsigned char* lds = tabY + kDwPwTab;
+    unsigned char* tabY = tab2 + kDwTabBytes;                     // reader's code table (YC)
+    unsigned char* lds = tabY + kDwTabBytes;
     unsigned char *tile = lds + G::tile, *x16 = lds + G::x16, *wl = lds + G::wl;
     float* ep = reinterpret_cast<float*>(lds + G::ep);
 
@@ -65,8 +63,7 @@ __global__ __launch_bounds__(kDwPwT, 2) void k_dwpw_codes(const DwPwCodesParams 
     const float r2 = p.enc2.r1, lo2 = p.enc2.lo, hi2 = p.enc2.hi;
 
     // the image's codes, 1 B per element: a lane's dword = 4 channels of one halo pixel
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t*>(reinterpret_cast<const uint8_t*>(p.x)) + (size_t)n * p.H * p.W * p.C, 0, (uint32_t)p.H * p.W * p.C, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = dw_rsrc(reinterpret_cast<const uint8_t*>(p.x) + (size_t)n * p.H * p.W * p.C, (uint32_t)p.H * p.W * p.C);
     const int gw = tw * TW * S - p.pad + iw;
     const int gh0 = th * TH * S - p.pad + ihh;
     const bool w_ok = col_live && (unsigned)gw < (unsigned)p.W;
@@ -76,7 +73,7 @@ __global__ __launch_bounds__(kDwPwT, 2) void k_dwpw_codes(const DwPwCodesParams 
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
         const bool ok = w_ok && (unsigned)(gh0 + RPL * i) < (unsigned)p.H && (RPL * i + ihh) < IH;
-        voff[i] = ok ? off0 + (uint32_t)i * step : kDwPwOobLoad;
+        voff[i] = ok ? off0 + (uint32_t)i * step : kDwBadRow;   // past every tensor (< 2^29 bytes) with the channel group's offset added
         asm volatile("" : "+v"(voff[i]));
     }
     uint32_t v[NI];
@@ -94,13 +91,13 @@ __global__ __launch_bounds__(kDwPwT, 2) void k_dwpw_codes(const DwPwCodesParams 
         floatx4 wt[9];
 #pragma unroll
         for (int k = 0; k < 9; ++k) wt[k] = *reinterpret_cast<const floatx4*>(p.wdw + (size_t)k * p.C + c);
-        const floatx4 psc = *reinterpret_cast<const floatx4*>(p.sc1 + c);
-        const floatx4 psh = *reinterpret_cast<const floatx4*>(p.sh1 + c);
+        floatx4 psc, psh;
+        dw_load_bn<true>(psc, psh, p.sc1, p.sh1, c);
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
             // zero padding (and the halo slots outside the tile's window) = the exact-zero code, as in k_dwc: the returned 0 would be
             // the code of the "tiny" class
-            const uint32_t codes = voff[i] == kDwPwOobLoad ? 0x01010101u : v[i];
+            const uint32_t codes = voff[i] == kDwBadRow ? 0x01010101u : v[i];
             *reinterpret_cast<float4*>(tile + lds_w + (uint32_t)i * (uint32_t)(RPL * ROWB)) = dec4_f32(codes, dtab);
         }
         __syncthreads();
@@ -155,8 +152,7 @@ __global__ __launch_bounds__(kDwPwT, 2) void k_dwpw_codes(const DwPwCodesParams 
     };
     if constexpr (YC) {
         const CodeQuant cq{p.encY.r1, p.encY.lo, p.encY.hi, p.relu2 ? 0 : 1, p.fmt_out};
-        const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<uint8_t*>(p.y) + (size_t)n * p.Ho * p.Wo * p.O, 0,
-                                                                             (uint32_t)p.Ho * p.Wo * p.O, 0x00020000);
+        const __amdgpu_buffer_rsrc_t ry = dw_rsrc(reinterpret_cast<uint8_t*>(p.y) + (size_t)n * p.Ho * p.Wo * p.O, (uint32_t)p.Ho * p.Wo * p.O);
 #pragma unroll
         for (int ui = 0; ui < UW; ++ui) {
             const int u = wv + NWV * ui;
@@ -171,15 +167,14 @@ __global__ __launch_bounds__(kDwPwT, 2) void k_dwpw_codes(const DwPwCodesParams 
 #pragma unroll
                     for (int jj = 0; jj < 4; ++jj) c[jj] = code4<false, false>(tile_out(ui, j0 + jj), cq, tabY);
                     rows_transpose4(c[0], c[1], c[2], c[3]);   // lane-quarter kq now holds channels 16 (j0 + kq) + 0..15 of its pixel
-                    uint32_t so = live ? pixoff + (uint32_t)((j0 + kq) * 16) : kDwPwOob;
+                    uint32_t so = live ? pixoff + (uint32_t)((j0 + kq) * 16) : kDwOob;
                     asm volatile("" : "+v"(so));
                     __builtin_amdgcn_raw_buffer_store_b128(u32x4{c[0], c[1], c[2], c[3]}, ry, so, 0, 0);
                 }
             }
         }
     } else {
-        const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(p.y) + (size_t)n * p.Ho * p.Wo * p.O, 0,
-                                                                             (uint32_t)p.Ho * p.Wo * p.O * 4u, 0x00020000);
+        const __amdgpu_buffer_rsrc_t ry = dw_rsrc(reinterpret_cast<float*>(p.y) + (size_t)n * p.Ho * p.Wo * p.O, (uint32_t)p.Ho * p.Wo * p.O * 4u);
         unsigned char* stg = tile + wv * 2048;   // [8 waves][2 KiB]: phase 2 reuses the (then idle) halo tile
         const int spx = lane >> 3, sch = lane & 7;
 #pragma unroll 1
@@ -198,7 +193,7 @@ __global__ __launch_bounds__(kDwPwT, 2) void k_dwpw_codes(const DwPwCodesParams 
                         const int pix = u * 16 + spx + 8 * h;                      // pixel of the tile
                         const int oh = pix / TW, owp = pix - oh * TW;
                         const bool live = pix < NPX && (oh0 + oh) < p.Ho && (ow0 + owp) < p.Wo;
-                        uint32_t so = live ? (uint32_t)(((oh0 + oh) * p.Wo + ow0 + owp) * p.O + j0 * 16 + sch * 4) * 4u : kDwPwOob;
+                        uint32_t so = live ? (uint32_t)(((oh0 + oh) * p.Wo + ow0 + owp) * p.O + j0 * 16 + sch * 4) * 4u : kDwOob;
                         asm volatile("" : "+v"(so));
                         __builtin_amdgcn_raw_buffer_store_b128(vv, ry, so, 0, 0);
                     }
@@ -209,7 +204,7 @@ __global__ __launch_bounds__(kDwPwT, 2) void k_dwpw_codes(const DwPwCodesParams 
 }
 
 // ---------------------------------------------------------------------------- host
-static size_t dwpw_codes_lds(int S, int KS, int NT) { return (size_t)kDecBytes + (size_t)2 * kDwPwTab + dwpw_geom_bytes(S, KS, NT); }
+static size_t dwpw_codes_lds(int S, int KS, int NT) { return (size_t)kDecBytes + (size_t)2 * kDwTabBytes + dwpw_geom_bytes(S, KS, NT); }
 
 // the reader's quantizer of a code-writing call (conv_abi.hip: consumer_quant_ok), and its table in the form the kernel carries
 static const EncArgs* dwpw_codes_reader(const slfp_conv2d_io& io) {

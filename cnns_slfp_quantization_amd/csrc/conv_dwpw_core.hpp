@@ -10,15 +10,17 @@
 // Here: the tile geometry and the LDS carve-up (DwPwGeom; the host's LDS size is the same struct's), the parameters both kernels
 // take (DwPwBase) with the one host function that fills them, and those device steps that leave every instance's register
 // counts where they were when they are called instead of spelled out (profiles/compare_kernels.py compares two builds by kernel
-// name).  What each kernel keeps is its input path, the NaN policy of the hand-over quantizer and the output branch, and four
+// name).  What each kernel keeps is its input path, the NaN policy of the hand-over quantizer and the output branch, and three
 // spans that are the same text in both files because every shared form of them moved a register count of some instance: the W
-// copy, voff[], the 3x3 tap loop and the staged float32 store.  Everything here is
-// __device__ __forceinline__ or constexpr.
+// copy, voff[] and the staged float32 store.  The depthwise stage's steps are conv_dw_core.hpp's where calling
+// them passes the same check (section 36: k_dwpw_codes keeps the tap loop, both keep the tap loads and the ReLU branch spelled out).
+// Everything here is __device__ __forceinline__ or constexpr.
 #pragma once
 #include "slfp_device.hpp"
 #include "slfp_enc.hpp"
 #include "slfp_host.hpp"
 #include "slfp_epilogue.hpp"
+#include "conv_dw_core.hpp"
 
 namespace slfp {
 
@@ -26,8 +28,6 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kDwPwT = 512;                      // threads: 64 pixel slots x 8 channel quads in phase 1, 8 waves in phase 2
-constexpr int kDwPwTab = (kEncEntries * 8 + 15) & ~15;   // bytes of one threshold table in LDS
-constexpr uint32_t kDwPwOob = 0xFFFFFFF0u;       // buffer offset past every tensor: the load returns 0, the store is dropped
 constexpr int dwpw_th(int s) { return s == 2 ? 7 : 14; }   // tile edge in depthwise outputs
 
 // S: depthwise stride; KS: K / 32 (1, 2, 4); NT: N / 16 channel tiles (4, 8, 16)
@@ -151,14 +151,12 @@ __device__ __forceinline__ DwPwIdx dwpw_index(const DwPwBase& p) {
     return d;
 }
 
-// conv_dw2.hip's / k_dwc's epilogue of one accumulator quad, psc / psh being the folded BatchNorm 1 of its channels:
-// (acc * Ka) * Kw, fma(scale, shift), the ReLU
+// The depthwise kernels' finish (conv_dw_core.hpp) of one accumulator quad, psc / psh being the folded BatchNorm 1 of its channels
 __device__ __forceinline__ float4 dwpw_bn1(const floatx4 acc, const floatx4 psc, const floatx4 psh, const DwPwBase& p) {
-    float u0 = (acc[0] * p.ka1) * p.kw1, u1 = (acc[1] * p.ka1) * p.kw1, u2 = (acc[2] * p.ka1) * p.kw1, u3 = (acc[3] * p.ka1) * p.kw1;
-    u0 = __builtin_fmaf(u0, psc[0], psh[0]); u1 = __builtin_fmaf(u1, psc[1], psh[1]);
-    u2 = __builtin_fmaf(u2, psc[2], psh[2]); u3 = __builtin_fmaf(u3, psc[3], psh[3]);
-    if (p.relu1) { u0 = fmaxf(u0, 0.f); u1 = fmaxf(u1, 0.f); u2 = fmaxf(u2, 0.f); u3 = fmaxf(u3, 0.f); }
-    return make_float4(u0, u1, u2, u3);
+    const floatx4 u = dw_finish<true>(acc, p.ka1, p.kw1, psc, psh, 0);
+    float4 r = make_float4(u[0], u[1], u[2], u[3]);
+    if (p.relu1) r = relu4(r);   // one branch around four max, as in k_dwc's float32 form: inside the finish it moves VGPR counts here
+    return r;
 }
 
 // Output quad j of the thread, quantized (q), into the fp16 image (channel group cg)

@@ -116,9 +116,10 @@ int launch_dw3x3_tile(const slfp_conv2d_desc& d, const ConvPlan& p, const float*
 bool dw3x3_rows_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, const float* bias, const PostOp& post);
 int launch_dw3x3_rows(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const float* wq9c,
                       const PostOp& post, float* y, hipStream_t stream);
-// which template instance launch_dw3x3 runs for this layer (the rows, tile or general kernel) under the switches read at load,
-// printed from the selection each launcher consumes (slfp_debug_dw3x3_instance; host only; grammar in include/slfp.h).  "none"
-// outside the family or where the launch would be refused; valid until the next call on the same thread.
+// which template instance launch_dw3x3 runs for this layer (the rows, tile or general kernel) under the switches read at load: each
+// launcher maps its selection to a kernel pointer and launches it, and the name is printed only after the same lookup returned one
+// (slfp_debug_dw3x3_instance; host only; grammar in include/slfp.h; what the four files share: conv_dw_core.hpp).  "none" outside
+// the family, where the launch would be refused or where the selection has no instance; valid until the next call on the same thread.
 const char* dw3x3_instance_name(const slfp_conv2d_desc& d, const ConvPlan& p, bool has_bias, const PostOp& post);
 const char* dw3x3_tile_name(const slfp_conv2d_desc& d, const ConvPlan& p, const PostOp& post);
 const char* dw3x3_rows_name(const slfp_conv2d_desc& d, const ConvPlan& p, const PostOp& post);
