@@ -58,7 +58,7 @@
 #include "slfp_enc.hpp"
 #include "slfp_codes.hpp"
 #include "slfp_host.hpp"
-#include "conv_pw_params.hpp"
+#include "conv_pw_core.hpp"
 
 namespace slfp {
 
@@ -91,15 +91,6 @@ __device__ __forceinline__ void frag_patch_nan(const float4 a, const float4 b, h
         if (xs[i] != xs[i]) h[i] = (_Float16)__uint_as_float(0x7FC00000u);
 }
 
-// element offset of input pixel row m (strided 1x1 reads pixel (oh*S, ow*S))
-__device__ __forceinline__ size_t x_row_offset(const PwParams& p, int64_t m) {
-    if (p.S == 1) return (size_t)m * p.K;
-    const int64_t hw = (int64_t)p.Ho * p.Wo;
-    const int64_t img = m / hw, r = m - img * hw;
-    const int oh = (int)(r / p.Wo), ow = (int)(r - (int64_t)oh * p.Wo);
-    return (size_t)(((img * p.H) + (int64_t)oh * p.S) * p.W + (int64_t)ow * p.S) * p.K;
-}
-
 template <int FMT, int PASSES>
 __device__ __forceinline__ void encode4(const float4 v, const ScaleDiv sd, const uint32_t* sT, half4& h, half4& l) {
     const float v0 = quantize_scaled<FMT, 4>(v.x, sd, sT);
@@ -120,8 +111,6 @@ __device__ __forceinline__ half8 join(const half4 a, const half4 b) {
 // ======================================================================================
 // k_pw_stream: W resident in LDS, X straight into MFMA fragments, 16-pixel work units.
 // ======================================================================================
-constexpr int kStreamThreads = 512;
-
 // KS = number of 32-deep k-steps actually swept (ceil(K/32)); the blob's stride is p.KS.
 // KFULL: K == 32 * KS, every k-step swept holds real channels (its loads carry no bound).  A8: K and N are even but not both multiples of 4 (ShuffleNetV2's
 // 58-channel branches): pixel rows are only 8-byte aligned, so every 16-byte access becomes two
@@ -159,21 +148,12 @@ __global__ __launch_bounds__(kStreamThreads) void k_pw_stream(const PwParams p) 
         reinterpret_cast<half8*>(wl_hi)[i] = reinterpret_cast<const half8*>(p.whi)[i];
         if constexpr (PASSES == 3) reinterpret_cast<half8*>(wl_lo)[i] = reinterpret_cast<const half8*>(p.wlo)[i];
     }
-    // per-channel epilogue vectors -> LDS once per workgroup: [256 * bias/s1/s2 | post scale | post shift],
-    // padded to the blob's channel count.  Read from global inside the sweep, the loads (and the 12 bias
-    // divisions) sit on the critical path of every 16-byte store: +12-38 % on these layers (bench.py --post).
+    // per-channel epilogue vectors (pw_fill_ep), padded to the blob's channel count
     float* ep = reinterpret_cast<float*>(smem + (size_t)(PASSES == 3 ? 2 : 1) * wfrags * 1024);
     const int n_pad = p.n_tiles * 16;
     unsigned char* stg = reinterpret_cast<unsigned char*>(ep + 3 * n_pad) + (threadIdx.x >> 6) * 2048;   // STG: this wave's 2 KiB
     const bool has_vec = p.bias != nullptr || p.post.scale != nullptr;   // wave-uniform
-    if (has_vec) {
-        for (int i = threadIdx.x; i < n_pad; i += kStreamThreads) {
-            const bool in = i < p.N;
-            ep[i] = (p.bias && in) ? bias_q256_1(p.bias[i], p.s1, p.s2) : 0.f;
-            ep[n_pad + i] = (p.post.scale && in) ? p.post.scale[i] : 1.f;
-            ep[2 * n_pad + i] = (p.post.scale && in) ? p.post.shift[i] : 0.f;
-        }
-    }
+    if (has_vec) pw_fill_ep<kStreamThreads>(ep, p, 0, n_pad);
     __syncthreads();
 
     const int lane = threadIdx.x & 63;
@@ -254,52 +234,14 @@ __global__ __launch_bounds__(kStreamThreads) void k_pw_stream(const PwParams p) 
         }
         // ---- sweep the output-channel tiles
         auto tile_out = [&](int j) {
-            floatx4 acc = floatx4{0.f, 0.f, 0.f, 0.f};
-            const _Float16* wj = wl_hi + ((size_t)j * p.KS) * 512 + lane * 8;
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                const half8 wh = *reinterpret_cast<const half8*>(wj + ks * 512);
-                if constexpr (PASSES == 3) {
-                    const half8 wl = *reinterpret_cast<const half8*>(wj + (size_t)wfrags * 512 + ks * 512);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, xh[ks], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xl[ks], acc, 0, 0, 0);
-                }
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xh[ks], acc, 0, 0, 0);
-            }
-            const int n = j * 16 + kq * 4;
-            float4 r;
-            if (has_vec) {   // bias and/or fused BN: all three vectors from LDS
-                const float4 bq = *reinterpret_cast<const float4*>(ep + n);
-                const float4 sc = *reinterpret_cast<const float4*>(ep + n_pad + n);
-                const float4 sh = *reinterpret_cast<const float4*>(ep + 2 * n_pad + n);
-                r = epilogue(acc, bq, p.s1x, p.s2);
-                if (p.post.scale) {
-                    r = affine4(r, sc, sh);
-                    if constexpr (!YC) {   // (no layer-output quantizer in front of a code output: refused on the host)
-                        if (p.post.layerout) r = layerout4(r);
-                    }
-                }
-            } else {
-                r = epilogue(acc, make_float4(0.f, 0.f, 0.f, 0.f), p.s1x, p.s2);
-            }
-            if constexpr (!RES && !YC) {   // with a residual the ReLU follows the add (res_add); with code output it is the quantizer's
-                if (p.post.relu) r = relu4(r);
-            }
-            return r;
+            const floatx4 acc = pw_sweep_lds<PASSES, KS>(wl_hi + ((size_t)j * p.KS) * 512 + lane * 8, (size_t)wfrags * 512, xh, xl);
+            return pw_finish<!RES && !YC, !YC>(acc, p, ep, n_pad, j * 16 + kq * 4, has_vec);
         };
         if constexpr (YC) {
             uint8_t* yr = p.yc + (size_t)m * p.N;
             const CodeQuant cq{p.enc_lo.r1, p.enc_lo.lo, p.enc_lo.hi, p.sgn, p.fmt_out};
-            for (int j0 = 0; j0 < p.n_tiles; j0 += 4) {   // n_tiles is a multiple of 4 (the blob is padded to 64 channels)
-                uint32_t c[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float4 r = tile_out(j0 + j);
-                    c[j] = code4<false, true>(r, cq, stab_lo);
-                }
-                const int n = (j0 + kq) * 16;   // after the transpose lane-quarter kq holds channels 16 (j0 + kq) + 0..15
-                store_codes16(c, yr + n, live && n < p.N);
-            }
+            for (int j0 = 0; j0 < p.n_tiles; j0 += 4)   // n_tiles is a multiple of 4 (the blob is padded to 64 channels)
+                pw_codes16_out<false, true>(j0, yr, live, 0, p.N, kq, cq, stab_lo, tile_out);
         } else if constexpr (STG) {
             // per-unit descriptor: rows beyond M and channels beyond N get an out-of-range offset (store dropped)
             const uint32_t ybytes = (uint32_t)(((uint64_t)(p.M - g * 16) * p.N * 4) > 0xFFFFFFFFull ? 0xFFFFFFFFull : ((uint64_t)(p.M - g * 16) * p.N * 4));
@@ -333,7 +275,7 @@ __global__ __launch_bounds__(kStreamThreads) void k_pw_stream(const PwParams p) 
                     else __builtin_amdgcn_raw_buffer_store_b128(v, ry, so, 0, 0);
                 }
             }
-        } else {
+        } else {   // this loop stands in conv_pw_codes.hip's k_pwc_stream too (without the A8 two-half store)
             float* yr = p.y + (size_t)m * p.N + kq * 4;
             // RES: the 16 bytes a store will overwrite, one tile ahead (unconditional: dead rows / channels re-read a live element)
             const float* rrow = (RES ? p.res : p.y) + (size_t)(live ? m : p.M - 1) * p.N;
@@ -382,12 +324,9 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pw_til
     static_assert(!YC || (TAB && !STG && !RES && PASSES == 1 && NT == 4), "code output: single-pass table kernels, four channel tiles per wave");
     constexpr int TABB = TAB ? kPwTab : 64;
     constexpr int TABL = (TAB && (PASSES == 3 || YC)) ? kPwTab : 16;
-    constexpr int T = 64 * WM * WN;
-    constexpr int BM = WM * MT * 16;
-    constexpr int BN = WN * NT * 16;
-    constexpr int NLD = BM * 16 / T;  // float4 loads per thread per 64-deep stage
-    static_assert(BM * 16 % T == 0, "staging must divide evenly");
-    constexpr int XBYTES = BM * 128;
+    using G = PwTile<WM, WN, MT, NT>;
+    constexpr int T = G::T, BM = G::BM, BN = G::BN, XBYTES = G::XBYTES;
+    constexpr int NLD = G::NLD;  // float4 loads per thread per 64-deep stage
 
     __shared__ __attribute__((aligned(16))) unsigned char stab[TABB];      // static: constant address (see k_pw_stream)
     __shared__ __attribute__((aligned(16))) unsigned char stab_lo[TABL];
@@ -405,19 +344,13 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pw_til
     const int wm = wave / WN, wn = wave % WN;
     const int col = lane & 15, kq = lane >> 4;
 
-    // ---- staging geometry: float4 #i of a thread covers row (tid>>4) + i*(T/16), k = (tid&15)*4.
-    // Inside its 32-deep k-step that float4 is element half (kc&7)>>2 of lane-quarter kc&3.
+    // ---- staging geometry (conv_pw_core.hpp): float4 #i of a thread covers row (tid>>4) + i*(T/16), k = (tid&15)*4
     const int kc = threadIdx.x & 15;
     const int st_chunk = (kc >> 3) * 4 + (kc & 3);
     const uint32_t st_sub = (uint32_t)((kc & 7) >> 2) * 8u;
     const float* src[NLD];
 #pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-        const int row = (threadIdx.x >> 4) + i * (T / 16);
-        int64_t m = m0 + (row < p.rb ? row : p.rb - 1);  // padding rows of the tile re-read its last row (L1 hits) ...
-        m = m < p.M ? m : p.M - 1;                       // ... and rows past the end the last pixel: computed and dropped
-        src[i] = p.x + x_row_offset(p, m) + kc * 4;
-    }
+    for (int i = 0; i < NLD; ++i) src[i] = p.x + pw_stage_row_offset<T>(p, m0, i) + kc * 4;
 
     float4 st[NLD];
     auto load_stage = [&](int t) {
@@ -480,24 +413,17 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pw_til
 
     const int KT = p.KS >> 1;  // 64-deep stages
     const int ntile0 = (int)nb * (BN / 16) + wn * NT;
-    const size_t wplane = (size_t)(p.wlo - p.whi);
-    // W fragments (fragment (ntile0 + j, k-step): 1 KiB, lane-linear; padded tiles clamp to the last real one) by buffer loads:
-    // descriptor + per-tile byte offsets in scalar registers (the wave index is made uniform for the compiler), ONE vector
-    // register of address (lane * 16) for all of them (8 address registers less than per-tile pointers).  A second W set
-    // (W double-buffered by k-step, as k_pwc_tiled does) then fits without spills, and was measured: 118.19 vs 118.53 k images/s
+    // W fragments by buffer loads (pw_w_rsrc, pw_w_offset): the addresses are scalar but for one vector register, so a second W set
+    // (W double-buffered by k-step, as k_pwc_tiled does) fits without spills, and was measured: 118.19 vs 118.53 k images/s
     // without it (200-step A/B, 9 / 6 runs) -- on the float32 interface the X loads and the encoder set the stage time.
+    // This single-buffered load_w and k_pwc_tiled's double-buffered one differ on purpose.
     const int wn_u = __builtin_amdgcn_readfirstlane(wn);
     const int ntile0u = (int)nb * (BN / 16) + wn_u * NT;
-    const uint64_t wbytes = (uint64_t)p.n_tiles * p.KS * 1024;
-    const uint32_t wrecs = (uint32_t)(wbytes > 0xFFFFFFFFull ? 0xFFFFFFFFull : wbytes);
-    const __amdgpu_buffer_rsrc_t rwh = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(p.whi), 0, wrecs, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rwl = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(PASSES == 3 ? p.wlo : p.whi), 0, wrecs, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rwh = pw_w_rsrc(p.whi, p);
+    const __amdgpu_buffer_rsrc_t rwl = pw_w_rsrc(PASSES == 3 ? p.wlo : p.whi, p);
     uint32_t wsoff[NT];   // scalar
 #pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        const int nt = ntile0u + j < p.n_tiles ? ntile0u + j : p.n_tiles - 1;
-        wsoff[j] = (uint32_t)nt * (uint32_t)p.KS * 1024u;
-    }
+    for (int j = 0; j < NT; ++j) wsoff[j] = pw_w_offset(p, ntile0u + j);
     const uint32_t wvoff = (uint32_t)lane * 16u;
     half8 wh[NT], wl[NT];
     auto load_w = [&](int kstep) {
@@ -515,6 +441,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pw_til
             if constexpr (PASSES == 3) wl[j] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rwl, wvoff, so, 0));
         }
     };
+    // (this step stands in k_pwc_tiled too, there with the double-buffered W registers: the shared form, which takes acc / wh / wl by
+    // reference, moved register counts of both kernels)
     auto mfma_step = [&](int buf, int ks) {
         const unsigned char* hi = xs + (size_t)buf * (PASSES == 3 ? 2 : 1) * XBYTES;
         const unsigned char* lo = hi + XBYTES;
@@ -601,19 +529,12 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pw_til
         mfma_step(buf, 1);
     }
 
-    // fused BN/ReLU: this workgroup's BN-channel slices of scale / shift go through the (now free) X tile
-    // in LDS, so the store loop reads them with two ds_read_b128 instead of two global loads per store
-    // (those sat on the critical path of every store: +13 % on these layers)
     const int n_lo = (int)nb * BN;
-    float* lsc = reinterpret_cast<float*>(xs);   // LDS
+    float* lsc = reinterpret_cast<float*>(xs);   // LDS: the (now free) X tile
     float* lsh = lsc + BN;
     if (p.post.scale) {
         __syncthreads();   // every wave is done with the X tile
-        for (int i = threadIdx.x; i < BN; i += T) {
-            const bool in = n_lo + i < p.N;
-            lsc[i] = in ? p.post.scale[n_lo + i] : 1.f;
-            lsh[i] = in ? p.post.shift[n_lo + i] : 0.f;
-        }
+        pw_bn_slice_fill<BN, T>(lsc, lsh, p.post.scale, p.post.shift, p.N, n_lo);
         __syncthreads();
     }
     SLFP_STAMP(13);
@@ -624,14 +545,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pw_til
             uint32_t c[NT];
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
-                const int n = (ntile0 + j) * 16 + kq * 4;
-                const bool in = n < p.N;   // channel tiles past C_out: computed from clamped weights, never stored
-                float4 r = epilogue(acc[i][j], in ? bias_q256(p, n) : make_float4(0.f, 0.f, 0.f, 0.f), p.s1x, p.s2);
-                if (p.post.scale) {
-                    const float4 sc = *reinterpret_cast<const float4*>(lsc + (in ? n - n_lo : 0));
-                    const float4 sh = *reinterpret_cast<const float4*>(lsh + (in ? n - n_lo : 0));
-                    r = affine4(r, sc, sh);
-                }
+                const float4 r = pw_tile_finish<false, false>(acc[i][j], p, (ntile0 + j) * 16 + kq * 4, n_lo, lsc, lsh);
                 c[j] = code4<false, true>(r, cq, stab_lo);   // the ReLU, if any, is the quantizer's
             }
             const int row = (wm * MT + i) * 16 + col;
@@ -641,26 +555,16 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pw_til
         return;
     }
     if constexpr (STG) {
+        // The staged store loop and the geometry above stand in k_pwc_tiled too (there with the DUAL code store, here with the nt hint
+        // and the diagnostics).
         unsigned char* stg = xs + 2 * (PASSES == 3 ? 2 : 1) * XBYTES + wave * (16 * kStgRow);   // private to this wave
         const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(p.y + (size_t)m0 * p.N, 0, ybytes, 0x00020000);
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
 #pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                const int n = (ntile0 + j) * 16 + kq * 4;
-                const bool in = n < p.N;   // channel tiles past C_out: computed from clamped weights, never stored
-                float4 r = epilogue(acc[i][j], in ? bias_q256(p, n) : make_float4(0.f, 0.f, 0.f, 0.f), p.s1x, p.s2);
-                if (p.post.scale) {
-                    const float4 sc = *reinterpret_cast<const float4*>(lsc + (in ? n - n_lo : 0));
-                    const float4 sh = *reinterpret_cast<const float4*>(lsh + (in ? n - n_lo : 0));
-                    r = affine4(r, sc, sh);
-                    if (p.post.layerout) r = layerout4(r);
-                }
-                if constexpr (!RES) {   // with a residual the ReLU follows the add (res_add_stg)
-                    if (p.post.relu) r = relu4(r);
-                }
-                *reinterpret_cast<float4*>(stg + col * kStgRow + j * 64 + kq * 16) = r;
-            }
+            for (int j = 0; j < NT; ++j)   // with a residual the ReLU follows the add (res_add_stg)
+                *reinterpret_cast<float4*>(stg + col * kStgRow + j * 64 + kq * 16) =
+                    pw_tile_finish<!RES, true>(acc[i][j], p, (ntile0 + j) * 16 + kq * 4, n_lo, lsc, lsh);
             // LDS operations of one wave execute in order: the reads see the writes, the next tile's writes follow the reads
 #pragma unroll
             for (int h = 0; h < 4; ++h) {
@@ -712,9 +616,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pw_til
 
 
 // ---------------------------------------------------------------------------- launch
-// once per (device, kernel), not per launch (round 1 re-armed the attribute on every launch)
-static int set_lds_limit(const void* fn, size_t lds) { return raise_lds_limit(fn, lds); }
-
 // CAN the LDS-resident stream kernel take this layer (W next to the tables and the staging area)?  Also what the planner asks
 // for channel counts that are even but not multiples of 4 (only that kernel has the 8-byte access path).
 bool pointwise_stream_fits(int64_t k_pad, int64_t n_pad, int passes) {
@@ -781,13 +682,8 @@ static int pw_select(const PwParams& p, const ConvPlan& plan, PwSel* s) {
     }
     if (p.K % 4 || p.N % 4) return fail(SLFP_ERR_UNSUPPORTED, "pointwise: channel counts not a multiple of 4 need the stream kernel");
     s->kernel = kPwTiled;
-    // widest channel tile: fewest re-reads / re-encodes of X.  (Narrower tiles for the small-M, deep-K
-    // layers of ResNet-50's last stages -- 49-196 pixel tiles at batch 64 -- were measured: more
-    // workgroups, but the redundant encode costs more than the idle CUs did.)
-    if (p.N > 256 && passes == 1) { s->wm = 1; s->wn = 8; s->mt = 4; }   // 64 px x 512 ch, 8 waves, 2 workgroups/CU
-    else if (p.N > 128) { s->wm = 1; s->wn = 4; s->mt = 4; }             // 64 px x 256 ch
-    else if (p.N > 64) { s->wm = 2; s->wn = 2; s->mt = 2; }              // 64 px x 128 ch
-    else { s->wm = 4; s->wn = 1; s->mt = 1; }                            // 64 px x  64 ch
+    const PwTiling t = pw_tiling(p.N, passes == 1);   // the three-pass path never takes {1, 8, 4}
+    s->wm = t.wm; s->wn = t.wn; s->mt = t.mt;
     s->kfull = p.K % 64 == 0;
     if (p.yc) {   // code output: the single-pass table form only (pointwise_entry_applicable)
         if (passes != 1 || !p.enc.valid || !p.enc_lo.valid || p.res)
@@ -803,124 +699,97 @@ static int pw_select(const PwParams& p, const ConvPlan& plan, PwSel* s) {
     return SLFP_OK;
 }
 
-static const char* fmt_word(int fmt) { return fmt == kFmtSfp7 ? "sfp7" : "act8"; }
-
 static const char* pw_sel_name(const PwSel& s) {
     static thread_local char buf[80];
     const char* tail = s.res ? "/res" : (s.yc ? "/yc" : "");
     int n;
     if (s.kernel == kPwStream)
         n = snprintf(buf, sizeof buf, "stream/ks%d/%s/%s/%s/p%d/%s%s", s.ks, s.a8 ? "a8" : (s.kfull ? "kfull" : "kpart"), s.tab ? "tab" : "long",
-                     s.stg ? "stg" : "dir", s.passes, fmt_word(s.fmt), tail);
+                     s.stg ? "stg" : "dir", s.passes, pw_fmt_word(s.fmt), tail);
     else
         n = snprintf(buf, sizeof buf, "tiled/%d%d%d/%s/%s/%s/p%d/%s%s", s.wm, s.wn, s.mt, s.kfull ? "kfull" : "kpart", s.tab ? "tab" : "long",
-                     s.stg ? "stg" : "dir", s.passes, fmt_word(s.fmt), tail);
+                     s.stg ? "stg" : "dir", s.passes, pw_fmt_word(s.fmt), tail);
     if (s.kernel == kPwStream && s.grid_cap > 0) snprintf(buf + n, sizeof buf - n, "/grid%d", s.grid_cap);
     return buf;
 }
 
-// dry (here and in the launchers below): stop once the instance is found, before anything touches a device -- pw_variant_name's check
-// that the launcher has the instance the selection names
-template <int FMT, int PASSES, int WM, int WN, int MT, bool KFULL>
-static int launch_tiled_k(PwParams& p, const PwSel& s, hipStream_t stream, bool dry) {
-    constexpr int NT = 4;
-    constexpr int BM = WM * MT * 16, BN = WN * NT * 16, T = 64 * WM * WN;
-    void (*fn)(const PwParams) = nullptr;
-    if (s.yc) {
-        if constexpr (PASSES == 1) fn = k_pw_tiled<FMT, 1, WM, WN, MT, NT, KFULL, true, false, false, true>;
-    } else if (s.res) {
-        fn = k_pw_tiled<FMT, PASSES, WM, WN, MT, NT, KFULL, true, true, true>;
-    } else if (s.stg) {
-        fn = k_pw_tiled<FMT, PASSES, WM, WN, MT, NT, KFULL, true, true>;
-    } else if (s.tab) {
-        fn = k_pw_tiled<FMT, PASSES, WM, WN, MT, NT, KFULL, true>;
-    } else {
-        fn = k_pw_tiled<FMT, PASSES, WM, WN, MT, NT, KFULL>;
-    }
-    if (!fn) return fail(SLFP_ERR_UNSUPPORTED, "pointwise: no tiled kernel instance for %s", pw_sel_name(s));
-    if (dry) return SLFP_OK;
-    p.n_blocks = (uint32_t)ceil_div((int64_t)p.N, BN);
-    // (Workgroups that own fewer rows than their tile -- 49 = a quarter image instead of 64, for an integral number of
-    // rounds on the 512 resident slots -- were measured: no gain, 61-64 vs 60 us on 512->512.  A workgroup's time is set
-    // by streaming all of W from L2, not by its rows.)
-    p.rb = BM;
-    p.m_blocks = (uint32_t)ceil_div(p.M, p.rb);
-    const int64_t nblocks = (int64_t)p.m_blocks * p.n_blocks;
-    if (nblocks > 0x7FFFFFFF) return fail(SLFP_ERR_UNSUPPORTED, "pointwise: grid too large");
-    p.nblocks = (uint32_t)nblocks;
-    // dynamic part (the tables are static LDS): the X double buffer, and the per-wave staging area of the staged epilogue
-    const size_t lds = (size_t)2 * (PASSES == 3 ? 2 : 1) * BM * 128 + (s.stg ? (size_t)(T / 64) * 16 * kStgRow : 0);
-    int rc = set_lds_limit(reinterpret_cast<const void*>(fn), lds);
-    if (rc != SLFP_OK) return rc;
-    hipLaunchKernelGGL(fn, dim3(p.nblocks), dim3(T), lds, stream, p);
-    return check_launch("slfp pointwise (tiled) kernel");
-}
-
-template <int FMT, int PASSES, int WM, int WN, int MT>
-static int launch_tiled(PwParams& p, const PwSel& s, hipStream_t stream, bool dry) {
-    if (s.kfull) return launch_tiled_k<FMT, PASSES, WM, WN, MT, true>(p, s, stream, dry);
-    return launch_tiled_k<FMT, PASSES, WM, WN, MT, false>(p, s, stream, dry);
-}
+// From the selection to the kernel: one typed lookup per kernel template.  nullptr: the launchers have no such instance.  The
+// launchers launch what the lookup returns and pw_variant_name asks it before it prints a name.
+typedef void (*PwFn)(const PwParams);
 
 template <int FMT, int PASSES, int KS>
-static int launch_stream_ks(PwParams& p, const PwSel& s, hipStream_t stream, bool dry) {
+static PwFn pw_stream_instance_ks(const PwSel& s) {
     constexpr bool kStgDefault = stream_stg_default(KS);
-    void (*fn)(const PwParams) = nullptr;
     if (s.yc) {
         if constexpr (PASSES == 1)
-            fn = s.kfull ? k_pw_stream<FMT, 1, KS, true, false, true, false, false, true> : k_pw_stream<FMT, 1, KS, false, false, true, false, false, true>;
-    } else if (s.res) {
-        if (s.stg == kStgDefault)
-            fn = s.kfull ? k_pw_stream<FMT, PASSES, KS, true, false, true, kStgDefault, true> : k_pw_stream<FMT, PASSES, KS, false, false, true, kStgDefault, true>;
-    } else if (s.a8) {
-        fn = s.tab ? k_pw_stream<FMT, PASSES, KS, false, true, true> : k_pw_stream<FMT, PASSES, KS, false, true>;
-    } else if (s.stg) {
-        fn = s.kfull ? k_pw_stream<FMT, PASSES, KS, true, false, true, true> : k_pw_stream<FMT, PASSES, KS, false, false, true, true>;
-    } else if (s.tab) {
-        fn = s.kfull ? k_pw_stream<FMT, PASSES, KS, true, false, true> : k_pw_stream<FMT, PASSES, KS, false, false, true>;
-    } else {
-        fn = s.kfull ? k_pw_stream<FMT, PASSES, KS, true> : k_pw_stream<FMT, PASSES, KS, false>;
+            return s.kfull ? k_pw_stream<FMT, 1, KS, true, false, true, false, false, true> : k_pw_stream<FMT, 1, KS, false, false, true, false, false, true>;
+        return nullptr;
     }
-    if (!fn) return fail(SLFP_ERR_UNSUPPORTED, "pointwise: no stream kernel instance for %s", pw_sel_name(s));
-    if (dry) return SLFP_OK;
-    const size_t lds = (size_t)(PASSES == 3 ? 2 : 1) * p.n_tiles * p.KS * 1024 + (size_t)3 * p.n_tiles * 16 * sizeof(float) +
-                       (s.stg ? (size_t)(kStreamThreads / 64) * 2048 : 0);   // dynamic part; the tables are static LDS
-    int rc = set_lds_limit(reinterpret_cast<const void*>(fn), lds);
-    if (rc != SLFP_OK) return rc;
-    // persistent grid: as many workgroups per CU as LDS and registers allow (<= 4), on every CU of the device
-    int per_cu = resident_blocks_per_cu(reinterpret_cast<const void*>(fn), kStreamThreads, lds);
-    per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
-    const int64_t groups = (p.M + 15) / 16;
-    int64_t grid = (int64_t)device_cu_count() * per_cu;
-    const int64_t need = ceil_div(groups, kStreamThreads / 64);
-    if (grid > need) grid = need;
-    if (s.grid_cap > 0 && grid > s.grid_cap) grid = s.grid_cap;   // SLFP_PW_GRID: several trips of the persistent loop at small shapes
-    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kStreamThreads), lds, stream, p);
-    return check_launch("slfp pointwise (stream) kernel");
+    if (s.res) {   // the residual forms exist for the default staging rule only
+        if (s.stg != kStgDefault) return nullptr;
+        return s.kfull ? k_pw_stream<FMT, PASSES, KS, true, false, true, kStgDefault, true> : k_pw_stream<FMT, PASSES, KS, false, false, true, kStgDefault, true>;
+    }
+    if (s.a8) return s.tab ? k_pw_stream<FMT, PASSES, KS, false, true, true> : k_pw_stream<FMT, PASSES, KS, false, true>;
+    if (s.stg) return s.kfull ? k_pw_stream<FMT, PASSES, KS, true, false, true, true> : k_pw_stream<FMT, PASSES, KS, false, false, true, true>;
+    if (s.tab) return s.kfull ? k_pw_stream<FMT, PASSES, KS, true, false, true> : k_pw_stream<FMT, PASSES, KS, false, false, true>;
+    return s.kfull ? k_pw_stream<FMT, PASSES, KS, true> : k_pw_stream<FMT, PASSES, KS, false>;
+}
+template <int FMT, int PASSES>
+static PwFn pw_stream_instance_fp(const PwSel& s) {
+    switch (s.ks) {
+        case 1: return pw_stream_instance_ks<FMT, PASSES, 1>(s);
+        case 2: return pw_stream_instance_ks<FMT, PASSES, 2>(s);
+        case 3: return pw_stream_instance_ks<FMT, PASSES, 3>(s);
+        case 4: return pw_stream_instance_ks<FMT, PASSES, 4>(s);
+        case 6: return pw_stream_instance_ks<FMT, PASSES, 6>(s);
+        case 8: return pw_stream_instance_ks<FMT, PASSES, 8>(s);
+        default: return nullptr;
+    }
 }
 
+template <int FMT, int PASSES, int WM, int WN, int MT, bool KFULL>
+static PwFn pw_tiled_instance_k(const PwSel& s) {
+    constexpr int NT = 4;
+    if (s.yc) {
+        if constexpr (PASSES == 1) return k_pw_tiled<FMT, 1, WM, WN, MT, NT, KFULL, true, false, false, true>;
+        return nullptr;
+    }
+    if (s.res) return k_pw_tiled<FMT, PASSES, WM, WN, MT, NT, KFULL, true, true, true>;
+    if (s.stg) return k_pw_tiled<FMT, PASSES, WM, WN, MT, NT, KFULL, true, true>;
+    if (s.tab) return k_pw_tiled<FMT, PASSES, WM, WN, MT, NT, KFULL, true>;
+    return k_pw_tiled<FMT, PASSES, WM, WN, MT, NT, KFULL>;
+}
 template <int FMT, int PASSES>
-static int launch_pw(PwParams& p, const PwSel& s, hipStream_t stream, bool dry) {
-    if (s.kernel == kPwStream) {
-        switch (s.ks) {
-            case 1: return launch_stream_ks<FMT, PASSES, 1>(p, s, stream, dry);
-            case 2: return launch_stream_ks<FMT, PASSES, 2>(p, s, stream, dry);
-            case 3: return launch_stream_ks<FMT, PASSES, 3>(p, s, stream, dry);
-            case 4: return launch_stream_ks<FMT, PASSES, 4>(p, s, stream, dry);
-            case 6: return launch_stream_ks<FMT, PASSES, 6>(p, s, stream, dry);
-            case 8: return launch_stream_ks<FMT, PASSES, 8>(p, s, stream, dry);
-            default: break;
-        }
-        return fail(SLFP_ERR_UNSUPPORTED, "pointwise: no stream kernel instance for %s", pw_sel_name(s));
-    }
-    const int t = s.wm * 100 + s.wn * 10 + s.mt;
-    if constexpr (PASSES == 1) {
-        if (t == 184) return launch_tiled<FMT, 1, 1, 8, 4>(p, s, stream, dry);
-    }
-    if (t == 144) return launch_tiled<FMT, PASSES, 1, 4, 4>(p, s, stream, dry);
-    if (t == 222) return launch_tiled<FMT, PASSES, 2, 2, 2>(p, s, stream, dry);
-    if (t == 411) return launch_tiled<FMT, PASSES, 4, 1, 1>(p, s, stream, dry);
-    return fail(SLFP_ERR_UNSUPPORTED, "pointwise: no tiled kernel instance for %s", pw_sel_name(s));
+static PwFn pw_tiled_instance_fp(const PwSel& s) {
+    return pw_tiling_instance<PASSES == 1>(s.wm, s.wn, s.mt, [&](auto t) -> PwFn {
+        using G = decltype(t);
+        return s.kfull ? pw_tiled_instance_k<FMT, PASSES, G::kWM, G::kWN, G::kMT, true>(s) : pw_tiled_instance_k<FMT, PASSES, G::kWM, G::kWN, G::kMT, false>(s);
+    });
+}
+
+// FMT / PASSES: SFP<3,3> is exact in fp16 (one pass), SLFP<3,4> takes one pass or three
+static PwFn pw_stream_instance(const PwSel& s) {
+    if (s.fmt == kFmtSfp7) return pw_stream_instance_fp<kFmtSfp7, 1>(s);
+    return s.passes == 3 ? pw_stream_instance_fp<kFmtAct8, 3>(s) : pw_stream_instance_fp<kFmtAct8, 1>(s);
+}
+static PwFn pw_tiled_instance(const PwSel& s) {
+    if (s.fmt == kFmtSfp7) return pw_tiled_instance_fp<kFmtSfp7, 1>(s);
+    return s.passes == 3 ? pw_tiled_instance_fp<kFmtAct8, 3>(s) : pw_tiled_instance_fp<kFmtAct8, 1>(s);
+}
+static PwFn pw_instance(const PwSel& s) { return s.kernel == kPwStream ? pw_stream_instance(s) : pw_tiled_instance(s); }
+
+static int launch_stream_ks(PwParams& p, const PwSel& s, hipStream_t stream) {
+    const PwFn fn = pw_stream_instance(s);
+    if (!fn) return fail(SLFP_ERR_UNSUPPORTED, "pointwise: no stream kernel instance for %s", pw_sel_name(s));
+    const size_t lds = (size_t)(s.passes == 3 ? 2 : 1) * p.n_tiles * p.KS * 1024 + (size_t)3 * p.n_tiles * 16 * sizeof(float) +
+                       (s.stg ? (size_t)(kStreamThreads / 64) * 2048 : 0);   // dynamic part; the tables are static LDS
+    return pw_launch_stream(fn, p, lds, s.grid_cap, stream, "slfp pointwise (stream) kernel");
+}
+
+static int launch_tiled(PwParams& p, const PwSel& s, hipStream_t stream) {
+    const PwFn fn = pw_tiled_instance(s);
+    if (!fn) return fail(SLFP_ERR_UNSUPPORTED, "pointwise: no tiled kernel instance for %s", pw_sel_name(s));
+    return pw_launch_tiled(fn, p, PwTiling{s.wm, s.wn, s.mt}, s.passes, s.stg, stream, "pointwise", "slfp pointwise (tiled) kernel");
 }
 
 // Does a residual form of the kernel launch_pointwise would pick exist?  Host-only: the planner's answer, the quantizer table
@@ -960,19 +829,12 @@ int launch_pointwise_entry(const slfp_conv2d_desc& d, const ConvPlan& plan, cons
     return launch_pointwise_any(d, plan, x, wfrag, bias, post, nullptr, stream, nullptr, reinterpret_cast<uint8_t*>(y_codes), io.y_ka, io.y_fmt);
 }
 
-static int pw_dispatch(PwParams& p, const PwSel& s, hipStream_t stream, bool dry) {
-    if (s.fmt == kFmtSfp7) return launch_pw<kFmtSfp7, 1>(p, s, stream, dry);  // exact in fp16
-    if (s.passes == 3) return launch_pw<kFmtAct8, 3>(p, s, stream, dry);
-    return launch_pw<kFmtAct8, 1>(p, s, stream, dry);
-}
-
-// The host-side part of PwParams that the selection reads: channel counts, which operands are present, the quantizer tables.
+// The host-side part of PwParams: what the descriptor and the plan give (the selection reads the channel counts), which operands are
+// present, the quantizer tables.
 static int pw_host_params(PwParams& p, const slfp_conv2d_desc& d, const ConvPlan& plan, const float* res, uint8_t* yc, float y_ka, int y_fmt) {
     p.res = res;
     p.yc = yc; p.fmt_out = y_fmt;
-    p.K = (int)d.c_in; p.N = (int)d.c_out;
-    p.KS = (int)(plan.k_pad / 32);
-    p.n_tiles = (int)(plan.n_pad / 16);
+    pw_fill_geom(p, d, plan);
     p.enc.valid = 0;
     p.enc_lo.valid = 0;
     if (!switches().pw_notab) {   // experiment switch (slfp_host.hpp), read once at load
@@ -998,7 +860,7 @@ const char* pw_variant_name(const slfp_conv2d_desc& d, const ConvPlan& plan, boo
     static uint8_t some_codes;
     PwSel s;
     if (pw_host_params(p, d, plan, has_res ? &some_res : nullptr, y_codes ? &some_codes : nullptr, y_ka, y_fmt) != SLFP_OK) return "none";
-    if (pw_select(p, plan, &s) != SLFP_OK || pw_dispatch(p, s, nullptr, true) != SLFP_OK) return "none";
+    if (pw_select(p, plan, &s) != SLFP_OK || !pw_instance(s)) return "none";
     return pw_sel_name(s);
 }
 
@@ -1012,13 +874,10 @@ static int launch_pointwise_any(const slfp_conv2d_desc& d, const ConvPlan& plan,
     if (rc != SLFP_OK) return rc;
     p.whi = reinterpret_cast<const _Float16*>(wfrag);
     p.wlo = p.whi + (size_t)plan.n_pad * plan.k_pad;
-    p.H = (int)d.h; p.W = (int)d.w; p.Ho = (int)plan.h_out; p.Wo = (int)plan.w_out; p.S = d.stride_h;
-    p.M = d.n * plan.h_out * plan.w_out;
     p.sd = make_scale_div(d.ka, 4);  // x / (Ka/16) == 16 * (x / Ka)
 #ifdef SLFP_PW_STAMPS
     { const char* e = getenv("SLFP_PW_DBG"); p.dbg = e ? reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 16)) : nullptr; }
 #endif
-    p.s1 = plan.s1; p.s2 = plan.s2; p.s1x = plan.s1 * (1.0f / 256.0f);
     {   // staged stores always carry the nt hint: a size threshold as in conv_dw2.hip (plain stores for outputs that fit the
         // Infinity Cache) measured 1.5 % SLOWER on the whole net here (profiles/ab_env_wn.sh); SLFP_PW_NT_MIN_MB: experiment switch
         const int64_t min_mb = switches().pw_nt_min_mb;
@@ -1027,7 +886,7 @@ static int launch_pointwise_any(const slfp_conv2d_desc& d, const ConvPlan& plan,
     PwSel s;
     rc = pw_select(p, plan, &s);
     if (rc != SLFP_OK) return rc;
-    return pw_dispatch(p, s, stream, false);
+    return s.kernel == kPwStream ? launch_stream_ks(p, s, stream) : launch_tiled(p, s, stream);
 }
 
 }  // namespace slfp

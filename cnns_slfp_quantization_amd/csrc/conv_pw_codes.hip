@@ -31,7 +31,7 @@
 #include "slfp_codes.hpp"
 #include "slfp_layerout_lut.hpp"
 #include "slfp_host.hpp"
-#include "conv_pw_params.hpp"
+#include "conv_pw_core.hpp"
 
 namespace slfp {
 
@@ -57,14 +57,6 @@ struct PwcParams {
                           // describe its reader as they do for YC; nullptr otherwise
 };
 
-__device__ __forceinline__ size_t xc_row_offset(const PwcParams& p, int64_t m) {
-    if (p.S == 1) return (size_t)m * p.K;
-    const int64_t hw = (int64_t)p.Ho * p.Wo;
-    const int64_t img = m / hw, r = m - img * hw;
-    const int oh = (int)(r / p.Wo), ow = (int)(r - (int64_t)oh * p.Wo);
-    return (size_t)(((img * p.H) + (int64_t)oh * p.S) * p.W + (int64_t)ow * p.S) * p.K;
-}
-
 __device__ __forceinline__ half8 dec_frag(uint32_t ca, uint32_t cb, const unsigned char* dtab) {
     const uint2 pa = dec4_f16(ca, dtab), pb = dec4_f16(cb, dtab);
     return __builtin_bit_cast(half8, u32x4{pa.x, pa.y, pb.x, pb.y});
@@ -82,8 +74,6 @@ __device__ __forceinline__ void dec_frag_hl(uint32_t ca, uint32_t cb, const unsi
 // ======================================================================================
 // k_pwc_stream: W resident in LDS, codes straight into MFMA fragments, 16-pixel work units.
 // ======================================================================================
-constexpr int kPwcThreads = 512;
-
 // KS: 32-deep k-steps (K = 32 * KS exactly); XW: K is a multiple of 64 (16-byte code loads + transpose), else two
 // dword loads per k-step; YC: output codes (N a multiple of 16), else float32.  RES (float32 out): y = relu?(affine(conv) + res),
 // each 16 bytes of p.res loaded with the address of the store they pair with, one channel tile ahead of its MFMA sweep.
@@ -102,7 +92,7 @@ constexpr int kPwcThreads = 512;
 // of W are resident (the blob's lo plane follows its hi plane, so one copy loop takes both), the table is kDecF16HL and every k-step
 // issues (w_lo, x_hi), (w_hi, x_lo), (w_hi, x_hi) as conv_pw.hip's three-pass k_pw_stream does: the same accumulators bit for bit.
 template <int FMT, int KS, bool XW, bool YC, bool RES = false, bool HALF = false, bool DUAL = false, bool LUTQ = false, int PASSES = 1>
-__global__ __launch_bounds__(kPwcThreads) void k_pwc_stream(const PwcParams p) {
+__global__ __launch_bounds__(kStreamThreads) void k_pwc_stream(const PwcParams p) {
     static_assert(PASSES == 1 || (PASSES == 3 && FMT == kFmtAct8 && !RES && !HALF && !DUAL && !LUTQ), "three passes: SLFP<3,4>, plain float32 or code output");
     constexpr int PL = PASSES == 3 ? 2 : 1;   // planes of W
     static_assert(!XW || KS % 2 == 0, "16-byte code loads cover two k-steps");
@@ -115,22 +105,15 @@ __global__ __launch_bounds__(kPwcThreads) void k_pwc_stream(const PwcParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     _Float16* wl = reinterpret_cast<_Float16*>(smem);
     const int wfrags = p.n_tiles * p.KS;  // 1 KiB each
-    dec_fill<FMT, PASSES == 3 ? kDecF16HL : kDecF16D, kPwcThreads>(sdec);
-    if constexpr ((YC && !LUTQ) || DUAL) enc_fill<kPwcThreads>(reinterpret_cast<uint2*>(senc), p.enc);
+    dec_fill<FMT, PASSES == 3 ? kDecF16HL : kDecF16D, kStreamThreads>(sdec);
+    if constexpr ((YC && !LUTQ) || DUAL) enc_fill<kStreamThreads>(reinterpret_cast<uint2*>(senc), p.enc);
     const lut_gptr lutg = LUTQ ? enc_carried_ptr(p.enc) : nullptr;
-    for (int i = threadIdx.x; i < PL * wfrags * 64; i += kPwcThreads)
+    for (int i = threadIdx.x; i < PL * wfrags * 64; i += kStreamThreads)
         reinterpret_cast<half8*>(wl)[i] = reinterpret_cast<const half8*>(p.whi)[i];
     float* ep = reinterpret_cast<float*>(smem + (size_t)PL * wfrags * 1024);   // [256 * bias/s1/s2 | post scale | post shift]
     const int n_pad = p.n_tiles * 16;
     const bool has_vec = p.bias != nullptr || p.post.scale != nullptr;   // wave-uniform
-    if (has_vec) {
-        for (int i = threadIdx.x; i < n_pad; i += kPwcThreads) {
-            const bool in = i < p.N;
-            ep[i] = (p.bias && in) ? bias_q256_1(p.bias[i], p.s1, p.s2) : 0.f;
-            ep[n_pad + i] = (p.post.scale && in) ? p.post.scale[i] : 1.f;
-            ep[2 * n_pad + i] = (p.post.scale && in) ? p.post.shift[i] : 0.f;
-        }
-    }
+    if (has_vec) pw_fill_ep<kStreamThreads>(ep, p, 0, n_pad);
     __syncthreads();
     const unsigned char* dtab = reinterpret_cast<const unsigned char*>(sdec);
     const CodeQuant cq{p.enc.r1, p.enc.lo, p.enc.hi, p.sgn, p.fmt_out};
@@ -138,13 +121,13 @@ __global__ __launch_bounds__(kPwcThreads) void k_pwc_stream(const PwcParams p) {
     const int lane = threadIdx.x & 63;
     const int col = lane & 15, kq = lane >> 4;
     const int64_t n_groups = (p.M + 15) >> 4;
-    const int64_t waves_total = (int64_t)gridDim.x * (kPwcThreads / 64);
-    const int64_t wave_id = (int64_t)blockIdx.x * (kPwcThreads / 64) + (threadIdx.x >> 6);
+    const int64_t waves_total = (int64_t)gridDim.x * (kStreamThreads / 64);
+    const int64_t wave_id = (int64_t)blockIdx.x * (kStreamThreads / 64) + (threadIdx.x >> 6);
 
     for (int64_t g = wave_id; g < n_groups; g += waves_total) {
         const int64_t m = g * 16 + col;
         const bool live = m < p.M;
-        const uint8_t* xr = p.x + xc_row_offset(p, live ? m : p.M - 1);   // rows past the end: clamped, computed, dropped
+        const uint8_t* xr = p.x + x_row_offset(p, live ? m : p.M - 1);   // rows past the end: clamped, computed, dropped
         uint32_t cw[KS][2];
         if constexpr (XW) {
             u32x4 v[KS / 2];
@@ -177,71 +160,34 @@ __global__ __launch_bounds__(kPwcThreads) void k_pwc_stream(const PwcParams p) {
         }
 
         auto tile_out = [&](int j) {
-            floatx4 acc = floatx4{0.f, 0.f, 0.f, 0.f};
-            const _Float16* wj = wl + ((size_t)j * p.KS) * 512 + lane * 8;
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                const half8 wh = *reinterpret_cast<const half8*>(wj + ks * 512);
-                if constexpr (PASSES == 3) {
-                    const half8 wlo = *reinterpret_cast<const half8*>(wj + (size_t)wfrags * 512 + ks * 512);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wlo, xh[ks], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xl[ks], acc, 0, 0, 0);
-                }
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xh[ks], acc, 0, 0, 0);
-            }
-            const int n = j * 16 + kq * 4;
-            float4 r;
-            if (has_vec) {
-                const float4 bq = *reinterpret_cast<const float4*>(ep + n);
-                const float4 sc = *reinterpret_cast<const float4*>(ep + n_pad + n);
-                const float4 sh = *reinterpret_cast<const float4*>(ep + 2 * n_pad + n);
-                r = epilogue(acc, bq, p.s1x, p.s2);
-                if (p.post.scale) r = affine4(r, sc, sh);
-            } else {
-                r = epilogue(acc, make_float4(0.f, 0.f, 0.f, 0.f), p.s1x, p.s2);
-            }
-            if constexpr (!YC && !RES) {   // with code output the ReLU is the quantizer's (enc4_code_relu); with a residual it follows the add
-                if (p.post.relu) r = relu4(r);
-            }
-            return r;
+            const floatx4 acc = pw_sweep_lds<PASSES, KS>(wl + ((size_t)j * p.KS) * 512 + lane * 8, (size_t)wfrags * 512, xh, xl);
+            return pw_finish<!YC && !RES, false>(acc, p, ep, n_pad, j * 16 + kq * 4, has_vec);
         };
         if constexpr (YC) {
             uint8_t* yr = reinterpret_cast<uint8_t*>(p.y) + (size_t)m * p.y_ld;
-            for (int j0 = 0; j0 < p.n_tiles; j0 += 4) {   // n_tiles is a multiple of 4 (the blob is padded to 64 channels)
-                uint32_t c[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float4 r = tile_out(j0 + j);
-                    c[j] = code4<LUTQ, false>(r, cq, senc, lutg);
-                }
-                const int n = (j0 + kq) * 16;   // after the transpose lane-quarter kq holds channels 16 (j0 + kq) + 0..15
-                store_codes16(c, yr + n, live && n < p.N);
-            }
+            for (int j0 = 0; j0 < p.n_tiles; j0 += 4)   // n_tiles is a multiple of 4 (the blob is padded to 64 channels)
+                pw_codes16_out<LUTQ, false>(j0, yr, live, 0, p.N, kq, cq, senc, tile_out, lutg);
         } else {
             float* yr = reinterpret_cast<float*>(p.y) + (size_t)m * p.N + kq * 4;
             // RES: unconditional loads (dead rows / channels re-read a live element and are dropped)
             const float* rrow = (RES ? p.res : reinterpret_cast<const float*>(p.y)) + (size_t)(live ? m : p.M - 1) * p.N;
-            float4 rn;
-            if constexpr (RES) rn = ld_stream4<SLFP_NT_PW_RES>(rrow + (kq * 4 < p.N ? kq * 4 : 0));
             if constexpr (DUAL) {
                 uint8_t* ycr = p.yc + (size_t)m * p.N;
+                float4 rn = ld_stream4<SLFP_NT_PW_RES>(rrow + (kq * 4 < p.N ? kq * 4 : 0));
                 for (int j0 = 0; j0 < p.n_tiles; j0 += 4) {   // n_tiles is a multiple of 4 (the blob is padded to 64 channels)
-                    uint32_t c[4];
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj) {
-                        const int j = j0 + jj;
+                    // the codes of the value just stored (the ReLU, where there is one, has run: enc4_code_relu sees r >= 0)
+                    pw_codes16_out<false, false>(j0, ycr, live, 0, p.N, kq, cq, senc, [&](int j) {
                         const float4 rc = rn;
                         const int n1 = (j + 1) * 16 + kq * 4;
                         rn = ld_stream4<SLFP_NT_PW_RES>(rrow + (n1 < p.N ? n1 : 0));
                         const float4 r = res_add(tile_out(j), rc, p.post.relu);
                         if (live && j * 16 + kq * 4 < p.N) *reinterpret_cast<float4*>(yr + j * 16) = r;
-                        // the codes of the value just stored (the ReLU, where there is one, has run: enc4_code_relu sees r >= 0)
-                        c[jj] = code4<false, false>(r, cq, senc);
-                    }
-                    const int n = (j0 + kq) * 16;   // after the transpose lane-quarter kq holds channels 16 (j0 + kq) + 0..15
-                    store_codes16(c, ycr + n, live && n < p.N);
+                        return r;
+                    });
                 }
-            } else {
+            } else {   // this loop stands in conv_pw.hip's k_pw_stream too (there with the A8 two-half store)
+                float4 rn;
+                if constexpr (RES) rn = ld_stream4<SLFP_NT_PW_RES>(rrow + (kq * 4 < p.N ? kq * 4 : 0));
                 for (int j = 0; j < p.n_tiles; ++j) {
                     float4 rc;
                     if constexpr (RES) {
@@ -311,14 +257,7 @@ __global__ __launch_bounds__(kSliceThreads, RES ? (DUAL ? kSliceDualWaves : 4) :
     constexpr int NCH = NTS * 16;
     const int n_lo = slice * NCH;
     const bool has_vec = p.bias != nullptr || p.post.scale != nullptr;
-    if (has_vec) {
-        for (int i = threadIdx.x; i < NCH; i += kSliceThreads) {
-            const bool in = n_lo + i < p.N;
-            ep[i] = (p.bias && in) ? bias_q256_1(p.bias[n_lo + i], p.s1, p.s2) : 0.f;
-            ep[NCH + i] = (p.post.scale && in) ? p.post.scale[n_lo + i] : 1.f;
-            ep[2 * NCH + i] = (p.post.scale && in) ? p.post.shift[n_lo + i] : 0.f;
-        }
-    }
+    if (has_vec) pw_fill_ep<kSliceThreads>(ep, p, n_lo, NCH);
     __syncthreads();
     const unsigned char* dtab = reinterpret_cast<const unsigned char*>(sdec);
     const CodeQuant cq{p.enc.r1, p.enc.lo, p.enc.hi, p.sgn, p.fmt_out};
@@ -333,18 +272,18 @@ __global__ __launch_bounds__(kSliceThreads, RES ? (DUAL ? kSliceDualWaves : 4) :
     {
         const int64_t g0 = (int64_t)rank * (kSliceThreads / 64) + (threadIdx.x >> 6);
         const int64_t m0 = (g0 < n_groups ? g0 : n_groups - 1) * 16 + col;
-        const uint8_t* x0 = p.x + xc_row_offset(p, m0 < p.M ? m0 : p.M - 1) + kq * 16;
+        const uint8_t* x0 = p.x + x_row_offset(p, m0 < p.M ? m0 : p.M - 1) + kq * 16;
 #pragma unroll
         for (int c2 = 0; c2 < KC / 2; ++c2) v[c2] = *reinterpret_cast<const u32x4*>(x0 + c2 * 64);
     }
     for (int64_t g = (int64_t)rank * (kSliceThreads / 64) + (threadIdx.x >> 6); g < n_groups; g += stride) {
         const int64_t m = g * 16 + col;
         const bool live = m < p.M;
-        const uint8_t* xr = p.x + xc_row_offset(p, live ? m : p.M - 1) + kq * 16;
+        const uint8_t* xr = p.x + x_row_offset(p, live ? m : p.M - 1) + kq * 16;
         // first chunk of the next unit of this wave (its own unit again on the last round: L1 hits, unused)
         const int64_t gn = g + stride < n_groups ? g + stride : g;
         const int64_t mn = gn * 16 + col;
-        const uint8_t* xrn = p.x + xc_row_offset(p, mn < p.M ? mn : p.M - 1) + kq * 16;
+        const uint8_t* xrn = p.x + x_row_offset(p, mn < p.M ? mn : p.M - 1) + kq * 16;
         floatx4 acc[NTS];
 #pragma unroll
         for (int j = 0; j < NTS; ++j) acc[j] = floatx4{0.f, 0.f, 0.f, 0.f};
@@ -380,36 +319,13 @@ __global__ __launch_bounds__(kSliceThreads, RES ? (DUAL ? kSliceDualWaves : 4) :
                 }
             }
         }
-        auto finish = [&](int j) {
-            const int n = j * 16 + kq * 4;   // channel inside the slice
-            float4 r;
-            if (has_vec) {
-                const float4 bq = *reinterpret_cast<const float4*>(ep + n);
-                const float4 sc = *reinterpret_cast<const float4*>(ep + NCH + n);
-                const float4 sh = *reinterpret_cast<const float4*>(ep + 2 * NCH + n);
-                r = epilogue(acc[j], bq, p.s1x, p.s2);
-                if (p.post.scale) r = affine4(r, sc, sh);
-            } else {
-                r = epilogue(acc[j], make_float4(0.f, 0.f, 0.f, 0.f), p.s1x, p.s2);
-            }
-            if constexpr (!YC && !RES) {   // with a residual the ReLU follows the add
-                if (p.post.relu) r = relu4(r);
-            }
-            return r;
+        auto finish = [&](int j) {   // j * 16 + kq * 4: channel inside the slice
+            return pw_finish<!YC && !RES, false>(acc[j], p, ep, NCH, j * 16 + kq * 4, has_vec);
         };
         if constexpr (YC) {
             uint8_t* yr = reinterpret_cast<uint8_t*>(p.y) + (size_t)m * p.y_ld + n_lo;
 #pragma unroll
-            for (int j0 = 0; j0 < NTS; j0 += 4) {
-                uint32_t c[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float4 r = finish(j0 + j);
-                    c[j] = code4<LUTQ, false>(r, cq, senc, lutg);
-                }
-                const int n = (j0 + kq) * 16;
-                store_codes16(c, yr + n, live && n_lo + n < p.N);
-            }
+            for (int j0 = 0; j0 < NTS; j0 += 4) pw_codes16_out<LUTQ, false>(j0, yr, live, n_lo, p.N, kq, cq, senc, finish, lutg);
         } else {
             float* yr = reinterpret_cast<float*>(p.y) + (size_t)m * p.N + n_lo + kq * 4;
             if constexpr (RES) {
@@ -419,7 +335,7 @@ __global__ __launch_bounds__(kSliceThreads, RES ? (DUAL ? kSliceDualWaves : 4) :
             if constexpr (DUAL) {
                 uint8_t* ycr = p.yc + (size_t)m * p.N + n_lo;
 #pragma unroll
-                for (int j0 = 0; j0 < NTS; j0 += 4) {
+                for (int j0 = 0; j0 < NTS; j0 += 4) {   // pw_codes16_out spelled out: through it the NTS = 8 instances grew by 9 vector instructions
                     uint32_t c[4];
 #pragma unroll
                     for (int jj = 0; jj < 4; ++jj) {
@@ -470,12 +386,9 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_ti
     static_assert(!DUAL || RES, "the second, code output belongs to the residual forms");
     static_assert(!LUTQ || YC, "the table epilogue belongs to the code-writing forms");
     constexpr int NT = 4;
-    constexpr int T = 64 * WM * WN;
-    constexpr int BM = WM * MT * 16;
-    constexpr int BN = WN * NT * 16;
-    constexpr int NLD = BM * 16 / T;  // code dwords per thread per 64-deep stage
-    static_assert(BM * 16 % T == 0, "staging must divide evenly");
-    constexpr int XBYTES = BM * 128;
+    using G = PwTile<WM, WN, MT, NT>;
+    constexpr int T = G::T, BM = G::BM, BN = G::BN, XBYTES = G::XBYTES;
+    constexpr int NLD = G::NLD;  // code dwords per thread per 64-deep stage
 
     __shared__ __attribute__((aligned(16))) uint32_t sdec[256];
     __shared__ __attribute__((aligned(16))) unsigned char senc[LUTQ ? kLayeroutLutBytes : ((YC || DUAL) ? kPwTab : 16)];
@@ -493,18 +406,13 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_ti
     const int wm = wave / WN, wn = wave % WN;
     const int col = lane & 15, kq = lane >> 4;
 
-    // staging geometry as in k_pw_tiled: dword #i of a thread = the 4 codes of row (tid>>4) + i*(T/16), k = (tid&15)*4
+    // staging geometry (conv_pw_core.hpp): dword #i of a thread = the 4 codes of row (tid>>4) + i*(T/16), k = (tid&15)*4
     const int kc = threadIdx.x & 15;
     const int st_chunk = (kc >> 3) * 4 + (kc & 3);
     const uint32_t st_sub = (uint32_t)((kc & 7) >> 2) * 8u;
     const uint8_t* src[NLD];
 #pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-        const int row = (threadIdx.x >> 4) + i * (T / 16);
-        int64_t m = m0 + (row < p.rb ? row : p.rb - 1);
-        m = m < p.M ? m : p.M - 1;
-        src[i] = p.x + xc_row_offset(p, m) + kc * 4;
-    }
+    for (int i = 0; i < NLD; ++i) src[i] = p.x + pw_stage_row_offset<T>(p, m0, i) + kc * 4;
     uint32_t st[NLD];
     auto load_stage = [&](int t) {
 #pragma unroll
@@ -534,19 +442,14 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_ti
 
     const int KT = p.KS >> 1;  // 64-deep stages
     const int ntile0 = (int)nb * (BN / 16) + wn * NT;
-    // W fragments by buffer loads: descriptor + per-tile byte offsets in scalar registers (the wave index is made uniform for
-    // the compiler), ONE vector register of address (lane * 16) for all of them -- the double buffer below needs the registers
+    // W fragments by buffer loads (pw_w_rsrc, pw_w_offset): scalar addresses but for one vector register -- the double buffer
+    // below needs the registers
     const int wn_u = __builtin_amdgcn_readfirstlane(wn);
     const int ntile0u = (int)nb * (BN / 16) + wn_u * NT;
-    const uint64_t wbytes = (uint64_t)p.n_tiles * p.KS * 1024;
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(p.whi), 0,
-                                                                        (uint32_t)(wbytes > 0xFFFFFFFFull ? 0xFFFFFFFFull : wbytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rw = pw_w_rsrc(p.whi, p);
     uint32_t wsoff[NT];   // scalar
 #pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        const int nt = ntile0u + j < p.n_tiles ? ntile0u + j : p.n_tiles - 1;
-        wsoff[j] = (uint32_t)nt * (uint32_t)p.KS * 1024u;
-    }
+    for (int j = 0; j < NT; ++j) wsoff[j] = pw_w_offset(p, ntile0u + j);
     const uint32_t wvoff = (uint32_t)lane * 16u;
     // W fragments double-buffered by k-step (a stage of codes is 2 registers per lane, so there is room -- the float32-interface
     // kernel has none): W(2t+1) is requested at the top of stage t, BEFORE the X loads of stage t+2, W(2t+2) once the first
@@ -554,8 +457,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_ti
     // wait sits behind X loads that have not been waited for already (loads retire in order through one counter).
     half8 whb[2][NT];
     half8 wlb[2][PASSES == 3 ? NT : 1];   // PASSES == 3: the lo plane's fragments, same offsets behind p.wlo
-    const __amdgpu_buffer_rsrc_t rwl = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(PASSES == 3 ? p.wlo : p.whi), 0,
-                                                                         (uint32_t)(wbytes > 0xFFFFFFFFull ? 0xFFFFFFFFull : wbytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rwl = pw_w_rsrc(PASSES == 3 ? p.wlo : p.whi, p);
     auto load_w = [&](int kstep, int b) {
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
@@ -565,6 +467,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_ti
                 wlb[b][j] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rwl, wvoff, wsoff[j] + (uint32_t)kstep * 1024u, 0));
         }
     };
+    // (this step stands in conv_pw.hip's k_pw_tiled too, there with single-buffered W and a diagnostic macro)
     auto mfma_step = [&](int buf, int ks, int b) {
         const unsigned char* hi = xs + (size_t)buf * PL * XBYTES;
 #pragma unroll
@@ -603,7 +506,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_ti
         mfma_step(buf, 1, 1);
         __syncthreads();
     }
-    // staged epilogue geometry (float32 out): piece h of tile row i = 4 pixel rows x the wave's 64 channels, 16 bytes per lane
+    // staged epilogue geometry (float32 out; this and the staged store loop below stand in k_pw_tiled too): piece h of tile row i = 4 pixel rows x the wave's 64 channels, 16 bytes per lane
     const int srow = lane >> 4, sch = lane & 15;
     const int n_st = ntile0 * 16 + sch * 4;
     const uint64_t yleft = (uint64_t)(p.M - m0) * p.N * 4;
@@ -633,26 +536,11 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) <= 4 ? 2 : 4) void k_pwc_ti
     float* lsh = lsc + BN;
     if (p.post.scale) {
         __syncthreads();
-        for (int i = threadIdx.x; i < BN; i += T) {
-            const bool in = n_lo + i < p.N;
-            lsc[i] = in ? p.post.scale[n_lo + i] : 1.f;
-            lsh[i] = in ? p.post.shift[n_lo + i] : 0.f;
-        }
+        pw_bn_slice_fill<BN, T>(lsc, lsh, p.post.scale, p.post.shift, p.N, n_lo);
         __syncthreads();
     }
-    auto out_tile = [&](int i, int j) {
-        const int n = (ntile0 + j) * 16 + kq * 4;
-        const bool in = n < p.N;
-        float4 r = epilogue(acc[i][j], bias_q256(in ? p.bias : nullptr, n, p.s1, p.s2), p.s1x, p.s2);
-        if (p.post.scale) {
-            const float4 sc = *reinterpret_cast<const float4*>(lsc + (in ? n - n_lo : 0));
-            const float4 sh = *reinterpret_cast<const float4*>(lsh + (in ? n - n_lo : 0));
-            r = affine4(r, sc, sh);
-        }
-        if constexpr (!YC && !RES) {   // with a residual the ReLU follows the add
-            if (p.post.relu) r = relu4(r);
-        }
-        return r;
+    auto out_tile = [&](int i, int j) {   // with a residual the ReLU follows the add; with code output it is the quantizer's
+        return pw_tile_finish<!YC && !RES, false>(acc[i][j], p, (ntile0 + j) * 16 + kq * 4, n_lo, lsc, lsh);
     };
     if constexpr (YC) {
         const CodeQuant cq{p.enc.r1, p.enc.lo, p.enc.hi, p.sgn, p.fmt_out};
@@ -767,16 +655,14 @@ static int pwc_select(int K, int N, const ConvPlan& plan, bool y_codes, bool has
         return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): unsupported channel count %d", K);
     }
     s->kernel = kPwcTiled;
-    if (N > 256) { s->wm = 1; s->wn = 8; s->mt = 4; }        // 64 px x 512 ch
-    else if (N > 128) { s->wm = 1; s->wn = 4; s->mt = 4; }   // 64 px x 256 ch
-    else if (N > 64) { s->wm = 2; s->wn = 2; s->mt = 2; }    // 64 px x 128 ch
-    else { s->wm = 4; s->wn = 1; s->mt = 1; }                // 64 px x  64 ch
+    const PwTiling t = pw_tiling(N, true);
+    s->wm = t.wm; s->wn = t.wn; s->mt = t.mt;
     return SLFP_OK;
 }
 
 static const char* pwc_sel_name(const PwcSel& s) {
     static thread_local char buf[64];
-    const char* fmt = s.fmt == kFmtSfp7 ? "sfp7" : "act8";
+    const char* fmt = pw_fmt_word(s.fmt);
     const char* form = s.yc ? (s.lut ? "yc-lut" : "yc") : (s.dual ? "res/dual" : (s.res ? "res" : "f32"));
     int n;
     if (s.kernel == kPwcStream) n = snprintf(buf, sizeof buf, "pwc-stream/ks%d/%s/%s/%s", s.ks, s.half ? "half" : (s.xw ? "xw" : "dw"), fmt, form);
@@ -787,74 +673,99 @@ static const char* pwc_sel_name(const PwcSel& s) {
     return buf;
 }
 
+// From the selection to the kernel: one typed lookup per kernel template.  nullptr: the launchers have no such instance.  launch_pwc_sel
+// launches what the lookup returns and the name functions ask it before they print a name.  The restrictions of the table epilogue
+// (LUT_OK) and of the three-pass mode live here, not in the kernels.
+typedef void (*PwcFn)(const PwcParams);
+
 template <int FMT, int KS, bool XW, bool HALF = false, int PASSES = 1>
-static int launch_pwc_stream(PwcParams& p, const PwcSel& s, hipStream_t stream, bool dry) {
-    const size_t lds = (size_t)(PASSES == 3 ? 2 : 1) * p.n_tiles * p.KS * 1024 + (size_t)3 * p.n_tiles * 16 * sizeof(float);
+static PwcFn pwc_stream_form(const PwcSel& s) {
     // the table epilogue: the whole-tile k-step counts the layerout nets' 1x1 layers have (32 / 64 / 128 input channels)
     constexpr bool LUT_OK = PASSES == 1 && !HALF && (KS == 1 || KS == 2 || KS == 4);
-    if (s.lut && !LUT_OK) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): no table-epilogue instance for %s", pwc_sel_name(s));
-    void (*fn)(const PwcParams);
-    if constexpr (PASSES == 3) {
-        if (s.res || s.dual) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): no three-pass residual instance for %s", pwc_sel_name(s));
-        fn = s.yc ? k_pwc_stream<FMT, KS, XW, true, false, false, false, false, 3> : k_pwc_stream<FMT, KS, XW, false, false, false, false, false, 3>;
+    if (s.lut && !LUT_OK) return nullptr;
+    if constexpr (PASSES == 3) {   // plain float32 or code output only
+        if (s.res || s.dual) return nullptr;
+        return s.yc ? k_pwc_stream<FMT, KS, XW, true, false, false, false, false, 3> : k_pwc_stream<FMT, KS, XW, false, false, false, false, false, 3>;
     } else {
-        fn = s.yc ? (s.lut ? k_pwc_stream<FMT, KS, XW, true, false, HALF, false, LUT_OK> : k_pwc_stream<FMT, KS, XW, true, false, HALF>)
-                  : (s.dual ? k_pwc_stream<FMT, KS, XW, false, true, HALF, true> : (s.res ? k_pwc_stream<FMT, KS, XW, false, true, HALF> : k_pwc_stream<FMT, KS, XW, false, false, HALF>));
+        if (s.yc) return s.lut ? k_pwc_stream<FMT, KS, XW, true, false, HALF, false, LUT_OK> : k_pwc_stream<FMT, KS, XW, true, false, HALF>;
+        if (s.dual) return k_pwc_stream<FMT, KS, XW, false, true, HALF, true>;
+        return s.res ? k_pwc_stream<FMT, KS, XW, false, true, HALF> : k_pwc_stream<FMT, KS, XW, false, false, HALF>;
     }
-    if (dry) return SLFP_OK;   // the instance exists: pwc_variant_name's check, before anything touches a device
-    int rc = raise_lds_limit(reinterpret_cast<const void*>(fn), lds);
-    if (rc != SLFP_OK) return rc;
-    int per_cu = resident_blocks_per_cu(reinterpret_cast<const void*>(fn), kPwcThreads, lds);
-    per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
-    const int64_t groups = (p.M + 15) / 16;
-    int64_t grid = (int64_t)device_cu_count() * per_cu;
-    const int64_t need = ceil_div(groups, kPwcThreads / 64);
-    if (grid > need) grid = need;
-    if (s.grid_cap > 0 && grid > s.grid_cap) grid = s.grid_cap;   // SLFP_PW_GRID: several trips of the persistent loop at small shapes
-    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kPwcThreads), lds, stream, p);
-    return check_launch("slfp pointwise (codes, stream) kernel");
+}
+template <int FMT, int PASSES>
+static PwcFn pwc_stream_instance_fp(const PwcSel& s) {
+    if (s.half) {
+        if constexpr (PASSES == 1) {
+            if (s.ks == 1) return pwc_stream_form<FMT, 1, false, true>(s);
+            if (s.ks == 2) return pwc_stream_form<FMT, 2, false, true>(s);
+        }
+        return nullptr;
+    }
+    switch (s.ks * 2 + (s.xw ? 1 : 0)) {
+        case 2: return pwc_stream_form<FMT, 1, false, false, PASSES>(s);
+        case 5: return pwc_stream_form<FMT, 2, true, false, PASSES>(s);
+        case 6: return pwc_stream_form<FMT, 3, false, false, PASSES>(s);
+        case 9: return pwc_stream_form<FMT, 4, true, false, PASSES>(s);
+        case 17: return pwc_stream_form<FMT, 8, true, false, PASSES>(s);
+        default: return nullptr;
+    }
+}
+static PwcFn pwc_stream_instance(const PwcSel& s) {
+    if (s.passes == 3) return s.fmt == kFmtAct8 ? pwc_stream_instance_fp<kFmtAct8, 3>(s) : nullptr;
+    return s.fmt == kFmtSfp7 ? pwc_stream_instance_fp<kFmtSfp7, 1>(s) : pwc_stream_instance_fp<kFmtAct8, 1>(s);
 }
 
-template <int FMT, int WM, int WN, int MT, int PASSES = 1>
-static int launch_pwc_tiled(PwcParams& p, const PwcSel& s, hipStream_t stream, bool dry) {
-    constexpr int BM = WM * MT * 16, BN = WN * 4 * 16, T = 64 * WM * WN;
-    p.n_blocks = (uint32_t)ceil_div((int64_t)p.N, BN);
-    p.rb = BM;
-    p.m_blocks = (uint32_t)ceil_div(p.M, p.rb);
-    const int64_t nblocks = (int64_t)p.m_blocks * p.n_blocks;
-    if (nblocks > 0x7FFFFFFF) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): grid too large");
-    p.nblocks = (uint32_t)nblocks;
-    const size_t lds = (size_t)2 * (PASSES == 3 ? 2 : 1) * BM * 128 + (s.yc ? 0 : (size_t)(T / 64) * 16 * kStgRow);
+template <int FMT, int WM, int WN, int MT, int PASSES>
+static PwcFn pwc_tiled_form(const PwcSel& s) {
     constexpr bool LUT_OK = PASSES == 1 && WM == 1 && WN == 8 && MT == 4;   // the table epilogue: the deep layers (C_out > 256)
-    if (s.lut && !LUT_OK) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): no table-epilogue instance for %s", pwc_sel_name(s));
-    void (*fn)(const PwcParams);
-    if constexpr (PASSES == 3) {
-        if (s.res || s.dual) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): no three-pass residual instance for %s", pwc_sel_name(s));
-        fn = s.yc ? k_pwc_tiled<FMT, WM, WN, MT, true, false, false, false, 3> : k_pwc_tiled<FMT, WM, WN, MT, false, false, false, false, 3>;
+    if (s.lut && !LUT_OK) return nullptr;
+    if constexpr (PASSES == 3) {   // plain float32 or code output only
+        if (s.res || s.dual) return nullptr;
+        return s.yc ? k_pwc_tiled<FMT, WM, WN, MT, true, false, false, false, 3> : k_pwc_tiled<FMT, WM, WN, MT, false, false, false, false, 3>;
     } else {
-        fn = s.yc ? (s.lut ? k_pwc_tiled<FMT, WM, WN, MT, true, false, false, LUT_OK> : k_pwc_tiled<FMT, WM, WN, MT, true>)
-                  : (s.dual ? k_pwc_tiled<FMT, WM, WN, MT, false, true, true> : (s.res ? k_pwc_tiled<FMT, WM, WN, MT, false, true> : k_pwc_tiled<FMT, WM, WN, MT, false>));
+        if (s.yc) return s.lut ? k_pwc_tiled<FMT, WM, WN, MT, true, false, false, LUT_OK> : k_pwc_tiled<FMT, WM, WN, MT, true>;
+        if (s.dual) return k_pwc_tiled<FMT, WM, WN, MT, false, true, true>;
+        return s.res ? k_pwc_tiled<FMT, WM, WN, MT, false, true> : k_pwc_tiled<FMT, WM, WN, MT, false>;
     }
-    if (dry) return SLFP_OK;   // the instance exists: pwc_variant_name's check, before anything touches a device
-    int rc = raise_lds_limit(reinterpret_cast<const void*>(fn), lds);
-    if (rc != SLFP_OK) return rc;
-    hipLaunchKernelGGL(fn, dim3(p.nblocks), dim3(T), lds, stream, p);
-    return check_launch("slfp pointwise (codes, tiled) kernel");
+}
+template <int FMT, int PASSES>
+static PwcFn pwc_tiled_instance_fp(const PwcSel& s) {
+    return pw_tiling_instance<PASSES == 1>(s.wm, s.wn, s.mt, [&](auto t) -> PwcFn {
+        using G = decltype(t);
+        return pwc_tiled_form<FMT, G::kWM, G::kWN, G::kMT, PASSES>(s);
+    });
+}
+static PwcFn pwc_tiled_instance(const PwcSel& s) {
+    if (s.passes == 3) return s.fmt == kFmtAct8 ? pwc_tiled_instance_fp<kFmtAct8, 3>(s) : nullptr;
+    return s.fmt == kFmtSfp7 ? pwc_tiled_instance_fp<kFmtSfp7, 1>(s) : pwc_tiled_instance_fp<kFmtAct8, 1>(s);
 }
 
 template <int FMT, int NTS>
-static int launch_pwc_slice(PwcParams& p, const PwcSel& s, hipStream_t stream, bool dry) {
-    const size_t lds = (size_t)NTS * p.KS * 1024 + (size_t)3 * NTS * 16 * sizeof(float);
+static PwcFn pwc_slice_form(const PwcSel& s) {
     constexpr bool LUT_OK = NTS == 8;   // the table epilogue: 256 -> 256 / 512
-    if (s.lut && !LUT_OK) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): no table-epilogue instance for %s", pwc_sel_name(s));
-    auto fn = s.yc ? (s.lut ? k_pwc_slice<FMT, NTS, true, false, false, LUT_OK> : k_pwc_slice<FMT, NTS, true>)
-                   : (s.dual ? k_pwc_slice<FMT, NTS, false, true, true> : (s.res ? k_pwc_slice<FMT, NTS, false, true> : k_pwc_slice<FMT, NTS, false>));
-    if (dry) return SLFP_OK;   // the instance exists: pwc_variant_name's check, before anything touches a device
+    if (s.lut && !LUT_OK) return nullptr;
+    if (s.yc) return s.lut ? k_pwc_slice<FMT, NTS, true, false, false, LUT_OK> : k_pwc_slice<FMT, NTS, true>;
+    if (s.dual) return k_pwc_slice<FMT, NTS, false, true, true>;
+    return s.res ? k_pwc_slice<FMT, NTS, false, true> : k_pwc_slice<FMT, NTS, false>;
+}
+static PwcFn pwc_slice_instance(const PwcSel& s) {
+    if (s.passes == 3) return nullptr;
+    if (s.nts == 8) return s.fmt == kFmtSfp7 ? pwc_slice_form<kFmtSfp7, 8>(s) : pwc_slice_form<kFmtAct8, 8>(s);
+    if (s.nts == 4) return s.fmt == kFmtSfp7 ? pwc_slice_form<kFmtSfp7, 4>(s) : pwc_slice_form<kFmtAct8, 4>(s);
+    return nullptr;
+}
+
+static PwcFn pwc_instance(const PwcSel& s) {
+    return s.kernel == kPwcSlice ? pwc_slice_instance(s) : (s.kernel == kPwcStream ? pwc_stream_instance(s) : pwc_tiled_instance(s));
+}
+
+static int launch_pwc_slice(PwcFn fn, PwcParams& p, const PwcSel& s, hipStream_t stream) {
+    const size_t lds = (size_t)s.nts * p.KS * 1024 + (size_t)3 * s.nts * 16 * sizeof(float);
     int rc = raise_lds_limit(reinterpret_cast<const void*>(fn), lds);
     if (rc != SLFP_OK) return rc;
     int per_cu = resident_blocks_per_cu(reinterpret_cast<const void*>(fn), kSliceThreads, lds);
     per_cu = per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu);
-    const int n_slices = p.n_tiles / NTS;
+    const int n_slices = p.n_tiles / s.nts;
     // grid = 8 (XCDs) x n_slices x ranks-per-XCD: as many whole (slice set) groups as fit the device
     const int64_t slots = (int64_t)device_cu_count() * per_cu;
     int64_t groups = slots / (8 * n_slices);
@@ -868,33 +779,15 @@ static int launch_pwc_slice(PwcParams& p, const PwcSel& s, hipStream_t stream, b
     return check_launch("slfp pointwise (codes, slice) kernel");
 }
 
-template <int FMT>
-static int launch_pwc_fmt(PwcParams& p, const PwcSel& s, hipStream_t stream, bool dry) {
-    if (s.kernel == kPwcSlice) {
-        if (s.nts == 8) return launch_pwc_slice<FMT, 8>(p, s, stream, dry);
-        if (s.nts == 4) return launch_pwc_slice<FMT, 4>(p, s, stream, dry);
-    } else if (s.kernel == kPwcStream) {
-        if (s.half) {
-            if (s.ks == 1) return launch_pwc_stream<FMT, 1, false, true>(p, s, stream, dry);
-            if (s.ks == 2) return launch_pwc_stream<FMT, 2, false, true>(p, s, stream, dry);
-        } else {
-            switch (s.ks * 2 + (s.xw ? 1 : 0)) {
-                case 2: return launch_pwc_stream<FMT, 1, false>(p, s, stream, dry);
-                case 5: return launch_pwc_stream<FMT, 2, true>(p, s, stream, dry);
-                case 6: return launch_pwc_stream<FMT, 3, false>(p, s, stream, dry);
-                case 9: return launch_pwc_stream<FMT, 4, true>(p, s, stream, dry);
-                case 17: return launch_pwc_stream<FMT, 8, true>(p, s, stream, dry);
-                default: break;
-            }
-        }
-    } else {
-        const int t = s.wm * 100 + s.wn * 10 + s.mt;
-        if (t == 184) return launch_pwc_tiled<FMT, 1, 8, 4>(p, s, stream, dry);
-        if (t == 144) return launch_pwc_tiled<FMT, 1, 4, 4>(p, s, stream, dry);
-        if (t == 222) return launch_pwc_tiled<FMT, 2, 2, 2>(p, s, stream, dry);
-        if (t == 411) return launch_pwc_tiled<FMT, 4, 1, 1>(p, s, stream, dry);
-    }
-    return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): no kernel instance for %s", pwc_sel_name(s));
+// Launches the instance of a selection (pwc_select or pwc_x3_select).
+static int launch_pwc_sel(PwcParams& p, const PwcSel& s, hipStream_t stream) {
+    const PwcFn fn = pwc_instance(s);
+    if (!fn) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): no kernel instance for %s", pwc_sel_name(s));
+    if (s.kernel == kPwcSlice) return launch_pwc_slice(fn, p, s, stream);
+    if (s.kernel == kPwcTiled)   // float32 out: the staged epilogue
+        return pw_launch_tiled(fn, p, PwTiling{s.wm, s.wn, s.mt}, s.passes, !s.yc, stream, "pointwise (codes)", "slfp pointwise (codes, tiled) kernel");
+    const size_t lds = (size_t)(s.passes == 3 ? 2 : 1) * p.n_tiles * p.KS * 1024 + (size_t)3 * p.n_tiles * 16 * sizeof(float);
+    return pw_launch_stream(fn, p, lds, s.grid_cap, stream, "slfp pointwise (codes, stream) kernel");
 }
 
 // ---- float32-equivalent (three-pass) mode: slfp_conv2d_fwd_codes_x3 ----
@@ -915,37 +808,15 @@ static int pwc_x3_select(int K, int N, const ConvPlan& plan, bool y_codes, PwcSe
     }
     if (K % 64 != 0) return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes, three passes): unsupported channel count %d", K);
     s->kernel = kPwcTiled;
-    if (N > 128) { s->wm = 1; s->wn = 4; s->mt = 4; }        // 64 px x 256 ch
-    else if (N > 64) { s->wm = 2; s->wn = 2; s->mt = 2; }    // 64 px x 128 ch
-    else { s->wm = 4; s->wn = 1; s->mt = 1; }                // 64 px x  64 ch
+    const PwTiling t = pw_tiling(N, false);   // the x3 path never takes {1, 8, 4}
+    s->wm = t.wm; s->wn = t.wn; s->mt = t.mt;
     return SLFP_OK;
 }
 
-static int launch_pwc_x3_sel(PwcParams& p, const PwcSel& s, hipStream_t stream, bool dry) {
-    if (s.kernel == kPwcStream) {
-        switch (s.ks) {
-            case 1: return launch_pwc_stream<kFmtAct8, 1, false, false, 3>(p, s, stream, dry);
-            case 2: return launch_pwc_stream<kFmtAct8, 2, true, false, 3>(p, s, stream, dry);
-            case 3: return launch_pwc_stream<kFmtAct8, 3, false, false, 3>(p, s, stream, dry);
-            case 4: return launch_pwc_stream<kFmtAct8, 4, true, false, 3>(p, s, stream, dry);
-            case 8: return launch_pwc_stream<kFmtAct8, 8, true, false, 3>(p, s, stream, dry);
-            default: break;
-        }
-    } else {
-        const int t = s.wm * 100 + s.wn * 10 + s.mt;
-        if (t == 144) return launch_pwc_tiled<kFmtAct8, 1, 4, 4, 3>(p, s, stream, dry);
-        if (t == 222) return launch_pwc_tiled<kFmtAct8, 2, 2, 2, 3>(p, s, stream, dry);
-        if (t == 411) return launch_pwc_tiled<kFmtAct8, 4, 1, 1, 3>(p, s, stream, dry);
-    }
-    return fail(SLFP_ERR_UNSUPPORTED, "pointwise (codes): no kernel instance for %s", pwc_sel_name(s));
-}
-
 const char* pwc_x3_variant_name(const slfp_conv2d_desc& d, const ConvPlan& plan, bool y_codes) {
-    PwcParams p = {};   // the dry dispatch reads none of the pointers
     PwcSel s;
     if (plan.family != kPointwise || plan.passes != 3 || pwc_x3_select((int)d.c_in, (int)d.c_out, plan, y_codes, &s) != SLFP_OK) return "none";
-    if (launch_pwc_x3_sel(p, s, nullptr, true) != SLFP_OK) return "none";
-    return pwc_sel_name(s);
+    return pwc_instance(s) ? pwc_sel_name(s) : "none";
 }
 
 bool pwc_x3_applicable(const slfp_conv2d_desc& d, const ConvPlan& plan, int post_flags, bool y_codes) {
@@ -960,15 +831,10 @@ static void pwc_fill(PwcParams& p, const slfp_conv2d_desc& d, const ConvPlan& pl
                      const PostOp& post, void* y, const CodeIo& io) {
     p.post = post;
     p.x = x; p.bias = bias; p.y = y; p.res = nullptr; p.yc = nullptr;
-    p.K = (int)d.c_in; p.N = (int)d.c_out;
+    pw_fill_geom(p, d, plan);
     p.y_ld = io.y_ld ? (int)io.y_ld : p.N;
-    p.KS = (int)(plan.k_pad / 32);
-    p.n_tiles = (int)(plan.n_pad / 16);
     p.whi = reinterpret_cast<const _Float16*>(wfrag);
     p.wlo = plan.passes == 3 ? p.whi + (size_t)plan.n_pad * plan.k_pad : nullptr;
-    p.H = (int)d.h; p.W = (int)d.w; p.Ho = (int)plan.h_out; p.Wo = (int)plan.w_out; p.S = d.stride_h;
-    p.M = d.n * plan.h_out * plan.w_out;
-    p.s1 = plan.s1; p.s2 = plan.s2; p.s1x = plan.s1 * (1.0f / 256.0f);
     p.sgn = post.relu ? 0 : 1;
     p.fmt_out = io.y_fmt;
     p.enc.valid = 0;
@@ -988,7 +854,7 @@ int launch_pwc_x3(const slfp_conv2d_desc& d, const ConvPlan& plan, const uint8_t
     PwcSel s;
     const int rc = pwc_x3_select(p.K, p.N, plan, io.y_codes, &s);
     if (rc != SLFP_OK) return rc;
-    return launch_pwc_x3_sel(p, s, stream, false);
+    return launch_pwc_sel(p, s, stream);
 }
 
 int launch_pwc(const slfp_conv2d_desc& d, const ConvPlan& plan, const uint8_t* x, const void* wfrag, const float* bias,
@@ -1015,17 +881,14 @@ int launch_pwc(const slfp_conv2d_desc& d, const ConvPlan& plan, const uint8_t* x
     const int rc = pwc_select(p.K, p.N, plan, y_codes, res != nullptr, res_codes != nullptr, &s);
     if (rc != SLFP_OK) return rc;
     s.lut = io.lut != nullptr;
-    if (s.fmt == kFmtSfp7) return launch_pwc_fmt<kFmtSfp7>(p, s, stream, false);
-    return launch_pwc_fmt<kFmtAct8>(p, s, stream, false);
+    return launch_pwc_sel(p, s, stream);
 }
 
 const char* pwc_variant_name(const slfp_conv2d_desc& d, const ConvPlan& plan, bool y_codes, bool has_res, bool has_dual, bool lut) {
-    PwcParams p = {};   // the dry dispatch reads none of the pointers
     PwcSel s;
     if (plan.family != kPointwise || pwc_select((int)d.c_in, (int)d.c_out, plan, y_codes, has_res, has_dual, &s) != SLFP_OK) return "none";
     s.lut = lut;
-    if ((s.fmt == kFmtSfp7 ? launch_pwc_fmt<kFmtSfp7>(p, s, nullptr, true) : launch_pwc_fmt<kFmtAct8>(p, s, nullptr, true)) != SLFP_OK) return "none";
-    return pwc_sel_name(s);
+    return pwc_instance(s) ? pwc_sel_name(s) : "none";
 }
 
 }  // namespace slfp

@@ -69,8 +69,6 @@ __device__ __forceinline__ u32x4 res_add_stg(const u32x4 v, const u32x4 q, const
 // 128-byte rows (64 fp16); XOR swizzle so that the 16 rows a fragment read touches hit
 // 16 distinct 16-byte slots (conflict-free ds_read_b128; cdna guide T2)
 __device__ __forceinline__ uint32_t lds_x_off(int row, int chunk16) {
-    // 128-byte rows (64 fp16); XOR swizzle so that the 16 rows a fragment read touches hit
-    // 16 distinct 16-byte slots (conflict-free ds_read_b128; cdna guide T2)
     return (uint32_t)row * 128u + (uint32_t)((chunk16 ^ (row & 7)) << 4);
 }
 
