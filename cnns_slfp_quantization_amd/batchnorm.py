@@ -1,7 +1,8 @@
 """Training-mode BatchNorm2d (+ReLU) on libslfp_hip's kernels (csrc/bn_train.hip; include/slfp.h states the order of every
 sum): the autograd Function behind fusion.TrainBatchNorm2d.  float32 channels_last tensors on the ROCm device only; there is no
 fallback in here -- the module decides with bn_train_supported() and otherwise runs ATen's batch_norm itself.  Also the residual,
-table and code forms of the same kernels, and the Function that spans BatchNorm -> ReLU -> Conv2d_Q on 1-byte codes."""
+table and code forms of the same kernels, the Function that spans BatchNorm -> ReLU -> Conv2d_Q on 1-byte codes, and the pair that
+puts a Bottleneck's trunk on codes: the tail that writes them next to float32 and the Conv2d_Q Function that reads them."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -143,17 +144,23 @@ class hip_bn_res_train(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        x, weight, save_mean, save_invstd = ctx.saved_tensors[:4]
-        y = ctx.saved_tensors[4] if ctx.relu else x   # relu == 0: y is not read; any valid pointer stands in
-        gy, gamma = _nhwc(gy), _vec(weight)
-        gx, ggamma, gbeta = _grads(ctx, x, save_mean, 2)
-        gres = None
-        if ctx.needs_input_grad[1]:
-            gres = torch.empty_like(x) if ctx.relu else gy   # relu == 0: g is gy itself, no copy is asked of the kernel
-        _call("slfp_bn_res_train_bwd", x, x.data_ptr(), y.data_ptr(), gy.data_ptr(), gamma.data_ptr(), save_mean.data_ptr(),
-              save_invstd.data_ptr(), 1 if ctx.relu else 0, gx.data_ptr(), _ptr(gres) if ctx.relu else None, _ptr(ggamma),
-              _ptr(gbeta))
-        return gx if ctx.needs_input_grad[0] else None, gres, ggamma, gbeta, None, None, None, None, None
+        return _bn_res_backward(ctx, gy) + (None,) * 5
+
+
+def _bn_res_backward(ctx, gy):
+    """(gx, gres, ggamma, gbeta) of slfp_bn_res_train_bwd from what hip_bn_res_train.forward saved: the backward of the residual
+    form and of the residual-and-codes form, whose inputs both start (x, res, weight, bias)."""
+    x, weight, save_mean, save_invstd = ctx.saved_tensors[:4]
+    y = ctx.saved_tensors[4] if ctx.relu else x   # relu == 0: y is not read; any valid pointer stands in
+    gy, gamma = _nhwc(gy), _vec(weight)
+    gx, ggamma, gbeta = _grads(ctx, x, save_mean, 2)
+    gres = None
+    if ctx.needs_input_grad[1]:
+        gres = torch.empty_like(x) if ctx.relu else gy   # relu == 0: g is gy itself, no copy is asked of the kernel
+    _call("slfp_bn_res_train_bwd", x, x.data_ptr(), y.data_ptr(), gy.data_ptr(), gamma.data_ptr(), save_mean.data_ptr(),
+          save_invstd.data_ptr(), 1 if ctx.relu else 0, gx.data_ptr(), _ptr(gres) if ctx.relu else None, _ptr(ggamma),
+          _ptr(gbeta))
+    return gx if ctx.needs_input_grad[0] else None, gres, ggamma, gbeta
 
 
 # ---- BatchNorm2d -> layerout_quantize_func -> activation (slfp_bn_lut_train_fwd / _bwd; DESIGN section 32) -------------------
@@ -332,3 +339,87 @@ class hip_bn_codes_conv_train(torch.autograd.Function):
             _call("slfp_bn_codes_train_bwd", x, x.data_ptr(), g.data_ptr(), gamma.data_ptr(), beta.data_ptr(), save_mean.data_ptr(),
                   save_invstd.data_ptr(), save_lo.data_ptr(), 1 if ctx.relu else 0, gx.data_ptr(), _ptr(ggamma), _ptr(gbeta))
         return gx if need[0] else None, ggamma, gbeta, gw, gb, None, None, None
+
+
+# ---- BatchNorm2d -> residual add -> ReLU that writes the float32 trunk AND its readers' codes (slfp_bn_res_codes_train_fwd;
+# DESIGN section 38) ---------------------------------------------------------------------------------------------------------------
+# The size rule of the residual-and-codes form, by the spread rule of sections 27-35: the smallest size class from which this class
+# and every larger measured one beat the better unlinked leg by more than that leg's round-to-round spread, in two runs.
+# Read from profiles/bn_res_codes_train_bench.json and its second run (ResNet-50's trunk shapes at batch 64 and 128, forward +
+# backward of [bn3 tail, next conv1 (+ downsample.0)], options.backward = "hip_all"; the better unlinked leg is the residual kernels
+# from 24 M elements on and the stock modules below; M = 2^20 elements of the trunk; speed-ups of the first, second run):
+#   98 M       both rows ahead in both runs: the boundary row 1.030x, 1.031x, the plain row 1.012x, 1.012x
+#   49 M       the two boundary rows ahead (1.008-1.018x), the two plain rows BEHIND in both runs (0.977x, 0.986x; 0.986x, 0.987x)
+#   24.5 M     64 x 28x28x512 into conv1 alone behind in both runs (0.991x, 0.994x), the other three rows ahead (1.013-1.028x)
+#   12.25 M, 6.12 M   every row ahead (1.045-1.174x) -- against the stock modules, the better unlinked leg there: what wins is
+#              mostly the residual kernels the default rule of section 33 leaves out at these sizes -- and under failing classes
+# So a trunk of fewer than 98 M elements stays float32 unless told otherwise (min_elements=0): at batch 128 that links the 56 x 56
+# trunks of layer1, at batch 64 nothing.  The whole Bottleneck-stack step at batch 64 moved from 15.167 to 15.147 ms with the seven
+# trunk links alone and from 14.861 to 14.792 ms on top of the in-block links.
+RES_CODES_MIN_ELEMENTS = 98 << 20
+
+
+def bn_res_codes_train_supported(x, ka, q_bit, min_elements=None):
+    """bn_train_supported under the residual-and-codes form's size rule (None: RES_CODES_MIN_ELEMENTS, which may leave everything
+    out), and slfp_bn_res_codes_train_supported for the readers' quantizer (ka: float32(Ka) as a Python float)."""
+    floor = RES_CODES_MIN_ELEMENTS if min_elements is None else min_elements
+    if floor is None or not bn_train_supported(x, floor):
+        return False
+    n, c, h, w = x.shape
+    return bool(_lib.load().slfp_bn_res_codes_train_supported(n, h, w, c, _lib.LAYOUT_NHWC, ka, int(q_bit)))
+
+
+class hip_bn_res_codes_train(torch.autograd.Function):
+    """hip_bn_res_train that also returns y as the uint8 channels_last extended codes of QA(y / ka), the quantizer of the Conv2d_Q
+    layers that read the trunk (slfp_bn_res_codes_train_fwd): (y, codes), the codes not differentiable.  y is bit for bit
+    hip_bn_res_train's and is what the backward reads, so the backward is hip_bn_res_train's own.  Saved for the backward is what
+    hip_bn_res_train saves; the codes belong to the readers (hip_trunk_codes_conv_train)."""
+
+    @staticmethod
+    def forward(ctx, x, res, weight, bias, running_mean, running_var, momentum, eps, relu, ka, q_bit):
+        if res.shape != x.shape or res.dtype != x.dtype or res.device != x.device:
+            raise ValueError("hip_bn_res_codes_train: the residual must have x's shape, dtype and device")
+        x = x.detach()
+        res = _nhwc(res.detach())
+        gamma, beta = _vec(weight), _vec(bias)
+        y, save_mean, save_invstd = _outputs(x, 2)
+        codes = torch.empty(x.shape, dtype=torch.uint8, device=x.device, memory_format=torch.channels_last)
+        _call("slfp_bn_res_codes_train_fwd", x, x.data_ptr(), res.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(running_mean),
+              _ptr(running_var), float(momentum), float(eps), 1 if relu else 0, float(ka), int(q_bit), y.data_ptr(), codes.data_ptr(),
+              save_mean.data_ptr(), save_invstd.data_ptr())
+        ctx.relu = bool(relu)
+        ctx.mark_non_differentiable(codes)
+        ctx.save_for_backward(x, weight, save_mean, save_invstd, *((y,) if ctx.relu else ()))
+        return y, codes
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy, _gcodes):
+        return _bn_res_backward(ctx, gy) + (None,) * 7
+
+
+class hip_trunk_codes_conv_train(torch.autograd.Function):
+    """conv(trunk) for a Conv2d_Q that reads a trunk linked by fusion.link_bottleneck_codes_train: `codes` are the trunk as the
+    extended codes of this conv's own quantizer, written by hip_bn_res_codes_train.  The differentiable inputs are the float32
+    trunk (never read), the conv's weight and (scaled) bias.  The forward is the conv's code-reading forward with freshly prepared
+    weights (never the cache: an optimizer steps `.data` unseen); saved are the codes and the weight, never the float32 tensor.  The
+    backward is slfp_conv2d_bwd_codes; its gx is the trunk's gradient, which autograd adds to the next tail's."""
+
+    @staticmethod
+    def forward(ctx, trunk, weight, bias, conv, codes):
+        from .conv2d_func import _launch, _plan
+        plan = _plan(conv, codes, weight, True, True, ("codes", True, None, None))
+        if not plan.ok:
+            raise RuntimeError("hip_trunk_codes_conv_train: no code-reading forward for this layer (slfp_conv2d_codes_supported)")
+        y = _launch(conv, plan, codes, weight, bias, cache=False)
+        ctx.conv, ctx.has_bias = conv, bias is not None
+        ctx.save_for_backward(codes, weight)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        from .conv2d_func import _conv_desc, _hip_backward_codes, _needs
+        codes, weight = ctx.saved_tensors
+        gx, gw, gb = _hip_backward_codes(ctx.conv, _conv_desc(ctx.conv, codes.shape, True, True), codes, weight, _nhwc(gy), _needs(ctx))
+        return gx, gw, gb, None, None

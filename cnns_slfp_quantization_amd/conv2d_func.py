@@ -864,6 +864,32 @@ def _conv_class(q_bit, Kw, Ka, bias_default, scaled_bias):
             self.output = out
             return out
 
+        def _reads_train_trunk(self, trunk, ttc):
+            """Does this module, in training mode, read the codes `ttc` = (codes, float32(Ka), q_bit) that ride on the float32
+            `trunk` instead of the tensor itself?"""
+            from .fusion import _link_conv_clean
+            codes = ttc[0]
+            if not (self.q_bit in (8, 7) and ttc[1:] == (_f32(self.Ka), self.q_bit) and _link_conv_clean(self)):
+                return False
+            if (trunk.dtype != torch.float32 or codes.shape != trunk.shape or codes.device != self.weight.device
+                    or not codes.is_contiguous(memory_format=torch.channels_last)):
+                return False
+            return (_bwd_codes_supported(self, codes.shape)
+                    and _plan(self, codes, self.weight, True, True, ("codes", True, None, None)).ok)
+
+        def _forward_train_trunk(self, trunk, codes):
+            from .batchnorm import hip_trunk_codes_conv_train
+            bias = self.bias if scaled_bias else None
+            need_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (trunk, self.weight, bias))
+            if need_grad:
+                out = hip_trunk_codes_conv_train.apply(trunk, self.weight, bias, self, codes)
+            else:
+                plan = _plan(self, codes, self.weight, True, True, ("codes", True, None, None))
+                with torch.no_grad():
+                    out = _launch(self, plan, codes, self.weight, bias, cache=False)
+            self.output = out
+            return out
+
         def forward_slice(self, input, out_slice):
             """`out_slice=(buffer, c_off)`: a linked code producer writes its codes into buffer[:, c_off:c_off + C_out] (uint8,
             channels_last, wider than this layer) in ONE launch (slfp_conv2d_fwd_codes_slice; `_last_kernel` ends in "+slice")
@@ -903,6 +929,12 @@ def _conv_class(q_bit, Kw, Ka, bias_default, scaled_bias):
                 # the codes a fusion.TrainBatchNormCodes2d wrote for THIS module's present quantizer, in a training step: BN -> ReLU ->
                 # conv as one autograd Function (or the bare code forward where nothing records).  The record leaves the tensor first
                 return self._forward_train_link(input, link)
+            ttc = input.__dict__.get("_train_trunk_codes") if type(input) is torch.Tensor and self.training else None
+            if ttc is not None and self._reads_train_trunk(input, ttc):
+                # the float32 trunk of a Bottleneck linked by fusion.link_bottleneck_codes_train carries the codes its bn3 tail wrote
+                # for THIS module's present quantizer, in a training step: read those (a stale or foreign scale, a module with
+                # something fused onto it or options.backward = "composite" reads the float32 tensor as ever)
+                return self._forward_train_trunk(input, ttc[0])
             tc = input.__dict__.get("_trunk_codes") if type(input) is torch.Tensor else None
             if tc is not None and not self.training and self.q_bit in (8, 7) and tc[1:] == (float(self.Ka), self.q_bit):
                 # the float32 trunk of a block linked by fusion.link_trunk carries the codes written for THIS module's present

@@ -46,11 +46,15 @@
 //              enc4_code_fmt<FMT, true> on the reader's kEncCode table in LDS and leave as one dword;  lo goes to save_lo
 //   backward   the ReLU's mask is t > 0 with t recomputed from x through bn_affine (y > 0 exactly where t > 0): no forward output
 //              is read;  the rest as the plain form
+// The residual-and-codes form (k_bn_apply_res_codes; slfp_bn_res_codes_train_fwd) is the residual forward with a second store: the
+// float32 trunk y as the residual form stores it and, next to it, y as the extended codes of the Conv2d_Q layers that read the
+// trunk, the four channels of a lane as one dword exactly as the code form stores them (behind the ReLU enc4_code_relu, else
+// enc4_code_fmt<FMT, true>).  One pass over x and res, the code form's one barrier (the table); its backward is the residual form's.
 // The two finalize kernels stage the records of 256 slabs x 8 channels in LDS with all 256 lanes (and the per-slab weights
 // n_b / n and n_a n_b / n, which depend on the slab index alone), then one lane per channel runs the serial chain.
 // Each of these is written once: bn_walk is the lane's walk over its rows (all five streaming kernels), bn_affine the apply's
 // expression (the apply of every form, and through bn_class the backward's recomputed class), bn_g the g of one element
-// (reduce, dx and the gres store), bn_forward / bn_backward the refusals and the three launches of a direction; the eight entry
+// (reduce, dx and the gres store), bn_forward / bn_backward the refusals and the three launches of a direction; the nine entry
 // points state their pointers and the refusals of their own form.
 #include "slfp_device.hpp"
 #include "slfp_enc.hpp"
@@ -336,11 +340,12 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_finalize(const BnArgs a, floa
     if (running_var) running_var[l.c] = (float)((1.0 - mo) * (double)running_var[l.c] + mo * (var * cnt / (cnt - 1.0)));
 }
 
-// The apply pass of every form.  CODES (V == 4, neither LUT nor RES): `enc` is the reader's kEncCode table, copied to LDS.
+// The apply pass of every form.  CODES (V == 4, never LUT): `enc` is the reader's kEncCode table, copied to LDS.  RES && CODES
+// stores both: the float32 pack of the residual form and the dword of the code form, of the same y.
 template <int V, bool LUT, bool RES, bool CODES>
 __device__ __forceinline__ void bn_apply(const BnArgs& a, const EncArgs* enc) {
     static_assert(!(LUT && RES), "the residual form has no table");
-    static_assert(!CODES || (V == 4 && !LUT && !RES), "codes leave four channels to a dword, behind the plain apply");
+    static_assert(!CODES || (V == 4 && !LUT), "codes leave four channels to a dword, behind the plain or the residual apply");
     const BnLane<V> l(a);
     const float* const sTab = bn_table_lds<LUT>(a.table);
     const unsigned char* const sE = bn_enc_lds<CODES>(enc);
@@ -352,7 +357,7 @@ __device__ __forceinline__ void bn_apply(const BnArgs& a, const EncArgs* enc) {
     for (int e = 0; e < V; ++e) map.sc.v[e] = map.sc.v[e] * gamma.v[e];
     const float* px = a.x + l.ch;
     const float* pr = RES ? a.res + l.ch : nullptr;
-    float* py = CODES ? nullptr : a.out + l.ch;
+    float* py = CODES && !RES ? nullptr : a.out + l.ch;
     const int relu = a.relu;
     constexpr int N = RES ? 2 : 1;
     bn_walk<4>(l.first, l.r1, l.nty, ld,
@@ -371,7 +376,7 @@ __device__ __forceinline__ void bn_apply(const BnArgs& a, const EncArgs* enc) {
                        } else {
                            float t = bn_affine<V>(b.p[0].v[e], map, e);
                            if constexpr (RES) t = t + b.p[1].v[e];   // the add is rounded on its own, the ReLU comes behind it
-                           if constexpr (!CODES) {   // the code quantizers fold the ReLU: enc4_code_relu
+                           if constexpr (!CODES || RES) {   // codes alone: the code quantizers fold the ReLU (enc4_code_relu)
                                if (relu) t = t < 0.f ? 0.f : t;
                            }
                            v.v[e] = t;
@@ -384,9 +389,8 @@ __device__ __forceinline__ void bn_apply(const BnArgs& a, const EncArgs* enc) {
                                                : (a.code_fmt == kFmtSfp7 ? enc4_code_fmt<kFmtSfp7, true>(t4, r1, lo, hi, sE)
                                                                          : enc4_code_fmt<kFmtAct8, true>(t4, r1, lo, hi, sE));
                        *reinterpret_cast<uint32_t*>(a.codes + o + (size_t)l.ch) = d;
-                   } else {
-                       bn_st<V>(py + o, v);
                    }
+                   if constexpr (!CODES || RES) bn_st<V>(py + o, v);
                });
 }
 
@@ -397,6 +401,10 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_apply(const BnArgs a) {
 
 __global__ __launch_bounds__(kBnThreads) void k_bn_apply_codes(const BnArgs a, const EncArgs enc) {
     bn_apply<4, false, false, true>(a, &enc);
+}
+
+__global__ __launch_bounds__(kBnThreads) void k_bn_apply_res_codes(const BnArgs a, const EncArgs enc) {
+    bn_apply<4, false, true, true>(a, &enc);
 }
 
 // What the backward loads of one row: x, gy and the forward's y (with relu only: otherwise y is never read; XM: never)
@@ -546,6 +554,7 @@ struct BnCodeCheck {
     bool ok;             // c % 4 == 0, and in the forward a y_ka and y_qbits with a proven code table (bn_codes_table)
     bool has_codes;      // the forward: y_codes counts among the pointers, 4-byte aligned
     const void* codes;
+    const char* query;   // the form's own support query, for the message
 };
 static int bn_check(const char* fn, int64_t n, int64_t h, int64_t w, int64_t c, int x_layout, int relu, const void* const* big,
                     int nbig, const void* const* small, int nsmall, const void* workspace, size_t ws_bytes, int64_t* m,
@@ -563,8 +572,8 @@ static int bn_check(const char* fn, int64_t n, int64_t h, int64_t w, int64_t c, 
         return fail(SLFP_ERR_UNSUPPORTED, "%s: no kernel for this shape / layout (slfp_bn_train_supported): NHWC only, and more "
                                           "than 1 value per channel", fn);
     if (cc && !cc->ok)
-        return fail(SLFP_ERR_UNSUPPORTED, "%s: no kernel for this shape / reader (slfp_bn_codes_train_supported): c %% 4 == 0, y_qbits "
-                                          "8 or 7, and a y_ka > 0 with a proven code table", fn);
+        return fail(SLFP_ERR_UNSUPPORTED, "%s: no kernel for this shape / reader (%s): c %% 4 == 0, y_qbits "
+                                          "8 or 7, and a y_ka > 0 with a proven code table", fn, cc->query);
     *m = n * h * w;
     const uintptr_t mask = c % 4 == 0 ? 15 : 3;
     for (int i = 0; i < nbig; ++i)
@@ -592,7 +601,7 @@ static void bn_geometry(BnArgs& a, const BnSplit& s, int64_t m, int64_t c, int r
     if (!a.gmean) a.gmean = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + bn_gmean_offset(s, c));
 }
 
-enum BnForm { kBnPlain, kBnTable, kBnRes, kBnCodes };
+enum BnForm { kBnPlain, kBnTable, kBnRes, kBnCodes, kBnResCodes };
 
 // What the code forms add to the supported set, host only: the reader's quantizer and a proven table for it.  Returns that table
 // (the one the apply is then launched with), or null.
@@ -605,7 +614,8 @@ static const EncArgs* bn_codes_table(int64_t c, float y_ka, int y_qbits) {
 }
 
 // The streaming kernels of a (vec, form); the residual form's statistics and reduce pass are the plain ones, the code form's
-// statistics too.  The code form's apply takes the reader's table by value behind the arguments (apply_codes; V == 4 only).
+// statistics too.  The code forms' apply takes the reader's table by value behind the arguments (apply_codes; V == 4 only); the
+// residual-and-codes form has the residual form's backward.
 using BnKernel = void (*)(BnArgs);
 using BnCodeKernel = void (*)(BnArgs, EncArgs);
 struct BnKernels { BnKernel stats, apply, reduce, dx; BnCodeKernel apply_codes; };
@@ -616,6 +626,11 @@ template <int V> static BnKernels bn_kernels(BnForm form) {
                 return {k_bn_stats<V>, nullptr, k_bn_bwd_reduce<V, false, true>, k_bn_bwd_dx<V, false, false, true>, k_bn_apply_codes};
             else
                 return {};   // no such kernels: bn_forward / bn_backward refuse a form without them
+        case kBnResCodes:
+            if constexpr (V == 4)
+                return {k_bn_stats<V>, nullptr, k_bn_bwd_reduce<V>, k_bn_bwd_dx<V, false, true>, k_bn_apply_res_codes};
+            else
+                return {};
         case kBnTable: return {k_bn_stats<V>, k_bn_apply<V, true>, k_bn_bwd_reduce<V, true>, k_bn_bwd_dx<V, true>, nullptr};
         case kBnRes: return {k_bn_stats<V>, k_bn_apply<V, false, true>, k_bn_bwd_reduce<V>, k_bn_bwd_dx<V, false, true>, nullptr};
         default: return {k_bn_stats<V>, k_bn_apply<V>, k_bn_bwd_reduce<V>, k_bn_bwd_dx<V>, nullptr};
@@ -640,19 +655,21 @@ static int bn_launched(const char* fn, const char* pass) {
 }
 
 // The forward of every form.  `a` holds the entry point's pointers (x, out, gamma, beta, res, table; gmean = save_lo in the
-// table and code forms; codes and code_fmt in the code form); `aliased` is the entry point's own aliasing refusal, or null; `y_ka`
-// is the code form's reader scale.
+// table and code forms; codes and code_fmt in the two code forms); `aliased` is the entry point's own aliasing refusal, or null;
+// `y_ka` is the code forms' reader scale.
 static int bn_forward(const char* fn, BnForm form, BnArgs a, float* running_mean, float* running_var, float momentum, float eps,
                       int relu, float* save_mean, float* save_invstd, const BnCall& g, const char* aliased, float y_ka = 0.f,
                       int y_qbits = 0) {
     a.mean = save_mean; a.invstd = save_invstd;
-    const bool codes = form == kBnCodes, has_lo = form == kBnTable || codes;
+    const bool res = form == kBnRes || form == kBnResCodes, codes = form == kBnCodes || form == kBnResCodes;
+    const bool has_lo = form == kBnTable || form == kBnCodes;
     const void* big[] = {a.x, a.out, a.res};
     const void* small[] = {a.gamma, a.beta, save_mean, save_invstd, a.gmean};
     const EncArgs* const enc = codes ? bn_codes_table(g.c, y_ka, y_qbits) : nullptr;   // fetched once: checked here, launched below
-    const BnCodeCheck cc = {enc != nullptr, true, a.codes};
+    const BnCodeCheck cc = {enc != nullptr, true, a.codes,
+                            form == kBnResCodes ? "slfp_bn_res_codes_train_supported" : "slfp_bn_codes_train_supported"};
     int64_t m = 0;
-    const int rc = bn_check(fn, g.n, g.h, g.w, g.c, g.x_layout, relu, big, form == kBnRes ? 3 : (codes ? 1 : 2), small, has_lo ? 5 : 4,
+    const int rc = bn_check(fn, g.n, g.h, g.w, g.c, g.x_layout, relu, big, res ? 3 : (codes ? 1 : 2), small, has_lo ? 5 : 4,
                             g.workspace, g.ws_bytes, &m, form == kBnTable, a.table, codes ? &cc : nullptr);
     if (rc != SLFP_OK) return rc;
     if ((running_mean == nullptr) != (running_var == nullptr))
@@ -688,7 +705,7 @@ static int bn_backward(const char* fn, BnForm form, BnArgs a, int relu, float* g
     const void* big[] = {a.x, a.y, a.gy, a.out};
     const void* small[] = {a.gamma, a.mean, a.invstd, a.beta, a.lo_fwd};
     const bool codes = form == kBnCodes;
-    const BnCodeCheck cc = {g.c % 4 == 0, false, nullptr};
+    const BnCodeCheck cc = {g.c % 4 == 0, false, nullptr, "slfp_bn_codes_train_supported"};
     int64_t m = 0;
     const int rc = bn_check(fn, g.n, g.h, g.w, g.c, g.x_layout, relu, big, 4, small, form == kBnTable || codes ? 5 : 3, g.workspace,
                             g.ws_bytes, &m, form == kBnTable, a.table, codes ? &cc : nullptr);
@@ -831,6 +848,25 @@ int slfp_bn_codes_train_bwd(const float* x, const float* gy, const float* gamma,
     a.lo_fwd = save_lo;
     return bn_backward("slfp_bn_codes_train_bwd", kBnCodes, a, relu, ggamma, gbeta, {n, h, w, c, x_layout, workspace, ws_bytes, stream},
                        nullptr, gx == x ? "gx may not alias x" : nullptr);
+}
+
+int slfp_bn_res_codes_train_supported(int64_t n, int64_t h, int64_t w, int64_t c, int x_layout, float y_ka, int y_qbits) {
+    return bn_supported(n, h, w, c, x_layout) && bn_codes_table(c, y_ka, y_qbits) ? 1 : 0;
+}
+
+int slfp_bn_res_codes_train_fwd(const float* x, const float* res, const float* gamma, const float* beta, float* running_mean,
+                                float* running_var, float momentum, float eps, int relu, float y_ka, int y_qbits, float* y,
+                                uint8_t* y_codes, float* save_mean, float* save_invstd, int64_t n, int64_t h, int64_t w, int64_t c,
+                                int x_layout, void* workspace, size_t ws_bytes, void* stream) {
+    BnArgs a = {};
+    a.x = x; a.res = res; a.out = y; a.codes = y_codes; a.code_fmt = bn_code_fmt(y_qbits); a.gamma = gamma; a.beta = beta;
+    const char* aliased = nullptr;
+    if (y == x || y == res) aliased = "y may alias neither x nor res (the backward reads x and y)";
+    const void* const others[] = {x, res, y, gamma, beta, running_mean, running_var, save_mean, save_invstd, workspace};
+    for (const void* o : others)
+        if (o == reinterpret_cast<const void*>(y_codes)) aliased = "y_codes may alias no other operand";
+    return bn_forward("slfp_bn_res_codes_train_fwd", kBnResCodes, a, running_mean, running_var, momentum, eps, relu, save_mean,
+                      save_invstd, {n, h, w, c, x_layout, workspace, ws_bytes, stream}, aliased, y_ka, y_qbits);
 }
 
 }  // extern "C"

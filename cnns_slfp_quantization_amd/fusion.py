@@ -44,6 +44,11 @@ undo function restores exactly that state; "also undone by" = the other undo fun
   link_codes_train(model)          -- (a TRAINING pass; before or     [BN, ReLU, Conv2d_Q]: the BN slot ->          unlink_codes_train
                                    after use_device_bn_train)         TrainBatchNormCodes2d, a stock ReLU ->
                                                                       FoldedReLU (_codes_train)
+  use_device_bottleneck_train      -- (a TRAINING pass)               block: instance forward, _bn_bottleneck;      restore_bottleneck_train /
+    (model, x)                                                        bn1..3 -> TrainBatchNorm2d                    restore_bn_train
+  link_bottleneck_codes_train      use_device_bottleneck_train        block: instance forward, _bn_bottleneck_codes; unlink_bottleneck_codes_train /
+    (model, x)                                                        bn1 / bn2 -> TrainBatchNormCodes2d            restore_bottleneck_train,
+                                                                      (_in_bottleneck); bn3 wrapper: _trunk         restore_bn_train
 
 The passes that take an example input share one forward trace (`_Trace`), one rule for "the same tensor" (`_Trace.same`), one
 eligibility predicate (`_code_eligible`), one record of wrapped children (`_wrap_children` / `_unwrap_children`) and one
@@ -2013,14 +2018,39 @@ class TrainBatchNorm2d(_DeviceBatchNorm):
     A block's forward may ask more of one call (use_device_bottleneck_train): forward(x, relu=True) applies a ReLU the module does
     not own, forward(x, residual=identity, relu=True) the tail of a Bottleneck on slfp_bn_res_train_fwd / _bwd (DESIGN section 33);
     where the kernels do not run, that call computes F.batch_norm, `+= residual`, relu with ATen as the stock block does.
-      _last_kernel   "bn_train[+relu]", "bn_res_train[+relu]", or "aten" """
+    After link_bottleneck_codes_train has told the wrapper the Conv2d_Q layers that read its tail (`_trunk`), a residual call that
+    passes _trunk_codes_ok runs slfp_bn_res_codes_train_fwd instead: the same float32 tensor, carrying the readers' 1-byte codes
+    as the tensor attribute `_train_trunk_codes` = (codes, Ka, q_bit); every other call runs what it ran.
+      _last_kernel   "bn_train[+relu]", "bn_res_train[+relu]", "bn_res_codes_train[+relu]", or "aten" """
 
     def __init__(self, bn, min_elements=None):
         super().__init__(bn, min_elements)
         self._relu = False
+        # link_bottleneck_codes_train: (the Conv2d_Q readers of this tail's output, float32(Ka), q_bit, min_elements) -- a tuple, so
+        # that the readers are no children of this module
+        self._trunk = None
 
     def extra_repr(self):
-        return f"{self.num_features}, eps={self.eps}, momentum={self.momentum}, relu={self._relu}"
+        trunk = "" if self._trunk is None else f", trunk codes for Ka={self._trunk[1]}, q_bit={self._trunk[2]}"
+        return f"{self.num_features}, eps={self.eps}, momentum={self.momentum}, relu={self._relu}{trunk}"
+
+    def _trunk_codes_ok(self, x):
+        """Does this call write the readers' codes next to the float32 trunk?  The size rule and
+        slfp_bn_res_codes_train_supported; options.backward "hip" / "hip_all"; every recorded reader still in training mode on this
+        device with the Ka and q_bit the link was made for, nothing fused onto it, a code-reading float32-output forward and a
+        backward kernel that reads its codes."""
+        from . import batchnorm as B
+        from .conv2d_func import _bwd_codes_supported, _bwd_flags, _f32, _plan
+        readers, ka, q_bit, floor = self._trunk
+        if _bwd_flags() is None or not B.bn_res_codes_train_supported(x, ka, q_bit, floor):
+            return False
+        for conv in readers:
+            if not (conv.training and conv.q_bit == q_bit and _f32(conv.Ka) == ka and _link_conv_clean(conv)
+                    and conv.weight.device == x.device):
+                return False
+            if not (_plan(conv, x, conv.weight, True, True, ("codes", True, None, None)).ok and _bwd_codes_supported(conv, x.shape)):
+                return False
+        return True
 
     def forward(self, x, *, relu=None, residual=None):
         """relu: None -- the module's own folded ReLU (`_relu`); True / False -- what a block's forward asks of this call
@@ -2035,6 +2065,17 @@ class TrainBatchNorm2d(_DeviceBatchNorm):
             floor = MIN_ELEMENTS if residual is None else RES_MIN_ELEMENTS
         fits = residual is None or (torch.is_tensor(residual) and residual.shape == x.shape and residual.dtype == x.dtype
                                     and residual.device == x.device)
+        if residual is not None and fits and self._trunk is not None:
+            # the trunk's readers are known (link_bottleneck_codes_train): under the size rule of that link, the same float32 tensor
+            # and, riding on it as `_train_trunk_codes`, (codes, Ka, q_bit) for them (Conv2d_Q.forward)
+            cops = self._kernel_operands(x, 0)
+            if cops is not None and self._trunk_codes_ok(x):
+                from .batchnorm import hip_bn_res_codes_train
+                _, ka, q_bit, _ = self._trunk
+                self._last_kernel = "bn_res_codes_train+relu" if relu else "bn_res_codes_train"
+                y, codes = hip_bn_res_codes_train.apply(x, residual, *cops, self.momentum, self.eps, relu, ka, q_bit)
+                y._train_trunk_codes = (codes, ka, q_bit)
+                return y
         ops = self._kernel_operands(x, floor) if fits else None
         if ops is not None:
             if residual is not None:
@@ -2146,7 +2187,9 @@ def _repoint_bn(wrap):
 
 
 def _restore_bn_bottleneck(blk):
-    """Take the instance-level forward off `blk` and put back the stock module wherever this pass created the wrapper."""
+    """Take the instance-level forward off `blk` and put back the stock module wherever this pass created the wrapper.  Links of
+    link_bottleneck_codes_train are undone first: they stand in the wrappers' slots."""
+    _unlink_bottleneck_codes(blk)
     created = blk.__dict__.pop("_bn_bottleneck")
     del blk.__dict__["forward"]
     for name, wrap in created.items():
@@ -2450,23 +2493,152 @@ def link_codes_train(model, min_elements=None):
     return done
 
 
+def _held_bn(wrap):
+    """What stood in a TrainBatchNormCodes2d's slot, pointed at the wrapper's current parameters, buffers and training flag."""
+    held = wrap._held[0]
+    stock = _repoint_bn(wrap)
+    if held is not stock:   # a TrainBatchNorm2d: the same Parameter and buffer objects again
+        for key in ("weight", "bias"):
+            held._parameters[key] = wrap._parameters[key]
+        for key in _BN_NAMES:
+            held._buffers[key] = wrap._buffers[key]
+        held.training = wrap.training
+    return held
+
+
 def unlink_codes_train(model):
     """Undo link_codes_train: every slot gets back what it held (the stock modules, or use_device_bn_train's wrappers), pointed at
-    the current parameters, buffers and training flag.  Returns the number of links undone."""
+    the current parameters, buffers and training flag.  The in-block links of link_bottleneck_codes_train are not this pass's and
+    stay (unlink_bottleneck_codes_train).  Returns the number of links undone."""
     n = 0
     for parent in list(model.modules()):
         for name, child in list(parent._modules.items()):
-            if isinstance(child, TrainBatchNormCodes2d):
-                held = child._held[0]
-                stock = _repoint_bn(child)
-                if held is not stock:   # a TrainBatchNorm2d: the same Parameter and buffer objects again
-                    for key in ("weight", "bias"):
-                        held._parameters[key] = child._parameters[key]
-                    for key in _BN_NAMES:
-                        held._buffers[key] = child._buffers[key]
-                    held.training = child.training
-                parent._modules[name] = held
+            if isinstance(child, TrainBatchNormCodes2d) and not child.__dict__.get("_in_bottleneck"):
+                parent._modules[name] = _held_bn(child)
                 n += 1
             elif isinstance(child, FoldedReLU) and getattr(child, "_codes_train", False):
                 parent._modules[name] = child.relu
     return n
+
+
+# ------------------------------------------------------------------ training-mode Bottlenecks on 1-byte codes: in-block links and the trunk
+def _bn_tail(bn, t):
+    """relu(bn(t)) of a rewritten Bottleneck: a link's wrapper owns its ReLU, a TrainBatchNorm2d is asked for it."""
+    return bn(t) if isinstance(bn, TrainBatchNormCodes2d) else bn(t, relu=True)
+
+
+def _bn_bottleneck_codes_forward(self, x):
+    """_bn_bottleneck_forward for a block with in-block links: a linked bn1 / bn2 hands its uint8 codes straight to conv2 / conv3.
+    It asks the module in the slot, so a slot that got its TrainBatchNorm2d back runs what _bn_bottleneck_forward runs."""
+    out = _bn_tail(self.bn1, self.conv1(x))
+    out = _bn_tail(self.bn2, self.conv2(out))
+    identity = x if getattr(self, "downsample", None) is None else self.downsample(x)
+    return self.bn3(self.conv3(out), residual=identity, relu=True)
+
+
+def _unlink_bottleneck_codes(blk):
+    """Undo what link_bottleneck_codes_train did to `blk`; returns (in-block links, trunk links) undone."""
+    import types
+    rec = blk.__dict__.pop("_bn_bottleneck_codes", None)
+    if rec is None:
+        return 0, 0
+    n = 0
+    for name, wrap in rec["in_block"].items():
+        if blk._modules.get(name) is wrap:
+            blk._modules[name] = _held_bn(wrap)
+            n += 1
+    t = 0
+    bn3 = rec["trunk"]
+    if bn3 is not None and bn3._trunk is not None:
+        bn3._trunk = None
+        t = 1
+    if blk.__dict__.get("forward") is not None and getattr(blk.__dict__["forward"], "__func__", None) is _bn_bottleneck_codes_forward:
+        blk.__dict__["forward"] = types.MethodType(_bn_bottleneck_forward, blk)
+    return n, t
+
+
+def link_bottleneck_codes_train(model, example_input, min_elements=None, *, in_block=True, trunk=True):
+    """Put the hand-overs of the training Bottlenecks of `model` on 1-byte codes.  It works on the blocks
+    use_device_bottleneck_train has rewritten (those carrying `_bn_bottleneck`); with none it returns (0, 0) and touches nothing.
+    In-block links: relu(bn1(.)) -> conv2 and relu(bn2(.)) -> conv3, where the slot holds a TrainBatchNorm2d without a folded ReLU
+    and the conv is a Conv2d_Q with q_bit 8 or 7, no raw bias and nothing fused onto it (_link_conv_clean).  The slot gets a
+    TrainBatchNormCodes2d made for that conv -- section 35's wrapper, with its per-call decision and fallback -- and the block an
+    instance-level forward that hands the uint8 tensor straight on.
+    Trunk links: one traced eval-mode forward on `example_input` (_Trace, as link_trunk uses it) finds for each rewritten block the
+    Conv2d_Q layers whose input IS its output: the next block's conv1, and downsample.0 at a stage boundary.  A link needs at least
+    one reader, every reader run exactly once and clean (_link_conv_clean), and all of them sharing (float32(Ka), q_bit): one code
+    tensor serves them.  The block's bn3 wrapper records the readers (`_trunk`); the readers themselves are not modified.  In a
+    training step the tail then runs slfp_bn_res_codes_train_fwd, and each reader its code-reading forward and slfp_conv2d_bwd_codes
+    (Conv2d_Q.forward; batchnorm.hip_trunk_codes_conv_train), call by call and only where TrainBatchNorm2d._trunk_codes_ok holds.
+    Never linked on the trunk: the stem's output into the first block (no rewritten block made it), a last block read only by the
+    pool, a boundary whose conv1 and downsample.0 differ in Ka; each costs exactly its own link.  The float32 trunk is still
+    written and saved (the ReLU's mask, the next add): a trunk link saves traffic at the readers, not memory.
+    min_elements: tensors of fewer elements stay float32 (None: batchnorm.CODES_MIN_ELEMENTS for in-block links and
+    batchnorm.RES_CODES_MIN_ELEMENTS for trunk links, either of which may be None = never; 0: every size).  in_block / trunk: make
+    only one kind of link (the measurement of section 38 times them apart).  Opt-in, never a default.
+    Parameters, buffers, state-dict keys and optimizer bindings do not change; the training flags are put back.  Returns
+    (in_block_links, trunk_links); unlink_bottleneck_codes_train undoes exactly these, restore_bottleneck_train and
+    restore_bn_train take them along."""
+    import types
+    from .conv2d_func import _f32
+    blocks = [m for m in model.modules() if "_bn_bottleneck" in m.__dict__ and "_bn_bottleneck_codes" not in m.__dict__]
+    if not blocks:
+        return 0, 0
+    flags = [(m, m.training) for m in model.modules()]
+    model.eval()
+    try:
+        tr = _Trace(model, example_input, blocks=blocks)
+        readers_of = {}
+        for blk in blocks if trunk else ():
+            io = tr.io(blk)
+            bn3 = blk._modules.get("bn3")
+            if io is None or not isinstance(bn3, TrainBatchNorm2d) or bn3._relu or bn3._trunk is not None or tr.runs(bn3) != 1:
+                continue
+            want = io[1]
+            if want.dim() != 4 or want.dtype != torch.float32:
+                continue
+            readers = [c.mod for c in tr.readers(want) if _is_conv_q(c.mod)]
+            if not readers or any(tr.runs(b) != 1 or not _link_conv_clean(b) for b in readers):
+                continue
+            if len({(_f32(b.Ka), int(b.q_bit)) for b in readers}) != 1:
+                continue   # one code tensor serves every reader
+            readers_of[blk] = tuple(readers)
+        tr.release()
+    finally:
+        for m, t in flags:
+            m.training = t
+    n_in = n_trunk = 0
+    for blk in blocks:
+        rec = {"in_block": {}, "trunk": None}
+        for bn_name, conv_name in (("bn1", "conv2"), ("bn2", "conv3")) if in_block else ():
+            bn, conv = blk._modules.get(bn_name), blk._modules.get(conv_name)
+            if (isinstance(bn, TrainBatchNorm2d) and not bn._relu and bn._trunk is None and bn.momentum is not None
+                    and _is_conv_q(conv) and _link_conv_clean(conv)
+                    and len(_slots_of(model, bn)) == 1 and len(_slots_of(model, conv)) == 1):
+                wrap = TrainBatchNormCodes2d(bn, None, conv, min_elements)
+                wrap.__dict__["_in_bottleneck"] = True
+                rec["in_block"][bn_name] = blk._modules[bn_name] = wrap
+        if blk in readers_of:
+            bn3 = blk._modules["bn3"]
+            ka, q_bit = _f32(readers_of[blk][0].Ka), int(readers_of[blk][0].q_bit)
+            bn3._trunk = (readers_of[blk], ka, q_bit, min_elements)
+            rec["trunk"] = bn3
+        if not rec["in_block"] and rec["trunk"] is None:
+            continue
+        blk.__dict__["_bn_bottleneck_codes"] = rec
+        if rec["in_block"]:
+            blk.__dict__["forward"] = types.MethodType(_bn_bottleneck_codes_forward, blk)
+        n_in += len(rec["in_block"])
+        n_trunk += rec["trunk"] is not None
+    return n_in, n_trunk
+
+
+def unlink_bottleneck_codes_train(model):
+    """Undo link_bottleneck_codes_train: the linked slots get their TrainBatchNorm2d back (pointed at the current parameters,
+    buffers and training flag), the bn3 wrappers forget their readers, the blocks get use_device_bottleneck_train's forward back.
+    Returns (in_block_links, trunk_links) undone."""
+    n = t = 0
+    for blk in list(model.modules()):
+        a, b = _unlink_bottleneck_codes(blk)
+        n, t = n + a, t + b
+    return n, t

@@ -740,6 +740,34 @@ int slfp_bn_codes_train_bwd(const float* x, const float* gy, const float* gamma,
                             int64_t n, int64_t h, int64_t w, int64_t c, int x_layout,
                             void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- training-mode BatchNorm2d + residual add (+ReLU) that writes the trunk AND its readers' codes (csrc/bn_train.hip, the
+ * residual-and-codes form) ------------------------------------------------------------------------------------------------------
+ * The trunk of a ResNet leaves a Bottleneck as relu(bn3(.) + identity) and is read by the next block's conv1 (and downsample.0 at a
+ * stage boundary), whose first act is quantize_act(y / Ka), and by the next block's add, which needs float32.  So the forward of
+ * slfp_bn_res_train_fwd stores, next to the float32 y, one byte per element: the extended code of the readers' quantizer (y_ka
+ * their Ka, y_qbits their q_bit, 8 or 7).  The training twin of slfp_conv2d_fwd_res_codes.  The contract is exact:
+ *   statistics save_mean, save_invstd and the running statistics are exactly those of slfp_bn_train_fwd on the same x.
+ *   forward    y is slfp_bn_res_train_fwd's, bit for bit: t = the apply with relu = 0;  z = t + res, rounded on its own;  relu:
+ *              y = z < 0 ? 0 : z.  y_codes[i] = the byte slfp_encode_f32(y, y_ka, fmt(y_qbits) | SLFP_FMT_EXT) gives element i,
+ *              through the readers' threshold table, a lane's four channels as one dword.  A NaN in y takes code 0x00: the trunk's
+ *              readers see the tiny class, the float32 trunk itself (and so the next add) still carries the NaN.  The apply pass
+ *              reads x and res once and writes y and y_codes once: 4 + 4 + 4 + 1 = 13 B per element against 12 B (17 B against
+ *              16 B with the statistics pass).
+ *   backward   slfp_bn_res_train_bwd, as it is: it reads x and y.
+ * No atomics; two calls give the same bits.  Supported (slfp_bn_res_codes_train_supported: 1 / 0, host only): the set of
+ * slfp_bn_train_supported, and in addition c % 4 == 0, y_qbits 8 or 7, y_ka > 0 with a proven code table; everything else is
+ * SLFP_ERR_UNSUPPORTED.  The workspace is that of slfp_bn_train_workspace_bytes.  The refusals of slfp_bn_res_train_fwd come
+ * first, in its order, then those of slfp_bn_codes_train_fwd (y_codes NULL: SLFP_ERR_BAD_ARG; not 4-byte aligned:
+ * SLFP_ERR_ALIGNMENT); y may alias neither x nor res, and y_codes may alias no other operand (x, res, y, the per-channel arrays,
+ * the running statistics, the workspace): SLFP_ERR_BAD_ARG.  Every refusal is made before any device work and leaves y, y_codes,
+ * the saves and the running statistics untouched.  n == 0 returns SLFP_OK. */
+int slfp_bn_res_codes_train_supported(int64_t n, int64_t h, int64_t w, int64_t c, int x_layout, float y_ka, int y_qbits);
+int slfp_bn_res_codes_train_fwd(const float* x, const float* res, const float* gamma, const float* beta, float* running_mean,
+                                float* running_var, float momentum, float eps, int relu, float y_ka, int y_qbits,
+                                float* y, uint8_t* y_codes, float* save_mean, float* save_invstd,
+                                int64_t n, int64_t h, int64_t w, int64_t c, int x_layout,
+                                void* workspace, size_t ws_bytes, void* stream);
+
 /* ---- self-check ------------------------------------------------------------------------
  * The kernels compute x / scale_div with an FMA correction chain on a host-computed
  * reciprocal instead of the IEEE division macro (csrc/slfp_device.hpp, ScaleDiv).  This
