@@ -51,6 +51,7 @@ SYMBOLS = (
     "slfp_bn_codes_train_supported", "slfp_bn_codes_train_fwd", "slfp_bn_codes_train_bwd",
     "slfp_conv2d_bwd_codes_supported", "slfp_conv2d_bwd_codes",
     "slfp_bn_res_codes_train_supported", "slfp_bn_res_codes_train_fwd",
+    "slfp_debug_bwd_instance",
 )
 
 
@@ -203,6 +204,7 @@ def load():
         "slfp_conv2d_codes_x3_supported": (ci, [dp, ctypes.POINTER(ConvIo), ci, ci]),
         "slfp_conv2d_fwd_codes_x3": (ci, [dp, ctypes.POINTER(ConvIo), vp, vp, vp, vp, vp, ci, vp, vp]),
         "slfp_debug_pwc_x3_variant": (ctypes.c_char_p, [dp, ctypes.POINTER(ConvIo)]),
+        "slfp_debug_bwd_instance": (ctypes.c_char_p, [dp, ctypes.c_uint, ci, ci, ci]),
     }
     assert set(sigs) == set(SYMBOLS)
     for name, (res, args) in sigs.items():

@@ -28,6 +28,7 @@
 #include "slfp_enc.hpp"
 #include "slfp_codes.hpp"
 #include "slfp_host.hpp"
+#include <cstdio>
 #include <type_traits>
 
 namespace slfp {
@@ -760,6 +761,10 @@ struct GwSplit {
     int splits, kps;
 };
 
+// Whole float4 groups of channels on both sides: what the VEC instances need of the shape (the pointers' 16-byte alignment is
+// checked at the entry points).
+static bool chan_vec(const slfp_conv2d_desc& d) { return d.c_in % 4 == 0 && d.c_out % 4 == 0; }
+
 static GwSplit gw_split(int64_t M, int64_t cout, int64_t ncol, int64_t tiles) {
     int64_t sp = ceil_div(8 * kBwdCUs, tiles);
     sp = std::min<int64_t>(sp, std::max<int64_t>(1, M / 256));
@@ -774,6 +779,7 @@ struct PwShape {
     int64_t M;       // rows = N*H*W
     int tm_x, tn_x;  // GX tiling
     int tm_w, tn_w;  // GW tiling
+    bool vec;        // float4 loads (chan_vec)
     int splits, kps; // GW split of M (gw_split)
 };
 
@@ -783,6 +789,7 @@ static PwShape pw_shape(const slfp_conv2d_desc& d) {
     const int64_t cin = d.c_in, cout = d.c_out;
     s.tm_x = s.M >= 128 ? 2 : 1;  s.tn_x = cin >= 128 ? 2 : 1;
     s.tm_w = cout >= 128 ? 2 : 1; s.tn_w = cin >= 128 ? 2 : 1;
+    s.vec = chan_vec(d);
     const GwSplit sp = gw_split(s.M, cout, cin, ceil_div(cout, 64 * s.tm_w) * ceil_div(cin, 64 * s.tn_w));
     s.splits = sp.splits; s.kps = sp.kps;
     return s;
@@ -793,6 +800,7 @@ struct DenseShape {
     int64_t ncol;    // gw GEMM columns = taps * C_in
     int tn_x;        // GX tiling (TM = 2)
     int tm_w, tn_w;  // GW tiling
+    bool vec;        // float4 loads (chan_vec); the scalar instances are tn_x = 1 and tm_w = tn_w = 1
     int splits, kps; // GW split of M (gw_split)
 };
 
@@ -801,9 +809,9 @@ static DenseShape dense_shape(const slfp_conv2d_desc& d, const ConvPlan& p) {
     s.M = d.n * p.h_out * p.w_out;
     s.ncol = (int64_t)d.kh * d.kw * d.c_in;
     const int64_t cout = d.c_out;
-    const bool vec = d.c_in % 4 == 0 && cout % 4 == 0;   // the scalar-gather instantiations exist at 64 x 64 only
-    s.tn_x = vec && d.c_in >= 128 ? 2 : 1;
-    s.tm_w = vec && cout >= 128 ? 2 : 1; s.tn_w = vec && s.ncol >= 128 ? 2 : 1;
+    s.vec = chan_vec(d);   // the scalar-gather instantiations exist at 64 x 64 only
+    s.tn_x = s.vec && d.c_in >= 128 ? 2 : 1;
+    s.tm_w = s.vec && cout >= 128 ? 2 : 1; s.tn_w = s.vec && s.ncol >= 128 ? 2 : 1;
     const GwSplit sp = gw_split(s.M, cout, s.ncol, ceil_div(cout, 64 * s.tm_w) * ceil_div(s.ncol, 64 * s.tn_w));
     s.splits = sp.splits; s.kps = sp.kps;
     return s;
@@ -865,13 +873,22 @@ static const EncArgs kNone{};   // the table argument of a kernel that uses none
 
 // The activation encode: the threshold table where act_table has one, else the long form of the format; the decode of the
 // format's codes where x arrives as codes.
+enum ActForm { kActTab = 0, kActLong = 1, kActCodes = 2 };
+static ActForm act_form(const EncArgs* tab, bool x_codes) { return x_codes ? kActCodes : (tab ? kActTab : kActLong); }
+
 template <class F>
 static void with_act_enc(const EncArgs* tab, int fmt_act, bool x_codes, F fn) {
-    if (x_codes && fmt_act == kFmtAct8) fn(Int<kCodes8>{}, kNone);
-    else if (x_codes) fn(Int<kCodes7>{}, kNone);
-    else if (tab) fn(Int<kEncTabQ>{}, *tab);
-    else if (fmt_act == kFmtAct8) fn(Int<kFmtAct8>{}, kNone);
-    else fn(Int<kFmtSfp7>{}, kNone);
+    const bool a8 = fmt_act == kFmtAct8;
+    switch (act_form(tab, x_codes)) {
+        case kActCodes:
+            if (a8) fn(Int<kCodes8>{}, kNone);
+            else fn(Int<kCodes7>{}, kNone);
+            break;
+        case kActTab: fn(Int<kEncTabQ>{}, *tab); break;
+        default:
+            if (a8) fn(Int<kFmtAct8>{}, kNone);
+            else fn(Int<kFmtSfp7>{}, kNone);
+    }
 }
 
 template <class F>
@@ -904,14 +921,14 @@ static void launch_dense_gx(const DenseGeom& g, int tn, bool vec, hipStream_t st
 }
 
 template <int AF>
-static void launch_dense_gw(const DenseGeom& g, const DenseShape& s, bool vec, hipStream_t st, const float* gy, const float* x,
+static void launch_dense_gw(const DenseGeom& g, const DenseShape& s, hipStream_t st, const float* gy, const float* x,
                             float* part, float* gbp, const EncArgs& t, const ScaleDiv& sd) {
     const dim3 grid((unsigned)ceil_div(g.Cout, 64 * s.tm_w), (unsigned)ceil_div(s.ncol, 64 * s.tn_w), (unsigned)s.splits);
     auto go = [&](auto TM, auto TN, auto VEC) {
         hipLaunchKernelGGL((k_dense_gw<decltype(TM)::value, decltype(TN)::value, AF, decltype(VEC)::value>), grid, dim3(256), 0, st,
                            gy, x, part, gbp, g, s.M, s.kps, t, sd);
     };
-    if (!vec) go(Int<1>{}, Int<1>{}, std::false_type{});   // the scalar gather exists at 64 x 64 only (dense_shape)
+    if (!s.vec) go(Int<1>{}, Int<1>{}, std::false_type{});   // the scalar gather exists at 64 x 64 only (dense_shape)
     else with_1_or_2(s.tm_w, [&](auto TM) { with_1_or_2(s.tn_w, [&](auto TN) { go(TM, TN, std::true_type{}); }); });
 }
 
@@ -994,20 +1011,19 @@ static int run_bwd(const slfp_conv2d_desc* d, unsigned flags, const float* x, co
         const DenseGeom g = dense_geom(*d, p);
         const int T = g.KH * g.KW;
         // every operand is 16-byte aligned (checked at the entry point; workspace offsets are multiples of 256)
-        const bool vec = (Cin % 4) == 0 && (Cout % 4) == 0;
         if (need_gx) {
             float* wt = reinterpret_cast<float*>(ws + L.wt);
             const int64_t nw = Cout * Cin * T;
             hipLaunchKernelGGL(k_oihw_to_tap, dim3((unsigned)ceil_div(nw, 256)), dim3(256), 0, st, wq, wt, (int)Cout, (int)Cin, T);
             if ((rc = check_launch("slfp dense backward weight re-layout kernel")) != SLFP_OK) return rc;
-            launch_dense_gx(g, s.tn_x, vec, st, gy_n, wt, gx_n, d->kw_scale);
+            launch_dense_gx(g, s.tn_x, s.vec, st, gy_n, wt, gx_n, d->kw_scale);
             if ((rc = check_launch("slfp dense backward (gx) kernel")) != SLFP_OK) return rc;
         }
         if (need_gw) {
             float* part = reinterpret_cast<float*>(ws + L.part);
             float* gbp = need_gb ? reinterpret_cast<float*>(ws + L.gbpart) : nullptr;
             with_act_enc(tab, p.fmt_act, x_codes, [&](auto AF, const EncArgs& t) {
-                launch_dense_gw<decltype(AF)::value>(g, s, vec, st, gy_n, x_n, part, gbp, t, sd);
+                launch_dense_gw<decltype(AF)::value>(g, s, st, gy_n, x_n, part, gbp, t, sd);
             });
             if ((rc = check_launch("slfp dense backward (gw) kernel")) != SLFP_OK) return rc;
             if ((rc = reduce_parts(st, part, s.splits, Cout * s.ncol, d->ka, 0, (int)Cin, T, gw, nullptr)) != SLFP_OK) return rc;
@@ -1015,7 +1031,7 @@ static int run_bwd(const slfp_conv2d_desc* d, unsigned flags, const float* x, co
         }
     } else {
         const PwShape s = pw_shape(*d);
-        const bool vec = (Cin % 4) == 0 && (Cout % 4) == 0 && aligned16(gy_n) && (!need_gw || x_codes || aligned16(x_n)) &&
+        const bool vec = s.vec && aligned16(gy_n) && (!need_gw || x_codes || aligned16(x_n)) &&
                          (!need_gx || aligned16(wq));   // (codes are read a dword at a time whatever vec says)
         if (need_gx) {
             GemmArgs a{gy_n, wq, gx_n, nullptr, (int)s.M, (int)Cin, (int)Cout, Cout, Cin, Cin, (int)Cout, d->kw_scale};
@@ -1069,6 +1085,38 @@ size_t slfp_conv2d_bwd_workspace_bytes_ex(const slfp_conv2d_desc* d, unsigned fl
     const BwdKind kind = bwd_kind_ex(*d, p, flags);
     if (kind == kBwdNone) return 0;
     return bwd_layout(*d, p, kind, need_gx != 0, need_gw != 0).total;
+}
+
+const char* slfp_debug_bwd_instance(const slfp_conv2d_desc* d, unsigned flags, int x_codes, int need_gx, int need_gw) {
+    static thread_local char buf[192];
+    ConvPlan p;
+    if (!d || (flags & ~SLFP_BWD_DENSE) || make_plan(d, &p) != SLFP_OK) return "composite";
+    const BwdKind kind = bwd_kind_ex(*d, p, flags);
+    if (kind == kBwdNone || (x_codes && !codes_ok(*d))) return "composite";
+    if (!need_gx && !need_gw) return "none";
+    static const char* const kForm[] = {"tab", "long", "codes"};
+    char enc[16];
+    std::snprintf(enc, sizeof enc, "%s/%s", kForm[act_form(act_table(d->ka, p.fmt_act, kEncF32), x_codes != 0)],
+                  p.fmt_act == kFmtAct8 ? "act8" : "sfp7");
+    auto v = [](bool vec) { return vec ? "v4" : "v1"; };
+    int n = 0;
+    if (kind == kBwdDw) {
+        std::snprintf(buf, sizeof buf, "dw/s%d/%s/b%d", (int)d->stride_h == 2 ? 2 : 1, enc, dw_blocks(dw_geom(*d, p)));
+        return buf;
+    }
+    if (kind == kBwdDense) {
+        const DenseShape s = dense_shape(*d, p);
+        if (need_gx) n += std::snprintf(buf + n, sizeof buf - n, "dense/gx/tn%d/%s", s.tn_x, v(s.vec));
+        if (need_gw)
+            std::snprintf(buf + n, sizeof buf - n, "%sdense/gw/tm%dtn%d/%s/%s/p%dk%d", n ? "+" : "", s.tm_w, s.tn_w, v(s.vec), enc, s.splits,
+                          s.kps);   // (!vec: dense_shape keeps tm_w = tn_w = 1, the one scalar instance launch_dense_gw has)
+        return buf;
+    }
+    const PwShape s = pw_shape(*d);
+    if (need_gx) n += std::snprintf(buf + n, sizeof buf - n, "pw/gx/tm%dtn%d/%s", s.tm_x, s.tn_x, v(s.vec));
+    if (need_gw)
+        std::snprintf(buf + n, sizeof buf - n, "%spw/gw/tm%dtn%d/%s/%s/p%dk%d", n ? "+" : "", s.tm_w, s.tn_w, v(s.vec), enc, s.splits, s.kps);
+    return buf;
 }
 
 int slfp_conv2d_bwd_ex(const slfp_conv2d_desc* d, unsigned flags, const float* x, const float* w_oihw, const float* gy,

@@ -852,6 +852,25 @@ int slfp_conv2d_bwd_codes_supported(const slfp_conv2d_desc* d, unsigned flags);
 int slfp_conv2d_bwd_codes(const slfp_conv2d_desc* d, unsigned flags, const uint8_t* x_codes, const float* w_oihw,
                           const float* gy, float* gx, float* gw_oihw, float* gb, void* workspace, void* stream);
 
+/* Which kernel instances of csrc/conv_bwd.hip slfp_conv2d_bwd_ex (x_codes == 0) or slfp_conv2d_bwd_codes (x_codes == 1) launches
+ * for this descriptor and these flags under the switches read at load, when gx (need_gx) and / or gw with gb (need_gw) are asked
+ * for.  One word per template argument a launcher chooses, then the runtime split the launch is sized by:
+ *   dw/s<1|2>/<tab|long|codes>/<act8|sfp7>/b<blocks>                                 k_dw3x3_bwd<S, AF>: one kernel gives gx, gw and gb
+ *   pw/gx/tm<1|2>tn<1|2>/<v4|v1>                                                     k_gemm_f32<TM, TN, false, kNoEnc, VEC>
+ *   pw/gw/tm<1|2>tn<1|2>/<v4|v1>/<tab|long|codes>/<act8|sfp7>/p<splits>k<kps>        k_gemm_f32<TM, TN, true, AF, VEC>
+ *   dense/gx/tn<1|2>/<v4|v1>                                                         k_dense_gx<TN, VEC>
+ *   dense/gw/tm<1|2>tn<1|2>/<v4|v1>/<tab|long|codes>/<act8|sfp7>/p<splits>k<kps>     k_dense_gw<TM, TN, AF, VEC>
+ * tab / long / codes: x is encoded on load through the threshold table or the long form, or arrives as codes and is decoded; the
+ * format word names the long form's or the codes' template argument and, with `tab`, the table's contents (one instance serves
+ * both formats).  v4 / v1: float4 or scalar loads (both channel counts multiples of 4, or not).  b: workgroups along x of the
+ * depthwise kernel, which walk the image units grid-stride; p, k: the splits of the gw contraction over its rows and the rows per
+ * split, p also being the partials k_reduce_parts sums (the pointwise family writes gw directly when p == 1).  With need_gx and
+ * need_gw both set the pointwise and dense families give "<gx string>+<gw string>".  "composite" where the entry point refuses
+ * (a null descriptor, unknown flag bits, an unsupported layer, codes that are not NHWC with C_in % 4 == 0); "none" when nothing is
+ * asked for.  Printed from the selection the launch consumes (bwd_kind_ex, pw_shape, dense_shape, dw_geom / dw_blocks, act_form).
+ * Host only: no device is touched.  The pointer stays valid until the next call on the same thread. */
+const char* slfp_debug_bwd_instance(const slfp_conv2d_desc* d, unsigned flags, int x_codes, int need_gx, int need_gw);
+
 /* ---- layout helpers (the reference is NCHW; the kernels are NHWC) -------------------- */
 int slfp_nchw_to_nhwc_f32(const float* x, float* y, int64_t n, int64_t c, int64_t h, int64_t w, void* stream);
 int slfp_nhwc_to_nchw_f32(const float* x, float* y, int64_t n, int64_t c, int64_t h, int64_t w, void* stream);

@@ -308,13 +308,47 @@ def test_finetune_bottleneck_every_step_matches_composite():
 
 
 # ---- 9. every instantiation, on both encodes ------------------------------------------------------------------------------
-# The smallest shape that selects each (TM, TN, VEC) of k_gemm_f32, k_dense_gx and k_dense_gw (pw_shape / dense_shape in
-# csrc/conv_bwd.hip): 128 channels or rows pick the 128-wide tile, 6 -> 10 the scalar loads.
+# The smallest shape that selects each (TM, TN) of the gw kernels and each TN of the gx kernels with float4 loads, and the scalar
+# loads once per family (pw_shape / dense_shape in csrc/conv_bwd.hip): 128 channels or rows pick the 128-wide tile, 6 -> 10 the
+# scalar loads.  INSTANCES says what slfp_debug_bwd_instance must report for each (n = 2, NHWC, the threshold table; split numbers
+# stripped); the instances these shapes leave out (k_gemm_f32's gx at tm1tn2, its scalar forms beyond tm1tn1, the code operands)
+# have their rows in tests/_bwd_variants.py.
 INSTANTIATIONS = (
     [("hip", _spec(ci, co, 1, 1, 0, 8)) for ci, co in ((64, 64), (128, 64), (64, 128), (128, 128))]   # M = 128: tm_x = 2
     + [("hip", _spec(64, 64, 1, 1, 0, 4)),                                                            # M = 32: tm_x = 1
        ("hip", _spec(6, 10, 1, 1, 0, 8))]
     + [("hip_all", _spec(ci, co, 3, 1, 1, 6, 5)) for ci, co in ((8, 8), (16, 16), (8, 128), (16, 128), (128, 8), (6, 10))])
+
+
+INSTANCES = (
+    [f"pw/gx/tm2tn{tn}/v4+pw/gw/tm{tm}tn{tn}/v4/tab/act8" for tm, tn in ((1, 1), (1, 2), (2, 1), (2, 2))]
+    + ["pw/gx/tm1tn1/v4+pw/gw/tm1tn1/v4/tab/act8", "pw/gx/tm2tn1/v1+pw/gw/tm1tn1/v1/tab/act8"]
+    + [f"dense/gx/tn1/v4+dense/gw/tm{tm}tn{tn}/v4/tab/act8" for tm, tn in ((1, 1), (1, 2), (2, 1), (2, 2))]
+    + ["dense/gx/tn2/v4+dense/gw/tm1tn2/v4/tab/act8", "dense/gx/tn1/v1+dense/gw/tm1tn1/v1/tab/act8"])
+
+
+def test_instantiations_select_what_they_claim():
+    """INSTANTIATIONS reaches the instances INSTANCES names, by the reporter that prints from the launch's own selection: a threshold
+    moved in pw_shape or dense_shape fails here instead of leaving an instance unrun."""
+    import ctypes
+    import re
+    L = _lib.load()
+    os.environ.pop("SLFP_LONG_ENCODE", None)
+    L.slfp_debug_reload_switches()
+    got = []
+    for mode, s in INSTANTIATIONS:
+        d = _lib.ConvDesc(n=2, c_in=s.c_in, h=s.h, w=s.w, c_out=s.c_out, kh=s.k[0], kw=s.k[1], stride_h=s.stride[0], stride_w=s.stride[1],
+                          pad_h=s.pad[0], pad_w=s.pad[1], dil_h=1, dil_w=1, groups=1, x_layout=_lib.LAYOUT_NHWC, y_layout=_lib.LAYOUT_NHWC,
+                          qbits=8, ka=cf._f32(s.Ka), kw_scale=cf._f32(s.Kw), mfma_passes=0, reserved=0)
+        said = L.slfp_debug_bwd_instance(ctypes.byref(d), _lib.BWD_DENSE if mode == "hip_all" else 0, 0, 1, 1).decode()
+        got.append(re.sub(r"/p\d+k\d+$", "", said))
+    assert got == INSTANCES
+    parts = {p for g in got for p in g.split("+")}
+    for fam in ("pw", "dense"):   # every float4 (TM, TN) of the gw kernels and the scalar form
+        assert {p for p in parts if p.startswith(fam + "/gw/")} == (
+            {f"{fam}/gw/tm{tm}tn{tn}/v4/tab/act8" for tm in (1, 2) for tn in (1, 2)} | {f"{fam}/gw/tm1tn1/v1/tab/act8"})
+    assert {p for p in parts if p.startswith("dense/gx/")} == {"dense/gx/tn1/v4", "dense/gx/tn2/v4", "dense/gx/tn1/v1"}
+    assert {p for p in parts if p.startswith("pw/gx/")} == {"pw/gx/tm2tn1/v4", "pw/gx/tm2tn2/v4", "pw/gx/tm1tn1/v4", "pw/gx/tm2tn1/v1"}
 
 
 @pytest.mark.parametrize("q", [8, 7])
