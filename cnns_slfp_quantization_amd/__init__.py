@@ -9,6 +9,7 @@ conv2d forward path behind the operator API of happyxtt/CNNs_SLFP_quantization.
     layer_specs.py   Conv2d_Q layer tables of the reference nets (shapes + calibration scales)
     sharding.py      batch-axis sharding + one-time weight broadcast (torch.distributed / RCCL)
     fusion.py        eval-BN + ReLU folded into the conv epilogues
+    fusion_train.py  the training-mode passes: BatchNorm tails on the kernels, hand-overs as 1-byte codes (reached as fusion.<name>)
     calibration.py   device-side max|.| statistics for Ka / Kw
     image_u8.py      uint8 pixels in front of the stems: normalisation as a float32 table (fusion.link_image_u8)
 """

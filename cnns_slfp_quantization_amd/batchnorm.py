@@ -128,23 +128,35 @@ class hip_bn_res_train(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, res, weight, bias, running_mean, running_var, momentum, eps, relu):
-        if res.shape != x.shape or res.dtype != x.dtype or res.device != x.device:
-            raise ValueError("hip_bn_res_train: the residual must have x's shape, dtype and device")
-        x = x.detach()
-        res = _nhwc(res.detach())
-        gamma, beta = _vec(weight), _vec(bias)
-        y, save_mean, save_invstd = _outputs(x, 2)
-        _call("slfp_bn_res_train_fwd", x, x.data_ptr(), res.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(running_mean),
-              _ptr(running_var), float(momentum), float(eps), 1 if relu else 0, y.data_ptr(), save_mean.data_ptr(),
-              save_invstd.data_ptr())
-        ctx.relu = bool(relu)
-        ctx.save_for_backward(x, weight, save_mean, save_invstd, *((y,) if ctx.relu else ()))
-        return y
+        return _bn_res_forward(ctx, "hip_bn_res_train", x, res, weight, bias, running_mean, running_var, momentum, eps, relu)[0]
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
         return _bn_res_backward(ctx, gy) + (None,) * 5
+
+
+def _bn_res_forward(ctx, who, x, res, weight, bias, running_mean, running_var, momentum, eps, relu, quant=None):
+    """The forward of the residual form and, with quant = (ka, q_bit), of the residual-and-codes form: the same call with the
+    quantizer behind `relu` and the code tensor behind y.  Saves what _bn_res_backward reads; returns (y, codes or None)."""
+    if res.shape != x.shape or res.dtype != x.dtype or res.device != x.device:
+        raise ValueError(f"{who}: the residual must have x's shape, dtype and device")
+    x = x.detach()
+    res = _nhwc(res.detach())
+    gamma, beta = _vec(weight), _vec(bias)
+    y, save_mean, save_invstd = _outputs(x, 2)
+    head = (x.data_ptr(), res.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(running_mean), _ptr(running_var), float(momentum),
+            float(eps), 1 if relu else 0)
+    codes = None
+    if quant is None:
+        _call("slfp_bn_res_train_fwd", x, *head, y.data_ptr(), save_mean.data_ptr(), save_invstd.data_ptr())
+    else:
+        codes = torch.empty(x.shape, dtype=torch.uint8, device=x.device, memory_format=torch.channels_last)
+        _call("slfp_bn_res_codes_train_fwd", x, *head, float(quant[0]), int(quant[1]), y.data_ptr(), codes.data_ptr(),
+              save_mean.data_ptr(), save_invstd.data_ptr())
+    ctx.relu = bool(relu)
+    ctx.save_for_backward(x, weight, save_mean, save_invstd, *((y,) if ctx.relu else ()))
+    return y, codes
 
 
 def _bn_res_backward(ctx, gy):
@@ -275,19 +287,27 @@ class TrainLink:
         self.save_mean, self.save_invstd, self.save_lo = saves
         self.relu, self.ka, self.q_bit, self.conv = bool(relu), ka, q_bit, conv
 
-    def made_for(self, conv):
-        """Were the codes written for `conv`'s present quantizer?"""
-        return conv is self.conv and conv.q_bit == self.q_bit and float(np.float32(float(conv.Ka))) == self.ka
+    def made_for(self, conv, codes):
+        """Were `codes` written for `conv`, and does it still read them?  Its own clause is the identity; the rest is the reader
+        check's host-only half: the wrapper that made this record asked the whole check in this same call, library included."""
+        from .conv2d_func import _train_codes_reader_matches
+        return conv is self.conv and _train_codes_reader_matches(conv, codes, self.ka, self.q_bit)
 
 
 def bn_codes_train_supported(x, ka, q_bit, min_elements=None):
     """bn_train_supported under the code form's size rule (None: CODES_MIN_ELEMENTS, which may leave everything out), and
     slfp_bn_codes_train_supported for the reader's quantizer (ka: float32(Ka) as a Python float)."""
-    floor = CODES_MIN_ELEMENTS if min_elements is None else min_elements
+    return _codes_form_supported(x, ka, q_bit, min_elements, CODES_MIN_ELEMENTS, "slfp_bn_codes_train_supported")
+
+
+def _codes_form_supported(x, ka, q_bit, floor, default_floor, query_name):
+    """bn_train_supported under a code form's size rule (floor None: `default_floor`, which may itself be None = never), then the
+    form's own library query for the reader's quantizer."""
+    floor = default_floor if floor is None else floor
     if floor is None or not bn_train_supported(x, floor):
         return False
     n, c, h, w = x.shape
-    return bool(_lib.load().slfp_bn_codes_train_supported(n, h, w, c, _lib.LAYOUT_NHWC, ka, int(q_bit)))
+    return bool(getattr(_lib.load(), query_name)(n, h, w, c, _lib.LAYOUT_NHWC, ka, int(q_bit)))
 
 
 def bn_codes_train_fwd(x, weight, bias, running_mean, running_var, momentum, eps, relu, ka, q_bit):
@@ -303,6 +323,17 @@ def bn_codes_train_fwd(x, weight, bias, running_mean, running_var, momentum, eps
     return (codes, *saves)
 
 
+def _codes_conv_forward(conv, codes, weight, bias, who):
+    """Conv2d_Q `conv`'s code-reading forward on training codes, with freshly prepared weights (never the cache): the one
+    plan-check-launch of both Functions below and of Conv2d_Q's own call where nothing records.  No kernel is an error here."""
+    from .conv2d_func import _launch, _train_codes_plan
+    plan = _train_codes_plan(conv, codes)
+    if not plan.ok:
+        raise RuntimeError(f"{who}: no code-reading forward for this layer (slfp_conv2d_codes_supported); undo the training "
+                           "code links (fusion.unlink_codes_train, fusion.unlink_bottleneck_codes_train)")
+    return _launch(conv, plan, codes, weight, bias, cache=False)
+
+
 class hip_bn_codes_conv_train(torch.autograd.Function):
     """conv(relu?(batch_norm(x))) for a pair linked by fusion.link_codes_train, as ONE Function: autograd cannot carry a gradient
     through the uint8 tensor between the two, and the float32 gradient between their backward kernels is a temporary.  The inputs
@@ -313,11 +344,7 @@ class hip_bn_codes_conv_train(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, bn_weight, bn_bias, weight, bias, conv, codes, link):
-        from .conv2d_func import _launch, _plan
-        plan = _plan(conv, codes, weight, True, True, ("codes", True, None, None))
-        if not plan.ok:
-            raise RuntimeError("hip_bn_codes_conv_train: no code-reading forward for this layer (slfp_conv2d_codes_supported)")
-        y = _launch(conv, plan, codes, weight, bias, cache=False)
+        y = _codes_conv_forward(conv, codes, weight, bias, "hip_bn_codes_conv_train")
         ctx.conv, ctx.relu, ctx.has_bias = conv, link.relu, bias is not None
         ctx.save_for_backward(x, codes, bn_weight, bn_bias, link.save_mean, link.save_invstd, link.save_lo, weight)
         return y
@@ -362,11 +389,7 @@ RES_CODES_MIN_ELEMENTS = 98 << 20
 def bn_res_codes_train_supported(x, ka, q_bit, min_elements=None):
     """bn_train_supported under the residual-and-codes form's size rule (None: RES_CODES_MIN_ELEMENTS, which may leave everything
     out), and slfp_bn_res_codes_train_supported for the readers' quantizer (ka: float32(Ka) as a Python float)."""
-    floor = RES_CODES_MIN_ELEMENTS if min_elements is None else min_elements
-    if floor is None or not bn_train_supported(x, floor):
-        return False
-    n, c, h, w = x.shape
-    return bool(_lib.load().slfp_bn_res_codes_train_supported(n, h, w, c, _lib.LAYOUT_NHWC, ka, int(q_bit)))
+    return _codes_form_supported(x, ka, q_bit, min_elements, RES_CODES_MIN_ELEMENTS, "slfp_bn_res_codes_train_supported")
 
 
 class hip_bn_res_codes_train(torch.autograd.Function):
@@ -377,19 +400,9 @@ class hip_bn_res_codes_train(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, res, weight, bias, running_mean, running_var, momentum, eps, relu, ka, q_bit):
-        if res.shape != x.shape or res.dtype != x.dtype or res.device != x.device:
-            raise ValueError("hip_bn_res_codes_train: the residual must have x's shape, dtype and device")
-        x = x.detach()
-        res = _nhwc(res.detach())
-        gamma, beta = _vec(weight), _vec(bias)
-        y, save_mean, save_invstd = _outputs(x, 2)
-        codes = torch.empty(x.shape, dtype=torch.uint8, device=x.device, memory_format=torch.channels_last)
-        _call("slfp_bn_res_codes_train_fwd", x, x.data_ptr(), res.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(running_mean),
-              _ptr(running_var), float(momentum), float(eps), 1 if relu else 0, float(ka), int(q_bit), y.data_ptr(), codes.data_ptr(),
-              save_mean.data_ptr(), save_invstd.data_ptr())
-        ctx.relu = bool(relu)
+        y, codes = _bn_res_forward(ctx, "hip_bn_res_codes_train", x, res, weight, bias, running_mean, running_var, momentum, eps,
+                                   relu, (ka, q_bit))
         ctx.mark_non_differentiable(codes)
-        ctx.save_for_backward(x, weight, save_mean, save_invstd, *((y,) if ctx.relu else ()))
         return y, codes
 
     @staticmethod
@@ -407,11 +420,7 @@ class hip_trunk_codes_conv_train(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, trunk, weight, bias, conv, codes):
-        from .conv2d_func import _launch, _plan
-        plan = _plan(conv, codes, weight, True, True, ("codes", True, None, None))
-        if not plan.ok:
-            raise RuntimeError("hip_trunk_codes_conv_train: no code-reading forward for this layer (slfp_conv2d_codes_supported)")
-        y = _launch(conv, plan, codes, weight, bias, cache=False)
+        y = _codes_conv_forward(conv, codes, weight, bias, "hip_trunk_codes_conv_train")
         ctx.conv, ctx.has_bias = conv, bias is not None
         ctx.save_for_backward(codes, weight)
         return y

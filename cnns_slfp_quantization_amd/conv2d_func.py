@@ -637,6 +637,33 @@ def _bwd_codes_supported(mod, shape):
     return bool(_lib.load().slfp_conv2d_bwd_codes_supported(ctypes.byref(_conv_desc(mod, shape, True, True)), flags))
 
 
+def _link_conv_clean(conv):
+    """A Conv2d_Q a training link may feed: q_bit 8 or 7, no raw (unscaled) bias, nothing fused or linked onto it."""
+    return (conv.q_bit in (8, 7) and (conv.bias is None or conv._scaled_bias) and conv._post is None and conv._code_out is None
+            and conv._image_table is None)
+
+
+def _train_codes_plan(conv, t):
+    """The plan of `conv`'s code-reading, float32-writing forward on a channels_last tensor of t's shape: what a training link runs."""
+    return _plan(conv, t, conv.weight, True, True, ("codes", True, None, None))
+
+
+def _train_codes_reader_matches(conv, t, ka, q_bit):
+    """The host-only half of _train_codes_reader_ok: `conv` is in training mode, its present quantizer is (ka, q_bit) -- ka as
+    _f32(Ka) --, nothing is fused or linked onto it and its weights are on t's device."""
+    return (conv.training and conv.q_bit == q_bit and _f32(conv.Ka) == ka and _link_conv_clean(conv)
+            and conv.weight.device == t.device)
+
+
+def _train_codes_reader_ok(conv, t, ka, q_bit):
+    """May Conv2d_Q `conv` read training codes of the quantizer (ka, q_bit) in place of the float32 tensor `t` (or: is `t` such a
+    code tensor; shape and device are what is read), forward and backward?  The one answer for every producer and reader of a
+    training link, the library asked last: _train_codes_reader_matches; a code-reading forward under the current
+    options (one cached plan); a backward kernel that reads the codes under options.backward (one query; "composite" has none)."""
+    return (_train_codes_reader_matches(conv, t, ka, q_bit) and _train_codes_plan(conv, t).ok
+            and _bwd_codes_supported(conv, t.shape))
+
+
 def _hip_backward_codes(mod, desc, codes, w, gy, needs):
     """_hip_backward with the activation operand as the 1-byte codes the layer read in its forward (slfp_conv2d_bwd_codes; NHWC):
     (gx, gw, gb) for needs = (gx, gw, gb wanted).  The caller has asked _bwd_codes_supported: a layer without the kernel is an
@@ -846,49 +873,25 @@ def _conv_class(q_bit, Kw, Ka, bias_default, scaled_bias):
             self.output = out
             return out
 
-        def _forward_train_link(self, codes, link):
-            from .batchnorm import hip_bn_codes_conv_train
-            del codes.__dict__["_train_link"]   # a finished step must not keep the BN's input alive through a stash
+        def _forward_train_codes(self, fn, front, codes, *back):
+            """This module on the training codes of a link: fn.apply(*front, weight, bias, self, codes, *back) where one of the
+            differentiable inputs (`front`, weight, bias) records, else the bare code-reading forward."""
+            from .batchnorm import _codes_conv_forward
             bias = self.bias if scaled_bias else None
-            need_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad
-                                                        for t in (link.x, link.weight, link.bias, self.weight, bias))
-            if need_grad:
-                out = hip_bn_codes_conv_train.apply(link.x, link.weight, link.bias, self.weight, bias, self, codes, link)
+            if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (*front, self.weight, bias)):
+                out = fn.apply(*front, self.weight, bias, self, codes, *back)
             else:
-                plan = _plan(self, codes, self.weight, True, True, ("codes", True, None, None))
-                if not plan.ok:
-                    raise RuntimeError("Conv2d_Q: no code-reading forward for this layer (slfp_conv2d_codes_supported); "
-                                       "call fusion.unlink_codes_train(model)")
                 with torch.no_grad():
-                    out = _launch(self, plan, codes, self.weight, bias, cache=False)
+                    out = _codes_conv_forward(self, codes, self.weight, bias, "Conv2d_Q")
             self.output = out
             return out
 
         def _reads_train_trunk(self, trunk, ttc):
             """Does this module, in training mode, read the codes `ttc` = (codes, float32(Ka), q_bit) that ride on the float32
-            `trunk` instead of the tensor itself?"""
-            from .fusion import _link_conv_clean
-            codes = ttc[0]
-            if not (self.q_bit in (8, 7) and ttc[1:] == (_f32(self.Ka), self.q_bit) and _link_conv_clean(self)):
-                return False
-            if (trunk.dtype != torch.float32 or codes.shape != trunk.shape or codes.device != self.weight.device
-                    or not codes.is_contiguous(memory_format=torch.channels_last)):
-                return False
-            return (_bwd_codes_supported(self, codes.shape)
-                    and _plan(self, codes, self.weight, True, True, ("codes", True, None, None)).ok)
-
-        def _forward_train_trunk(self, trunk, codes):
-            from .batchnorm import hip_trunk_codes_conv_train
-            bias = self.bias if scaled_bias else None
-            need_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (trunk, self.weight, bias))
-            if need_grad:
-                out = hip_trunk_codes_conv_train.apply(trunk, self.weight, bias, self, codes)
-            else:
-                plan = _plan(self, codes, self.weight, True, True, ("codes", True, None, None))
-                with torch.no_grad():
-                    out = _launch(self, plan, codes, self.weight, bias, cache=False)
-            self.output = out
-            return out
+            `trunk` instead of the tensor itself?  Its own clauses are the code tensor's: the trunk's shape, channels_last."""
+            codes, ka, q_bit = ttc
+            return (trunk.dtype == torch.float32 and codes.shape == trunk.shape
+                    and codes.is_contiguous(memory_format=torch.channels_last) and _train_codes_reader_ok(self, codes, ka, q_bit))
 
         def forward_slice(self, input, out_slice):
             """`out_slice=(buffer, c_off)`: a linked code producer writes its codes into buffer[:, c_off:c_off + C_out] (uint8,
@@ -925,16 +928,19 @@ def _conv_class(q_bit, Kw, Ka, bias_default, scaled_bias):
                 self.output = _hip_conv2d_u8(self, input, self.weight, self.bias if scaled_bias else None, order)
                 return self.output
             link = input.__dict__.get("_train_link") if type(input) is torch.Tensor and input.dtype == torch.uint8 else None
-            if link is not None and self.training and self.q_bit in (8, 7) and link.made_for(self):
-                # the codes a fusion.TrainBatchNormCodes2d wrote for THIS module's present quantizer, in a training step: BN -> ReLU ->
-                # conv as one autograd Function (or the bare code forward where nothing records).  The record leaves the tensor first
-                return self._forward_train_link(input, link)
+            if link is not None and link.made_for(self, input):
+                # the codes a fusion.TrainBatchNormCodes2d wrote for THIS module's present quantizer, in a training step: BN -> ReLU -> conv
+                # as one autograd Function.  The record leaves the tensor first: a finished step must not keep the BN's input alive
+                from .batchnorm import hip_bn_codes_conv_train
+                del input.__dict__["_train_link"]
+                return self._forward_train_codes(hip_bn_codes_conv_train, (link.x, link.weight, link.bias), input, link)
             ttc = input.__dict__.get("_train_trunk_codes") if type(input) is torch.Tensor and self.training else None
             if ttc is not None and self._reads_train_trunk(input, ttc):
                 # the float32 trunk of a Bottleneck linked by fusion.link_bottleneck_codes_train carries the codes its bn3 tail wrote
                 # for THIS module's present quantizer, in a training step: read those (a stale or foreign scale, a module with
                 # something fused onto it or options.backward = "composite" reads the float32 tensor as ever)
-                return self._forward_train_trunk(input, ttc[0])
+                from .batchnorm import hip_trunk_codes_conv_train
+                return self._forward_train_codes(hip_trunk_codes_conv_train, (input,), ttc[0])
             tc = input.__dict__.get("_trunk_codes") if type(input) is torch.Tensor else None
             if tc is not None and not self.training and self.q_bit in (8, 7) and tc[1:] == (float(self.Ka), self.q_bit):
                 # the float32 trunk of a block linked by fusion.link_trunk carries the codes written for THIS module's present

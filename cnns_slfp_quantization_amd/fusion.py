@@ -36,23 +36,15 @@ undo function restores exactly that state; "also undone by" = the other undo fun
                                                                       pools -> CodeMaxPool2d, ReLUs -> CodeReLU,
                                                                       identity avg-pools -> CodePass
   use_device_avgpool(model, x)     --                                 global average pools -> GlobalAvgPool2d,      restore_avgpool
-                                                                      a ReLU in front -> FoldedReLU (pool._relu)
+                                                                      (_relu), a ReLU in front -> FoldedReLU("avgpool")
   link_pool_head(model, x)         use_device_avgpool; before         pool: _code_out, _pool_link; Linear_Q:        unlink_pool_head /
                                    link_head                          _code_in                                      restore_avgpool
-  use_device_bn_train(model)       -- (a TRAINING pass: before or     nn.BatchNorm2d -> TrainBatchNorm2d, a ReLU    restore_bn_train
-                                   after model.train())               behind it -> FoldedReLU (bn._relu)
-  link_codes_train(model)          -- (a TRAINING pass; before or     [BN, ReLU, Conv2d_Q]: the BN slot ->          unlink_codes_train
-                                   after use_device_bn_train)         TrainBatchNormCodes2d, a stock ReLU ->
-                                                                      FoldedReLU (_codes_train)
-  use_device_bottleneck_train      -- (a TRAINING pass)               block: instance forward, _bn_bottleneck;      restore_bottleneck_train /
-    (model, x)                                                        bn1..3 -> TrainBatchNorm2d                    restore_bn_train
-  link_bottleneck_codes_train      use_device_bottleneck_train        block: instance forward, _bn_bottleneck_codes; unlink_bottleneck_codes_train /
-    (model, x)                                                        bn1 / bn2 -> TrainBatchNormCodes2d            restore_bottleneck_train,
-                                                                      (_in_bottleneck); bn3 wrapper: _trunk         restore_bn_train
+  the TRAINING passes              fusion_train.py: its header has their rows; the names imported at the end of this file are re-exported
 
 The passes that take an example input share one forward trace (`_Trace`), one rule for "the same tensor" (`_Trace.same`), one
 eligibility predicate (`_code_eligible`), one record of wrapped children (`_wrap_children` / `_unwrap_children`) and one
-verify-or-roll-back step (`_verified`): DESIGN section 20.
+verify-or-roll-back step (`_verified`): DESIGN section 20.  The undo functions that put modules back share one slot walk
+(`_restore_slots`); a FoldedReLU names the pass that owns it, and only that pass's undo takes it back.
 """
 import collections
 import ctypes
@@ -1691,12 +1683,17 @@ def unlink_head(model):
 
 # ------------------------------------------------------------------ the global average pool in front of the classifier
 class FoldedReLU(nn.Module):
-    """An nn.ReLU in front of a GlobalAvgPool2d that applies it (`_relu`): the identity, in the style of CodeReLU.  The original is
-    kept (`relu`); it has no parameters, the state dict does not change."""
+    """The slot of an nn.ReLU that the wrapper next to it applies: the identity, in the style of CodeReLU.  The original is kept
+    (`relu`); it has no parameters, the state dict does not change.  `owner` names the pass that put it there, whose undo function
+    alone takes it back: "avgpool" (use_device_avgpool: the GlobalAvgPool2d behind it applies the ReLU), "bn_train"
+    (use_device_bn_train: the TrainBatchNorm2d in front of it), "codes_train" (link_codes_train: the TrainBatchNormCodes2d in front)."""
 
-    def __init__(self, relu):
+    def __init__(self, relu, owner):
         super().__init__()
+        if owner not in ("avgpool", "bn_train", "codes_train"):
+            raise ValueError(f"FoldedReLU: owner must be 'avgpool', 'bn_train' or 'codes_train', got {owner!r}")
         self.relu = relu
+        self.owner = owner
 
     def forward(self, x):
         return x
@@ -1776,6 +1773,22 @@ def _slots_of(model, child):
     return [(parent, name) for parent in model.modules() for name, c in parent._modules.items() if c is child]
 
 
+def _restore_slots(model, unwrap, unfold):
+    """The slot walk of the undo functions that put modules back: `unwrap(child)` (wrappers) and `unfold(child)` (placeholders)
+    return the module to put back, or None for a child that is not their pass's.  Returns the number of distinct wrappers replaced."""
+    wrappers = {}   # by identity; holding them keeps an id from being reused within the walk
+    for parent in list(model.modules()):
+        for name, child in list(parent._modules.items()):
+            back = unwrap(child)
+            if back is not None:
+                wrappers[id(child)] = child
+            else:
+                back = unfold(child)
+            if back is not None:
+                parent._modules[name] = back
+    return len(wrappers)
+
+
 def use_device_avgpool(model, example_input):
     """Run the global average pools of `model` on libslfp_hip's kernel: one traced forward on `example_input` finds every module,
     run once, that is an nn.AdaptiveAvgPool2d with output size 1 / (1, 1) or an nn.AvgPool2d whose recorded input is exactly one
@@ -1837,24 +1850,19 @@ def use_device_avgpool(model, example_input):
             parent._modules[name] = wrap
         if relu is not None:
             for parent, name in _slots_of(model, relu):
-                parent._modules[name] = FoldedReLU(relu)
+                parent._modules[name] = FoldedReLU(relu, "avgpool")
         done += 1
     tr.release()
     return done
 
 
 def restore_avgpool(model):
-    """Undo use_device_avgpool (and, first, link_pool_head): every slot gets its original module back."""
+    """Undo use_device_avgpool (and, first, link_pool_head): every slot gets its original module back.  Of the FoldedReLU
+    placeholders only this pass's own (owner "avgpool") are taken; those of the training passes stay with their wrappers.  Returns
+    the number of pools restored."""
     unlink_pool_head(model)
-    n = 0
-    for parent in list(model.modules()):
-        for name, child in list(parent._modules.items()):
-            if isinstance(child, GlobalAvgPool2d):
-                parent._modules[name] = child.mod
-                n += 1
-            elif isinstance(child, FoldedReLU) and not getattr(child, "_bn_train", False):   # (use_device_bn_train's stay)
-                parent._modules[name] = child.relu
-    return n
+    return _restore_slots(model, lambda c: c.mod if isinstance(c, GlobalAvgPool2d) else None,
+                          lambda c: c.relu if isinstance(c, FoldedReLU) and c.owner == "avgpool" else None)
 
 
 def _restore_pool_link(pool):
@@ -1950,695 +1958,10 @@ def unlink_pool_head(model):
     return n
 
 
-# ------------------------------------------------------------------ training-mode BatchNorm2d (+ReLU) on the device kernels
-_BN_NAMES = ("running_mean", "running_var", "num_batches_tracked")
-
-
-class _DeviceBatchNorm(nn.Module):
-    """What TrainBatchNorm2d, TrainBatchNormLayerout2d and TrainBatchNormCodes2d share: the stock nn.BatchNorm2d's attributes and the SAME Parameter and
-    buffer objects under the same names (the stock module itself is kept outside _modules, `_bn`), the num_batches_tracked tick,
-    the rule for when the kernels may run, and the F.batch_norm path on the same buffers for everything else."""
-    _version = 2   # nn.BatchNorm2d's state-dict version (num_batches_tracked)
-
-    def __init__(self, bn, min_elements):
-        super().__init__()
-        object.__setattr__(self, "_bn", bn)
-        self.min_elements = min_elements
-        self.training = bn.training
-        self.num_features, self.eps, self.momentum = bn.num_features, bn.eps, bn.momentum
-        self.affine, self.track_running_stats = bn.affine, bn.track_running_stats
-        self.register_parameter("weight", bn.weight)
-        self.register_parameter("bias", bn.bias)
-        for name in _BN_NAMES:
-            self.register_buffer(name, getattr(bn, name))
-        self._last_kernel = None
-
-    def _begin(self, x):
-        """What every call does first: the stock module's refusal of a non-4-d input, and its num_batches_tracked tick."""
-        if x.dim() != 4:
-            raise ValueError(f"expected 4D input (got {x.dim()}D input)")
-        if self.training and self.track_running_stats and self.num_batches_tracked is not None:
-            self.num_batches_tracked.add_(1)
-
-    def _kernel_operands(self, x, min_elements):
-        """(weight, bias, running_mean, running_var) where the kernels may run this call, else None.  They may in training mode,
-        without autocast, on a ROCm float32 tensor batchnorm.bn_train_supported accepts at this size rule, with these four
-        float32 on its device: the kernels are handed their addresses and read and write float32 there."""
-        from .batchnorm import bn_train_supported
-        if not (self.training and x.is_cuda and x.dtype == torch.float32) or torch.is_autocast_enabled():
-            return None
-        ops = (self.weight, self.bias, self.running_mean, self.running_var)
-        for t in ops:
-            if t is None or t.dtype != torch.float32 or t.device != x.device:
-                return None
-        return ops if bn_train_supported(x, min_elements) else None
-
-    def _aten(self, x):
-        """F.batch_norm as the stock module calls it, on the same parameters and buffers."""
-        self._last_kernel = "aten"
-        stats = self.training or (self.running_mean is None and self.running_var is None)
-        keep = not self.training or self.track_running_stats
-        return torch.nn.functional.batch_norm(x, self.running_mean if keep else None, self.running_var if keep else None,
-                                              self.weight, self.bias, stats, self.momentum, self.eps)
-
-
-class TrainBatchNorm2d(_DeviceBatchNorm):
-    """An affine nn.BatchNorm2d (momentum not None) whose training-mode forward and backward run on libslfp_hip's kernels
-    (slfp_bn_train_fwd / slfp_bn_train_bwd), with the nn.ReLU behind it folded in (`_relu`).  It registers the
-    SAME Parameter and buffer objects under the same names, so state-dict keys do not change and an optimizer built before the swap
-    keeps working; the original module is kept outside _modules (`_bn`).  Deliberately not a subclass of nn.BatchNorm2d: the
-    eval-mode passes (fuse_bn_relu, fuse_named_bn) match by isinstance and so never fold a BN whose ReLU lives inside it.
-    The kernels run in training mode on a ROCm float32 4-d channels_last tensor that slfp_bn_train_supported accepts and that
-    has at least `min_elements` elements (None: batchnorm.MIN_ELEMENTS, below which the stock modules measured no slower), with
-    weight, bias and the running statistics float32 on its device; eval mode, CPU tensors, autocast, other dtypes or layouts,
-    smaller tensors, parameters or buffers of another dtype or device and a module without running-statistics buffers go to
-    F.batch_norm with the same buffers (then relu, if folded), which is what the stock modules compute.  The output is saved
-    for the backward only with a folded ReLU; without one it may be changed in place behind the module (`out += identity`, a
-    shared in-place ReLU), as behind the stock module.
-    A block's forward may ask more of one call (use_device_bottleneck_train): forward(x, relu=True) applies a ReLU the module does
-    not own, forward(x, residual=identity, relu=True) the tail of a Bottleneck on slfp_bn_res_train_fwd / _bwd (DESIGN section 33);
-    where the kernels do not run, that call computes F.batch_norm, `+= residual`, relu with ATen as the stock block does.
-    After link_bottleneck_codes_train has told the wrapper the Conv2d_Q layers that read its tail (`_trunk`), a residual call that
-    passes _trunk_codes_ok runs slfp_bn_res_codes_train_fwd instead: the same float32 tensor, carrying the readers' 1-byte codes
-    as the tensor attribute `_train_trunk_codes` = (codes, Ka, q_bit); every other call runs what it ran.
-      _last_kernel   "bn_train[+relu]", "bn_res_train[+relu]", "bn_res_codes_train[+relu]", or "aten" """
-
-    def __init__(self, bn, min_elements=None):
-        super().__init__(bn, min_elements)
-        self._relu = False
-        # link_bottleneck_codes_train: (the Conv2d_Q readers of this tail's output, float32(Ka), q_bit, min_elements) -- a tuple, so
-        # that the readers are no children of this module
-        self._trunk = None
-
-    def extra_repr(self):
-        trunk = "" if self._trunk is None else f", trunk codes for Ka={self._trunk[1]}, q_bit={self._trunk[2]}"
-        return f"{self.num_features}, eps={self.eps}, momentum={self.momentum}, relu={self._relu}{trunk}"
-
-    def _trunk_codes_ok(self, x):
-        """Does this call write the readers' codes next to the float32 trunk?  The size rule and
-        slfp_bn_res_codes_train_supported; options.backward "hip" / "hip_all"; every recorded reader still in training mode on this
-        device with the Ka and q_bit the link was made for, nothing fused onto it, a code-reading float32-output forward and a
-        backward kernel that reads its codes."""
-        from . import batchnorm as B
-        from .conv2d_func import _bwd_codes_supported, _bwd_flags, _f32, _plan
-        readers, ka, q_bit, floor = self._trunk
-        if _bwd_flags() is None or not B.bn_res_codes_train_supported(x, ka, q_bit, floor):
-            return False
-        for conv in readers:
-            if not (conv.training and conv.q_bit == q_bit and _f32(conv.Ka) == ka and _link_conv_clean(conv)
-                    and conv.weight.device == x.device):
-                return False
-            if not (_plan(conv, x, conv.weight, True, True, ("codes", True, None, None)).ok and _bwd_codes_supported(conv, x.shape)):
-                return False
-        return True
-
-    def forward(self, x, *, relu=None, residual=None):
-        """relu: None -- the module's own folded ReLU (`_relu`); True / False -- what a block's forward asks of this call
-        (use_device_bottleneck_train).  residual: a tensor of x's shape added behind the affine map and in front of the ReLU, the
-        `out += identity` of a Bottleneck; on the kernels it is slfp_bn_res_train_fwd / _bwd, under a size
-        rule of its own (batchnorm.RES_MIN_ELEMENTS where min_elements is None)."""
-        from .batchnorm import hip_bn_train, hip_bn_res_train, MIN_ELEMENTS, RES_MIN_ELEMENTS
-        self._begin(x)
-        relu = self._relu if relu is None else bool(relu)
-        floor = self.min_elements
-        if floor is None:
-            floor = MIN_ELEMENTS if residual is None else RES_MIN_ELEMENTS
-        fits = residual is None or (torch.is_tensor(residual) and residual.shape == x.shape and residual.dtype == x.dtype
-                                    and residual.device == x.device)
-        if residual is not None and fits and self._trunk is not None:
-            # the trunk's readers are known (link_bottleneck_codes_train): under the size rule of that link, the same float32 tensor
-            # and, riding on it as `_train_trunk_codes`, (codes, Ka, q_bit) for them (Conv2d_Q.forward)
-            cops = self._kernel_operands(x, 0)
-            if cops is not None and self._trunk_codes_ok(x):
-                from .batchnorm import hip_bn_res_codes_train
-                _, ka, q_bit, _ = self._trunk
-                self._last_kernel = "bn_res_codes_train+relu" if relu else "bn_res_codes_train"
-                y, codes = hip_bn_res_codes_train.apply(x, residual, *cops, self.momentum, self.eps, relu, ka, q_bit)
-                y._train_trunk_codes = (codes, ka, q_bit)
-                return y
-        ops = self._kernel_operands(x, floor) if fits else None
-        if ops is not None:
-            if residual is not None:
-                self._last_kernel = "bn_res_train+relu" if relu else "bn_res_train"
-                return hip_bn_res_train.apply(x, residual, *ops, self.momentum, self.eps, relu)
-            self._last_kernel = "bn_train+relu" if relu else "bn_train"
-            return hip_bn_train.apply(x, *ops, self.momentum, self.eps, relu)
-        y = self._aten(x)
-        if residual is not None:
-            y += residual   # the stock block's own statements: out = bn3(out); out += identity; out = relu(out)
-        return torch.relu(y) if relu else y
-
-
-def _bn_train_candidate(m):
-    return type(m) is nn.BatchNorm2d and m.affine and m.momentum is not None
-
-
-def use_device_bn_train(model, min_elements=None):
-    """Run the training-mode BatchNorm2d modules of `model` on libslfp_hip's kernels: every affine nn.BatchNorm2d with a momentum
-    gets a TrainBatchNorm2d in its slot(s).  Where the module behind it in the same nn.Sequential is a plain nn.ReLU (in place or
-    not) and both are held in exactly one slot, the ReLU is folded into the kernels (`_relu`; its slot becomes FoldedReLU).  A
-    hand-wired BN (ResNet-50's bn1..3, whose ReLU module is shared) is swapped without a ReLU, and a layerout_quantize_func
-    between BN and ReLU keeps the ReLU out.  Opt-in; eval mode and everything the kernels do not take run what the stock
-    modules run, and so do tensors of fewer than `min_elements` elements (None: batchnorm.MIN_ELEMENTS, the measured rule of
-    DESIGN section 27; 0: every size).  Returns the number of modules swapped; restore_bn_train undoes them."""
-    todo = [(m, _slots_of(model, m)) for m in model.modules() if _bn_train_candidate(m)]
-    done = 0
-    for bn, slots in todo:
-        if not slots:   # `model` itself
-            continue
-        relu = None
-        if len(slots) == 1 and isinstance(slots[0][0], nn.Sequential):
-            kids = list(slots[0][0]._modules.values())
-            i = next(k for k, kid in enumerate(kids) if kid is bn)
-            if i + 1 < len(kids) and type(kids[i + 1]) is nn.ReLU and len(_slots_of(model, kids[i + 1])) == 1:
-                relu = kids[i + 1]
-        wrap = TrainBatchNorm2d(bn, min_elements)
-        wrap._relu = relu is not None
-        for parent, name in slots:
-            parent._modules[name] = wrap
-        if relu is not None:
-            folded = FoldedReLU(relu)
-            folded._bn_train = True
-            for parent, name in _slots_of(model, relu):
-                parent._modules[name] = folded
-        done += 1
-    return done
-
-
-def restore_bn_train(model):
-    """Undo use_device_bn_train: every slot gets its original module back; the originals are pointed at the current parameters
-    and buffers (the model may have been moved or cast in between) and take the wrapper's training flag.  Blocks rewritten by
-    use_device_bottleneck_train are restored first (restore_bottleneck_train): their instance-level forward calls bn1..3 with
-    keywords a stock BatchNorm does not take.  Links of link_codes_train are undone first too (unlink_codes_train): a wrapper of
-    theirs would hand the restored nn.ReLU a uint8 tensor."""
-    restore_bottleneck_train(model)
-    unlink_codes_train(model)
-    n = 0
-    seen = set()
-    for parent in list(model.modules()):
-        for name, child in list(parent._modules.items()):
-            if isinstance(child, TrainBatchNorm2d):
-                if id(child) not in seen:
-                    seen.add(id(child))
-                    n += 1
-                parent._modules[name] = _repoint_bn(child)
-            elif isinstance(child, FoldedReLU) and getattr(child, "_bn_train", False):
-                parent._modules[name] = child.relu
-    return n
-
-
-# ------------------------------------------------------------------ training-mode Bottleneck tails: BN + ReLU, BN + add + ReLU
-_BN_BOTTLENECK_BNS = ("bn1", "bn2", "bn3")
-
-
-def _bn_bottleneck_forward(self, x):
-    """The dataflow of the Bottleneck the reference copies (nets_imgnet/resnet50.py:71-90) with each ReLU, and the add in front of
-    the last one, handed to the TrainBatchNorm2d in front of it."""
-    out = self.bn1(self.conv1(x), relu=True)
-    out = self.bn2(self.conv2(out), relu=True)
-    identity = x if getattr(self, "downsample", None) is None else self.downsample(x)
-    return self.bn3(self.conv3(out), residual=identity, relu=True)
-
-
-def _bn_wrappable(m):
-    """A BatchNorm a later pass may take: the stock module use_device_bn_train takes, or its wrapper without a folded ReLU."""
-    return _bn_train_candidate(m) or (isinstance(m, TrainBatchNorm2d) and not m._relu)
-
-
-def _bn_bottleneck_candidate(blk):
-    if isinstance(blk, nn.Sequential) or "forward" in blk.__dict__:
-        return False
-    ch = blk._modules
-    if any(ch.get(k) is None for k in _BOTTLENECK_CHILDREN + ("bn3",)) or "downsample" not in ch and not hasattr(blk, "downsample"):
-        return False
-    return type(ch["relu"]) is nn.ReLU and all(_bn_wrappable(ch[k]) for k in _BN_BOTTLENECK_BNS)
-
-
-def _repoint_bn(wrap):
-    """The stock module of a TrainBatchNorm2d or TrainBatchNormLayerout2d, pointed at the wrapper's current parameters, buffers and
-    training flag (a move or a cast since the swap replaced them on the wrapper alone: its stock module sits outside _modules)."""
-    bn = wrap._bn
-    for key in ("weight", "bias"):
-        bn._parameters[key] = wrap._parameters[key]
-    for key in _BN_NAMES:
-        bn._buffers[key] = wrap._buffers[key]
-    bn.training = wrap.training
-    return bn
-
-
-def _restore_bn_bottleneck(blk):
-    """Take the instance-level forward off `blk` and put back the stock module wherever this pass created the wrapper.  Links of
-    link_bottleneck_codes_train are undone first: they stand in the wrappers' slots."""
-    _unlink_bottleneck_codes(blk)
-    created = blk.__dict__.pop("_bn_bottleneck")
-    del blk.__dict__["forward"]
-    for name, wrap in created.items():
-        if blk._modules.get(name) is wrap:
-            blk._modules[name] = _repoint_bn(wrap)
-
-
-def use_device_bottleneck_train(model, example_input, min_elements=None):
-    """Run the three tails of every training-mode Bottleneck of `model` on libslfp_hip's kernels: relu(bn1(.)) and relu(bn2(.)) as
-    slfp_bn_train_fwd / _bwd with the ReLU folded, and out = bn3(out); out += identity; out = relu(out) as slfp_bn_res_train_fwd /
-    _bwd.  A candidate is a non-Sequential module without an instance-level forward that has the children
-    conv1 / bn1 / conv2 / bn2 / conv3 / bn3 / relu and a `downsample` attribute (None allowed), bn1..3 each an affine
-    nn.BatchNorm2d with a momentum held in that one slot, or a TrainBatchNorm2d without a folded ReLU, and relu a plain nn.ReLU;
-    the convolutions may be any module and are not touched.  It gets TrainBatchNorm2d wrappers in the three slots (wrappers that
-    are there already are reused) and an instance-level forward with the block's dataflow.  A name is only a convention, so -- the
-    rule of fuse_residual -- the pass verifies: it puts the model in eval mode (there every BatchNorm is F.batch_norm with the
-    running statistics and nothing is updated, so the rewritten dataflow must equal the stock one exactly), traces one no_grad
-    forward on `example_input`, and each rewritten block must reproduce its recorded output bit for bit on its recorded input
-    (otherwise it is restored and not counted); then the rewritten model must reproduce the recorded output bit for bit
-    (otherwise everything is restored and 0 is returned).  The training flags are put back in every case.  Parameters, buffers
-    and state-dict keys do not change.  Composes with use_device_bn_train in either order (a BatchNorm inside `downsample` is that
-    pass's).  Tensors of fewer than `min_elements` elements run what the stock block runs (None: batchnorm.MIN_ELEMENTS for
-    bn1 / bn2, batchnorm.RES_MIN_ELEMENTS for bn3; 0: every size).  Returns the number of blocks rewritten;
-    restore_bottleneck_train undoes them."""
-    import types
-    cands = [m for m in model.modules() if _bn_bottleneck_candidate(m)
-             and all(isinstance(m._modules[k], TrainBatchNorm2d) or len(_slots_of(model, m._modules[k])) == 1
-                     for k in _BN_BOTTLENECK_BNS)]
-    if not cands:
-        return 0
-    flags = [(m, m.training) for m in model.modules()]
-    made = []
-    model.eval()
-    try:
-        tr = _Trace(model, example_input, blocks=cands)
-        y0 = tr.output
-        done = []
-        for blk in cands:
-            io = tr.io(blk)
-            if io is None:
-                continue   # not run, run twice, or not a tensor -> tensor block
-            x, want = io
-            created = {}
-            for name in _BN_BOTTLENECK_BNS:
-                bn = blk._modules[name]
-                if not isinstance(bn, TrainBatchNorm2d):
-                    created[name] = blk._modules[name] = TrainBatchNorm2d(bn, min_elements)
-            made += created.values()
-            blk.__dict__["_bn_bottleneck"] = created
-            blk.__dict__["forward"] = types.MethodType(_bn_bottleneck_forward, blk)
-            if _verified(lambda: blk(x), want, lambda: _restore_bn_bottleneck(blk)):
-                done.append(blk)
-        tr.release()
-        if not done:
-            return 0
-
-        def undo():
-            for blk in done:
-                _restore_bn_bottleneck(blk)
-
-        return len(done) if _verified(lambda: model(example_input), y0, undo) else 0
-    finally:
-        for m, t in flags:
-            m.training = t
-        for wrap in made:   # created in eval mode: the stock module's flag is the slot's
-            wrap.training = wrap._bn.training
-
-
-def restore_bottleneck_train(model):
-    """Undo use_device_bottleneck_train: the blocks lose their instance-level forward and exactly the wrappers that pass created
-    give their slots back to the stock modules (pointed at the current parameters and buffers); wrappers that were there before
-    it stay.  Returns the number of blocks restored."""
-    n = 0
-    for blk in list(model.modules()):
-        if "_bn_bottleneck" in blk.__dict__:
-            _restore_bn_bottleneck(blk)
-            n += 1
-    return n
-
-
-# ------------------------------------------------------------------ training-mode BatchNorm2d -> layer-output quantizer -> activation
-class FoldedTail(nn.Module):
-    """The slot of a layerout_quantize_func or of an activation module that a TrainBatchNormLayerout2d in front of it applies:
-    the identity, in the style of FoldedReLU.  The original is kept outside _modules (`mod`); it has no parameters, the state
-    dict does not change."""
-
-    def __init__(self, mod):
-        super().__init__()
-        object.__setattr__(self, "mod", mod)
-        self.training = mod.training
-
-    def extra_repr(self):
-        return type(self.mod).__name__
-
-    def forward(self, x):
-        return x
-
-
-class TrainBatchNormLayerout2d(_DeviceBatchNorm):
-    """The tail [BatchNorm2d, layerout_quantize_func(q_bit 7 or 8), activation(s)] of a training block of MobileNetV1_swish /
-    VGG16_gelu on libslfp_hip's kernels (slfp_bn_lut_train_fwd / slfp_bn_lut_train_bwd): behind the quantizer a
-    value is one of a few thousand classes, so the activation and its derivative are two float32 tables
-    (batchnorm.layerout_act_tables, built by the stock modules themselves, lazily per device).  As TrainBatchNorm2d it registers
-    the SAME Parameter and buffer objects under the same names and keeps the original modules outside _modules (`_bn`,
-    `_layerout`, `_acts`); it is not an nn.BatchNorm2d subclass.  The kernels run in training mode on a ROCm float32 4-d
-    channels_last tensor that slfp_bn_train_supported accepts and that has at least `min_elements` elements (None:
-    batchnorm.LUT_MIN_ELEMENTS, the measured rule), with weight, bias and the running statistics float32 on its device.  Eval mode, CPU tensors, autocast, other dtypes or layouts and smaller tensors
-    run F.batch_norm on the same buffers, then the kept quantizer module, then the kept activation modules: bit for bit what the
-    stock modules compute.  The output is never saved for the backward; it may be changed in place behind the module.
-      _last_kernel   "bn_lut_train", or "aten" """
-
-    def __init__(self, bn, layerout, acts, min_elements=None):
-        from .batchnorm import _lut_act_types
-        if isinstance(bn, TrainBatchNorm2d):
-            if bn._relu:
-                raise ValueError("TrainBatchNormLayerout2d: the TrainBatchNorm2d has a ReLU folded in")
-            bn = _repoint_bn(bn)   # the wrapper holds the current Parameters and buffers
-        acts = tuple(acts)
-        for act in acts:
-            if type(act) not in _lut_act_types():
-                raise TypeError(f"TrainBatchNormLayerout2d: {type(act).__name__} has no derivative table")
-        super().__init__(bn, min_elements)
-        object.__setattr__(self, "_layerout", layerout)
-        object.__setattr__(self, "_acts", acts)
-        self._tables = {}
-
-    def extra_repr(self):
-        return (f"{self.num_features}, eps={self.eps}, momentum={self.momentum}, layerout={self._layerout.q_bit}, "
-                f"acts={[type(a).__name__ for a in self._acts]}")
-
-    def tables(self, device):
-        """(F, D) of batchnorm.layerout_act_tables on `device`, built once per device."""
-        key = str(device)
-        t = self._tables.get(key)
-        if t is None:
-            from .batchnorm import layerout_act_tables
-            t = self._tables[key] = layerout_act_tables(self._acts, device)
-        return t
-
-    def forward(self, x):
-        from .batchnorm import hip_bn_lut_train, LUT_MIN_ELEMENTS
-        self._begin(x)
-        ops = self._kernel_operands(x, LUT_MIN_ELEMENTS if self.min_elements is None else self.min_elements)
-        if ops is not None:
-            self._last_kernel = "bn_lut_train"
-            return hip_bn_lut_train.apply(x, *ops, self.momentum, self.eps, *self.tables(x.device))
-        y = self._aten(x)
-        y = self._layerout(y)
-        for act in self._acts:
-            y = act(y)
-        return y
-
-
-def use_device_bn_layerout_train(model, min_elements=None):
-    """Run the training blocks [BatchNorm2d, layerout_quantize_func, ReLU | Swish | GELU | ...] of `model` on libslfp_hip's table
-    kernels: inside an nn.Sequential, an affine nn.BatchNorm2d with a momentum (or a TrainBatchNorm2d without a folded ReLU, so
-    this pass and use_device_bn_train may run in either order), directly followed by a layerout_quantize_func with q_bit 7 or 8
-    and by one activation module batchnorm.layerout_act_tables accepts, each held in exactly one slot, becomes a
-    TrainBatchNormLayerout2d; the quantizer's and the activation's slots become FoldedTail placeholders.  q_bit == 32 (no
-    quantizer: no table), activation_func.STL, a shared module and a hand-wired block are skipped.  Opt-in; eval mode and everything
-    the kernels do not take run what the stock modules run, and so do tensors of fewer than `min_elements` elements (None:
-    batchnorm.LUT_MIN_ELEMENTS, the measured rule of DESIGN section 32; 0: every size).  Returns the number of blocks taken;
-    restore_bn_layerout_train undoes them."""
-    from .batchnorm import _lut_act_types
-    done = 0
-    for seq in [s for s in model.modules() if isinstance(s, nn.Sequential)]:
-        names = list(seq._modules.keys())
-        for i in range(len(names) - 2):
-            bn, lo, act = (seq._modules[k] for k in names[i:i + 3])
-            if not (_bn_wrappable(bn) and _is_layerout(lo) and type(act) in _lut_act_types()):
-                continue
-            if any(len(_slots_of(model, m)) != 1 for m in (bn, lo, act)):
-                continue
-            seq._modules[names[i]] = TrainBatchNormLayerout2d(bn, lo, (act,), min_elements)
-            seq._modules[names[i + 1]] = FoldedTail(lo)
-            seq._modules[names[i + 2]] = FoldedTail(act)
-            done += 1
-    return done
-
-
-def restore_bn_layerout_train(model):
-    """Undo use_device_bn_layerout_train: every slot gets its original module back (the stock nn.BatchNorm2d, also where a
-    TrainBatchNorm2d stood in the slot); the originals are pointed at the current parameters and buffers (the model may have been
-    moved or cast in between) and take the placeholders' training flags."""
-    n = 0
-    for parent in list(model.modules()):
-        for name, child in list(parent._modules.items()):
-            if isinstance(child, TrainBatchNormLayerout2d):
-                parent._modules[name] = _repoint_bn(child)
-                n += 1
-            elif isinstance(child, FoldedTail):
-                child.mod.training = child.training
-                parent._modules[name] = child.mod
-    return n
-
-
-# ------------------------------------------------------------------ training-mode BatchNorm2d + ReLU -> the next Conv2d_Q on 1-byte codes
-class TrainBatchNormCodes2d(_DeviceBatchNorm):
-    """The BatchNorm2d of a run [BatchNorm2d, ReLU, Conv2d_Q] linked by link_codes_train: in a training step it
-    runs slfp_bn_codes_train_fwd without recording and returns relu(batch_norm(x)) as the uint8 channels_last codes of the
-    Conv2d_Q's own quantizer; the tensor carries a batchnorm.TrainLink (attribute `_train_link`: x with its graph, the operands,
-    the saves), the ReLU slot passes it through and the Conv2d_Q runs BN -> ReLU -> conv as one autograd Function on it
-    (batchnorm.hip_bn_codes_conv_train).  As TrainBatchNorm2d it registers the SAME Parameter and buffer objects under the same
-    names; what stood in the two slots is kept outside _modules (`_held`).
-    The code path is taken per call only where all of this holds: training mode, no autocast, a channels_last float32 ROCm input of
-    at least `min_elements` elements (None: batchnorm.CODES_MIN_ELEMENTS) with float32 parameters and buffers on its device;
-    slfp_bn_codes_train_supported; a code-reading float32-output forward for the conv under the current options;
-    slfp_conv2d_bwd_codes_supported under options.backward "hip" / "hip_all" ("composite" never takes it); and the conv still in
-    training mode with the Ka and q_bit the link was made for, nothing fused onto it.  Otherwise the call does what stood in the
-    slots does -- a TrainBatchNorm2d with its folded ReLU under its own size rule, or F.batch_norm and a ReLU -- and the conv
-    sees float32.
-      _last_kernel   "bn_codes_train+relu", or "bn_train+relu" / "aten" """
-
-    def __init__(self, held_bn, held_relu, conv, min_elements=None):
-        from .conv2d_func import _f32
-        kernels = isinstance(held_bn, TrainBatchNorm2d)
-        super().__init__(_repoint_bn(held_bn) if kernels else held_bn, min_elements)
-        object.__setattr__(self, "_held", (held_bn, held_relu))
-        object.__setattr__(self, "_conv", conv)
-        self._fallback = (kernels, held_bn.min_elements if kernels else None)   # what the slot ran: the kernels (+ size rule) or ATen
-        self._ka, self._q_bit = _f32(conv.Ka), conv.q_bit
-
-    def extra_repr(self):
-        return f"{self.num_features}, eps={self.eps}, momentum={self.momentum}, relu=True, codes for Ka={self._ka}, q_bit={self._q_bit}"
-
-    def _codes_ok(self, x):
-        from . import batchnorm as B
-        from .conv2d_func import _bwd_codes_supported, _f32, _plan
-        conv = self._conv
-        if not (conv.training and conv.q_bit == self._q_bit and _f32(conv.Ka) == self._ka and _link_conv_clean(conv)):
-            return False
-        if conv.weight.device != x.device or not B.bn_codes_train_supported(x, self._ka, self._q_bit, self.min_elements):
-            return False
-        return _plan(conv, x, conv.weight, True, True, ("codes", True, None, None)).ok and _bwd_codes_supported(conv, x.shape)
-
-    def forward(self, x):
-        from . import batchnorm as B
-        self._begin(x)
-        ops = self._kernel_operands(x, 0)
-        if ops is not None and self._codes_ok(x):
-            codes, *saves = B.bn_codes_train_fwd(x, *ops, self.momentum, self.eps, True, self._ka, self._q_bit)
-            codes._train_link = B.TrainLink(x, self.weight, self.bias, saves, True, self._ka, self._q_bit, self._conv)
-            self._last_kernel = "bn_codes_train+relu"
-            return codes
-        kernels, floor = self._fallback
-        ops = self._kernel_operands(x, B.MIN_ELEMENTS if floor is None else floor) if kernels else None
-        if ops is not None:
-            self._last_kernel = "bn_train+relu"
-            return B.hip_bn_train.apply(x, *ops, self.momentum, self.eps, True)
-        return torch.relu(self._aten(x))
-
-
-def _link_conv_clean(conv):
-    """A Conv2d_Q a training link may feed: q_bit 8 or 7, no raw (unscaled) bias, nothing fused or linked onto it."""
-    return (conv.q_bit in (8, 7) and (conv.bias is None or conv._scaled_bias) and conv._post is None and conv._code_out is None
-            and conv._image_table is None)
-
-
-def _flat_slots(seq, model, once=True):
-    """(parent, name, module, once) of the leaves of nested nn.Sequentials, in the order they run.  once: every nested Sequential
-    around the leaf sits in exactly one slot of `model`, so the leaf appears once in this order and has one successor."""
-    for name, m in seq._modules.items():
-        if isinstance(m, nn.Sequential):
-            yield from _flat_slots(m, model, once and len(_slots_of(model, m)) == 1)
-        else:
-            yield seq, name, m, once
-
-
-def link_codes_train(model, min_elements=None):
-    """Hand activations from BatchNorm to the next Conv2d_Q as 1-byte codes in a TRAINING step.  Candidates are
-    runs [BatchNorm2d | TrainBatchNorm2d with a folded ReLU, ReLU | FoldedReLU, Conv2d_Q] in the flattened leaf order of nested
-    nn.Sequentials, so a block's last ReLU meets the next block's first conv (nets_imgnet/mobilenetv1.py:24-41).  ATen is never
-    asked to read a uint8 tensor: each of the three sits in exactly one slot (and so does every nested Sequential around it: a
-    block held twice has two successors), the BN is affine with a momentum, the conv has q_bit 8
-    or 7, no raw bias and nothing fused onto it (_post, _code_out, _image_table).  Hand-wired blocks (Bottleneck, Fire, ShuffleNet
-    units) are left alone.  The BN's slot gets a TrainBatchNormCodes2d, a stock ReLU's slot a FoldedReLU; the conv is not touched
-    (Conv2d_Q.forward recognises the record on its input).  Opt-in: every call decides for itself (TrainBatchNormCodes2d), and
-    tensors of fewer than `min_elements` elements (None: batchnorm.CODES_MIN_ELEMENTS; 0: every size) stay float32.  Composes with
-    use_device_bn_train in either order.  Returns the number of links; unlink_codes_train undoes them."""
-    nested = {c for m in model.modules() if isinstance(m, nn.Sequential) for c in m._modules.values() if isinstance(c, nn.Sequential)}
-    done = 0
-    for seq in [m for m in model.modules() if isinstance(m, nn.Sequential) and m not in nested]:
-        leaves = list(_flat_slots(seq, model))
-        i = 0
-        while i + 2 < len(leaves):
-            (pb, nb, bn, o1), (pr, nr, relu, o2), (_, _, conv, o3) = leaves[i:i + 3]
-            stock = _bn_train_candidate(bn) and type(relu) is nn.ReLU
-            swapped = (isinstance(bn, TrainBatchNorm2d) and bn._relu and bn.momentum is not None and isinstance(relu, FoldedReLU)
-                       and getattr(relu, "_bn_train", False))
-            if not ((stock or swapped) and o1 and o2 and o3 and _is_conv_q(conv) and _link_conv_clean(conv)
-                    and all(len(_slots_of(model, m)) == 1 for m in (bn, relu, conv))):
-                i += 1
-                continue
-            pb._modules[nb] = TrainBatchNormCodes2d(bn, relu, conv, min_elements)
-            if stock:
-                folded = FoldedReLU(relu)
-                folded._codes_train = True
-                pr._modules[nr] = folded
-            done += 1
-            i += 3
-    return done
-
-
-def _held_bn(wrap):
-    """What stood in a TrainBatchNormCodes2d's slot, pointed at the wrapper's current parameters, buffers and training flag."""
-    held = wrap._held[0]
-    stock = _repoint_bn(wrap)
-    if held is not stock:   # a TrainBatchNorm2d: the same Parameter and buffer objects again
-        for key in ("weight", "bias"):
-            held._parameters[key] = wrap._parameters[key]
-        for key in _BN_NAMES:
-            held._buffers[key] = wrap._buffers[key]
-        held.training = wrap.training
-    return held
-
-
-def unlink_codes_train(model):
-    """Undo link_codes_train: every slot gets back what it held (the stock modules, or use_device_bn_train's wrappers), pointed at
-    the current parameters, buffers and training flag.  The in-block links of link_bottleneck_codes_train are not this pass's and
-    stay (unlink_bottleneck_codes_train).  Returns the number of links undone."""
-    n = 0
-    for parent in list(model.modules()):
-        for name, child in list(parent._modules.items()):
-            if isinstance(child, TrainBatchNormCodes2d) and not child.__dict__.get("_in_bottleneck"):
-                parent._modules[name] = _held_bn(child)
-                n += 1
-            elif isinstance(child, FoldedReLU) and getattr(child, "_codes_train", False):
-                parent._modules[name] = child.relu
-    return n
-
-
-# ------------------------------------------------------------------ training-mode Bottlenecks on 1-byte codes: in-block links and the trunk
-def _bn_tail(bn, t):
-    """relu(bn(t)) of a rewritten Bottleneck: a link's wrapper owns its ReLU, a TrainBatchNorm2d is asked for it."""
-    return bn(t) if isinstance(bn, TrainBatchNormCodes2d) else bn(t, relu=True)
-
-
-def _bn_bottleneck_codes_forward(self, x):
-    """_bn_bottleneck_forward for a block with in-block links: a linked bn1 / bn2 hands its uint8 codes straight to conv2 / conv3.
-    It asks the module in the slot, so a slot that got its TrainBatchNorm2d back runs what _bn_bottleneck_forward runs."""
-    out = _bn_tail(self.bn1, self.conv1(x))
-    out = _bn_tail(self.bn2, self.conv2(out))
-    identity = x if getattr(self, "downsample", None) is None else self.downsample(x)
-    return self.bn3(self.conv3(out), residual=identity, relu=True)
-
-
-def _unlink_bottleneck_codes(blk):
-    """Undo what link_bottleneck_codes_train did to `blk`; returns (in-block links, trunk links) undone."""
-    import types
-    rec = blk.__dict__.pop("_bn_bottleneck_codes", None)
-    if rec is None:
-        return 0, 0
-    n = 0
-    for name, wrap in rec["in_block"].items():
-        if blk._modules.get(name) is wrap:
-            blk._modules[name] = _held_bn(wrap)
-            n += 1
-    t = 0
-    bn3 = rec["trunk"]
-    if bn3 is not None and bn3._trunk is not None:
-        bn3._trunk = None
-        t = 1
-    if blk.__dict__.get("forward") is not None and getattr(blk.__dict__["forward"], "__func__", None) is _bn_bottleneck_codes_forward:
-        blk.__dict__["forward"] = types.MethodType(_bn_bottleneck_forward, blk)
-    return n, t
-
-
-def link_bottleneck_codes_train(model, example_input, min_elements=None, *, in_block=True, trunk=True):
-    """Put the hand-overs of the training Bottlenecks of `model` on 1-byte codes.  It works on the blocks
-    use_device_bottleneck_train has rewritten (those carrying `_bn_bottleneck`); with none it returns (0, 0) and touches nothing.
-    In-block links: relu(bn1(.)) -> conv2 and relu(bn2(.)) -> conv3, where the slot holds a TrainBatchNorm2d without a folded ReLU
-    and the conv is a Conv2d_Q with q_bit 8 or 7, no raw bias and nothing fused onto it (_link_conv_clean).  The slot gets a
-    TrainBatchNormCodes2d made for that conv -- section 35's wrapper, with its per-call decision and fallback -- and the block an
-    instance-level forward that hands the uint8 tensor straight on.
-    Trunk links: one traced eval-mode forward on `example_input` (_Trace, as link_trunk uses it) finds for each rewritten block the
-    Conv2d_Q layers whose input IS its output: the next block's conv1, and downsample.0 at a stage boundary.  A link needs at least
-    one reader, every reader run exactly once and clean (_link_conv_clean), and all of them sharing (float32(Ka), q_bit): one code
-    tensor serves them.  The block's bn3 wrapper records the readers (`_trunk`); the readers themselves are not modified.  In a
-    training step the tail then runs slfp_bn_res_codes_train_fwd, and each reader its code-reading forward and slfp_conv2d_bwd_codes
-    (Conv2d_Q.forward; batchnorm.hip_trunk_codes_conv_train), call by call and only where TrainBatchNorm2d._trunk_codes_ok holds.
-    Never linked on the trunk: the stem's output into the first block (no rewritten block made it), a last block read only by the
-    pool, a boundary whose conv1 and downsample.0 differ in Ka; each costs exactly its own link.  The float32 trunk is still
-    written and saved (the ReLU's mask, the next add): a trunk link saves traffic at the readers, not memory.
-    min_elements: tensors of fewer elements stay float32 (None: batchnorm.CODES_MIN_ELEMENTS for in-block links and
-    batchnorm.RES_CODES_MIN_ELEMENTS for trunk links, either of which may be None = never; 0: every size).  in_block / trunk: make
-    only one kind of link (the measurement of section 38 times them apart).  Opt-in, never a default.
-    Parameters, buffers, state-dict keys and optimizer bindings do not change; the training flags are put back.  Returns
-    (in_block_links, trunk_links); unlink_bottleneck_codes_train undoes exactly these, restore_bottleneck_train and
-    restore_bn_train take them along."""
-    import types
-    from .conv2d_func import _f32
-    blocks = [m for m in model.modules() if "_bn_bottleneck" in m.__dict__ and "_bn_bottleneck_codes" not in m.__dict__]
-    if not blocks:
-        return 0, 0
-    flags = [(m, m.training) for m in model.modules()]
-    model.eval()
-    try:
-        tr = _Trace(model, example_input, blocks=blocks)
-        readers_of = {}
-        for blk in blocks if trunk else ():
-            io = tr.io(blk)
-            bn3 = blk._modules.get("bn3")
-            if io is None or not isinstance(bn3, TrainBatchNorm2d) or bn3._relu or bn3._trunk is not None or tr.runs(bn3) != 1:
-                continue
-            want = io[1]
-            if want.dim() != 4 or want.dtype != torch.float32:
-                continue
-            readers = [c.mod for c in tr.readers(want) if _is_conv_q(c.mod)]
-            if not readers or any(tr.runs(b) != 1 or not _link_conv_clean(b) for b in readers):
-                continue
-            if len({(_f32(b.Ka), int(b.q_bit)) for b in readers}) != 1:
-                continue   # one code tensor serves every reader
-            readers_of[blk] = tuple(readers)
-        tr.release()
-    finally:
-        for m, t in flags:
-            m.training = t
-    n_in = n_trunk = 0
-    for blk in blocks:
-        rec = {"in_block": {}, "trunk": None}
-        for bn_name, conv_name in (("bn1", "conv2"), ("bn2", "conv3")) if in_block else ():
-            bn, conv = blk._modules.get(bn_name), blk._modules.get(conv_name)
-            if (isinstance(bn, TrainBatchNorm2d) and not bn._relu and bn._trunk is None and bn.momentum is not None
-                    and _is_conv_q(conv) and _link_conv_clean(conv)
-                    and len(_slots_of(model, bn)) == 1 and len(_slots_of(model, conv)) == 1):
-                wrap = TrainBatchNormCodes2d(bn, None, conv, min_elements)
-                wrap.__dict__["_in_bottleneck"] = True
-                rec["in_block"][bn_name] = blk._modules[bn_name] = wrap
-        if blk in readers_of:
-            bn3 = blk._modules["bn3"]
-            ka, q_bit = _f32(readers_of[blk][0].Ka), int(readers_of[blk][0].q_bit)
-            bn3._trunk = (readers_of[blk], ka, q_bit, min_elements)
-            rec["trunk"] = bn3
-        if not rec["in_block"] and rec["trunk"] is None:
-            continue
-        blk.__dict__["_bn_bottleneck_codes"] = rec
-        if rec["in_block"]:
-            blk.__dict__["forward"] = types.MethodType(_bn_bottleneck_codes_forward, blk)
-        n_in += len(rec["in_block"])
-        n_trunk += rec["trunk"] is not None
-    return n_in, n_trunk
-
-
-def unlink_bottleneck_codes_train(model):
-    """Undo link_bottleneck_codes_train: the linked slots get their TrainBatchNorm2d back (pointed at the current parameters,
-    buffers and training flag), the bn3 wrappers forget their readers, the blocks get use_device_bottleneck_train's forward back.
-    Returns (in_block_links, trunk_links) undone."""
-    n = t = 0
-    for blk in list(model.modules()):
-        a, b = _unlink_bottleneck_codes(blk)
-        n, t = n + a, t + b
-    return n, t
+# ------------------------------------------------------------------ the training-mode passes: fusion_train.py, reached as fusion.<name>
+# (the last statement here, as the import of this module's names is there: whichever is imported first, the other finds its names)
+from .fusion_train import (   # noqa: E402,F401
+    FoldedTail, TrainBatchNorm2d, TrainBatchNormCodes2d, TrainBatchNormLayerout2d, _bn_bottleneck_candidate,
+    use_device_bn_train, restore_bn_train, use_device_bn_layerout_train, restore_bn_layerout_train,
+    use_device_bottleneck_train, restore_bottleneck_train, link_codes_train, unlink_codes_train,
+    link_bottleneck_codes_train, unlink_bottleneck_codes_train)
