@@ -52,6 +52,7 @@ SYMBOLS = (
     "slfp_conv2d_bwd_codes_supported", "slfp_conv2d_bwd_codes",
     "slfp_bn_res_codes_train_supported", "slfp_bn_res_codes_train_fwd",
     "slfp_debug_bwd_instance",
+    "slfp_bn_lut_codes_train_supported", "slfp_bn_lut_codes_train_fwd",
 )
 
 
@@ -194,6 +195,8 @@ def load():
         "slfp_bn_codes_train_fwd": (ci, [vp, vp, vp, vp, vp, cf, cf, ci, cf, ci, vp, vp, vp, vp, i64, i64, i64, i64, ci, vp, sz, vp]),
         "slfp_bn_codes_train_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, i64, i64, i64, i64, ci, vp, sz, vp]),
         "slfp_bn_res_codes_train_supported": (ci, [i64, i64, i64, i64, ci, cf, ci]),
+        "slfp_bn_lut_codes_train_supported": (ci, [i64, i64, i64, i64, ci]),
+        "slfp_bn_lut_codes_train_fwd": (ci, [vp, vp, vp, vp, vp, cf, cf, vp, vp, vp, vp, vp, i64, i64, i64, i64, ci, vp, sz, vp]),
         "slfp_bn_res_codes_train_fwd": (ci, [vp, vp, vp, vp, vp, vp, cf, cf, ci, cf, ci, vp, vp, vp, vp, i64, i64, i64, i64, ci, vp, sz, vp]),
         "slfp_debug_bn_split": (ci, [i64, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
         "slfp_debug_dwpw_instance": (ctypes.c_char_p, [dp, dp, ctypes.POINTER(ConvIo), ci, ci, ci]),

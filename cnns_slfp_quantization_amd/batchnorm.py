@@ -1,8 +1,9 @@
 """Training-mode BatchNorm2d (+ReLU) on libslfp_hip's kernels (csrc/bn_train.hip; include/slfp.h states the order of every
 sum): the autograd Function behind fusion.TrainBatchNorm2d.  float32 channels_last tensors on the ROCm device only; there is no
 fallback in here -- the module decides with bn_train_supported() and otherwise runs ATen's batch_norm itself.  Also the residual,
-table and code forms of the same kernels, the Function that spans BatchNorm -> ReLU -> Conv2d_Q on 1-byte codes, and the pair that
-puts a Bottleneck's trunk on codes: the tail that writes them next to float32 and the Conv2d_Q Function that reads them."""
+table and code forms of the same kernels, the Function that spans BatchNorm -> ReLU -> Conv2d_Q (or BatchNorm -> layer-output
+quantizer -> activation -> Conv2d_Q) on 1-byte codes, and the pair that puts a Bottleneck's trunk on codes: the tail that writes
+them next to float32 and the Conv2d_Q Function that reads them."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -230,6 +231,53 @@ def layerout_act_tables(acts, device):
     return F.contiguous(), D.contiguous()
 
 
+def _layerout_values():
+    """(class values as a float32 numpy array of _lib.LAYEROUT_LUT_BYTES entries, padding 0; the number of classes)."""
+    n = _lib.LAYEROUT_LUT_BYTES
+    L = _lib.load()
+    vals = np.zeros(n, dtype=np.float32)
+    _lib.check(L.slfp_layerout_lut_values(vals.ctypes.data, n))
+    return vals, L.slfp_layerout_lut_classes()
+
+
+def _layerout_code_bytes(acts, ka, q_bit, device, who, relu_first=False):
+    """The one builder of a byte table over the layer-output class (fusion._layerout_table for inference, layerout_code_table for
+    training): per slot of slfp_layerout_lut_values the reader's extended code of act_k(... act_1(relu?(value)) ...), the stock
+    modules themselves run under no_grad on `device`, then hip_encode (NaN -> 0x00, as everywhere on the code path).  relu_first is
+    a ReLU folded in front with the kernels' semantics: fmaxf(NaN, 0) is 0 (torch.relu would keep the NaN).  Padding slots are
+    treated as the value 0."""
+    from .conv2d_func import _act_fmt
+    from .sfp_quant import hip_encode
+    vals, _ = _layerout_values()
+    with torch.no_grad():
+        v = torch.from_numpy(vals).to(device)
+        if relu_first:
+            v = torch.where(v > 0, v, torch.zeros_like(v))
+        for act in acts:
+            v = act(v.clone())   # (an in-place module writes into the copy)
+        if not torch.is_tensor(v) or v.shape != (len(vals),) or v.dtype != torch.float32:
+            raise RuntimeError(f"{who}: an activation module did not return an elementwise float32 result")
+        return hip_encode(v.contiguous(), ka, _act_fmt(q_bit))
+
+
+def layerout_code_table(acts, ka, q_bit, device):
+    """The uint8 table of _lib.LAYEROUT_LUT_BYTES entries on the ROCm `device` that slfp_bn_lut_codes_train_fwd indexes by
+    layer-output class: the extended code, in the reader's quantizer QA(. / ka) of q_bit 8 or 7, of the stock modules `acts` applied
+    in order to the class value (slfp_layerout_lut_values -> the modules under no_grad -> hip_encode).  Index 0, the NaN class, is
+    0x00; padding slots are 0.  It accepts exactly the module types layerout_act_tables accepts -- the backward needs the
+    derivative table of the same modules -- so activation_func.STL is refused."""
+    acts = list(acts)
+    for act in acts:
+        if type(act) not in _lut_act_types():
+            raise TypeError(f"layerout_code_table: {type(act).__name__} is not an elementwise activation with a derivative table "
+                            "(nn.ReLU, nn.GELU, nn.SiLU, nn.Sigmoid, activation_func.Swish, activation_func.Sigmoid)")
+    if q_bit not in (8, 7):
+        raise ValueError(f"layerout_code_table: the reader's q_bit must be 8 or 7, got {q_bit}")
+    t = _layerout_code_bytes(acts, ka, q_bit, device, "layerout_code_table")
+    t[_layerout_values()[1]:] = 0
+    return t
+
+
 class hip_bn_lut_train(torch.autograd.Function):
     """y = act(layerout(batch_norm(x))) with batch statistics, the activation as the table `ftab` over the layer-output class and
     its derivative as `dtab` (layerout_act_tables, on x's device); running_mean / running_var are updated in place.  x:
@@ -277,15 +325,19 @@ CODES_MIN_ELEMENTS = 24 << 20
 
 
 class TrainLink:
-    """What a TrainBatchNormCodes2d hands its Conv2d_Q next to the code tensor (as the tensor attribute `_train_link`): the BN's
-    input with its graph, the BN's operands, the three per-channel arrays the forward saved, and the quantizer the codes were
-    written for.  The conv takes it off the tensor before it stashes the codes: a finished step must not keep x alive."""
-    __slots__ = ("x", "weight", "bias", "save_mean", "save_invstd", "save_lo", "relu", "ka", "q_bit", "conv")
+    """What a TrainBatchNormCodes2d or a TrainBatchNormLayeroutCodes2d hands its Conv2d_Q next to the code tensor (as the tensor
+    attribute `_train_link`): the BN's input with its graph, the BN's operands, the three per-channel arrays the forward saved,
+    and the quantizer the codes were written for.  The conv takes it off the tensor before it stashes the codes: a finished step
+    must not keep x alive."""
+    __slots__ = ("x", "weight", "bias", "save_mean", "save_invstd", "save_lo", "relu", "ka", "q_bit", "conv", "dtab")
 
-    def __init__(self, x, weight, bias, saves, relu, ka, q_bit, conv):
+    def __init__(self, x, weight, bias, saves, relu, ka, q_bit, conv, dtab=None):
         self.x, self.weight, self.bias = x, weight, bias
         self.save_mean, self.save_invstd, self.save_lo = saves
         self.relu, self.ka, self.q_bit, self.conv = bool(relu), ka, q_bit, conv
+        # the table form (TrainBatchNormLayeroutCodes2d): the derivative table of the activation behind the layer-output
+        # quantizer, which slfp_bn_lut_train_bwd multiplies by; None: the ReLU form, whose backward is slfp_bn_codes_train_bwd
+        self.dtab = dtab
 
     def made_for(self, conv, codes):
         """Were `codes` written for `conv`, and does it still read them?  Its own clause is the identity; the rest is the reader
@@ -297,17 +349,18 @@ class TrainLink:
 def bn_codes_train_supported(x, ka, q_bit, min_elements=None):
     """bn_train_supported under the code form's size rule (None: CODES_MIN_ELEMENTS, which may leave everything out), and
     slfp_bn_codes_train_supported for the reader's quantizer (ka: float32(Ka) as a Python float)."""
-    return _codes_form_supported(x, ka, q_bit, min_elements, CODES_MIN_ELEMENTS, "slfp_bn_codes_train_supported")
+    return _codes_form_supported(x, min_elements, CODES_MIN_ELEMENTS, "slfp_bn_codes_train_supported", ka, int(q_bit))
 
 
-def _codes_form_supported(x, ka, q_bit, floor, default_floor, query_name):
+def _codes_form_supported(x, floor, default_floor, query_name, *reader):
     """bn_train_supported under a code form's size rule (floor None: `default_floor`, which may itself be None = never), then the
-    form's own library query for the reader's quantizer."""
+    form's own library query: with the reader's quantizer (`reader` = ka, q_bit) where the form is told it, without for the table
+    form, whose table holds it."""
     floor = default_floor if floor is None else floor
     if floor is None or not bn_train_supported(x, floor):
         return False
     n, c, h, w = x.shape
-    return bool(getattr(_lib.load(), query_name)(n, h, w, c, _lib.LAYOUT_NHWC, ka, int(q_bit)))
+    return bool(getattr(_lib.load(), query_name)(n, h, w, c, _lib.LAYOUT_NHWC, *reader))
 
 
 def bn_codes_train_fwd(x, weight, bias, running_mean, running_var, momentum, eps, relu, ka, q_bit):
@@ -323,6 +376,52 @@ def bn_codes_train_fwd(x, weight, bias, running_mean, running_var, momentum, eps
     return (codes, *saves)
 
 
+# ---- BatchNorm2d -> layerout_quantize_func -> activation -> the next Conv2d_Q on 1-byte codes, in a training step
+# (slfp_bn_lut_codes_train_fwd, slfp_conv2d_bwd_codes and slfp_bn_lut_train_bwd) -----------------------------
+# The size rule of the table-and-codes form, by the spread rule of DESIGN sections 27, 32 and 35: the smallest size class from which
+# this class and every larger measured one beat the better unlinked leg by more than that leg's round-to-round spread, in two runs.
+# Read from profiles/bn_lut_codes_train_bench.json and its first run (_first.json): the hand-over shapes of vgg16_cifar32 (GELU,
+# "hip_all"), mobilenetv1_cifar32 and mobilenetv1_imagenet224 (Swish, "hip") at batch 128 and 256, forward + backward of [BN,
+# layerout, act, Conv2d_Q]; the better unlinked leg was the table kernels (use_device_bn_layerout_train(min_elements=0)) on every
+# row; M = 2^20 elements of the BatchNorm's tensor; rows ahead beyond the spread in the first, second run of the rows of the
+# class; speed-ups of the second run:
+#   196 M             1, 1 of 1      1.22x (the stride-2 depthwise reader of 256 x 112x112x64)
+#   98 M              5, 5 of 6      1.05-1.22x; the 1x1 32->64 reader at 112x112 BEHIND in both runs (0.989x, 0.989x)
+#   49 M              7, 7 of 9      1.03-1.16x; the 1x1 32->64 and 64->128 readers BEHIND in both (0.987x / 0.989x,
+#                                    0.981x / 0.978x)
+#   24.5 M            7, 7 of 8      1.05-1.17x; the 1x1 64->128 reader at 56x56 BEHIND in both (0.989x, 0.984x)
+#   16 M, 8 M, 3.06 M every row ahead in both runs (1.03-1.05x), under failing classes
+#   12.25 M           6, 7 of 7      1.04-1.06x; the 7x7 depthwise row behind in the first run (0.984x)
+#   6.12 M            3, 3 of 4      the 7x7 depthwise row at batch 128 BEHIND in both (0.883x, 0.900x)
+#   4 M and below     most rows BEHIND in both runs, 0.87-0.95x; a few rows ahead by 1-3 %.  (Both legs are ten launches from
+#                     Python there; why the linked one is the slower was not measured.)
+# So only hand-overs of 196 M elements and more are linked unless told otherwise (min_elements=0): at batch 128 of the CIFAR nets,
+# and of MobileNetV1-224, the default links NOTHING.  What loses in the large classes is one kind of row, the 1x1 reader with 32 or
+# 64 input channels, by 1-2 %; every depthwise, dense 3x3 and wider 1x1 reader from 8 M elements on was ahead in both runs but the
+# 7x7 depthwise one.  The CIFAR steps at batch 128 (hand-overs of 2 M elements and fewer there, 8 M in VGG): MobileNetV1_swish
+# 5.00 -> 5.53 ms with all 26 linked (SLOWER), VGG16_gelu 7.20 -> 7.13 ms with all 8.
+LUT_CODES_MIN_ELEMENTS = 196 << 20
+
+
+def bn_lut_codes_train_supported(x, min_elements=None):
+    """bn_train_supported under the table-and-codes form's size rule (None: LUT_CODES_MIN_ELEMENTS, which may be None = never), and
+    slfp_bn_lut_codes_train_supported (C % 4 == 0).  The reader's quantizer is in the table, not in the query."""
+    return _codes_form_supported(x, min_elements, LUT_CODES_MIN_ELEMENTS, "slfp_bn_lut_codes_train_supported")
+
+
+def bn_lut_codes_train_fwd(x, weight, bias, running_mean, running_var, momentum, eps, code_table):
+    """slfp_bn_lut_codes_train_fwd on a tensor bn_lut_codes_train_supported accepts, without recording: (codes, save_mean,
+    save_invstd, save_lo), codes a uint8 channels_last tensor of x's shape holding code_table[class of layerout(batch_norm(x))]
+    (code_table: layerout_code_table, on x's device); the running statistics are updated in place."""
+    x = x.detach()
+    gamma, beta = _vec(weight), _vec(bias)
+    codes = torch.empty(x.shape, dtype=torch.uint8, device=x.device, memory_format=torch.channels_last)
+    saves = [x.new_empty(x.shape[1]) for _ in range(3)]
+    _call("slfp_bn_lut_codes_train_fwd", x, x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(running_mean), _ptr(running_var),
+          float(momentum), float(eps), code_table.data_ptr(), codes.data_ptr(), *(t.data_ptr() for t in saves))
+    return (codes, *saves)
+
+
 def _codes_conv_forward(conv, codes, weight, bias, who):
     """Conv2d_Q `conv`'s code-reading forward on training codes, with freshly prepared weights (never the cache): the one
     plan-check-launch of both Functions below and of Conv2d_Q's own call where nothing records.  No kernel is an error here."""
@@ -330,22 +429,25 @@ def _codes_conv_forward(conv, codes, weight, bias, who):
     plan = _train_codes_plan(conv, codes)
     if not plan.ok:
         raise RuntimeError(f"{who}: no code-reading forward for this layer (slfp_conv2d_codes_supported); undo the training "
-                           "code links (fusion.unlink_codes_train, fusion.unlink_bottleneck_codes_train)")
+                           "code links (fusion.unlink_codes_train, fusion.unlink_layerout_codes_train, "
+                           "fusion.unlink_bottleneck_codes_train)")
     return _launch(conv, plan, codes, weight, bias, cache=False)
 
 
 class hip_bn_codes_conv_train(torch.autograd.Function):
-    """conv(relu?(batch_norm(x))) for a pair linked by fusion.link_codes_train, as ONE Function: autograd cannot carry a gradient
-    through the uint8 tensor between the two, and the float32 gradient between their backward kernels is a temporary.  The inputs
-    are the BN's x, weight and bias and the conv's weight and (scaled) bias; `codes` and `link` (TrainLink) are what the BN wrapper
-    produced already.  The forward runs the conv's code-reading forward with freshly prepared weights (never the cache: an
-    optimizer steps `.data` unseen); saved are x, the codes, the three per-channel arrays and the weights -- 5 bytes per element
-    where the unlinked pair saves x and y.  The backward runs slfp_conv2d_bwd_codes, then slfp_bn_codes_train_bwd on its gx."""
+    """conv(relu?(batch_norm(x))) for a pair linked by fusion.link_codes_train, or conv(act(layerout(batch_norm(x)))) for a block
+    linked by fusion.link_layerout_codes_train (the link then carries the activation's derivative table, `dtab`), as ONE Function:
+    autograd cannot carry a gradient through the uint8 tensor between the two, and the float32 gradient between their backward
+    kernels is a temporary.  The inputs are the BN's x, weight and bias and the conv's weight and (scaled) bias; `codes` and `link`
+    (TrainLink) are what the BN wrapper produced already.  The forward runs the conv's code-reading forward with freshly prepared
+    weights (never the cache: an optimizer steps `.data` unseen); saved are x, the codes, the three per-channel arrays and the
+    weights -- 5 bytes per element where the unlinked pair saves x and y -- and the link's table is kept.  The backward runs
+    slfp_conv2d_bwd_codes, then on its gx slfp_bn_codes_train_bwd, or slfp_bn_lut_train_bwd with `dtab` where the link has one."""
 
     @staticmethod
     def forward(ctx, x, bn_weight, bn_bias, weight, bias, conv, codes, link):
         y = _codes_conv_forward(conv, codes, weight, bias, "hip_bn_codes_conv_train")
-        ctx.conv, ctx.relu, ctx.has_bias = conv, link.relu, bias is not None
+        ctx.conv, ctx.relu, ctx.has_bias, ctx.dtab = conv, link.relu, bias is not None, link.dtab
         ctx.save_for_backward(x, codes, bn_weight, bn_bias, link.save_mean, link.save_invstd, link.save_lo, weight)
         return y
 
@@ -363,8 +465,12 @@ class hip_bn_codes_conv_train(torch.autograd.Function):
         if need_bn:
             gamma, beta = _vec(bn_weight), _vec(bn_bias)
             gx, ggamma, gbeta = _grads(ctx, x, save_mean, 1)
-            _call("slfp_bn_codes_train_bwd", x, x.data_ptr(), g.data_ptr(), gamma.data_ptr(), beta.data_ptr(), save_mean.data_ptr(),
-                  save_invstd.data_ptr(), save_lo.data_ptr(), 1 if ctx.relu else 0, gx.data_ptr(), _ptr(ggamma), _ptr(gbeta))
+            head = (x.data_ptr(), g.data_ptr(), gamma.data_ptr(), beta.data_ptr(), save_mean.data_ptr(), save_invstd.data_ptr(),
+                    save_lo.data_ptr())
+            if ctx.dtab is not None:   # the table form: the class is recomputed from x, g is multiplied by the derivative there
+                _call("slfp_bn_lut_train_bwd", x, *head, ctx.dtab.data_ptr(), gx.data_ptr(), _ptr(ggamma), _ptr(gbeta))
+            else:
+                _call("slfp_bn_codes_train_bwd", x, *head, 1 if ctx.relu else 0, gx.data_ptr(), _ptr(ggamma), _ptr(gbeta))
         return gx if need[0] else None, ggamma, gbeta, gw, gb, None, None, None
 
 
@@ -389,7 +495,7 @@ RES_CODES_MIN_ELEMENTS = 98 << 20
 def bn_res_codes_train_supported(x, ka, q_bit, min_elements=None):
     """bn_train_supported under the residual-and-codes form's size rule (None: RES_CODES_MIN_ELEMENTS, which may leave everything
     out), and slfp_bn_res_codes_train_supported for the readers' quantizer (ka: float32(Ka) as a Python float)."""
-    return _codes_form_supported(x, ka, q_bit, min_elements, RES_CODES_MIN_ELEMENTS, "slfp_bn_res_codes_train_supported")
+    return _codes_form_supported(x, min_elements, RES_CODES_MIN_ELEMENTS, "slfp_bn_res_codes_train_supported", ka, int(q_bit))
 
 
 class hip_bn_res_codes_train(torch.autograd.Function):

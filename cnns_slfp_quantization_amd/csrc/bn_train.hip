@@ -50,11 +50,17 @@
 // float32 trunk y as the residual form stores it and, next to it, y as the extended codes of the Conv2d_Q layers that read the
 // trunk, the four channels of a lane as one dword exactly as the code form stores them (behind the ReLU enc4_code_relu, else
 // enc4_code_fmt<FMT, true>).  One pass over x and res, the code form's one barrier (the table); its backward is the residual form's.
+// The table-and-codes form (k_bn_apply_lut_codes; slfp_bn_lut_codes_train_fwd) is the LUT forward with the reader's quantizer folded
+// into the table: behind the layer-output quantizer, act and the next Conv2d_Q's quantize_act(. / Ka) are ONE byte per class
+// (code_table, SLFP_LAYEROUT_LUT_BYTES bytes, built by the caller), C % 4 == 0:
+//   forward    t and the class as the LUT form;  byte = code_table[class];  a lane's four bytes leave as one dword, as the code form
+//              stores them;  no float32 y is written.  Only the byte table is in LDS (4 928 B, not the float table's 19 712 B).
+//   backward   slfp_bn_lut_train_bwd as it is: it recomputes the class from x and reads no forward output.
 // The two finalize kernels stage the records of 256 slabs x 8 channels in LDS with all 256 lanes (and the per-slab weights
 // n_b / n and n_a n_b / n, which depend on the slab index alone), then one lane per channel runs the serial chain.
 // Each of these is written once: bn_walk is the lane's walk over its rows (all five streaming kernels), bn_affine the apply's
 // expression (the apply of every form, and through bn_class the backward's recomputed class), bn_g the g of one element
-// (reduce, dx and the gres store), bn_forward / bn_backward the refusals and the three launches of a direction; the nine entry
+// (reduce, dx and the gres store), bn_forward / bn_backward the refusals and the three launches of a direction; the ten entry
 // points state their pointers and the refusals of their own form.
 #include "slfp_device.hpp"
 #include "slfp_enc.hpp"
@@ -128,7 +134,8 @@ struct BnArgs {
     float4* part;          // backward workspace: [S][C] (sg, sx, sd, 0)
     float* gmean;          // workspace behind the records: backward [3][C] mb, mg, lo; forward [C] lo = f32(mean - save_mean)
     const float* lo_fwd;   // LUT backward: the forward's lo (save_lo)
-    const float* table;    // LUT forms: act_table (forward) / dact_table (backward), kBnTableFloats floats
+    const float* table;    // LUT forms: act_table (forward) / dact_table (backward), kBnTableFloats floats; the table-and-codes
+                           // forward: the reader's byte table over the class (bn_code_lds reads it as bytes)
     const float* res;      // residual forward: the operand added behind the affine map
     float* gres;           // residual backward: the residual's gradient g, or null
     uint8_t* codes;        // code forward: y as the reader's extended codes, [M][C] bytes
@@ -183,6 +190,21 @@ template <bool CODES> __device__ __forceinline__ const unsigned char* bn_enc_lds
         enc_fill<kBnThreads>(sEnc, *enc);
         __syncthreads();
         return reinterpret_cast<const unsigned char*>(sEnc);
+    } else {
+        return nullptr;
+    }
+}
+
+// Table-and-codes form: the workgroup's copy of the reader's byte table over the layer-output class in LDS (308 pieces of 16
+// bytes), published by the barrier (every lane calls this).
+template <bool ON> __device__ __forceinline__ const uint8_t* bn_code_lds(const void* g) {
+    if constexpr (ON) {
+        static_assert(SLFP_LAYEROUT_LUT_BYTES % 16 == 0 && SLFP_LAYEROUT_LUT_BYTES >= kLayeroutClasses, "copied 16 bytes at a time");
+        __shared__ __attribute__((aligned(16))) uint8_t sCode[SLFP_LAYEROUT_LUT_BYTES];
+        for (int i = threadIdx.x; i < SLFP_LAYEROUT_LUT_BYTES / 16; i += kBnThreads)
+            reinterpret_cast<uint4*>(sCode)[i] = reinterpret_cast<const uint4*>(g)[i];
+        __syncthreads();
+        return sCode;
     } else {
         return nullptr;
     }
@@ -340,15 +362,17 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_finalize(const BnArgs a, floa
     if (running_var) running_var[l.c] = (float)((1.0 - mo) * (double)running_var[l.c] + mo * (var * cnt / (cnt - 1.0)));
 }
 
-// The apply pass of every form.  CODES (V == 4, never LUT): `enc` is the reader's kEncCode table, copied to LDS.  RES && CODES
-// stores both: the float32 pack of the residual form and the dword of the code form, of the same y.
+// The apply pass of every form.  CODES (V == 4) without LUT: `enc` is the reader's kEncCode table, copied to LDS.  RES && CODES
+// stores both: the float32 pack of the residual form and the dword of the code form, of the same y.  LUT && CODES: a.table is
+// the reader's byte table over the class, the only table in LDS; `enc` is null and no float32 is stored.
 template <int V, bool LUT, bool RES, bool CODES>
 __device__ __forceinline__ void bn_apply(const BnArgs& a, const EncArgs* enc) {
     static_assert(!(LUT && RES), "the residual form has no table");
-    static_assert(!CODES || (V == 4 && !LUT), "codes leave four channels to a dword, behind the plain or the residual apply");
+    static_assert(!CODES || V == 4, "codes leave four channels to a dword");
     const BnLane<V> l(a);
-    const float* const sTab = bn_table_lds<LUT>(a.table);
-    const unsigned char* const sE = bn_enc_lds<CODES>(enc);
+    const float* const sTab = bn_table_lds<LUT && !CODES>(a.table);
+    const unsigned char* const sE = bn_enc_lds<CODES && !LUT>(enc);
+    const uint8_t* const sCode = bn_code_lds<LUT && CODES>(a.table);
     if (!l.live) return;
     const size_t ld = (size_t)a.c;
     BnMap<V> map = {bn_ld<V>(a.mean + l.ch), bn_ld<V>(a.gmean + l.ch), bn_ld<V>(a.invstd + l.ch), bn_ld<V>(a.beta + l.ch)};
@@ -368,6 +392,14 @@ __device__ __forceinline__ void bn_apply(const BnArgs& a, const EncArgs* enc) {
                    return b;
                },
                [&](const size_t o, const BnRow<V, N>& b) {
+                   if constexpr (LUT && CODES) {
+                       // whole-register shifts and ors: no sub-dword VALU write in front of the store
+                       uint32_t d = 0;
+#pragma unroll
+                       for (int e = 0; e < V; ++e) d = d | ((uint32_t)sCode[bn_class<V>(b.p[0].v[e], map, e)] << (8 * e));
+                       *reinterpret_cast<uint32_t*>(a.codes + o + (size_t)l.ch) = d;
+                       return;
+                   }
                    Pack<V> v;
 #pragma unroll
                    for (int e = 0; e < V; ++e) {
@@ -382,7 +414,7 @@ __device__ __forceinline__ void bn_apply(const BnArgs& a, const EncArgs* enc) {
                            v.v[e] = t;
                        }
                    }
-                   if constexpr (CODES) {
+                   if constexpr (CODES && !LUT) {
                        const float4 t4 = make_float4(v.v[0], v.v[1], v.v[2], v.v[3]);
                        const float r1 = enc->r1, lo = enc->lo, hi = enc->hi;
                        const uint32_t d = relu ? enc4_code_relu<>(t4, r1, lo, hi, sE)
@@ -405,6 +437,10 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_apply_codes(const BnArgs a, c
 
 __global__ __launch_bounds__(kBnThreads) void k_bn_apply_res_codes(const BnArgs a, const EncArgs enc) {
     bn_apply<4, false, true, true>(a, &enc);
+}
+
+__global__ __launch_bounds__(kBnThreads) void k_bn_apply_lut_codes(const BnArgs a) {
+    bn_apply<4, true, false, true>(a, nullptr);
 }
 
 // What the backward loads of one row: x, gy and the forward's y (with relu only: otherwise y is never read; XM: never)
@@ -555,6 +591,7 @@ struct BnCodeCheck {
     bool has_codes;      // the forward: y_codes counts among the pointers, 4-byte aligned
     const void* codes;
     const char* query;   // the form's own support query, for the message
+    bool by_table;       // the table-and-codes form: the caller's byte table holds the reader's quantizer, c % 4 == 0 is all
 };
 static int bn_check(const char* fn, int64_t n, int64_t h, int64_t w, int64_t c, int x_layout, int relu, const void* const* big,
                     int nbig, const void* const* small, int nsmall, const void* workspace, size_t ws_bytes, int64_t* m,
@@ -571,6 +608,8 @@ static int bn_check(const char* fn, int64_t n, int64_t h, int64_t w, int64_t c, 
     if (!bn_supported(n, h, w, c, x_layout))
         return fail(SLFP_ERR_UNSUPPORTED, "%s: no kernel for this shape / layout (slfp_bn_train_supported): NHWC only, and more "
                                           "than 1 value per channel", fn);
+    if (cc && !cc->ok && cc->by_table)
+        return fail(SLFP_ERR_UNSUPPORTED, "%s: no kernel for this shape (%s): c %% 4 == 0", fn, cc->query);
     if (cc && !cc->ok)
         return fail(SLFP_ERR_UNSUPPORTED, "%s: no kernel for this shape / reader (%s): c %% 4 == 0, y_qbits "
                                           "8 or 7, and a y_ka > 0 with a proven code table", fn, cc->query);
@@ -601,7 +640,7 @@ static void bn_geometry(BnArgs& a, const BnSplit& s, int64_t m, int64_t c, int r
     if (!a.gmean) a.gmean = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + bn_gmean_offset(s, c));
 }
 
-enum BnForm { kBnPlain, kBnTable, kBnRes, kBnCodes, kBnResCodes };
+enum BnForm { kBnPlain, kBnTable, kBnRes, kBnCodes, kBnResCodes, kBnTableCodes };
 
 // What the code forms add to the supported set, host only: the reader's quantizer and a proven table for it.  Returns that table
 // (the one the apply is then launched with), or null.
@@ -615,7 +654,8 @@ static const EncArgs* bn_codes_table(int64_t c, float y_ka, int y_qbits) {
 
 // The streaming kernels of a (vec, form); the residual form's statistics and reduce pass are the plain ones, the code form's
 // statistics too.  The code forms' apply takes the reader's table by value behind the arguments (apply_codes; V == 4 only); the
-// residual-and-codes form has the residual form's backward.
+// residual-and-codes form has the residual form's backward.  The table-and-codes form (V == 4 only) has an ordinary apply, which
+// finds its byte table in the arguments, and the table form's backward.
 using BnKernel = void (*)(BnArgs);
 using BnCodeKernel = void (*)(BnArgs, EncArgs);
 struct BnKernels { BnKernel stats, apply, reduce, dx; BnCodeKernel apply_codes; };
@@ -629,6 +669,11 @@ template <int V> static BnKernels bn_kernels(BnForm form) {
         case kBnResCodes:
             if constexpr (V == 4)
                 return {k_bn_stats<V>, nullptr, k_bn_bwd_reduce<V>, k_bn_bwd_dx<V, false, true>, k_bn_apply_res_codes};
+            else
+                return {};
+        case kBnTableCodes:
+            if constexpr (V == 4)
+                return {k_bn_stats<V>, k_bn_apply_lut_codes, k_bn_bwd_reduce<V, true>, k_bn_bwd_dx<V, true>, nullptr};
             else
                 return {};
         case kBnTable: return {k_bn_stats<V>, k_bn_apply<V, true>, k_bn_bwd_reduce<V, true>, k_bn_bwd_dx<V, true>, nullptr};
@@ -656,21 +701,25 @@ static int bn_launched(const char* fn, const char* pass) {
 
 // The forward of every form.  `a` holds the entry point's pointers (x, out, gamma, beta, res, table; gmean = save_lo in the
 // table and code forms; codes and code_fmt in the two code forms); `aliased` is the entry point's own aliasing refusal, or null;
-// `y_ka` is the code forms' reader scale.
+// `y_ka` is the code forms' reader scale (the table-and-codes form has none: its table holds the reader's quantizer).
 static int bn_forward(const char* fn, BnForm form, BnArgs a, float* running_mean, float* running_var, float momentum, float eps,
                       int relu, float* save_mean, float* save_invstd, const BnCall& g, const char* aliased, float y_ka = 0.f,
                       int y_qbits = 0) {
     a.mean = save_mean; a.invstd = save_invstd;
-    const bool res = form == kBnRes || form == kBnResCodes, codes = form == kBnCodes || form == kBnResCodes;
-    const bool has_lo = form == kBnTable || form == kBnCodes;
+    const bool by_table = form == kBnTableCodes;
+    const bool res = form == kBnRes || form == kBnResCodes, codes = form == kBnCodes || form == kBnResCodes || by_table;
+    const bool has_lo = form == kBnTable || form == kBnCodes || by_table;
     const void* big[] = {a.x, a.out, a.res};
     const void* small[] = {a.gamma, a.beta, save_mean, save_invstd, a.gmean};
-    const EncArgs* const enc = codes ? bn_codes_table(g.c, y_ka, y_qbits) : nullptr;   // fetched once: checked here, launched below
-    const BnCodeCheck cc = {enc != nullptr, true, a.codes,
-                            form == kBnResCodes ? "slfp_bn_res_codes_train_supported" : "slfp_bn_codes_train_supported"};
+    const bool by_enc = codes && !by_table;   // the reader's threshold table travels behind the arguments
+    const EncArgs* const enc = by_enc ? bn_codes_table(g.c, y_ka, y_qbits) : nullptr;   // fetched once: checked here, launched below
+    const BnCodeCheck cc = {by_table ? g.c % 4 == 0 : enc != nullptr, true, a.codes,
+                            by_table ? "slfp_bn_lut_codes_train_supported"
+                                     : (form == kBnResCodes ? "slfp_bn_res_codes_train_supported" : "slfp_bn_codes_train_supported"),
+                            by_table};
     int64_t m = 0;
     const int rc = bn_check(fn, g.n, g.h, g.w, g.c, g.x_layout, relu, big, res ? 3 : (codes ? 1 : 2), small, has_lo ? 5 : 4,
-                            g.workspace, g.ws_bytes, &m, form == kBnTable, a.table, codes ? &cc : nullptr);
+                            g.workspace, g.ws_bytes, &m, form == kBnTable || by_table, a.table, codes ? &cc : nullptr);
     if (rc != SLFP_OK) return rc;
     if ((running_mean == nullptr) != (running_var == nullptr))
         return fail(SLFP_ERR_BAD_ARG, "%s: running_mean and running_var are given together or not at all", fn);
@@ -681,7 +730,7 @@ static int bn_forward(const char* fn, BnForm form, BnArgs a, float* running_mean
     const BnSplit s = bn_split(m, g.c);
     bn_geometry(a, s, m, g.c, relu, g.workspace);
     const BnKernels k = bn_kernels(s.vec, form);
-    if (!k.stats || !(codes ? (k.apply_codes && enc) : (bool)k.apply))
+    if (!k.stats || !(by_enc ? (k.apply_codes && enc) : (bool)k.apply))
         return fail(SLFP_ERR_UNSUPPORTED, "%s: no kernels of this form for %d channel(s) per lane", fn, s.vec);
     const dim3 grid((unsigned)s.slabs, (unsigned)s.tiles), block(kBnThreads);
     const hipStream_t st = as_stream(g.stream);
@@ -692,7 +741,7 @@ static int bn_forward(const char* fn, BnForm form, BnArgs a, float* running_mean
                        eps, save_mean, save_invstd);
     e = bn_launched(fn, "finalize");
     if (e != SLFP_OK) return e;
-    if (codes) hipLaunchKernelGGL(k.apply_codes, grid, block, 0, st, a, *enc);
+    if (by_enc) hipLaunchKernelGGL(k.apply_codes, grid, block, 0, st, a, *enc);
     else hipLaunchKernelGGL(k.apply, grid, block, 0, st, a);
     return bn_launched(fn, "apply");
 }
@@ -705,7 +754,7 @@ static int bn_backward(const char* fn, BnForm form, BnArgs a, int relu, float* g
     const void* big[] = {a.x, a.y, a.gy, a.out};
     const void* small[] = {a.gamma, a.mean, a.invstd, a.beta, a.lo_fwd};
     const bool codes = form == kBnCodes;
-    const BnCodeCheck cc = {g.c % 4 == 0, false, nullptr, "slfp_bn_codes_train_supported"};
+    const BnCodeCheck cc = {g.c % 4 == 0, false, nullptr, "slfp_bn_codes_train_supported", false};
     int64_t m = 0;
     const int rc = bn_check(fn, g.n, g.h, g.w, g.c, g.x_layout, relu, big, 4, small, form == kBnTable || codes ? 5 : 3, g.workspace,
                             g.ws_bytes, &m, form == kBnTable, a.table, codes ? &cc : nullptr);
@@ -819,6 +868,24 @@ int slfp_bn_lut_train_bwd(const float* x, const float* gy, const float* gamma, c
     a.lo_fwd = save_lo; a.table = dact_table;
     return bn_backward("slfp_bn_lut_train_bwd", kBnTable, a, 0, ggamma, gbeta, {n, h, w, c, x_layout, workspace, ws_bytes, stream},
                        nullptr, gx == x ? "gx may not alias x" : nullptr);
+}
+
+int slfp_bn_lut_codes_train_supported(int64_t n, int64_t h, int64_t w, int64_t c, int x_layout) {
+    return bn_supported(n, h, w, c, x_layout) && c % 4 == 0 ? 1 : 0;
+}
+
+int slfp_bn_lut_codes_train_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                                float momentum, float eps, const uint8_t* code_table, uint8_t* y_codes, float* save_mean,
+                                float* save_invstd, float* save_lo, int64_t n, int64_t h, int64_t w, int64_t c, int x_layout,
+                                void* workspace, size_t ws_bytes, void* stream) {
+    BnArgs a = {};
+    a.x = x; a.codes = y_codes; a.gamma = gamma; a.beta = beta;
+    a.table = reinterpret_cast<const float*>(code_table);   // read as bytes (bn_code_lds)
+    a.gmean = save_lo;   // as the table form: slfp_bn_lut_train_bwd recomputes the class from it
+    return bn_forward("slfp_bn_lut_codes_train_fwd", kBnTableCodes, a, running_mean, running_var, momentum, eps, 0, save_mean,
+                      save_invstd, {n, h, w, c, x_layout, workspace, ws_bytes, stream},
+                      reinterpret_cast<const void*>(x) == reinterpret_cast<const void*>(y_codes)
+                          ? "y_codes may not alias x (the backward reads x)" : nullptr);
 }
 
 int slfp_bn_codes_train_supported(int64_t n, int64_t h, int64_t w, int64_t c, int x_layout, float y_ka, int y_qbits) {

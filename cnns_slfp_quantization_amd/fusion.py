@@ -50,7 +50,6 @@ import collections
 import ctypes
 import warnings
 
-import numpy as np
 import torch
 import torch.nn as nn
 
@@ -826,21 +825,8 @@ def _layerout_table(a, acts, out, device):
     """The uint8 table of producer `a` for the reader `out` = (Ka, q_bit): per layer-output class (slfp_layerout_lut_values) the
     reader's extended code of act_k(... act_1(relu?(value)) ...), computed by the stock modules themselves on `device`.  relu? is
     the ReLU folded into a's epilogue with the kernels' semantics: fmaxf(NaN, 0) is 0 (torch.relu would keep the NaN)."""
-    from . import _lib
-    from .conv2d_func import _act_fmt
-    from .sfp_quant import hip_encode
-    n = _lib.LAYEROUT_LUT_BYTES
-    vals = np.zeros(n, dtype=np.float32)
-    _lib.check(_lib.load().slfp_layerout_lut_values(vals.ctypes.data, n))
-    with torch.no_grad():
-        v = torch.from_numpy(vals).to(device)
-        if _post_flags(a) & 1:
-            v = torch.where(v > 0, v, torch.zeros_like(v))
-        for act in acts:
-            v = act(v.clone())
-        if not torch.is_tensor(v) or v.shape != (n,) or v.dtype != torch.float32:
-            raise RuntimeError("link_layerout: an activation module did not return an elementwise float32 result")
-        return hip_encode(v.contiguous(), out[0], _act_fmt(out[1]))   # NaN -> 0x00, as everywhere on the code path
+    from .batchnorm import _layerout_code_bytes   # the one builder, shared with the training table (batchnorm.layerout_code_table)
+    return _layerout_code_bytes(acts, out[0], out[1], device, "link_layerout", bool(_post_flags(a) & 1))
 
 
 def link_layerout(model, example_input):
@@ -1964,4 +1950,5 @@ from .fusion_train import (   # noqa: E402,F401
     FoldedTail, TrainBatchNorm2d, TrainBatchNormCodes2d, TrainBatchNormLayerout2d, _bn_bottleneck_candidate,
     use_device_bn_train, restore_bn_train, use_device_bn_layerout_train, restore_bn_layerout_train,
     use_device_bottleneck_train, restore_bottleneck_train, link_codes_train, unlink_codes_train,
-    link_bottleneck_codes_train, unlink_bottleneck_codes_train)
+    link_bottleneck_codes_train, unlink_bottleneck_codes_train,
+    TrainBatchNormLayeroutCodes2d, link_layerout_codes_train, unlink_layerout_codes_train)

@@ -16,10 +16,15 @@ The table continues fusion.py's, with its columns; all of these are TRAINING pas
   link_bottleneck_codes_train      use_device_bottleneck_train        block: _bn_bottleneck_codes; bn1 / bn2 ->     unlink_bottleneck_codes_train /
     (model, x)                                                        TrainBatchNormCodes2d (_in_bottleneck); bn3   restore_bottleneck_train,
                                                                       wrapper: _trunk                               restore_bn_train
+  link_layerout_codes_train(model) -- (before or after                [BN, layerout_quantize_func, activation,      unlink_layerout_codes_train /
+                                   use_device_bn_layerout_train,      Conv2d_Q]: the BN slot ->                     restore_bn_layerout_train
+                                   use_device_bn_train)               TrainBatchNormLayeroutCodes2d, a stock
+                                                                      quantizer / activation ->
+                                                                      FoldedTail("layerout_codes_train")
 
-Shared: a placeholder belongs to one pass (FoldedReLU.owner; a FoldedTail is use_device_bn_layerout_train's) and
-only that pass's undo takes it back; fusion._restore_slots, _repoint, _eval_mode, _bn_bottleneck_forward are each the one of their
-kind; "may this Conv2d_Q read these training codes" is answered by conv2d_func._train_codes_reader_ok.
+Shared: a placeholder belongs to one pass (FoldedReLU.owner, FoldedTail.owner) and only that pass's undo takes
+it back; fusion._restore_slots, _repoint, _eval_mode, _bn_bottleneck_forward are each the one of their kind; "may this Conv2d_Q read
+these training codes" is answered by conv2d_func._train_codes_reader_ok.
 """
 import contextlib
 import types
@@ -343,17 +348,22 @@ def restore_bottleneck_train(model):
 
 # ------------------------------------------------------------------ training-mode BatchNorm2d -> layer-output quantizer -> activation
 class FoldedTail(nn.Module):
-    """The slot of a layerout_quantize_func or of an activation module that a TrainBatchNormLayerout2d in front of it applies:
-    the identity, in the style of FoldedReLU.  The original is kept outside _modules (`mod`); it has no parameters, the state
-    dict does not change."""
+    """The slot of a layerout_quantize_func or of an activation module that the wrapper in front of it applies: the identity, in
+    the style of FoldedReLU.  The original is kept outside _modules (`mod`); it has no parameters, the state dict does not change.
+    `owner` names the pass that put it there, whose undo alone takes it back: "bn_layerout_train" (use_device_bn_layerout_train:
+    a TrainBatchNormLayerout2d in front; the default) or "layerout_codes_train" (link_layerout_codes_train: a
+    TrainBatchNormLayeroutCodes2d in front, whose uint8 codes pass through)."""
 
-    def __init__(self, mod):
+    def __init__(self, mod, owner="bn_layerout_train"):
         super().__init__()
+        if owner not in ("bn_layerout_train", "layerout_codes_train"):
+            raise ValueError(f"FoldedTail: owner must be 'bn_layerout_train' or 'layerout_codes_train', got {owner!r}")
         object.__setattr__(self, "mod", mod)
+        self.owner = owner
         self.training = mod.training
 
     def extra_repr(self):
-        return type(self.mod).__name__
+        return f"{type(self.mod).__name__}, owner={self.owner}"
 
     def forward(self, x):
         return x
@@ -440,13 +450,19 @@ def use_device_bn_layerout_train(model, min_elements=None):
 def restore_bn_layerout_train(model):
     """Undo use_device_bn_layerout_train: every slot gets its original module back (the stock nn.BatchNorm2d, also where a
     TrainBatchNorm2d stood in the slot); the originals are pointed at the current parameters and buffers (the model may have been
-    moved or cast in between) and take the placeholders' training flags."""
-    def unfold(c):
-        if isinstance(c, FoldedTail):
-            c.mod.training = c.training
-            return c.mod
+    moved or cast in between) and take the placeholders' training flags.  Links of link_layerout_codes_train are undone first
+    (unlink_layerout_codes_train): a wrapper of theirs would hand the restored quantizer a uint8 tensor."""
+    unlink_layerout_codes_train(model)
+    return _restore_slots(model, lambda c: _repoint(c._bn, c) if isinstance(c, TrainBatchNormLayerout2d) else None,
+                          lambda c: _unfold_tail(c, "bn_layerout_train"))
 
-    return _restore_slots(model, lambda c: _repoint(c._bn, c) if isinstance(c, TrainBatchNormLayerout2d) else None, unfold)
+
+def _unfold_tail(c, owner):
+    """The module behind a FoldedTail of `owner`, with the placeholder's training flag; None for any other child."""
+    if isinstance(c, FoldedTail) and c.owner == owner:
+        c.mod.training = c.training
+        return c.mod
+    return None
 
 
 # ------------------------------------------------------------------ training-mode BatchNorm2d + ReLU -> the next Conv2d_Q on 1-byte codes
@@ -554,6 +570,146 @@ def unlink_codes_train(model):
     return _restore_slots(
         model, lambda c: _held_bn(c) if isinstance(c, TrainBatchNormCodes2d) and not c.__dict__.get("_in_bottleneck") else None,
         lambda c: c.relu if isinstance(c, FoldedReLU) and c.owner == "codes_train" else None)
+
+
+# ------------------------------------------------------------------ training-mode BatchNorm2d -> layer-output quantizer -> activation -> the next Conv2d_Q on 1-byte codes
+class TrainBatchNormLayeroutCodes2d(_DeviceBatchNorm):
+    """The BatchNorm2d of a run [BatchNorm2d, layerout_quantize_func(q_bit 7 or 8), activation, Conv2d_Q] linked by
+    link_layerout_codes_train: in a training step it runs slfp_bn_lut_codes_train_fwd without recording and
+    returns act(layerout(batch_norm(x))) as the uint8 channels_last codes of the Conv2d_Q's own quantizer -- behind the layer-output
+    quantizer the activation and the reader's quantize_act(. / Ka) are one byte table over the class (batchnorm.layerout_code_table).
+    The tensor carries a batchnorm.TrainLink with the activation's derivative table; the two slots behind pass it through and the
+    Conv2d_Q runs BN -> quantizer -> activation -> conv as one autograd Function on it (batchnorm.hip_bn_codes_conv_train, whose
+    backward is slfp_conv2d_bwd_codes, then slfp_bn_lut_train_bwd).  As the other wrappers it registers the SAME Parameter and buffer
+    objects under the same names; what stood in the three slots is kept outside _modules (`_held`), and so are the stock quantizer
+    and activation (`_layerout`, `_acts`).  The (F, D) tables and the code table are built lazily per device.
+    The code path is taken per call only where all of this holds: training mode, no autocast, a channels_last float32 ROCm input of
+    at least `min_elements` elements (None: batchnorm.LUT_CODES_MIN_ELEMENTS, which may be None = never) with float32 parameters and
+    buffers on its device; slfp_bn_lut_codes_train_supported (C % 4 == 0); and conv2d_func._train_codes_reader_ok for the conv with
+    the Ka and q_bit the link was made for (options.backward = "composite" never takes it).  Otherwise the call does what stood in
+    the slots does -- a TrainBatchNormLayerout2d under its own size rule, or F.batch_norm, the kept quantizer, the kept activation
+    -- and the conv sees float32.  A layer-output value of exactly zero is the NaN class: the float32 path hands the reader that
+    NaN, the code path 0x00, the tiny class (DESIGN sections 21, 35); the BN's own outputs do not differ.
+      _last_kernel   "bn_lut_codes_train", or "bn_lut_train" / "aten" """
+
+    def __init__(self, held_bn, held_layerout, held_act, conv, min_elements=None):
+        lut = isinstance(held_bn, TrainBatchNormLayerout2d)
+        super().__init__(_repoint(held_bn._bn, held_bn) if lut or isinstance(held_bn, TrainBatchNorm2d) else held_bn, min_elements)
+        layerout = held_layerout.mod if isinstance(held_layerout, FoldedTail) else held_layerout
+        act = held_act.mod if isinstance(held_act, FoldedTail) else held_act
+        if type(act) not in B._lut_act_types():
+            raise TypeError(f"TrainBatchNormLayeroutCodes2d: {type(act).__name__} has no derivative table")
+        # a TrainBatchNorm2d (without a folded ReLU) is taken as the stock module it wraps, as TrainBatchNormLayerout2d takes it
+        object.__setattr__(self, "_held", (held_bn if lut else self._bn, held_layerout, held_act))
+        object.__setattr__(self, "_layerout", layerout)
+        object.__setattr__(self, "_acts", (act,))
+        object.__setattr__(self, "_conv", conv)
+        self._fallback = (lut, held_bn.min_elements if lut else None)   # what the slots ran: the table kernels (+ size rule) or ATen
+        self._ka, self._q_bit = _f32(conv.Ka), conv.q_bit
+        self._tables, self._code_tables = {}, {}
+
+    def extra_repr(self):
+        return (f"{self.num_features}, eps={self.eps}, momentum={self.momentum}, layerout={self._layerout.q_bit}, "
+                f"acts={[type(a).__name__ for a in self._acts]}, codes for Ka={self._ka}, q_bit={self._q_bit}")
+
+    def tables(self, device):
+        """(F, D) of batchnorm.layerout_act_tables on `device`, built once per device."""
+        key = str(device)
+        t = self._tables.get(key)
+        if t is None:
+            t = self._tables[key] = B.layerout_act_tables(self._acts, device)
+        return t
+
+    def code_table(self, device):
+        """batchnorm.layerout_code_table for the linked conv's quantizer on `device`, built once per device."""
+        key = str(device)
+        t = self._code_tables.get(key)
+        if t is None:
+            t = self._code_tables[key] = B.layerout_code_table(self._acts, self._ka, self._q_bit, device)
+        return t
+
+    def _codes_ok(self, x):
+        """The form's own size rule and library query, then the reader check (conv2d_func._train_codes_reader_ok)."""
+        return B.bn_lut_codes_train_supported(x, self.min_elements) and _train_codes_reader_ok(self._conv, x, self._ka, self._q_bit)
+
+    def forward(self, x):
+        self._begin(x)
+        ops = self._kernel_operands(x, 0)
+        if ops is not None and self._codes_ok(x):
+            codes, *saves = B.bn_lut_codes_train_fwd(x, *ops, self.momentum, self.eps, self.code_table(x.device))
+            codes._train_link = B.TrainLink(x, self.weight, self.bias, saves, False, self._ka, self._q_bit, self._conv,
+                                            self.tables(x.device)[1])
+            self._last_kernel = "bn_lut_codes_train"
+            return codes
+        lut, floor = self._fallback
+        ops = self._kernel_operands(x, B.LUT_MIN_ELEMENTS if floor is None else floor) if lut else None
+        if ops is not None:
+            self._last_kernel = "bn_lut_train"
+            return B.hip_bn_lut_train.apply(x, *ops, self.momentum, self.eps, *self.tables(x.device))
+        y = self._aten(x)
+        y = self._layerout(y)
+        for act in self._acts:
+            y = act(y)
+        return y
+
+
+def link_layerout_codes_train(model, min_elements=None):
+    """Hand activations from a layer-output-quantized block to the next Conv2d_Q as 1-byte codes in a TRAINING step (DESIGN section
+    41).  Candidates are runs of four in the flattened leaf order of nested nn.Sequentials (_flat_slots):
+    [nn.BatchNorm2d | TrainBatchNorm2d without a folded ReLU | TrainBatchNormLayerout2d, layerout_quantize_func(q_bit 7 or 8) | its
+    FoldedTail, one activation batchnorm.layerout_act_tables accepts | its FoldedTail, Conv2d_Q].  Each of the four sits in exactly
+    one slot (and so does every nested Sequential around it), the BN is affine with a momentum, the conv has q_bit 8 or 7, no raw
+    bias and nothing fused onto it (_link_conv_clean).  The Conv2d_Q must stand DIRECTLY behind the activation: an nn.MaxPool2d in
+    between (the last pair of each VGG stage) leaves the pair unlinked, since bit-equal pool gradients need the float32 argmax, whose
+    ties differ from ties among codes.  q_bit == 32, activation_func.STL, a shared module, a BN with a folded ReLU and hand-wired
+    blocks are skipped.  The BN's slot gets a TrainBatchNormLayeroutCodes2d, a stock quantizer's and activation's slots a
+    FoldedTail("layerout_codes_train"); placeholders of use_device_bn_layerout_train stay where they are; the conv is not touched
+    (Conv2d_Q.forward recognises the record on its input).  Opt-in: every call decides for itself, and tensors of fewer than
+    `min_elements` elements (None: batchnorm.LUT_CODES_MIN_ELEMENTS, which may be None = never; 0: every size) stay float32.
+    Composes with use_device_bn_layerout_train and use_device_bn_train in either order.  A TrainBatchNorm2d in the BN's slot is
+    taken as the stock module it wraps, as use_device_bn_layerout_train takes it: the wrapper's fallback is then ATen, not the
+    plain BatchNorm kernels, and the undo puts the stock nn.BatchNorm2d into the slot.  Returns the number of links;
+    unlink_layerout_codes_train undoes them."""
+    nested = {c for m in model.modules() if isinstance(m, nn.Sequential) for c in m._modules.values() if isinstance(c, nn.Sequential)}
+    done = 0
+    for seq in [m for m in model.modules() if isinstance(m, nn.Sequential) and m not in nested]:
+        leaves = list(_flat_slots(seq, model))
+        i = 0
+        while i + 3 < len(leaves):
+            (pb, nb, bn, o1), (pl, nl, lo, o2), (pa, na, act, o3), (_, _, conv, o4) = leaves[i:i + 4]
+            stock = _bn_wrappable(bn) and _is_layerout(lo) and type(act) in B._lut_act_types()
+            swapped = (isinstance(bn, TrainBatchNormLayerout2d) and bn.momentum is not None and len(bn._acts) == 1
+                       and all(isinstance(t, FoldedTail) and t.owner == "bn_layerout_train" for t in (lo, act))
+                       and lo.mod is bn._layerout and act.mod is bn._acts[0])
+            if not ((stock or swapped) and o1 and o2 and o3 and o4 and _is_conv_q(conv) and _link_conv_clean(conv)
+                    and all(len(_slots_of(model, m)) == 1 for m in (bn, lo, act, conv))):
+                i += 1
+                continue
+            pb._modules[nb] = TrainBatchNormLayeroutCodes2d(bn, lo, act, conv, min_elements)
+            if stock:
+                pl._modules[nl] = FoldedTail(lo, "layerout_codes_train")
+                pa._modules[na] = FoldedTail(act, "layerout_codes_train")
+            done += 1
+            i += 3
+    return done
+
+
+def _held_layerout_bn(wrap):
+    """What a TrainBatchNormLayeroutCodes2d gives its slot back: the stock BatchNorm or the TrainBatchNormLayerout2d it holds,
+    pointed at the wrapper's current parameters, buffers and training flag."""
+    _repoint(wrap._bn, wrap)   # the stock module, which a held TrainBatchNormLayerout2d keeps as its own `_bn`
+    return _repoint(wrap._held[0], wrap)
+
+
+def unlink_layerout_codes_train(model):
+    """Undo link_layerout_codes_train: every slot gets back what it held (the stock modules, or use_device_bn_layerout_train's
+    wrapper, whose placeholders stayed), pointed at the current parameters, buffers and training flags.  One slot does not get
+    back what stood in it: where the link found a TrainBatchNorm2d (use_device_bn_train before the link) the slot gets the
+    stock nn.BatchNorm2d that wrapper stood for -- what restore_bn_train would have put there, and what
+    restore_bn_layerout_train does in the same case; run use_device_bn_train again to have the kernels back.  Returns the
+    number of links undone."""
+    return _restore_slots(model, lambda c: _held_layerout_bn(c) if isinstance(c, TrainBatchNormLayeroutCodes2d) else None,
+                          lambda c: _unfold_tail(c, "layerout_codes_train"))
 
 
 # ------------------------------------------------------------------ training-mode Bottlenecks on 1-byte codes: in-block links and the trunk

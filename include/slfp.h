@@ -768,6 +768,40 @@ int slfp_bn_res_codes_train_fwd(const float* x, const float* res, const float* g
                                 int64_t n, int64_t h, int64_t w, int64_t c, int x_layout,
                                 void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- training-mode BatchNorm2d -> layer-output quantizer -> activation that writes the next Conv2d_Q's codes (csrc/bn_train.hip,
+ * the table-and-codes form) ---------------------------------------------------------------------------------------------------
+ * In Conv2d_Q -> BatchNorm2d -> layerout_quantize_func -> Swish | GELU -> Conv2d_Q (nets_cifar/mobilenetv1.py:176-250,
+ * nets_cifar/vgg16.py:186-293) a value behind the layer-output quantizer is one of slfp_layerout_lut_classes() classes, so the
+ * activation followed by the reader's quantize_act(. / Ka) is ONE byte per class: the training twin of slfp_conv2d_fwd_codes_lut.
+ * code_table: device memory, SLFP_LAYEROUT_LUT_BYTES bytes, 16-byte aligned; index i is the class of slfp_layerout_lut_values /
+ * layerout_class, index 0 the NaN class; the caller builds it (code_table[i] = the extended code, in the reader's Ka and q_bit, of
+ * act(value_i); the NaN class and the padding 0x00).  The kernel is not told the reader's Ka or q_bit: the table holds them.  The
+ * contract is exact:
+ *   statistics save_mean, save_invstd, save_lo and the running statistics are bit-identical to slfp_bn_lut_train_fwd on the same x.
+ *   forward    t = (((x - save_mean) - save_lo) * (save_invstd * gamma)) + beta, the LUT form's expression;
+ *              y_codes[i] = code_table[layerout_class(layerout_bits(t_i))].  With a table built as above that is the byte
+ *              slfp_encode_f32(fmt | SLFP_FMT_EXT) gives slfp_bn_lut_train_fwd's y, except where that y is a NaN (the exact-zero
+ *              class): the float32 interface hands the reader the NaN, the codes hand it 0x00, the tiny class, as everywhere on the
+ *              code path.  No float32 y is written.  The apply pass reads x once and writes one byte per element, a lane's four
+ *              channels as one dword; each workgroup holds the byte table alone in LDS (4 928 B against the float table's 19 712 B).
+ *   backward   there is no new entry point: the backward is slfp_bn_lut_train_bwd, unchanged, with the dact_table of the same
+ *              activation.  It recomputes every class from x and the three saves and reads no forward output.
+ * No atomics; two calls give the same bits; a NaN or an inf stays in its channel.  Supported (slfp_bn_lut_codes_train_supported:
+ * 1 / 0, host only): the set of slfp_bn_train_supported, and in addition c % 4 == 0; everything else is SLFP_ERR_UNSUPPORTED.  The
+ * workspace is that of slfp_bn_train_workspace_bytes.  The refusals are those of slfp_bn_lut_train_fwd, in its order, before any
+ * device work, leaving the outputs untouched: y_codes stands where y stood (NULL: SLFP_ERR_BAD_ARG; not 4-byte aligned:
+ * SLFP_ERR_ALIGNMENT, behind x), code_table where act_table stood (NULL: SLFP_ERR_BAD_ARG; not 16-byte aligned:
+ * SLFP_ERR_ALIGNMENT, behind the per-channel arrays).  y_codes may not alias x.  n == 0 returns SLFP_OK.
+ * Algorithmic traffic per element (computed from the code, not measured): forward 4 + 4 + 1 = 9 B against the LUT form's 12 B; the
+ * reader's forward and its weight gradient read 1 B each against 4 B; the backward's 20 B are the LUT form's; saved for the
+ * backward are x and the codes, 5 B against 8 B. */
+int slfp_bn_lut_codes_train_supported(int64_t n, int64_t h, int64_t w, int64_t c, int x_layout);
+int slfp_bn_lut_codes_train_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                                float momentum, float eps, const uint8_t* code_table, uint8_t* y_codes,
+                                float* save_mean, float* save_invstd, float* save_lo,
+                                int64_t n, int64_t h, int64_t w, int64_t c, int x_layout,
+                                void* workspace, size_t ws_bytes, void* stream);
+
 /* ---- self-check ------------------------------------------------------------------------
  * The kernels compute x / scale_div with an FMA correction chain on a host-computed
  * reciprocal instead of the IEEE division macro (csrc/slfp_device.hpp, ScaleDiv).  This
