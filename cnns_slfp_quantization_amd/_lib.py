@@ -15,6 +15,7 @@ FMT_ACT8, FMT_W8, FMT_SFP7, FMT_EXT = 0, 1, 2, 4
 LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
 BWD_DENSE = 1  # slfp_conv2d_bwd_*_ex flags: SLFP_BWD_DENSE
 MFMA_DEFAULT, MFMA_F16X1, MFMA_F16X3 = 0, 1, 3
+MFMA_FP8 = 8   # SLFP_MFMA_FP8: q_bit 7, 1x1, code input, E4M3 operands (include/slfp.h)
 OPT_SGD, OPT_DSGD, OPT_SSGD = 0, 1, 2
 LAYEROUT_LUT_BYTES = 4928  # SLFP_LAYEROUT_LUT_BYTES
 LAYEROUT_TABLE_FLOATS = LAYEROUT_LUT_BYTES  # SLFP_LAYEROUT_TABLE_FLOATS: one float32 per layer-output class, padded alike

@@ -121,9 +121,10 @@ def _w_fmt(q_bit):
     return _lib.FMT_W8 if q_bit == 8 else _lib.FMT_SFP7
 
 
-def _conv_desc(mod, shape, nhwc_in=True, nhwc_out=True):
+def _conv_desc(mod, shape, nhwc_in=True, nhwc_out=True, fp8=False):
     """The C ABI's descriptor of module `mod` on an input of `shape` (N, C, H, W) in the given layouts: the one place that
-    spells the struct's fields.  A Linear_Q is the pointwise geometry (1x1, stride 1, no padding) with H = W = 1."""
+    spells the struct's fields.  A Linear_Q is the pointwise geometry (1x1, stride 1, no padding) with H = W = 1.  fp8: the
+    descriptor of a module marked `_fp8` for a forward on codes (_plan): SLFP_MFMA_FP8 instead of options.mfma_passes."""
     n, c, h, w = shape
     if isinstance(mod, nn.Linear):
         c_out, kh, kw, groups = mod.out_features, 1, 1, 1
@@ -139,7 +140,7 @@ def _conv_desc(mod, shape, nhwc_in=True, nhwc_out=True):
                          x_layout=_lib.LAYOUT_NHWC if nhwc_in else _lib.LAYOUT_NCHW,
                          y_layout=_lib.LAYOUT_NHWC if nhwc_out else _lib.LAYOUT_NCHW,
                          qbits=mod.q_bit, ka=_f32(_scalar_scale(mod.Ka, "Ka")), kw_scale=_f32(_scalar_scale(mod.Kw, "Kw")),
-                         mfma_passes=options.mfma_passes, reserved=0)
+                         mfma_passes=_lib.MFMA_FP8 if fp8 else options.mfma_passes, reserved=0)
 
 
 def _conv_io(x_codes, out):
@@ -244,6 +245,24 @@ _KINDS = {
 }
 
 
+_FP8_KINDS = ("codes", "slice")   # the forms SLFP_MFMA_FP8 serves, with code input
+
+
+def _fp8_forms_supported(mod):
+    """fusion.use_fp8_operands: has `mod` run on code input as "codes" / "slice" (its cached plans: the linking passes ran it), and
+    does the library take every one of those forms with an SLFP_MFMA_FP8 descriptor?"""
+    forms = [(key, plan) for key, plan in mod._plans.items()
+             if plan.kind in _FP8_KINDS and plan.ok and plan.io.x_codes and plan.desc.mfma_passes != _lib.MFMA_FP8]
+    if not forms:
+        return False
+    flags = int(mod._post[2]) if mod._post is not None else 0
+    for key, plan in forms:
+        d = _conv_desc(mod, key[1], True, True, fp8=True)
+        if not _supported(mod, key[1], plan.kind, True, key[0][2], flags, key[0][3], d, plan.io):
+            return False
+    return True
+
+
 def _ptr(t):
     """A tensor's address for the C ABI; None (NULL) for an absent one."""
     return t.data_ptr() if t is not None else None
@@ -279,12 +298,15 @@ def _plan(mod, x, weight, nhwc_in, nhwc_out, codes=None):
     float32 interface, else (kind of _KINDS, does x hold codes, mod._code_out or None, extra) with extra = the channel count of the
     wider tensor for "slice", whether a ReLU follows the add for "res" and "res_codes" (whose `out` is mod._trunk_code_out)."""
     shape = x.shape
-    key = (codes, shape, nhwc_in, nhwc_out, _scale_key(mod.Ka, "Ka"), _scale_key(mod.Kw, "Kw"), options.mfma_passes,
+    # a module marked by fusion.use_fp8_operands: its forwards on codes take the E4M3 descriptor (a blob and a kernel name of their
+    # own, so the prepared-weight cache never mixes the two blobs of one weight); every other form keeps the module's usual one
+    fp8 = bool(getattr(mod, "_fp8", False) and codes is not None and codes[0] in _FP8_KINDS and codes[1])
+    key = (codes, shape, nhwc_in, nhwc_out, _scale_key(mod.Ka, "Ka"), _scale_key(mod.Kw, "Kw"), options.mfma_passes, fp8,
            mod.stride, mod.padding, mod.dilation, weight.shape)
     plan = mod._plans.get(key) if options.plan_cache else None
     if plan is None:
         L = _lib.load()
-        d = _conv_desc(mod, shape, nhwc_in, nhwc_out)
+        d = _conv_desc(mod, shape, nhwc_in, nhwc_out, fp8)
         if shape[1] != mod.in_channels:
             raise RuntimeError(f"Given groups={mod.groups}, weight of size {list(weight.shape)}, expected input"
                                f"{list(shape)} to have {mod.in_channels} channels, but got {shape[1]} channels instead")
@@ -806,6 +828,7 @@ def _conv_class(q_bit, Kw, Ka, bias_default, scaled_bias):
             self._code_out = None   # (Ka, q_bit) of the next Conv2d_Q: hand it 1-byte codes (fusion.link_codes)
             self._code_entry = False   # with _code_out on a float32 input: ONE slfp_conv2d_fwd_entry launch where the library has it
             self._code_x3 = False   # on a code input that "codes" refuses: slfp_conv2d_fwd_codes_x3 (fusion.link_codes(x3=True))
+            self._fp8 = False   # forwards on code input run with E4M3 operands, SLFP_MFMA_FP8 (fusion.use_fp8_operands)
             # with _code_out behind a layer-output epilogue: the uint8 table of SLFP_LAYEROUT_LUT_BYTES entries that maps a
             # layer-output class to the reader's code (fusion.link_layerout); slfp_conv2d_fwd_codes_lut then runs.  A buffer, so
             # that it follows the module across devices; not persistent: the state dict keeps the reference's keys

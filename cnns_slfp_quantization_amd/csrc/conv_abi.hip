@@ -28,8 +28,10 @@ static int make_plan_core(const slfp_conv2d_desc* d, ConvPlan* plan) {
     if (!(d->ka > 0.f) || !(d->kw_scale > 0.f)) return fail(SLFP_ERR_BAD_ARG, "conv2d: Ka and Kw must be > 0");
     if (!scale_div_ok(d->ka) || !scale_div_ok(d->kw_scale))
         return fail(SLFP_ERR_UNSUPPORTED, "conv2d: Ka and Kw must be within [1e-30, 1e30]");
+    if (d->mfma_passes == SLFP_MFMA_FP8)   // make_plan(fp8_ok) plans such a descriptor in the default mode first
+        return fail(SLFP_ERR_UNSUPPORTED, "conv2d: SLFP_MFMA_FP8 (E4M3 operands) serves weight preparation and slfp_conv2d_fwd_codes[_slice] only");
     if (d->mfma_passes != SLFP_MFMA_DEFAULT && d->mfma_passes != SLFP_MFMA_F16X1 && d->mfma_passes != SLFP_MFMA_F16X3)
-        return fail(SLFP_ERR_BAD_ARG, "conv2d: mfma_passes must be 0, 1 or 3");
+        return fail(SLFP_ERR_BAD_ARG, "conv2d: mfma_passes must be 0, 1, 3 or 8");
     const int64_t eh = d->h + 2 * (int64_t)d->pad_h - (int64_t)d->dil_h * (d->kh - 1) - 1;
     const int64_t ew = d->w + 2 * (int64_t)d->pad_w - (int64_t)d->dil_w * (d->kw - 1) - 1;
     if (eh < 0 || ew < 0) return fail(SLFP_ERR_SHAPE, "conv2d: kernel larger than the padded input");
@@ -42,6 +44,7 @@ static int make_plan_core(const slfp_conv2d_desc* d, ConvPlan* plan) {
     plan->passes = d->qbits == 7 ? 1 : (d->mfma_passes == SLFP_MFMA_F16X3 ? 3 : 1);
     plan->k_pad = plan->n_pad = 0;
     plan->repad = false;
+    plan->fp8 = false;
     plan->cpi = d->c_in; plan->cpo = d->c_out;
     plan->s1 = d->ka;
     plan->s2 = d->kw_scale;
@@ -104,7 +107,23 @@ static bool padded_desc(const slfp_conv2d_desc& d, slfp_conv2d_desc* d2) {
     return true;
 }
 
-int make_plan(const slfp_conv2d_desc* d, ConvPlan* plan) {
+// SLFP_MFMA_FP8: the descriptor is validated and planned in the default mode, then held to what conv_pw_fp8.hip serves.
+static int make_plan_fp8(const slfp_conv2d_desc* d, ConvPlan* plan) {
+    slfp_conv2d_desc d1 = *d;
+    d1.mfma_passes = SLFP_MFMA_DEFAULT;
+    const int rc = make_plan_core(&d1, plan);
+    if (rc != SLFP_OK) return rc;
+    if (d->qbits != 7) return fail(SLFP_ERR_UNSUPPORTED, "conv2d: SLFP_MFMA_FP8 needs qbits 7 (SFP<3,3> is exact in E4M3; SLFP<3,4> is not)");
+    if (plan->family != kPointwise || !pw8_applicable(*d))
+        return fail(SLFP_ERR_UNSUPPORTED, "conv2d: SLFP_MFMA_FP8 serves 1x1, groups 1, stride 1, NHWC layers with C_in 16, 48 or 32 x {1, 2, 3, 4, 8, 12, 16, 32} "
+                                          "and C_out a multiple of 4 (include/slfp.h)");
+    plan->fp8 = true;
+    plan->wprep_bytes = round256(pw8_wprep_bytes(*plan));
+    return SLFP_OK;
+}
+
+int make_plan(const slfp_conv2d_desc* d, ConvPlan* plan, bool fp8_ok) {
+    if (fp8_ok && d && plan && d->mfma_passes == SLFP_MFMA_FP8) return make_plan_fp8(d, plan);
     int rc = make_plan_core(d, plan);
     if (rc != SLFP_OK || plan->family != kDirect) return rc;
     slfp_conv2d_desc d2;
@@ -233,6 +252,7 @@ int launch_prepare_weights(const slfp_conv2d_desc& d, const ConvPlan& p, const f
 }
 
 static const char* family_name(const ConvPlan& p, const slfp_conv2d_desc& d) {
+    if (p.fp8) return "pw_mfma_fp8";
     if (p.family == kDirect && stem_applicable(d)) return "stem_nhwc";
     if (p.repad) {  // the same kernels on channel-padded copies (ConvPlan::repad)
         if (p.family == kDw3x3) return "repad+dw3x3_nhwc";
@@ -260,7 +280,7 @@ extern "C" {
 
 int slfp_conv2d_out_shape(const slfp_conv2d_desc* d, int64_t* h_out, int64_t* w_out) {
     ConvPlan p;
-    const int rc = make_plan(d, &p);
+    const int rc = make_plan(d, &p, true);
     if (rc != SLFP_OK) return rc;
     if (h_out) *h_out = p.h_out;
     if (w_out) *w_out = p.w_out;
@@ -269,7 +289,7 @@ int slfp_conv2d_out_shape(const slfp_conv2d_desc* d, int64_t* h_out, int64_t* w_
 
 const char* slfp_conv2d_kernel_name(const slfp_conv2d_desc* d) {
     ConvPlan p;
-    if (make_plan(d, &p) != SLFP_OK) return "invalid";
+    if (make_plan(d, &p, true) != SLFP_OK) return "invalid";
     return family_name(p, *d);
 }
 
@@ -302,17 +322,18 @@ const char* slfp_debug_pw_variant(const slfp_conv2d_desc* d, const slfp_conv2d_i
 
 size_t slfp_conv2d_wprep_bytes(const slfp_conv2d_desc* d) {
     ConvPlan p;
-    if (make_plan(d, &p) != SLFP_OK) return 0;
+    if (make_plan(d, &p, true) != SLFP_OK) return 0;
     return p.wprep_bytes;
 }
 
 static int prepare_weights(const char* fn, const slfp_conv2d_desc* d, const void* w, void* wprep, float* weight_q_oihw, void* stream,
                            bool codes) {
     ConvPlan p;
-    const int rc = make_plan(d, &p);
+    const int rc = make_plan(d, &p, true);
     if (rc != SLFP_OK) return rc;
     if (!w || !wprep) return fail(SLFP_ERR_BAD_ARG, "%s: null pointer", fn);
     if (!aligned16(wprep)) return fail(SLFP_ERR_ALIGNMENT, "%s: wprep must be 16-byte aligned", fn);
+    if (p.fp8) return launch_pw8_prepare(*d, p, w, wprep, weight_q_oihw, as_stream(stream), codes);
     return launch_prepare_weights(*d, p, reinterpret_cast<const float*>(w), wprep, weight_q_oihw, as_stream(stream), codes);
 }
 
@@ -356,7 +377,7 @@ static WsLayout ws_layout(const slfp_conv2d_desc* d, const ConvPlan& p) {
 
 extern "C" size_t slfp_conv2d_workspace_bytes(const slfp_conv2d_desc* d) {
     ConvPlan p;
-    if (make_plan(d, &p) != SLFP_OK) return 0;
+    if (make_plan(d, &p, true) != SLFP_OK) return 0;
     return ws_layout(d, p).total;
 }
 
@@ -370,6 +391,7 @@ enum CodeRoute {
     kRouteDense,       // dense k x k (needs the workspace)
     kRouteStemSmall,   // the small-K MFMA stem with code output
     kRouteStemMfma,    // the large-kernel MFMA stem with code output (its two-kernel form needs the workspace)
+    kRoutePw8,         // pointwise on codes with E4M3 operands (SLFP_MFMA_FP8)
 };
 
 static int y_fmt_of(int y_qbits) { return y_qbits == 7 ? kFmtSfp7 : kFmtAct8; }
@@ -389,6 +411,11 @@ static bool code_path_ok(const slfp_conv2d_desc* d, int relu) {
 // The three route functions take the plan make_plan built for `d`.
 // need_table: the producer applies the reader's quantizer through its threshold table (not the table epilogue: lut_route).
 static CodeRoute codes_route(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, bool has_bias, int relu, const ConvPlan& p, bool need_table = true) {
+    if (p.fp8) {   // SLFP_MFMA_FP8: code input only, optional ReLU, float32 or codes out; the layouts are make_plan's
+        if (io->x_codes != 1 || (io->y_codes != 0 && io->y_codes != 1) || (relu & ~SLFP_POST_RELU) != 0) return kRouteNone;
+        if (io->y_codes && (d->c_out % 16 != 0 || !consumer_quant_ok(io) || !enc_table(io->y_ka, y_fmt_of(io->y_qbits), kEncCode)->valid)) return kRouteNone;
+        return kRoutePw8;
+    }
     if (!code_path_ok(d, relu)) return kRouteNone;
     if (io->y_codes && (!consumer_quant_ok(io) || (need_table && !enc_table(io->y_ka, y_fmt_of(io->y_qbits), kEncCode)->valid))) return kRouteNone;
     if (io->x_codes) {
@@ -406,7 +433,7 @@ static CodeRoute codes_route(const slfp_conv2d_desc* d, const slfp_conv2d_io* io
 }
 
 // The kernels whose code store takes a pixel stride (a channel slice of a wider tensor): pw_mfma_* on codes, the dense code epilogue.
-static bool slice_route(CodeRoute route) { return route == kRoutePwc || route == kRouteDense; }
+static bool slice_route(CodeRoute route) { return route == kRoutePwc || route == kRouteDense || route == kRoutePw8; }
 static bool y_ld_ok(const slfp_conv2d_desc* d, int64_t y_ld) { return y_ld >= d->c_out && y_ld % 16 == 0 && y_ld <= 0x7FFFFFFF; }
 
 // Pointwise, float32 in -> codes out: the layer at which a chain of codes begins (slfp_conv2d_fwd_entry).  A query and an entry
@@ -462,10 +489,14 @@ static bool x3_route(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int re
 // slfp_debug_pw_variant: the route the matching forward entry point takes (refused: "none"), then the launcher's own selection.
 static const char* pw_variant(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, bool has_res, bool has_res_codes, int64_t y_ld) {
     ConvPlan p;
-    if (!d || make_plan(d, &p) != SLFP_OK || p.family != kPointwise) return "none";
+    if (!d || make_plan(d, &p, true) != SLFP_OK || p.family != kPointwise) return "none";
     const slfp_conv2d_io f32{0, 0, 1.f, 8};
     if (!io) io = &f32;
     const int y_fmt = y_fmt_of(io->y_qbits);
+    if (p.fp8) {           // slfp_conv2d_fwd_codes / slfp_conv2d_fwd_codes_slice only
+        if (has_res || has_res_codes || (y_ld && (!io->y_codes || !y_ld_ok(d, y_ld))) || codes_route(d, io, false, 0, p) != kRoutePw8) return "none";
+        return pw8_variant_name(*d, p, io->y_codes != 0);
+    }
     if (has_res_codes) {   // slfp_conv2d_fwd_res_codes
         if (!has_res || y_ld || !res_codes_route(d, io, false, 0, p)) return "none";
         return pwc_variant_name(*d, p, false, true, true);
@@ -595,7 +626,7 @@ static int resolve(FwdKind kind, const char* fn, const FwdArgs& a, Resolved* r) 
     const slfp_conv2d_desc* d = a.d;
     const slfp_conv2d_io* io = a.io;
     if (kind != kFwdPost && (!d || !io)) return fail(SLFP_ERR_BAD_ARG, "%s: null descriptor", fn);
-    const int rc = make_plan(d, &r->p);
+    const int rc = make_plan(d, &r->p, kind == kFwdCodes || kind == kFwdSlice);
     if (rc != SLFP_OK) return rc;
     const bool with_res = kind == kFwdRes || kind == kFwdResCodes;
     if (!a.x || !a.wprep || !a.y || (with_res && !a.res) || (kind == kFwdResCodes && !a.y_codes)) return fail(SLFP_ERR_BAD_ARG, "%s: null pointer", fn);
@@ -696,6 +727,7 @@ static int launch_codes(const FwdArgs& a, const Resolved& r, hipStream_t st) {
     switch (r.route) {
         case kRouteDwc: return launch_dwc(d, r.p, xc, reinterpret_cast<const float*>(a.wprep), r.post, a.y, r.cio, st);
         case kRoutePwc: return launch_pwc(d, r.p, xc, a.wprep, a.bias, r.post, a.y, r.cio, st);
+        case kRoutePw8: return launch_pw8(d, r.p, xc, a.wprep, a.bias, r.post, a.y, r.cio, st);
         case kRouteDense: return launch_dense_mfma_io(d, r.p, a.x, a.wprep, a.bias, r.post, a.y, a.workspace, r.cio, st);
         case kRouteStemSmall: return launch_stem_small_io(d, r.p, xf, a.wprep, a.bias, r.post, a.y, r.cio, st);
         case kRouteStemMfma: return launch_stem_mfma_io(d, r.p, xf, a.wprep, a.bias, r.post, a.y, a.workspace, r.cio, st);
@@ -824,12 +856,12 @@ int slfp_conv2d_fwd_codes_lut(const slfp_conv2d_desc* d, const slfp_conv2d_io* i
 // The four queries: the route functions behind a null check and make_plan.
 int slfp_conv2d_codes_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int relu) {
     ConvPlan p;
-    return d && io && make_plan(d, &p) == SLFP_OK && codes_route(d, io, has_bias != 0, relu, p) != kRouteNone;
+    return d && io && make_plan(d, &p, true) == SLFP_OK && codes_route(d, io, has_bias != 0, relu, p) != kRouteNone;
 }
 
 int slfp_conv2d_codes_slice_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int relu, int64_t y_ld) {
     ConvPlan p;
-    return d && io && io->y_codes && make_plan(d, &p) == SLFP_OK && slice_route(codes_route(d, io, has_bias != 0, relu, p)) && y_ld_ok(d, y_ld);
+    return d && io && io->y_codes && make_plan(d, &p, true) == SLFP_OK && slice_route(codes_route(d, io, has_bias != 0, relu, p)) && y_ld_ok(d, y_ld);
 }
 
 int slfp_conv2d_entry_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int relu) {

@@ -66,6 +66,7 @@ struct Switches {
     bool stem_im2row;         // SLFP_STEM_IM2ROW: large-kernel stems through the im2row workspace (the round-1 form; A/B of k_stem_rows)
     int dw_rows;              // SLFP_DW_ROWS: -1 (unset) the measured rule, 0 never, else bit k = size class k (dw_rows_class) on k_dw3x3_rows
     int pw_grid;              // SLFP_PW_GRID: cap of the persistent pointwise grids (0: unset, no cap)
+    int pw8_pg;               // SLFP_PW8_PG=1|2: force the pixel groups per unit of the fp8 pointwise kernel (A/B runs, tests); 0 (unset): its rule
     int pw_stream_max_kb;     // SLFP_PW_STREAM_MAX_KB: largest W (KiB, fp16) the float32-interface path gives to the LDS-resident stream kernel (default 30; its capacity is 128)
 };
 const Switches& switches();
@@ -99,10 +100,13 @@ struct ConvPlan {
     // the inner (padded) launch.
     bool repad;
     int64_t cpi, cpo;
+    bool fp8;      // SLFP_MFMA_FP8: the pointwise family on E4M3 operands (conv_pw_fp8.hip); wprep_bytes is that kernel's blob
 };
 
 // Validates `d` and fills `plan`; returns SLFP_OK or an error status (error text recorded).
-int make_plan(const slfp_conv2d_desc* d, ConvPlan* plan);
+// fp8_ok: the caller serves SLFP_MFMA_FP8 descriptors (weight preparation, slfp_conv2d_fwd_codes[_slice] and their queries, the shape
+// and name queries); everywhere else such a descriptor is SLFP_ERR_UNSUPPORTED here, before any device work.
+int make_plan(const slfp_conv2d_desc* d, ConvPlan* plan, bool fp8_ok = false);
 
 // ---- launchers implemented next to their kernels (all NHWC, all async on `stream`) ----
 int launch_quantize(const float* x, float* y, size_t n, float scale, int fmt, hipStream_t stream);
@@ -179,6 +183,15 @@ bool pwc_x3_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, int post_fl
 int launch_pwc_x3(const slfp_conv2d_desc& d, const ConvPlan& p, const uint8_t* x, const void* wfrag, const float* bias,
                   const PostOp& post, void* y, const CodeIo& io, hipStream_t stream);
 const char* pwc_x3_variant_name(const slfp_conv2d_desc& d, const ConvPlan& p, bool y_codes);
+// pointwise on codes with E4M3 operands (conv_pw_fp8.hip; SLFP_MFMA_FP8): SFP<3,3> codes in, codes or float32 out, a blob of its own.
+// pw8_applicable: the layer geometry the kernel family serves (host only); the variant name is printed from the selection the launch
+// consumes ("none" where it would be refused; valid until the next call on the same thread).
+bool pw8_applicable(const slfp_conv2d_desc& d);
+size_t pw8_wprep_bytes(const ConvPlan& p);
+int launch_pw8_prepare(const slfp_conv2d_desc& d, const ConvPlan& p, const void* w, void* wprep, float* weight_q_oihw, hipStream_t stream, bool codes);
+int launch_pw8(const slfp_conv2d_desc& d, const ConvPlan& p, const uint8_t* x, const void* wprep, const float* bias,
+               const PostOp& post, void* y, const CodeIo& io, hipStream_t stream);
+const char* pw8_variant_name(const slfp_conv2d_desc& d, const ConvPlan& p, bool y_codes);
 // the MobileNetV1 image stem with code output (conv_direct.hip)
 bool stem_codes_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, int post_flags);
 int launch_stem_codes(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const float* wq_hwio, const float* bias,

@@ -331,6 +331,44 @@ class DwPwBlock(nn.Module):
         return y
 
 
+def use_fp8_operands(model, example_input=None, rtol=1e-5):
+    """Run after the linking passes (link_codes*, fuse_fire): every q_bit-7 Conv2d_Q that reads 1-byte codes and whose forms -- plain,
+    code output, channel slice, as the linked model has run them -- the library takes with E4M3 operands (SLFP_MFMA_FP8,
+    csrc/conv_pw_fp8.hip: 1x1, stride 1) is marked `_fp8`; its forwards on codes then run k_pw8 on a weight blob of their own.
+    Every SFP<3,3> value is exact in E4M3, so the products are exact; only the matrix unit's summation order may differ from the fp16
+    kernels'.  With `example_input` the model's output is compared before and after, tensor-relative: if it moved by more than `rtol`
+    everything is taken back and a RuntimeError says so (the contract of fuse_named_bn(rtol=...); rtol=None: no check).  Parameters, buffers and
+    state-dict keys are untouched.  Returns the number of marked modules; restore_fp8_operands(model) undoes the pass."""
+    from .conv2d_func import _fp8_forms_supported
+    y0 = None
+    if example_input is not None:
+        with torch.no_grad():
+            y0 = model(example_input)   # also fills the plans of the forms the modules run in
+    done = [m for m in model.modules()
+            if _is_conv_q(m) and m.q_bit == 7 and not m._fp8 and tuple(m.kernel_size) == (1, 1) and _fp8_forms_supported(m)]
+    for m in done:
+        m._fp8 = True
+    if y0 is not None and done:
+        with torch.no_grad():
+            y1 = model(example_input)
+        err = float((y1 - y0).abs().max() / y0.abs().max().clamp_min(1e-30))
+        if rtol is not None and not err <= rtol:
+            for m in done:
+                m._fp8 = False
+            raise RuntimeError(f"use_fp8_operands: the model's output moved by {err:.3e} (> {rtol}); nothing was changed")
+    return len(done)
+
+
+def restore_fp8_operands(model):
+    """Undo use_fp8_operands."""
+    n = 0
+    for m in model.modules():
+        if _is_conv_q(m) and getattr(m, "_fp8", False):
+            m._fp8 = False
+            n += 1
+    return n
+
+
 def _is_dw(m):
     return _is_conv_q(m) and m.groups == m.in_channels == m.out_channels and tuple(m.kernel_size) == (3, 3)
 

@@ -53,6 +53,17 @@ extern "C" {
 #define SLFP_MFMA_DEFAULT 0 /* library default = SLFP_MFMA_F16X1 (meets the 1e-3 parity bar) */
 #define SLFP_MFMA_F16X1 1   /* one fp16 MFMA pass: ~2.5e-4 tensor-relative error on SLFP<3,4> */
 #define SLFP_MFMA_F16X3 3   /* hi/lo split, three passes: float32-equivalent (~1e-6) */
+/* qbits 7, 1x1, code input: OCP E4M3 operands of 16 * Q on v_mfma_f32_16x16x32_fp8_fp8 (every SFP<3,3> value is exact in E4M3, so
+ * the products are exact; both operands are split by exponent, four MFMAs per k-step, so that the matrix unit also adds them exactly:
+ * the SFP<3,3> bar of 1e-5 holds).  Opt-in, with a weight blob of its own: a descriptor in this
+ * mode is served by slfp_conv2d_wprep_bytes, slfp_conv2d_prepare_weights[_codes], slfp_conv2d_codes_supported,
+ * slfp_conv2d_codes_slice_supported, slfp_conv2d_fwd_codes[_ws], slfp_conv2d_fwd_codes_slice and the shape / name queries; every other
+ * entry point returns SLFP_ERR_UNSUPPORTED before any device work, and so does qbits 8.  Supported: 1x1, groups 1, stride 1, no padding,
+ * NHWC on both sides, C_in 16, 48 or 32 x {1, 2, 3, 4, 8, 12, 16, 32}, C_out a multiple of 4 (float32 out) or 16 (codes out, dense or a
+ * channel slice), io->x_codes == 1, optional bias and post scale / shift, relu 0 or SLFP_POST_RELU.  slfp_conv2d_kernel_name:
+ * "pw_mfma_fp8"; slfp_debug_pw_variant: fp8/ks<KS>/pg<PG>/ns<slices>/<f32|yc> (k_pw8<KS, PG, YC>; /grid<n> under SLFP_PW_GRID;
+ * SLFP_PW8_PG=1|2 forces PG). */
+#define SLFP_MFMA_FP8 8
 
 int slfp_version(void);
 /* Re-reads the SLFP_* experiment switches from the environment (profiles/variants.py); not for production use. */
