@@ -54,6 +54,8 @@ SYMBOLS = (
     "slfp_bn_res_codes_train_supported", "slfp_bn_res_codes_train_fwd",
     "slfp_debug_bwd_instance",
     "slfp_bn_lut_codes_train_supported", "slfp_bn_lut_codes_train_fwd",
+    "slfp_conv2d_entry_lut_supported", "slfp_conv2d_fwd_entry_lut", "slfp_conv2d_exit_layerout_supported", "slfp_conv2d_fwd_exit_layerout",
+    "slfp_debug_pwr_instance",
 )
 
 
@@ -176,6 +178,11 @@ def load():
         "slfp_conv2d_codes_lut_supported": (ci, [dp, ctypes.POINTER(ConvIo), ci, i64]),
         "slfp_conv2d_fwd_codes_lut": (ci, [dp, ctypes.POINTER(ConvIo), vp, vp, vp, vp, vp, vp, vp, i64, vp, vp]),
         "slfp_debug_layerout_lut_mismatches": (ci, [vp, vp]),
+        "slfp_conv2d_entry_lut_supported": (ci, [dp, ctypes.POINTER(ConvIo), ci, i64, i64]),
+        "slfp_conv2d_fwd_entry_lut": (ci, [dp, ctypes.POINTER(ConvIo), vp, i64, vp, vp, vp, vp, vp, vp, i64, vp]),
+        "slfp_conv2d_exit_layerout_supported": (ci, [dp, ctypes.POINTER(ConvIo), ci, ci, ci, i64, i64, i64, i64, i64]),
+        "slfp_conv2d_fwd_exit_layerout": (ci, [dp, ctypes.POINTER(ConvIo), vp, i64, vp, vp, vp, vp, ci, vp, i64, vp, i64, i64, i64, vp]),
+        "slfp_debug_pwr_instance": (ctypes.c_char_p, [dp, ctypes.POINTER(ConvIo), ci]),
         "slfp_dwpw_codes_supported": (ci, [dp, dp, ctypes.POINTER(ConvIo), ci, ci, ci]),
         "slfp_dwpw_fwd_codes": (ci, [dp, dp, ctypes.POINTER(ConvIo), vp, vp, vp, vp, ci, vp, vp, vp, vp, ci, vp, vp]),
         "slfp_linear_fc_supported": (ci, [i64, i64, i64, ci, ci, ctypes.POINTER(ConvIo), ci, ci]),

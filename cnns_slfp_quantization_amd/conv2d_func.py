@@ -585,6 +585,78 @@ def _hip_conv2d_slice(mod, x, weight, bias, out_slice):
     return buf
 
 
+def _pwr_call(mod, shape, fn, x_keep):
+    """What the three launches of a linked ShuffleNetV2 branch (fusion.link_shuffle_units) share: the module's own descriptor on an
+    input of `shape`, its prepared blob from the module's cache, its epilogue vectors, the stream; fn(d, blob, bias, scale, shift,
+    flags, stream handle) makes the call.  x_keep: what `input_q` is derived from afterwards (float32 slice or codes)."""
+    d = _conv_desc(mod, shape)
+    dev = mod.weight.device
+    with _on_device(dev):
+        stream = torch.cuda.current_stream(dev)
+        blob = _conv_weights(mod, d, mod.weight, stream, True)
+        b, ps, psh, flags = _epilogue_args(mod, mod.bias, dev)
+        _lib.check(fn(ctypes.byref(d), blob.data_ptr(), _ptr(b), _ptr(ps), _ptr(psh), flags, stream.cuda_stream))
+    codes = x_keep.dtype == torch.uint8
+    mod.__dict__.update(_last_input=None if codes else x_keep.detach(), _last_codes=x_keep.detach() if codes else None, _last_pixels=None,
+                        _input_q=None)
+
+
+def _hip_pwr_entry(mod, x, c0, lut, out, pitch):
+    """The first 1x1 layer of a linked ShuffleNetV2 branch: ONE slfp_conv2d_fwd_entry_lut call on channels c0 .. c0 + C_in - 1 of the
+    float32 channels_last tensor `x` (a slice that is never copied); returns the codes for the reader `out` = (Ka, q_bit), behind the
+    table `lut`, as a uint8 channels_last tensor of `pitch` channels whose padding channels are 0x00."""
+    n, cw, h, w = x.shape
+    y = torch.empty((n, pitch, h, w), dtype=torch.uint8, device=x.device, memory_format=torch.channels_last)
+    io = _conv_io(False, out)
+    L = _lib.load()
+    _pwr_call(mod, (n, mod.in_channels, h, w), lambda d, blob, b, ps, psh, flags, st: L.slfp_conv2d_fwd_entry_lut(
+        d, ctypes.byref(io), x.data_ptr() + 4 * c0, cw, blob, b, ps, psh, lut.data_ptr(), y.data_ptr(), pitch, st), x[:, c0:c0 + mod.in_channels])
+    mod.__dict__["_last_kernel"] = "pwr_entry+lut"
+    return y
+
+
+def _hip_pwr_exit(mod, codes, passed, p0):
+    """The last 1x1 layer of a linked ShuffleNetV2 branch: ONE slfp_conv2d_fwd_exit_layerout call on the codes of a uint8
+    channels_last tensor (its channel count is the pitch).  Returns the unit's output, float32 channels_last with 2 C_out channels:
+    channel 2i is channel p0 + i of the float32 channels_last tensor `passed`, channel 2i + 1 result i -- channel_shuffle(cat(.), 2)."""
+    n, pitch, h, w = codes.shape
+    c = mod.out_channels
+    y = torch.empty((n, 2 * c, h, w), dtype=torch.float32, device=codes.device, memory_format=torch.channels_last)
+    io = _conv_io(True, None)
+    L = _lib.load()
+    _pwr_call(mod, (n, mod.in_channels, h, w), lambda d, blob, b, ps, psh, flags, st: L.slfp_conv2d_fwd_exit_layerout(
+        d, ctypes.byref(io), codes.data_ptr(), pitch, blob, b, ps, psh, flags, passed.data_ptr() + 4 * p0, passed.shape[1], y.data_ptr(), 2 * c, 1, 2, st),
+        codes[:, :mod.in_channels])
+    mod.__dict__["_last_kernel"] = "pwr_exit+pass"
+    return y
+
+
+def _hip_dw_codes_padded(mod, codes, pad, out):
+    """The depthwise 3x3 in the middle of a linked ShuffleNetV2 branch as an ordinary C = pitch code layer of slfp_conv2d_fwd_codes:
+    `pad` = (weights, scale, shift) zero-padded to the pitch by fusion.link_shuffle_units.  Codes in, codes for `out` = (Ka, q_bit) out."""
+    n, pitch, h, w = codes.shape
+    d = _conv_desc(mod, (n, pitch, h, w))
+    d.c_out = d.groups = pitch
+    io = _conv_io(True, out)
+    wpad, ps, psh, cache = pad
+    L = _lib.load()
+    with _on_device(codes.device):
+        stream = torch.cuda.current_stream(codes.device)
+        blob = cache.get("blob")
+        if blob is None:   # inference only: the padded weights are a snapshot taken at link time
+            blob = torch.empty(L.slfp_conv2d_wprep_bytes(ctypes.byref(d)), dtype=torch.uint8, device=codes.device)
+            _lib.check(L.slfp_conv2d_prepare_weights(ctypes.byref(d), wpad.data_ptr(), blob.data_ptr(), None, stream.cuda_stream))
+            cache["blob"] = blob
+        ho, wo = ctypes.c_int64(), ctypes.c_int64()
+        _lib.check(L.slfp_conv2d_out_shape(ctypes.byref(d), ctypes.byref(ho), ctypes.byref(wo)))
+        y = torch.empty((n, pitch, ho.value, wo.value), dtype=torch.uint8, device=codes.device, memory_format=torch.channels_last)
+        _lib.check(L.slfp_conv2d_fwd_codes_ws(ctypes.byref(d), ctypes.byref(io), codes.data_ptr(), blob.data_ptr(), None, ps.data_ptr(), psh.data_ptr(),
+                                              int(mod._post[2]), y.data_ptr(), None, stream.cuda_stream))
+    mod.__dict__.update(_last_kernel="dw3x3_nhwc+codes_in+codes_out+pitch", _last_input=None, _last_codes=codes[:, :mod.in_channels].detach(),
+                        _last_pixels=None, _input_q=None)
+    return y
+
+
 def _hip_conv2d_res(mod, x, weight, bias, residual, relu, trunk=None):
     """Conv2d_Q.forward(x, residual=r) as ONE slfp_conv2d_fwd_res call: relu?(epilogue(conv(x)) + r), bit-identical to the
     module's ordinary forward followed by torch.add and torch.relu.  `x` is float32 or the uint8 codes a linked producer

@@ -961,6 +961,88 @@ int slfp_conv2d_fwd_res_codes(const slfp_conv2d_desc* d, const slfp_conv2d_io* i
 
 }  // extern "C"
 
+// ---- the two ragged 1x1 layers of a ShuffleNetV2 residual branch (include/slfp.h; conv_pw_ragged.hip) ----
+// What precedes the pointers: descriptor, io, plan, then the launcher's own check of pitches, offsets and LDS fit.
+static int entry_lut_resolve(const char* fn, const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int64_t x_ld, int64_t y_ld, ConvPlan* p) {
+    if (!d || !io) return fail(SLFP_ERR_BAD_ARG, "%s: null descriptor", fn);
+    const int rc = make_plan(d, p);
+    if (rc != SLFP_OK) return rc;
+    if (io->x_codes != 0 || io->y_codes != 1) return fail(SLFP_ERR_BAD_ARG, "%s: reads float32 and writes codes (io->x_codes == 0, io->y_codes == 1)", fn);
+    if (!consumer_quant_ok(io))
+        return fail(SLFP_ERR_BAD_ARG, "%s: io->y_qbits must be 8 or 7 (got %d) and io->y_ka a positive scale within [1e-30, 1e30]", fn, io->y_qbits);
+    return pwr_entry_check(*d, *p, x_ld, y_ld);
+}
+
+static int exit_layerout_resolve(const char* fn, const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int flags, bool has_post, bool has_pass,
+                                 int64_t x_ld, int64_t pass_ld, int64_t y_ld, int64_t y_c0, int64_t y_cs, ConvPlan* p) {
+    if (!d || !io) return fail(SLFP_ERR_BAD_ARG, "%s: null descriptor", fn);
+    const int rc = make_plan(d, p);
+    if (rc != SLFP_OK) return rc;
+    if (io->x_codes != 1 || io->y_codes != 0) return fail(SLFP_ERR_BAD_ARG, "%s: reads codes and writes float32 (io->x_codes == 1, io->y_codes == 0)", fn);
+    if ((flags & ~(SLFP_POST_RELU | SLFP_POST_LAYEROUT)) != 0) return fail(SLFP_ERR_BAD_ARG, "%s: unknown flag bits in `relu`", fn);
+    if ((flags & SLFP_POST_LAYEROUT) && !has_post) return fail(SLFP_ERR_BAD_ARG, "%s: SLFP_POST_LAYEROUT needs post_scale / post_shift", fn);
+    return pwr_exit_check(*d, *p, has_pass, x_ld, pass_ld, y_ld, y_c0, y_cs);
+}
+
+static bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+
+extern "C" {
+
+int slfp_conv2d_entry_lut_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int64_t x_ld, int64_t y_ld) {
+    (void)has_bias;   // the kernel takes a bias
+    ConvPlan p;
+    return entry_lut_resolve("slfp_conv2d_entry_lut_supported", d, io, x_ld, y_ld, &p) == SLFP_OK;
+}
+
+int slfp_conv2d_fwd_entry_lut(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const float* x, int64_t x_ld, const void* wprep,
+                              const float* bias, const float* post_scale, const float* post_shift, const uint8_t* lut, void* y_codes,
+                              int64_t y_ld, void* stream) {
+    const char* fn = "slfp_conv2d_fwd_entry_lut";
+    ConvPlan p;
+    const int rc = entry_lut_resolve(fn, d, io, x_ld, y_ld, &p);
+    if (rc != SLFP_OK) return rc;
+    if (!x || !wprep || !y_codes) return fail(SLFP_ERR_BAD_ARG, "%s: null pointer", fn);
+    if (!lut || !post_scale || !post_shift)
+        return fail(SLFP_ERR_BAD_ARG, "%s: lut, post_scale and post_shift are required (the table is indexed by the layer-output class of the affine's result)", fn);
+    if (!aligned8(x)) return fail(SLFP_ERR_ALIGNMENT, "%s: x (the slice's first channel) must be 8-byte aligned", fn);
+    if (!aligned16(y_codes) || !aligned16(wprep) || !aligned16(lut)) return fail(SLFP_ERR_ALIGNMENT, "%s: y_codes, wprep and lut must be 16-byte aligned", fn);
+    const PostOp post{post_scale, post_shift, 0, 0};
+    return launch_pwr_entry(*d, p, x, x_ld, wprep, bias, post, lut, reinterpret_cast<uint8_t*>(y_codes), y_ld, as_stream(stream));
+}
+
+int slfp_conv2d_exit_layerout_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int relu, int has_pass, int64_t x_ld,
+                                        int64_t pass_ld, int64_t y_ld, int64_t y_c0, int64_t y_cs) {
+    (void)has_bias;   // the kernel takes a bias
+    ConvPlan p;
+    return exit_layerout_resolve("slfp_conv2d_exit_layerout_supported", d, io, relu, true, has_pass != 0, x_ld, pass_ld, y_ld, y_c0, y_cs, &p) == SLFP_OK;
+}
+
+int slfp_conv2d_fwd_exit_layerout(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x_codes, int64_t x_ld, const void* wprep,
+                                  const float* bias, const float* post_scale, const float* post_shift, int relu, const float* pass,
+                                  int64_t pass_ld, float* y, int64_t y_ld, int64_t y_c0, int64_t y_cs, void* stream) {
+    const char* fn = "slfp_conv2d_fwd_exit_layerout";
+    if ((post_scale == nullptr) != (post_shift == nullptr)) return fail(SLFP_ERR_BAD_ARG, "%s: post_scale and post_shift must be given together", fn);
+    ConvPlan p;
+    const int rc = exit_layerout_resolve(fn, d, io, relu, post_scale != nullptr, pass != nullptr, x_ld, pass_ld, y_ld, y_c0, y_cs, &p);
+    if (rc != SLFP_OK) return rc;
+    if (!x_codes || !wprep || !y) return fail(SLFP_ERR_BAD_ARG, "%s: null pointer", fn);
+    if (!aligned16(x_codes) || !aligned16(wprep)) return fail(SLFP_ERR_ALIGNMENT, "%s: x_codes and wprep must be 16-byte aligned", fn);
+    if (!aligned8(y) || !aligned8(pass)) return fail(SLFP_ERR_ALIGNMENT, "%s: y and pass (the float32 slices) must be 8-byte aligned", fn);
+    const PostOp post{post_scale, post_shift, (relu & SLFP_POST_RELU) ? 1 : 0, (relu & SLFP_POST_LAYEROUT) ? 1 : 0};
+    return launch_pwr_exit(*d, p, reinterpret_cast<const uint8_t*>(x_codes), x_ld, wprep, bias, post, pass, pass_ld, y, y_ld, y_c0, y_cs,
+                           as_stream(stream));
+}
+
+const char* slfp_debug_pwr_instance(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_pass) {
+    ConvPlan p;
+    if (!d || !io || make_plan(d, &p) != SLFP_OK) return "none";
+    if (io->x_codes == 0 && io->y_codes == 1) return has_pass ? "none" : pwr_instance_name(*d, p, true, false);
+    if (io->x_codes == 1 && io->y_codes == 0) return pwr_instance_name(*d, p, false, has_pass != 0);
+    return "none";
+}
+
+}  // extern "C"
+
 // ---- image stems on uint8 pixels + a float32 pixel table (include/slfp.h: slfp_conv2d_fwd_u8) ----
 enum U8Route { kU8None = 0, kU8Fixed, kU8Small, kU8Mfma };
 

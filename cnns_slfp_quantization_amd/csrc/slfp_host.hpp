@@ -192,6 +192,19 @@ int launch_pw8_prepare(const slfp_conv2d_desc& d, const ConvPlan& p, const void*
 int launch_pw8(const slfp_conv2d_desc& d, const ConvPlan& p, const uint8_t* x, const void* wprep, const float* bias,
                const PostOp& post, void* y, const CodeIo& io, hipStream_t stream);
 const char* pw8_variant_name(const slfp_conv2d_desc& d, const ConvPlan& p, bool y_codes);
+// the 1x1 layers at the two ends of a ShuffleNetV2 residual branch (conv_pw_ragged.hip): any even channel count on the float32 side,
+// codes at a pitch that is a multiple of 32 on the other.  entry: float32 channel slice (pitch x_ld floats) -> codes through the
+// layer-output byte table (pitch y_ld bytes, padding 0x00).  exit: codes (pitch x_ld bytes) -> float32 behind affine / layer-output
+// quantizer / ReLU at y[pix * y_ld + y_c0 + i * y_cs]; y_cs == 2 with `pass`: pass[pix * pass_ld + i] lands in front of result i.
+// The *_check functions validate pitches, offsets and LDS fit without pointers (the support queries); the launchers call them again.
+// The name is printed from the selection the launch consumes ("none" where it would be refused).
+int pwr_entry_check(const slfp_conv2d_desc& d, const ConvPlan& p, int64_t x_ld, int64_t y_ld);
+int pwr_exit_check(const slfp_conv2d_desc& d, const ConvPlan& p, bool has_pass, int64_t x_ld, int64_t pass_ld, int64_t y_ld, int64_t y_c0, int64_t y_cs);
+int launch_pwr_entry(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, int64_t x_ld, const void* wfrag, const float* bias,
+                     const PostOp& post, const uint8_t* lut, uint8_t* y_codes, int64_t y_ld, hipStream_t stream);
+int launch_pwr_exit(const slfp_conv2d_desc& d, const ConvPlan& p, const uint8_t* x_codes, int64_t x_ld, const void* wfrag, const float* bias,
+                    const PostOp& post, const float* pass, int64_t pass_ld, float* y, int64_t y_ld, int64_t y_c0, int64_t y_cs, hipStream_t stream);
+const char* pwr_instance_name(const slfp_conv2d_desc& d, const ConvPlan& p, bool entry, bool pass);
 // the MobileNetV1 image stem with code output (conv_direct.hip)
 bool stem_codes_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, int post_flags);
 int launch_stem_codes(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const float* wq_hwio, const float* bias,

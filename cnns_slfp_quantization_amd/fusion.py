@@ -814,11 +814,15 @@ def link_codes_traced(model, example_input, entries=False, x3=False):
 
 
 def unlink_codes(model):
-    """Undo link_codes / link_codes_traced / link_stem / link_layerout (and, uncounted, every link of link_trunk: its producers read
+    """Undo link_codes / link_codes_traced / link_stem / link_layerout / link_shuffle_units (and, uncounted, every link of link_trunk: its producers read
     codes)."""
     n = 0
     unlink_trunk(model)
     unlink_head(model)   # (uncounted, as link_trunk's: a head link's producer may be the last conv of a chain)
+    for m in model.modules():   # link_shuffle_units: a unit's own forward comes back
+        if "_shuffle_link" in m.__dict__:
+            _unlink_shuffle_unit(m)
+            n += 1
     for parent in model.modules():
         for name, child in list(parent._modules.items()):
             if isinstance(child, CodeMaxPool2d):
@@ -953,6 +957,116 @@ def link_layerout(model, example_input):
         _unwrap_children(wrapped)
 
     return len(made) if _verified(lambda: model(example_input), y0, undo) else 0
+
+
+# ------------------------------------------------------------------ ShuffleNetV2 units: the residual branch on codes
+def _shuffle_branch(unit):
+    """(conv0, dw, conv6) of a ShuffleNetV2 unit after fuse_bn_relu, or None: children `residual` / `shortcut`, `stride`, and a residual
+    branch [1x1 + BN + layerout + ReLU, dw3x3 + BN, 1x1 + BN + layerout + ReLU] with nothing but nn.Identity in between."""
+    res, sc = unit._modules.get("residual"), unit._modules.get("shortcut")
+    if not isinstance(res, nn.Sequential) or not isinstance(sc, nn.Sequential) or getattr(unit, "stride", None) not in (1, 2):
+        return None
+    convs = [m for m in res if not isinstance(m, nn.Identity)]
+    if len(convs) != 3 or not all(_is_conv_q(m) and m.q_bit in (8, 7) and not m.training and m.bias is None and m._post is not None
+                                  and m._post[0] is not None and m._code_out is None for m in convs):
+        return None
+    a, dw, b = convs
+    c = a.out_channels
+    pw = lambda m: m.kernel_size == (1, 1) and m.groups == 1 and tuple(m.stride) == (1, 1) and _post_flags(m) == 3   # noqa: E731
+    if not (pw(a) and pw(b) and b.in_channels == c and c % 2 == 0 and b.out_channels % 2 == 0 and a.q_bit == dw.q_bit == b.q_bit):
+        return None
+    if not (dw.kernel_size == (3, 3) and dw.groups == dw.in_channels == dw.out_channels == c and _post_flags(dw) == 0
+            and tuple(dw.stride) == (unit.stride, unit.stride)):
+        return None
+    if unit.stride == 1 and (len(sc) != 0 or a.in_channels != c or b.out_channels != c):
+        return None
+    return a, dw, b
+
+
+def _linked_unit_forward(unit, x):
+    """forward of a unit linked by link_shuffle_units: entry -> k_dwc -> exit, three launches, no split / cat / shuffle copies.  An
+    input the kernels do not take (not a float32 channels_last ROCm tensor) runs the unit's own forward."""
+    from .conv2d_func import _hip_dw_codes_padded, _hip_pwr_entry, _hip_pwr_exit
+    a, dw, b, lut, pad, pitch = unit._shuffle_link
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)
+            and x.device == a.weight.device and not torch.is_grad_enabled()):
+        return type(unit).forward(unit, x)
+    c = b.out_channels
+    if unit.stride == 1:   # the split is two channel slices of x: the second feeds the branch, the first passes through
+        h1 = _hip_pwr_entry(a, x, c, lut, _reader_quant(dw), pitch)
+        passed, p0 = x, 0
+    else:
+        h1 = _hip_pwr_entry(a, x, 0, lut, _reader_quant(dw), pitch)
+        passed, p0 = unit.shortcut(x), 0
+        if not passed.is_contiguous(memory_format=torch.channels_last):
+            passed = passed.contiguous(memory_format=torch.channels_last)
+    h2 = _hip_dw_codes_padded(dw, h1, pad, _reader_quant(b))
+    unit.__dict__["_shuffle_handover"] = (h1, h2)
+    return _hip_pwr_exit(b, h2, passed, p0)
+
+
+def link_shuffle_units(model, example_input):
+    """After fuse_bn_relu, opt-in, inference only: every ShuffleNetV2 unit (children `residual` / `shortcut`, `stride`; recognised by
+    structure, _shuffle_branch) runs its residual branch on 1-byte codes.  The two hand-over tensors inside the branch are uint8 with a
+    pitch of P = round_up(c, 32) channels; the first 1x1 layer reads its half of the float32 trunk as a channel slice and writes codes
+    through the byte table of its layer-output classes (_layerout_table: ReLU + the depthwise layer's quantizer;
+    slfp_conv2d_fwd_entry_lut), the depthwise 3x3 is a C = P code layer with zero-padded weights and BN vectors, the last 1x1 layer
+    reads codes and writes the unit's float32 output with the shortcut half interleaved (slfp_conv2d_fwd_exit_layerout): split, cat
+    and channel_shuffle run as no kernel of their own.  A stride-2 unit keeps its shortcut branch as it is; its output is the exit's
+    `pass` operand.  The model must be channels_last (an NCHW-contiguous example input is refused).  The whole set is verified with
+    torch.equal against the unlinked output on `example_input` and rolled back otherwise.  State-dict keys and parameters are
+    untouched.  Returns the number of linked units; unlink_codes undoes them."""
+    from . import _lib
+    from .conv2d_func import _conv_desc, _conv_io
+    if model.training or not (torch.is_tensor(example_input) and example_input.is_cuda and example_input.dim() == 4
+                              and example_input.is_contiguous(memory_format=torch.channels_last)):
+        return 0
+    units = [m for m in model.modules() if "_shuffle_link" not in m.__dict__ and _shuffle_branch(m) is not None]
+    tr = _Trace(model, example_input, blocks=units)
+    y0 = tr.output
+    L, made = _lib.load(), []
+    for u in units:
+        a, dw, b = _shuffle_branch(u)
+        io_u = tr.io(u)
+        if io_u is None or tr.io(a) is None or tr.io(b) is None:
+            continue
+        x, xa, xb = io_u[0], tr.io(a)[0], tr.io(b)[0]
+        if not (x.dtype == torch.float32 and x.dim() == 4):   # (its layout is the unlinked producer's: a linked unit writes channels_last)
+            continue
+        c, pitch = b.in_channels, (b.in_channels + 31) // 32 * 32
+        da, db = _conv_desc(a, tuple(xa.shape)), _conv_desc(b, tuple(xb.shape))
+        ddw = _conv_desc(dw, (xa.shape[0], pitch) + tuple(xa.shape[2:]))
+        ddw.c_out = ddw.groups = pitch
+        io_dw = _conv_io(True, _reader_quant(b))
+        ok = (L.slfp_conv2d_entry_lut_supported(ctypes.byref(da), ctypes.byref(_conv_io(False, _reader_quant(dw))), 0, int(x.shape[1]), pitch)
+              and L.slfp_conv2d_exit_layerout_supported(ctypes.byref(db), ctypes.byref(_conv_io(True, None)), 0, 3, 1, pitch, 2 * b.out_channels,
+                                                        2 * b.out_channels, 1, 2)
+              and L.slfp_conv2d_codes_supported(ctypes.byref(ddw), ctypes.byref(io_dw), 0, 0))
+        if not ok:
+            continue
+        dev = a.weight.device
+        wpad = torch.zeros((pitch, 1, 3, 3), device=dev)
+        wpad[:c] = dw.weight.detach()
+        ps, psh = torch.ones(pitch, device=dev), torch.zeros(pitch, device=dev)
+        ps[:c], psh[:c] = dw._post[0], dw._post[1]
+        lut = _layerout_table(a, [], _reader_quant(dw), dev)
+        u.__dict__["_shuffle_link"] = (a, dw, b, lut, (wpad, ps, psh, {}), pitch)
+        u.__dict__["forward"] = _linked_unit_forward.__get__(u)
+        made.append(u)
+    tr.release()
+    if not made:
+        return 0
+
+    def undo():
+        for u in made:
+            _unlink_shuffle_unit(u)
+
+    return len(made) if _verified(lambda: model(example_input), y0, undo, reraise=True) else 0
+
+
+def _unlink_shuffle_unit(u):
+    for key in ("_shuffle_link", "_shuffle_handover", "forward"):
+        u.__dict__.pop(key, None)
 
 
 def _code_eligible_reader(m):

@@ -460,6 +460,41 @@ int slfp_conv2d_fwd_codes_lut(const slfp_conv2d_desc* d, const slfp_conv2d_io* i
                               int64_t y_ld, void* workspace, void* stream);
 int slfp_debug_layerout_lut_mismatches(unsigned long long* out1, void* stream);
 
+/* ---- the two 1x1 layers at the ends of a ShuffleNetV2 residual branch (csrc/conv_pw_ragged.hip) ------------------------------
+ * A branch is [1x1, BN, layerout, ReLU, dw3x3, BN, 1x1, BN, layerout, ReLU] on c = 58 / 116 / 232 channels: even, no multiple of
+ * 16.  Inside it the codes are stored at a pitch of P = round_up(c, 32) bytes per pixel with 0x00 in the padding, so the depthwise
+ * layer in the middle is an ordinary C = P code layer (zero-padded weights and BN vectors); the two 1x1 layers have one ragged,
+ * float32 side each.  Both read the layer's own slfp_conv2d_prepare_weights blob: 1x1, stride 1, groups 1, NHWC, even C_in >= 8 and
+ * even C_out, single-pass mode, and W (padded) with its tables must fit LDS (C_in <= 256; 232 -> 232 fits).
+ *
+ * slfp_conv2d_fwd_entry_lut: x is a float32 pixel row of C_in channels every x_ld floats (x_ld > C_in: a channel slice of a wider
+ * tensor, never copied; x 8-byte aligned, x_ld even).  Per output element the kernel stores
+ *     lut[class(layerout(fma(r, post_scale[c], post_shift[c])))]
+ * exactly as slfp_conv2d_fwd_codes_lut does (same table, same rules for io), at y_codes[pix * y_ld + c]; y_ld is a multiple of 32
+ * and the bytes of channels C_out .. y_ld - 1 are 0x00.  Nothing else is written.
+ *
+ * slfp_conv2d_fwd_exit_layerout: x_codes holds this layer's input codes at a pitch of x_ld bytes (a multiple of 32, >= C_in; 16-byte
+ * aligned).  `relu` takes SLFP_POST_RELU and SLFP_POST_LAYEROUT; the value of channel i is what slfp_conv2d_fwd_post stores for
+ * the decoded input, bit for bit, and goes to y[pix * y_ld + y_c0 + i * y_cs], y_cs 1 or 2.  With y_cs == 2 a `pass` operand is
+ * required: pass[pix * pass_ld + i] is copied to y[pix * y_ld + y_c0 - 1 + 2 i], in front of result i -- with y_c0 == 1 and
+ * y_ld == 2 C_out the row is channel_shuffle(cat(pass, result), 2).  y, pass: 8-byte aligned float32 slices; y_ld and the first
+ * channel written are even.  pass == NULL with y_cs == 2, and pass with y_cs == 1, are refused.
+ *
+ * The queries (host only) answer 1 / 0 and leave the reason of a 0 in slfp_last_error.  Refusals are SLFP_ERR_UNSUPPORTED; there
+ * is no fallback.  slfp_debug_pwr_instance: the kernel instance a call runs, "pwr-entry/ks<KS>/<fmt>/lut" (io: float32 in, codes
+ * out) or "pwr-exit/ks<KS>/<xw|dw>/<fmt>/<pass|f32>" (io: codes in, float32 out), "/grid<n>" under SLFP_PW_GRID; "none" where the
+ * call would be refused.  Valid until the next call on the same thread. */
+int slfp_conv2d_entry_lut_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int64_t x_ld, int64_t y_ld);
+int slfp_conv2d_fwd_entry_lut(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const float* x, int64_t x_ld, const void* wprep,
+                              const float* bias, const float* post_scale, const float* post_shift, const uint8_t* lut, void* y_codes,
+                              int64_t y_ld, void* stream);
+int slfp_conv2d_exit_layerout_supported(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_bias, int relu, int has_pass,
+                                        int64_t x_ld, int64_t pass_ld, int64_t y_ld, int64_t y_c0, int64_t y_cs);
+int slfp_conv2d_fwd_exit_layerout(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, const void* x_codes, int64_t x_ld, const void* wprep,
+                                  const float* bias, const float* post_scale, const float* post_shift, int relu, const float* pass,
+                                  int64_t pass_ld, float* y, int64_t y_ld, int64_t y_c0, int64_t y_cs, void* stream);
+const char* slfp_debug_pwr_instance(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_pass);
+
 /* ---- Image stems that read uint8 pixels ----
  * A decoded image is HWC bytes; ToTensor() + Normalize(mean, std) -- or any per-channel elementwise preprocessing -- maps byte v of
  * channel c to one of 256 float32 values, pix_table[c][v].  slfp_conv2d_fwd_u8 takes the bytes and that table.
