@@ -56,6 +56,7 @@ SYMBOLS = (
     "slfp_bn_lut_codes_train_supported", "slfp_bn_lut_codes_train_fwd",
     "slfp_conv2d_entry_lut_supported", "slfp_conv2d_fwd_entry_lut", "slfp_conv2d_exit_layerout_supported", "slfp_conv2d_fwd_exit_layerout",
     "slfp_debug_pwr_instance",
+    "slfp_conv2d_bwd_bf16_supported", "slfp_conv2d_bwd_bf16_workspace_bytes", "slfp_conv2d_bwd_bf16", "slfp_debug_bwd_bf16_instance",
 )
 
 
@@ -216,6 +217,10 @@ def load():
         "slfp_conv2d_fwd_codes_x3": (ci, [dp, ctypes.POINTER(ConvIo), vp, vp, vp, vp, vp, ci, vp, vp]),
         "slfp_debug_pwc_x3_variant": (ctypes.c_char_p, [dp, ctypes.POINTER(ConvIo)]),
         "slfp_debug_bwd_instance": (ctypes.c_char_p, [dp, ctypes.c_uint, ci, ci, ci]),
+        "slfp_conv2d_bwd_bf16_supported": (ci, [dp, ctypes.c_uint, ci]),
+        "slfp_conv2d_bwd_bf16_workspace_bytes": (sz, [dp, ctypes.c_uint, ci, ci]),
+        "slfp_conv2d_bwd_bf16": (ci, [dp, ctypes.c_uint, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "slfp_debug_bwd_bf16_instance": (ctypes.c_char_p, [dp, ctypes.c_uint, ci, ci, ci]),
     }
     assert set(sigs) == set(SYMBOLS)
     for name, (res, args) in sigs.items():

@@ -68,6 +68,9 @@ class _Options:
                                      # measurements of profiles/dwpw_codes_bench.py; dwpw_all forces every supported pair here too
     backward = "composite"           # "composite": the reference's STE composite; "hip": slfp_conv2d_bwd where it covers the layer
                                      # (3x3 depthwise, stride-1 1x1, Linear_Q); "hip_all": also the dense family (SLFP_BWD_DENSE)
+    backward_gemm = "f32"            # the matrix cores of the pointwise / Linear_Q backward under "hip" / "hip_all": "f32" (float32 MFMA);
+                                     # "bf16x3": slfp_conv2d_bwd_bf16 (an exact three-way bf16 split of every operand, the same bars)
+                                     # wherever slfp_conv2d_bwd_bf16_supported says yes, the float32 kernels everywhere else
     linear_kernel = "pointwise"      # "pointwise": Linear_Q in inference is a 1x1 convolution over the batch (slfp_linear_fwd_prepared);
                                      # "fc": the weight-streaming kernel (slfp_linear_fwd_fc) wherever slfp_linear_fc_supported
                                      # says yes -- the same bits.  A Linear_Q linked by fusion.link_head runs "fc" either way
@@ -75,12 +78,15 @@ class _Options:
     def __setattr__(self, name, value):
         if name == "backward" and value not in _BACKWARDS:
             raise ValueError(f"options.backward must be one of {_BACKWARDS}, got {value!r}")
+        if name == "backward_gemm" and value not in _BACKWARD_GEMMS:
+            raise ValueError(f"options.backward_gemm must be one of {_BACKWARD_GEMMS}, got {value!r}")
         if name == "linear_kernel" and value not in _LINEAR_KERNELS:
             raise ValueError(f"options.linear_kernel must be one of {_LINEAR_KERNELS}, got {value!r}")
         super().__setattr__(name, value)
 
 
 _BACKWARDS = ("composite", "hip", "hip_all")
+_BACKWARD_GEMMS = ("f32", "bf16x3")
 _LINEAR_KERNELS = ("pointwise", "fc")
 options = _Options()
 
@@ -710,12 +716,32 @@ def _hip_backward(mod, desc, x, w, gy, needs):
     gw = torch.empty(w.shape, dtype=torch.float32, device=x.device) if run_gw else None
     gb = torch.empty(desc.c_out, dtype=torch.float32, device=x.device) if need_gb else None
     with _on_device(x.device):
+        if _bwd_bf16(desc, flags, False):
+            _run_bwd_bf16(mod, desc, flags, x, None, w, gy, gx, gw, gb, need_gx, run_gw)
+            return gx, gw if need_gw else None, gb
         nbytes = L.slfp_conv2d_bwd_workspace_bytes_ex(ctypes.byref(desc), flags, int(need_gx), int(run_gw))
         ws = _workspace(x.device, nbytes) if nbytes else None
         _lib.check(L.slfp_conv2d_bwd_ex(ctypes.byref(desc), flags, x.data_ptr(), w.data_ptr(), gy.data_ptr(), _ptr(gx), _ptr(gw),
                                         _ptr(gb), _ptr(ws), _stream_handle(x)))
     mod._last_bwd_kernel = L.slfp_conv2d_bwd_kernel_name_ex(ctypes.byref(desc), flags).decode()
     return gx, gw if need_gw else None, gb
+
+
+def _bwd_bf16(desc, flags, x_codes):
+    """Does this backward call take slfp_conv2d_bwd_bf16 (options.backward_gemm = "bf16x3" and the library covers the layer)?"""
+    return options.backward_gemm == "bf16x3" and bool(_lib.load().slfp_conv2d_bwd_bf16_supported(ctypes.byref(desc), flags, int(x_codes)))
+
+
+def _run_bwd_bf16(mod, desc, flags, x, codes, w, gy, gx, gw, gb, need_gx, run_gw):
+    """One slfp_conv2d_bwd_bf16 call on the operands _hip_backward / _hip_backward_codes prepared (exactly one of x / codes), on the
+    current device and stream of that operand."""
+    L = _lib.load()
+    src = x if codes is None else codes
+    nbytes = L.slfp_conv2d_bwd_bf16_workspace_bytes(ctypes.byref(desc), flags, int(need_gx), int(run_gw))
+    ws = _workspace(src.device, nbytes) if nbytes else None
+    _lib.check(L.slfp_conv2d_bwd_bf16(ctypes.byref(desc), flags, _ptr(x), _ptr(codes), w.data_ptr(), gy.data_ptr(), _ptr(gx), _ptr(gw),
+                                      _ptr(gb), _ptr(ws), _stream_handle(src)))
+    mod._last_bwd_kernel = "pw_bwd_mfma_bf16x3"
 
 
 def _bwd_flags():
@@ -776,6 +802,9 @@ def _hip_backward_codes(mod, desc, codes, w, gy, needs):
     gw = torch.empty(w.shape, dtype=torch.float32, device=codes.device) if run_gw else None
     gb = torch.empty(desc.c_out, dtype=torch.float32, device=codes.device) if need_gb else None
     with _on_device(codes.device):
+        if _bwd_bf16(desc, flags, True):
+            _run_bwd_bf16(mod, desc, flags, None, codes, w, gy, gx, gw, gb, need_gx, run_gw)
+            return gx, gw if need_gw else None, gb
         nbytes = L.slfp_conv2d_bwd_workspace_bytes_ex(ctypes.byref(desc), flags, int(need_gx), int(run_gw))
         ws = _workspace(codes.device, nbytes) if nbytes else None
         _lib.check(L.slfp_conv2d_bwd_codes(ctypes.byref(desc), flags, codes.data_ptr(), w.data_ptr(), gy.data_ptr(), _ptr(gx), _ptr(gw),

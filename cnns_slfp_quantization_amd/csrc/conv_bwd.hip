@@ -28,6 +28,7 @@
 #include "slfp_enc.hpp"
 #include "slfp_codes.hpp"
 #include "slfp_host.hpp"
+#include "conv_bwd_shared.hpp"
 #include <cstdio>
 #include <type_traits>
 
@@ -715,6 +716,8 @@ static BwdKind bwd_kind(const slfp_conv2d_desc& d) {
     return kBwdNone;
 }
 
+bool bwd_is_pw(const slfp_conv2d_desc& d) { return bwd_kind(d) == kBwdPw; }
+
 // The dense family (SLFP_BWD_DENSE) takes what bwd_kind leaves: groups 1, dilation 1, any kernel size / stride / padding.
 static bool dense_ok(const slfp_conv2d_desc& d, const ConvPlan& p) {
     if (d.groups != 1 || d.dil_h != 1 || d.dil_w != 1) return false;
@@ -755,17 +758,14 @@ static int dw_blocks(const DwGeom& g) {
     return (int)(pb < 1 ? 1 : pb);
 }
 
-// The split of a GW contraction over its M rows: ~8 workgroups per CU, at least 256 rows per split, partials (cout x ncol
-// and the cout bias sums per split) within kPartCapFloats, at most kMaxParts splits of whole k-steps.
-struct GwSplit {
-    int splits, kps;
-};
+// The split of a GW contraction over its M rows (GwSplit, conv_bwd_shared.hpp): ~8 workgroups per CU, at least 256 rows per split,
+// partials (cout x ncol and the cout bias sums per split) within kPartCapFloats, at most kMaxParts splits of whole k-steps.
 
 // Whole float4 groups of channels on both sides: what the VEC instances need of the shape (the pointers' 16-byte alignment is
 // checked at the entry points).
 static bool chan_vec(const slfp_conv2d_desc& d) { return d.c_in % 4 == 0 && d.c_out % 4 == 0; }
 
-static GwSplit gw_split(int64_t M, int64_t cout, int64_t ncol, int64_t tiles) {
+GwSplit gw_split(int64_t M, int64_t cout, int64_t ncol, int64_t tiles) {
     int64_t sp = ceil_div(8 * kBwdCUs, tiles);
     sp = std::min<int64_t>(sp, std::max<int64_t>(1, M / 256));
     sp = std::min<int64_t>(sp, std::max<int64_t>(1, kPartCapFloats / (cout * ncol + cout)));
@@ -932,7 +932,7 @@ static void launch_dense_gw(const DenseGeom& g, const DenseShape& s, hipStream_t
     else with_1_or_2(s.tm_w, [&](auto TM) { with_1_or_2(s.tn_w, [&](auto TN) { go(TM, TN, std::true_type{}); }); });
 }
 
-static int reduce_parts(hipStream_t st, const float* part, int P, int64_t ncols, float scale, int dwC, int Cin, int T, float* gw,
+int reduce_parts(hipStream_t st, const float* part, int P, int64_t ncols, float scale, int dwC, int Cin, int T, float* gw,
                         float* gb) {
     hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)ceil_div(ncols, kRedCols)), dim3(kRedCols * kRedRows), 0, st, part, P, ncols,
                        scale, dwC, Cin, T, gw, gb);
@@ -940,7 +940,7 @@ static int reduce_parts(hipStream_t st, const float* part, int P, int64_t ncols,
 }
 
 // gb[co] = sum over the splits of the GW kernels' bias partials
-static int reduce_gb(hipStream_t st, const float* gbpart, int splits, int64_t cout, float* gb) {
+int reduce_gb(hipStream_t st, const float* gbpart, int splits, int64_t cout, float* gb) {
     return reduce_parts(st, gbpart, splits, cout, 1.0f, 0, 0, 0, gb, nullptr);
 }
 

@@ -1,0 +1,23 @@
+// conv_bwd_shared.hpp -- what conv_bwd.hip lends the other backward translation units (conv_bwd_bf16.hip): the family test,
+// the split rule of a weight-gradient contraction and the fixed-order reduction of its partials.  Defined in conv_bwd.hip.
+#pragma once
+#include "slfp_host.hpp"
+
+namespace slfp {
+
+// stride-1 pad-0 groups-1 1x1 layers (a Linear_Q is one with h = w = 1): the `pw` family of bwd_kind
+bool bwd_is_pw(const slfp_conv2d_desc& d);
+
+// The split of a GW contraction over its M rows: ~8 workgroups per CU, at least 256 rows per split, partials (cout x ncol
+// and the cout bias sums per split) within 32 MiB, at most 1024 splits, each a whole number of 16-row k-steps.
+struct GwSplit {
+    int splits, kps;
+};
+GwSplit gw_split(int64_t M, int64_t cout, int64_t ncol, int64_t tiles);
+
+// k_reduce_parts: gw[col] = scale * sum_p part[p][col] in a fixed order (dwC, Cin, T: the depthwise / dense output layouts; 0 here)
+int reduce_parts(hipStream_t st, const float* part, int P, int64_t ncols, float scale, int dwC, int Cin, int T, float* gw, float* gb);
+// gb[co] = sum over the splits of the GW kernels' bias partials
+int reduce_gb(hipStream_t st, const float* gbpart, int splits, int64_t cout, float* gb);
+
+}  // namespace slfp

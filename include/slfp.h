@@ -951,6 +951,34 @@ int slfp_conv2d_bwd_codes(const slfp_conv2d_desc* d, unsigned flags, const uint8
  * Host only: no device is touched.  The pointer stays valid until the next call on the same thread. */
 const char* slfp_debug_bwd_instance(const slfp_conv2d_desc* d, unsigned flags, int x_codes, int need_gx, int need_gw);
 
+/* The pointwise family ("pw_bwd_mfma_f32": stride-1 1x1 layers, Linear_Q) a second time, on the bf16 matrix cores
+ * (csrc/conv_bwd_bf16.hip; kernel name "pw_bwd_mfma_bf16x3").  Every float32 operand is split exactly into three bf16 pieces on its
+ * way into LDS and the six piece products of order <= 2 are accumulated in float32 by v_mfma_f32_32x32x16_bf16: each product is
+ * exact and what is dropped is below 2 * 2^-24 |g||x| per product, so the gradients hold the bars of the float32 kernels (they are
+ * not bit-equal to them: the sums associate differently).  Same semantics as slfp_conv2d_bwd_ex / slfp_conv2d_bwd_codes: xq is
+ * encoded on load (threshold table) or decoded from its codes, gw is split over N*H*W and reduced in a fixed order, no atomics:
+ * two calls give equal bits.  Opt-in: nothing else calls it.  Exactly one of x (float32) and x_codes (as slfp_conv2d_bwd_codes)
+ * is non-NULL, also when gw is not asked for (SLFP_ERR_BAD_ARG otherwise, checked behind the flag bits); the other argument checks
+ * are those of slfp_conv2d_bwd_ex, in its order, before any device work.  `flags` means what it means there: SLFP_BWD_DENSE is
+ * accepted, and the dense layers it would add are refused here.  Supported (slfp_conv2d_bwd_bf16_supported: 1 / 0, the reason of a
+ * 0 in slfp_last_error; host only): the pw family, x and y NHWC, C_in and C_out multiples of 8, qbits 8 or 7, N*H*W < 2^31, and
+ * with float32 x a proven threshold table for Ka; not the two classes measured no faster than the float32 kernels (DESIGN.md
+ * section 44): N*H*W < 512 under a weight of more than 2^24 elements, and min(C_in, C_out) <= 64 with max(C_in, C_out) >= 128 at
+ * N*H*W >= 65536.  The workspace query takes no x_codes: it answers for both operand forms and does not depend on the table.  Everything else is SLFP_ERR_UNSUPPORTED -- the library never falls back to the
+ * float32 kernels by itself.  Workspace: slfp_conv2d_bwd_bf16_workspace_bytes (0 where unsupported), 16-byte aligned.
+ * Differences to the float32 kernels: an inf in gy splits into (inf, NaN, NaN), so an output they make +-inf can be NaN here (the
+ * set of non-finite elements is the same); pieces below 2^-126 may be flushed by the matrix unit; gb is a float32 VALU sum.
+ * slfp_debug_bwd_bf16_instance: what the launch is sized by, printed from the selection it consumes (host only; valid until the
+ * next call on the same thread):
+ *   pwb/gx/tm<1|2>tn<1|2>/t6                               k_bf16_gemm<TM, TN, false, ..>: 64 TM x 64 TN workgroup tiles, six terms
+ *   pwb/gw/tm<1|2>tn<1|2>/t6/<tab|codes>/p<splits>k<kps>   k_bf16_gemm<TM, TN, true, ..>: x through the table or as codes; the splits
+ * joined by "+" when both are asked for; "none" where the entry point refuses or nothing is asked for. */
+int slfp_conv2d_bwd_bf16_supported(const slfp_conv2d_desc* d, unsigned flags, int x_codes);
+size_t slfp_conv2d_bwd_bf16_workspace_bytes(const slfp_conv2d_desc* d, unsigned flags, int need_gx, int need_gw);
+int slfp_conv2d_bwd_bf16(const slfp_conv2d_desc* d, unsigned flags, const float* x, const uint8_t* x_codes, const float* w_oihw,
+                         const float* gy, float* gx, float* gw_oihw, float* gb, void* workspace, void* stream);
+const char* slfp_debug_bwd_bf16_instance(const slfp_conv2d_desc* d, unsigned flags, int x_codes, int need_gx, int need_gw);
+
 /* ---- layout helpers (the reference is NCHW; the kernels are NHWC) -------------------- */
 int slfp_nchw_to_nhwc_f32(const float* x, float* y, int64_t n, int64_t c, int64_t h, int64_t w, void* stream);
 int slfp_nhwc_to_nchw_f32(const float* x, float* y, int64_t n, int64_t c, int64_t h, int64_t w, void* stream);
