@@ -57,6 +57,8 @@ SYMBOLS = (
     "slfp_conv2d_entry_lut_supported", "slfp_conv2d_fwd_entry_lut", "slfp_conv2d_exit_layerout_supported", "slfp_conv2d_fwd_exit_layerout",
     "slfp_debug_pwr_instance",
     "slfp_conv2d_bwd_bf16_supported", "slfp_conv2d_bwd_bf16_workspace_bytes", "slfp_conv2d_bwd_bf16", "slfp_debug_bwd_bf16_instance",
+    "slfp_conv2d_bwd_dense_bf16_supported", "slfp_conv2d_bwd_dense_bf16_workspace_bytes", "slfp_conv2d_bwd_dense_bf16",
+    "slfp_debug_bwd_dense_bf16_instance",
 )
 
 
@@ -221,6 +223,10 @@ def load():
         "slfp_conv2d_bwd_bf16_workspace_bytes": (sz, [dp, ctypes.c_uint, ci, ci]),
         "slfp_conv2d_bwd_bf16": (ci, [dp, ctypes.c_uint, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "slfp_debug_bwd_bf16_instance": (ctypes.c_char_p, [dp, ctypes.c_uint, ci, ci, ci]),
+        "slfp_conv2d_bwd_dense_bf16_supported": (ci, [dp, ctypes.c_uint, ci]),
+        "slfp_conv2d_bwd_dense_bf16_workspace_bytes": (sz, [dp, ctypes.c_uint, ci, ci]),
+        "slfp_conv2d_bwd_dense_bf16": (ci, [dp, ctypes.c_uint, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "slfp_debug_bwd_dense_bf16_instance": (ctypes.c_char_p, [dp, ctypes.c_uint, ci, ci, ci]),
     }
     assert set(sigs) == set(SYMBOLS)
     for name, (res, args) in sigs.items():

@@ -70,7 +70,9 @@ class _Options:
                                      # (3x3 depthwise, stride-1 1x1, Linear_Q); "hip_all": also the dense family (SLFP_BWD_DENSE)
     backward_gemm = "f32"            # the matrix cores of the pointwise / Linear_Q backward under "hip" / "hip_all": "f32" (float32 MFMA);
                                      # "bf16x3": slfp_conv2d_bwd_bf16 (an exact three-way bf16 split of every operand, the same bars)
-                                     # wherever slfp_conv2d_bwd_bf16_supported says yes, the float32 kernels everywhere else
+                                     # wherever slfp_conv2d_bwd_bf16_supported says yes, the float32 kernels everywhere else;
+                                     # "bf16x3_all": "bf16x3", and under "hip_all" also the dense family on the same split
+                                     # (slfp_conv2d_bwd_dense_bf16) wherever slfp_conv2d_bwd_dense_bf16_supported says yes
     linear_kernel = "pointwise"      # "pointwise": Linear_Q in inference is a 1x1 convolution over the batch (slfp_linear_fwd_prepared);
                                      # "fc": the weight-streaming kernel (slfp_linear_fwd_fc) wherever slfp_linear_fc_supported
                                      # says yes -- the same bits.  A Linear_Q linked by fusion.link_head runs "fc" either way
@@ -86,7 +88,7 @@ class _Options:
 
 
 _BACKWARDS = ("composite", "hip", "hip_all")
-_BACKWARD_GEMMS = ("f32", "bf16x3")
+_BACKWARD_GEMMS = ("f32", "bf16x3", "bf16x3_all")
 _LINEAR_KERNELS = ("pointwise", "fc")
 options = _Options()
 
@@ -716,8 +718,9 @@ def _hip_backward(mod, desc, x, w, gy, needs):
     gw = torch.empty(w.shape, dtype=torch.float32, device=x.device) if run_gw else None
     gb = torch.empty(desc.c_out, dtype=torch.float32, device=x.device) if need_gb else None
     with _on_device(x.device):
-        if _bwd_bf16(desc, flags, False):
-            _run_bwd_bf16(mod, desc, flags, x, None, w, gy, gx, gw, gb, need_gx, run_gw)
+        family = _bwd_bf16(desc, flags, False)
+        if family:
+            _run_bwd_bf16(mod, family, desc, flags, x, None, w, gy, gx, gw, gb, need_gx, run_gw)
             return gx, gw if need_gw else None, gb
         nbytes = L.slfp_conv2d_bwd_workspace_bytes_ex(ctypes.byref(desc), flags, int(need_gx), int(run_gw))
         ws = _workspace(x.device, nbytes) if nbytes else None
@@ -728,20 +731,31 @@ def _hip_backward(mod, desc, x, w, gy, needs):
 
 
 def _bwd_bf16(desc, flags, x_codes):
-    """Does this backward call take slfp_conv2d_bwd_bf16 (options.backward_gemm = "bf16x3" and the library covers the layer)?"""
-    return options.backward_gemm == "bf16x3" and bool(_lib.load().slfp_conv2d_bwd_bf16_supported(ctypes.byref(desc), flags, int(x_codes)))
+    """The bf16x3 entry-point family this backward call takes under options.backward_gemm, or None (the float32 kernels): "pw" where
+    slfp_conv2d_bwd_bf16 covers the layer ("bf16x3", "bf16x3_all"), "dense" where slfp_conv2d_bwd_dense_bf16 does ("bf16x3_all";
+    the library asks for SLFP_BWD_DENSE in `flags`, that is options.backward = "hip_all")."""
+    if options.backward_gemm == "f32":
+        return None
+    L = _lib.load()
+    if L.slfp_conv2d_bwd_bf16_supported(ctypes.byref(desc), flags, int(x_codes)):
+        return "pw"
+    if options.backward_gemm == "bf16x3_all" and L.slfp_conv2d_bwd_dense_bf16_supported(ctypes.byref(desc), flags, int(x_codes)):
+        return "dense"
+    return None
 
 
-def _run_bwd_bf16(mod, desc, flags, x, codes, w, gy, gx, gw, gb, need_gx, run_gw):
-    """One slfp_conv2d_bwd_bf16 call on the operands _hip_backward / _hip_backward_codes prepared (exactly one of x / codes), on the
-    current device and stream of that operand."""
+def _run_bwd_bf16(mod, family, desc, flags, x, codes, w, gy, gx, gw, gb, need_gx, run_gw):
+    """One slfp_conv2d_bwd_bf16 ("pw") or slfp_conv2d_bwd_dense_bf16 ("dense") call on the operands _hip_backward /
+    _hip_backward_codes prepared (exactly one of x / codes), on the current device and stream of that operand."""
     L = _lib.load()
     src = x if codes is None else codes
-    nbytes = L.slfp_conv2d_bwd_bf16_workspace_bytes(ctypes.byref(desc), flags, int(need_gx), int(run_gw))
+    size, run = ((L.slfp_conv2d_bwd_bf16_workspace_bytes, L.slfp_conv2d_bwd_bf16) if family == "pw" else
+                 (L.slfp_conv2d_bwd_dense_bf16_workspace_bytes, L.slfp_conv2d_bwd_dense_bf16))
+    nbytes = size(ctypes.byref(desc), flags, int(need_gx), int(run_gw))
     ws = _workspace(src.device, nbytes) if nbytes else None
-    _lib.check(L.slfp_conv2d_bwd_bf16(ctypes.byref(desc), flags, _ptr(x), _ptr(codes), w.data_ptr(), gy.data_ptr(), _ptr(gx), _ptr(gw),
-                                      _ptr(gb), _ptr(ws), _stream_handle(src)))
-    mod._last_bwd_kernel = "pw_bwd_mfma_bf16x3"
+    _lib.check(run(ctypes.byref(desc), flags, _ptr(x), _ptr(codes), w.data_ptr(), gy.data_ptr(), _ptr(gx), _ptr(gw), _ptr(gb), _ptr(ws),
+                   _stream_handle(src)))
+    mod._last_bwd_kernel = f"{family}_bwd_mfma_bf16x3"
 
 
 def _bwd_flags():
@@ -802,8 +816,9 @@ def _hip_backward_codes(mod, desc, codes, w, gy, needs):
     gw = torch.empty(w.shape, dtype=torch.float32, device=codes.device) if run_gw else None
     gb = torch.empty(desc.c_out, dtype=torch.float32, device=codes.device) if need_gb else None
     with _on_device(codes.device):
-        if _bwd_bf16(desc, flags, True):
-            _run_bwd_bf16(mod, desc, flags, None, codes, w, gy, gx, gw, gb, need_gx, run_gw)
+        family = _bwd_bf16(desc, flags, True)
+        if family:
+            _run_bwd_bf16(mod, family, desc, flags, None, codes, w, gy, gx, gw, gb, need_gx, run_gw)
             return gx, gw if need_gw else None, gb
         nbytes = L.slfp_conv2d_bwd_workspace_bytes_ex(ctypes.byref(desc), flags, int(need_gx), int(run_gw))
         ws = _workspace(codes.device, nbytes) if nbytes else None

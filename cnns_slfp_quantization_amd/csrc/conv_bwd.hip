@@ -509,15 +509,7 @@ __global__ __launch_bounds__(256) void k_gemm_f32(const GemmArgs ga, const EncAr
 // k_dense_gw: GWp[z][co][(tap,ci)] = sum_{m=(n,ho,wo) in split z} GY[m][co] * QA(X[n, ho*stride_h-pad_h+kh, wo*stride_w-pad_w+kw, ci]/Ka),
 // xq encoded on load as in k_gemm_f32 (never materialised), which it differs from in the B-tile gather only;
 // k_reduce_parts adds the splits in a fixed order, applies Ka and writes OIHW.
-struct DenseGeom {
-    int N, H, W, Cin, Ho, Wo, Cout, KH, KW, sh, sw, padh, padw;
-};
-
-// rows (input pixels) of phase (a, b): n x ceil((H - a) / sh) x ceil((W - b) / sw)
-__host__ __device__ __forceinline__ int dense_phase_extent(int extent, int phase, int stride) {
-    return (extent - phase + stride - 1) / stride;
-}
-
+// (DenseGeom and dense_phase_extent: conv_bwd_shared.hpp)
 struct TapStep { int t, c0; };   // a k-step of k_dense_gx: BK output channels from c0 of tap t
 
 template <int TN, bool VEC>
@@ -731,6 +723,8 @@ static BwdKind bwd_kind_ex(const slfp_conv2d_desc& d, const ConvPlan& p, unsigne
     return k;
 }
 
+bool bwd_is_dense(const slfp_conv2d_desc& d, const ConvPlan& p, unsigned flags) { return bwd_kind_ex(d, p, flags) == kBwdDense; }
+
 static size_t r256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // The split choices depend on the shape only (not on the device), so that the workspace size is a pure function of the
@@ -817,13 +811,13 @@ static DenseShape dense_shape(const slfp_conv2d_desc& d, const ConvPlan& p) {
     return s;
 }
 
-static DenseGeom dense_geom(const slfp_conv2d_desc& d, const ConvPlan& p) {
+DenseGeom dense_geom(const slfp_conv2d_desc& d, const ConvPlan& p) {
     return DenseGeom{(int)d.n, (int)d.h, (int)d.w, (int)d.c_in, (int)p.h_out, (int)p.w_out, (int)d.c_out, (int)d.kh, (int)d.kw,
                      (int)d.stride_h, (int)d.stride_w, (int)d.pad_h, (int)d.pad_w};
 }
 
 // workgroups of k_dense_gx along x: the 128-row tiles of every (h mod stride_h, w mod stride_w) phase
-static int64_t dense_gx_tiles(const DenseGeom& g) {
+int64_t dense_gx_tiles(const DenseGeom& g) {
     int64_t tiles = 0;
     for (int a = 0; a < g.sh; ++a)
         for (int b = 0; b < g.sw; ++b)

@@ -979,6 +979,33 @@ int slfp_conv2d_bwd_bf16(const slfp_conv2d_desc* d, unsigned flags, const float*
                          const float* gy, float* gx, float* gw_oihw, float* gb, void* workspace, void* stream);
 const char* slfp_debug_bwd_bf16_instance(const slfp_conv2d_desc* d, unsigned flags, int x_codes, int need_gx, int need_gw);
 
+/* The dense family of slfp_conv2d_bwd_ex under SLFP_BWD_DENSE ("dense_bwd_mfma_f32": groups 1, dilation 1, any kernel size / stride /
+ * padding that is neither the pw family nor the depthwise 3x3) a second time, on the bf16 matrix cores with the exact three-way
+ * split of slfp_conv2d_bwd_bf16 (csrc/conv_bwd_dense_bf16.hip; kernel name "dense_bwd_mfma_bf16x3").  The
+ * arithmetic, the semantics (xq encoded on load through the threshold table or decoded from its codes, gw split over N*Ho*Wo and
+ * reduced in a fixed order into OIHW, no atomics: two calls give equal bits), the arguments and the order of the argument checks
+ * are those of slfp_conv2d_bwd_bf16.  Opt-in: nothing else calls it.  Supported (slfp_conv2d_bwd_dense_bf16_supported: 1 / 0, the
+ * reason of a 0 in slfp_last_error; host only): the layer is the dense family of slfp_conv2d_bwd_ex under `flags` & SLFP_BWD_DENSE
+ * (without the flag dense layers are refused; the pw and depthwise families are refused here, they have their own entry points),
+ * x and y NHWC, C_in and C_out multiples of 8 (so not the C_in = 3 stems), qbits 8 or 7, dense_ok's 32-bit limits (with N*Ho*Wo
+ * below 2^31 - 256, taps * C_in within 65535 * 64 and C_out within 65535 * 32: one k-step past the last row and the grids), and with
+ * float32 x a proven threshold table for Ka.  No geometry class is refused for its speed: every measured layer (the dense layers
+ * of VGG-16, ResNet-50, SqueezeNet and AlexNet at batch 128) is faster than the float32 dense kernels beyond both legs' spread
+ * (1.19-1.77x), so no bound is stated.  Everything else is SLFP_ERR_UNSUPPORTED, decided before any device work -- the
+ * library never falls back by itself.  Workspace: slfp_conv2d_bwd_dense_bf16_workspace_bytes (0 where unsupported; takes no x_codes
+ * and does not depend on the table), 16-byte aligned.  Differences to the float32 kernels: those of slfp_conv2d_bwd_bf16 (an inf in
+ * gy can give NaN where they give +-inf, the set of non-finite elements is the same where no padding zero meets the inf; pieces
+ * below 2^-126 may be flushed; not bit-equal).
+ * slfp_debug_bwd_dense_bf16_instance (host only; valid until the next call on the same thread):
+ *   dnb/gx/tn<1|2>/t6                                      k_dense_gx_bf16<TN>: 128 x 64 TN workgroup tiles inside one stride phase
+ *   dnb/gw/tm<1|2>tn<1|2>/t6/<tab|codes>/p<splits>k<kps>   k_bf16_gemm<TM, TN, true, .., Bf16DenseArgs>: columns (tap, ci), rows m
+ * joined by "+" when both are asked for; "none" where the entry point refuses or nothing is asked for. */
+int slfp_conv2d_bwd_dense_bf16_supported(const slfp_conv2d_desc* d, unsigned flags, int x_codes);
+size_t slfp_conv2d_bwd_dense_bf16_workspace_bytes(const slfp_conv2d_desc* d, unsigned flags, int need_gx, int need_gw);
+int slfp_conv2d_bwd_dense_bf16(const slfp_conv2d_desc* d, unsigned flags, const float* x, const uint8_t* x_codes, const float* w_oihw,
+                               const float* gy, float* gx, float* gw_oihw, float* gb, void* workspace, void* stream);
+const char* slfp_debug_bwd_dense_bf16_instance(const slfp_conv2d_desc* d, unsigned flags, int x_codes, int need_gx, int need_gw);
+
 /* ---- layout helpers (the reference is NCHW; the kernels are NHWC) -------------------- */
 int slfp_nchw_to_nhwc_f32(const float* x, float* y, int64_t n, int64_t c, int64_t h, int64_t w, void* stream);
 int slfp_nhwc_to_nchw_f32(const float* x, float* y, int64_t n, int64_t c, int64_t h, int64_t w, void* stream);
