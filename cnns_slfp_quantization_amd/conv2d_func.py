@@ -76,6 +76,8 @@ class _Options:
     linear_kernel = "pointwise"      # "pointwise": Linear_Q in inference is a 1x1 convolution over the batch (slfp_linear_fwd_prepared);
                                      # "fc": the weight-streaming kernel (slfp_linear_fwd_fc) wherever slfp_linear_fc_supported
                                      # says yes -- the same bits.  A Linear_Q linked by fusion.link_head runs "fc" either way
+    dilated = "direct"               # dilated dense Conv2d_Q layers: "direct" (the float32 direct kernel); "mfma": the phase-tiled
+                                     # matrix-core kernel (SLFP_DESC_DILATED_MFMA) wherever the library takes the layer
 
     def __setattr__(self, name, value):
         if name == "backward" and value not in _BACKWARDS:
@@ -84,12 +86,15 @@ class _Options:
             raise ValueError(f"options.backward_gemm must be one of {_BACKWARD_GEMMS}, got {value!r}")
         if name == "linear_kernel" and value not in _LINEAR_KERNELS:
             raise ValueError(f"options.linear_kernel must be one of {_LINEAR_KERNELS}, got {value!r}")
+        if name == "dilated" and value not in _DILATEDS:
+            raise ValueError(f"options.dilated must be one of {_DILATEDS}, got {value!r}")
         super().__setattr__(name, value)
 
 
 _BACKWARDS = ("composite", "hip", "hip_all")
 _BACKWARD_GEMMS = ("f32", "bf16x3", "bf16x3_all")
 _LINEAR_KERNELS = ("pointwise", "fc")
+_DILATEDS = ("direct", "mfma")
 options = _Options()
 
 
@@ -148,7 +153,8 @@ def _conv_desc(mod, shape, nhwc_in=True, nhwc_out=True, fp8=False):
                          x_layout=_lib.LAYOUT_NHWC if nhwc_in else _lib.LAYOUT_NCHW,
                          y_layout=_lib.LAYOUT_NHWC if nhwc_out else _lib.LAYOUT_NCHW,
                          qbits=mod.q_bit, ka=_f32(_scalar_scale(mod.Ka, "Ka")), kw_scale=_f32(_scalar_scale(mod.Kw, "Kw")),
-                         mfma_passes=_lib.MFMA_FP8 if fp8 else options.mfma_passes, reserved=0)
+                         mfma_passes=_lib.MFMA_FP8 if fp8 else options.mfma_passes,
+                         reserved=_lib.DESC_DILATED_MFMA if options.dilated == "mfma" else 0)
 
 
 def _conv_io(x_codes, out):
@@ -310,7 +316,7 @@ def _plan(mod, x, weight, nhwc_in, nhwc_out, codes=None):
     # own, so the prepared-weight cache never mixes the two blobs of one weight); every other form keeps the module's usual one
     fp8 = bool(getattr(mod, "_fp8", False) and codes is not None and codes[0] in _FP8_KINDS and codes[1])
     key = (codes, shape, nhwc_in, nhwc_out, _scale_key(mod.Ka, "Ka"), _scale_key(mod.Kw, "Kw"), options.mfma_passes, fp8,
-           mod.stride, mod.padding, mod.dilation, weight.shape)
+           mod.stride, mod.padding, mod.dilation, weight.shape, options.dilated)
     plan = mod._plans.get(key) if options.plan_cache else None
     if plan is None:
         L = _lib.load()

@@ -28,6 +28,7 @@ static int make_plan_core(const slfp_conv2d_desc* d, ConvPlan* plan) {
     if (!(d->ka > 0.f) || !(d->kw_scale > 0.f)) return fail(SLFP_ERR_BAD_ARG, "conv2d: Ka and Kw must be > 0");
     if (!scale_div_ok(d->ka) || !scale_div_ok(d->kw_scale))
         return fail(SLFP_ERR_UNSUPPORTED, "conv2d: Ka and Kw must be within [1e-30, 1e30]");
+    if (d->reserved & ~SLFP_DESC_DILATED_MFMA) return fail(SLFP_ERR_BAD_ARG, "conv2d: unknown bits in `reserved` (SLFP_DESC_*)");
     if (d->mfma_passes == SLFP_MFMA_FP8)   // make_plan(fp8_ok) plans such a descriptor in the default mode first
         return fail(SLFP_ERR_UNSUPPORTED, "conv2d: SLFP_MFMA_FP8 (E4M3 operands) serves weight preparation and slfp_conv2d_fwd_codes[_slice] only");
     if (d->mfma_passes != SLFP_MFMA_DEFAULT && d->mfma_passes != SLFP_MFMA_F16X1 && d->mfma_passes != SLFP_MFMA_F16X3)
@@ -81,6 +82,11 @@ static int make_plan_core(const slfp_conv2d_desc* d, ConvPlan* plan) {
         plan->n_pad = ceil_div(d->c_out, 16) * 16;
         // one fp16 plane, plus the residual plane in float32-equivalent mode
         plan->wprep_bytes = round256((size_t)(plan->passes == 3 ? 2 : 1) * d->kh * d->kw * plan->k_pad * plan->n_pad * sizeof(_Float16));
+    } else if ((d->reserved & SLFP_DESC_DILATED_MFMA) && dense_dil_applicable(*d, plan->passes)) {
+        plan->family = kDenseDil;   // opt-in; the dense family's blob (one plane)
+        plan->k_pad = ceil_div(d->c_in, 64) * 64;
+        plan->n_pad = ceil_div(d->c_out, 16) * 16;
+        plan->wprep_bytes = round256((size_t)d->kh * d->kw * plan->k_pad * plan->n_pad * sizeof(_Float16));
     } else {
         plan->family = kDirect;
         plan->wprep_bytes = round256((size_t)d->kh * d->kw * cg * d->c_out * sizeof(float));
@@ -234,7 +240,8 @@ int launch_prepare_weights(const slfp_conv2d_desc& d, const ConvPlan& p, const f
                            float* weight_q_oihw, hipStream_t stream, bool codes) {
     const int Cg = (int)(d.c_in / d.groups);
     const int64_t total = d.c_out * Cg * d.kh * d.kw;
-    if (p.family == kPointwise || p.family == kDenseMfma || p.family == kStemMfma || p.family == kStemSmall || p.repad) {
+    const bool dense_blob = p.family == kDenseMfma || p.family == kDenseDil;   // conv_dense_dil.hip reads conv_dense.hip's blob
+    if (p.family == kPointwise || dense_blob || p.family == kStemMfma || p.family == kStemSmall || p.repad) {
         if (hipMemsetAsync(wprep, 0, p.wprep_bytes, stream) != hipSuccess) return check_launch("hipMemsetAsync(wprep)");
     }
     const int64_t plane = p.family == kStemMfma ? p.n_pad : p.k_pad * p.n_pad;
@@ -242,9 +249,9 @@ int launch_prepare_weights(const slfp_conv2d_desc& d, const ConvPlan& p, const f
     const unsigned grid = (unsigned)ceil_div(total, 256);
     const ScaleDiv sd = make_scale_div(d.kw_scale);
     // depthwise: row pitch of the [9][C] table (padded channel count); dense MFMA: 1 = also write the residual plane
-    const int ldo = p.family == kDenseMfma ? (p.passes == 3 ? 1 : 0) : (int)p.cpo;
+    const int ldo = dense_blob ? (p.passes == 3 ? 1 : 0) : (int)p.cpo;
 #define SLFP_PREP(FF, CC) hipLaunchKernelGGL((k_prepare<FF, CC>), dim3(grid), dim3(256), 0, stream, w_oihw, wprep, weight_q_oihw, total, \
-                                             (int)d.c_out, Cg, (int)d.kh, (int)d.kw, sd, (int)p.family, KS, plane, ldo)
+                                             (int)d.c_out, Cg, (int)d.kh, (int)d.kw, sd, dense_blob ? (int)kDenseMfma : (int)p.family, KS, plane, ldo)
     if (p.fmt_w == kFmtW8) { if (codes) SLFP_PREP(kFmtW8, true); else SLFP_PREP(kFmtW8, false); }
     else { if (codes) SLFP_PREP(kFmtSfp7, true); else SLFP_PREP(kFmtSfp7, false); }
 #undef SLFP_PREP
@@ -262,6 +269,7 @@ static const char* family_name(const ConvPlan& p, const slfp_conv2d_desc& d) {
         case kDw3x3: return "dw3x3_nhwc";
         case kPointwise: return p.fmt_act == kFmtSfp7 ? "pw_mfma_f16_exact" : (p.passes == 3 ? "pw_mfma_f16x3" : "pw_mfma_f16x1");
         case kDenseMfma: return p.fmt_act == kFmtSfp7 ? "dense_mfma_f16_exact" : (p.passes == 3 ? "dense_mfma_f16x3" : "dense_mfma_f16x1");
+        case kDenseDil: return p.fmt_act == kFmtSfp7 ? "dense_dil_mfma_f16_exact" : "dense_dil_mfma_f16x1";
         case kStemMfma: return p.fmt_act == kFmtSfp7 ? "stem_mfma_f16_exact" : "stem_mfma_f16x1";
         case kStemSmall: return p.fmt_act == kFmtSfp7 ? "stem_small_mfma_f16_exact" : "stem_small_mfma_f16x1";
         default: return "direct_nhwc";
@@ -316,6 +324,12 @@ const char* slfp_debug_dense_variant(const slfp_conv2d_desc* d, int x_codes) {
     return dense_variant_name(*d, p, x_codes != 0);
 }
 
+const char* slfp_debug_dense_dil_variant(const slfp_conv2d_desc* d) {
+    ConvPlan p;
+    if (make_plan(d, &p) != SLFP_OK) return "none";
+    return dense_dil_variant_name(*d, p);
+}
+
 const char* slfp_debug_pw_variant(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_res, int has_res_codes, int64_t y_ld) {
     return pw_variant(d, io, has_res != 0, has_res_codes != 0, y_ld);
 }
@@ -366,7 +380,7 @@ static WsLayout ws_layout(const slfp_conv2d_desc* d, const ConvPlan& p) {
     l.x_nhwc = take(d->x_layout == SLFP_LAYOUT_NCHW, round256((size_t)d->n * d->c_in * d->h * d->w * sizeof(float)));
     l.y_nhwc = take(d->y_layout == SLFP_LAYOUT_NCHW, round256((size_t)d->n * d->c_out * p.h_out * p.w_out * sizeof(float)));
     l.operand = at;
-    if (p.family == kDenseMfma) at += dense_mfma_workspace_bytes(*d, p.passes);
+    if (p.family == kDenseMfma || p.family == kDenseDil) at += dense_mfma_workspace_bytes(*d, p.passes);
     if (p.family == kStemMfma) at += stem_mfma_workspace_bytes(*d, p.w_out);
     l.x_pad = take(p.repad && p.cpi != d->c_in, round256((size_t)d->n * d->h * d->w * p.cpi * sizeof(float)));
     l.y_pad = take(p.repad && p.cpo != d->c_out, round256((size_t)d->n * p.h_out * p.w_out * p.cpo * sizeof(float)));
@@ -797,6 +811,7 @@ int slfp_conv2d_fwd_post(const slfp_conv2d_desc* d, const float* x, const void* 
             case kDw3x3: rc = launch_dw3x3(*d, p, x_nhwc, reinterpret_cast<const float*>(wprep), bias, post, y_nhwc, st); break;
             case kPointwise: rc = launch_pointwise(*d, p, x_nhwc, wprep, bias, post, y_nhwc, st); break;
             case kDenseMfma: rc = launch_dense_mfma(*d, p, x_nhwc, wprep, bias, post, y_nhwc, ws + l.operand, st); break;
+            case kDenseDil: rc = launch_dense_dil(*d, p, x_nhwc, wprep, bias, post, y_nhwc, ws + l.operand, st); break;
             case kStemMfma: rc = launch_stem_mfma(*d, p, x_nhwc, wprep, bias, post, y_nhwc, ws + l.operand, st); break;
             case kStemSmall: rc = launch_stem_small(*d, p, x_nhwc, wprep, bias, post, y_nhwc, st); break;
             default: rc = launch_direct(*d, p, x_nhwc, reinterpret_cast<const float*>(wprep), bias, post, y_nhwc, st); break;

@@ -30,10 +30,10 @@
 #include "slfp_layerout_lut.hpp"
 #include "slfp_host.hpp"
 #include "slfp_epilogue.hpp"
+#include "conv_dense_core.hpp"
 
 namespace slfp {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 
 constexpr int kDnThreads = 512;
@@ -68,22 +68,6 @@ struct DenseParams {
     EncArgsCompact enc_in;   // kEncF16P table of (Ka, fmt_act)
     int y_ld;             // yc: bytes from one pixel's codes to the next (O: a dense tensor; more: a channel slice of a wider one)
 };
-
-__device__ __forceinline__ uint32_t dn_x_off(int row, int chunk16) {
-    // 128-byte rows; a fragment read touches 16 rows base .. base+15 for ANY base (taps shift it).
-    // ds_read_b128 is served in lane groups {0-3,12-15,20-27}, ... = 8 lanes of an even lane-quarter
-    // (rows +0..3, +12..15) and 8 of the next odd one (rows +4..11): bit 0 of the chunk (= parity of
-    // the lane-quarter) is left alone so the two halves of a group never meet; bits 1-2 are rotated
-    // by (row >> 1) & 3, which takes 4 distinct values on each half's 4 same-parity rows; (row & 1)
-    // picks the 128-byte half of the 256-byte bank line.  16 distinct slots per group (profiles/
-    // r01f_vgg16 measured 18 % conflict cycles with the plain (row >> 1) & 7 rotation).
-    return (uint32_t)row * 128u + (uint32_t)((chunk16 ^ (((row >> 1) & 3) << 1)) << 4);
-}
-
-__device__ __forceinline__ void glds16(const void* g, void* l) {  // 64 lanes x 16 B -> 1 KiB of LDS at (wave-uniform) l
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
 
 // Pre-pass: x (float32 NHWC) -> xe = fp16(16 * QA(x / Ka)), NHWC with C padded to a multiple of 64 (whole chunks)
 // and, inside every 32-channel group, 16-byte chunk j = channels {4j..4j+3, 16+4j..16+4j+3}: exactly
@@ -897,6 +881,21 @@ size_t dense_mfma_workspace_bytes(const slfp_conv2d_desc& d, int passes) {
     return 256 + (size_t)dense_planes(d, passes) * dense_plane_bytes(d);
 }
 
+// The pre-pass of both dense families on a float32 input: workspace = [zero page][xe][its residual plane when lo_plane].
+void launch_dense_encode(const slfp_conv2d_desc& d, int fmt_act, const float* x, void* workspace, bool lo_plane, hipStream_t stream) {
+    unsigned char* zero_page = reinterpret_cast<unsigned char*>(workspace);
+    _Float16* xe = reinterpret_cast<_Float16*>(zero_page + 256);
+    _Float16* xlo = lo_plane ? reinterpret_cast<_Float16*>(zero_page + 256 + dense_plane_bytes(d)) : nullptr;
+    const int cp = (int)dense_cp(d);
+    const int64_t n_chunks16 = d.n * d.h * d.w * (cp / 8);
+    const ScaleDiv sd = make_scale_div(d.ka, 4);
+    const unsigned egrid = (unsigned)ceil_div(n_chunks16, 256);
+    if (fmt_act == kFmtAct8)
+        hipLaunchKernelGGL((k_dense_encode<kFmtAct8>), dim3(egrid), dim3(256), 0, stream, x, xe, xlo, zero_page, n_chunks16, (int)d.c_in, cp, sd);
+    else
+        hipLaunchKernelGGL((k_dense_encode<kFmtSfp7>), dim3(egrid), dim3(256), 0, stream, x, xe, xlo, zero_page, n_chunks16, (int)d.c_in, cp, sd);
+}
+
 // ---- the weights-resident persistent form (k_dense3x3_res)
 static bool dense_res_applicable(const slfp_conv2d_desc& d, int planes, int cp) {
     return planes == 1 && cp == 64 && d.kh == 3 && d.kw == 3 && d.stride_h == 1 && d.pad_h <= 1 && d.pad_w <= 1 &&
@@ -1068,7 +1067,6 @@ int launch_dense_mfma_io(const slfp_conv2d_desc& d, const ConvPlan& plan, const 
     _Float16* xlo = planes == 2 ? reinterpret_cast<_Float16*>(zero_page + 256 + dense_plane_bytes(d)) : nullptr;
     const int cp = (int)dense_cp(d);
     const int64_t n_chunks16 = d.n * d.h * d.w * (cp / 8);
-    const ScaleDiv sd = make_scale_div(d.ka, 4);
     const unsigned egrid = (unsigned)ceil_div(n_chunks16, 256);
     if (tx) {
         // no pre-pass
@@ -1078,10 +1076,9 @@ int launch_dense_mfma_io(const slfp_conv2d_desc& d, const ConvPlan& plan, const 
             hipLaunchKernelGGL((k_dense_decode<kFmtAct8>), dim3(egrid), dim3(256), 0, stream, xc, xe, xlo, zero_page, n_chunks16, (int)d.c_in, cp);
         else
             hipLaunchKernelGGL((k_dense_decode<kFmtSfp7>), dim3(egrid), dim3(256), 0, stream, xc, xe, xlo, zero_page, n_chunks16, (int)d.c_in, cp);
-    } else if (plan.fmt_act == kFmtAct8)
-        hipLaunchKernelGGL((k_dense_encode<kFmtAct8>), dim3(egrid), dim3(256), 0, stream, x, xe, xlo, zero_page, n_chunks16, (int)d.c_in, cp, sd);
-    else
-        hipLaunchKernelGGL((k_dense_encode<kFmtSfp7>), dim3(egrid), dim3(256), 0, stream, x, xe, xlo, zero_page, n_chunks16, (int)d.c_in, cp, sd);
+    } else {
+        launch_dense_encode(d, plan.fmt_act, x, workspace, xlo != nullptr, stream);
+    }
     int rc = check_launch("slfp dense encode kernel");
     if (rc != SLFP_OK) return rc;
     // ---- pass 2: implicit GEMM

@@ -81,7 +81,7 @@ inline const EncArgs* act_table(float ka, int fmt_act, int rep) {
 }
 
 // Kernel families (slfp_conv2d_kernel_name reports them).
-enum KernelFamily { kDw3x3 = 0, kPointwise = 1, kDirect = 2, kDenseMfma = 3, kStemMfma = 4, kStemSmall = 5 };
+enum KernelFamily { kDw3x3 = 0, kPointwise = 1, kDirect = 2, kDenseMfma = 3, kStemMfma = 4, kStemSmall = 5, kDenseDil = 6 };
 
 struct ConvPlan {
     KernelFamily family;
@@ -269,6 +269,16 @@ int launch_dense_mfma_io(const slfp_conv2d_desc& d, const ConvPlan& p, const voi
 const char* dense_variant_name(const slfp_conv2d_desc& d, const ConvPlan& p, bool x_codes);
 // is there a table-epilogue instance (CodeIo::lut) of the kernel launch_dense_mfma_io picks for this layer?  Host only.
 bool dense_lut_applicable(const slfp_conv2d_desc& d, const ConvPlan& p, bool x_codes);
+// the pre-pass of both dense families on a float32 input: zero page + fp16 copy (+ its residual plane) into `workspace`
+void launch_dense_encode(const slfp_conv2d_desc& d, int fmt_act, const float* x, void* workspace, bool lo_plane, hipStream_t stream);
+// dilated dense k x k, groups 1, stride 1, as dil_h * dil_w undilated phases on MFMA (conv_dense_dil.hip; opt-in:
+// SLFP_DESC_DILATED_MFMA).  The dense family's blob and workspace (dense_mfma_workspace_bytes(d, 1)); float32 in, float32 out.
+bool dense_dil_applicable(const slfp_conv2d_desc& d, int passes);
+int launch_dense_dil(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const void* wblob, const float* bias,
+                     const PostOp& post, float* y, void* workspace, hipStream_t stream);
+// what launch_dense_dil decides for this layer, printed from the selection it consumes (slfp_debug_dense_dil_variant; host
+// only).  "none" outside the family; valid until the next call on the same thread.
+const char* dense_dil_variant_name(const slfp_conv2d_desc& d, const ConvPlan& p);
 // codes: `w_oihw` points at 1-byte extended weight codes (slfp_encode_f32 | SLFP_FMT_EXT) instead of float32 weights
 int launch_prepare_weights(const slfp_conv2d_desc& d, const ConvPlan& p, const float* w_oihw, void* wprep,
                            float* weight_q_oihw, hipStream_t stream, bool codes = false);

@@ -65,6 +65,18 @@ extern "C" {
  * SLFP_PW8_PG=1|2 forces PG). */
 #define SLFP_MFMA_FP8 8
 
+/* slfp_conv2d_desc.reserved: option bits; every bit not named here must be 0 (SLFP_ERR_BAD_ARG otherwise).
+ * SLFP_DESC_DILATED_MFMA: dilated dense layers on the matrix cores (csrc/conv_dense_dil.hip) instead of the float32 direct kernel.
+ * Taken for groups 1, stride 1, dil_h / dil_w >= 1 and not both 1, kh * kw > 1, C_in a multiple of 4 and >= 16, C_out a multiple
+ * of 4, qbits 8 in the single-pass mode (SLFP_MFMA_DEFAULT / SLFP_MFMA_F16X1; the 1e-3 bar) or qbits 7 (exact), a kernel and
+ * padding for which a tiling fits in LDS, H * W * (C_in + 63) < 2^30; float32 in, float32 out through slfp_conv2d_fwd /
+ * slfp_conv2d_fwd_post (both layouts; NCHW is transposed by the entry point as for every family).  slfp_conv2d_kernel_name then
+ * says "dense_dil_mfma_f16x1" / "dense_dil_mfma_f16_exact", and the weight blob and workspace are those of the same layer at
+ * dilation 1 ("dense_mfma_*").  On every other descriptor the bit changes nothing: a dilated layer the kernel does not take
+ * (stride 2, groups, SLFP_MFMA_F16X3, C_in < 16) stays "direct_nhwc", the code queries keep answering 0 for dilated layers and the
+ * backward stays "composite". */
+#define SLFP_DESC_DILATED_MFMA 1
+
 int slfp_version(void);
 /* Re-reads the SLFP_* experiment switches from the environment (profiles/variants.py); not for production use. */
 void slfp_debug_reload_switches(void);
@@ -105,7 +117,7 @@ typedef struct slfp_conv2d_desc {
     int32_t qbits;            /* 8 = SLFP<3,4>, 7 = SFP<3,3>  (32 is a host-side passthrough) */
     float ka, kw_scale;       /* float32(Ka), float32(Kw): the module's calibration scales    */
     int32_t mfma_passes;      /* SLFP_MFMA_*                                                   */
-    int32_t reserved;
+    int32_t reserved;         /* SLFP_DESC_* option bits; 0: the defaults                      */
 } slfp_conv2d_desc;
 
 /* Validates the geometry; writes the output spatial size. */
@@ -126,6 +138,11 @@ const char* slfp_debug_dw3x3_variant(const slfp_conv2d_desc* d, int has_post);
  * is printed from the selection the launch consumes.  Host only: no device is touched.  The pointer stays valid
  * until the next call on the same thread. */
 const char* slfp_debug_dense_variant(const slfp_conv2d_desc* d, int x_codes);
+/* Which dilated dense kernel instance (csrc/conv_dense_dil.hip) a forward of this descriptor launches; "none" when the descriptor
+ * is not of the dense_dil_mfma_* family (SLFP_DESC_DILATED_MFMA).  "<frag>/<wm><wn><mt>/ns<N>": the 16 pixels of an MFMA fragment
+ * in phase-grid coordinates ("16x1" or "8x2"), the tiling, halo slots per wave, e.g. "8x2/421/ns3".  Printed from the selection
+ * the launch consumes.  Host only; the pointer stays valid until the next call on the same thread. */
+const char* slfp_debug_dense_dil_variant(const slfp_conv2d_desc* d);
 /* Which pointwise (1x1) kernel instance (csrc/conv_pw.hip, csrc/conv_pw_codes.hip) the matching forward entry point launches for
  * this descriptor under the switches read at load; "none" outside the pw_mfma_* family or where that entry point refuses the
  * call.  io (NULL: float32 on both sides) says whether codes come in and go out and describes the reader of output codes; has_res:
