@@ -35,7 +35,10 @@ Linear_Q layers through one slfp_conv2d_bwd call each (float32 accumulation, det
 `module._last_bwd_kernel` names what ran) and keeps every other layer on the composite;
 "hip_all" is "hip" plus SLFP_BWD_DENSE: every other groups-1, dilation-1 layer (dense k x k,
 strided 1x1, the C_in = 3 stems) runs on the implicit-GEMM family `dense_bwd_mfma_f32`, and
-only grouped non-depthwise and dilated layers stay on the composite.
+only grouped non-depthwise and dilated layers stay on the composite (their FORWARD leaves the
+float32 direct kernel for a matrix-core one under `options.grouped` / `options.dilated` = "mfma";
+grouped layers outside that kernel's envelope -- group widths above 64, dilated or stride-3
+grouped layers, SLFP_MFMA_F16X3 -- stay on the direct kernel; include/slfp.h).
 """
 import contextlib
 import ctypes
@@ -78,6 +81,9 @@ class _Options:
                                      # says yes -- the same bits.  A Linear_Q linked by fusion.link_head runs "fc" either way
     dilated = "direct"               # dilated dense Conv2d_Q layers: "direct" (the float32 direct kernel); "mfma": the phase-tiled
                                      # matrix-core kernel (SLFP_DESC_DILATED_MFMA) wherever the library takes the layer
+    grouped = "direct"               # grouped (1 < groups, not depthwise 3x3) Conv2d_Q layers: "direct" (the float32 direct kernel);
+                                     # "mfma": the block-diagonal matrix-core kernel (SLFP_DESC_GROUPED_MFMA) wherever the library
+                                     # takes the layer; a NaN activation then marks its whole group SET (include/slfp.h)
 
     def __setattr__(self, name, value):
         if name == "backward" and value not in _BACKWARDS:
@@ -88,6 +94,8 @@ class _Options:
             raise ValueError(f"options.linear_kernel must be one of {_LINEAR_KERNELS}, got {value!r}")
         if name == "dilated" and value not in _DILATEDS:
             raise ValueError(f"options.dilated must be one of {_DILATEDS}, got {value!r}")
+        if name == "grouped" and value not in _GROUPEDS:
+            raise ValueError(f"options.grouped must be one of {_GROUPEDS}, got {value!r}")
         super().__setattr__(name, value)
 
 
@@ -95,6 +103,7 @@ _BACKWARDS = ("composite", "hip", "hip_all")
 _BACKWARD_GEMMS = ("f32", "bf16x3", "bf16x3_all")
 _LINEAR_KERNELS = ("pointwise", "fc")
 _DILATEDS = ("direct", "mfma")
+_GROUPEDS = ("direct", "mfma")
 options = _Options()
 
 
@@ -154,7 +163,8 @@ def _conv_desc(mod, shape, nhwc_in=True, nhwc_out=True, fp8=False):
                          y_layout=_lib.LAYOUT_NHWC if nhwc_out else _lib.LAYOUT_NCHW,
                          qbits=mod.q_bit, ka=_f32(_scalar_scale(mod.Ka, "Ka")), kw_scale=_f32(_scalar_scale(mod.Kw, "Kw")),
                          mfma_passes=_lib.MFMA_FP8 if fp8 else options.mfma_passes,
-                         reserved=_lib.DESC_DILATED_MFMA if options.dilated == "mfma" else 0)
+                         reserved=(_lib.DESC_DILATED_MFMA if options.dilated == "mfma" else 0)
+                         | (_lib.DESC_GROUPED_MFMA if options.grouped == "mfma" else 0))
 
 
 def _conv_io(x_codes, out):
@@ -316,7 +326,7 @@ def _plan(mod, x, weight, nhwc_in, nhwc_out, codes=None):
     # own, so the prepared-weight cache never mixes the two blobs of one weight); every other form keeps the module's usual one
     fp8 = bool(getattr(mod, "_fp8", False) and codes is not None and codes[0] in _FP8_KINDS and codes[1])
     key = (codes, shape, nhwc_in, nhwc_out, _scale_key(mod.Ka, "Ka"), _scale_key(mod.Kw, "Kw"), options.mfma_passes, fp8,
-           mod.stride, mod.padding, mod.dilation, weight.shape, options.dilated)
+           mod.stride, mod.padding, mod.dilation, weight.shape, options.dilated, options.grouped)
     plan = mod._plans.get(key) if options.plan_cache else None
     if plan is None:
         L = _lib.load()

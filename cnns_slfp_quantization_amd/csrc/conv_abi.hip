@@ -28,7 +28,7 @@ static int make_plan_core(const slfp_conv2d_desc* d, ConvPlan* plan) {
     if (!(d->ka > 0.f) || !(d->kw_scale > 0.f)) return fail(SLFP_ERR_BAD_ARG, "conv2d: Ka and Kw must be > 0");
     if (!scale_div_ok(d->ka) || !scale_div_ok(d->kw_scale))
         return fail(SLFP_ERR_UNSUPPORTED, "conv2d: Ka and Kw must be within [1e-30, 1e30]");
-    if (d->reserved & ~SLFP_DESC_DILATED_MFMA) return fail(SLFP_ERR_BAD_ARG, "conv2d: unknown bits in `reserved` (SLFP_DESC_*)");
+    if (d->reserved & ~(SLFP_DESC_DILATED_MFMA | SLFP_DESC_GROUPED_MFMA)) return fail(SLFP_ERR_BAD_ARG, "conv2d: unknown bits in `reserved` (SLFP_DESC_*)");
     if (d->mfma_passes == SLFP_MFMA_FP8)   // make_plan(fp8_ok) plans such a descriptor in the default mode first
         return fail(SLFP_ERR_UNSUPPORTED, "conv2d: SLFP_MFMA_FP8 (E4M3 operands) serves weight preparation and slfp_conv2d_fwd_codes[_slice] only");
     if (d->mfma_passes != SLFP_MFMA_DEFAULT && d->mfma_passes != SLFP_MFMA_F16X1 && d->mfma_passes != SLFP_MFMA_F16X3)
@@ -87,6 +87,13 @@ static int make_plan_core(const slfp_conv2d_desc* d, ConvPlan* plan) {
         plan->k_pad = ceil_div(d->c_in, 64) * 64;
         plan->n_pad = ceil_div(d->c_out, 16) * 16;
         plan->wprep_bytes = round256((size_t)d->kh * d->kw * plan->k_pad * plan->n_pad * sizeof(_Float16));
+    } else if ((d->reserved & SLFP_DESC_GROUPED_MFMA) && grouped_applicable(*d, plan->passes, plan->fmt_act)) {
+        plan->family = kGroupedMfma;   // opt-in; block-diagonal blob [set][n_tile][k_step][64][8], no workspace
+        GroupedSel gsel;
+        grouped_select(*d, plan->passes, plan->fmt_act, &gsel);
+        plan->k_pad = (int64_t)gsel.ksteps * 32;
+        plan->n_pad = (int64_t)gsel.n_sets * gsel.ow;
+        plan->wprep_bytes = round256((size_t)gsel.n_sets * gsel.nt * gsel.ksteps * 64 * 8 * sizeof(_Float16));
     } else {
         plan->family = kDirect;
         plan->wprep_bytes = round256((size_t)d->kh * d->kw * cg * d->c_out * sizeof(float));
@@ -212,6 +219,14 @@ __global__ __launch_bounds__(256) void k_prepare(const float* __restrict__ w, vo
         const int r = kw * Cg + ci, ks = kh * KS + (r >> 5);
         const size_t at = ((((size_t)ks * plane + (o >> 4)) * 64) + (size_t)(((r & 31) >> 3) * 16 + (o & 15))) * 8 + (r & 7);
         reinterpret_cast<_Float16*>(prep)[at] = (_Float16)(16.0f * q);
+    } else if (family == kGroupedMfma) {
+        // block-diagonal A fragments per group set (`plane` = groups per set gs, `ldo` = C_out / groups): conv_grouped.hip.
+        // k = tap * span + (channel inside the set), 8 consecutive k per lane; foreign groups' entries stay the memset's zeros
+        const int gs = (int)plane, Og = ldo, g = o / Og, set = g / gs;
+        const int ol = (g - set * gs) * Og + (o - g * Og), nt = gs * Og / 16;
+        const int k = (kh * KW + kw) * (gs * Cg) + (g - set * gs) * Cg + ci;
+        const size_t at = ((((size_t)set * nt + (ol >> 4)) * KS + (k >> 5)) * 64 + (size_t)(((k & 31) >> 3) * 16 + (ol & 15))) * 8 + (k & 7);
+        reinterpret_cast<_Float16*>(prep)[at] = (_Float16)(16.0f * q);
     } else if (family == kDenseMfma) {
         // tap-major copy of the pointwise fragment order (single fp16 plane): conv_dense.hip
         const int nt = o >> 4, row = o & 15, ks = ci >> 5, kk = ci & 31;
@@ -241,15 +256,21 @@ int launch_prepare_weights(const slfp_conv2d_desc& d, const ConvPlan& p, const f
     const int Cg = (int)(d.c_in / d.groups);
     const int64_t total = d.c_out * Cg * d.kh * d.kw;
     const bool dense_blob = p.family == kDenseMfma || p.family == kDenseDil;   // conv_dense_dil.hip reads conv_dense.hip's blob
-    if (p.family == kPointwise || dense_blob || p.family == kStemMfma || p.family == kStemSmall || p.repad) {
+    if (p.family == kPointwise || dense_blob || p.family == kStemMfma || p.family == kStemSmall || p.family == kGroupedMfma || p.repad) {
         if (hipMemsetAsync(wprep, 0, p.wprep_bytes, stream) != hipSuccess) return check_launch("hipMemsetAsync(wprep)");
     }
-    const int64_t plane = p.family == kStemMfma ? p.n_pad : p.k_pad * p.n_pad;
+    int64_t plane = p.family == kStemMfma ? p.n_pad : p.k_pad * p.n_pad;
     const int KS = p.family == kStemMfma ? (int)p.k_pad : (int)(p.k_pad / 32);
     const unsigned grid = (unsigned)ceil_div(total, 256);
     const ScaleDiv sd = make_scale_div(d.kw_scale);
     // depthwise: row pitch of the [9][C] table (padded channel count); dense MFMA: 1 = also write the residual plane
-    const int ldo = dense_blob ? (p.passes == 3 ? 1 : 0) : (int)p.cpo;
+    int ldo = dense_blob ? (p.passes == 3 ? 1 : 0) : (int)p.cpo;
+    if (p.family == kGroupedMfma) {   // groups per set, channels per group (k_prepare's kGroupedMfma branch)
+        GroupedSel gsel;
+        if (!grouped_select(d, p.passes, p.fmt_act, &gsel)) return fail(SLFP_ERR_UNSUPPORTED, "grouped MFMA conv: layer outside the family");
+        plane = gsel.gs;
+        ldo = (int)(d.c_out / d.groups);
+    }
 #define SLFP_PREP(FF, CC) hipLaunchKernelGGL((k_prepare<FF, CC>), dim3(grid), dim3(256), 0, stream, w_oihw, wprep, weight_q_oihw, total, \
                                              (int)d.c_out, Cg, (int)d.kh, (int)d.kw, sd, dense_blob ? (int)kDenseMfma : (int)p.family, KS, plane, ldo)
     if (p.fmt_w == kFmtW8) { if (codes) SLFP_PREP(kFmtW8, true); else SLFP_PREP(kFmtW8, false); }
@@ -270,6 +291,7 @@ static const char* family_name(const ConvPlan& p, const slfp_conv2d_desc& d) {
         case kPointwise: return p.fmt_act == kFmtSfp7 ? "pw_mfma_f16_exact" : (p.passes == 3 ? "pw_mfma_f16x3" : "pw_mfma_f16x1");
         case kDenseMfma: return p.fmt_act == kFmtSfp7 ? "dense_mfma_f16_exact" : (p.passes == 3 ? "dense_mfma_f16x3" : "dense_mfma_f16x1");
         case kDenseDil: return p.fmt_act == kFmtSfp7 ? "dense_dil_mfma_f16_exact" : "dense_dil_mfma_f16x1";
+        case kGroupedMfma: return p.fmt_act == kFmtSfp7 ? "grouped_mfma_f16_exact" : "grouped_mfma_f16x1";
         case kStemMfma: return p.fmt_act == kFmtSfp7 ? "stem_mfma_f16_exact" : "stem_mfma_f16x1";
         case kStemSmall: return p.fmt_act == kFmtSfp7 ? "stem_small_mfma_f16_exact" : "stem_small_mfma_f16x1";
         default: return "direct_nhwc";
@@ -328,6 +350,12 @@ const char* slfp_debug_dense_dil_variant(const slfp_conv2d_desc* d) {
     ConvPlan p;
     if (make_plan(d, &p) != SLFP_OK) return "none";
     return dense_dil_variant_name(*d, p);
+}
+
+const char* slfp_debug_grouped_variant(const slfp_conv2d_desc* d) {
+    ConvPlan p;
+    if (make_plan(d, &p) != SLFP_OK) return "none";
+    return grouped_variant_name(*d, p);
 }
 
 const char* slfp_debug_pw_variant(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_res, int has_res_codes, int64_t y_ld) {
@@ -812,6 +840,7 @@ int slfp_conv2d_fwd_post(const slfp_conv2d_desc* d, const float* x, const void* 
             case kPointwise: rc = launch_pointwise(*d, p, x_nhwc, wprep, bias, post, y_nhwc, st); break;
             case kDenseMfma: rc = launch_dense_mfma(*d, p, x_nhwc, wprep, bias, post, y_nhwc, ws + l.operand, st); break;
             case kDenseDil: rc = launch_dense_dil(*d, p, x_nhwc, wprep, bias, post, y_nhwc, ws + l.operand, st); break;
+            case kGroupedMfma: rc = launch_grouped(*d, p, x_nhwc, wprep, bias, post, y_nhwc, st); break;
             case kStemMfma: rc = launch_stem_mfma(*d, p, x_nhwc, wprep, bias, post, y_nhwc, ws + l.operand, st); break;
             case kStemSmall: rc = launch_stem_small(*d, p, x_nhwc, wprep, bias, post, y_nhwc, st); break;
             default: rc = launch_direct(*d, p, x_nhwc, reinterpret_cast<const float*>(wprep), bias, post, y_nhwc, st); break;

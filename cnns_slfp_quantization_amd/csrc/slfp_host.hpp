@@ -81,7 +81,7 @@ inline const EncArgs* act_table(float ka, int fmt_act, int rep) {
 }
 
 // Kernel families (slfp_conv2d_kernel_name reports them).
-enum KernelFamily { kDw3x3 = 0, kPointwise = 1, kDirect = 2, kDenseMfma = 3, kStemMfma = 4, kStemSmall = 5, kDenseDil = 6 };
+enum KernelFamily { kDw3x3 = 0, kPointwise = 1, kDirect = 2, kDenseMfma = 3, kStemMfma = 4, kStemSmall = 5, kDenseDil = 6, kGroupedMfma = 7 };
 
 struct ConvPlan {
     KernelFamily family;
@@ -279,6 +279,24 @@ int launch_dense_dil(const slfp_conv2d_desc& d, const ConvPlan& p, const float* 
 // what launch_dense_dil decides for this layer, printed from the selection it consumes (slfp_debug_dense_dil_variant; host
 // only).  "none" outside the family; valid until the next call on the same thread.
 const char* dense_dil_variant_name(const slfp_conv2d_desc& d, const ConvPlan& p);
+// grouped k x k (1 < groups, not the depthwise 3x3) as a block-diagonal GEMM over group sets on MFMA (conv_grouped.hip; opt-in:
+// SLFP_DESC_GROUPED_MFMA).  wblob = [set][n_tile][k_step][64][8] fp16 with k = (kh*KW + kw)*span + c; no workspace; float32 in,
+// float32 out.  grouped_select is the single place that decides what the family takes and how: the plan, the blob's shape,
+// the launch and the debug name (slfp_debug_grouped_variant; "none" outside the family; valid until the next call on the same
+// thread) all read it.  Host only.
+struct GroupedSel {
+    int gs, span, ow;        // groups per set; input / output channels of a set
+    int nt, ksteps, taps;    // 16-channel tiles per set; 32-deep k-steps of K = taps * span
+    int n_sets, sw;          // sets; adjacent sets per workgroup
+    int ih, iw, pitch;       // halo tile: rows, pixels per row, bytes per pixel
+    uint32_t off_koff, off_w, off_x;
+    size_t lds;
+};
+bool grouped_select(const slfp_conv2d_desc& d, int passes, int fmt_act, GroupedSel* s);
+bool grouped_applicable(const slfp_conv2d_desc& d, int passes, int fmt_act);
+int launch_grouped(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const void* wblob, const float* bias,
+                   const PostOp& post, float* y, hipStream_t stream);
+const char* grouped_variant_name(const slfp_conv2d_desc& d, const ConvPlan& p);
 // codes: `w_oihw` points at 1-byte extended weight codes (slfp_encode_f32 | SLFP_FMT_EXT) instead of float32 weights
 int launch_prepare_weights(const slfp_conv2d_desc& d, const ConvPlan& p, const float* w_oihw, void* wprep,
                            float* weight_q_oihw, hipStream_t stream, bool codes = false);

@@ -73,9 +73,23 @@ extern "C" {
  * slfp_conv2d_fwd_post (both layouts; NCHW is transposed by the entry point as for every family).  slfp_conv2d_kernel_name then
  * says "dense_dil_mfma_f16x1" / "dense_dil_mfma_f16_exact", and the weight blob and workspace are those of the same layer at
  * dilation 1 ("dense_mfma_*").  On every other descriptor the bit changes nothing: a dilated layer the kernel does not take
- * (stride 2, groups, SLFP_MFMA_F16X3, C_in < 16) stays "direct_nhwc", the code queries keep answering 0 for dilated layers and the
- * backward stays "composite". */
+ * (stride 2, a dilated grouped layer, SLFP_MFMA_F16X3, C_in < 16) stays "direct_nhwc", the code queries keep answering 0 for dilated
+ * layers and the backward stays "composite".
+ * SLFP_DESC_GROUPED_MFMA: grouped layers (1 < groups, other than the depthwise 3x3 of "dw3x3_nhwc") on the matrix cores
+ * (csrc/conv_grouped.hip) instead of the float32 direct kernel, as a block-diagonal GEMM over GROUP SETS: with Cg = C_in / groups and
+ * Og = C_out / groups, a set is gs = 16 / gcd(Og, 16) consecutive groups.  Taken for dilation 1, stride_h == stride_w in {1, 2},
+ * kh, kw in 1..5, pad_h < kh, pad_w < kw, Cg and Og multiples of 4, a set's input span gs * Cg a multiple of 8, gs * Cg <= 64 and
+ * gs * Og <= 64, a set's weights plus one halo tile within 160 KiB of LDS, H * W * C_in < 2^30, a threshold table for Ka, qbits 8
+ * in the single-pass mode (SLFP_MFMA_DEFAULT / SLFP_MFMA_F16X1; the 1e-3 bar) or qbits 7 (exact); float32 in, float32 out through
+ * slfp_conv2d_fwd / slfp_conv2d_fwd_post (both layouts), no operand workspace.  slfp_conv2d_kernel_name then says
+ * "grouped_mfma_f16x1" / "grouped_mfma_f16_exact" and slfp_conv2d_wprep_bytes is the size of the blob [set][16-channel tile]
+ * [k-step][64][8] fp16.  NaN: the blob's off-diagonal zeros turn a NaN activation into NaN for every output channel of its group
+ * SET at the pixels whose window holds it; the direct kernel marks its own group only -- which is why the bit is an option.  On
+ * every other descriptor the bit changes nothing: group widths above 64 (AlexNet's groups 2), Cg % 4 != 0, dilation, stride 3,
+ * SLFP_MFMA_F16X3 stay "direct_nhwc", the code / residual / u8 / fp8 queries keep answering 0 or SLFP_ERR_UNSUPPORTED for grouped
+ * layers and the backward stays "composite".  Bits 2 and 4 are not assigned. */
 #define SLFP_DESC_DILATED_MFMA 1
+#define SLFP_DESC_GROUPED_MFMA 8
 
 int slfp_version(void);
 /* Re-reads the SLFP_* experiment switches from the environment (profiles/variants.py); not for production use. */
@@ -143,6 +157,12 @@ const char* slfp_debug_dense_variant(const slfp_conv2d_desc* d, int x_codes);
  * in phase-grid coordinates ("16x1" or "8x2"), the tiling, halo slots per wave, e.g. "8x2/421/ns3".  Printed from the selection
  * the launch consumes.  Host only; the pointer stays valid until the next call on the same thread. */
 const char* slfp_debug_dense_dil_variant(const slfp_conv2d_desc* d);
+/* What the grouped kernel (csrc/conv_grouped.hip) decides for a forward of this descriptor; "none" when the descriptor is not of the
+ * grouped_mfma_* family (SLFP_DESC_GROUPED_MFMA).  "gs<G>/sp<span>/nt<NT>/ks<KS>/sw<SW>/wk<WK>": groups per set, a set's input
+ * channels, its 16-channel output tiles (the k_grouped<NT> instance), 32-deep k-steps of K = kh * kw * span, adjacent sets per
+ * workgroup, workgroups that share the 8 x 16 pixel tiles of one (image, set chunk), e.g. "gs4/sp16/nt1/ks5/sw2/wk4".  Printed from
+ * the selection the launch consumes.  Host only; the pointer stays valid until the next call on the same thread. */
+const char* slfp_debug_grouped_variant(const slfp_conv2d_desc* d);
 /* Which pointwise (1x1) kernel instance (csrc/conv_pw.hip, csrc/conv_pw_codes.hip) the matching forward entry point launches for
  * this descriptor under the switches read at load; "none" outside the pw_mfma_* family or where that entry point refuses the
  * call.  io (NULL: float32 on both sides) says whether codes come in and go out and describes the reader of output codes; has_res:
