@@ -17,6 +17,7 @@ BWD_DENSE = 1  # slfp_conv2d_bwd_*_ex flags: SLFP_BWD_DENSE
 MFMA_DEFAULT, MFMA_F16X1, MFMA_F16X3 = 0, 1, 3
 DESC_DILATED_MFMA = 1  # slfp_conv2d_desc.reserved: SLFP_DESC_DILATED_MFMA
 DESC_GROUPED_MFMA = 8  # slfp_conv2d_desc.reserved: SLFP_DESC_GROUPED_MFMA
+DESC_DW_KXK = 16  # slfp_conv2d_desc.reserved: SLFP_DESC_DW_KXK
 MFMA_FP8 = 8   # SLFP_MFMA_FP8: q_bit 7, 1x1, code input, E4M3 operands (include/slfp.h)
 OPT_SGD, OPT_DSGD, OPT_SSGD = 0, 1, 2
 LAYEROUT_LUT_BYTES = 4928  # SLFP_LAYEROUT_LUT_BYTES
@@ -61,7 +62,7 @@ SYMBOLS = (
     "slfp_conv2d_bwd_bf16_supported", "slfp_conv2d_bwd_bf16_workspace_bytes", "slfp_conv2d_bwd_bf16", "slfp_debug_bwd_bf16_instance",
     "slfp_conv2d_bwd_dense_bf16_supported", "slfp_conv2d_bwd_dense_bf16_workspace_bytes", "slfp_conv2d_bwd_dense_bf16",
     "slfp_debug_bwd_dense_bf16_instance",
-    "slfp_debug_dense_dil_variant", "slfp_debug_grouped_variant",
+    "slfp_debug_dense_dil_variant", "slfp_debug_grouped_variant", "slfp_debug_dwk_variant",
 )
 
 
@@ -134,6 +135,7 @@ def load():
         "slfp_debug_dense_variant": (ctypes.c_char_p, [dp, ci]),
         "slfp_debug_dense_dil_variant": (ctypes.c_char_p, [dp]),
         "slfp_debug_grouped_variant": (ctypes.c_char_p, [dp]),
+        "slfp_debug_dwk_variant": (ctypes.c_char_p, [dp]),
         "slfp_debug_pw_variant": (ctypes.c_char_p, [dp, ctypes.POINTER(ConvIo), ci, ci, i64]),
         "slfp_conv2d_wprep_bytes": (sz, [dp]),
         "slfp_conv2d_prepare_weights": (ci, [dp, vp, vp, vp, vp]),

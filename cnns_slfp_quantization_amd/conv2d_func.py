@@ -39,6 +39,8 @@ only grouped non-depthwise and dilated layers stay on the composite (their FORWA
 float32 direct kernel for a matrix-core one under `options.grouped` / `options.dilated` = "mfma";
 grouped layers outside that kernel's envelope -- group widths above 64, dilated or stride-3
 grouped layers, SLFP_MFMA_F16X3 -- stay on the direct kernel; include/slfp.h).
+`options.depthwise` = "kxk" moves the forward of depthwise 5x5 / 7x7 layers (stride 1 / 2, C a multiple of 4) from the direct
+kernel to `dwk_nhwc` (SLFP_DESC_DW_KXK), bit-equal to it; their backward stays on the composite.
 """
 import contextlib
 import ctypes
@@ -84,6 +86,8 @@ class _Options:
     grouped = "direct"               # grouped (1 < groups, not depthwise 3x3) Conv2d_Q layers: "direct" (the float32 direct kernel);
                                      # "mfma": the block-diagonal matrix-core kernel (SLFP_DESC_GROUPED_MFMA) wherever the library
                                      # takes the layer; a NaN activation then marks its whole group SET (include/slfp.h)
+    depthwise = "direct"             # depthwise 5x5 / 7x7 Conv2d_Q layers: "direct" (the float32 direct kernel); "kxk": the
+                                     # run-and-row-window kernel (SLFP_DESC_DW_KXK) wherever the library takes the layer -- the same bits
 
     def __setattr__(self, name, value):
         if name == "backward" and value not in _BACKWARDS:
@@ -96,6 +100,8 @@ class _Options:
             raise ValueError(f"options.dilated must be one of {_DILATEDS}, got {value!r}")
         if name == "grouped" and value not in _GROUPEDS:
             raise ValueError(f"options.grouped must be one of {_GROUPEDS}, got {value!r}")
+        if name == "depthwise" and value not in _DEPTHWISES:
+            raise ValueError(f"options.depthwise must be one of {_DEPTHWISES}, got {value!r}")
         super().__setattr__(name, value)
 
 
@@ -104,6 +110,7 @@ _BACKWARD_GEMMS = ("f32", "bf16x3", "bf16x3_all")
 _LINEAR_KERNELS = ("pointwise", "fc")
 _DILATEDS = ("direct", "mfma")
 _GROUPEDS = ("direct", "mfma")
+_DEPTHWISES = ("direct", "kxk")
 options = _Options()
 
 
@@ -164,7 +171,8 @@ def _conv_desc(mod, shape, nhwc_in=True, nhwc_out=True, fp8=False):
                          qbits=mod.q_bit, ka=_f32(_scalar_scale(mod.Ka, "Ka")), kw_scale=_f32(_scalar_scale(mod.Kw, "Kw")),
                          mfma_passes=_lib.MFMA_FP8 if fp8 else options.mfma_passes,
                          reserved=(_lib.DESC_DILATED_MFMA if options.dilated == "mfma" else 0)
-                         | (_lib.DESC_GROUPED_MFMA if options.grouped == "mfma" else 0))
+                         | (_lib.DESC_GROUPED_MFMA if options.grouped == "mfma" else 0)
+                         | (_lib.DESC_DW_KXK if options.depthwise == "kxk" else 0))
 
 
 def _conv_io(x_codes, out):
@@ -326,7 +334,7 @@ def _plan(mod, x, weight, nhwc_in, nhwc_out, codes=None):
     # own, so the prepared-weight cache never mixes the two blobs of one weight); every other form keeps the module's usual one
     fp8 = bool(getattr(mod, "_fp8", False) and codes is not None and codes[0] in _FP8_KINDS and codes[1])
     key = (codes, shape, nhwc_in, nhwc_out, _scale_key(mod.Ka, "Ka"), _scale_key(mod.Kw, "Kw"), options.mfma_passes, fp8,
-           mod.stride, mod.padding, mod.dilation, weight.shape, options.dilated, options.grouped)
+           mod.stride, mod.padding, mod.dilation, weight.shape, options.dilated, options.grouped, options.depthwise)
     plan = mod._plans.get(key) if options.plan_cache else None
     if plan is None:
         L = _lib.load()

@@ -28,7 +28,7 @@ static int make_plan_core(const slfp_conv2d_desc* d, ConvPlan* plan) {
     if (!(d->ka > 0.f) || !(d->kw_scale > 0.f)) return fail(SLFP_ERR_BAD_ARG, "conv2d: Ka and Kw must be > 0");
     if (!scale_div_ok(d->ka) || !scale_div_ok(d->kw_scale))
         return fail(SLFP_ERR_UNSUPPORTED, "conv2d: Ka and Kw must be within [1e-30, 1e30]");
-    if (d->reserved & ~(SLFP_DESC_DILATED_MFMA | SLFP_DESC_GROUPED_MFMA)) return fail(SLFP_ERR_BAD_ARG, "conv2d: unknown bits in `reserved` (SLFP_DESC_*)");
+    if (d->reserved & ~(SLFP_DESC_DILATED_MFMA | SLFP_DESC_GROUPED_MFMA | SLFP_DESC_DW_KXK)) return fail(SLFP_ERR_BAD_ARG, "conv2d: unknown bits in `reserved` (SLFP_DESC_*)");
     if (d->mfma_passes == SLFP_MFMA_FP8)   // make_plan(fp8_ok) plans such a descriptor in the default mode first
         return fail(SLFP_ERR_UNSUPPORTED, "conv2d: SLFP_MFMA_FP8 (E4M3 operands) serves weight preparation and slfp_conv2d_fwd_codes[_slice] only");
     if (d->mfma_passes != SLFP_MFMA_DEFAULT && d->mfma_passes != SLFP_MFMA_F16X1 && d->mfma_passes != SLFP_MFMA_F16X3)
@@ -95,7 +95,8 @@ static int make_plan_core(const slfp_conv2d_desc* d, ConvPlan* plan) {
         plan->n_pad = (int64_t)gsel.n_sets * gsel.ow;
         plan->wprep_bytes = round256((size_t)gsel.n_sets * gsel.nt * gsel.ksteps * 64 * 8 * sizeof(_Float16));
     } else {
-        plan->family = kDirect;
+        DwkSel ksel;   // opt-in; the direct family's blob [kh][kw][C], no workspace
+        plan->family = ((d->reserved & SLFP_DESC_DW_KXK) && dwk_select(*d, plan->fmt_act, &ksel)) ? kDwKxK : kDirect;
         plan->wprep_bytes = round256((size_t)d->kh * d->kw * cg * d->c_out * sizeof(float));
     }
     return SLFP_OK;
@@ -272,7 +273,7 @@ int launch_prepare_weights(const slfp_conv2d_desc& d, const ConvPlan& p, const f
         ldo = (int)(d.c_out / d.groups);
     }
 #define SLFP_PREP(FF, CC) hipLaunchKernelGGL((k_prepare<FF, CC>), dim3(grid), dim3(256), 0, stream, w_oihw, wprep, weight_q_oihw, total, \
-                                             (int)d.c_out, Cg, (int)d.kh, (int)d.kw, sd, dense_blob ? (int)kDenseMfma : (int)p.family, KS, plane, ldo)
+                                             (int)d.c_out, Cg, (int)d.kh, (int)d.kw, sd, dense_blob ? (int)kDenseMfma : (p.family == kDwKxK ? (int)kDirect : (int)p.family), KS, plane, ldo)
     if (p.fmt_w == kFmtW8) { if (codes) SLFP_PREP(kFmtW8, true); else SLFP_PREP(kFmtW8, false); }
     else { if (codes) SLFP_PREP(kFmtSfp7, true); else SLFP_PREP(kFmtSfp7, false); }
 #undef SLFP_PREP
@@ -292,6 +293,7 @@ static const char* family_name(const ConvPlan& p, const slfp_conv2d_desc& d) {
         case kDenseMfma: return p.fmt_act == kFmtSfp7 ? "dense_mfma_f16_exact" : (p.passes == 3 ? "dense_mfma_f16x3" : "dense_mfma_f16x1");
         case kDenseDil: return p.fmt_act == kFmtSfp7 ? "dense_dil_mfma_f16_exact" : "dense_dil_mfma_f16x1";
         case kGroupedMfma: return p.fmt_act == kFmtSfp7 ? "grouped_mfma_f16_exact" : "grouped_mfma_f16x1";
+        case kDwKxK: return "dwk_nhwc";
         case kStemMfma: return p.fmt_act == kFmtSfp7 ? "stem_mfma_f16_exact" : "stem_mfma_f16x1";
         case kStemSmall: return p.fmt_act == kFmtSfp7 ? "stem_small_mfma_f16_exact" : "stem_small_mfma_f16x1";
         default: return "direct_nhwc";
@@ -356,6 +358,12 @@ const char* slfp_debug_grouped_variant(const slfp_conv2d_desc* d) {
     ConvPlan p;
     if (make_plan(d, &p) != SLFP_OK) return "none";
     return grouped_variant_name(*d, p);
+}
+
+const char* slfp_debug_dwk_variant(const slfp_conv2d_desc* d) {
+    ConvPlan p;
+    if (make_plan(d, &p) != SLFP_OK) return "none";
+    return dwk_variant_name(*d, p);
 }
 
 const char* slfp_debug_pw_variant(const slfp_conv2d_desc* d, const slfp_conv2d_io* io, int has_res, int has_res_codes, int64_t y_ld) {
@@ -841,6 +849,10 @@ int slfp_conv2d_fwd_post(const slfp_conv2d_desc* d, const float* x, const void* 
             case kDenseMfma: rc = launch_dense_mfma(*d, p, x_nhwc, wprep, bias, post, y_nhwc, ws + l.operand, st); break;
             case kDenseDil: rc = launch_dense_dil(*d, p, x_nhwc, wprep, bias, post, y_nhwc, ws + l.operand, st); break;
             case kGroupedMfma: rc = launch_grouped(*d, p, x_nhwc, wprep, bias, post, y_nhwc, st); break;
+            case kDwKxK:   // a layer-output post-op is the direct kernel's; it reads the same blob
+                if (post.layerout) rc = launch_direct(*d, p, x_nhwc, reinterpret_cast<const float*>(wprep), bias, post, y_nhwc, st);
+                else rc = launch_dwk(*d, p, x_nhwc, reinterpret_cast<const float*>(wprep), bias, post, y_nhwc, st);
+                break;
             case kStemMfma: rc = launch_stem_mfma(*d, p, x_nhwc, wprep, bias, post, y_nhwc, ws + l.operand, st); break;
             case kStemSmall: rc = launch_stem_small(*d, p, x_nhwc, wprep, bias, post, y_nhwc, st); break;
             default: rc = launch_direct(*d, p, x_nhwc, reinterpret_cast<const float*>(wprep), bias, post, y_nhwc, st); break;

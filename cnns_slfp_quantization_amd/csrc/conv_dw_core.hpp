@@ -1,5 +1,6 @@
 // conv_dw_core.hpp -- what the depthwise 3x3 kernels share, written once (gfx950): conv_dw.hip (k_dw3x3), conv_dw2.hip (k_dw3x3_tile),
 // conv_dw3.hip (k_dw3x3_rows), conv_dwc.hip (k_dwc) and, through conv_dwpw_core.hpp, the depthwise stage of the two block kernels.
+// conv_dwk.hip (k_dwk, depthwise 5x5 / 7x7) reuses the descriptor, halo, BatchNorm, store and launch steps and adds dw_finish_bias.
 // The arithmetic these steps carry out is stated once, in include/slfp.h next to slfp_debug_dw3x3_instance.
 //
 // Everything is __device__ __forceinline__, constexpr or inline.  A kernel calls a step only where that leaves every .amdhsa_*
@@ -96,6 +97,22 @@ __device__ __forceinline__ f32x4 dw_finish(const f32x4 acc, const float ka, cons
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         float u = (acc[e] * ka) * kw;
+        if constexpr (POST) u = __builtin_fmaf(u, psc[e], psh[e]);
+        if (relu) u = fmaxf(u, 0.f);
+        rr[e] = u;
+    }
+    return rr;
+}
+
+// The finish of the kernels that carry a bias (conv_dwk.hip), term for term what k_direct computes: ((acc + bq) * s1) * s2 with
+// bq = (bias / s1) / s2 (0 without a bias), then post_apply1's fma and max.
+template <bool POST>
+__device__ __forceinline__ f32x4 dw_finish_bias(const f32x4 acc, const f32x4 bq, const float s1, const float s2, const f32x4 psc,
+                                                const f32x4 psh, const int relu) {
+    f32x4 rr;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float u = ((acc[e] + bq[e]) * s1) * s2;
         if constexpr (POST) u = __builtin_fmaf(u, psc[e], psh[e]);
         if (relu) u = fmaxf(u, 0.f);
         rr[e] = u;

@@ -81,7 +81,7 @@ inline const EncArgs* act_table(float ka, int fmt_act, int rep) {
 }
 
 // Kernel families (slfp_conv2d_kernel_name reports them).
-enum KernelFamily { kDw3x3 = 0, kPointwise = 1, kDirect = 2, kDenseMfma = 3, kStemMfma = 4, kStemSmall = 5, kDenseDil = 6, kGroupedMfma = 7 };
+enum KernelFamily { kDw3x3 = 0, kPointwise = 1, kDirect = 2, kDenseMfma = 3, kStemMfma = 4, kStemSmall = 5, kDenseDil = 6, kGroupedMfma = 7, kDwKxK = 8 };
 
 struct ConvPlan {
     KernelFamily family;
@@ -297,6 +297,21 @@ bool grouped_applicable(const slfp_conv2d_desc& d, int passes, int fmt_act);
 int launch_grouped(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const void* wblob, const float* bias,
                    const PostOp& post, float* y, hipStream_t stream);
 const char* grouped_variant_name(const slfp_conv2d_desc& d, const ConvPlan& p);
+// depthwise 5x5 / 7x7, stride 1 / 2, on the run-and-row-window kernel (conv_dwk.hip; opt-in: SLFP_DESC_DW_KXK).  wq = the direct
+// family's blob [kh][kw][C] float32; no workspace; float32 in, float32 out.  dwk_select is the single place that decides what the
+// family takes (from the descriptor alone: the plan asks it), the tile, the grid and the debug name (slfp_debug_dwk_variant; "none"
+// outside the family; valid until the next call on the same thread).  A layer-output post-op is not the kernel's: the forward runs
+// such a call on the direct kernel, which reads the same blob.  Host only.
+struct DwkSel {
+    int k, s;                       // kernel size (5, 7), stride (1, 2)
+    int th, tw, r, rh, nt;          // output tile, a lane's unit (columns x rows), threads: the k_dwk instance
+    int tiles_h, tiles_w, cgroups;  // tiles per image, 32-channel groups (the last one may be ragged)
+    uint32_t nblocks;
+};
+bool dwk_select(const slfp_conv2d_desc& d, int fmt_act, DwkSel* s);
+int launch_dwk(const slfp_conv2d_desc& d, const ConvPlan& p, const float* x, const float* wq, const float* bias, const PostOp& post,
+               float* y, hipStream_t stream);
+const char* dwk_variant_name(const slfp_conv2d_desc& d, const ConvPlan& p);
 // codes: `w_oihw` points at 1-byte extended weight codes (slfp_encode_f32 | SLFP_FMT_EXT) instead of float32 weights
 int launch_prepare_weights(const slfp_conv2d_desc& d, const ConvPlan& p, const float* w_oihw, void* wprep,
                            float* weight_q_oihw, hipStream_t stream, bool codes = false);

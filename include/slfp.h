@@ -87,9 +87,22 @@ extern "C" {
  * SET at the pixels whose window holds it; the direct kernel marks its own group only -- which is why the bit is an option.  On
  * every other descriptor the bit changes nothing: group widths above 64 (AlexNet's groups 2), Cg % 4 != 0, dilation, stride 3,
  * SLFP_MFMA_F16X3 stay "direct_nhwc", the code / residual / u8 / fp8 queries keep answering 0 or SLFP_ERR_UNSUPPORTED for grouped
- * layers and the backward stays "composite".  Bits 2 and 4 are not assigned. */
+ * layers and the backward stays "composite".
+ * SLFP_DESC_DW_KXK: depthwise 5x5 and 7x7 layers on the run-and-row-window kernel (csrc/conv_dwk.hip) instead of the float32 direct
+ * kernel.  Taken for groups == C_in == C_out, kh == kw in {5, 7}, dilation 1, stride_h == stride_w in {1, 2}, pad_h and pad_w
+ * independently in 0 .. (k - 1) / 2, C a multiple of 4, one image of x and of y below 2^29 elements, a threshold table for Ka, qbits 8
+ * or 7, any mfma_passes the direct kernel accepts (nothing here touches the matrix unit), optional bias and post scale / shift + ReLU;
+ * float32 in, float32 out through slfp_conv2d_fwd / slfp_conv2d_fwd_post (both layouts), no workspace.  slfp_conv2d_kernel_name then
+ * says "dwk_nhwc"; the weight blob is the direct kernel's (quantized float32 [kh][kw][C], the same bytes and the same size).  The
+ * arithmetic is the direct kernel's term for term -- one fma per tap from +0 in (kh, kw) order, ((acc + bias_q) * Ka) * Kw, the
+ * post-op -- so the outputs are bit-equal to it, NaN mask included (a NaN marks its own channel only).  A call with
+ * SLFP_POST_LAYEROUT runs the direct kernel on the same blob.  On every other descriptor the bit changes nothing: other kernel sizes,
+ * kh != kw, dilation, stride 3, larger paddings, C % 4 != 0 (no channel re-padding), 1 < groups < C stay "direct_nhwc" (3x3 stays
+ * "dw3x3_nhwc"), the code / residual / u8 / fp8 queries keep answering 0 or SLFP_ERR_UNSUPPORTED and the backward stays
+ * "composite".  Bits 2 and 4 are not assigned. */
 #define SLFP_DESC_DILATED_MFMA 1
 #define SLFP_DESC_GROUPED_MFMA 8
+#define SLFP_DESC_DW_KXK 16
 
 int slfp_version(void);
 /* Re-reads the SLFP_* experiment switches from the environment (profiles/variants.py); not for production use. */
@@ -163,6 +176,11 @@ const char* slfp_debug_dense_dil_variant(const slfp_conv2d_desc* d);
  * workgroup, workgroups that share the 8 x 16 pixel tiles of one (image, set chunk), e.g. "gs4/sp16/nt1/ks5/sw2/wk4".  Printed from
  * the selection the launch consumes.  Host only; the pointer stays valid until the next call on the same thread. */
 const char* slfp_debug_grouped_variant(const slfp_conv2d_desc* d);
+/* What the depthwise k x k kernel (csrc/conv_dwk.hip) decides for a forward of this descriptor; "none" when the descriptor is not of
+ * the "dwk_nhwc" family (SLFP_DESC_DW_KXK).  "k<K>/s<S>/<TH>x<TW>/r<R>x<RH>": kernel size, stride, the output tile of a workgroup,
+ * the run of output columns x rows one lane owns, e.g. "k7/s1/14x14/r4x4".  Printed from the selection the launch consumes.  Host
+ * only; the pointer stays valid until the next call on the same thread. */
+const char* slfp_debug_dwk_variant(const slfp_conv2d_desc* d);
 /* Which pointwise (1x1) kernel instance (csrc/conv_pw.hip, csrc/conv_pw_codes.hip) the matching forward entry point launches for
  * this descriptor under the switches read at load; "none" outside the pw_mfma_* family or where that entry point refuses the
  * call.  io (NULL: float32 on both sides) says whether codes come in and go out and describes the reader of output codes; has_res:
